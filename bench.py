@@ -1,6 +1,6 @@
 """Headline benchmark: alpha-vector backups / second at |S|=30000, |B|=1024 per GPU.
 
-    python bench.py --gpus N --steps K --warmup W          (N=1)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]   (N=1)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (N>1)
 
 A step is ONE point-based backup of SURVEY 8d's metric, of a belief block the engine has NOT seen as a block before:
@@ -11,9 +11,13 @@ dead-triple flags -- is built inside the step, as in a solve, which backs each n
 assembly) against the resident alpha set, THEN its results -- the U distinct alpha' rows, the per-belief index into them
 and the actions -- copied into page-locked host buffers (``pbvi_backup_fetch_compact``), synchronised.  That is what the
 reference's own ``backup_times`` contain: ``ValueFunction.__init__``'s ``tobytes()`` forces the device-to-host copy
-(src/mdp.py:667-669).  ``value`` = beliefs / MEDIAN step time (median of the timed calls).  Beside it:
-``value_reused_block`` (round 2's ``value``: the same block backed up again and again, its indexes kept), the mean over
-the whole timed region and the device-resident figure (results left in HBM).
+(src/mdp.py:667-669).  ``value`` = beliefs / MEDIAN step time (median of the timed calls), beside it the
+mean over the whole timed region.  A plain run sets up, warms up, times ``--steps`` steps and prints its line; with
+``--full`` it then also measures ``value_reused_block`` (round 2's ``value``: the same block backed up again and again, its
+indexes kept), the device-resident figure (results left in HBM), the PCIe-inclusive figure, the secondary configurations
+and the CPU baseline.  ``--dump-outputs DIR`` writes what the last timed step returned to its caller as ``DIR/<name>.npy``
+(``alpha``: the distinct alpha' rows in key order, ``alpha_rows``: which of them ``alpha`` holds -- all unless they exceed
+64 MB, then a fixed seeded sample --, ``index``: per belief the row of its alpha', ``actions``: per belief its action).
 
 With N>1 the beliefs are sharded and each step is the product path of ``dist.sharded_engine_step``: local backup, ONE
 all-gather of integers (per-belief index / action / keep + the keys of the distinct rows), global dedup, and every
@@ -21,8 +25,8 @@ replica appends the globally distinct rows to its alpha store.  ``--scaling weak
 GPU; ``--scaling strong --beliefs-total 8192`` is BASELINE config 5 literally.
 
 Workload: the synthetic olfactory model of SURVEY.md 8d, reachable-sparse R=1 (BASELINE config "reachable-sparse CSR
-SpMM backup", as every large model of the reference).  The other BASELINE configurations that fit one GPU run in the
-same process and are reported under ``secondary``, each with its own roofline: ``c3_dense`` (dense projection as
+SpMM backup", as every large model of the reference).  With ``--full`` the other BASELINE configurations that fit one GPU
+run in the same process and are reported under ``secondary``, each with its own roofline: ``c3_dense`` (dense projection as
 |A||O| MFMA GEMMs over densified T.O, every tile multiplied), ``c4_f64`` (the reference's precision), ``c4_r5``
 (stochastic moves, 5 reachable states).  Prints ONE JSON line on rank 0.
 """
@@ -191,6 +195,25 @@ def timed_steps(step, steps: int, warmup: int, fence):
     return np.asarray(per), time.perf_counter() - t0, outs
 
 
+DUMP_BYTES = 60 * 10**6           # --dump-outputs: at most 64 MB however counted
+
+
+def dump_outputs(out_dir: str, host: HostResults, U: int, row_of_key: np.ndarray):
+    """``--dump-outputs``: the last step's results as the caller holds them (``alpha'[b] == rows[row_of_key[index[b]]]``),
+    written as float arrays.  The distinct rows go in key order (first occurrence over the beliefs); past the byte budget a
+    fixed seeded sample of them, named in ``alpha_rows``."""
+    os.makedirs(out_dir, exist_ok=True)
+    B, S = host.index.shape[0], host.rows.shape[1]
+    room = max(1, (DUMP_BYTES - 3 * B * 8) // (S * host.rows.itemsize + 8))
+    keys = np.arange(U)
+    if U > room:
+        keys = np.sort(np.random.default_rng(0).choice(U, room, replace=False))
+    np.save(os.path.join(out_dir, 'alpha.npy'), host.rows[row_of_key[keys]])
+    np.save(os.path.join(out_dir, 'alpha_rows.npy'), keys.astype(np.float64))
+    np.save(os.path.join(out_dir, 'index.npy'), host.index.astype(np.float64))
+    np.save(os.path.join(out_dir, 'actions.npy'), host.actions.astype(np.float64))
+
+
 def measure_config(name, m, alpha, beliefs, dtype, mode, steps, warmup, fence, true_dense=False, screen=None, fused=None,
                    formulation=None, pmc_tag=None):
     """One single-GPU configuration measured like round 2's headline (run + results to pinned host, median; the SAME
@@ -245,7 +268,7 @@ def main():
     ap.add_argument('--beliefs-total', type=int, default=8192, help='beliefs over all GPUs (--scaling strong: BASELINE config 5)')
     ap.add_argument('--alphas', type=int, default=1024)
     ap.add_argument('--reach', type=int, default=1, choices=[1, 5], help='reachable states per (s,a)')
-    ap.add_argument('--cpu-sample', type=int, default=1024, help='beliefs in the CPU baseline sample (0 = skip)')
+    ap.add_argument('--cpu-sample', type=int, default=1024, help='beliefs in the CPU baseline sample of --full (0 = skip)')
     ap.add_argument('--grid', type=str, default='75x400')
     ap.add_argument('--dtype', type=str, default='f32', choices=['f32', 'f64'], help='engine arithmetic type')
     ap.add_argument('--formulation', type=str, default='auto', choices=['auto', 'alpha', 'belief'],
@@ -257,7 +280,12 @@ def main():
                                                             'of pbvi_backup_run_fetch')
     ap.add_argument('--blocks', type=int, default=3, help='belief blocks in the device store the timed steps rotate over')
     ap.add_argument('--secondary', type=str, default='auto', choices=['auto', 'none'],
-                    help="'auto': on one GPU with the default workload also measure c3_dense, c4_f64, c4_r5")
+                    help="'auto': with --full, on one GPU with the default workload also measure c3_dense, c4_f64, c4_r5")
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline steps also measure the reused-block, device-resident and PCIe-inclusive variants, '
+                         'the secondary configurations and the CPU baseline')
+    ap.add_argument('--dump-outputs', type=str, default=None, metavar='DIR',
+                    help="write what the last timed step returned (distinct alpha' rows, index, actions) as DIR/<name>.npy")
     args = ap.parse_args()
 
     import torch
@@ -275,6 +303,8 @@ def main():
         local_rank = local_rank % max(1, torch.cuda.device_count())
     torch.cuda.set_device(local_rank)
     distributed = world > 1 or os.environ.get('PBVI_FORCE_DIST') == '1'   # the latter: rehearse the RCCL path on one GPU
+    if distributed and args.dump_outputs:
+        raise SystemExit('--dump-outputs: single-process runs only')
     dist = None
     if distributed:
         import torch.distributed as dist
@@ -348,24 +378,26 @@ def main():
             return st
         if args.two_calls:
             st = eng.run(m.gamma)
-            eng.fetch_compact_into(host.rows, host.index, host.actions)   # U rows + index + actions -> pinned host, synchronised
+            step.u = eng.fetch_compact_into(host.rows, host.index, host.actions)   # U rows + index + actions -> pinned host, synchronised
         else:
             # the same in one call, the rows leaving for the host while the refinement still runs (pbvi_backup_run_fetch)
-            st, _, _ = eng.run_fetch_into(m.gamma, host.rows, host.slot, host.index, host.actions)
+            st, step.u, _ = eng.run_fetch_into(m.gamma, host.rows, host.slot, host.index, host.actions)
         return st
     step.n = 0
 
     per_step, elapsed, stats = timed_steps(step, args.steps, args.warmup, fence)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, host, step.u, np.arange(step.u) if args.two_calls else host.slot)
     if distributed:
         t = torch.tensor(np.concatenate([[elapsed], per_step]), dtype=torch.float64, device='cpu' if backend == 'gloo' else 'cuda')
         dist.all_reduce(t, op=dist.ReduceOp.MAX)                    # slowest rank, step by step and over the region
         elapsed, per_step = float(t[0].item()), t[1:].cpu().numpy()
 
-    # device-resident variant: the same backups with the results left in HBM
+    # --full: the device-resident variant, the same backups with the results left in HBM, and the others below
     resident_ms = None
     host_ms = None
     reused = None
-    if not distributed:
+    if args.full and not distributed:
         if rotate:                                    # round 2's metric: one block backed up again and again
             eng.set_beliefs(beliefs)
 
@@ -465,10 +497,10 @@ def main():
     host.close()
     eng.close()
 
-    # The other BASELINE configurations that fit one GPU, in the same process (single-GPU default run only)
+    # --full: the other BASELINE configurations that fit one GPU, in the same process (single-GPU default workload only)
     default_workload = (world == 1 and not distributed and args.mode == 'sparse' and args.dtype == 'f32' and args.reach == 1
                         and args.grid == '75x400' and args.alphas == 1024 and B == 1024)
-    if rank == 0 and args.secondary == 'auto' and default_workload:
+    if rank == 0 and args.full and args.secondary == 'auto' and default_workload:
         sec = {}
         try:
             sec['c4_unfused'] = measure_config('the headline workload with the Gamma projection as a kernel of its own (round 1\'s '
@@ -513,7 +545,7 @@ def main():
             sec['error'] = f'{type(e).__name__}: {e}'
         out['secondary'] = sec
     if rank == 0:
-        if world == 1 and not distributed and args.cpu_sample > 0:
+        if args.full and world == 1 and not distributed and args.cpu_sample > 0:
             out['cpu_baseline'] = cpu_baseline(m, alpha, beliefs, min(args.cpu_sample, B))
         print(json.dumps(out), flush=True)
     if distributed:

@@ -43,6 +43,6 @@ python3 examples/olfactory_fsvi.py --expansions 300 --growth 100 --dtype f64 > $
 echo fsvi done
 PBVI_FORCE_DIST=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 python3 bench.py --cpu-sample 0 --secondary none --steps 20 > $O/dist_1rank_rccl.json 2> $O/dist_1rank.err
 echo dist done
-python3 bench.py --steps 50 --warmup 10 > $O/bench_default.json 2> $O/bench_default.err
+python3 bench.py --full --steps 50 --warmup 10 > $O/bench_default.json 2> $O/bench_default.err
 echo bench done
 du -sh $O
