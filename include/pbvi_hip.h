@@ -89,6 +89,8 @@ typedef struct pbvi_stats {
                                 copies of the operands, near-ties re-decided from the fp64 originals), 0 = pure fp64 */
     int32_t fused_projection; /* 1 when the score GEMM generated its Gamma tiles in the operand staging (R = 1, fp32
                                 scoring, alpha-side formulation): ms_project then covers only the few projected rows */
+    int32_t score_split;      /* 1 when the scores came from bf16 MFMAs on the three-term operand split (fp32 engines,
+                                alpha-side formulation; pbvi_set_score_split), 0 = fp32 MFMAs */
 } pbvi_stats_t;
 
 /* Library / device queries. */
@@ -417,6 +419,17 @@ int pbvi_set_f64_screen(pbvi_engine_t* e, int mode);
  * dense mode).
  */
 int pbvi_set_fused_projection(pbvi_engine_t* e, int enable);
+
+/*
+ * fp32 engines (a no-op setting on fp64 ones and on their fp32 screen): where the backup's alpha-side score GEMM runs.
+ * 1 (default) = on bf16 MFMAs with a three-term operand split (x = hi + lo, products hi*hi + hi*lo + lo*hi, fp32
+ * accumulation) when the GEMM is large, with the near-tie window widened by the split's error bound, so indices,
+ * actions and alpha' rows are those of the fp32 GEMM; 0 = never; 2 = always (tests).  The fp32 GEMM is kept for the
+ * value-max GEMMs, the belief-side formulation and after pbvi_set_tie_window(rel > 0).  With R > 1 reachable states
+ * per (s, a) the split reads the projected Gamma rows: pbvi_set_fused_projection(2) then does not fuse.
+ * PBVI_SCORE_SPLIT=off|auto|always in the environment sets the initial mode.  pbvi_stats_t.score_split reports it.
+ */
+int pbvi_set_score_split(pbvi_engine_t* e, int mode);
 
 /* Tuning knob for f32 engines: relative half-width of the near-tie window that sends an
  * argmax to fp64 refinement (<= 0 restores the default derived from |S|). */

@@ -128,7 +128,8 @@ template <typename T>
 hipError_t launch_argmax(SlabView<T> sv, int V, int G, int B, const uint8_t* dead, double tol_rel, double tol_abs,
                          const int* chain_steps /* device: K-tile steps of the longest f32 chain; used when tol_rel < 0 */,
                          int flag_all, int32_t* best_v, double* best_score, double* err, int32_t* queue, int* qcount,
-                         hipStream_t st, double tol_extra = 0.0 /* added to the relative window: input rounding of a screen */);
+                         hipStream_t st, double tol_extra = 0.0 /* added to the relative window: input rounding of a screen */,
+                         int split = 0 /* the scores came from the split bf16 GEMM: its window (score_window) */);
 
 // Work list of the refinement: entries with many near-tied candidates hand their (entry, candidate) pairs to a
 // grid-wide pass instead of scoring them one block per entry (device memory; items_v == nullptr: all in-block).
@@ -211,7 +212,8 @@ template <typename T>
 hipError_t launch_action(int B, ModelView<T> mv, SlabView<T> sv, int64_t rd_col0, double tol_rel, const int* chain_steps,
                          const double* best_score, const double* err, double* rdot, double* rdot_err, int32_t* action,
                          int32_t* aqueue, int* aqcount, hipStream_t st, double tol_extra = 0.0,
-                         uint8_t* acand = nullptr /* [B][A] out: action inside the window of the best lower bound */);
+                         uint8_t* acand = nullptr /* [B][A] out: action inside the window of the best lower bound */,
+                         int split = 0 /* rdot came from the split bf16 GEMM */);
 constexpr int ACTION_SPLIT = 8;          // parts each exact dot of the action refinement is cut into (val_exact: [B][A][1+O][ACTION_SPLIT])
 template <typename T>
 hipError_t launch_refine_action(const T* bel, int ldb, int B, const T* alpha, int lda, ModelView<T> mv, double gamma,

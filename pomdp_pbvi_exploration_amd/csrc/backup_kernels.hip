@@ -677,6 +677,20 @@ hipError_t launch_dead(const T* bel, int ldb, int B, ModelView<T> mv, const unsi
     return hipGetLastError();
 }
 
+// Relative error bound of an fp32-engine score against its magnitude (tol_rel < 0: from the stream-K share size, known
+// only on the device).  f32 GEMM: 8 * 2^-24 * (sqrt(longest fma chain) + 1).  split (bf16 MFMAs on the three-term split,
+// gemm.hip scheduler 2d): the chain counted as 3x as many additions, plus 3.1 * 2^-16 for the dropped bl*gl term and the
+// lo roundings ((3u^2 + 2u^3) |b||g| per product, u = 2^-8), the whole scaled by 1 + 2^-11 because the magnitude it
+// multiplies came from the same GEMM (low by at most that bound, ~1e-4 relative).
+__device__ __forceinline__ double score_window(double tol_rel, const int* chain_steps, int split) {
+    const double u24 = 5.9604644775390625e-08;
+    double tr = tol_rel;
+    if (chain_steps != nullptr && tol_rel < 0.0)
+        tr = 8.0 * u24 * (sqrt((double)chain_steps[0] * 32.0 * (split ? 3.0 : 1.0)) + 1.0);
+    if (split) tr = (tr + 3.1 * 1.52587890625e-05) * (1.0 + 4.8828125e-04);
+    return tr;
+}
+
 // ------------------------------------------------------------------------- //
 // argmax over alpha-vectors, one wavefront per (belief, group) row segment.
 // np.argmax semantics: first maximum.  src/pomdp.py:1495 (argmax part)
@@ -684,7 +698,7 @@ hipError_t launch_dead(const T* bel, int ldb, int B, ModelView<T> mv, const unsi
 template <typename T>
 __global__ void k_argmax(SlabView<T> sv, int V, int G, int B, const uint8_t* __restrict__ dead, double tol_rel,
                          double tol_abs, double tol_extra, const int* __restrict__ chain_steps, int flag_all, int32_t* __restrict__ best_v, double* __restrict__ best_score,
-                         double* __restrict__ err, int32_t* __restrict__ queue, int* __restrict__ qcount) {
+                         double* __restrict__ err, int32_t* __restrict__ queue, int* __restrict__ qcount, int split) {
     const int lane = threadIdx.x & 63;
     const int64_t gw = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (gw >= (int64_t)B * G) return;
@@ -801,10 +815,8 @@ __global__ void k_argmax(SlabView<T> sv, int V, int G, int B, const uint8_t* __r
         const double mag = fmax(fabs((double)m), fabs(sv.magnitude(b, g, G, V)));
         // f32 error model: 8 * 2^-24 * sqrt(longest fma chain) (+ slab sums); the chain length is the
         // stream-K share size, known only on the device
-        double tr = tol_rel;
-        if (chain_steps != nullptr && tol_rel < 0.0)
-            tr = 8.0 * 5.9604644775390625e-08 * (sqrt((double)chain_steps[0] * 32.0) + 1.0);
-        if (sv.push) tr += 2.0 * 5.9604644775390625e-08;    // bp is rounded once to f32 after its f64 accumulation
+        const double tr = score_window(tol_rel, chain_steps, split) + (sv.push ? 2.0 * 5.9604644775390625e-08 : 0.0);
+        // (sv.push: bp is rounded once to f32 after its f64 accumulation)
         E = (tr + tol_extra) * mag + tol_abs;               // tol_extra: input rounding of an fp32 screen of fp64 operands
         push = (flag_all || (double)m2 >= (double)m - 2.0 * E) ? 1 : 0;
     }
@@ -822,11 +834,11 @@ __global__ void k_argmax(SlabView<T> sv, int V, int G, int B, const uint8_t* __r
 template <typename T>
 hipError_t launch_argmax(SlabView<T> sv, int V, int G, int B, const uint8_t* dead, double tol_rel, double tol_abs,
                          const int* chain_steps, int flag_all, int32_t* best_v, double* best_score, double* err,
-                         int32_t* queue, int* qcount, hipStream_t st, double tol_extra) {
+                         int32_t* queue, int* qcount, hipStream_t st, double tol_extra, int split) {
     const int64_t rows = (int64_t)B * G;
     if (rows <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_argmax<T>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, sv, V, G, B, dead, tol_rel,
-                       tol_abs, tol_extra, chain_steps, flag_all, best_v, best_score, err, queue, qcount);
+                       tol_abs, tol_extra, chain_steps, flag_all, best_v, best_score, err, queue, qcount, split);
     return hipGetLastError();
 }
 
@@ -1561,16 +1573,15 @@ __global__ void k_action_select(int B, int per_block, ModelView<T> mv, SlabView<
                                 const int* __restrict__ chain_steps, const double* __restrict__ best_score,
                                 const double* __restrict__ err, double* __restrict__ rdot, double* __restrict__ rdot_err,
                                 int32_t* __restrict__ action, int32_t* __restrict__ aqueue, int* __restrict__ aqcount,
-                                uint8_t* __restrict__ acand /* [B][A]: action within the window of the best lower bound (or nullptr) */) {
+                                uint8_t* __restrict__ acand /* [B][A]: action within the window of the best lower bound (or nullptr) */,
+                                int split) {
     __shared__ double sv_[256], se_[256];
     const int A = mv.A;
     const int lb = threadIdx.x / A, a = threadIdx.x - lb * A;
     const int b = blockIdx.x * per_block + lb;
     const bool live = lb < per_block && b < B;
     if (live) {
-        double tr = tol_rel;
-        if (chain_steps != nullptr && tol_rel < 0.0) tr = 8.0 * 5.9604644775390625e-08 * (sqrt((double)chain_steps[0] * 32.0) + 1.0);
-        tr += tol_extra;
+        const double tr = score_window(tol_rel, chain_steps, split) + tol_extra;
         double rd, E = 0.0;
         if (sv.push) {
             rd = sv.aux_rd[(int64_t)b * A + a];               // f64 dot: exact to 1e-16, no window needed
@@ -1619,12 +1630,12 @@ __global__ void k_action_select(int B, int per_block, ModelView<T> mv, SlabView<
 template <typename T>
 hipError_t launch_action(int B, ModelView<T> mv, SlabView<T> sv, int64_t rd_col0, double tol_rel, const int* chain_steps,
                          const double* best_score, const double* err, double* rdot, double* rdot_err, int32_t* action,
-                         int32_t* aqueue, int* aqcount, hipStream_t st, double tol_extra, uint8_t* acand) {
+                         int32_t* aqueue, int* aqcount, hipStream_t st, double tol_extra, uint8_t* acand, int split) {
     if (B <= 0) return hipSuccess;
     if (mv.A > 256) return hipErrorInvalidValue;
     const int per_block = 256 / mv.A;
     hipLaunchKernelGGL(k_action_select<T>, dim3((B + per_block - 1) / per_block), dim3(256), 0, st, B, per_block, mv, sv, rd_col0,
-                       tol_rel, tol_extra, chain_steps, best_score, err, rdot, rdot_err, action, aqueue, aqcount, acand);
+                       tol_rel, tol_extra, chain_steps, best_score, err, rdot, rdot_err, action, aqueue, aqcount, acand, split);
     return hipGetLastError();
 }
 
@@ -2288,12 +2299,13 @@ hipError_t launch_walk_step(const double* base, ModelView<T> mv, const double* r
                                        int32_t*, int*, hipStream_t, const uint8_t*, const int32_t*);                                                   \
     template hipError_t launch_belief_tiles<T>(const T*, int, int, int, int, int32_t*, int32_t*, hipStream_t);         \
     template hipError_t launch_argmax<T>(SlabView<T>, int, int, int, const uint8_t*, double, double, const int*, int,  \
-                                         int32_t*, double*, double*, int32_t*, int*, hipStream_t, double);             \
+                                         int32_t*, double*, double*, int32_t*, int*, hipStream_t, double, int);        \
     template hipError_t launch_refine<T, T>(bool, SlabView<T>, int, int, int, const int32_t*, const int*, const T*, int, \
                                          const T*, int, ModelView<T>, double, const int32_t*, const int32_t*,          \
                                          const uint8_t*, int32_t*, double*, double*, int*, RefineWork, hipStream_t);   \
     template hipError_t launch_action<T>(int, ModelView<T>, SlabView<T>, int64_t, double, const int*, const double*,   \
-                                         const double*, double*, double*, int32_t*, int32_t*, int*, hipStream_t, double, uint8_t*); \
+                                         const double*, double*, double*, int32_t*, int32_t*, int*, hipStream_t, double, uint8_t*, \
+                                         int);                                                                          \
     template hipError_t launch_refine_action<T>(const T*, int, int, const T*, int, ModelView<T>, double,               \
                                                 const int32_t*, const int32_t*, const int32_t*, const int*,            \
                                                 const double*, const double*, const int32_t*, const double*,           \

@@ -623,6 +623,7 @@ struct ScoreIO {                      // the pipeline buffers the stage writes /
     hipEvent_t* ev;                   // ev[1] after the projection, ev[2] after the GEMM, ev[3] after the argmax
     bool stats;
     double tol_extra;                 // added to the relative tie window (input rounding of a screen)
+    bool allow_split;                 // the scores may come from the split bf16 GEMM (not on an fp64 engine's screen)
 };
 template <typename TS>
 struct ScoreStage {
@@ -632,6 +633,7 @@ struct ScoreStage {
     const int* chain;
     int64_t rd_col0, extra_row0, f64_pairs;
     bool fused;                       // the GEMM generated its Gamma tiles itself (gemm.hip, scheduler 2b)
+    int split;                        // 1: bf16 MFMAs on the three-term operand split (gemm.hip, scheduler 2d)
 };
 
 class EngineBase {
@@ -664,6 +666,7 @@ class EngineBase {
     virtual int alpha_layout(int64_t* free_rows, int64_t* layouts) = 0;
     virtual int set_formulation(int f) = 0;
     virtual int set_screen(int mode) = 0;
+    virtual int set_score_split(int mode) = 0;
     virtual int set_fused(int enable) = 0;
     virtual int64_t device_bytes() const = 0;
     virtual int64_t store_append(int which, const void* rows, int64_t n) = 0;
@@ -800,6 +803,8 @@ class EngineT : public EngineBase {
     bool have_result_ = false, res_sorted_ = false;
     int64_t res_B_ = 0;
     int screen_mode_ = 1;                                    // fp64 engines: 0 never screen, 1 when the GEMM is large, 2 always
+    int split_mode_ = 1;                                     // fp32 backup scores on the split bf16 GEMM: 0 never, 1 when large, 2 always
+    bool split_supported_ = false;                           // fp32: the device keeps subnormal bf16 operands (probed at creation)
     int fuse_project_ = 1;                                   // fp32: Gamma tiles generated inside the score GEMM; 0 never, 1 = where it
                                                              // is faster (R = 1), 2 = also for R = 2..7 (measured slower)
     double irr_frac_ = 0.0;                                  // share of (action, K tile) with non-consecutive successors
@@ -898,11 +903,16 @@ class EngineT : public EngineBase {
             const std::string v(f);
             screen_mode_ = (v == "off" || v == "0") ? 0 : (v == "always" || v == "2") ? 2 : 1;
         }
+        if (const char* f = getenv("PBVI_SCORE_SPLIT")) {     // initial setting (tests run the whole suite with the split forced)
+            const std::string v(f);
+            split_mode_ = (v == "off" || v == "0") ? 0 : (v == "always" || v == "2") ? 2 : 1;
+        }
         if (const char* f = getenv("PBVI_FORMULATION")) {     // initial setting (tests run the whole suite both ways)
             const std::string v(f);
             formulation_ = (v == "alpha" || v == "1") ? 1 : (v == "belief" || v == "2") ? 2 : 0;
         }
         HIPCHK(hipSetDevice(device_));
+        if constexpr (kF32) split_supported_ = gemm_split_supported(device_) != 0;
         if (shared_main != nullptr) {   // an fp32 screen lives on its fp64 engine's streams: one pipeline, one order
             stream_ = shared_main;
             stream2_ = shared_side;
@@ -1767,7 +1777,7 @@ class EngineT : public EngineBase {
     // scores of X rows (default: the resident belief block) against the rows of Y
     int score_gemm(const T* Y, int64_t rows_y, const uint8_t* nzB, int G, int v_group, SlabView<T>* sv,
                    const T* X = nullptr, int64_t x_rows = 0, const uint8_t* nzX = nullptr, hipStream_t list_stream = nullptr,
-                   const FusedB* fused = nullptr);
+                   const FusedB* fused = nullptr, int* split = nullptr /* in: wanted, out: done (scheduler 2d) */);
 
     int project_dense(double gamma);   // K1-dense: Gamma = gamma * alpha . D_ao^T as A*O (batched) GEMMs
     int backup_run(double gamma, int flags, pbvi_stats_t* st) override;
@@ -2327,6 +2337,12 @@ class EngineT : public EngineBase {
         static const bool off = getenv("PBVI_NO_SKINNY") != nullptr;      // debug / A-B only
         return kF32 && !off && V_ > 0 && V_ <= 64 && mode_ == PBVI_SPARSE;
     }
+    // automatic score split: from this many dense 256x256x32 tile-steps of the padded score GEMM (C4: 274k)
+    static constexpr int64_t kSplitMinSteps = 16384;
+    bool split_pays(int64_t n_rows_alloc, int k_tiles) const {
+        const int64_t dense_steps = (B_pad_ / GEMM_BM) * (n_rows_alloc / GEMM_BN) * (int64_t)k_tiles;
+        return dense_steps >= kSplitMinSteps;
+    }
     // fp64 engines: MFMA GEMM unless the problem is a handful of tiles (the plain kernel is as good there)
     static bool f64_uses_mfma(int64_t m_rows, int64_t n_rows) {
         static const bool simple = getenv("PBVI_F64_SIMPLE") != nullptr;      // debug / A-B only
@@ -2341,6 +2357,11 @@ class EngineT : public EngineBase {
     int set_screen(int mode) override {
         if (mode < 0 || mode > 2) FAIL(PBVI_EINVAL, "set_f64_screen: 0 = never, 1 = automatic, 2 = always");
         screen_mode_ = mode;
+        return PBVI_OK;
+    }
+    int set_score_split(int mode) override {
+        if (mode < 0 || mode > 2) FAIL(PBVI_EINVAL, "set_score_split: 0 = never, 1 = automatic, 2 = always");
+        split_mode_ = mode;
         return PBVI_OK;
     }
     int set_formulation(int f) override {
@@ -2370,7 +2391,8 @@ class EngineT : public EngineBase {
 
 template <typename T>
 int EngineT<T>::score_gemm(const T* Y, int64_t rows_y, const uint8_t* nzB, int G, int v_group, SlabView<T>* sv,
-                           const T* X, int64_t x_rows, const uint8_t* nzX, hipStream_t list_stream, const FusedB* fused) {
+                           const T* X, int64_t x_rows, const uint8_t* nzX, hipStream_t list_stream, const FusedB* fused,
+                           int* split) {
     int rc;
     const int64_t m_rows = X ? x_rows : B_;
     const int64_t m_pad = X ? round_up(x_rows, GEMM_BM) : B_pad_;
@@ -2388,10 +2410,12 @@ int EngineT<T>::score_gemm(const T* Y, int64_t rows_y, const uint8_t* nzB, int G
         if ((rc = kcount_.ensure(pairs * sizeof(int), &bytes_))) return rc;
         if ((rc = nchunks_.ensure(pairs * sizeof(int), &bytes_))) return rc;
         if ((rc = skws_.ensure(streamk_workspace_ints(plan_) * sizeof(int), &bytes_))) return rc;
+        const int sp = split != nullptr && *split && plan_.streamk && (fused == nullptr || fused->R == 1) ? 1 : 0;
+        if (split != nullptr) *split = sp;
         HIPCHK(launch_gemm_nt_f32((const float*)X, S_pad_, (const float*)Y, S_pad_, slabs_.as<float>(), plan_,
                                   nzX, nzB, G, v_group, (int)rows_y, klist_.as<int>(), kcount_.as<int>(),
                                   nchunks_.as<int>(), stream_, 1, 0, 0, skws_.as<int>(), list_stream, ev_lists_, nullptr, nullptr,
-                                  fused));
+                                  fused, sp));
         sv->slabs = slabs_.as<T>();
         sv->slab_stride = plan_.slab_stride;
         sv->ldc = plan_.ldc;
@@ -2615,11 +2639,19 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
     // groups and the tail tile are projected ("mat" tiles).  Then only THOSE tiles exist in memory: tile tn of Gamma
     // lives at compact tile ctile[tn] (C4: one tile, 30 MB, instead of 2.24 GB; the reference's CuPy path died
     // allocating Gamma[A,O,V,S], Sea_Robin_Real.ipynb:913).
+    // The split bf16 GEMM (gemm.hip, scheduler 2d) for the alpha-side scores of an fp32 engine, unless the caller set its
+    // own tie window (defined against the fp32 GEMM) or the device flushes subnormal bf16 operands.  Automatic: by shape
+    // only (split_pays), so the fused and the projected route decide alike.  With R > 1 the split takes the projected
+    // route: the R > 1 fused kernel (scheduler 2c, never chosen by default) has no split variant.
+    int want_split = 0;
+    if constexpr (kF32)
+        want_split = io.allow_split && !use_push && tie_rel_user_ <= 0.0 && split_supported_ &&
+                     (split_mode_ == 2 || (split_mode_ == 1 && split_pays(n_rows_alloc, k_tiles)));
     bool will_fuse = false;
     if constexpr (kF32) {
         static const bool no_fuse = getenv("PBVI_NO_FUSED_PROJECT") != nullptr;     // debug / A-B only
         will_fuse = !use_push && mode_ == PBVI_SPARSE && !no_fuse && irr_.p != nullptr &&
-                    (R_ == 1 ? fuse_project_ >= 1 : (R_ <= 7 && fuse_project_ >= 2));
+                    (R_ == 1 ? fuse_project_ >= 1 : (R_ <= 7 && fuse_project_ >= 2 && !want_split));
     }
     static const bool no_compact = getenv("PBVI_NO_COMPACT_GAMMA") != nullptr;      // debug / A-B only
     const bool compact = will_fuse && R_ == 1 && !no_compact;
@@ -2671,6 +2703,7 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
     SlabView<T> sv;
     out->extra_row0 = -1;
     out->fused = false;
+    out->split = 0;
     if (use_push) {
         // K1 (belief side): every belief through every (a, o); K2: [B*A*O] x [V]
         if ((rc = build_inverse_lists())) return rc;
@@ -2761,7 +2794,10 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
         HIPCHK(hipEventRecord(io.ev[1], stream_));
         // K2: scores
         // (its tile lists and stream-K plan are built on the side stream, beside the projection)
-        if ((rc = score_gemm(gam_.as<T>(), N, nzB_.as<uint8_t>(), AO, (int)V_, &sv, nullptr, 0, nullptr, io.side, fused))) return rc;
+        int split = want_split;
+        if ((rc = score_gemm(gam_.as<T>(), N, nzB_.as<uint8_t>(), AO, (int)V_, &sv, nullptr, 0, nullptr, io.side, fused, &split)))
+            return rc;
+        out->split = split;
         out->fused = fused != nullptr;
     }
     HIPCHK(hipEventRecord(io.ev[2], stream_));
@@ -2773,7 +2809,7 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
     out->rd_col0 = (int64_t)AO * Vt;
     out->f64_pairs = f64_pairs_;
     HIPCHK(launch_argmax<T>(sv, (int)V_, AO, (int)B_, io.dead, out->tol_rel, 0.0, out->chain, 0, io.best_v, io.best_score,
-                            io.err, io.queue, io.qcount, stream_, io.tol_extra));
+                            io.err, io.queue, io.qcount, stream_, io.tol_extra, out->split));
     HIPCHK(hipEventRecord(io.ev[3], stream_));
     out->sv = sv;
     return PBVI_OK;
@@ -2993,6 +3029,7 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
     io.stats = st != nullptr;
     // a screen multiplies operands rounded to fp32 (alpha, belief, RTO: 2^-24 relative each) and gamma in fp32
     io.tol_extra = screened ? 4.0 * 5.9604644775390625e-08 : 0.0;
+    io.allow_split = !screened;
     ScoreStage<TS> sc;
     if ((rc = scorer.stage_scores(gamma, use_push, io, &sc))) return rc;
     const SlabView<TS>& sv = sc.sv;
@@ -3073,7 +3110,7 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
         // refinement cost it 0.13 ms: a net loss.)
         HIPCHK(launch_action<TS>((int)B_, scorer.view(), sv, sc.rd_col0, sc.tol_rel, sc.chain, best_score_.as<double>(), err_.as<double>(),
                                  e_rdot_.as<double>(), e_rdot_.as<double>() + (size_t)B_ * A_, e_act_.as<int32_t>(), nullptr, nullptr, stream_,
-                                 io.tol_extra));
+                                 io.tol_extra, nullptr, sc.split));
         const int32_t* pa = e_act_.as<int32_t>();
         const int32_t* pb = e_bv_.as<int32_t>();
         if (sorted_) {
@@ -3158,7 +3195,7 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
         HIPCHK(launch_action<TS>((int)B_, scorer.view(), sv, sc.rd_col0, sc.tol_rel, sc.chain, best_score_.as<double>(),
                                  err_.as<double>(), rdot_.as<double>(), rdot_err, action_.as<int32_t>(),
                                  windows ? aqueue_.as<int32_t>() : nullptr, aqcount, stream_, io.tol_extra,
-                                 windows ? acand_.as<uint8_t>() : nullptr));
+                                 windows ? acand_.as<uint8_t>() : nullptr, sc.split));
         if (windows)
             HIPCHK(launch_refine_action<T>(bel_.as<T>(), S_pad_, (int)B_, alpha_.as<T>(), S_pad_, mv, gamma,
                                            btl_.as<int32_t>(), btc_.as<int32_t>(),
@@ -3333,6 +3370,7 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
         }
         st->screened = screened ? 1 : 0;
         st->fused_projection = sc.fused ? 1 : 0;
+        st->score_split = sc.split;
     }
     return PBVI_OK;
 }
@@ -3812,6 +3850,10 @@ int pbvi_set_fused_projection(pbvi_engine_t* e, int enable) {
 int pbvi_set_f64_screen(pbvi_engine_t* e, int mode) {
     NEED(e);
     return e->impl->set_screen(mode);
+}
+int pbvi_set_score_split(pbvi_engine_t* e, int mode) {
+    NEED(e);
+    return e->impl->set_score_split(mode);
 }
 int pbvi_set_value_max_exact(pbvi_engine_t* e, int exact) {
     NEED(e);

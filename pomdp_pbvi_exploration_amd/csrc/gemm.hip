@@ -28,6 +28,8 @@
 #include "pbvi_common.h"
 
 #include <cstdlib>
+#include <map>
+#include <mutex>
 
 namespace pbvi {
 
@@ -739,6 +741,310 @@ __global__ __launch_bounds__(512) void k_gemm_nt_f32_streamk_fused_r(
 }
 
 // --------------------------------------------------------------------------- //
+// scheduler 2d: stream-K on bf16 MFMAs with a three-term operand split (fp32 data, fp32 accumulation)
+// --------------------------------------------------------------------------- //
+// Every operand element x is split as hi = RNE_bf16(x), lo = RNE_bf16(x - hi) (x - hi is exact in fp32), and a product
+// b*g is taken as bh*gh + bh*gl + bl*gh: three v_mfma_f32_32x32x16_bf16 per 32x32x16 block, 3/16 of the MFMA cycles of
+// the fp32 instruction.  Per product |b*g - (bh*gh + bh*gl + bl*gh)| <= (3u^2 + 2u^3)|b||g|, u = 2^-8; the engine widens
+// the tie window by that (numerics).  A finite |x| above the largest finite bf16 (where RNE would give inf)
+// takes hi = +-max bf16 instead, which keeps the same bound within 1 %.
+// Both operands are loaded to registers, split there and written to LDS: a 256-row x 32-k stage of (hi, lo) is 32 KiB,
+// the size of an fp32 stage, so the double buffer and the source-side XOR swizzle carry over -- LDS row r holds 8 chunks
+// of 8 bf16: hi k 0-7, 8-15, 16-23, 24-31, then lo in the same order, chunk c at physical chunk c ^ ((r>>1)&7).  Lane
+// (i, h) of the k-half kk reads hi chunk 2kk+h and lo chunk 4+2kk+h of its rows: k = 16kk + 8h + j, the MFMA's own order.
+// The B operand is generated (scheduler 2b's arithmetic, then split) or read from fp32 rows in HBM; the two routes write
+// the same LDS image, so they issue the same MFMAs on the same bits.  Plan, lists, slabs: unchanged.
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+__device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b) {
+    uint32_t r;
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));    // a -> bits 0-15, b -> bits 16-31, RNE
+    return r;
+}
+__device__ __forceinline__ float bf16_sat(float x) {
+    const float m = 0x1.fep127f;                                        // largest finite bf16
+    return fabsf(x) > m ? copysignf(m, x) : x;                          // (a NaN stays a NaN)
+}
+__device__ __forceinline__ void split_pair(float x0, float x1, uint32_t& hi, uint32_t& lo) {
+#pragma clang fp contract(off)
+    hi = cvt_pk_bf16(bf16_sat(x0), bf16_sat(x1));
+    const float h0 = __uint_as_float(hi << 16), h1 = __uint_as_float(hi & 0xffff0000u);
+    lo = cvt_pk_bf16(x0 - h0, x1 - h1);
+}
+// 8 consecutive k of one row (x0: k 0-3, x1: k 4-7) -> hi and lo chunks of that row's LDS image
+__device__ __forceinline__ void split_store(float* lop, int row, int kg, const f32x4& x0, const f32x4& x1) {
+    i32x4 hi, lo;
+    uint32_t h, l;
+    split_pair(x0[0], x0[1], h, l); hi[0] = (int)h; lo[0] = (int)l;
+    split_pair(x0[2], x0[3], h, l); hi[1] = (int)h; lo[1] = (int)l;
+    split_pair(x1[0], x1[1], h, l); hi[2] = (int)h; lo[2] = (int)l;
+    split_pair(x1[2], x1[3], h, l); hi[3] = (int)h; lo[3] = (int)l;
+    const int sw = (row >> 1) & 7;
+    *(i32x4*)(lop + row * GEMM_BK + (kg ^ sw) * 4) = hi;
+    *(i32x4*)(lop + row * GEMM_BK + ((4 + kg) ^ sw) * 4) = lo;
+}
+
+__device__ __forceinline__ void split_compute(const TileThread& t, const float* lds, int buf, f32x16 (&acc)[4][2]) {
+    const float* la = lds + buf * 2 * TILE_FLOATS;
+    const float* lb = la + TILE_FLOATS;
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+        i32x4 ah[4], al[4], bh[2], bl[2];
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi) {
+            const int r = t.a_row[mi], sw = (r >> 1) & 7;
+            ah[mi] = *(const i32x4*)(la + r * GEMM_BK + ((2 * kk + t.h) ^ sw) * 4);
+            al[mi] = *(const i32x4*)(la + r * GEMM_BK + ((4 + 2 * kk + t.h) ^ sw) * 4);
+        }
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) {
+            const int r = t.b_row[ni], sw = (r >> 1) & 7;
+            bh[ni] = *(const i32x4*)(lb + r * GEMM_BK + ((2 * kk + t.h) ^ sw) * 4);
+            bl[ni] = *(const i32x4*)(lb + r * GEMM_BK + ((4 + 2 * kk + t.h) ^ sw) * 4);
+        }
+        // per element the order is fixed: + bh*gh, + bh*gl, + bl*gh (term-major over the 8 blocks: no dependent pairs back to back)
+#pragma unroll
+        for (int term = 0; term < 3; ++term)
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni) {
+                    const i32x4 a = term == 2 ? al[mi] : ah[mi];
+                    const i32x4 b = term == 1 ? bl[ni] : bh[ni];
+                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b),
+                                                                          acc[mi][ni], 0, 0, 0);
+                }
+    }
+}
+
+// Multiply list entries [i0, i1) of one pair.  gen: the B tile is generated (rsrow / rtorow: the group's successor and RTO
+// rows; arow0: alpha row of this thread's first staging row; a_step: 128 rows of alpha); else it is read from Bblk.
+// Staging: thread tid takes k-group kg = tid & 3 (8 states) of rows it * 128 + (tid >> 2), it = 0, 1, of both operands.
+// Loads are inline assembly counted by explicit s_waitcnt (see ld16): per K step, in issue order, [4 table loads] + 4
+// belief loads + [4 Gamma row loads], then [the alpha loads, once the tables are in]; everything is waited for behind the
+// step's MFMAs, split and written to the other buffer.
+__device__ __forceinline__ void tile_run_split(const TileThread& t, float* lds, const float* Ablk, int lda, const float* Bblk,
+                                               int ldb, bool gen, const int32_t* __restrict__ rsrow,
+                                               const float* __restrict__ rtorow, const float* __restrict__ arow0,
+                                               int64_t a_step, float gamma, const int* __restrict__ kl, int i0, int i1,
+                                               f32x16 (&acc)[4][2]) {
+    const int tid = threadIdx.x;
+    const int kg = tid & 3, r0 = tid >> 2;
+    f32x4 xa[2][2], xb[2][2];
+    i32x4 idx[2];
+    f32x4 w[2];
+    auto load_rows = [&](f32x4 (&x)[2][2], const float* base, int ld, int entry) {
+        const int k = (entry & KL_MASK) * GEMM_BK + kg * 8;
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            const float* p = base + (int64_t)(it * 128 + r0) * ld + k;
+            ld16(x[it][0], p);
+            ld16(x[it][1], p + 4);
+        }
+    };
+    auto tables = [&](int entry) {
+        const int s = (entry & KL_MASK) * GEMM_BK + kg * 8;
+        ld16i(idx[0], rsrow + s);
+        ld16i(idx[1], rsrow + s + 4);
+        ld16(w[0], rtorow + s);
+        ld16(w[1], rtorow + s + 4);
+    };
+    auto alphas = [&](int entry) {
+        if (entry >> KL_IRR_BIT) {                        // block-uniform: some 4-state chunk of the K tile needs gathers
+#pragma unroll
+            for (int it = 0; it < 2; ++it) {
+                const float* arow = arow0 + it * a_step;
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    float e0, e1, e2, e3;
+                    ld4(e0, arow + idx[q][0]);
+                    ld4(e1, arow + idx[q][1]);
+                    ld4(e2, arow + idx[q][2]);
+                    ld4(e3, arow + idx[q][3]);
+                    asm volatile("s_waitcnt vmcnt(0)\n\tv_mov_b32 %0, %4\n\tv_mov_b32 %1, %5\n\tv_mov_b32 %2, %6\n\tv_mov_b32 %3, %7"
+                                 : "=&v"(xb[it][q].x), "=&v"(xb[it][q].y), "=&v"(xb[it][q].z), "=&v"(xb[it][q].w)
+                                 : "v"(e0), "v"(e1), "v"(e2), "v"(e3)
+                                 : "memory");
+                }
+            }
+        } else {
+#pragma unroll
+            for (int it = 0; it < 2; ++it) {
+                ld16(xb[it][0], arow0 + it * a_step + idx[0][0]);
+                ld16(xb[it][1], arow0 + it * a_step + idx[1][0]);
+            }
+        }
+    };
+    auto store = [&](int buf) {
+        float* la = lds + buf * 2 * TILE_FLOATS;
+        float* lb = la + TILE_FLOATS;
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            split_store(la, it * 128 + r0, kg, xa[it][0], xa[it][1]);
+            if (gen)
+                split_store(lb, it * 128 + r0, kg, fused_value(gamma, w[0], xb[it][0]), fused_value(gamma, w[1], xb[it][1]));
+            else
+                split_store(lb, it * 128 + r0, kg, xb[it][0], xb[it][1]);
+        }
+    };
+    auto wait_all = [&]() {
+        asm volatile("s_waitcnt vmcnt(0)"
+                     : "+v"(xa[0][0]), "+v"(xa[0][1]), "+v"(xa[1][0]), "+v"(xa[1][1]), "+v"(xb[0][0]), "+v"(xb[0][1]),
+                       "+v"(xb[1][0]), "+v"(xb[1][1])::"memory");
+    };
+    // first tile of the segment: nothing to overlap with
+    {
+        const int e0 = kl[i0];
+        if (gen) {
+            tables(e0);
+            asm volatile("s_waitcnt vmcnt(0)" : "+v"(idx[0]), "+v"(idx[1]), "+v"(w[0]), "+v"(w[1])::"memory");
+            alphas(e0);
+        } else {
+            load_rows(xb, Bblk, ldb, e0);
+        }
+        load_rows(xa, Ablk, lda, e0);
+        wait_all();
+        store(0);
+    }
+    int k_next = (i0 + 1 < i1) ? kl[i0 + 1] : 0;         // list entries are read one step ahead of their use
+    __syncthreads();
+    int buf = 0;
+    for (int it = i0; it < i1; ++it) {
+        int k_after = 0;
+        const bool more = it + 1 < i1;                    // block-uniform
+        if (more) {
+            if (gen) tables(k_next);                      // the 4 table loads first: they are waited for first
+            load_rows(xa, Ablk, lda, k_next);
+            if (!gen) load_rows(xb, Bblk, ldb, k_next);
+            if (it + 2 < i1) k_after = kl[it + 2];
+        }
+        split_compute(t, lds, buf, acc);
+        if (more) {
+            if (gen) {
+                asm volatile("s_waitcnt vmcnt(4)" : "+v"(idx[0]), "+v"(idx[1]), "+v"(w[0]), "+v"(w[1])::"memory");
+                alphas(k_next);
+            }
+            wait_all();
+            store(buf ^ 1);
+        }
+        __syncthreads();
+        buf ^= 1;
+        k_next = k_after;
+    }
+}
+
+// fb.mat == nullptr: every B tile is read from fp32 rows (the projected route); else scheduler 2b's tiles (R = 1).
+__global__ __launch_bounds__(512) void k_gemm_split_streamk(
+    const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb, FusedB fb, float* __restrict__ C, int ldc,
+    int64_t slab_stride, int tiles_m, int pairs, int k_tiles, const int* __restrict__ klist, const int* __restrict__ kcount,
+    const int* __restrict__ prefix, const int* __restrict__ start_pair, const int* __restrict__ first_block,
+    const int* __restrict__ plan, int ovh) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int nb = gridDim.x;
+    int L;
+    {
+        const int bid = blockIdx.x, xcd = bid & 7, qq = nb >> 3, r = nb & 7;
+        const int base = (xcd < r) ? xcd * (qq + 1) : r * (qq + 1) + (xcd - r) * qq;
+        L = base + (bid >> 3);
+    }
+    const int q = plan[0], T = plan[1];
+    int64_t pos = (int64_t)L * q;
+    if (pos >= T) return;
+    const int64_t end = (pos + q < T) ? pos + q : T;
+    int p = start_pair[L];
+    if (p < 0) return;
+    TileThread t;
+    t.init();
+    while (pos < end && p < pairs) {
+        const int cnt = kcount[p];
+        if (cnt == 0) {                                  // block-uniform
+            ++p;
+            continue;
+        }
+        const int u_lo = (int)(pos - prefix[p]);
+        const int64_t room = end - pos;
+        const int u_hi = (u_lo + room < cnt + ovh) ? (int)(u_lo + room) : cnt + ovh;
+        const int lo = u_lo > ovh ? u_lo - ovh : 0;
+        const int hi = u_hi > ovh ? u_hi - ovh : 0;
+        if (hi > lo) {
+            const int tm = p % tiles_m, tn = p / tiles_m;
+            f32x16 acc[4][2];
+            tile_zero(acc);
+            const float* Ablk = A + (int64_t)tm * 256 * lda;
+            if (fb.mat == nullptr || fb.mat[tn]) {       // block-uniform: fp32 rows from B
+                const int bt = (fb.mat != nullptr && fb.ctile != nullptr) ? fb.ctile[tn] : tn;
+                tile_run_split(t, lds, Ablk, lda, B + (int64_t)bt * 256 * ldb, ldb, false, nullptr, nullptr, nullptr, 0, 0.f,
+                               klist + (int64_t)p * k_tiles, lo, hi, acc);
+            } else {
+                const int r0 = tn * 256;
+                const int g = r0 / fb.V, v0 = r0 - g * fb.V;
+                tile_run_split(t, lds, Ablk, lda, nullptr, 0, true, fb.rs + (int64_t)(g / fb.O) * fb.S_pad,
+                               fb.rto + (int64_t)g * fb.S_pad, fb.alpha + (int64_t)(v0 + (threadIdx.x >> 2)) * fb.lda,
+                               (int64_t)128 * fb.lda, fb.gamma, klist + (int64_t)p * k_tiles, lo, hi, acc);
+            }
+            const bool cont = L != first_block[p];
+            tile_store(t, cont ? C + slab_stride + (int64_t)L * (256 * 256) : C, cont ? 256 : ldc, cont ? 0 : tm, cont ? 0 : tn, acc);
+        }
+        pos += u_hi - u_lo;
+        ++p;
+    }
+}
+
+// One wave: does the split path keep subnormal lo parts and subnormal products?  out[0] = 1 if
+//   x = (1 + 2^-7) 2^-120 + 2^-132 (a bf16-subnormal lo) times 1 comes back as x, and 2^-100 * 2^-30 as 2^-130.
+__global__ void k_split_probe(float* out) {
+    const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
+    float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, b[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const float x = 0x1.02p-120f + 0x1p-132f;
+    if (h == 0) {
+        a[0] = x;                                        // A[r][0]
+        a[1] = 0x1p-100f;                                // A[r][1]
+        if (r == 0) b[0] = 1.f;                          // B[0][0]
+        if (r == 1) b[1] = 0x1p-30f;                     // B[1][1]
+    }
+    i32x4 ah, al, bh, bl;
+    uint32_t hh, ll;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        split_pair(a[2 * p], a[2 * p + 1], hh, ll); ah[p] = (int)hh; al[p] = (int)ll;
+        split_pair(b[2 * p], b[2 * p + 1], hh, ll); bh[p] = (int)hh; bl[p] = (int)ll;
+    }
+    f32x16 acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah), __builtin_bit_cast(bf16x8, bh), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah), __builtin_bit_cast(bf16x8, bl), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, al), __builtin_bit_cast(bf16x8, bh), acc, 0, 0, 0);
+    // C[0][c] sits in register 0 of lane c (h = 0)
+    if (lane < 2) out[lane] = acc[0];
+    if (lane == 0) out[2] = x;
+}
+
+// Probed once per device (engine creation), on a stream of its own; the result is cached under a lock.
+int gemm_split_supported(int device) {
+    static std::mutex mu;
+    static std::map<int, int> known;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = known.find(device);
+    if (it != known.end()) return it->second;
+    int ok = 0;
+    float* d = nullptr;
+    hipStream_t st = nullptr;
+    float h[3] = {0.f, 0.f, 0.f};
+    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess && hipMalloc((void**)&d, sizeof(h)) == hipSuccess) {
+        hipLaunchKernelGGL(k_split_probe, dim3(1), dim3(64), 0, st, d);
+        if (hipGetLastError() == hipSuccess && hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, st) == hipSuccess &&
+            hipStreamSynchronize(st) == hipSuccess)
+            ok = (h[0] == h[2] && h[1] == 0x1p-130f) ? 1 : 0;
+    }
+    (void)hipGetLastError();
+    if (d != nullptr) (void)hipFree(d);
+    if (st != nullptr) (void)hipStreamDestroy(st);
+    known[device] = ok;
+    return ok;
+}
+
+// --------------------------------------------------------------------------- //
 // Zero-tile bookkeeping
 // --------------------------------------------------------------------------- //
 // nz[tile][kt] = 1 iff the 256-row x 32-column block of X has a non-zero entry.
@@ -883,6 +1189,8 @@ static hipError_t set_lds_attr() {
     e = hipFuncSetAttribute((const void*)k_gemm_nt_f32_streamk_fused, hipFuncAttributeMaxDynamicSharedMemorySize,
                             GEMM_LDS_BYTES);
     if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute((const void*)k_gemm_split_streamk, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
+    if (e != hipSuccess) return e;
 #define PBVI_FUSED_R_ATTR(RR)                                                                                          \
     e = hipFuncSetAttribute((const void*)k_gemm_nt_f32_streamk_fused_r<RR>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                             GEMM_LDS_BYTES_R);                                                                          \
@@ -897,7 +1205,7 @@ hipError_t launch_gemm_nt_f32(const float* A, int lda, const float* B, int ldb, 
                               const uint8_t* nzA, const uint8_t* nzB, int G, int v_group, int n_rows, int* klist,
                               int* kcount, int* nchunks, hipStream_t stream, int batch, int64_t batch_stride_b,
                               int64_t batch_stride_c, int* streamk_ws, hipStream_t list_stream, hipEvent_t list_event,
-                              hipEvent_t ev_before, hipEvent_t ev_after, const FusedB* fused) {
+                              hipEvent_t ev_before, hipEvent_t ev_after, const FusedB* fused, int split) {
     hipError_t e = set_lds_attr();
     if (e != hipSuccess) return e;
     if (batch < 1 || batch > 65535) return hipErrorInvalidValue;
@@ -907,6 +1215,7 @@ hipError_t launch_gemm_nt_f32(const float* A, int lda, const float* B, int ldb, 
     // list_stream they are built beside whatever `stream` is still doing (the Gamma projection) and the GEMM waits.
     hipStream_t ls = (list_stream != nullptr && list_event != nullptr) ? list_stream : stream;
     if (fused != nullptr && !pl.streamk) return hipErrorInvalidValue;
+    if (split && (!pl.streamk || (fused != nullptr && fused->R != 1))) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_build_klists, dim3(pairs, batch), dim3(256), 0, ls, nzA, nzB, G, v_group, n_rows,
                        pl.tiles_m, pl.k_tiles, pl.chunk_len, force_dense, klist, kcount, nchunks,
                        fused != nullptr ? fused->irr : nullptr, fused != nullptr ? fused->O : 1);
@@ -927,7 +1236,13 @@ hipError_t launch_gemm_nt_f32(const float* A, int lda, const float* B, int ldb, 
             if ((e = hipEventRecord(list_event, ls)) != hipSuccess) return e;
             if ((e = hipStreamWaitEvent(stream, list_event, 0)) != hipSuccess) return e;
         }
-        if (fused != nullptr && fused->R > 1) {
+        if (split) {
+            FusedB fb{};
+            if (fused != nullptr) fb = *fused;           // (else fb.mat == nullptr: every B tile from fp32 rows)
+            hipLaunchKernelGGL(k_gemm_split_streamk, dim3(pl.nblocks), dim3(512), GEMM_LDS_BYTES, stream, A, lda, B, ldb, fb, C,
+                               pl.ldc, pl.slab_stride, pl.tiles_m, pairs, pl.k_tiles, klist, kcount, prefix, start_pair,
+                               first_block, plan, ovh);
+        } else if (fused != nullptr && fused->R > 1) {
             switch (fused->R) {
 #define PBVI_FUSED_R_CASE(RR)                                                                                                   \
     case RR:                                                                                                                    \

@@ -33,7 +33,7 @@ EXPORTS = [
     'pbvi_value_max_store', 'pbvi_belief_store_count', 'pbvi_alpha_store_count', 'pbvi_set_value_max_exact', 'pbvi_alpha_layout',
     'pbvi_belief_walk_keys', 'pbvi_backup_fetch_value_max',
     'pbvi_backup_fetch_compact', 'pbvi_host_alloc', 'pbvi_host_free', 'pbvi_debug_gemm_dense',
-    'pbvi_backup_fetch_exchange_padded', 'pbvi_assemble_rows_store', 'pbvi_exchange_merge', 'pbvi_backup_run_fetch', 'pbvi_debug_alloc_limit', 'pbvi_engine_after_oom', 'pbvi_set_f64_screen', 'pbvi_set_fused_projection', 'pbvi_backup_fetch_row_hashes',
+    'pbvi_backup_fetch_exchange_padded', 'pbvi_assemble_rows_store', 'pbvi_exchange_merge', 'pbvi_backup_run_fetch', 'pbvi_debug_alloc_limit', 'pbvi_engine_after_oom', 'pbvi_set_f64_screen', 'pbvi_set_fused_projection', 'pbvi_backup_fetch_row_hashes', 'pbvi_set_score_split',
 ]
 
 
@@ -50,7 +50,8 @@ class PbviStats(C.Structure):
                 ('score_flops', C.c_int64), ('score_flops_executed', C.c_int64), ('score_tiles_dense', C.c_int64),
                 ('score_tiles_run', C.c_int64), ('project_flops', C.c_int64), ('project_flops_executed', C.c_int64),
                 ('split_k', C.c_int32), ('formulation', C.c_int32), ('n_refine_candidates', C.c_int64),
-                ('ms_project_gemm', C.c_double), ('screened', C.c_int32), ('fused_projection', C.c_int32)]
+                ('ms_project_gemm', C.c_double), ('screened', C.c_int32), ('fused_projection', C.c_int32),
+                ('score_split', C.c_int32)]
 
     def as_dict(self) -> dict:
         return {name: getattr(self, name) for name, _ in self._fields_}
@@ -120,6 +121,7 @@ def load_library(path: str = LIB_PATH):
         'pbvi_set_formulation': (C.c_int, [vp, C.c_int]),
         'pbvi_set_f64_screen': (C.c_int, [vp, C.c_int]),
         'pbvi_set_fused_projection': (C.c_int, [vp, C.c_int]),
+        'pbvi_set_score_split': (C.c_int, [vp, C.c_int]),
         'pbvi_belief_walk': (C.c_int64, [vp, f64p, C.c_int64, i32p, i32p, u8p, f64p]),
         'pbvi_engine_set_rto_f64': (C.c_int, [vp, f64p]),
         'pbvi_backup_fetch_unique_keys': (C.c_int, [vp, vp]),
@@ -1023,6 +1025,11 @@ class Engine:
         """fp64 engines: ``'off'`` (pure fp64 arithmetic), ``'auto'`` (fp32 screen + fp64 re-decision of near-ties when the
         score GEMM is large; default) or ``'always'`` (``pbvi_set_f64_screen``)."""
         self._ck(self._lib.pbvi_set_f64_screen(self._h, {'off': 0, 'auto': 1, 'always': 2}[mode]))
+
+    def set_score_split(self, mode: str = 'auto') -> None:
+        """fp32 engines: backup scores from bf16 MFMAs on a three-term operand split with a widened tie window (same
+        results): ``'off'``, ``'auto'`` (when the score GEMM is large; default) or ``'always'`` (``pbvi_set_score_split``)."""
+        self._ck(self._lib.pbvi_set_score_split(self._h, {'off': 0, 'auto': 1, 'always': 2}[mode]))
 
     def set_tie_window(self, rel: float) -> None:
         self._ck(self._lib.pbvi_set_tie_window(self._h, float(rel)))

@@ -24,9 +24,10 @@ run screen_always PBVI_F64_SCREEN=always
 run screen_off PBVI_F64_SCREEN=off
 run poison PBVI_POISON=1
 run no_l1 PBVI_NO_L1_SCREEN=1
+run split_always PBVI_SCORE_SPLIT=always
 echo "" >> $O/summary.md
 echo "## failed / skipped tests per mode" >> $O/summary.md
-for f in default belief nofuse screen_always screen_off poison no_l1; do
+for f in default belief nofuse screen_always screen_off poison no_l1 split_always; do
   echo "" >> $O/summary.md
   echo "### $f" >> $O/summary.md
   echo '```' >> $O/summary.md
