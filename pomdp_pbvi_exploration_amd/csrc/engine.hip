@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "backup_kernels.h"
+#include "split_bf16.h"
 
 namespace pbvi {
 
@@ -424,10 +425,12 @@ __global__ void k_rank_sort(const int32_t* __restrict__ key, int B, int32_t* __r
 // dst row y = src row ids[perm[y]] (either map may be null), 16 bytes per lane; ld is a multiple of 32 elements
 __device__ __forceinline__ void tile_or_block(const uint8_t* __restrict__ flags, const int32_t* __restrict__ perm, int B, int k_tiles,
                                               uint8_t* __restrict__ nz, int bx, int tile);
+// plane != nullptr (fp32): the rows' split plane too (split_bf16.h), from the same registers
 template <typename T>
 __global__ void k_gather_rows_v(const T* __restrict__ src, T* __restrict__ dst, int ld, const int32_t* __restrict__ perm,
                                 const int32_t* __restrict__ ids, const uint8_t* __restrict__ flags = nullptr, int B = 0,
-                                int k_tiles = 0, uint8_t* __restrict__ nz = nullptr, int or_rows = 0) {
+                                int k_tiles = 0, uint8_t* __restrict__ nz = nullptr, int or_rows = 0,
+                                uint32_t* __restrict__ plane = nullptr) {
     // The first or_rows rows of the grid build the block's zero map (they need the order only, like the
     // gather): as a kernel of its own in front of the gather it was 14 us on the path to the score GEMM.
     if ((int)blockIdx.y < or_rows) {
@@ -442,7 +445,29 @@ __global__ void k_gather_rows_v(const T* __restrict__ src, T* __restrict__ dst, 
     int r = row;
     if (perm) r = perm[r];
     if (ids) r = ids[r];
-    *(TN*)(dst + (int64_t)row * ld + (int64_t)c * NS) = *(const TN*)(src + (int64_t)r * ld + (int64_t)c * NS);
+    const TN v = *(const TN*)(src + (int64_t)r * ld + (int64_t)c * NS);
+    *(TN*)(dst + (int64_t)row * ld + (int64_t)c * NS) = v;
+    if constexpr (NS == 4) {
+        if (plane != nullptr) {                           // chunk c = states 4j .. 4j+3 of K tile c / 8, j = c & 7
+            uint2 hi, lo;
+            split_quad(v[0], v[1], v[2], v[3], hi, lo);
+            uint32_t* pw = plane + (int64_t)row * ld + (c >> 3) * GEMM_BK + 2 * (c & 7);
+            *(uint2*)pw = hi;
+            *(uint2*)(pw + 16) = lo;
+        }
+    }
+}
+
+// The split plane (split_bf16.h) of n floats of rows whose length is a multiple of GEMM_BK, 16 bytes per lane
+__global__ void k_split_plane(const float* __restrict__ x, uint32_t* __restrict__ plane, int64_t n) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c * 4 >= n) return;
+    const float4 v = *(const float4*)(x + c * 4);
+    uint2 hi, lo;
+    split_quad(v.x, v.y, v.z, v.w, hi, lo);
+    uint32_t* pw = plane + (c >> 3) * GEMM_BK + 2 * (c & 7);
+    *(uint2*)pw = hi;
+    *(uint2*)(pw + 16) = lo;
 }
 
 // nz[tile][kt] = OR of flags[perm[r]][kt] over the rows r of the 256-row tile (rows >= B are padding).  Block =
@@ -728,6 +753,8 @@ class EngineT : public EngineBase {
     int64_t V_ = 0;
     DevBuf bel_;
     int64_t B_ = 0, B_pad_ = 0;
+    DevBuf belsp_;                                           // fp32: bel_'s split plane for the split score GEMM (split_bf16.h)
+    uint64_t belsp_ver_ = 0;                                 // the bel_ version belsp_ holds (0: none)
     DevBuf gam_, slabs_, best_v_, best_score_, err_, dead_, queue_, counters_, rdot_, action_, aqueue_, out_, keep_;
     DevBuf bv2_, bs2_, err2_, queue2_, prune_cnt_;
     DevBuf stage_, keys_, perm_, action_res_, best_res_;   // belief reordering (f32, B > 256)
@@ -835,7 +862,7 @@ class EngineT : public EngineBase {
             delete screen_;
             screen_ = nullptr;
         }
-        DevBuf* all[] = {&rs_, &rto_, &er_, &sup_, &alpha_buf_, &alpha_small_, &bel_, &gam_, &slabs_, &best_v_, &best_score_, &err_,
+        DevBuf* all[] = {&rs_, &rto_, &er_, &sup_, &alpha_buf_, &alpha_small_, &bel_, &belsp_, &gam_, &slabs_, &best_v_, &best_score_, &err_,
                          &dead_, &queue_, &counters_, &rdot_, &action_, &aqueue_, &out_, &keep_, &bv2_, &bs2_,
                          &err2_, &queue2_, &prune_cnt_, &nzB_, &nzA_, &klist_, &kcount_, &nchunks_, &need_, &skws_, &stage_, &keys_, &perm_,
                          &action_res_, &best_res_, &rep_, &uniq_, &inv_, &slot_, &out_full_, &btl_, &btc_, &val_exact_, &store_[0], &store_[1], &ids_, &in_ptr_, &in_src_, &bu_act_, &bu_obs_,
@@ -1183,6 +1210,12 @@ class EngineT : public EngineBase {
         if ((rc = perm_.ensure((size_t)B * sizeof(int32_t), &bytes_))) return rc;
         if ((rc = nzA_.ensure((size_t)(Bp / GEMM_BM) * k_tiles, &bytes_))) return rc;
         if (Bp > B) HIPCHK(hipMemsetAsync(bel_.as<T>() + (size_t)B * S_pad_, 0, (size_t)(Bp - B) * S_pad_ * sizeof(T), stream_));
+        // the split plane rides along with the gather once score_gemm has allocated it (the first split backup)
+        uint32_t* plane = nullptr;
+        if (kF32 && split_mode_ != 0 && split_supported_ && belsp_.cap >= (size_t)Bp * S_pad_ * sizeof(float)) {
+            plane = belsp_.as<uint32_t>();
+            if (Bp > B) HIPCHK(hipMemsetAsync(plane + (size_t)B * S_pad_, 0, (size_t)(Bp - B) * S_pad_ * sizeof(float), stream_));
+        }
         static const bool no_sort = getenv("PBVI_NO_BELIEF_SORT") != nullptr;     // debug / A-B only
         sorted_ = B > (kF32 ? GEMM_BM : 128) && !no_sort;     // more than one row block of the score GEMM
         hipLaunchKernelGGL(k_row_flags<T>, dim3((unsigned)B), dim3(256), 0, stream_, src, S_pad_, src_ids, S_pad_, k_tiles,
@@ -1199,7 +1232,8 @@ class EngineT : public EngineBase {
         constexpr int NS = 16 / (int)sizeof(T);
         const int or_rows = (int)(Bp / GEMM_BM);
         hipLaunchKernelGGL(k_gather_rows_v<T>, dim3((S_pad_ / NS + 255) / 256, (unsigned)(B + or_rows)), dim3(256), 0, stream_, src,
-                           bel_.as<T>(), S_pad_, perm, src_ids, rowflags_.as<uint8_t>(), (int)B, k_tiles, nzA_.as<uint8_t>(), or_rows);
+                           bel_.as<T>(), S_pad_, perm, src_ids, rowflags_.as<uint8_t>(), (int)B, k_tiles, nzA_.as<uint8_t>(), or_rows,
+                           plane);
         HIPCHK(hipGetLastError());
         if (!ev_nzA_) HIPCHK(hipEventCreateWithFlags(&ev_nzA_, hipEventDisableTiming));
         HIPCHK(hipEventRecord(ev_nzA_, stream_));
@@ -1208,6 +1242,7 @@ class EngineT : public EngineBase {
         ++bel_ver_;
         rowflags_ver_ = bel_ver_;
         nzA_ver_ = bel_ver_;
+        belsp_ver_ = plane != nullptr ? bel_ver_ : 0;
         h_perm_valid_ = false;
         have_result_ = false;
         btl_valid_ = false;
@@ -1608,7 +1643,7 @@ class EngineT : public EngineBase {
         (void)hipStreamSynchronize(stream_);
         if (stream2_) (void)hipStreamSynchronize(stream2_);
         if (stream3_) (void)hipStreamSynchronize(stream3_);
-        DevBuf* drop[] = {&alpha_buf_, &alpha_small_, &bel_, &gam_, &slabs_, &best_v_, &best_score_, &err_, &dead_, &queue_, &rdot_,
+        DevBuf* drop[] = {&alpha_buf_, &alpha_small_, &bel_, &belsp_, &gam_, &slabs_, &best_v_, &best_score_, &err_, &dead_, &queue_, &rdot_,
                           &action_, &aqueue_, &out_, &keep_, &bv2_, &bs2_, &err2_, &queue2_, &prune_cnt_, &nzA_, &klist_, &kcount_,
                           &nchunks_, &need_, &skws_, &stage_, &keys_, &perm_, &action_res_, &best_res_, &rep_, &uniq_, &inv_, &slot_,
                           &out_full_, &btl_, &btc_, &val_exact_, &store_[0], &store_[1], &ids_, &bu_act_, &bu_obs_, &bu_unnorm_,
@@ -1638,6 +1673,7 @@ class EngineT : public EngineBase {
         last_deferred_nothing_ = false;
         ++alpha_ver_;
         ++bel_ver_;
+        belsp_ver_ = 0;
         if (screen_) {
             screen_alpha_seen_ = screen_bel_seen_ = 0;
             screen_layout_seen_ = 0;
@@ -2343,6 +2379,25 @@ class EngineT : public EngineBase {
         const int64_t dense_steps = (B_pad_ / GEMM_BM) * (n_rows_alloc / GEMM_BN) * (int64_t)k_tiles;
         return dense_steps >= kSplitMinSteps;
     }
+    // fp32: bring the resident block's split plane up to date (allocated on first use, rebuilt from bel_ when a path that
+    // changes bel_ did not write it).  false: it does not fit (the caller keeps the fp32 GEMM).  The split kernel addresses
+    // 256 rows of the plane with 32-bit byte offsets, hence the bound on S_pad.
+    bool split_plane() {
+        const size_t bytes = (size_t)B_pad_ * S_pad_ * sizeof(float);
+        if (bytes == 0 || S_pad_ > (1 << 22)) return false;
+        if (belsp_.cap < bytes) {
+            if (!DevBuf::headroom_ok(bytes_, bytes) || belsp_.ensure(bytes, &bytes_) != PBVI_OK) return false;
+            belsp_ver_ = 0;
+        }
+        if (belsp_ver_ != bel_ver_) {
+            const int64_t n = (int64_t)B_pad_ * S_pad_;
+            hipLaunchKernelGGL(k_split_plane, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, stream_, bel_.as<float>(),
+                               belsp_.as<uint32_t>(), n);
+            if (hipGetLastError() != hipSuccess) return false;
+            belsp_ver_ = bel_ver_;
+        }
+        return true;
+    }
     // fp64 engines: MFMA GEMM unless the problem is a handful of tiles (the plain kernel is as good there)
     static bool f64_uses_mfma(int64_t m_rows, int64_t n_rows) {
         static const bool simple = getenv("PBVI_F64_SIMPLE") != nullptr;      // debug / A-B only
@@ -2396,6 +2451,7 @@ int EngineT<T>::score_gemm(const T* Y, int64_t rows_y, const uint8_t* nzB, int G
     int rc;
     const int64_t m_rows = X ? x_rows : B_;
     const int64_t m_pad = X ? round_up(x_rows, GEMM_BM) : B_pad_;
+    const bool own_block = X == nullptr;
     if (!X) {
         X = bel_.as<T>();
         nzX = nzA_.as<uint8_t>();
@@ -2410,9 +2466,10 @@ int EngineT<T>::score_gemm(const T* Y, int64_t rows_y, const uint8_t* nzB, int G
         if ((rc = kcount_.ensure(pairs * sizeof(int), &bytes_))) return rc;
         if ((rc = nchunks_.ensure(pairs * sizeof(int), &bytes_))) return rc;
         if ((rc = skws_.ensure(streamk_workspace_ints(plan_) * sizeof(int), &bytes_))) return rc;
-        const int sp = split != nullptr && *split && plan_.streamk && (fused == nullptr || fused->R == 1) ? 1 : 0;
+        int sp = split != nullptr && *split && plan_.streamk && (fused == nullptr || fused->R == 1) ? 1 : 0;
+        if (sp && (!own_block || !split_plane())) sp = 0;      // no plane: the fp32 GEMM (same outputs)
         if (split != nullptr) *split = sp;
-        HIPCHK(launch_gemm_nt_f32((const float*)X, S_pad_, (const float*)Y, S_pad_, slabs_.as<float>(), plan_,
+        HIPCHK(launch_gemm_nt_f32(sp ? belsp_.as<float>() : (const float*)X, S_pad_, (const float*)Y, S_pad_, slabs_.as<float>(), plan_,
                                   nzX, nzB, G, v_group, (int)rows_y, klist_.as<int>(), kcount_.as<int>(),
                                   nchunks_.as<int>(), stream_, 1, 0, 0, skws_.as<int>(), list_stream, ev_lists_, nullptr, nullptr,
                                   fused, sp));

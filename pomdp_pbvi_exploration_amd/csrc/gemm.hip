@@ -26,6 +26,7 @@
 //    so equal shares of listed tile-steps is what balances the chip.  A pair split over several blocks
 //    leaves one partial slab per block; the consumer sums them in a fixed order (deterministic).
 #include "pbvi_common.h"
+#include "split_bf16.h"
 
 #include <cstdlib>
 #include <map>
@@ -748,29 +749,16 @@ __global__ __launch_bounds__(512) void k_gemm_nt_f32_streamk_fused_r(
 // the fp32 instruction.  Per product |b*g - (bh*gh + bh*gl + bl*gh)| <= (3u^2 + 2u^3)|b||g|, u = 2^-8; the engine widens
 // the tie window by that (numerics).  A finite |x| above the largest finite bf16 (where RNE would give inf)
 // takes hi = +-max bf16 instead, which keeps the same bound within 1 %.
-// Both operands are loaded to registers, split there and written to LDS: a 256-row x 32-k stage of (hi, lo) is 32 KiB,
-// the size of an fp32 stage, so the double buffer and the source-side XOR swizzle carry over -- LDS row r holds 8 chunks
+// A 256-row x 32-k stage of (hi, lo) is 32 KiB, the size of an fp32 stage, so the double buffer and the source-side XOR
+// swizzle carry over -- LDS row r holds 8 chunks
 // of 8 bf16: hi k 0-7, 8-15, 16-23, 24-31, then lo in the same order, chunk c at physical chunk c ^ ((r>>1)&7).  Lane
 // (i, h) of the k-half kk reads hi chunk 2kk+h and lo chunk 4+2kk+h of its rows: k = 16kk + 8h + j, the MFMA's own order.
-// The B operand is generated (scheduler 2b's arithmetic, then split) or read from fp32 rows in HBM; the two routes write
-// the same LDS image, so they issue the same MFMAs on the same bits.  Plan, lists, slabs: unchanged.
+// The belief operand arrives pre-split: the engine keeps a split plane of the block (split_bf16.h), written once per block
+// with the same split code, and it is staged by LDS-DMA.  The B operand is generated (scheduler 2b's arithmetic, then
+// split) or read from fp32 rows in HBM and split in registers; the two routes write the same LDS image, so they issue the
+// same MFMAs on the same bits.  Plan, lists, slabs: unchanged.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-__device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b) {
-    uint32_t r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));    // a -> bits 0-15, b -> bits 16-31, RNE
-    return r;
-}
-__device__ __forceinline__ float bf16_sat(float x) {
-    const float m = 0x1.fep127f;                                        // largest finite bf16
-    return fabsf(x) > m ? copysignf(m, x) : x;                          // (a NaN stays a NaN)
-}
-__device__ __forceinline__ void split_pair(float x0, float x1, uint32_t& hi, uint32_t& lo) {
-#pragma clang fp contract(off)
-    hi = cvt_pk_bf16(bf16_sat(x0), bf16_sat(x1));
-    const float h0 = __uint_as_float(hi << 16), h1 = __uint_as_float(hi & 0xffff0000u);
-    lo = cvt_pk_bf16(x0 - h0, x1 - h1);
-}
 // 8 consecutive k of one row (x0: k 0-3, x1: k 4-7) -> hi and lo chunks of that row's LDS image
 __device__ __forceinline__ void split_store(float* lop, int row, int kg, const f32x4& x0, const f32x4& x1) {
     i32x4 hi, lo;
@@ -784,68 +772,94 @@ __device__ __forceinline__ void split_store(float* lop, int row, int kg, const f
     *(i32x4*)(lop + row * GEMM_BK + ((4 + kg) ^ sw) * 4) = lo;
 }
 
-__device__ __forceinline__ void split_compute(const TileThread& t, const float* lds, int buf, f32x16 (&acc)[4][2]) {
+// Fragments of one k-half of the staged tile pair: the hi and lo chunks of the wave's 4 A rows and 2 B rows
+struct SplitFrag {
+    i32x4 ah[4], al[4], bh[2], bl[2];
+};
+// Term `term` of k-half kk over the wave's 8 blocks, after reading the fragments it is the first to need (term 0: ah, bh;
+// 1: bl; 2: al -- at most 32 fragment VGPRs live instead of 48).  Per element the order is fixed: + bh*gh, + bh*gl,
+// + bl*gh, then the next k-half (term-major over the 8 blocks: no dependent pairs back to back).
+__device__ __forceinline__ void split_group(const TileThread& t, const float* lds, int buf, int kk, int term, SplitFrag& f,
+                                            f32x16 (&acc)[4][2]) {
     const float* la = lds + buf * 2 * TILE_FLOATS;
     const float* lb = la + TILE_FLOATS;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-        i32x4 ah[4], al[4], bh[2], bl[2];
+    const int hc = 2 * kk + t.h;                          // logical chunk of the hi part; lo: 4 + hc
+    if (term != 1) {
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi) {
             const int r = t.a_row[mi], sw = (r >> 1) & 7;
-            ah[mi] = *(const i32x4*)(la + r * GEMM_BK + ((2 * kk + t.h) ^ sw) * 4);
-            al[mi] = *(const i32x4*)(la + r * GEMM_BK + ((4 + 2 * kk + t.h) ^ sw) * 4);
+            if (term == 0) f.ah[mi] = *(const i32x4*)(la + r * GEMM_BK + (hc ^ sw) * 4);
+            else f.al[mi] = *(const i32x4*)(la + r * GEMM_BK + ((4 + hc) ^ sw) * 4);
         }
+    }
+    if (term != 2) {
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni) {
             const int r = t.b_row[ni], sw = (r >> 1) & 7;
-            bh[ni] = *(const i32x4*)(lb + r * GEMM_BK + ((2 * kk + t.h) ^ sw) * 4);
-            bl[ni] = *(const i32x4*)(lb + r * GEMM_BK + ((4 + 2 * kk + t.h) ^ sw) * 4);
+            if (term == 0) f.bh[ni] = *(const i32x4*)(lb + r * GEMM_BK + (hc ^ sw) * 4);
+            else f.bl[ni] = *(const i32x4*)(lb + r * GEMM_BK + ((4 + hc) ^ sw) * 4);
         }
-        // per element the order is fixed: + bh*gh, + bh*gl, + bl*gh (term-major over the 8 blocks: no dependent pairs back to back)
-#pragma unroll
-        for (int term = 0; term < 3; ++term)
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni) {
-                    const i32x4 a = term == 2 ? al[mi] : ah[mi];
-                    const i32x4 b = term == 1 ? bl[ni] : bh[ni];
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b),
-                                                                          acc[mi][ni], 0, 0, 0);
-                }
     }
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) {
+            const i32x4 a = term == 2 ? f.al[mi] : f.ah[mi];
+            const i32x4 b = term == 1 ? f.bl[ni] : f.bh[ni];
+            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b),
+                                                                  acc[mi][ni], 0, 0, 0);
+        }
 }
 
-// Multiply list entries [i0, i1) of one pair.  gen: the B tile is generated (rsrow / rtorow: the group's successor and RTO
-// rows; arow0: alpha row of this thread's first staging row; a_step: 128 rows of alpha); else it is read from Bblk.
-// Staging: thread tid takes k-group kg = tid & 3 (8 states) of rows it * 128 + (tid >> 2), it = 0, 1, of both operands.
-// Loads are inline assembly counted by explicit s_waitcnt (see ld16): per K step, in issue order, [4 table loads] + 4
-// belief loads + [4 Gamma row loads], then [the alpha loads, once the tables are in]; everything is waited for behind the
-// step's MFMAs, split and written to the other buffer.
-__device__ __forceinline__ void tile_run_split(const TileThread& t, float* lds, const float* Ablk, int lda, const float* Bblk,
+// Multiply list entries [i0, i1) of one pair.  Aplane: the belief rows' split plane (split_bf16.h), staged by LDS-DMA
+// exactly like an fp32 operand (tile_stage's source swizzle), so the A image needs no register pass.  gen: the B tile is
+// generated (rsrow / rtorow: the group's successor and RTO rows; arow0: alpha row of this thread's first staging row;
+// a_step: 128 rows of alpha); else it is read from the fp32 rows at Bblk.  B staging: thread tid takes k-group
+// kg = tid & 3 (8 states) of rows it * 128 + (tid >> 2), it = 0, 1, loads them to registers, splits them and writes both
+// halves of that row's LDS image.  Loads are inline assembly counted by explicit s_waitcnt (see ld16).  A K step is six
+// MFMA groups of 8 (k-half x term) that carry the latencies of the NEXT tile's operands, as in tile_run_fused; the
+// successor indices are loaded one step earlier still, so no dependent load chain sits inside a step (a step is only
+// ~3000 SIMD cycles, about two memory round trips):
+//   gen:  alphas + weights (tile k+1), indices (k+2), A DMA (k+1) | kk0 t0 | kk0 t1 | kk0 t2 | kk1 t0 | wait alphas;
+//         B rows 0-127 | kk1 t1 | B rows 128-255 | kk1 t2 | barrier
+//   else: B rows, A DMA | kk0 t0 | kk0 t1 | kk0 t2 | kk1 t0 | wait B rows; B rows 0-127 | kk1 t1 | B rows 128-255 | kk1 t2 |
+//         barrier
+__device__ __forceinline__ void tile_run_split(const TileThread& t, float* lds, const float* Aplane, int lda, const float* Bblk,
                                                int ldb, bool gen, const int32_t* __restrict__ rsrow,
                                                const float* __restrict__ rtorow, const float* __restrict__ arow0,
                                                int64_t a_step, float gamma, const int* __restrict__ kl, int i0, int i1,
                                                f32x16 (&acc)[4][2]) {
     const int tid = threadIdx.x;
     const int kg = tid & 3, r0 = tid >> 2;
-    f32x4 xa[2][2], xb[2][2];
+    f32x4 xb[2][2];
     i32x4 idx[2];
     f32x4 w[2];
-    auto load_rows = [&](f32x4 (&x)[2][2], const float* base, int ld, int entry) {
+    // A staging: one 32-bit lane offset from a block-uniform base (the engine keeps 256 rows of the plane under 4 GiB), so
+    // the loop keeps one VGPR of addresses instead of four 64-bit pointers
+    const uint32_t a_off = (uint32_t)(t.srow[0] * lda + t.scol[0]) * 4u;     // srow[it] = srow[0] + 64 it, same scol
+    auto stage_a = [&](int buf, int entry) {
+        const char* base = (const char*)(Aplane + (int64_t)(entry & KL_MASK) * GEMM_BK);
+        float* la = lds + buf * 2 * TILE_FLOATS;
+#pragma unroll
+        for (int it = 0; it < 4; ++it)
+            glds16((const float*)(base + (int64_t)it * 64 * lda * 4 + a_off), la + (it * 512 + t.wid * 64) * 4);
+    };
+    auto load_rows = [&](int entry) {
         const int k = (entry & KL_MASK) * GEMM_BK + kg * 8;
 #pragma unroll
         for (int it = 0; it < 2; ++it) {
-            const float* p = base + (int64_t)(it * 128 + r0) * ld + k;
-            ld16(x[it][0], p);
-            ld16(x[it][1], p + 4);
+            const float* p = Bblk + (int64_t)(it * 128 + r0) * ldb + k;
+            ld16(xb[it][0], p);
+            ld16(xb[it][1], p + 4);
         }
     };
-    auto tables = [&](int entry) {
+    auto indices = [&](int entry) {                     // successor indices: two K steps ahead of the tile's store
         const int s = (entry & KL_MASK) * GEMM_BK + kg * 8;
         ld16i(idx[0], rsrow + s);
         ld16i(idx[1], rsrow + s + 4);
+    };
+    auto weights = [&](int entry) {                     // RTO weights: with the alpha loads, one step ahead
+        const int s = (entry & KL_MASK) * GEMM_BK + kg * 8;
         ld16(w[0], rtorow + s);
         ld16(w[1], rtorow + s + 4);
     };
@@ -875,65 +889,81 @@ __device__ __forceinline__ void tile_run_split(const TileThread& t, float* lds, 
             }
         }
     };
-    auto store = [&](int buf) {
-        float* la = lds + buf * 2 * TILE_FLOATS;
-        float* lb = la + TILE_FLOATS;
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            split_store(la, it * 128 + r0, kg, xa[it][0], xa[it][1]);
-            if (gen)
-                split_store(lb, it * 128 + r0, kg, fused_value(gamma, w[0], xb[it][0]), fused_value(gamma, w[1], xb[it][1]));
-            else
-                split_store(lb, it * 128 + r0, kg, xb[it][0], xb[it][1]);
-        }
-    };
-    auto wait_all = [&]() {
-        asm volatile("s_waitcnt vmcnt(0)"
-                     : "+v"(xa[0][0]), "+v"(xa[0][1]), "+v"(xa[1][0]), "+v"(xa[1][1]), "+v"(xb[0][0]), "+v"(xb[0][1]),
-                       "+v"(xb[1][0]), "+v"(xb[1][1])::"memory");
+    auto store_b = [&](int buf, int it) {                 // rows it * 128 + r0
+        float* lb = lds + buf * 2 * TILE_FLOATS + TILE_FLOATS;
+        if (gen)
+            split_store(lb, it * 128 + r0, kg, fused_value(gamma, w[0], xb[it][0]), fused_value(gamma, w[1], xb[it][1]));
+        else
+            split_store(lb, it * 128 + r0, kg, xb[it][0], xb[it][1]);
     };
     // first tile of the segment: nothing to overlap with
     {
         const int e0 = kl[i0];
         if (gen) {
-            tables(e0);
-            asm volatile("s_waitcnt vmcnt(0)" : "+v"(idx[0]), "+v"(idx[1]), "+v"(w[0]), "+v"(w[1])::"memory");
+            indices(e0);
+            weights(e0);
+            asm volatile("s_waitcnt vmcnt(0)" : "+v"(idx[0]), "+v"(idx[1])::"memory");
             alphas(e0);
+            indices(i0 + 1 < i1 ? kl[i0 + 1] : 0);        // (unconditional: see the waits in the loop)
         } else {
-            load_rows(xb, Bblk, ldb, e0);
+            load_rows(e0);
         }
-        load_rows(xa, Ablk, lda, e0);
-        wait_all();
-        store(0);
+        stage_a(0, e0);
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(xb[0][0]), "+v"(xb[0][1]), "+v"(xb[1][0]), "+v"(xb[1][1]), "+v"(w[0]), "+v"(w[1]),
+                     "+v"(idx[0]), "+v"(idx[1])::"memory");
+        store_b(0, 0);
+        store_b(0, 1);
     }
-    int k_next = (i0 + 1 < i1) ? kl[i0 + 1] : 0;         // list entries are read one step ahead of their use
+    // list entries are read ahead of their use
+    int k_next = (i0 + 1 < i1) ? kl[i0 + 1] : 0;
+    int k_after = (i0 + 2 < i1) ? kl[i0 + 2] : 0;
     __syncthreads();
     int buf = 0;
     for (int it = i0; it < i1; ++it) {
-        int k_after = 0;
+        int k_after2 = 0;
         const bool more = it + 1 < i1;                    // block-uniform
-        if (more) {
-            if (gen) tables(k_next);                      // the 4 table loads first: they are waited for first
-            load_rows(xa, Ablk, lda, k_next);
-            if (!gen) load_rows(xb, Bblk, ldb, k_next);
-            if (it + 2 < i1) k_after = kl[it + 2];
-        }
-        split_compute(t, lds, buf, acc);
+        // Issue order (vector memory returns in order, so the waits below count): gen -- the next tile's alpha loads
+        // (their indices arrived during the previous step) and weights, the indices of the tile after it, then the 4 A
+        // DMA loads; else the 4 B row loads, then the 4 A DMA loads.
         if (more) {
             if (gen) {
-                asm volatile("s_waitcnt vmcnt(4)" : "+v"(idx[0]), "+v"(idx[1]), "+v"(w[0]), "+v"(w[1])::"memory");
                 alphas(k_next);
+                weights(k_next);
+                indices(k_after);                         // K tile 0 past the list's end: unused, but always 2 loads
+            } else {
+                load_rows(k_next);
             }
-            wait_all();
-            store(buf ^ 1);
+            stage_a(buf ^ 1, k_next);
+            if (it + 3 < i1) k_after2 = kl[it + 3];
         }
+        SplitFrag f;
+        split_group(t, lds, buf, 0, 0, f, acc);
+        split_group(t, lds, buf, 0, 1, f, acc);
+        split_group(t, lds, buf, 0, 2, f, acc);
+        split_group(t, lds, buf, 1, 0, f, acc);
+        // The waits take the loaded registers as operands, so nothing copies them before they arrive; a wait must not
+        // depend on a run-time condition (two asm statements would get operand copies placed ahead of the wait).
+        if (more) {
+            if (gen)                                      // alphas + weights in; the indices and the DMA may not be
+                asm volatile("s_waitcnt vmcnt(6)" : "+v"(xb[0][0]), "+v"(xb[0][1]), "+v"(xb[1][0]), "+v"(xb[1][1]), "+v"(w[0]),
+                             "+v"(w[1])::"memory");
+            else                                          // the B rows in; the DMA may not be
+                asm volatile("s_waitcnt vmcnt(4)" : "+v"(xb[0][0]), "+v"(xb[0][1]), "+v"(xb[1][0]), "+v"(xb[1][1])::"memory");
+            store_b(buf ^ 1, 0);
+        }
+        split_group(t, lds, buf, 1, 1, f, acc);
+        if (more) store_b(buf ^ 1, 1);
+        split_group(t, lds, buf, 1, 2, f, acc);
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(idx[0]), "+v"(idx[1])::"memory");
         __syncthreads();
         buf ^= 1;
         k_next = k_after;
+        k_after = k_after2;
     }
 }
 
-// fb.mat == nullptr: every B tile is read from fp32 rows (the projected route); else scheduler 2b's tiles (R = 1).
+// A: the belief block's split plane.  fb.mat == nullptr: every B tile is read from fp32 rows (the projected route); else
+// scheduler 2b's tiles (R = 1).
 __global__ __launch_bounds__(512) void k_gemm_split_streamk(
     const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb, FusedB fb, float* __restrict__ C, int ldc,
     int64_t slab_stride, int tiles_m, int pairs, int k_tiles, const int* __restrict__ klist, const int* __restrict__ kcount,

@@ -68,7 +68,8 @@ hipError_t launch_gemm_nt_f32(const float* A, int lda, const float* B, int ldb, 
                               hipStream_t list_stream = nullptr, hipEvent_t list_event = nullptr,
                               hipEvent_t ev_before = nullptr, hipEvent_t ev_after = nullptr,   // around the GEMM kernel (non-stream-K)
                               const FusedB* fused = nullptr, int split = 0);
-// split: bf16 MFMAs on the three-term operand split (gemm.hip, scheduler 2d; stream-K only, fused R = 1 or none).
+// split: bf16 MFMAs on the three-term operand split (gemm.hip, scheduler 2d; stream-K only, fused R = 1 or none).  A is
+// then the split plane of the A rows (split_bf16.h), not their fp32 values; nzA still describes the fp32 rows.
 // gemm_split_supported(device): 1 when that path keeps subnormal lo parts and products on the device (probed once each).
 int gemm_split_supported(int device);
 // fused: generate the B tiles that lie inside one row group (stream-K only); the others are read from B.
