@@ -91,6 +91,10 @@ typedef struct pbvi_stats {
                                 scoring, alpha-side formulation): ms_project then covers only the few projected rows */
     int32_t score_split;      /* 1 when the scores came from bf16 MFMAs on the three-term operand split (fp32 engines,
                                 alpha-side formulation; pbvi_set_score_split), 0 = fp32 MFMAs */
+    int32_t gamma_chunks;     /* alpha-side formulation: 1 = Gamma held whole (or compact: fused projection), n > 1 = Gamma
+                                tiled over the alpha set into n chunks (pbvi_set_gamma_tiling); 0 = belief-side call.  In a
+                                tiled call ms_project / ms_score are sums over the chunks and ms_argmax includes the
+                                chunks' fold passes */
 } pbvi_stats_t;
 
 /* Library / device queries. */
@@ -430,6 +434,39 @@ int pbvi_set_fused_projection(pbvi_engine_t* e, int enable);
  * PBVI_SCORE_SPLIT=off|auto|always in the environment sets the initial mode.  pbvi_stats_t.score_split reports it.
  */
 int pbvi_set_score_split(pbvi_engine_t* e, int mode);
+
+/*
+ * Gamma tiled over the alpha set (alpha-side formulation, sparse mode, engines that hold the projected rows in HBM: R > 1,
+ * fp64 scoring and its fp32 screen, R = 1 after pbvi_set_fused_projection(0)).  The alpha set is walked in chunks of
+ * chunk_rows rows: each chunk is projected into one chunk-sized Gamma buffer, multiplied, and its split-K partial slabs are
+ * folded (in the slab order the argmax uses) into a full-width score matrix [B][A*O*(V+1)+2A]; argmax, refinement, action
+ * stage, dedup and assembly then run once on that matrix, so first-max ties go to the lowest GLOBAL alpha index and the
+ * results are those of the untiled call.  The refinement's level-1 screen (it reads the projected rows) is off in a
+ * tiled call; the tie window is the widest over the chunks' GEMM plans.
+ *   mode 0 (default): never -- Gamma is held whole;  1: automatic -- only when Gamma and its score slabs do not fit what
+ *   the engine may still allocate (then, with the formulation on automatic, the cost model alone picks the side: the
+ *   belief side is no longer taken for memory);  2: always (tests, A/B runs).
+ *   chunk_rows: alpha rows per chunk, rounded up to a multiple of 4; 0 = as many as fit (pbvi_gamma_tiling_plan).
+ * A request that leaves one chunk runs the untiled path.  Ignored (pbvi_stats_t.gamma_chunks == 1) in dense mode and where
+ * Gamma is compact already (fused projection).  An fp64 engine forwards the setting to its fp32 screen.  -1 on bad
+ * arguments.  PBVI_GAMMA_TILING=off|auto|always[:rows] in the environment sets the initial mode.
+ */
+int pbvi_set_gamma_tiling(pbvi_engine_t* e, int mode, int64_t chunk_rows);
+/*
+ * The planner behind it: pure host arithmetic, callable with no GPU and no engine.  For a model of S states, A actions,
+ * O observations, V alpha-vectors against B beliefs, dtype 0 = fp32 / 1 = fp64 scoring, and budget_bytes of device memory
+ * for the scoring stage's buffers:
+ *   *chunk_rows in: 0 = choose (one chunk when everything fits, else the fewest equal chunks that fit), > 0 = use this
+ *               many rows (rounded up to a multiple of 4);  out: rows per chunk (a multiple of 4; >= V with one chunk)
+ *   *n_chunks   out: ceil(V / chunk_rows)
+ *   *bytes_needed out: an upper bound of the chunk's Gamma rows, its score slabs and GEMM tile lists, plus -- with more
+ *               than one chunk -- the full score matrix (one chunk needs none).  Non-decreasing in chunk_rows among tiled
+ *               plans.
+ * Returns 0, -1 on bad arguments, -2 (with a pbvi_last_error text) when the plan -- a 4-row chunk, if the planner
+ * chooses -- exceeds the budget.
+ */
+int pbvi_gamma_tiling_plan(int32_t S, int32_t A, int32_t O, int64_t V, int64_t B, int dtype, int64_t budget_bytes,
+                           int64_t* chunk_rows, int64_t* n_chunks, int64_t* bytes_needed);
 
 /* Tuning knob for f32 engines: relative half-width of the near-tie window that sends an
  * argmax to fp64 refinement (<= 0 restores the default derived from |S|). */

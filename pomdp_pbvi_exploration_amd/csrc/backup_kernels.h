@@ -131,6 +131,15 @@ hipError_t launch_argmax(SlabView<T> sv, int V, int G, int B, const uint8_t* dea
                          hipStream_t st, double tol_extra = 0.0 /* added to the relative window: input rounding of a screen */,
                          int split = 0 /* the scores came from the split bf16 GEMM: its window (score_window) */);
 
+// Gamma tiled over the alpha set: sums the split-K slabs of ONE chunk's score GEMM (sv: alpha rows [v0, v0 + Vc) scored as a
+// Vc-row alpha set, column g * Vc + v, then tail_cols = G + 2A magnitude / reward columns when this is the last chunk, else
+// 0) in SlabView's slab order and writes the scores to columns g * V + v0 + v (tail: G * V + ...) of dst [B][ldd], which
+// the later stages read as a single slab (fixed = 1).  chain (device, or nullptr): this GEMM's stream-K share size;
+// chain_max[0] keeps the largest seen (the caller zeroes it before the first chunk).
+template <typename T>
+hipError_t launch_fold_chunk(SlabView<T> sv, int B, int G, int Vc, int V, int v0, int tail_cols, T* dst, int64_t ldd,
+                             const int* chain, int* chain_max, hipStream_t st);
+
 // Work list of the refinement: entries with many near-tied candidates hand their (entry, candidate) pairs to a
 // grid-wide pass instead of scoring them one block per entry (device memory; items_v == nullptr: all in-block).
 struct RefineWork {

@@ -843,6 +843,80 @@ hipError_t launch_argmax(SlabView<T> sv, int V, int G, int B, const uint8_t* dea
 }
 
 // ------------------------------------------------------------------------- //
+// Gamma tiled over the alpha set (pbvi_set_gamma_tiling): the front half of k_argmax with a column scatter.  The score
+// GEMM of ONE chunk (alpha rows [v0, v0 + Vc), laid out as the Gamma of a Vc-row alpha set: column g * Vc + v, then --
+// read from the last chunk only -- the G magnitude and 2A reward columns) left split-K partial slabs; they are summed
+// in SlabView's fixed slab order and the finished score lands at column g * V + v0 + v (tail: G * V + ...) of the
+// full-width matrix dst [B][ldd] that k_argmax, the refinement and k_action_select then read as a single slab.
+// Bandwidth-bound: every slab value is read once and every score written once, 16 bytes per lane on fp32 slabs whose
+// groups are 4-column aligned (the last, ragged chunk and fp64 slabs go element-wise through SlabView::at).
+// chain_max[0] (stream-K share size, widest over the chunks so far) is kept by one thread: chunks are stream-ordered.
+// ------------------------------------------------------------------------- //
+template <typename T>
+__global__ void k_fold_chunk(SlabView<T> sv, int B, int G, int Vc, int V, int v0, int tail_cols, T* __restrict__ dst,
+                             int64_t ldd, const int* __restrict__ chain, int* __restrict__ chain_max) {
+    if (chain != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+        const int c = chain[0];
+        if (c > chain_max[0]) chain_max[0] = c;
+    }
+    const int64_t group_cols = (int64_t)G * Vc, n_cols = group_cols + tail_cols;
+    const int64_t j0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (j0 >= n_cols) return;
+    bool vec4 = false;
+    if constexpr (sizeof(T) == 4) vec4 = sv.nchunks != nullptr && (Vc & 3) == 0 && (sv.ldc & 3) == 0 && j0 + 3 < group_cols;
+    // destination of chunk column j
+    auto out_col = [&](int64_t j) -> int64_t {
+        if (j >= group_cols) return (int64_t)G * V + (j - group_cols);
+        const int64_t g = j / Vc;
+        return g * V + v0 + (j - g * Vc);
+    };
+    const int64_t d0 = out_col(j0);
+    for (int b = blockIdx.y; b < B; b += gridDim.y) {
+        T* drow = dst + (int64_t)b * ldd;
+        if (vec4) {
+            if constexpr (sizeof(T) == 4) {
+                typedef float F4 __attribute__((ext_vector_type(4)));
+                const float* p = (const float*)sv.slabs + (int64_t)b * sv.ldc + j0;
+                const int64_t pair = (j0 >> 8) * sv.tiles_m + (b >> 8);
+                const int n = sv.nchunks[pair];
+                F4 acc = {0.f, 0.f, 0.f, 0.f};
+                if (n > 0) acc = acc + *(const F4*)p;
+                if (n > 1) {
+                    if (sv.first_block != nullptr) {         // continuation tiles behind the full slab (SlabView)
+                        const float* x = (const float*)sv.slabs + sv.slab_stride + (int64_t)(sv.first_block[pair] + 1) * (256 * 256) +
+                                         (b & 255) * 256 + (j0 & 255);
+                        for (int z = 1; z < n; ++z, x += 256 * 256) acc = acc + *(const F4*)x;
+                    } else {
+                        for (int z = 1; z < n; ++z) acc = acc + *(const F4*)(p + (int64_t)z * sv.slab_stride);
+                    }
+                }
+                if (((d0 | ldd) & 3) == 0) {
+                    *(F4*)((float*)drow + d0) = acc;
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) drow[d0 + i] = acc[i];
+                }
+            }
+        } else {
+            for (int i = 0; i < 4 && j0 + i < n_cols; ++i) drow[out_col(j0 + i)] = sv.at(b, j0 + i);
+        }
+    }
+}
+
+template <typename T>
+hipError_t launch_fold_chunk(SlabView<T> sv, int B, int G, int Vc, int V, int v0, int tail_cols, T* dst, int64_t ldd,
+                             const int* chain, int* chain_max, hipStream_t st) {
+    const int64_t n_cols = (int64_t)G * Vc + tail_cols;
+    if (B <= 0 || n_cols <= 0) return hipSuccess;
+    if (Vc <= 0 || v0 < 0 || v0 + Vc > V || (int64_t)G * V + tail_cols > ldd || sv.push) return hipErrorInvalidValue;
+    const int64_t bx = (n_cols + 1023) / 1024;
+    if (bx > 0x7fffffff) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_fold_chunk<T>, dim3((unsigned)bx, (unsigned)(B < 65535 ? B : 65535)), dim3(256), 0, st, sv, B, G, Vc, V,
+                       v0, tail_cols, dst, ldd, chain, chain_max);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------- //
 // fp64 re-decision of a queued (belief, group): every candidate whose f32 score is
 // within the error window of the f32 maximum is re-scored exactly (f32 x f32 products
 // are exact in f64) and the first maximum of the exact scores wins.
@@ -2300,6 +2374,8 @@ hipError_t launch_walk_step(const double* base, ModelView<T> mv, const double* r
     template hipError_t launch_belief_tiles<T>(const T*, int, int, int, int, int32_t*, int32_t*, hipStream_t);         \
     template hipError_t launch_argmax<T>(SlabView<T>, int, int, int, const uint8_t*, double, double, const int*, int,  \
                                          int32_t*, double*, double*, int32_t*, int*, hipStream_t, double, int);        \
+    template hipError_t launch_fold_chunk<T>(SlabView<T>, int, int, int, int, int, int, T*, int64_t, const int*, int*,   \
+                                             hipStream_t);                                                             \
     template hipError_t launch_refine<T, T>(bool, SlabView<T>, int, int, int, const int32_t*, const int*, const T*, int, \
                                          const T*, int, ModelView<T>, double, const int32_t*, const int32_t*,          \
                                          const uint8_t*, int32_t*, double*, double*, int*, RefineWork, hipStream_t);   \

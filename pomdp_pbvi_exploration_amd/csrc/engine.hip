@@ -634,6 +634,68 @@ __global__ void k_match_rows(int AO, int O, const int* __restrict__ ucount, cons
     }
 }
 
+// Gamma tiled over the alpha set (pbvi_set_gamma_tiling): memory planning, pure host arithmetic (pbvi_gamma_tiling_plan).
+// Upper bounds of what the scoring stage allocates for a chunk of Vc alpha rows -- a chunk is scored as the Gamma of a
+// Vc-row alpha set, A*O*(Vc+1)+2A rows -- none of which depends on the device: the stream-K continuation tiles are counted
+// for 512 blocks (the grid is one block per CU), the fp64 K parts at their 64 MiB ceiling (gemm_f64_split).
+struct TilingPlan {
+    int64_t chunk_rows = 0, n_chunks = 0, bytes = 0;
+};
+static int64_t tiling_chunk_bytes(int64_t S_pad, int64_t AO, int64_t A, int64_t B, bool f32, int64_t Vc) {
+    const int64_t n = AO * (Vc + 1) + 2 * A, k_tiles = S_pad / GEMM_BK;
+    if (f32) {
+        const int64_t n_pad = round_up(n, GEMM_BN), m_pad = round_up(B, GEMM_BM), pairs = (m_pad / GEMM_BM) * (n_pad / GEMM_BN);
+        return n_pad * S_pad * 4                              // Gamma rows
+               + (m_pad * n_pad + (int64_t)512 * 256 * 256) * 4   // first slab + continuation tiles
+               + pairs * (k_tiles + 4) * 4 + 4096             // tile lists, counts, stream-K workspace
+               + AO * k_tiles;                                // need map
+    }
+    const int64_t pairs = ((B + 127) / 128) * ((n + 127) / 128 + 4);
+    return n * S_pad * 8 + std::max<int64_t>((int64_t)64 << 20, B * n * 8) + pairs * (k_tiles + 35) * 4 + (k_tiles + 2) * 4 +
+           AO * k_tiles;
+}
+static int64_t tiling_matrix_bytes(int64_t AO, int64_t A, int64_t V, int64_t B, bool f32) {
+    return B * round_up(AO * (V + 1) + 2 * A, 4) * (f32 ? 4 : 8);
+}
+// want_rows 0: one chunk when the whole fits, else the fewest equal chunks that fit.  PBVI_OK, PBVI_EINVAL, PBVI_ENOMEM.
+static int tiling_plan(int64_t S, int64_t A, int64_t O, int64_t V, int64_t B, bool f32, int64_t budget, int64_t want_rows,
+                       TilingPlan* out) {
+    if (S <= 0 || A <= 0 || O <= 0 || V <= 0 || B <= 0 || budget < 0 || want_rows < 0 || A * O > 0x7fffffff ||
+        S > 0x7fffffff - GEMM_BK)
+        return PBVI_EINVAL;
+    const int64_t S_pad = round_up(S, GEMM_BK), AO = A * O;
+    if ((double)AO * (double)(V + 1) + 2.0 * A > 2147483647.0) return PBVI_EINVAL;
+    const int64_t matrix = tiling_matrix_bytes(AO, A, V, B, f32);
+    auto bytes_of = [&](int64_t Vc) {
+        return Vc >= V ? tiling_chunk_bytes(S_pad, AO, A, B, f32, V) : tiling_chunk_bytes(S_pad, AO, A, B, f32, Vc) + matrix;
+    };
+    int64_t Vc;
+    if (want_rows > 0) {
+        Vc = round_up(want_rows, 4);
+    } else if (bytes_of(V) <= budget) {
+        Vc = round_up(V, 4);
+    } else {
+        int64_t lo = 4, hi = round_up(V, 4) - 4;             // largest multiple of 4 below V that fits (bytes_of ascends there)
+        if (hi < 4 || bytes_of(4) > budget) {
+            out->chunk_rows = 4;
+            out->n_chunks = (V + 3) / 4;
+            out->bytes = bytes_of(4);
+            return PBVI_ENOMEM;
+        }
+        while (lo < hi) {
+            const int64_t mid = (lo / 4 + hi / 4 + 1) / 2 * 4;
+            if (bytes_of(mid) <= budget) lo = mid;
+            else hi = mid - 4;
+        }
+        const int64_t n = (V + lo - 1) / lo;
+        Vc = round_up((V + n - 1) / n, 4);                   // equal chunks: never more rows than `lo`, same count
+    }
+    out->chunk_rows = Vc;
+    out->n_chunks = (V + Vc - 1) / Vc;
+    out->bytes = bytes_of(Vc);
+    return out->bytes <= budget ? PBVI_OK : PBVI_ENOMEM;
+}
+
 // The scoring stage (K1, K2, first-max) runs on an engine or on an fp64 engine's fp32 screen (EngineT::stage_scores).
 struct ScoreIO {                      // the pipeline buffers the stage writes / reads: owned by the engine that continues
     int32_t* best_v;
@@ -659,6 +721,7 @@ struct ScoreStage {
     int64_t rd_col0, extra_row0, f64_pairs;
     bool fused;                       // the GEMM generated its Gamma tiles itself (gemm.hip, scheduler 2b)
     int split;                        // 1: bf16 MFMAs on the three-term operand split (gemm.hip, scheduler 2d)
+    int chunks;                       // alpha side: chunks Gamma was tiled into (1 = held whole or compact); 0 = belief side
 };
 
 class EngineBase {
@@ -692,6 +755,7 @@ class EngineBase {
     virtual int set_formulation(int f) = 0;
     virtual int set_screen(int mode) = 0;
     virtual int set_score_split(int mode) = 0;
+    virtual int set_gamma_tiling(int mode, int64_t chunk_rows) = 0;
     virtual int set_fused(int enable) = 0;
     virtual int64_t device_bytes() const = 0;
     virtual int64_t store_append(int which, const void* rows, int64_t n) = 0;
@@ -757,6 +821,14 @@ class EngineT : public EngineBase {
     uint64_t belsp_ver_ = 0;                                 // the bel_ version belsp_ holds (0: none)
     DevBuf gam_, slabs_, best_v_, best_score_, err_, dead_, queue_, counters_, rdot_, action_, aqueue_, out_, keep_;
     DevBuf bv2_, bs2_, err2_, queue2_, prune_cnt_;
+    // Gamma tiled over the alpha set (pbvi_set_gamma_tiling): 0 never, 1 when Gamma does not fit, 2 always; rows per chunk
+    // (0 = planned); the full-width score matrix the chunks are folded into; the widest stream-K share size of the chunks'
+    // GEMMs; events around each chunk's projection / GEMM / fold (statistics)
+    int tiling_mode_ = 0;
+    int64_t tiling_rows_ = 0;
+    DevBuf scores_, chain_max_;
+    std::vector<hipEvent_t> tile_ev_;
+    int tile_ev_chunks_ = 0;
     DevBuf stage_, keys_, perm_, action_res_, best_res_;   // belief reordering (f32, B > 256)
     DevBuf rep_, uniq_, inv_, slot_, out_full_;            // K6 key dedup: out_ holds the unique rows
     DevBuf store_[2], ids_;                                // device row stores: [0] alpha-vectors, [1] beliefs
@@ -868,7 +940,7 @@ class EngineT : public EngineBase {
                          &action_res_, &best_res_, &rep_, &uniq_, &inv_, &slot_, &out_full_, &btl_, &btc_, &val_exact_, &store_[0], &store_[1], &ids_, &in_ptr_, &in_src_, &bu_act_, &bu_obs_,
                          &bu_unnorm_, &bu_mass_, &bu_out_, &bu_row_, &walk64_, &rto64_, &bp_, &nzP_, &pmag_, &prd_, &keys_tmp_, &keys_act_, &keys_best_, &keys_rows_, &rf_v_, &rf_slot_, &rf_sc_, &rf_entry_, &rf_n_, &rf_tiles_,
                          &snz_, &sbtl_, &sbtc_, &vmax_bk_, &rf_ibv_, &rf_ibi_, &rf_cnt_, &rf_W_, &rf_Cx_, &rf_nzW_, &rf_klW_, &rf_kcW_,
-                         &dense_, &nzD_, &nzAlpha_, &prod_, &klistD_, &kcountD_, &nchunksD_, &mat_, &vlist_, &irr_, &rowflags_, &nzBw_, &scr_flag_, &ctile_, &acand_, &rf_q2_, &rf_q2p_, &rf_q2d_, &e_bv_, &e_bs_, &e_err_, &e_rdot_, &e_act_, &e_ares_, &e_bres_, &e_rep_, &e_uniq_, &e_inv_, &e_slotd_, &e_cnt_, &e_out_, &e_slot_};
+                         &dense_, &nzD_, &nzAlpha_, &prod_, &klistD_, &kcountD_, &nchunksD_, &mat_, &vlist_, &irr_, &rowflags_, &nzBw_, &scr_flag_, &ctile_, &acand_, &rf_q2_, &rf_q2p_, &rf_q2d_, &e_bv_, &e_bs_, &e_err_, &e_rdot_, &e_act_, &e_ares_, &e_bres_, &e_rep_, &e_uniq_, &e_inv_, &e_slotd_, &e_cnt_, &e_out_, &e_slot_, &scores_, &chain_max_};
         // every call is checked only to name a failure when PBVI_DEBUG is set; the thread's sticky last-error is cleared at
         // the end either way, so that a later launch check does not report a stale error of this teardown
         static const bool dbg = getenv("PBVI_DEBUG") != nullptr;
@@ -878,6 +950,8 @@ class EngineT : public EngineBase {
         for (auto& e : walk_ev_)
             if (e) chk(hipEventDestroy(e), "hipEventDestroy(walk)");
         for (DevBuf* b : all) b->release();
+        for (auto& e : tile_ev_)
+            if (e) chk(hipEventDestroy(e), "hipEventDestroy(tile)");
         if (host_stage_) chk(hipHostFree(host_stage_), "hipHostFree(stage)");
         if (ids_pin_) chk(hipHostFree(ids_pin_), "hipHostFree(ids)");
         if (h_flag_) chk(hipHostFree(h_flag_), "hipHostFree(flag)");
@@ -933,6 +1007,11 @@ class EngineT : public EngineBase {
         if (const char* f = getenv("PBVI_SCORE_SPLIT")) {     // initial setting (tests run the whole suite with the split forced)
             const std::string v(f);
             split_mode_ = (v == "off" || v == "0") ? 0 : (v == "always" || v == "2") ? 2 : 1;
+        }
+        if (const char* f = getenv("PBVI_GAMMA_TILING")) {    // initial setting: off|auto|always[:rows]
+            const std::string v(f), m = v.substr(0, v.find(':'));
+            tiling_mode_ = (m == "always" || m == "2") ? 2 : (m == "auto" || m == "1") ? 1 : 0;
+            tiling_rows_ = v.find(':') == std::string::npos ? 0 : std::max<int64_t>(0, atoll(v.c_str() + v.find(':') + 1));
         }
         if (const char* f = getenv("PBVI_FORMULATION")) {     // initial setting (tests run the whole suite both ways)
             const std::string v(f);
@@ -1650,7 +1729,7 @@ class EngineT : public EngineBase {
                           &bu_mass_, &bu_out_, &bu_row_, &walk64_, &bp_, &nzP_, &pmag_, &prd_, &keys_tmp_, &keys_act_, &keys_best_,
                           &keys_rows_, &rf_v_, &rf_slot_, &rf_sc_, &rf_entry_, &rf_n_, &rf_tiles_, &snz_, &sbtl_, &sbtc_, &vmax_bk_,
                           &rf_ibv_, &rf_ibi_, &rf_cnt_, &rf_W_, &rf_Cx_, &rf_nzW_, &rf_klW_, &rf_kcW_, &nzAlpha_, &prod_, &klistD_,
-                          &kcountD_, &nchunksD_, &mat_, &vlist_, &rowflags_, &ctile_, &acand_, &rf_q2_, &rf_q2p_, &rf_q2d_, &e_bv_, &e_bs_, &e_err_, &e_rdot_, &e_act_, &e_ares_, &e_bres_, &e_rep_, &e_uniq_, &e_inv_, &e_slotd_, &e_out_, &e_slot_};
+                          &kcountD_, &nchunksD_, &mat_, &vlist_, &rowflags_, &ctile_, &acand_, &rf_q2_, &rf_q2p_, &rf_q2d_, &e_bv_, &e_bs_, &e_err_, &e_rdot_, &e_act_, &e_ares_, &e_bres_, &e_rep_, &e_uniq_, &e_inv_, &e_slotd_, &e_out_, &e_slot_, &scores_};
         for (DevBuf* b : drop) {
             bytes_ -= (int64_t)b->cap;
             b->release();
@@ -1821,6 +1900,8 @@ class EngineT : public EngineBase {
     // ---- the scoring stage (K1, K2, first-max), runnable on this engine or on an fp64 engine's fp32 screen ---- //
     bool choose_push(int64_t N) const;
     int stage_scores(double gamma, bool use_push, const ScoreIO& io, ScoreStage<T>* out);
+    int stage_scores_tiled(double gamma, const ScoreIO& io, int want_split, int64_t Vc, int64_t n_chunks, ScoreStage<T>* out);
+    int ensure_exact(DevBuf& b, size_t bytes);
     template <typename TS>
     int run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_stats_t* st);
     int ensure_screen();
@@ -2441,6 +2522,32 @@ class EngineT : public EngineBase {
         tie_rel_user_ = rel;
         return PBVI_OK;
     }
+    int set_gamma_tiling(int mode, int64_t chunk_rows) override {
+        if (mode < 0 || mode > 2 || chunk_rows < 0)
+            FAIL(PBVI_EINVAL, "set_gamma_tiling: mode 0 = never, 1 = automatic, 2 = always; chunk_rows >= 0");
+        tiling_mode_ = mode;
+        tiling_rows_ = chunk_rows;
+        if (screen_) {
+            screen_->tiling_mode_ = mode;
+            screen_->tiling_rows_ = chunk_rows;
+        }
+        return PBVI_OK;
+    }
+    // statistics of a tiled call: kernel times summed over the chunks (events recorded by stage_scores_tiled)
+    void tile_times(hipEvent_t first, double* ms_project, double* ms_gemm, double* ms_fold) const {
+        *ms_project = *ms_gemm = *ms_fold = 0.0;
+        hipEvent_t prev = first;
+        for (int c = 0; c < tile_ev_chunks_; ++c) {
+            float t[3] = {0.f, 0.f, 0.f};
+            (void)hipEventElapsedTime(&t[0], prev, tile_ev_[(size_t)3 * c]);
+            (void)hipEventElapsedTime(&t[1], tile_ev_[(size_t)3 * c], tile_ev_[(size_t)3 * c + 1]);
+            (void)hipEventElapsedTime(&t[2], tile_ev_[(size_t)3 * c + 1], tile_ev_[(size_t)3 * c + 2]);
+            *ms_project += t[0];
+            *ms_gemm += t[1];
+            *ms_fold += t[2];
+            prev = tile_ev_[(size_t)3 * c + 2];
+        }
+    }
     int64_t device_bytes() const override { return bytes_ + (screen_ ? screen_->bytes_ : 0); }
 };
 
@@ -2664,7 +2771,8 @@ bool EngineT<T>::choose_push(int64_t N) const {
     const int64_t row = (int64_t)S_pad_ * (int64_t)sizeof(T);
     const int64_t n_pull = kF32 ? round_up(N, GEMM_BN) : N, m_push = round_up((int64_t)B_ * AO + B_, GEMM_BM);
     const int64_t gam_new = gamma_compact ? 0 : std::max<int64_t>(0, n_pull * row - (int64_t)gam_.cap);
-    if (gam_new > ((int64_t)1 << 28)) {
+    // (with Gamma tiling on, the alpha side fits whatever |V| is: the cost model alone decides)
+    if (gam_new > ((int64_t)1 << 28) && tiling_mode_ == 0) {
         // the score slabs count too
         auto slabs = [&](int64_t m, int64_t n) {
             if constexpr (kF32) return make_gemm_plan((int)round_up(m, GEMM_BM), (int)round_up(n, GEMM_BN), S_pad_).c_floats * 4;
@@ -2740,6 +2848,30 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
             HIPCHK(hipMemcpyAsync(vlist_.p, h_vlist_.data(), h_vlist_.size() * sizeof(int), hipMemcpyHostToDevice, stream_));
             mat_V_ = V_;
             gam_pad_ptr_ = nullptr;                          // the pad rows sit elsewhere now
+        }
+    }
+    out->chunks = use_push ? 0 : 1;
+    if (!use_push && tiling_mode_ != 0 && !will_fuse && mode_ == PBVI_SPARSE) {
+        // Gamma tiled over the alpha set?  What this stage may use: the engine's room plus the buffers it would re-allocate,
+        // less what the later stages of the call still ask for (early rows, the belief-dominance GEMM's slabs, small
+        // buffers; the refinement's work lists were reserved by run_pipeline already).
+        const int64_t held = (int64_t)(gam_.cap + slabs_.cap + scores_.cap + klist_.cap);
+        const int64_t free_now = room();
+        const int64_t avail = free_now > INT64_MAX - held ? INT64_MAX : free_now + held;
+        const int64_t reserve = avail / 16 + 2 * B_ * (int64_t)S_pad_ * (int64_t)sizeof(T) +
+                                (B_pad_ * round_up(Vt, GEMM_BN) + (int64_t)512 * 256 * 256) * (int64_t)sizeof(T);
+        const int64_t budget = std::max<int64_t>(0, avail - reserve);
+        TilingPlan tp;
+        bool plan = tiling_mode_ == 2;
+        if (tiling_mode_ == 1) plan = tiling_chunk_bytes(S_pad_, AO, A_, B_, kF32, V_) > budget;
+        if (plan) {
+            rc = tiling_plan(S_, A_, O_, V_, B_, kF32, budget, tiling_rows_, &tp);
+            if (rc == PBVI_EINVAL) FAIL(PBVI_EINVAL, "gamma tiling: shape out of range");
+            if (rc == PBVI_ENOMEM && tiling_rows_ == 0)
+                FAIL(PBVI_ENOMEM, "gamma tiling: a 4-row chunk and the score matrix need " + std::to_string(tp.bytes) +
+                                      " bytes, the engine may still allocate " + std::to_string(budget));
+            // (a chunk size the caller named is tried as it is: the planner's figures are upper bounds)
+            if (tp.n_chunks > 1) return stage_scores_tiled(gamma, io, want_split, tp.chunk_rows, tp.n_chunks, out);
         }
     }
     if (!use_push) {
@@ -2872,6 +3004,121 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
     return PBVI_OK;
 }
 
+// A buffer planned to the byte: DevBuf::ensure gives a buffer that GROWS up to twice the request while there is headroom,
+// which the tiling plan did not count.  Released first, it is allocated at exactly `bytes`.
+template <typename T>
+int EngineT<T>::ensure_exact(DevBuf& b, size_t bytes) {
+    if (bytes > b.cap && b.p != nullptr) {
+        HIPCHK(hipStreamSynchronize(stream_));
+        bytes_ -= (int64_t)b.cap;
+        b.release();
+    }
+    return b.ensure(bytes, &bytes_);
+}
+
+// The alpha-side scoring stage with Gamma tiled over the alpha set (pbvi_set_gamma_tiling): n_chunks chunks of Vc alpha
+// rows (the last one ragged).  A chunk of Gamma is exactly the Gamma of a smaller alpha set -- rows [v0, v0 + vc) of
+// alpha_ followed by one more row that k_project takes for the magnitude row: the NEXT chunk's first row, whose scores
+// nobody reads, or, behind the last chunk, the true max_v |alpha| row over the whole set -- so projection, need map and
+// GEMM run as they are on one chunk-sized Gamma buffer, and k_fold_chunk sums each chunk's partial slabs into the
+// full-width score matrix.  First-max, tie windows, refinement and the action stage then see ONE matrix: ties across
+// chunk seams go to the lowest global index by construction.
+template <typename T>
+int EngineT<T>::stage_scores_tiled(double gamma, const ScoreIO& io, int want_split, int64_t Vc, int64_t n_chunks,
+                                   ScoreStage<T>* out) {
+    int rc;
+    const int AO = A_ * O_;
+    const int64_t Vt = V_ + 1, N = (int64_t)AO * Vt + 2 * A_;
+    const ModelView<T> mv = view();
+    const int k_tiles = S_pad_ / GEMM_BK;
+    const int64_t ldd = round_up(N, 4);
+    if (ldd > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "gamma tiling: score matrix wider than int32");
+    // the fold target first (the chunk size was planned beside it), then the buffers of the largest chunk
+    if ((rc = ensure_exact(scores_, (size_t)B_ * ldd * sizeof(T)))) return rc;
+    const int64_t n_big = (int64_t)AO * (Vc + 1) + 2 * A_, rows_big = kF32 ? round_up(n_big, GEMM_BN) : n_big;
+    if ((rc = ensure_exact(gam_, (size_t)rows_big * S_pad_ * sizeof(T)))) return rc;
+    if constexpr (kF32) {
+        if ((rc = ensure_exact(slabs_, (size_t)make_gemm_plan((int)B_pad_, (int)rows_big, S_pad_).c_floats * sizeof(float)))) return rc;
+    } else {
+        const int sp = f64_uses_mfma(B_, n_big) ? gemm_f64_split((int)B_, (int)n_big, k_tiles) : 1;
+        if ((rc = ensure_exact(slabs_, (size_t)sp * B_ * n_big * sizeof(T)))) return rc;
+    }
+    if ((rc = need_.ensure((size_t)AO * k_tiles, &bytes_))) return rc;
+    if ((rc = chain_max_.ensure(sizeof(int), &bytes_))) return rc;
+    HIPCHK(hipMemsetAsync(chain_max_.p, 0, sizeof(int), stream_));
+    tile_ev_chunks_ = 0;
+    if (io.stats) {
+        while ((int64_t)tile_ev_.size() < 3 * n_chunks) {
+            hipEvent_t e = nullptr;
+            HIPCHK(hipEventCreate(&e));
+            tile_ev_.push_back(e);
+        }
+        tile_ev_chunks_ = (int)n_chunks;
+    }
+    double tol = 0.0;
+    bool on_device = false;                                  // some chunk's window comes from its stream-K share size
+    out->split = 0;
+    for (int64_t c = 0; c < n_chunks; ++c) {
+        const int64_t v0 = c * Vc, vc = std::min<int64_t>(Vc, V_ - v0);
+        const bool last = c == n_chunks - 1;
+        const int64_t n_c = (int64_t)AO * (vc + 1) + 2 * A_, rows_c = kF32 ? round_up(n_c, GEMM_BN) : n_c;
+        // pad rows of this chunk's shape: the (buffer, row count, layout) key covers the ragged last chunk
+        if (rows_c > n_c && (gam_pad_ptr_ != gam_.p || gam_pad_N_ != n_c || gam_pad_compact_)) {
+            HIPCHK(hipMemsetAsync(gam_.as<T>() + (size_t)n_c * S_pad_, 0, (size_t)(rows_c - n_c) * S_pad_ * sizeof(T), stream_));
+            gam_pad_ptr_ = gam_.p;
+            gam_pad_N_ = n_c;
+            gam_pad_compact_ = false;
+        }
+        const uint8_t* need = nullptr;
+        if (kF32 || f64_uses_mfma(B_, n_c)) {
+            HIPCHK(launch_need_tiles(nzA_.as<uint8_t>(), (int)(B_pad_ / GEMM_BM), nzB_.as<uint8_t>(), AO, (int)vc, k_tiles,
+                                     need_.as<uint8_t>(), stream_));
+            need = need_.as<uint8_t>();
+        }
+        HIPCHK(launch_project<T>(alpha_.as<T>() + (size_t)v0 * S_pad_, S_pad_, (int)(vc + 1), mv, (T)gamma, gam_.as<T>(), S_pad_,
+                                 need, k_tiles, stream_));
+        HIPCHK(launch_tail_rows<T>(mv, gam_.as<T>(), (int64_t)AO * (vc + 1), S_pad_, stream_, nullptr));
+        if (c == 0) HIPCHK(hipEventRecord(io.ev[1], stream_));
+        if (io.stats) HIPCHK(hipEventRecord(tile_ev_[(size_t)3 * c], stream_));
+        // (tile lists and stream-K plan on the main stream: the list buffers are the previous chunk's GEMM's)
+        SlabView<T> sv;
+        int split = want_split;
+        if ((rc = score_gemm(gam_.as<T>(), n_c, nzB_.as<uint8_t>(), AO, (int)vc, &sv, nullptr, 0, nullptr, nullptr, nullptr, &split)))
+            return rc;
+        if (io.stats) HIPCHK(hipEventRecord(tile_ev_[(size_t)3 * c + 1], stream_));
+        if (c > 0 && split != out->split) FAIL(PBVI_ERUNTIME, "gamma tiling: the chunks' GEMMs disagree about the operand split");
+        out->split = split;
+        const double t = tie_window(kF32 ? plan_.chunk_len * GEMM_BK : S_pad_);
+        if (t < 0.0) on_device = true;
+        else tol = std::max(tol, t);
+        HIPCHK(launch_fold_chunk<T>(sv, (int)B_, AO, (int)vc, (int)V_, (int)v0, last ? AO + 2 * A_ : 0, scores_.as<T>(), ldd,
+                                    chain_steps(), chain_max_.as<int>(), stream_));
+        if (io.stats) HIPCHK(hipEventRecord(tile_ev_[(size_t)3 * c + 2], stream_));
+    }
+    HIPCHK(hipEventRecord(io.ev[2], stream_));
+    HIPCHK(hipStreamWaitEvent(stream_, io.join, 0));       // dead flags + rdot ready
+    SlabView<T> full;
+    full.slabs = scores_.as<T>();
+    full.slab_stride = 0;
+    full.ldc = (int)ldd;
+    full.nchunks = nullptr;
+    full.tiles_m = 0;
+    full.fixed = 1;
+    out->plan = plan_;                                     // (the last chunk's: statistics)
+    out->tol_rel = on_device ? -1.0 : tol;                 // the widest window over the chunks
+    out->chain = on_device ? chain_max_.as<int>() : nullptr;
+    out->rd_col0 = (int64_t)AO * Vt;
+    out->extra_row0 = -1;
+    out->f64_pairs = f64_pairs_;
+    out->fused = false;
+    out->chunks = (int)n_chunks;
+    HIPCHK(launch_argmax<T>(full, (int)V_, AO, (int)B_, io.dead, out->tol_rel, 0.0, out->chain, 0, io.best_v, io.best_score,
+                            io.err, io.queue, io.qcount, stream_, io.tol_extra, out->split));
+    HIPCHK(hipEventRecord(io.ev[3], stream_));
+    out->sv = full;
+    return PBVI_OK;
+}
+
 // fp64 engines: an fp32 twin of the model on the same device and streams, used as a SCREEN.  The fp64 MFMA GEMM runs at
 // its instruction's ceiling (47.6 TFLOP/s measured) -- a third of the fp32 stream-K GEMM -- and decides
 // nothing the fp32 one cannot decide except near-ties.  So the scores are computed in fp32 on rounded copies of the
@@ -2965,6 +3212,8 @@ int EngineT<T>::sync_screen() {
         }
         sc->formulation_ = formulation_;
         sc->tie_rel_user_ = tie_rel_user_;
+        sc->tiling_mode_ = tiling_mode_;
+        sc->tiling_rows_ = tiling_rows_;
         return PBVI_OK;
     }
 }
@@ -3087,6 +3336,10 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
     // a screen multiplies operands rounded to fp32 (alpha, belief, RTO: 2^-24 relative each) and gamma in fp32
     io.tol_extra = screened ? 4.0 * 5.9604644775390625e-08 : 0.0;
     io.allow_split = !screened;
+    if (windows && !use_push && scorer.tiling_mode_ != 0) {   // Gamma tiling plans with what is free: the refinement's work
+        RefineWork reserve;                                   // lists (the largest buffers of the later stages) come first
+        if ((rc = refine_work(pairs, V_, &reserve))) return rc;
+    }
     ScoreStage<TS> sc;
     if ((rc = scorer.stage_scores(gamma, use_push, io, &sc))) return rc;
     const SlabView<TS>& sv = sc.sv;
@@ -3205,7 +3458,8 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
             // Gamma is in HBM as the GEMM read it (projection kernel, not the fused GEMM): the per-entry pass first
             // separates candidates by fp64 sums over those fp32 rows (backup_kernels.h, RefineWork::gam)
             static const bool no_l1 = getenv("PBVI_NO_L1_SCREEN") != nullptr;      // debug / A-B only
-            if (!no_l1 && !use_push && !sc.fused && mode_ == PBVI_SPARSE) {
+            // (not in a tiled call: a chunk's rows are gone by now)
+            if (!no_l1 && !use_push && !sc.fused && sc.chunks <= 1 && mode_ == PBVI_SPARSE) {
                 work.gam = (const float*)gam_.p;
                 work.ldg = S_pad_;
                 work.l1_rel = (double)(R_ + 4) * 5.9604644775390625e-08;
@@ -3428,6 +3682,12 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
         st->screened = screened ? 1 : 0;
         st->fused_projection = sc.fused ? 1 : 0;
         st->score_split = sc.split;
+        st->gamma_chunks = sc.chunks;
+        if (sc.chunks > 1) {                                 // sums over the chunks; the folds count with the argmax
+            double fold = 0.0;
+            scorer.tile_times(ev_[0], &st->ms_project, &st->ms_score, &fold);
+            st->ms_argmax = fold + el(2, 3);
+        }
     }
     return PBVI_OK;
 }
@@ -3919,6 +4179,26 @@ int pbvi_set_value_max_exact(pbvi_engine_t* e, int exact) {
 int pbvi_alpha_layout(pbvi_engine_t* e, int64_t* free_rows, int64_t* layouts) {
     NEED(e);
     return e->impl->alpha_layout(free_rows, layouts);
+}
+int pbvi_set_gamma_tiling(pbvi_engine_t* e, int mode, int64_t chunk_rows) {
+    NEED(e);
+    return e->impl->set_gamma_tiling(mode, chunk_rows);
+}
+int pbvi_gamma_tiling_plan(int32_t S, int32_t A, int32_t O, int64_t V, int64_t B, int dtype, int64_t budget_bytes,
+                           int64_t* chunk_rows, int64_t* n_chunks, int64_t* bytes_needed) {
+    using namespace pbvi;
+    if (!chunk_rows || !n_chunks || !bytes_needed || (dtype != 0 && dtype != 1))
+        FAIL(PBVI_EINVAL, "gamma_tiling_plan: null output or dtype not 0 (fp32) / 1 (fp64)");
+    pbvi::TilingPlan tp;
+    const int rc = pbvi::tiling_plan(S, A, O, V, B, dtype == 0, budget_bytes, *chunk_rows, &tp);
+    if (rc == PBVI_EINVAL) FAIL(PBVI_EINVAL, "gamma_tiling_plan: S, A, O, V, B must be positive, budget and chunk_rows >= 0, A*O*(V+1)+2A within int32");
+    *chunk_rows = tp.chunk_rows;
+    *n_chunks = tp.n_chunks;
+    *bytes_needed = tp.bytes;
+    if (rc == PBVI_ENOMEM)
+        FAIL(PBVI_ENOMEM, "gamma_tiling_plan: chunks of " + std::to_string(tp.chunk_rows) + " alpha rows need " +
+                              std::to_string(tp.bytes) + " bytes, the budget is " + std::to_string(budget_bytes));
+    return PBVI_OK;
 }
 int pbvi_set_tie_window(pbvi_engine_t* e, double rel) {
     NEED(e);

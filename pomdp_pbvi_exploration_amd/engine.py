@@ -34,6 +34,7 @@ EXPORTS = [
     'pbvi_belief_walk_keys', 'pbvi_backup_fetch_value_max',
     'pbvi_backup_fetch_compact', 'pbvi_host_alloc', 'pbvi_host_free', 'pbvi_debug_gemm_dense',
     'pbvi_backup_fetch_exchange_padded', 'pbvi_assemble_rows_store', 'pbvi_exchange_merge', 'pbvi_backup_run_fetch', 'pbvi_debug_alloc_limit', 'pbvi_engine_after_oom', 'pbvi_set_f64_screen', 'pbvi_set_fused_projection', 'pbvi_backup_fetch_row_hashes', 'pbvi_set_score_split',
+    'pbvi_set_gamma_tiling', 'pbvi_gamma_tiling_plan',
 ]
 
 
@@ -51,7 +52,7 @@ class PbviStats(C.Structure):
                 ('score_tiles_run', C.c_int64), ('project_flops', C.c_int64), ('project_flops_executed', C.c_int64),
                 ('split_k', C.c_int32), ('formulation', C.c_int32), ('n_refine_candidates', C.c_int64),
                 ('ms_project_gemm', C.c_double), ('screened', C.c_int32), ('fused_projection', C.c_int32),
-                ('score_split', C.c_int32)]
+                ('score_split', C.c_int32), ('gamma_chunks', C.c_int32)]
 
     def as_dict(self) -> dict:
         return {name: getattr(self, name) for name, _ in self._fields_}
@@ -122,6 +123,9 @@ def load_library(path: str = LIB_PATH):
         'pbvi_set_f64_screen': (C.c_int, [vp, C.c_int]),
         'pbvi_set_fused_projection': (C.c_int, [vp, C.c_int]),
         'pbvi_set_score_split': (C.c_int, [vp, C.c_int]),
+        'pbvi_set_gamma_tiling': (C.c_int, [vp, C.c_int, C.c_int64]),
+        'pbvi_gamma_tiling_plan': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int, C.c_int64,
+                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         'pbvi_belief_walk': (C.c_int64, [vp, f64p, C.c_int64, i32p, i32p, u8p, f64p]),
         'pbvi_engine_set_rto_f64': (C.c_int, [vp, f64p]),
         'pbvi_backup_fetch_unique_keys': (C.c_int, [vp, vp]),
@@ -155,6 +159,23 @@ def debug_alloc_limit(mb: int) -> int:
     """Cap (MiB; < 0: none) on the device bytes one engine may hold (``pbvi_debug_alloc_limit``): a deterministic
     out-of-memory for tests of the ``MemoryError`` contract of ``PBVI_Solver.solve``.  Returns the previous cap."""
     return int(load_library().pbvi_debug_alloc_limit(int(mb)))
+
+
+def gamma_tiling_plan(S: int, A: int, O: int, V: int, B: int, dtype: str = 'f32', budget_bytes: int = 0,
+                      chunk_rows: int = 0) -> tuple:
+    """The Gamma-tiling planner (``pbvi_gamma_tiling_plan``; host arithmetic, no GPU): ``(chunk_rows, n_chunks,
+    bytes_needed)`` for scoring V alpha-vectors against B beliefs on the alpha side within ``budget_bytes`` of device
+    memory.  ``chunk_rows=0`` lets the planner choose.  ``MemoryError`` when the plan exceeds the budget, ``ValueError``
+    on bad arguments."""
+    if dtype not in ('f32', 'f64'):
+        raise ValueError("dtype must be 'f32' or 'f64'")
+    for name, v in (('S', S), ('A', A), ('O', O)):
+        if not -2**31 <= int(v) < 2**31:
+            raise ValueError(f'{name} out of range')
+    rows, n, need = C.c_int64(int(chunk_rows)), C.c_int64(0), C.c_int64(0)
+    _check(load_library().pbvi_gamma_tiling_plan(int(S), int(A), int(O), int(V), int(B), 0 if dtype == 'f32' else 1,
+                                                 int(budget_bytes), C.byref(rows), C.byref(n), C.byref(need)))
+    return int(rows.value), int(n.value), int(need.value)
 
 
 def debug_gemm_dense(enable: bool) -> bool:
@@ -402,6 +423,7 @@ class Engine:
         self.serial = Engine._nonce + (next(Engine._serials),)
         self._alpha_token = None
         self._formulation = None                # see the property
+        self._gamma_tiling = None               # see the property
         self.last_stats = {}                    # pbvi_stats_t of the last run()
         self._store_epoch = {'alpha': 0, 'belief': 0}
         self._resident = {'alpha': None, 'belief': None}     # store ids of the working alpha set / belief block
@@ -1030,6 +1052,23 @@ class Engine:
         """fp32 engines: backup scores from bf16 MFMAs on a three-term operand split with a widened tie window (same
         results): ``'off'``, ``'auto'`` (when the score GEMM is large; default) or ``'always'`` (``pbvi_set_score_split``)."""
         self._ck(self._lib.pbvi_set_score_split(self._h, {'off': 0, 'auto': 1, 'always': 2}[mode]))
+
+    def set_gamma_tiling(self, mode: str = 'off', chunk_rows: int = 0) -> None:
+        """Alpha-side backups whose Gamma is projected into HBM (R > 1, fp64 scoring, unfused R = 1): walk the alpha set in
+        chunks of ``chunk_rows`` rows (0 = as many as fit) through one chunk-sized Gamma buffer -- ``'off'`` (default),
+        ``'auto'`` (only when Gamma does not fit what the engine may still allocate) or ``'always'``.  Same results;
+        ``last_stats['gamma_chunks']`` reports the chunks (``pbvi_set_gamma_tiling``)."""
+        self._ck(self._lib.pbvi_set_gamma_tiling(self._h, {'off': 0, 'auto': 1, 'always': 2}[mode], int(chunk_rows)))
+        self._gamma_tiling = (mode, int(chunk_rows))
+
+    @property
+    def gamma_tiling(self) -> tuple:
+        """``(mode, chunk_rows)`` as ``set_gamma_tiling`` last made it (initially ``PBVI_GAMMA_TILING`` or ``('off', 0)``)."""
+        if self._gamma_tiling is None:
+            mode, _, rows = os.environ.get('PBVI_GAMMA_TILING', '').partition(':')
+            mode = {'auto': 'auto', '1': 'auto', 'always': 'always', '2': 'always'}.get(mode, 'off')
+            self._gamma_tiling = (mode, max(0, int(rows)) if rows.lstrip('-').isdigit() else 0)
+        return self._gamma_tiling
 
     def set_tie_window(self, rel: float) -> None:
         self._ck(self._lib.pbvi_set_tie_window(self._h, float(rel)))

@@ -451,6 +451,8 @@ class PBVI_Solver(Solver):
             # runs the backup, and only the distinct new rows come back.
             eng = value_function.model.engine
             beliefs = belief_set.belief_list
+            if self.tile_gamma and eng.gamma_tiling[0] == 'off':
+                eng.set_gamma_tiling('auto')
             try:
                 if self._belief_chunk is not None and len(beliefs) > self._belief_chunk:
                     raise MemoryError('an earlier backup of this solver only fitted in belief chunks')
@@ -471,6 +473,10 @@ class PBVI_Solver(Solver):
             new_vf.extend(value_function)
         return new_vf
 
+    # True: the engines this solver backs up on tile Gamma over the alpha set when it does not fit the device
+    # (Engine.set_gamma_tiling('auto')): an alpha-side backup is then served by ONE engine call within the memory there is,
+    # and the belief chunks below are reached only if that call still raises MemoryError.  False: nothing changes.
+    tile_gamma = False
     _belief_chunk = None      # set once a block only fitted the device in pieces: later backups start there
 
     def _backup_block(self, eng, value_function, belief_set, beliefs, belief_dominance_prune):
