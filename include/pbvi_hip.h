@@ -108,6 +108,8 @@ const char* pbvi_last_error(void);
  *   reach_states [S][A][R] int32  = model.reachable_states            (src/mdp.py:194-201,296-335)
  *   rto          [S][A][O][R] T   = model.reachable_transitional_observation_table (src/pomdp.py:201-202)
  *   exp_reward   [S][A] T         = model.expected_rewards_table      (src/pomdp.py:251)
+ * Model shapes the backup kernels cannot run are refused here with PBVI_EUNSUPPORTED (never by a launch in the middle of
+ * a backup): A <= 256 and A * (1 + O) <= 65535.  S, O and R are otherwise bounded by memory only.
  */
 int pbvi_engine_create(pbvi_engine_t** out, int device, int32_t S, int32_t A, int32_t O, int32_t R,
                        const int32_t* reach_states, const void* rto, const void* exp_reward,
@@ -125,7 +127,7 @@ int64_t pbvi_alpha_count(const pbvi_engine_t* e);
 
 /*
  * Device-resident belief block.  Replaces BeliefSet.to_gpu (src/pomdp.py:613-634).
- *   beliefs [B][S] T, row-major.
+ *   beliefs [B][S] T, row-major, 1 <= B <= 65535 (PBVI_EUNSUPPORTED above; pbvi_beliefs_select has the same limit).
  */
 int pbvi_beliefs_set(pbvi_engine_t* e, const void* beliefs, int64_t B);
 
@@ -267,6 +269,7 @@ int64_t pbvi_assemble_rows_store(pbvi_engine_t* e, double gamma, int64_t n, cons
  *   out_keys   [sum of the messages' counts][key_width]  the globally distinct keys in order of first occurrence
  *   out_index  [n_total]  position of each belief's key in out_keys     out_action / out_keep [n_total]
  * Returns the number of distinct keys, or a negative error code.  Pure host code: needs no engine and no device.
+ * key_width (1 + O) >= 1 has no bound of its own: one message, per * (3 + key_width) + 1 int32 words, must fit int32.
  */
 int64_t pbvi_exchange_merge(const int32_t* all_meta, int32_t world, int64_t stride, int64_t per, int32_t key_width,
                             int64_t n_total, int32_t* out_keys, int32_t* out_index, int32_t* out_action, uint8_t* out_keep);

@@ -430,7 +430,7 @@ template <typename T>
 __global__ void k_gather_rows_v(const T* __restrict__ src, T* __restrict__ dst, int ld, const int32_t* __restrict__ perm,
                                 const int32_t* __restrict__ ids, const uint8_t* __restrict__ flags = nullptr, int B = 0,
                                 int k_tiles = 0, uint8_t* __restrict__ nz = nullptr, int or_rows = 0,
-                                uint32_t* __restrict__ plane = nullptr) {
+                                uint32_t* __restrict__ plane = nullptr, int row0 = 0) {
     // The first or_rows rows of the grid build the block's zero map (they need the order only, like the
     // gather): as a kernel of its own in front of the gather it was 14 us on the path to the score GEMM.
     if ((int)blockIdx.y < or_rows) {
@@ -441,7 +441,7 @@ __global__ void k_gather_rows_v(const T* __restrict__ src, T* __restrict__ dst, 
     typedef T TN __attribute__((ext_vector_type(NS)));
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c * NS >= ld) return;
-    const int row = blockIdx.y - or_rows;
+    const int row = row0 + (int)blockIdx.y - or_rows;
     int r = row;
     if (perm) r = perm[r];
     if (ids) r = ids[r];
@@ -918,7 +918,7 @@ class EngineT : public EngineBase {
     int64_t mat_V_ = -1;
     uint64_t dead_ver_ = 0;                                  // belief-block version dead_ / btl_ / btc_ describe
     int64_t dead_pairs_ = 0, dead_count_ = 0;
-    int* rf_counts_ = nullptr;                               // [2] in host_stage_: what the refinement's per-entry pass deferred
+    int* rf_counts_ = nullptr;                               // h_flag_[24..25]: what the refinement's per-entry pass deferred
     bool last_deferred_nothing_ = false;                     // (the first backup of an engine reads the counts mid-pipeline)
     bool owns_streams_ = true;                               // false: a screen running on its fp64 engine's streams
     EngineT<float>* screen_ = nullptr;                       // fp64 engines: the fp32 screen (see ensure_screen)
@@ -1310,10 +1310,15 @@ class EngineT : public EngineBase {
         // the zero map (the first rows of the grid) and the rows in that order, one launch
         constexpr int NS = 16 / (int)sizeof(T);
         const int or_rows = (int)(Bp / GEMM_BM);
-        hipLaunchKernelGGL(k_gather_rows_v<T>, dim3((S_pad_ / NS + 255) / 256, (unsigned)(B + or_rows)), dim3(256), 0, stream_, src,
-                           bel_.as<T>(), S_pad_, perm, src_ids, rowflags_.as<uint8_t>(), (int)B, k_tiles, nzA_.as<uint8_t>(), or_rows,
-                           plane);
-        HIPCHK(hipGetLastError());
+        // (grid.y is at most 65535: a block near the limit goes in two launches, the zero map with the first)
+        for (int64_t r0 = 0, orr = or_rows; r0 < B; orr = 0) {
+            const int64_t cnt = std::min<int64_t>(B - r0, 65535 - orr);
+            hipLaunchKernelGGL(k_gather_rows_v<T>, dim3((S_pad_ / NS + 255) / 256, (unsigned)(cnt + orr)), dim3(256), 0, stream_, src,
+                               bel_.as<T>(), S_pad_, perm, src_ids, rowflags_.as<uint8_t>(), (int)B, k_tiles, nzA_.as<uint8_t>(), (int)orr,
+                               plane, (int)r0);
+            HIPCHK(hipGetLastError());
+            r0 += cnt;
+        }
         if (!ev_nzA_) HIPCHK(hipEventCreateWithFlags(&ev_nzA_, hipEventDisableTiming));
         HIPCHK(hipEventRecord(ev_nzA_, stream_));
         B_ = B;
@@ -1331,7 +1336,7 @@ class EngineT : public EngineBase {
     // one page-locked int for flags read back with the results (a stack variable would be written by the copy after an
     // early error return had released it)
     int* pinned_flag() {
-        if (!h_flag_ && hipHostMalloc((void**)&h_flag_, 128, hipHostMallocDefault) != hipSuccess) {   // 32 ints: [16..23] = run_fetch's counters
+        if (!h_flag_ && hipHostMalloc((void**)&h_flag_, 128, hipHostMallocDefault) != hipSuccess) {   // 32 ints: [16..23] = run_fetch's counters, [24..25] = rf_counts_
             (void)hipGetLastError();
             h_flag_ = nullptr;
         }
@@ -2225,6 +2230,7 @@ class EngineT : public EngineBase {
     int prune_dominated(uint8_t* keep) override {
         if (V_ <= 0) FAIL(PBVI_EINVAL, "prune_dominated: no alpha set resident");
         if (!keep) FAIL(PBVI_EINVAL, "prune_dominated: keep is NULL");
+        if (V_ > 4 * 65535) FAIL(PBVI_EUNSUPPORTED, "prune_dominated: at most 262140 alpha-vectors");   // grid.y = ceil(V / 4)
         HIPCHK(hipSetDevice(device_));
         int rc = prune_cnt_.ensure((size_t)V_ * sizeof(int), &bytes_);
         if (rc) return rc;
@@ -3271,7 +3277,7 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
     if ((rc = keep_.ensure((size_t)B_, &bytes_))) return rc;
     int* qcount = counters_.as<int>();
     int* aqcount = counters_.as<int>() + 1;
-    if (windows && (rc = stage_reserve(256))) return rc;      // pinned room for the refinement's counts, while the stream is idle
+    if (windows && (rc = stage_reserve(256))) return rc;      // the pinned bounce buffer of the fetches that follow, allocated while the stream is idle
     HIPCHK(hipMemsetAsync(counters_.p, 0, 8 * sizeof(int), stream_));
 
     HIPCHK(hipEventRecord(ev_[0], stream_));
@@ -3465,9 +3471,11 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
                 work.l1_rel = (double)(R_ + 4) * 5.9604644775390625e-08;
             }
         }
-        // the counts land in the engine's pinned bounce buffer (reserved at the top of the call; idle during a backup:
-        // results are staged through it only by the fetch calls that follow)
-        rf_counts_ = reinterpret_cast<int*>(host_stage_);
+        // the counts land in two of the engine's pinned flag words -- not in the staging buffer: run_fetch stages results
+        // through that one before the counts are read, and out_add may reset or reallocate it
+        rf_counts_ = pinned_flag();
+        if (!rf_counts_) FAIL(PBVI_ENOMEM, "backup_run: pinned flag");
+        rf_counts_ += 24;
         rf_counts_[0] = rf_counts_[1] = 0;
         static const bool no_spec = getenv("PBVI_NO_SPECULATION") != nullptr;      // debug / A-B only
         // (not with the belief-dominance test: its own value-max refinement re-uses the work-list buffers, so the
@@ -3579,7 +3587,6 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
         if (early_used_ && rf_dst_.slot != nullptr) {        // run_fetch: slots, index, actions (best, keep) with this read-back
             int rc2;
             if ((rc2 = out_begin())) return rc2;
-            out_used_ = 256;                                 // (the first bytes of the staging buffer hold the refinement's counts)
             if ((rc2 = out_add(rf_dst_.slot, e_slot_.p, (size_t)B_ * sizeof(int32_t)))) return rc2;
             if ((rc2 = out_add(rf_dst_.index, inv_.p, (size_t)B_ * sizeof(int32_t)))) return rc2;
             if ((rc2 = out_add(rf_dst_.action, res_action_, (size_t)B_ * sizeof(int32_t)))) return rc2;
@@ -3857,6 +3864,12 @@ int pbvi_engine_create(pbvi_engine_t** out, int device, int32_t S, int32_t A, in
     if (!reach_states || !rto || !exp_reward) FAIL(PBVI_EINVAL, "engine_create: NULL table");
     if (dtype != PBVI_F32 && dtype != PBVI_F64) FAIL(PBVI_EINVAL, "engine_create: dtype must be PBVI_F32 or PBVI_F64");
     if (mode != PBVI_SPARSE && mode != PBVI_DENSE) FAIL(PBVI_EINVAL, "engine_create: unknown mode");
+    // Limits of the backup kernels, refused here rather than by a launcher in the middle of a backup: the action kernel
+    // keeps one value per action in a 256-thread block, and (action, observation) pairs / (action, term) pairs index
+    // grid.y and grid.z (at most 65535).  A * (1 + O) <= 65535 implies A * O <= 65535.
+    if (A > 256) FAIL(PBVI_EUNSUPPORTED, "engine_create: at most 256 actions (A <= 256)");
+    if ((int64_t)A * (1 + (int64_t)O) > 65535)
+        FAIL(PBVI_EUNSUPPORTED, "engine_create: at most 65535 action-observation terms (A * (1 + O) <= 65535)");
     int ndev = pbvi_device_count();
     if (ndev <= 0) FAIL(PBVI_ERUNTIME, "engine_create: no HIP device visible");
     if (device < 0 || device >= ndev) FAIL(PBVI_EINVAL, "engine_create: device index out of range");
@@ -3952,13 +3965,15 @@ int64_t pbvi_assemble_rows_store(pbvi_engine_t* e, double gamma, int64_t n, cons
 // messages of 1024 beliefs; this is a few microseconds).
 int64_t pbvi_exchange_merge(const int32_t* all_meta, int32_t world, int64_t stride, int64_t per, int32_t key_width,
                             int64_t n_total, int32_t* out_keys, int32_t* out_index, int32_t* out_action, uint8_t* out_keep) {
-    if (!all_meta || world <= 0 || per <= 0 || key_width <= 0 || key_width > 64 || n_total < 0 || !out_keys || !out_index ||
+    if (!all_meta || world <= 0 || per <= 0 || key_width <= 0 || n_total < 0 || !out_keys || !out_index ||
         !out_action || !out_keep) {
         pbvi::set_error("exchange_merge: bad arguments");
         return PBVI_EINVAL;
     }
     const int64_t n_meta = 1 + 3 * per + per * (int64_t)key_width;
-    if (stride < n_meta || n_total > (int64_t)world * per || (int64_t)world * per > 0x7fffffff) {
+    // (positions and counts are int32 words of the message: one message must stay addressable by them)
+    if (per > 0x7fffffff / ((int64_t)key_width + 3) || stride < n_meta || n_total > (int64_t)world * per ||
+        (int64_t)world * per > 0x7fffffff) {
         pbvi::set_error("exchange_merge: message stride / belief count do not fit the block size");
         return PBVI_EINVAL;
     }

@@ -523,7 +523,9 @@ class PBVI_Solver(Solver):
         single belief that does not fit re-raises, which ``solve`` turns into the partial result
         (``src/pomdp.py:2399-2401``)."""
         chunk = self._belief_chunk if self._belief_chunk is not None else (len(beliefs) + 1) // 2
-        chunk = max(1, min(chunk, (len(beliefs) + 1) // 2))
+        # (never above the block size of one engine call: the engine refuses larger blocks with an error that is not a
+        # MemoryError, which the halving below would not catch)
+        chunk = max(1, min(chunk, (len(beliefs) + 1) // 2, self.BELIEF_BLOCK))
         setting = eng.formulation
         while True:
             # (not inside the try: a value function that does not fit by itself is not cured by smaller chunks)

@@ -223,3 +223,28 @@ def checksum(*arrays) -> str:
     for a in arrays:
         h.update(np.ascontiguousarray(a).tobytes())
     return h.hexdigest()
+
+
+def twin_rows_case(B: int = 320):
+    """One action, one observation, identity transitions: score[b, v] = gamma * b . alpha[v] and the key of belief b is its
+    best alpha row.  Belief b weighs states 2b and 2b+1 with w and 1 - w, w a little above 1/2; alpha row 2b is 1 on both,
+    its twin 2b+1 is one fp32 step above 1 on state 2b and the same step below on state 2b+1.  In exact arithmetic the twin
+    wins by (2 w - 1) * 2^-23, far below what an fp32 sum near 1 resolves: the fp32 first maximum is often the base row, the
+    fp64 decision always the twin (tests of the early-row slots of ``pbvi_backup_run_fetch``).  Returns
+    ``(S, reachable_states, rto, expected_rewards, alpha, beliefs)``."""
+    rng = np.random.default_rng(21)
+    S, V = 2 * B, 2 * B
+    w = (0.5 + rng.uniform(2.0 ** -12, 2.0 ** -7, B)).astype(np.float32)
+    b = np.zeros((B, S), dtype=np.float32)
+    b[np.arange(B), 2 * np.arange(B)] = w
+    b[np.arange(B), 2 * np.arange(B) + 1] = np.float32(1.0) - w
+    alpha = np.zeros((V, S), dtype=np.float32)
+    step = np.float32(2.0 ** -23)
+    for i in range(B):
+        alpha[2 * i, 2 * i:2 * i + 2] = 1.0
+        alpha[2 * i + 1, 2 * i] = np.float32(1.0) + step
+        alpha[2 * i + 1, 2 * i + 1] = np.float32(1.0) - step
+    rs = np.arange(S, dtype=np.int64)[:, None, None]
+    rto = np.ones((S, 1, 1, 1))
+    er = np.zeros((S, 1))
+    return S, rs, rto, er, alpha.astype(np.float64), b.astype(np.float64)

@@ -149,6 +149,51 @@ def test_gather_keys_world2(tmp_path):
     assert os.path.exists(tmp_path / 'kok0') and os.path.exists(tmp_path / 'kok1')
 
 
+def _worker_keys_wide(rank, world, port, out_dir, O):
+    sys.path.insert(0, REPO)
+    os.environ['MASTER_ADDR'] = '127.0.0.1'
+    os.environ['MASTER_PORT'] = str(port)
+    dist.init_process_group('gloo', rank=rank, world_size=world)
+    try:
+        from pomdp_pbvi_exploration_amd.dist import gather_keys
+        S, per = 4, 6
+        count = 3 + rank
+        # rank r's key u: action u % 2, entries all 7 except the LAST one, which carries u -- and key 0 is the same on
+        # both ranks, so the merge has to compare all 1 + O entries to keep the others apart and to join that one
+        keys = torch.full((per, 1 + O), 7, dtype=torch.int32)
+        keys[:count, 0] = torch.arange(count, dtype=torch.int32) % 2
+        keys[:count, O] = torch.arange(count, dtype=torch.int32) * (1 + 100 * rank)
+        idx = torch.arange(per, dtype=torch.int32) % count
+        acts = keys[idx.long(), 0].clone()
+        keep = torch.ones(per, dtype=torch.uint8)
+        n_distinct = 3 + 4 - 1
+
+        def assemble(all_keys):
+            assert isinstance(all_keys, np.ndarray) and all_keys.shape == (n_distinct, 1 + O), all_keys.shape
+            k = torch.from_numpy(all_keys)
+            return k[:, O:O + 1].double().repeat(1, S)
+
+        uniq, gidx, a, k = gather_keys(dist, None, keys, count, idx, acts, keep, world * per, assemble)
+        assert uniq.shape == (n_distinct, S)
+        full = uniq[torch.from_numpy(gidx)][:, 0]
+        exp = torch.cat([((torch.arange(per) % (3 + r)) * (1 + 100 * r)).double() for r in range(world)])
+        assert torch.equal(full, exp)
+        assert a.tolist() == torch.cat([(torch.arange(per) % (3 + r)) % 2 for r in range(world)]).tolist()
+        assert all(k.tolist())
+        open(os.path.join(out_dir, f'wok{rank}'), 'w').write('ok')
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize('O', [64, 200])
+def test_gather_keys_world2_with_64_or_more_observations(tmp_path, O):
+    """The key exchange of a model with O >= 64 (key width 1 + O > 64), which the native merge used to refuse as a
+    corrupt message."""
+    port = _free_port()
+    mp.spawn(_worker_keys_wide, args=(2, port, str(tmp_path), O), nprocs=2, join=True)
+    assert os.path.exists(tmp_path / 'wok0') and os.path.exists(tmp_path / 'wok1')
+
+
 def test_merge_exchange_dedups_equal_keys_across_ranks_and_handles_empty_shards():
     """Host side of the key exchange: the same key found by two ranks is one row; a rank without beliefs contributes a
     zero-count message; per-belief indices follow the global belief order."""

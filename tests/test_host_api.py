@@ -588,3 +588,181 @@ def test_backup_in_belief_chunks_halves_until_one_fits_and_gives_the_block_resul
     solver._belief_chunk = None
     with pytest.raises(MemoryError):
         solver._backup_in_chunks(Dev(fits=0), vf, beliefs, False)
+
+
+def test_backup_in_belief_chunks_never_exceeds_the_engine_block_limit():
+    """A belief list longer than twice the engine's block limit: the first chunk (half the list) would be refused by the
+    engine with PBVI_EUNSUPPORTED, which Engine._ck raises as RuntimeError -- not the MemoryError the halving loop catches.
+    The chunk is clamped to BELIEF_BLOCK, so the refusal is never provoked, and the union of the chunks' rows is the
+    unchunked NumPy result."""
+    from types import SimpleNamespace
+    model, _ = load_POMDP_file(os.path.join(EXAMPLES, '4x3.95-no_loop_2_grid.POMDP'))
+    rng = np.random.default_rng(11)
+    S = model.state_count
+    vf = ValueFunction(model, rng.normal(size=(9, S)), rng.integers(0, model.action_count, 9))
+    bel = rng.random((37, S))
+    bel /= bel.sum(axis=1, keepdims=True)
+    beliefs = [Belief(model, r) for r in bel]
+    solver = PBVI_Solver(gamma=0.95, eps=1e-6)
+    LIMIT = 8
+    solver.BELIEF_BLOCK = LIMIT
+    assert len(beliefs) > 2 * LIMIT
+
+    class Dev:
+        """NumPy stand-in for the engine: blocks above `limit` are refused as pbvi_beliefs_select refuses them (status
+        PBVI_EUNSUPPORTED -> RuntimeError in Engine._ck), blocks above `fits` run out of memory."""
+        def __init__(self, limit, fits):
+            self.limit, self.fits, self.formulation, self.runs, self.alpha, self.block = limit, fits, 'auto', [], None, None
+
+        def set_formulation(self, which):
+            self.formulation = which
+
+        def sync_rows(self, which, objs, values_of, owner=None):
+            rows = np.array([values_of(x) for x in objs])
+            if which == 'alpha':
+                self.alpha = rows
+                return
+            if len(rows) > self.limit:
+                raise RuntimeError(f'pbvi engine error -4: at most {self.limit} beliefs per block')
+            self.block = rows
+
+        def run(self, gamma, prune):
+            if len(self.block) > self.fits:
+                self.alpha = self.block = None
+                raise MemoryError('stub: block too large')
+            self.runs.append(len(self.block))
+            return {}
+
+        def fetch(self):
+            rows, acts = solver._backup_numpy(model, self.block, self.alpha, False)
+            return SimpleNamespace(value_function_rows=lambda use_keep=False: (rows, acts))
+
+    want_rows, want_acts = solver._backup_numpy(model, bel, vf.alpha_vector_array, False)
+    want = ValueFunction(model, want_rows, want_acts)
+    srt = lambda v: v.alpha_vector_array[np.lexsort(v.alpha_vector_array.T[::-1])]
+    dev = Dev(limit=LIMIT, fits=LIMIT)
+    rows, acts = solver._backup_in_chunks(dev, vf, beliefs, False)
+    assert dev.runs == [8, 8, 8, 8, 5] and solver._belief_chunk == LIMIT
+    got = ValueFunction(model, rows, acts)
+    assert len(got) == len(want)
+    np.testing.assert_array_equal(srt(got), srt(want))
+    assert dev.formulation == 'auto'
+    # the block limit and a memory limit below it together: clamped first, then halved (8 -> 4 -> 2)
+    solver._belief_chunk = None
+    dev = Dev(limit=LIMIT, fits=3)
+    rows, acts = solver._backup_in_chunks(dev, vf, beliefs, False)
+    assert solver._belief_chunk == 2 and set(dev.runs) <= {1, 2} and sum(dev.runs) == len(beliefs)
+    np.testing.assert_array_equal(srt(ValueFunction(model, rows, acts)), srt(want))
+    # a chunk size remembered from a solve with a larger limit is clamped too
+    solver._belief_chunk = 3 * LIMIT
+    dev = Dev(limit=LIMIT, fits=LIMIT)
+    solver._backup_in_chunks(dev, vf, beliefs, False)
+    assert max(dev.runs) == LIMIT
+
+
+def _numpy_exchange_merge(all_meta, per, kw, n_total):
+    """The NumPy merge pbvi_exchange_merge replaced: distinct keys in order of first occurrence over the ranks'
+    messages, and per belief (global order) the position of its key."""
+    world = all_meta.shape[0]
+    rows, owner = [], []
+    for r in range(world):
+        c = int(all_meta[r, 0])
+        rows.append(all_meta[r, 1 + 3 * per:1 + 3 * per + c * kw].reshape(c, kw))
+        owner.append(np.full(c, r))
+    rows = np.concatenate(rows)
+    base = np.concatenate([[0], np.cumsum([int(all_meta[r, 0]) for r in range(world)])])
+    uniq, first, inv = np.unique(rows, axis=0, return_index=True, return_inverse=True)
+    order = np.argsort(first, kind='stable')                 # np.unique sorts: back to first-occurrence order
+    rank_of = np.empty(len(order), dtype=np.int64)
+    rank_of[order] = np.arange(len(order))
+    pos = rank_of[np.asarray(inv).reshape(-1)]
+    idx, act, keep = [], [], []
+    for r in range(world):
+        lo = min(r * per, n_total)
+        n = min(lo + per, n_total) - lo
+        idx.append(pos[base[r] + all_meta[r, 1:1 + n]])
+        act.append(all_meta[r, 1 + per:1 + per + n])
+        keep.append(all_meta[r, 1 + 2 * per:1 + 2 * per + n] != 0)
+    return rows[np.sort(first)], np.concatenate(idx), np.concatenate(act), np.concatenate(keep)
+
+
+@pytest.mark.parametrize('key_width', [3, 64, 65, 201])
+def test_exchange_merge_of_wide_keys_equals_the_numpy_merge(key_width):
+    """pbvi_exchange_merge (host code, no GPU) for key widths 1 + O up to and beyond 64 -- a model with 63, 64 or 200
+    observations -- against the NumPy merge it replaced.  Keys repeat within and across ranks and differ only in their LAST
+    entry in places, so a comparison that stopped at 64 entries would merge distinct keys."""
+    from pomdp_pbvi_exploration_amd.dist import merge_exchange
+    rng = np.random.default_rng(100 + key_width)
+    world, per, n_total = 3, 23, 3 * 23 - 4
+    pool = rng.integers(0, 5, size=(12, key_width)).astype(np.int32)
+    pool[1] = pool[0]
+    pool[1, -1] += 1                                         # equal up to the last entry
+    pool[3] = pool[2]
+    pool[3, 0] += 1
+    n_meta = 1 + 3 * per + per * key_width
+    allm = np.zeros((world, n_meta + 2), dtype=np.int32)     # a trailer may follow the payload
+    for r in range(world):
+        c = int(rng.integers(3, per + 1))
+        keys = pool[rng.integers(0, len(pool), c)]
+        n = min(per, n_total - r * per)
+        allm[r, 0] = c
+        allm[r, 1:1 + n] = rng.integers(0, c, n)
+        allm[r, 1 + per:1 + per + n] = rng.integers(0, 4, n)
+        allm[r, 1 + 2 * per:1 + 2 * per + n] = rng.integers(0, 2, n)
+        allm[r, 1 + 3 * per:1 + 3 * per + c * key_width] = keys.reshape(-1)
+    keys, idx, act, keep = merge_exchange(allm, per, key_width, n_total)
+    wk, wi, wa, wkeep = _numpy_exchange_merge(allm, per, key_width, n_total)
+    np.testing.assert_array_equal(keys, wk)
+    np.testing.assert_array_equal(idx, wi)
+    np.testing.assert_array_equal(act, wa)
+    np.testing.assert_array_equal(keep, wkeep)
+    assert len(keys) < sum(int(c) for c in allm[:, 0])       # the case does merge keys
+
+
+def test_exchange_merge_refuses_what_the_int32_message_cannot_hold():
+    """The bounds that replaced ``key_width <= 64``: a key needs at least one entry, and one message -- 1 + per (3 + key_width)
+    int32 words, addressed by int32 positions -- must fit the int32 range.  The second call passes every other check (the
+    stride is larger than the message, world * per and n_total are small), so only that bound can refuse it; it returns
+    before anything is read or allocated."""
+    import ctypes as C
+    from pomdp_pbvi_exploration_amd.dist import merge_exchange
+    from pomdp_pbvi_exploration_amd.engine import load_library
+    with pytest.raises(ValueError):
+        merge_exchange(np.zeros((1, 8), dtype=np.int32), 1, 0, 1)                     # no key at all
+    lib = load_library()
+    meta = np.zeros(8, dtype=np.int32)
+    out = np.zeros(8, dtype=np.int32)
+    per, kw = 2 ** 29, 5                                                               # per * (3 + kw) = 2^32
+    rc = lib.pbvi_exchange_merge(meta.ctypes.data, 1, 2 ** 40, per, kw, 1, out.ctypes.data, out.ctypes.data, out.ctypes.data,
+                                 out.ctypes.data)
+    assert rc == -1 and b'do not fit' in lib.pbvi_last_error()
+    per = (2 ** 31 - 1) // (kw + 3) + 1                                                # the first block size past the bound
+    rc = lib.pbvi_exchange_merge(meta.ctypes.data, 1, 2 ** 40, per, kw, 1, out.ctypes.data, out.ctypes.data, out.ctypes.data,
+                                 out.ctypes.data)
+    assert rc == -1 and b'do not fit' in lib.pbvi_last_error()
+
+
+def test_twin_rows_make_fp32_and_fp64_decisions_disagree_on_the_host():
+    """CPU check of the construction behind test_run_fetch_slot_overflow_falls_back_to_the_plain_order (no engine): emulated
+    fp32 accumulation, in either order and with or without a fused multiply-add, picks another row than fp64 for a large
+    share of the beliefs."""
+    from pomdp_pbvi_exploration_amd import synth
+    S, rs, rto, er, alpha, b = synth.twin_rows_case()
+    B = b.shape[0]
+    exact = np.argmax(b @ alpha.T, axis=1)
+    assert np.array_equal(exact, 2 * np.arange(B) + 1)       # fp64: always the twin
+    a32, b32 = alpha.astype(np.float32), b.astype(np.float32)
+    i = np.arange(B)
+    for fused in (False, True):
+        for order in (0, 1):
+            s0, s1 = (2 * i, 2 * i + 1) if order == 0 else (2 * i + 1, 2 * i)
+            score = np.empty((B, 2), dtype=np.float32)
+            for t in range(2):
+                row = 2 * i + t
+                first = (b32[i, s0] * a32[row, s0]).astype(np.float32)
+                if fused:
+                    score[:, t] = (first.astype(np.float64) + b32[i, s1].astype(np.float64) * a32[row, s1].astype(np.float64)).astype(np.float32)
+                else:
+                    score[:, t] = (first + (b32[i, s1] * a32[row, s1]).astype(np.float32)).astype(np.float32)
+            first_max = 2 * i + np.argmax(score, axis=1)
+            assert np.count_nonzero(first_max != exact) > B // 4, (fused, order, np.count_nonzero(first_max != exact))
