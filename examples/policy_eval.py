@@ -28,6 +28,8 @@ def main():
     ap.add_argument('--max-steps', type=int, default=300)
     ap.add_argument('--dtype', default='f32', choices=['f32', 'f64'])
     ap.add_argument('--grid', default='75x400')
+    ap.add_argument('--lookahead', type=int, default=0, choices=[0, 1],
+                    help='0: actions[argmax_v b.alpha_v] (the reference policy); 1: one-step lookahead argmax_a Q(b,a)')
     ap.add_argument('--cpu-steps', type=int, default=0, help='also time this many steps of the host NumPy path')
     args = ap.parse_args()
     set_quiet(True)
@@ -52,7 +54,7 @@ def main():
                                                           use_gpu=True, engine_dtype=args.dtype, print_progress=False)
     print(f'solve: S={m.S} expansions={len(hist.expansion_times)} |V|={len(vf)} in {time.perf_counter() - t0:.2f}s', flush=True)
 
-    agent = Agent(vf.model, vf)
+    agent = Agent(vf.model, vf, lookahead=args.lookahead, gamma=m.gamma)
     np.random.seed(1)
     t0 = time.perf_counter()
     totals, hists = agent.run_n_simulations_parallel(n=args.n, max_steps=args.max_steps, print_progress=False,
@@ -63,7 +65,7 @@ def main():
           f'belief-steps={steps} ({steps / wall:.0f} belief-steps/s)  reference CuPy: 41.8 s for 1000 x 300', flush=True)
 
     if args.cpu_steps > 0:
-        host_agent = Agent(model, vf.to_cpu())
+        host_agent = Agent(model, vf.to_cpu(), lookahead=args.lookahead, gamma=m.gamma)
         np.random.seed(1)
         t0 = time.perf_counter()
         _, hh = host_agent.run_n_simulations_parallel(n=args.n, max_steps=args.cpu_steps, print_progress=False,

@@ -303,6 +303,33 @@ int pbvi_prune_dominated(pbvi_engine_t* e, uint8_t* keep /* [V] */);
 int pbvi_value_max(pbvi_engine_t* e, double* out_value, int32_t* out_index);
 
 /*
+ * One-step lookahead values of the resident belief block over the working alpha set: the quantity the backup's action
+ * stage maximises (src/pomdp.py:1485-1506: Gamma :1485-1491, best_alpha_ind :1495, the per-action sums :1497-1505), for
+ * EVERY (belief, action), exact in fp64 whatever the engine's type (an fp32 engine reads its fp32 tables, alpha rows and
+ * beliefs and sums in fp64):
+ *   Q[b][a] = b . ER[:,a] + gamma * sum_o max_v b . Gamma[a,o,v,:]
+ *           = sum_s b[s] * ( ER[s,a] + gamma * sum_o sum_r RTO[s,a,o,r] * alpha[best_v[b,a,o]][rs[s,a,r]] )
+ * with best_v[b,a,o] = first argmax_v b . Gamma[a,o,v,:] decided by the backup's own scoring, argmax and near-tie
+ * refinement stages (every setting of pbvi_set_formulation, pbvi_set_f64_screen, pbvi_set_score_split,
+ * pbvi_set_fused_projection and pbvi_set_gamma_tiling applies as it does to pbvi_backup_run: a Gamma-tiled call WORKS and
+ * returns what the untiled call returns).  An observation that is impossible for (b, a) adds 0.  A one-step lookahead
+ * policy executes a*(b) = argmax_a Q[b][a].
+ *   out_q      [B][A] double, caller's belief order           (required: NULL gives PBVI_EINVAL)
+ *   out_action [B] int32, may be NULL: the first maximum over a of the out_q row being returned, so
+ *              out_action[b] == argmax_a out_q[b][:] holds EXACTLY, by construction (np.argmax semantics)
+ *   out_best_v [B][A][O] int32, may be NULL: best_alpha_ind (src/pomdp.py:1495)
+ * The sums run over each belief's non-zero 32-state tiles in a fixed order without atomics: the same bits on every run, and
+ * the same bits from every pipeline setting that decides the same best_v.  No row is deduplicated, assembled or moved.
+ * The belief block, the alpha set and both row stores are left as they were: a later pbvi_backup_run / pbvi_value_max
+ * returns what it would have returned without this call.  The stage buffers of the backup are re-used, however: the
+ * results of an EARLIER pbvi_backup_run can no longer be fetched afterwards (the fetches report that no result is resident).
+ * PBVI_EINVAL without a resident belief block or alpha set (as pbvi_backup_run); PBVI_EUNSUPPORTED, with a
+ * pbvi_last_error text, on a PBVI_DENSE engine.
+ */
+int pbvi_q_values(pbvi_engine_t* e, double gamma, double* out_q /* [B][A] */, int32_t* out_action /* [B], may be NULL */,
+                  int32_t* out_best_v /* [B][A][O], may be NULL */);
+
+/*
  * The same maxima for rows [0, n) of the BELIEF STORE (pbvi_belief_store_append / pbvi_belief_walk order) against the
  * working alpha set, with the store itself as the GEMM operand: nothing is gathered or sorted and the zero maps and
  * tile lists of rows scored before are kept.  compute_change (src/pomdp.py:2141-2169) scores the whole accumulated

@@ -231,6 +231,18 @@ hipError_t launch_refine_action(const T* bel, int ldb, int B, const T* alpha, in
                                 const double* best_score, const double* err, double* val_exact /* [B][A][1+O][ACTION_SPLIT] scratch */,
                                 int32_t* action, hipStream_t st, const uint8_t* acand = nullptr /* launch_action's */);
 
+// One-step lookahead values (pbvi_q_values), exact in f64 whatever T, over the beliefs' non-zero tiles (btl / btc required):
+//   q[b][a] = sum_s bel[b][s] * (ER[s,a] + gamma * sum_o sum_r rto[a][o][r][s] * alpha[best_v[b,a,o]][rs[a][r][s]])
+// for the rows of the resident block in ENGINE order (q: [B][A] scratch); triples with dead[b][a*O+o] != 0 add nothing.
+// A second kernel writes the caller-order results (perm: caller row of engine row b, nullptr = identity):
+//   q_out [B][A], action_out [B] = first maximum of q_out's row, best_out [B][A][O] (may be nullptr) = best_v's rows.
+// Fixed reduction order, no atomics: a function of (bel, alpha, model, best_v) alone, bit for bit.
+template <typename T>
+hipError_t launch_q_exact(const T* bel, int ldb, int B, const T* alpha, int lda, int V, ModelView<T> mv, double gamma,
+                          const int32_t* btl, const int32_t* btc, const int32_t* best_v, const uint8_t* dead,
+                          const int32_t* perm, double* q, double* q_out, int32_t* action_out, int32_t* best_out,
+                          hipStream_t st);
+
 // K3: out[u][s] = ER[s,a*] + sum_o gamma * sum_r rto[a*][o][r][s] * alpha[v*[b,a*,o]][rs[a*][r][s]], b = rows[u]
 // (rows/n_rows on the device: only the unique (a*, v*) keys are assembled; nullptr = every belief)
 template <typename T>

@@ -1827,6 +1827,112 @@ hipError_t launch_refine_action(const T* bel, int ldb, int B, const T* alpha, in
 }
 
 // ------------------------------------------------------------------------- //
+// One-step lookahead values of every (belief, action) of the block, exact in f64 (pbvi_q_values):
+//   q[b][a] = sum_s b[s] * ( ER[s,a] + gamma * sum_r sum_o rto[a][o][r][s] * alpha[best_v[b,a,o]][rs[a][r][s]] )
+// One block per (b, a) -- unlike k_refine_action's queue of a few dozen beliefs this pass has B * A items, enough to fill
+// the device without cutting a dot into parts, and the 1 + O terms of an action share one walk over the belief's tile
+// list: the belief, the reward row and the successor indices rs[a][r][s] are read once per state and serve all O gathers.
+// Half-wave q of the block's 8 takes list entries q, q + 8, ...; Q_IN_FLIGHT entries per half-wave are in flight with
+// unconditional loads.  Reduction: per-thread partials in a fixed order, xor-shuffle wave sum, then the 4 wave sums in
+// order (block_sum): no atomics, the same bits on every run, and -- the walk depends on the belief's tile list alone --
+// the same bits from every pipeline that hands over the same best_v.  Dead triples are skipped (they would add exact zeros).
+// ------------------------------------------------------------------------- //
+constexpr int Q_IN_FLIGHT = 4;
+template <typename T>
+__global__ void __launch_bounds__(256) k_q_exact(const T* __restrict__ bel, int ldb, const T* __restrict__ alpha, int lda, int V,
+                                                 ModelView<T> mv, double gamma, const int32_t* __restrict__ btl,
+                                                 const int32_t* __restrict__ btc, const int32_t* __restrict__ best_v,
+                                                 const uint8_t* __restrict__ dead /* [B][A*O] or nullptr */,
+                                                 double* __restrict__ q /* [B][A] */) {
+    __shared__ double red[4];
+    const int b = blockIdx.x, a = blockIdx.y;
+    const int k_tiles = mv.S_pad >> 5;
+    const int n = btc[b];
+    const int32_t* __restrict__ list = btl + (int64_t)b * k_tiles;
+    const T* __restrict__ brow = bel + (int64_t)b * ldb;
+    const T* __restrict__ er = mv.er + (int64_t)a * mv.S_pad;
+    const int32_t* __restrict__ rs = mv.rs + (int64_t)a * mv.R * mv.S_pad;
+    const T* __restrict__ rto = mv.rto + (int64_t)a * mv.O * mv.R * mv.S_pad;
+    const int64_t e0 = ((int64_t)b * mv.A + a) * mv.O;
+    const int hq = threadIdx.x >> 5, l = threadIdx.x & 31;
+    double acc[Q_IN_FLIGHT];
+#pragma unroll
+    for (int j = 0; j < Q_IN_FLIGHT; ++j) acc[j] = 0.0;
+    for (int i0 = hq; i0 < n; i0 += 8 * Q_IN_FLIGHT) {
+        int s[Q_IN_FLIGHT];
+        bool ok[Q_IN_FLIGHT];
+        double g[Q_IN_FLIGHT];
+#pragma unroll
+        for (int j = 0; j < Q_IN_FLIGHT; ++j) {
+            const int i = i0 + 8 * j;
+            ok[j] = i < n;
+            s[j] = list[ok[j] ? i : i0] * 32 + l;            // < S_pad; pads hold rs = 0, rto = 0, er = 0, b = 0
+            g[j] = 0.0;
+        }
+        for (int r = 0; r < mv.R; ++r) {
+            const int64_t ro = (int64_t)r * mv.S_pad;
+            int idx[Q_IN_FLIGHT];
+#pragma unroll
+            for (int j = 0; j < Q_IN_FLIGHT; ++j) idx[j] = rs[ro + s[j]];
+            for (int o = 0; o < mv.O; ++o) {
+                if (dead != nullptr && dead[e0 + o]) continue;       // block-uniform
+                int v = best_v[e0 + o];
+                v = v < 0 ? 0 : (v < V ? v : V - 1);
+                const T* __restrict__ arow = alpha + (int64_t)v * lda;
+                const T* __restrict__ t = rto + ((int64_t)o * mv.R + r) * mv.S_pad;
+#pragma unroll
+                for (int j = 0; j < Q_IN_FLIGHT; ++j) g[j] += (double)t[s[j]] * (double)arow[idx[j]];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < Q_IN_FLIGHT; ++j)
+            acc[j] += ok[j] ? (double)brow[s[j]] * ((double)er[s[j]] + gamma * g[j]) : 0.0;
+    }
+    const double v = block_sum((acc[0] + acc[1]) + (acc[2] + acc[3]), red);
+    if (threadIdx.x == 0) q[(int64_t)b * mv.A + a] = v;
+}
+
+// Tail of the pass: first maximum over a of the q row being returned (np.argmax: a NaN counts as the maximum), and the
+// row, the action and (best_o != nullptr) the belief's best_v entries moved to the caller's belief order.
+__global__ void k_q_finish(int A, int AO, const int32_t* __restrict__ perm /* or nullptr */, const double* __restrict__ q,
+                           const int32_t* __restrict__ best_v, double* __restrict__ q_o, int32_t* __restrict__ action_o,
+                           int32_t* __restrict__ best_o) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int d = perm ? perm[b] : b;
+    if (tid == 0) {
+        const double* row = q + (int64_t)b * A;
+        int best = 0;
+        double bv = row[0];
+        q_o[(int64_t)d * A] = bv;
+        for (int a = 1; a < A; ++a) {
+            const double x = row[a];
+            q_o[(int64_t)d * A + a] = x;
+            if (x > bv || (x != x && bv == bv)) {
+                bv = x;
+                best = a;
+            }
+        }
+        action_o[d] = best;
+    }
+    if (best_o != nullptr)
+        for (int j = tid; j < AO; j += blockDim.x) best_o[(int64_t)d * AO + j] = best_v[(int64_t)b * AO + j];
+}
+
+template <typename T>
+hipError_t launch_q_exact(const T* bel, int ldb, int B, const T* alpha, int lda, int V, ModelView<T> mv, double gamma,
+                          const int32_t* btl, const int32_t* btc, const int32_t* best_v, const uint8_t* dead,
+                          const int32_t* perm, double* q, double* q_out, int32_t* action_out, int32_t* best_out,
+                          hipStream_t st) {
+    if (B <= 0) return hipSuccess;
+    if (V <= 0 || mv.A > 65535 || btl == nullptr || btc == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_q_exact<T>, dim3(B, mv.A), dim3(256), 0, st, bel, ldb, alpha, lda, V, mv, gamma, btl, btc, best_v, dead, q);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_q_finish, dim3(B), dim3(64), 0, st, mv.A, mv.A * mv.O, perm, q, best_v, q_out, action_out, best_out);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------- //
 // K3: alpha' rows.  src/pomdp.py:1497-1506 restricted to the winning action:
 //   out[b][s] = ER[s,a*] + ((G0 + G1) + G2 ...),  G_o = gamma * sum_r rto * alpha_{v*[b,a*,o]}[rs]
 // evaluated in f64 in the reference's association, rounded once to T.
@@ -2386,6 +2492,9 @@ hipError_t launch_walk_step(const double* base, ModelView<T> mv, const double* r
                                                 const int32_t*, const int32_t*, const int32_t*, const int*,            \
                                                 const double*, const double*, const int32_t*, const double*,           \
                                                 const double*, double*, int32_t*, hipStream_t, const uint8_t*);                        \
+    template hipError_t launch_q_exact<T>(const T*, int, int, const T*, int, int, ModelView<T>, double, const int32_t*,  \
+                                          const int32_t*, const int32_t*, const uint8_t*, const int32_t*, double*, double*, \
+                                          int32_t*, int32_t*, hipStream_t);                                              \
     template hipError_t launch_assemble<T>(const T*, int, ModelView<T>, double, const int32_t*, const int32_t*,        \
                                            const int32_t*, const int*, int, T*, int, hipStream_t);                     \
     template hipError_t launch_expand_rows<T>(const T*, const int32_t*, T*, int, int, hipStream_t);                    \

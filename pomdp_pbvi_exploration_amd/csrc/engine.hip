@@ -772,6 +772,7 @@ class EngineBase {
     virtual int64_t beliefs_count() const = 0;
     virtual int walk_keys(int64_t n, uint64_t* out_keys) = 0;
     virtual int backup_value_max(double* out_value) = 0;
+    virtual int q_values(double gamma, double* out_q, int32_t* out_action, int32_t* out_best) = 0;
 };
 
 template <typename T>
@@ -851,6 +852,8 @@ class EngineT : public EngineBase {
     size_t host_stage_cap_ = 0;
     DevBuf keys_tmp_, keys_act_, keys_best_, keys_rows_;    // unique-row keys out / rows from keys in (multi-GPU exchange)
     DevBuf acand_;                                           // [B][A] action inside the window (k_action_select -> k_refine_action)
+    DevBuf q_, q_res_, q_act_;                               // pbvi_q_values: q [B][A] in engine order / caller order, its argmax [B]
+    bool q_only_ = false, q_want_best_ = false;              // run_pipeline stops behind the refinement and runs launch_q_exact
     DevBuf rf_q2_, rf_q2p_, rf_q2d_;                         // k_refine_split: entries / candidates, partial scores, arrival counters
     DevBuf rf_v_, rf_slot_, rf_sc_, rf_entry_, rf_n_, rf_tiles_, rf_ibv_, rf_ibi_, rf_cnt_, rf_W_, rf_Cx_, rf_nzW_, rf_klW_, rf_kcW_;   // refinement work list
     int formulation_ = 0;                                   // 0 auto, 1 project alpha-vectors, 2 project beliefs
@@ -940,7 +943,7 @@ class EngineT : public EngineBase {
                          &action_res_, &best_res_, &rep_, &uniq_, &inv_, &slot_, &out_full_, &btl_, &btc_, &val_exact_, &store_[0], &store_[1], &ids_, &in_ptr_, &in_src_, &bu_act_, &bu_obs_,
                          &bu_unnorm_, &bu_mass_, &bu_out_, &bu_row_, &walk64_, &rto64_, &bp_, &nzP_, &pmag_, &prd_, &keys_tmp_, &keys_act_, &keys_best_, &keys_rows_, &rf_v_, &rf_slot_, &rf_sc_, &rf_entry_, &rf_n_, &rf_tiles_,
                          &snz_, &sbtl_, &sbtc_, &vmax_bk_, &rf_ibv_, &rf_ibi_, &rf_cnt_, &rf_W_, &rf_Cx_, &rf_nzW_, &rf_klW_, &rf_kcW_,
-                         &dense_, &nzD_, &nzAlpha_, &prod_, &klistD_, &kcountD_, &nchunksD_, &mat_, &vlist_, &irr_, &rowflags_, &nzBw_, &scr_flag_, &ctile_, &acand_, &rf_q2_, &rf_q2p_, &rf_q2d_, &e_bv_, &e_bs_, &e_err_, &e_rdot_, &e_act_, &e_ares_, &e_bres_, &e_rep_, &e_uniq_, &e_inv_, &e_slotd_, &e_cnt_, &e_out_, &e_slot_, &scores_, &chain_max_};
+                         &dense_, &nzD_, &nzAlpha_, &prod_, &klistD_, &kcountD_, &nchunksD_, &mat_, &vlist_, &irr_, &rowflags_, &nzBw_, &scr_flag_, &ctile_, &acand_, &q_, &q_res_, &q_act_, &rf_q2_, &rf_q2p_, &rf_q2d_, &e_bv_, &e_bs_, &e_err_, &e_rdot_, &e_act_, &e_ares_, &e_bres_, &e_rep_, &e_uniq_, &e_inv_, &e_slotd_, &e_cnt_, &e_out_, &e_slot_, &scores_, &chain_max_};
         // every call is checked only to name a failure when PBVI_DEBUG is set; the thread's sticky last-error is cleared at
         // the end either way, so that a later launch check does not report a stale error of this teardown
         static const bool dbg = getenv("PBVI_DEBUG") != nullptr;
@@ -1734,7 +1737,7 @@ class EngineT : public EngineBase {
                           &bu_mass_, &bu_out_, &bu_row_, &walk64_, &bp_, &nzP_, &pmag_, &prd_, &keys_tmp_, &keys_act_, &keys_best_,
                           &keys_rows_, &rf_v_, &rf_slot_, &rf_sc_, &rf_entry_, &rf_n_, &rf_tiles_, &snz_, &sbtl_, &sbtc_, &vmax_bk_,
                           &rf_ibv_, &rf_ibi_, &rf_cnt_, &rf_W_, &rf_Cx_, &rf_nzW_, &rf_klW_, &rf_kcW_, &nzAlpha_, &prod_, &klistD_,
-                          &kcountD_, &nchunksD_, &mat_, &vlist_, &rowflags_, &ctile_, &acand_, &rf_q2_, &rf_q2p_, &rf_q2d_, &e_bv_, &e_bs_, &e_err_, &e_rdot_, &e_act_, &e_ares_, &e_bres_, &e_rep_, &e_uniq_, &e_inv_, &e_slotd_, &e_out_, &e_slot_, &scores_};
+                          &kcountD_, &nchunksD_, &mat_, &vlist_, &rowflags_, &ctile_, &acand_, &q_, &q_res_, &q_act_, &rf_q2_, &rf_q2p_, &rf_q2d_, &e_bv_, &e_bs_, &e_err_, &e_rdot_, &e_act_, &e_ares_, &e_bres_, &e_rep_, &e_uniq_, &e_inv_, &e_slotd_, &e_out_, &e_slot_, &scores_};
         for (DevBuf* b : drop) {
             bytes_ -= (int64_t)b->cap;
             b->release();
@@ -2272,6 +2275,27 @@ class EngineT : public EngineBase {
                 if (out_index) out_index[h_perm_[(size_t)i]] = ti[(size_t)i];
             }
         return PBVI_OK;
+    }
+
+    // One-step lookahead values of the resident block against the working alpha set: the backup's pipeline up to best_v
+    // (run_pipeline with q_only_), launch_q_exact behind it, results copied out in the caller's belief order.  best_v_ and
+    // the other stage buffers are overwritten, so an earlier backup's results are no longer fetchable afterwards.
+    int q_values(double gamma, double* out_q, int32_t* out_action, int32_t* out_best) override {
+        if (!out_q) FAIL(PBVI_EINVAL, "q_values: NULL out_q");
+        if (V_ <= 0) FAIL(PBVI_EINVAL, "q_values: no alpha set resident (call pbvi_alpha_set)");
+        if (B_ <= 0) FAIL(PBVI_EINVAL, "q_values: no belief block resident (call pbvi_beliefs_set)");
+        if (mode_ != PBVI_SPARSE) FAIL(PBVI_EUNSUPPORTED, "q_values: not available on a PBVI_DENSE engine (create it with PBVI_SPARSE)");
+        q_only_ = true;
+        q_want_best_ = out_best != nullptr;
+        int rc = backup_run(gamma, 0, nullptr);
+        q_only_ = q_want_best_ = false;
+        have_result_ = have_bk_vmax_ = false;
+        if (rc) return rc;
+        if ((rc = out_begin())) return rc;
+        if ((rc = out_add(out_q, q_res_.p, (size_t)B_ * A_ * sizeof(double)))) return rc;
+        if (out_action && (rc = out_add(out_action, q_act_.p, (size_t)B_ * sizeof(int32_t)))) return rc;
+        if (out_best && (rc = out_add(out_best, best_res_.p, (size_t)B_ * A_ * O_ * sizeof(int32_t)))) return rc;
+        return out_finish();
     }
 
     int64_t store_count(int which) const override { return (which == 0 || which == 1) ? store_rows_[which] : -1; }
@@ -3273,7 +3297,7 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
     if ((rc = action_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
     if ((rc = aqueue_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
     if ((rc = acand_.ensure((size_t)B_ * A_, &bytes_))) return rc;
-    if ((rc = out_.ensure((size_t)B_ * S_ * sizeof(T), &bytes_))) return rc;
+    if (!q_only_ && (rc = out_.ensure((size_t)B_ * S_ * sizeof(T), &bytes_))) return rc;
     if ((rc = keep_.ensure((size_t)B_, &bytes_))) return rc;
     int* qcount = counters_.as<int>();
     int* aqcount = counters_.as<int>() + 1;
@@ -3320,7 +3344,7 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
                               windows ? btc_.as<int32_t>() : nullptr, prd_.as<double>(), side));
     }
     // (run_fetch's provisional pipeline: its counters are cleared here, beside the projection, not in front of its kernels)
-    const bool early_wanted = windows && early_rows_ != nullptr && !(flags & PBVI_BELIEF_DOMINANCE) && early_cap_ >= B_ && !no_side;
+    const bool early_wanted = windows && !q_only_ && early_rows_ != nullptr && !(flags & PBVI_BELIEF_DOMINANCE) && early_cap_ >= B_ && !no_side;
     if (early_wanted) {
         if ((rc = e_cnt_.ensure(4 * sizeof(int), &bytes_))) return rc;
         HIPCHK(hipMemsetAsync(e_cnt_.p, 0, 4 * sizeof(int), side));
@@ -3480,7 +3504,8 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
         static const bool no_spec = getenv("PBVI_NO_SPECULATION") != nullptr;      // debug / A-B only
         // (not with the belief-dominance test: its own value-max refinement re-uses the work-list buffers, so the
         // deferred entries of this one have to be finished first)
-        speculate = !no_spec && last_deferred_nothing_ && work.items_v != nullptr && !(flags & PBVI_BELIEF_DOMINANCE);
+        // (nor for pbvi_q_values, whose one stage behind the refinement needs the final best_v)
+        speculate = !no_spec && !q_only_ && last_deferred_nothing_ && work.items_v != nullptr && !(flags & PBVI_BELIEF_DOMINANCE);
         HIPCHK((launch_refine_scan<T, TS>(true, sv, (int)V_, AO, (int)pairs, queue_.as<int32_t>(), qcount, bel_.as<T>(), S_pad_,
                                           alpha_.as<T>(), S_pad_, mv, gamma, btl_.as<int32_t>(), btc_.as<int32_t>(),
                                           nzB_.as<uint8_t>(), best_v_.as<int32_t>(), best_score_.as<double>(), err_.as<double>(),
@@ -3505,6 +3530,32 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
         HIPCHK(hipMemcpyAsync(kc_pin_, scorer.kcount_.p, n_kcount * sizeof(int), hipMemcpyDeviceToHost, stream_));
     HIPCHK(hipEventRecord(ev_[4], stream_));
     const int32_t* perm = sorted_ ? perm_.as<int32_t>() : nullptr;
+    if (q_only_) {   // pbvi_q_values: best_v is final; exact Q of every (belief, action) from it, and nothing else
+        if (xr_pending) HIPCHK(hipStreamWaitEvent(stream_, ev_xr_[1], 0));       // (the side stream still reads this call's slabs)
+        if (!btl_valid_) {   // pure fp64 scoring: k_dead did not run; the same lists from the beliefs alone
+            if ((rc = btl_.ensure((size_t)B_ * k_tiles * sizeof(int32_t), &bytes_))) return rc;
+            if ((rc = btc_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
+            HIPCHK(launch_belief_tiles<T>(bel_.as<T>(), S_pad_, (int)B_, S_, k_tiles, btl_.as<int32_t>(), btc_.as<int32_t>(), stream_));
+            btl_valid_ = true;
+        }
+        if ((rc = q_.ensure((size_t)B_ * A_ * sizeof(double), &bytes_))) return rc;
+        if ((rc = q_res_.ensure((size_t)B_ * A_ * sizeof(double), &bytes_))) return rc;
+        if ((rc = q_act_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
+        if (q_want_best_ && (rc = best_res_.ensure((size_t)pairs * sizeof(int32_t), &bytes_))) return rc;
+        HIPCHK(launch_q_exact<T>(bel_.as<T>(), S_pad_, (int)B_, alpha_.as<T>(), S_pad_, (int)V_, mv, gamma, btl_.as<int32_t>(),
+                                 btc_.as<int32_t>(), best_v_.as<int32_t>(), windows ? dead_.as<uint8_t>() : nullptr, perm,
+                                 q_.as<double>(), q_res_.as<double>(), q_act_.as<int32_t>(),
+                                 q_want_best_ ? best_res_.as<int32_t>() : nullptr, stream_));
+        int* f = pinned_flag();
+        if (!f) FAIL(PBVI_ENOMEM, "q_values: pinned flag");
+        HIPCHK(hipMemcpyAsync(f + 16, counters_.p, 8 * sizeof(int), hipMemcpyDeviceToHost, stream_));
+        if constexpr (screened) {
+            if (scr_flag_.p) HIPCHK(hipMemcpyAsync(f + 1, scr_flag_.p, sizeof(int), hipMemcpyDeviceToHost, stream_));
+        }
+        HIPCHK(hipStreamSynchronize(stream_));
+        if (windows && dead_count_ < 0) dead_count_ = f[16 + 5];    // k_dead counted this block's dead triples in this call
+        return PBVI_OK;
+    }
     int* ucount = counters_.as<int>() + 3;
     int h_cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // all counters in the one read-back that precedes the final sync
     auto later_stages = [&]() -> int {
@@ -4088,6 +4139,10 @@ int pbvi_backup(pbvi_engine_t* e, const void* beliefs, int64_t B, double gamma, 
     rc = e->impl->backup_run(gamma, flags, stats);
     if (rc) return rc;
     return e->impl->backup_fetch(out_alpha, out_action, out_best_alpha, out_keep);
+}
+int pbvi_q_values(pbvi_engine_t* e, double gamma, double* out_q, int32_t* out_action, int32_t* out_best_v) {
+    NEED(e);
+    return e->impl->q_values(gamma, out_q, out_action, out_best_v);
 }
 int pbvi_prune_dominated(pbvi_engine_t* e, uint8_t* keep) {
     NEED(e);

@@ -34,7 +34,7 @@ EXPORTS = [
     'pbvi_belief_walk_keys', 'pbvi_backup_fetch_value_max',
     'pbvi_backup_fetch_compact', 'pbvi_host_alloc', 'pbvi_host_free', 'pbvi_debug_gemm_dense',
     'pbvi_backup_fetch_exchange_padded', 'pbvi_assemble_rows_store', 'pbvi_exchange_merge', 'pbvi_backup_run_fetch', 'pbvi_debug_alloc_limit', 'pbvi_engine_after_oom', 'pbvi_set_f64_screen', 'pbvi_set_fused_projection', 'pbvi_backup_fetch_row_hashes', 'pbvi_set_score_split',
-    'pbvi_set_gamma_tiling', 'pbvi_gamma_tiling_plan',
+    'pbvi_set_gamma_tiling', 'pbvi_gamma_tiling_plan', 'pbvi_q_values',
 ]
 
 
@@ -100,6 +100,7 @@ def load_library(path: str = LIB_PATH):
         'pbvi_prune_dominated': (C.c_int, [vp, u8p]),
         'pbvi_value_max': (C.c_int, [vp, f64p, i32p]),
         'pbvi_value_max_store': (C.c_int, [vp, C.c_int64, f64p, i32p]),
+        'pbvi_q_values': (C.c_int, [vp, C.c_double, f64p, i32p, i32p]),
         'pbvi_belief_store_count': (C.c_int64, [vp]),
         'pbvi_backup_fetch_value_max': (C.c_int, [vp, f64p]),
         'pbvi_belief_walk_keys': (C.c_int, [vp, C.c_int64, C.POINTER(C.c_uint64)]),
@@ -947,6 +948,20 @@ class Engine:
         self._ck(self._lib.pbvi_value_max(self._h, val.ctypes.data_as(C.POINTER(C.c_double)),
                                         idx.ctypes.data_as(C.POINTER(C.c_int32))))
         return val, idx.astype(np.int64)
+
+    def q_values_resident(self, gamma: float, want_best: bool = False):
+        """One-step lookahead values of the resident belief block over the working alpha set (``pbvi_q_values``):
+        ``(Q [B,A] f64, argmax_a Q [B])`` with ``Q[b,a] = b.ER[:,a] + gamma * sum_o max_v b.Gamma[a,o,v]``
+        (``src/pomdp.py:1485-1506``); ``want_best=True`` appends ``best_alpha_ind [B,A,O]``."""
+        q = np.empty((self.B, self.A), dtype=np.float64)
+        act = np.empty(self.B, dtype=np.int32)
+        best = np.empty((self.B, self.A, self.O), dtype=np.int32) if want_best else None
+        self._ck(self._lib.pbvi_q_values(self._h, float(gamma), q.ctypes.data_as(C.POINTER(C.c_double)),
+                                       act.ctypes.data_as(C.POINTER(C.c_int32)),
+                                       best.ctypes.data_as(C.POINTER(C.c_int32)) if want_best else None))
+        if want_best:
+            return q, act.astype(np.int64), best.astype(np.int64)
+        return q, act.astype(np.int64)
 
     def belief_update(self, beliefs: np.ndarray, actions, observations) -> np.ndarray:
         """Batched Bayes step: row b of the result is ``Belief(beliefs[b]).update(actions[b], observations[b])``

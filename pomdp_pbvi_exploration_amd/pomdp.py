@@ -570,6 +570,22 @@ class PBVI_Solver(Solver):
             rows, acts = rows[better], acts[better]
         return rows, acts
 
+    def q_values(self, model: Model, beliefs, value_function: ValueFunction) -> np.ndarray:
+        """One-step lookahead values ``Q[b,a] = b.ER[:,a] + gamma * sum_o max_v b.Gamma[a,o,v]`` (Gamma as in
+        ``src/pomdp.py:1485-1491``; the quantity the backup maximises over ``a``, ``:1495-1505``) of a ``BeliefSet``, a
+        ``Belief`` or a ``[B,S]`` array, as ``[B,A]`` float64.  With the value function on the GPU the HIP engine
+        computes it (``pbvi_q_values``), in blocks of ``_DeviceBeliefBlock.CHUNK`` beliefs; otherwise NumPy does."""
+        if isinstance(beliefs, BeliefSet):
+            arr = beliefs.belief_array
+        elif isinstance(beliefs, Belief):
+            arr = beliefs.values[None, :]
+        else:
+            arr = np.asarray(beliefs)
+            arr = arr[None, :] if arr.ndim == 1 else arr
+        if value_function.is_on_gpu:
+            return _q_values_device(value_function, arr, self.gamma)[0]
+        return _q_values_numpy(model.cpu_model if model.is_on_gpu else model, arr, value_function.alpha_vector_array, self.gamma)
+
     # ------------------------------------------------------------------ #
     # belief expansion (host side; out of the accelerated path)
     # ------------------------------------------------------------------ #
@@ -1092,6 +1108,31 @@ class SimulationSet:
         return rewards, observations
 
 
+def _q_values_numpy(model: Model, b: np.ndarray, alpha: np.ndarray, gamma: float) -> np.ndarray:
+    """``Q[b,a] = b.ER[:,a] + gamma * sum_o max_v b.Gamma[a,o,v]`` in the array statements of the host backup."""
+    V = alpha.shape[0]
+    alpha_r = alpha[np.arange(V)[:, None, None, None], model.reachable_states[None, :, :, :]]
+    gamma_aovs = gamma * np.einsum('saor,vsar->aovs', model.reachable_transitional_observation_table, alpha_r)
+    scores = np.tensordot(b, gamma_aovs, (1, 3))                                   # [B,A,O,V]
+    return np.matmul(b, model.expected_rewards_table) + np.sum(np.max(scores, axis=3), axis=2)
+
+
+def _q_values_device(value_function: ValueFunction, arr: np.ndarray, gamma: float):
+    """``(Q [B,A], argmax_a Q [B])`` from the HIP engine, ``_DeviceBeliefBlock.CHUNK`` beliefs at a time."""
+    eng = value_function.model.engine
+    eng.sync_rows('alpha', value_function.alpha_vector_list, lambda v: v.values)
+    qs, acts = [], []
+    for i0 in range(0, arr.shape[0], _DeviceBeliefBlock.CHUNK):
+        eng.set_beliefs(arr[i0:i0 + _DeviceBeliefBlock.CHUNK])
+        q, a = eng.q_values_resident(gamma)
+        qs.append(q)
+        acts.append(a)
+    if len(qs) == 1:
+        return qs[0], acts[0]
+    A = value_function.model.action_count
+    return (np.concatenate(qs) if qs else np.zeros((0, A))), (np.concatenate(acts) if acts else np.zeros(0, dtype=np.int64))
+
+
 class _HostBeliefBlock:
     """Belief block of the parallel simulator held in NumPy (reference CPU statements, ``:3029``, ``:3306-3311``)."""
 
@@ -1100,6 +1141,10 @@ class _HostBeliefBlock:
 
     def best_vectors(self) -> np.ndarray:
         return np.argmax(np.matmul(self.b, self.alpha.T), axis=1)
+
+    def best_actions(self, gamma: float) -> np.ndarray:
+        """One-step lookahead: ``argmax_a Q(b,a)`` of every belief of the block."""
+        return np.argmax(_q_values_numpy(self.m, self.b, self.alpha, gamma), axis=1)
 
     def advance(self, actions: np.ndarray, observations: np.ndarray, keep: np.ndarray) -> None:
         m, n = self.m, self.b.shape[0]
@@ -1140,6 +1185,17 @@ class _DeviceBeliefBlock:
             out.append(self.eng.max_value_resident()[1])
         return np.concatenate(out) if out else np.zeros(0, dtype=np.int64)
 
+    def best_actions(self, gamma: float) -> np.ndarray:
+        """One-step lookahead: ``argmax_a Q(b,a)`` of every belief of the block (``pbvi_q_values``; the resident block
+        stays on the device)."""
+        if self.chunks is None:
+            return self.eng.q_values_resident(gamma)[1]
+        out = []
+        for c in self.chunks:
+            self.eng.set_beliefs(c)
+            out.append(self.eng.q_values_resident(gamma)[1])
+        return np.concatenate(out) if out else np.zeros(0, dtype=np.int64)
+
     def advance(self, actions: np.ndarray, observations: np.ndarray, keep: np.ndarray) -> None:
         if self.chunks is None:
             self.eng.advance_beliefs(actions, observations, keep)
@@ -1159,11 +1215,20 @@ class _DeviceBeliefBlock:
 
 class Agent:
     """Greedy agent over a value function (``src/pomdp.py:2948-3380``): best action for a belief, single
-    simulations, and n simulations advanced together with the belief block on the host or in the HIP engine."""
+    simulations, and n simulations advanced together with the belief block on the host or in the HIP engine.
 
-    def __init__(self, model: Model, value_function: Union[ValueFunction, None] = None) -> None:
+    ``lookahead=0``: the reference's policy, ``actions[argmax_v b.alpha_v]``.  ``lookahead=1``: the one-step lookahead
+    policy ``argmax_a Q(b,a)``, ``Q(b,a) = b.ER[:,a] + gamma * sum_o max_v b.Gamma[a,o,v]`` (``PBVI_Solver.q_values``),
+    with discount ``gamma``."""
+
+    def __init__(self, model: Model, value_function: Union[ValueFunction, None] = None, lookahead: int = 0,
+                 gamma: float = 0.99) -> None:
+        if lookahead not in (0, 1):
+            raise ValueError(f'lookahead must be 0 or 1, not {lookahead!r}')
         self.model = model
         self.value_function = value_function
+        self.lookahead = lookahead
+        self.gamma = gamma
 
     def train(self, solver: PBVI_Solver, expansions: int, horizon: int) -> SolverHistory:
         self.value_function, hist = solver.solve(self.model, expansions, horizon)
@@ -1175,6 +1240,12 @@ class Agent:
         assert vf is not None, "No value function, training probably has to be run..."
         single = isinstance(belief, Belief)
         arr = belief.values[None, :] if single else belief
+        if self.lookahead == 1:
+            if vf.is_on_gpu:
+                acts = _q_values_device(vf, arr, self.gamma)[1]
+            else:
+                acts = np.argmax(_q_values_numpy(vf.model, arr, vf.alpha_vector_array, self.gamma), axis=1)
+            return int(acts[0]) if single else acts
         if vf.is_on_gpu:
             eng = vf.model.engine
             eng.sync_rows('alpha', vf.alpha_vector_list, lambda v: v.values)
@@ -1277,7 +1348,7 @@ class Agent:
 
         t0 = datetime.now()
         for i in range(max_steps):
-            best_actions = vf.actions[block.best_vectors()]
+            best_actions = block.best_actions(self.gamma) if self.lookahead == 1 else vf.actions[block.best_vectors()]
             rewards, observations = simulator_set.run_actions(best_actions)
             finished = simulator_set.is_done
             block.advance(best_actions, observations, ~finished)
