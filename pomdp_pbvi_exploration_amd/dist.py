@@ -25,7 +25,9 @@ return value as the single-process backup.  It is opt-in because it is only corr
 the same model, belief set and value function -- ranks that run independent experiments (the reference's
 one-process-per-GPU ``run_test.py`` pattern) must not be coupled by a collective they did not ask for.  What can be
 checked is checked: every message carries ``(n_total, |V|, a fingerprint of the alpha set's store ids)`` behind the
-engine's payload and every rank compares all of them after the gather (``ReplicaMismatch``).
+engine's payload and every rank compares all of them after the gather (``ReplicaMismatch``).  The same trailer carries
+the rank's STATUS: a rank that ran out of memory still sends, and the ranks halve the belief chunk together and finish
+the backup in rounds (``sharded_backup``), or raise ``MemoryError`` together.
 
 Hardware status: the >= 2-rank RCCL path has not run on GPUs in any round (one-GPU boxes); it is covered by gloo tests
 with one engine per rank and by a one-rank RCCL group.
@@ -85,14 +87,33 @@ def alpha_fingerprint(engine) -> int:
     return zlib.crc32(np.ascontiguousarray(ids, dtype=np.int32).tobytes()) & 0x7fffffff
 
 
-def trailer_values(n_total: int, V: int, fingerprint: int) -> np.ndarray:
-    return np.array([_MAGIC, n_total & 0x7fffffff, V & 0x7fffffff, fingerprint & 0x7fffffff], dtype=np.int32)
+# Status of a rank in one exchange round.  It rides in the trailer's first word (magic + status), so a message in which
+# every rank is fine is what it always was; a status is never a replica mismatch.
+STATUS_OK, STATUS_OOM, STATUS_MORE = 0, 1, 2
+# Beliefs the engine takes per call: a shard above it goes through sharded_backup in several rounds
+SHARD_BLOCK_LIMIT = 65535
+
+
+def trailer_values(n_total: int, V: int, fingerprint: int, status: int = STATUS_OK) -> np.ndarray:
+    return np.array([_MAGIC + status, n_total & 0x7fffffff, V & 0x7fffffff, fingerprint & 0x7fffffff], dtype=np.int32)
+
+
+def trailer_statuses(all_meta: np.ndarray, n_meta: int) -> np.ndarray:
+    """[world] status of every rank's message (anything but a known status is left for ``check_trailers`` to refuse)."""
+    return all_meta[:, n_meta].astype(np.int64) - _MAGIC
 
 
 def check_trailers(all_meta: np.ndarray, n_meta: int, mine: np.ndarray) -> None:
-    """all_meta [world, n_meta + TRAILER]: every rank's trailer must equal this rank's."""
+    """all_meta [world, n_meta + TRAILER]: every rank's trailer must equal this rank's -- up to the status, and up to
+    (|V|, alpha fingerprint) where a rank reports ``STATUS_OOM``: its engine holds no alpha set any more."""
     got = all_meta[:, n_meta:n_meta + TRAILER]
-    bad = np.flatnonzero(np.any(got != mine[None, :], axis=1))
+    diff = got != mine[None, :]
+    st, my = trailer_statuses(all_meta, n_meta), int(mine[0]) - _MAGIC
+    if my != STATUS_OK or np.any(st != STATUS_OK):
+        known = (st >= STATUS_OK) & (st <= STATUS_MORE)
+        diff[:, 0] = ~known
+        diff[known & ((st == STATUS_OOM) | (my == STATUS_OOM)), 2:] = False
+    bad = np.flatnonzero(np.any(diff, axis=1))
     if bad.size:
         r = int(bad[0])
         raise ReplicaMismatch(f'sharded backup: rank {r} sent (magic, n_total, |V|, alpha fingerprint) = {got[r].tolist()}, '
@@ -307,6 +328,54 @@ def exchange_keys(dist, group, meta, per: int, key_width: int, n_total: int, tra
     return out
 
 
+def gather_round(dist, group, meta, n_meta: int, trailer: np.ndarray):
+    """One round of ``sharded_backup``: ONE ``all_gather_into_tensor`` of the ranks' messages (``n_meta`` payload entries
+    + ``TRAILER``; ``trailer`` carries this rank's status and is written behind the payload here).  Every rank takes part
+    whatever happened to it locally.  Returns ``(all messages [world, n_meta + TRAILER] on the host, statuses [world])``
+    after the trailer check."""
+    import torch
+    world = dist.get_world_size(group)
+    n_msg = int(meta.shape[0])
+    if n_msg != n_meta + TRAILER:
+        raise ValueError(f'exchange message has {n_msg} entries, the round needs {n_meta} + {TRAILER}')
+    meta[n_meta:] = torch.from_numpy(trailer).to(meta.device)
+    flat = torch.empty(world * n_msg, dtype=torch.int32, device=meta.device)
+    dist.all_gather_into_tensor(flat, meta, group=group)
+    host = flat.view(world, n_msg).cpu().numpy()
+    check_trailers(host, n_meta, trailer)
+    return host, trailer_statuses(host, n_meta)
+
+
+def merge_rounds(rounds, per: int, key_width: int, n_total: int):
+    """``merge_exchange`` over the rounds of one sharded backup.  ``rounds``: ``(all messages [world, >= 1 + 3 c + c kw],
+    c, offset)`` per round -- rank ``r``'s message of that round covers beliefs ``[offset, offset + c)`` of its shard
+    ``[r per, min((r + 1) per, n_total))``.  Every rank's rounds are laid end to end into the one-round message of block
+    size ``per`` (per-belief entries at their offset, the rounds' keys one after the other, indices shifted), and those
+    go through the native merge once: equal keys of different rounds or ranks become one row, and the result is what
+    one round of block size ``per`` gives."""
+    if len(rounds) == 1 and rounds[0][1] == per and rounds[0][2] == 0:
+        return merge_exchange(rounds[0][0], per, key_width, n_total)
+    world = rounds[0][0].shape[0]
+    k0 = 1 + 3 * per
+    comb = np.zeros((world, k0 + per * key_width), dtype=np.int32)
+    for r in range(world):
+        lo, hi, _ = shard_bounds(n_total, world, r)
+        u = 0
+        for host, c, off in rounds:
+            n = min(max(hi - lo - off, 0), c)
+            msg = host[r]
+            cnt = int(msg[0])
+            if cnt < 0 or cnt > n:
+                raise ValueError(f'corrupt exchange message: rank {r} sent {cnt} distinct rows for {n} beliefs')
+            comb[r, 1 + off:1 + off + n] = msg[1:1 + n] + u
+            comb[r, 1 + per + off:1 + per + off + n] = msg[1 + c:1 + c + n]
+            comb[r, 1 + 2 * per + off:1 + 2 * per + off + n] = msg[1 + 2 * c:1 + 2 * c + n]
+            comb[r, k0 + u * key_width:k0 + (u + cnt) * key_width] = msg[1 + 3 * c:1 + 3 * c + cnt * key_width]
+            u += cnt
+        comb[r, 0] = u
+    return merge_exchange(comb, per, key_width, n_total)
+
+
 def gather_packed(dist, group, meta, per: int, key_width: int, n_total: int, assemble):
     """Key exchange + rows: ``assemble(keys [n, 1+O] int32 ndarray) -> rows [n, S]`` rebuilds the globally distinct
     rows (``pbvi_assemble_rows`` / ``_store``: byte-identical to the rows the producing rank holds).  At C4 that is
@@ -370,8 +439,8 @@ class EngineShard:
             self._keys = t.zeros(n, dtype=t.int32, device=self.device)
         return self._keys
 
-    def trailer(self, n_total: int) -> np.ndarray:
-        return trailer_values(n_total, int(self.engine.alpha_count), alpha_fingerprint(self.engine))
+    def trailer(self, n_total: int, status: int = STATUS_OK) -> np.ndarray:
+        return trailer_values(n_total, int(self.engine.alpha_count), alpha_fingerprint(self.engine), status)
 
     def run_resident_packed(self, per: int = None):
         """For the key exchange: run, then the engine packs count, index, actions, keep and the keys of its distinct rows
@@ -439,10 +508,26 @@ def _first_occurrence(idx: np.ndarray):
     return idx[first], first
 
 
+def _agree_host(dist, group, carrier, n_total: int, V: int, status: int) -> np.ndarray:
+    """The status agreement of the host-mirror branch: a gather of trailers alone.  Returns every rank's status."""
+    import torch
+    meta = torch.zeros(TRAILER, dtype=torch.int32, device=carrier)
+    return gather_round(dist, group, meta, 0, trailer_values(n_total, V, 0, status))[1]
+
+
 def sharded_backup(solver, model, belief_set, value_function, belief_dominance_prune: bool, group=None):
     """``PBVI_Solver.backup`` (``src/pomdp.py:1447-1519``, before the ``append`` union) with the beliefs sharded over
     the ranks of ``group``.  Every rank calls it with identical arguments (replicated model, belief set and value
-    function) and gets the identical ``ValueFunction`` back: the single-process result."""
+    function) and gets the identical ``ValueFunction`` back: the single-process result.
+
+    The engine path runs in ROUNDS over a chunk size ``c`` that all ranks hold equal (``min(per, SHARD_BLOCK_LIMIT)``,
+    or the chunk an earlier backup of this solve settled on): per round every rank backs up the next ``c`` beliefs of
+    its shard (or fewer, or none) and sends one message padded to ``c`` whose trailer carries its status.  A rank whose
+    local part raised ``MemoryError`` still sends -- an empty message with ``STATUS_OOM`` -- and then every rank drops
+    the round, returns its engine to the fresh state (the replicas keep numbering their store rows alike), halves ``c``
+    and redoes the round from the same offset; a round that fails at ``c == 1`` raises ``MemoryError`` on every rank
+    (``.shard_round`` names the round), which ``solve`` turns into the partial result on all of them.  Rounds go on
+    while a rank reports ``STATUS_MORE``; the rows are assembled and stored once, after the last one."""
     import torch
     import torch.distributed as dist
     from .mdp import AlphaVector, ValueFunction
@@ -453,13 +538,23 @@ def sharded_backup(solver, model, belief_set, value_function, belief_dominance_p
     carrier = _carrier_device(dist, group, value_function.model.engine.device if value_function.is_on_gpu else None)
 
     if not value_function.is_on_gpu:
-        # host mirror: the reference's NumPy statements on this rank's block, per-belief rows exchanged
+        # host mirror: the reference's NumPy statements on this rank's block, per-belief rows exchanged.  One round (it
+        # has no block limit); the ranks first agree that every local part went through.
         S = model.state_count
-        if hi > lo:
-            rows, acts, keep = solver._backup_numpy(model, belief_set.belief_array[lo:hi], value_function.alpha_vector_array,
-                                                    belief_dominance_prune, return_mask=True)
-        else:
-            rows, acts, keep = np.zeros((0, S)), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=bool)
+        status = STATUS_OK
+        try:
+            if hi > lo:
+                rows, acts, keep = solver._backup_numpy(model, belief_set.belief_array[lo:hi], value_function.alpha_vector_array,
+                                                        belief_dominance_prune, return_mask=True)
+            else:
+                rows, acts, keep = np.zeros((0, S)), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=bool)
+        except MemoryError:
+            status = STATUS_OOM
+        st = _agree_host(dist, group, carrier, n_total, len(value_function), status)
+        if np.any(st == STATUS_OOM):
+            err = MemoryError(f'sharded backup: rank(s) {np.flatnonzero(st == STATUS_OOM).tolist()} ran out of memory')
+            err.shard_round = 0
+            raise err
         sb = ShardedBackup(group)
         t_rows, t_acts, t_keep = sb.gather_rows(torch.from_numpy(np.ascontiguousarray(rows, dtype=np.float64)).to(carrier),
                                                 torch.from_numpy(np.ascontiguousarray(acts, dtype=np.int64)).to(carrier),
@@ -468,16 +563,55 @@ def sharded_backup(solver, model, belief_set, value_function, belief_dominance_p
         return ValueFunction(model, t_rows.cpu().numpy()[k], t_acts.cpu().numpy()[k])
 
     eng = value_function.model.engine
-    eng.sync_rows('alpha', value_function.alpha_vector_list, lambda v: v.values, owner=value_function)
     shard = EngineShard(eng, solver.gamma, belief_dominance_prune, carrier=carrier)
-    if hi > lo:
-        if hi - lo > 65535:
-            raise NotImplementedError('sharded backup: at most 65535 beliefs per rank and call')
-        eng.sync_rows('belief', beliefs[lo:hi], lambda b: b.values)
-        meta, per, kw, _ = shard.run_resident_packed(per)
-    else:
-        meta, per, kw = shard.empty_message(per)
-    keys, idx, act, keep = exchange_keys(dist, group, meta, per, kw, n_total, trailer=shard.trailer(n_total))
+    have, kw = hi - lo, 1 + eng.O
+    c = max(1, min(per, SHARD_BLOCK_LIMIT))
+    remembered = getattr(solver, '_belief_chunk', None)
+    for_memory = remembered is not None               # chunks because of memory, not of the block limit
+    if for_memory:
+        c = max(1, min(c, int(remembered)))
+    setting = eng.formulation
+    rounds, off, k = [], 0, 0
+    try:
+        while True:
+            n = min(max(have - off, 0), c)
+            status = STATUS_MORE if have - off > c else STATUS_OK
+            try:
+                if for_memory:
+                    # as PBVI_Solver._backup_in_chunks: a chunk projects the BELIEFS, whose footprint shrinks with it
+                    eng.set_formulation('belief' if c <= len(value_function) else 'auto')
+                eng.sync_rows('alpha', value_function.alpha_vector_list, lambda v: v.values, owner=value_function)
+                if n > 0:
+                    eng.sync_rows('belief', beliefs[lo + off:lo + off + n], lambda b: b.values)
+                    meta = shard.run_resident_packed(c)[0]
+                else:
+                    meta = shard.empty_message(c)[0]
+                trailer = shard.trailer(n_total, status)
+            except MemoryError:
+                meta = shard.empty_message(c)[0]
+                trailer = trailer_values(n_total, 0, 0, STATUS_OOM)
+            host, st = gather_round(dist, group, meta, eng.exchange_size(c), trailer)
+            if np.any(st == STATUS_OOM):
+                eng.after_oom()                       # every rank: replicas that reset together stay identical
+                if c == 1:
+                    err = MemoryError(f'sharded backup: round {k} does not fit the device of rank(s) '
+                                      f'{np.flatnonzero(st == STATUS_OOM).tolist()} at one belief per rank')
+                    err.shard_round = k
+                    raise err
+                c = (c + 1) // 2
+                for_memory = True
+            else:
+                rounds.append((host, c, off))
+                off += c
+                if not np.any(st == STATUS_MORE):
+                    break
+            k += 1
+    finally:
+        if eng.formulation != setting:
+            eng.set_formulation(setting)
+    if for_memory:
+        solver._belief_chunk = c                      # later backups of this solve start there, on every rank
+    keys, idx, act, keep = merge_rounds(rounds, per, kw, n_total)
     if belief_dominance_prune:
         idx, act = idx[keep], act[keep]
     used, first_pos = _first_occurrence(idx)              # the order the reference's byte-dedup produces
@@ -486,8 +620,8 @@ def sharded_backup(solver, model, belief_set, value_function, belief_dominance_p
     rows, first = eng.assemble_rows_store(keys[used], solver.gamma)
     tag = eng.store_tag('alpha')
     vectors = []
-    for k, (row, a) in enumerate(zip(rows, act[first_pos])):
+    for j, (row, a) in enumerate(zip(rows, act[first_pos])):
         v = AlphaVector(row, int(a))
-        v._dev = (tag, first + k)
+        v._dev = (tag, first + j)
         vectors.append(v)
     return ValueFunction(value_function.model, vectors)

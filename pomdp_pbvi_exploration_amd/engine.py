@@ -462,15 +462,21 @@ class Engine:
         "return the partial result" like the reference (``src/pomdp.py:2399-2401``)."""
         if rc == -2:
             msg = (self._lib.pbvi_last_error() or b'').decode(errors='replace')
-            self._lib.pbvi_engine_after_oom(self._h)
-            self._resident = {'alpha': None, 'belief': None}
-            for k in self._store_epoch:                  # residency tags of AlphaVector / Belief objects no longer match
-                self._store_epoch[k] += 1
-            self._vmax_cache, self._vmax_epochs = [], None
-            self._alpha_token = None
-            self.B = 0
+            self.after_oom()
             raise MemoryError(msg)
         _check(rc)
+
+    def after_oom(self) -> None:
+        """Back to the freshly created state (``pbvi_engine_after_oom``), as ``_ck`` does before it raises ``MemoryError``.
+        On its own for the ranks of a sharded backup: when one rank ran out of memory every rank drops its stores, so
+        that the replicas number their rows alike again (``dist.sharded_backup``)."""
+        self._lib.pbvi_engine_after_oom(self._h)
+        self._resident = {'alpha': None, 'belief': None}
+        for k in self._store_epoch:                  # residency tags of AlphaVector / Belief objects no longer match
+            self._store_epoch[k] += 1
+        self._vmax_cache, self._vmax_epochs = [], None
+        self._alpha_token = None
+        self.B = 0
 
     # -- residency ------------------------------------------------------- #
     def _as_rows(self, arr: np.ndarray) -> np.ndarray:
