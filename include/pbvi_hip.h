@@ -296,6 +296,22 @@ int pbvi_backup(pbvi_engine_t* e, const void* beliefs, int64_t B, double gamma, 
 int pbvi_prune_dominated(pbvi_engine_t* e, uint8_t* keep /* [V] */);
 
 /*
+ * The same prune from the pairs that involve a new row only (two launches of k_dominated_rect: all x new, new x old):
+ *   keep[i] == 1  iff  (is_new[i] ? 0 : 1) + #{j : (is_new[i] || is_new[j]) and alpha[j][s] >= alpha[i][s] for every s} == 1
+ * (j ranges over every resident row, i itself included; the comparison is the one of pbvi_prune_dominated, so a row that
+ * holds a NaN dominates nothing and is dominated by nothing, itself included).
+ * PRECONDITION, NOT CHECKED: the rows with is_new[i] == 0 are free of domination among themselves -- the survivors of an
+ * earlier pbvi_prune_dominated / pbvi_prune_dominated_masked on this engine, or any subset of them.  Then keep equals
+ * what pbvi_prune_dominated returns for the same rows, bit for bit, from 2*V*dV - dV*dV pair tests instead of V*V.  When
+ * it does not hold the result is exactly the formula above: a pair of two old rows is never looked at.
+ * An all-ones is_new is the full prune; an all-zeros is_new keeps every row and launches nothing.
+ *   is_new [V] uint8 (non-zero = new), keep [V] uint8; host memory.  PBVI_EINVAL when either is NULL or no alpha set is
+ *   resident, PBVI_EUNSUPPORTED above 262140 alpha-vectors (as pbvi_prune_dominated), PBVI_ENOMEM as everywhere
+ *   (pbvi_engine_after_oom).
+ */
+int pbvi_prune_dominated_masked(pbvi_engine_t* e, const uint8_t* is_new /* [V] */, uint8_t* keep /* [V] */);
+
+/*
  * max_v b.alpha_v over the resident alpha set for the resident belief block
  * (compute_change, src/pomdp.py:2165-2166; also the |V|-limiter scan :2349-2352).
  *   out_value [B] double, out_index [B] int32 (first max), either may be NULL.

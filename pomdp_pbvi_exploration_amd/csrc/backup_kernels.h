@@ -287,4 +287,13 @@ hipError_t launch_walk_step(const double* base, ModelView<T> mv, const double* r
 template <typename T>
 hipError_t launch_dominated(const T* alpha, int lda, int V, int S, int* cnt, hipStream_t st);
 
+// incremental prune level 2 (k_dominated_rect): rows[0, n_old) are the rows known to be free of mutual domination,
+// rows[n_old, n_old + n_new) the new ones (device list of row indices).  Two passes on `st`: (all x new), then
+// (new x old); cnt[i] += #{j : the pair (i, j) holds a new row and alpha[j] >= alpha[i] everywhere}.  Launches are cut
+// so that no grid dimension exceeds `piece` (1..65535); nothing is launched for n_new == 0.  alpha must be 16-byte
+// aligned and lda a multiple of 16 bytes.
+template <typename T>
+hipError_t launch_dominated_masked(const T* alpha, int lda, int S, const int32_t* rows, int n_old, int n_new, int* cnt,
+                                   int piece, hipStream_t st);
+
 }  // namespace pbvi

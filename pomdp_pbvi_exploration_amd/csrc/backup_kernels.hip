@@ -8,6 +8,8 @@
 // results are deterministic run to run.
 #include "backup_kernels.h"
 
+#include <algorithm>
+#include <cstdint>
 #include <cstdlib>
 #include <limits>
 
@@ -2131,6 +2133,72 @@ hipError_t launch_dominated(const T* alpha, int lda, int V, int S, int* cnt, hip
 }
 
 // ------------------------------------------------------------------------- //
+// Incremental prune level 2: the pairs (i, j) of a rectangle I x J of row indices, same predicate and NaN behaviour as
+// k_dominated (a NaN on either side fails the step).  Rows whose mutual domination is already known to be absent are
+// simply not paired: launch_dominated_masked below runs (all x new) and (new x old), so two old rows never meet.
+// One wavefront per pair, the four waves of a block share row i.  Most pairs die in the first 64 states, so that
+// step reads one element per lane (one or two cache lines per row); a pair that survives it is a near-dominator and
+// goes on in 16-byte loads, 64 lanes x (16 / sizeof(T)) states per step, leaving at the first step that fails.
+// Every 16-byte chunk that starts below S lies inside its row: lda is a multiple of the chunk (checked at launch).
+// ------------------------------------------------------------------------- //
+template <typename T>
+__global__ __launch_bounds__(256) void k_dominated_rect(const T* __restrict__ alpha, int lda, int S,
+                                                        const int32_t* __restrict__ I, const int32_t* __restrict__ J, int nJ,
+                                                        int* __restrict__ cnt) {
+    constexpr int W = 16 / (int)sizeof(T);                  // elements of one 16-byte load
+    struct alignas(16) Chunk {
+        T v[W];
+    };
+    const int lane = threadIdx.x & 63;
+    const int jj = blockIdx.y * 4 + (threadIdx.x >> 6);     // wave-uniform
+    if (jj >= nJ) return;
+    const int i = I[blockIdx.x];
+    const T* ai = alpha + (int64_t)i * lda;
+    const T* aj = alpha + (int64_t)J[jj] * lda;
+    if (__any((lane < S) ? !(aj[lane] >= ai[lane]) : 0)) return;
+    for (int s0 = 64; s0 < S; s0 += 64 * W) {
+        const int s = s0 + lane * W;
+        int bad = 0;
+        if (s < S) {
+            const Chunk x = *reinterpret_cast<const Chunk*>(ai + s);
+            const Chunk y = *reinterpret_cast<const Chunk*>(aj + s);
+#pragma unroll
+            for (int k = 0; k < W; ++k) bad |= (s + k < S) & !(y.v[k] >= x.v[k]);
+        }
+        if (__any(bad)) return;
+    }
+    if (lane == 0) atomicAdd(&cnt[i], 1);
+}
+
+// cnt[i] += #{j in J : alpha[j] >= alpha[i] everywhere} for every i in I, in launches of at most `piece` rows of I by
+// `piece` blocks of four rows of J (1 <= piece <= 65535: no grid dimension above it)
+template <typename T>
+static hipError_t launch_dominated_rect(const T* alpha, int lda, int S, const int32_t* I, int nI, const int32_t* J, int nJ,
+                                        int* cnt, int piece, hipStream_t st) {
+    for (int i0 = 0; i0 < nI; i0 += piece)
+        for (int j0 = 0; j0 < nJ; j0 += 4 * piece) {
+            const int ni = std::min(piece, nI - i0), nj = std::min(4 * piece, nJ - j0);
+            hipLaunchKernelGGL(k_dominated_rect<T>, dim3(ni, (nj + 3) / 4), dim3(256), 0, st, alpha, lda, S, I + i0, J + j0, nj,
+                               cnt);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+    return hipSuccess;
+}
+
+template <typename T>
+hipError_t launch_dominated_masked(const T* alpha, int lda, int S, const int32_t* rows, int n_old, int n_new, int* cnt,
+                                   int piece, hipStream_t st) {
+    if (n_old < 0 || n_new < 0 || piece < 1 || piece > 65535) return hipErrorInvalidValue;
+    if (lda % (16 / (int)sizeof(T)) != 0 || (reinterpret_cast<uintptr_t>(alpha) & 15) != 0 || S > lda) return hipErrorInvalidValue;
+    if (n_new == 0) return hipSuccess;
+    const int32_t* fresh = rows + n_old;
+    hipError_t e = launch_dominated_rect<T>(alpha, lda, S, rows, n_old + n_new, fresh, n_new, cnt, piece, st);   // pass A
+    if (e != hipSuccess) return e;
+    return launch_dominated_rect<T>(alpha, lda, S, fresh, n_new, rows, n_old, cnt, piece, st);                   // pass B
+}
+
+// ------------------------------------------------------------------------- //
 // Batched belief update (Bayes step).  Reference: Belief.update, src/pomdp.py:405-411 (one belief at a time,
 // np.bincount scatter); batched form in the simulator, src/pomdp.py:3277-3310.
 //   u[b, s'] = sum over (s, r) with rs[s, a_b, r] == s' of  b[b, s] * RTO[s, a_b, o_b, r];   b'[b] = u[b] / sum(u[b])
@@ -2513,7 +2581,8 @@ hipError_t launch_walk_step(const double* base, ModelView<T> mv, const double* r
                                              const double*, const int32_t*, const int32_t*, int, int, double*, double*,   \
                                              hipStream_t);                                                               \
     template hipError_t launch_walk_finish<T>(const double*, const double*, ModelView<T>, double*, T*, hipStream_t);     \
-    template hipError_t launch_dominated<T>(const T*, int, int, int, int*, hipStream_t);
+    template hipError_t launch_dominated<T>(const T*, int, int, int, int*, hipStream_t);                                   \
+    template hipError_t launch_dominated_masked<T>(const T*, int, int, const int32_t*, int, int, int*, int, hipStream_t);
 PBVI_INST(float)
 PBVI_INST(double)
 #define PBVI_INST_REFINE(T, TS)                                                                                        \

@@ -746,6 +746,7 @@ class EngineBase {
     virtual int assemble_keys(double gamma, int64_t n, const int32_t* keys, void* out_rows) = 0;
     virtual int64_t assemble_keys_store(double gamma, int64_t n, const int32_t* keys, void* out_rows) = 0;
     virtual int prune_dominated(uint8_t* keep) = 0;
+    virtual int prune_dominated_masked(const uint8_t* is_new, uint8_t* keep) = 0;
     virtual int value_max(double* out_value, int32_t* out_index) = 0;
     virtual int value_max_store(int64_t n, double* out_value, int32_t* out_index) = 0;
     virtual int64_t store_count(int which) const = 0;
@@ -2243,6 +2244,45 @@ class EngineT : public EngineBase {
         HIPCHK(hipMemcpyAsync(cnt.data(), prune_cnt_.p, (size_t)V_ * sizeof(int), hipMemcpyDeviceToHost, stream_));
         HIPCHK(hipStreamSynchronize(stream_));
         for (int64_t i = 0; i < V_; ++i) keep[i] = (cnt[(size_t)i] == 1) ? 1 : 0;
+        return PBVI_OK;
+    }
+
+    // The same mask from the pairs that hold at least one new row (k_dominated_rect): exact whenever the rows with
+    // is_new == 0 are free of mutual domination, which is NOT checked.  The row list (old rows, then new rows) and the
+    // start counts (1 for an old row, which never meets itself; 0 for a new one, which does, once) are built here and
+    // travel through the pinned staging buffer in one copy; the counts come back into the same buffer.
+    int prune_dominated_masked(const uint8_t* is_new, uint8_t* keep) override {
+        if (V_ <= 0) FAIL(PBVI_EINVAL, "prune_dominated_masked: no alpha set resident");
+        if (!is_new) FAIL(PBVI_EINVAL, "prune_dominated_masked: is_new is NULL");
+        if (!keep) FAIL(PBVI_EINVAL, "prune_dominated_masked: keep is NULL");
+        if (V_ > 4 * 65535) FAIL(PBVI_EUNSUPPORTED, "prune_dominated_masked: at most 262140 alpha-vectors");   // as prune_dominated
+        const int V = (int)V_;
+        int n_new = 0;
+        for (int i = 0; i < V; ++i) n_new += is_new[i] ? 1 : 0;
+        if (n_new == 0) {                                    // no pair to test: nothing is launched
+            std::memset(keep, 1, (size_t)V);
+            return PBVI_OK;
+        }
+        HIPCHK(hipSetDevice(device_));
+        int rc = prune_cnt_.ensure((size_t)2 * V * sizeof(int), &bytes_);
+        if (rc) return rc;
+        if ((rc = stage_reserve((size_t)3 * V * sizeof(int)))) return rc;
+        int* h_cnt = static_cast<int*>(host_stage_);
+        int32_t* h_rows = h_cnt + V;
+        int* h_out = h_rows + V;
+        const int n_old = V - n_new;
+        for (int i = 0, o = 0, f = n_old; i < V; ++i) {
+            h_cnt[i] = is_new[i] ? 0 : 1;
+            h_rows[is_new[i] ? f++ : o++] = i;
+        }
+        int* d_cnt = prune_cnt_.as<int>();
+        HIPCHK(hipMemcpyAsync(d_cnt, h_cnt, (size_t)2 * V * sizeof(int), hipMemcpyHostToDevice, stream_));
+        int piece = 65535;
+        if (const char* c = getenv("PBVI_PRUNE_PIECE")) piece = (int)std::min<int64_t>(65535, std::max<int64_t>(1, atoll(c)));   // tests
+        HIPCHK(launch_dominated_masked<T>(alpha_.as<T>(), S_pad_, S_, d_cnt + V, n_old, n_new, d_cnt, piece, stream_));
+        HIPCHK(hipMemcpyAsync(h_out, d_cnt, (size_t)V * sizeof(int), hipMemcpyDeviceToHost, stream_));
+        HIPCHK(hipStreamSynchronize(stream_));
+        for (int i = 0; i < V; ++i) keep[i] = (h_out[i] == 1) ? 1 : 0;
         return PBVI_OK;
     }
 
@@ -4147,6 +4187,10 @@ int pbvi_q_values(pbvi_engine_t* e, double gamma, double* out_q, int32_t* out_ac
 int pbvi_prune_dominated(pbvi_engine_t* e, uint8_t* keep) {
     NEED(e);
     return e->impl->prune_dominated(keep);
+}
+int pbvi_prune_dominated_masked(pbvi_engine_t* e, const uint8_t* is_new, uint8_t* keep) {
+    NEED(e);
+    return e->impl->prune_dominated_masked(is_new, keep);
 }
 int pbvi_value_max(pbvi_engine_t* e, double* out_value, int32_t* out_index) {
     NEED(e);

@@ -34,7 +34,7 @@ EXPORTS = [
     'pbvi_belief_walk_keys', 'pbvi_backup_fetch_value_max',
     'pbvi_backup_fetch_compact', 'pbvi_host_alloc', 'pbvi_host_free', 'pbvi_debug_gemm_dense',
     'pbvi_backup_fetch_exchange_padded', 'pbvi_assemble_rows_store', 'pbvi_exchange_merge', 'pbvi_backup_run_fetch', 'pbvi_debug_alloc_limit', 'pbvi_engine_after_oom', 'pbvi_set_f64_screen', 'pbvi_set_fused_projection', 'pbvi_backup_fetch_row_hashes', 'pbvi_set_score_split',
-    'pbvi_set_gamma_tiling', 'pbvi_gamma_tiling_plan', 'pbvi_q_values',
+    'pbvi_set_gamma_tiling', 'pbvi_gamma_tiling_plan', 'pbvi_q_values', 'pbvi_prune_dominated_masked',
 ]
 
 
@@ -98,6 +98,7 @@ def load_library(path: str = LIB_PATH):
         'pbvi_backup_device_results': (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
         'pbvi_backup': (C.c_int, [vp, vp, C.c_int64, C.c_double, C.c_int, vp, i32p, i32p, u8p, sp]),
         'pbvi_prune_dominated': (C.c_int, [vp, u8p]),
+        'pbvi_prune_dominated_masked': (C.c_int, [vp, u8p, u8p]),
         'pbvi_value_max': (C.c_int, [vp, f64p, i32p]),
         'pbvi_value_max_store': (C.c_int, [vp, C.c_int64, f64p, i32p]),
         'pbvi_q_values': (C.c_int, [vp, C.c_double, f64p, i32p, i32p]),
@@ -934,9 +935,28 @@ class Engine:
         self._ck(self._lib.pbvi_prune_dominated(self._h, keep.ctypes.data_as(C.POINTER(C.c_uint8))))
         return keep.astype(bool)
 
-    def prune_dominated_objects(self, objects, values_of, owner=None) -> np.ndarray:
-        """Same for a list of AlphaVector objects: rows already in the device store are not uploaded again."""
+    def _prune_masked_resident(self, n: int, is_new) -> np.ndarray:
+        new = np.ascontiguousarray(np.asarray(is_new).astype(bool), dtype=np.uint8)
+        if new.shape != (n,):
+            raise ValueError(f'is_new must be [{n}]')
+        keep = np.empty(n, dtype=np.uint8)
+        u8 = C.POINTER(C.c_uint8)
+        self._ck(self._lib.pbvi_prune_dominated_masked(self._h, new.ctypes.data_as(u8), keep.ctypes.data_as(u8)))
+        return keep.astype(bool)
+
+    def prune_dominated_masked(self, alpha: np.ndarray, is_new) -> np.ndarray:
+        """The level-2 prune from the pairs that hold a new row only (``pbvi_prune_dominated_masked``): equal to
+        ``prune_dominated(alpha)`` whenever the rows with ``is_new == False`` are free of domination among themselves.
+        That precondition is the caller's and is not checked."""
+        self._ensure_alpha(alpha)
+        return self._prune_masked_resident(alpha.shape[0], is_new)
+
+    def prune_dominated_objects(self, objects, values_of, owner=None, is_new=None) -> np.ndarray:
+        """Same for a list of AlphaVector objects: rows already in the device store are not uploaded again.
+        ``is_new`` (bool per object) takes the incremental route of ``prune_dominated_masked``."""
         self.sync_rows('alpha', objects, values_of, owner)
+        if is_new is not None:
+            return self._prune_masked_resident(len(objects), is_new)
         keep = np.empty(len(objects), dtype=np.uint8)
         self._ck(self._lib.pbvi_prune_dominated(self._h, keep.ctypes.data_as(C.POINTER(C.c_uint8))))
         return keep.astype(bool)

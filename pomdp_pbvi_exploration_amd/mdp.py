@@ -411,6 +411,19 @@ class AlphaVector:
         return _AlphaKey.from_hash(h, self.values) if h is not None else _AlphaKey(self.values)
 
 
+class _PruneToken:
+    """Identity of one value function's level-2 prunes.  An ``AlphaVector`` whose ``_l2`` attribute IS the token of the
+    value function that holds it survived a level-2 prune of that value function and has been there since: such rows
+    are free of point-wise domination among themselves, so the next prune only tests pairs that involve another row.
+    A token belongs to one value function at a time (``ValueFunction._take_prune_flags`` moves it)."""
+    __slots__ = ()
+
+
+def _incremental_prune_enabled() -> bool:
+    """``PBVI_NO_INCREMENTAL_PRUNE=1`` forces every level-2 prune to test all pairs (A/B of the incremental route)."""
+    return os.environ.get('PBVI_NO_INCREMENTAL_PRUNE', '0') in ('', '0')
+
+
 class ValueFunction:
     """A set of alpha-vectors with the reference's container semantics.
 
@@ -419,7 +432,11 @@ class ValueFunction:
     * ``extend``: this set's vectors first, then the other's; on identical bytes
       the other's object replaces ours in place (``src/mdp.py:763-779``);
     * ``prune(level=2)``: drop every row some other row dominates point-wise
-      (``src/mdp.py:857-866``); runs on the HIP engine when the set is on the GPU.
+      (``src/mdp.py:857-866``); runs on the HIP engine when the set is on the GPU.  The survivors are flagged
+      (``_PruneToken``); a later level-2 prune tests only the pairs that involve an unflagged row -- appended or
+      extended vectors -- and returns the same set.  ``extend`` on a value function without flagged rows, and the
+      solver's |V| limiter, take the flags over with the vectors; a value function built from an array, a file,
+      ``+``, ``to_gpu`` or ``to_cpu`` starts without any.
     """
 
     def __init__(self, model: Model, alpha_vectors: Union[list, np.ndarray] = [], action_list=[]):
@@ -439,6 +456,40 @@ class ValueFunction:
         self._uniqueness_dict = {v.key: v for v in vectors}
         self._vector_list = list(self._uniqueness_dict.values())
         self._pruning_level = 1
+        self._l2_token = None
+
+    # -- level-2 prune flags -------------------------------------------- #
+    def _l2_clean_mask(self, vectors: list) -> np.ndarray:
+        """True where the vector survived a level-2 prune of THIS value function."""
+        tok = getattr(self, '_l2_token', None)
+        if tok is None:
+            return np.zeros(len(vectors), dtype=bool)
+        return np.fromiter((v.__dict__.get('_l2') is tok for v in vectors), dtype=bool, count=len(vectors))
+
+    def _l2_flag(self, survivors, removed=()) -> None:
+        if getattr(self, '_l2_token', None) is None:
+            self._l2_token = _PruneToken()
+        for v in survivors:
+            v._l2 = self._l2_token
+        for v in removed:
+            v.__dict__.pop('_l2', None)
+
+    def _take_prune_flags(self, source: 'ValueFunction', index=None) -> None:
+        """This value function holds a subset of ``source``'s vectors (or ``source``'s own objects next to unflagged
+        ones) and takes its prune token over; ``source`` is left without one, so a token never serves two sets.
+        ``index[p]``: position in ``source`` of this set's vector p when the objects were rebuilt from an array."""
+        tok = getattr(source, '_l2_token', None)
+        if tok is None or source is self:
+            return
+        if index is not None:
+            mine, theirs = self.alpha_vector_list, source.alpha_vector_list
+            if len(mine) != len(index):                     # the constructor folded rows: positions say nothing
+                return
+            for v, i in zip(mine, index):
+                if theirs[int(i)].__dict__.get('_l2') is tok:
+                    v._l2 = tok
+        self._l2_token = tok
+        source._l2_token = None
 
     @property
     def alpha_vector_list(self) -> list:
@@ -477,10 +528,13 @@ class ValueFunction:
         out._vector_array = None
         out._actions = None
         out._pruning_level = 1
+        out._l2_token = None
         return out
 
     def append(self, alpha_vector: AlphaVector) -> None:
         assert alpha_vector.values.shape[0] == self.model.state_count, "Vector to add to value function doesn't have the right size"
+        if self._uniqueness_dict.get(alpha_vector.key) is not alpha_vector:
+            alpha_vector.__dict__.pop('_l2', None)          # not (yet) a survivor of a level-2 prune of this set
         self._uniqueness_dict[alpha_vector.key] = alpha_vector
         self._vector_list = list(self._uniqueness_dict.values())
         self._dev_ids = None
@@ -511,6 +565,20 @@ class ValueFunction:
                     if not fresh[j]:
                         ids_mine[slot_of[k]] = b[1][j]
             carried = (a[0], np.concatenate([ids_mine, b[1][fresh]]))
+        # level-2 prune flags.  The solve loop extends the fresh result of a backup with the pruned set: this set has no
+        # flagged row, so it takes the other's token and the other's survivors stay flagged in it.  Otherwise this
+        # set's flags stand and whatever comes in is new.
+        if other is not self:
+            if getattr(other, '_l2_token', None) is not None and not self._l2_clean_mask(list(mine.values())).any():
+                for k, v in mine.items():
+                    if theirs.get(k) is not v:
+                        v.__dict__.pop('_l2', None)         # a flag left over from a set this vector was dropped from
+                self._l2_token = None
+                self._take_prune_flags(other)
+            else:
+                for k, v in theirs.items():
+                    if mine.get(k) is not v:
+                        v.__dict__.pop('_l2', None)
         mine.update(theirs)
         self._vector_list = list(mine.values())
         self._dev_ids = carried
@@ -577,7 +645,13 @@ class ValueFunction:
         if level >= 2 and self._pruning_level < 2:
             if self.is_on_gpu:      # on the objects: kept vectors keep their device-store rows, nothing is re-stacked
                 vecs = self.alpha_vector_list
-                keep = self.model.engine.prune_dominated_objects(vecs, lambda v: v.values, owner=self)
+                clean = self._l2_clean_mask(vecs)
+                if clean.any() and _incremental_prune_enabled():
+                    # flagged rows are free of mutual domination: only pairs with an unflagged row can change a count
+                    keep = self.model.engine.prune_dominated_objects(vecs, lambda v: v.values, owner=self, is_new=~clean)
+                else:
+                    keep = self.model.engine.prune_dominated_objects(vecs, lambda v: v.values, owner=self)
+                self._l2_flag([v for v, kp in zip(vecs, keep) if kp], [v for v, kp in zip(vecs, keep) if not kp])
                 items = list(self._uniqueness_dict.items())
                 if len(items) == len(vecs):
                     self._uniqueness_dict = {k: v for (k, v), kp in zip(items, keep) if kp}
@@ -588,13 +662,26 @@ class ValueFunction:
                 self._actions = None
             else:
                 arr = self.alpha_vector_array
+                vecs = self.alpha_vector_list
+                clean = self._l2_clean_mask(vecs) if len(vecs) == arr.shape[0] else np.zeros(arr.shape[0], dtype=bool)
                 keep = np.zeros(arr.shape[0], dtype=bool)
-                for i, v in enumerate(arr):
-                    keep[i] = np.count_nonzero(np.all(arr >= v, axis=1)) == 1
+                if clean.any() and _incremental_prune_enabled():
+                    # the same counts from the pairs that hold an unflagged row: a flagged row starts at 1 (itself) and
+                    # meets the unflagged rows only, an unflagged row meets every row
+                    fresh = arr[~clean]
+                    for i, v in enumerate(arr):
+                        if clean[i]:
+                            keep[i] = np.count_nonzero(np.all(fresh >= v, axis=1)) == 0
+                        else:
+                            keep[i] = np.count_nonzero(np.all(arr >= v, axis=1)) == 1
+                else:
+                    for i, v in enumerate(arr):
+                        keep[i] = np.count_nonzero(np.all(arr >= v, axis=1)) == 1
                 self._vector_array = arr[keep]
                 self._actions = self.actions[keep]
                 self._uniqueness_dict = {_AlphaKey(r): AlphaVector(r, a) for r, a in zip(self._vector_array, self._actions)}
                 self._vector_list = list(self._uniqueness_dict.values())
+                self._l2_flag(self._vector_list)
             self._dev_ids = None
         self._pruning_level = level
 

@@ -844,9 +844,15 @@ class PBVI_Solver(Solver):
         if value_function.is_on_gpu:
             # on the objects: the surviving vectors keep their rows in the device store, nothing is re-stacked
             gone = set(int(i) for i in drop)
-            return ValueFunction(value_function.model, [v for i, v in enumerate(value_function.alpha_vector_list) if i not in gone])
-        return ValueFunction(model, np.delete(value_function.alpha_vector_array, drop, axis=0),
-                             np.delete(value_function.actions, drop))
+            limited = ValueFunction(value_function.model, [v for i, v in enumerate(value_function.alpha_vector_list) if i not in gone])
+            for i in gone:
+                value_function.alpha_vector_list[i].__dict__.pop('_l2', None)
+            limited._take_prune_flags(value_function)       # a subset of a domination-free set is domination-free
+            return limited
+        limited = ValueFunction(model, np.delete(value_function.alpha_vector_array, drop, axis=0),
+                                np.delete(value_function.actions, drop))
+        limited._take_prune_flags(value_function, index=np.delete(np.arange(n), drop))
+        return limited
 
     def solve(self, model: Model, expansions: int, full_backup: Union[bool, None] = None, update_passes: int = 1,
               max_belief_growth: int = 10, initial_belief=None, initial_value_function=None, prune_level: int = 1,
@@ -854,7 +860,8 @@ class PBVI_Solver(Solver):
               history_tracking_level: int = 1, print_progress: bool = True, engine_dtype: str = 'f64'):
         """Expand / backup loop (``src/pomdp.py:2172-2413``).  ``engine_dtype``
         ('f64' or 'f32') is the one added keyword: the arithmetic type of the HIP
-        engine when ``use_gpu=True``."""
+        engine when ``use_gpu=True``.  ``prune_level=2, prune_interval=1`` is cheap: after the first level-2 prune only
+        the pairs that involve the rows a backup added are tested (``ValueFunction.prune``), with the same result."""
         if use_gpu:
             model = model.to_gpu(engine_dtype) if not model.is_on_gpu else model
 
@@ -947,6 +954,8 @@ class FSVI_Solver(PBVI_Solver):
               initial_value_function=None, prune_level: int = 1, prune_interval: int = 10,
               limit_value_function_size: int = -1, use_gpu: bool = False, history_tracking_level: int = 1,
               print_progress: bool = True, engine_dtype: str = 'f64'):
+        """``PBVI_Solver.solve`` with ``full_backup=False``.  ``prune_level=2, prune_interval=1`` is cheap: a level-2
+        prune after the first tests only the pairs that involve the rows the backup added."""
         return super().solve(model=model, expansions=expansions, full_backup=False, update_passes=update_passes,
                              max_belief_growth=max_belief_growth, initial_belief=initial_belief,
                              initial_value_function=initial_value_function, prune_level=prune_level,
@@ -971,6 +980,8 @@ class HSVI_Solver(PBVI_Solver):
     def solve(self, model, expansions, max_belief_growth: int = 10, initial_belief=None, initial_value_function=None,
               prune_level: int = 1, prune_interval: int = 10, limit_value_function_size: int = -1, use_gpu: bool = False,
               history_tracking_level: int = 1, print_progress: bool = True, engine_dtype: str = 'f64'):
+        """``PBVI_Solver.solve`` with ``full_backup=False`` and one update pass.  ``prune_level=2, prune_interval=1`` is
+        cheap: a level-2 prune after the first tests only the pairs that involve the rows the backup added."""
         return super().solve(model=model, expansions=expansions, full_backup=False, update_passes=1,
                              max_belief_growth=max_belief_growth, initial_belief=initial_belief,
                              initial_value_function=initial_value_function, prune_level=prune_level,
