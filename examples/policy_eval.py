@@ -5,6 +5,7 @@ The reference publishes one timing for this step (sim_runtime_test.ipynb:223, BA
 300 steps in 41.8 s on its CuPy path (S=22021, unnamed GPU).  This script runs the same call shape.
 
     python examples/policy_eval.py --expansions 60 --n 1000 --max-steps 300
+    python examples/policy_eval.py --reach 5 --device-sim 7      # stochastic moves, simulator on the device too
 """
 import argparse
 import os
@@ -31,12 +32,22 @@ def main():
     ap.add_argument('--lookahead', type=int, default=0, choices=[0, 1],
                     help='0: actions[argmax_v b.alpha_v] (the reference policy); 1: one-step lookahead argmax_a Q(b,a)')
     ap.add_argument('--cpu-steps', type=int, default=0, help='also time this many steps of the host NumPy path')
+    ap.add_argument('--reach', type=int, default=1, choices=[1, 5],
+                    help='reachable states per (state, action): 1 = deterministic moves, 5 = the intended move with 0.8')
+    ap.add_argument('--device-sim', type=int, default=None, metavar='SEED',
+                    help='counter-based simulator draws with this seed: the whole step loop runs in the engine '
+                         '(pbvi_rollout) instead of drawing on the host from NumPy\'s stream')
+    ap.add_argument('--repeat', type=int, default=1, help='run the evaluation this many times (the first one warms up)')
     args = ap.parse_args()
     set_quiet(True)
     H, W = (int(x) for x in args.grid.split('x'))
-    m = synth.olfactory_model(H=H, W=W, R=1, f32=False)
+    m = synth.olfactory_model(H=H, W=W, R=args.reach, f32=False)
     model = Model(states=m.S, actions=m.A, observations=m.O, reachable_states=m.reachable_states,
                   observation_table=m.observation_table, end_states=[m.goal], start_probabilities=list(m.start_belief))
+    if args.reach > 1:                                 # the tables of the stochastic-move model, as the tests' mirror builds them
+        model.reachable_probabilities = m.reachable_probabilities
+        model.reachable_transitional_observation_table = m.rto
+        model.expected_rewards_table = m.expected_rewards
     # MDP value iteration that seeds FSVI: device sweeps vs the host NumPy loop (same result, see tests)
     t0 = time.perf_counter()
     mdp_dev, h_dev = VI_Solver(gamma=m.gamma, eps=1e-6).solve(model, use_gpu=True, print_progress=False)
@@ -55,14 +66,18 @@ def main():
     print(f'solve: S={m.S} expansions={len(hist.expansion_times)} |V|={len(vf)} in {time.perf_counter() - t0:.2f}s', flush=True)
 
     agent = Agent(vf.model, vf, lookahead=args.lookahead, gamma=m.gamma)
-    np.random.seed(1)
-    t0 = time.perf_counter()
-    totals, hists = agent.run_n_simulations_parallel(n=args.n, max_steps=args.max_steps, print_progress=False,
-                                                     print_stats=True)
-    wall = time.perf_counter() - t0
-    steps = sum(len(h.actions) for h in hists)
-    print(f'gpu ({args.dtype}): n={args.n} max_steps={args.max_steps} |V|={len(vf)} wall={wall:.2f}s '
-          f'belief-steps={steps} ({steps / wall:.0f} belief-steps/s)  reference CuPy: 41.8 s for 1000 x 300', flush=True)
+    sim = 'host simulator' if args.device_sim is None else f'device simulator, seed {args.device_sim}'
+    for rep in range(args.repeat):
+        np.random.seed(1)
+        t0 = time.perf_counter()
+        totals, hists = agent.run_n_simulations_parallel(n=args.n, max_steps=args.max_steps, print_progress=False,
+                                                         print_stats=rep == args.repeat - 1, device_rng_seed=args.device_sim)
+        wall = time.perf_counter() - t0
+        steps = sum(len(h.actions) for h in hists)
+        lock_steps = max(len(h.actions) for h in hists)
+        print(f'gpu ({args.dtype}, R={args.reach}, {sim}): n={args.n} max_steps={args.max_steps} |V|={len(vf)} wall={wall:.3f}s '
+              f'lock-steps={lock_steps} ({1e3 * wall / lock_steps:.3f} ms/step) belief-steps={steps} '
+              f'({steps / wall:.0f} belief-steps/s)  reference CuPy: 41.8 s for 1000 x 300', flush=True)
 
     if args.cpu_steps > 0:
         host_agent = Agent(model, vf.to_cpu(), lookahead=args.lookahead, gamma=m.gamma)

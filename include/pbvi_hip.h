@@ -402,6 +402,46 @@ int pbvi_beliefs_fetch(pbvi_engine_t* e, void* out_beliefs);
 int64_t pbvi_beliefs_count(const pbvi_engine_t* e);
 
 /*
+ * Device-resident policy rollout: T lock-step steps of the parallel simulator (Agent.run_n_simulations_parallel,
+ * src/pomdp.py:3203-3380, with SimulationSet.run_actions, :2893-2945, as its draw; the per-step loop of this package's host seam is the
+ * pbvi_value_max / pbvi_q_values + host draw + pbvi_beliefs_advance chain above) for the resident belief block against the
+ * resident alpha set, without leaving the device between steps.  Row b of the block is simulation first_sim_id + b.
+ * For step t = 0 .. T-1 and every simulation i still running:
+ *   action   lookahead 0: a = alpha_actions[first argmax_v b.alpha_v], decided as pbvi_value_max decides it;
+ *            lookahead 1: a = first argmax_a Q(b, a), pbvi_q_values' out_action (discount gamma; unused for lookahead 0)
+ *   uniform  u = uniform01(splitmix64(seed, i), t): x = seed + (idx + 1) * 0x9E3779B97F4A7C15; z = (x ^ x >> 30) *
+ *            0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; hash = z ^ z >> 31 (all mod 2^64), applied to
+ *            (seed, i) and then to (that hash, t); u = (hash >> 11) * 2^-53.  One uniform per simulation and step.
+ *   draw     w[k] = (double) RTO[s, a, o, r], k = o * R + r, from the table the engine was created with (an fp32 engine's fp32
+ *            values widened; never the pbvi_engine_set_rto_f64 copy); c[k] = c[k-1] + w[k] by sequential fp64 additions;
+ *            k* = the first k with u * c[O*R-1] < c[k], or the last k with w[k] > 0 if rounding leaves none;
+ *            o = k* / R, s' = reach_states[s, a, k* % R].  RTO[s,a,o,r] = P(r | s,a) P(o | s'_r, a), so this is the joint law
+ *            of the reference's successor-then-observation draw (SimulationSet.run_actions, src/pomdp.py:2918-2932) from one uniform.
+ *   belief   b <- update(b, a, o), as pbvi_beliefs_advance computes it
+ *   done     end_mask[s'] != 0 finishes the simulation at step t: out_steps[i] = t + 1, it takes no further part
+ *            (src/pomdp.py:3326-3329) and its later trajectory entries are -1.  Otherwise out_steps[i] = T.
+ * A trajectory is a function of (model tables, alpha set, start belief, start state, seed, simulation id) alone: not of B,
+ * of which other simulations share the block, or of how a large run is cut into calls (advance first_sim_id by the rows of
+ * the earlier calls).
+ *   alpha_actions [V] int32 (ValueFunction.actions), start_states [B] int32, end_mask [S] uint8 (non-zero = end state): host
+ *   out_states [T+1][B] (row 0 = start_states), out_actions [T][B], out_observations [T][B], out_steps [B]: int32, host
+ *   memory, caller's belief order; any of them may be NULL.  They arrive in one transfer at the end of the call.
+ * Afterwards the resident block holds the beliefs of the simulations still running, in caller order (pbvi_beliefs_count /
+ * pbvi_beliefs_fetch); when every simulation finished no block is resident, as after pbvi_beliefs_advance.  The alpha set
+ * and both row stores are untouched; the backup's stage buffers are re-used (an earlier pbvi_backup_run's results can no
+ * longer be fetched).  Every index array is validated on the host before the first launch.
+ * PBVI_EINVAL: no resident belief block or alpha set, NULL input, a start state outside [0, S), an alpha_actions entry
+ * outside [0, A), lookahead not 0 or 1, T < 1, or a model with a pair (s, a) whose RTO entries sum to 0 (nothing can follow
+ * it).  PBVI_EUNSUPPORTED, with a pbvi_last_error text: lookahead 1 on a PBVI_DENSE engine (as pbvi_q_values), or
+ * (T + 1) * B beyond the int32 trajectory slot index.  PBVI_ENOMEM as everywhere (pbvi_engine_after_oom): the trajectory
+ * buffers, (3 T + 2) * B int32, are device memory of the engine and count against pbvi_debug_alloc_limit.
+ */
+int pbvi_rollout(pbvi_engine_t* e, const int32_t* alpha_actions /* [V] */, int lookahead, double gamma,
+                 const int32_t* start_states /* [B] */, const uint8_t* end_mask /* [S] */, uint64_t first_sim_id, uint64_t seed,
+                 int64_t T, int32_t* out_states /* [T+1][B] */, int32_t* out_actions /* [T][B] */,
+                 int32_t* out_observations /* [T][B] */, int32_t* out_steps /* [B] */);
+
+/*
  * MDP value iteration on the device (VI_Solver.solve, src/mdp.py:1442-1525; seeds FSVI / HSVI):
  *   rows[a][s] = ER[s,a] + gamma * sum_r P[s,a,r] * v[rs[s,a,r]];   v'[s] = max_a rows[a][s]
  * repeated from v0 until max_s |v' - v| < max_change_limit (the reference's eps * gamma / (1 - gamma)) or

@@ -268,6 +268,27 @@ hipError_t launch_belief_update(const T* bel, int ldb, int B, ModelView<T> mv, c
                                 const int32_t* act, const int32_t* obs, const int32_t* out_row, double* unnorm,
                                 double* mass, T* out, int ldo, hipStream_t st);
 
+// Simulator draw of the device-resident rollout (pbvi_rollout), one lane per live simulation in ENGINE row order i
+// (c = perm ? perm[i] : i is the row's place among the live simulations in caller order, og = orig[c] its trajectory row):
+//   a  = alpha_actions ? alpha_actions[index[i]] : index[c]       (index: [n] engine order / caller order respectively)
+//   u  = uniform01(splitmix64(seed, first_id + og), t)            (synth.py's hash: 53 bits * 2^-53)
+//   k  = first k with u * c[K-1] < c[k], c = sequential fp64 prefix sums of (double) RTO[state[c], a, :, :] (K = O * R
+//        entries, k = o * R + r); if rounding leaves none, the last k with a positive entry
+//   o = k / R, s' = rs[state[c], a, k % R];   done = end_mask[s'] != 0
+// Writes act_e[i] = a, obs_e[i] = o (what launch_belief_update reads), next_state[c] = s', keep[c] = !done, the trajectory
+// slots tr_actions / tr_obs [t][og], tr_states [t+1][og] (row length n0) and steps[og] = t + 1 when done.
+template <typename T>
+hipError_t launch_rollout_draw(int n, ModelView<T> mv, const int32_t* perm, const int32_t* index, const int32_t* alpha_actions,
+                               int V, const int32_t* state, const int32_t* orig, const uint8_t* end_mask, uint64_t seed,
+                               uint64_t first_id, int t, int n0, int32_t* act_e, int32_t* obs_e, int32_t* next_state,
+                               uint8_t* keep, int32_t* tr_states, int32_t* tr_actions, int32_t* tr_obs, int32_t* steps,
+                               hipStream_t st);
+// Its done-filter (one block, n <= 65535): dst[c] = place of caller row c among the survivors or -1, row_e[i] = dst[perm[i]]
+// (launch_belief_update's out_row), state_out / orig_out = the survivors' entries moved up in caller order, *count = survivors.
+hipError_t launch_rollout_compact(int n, const uint8_t* keep, const int32_t* perm, const int32_t* state_in,
+                                  const int32_t* orig_in, int32_t* dst, int32_t* row_e, int32_t* state_out, int32_t* orig_out,
+                                  int* count, hipStream_t st);
+
 // one step of the belief walk: out64 [S] / out_store [S_pad] = normalised update of `base` (fp64 [S]) with (a, o);
 // unnorm [S], partial [ceil(S_pad/256)] fp64 scratch; rto64: fp64 copy of RTO in mv's layout, or nullptr = use mv.rto
 // one kernel per step: pushes belief i and writes belief i (normalising the previous raw result on the fly); see the kernel

@@ -2537,8 +2537,145 @@ hipError_t launch_walk_step(const double* base, ModelView<T> mv, const double* r
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------- //
+// Device-resident policy rollout (pbvi_rollout): the simulator stage between action selection and the Bayes step.
+// Reference: SimulationSet.run_actions, src/pomdp.py:2893-2945 (successor, then observation, from NumPy's global stream).
+// Here ONE counter-based uniform per (simulation, step) picks the (observation, successor) pair from the joint row
+// RTO[s, a, :, :] by a sequential fp64 prefix sum -- the same law, and a pure function of (seed, simulation id, step).
+// ------------------------------------------------------------------------- //
+__device__ __forceinline__ uint64_t rollout_mix(uint64_t seed, uint64_t idx) {     // synth.splitmix64
+    const uint64_t x = seed + (idx + 1ull) * 0x9E3779B97F4A7C15ull;
+    uint64_t z = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// One lane per live simulation, in ENGINE row order i (the order act_e / obs_e feed k_belief_push in); c = perm[i] is the
+// row's place among the live simulations in the caller's order, og = orig[c] its row in the call's trajectory arrays.
+//   index: lookahead 0 -> [n] first argmax_v b.alpha_v per ENGINE row, mapped through alpha_actions [V];
+//          lookahead 1 -> [n] argmax_a Q per CALLER row (alpha_actions == nullptr)
+// The row is walked twice with the same sequential additions (total, then the first k with u * total < c[k]): no local
+// array, whatever O * R is.  An index outside its range (a NaN belief's argmax) is read as 0 rather than followed.
+template <typename T>
+__global__ void k_rollout_draw(int n, ModelView<T> mv, const int32_t* __restrict__ perm, const int32_t* __restrict__ index,
+                               const int32_t* __restrict__ alpha_actions, int V, const int32_t* __restrict__ state,
+                               const int32_t* __restrict__ orig, const uint8_t* __restrict__ end_mask, uint64_t seed,
+                               uint64_t first_id, int t, int n0, int32_t* __restrict__ act_e, int32_t* __restrict__ obs_e,
+                               int32_t* __restrict__ next_state, uint8_t* __restrict__ keep, int32_t* __restrict__ tr_states,
+                               int32_t* __restrict__ tr_actions, int32_t* __restrict__ tr_obs, int32_t* __restrict__ steps) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int c = perm ? perm[i] : i;
+    int a;
+    if (alpha_actions) {
+        int v = index[i];
+        if (v < 0 || v >= V) v = 0;
+        a = alpha_actions[v];
+    } else {
+        a = index[c];
+    }
+    if (a < 0 || a >= mv.A) a = 0;
+    const int s = state[c], og = orig[c];
+    const uint64_t bits = rollout_mix(rollout_mix(seed, first_id + (uint64_t)og), (uint64_t)t) >> 11;
+    const double u = (double)bits * (1.0 / 9007199254740992.0);
+    const T* row = mv.rto + (int64_t)a * mv.O * mv.R * mv.S_pad + s;      // entry k = o * R + r at row[k * S_pad]
+    const int K = mv.O * mv.R;
+    double total = 0.0;
+    for (int k = 0; k < K; ++k) total += (double)row[(int64_t)k * mv.S_pad];
+    const double thr = u * total;
+    double cum = 0.0;
+    int pick = -1, last_pos = 0;
+    for (int k = 0; k < K; ++k) {
+        const double w = (double)row[(int64_t)k * mv.S_pad];
+        cum += w;
+        if (w > 0.0) last_pos = k;
+        if (thr < cum) {
+            pick = k;
+            break;
+        }
+    }
+    if (pick < 0) pick = last_pos;                          // rounding left none: the last entry with weight
+    const int o = pick / mv.R, r = pick - o * mv.R;
+    const int sn = mv.rs[((int64_t)a * mv.R + r) * mv.S_pad + s];
+    const bool done = end_mask[sn] != 0;
+    act_e[i] = a;
+    obs_e[i] = o;
+    next_state[c] = sn;
+    keep[c] = done ? 0 : 1;
+    const int64_t slot = (int64_t)t * n0 + og;
+    tr_actions[slot] = a;
+    tr_obs[slot] = o;
+    tr_states[slot + n0] = sn;
+    if (done) steps[og] = t + 1;
+}
+
+// The done-filter of the live simulations, one block: dst[c] = place of caller row c among the survivors (-1 = finished),
+// row_e[i] = dst[perm[i]] (k_belief_norm's out_row, engine order), the survivors' states and trajectory rows moved up in
+// caller order, *count = survivors.  n <= 65535.
+__global__ void __launch_bounds__(1024) k_rollout_compact(int n, const uint8_t* __restrict__ keep, const int32_t* __restrict__ perm,
+                                                           const int32_t* __restrict__ state_in, const int32_t* __restrict__ orig_in,
+                                                           int32_t* __restrict__ dst, int32_t* __restrict__ row_e,
+                                                           int32_t* __restrict__ state_out, int32_t* __restrict__ orig_out,
+                                                           int* __restrict__ count) {
+    __shared__ int part[1024];
+    const int tid = threadIdx.x;
+    const int per = (n + 1023) / 1024;
+    const int c0 = min(tid * per, n), c1 = min(c0 + per, n);
+    int cnt = 0;
+    for (int c = c0; c < c1; ++c) cnt += keep[c] != 0;
+    part[tid] = cnt;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+        const int v = tid >= off ? part[tid - off] : 0;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    int pos = part[tid] - cnt;
+    for (int c = c0; c < c1; ++c) {
+        if (keep[c] != 0) {
+            dst[c] = pos;
+            state_out[pos] = state_in[c];
+            orig_out[pos] = orig_in[c];
+            ++pos;
+        } else {
+            dst[c] = -1;
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += 1024) row_e[i] = dst[perm ? perm[i] : i];
+    if (tid == 1023) *count = part[1023];
+}
+
+template <typename T>
+hipError_t launch_rollout_draw(int n, ModelView<T> mv, const int32_t* perm, const int32_t* index, const int32_t* alpha_actions,
+                               int V, const int32_t* state, const int32_t* orig, const uint8_t* end_mask, uint64_t seed,
+                               uint64_t first_id, int t, int n0, int32_t* act_e, int32_t* obs_e, int32_t* next_state,
+                               uint8_t* keep, int32_t* tr_states, int32_t* tr_actions, int32_t* tr_obs, int32_t* steps,
+                               hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    if (n > n0 || t < 0 || (int64_t)(t + 2) * n0 > 0x7fffffffll) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_rollout_draw<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, mv, perm, index, alpha_actions, V,
+                       state, orig, end_mask, seed, first_id, t, n0, act_e, obs_e, next_state, keep, tr_states, tr_actions,
+                       tr_obs, steps);
+    return hipGetLastError();
+}
+
+hipError_t launch_rollout_compact(int n, const uint8_t* keep, const int32_t* perm, const int32_t* state_in,
+                                  const int32_t* orig_in, int32_t* dst, int32_t* row_e, int32_t* state_out, int32_t* orig_out,
+                                  int* count, hipStream_t st) {
+    if (n <= 0 || n > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_rollout_compact, dim3(1), dim3(1024), 0, st, n, keep, perm, state_in, orig_in, dst, row_e, state_out,
+                       orig_out, count);
+    return hipGetLastError();
+}
+
 // explicit instantiations
 #define PBVI_INST(T)                                                                                                   \
+    template hipError_t launch_rollout_draw<T>(int, ModelView<T>, const int32_t*, const int32_t*, const int32_t*, int,  \
+                                               const int32_t*, const int32_t*, const uint8_t*, uint64_t, uint64_t, int, \
+                                               int, int32_t*, int32_t*, int32_t*, uint8_t*, int32_t*, int32_t*,         \
+                                               int32_t*, int32_t*, hipStream_t);                                       \
     template hipError_t launch_support<T>(ModelView<T>, uint8_t*, hipStream_t);                                        \
     template hipError_t launch_project<T>(const T*, int, int, ModelView<T>, T, T*, int, const uint8_t*, int,           \
                                           hipStream_t, const uint8_t*, const int*, int, const int32_t*, const int32_t*); \

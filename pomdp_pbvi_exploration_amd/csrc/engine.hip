@@ -774,6 +774,9 @@ class EngineBase {
     virtual int walk_keys(int64_t n, uint64_t* out_keys) = 0;
     virtual int backup_value_max(double* out_value) = 0;
     virtual int q_values(double gamma, double* out_q, int32_t* out_action, int32_t* out_best) = 0;
+    virtual int rollout(const int32_t* alpha_actions, int lookahead, double gamma, const int32_t* start_states,
+                        const uint8_t* end_mask, uint64_t first_sim_id, uint64_t seed, int64_t T, int32_t* out_states,
+                        int32_t* out_actions, int32_t* out_observations, int32_t* out_steps) = 0;
 };
 
 template <typename T>
@@ -855,6 +858,11 @@ class EngineT : public EngineBase {
     DevBuf acand_;                                           // [B][A] action inside the window (k_action_select -> k_refine_action)
     DevBuf q_, q_res_, q_act_;                               // pbvi_q_values: q [B][A] in engine order / caller order, its argmax [B]
     bool q_only_ = false, q_want_best_ = false;              // run_pipeline stops behind the refinement and runs launch_q_exact
+    // pbvi_rollout: trajectories [T+1][n] states | [T][n] actions | [T][n] observations | [n] steps; the live simulations'
+    // true states and trajectory rows (caller order, double-buffered across the done-filter), keep flags, the filter's
+    // row map (+ 1 int: the survivor count), alpha_actions [V], end mask [S]
+    DevBuf ro_traj_, ro_state_[2], ro_orig_[2], ro_keep_, ro_dst_, ro_aact_, ro_end_;
+    int64_t zero_row_ = -1;                                  // first s * A + a whose RTO[s, a, :, :] sums to 0 (-1: none)
     DevBuf rf_q2_, rf_q2p_, rf_q2d_;                         // k_refine_split: entries / candidates, partial scores, arrival counters
     DevBuf rf_v_, rf_slot_, rf_sc_, rf_entry_, rf_n_, rf_tiles_, rf_ibv_, rf_ibi_, rf_cnt_, rf_W_, rf_Cx_, rf_nzW_, rf_klW_, rf_kcW_;   // refinement work list
     int formulation_ = 0;                                   // 0 auto, 1 project alpha-vectors, 2 project beliefs
@@ -944,7 +952,7 @@ class EngineT : public EngineBase {
                          &action_res_, &best_res_, &rep_, &uniq_, &inv_, &slot_, &out_full_, &btl_, &btc_, &val_exact_, &store_[0], &store_[1], &ids_, &in_ptr_, &in_src_, &bu_act_, &bu_obs_,
                          &bu_unnorm_, &bu_mass_, &bu_out_, &bu_row_, &walk64_, &rto64_, &bp_, &nzP_, &pmag_, &prd_, &keys_tmp_, &keys_act_, &keys_best_, &keys_rows_, &rf_v_, &rf_slot_, &rf_sc_, &rf_entry_, &rf_n_, &rf_tiles_,
                          &snz_, &sbtl_, &sbtc_, &vmax_bk_, &rf_ibv_, &rf_ibi_, &rf_cnt_, &rf_W_, &rf_Cx_, &rf_nzW_, &rf_klW_, &rf_kcW_,
-                         &dense_, &nzD_, &nzAlpha_, &prod_, &klistD_, &kcountD_, &nchunksD_, &mat_, &vlist_, &irr_, &rowflags_, &nzBw_, &scr_flag_, &ctile_, &acand_, &q_, &q_res_, &q_act_, &rf_q2_, &rf_q2p_, &rf_q2d_, &e_bv_, &e_bs_, &e_err_, &e_rdot_, &e_act_, &e_ares_, &e_bres_, &e_rep_, &e_uniq_, &e_inv_, &e_slotd_, &e_cnt_, &e_out_, &e_slot_, &scores_, &chain_max_};
+                         &dense_, &nzD_, &nzAlpha_, &prod_, &klistD_, &kcountD_, &nchunksD_, &mat_, &vlist_, &irr_, &rowflags_, &nzBw_, &scr_flag_, &ctile_, &acand_, &q_, &q_res_, &q_act_, &rf_q2_, &rf_q2p_, &rf_q2d_, &e_bv_, &e_bs_, &e_err_, &e_rdot_, &e_act_, &e_ares_, &e_bres_, &e_rep_, &e_uniq_, &e_inv_, &e_slotd_, &e_cnt_, &e_out_, &e_slot_, &scores_, &chain_max_, &ro_traj_, &ro_state_[0], &ro_state_[1], &ro_orig_[0], &ro_orig_[1], &ro_keep_, &ro_dst_, &ro_aact_, &ro_end_};
         // every call is checked only to name a failure when PBVI_DEBUG is set; the thread's sticky last-error is cleared at
         // the end either way, so that a later launch check does not report a stale error of this teardown
         static const bool dbg = getenv("PBVI_DEBUG") != nullptr;
@@ -1067,6 +1075,11 @@ class EngineT : public EngineBase {
         for (int s = 0; s < S; ++s)
             for (int a = 0; a < A; ++a) {
                 h_er[(size_t)a * S_pad_ + s] = er[(size_t)s * A + a];
+                if (zero_row_ < 0) {   // a state-action pair nothing can follow: the simulator draw (rollout) refuses the model
+                    double tot = 0.0;
+                    for (int k = 0; k < O * R; ++k) tot += (double)rto[((size_t)s * A + a) * O * R + k];
+                    if (!(tot > 0.0)) zero_row_ = (int64_t)s * A + a;
+                }
                 for (int r = 0; r < R; ++r) {
                     const int32_t t = reach[((size_t)s * A + a) * R + r];
                     if (t < 0 || t >= S) FAIL(PBVI_EINVAL, "reach_states entry out of range [0,S)");
@@ -1464,9 +1477,6 @@ class EngineT : public EngineBase {
         if ((rc = bu_act_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
         if ((rc = bu_obs_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
         if ((rc = bu_row_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
-        if ((rc = bu_unnorm_.ensure((size_t)B_ * S_ * sizeof(double), &bytes_))) return rc;
-        if ((rc = bu_mass_.ensure((size_t)B_ * sizeof(double), &bytes_))) return rc;
-        if ((rc = stage_.ensure((size_t)nb * S_pad_ * sizeof(T), &bytes_))) return rc;
         if ((rc = host_perm())) return rc;
         std::vector<int32_t> ha((size_t)B_), ho((size_t)B_), hr((size_t)B_);
         for (int64_t i = 0; i < B_; ++i) {               // engine row i holds the caller's row c
@@ -1478,13 +1488,141 @@ class EngineT : public EngineBase {
         HIPCHK(hipMemcpyAsync(bu_act_.p, ha.data(), (size_t)B_ * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
         HIPCHK(hipMemcpyAsync(bu_obs_.p, ho.data(), (size_t)B_ * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
         HIPCHK(hipMemcpyAsync(bu_row_.p, hr.data(), (size_t)B_ * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+        return advance_resident(nb, true);               // (synchronises: ha/ho/hr are pageable host vectors)
+    }
+
+    // The Bayes step + done-filter of beliefs_advance from arrays that are on the device already, in ENGINE row order:
+    // bu_act_ / bu_obs_ [B_] = (action, observation) of each row, bu_row_ [B_] = its row among the nb survivors (caller
+    // order) or -1.  Filled by an upload (beliefs_advance) or by the rollout's draw and filter kernels.
+    int advance_resident(int64_t nb, bool sync_before_finish) {
+        int rc;
+        if ((rc = bu_unnorm_.ensure((size_t)B_ * S_ * sizeof(double), &bytes_))) return rc;
+        if ((rc = bu_mass_.ensure((size_t)B_ * sizeof(double), &bytes_))) return rc;
+        if ((rc = stage_.ensure((size_t)nb * S_pad_ * sizeof(T), &bytes_))) return rc;
         HIPCHK(hipMemsetAsync(bu_mass_.p, 0, (size_t)B_ * sizeof(double), stream_));
         HIPCHK(hipMemsetAsync(stage_.p, 0, (size_t)nb * S_pad_ * sizeof(T), stream_));   // pad columns stay zero
         HIPCHK(launch_belief_update<T>(bel_.as<T>(), S_pad_, (int)B_, view(), in_ptr_.as<int32_t>(), in_src_.as<int32_t>(),
                                        bu_act_.as<int32_t>(), bu_obs_.as<int32_t>(), bu_row_.as<int32_t>(),
                                        bu_unnorm_.as<double>(), bu_mass_.as<double>(), stage_.as<T>(), S_pad_, stream_));
-        HIPCHK(hipStreamSynchronize(stream_));           // ha/ho/hr are pageable host vectors
+        if (sync_before_finish) HIPCHK(hipStreamSynchronize(stream_));
         return beliefs_finish(nb, stage_.as<T>(), nullptr);
+    }
+
+    // T lock-step simulation steps of the resident block against the resident alpha set, on the device (pbvi_rollout):
+    // per step the value-max or Q-value stage with its index left on the device, the simulator draw, the done-filter and
+    // the Bayes step of beliefs_advance.  Finished rows are dropped after EVERY step ("Device-resident
+    // rollouts"): the one host read per step is the survivor count, which sizes the next step's launches.
+    int rollout(const int32_t* alpha_actions, int lookahead, double gamma, const int32_t* start_states, const uint8_t* end_mask,
+                uint64_t first_sim_id, uint64_t seed, int64_t n_steps, int32_t* out_states, int32_t* out_actions,
+                int32_t* out_observations, int32_t* out_steps) override {
+        if (V_ <= 0) FAIL(PBVI_EINVAL, "rollout: no alpha set resident (call pbvi_alpha_set)");
+        if (B_ <= 0) FAIL(PBVI_EINVAL, "rollout: no belief block resident (call pbvi_beliefs_set)");
+        if (!alpha_actions || !start_states || !end_mask) FAIL(PBVI_EINVAL, "rollout: NULL argument");
+        if (lookahead != 0 && lookahead != 1) FAIL(PBVI_EINVAL, "rollout: lookahead must be 0 or 1");
+        if (n_steps < 1) FAIL(PBVI_EINVAL, "rollout: T must be at least 1");
+        if (lookahead == 1 && mode_ != PBVI_SPARSE)
+            FAIL(PBVI_EUNSUPPORTED, "rollout: lookahead = 1 is not available on a PBVI_DENSE engine (create it with PBVI_SPARSE)");
+        const int64_t n0 = B_;
+        if (n_steps >= 0x7fffffff || (n_steps + 1) * n0 > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "rollout: T * B exceeds the int32 trajectory slot index");
+        if ((int64_t)S_ * R_ > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "rollout: S*R exceeds int32");
+        for (int64_t b = 0; b < n0; ++b)
+            if (start_states[b] < 0 || start_states[b] >= S_) FAIL(PBVI_EINVAL, "rollout: start state out of range [0,S)");
+        for (int64_t v = 0; v < V_; ++v)
+            if (alpha_actions[v] < 0 || alpha_actions[v] >= A_) FAIL(PBVI_EINVAL, "rollout: alpha_actions entry out of range [0,A)");
+        if (zero_row_ >= 0)
+            FAIL(PBVI_EINVAL, "rollout: RTO[s,a,:,:] sums to 0 for s = " + std::to_string(zero_row_ / A_) + ", a = " +
+                                  std::to_string(zero_row_ % A_) + ": nothing can follow that state-action pair");
+        HIPCHK(hipSetDevice(device_));
+        int rc;
+        const size_t n_st = (size_t)(n_steps + 1) * n0, n_ao = (size_t)n_steps * n0, n_traj = n_st + 2 * n_ao + (size_t)n0;
+        if ((rc = ro_traj_.ensure(n_traj * sizeof(int32_t), &bytes_))) return rc;
+        for (int k = 0; k < 2; ++k) {
+            if ((rc = ro_state_[k].ensure((size_t)n0 * sizeof(int32_t), &bytes_))) return rc;
+            if ((rc = ro_orig_[k].ensure((size_t)n0 * sizeof(int32_t), &bytes_))) return rc;
+        }
+        if ((rc = ro_keep_.ensure((size_t)n0, &bytes_))) return rc;
+        if ((rc = ro_dst_.ensure((size_t)(n0 + 1) * sizeof(int32_t), &bytes_))) return rc;
+        if ((rc = ro_aact_.ensure((size_t)V_ * sizeof(int32_t), &bytes_))) return rc;
+        if ((rc = ro_end_.ensure((size_t)S_, &bytes_))) return rc;
+        if ((rc = bu_act_.ensure((size_t)n0 * sizeof(int32_t), &bytes_))) return rc;
+        if ((rc = bu_obs_.ensure((size_t)n0 * sizeof(int32_t), &bytes_))) return rc;
+        if ((rc = bu_row_.ensure((size_t)n0 * sizeof(int32_t), &bytes_))) return rc;
+        if ((rc = build_inverse_lists())) return rc;
+        int* h_count = pinned_flag();
+        if (!h_count) FAIL(PBVI_ENOMEM, "rollout: pinned flag");
+        h_count += 10;
+        int32_t* tr_states = ro_traj_.as<int32_t>();
+        int32_t* tr_actions = tr_states + n_st;
+        int32_t* tr_obs = tr_actions + n_ao;
+        int32_t* tr_steps = tr_obs + n_ao;
+        {   // slots never reached stay -1; row 0 of the states = the start states; a simulation that never finishes took T steps
+            std::vector<int32_t> iota((size_t)n0), full((size_t)n0, (int32_t)n_steps);
+            for (int64_t b = 0; b < n0; ++b) iota[(size_t)b] = (int32_t)b;
+            HIPCHK(hipMemsetAsync(ro_traj_.p, 0xFF, (n_traj - (size_t)n0) * sizeof(int32_t), stream_));
+            HIPCHK(hipMemcpyAsync(tr_states, start_states, (size_t)n0 * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+            HIPCHK(hipMemcpyAsync(tr_steps, full.data(), (size_t)n0 * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+            HIPCHK(hipMemcpyAsync(ro_state_[0].p, start_states, (size_t)n0 * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+            HIPCHK(hipMemcpyAsync(ro_orig_[0].p, iota.data(), (size_t)n0 * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+            HIPCHK(hipMemcpyAsync(ro_aact_.p, alpha_actions, (size_t)V_ * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+            HIPCHK(hipMemcpyAsync(ro_end_.p, end_mask, (size_t)S_, hipMemcpyHostToDevice, stream_));
+            HIPCHK(hipStreamSynchronize(stream_));            // the caller's arrays and the two vectors are free again
+        }
+        int oc = 0;
+        for (int64_t t = 0; t < n_steps; ++t) {
+            const int32_t* index;
+            if (lookahead == 0) {
+                if ((rc = value_max_device())) return rc;
+                index = bv2_.as<int32_t>();                   // engine row order
+            } else {
+                q_only_ = true;
+                q_want_best_ = false;
+                rc = backup_run(gamma, 0, nullptr);
+                q_only_ = false;
+                have_result_ = have_bk_vmax_ = false;
+                if (rc) return rc;
+                index = q_act_.as<int32_t>();                 // caller row order
+            }
+            const int n = (int)B_;
+            const int32_t* perm = sorted_ ? perm_.as<int32_t>() : nullptr;
+            // true states: live in ro_state_[0]; the draw leaves the next states in [1], row for row, and the filter moves
+            // the survivors' back up into [0].  Trajectory rows: the filter moves them from one ro_orig_ buffer to the other.
+            HIPCHK(launch_rollout_draw<T>(n, view(), perm, index, lookahead == 0 ? ro_aact_.as<int32_t>() : nullptr, (int)V_,
+                                          ro_state_[0].as<int32_t>(), ro_orig_[oc].as<int32_t>(), ro_end_.as<uint8_t>(), seed,
+                                          first_sim_id, (int)t, (int)n0, bu_act_.as<int32_t>(), bu_obs_.as<int32_t>(),
+                                          ro_state_[1].as<int32_t>(), ro_keep_.as<uint8_t>(), tr_states, tr_actions, tr_obs,
+                                          tr_steps, stream_));
+            HIPCHK(launch_rollout_compact(n, ro_keep_.as<uint8_t>(), perm, ro_state_[1].as<int32_t>(),
+                                          ro_orig_[oc].as<int32_t>(), ro_dst_.as<int32_t>(), bu_row_.as<int32_t>(),
+                                          ro_state_[0].as<int32_t>(), ro_orig_[oc ^ 1].as<int32_t>(),
+                                          ro_dst_.as<int>() + n0, stream_));
+            oc ^= 1;
+            HIPCHK(hipMemcpyAsync(h_count, ro_dst_.as<int>() + n0, sizeof(int), hipMemcpyDeviceToHost, stream_));
+            HIPCHK(hipStreamSynchronize(stream_));
+            const int64_t nb = *h_count;
+            if (nb < 0 || nb > n) FAIL(PBVI_ERUNTIME, "rollout: survivor count out of range");
+            if (nb == 0) {                                    // every simulation finished
+                B_ = 0;
+                B_pad_ = 0;
+                sorted_ = false;
+                have_result_ = false;
+                break;
+            }
+            if ((rc = advance_resident(nb, false))) return rc;
+        }
+        const int32_t* src[4] = {tr_states, tr_actions, tr_obs, tr_steps};
+        int32_t* dsts[4] = {out_states, out_actions, out_observations, out_steps};
+        const size_t len[4] = {n_st, n_ao, n_ao, (size_t)n0};
+        // one transfer of the whole trajectory buffer into the pinned staging area, then host copies of the parts asked for
+        if (out_states || out_actions || out_observations || out_steps) {
+            if ((rc = stage_reserve(n_traj * sizeof(int32_t)))) return rc;
+            HIPCHK(hipMemcpyAsync(host_stage_, ro_traj_.p, n_traj * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+            HIPCHK(hipStreamSynchronize(stream_));
+            for (int k = 0; k < 4; ++k)
+                if (dsts[k]) host_copy(dsts[k], (const char*)host_stage_ + (size_t)(src[k] - tr_states) * sizeof(int32_t), len[k] * sizeof(int32_t));
+        } else {
+            HIPCHK(hipStreamSynchronize(stream_));
+        }
+        return PBVI_OK;
     }
 
     // resident belief block back to the host (or a device buffer), caller order: [B][S] T
@@ -1738,7 +1876,7 @@ class EngineT : public EngineBase {
                           &bu_mass_, &bu_out_, &bu_row_, &walk64_, &bp_, &nzP_, &pmag_, &prd_, &keys_tmp_, &keys_act_, &keys_best_,
                           &keys_rows_, &rf_v_, &rf_slot_, &rf_sc_, &rf_entry_, &rf_n_, &rf_tiles_, &snz_, &sbtl_, &sbtc_, &vmax_bk_,
                           &rf_ibv_, &rf_ibi_, &rf_cnt_, &rf_W_, &rf_Cx_, &rf_nzW_, &rf_klW_, &rf_kcW_, &nzAlpha_, &prod_, &klistD_,
-                          &kcountD_, &nchunksD_, &mat_, &vlist_, &rowflags_, &ctile_, &acand_, &q_, &q_res_, &q_act_, &rf_q2_, &rf_q2p_, &rf_q2d_, &e_bv_, &e_bs_, &e_err_, &e_rdot_, &e_act_, &e_ares_, &e_bres_, &e_rep_, &e_uniq_, &e_inv_, &e_slotd_, &e_out_, &e_slot_, &scores_};
+                          &kcountD_, &nchunksD_, &mat_, &vlist_, &rowflags_, &ctile_, &acand_, &q_, &q_res_, &q_act_, &rf_q2_, &rf_q2p_, &rf_q2d_, &e_bv_, &e_bs_, &e_err_, &e_rdot_, &e_act_, &e_ares_, &e_bres_, &e_rep_, &e_uniq_, &e_inv_, &e_slotd_, &e_out_, &e_slot_, &scores_, &ro_traj_, &ro_state_[0], &ro_state_[1], &ro_orig_[0], &ro_orig_[1], &ro_keep_, &ro_dst_, &ro_aact_, &ro_end_};
         for (DevBuf* b : drop) {
             bytes_ -= (int64_t)b->cap;
             b->release();
@@ -4251,6 +4389,13 @@ int pbvi_engine_set_rto_f64(pbvi_engine_t* e, const double* rto) {
     return e->impl->set_rto_f64(rto);
 }
 
+int pbvi_rollout(pbvi_engine_t* e, const int32_t* alpha_actions, int lookahead, double gamma, const int32_t* start_states,
+                 const uint8_t* end_mask, uint64_t first_sim_id, uint64_t seed, int64_t T, int32_t* out_states,
+                 int32_t* out_actions, int32_t* out_observations, int32_t* out_steps) {
+    NEED(e);
+    return e->impl->rollout(alpha_actions, lookahead, gamma, start_states, end_mask, first_sim_id, seed, T, out_states,
+                            out_actions, out_observations, out_steps);
+}
 int pbvi_beliefs_fetch(pbvi_engine_t* e, void* out_beliefs) {
     NEED(e);
     return e->impl->beliefs_fetch(out_beliefs);

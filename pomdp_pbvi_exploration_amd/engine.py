@@ -35,6 +35,7 @@ EXPORTS = [
     'pbvi_backup_fetch_compact', 'pbvi_host_alloc', 'pbvi_host_free', 'pbvi_debug_gemm_dense',
     'pbvi_backup_fetch_exchange_padded', 'pbvi_assemble_rows_store', 'pbvi_exchange_merge', 'pbvi_backup_run_fetch', 'pbvi_debug_alloc_limit', 'pbvi_engine_after_oom', 'pbvi_set_f64_screen', 'pbvi_set_fused_projection', 'pbvi_backup_fetch_row_hashes', 'pbvi_set_score_split',
     'pbvi_set_gamma_tiling', 'pbvi_gamma_tiling_plan', 'pbvi_q_values', 'pbvi_prune_dominated_masked',
+    'pbvi_rollout',
 ]
 
 
@@ -117,6 +118,8 @@ def load_library(path: str = LIB_PATH):
         'pbvi_debug_poison': (C.c_int, [C.c_int]),
         'pbvi_belief_update': (C.c_int, [vp, i32p, i32p, vp]),
         'pbvi_beliefs_advance': (C.c_int, [vp, i32p, i32p, u8p, C.POINTER(C.c_int64)]),
+        'pbvi_rollout': (C.c_int, [vp, i32p, C.c_int, C.c_double, i32p, u8p, C.c_uint64, C.c_uint64, C.c_int64,
+                                   i32p, i32p, i32p, i32p]),
         'pbvi_beliefs_fetch': (C.c_int, [vp, vp]),
         'pbvi_beliefs_count': (C.c_int64, [vp]),
         'pbvi_mdp_value_iteration': (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, i32p, f64p, f64p, f64p,
@@ -1057,6 +1060,43 @@ class Engine:
                                               o.ctypes.data_as(C.POINTER(C.c_int32)), kp, C.byref(nb)))
         self.B = int(nb.value)
         return self.B
+
+    def rollout(self, alpha_actions, start_states, end_mask, seed: int, T: int, first_sim_id: int = 0, lookahead: int = 0,
+                gamma: float = 0.99):
+        """``T`` lock-step simulation steps of the resident belief block against the working alpha set, entirely on the
+        device (``pbvi_rollout``): action selection, the counter-based simulator draw and the Bayes step per step.
+        Row ``b`` of the block is simulation ``first_sim_id + b`` of stream ``seed``.  Returns ``(states [T+1,B], actions
+        [T,B], observations [T,B], steps [B])`` as int32 arrays in the caller's belief order, ``-1`` behind a finished
+        simulation's last step.  Afterwards the resident block holds the beliefs of the simulations still running
+        (``self.B`` of them; ``fetch_beliefs``)."""
+        aa = np.ascontiguousarray(alpha_actions, dtype=np.int32)
+        ss = np.ascontiguousarray(start_states, dtype=np.int32)
+        em = np.ascontiguousarray(end_mask, dtype=np.uint8)
+        if aa.shape != (self.alpha_count,):
+            raise ValueError('alpha_actions must be [V]')
+        if ss.shape != (self.B,):
+            raise ValueError('start_states must be [B]')
+        if em.shape != (self.S,):
+            raise ValueError('end_mask must be [S]')
+        if not (0 <= int(seed) < 1 << 64 and 0 <= int(first_sim_id) < 1 << 64):
+            raise ValueError('seed and first_sim_id must fit an unsigned 64-bit integer')
+        T, B = int(T), self.B
+        if T >= 1 and (T + 1) * B <= 0x7fffffff:
+            states = np.empty((T + 1, B), dtype=np.int32)
+            actions = np.empty((T, B), dtype=np.int32)
+            observations = np.empty((T, B), dtype=np.int32)
+        else:                                    # the call refuses these: nothing is written
+            states = actions = observations = np.empty((0, B), dtype=np.int32)
+        steps = np.empty(B, dtype=np.int32)
+        i32p = C.POINTER(C.c_int32)
+        self._resident['belief'] = None
+        self._ck(self._lib.pbvi_rollout(self._h, aa.ctypes.data_as(i32p), int(lookahead), float(gamma),
+                                        ss.ctypes.data_as(i32p), em.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                        int(first_sim_id), int(seed), T, states.ctypes.data_as(i32p),
+                                        actions.ctypes.data_as(i32p), observations.ctypes.data_as(i32p),
+                                        steps.ctypes.data_as(i32p)))
+        self.B = int(self._lib.pbvi_beliefs_count(self._h))
+        return states, actions, observations, steps
 
     def fetch_beliefs(self) -> np.ndarray:
         """The resident belief block, ``[B,S]`` in caller order."""

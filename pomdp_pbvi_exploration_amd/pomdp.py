@@ -1144,6 +1144,111 @@ def _q_values_device(value_function: ValueFunction, arr: np.ndarray, gamma: floa
     return (np.concatenate(qs) if qs else np.zeros((0, A))), (np.concatenate(acts) if acts else np.zeros(0, dtype=np.int64))
 
 
+# --------------------------------------------------------------------------- #
+# Counter-based rollouts: the definition ``pbvi_rollout`` implements on the device, restated with NumPy
+# --------------------------------------------------------------------------- #
+def _rollout_tables(model):
+    """The tables a rollout reads under ``Model``'s attribute names, from a ``Model`` or a ``synth.SynthModel`` (whose one
+    end state is its goal)."""
+    from types import SimpleNamespace
+    if hasattr(model, 'reachable_transitional_observation_table'):
+        m = model.cpu_model if getattr(model, 'is_on_gpu', False) else model
+        return SimpleNamespace(state_count=m.state_count, action_count=m.action_count, observation_count=m.observation_count,
+                               reachable_state_count=m.reachable_state_count, reachable_states=np.asarray(m.reachable_states),
+                               reachable_transitional_observation_table=np.asarray(m.reachable_transitional_observation_table),
+                               expected_rewards_table=np.asarray(m.expected_rewards_table),
+                               end_states=np.asarray(m.end_states, dtype=np.int64))
+    return SimpleNamespace(state_count=model.S, action_count=model.A, observation_count=model.O, reachable_state_count=model.R,
+                           reachable_states=np.asarray(model.reachable_states),
+                           reachable_transitional_observation_table=np.asarray(model.rto),
+                           expected_rewards_table=np.asarray(model.expected_rewards),
+                           end_states=np.asarray(getattr(model, 'end_states', [model.goal]), dtype=np.int64))
+
+
+def rollout_uniform(seed: int, sim_ids, t) -> np.ndarray:
+    """``u(i, t) = uniform01(splitmix64(seed, i), t)``: the one uniform of simulation ``i`` (global id) at step ``t``."""
+    if not 0 <= int(seed) < 1 << 64:
+        raise ValueError('seed must fit an unsigned 64-bit integer')
+    from . import synth
+    return synth.uniform01(synth.splitmix64(int(seed), sim_ids), t)
+
+
+def rollout_draw(rows: np.ndarray, u: np.ndarray) -> np.ndarray:
+    """Index ``k`` drawn from each ``[O*R]`` row of weights with its uniform: the first ``k`` with ``u * c[-1] < c[k]``,
+    ``c`` the sequential fp64 prefix sums; where rounding leaves none, the last ``k`` with a positive weight."""
+    rows = np.asarray(rows, dtype=np.float64)
+    c = np.cumsum(rows, axis=1)
+    if not np.all(c[:, -1] > 0):
+        raise ValueError('a row of RTO[s, a, :, :] sums to 0: nothing can follow that state-action pair')
+    hit = (np.asarray(u, dtype=np.float64) * c[:, -1])[:, None] < c
+    k = np.argmax(hit, axis=1)
+    none = ~hit.any(axis=1)
+    if none.any():
+        k[none] = rows.shape[1] - 1 - np.argmax(rows[none, ::-1] > 0, axis=1)
+    return k
+
+
+def rollout_numpy(model, alpha, alpha_actions, beliefs, start_states, seed: int, first_sim_id: int, T: int,
+                  lookahead: int = 0, gamma: float = 0.99, table_dtype=np.float64, return_beliefs: bool = False):
+    """``T`` lock-step simulation steps with counter-based draws, on the host: what ``pbvi_rollout`` computes on the device.
+
+    Row ``b`` of ``beliefs`` is simulation ``first_sim_id + b``.  Per step and running simulation: the action
+    (``alpha_actions[argmax_v b.alpha_v]``, or ``argmax_a Q(b,a)`` for ``lookahead=1``), one uniform
+    ``rollout_uniform(seed, id, t)``, the ``(observation, successor)`` pair drawn from ``RTO[s, a, :, :]`` -- cast to
+    ``table_dtype``, the engine's arithmetic type, and widened -- by ``rollout_draw``, the Bayes update
+    (``_HostBeliefBlock.advance``) and the done-filter.  Returns ``(states [T+1,n], actions [T,n], observations [T,n],
+    steps [n])`` as int32 arrays, ``-1`` behind a finished simulation's last step; with ``return_beliefs`` also the
+    ``[n_running, S]`` beliefs of the simulations still running, in order.  A trajectory depends on its own row and id
+    only, so a run cut into chunks (``first_sim_id`` advanced by the rows before) returns the same rows."""
+    from types import SimpleNamespace
+    m = _rollout_tables(model)
+    S, A, O, R = m.state_count, m.action_count, m.observation_count, m.reachable_state_count
+    if lookahead not in (0, 1):
+        raise ValueError(f'lookahead must be 0 or 1, not {lookahead!r}')
+    T = int(T)
+    if T < 1:
+        raise ValueError('T must be at least 1')
+    alpha = np.asarray(alpha, dtype=np.float64)
+    acts = np.asarray(alpha_actions).astype(np.int64)
+    b = np.array(beliefs, dtype=np.float64)
+    s = np.asarray(start_states).astype(np.int64)
+    n = b.shape[0]
+    if b.ndim != 2 or b.shape[1] != S or alpha.ndim != 2 or alpha.shape[1] != S:
+        raise ValueError(f'beliefs and alpha must be [*, {S}] arrays')
+    if s.shape != (n,) or (n and (s.min() < 0 or s.max() >= S)):
+        raise ValueError('start_states must be [n] with entries in [0, S)')
+    if acts.shape != (alpha.shape[0],) or acts.min() < 0 or acts.max() >= A:
+        raise ValueError('alpha_actions must be [V] with entries in [0, A)')
+    rto = np.ascontiguousarray(m.reachable_transitional_observation_table, dtype=table_dtype).astype(np.float64).reshape(S, A, O * R)
+    if not np.all(np.cumsum(rto, axis=2)[:, :, -1] > 0):
+        raise ValueError('a row of RTO[s, a, :, :] sums to 0: nothing can follow that state-action pair')
+    end = np.zeros(S, dtype=bool)
+    end[m.end_states] = True
+    with np.errstate(over='ignore'):
+        ids = np.uint64(int(first_sim_id)) + np.arange(n, dtype=np.uint64)
+    states = np.full((T + 1, n), -1, dtype=np.int32)
+    actions = np.full((T, n), -1, dtype=np.int32)
+    observations = np.full((T, n), -1, dtype=np.int32)
+    steps = np.full(n, T, dtype=np.int32)
+    states[0] = s
+    block = _HostBeliefBlock(m, SimpleNamespace(alpha_vector_array=alpha), b)
+    alive = np.arange(n)
+    for t in range(T):
+        if alive.size == 0:
+            break
+        a = block.best_actions(gamma) if lookahead == 1 else acts[block.best_vectors()]
+        k = rollout_draw(rto[s, a], rollout_uniform(seed, ids[alive], t))
+        o, sn = k // R, m.reachable_states[s, a, k % R]
+        done = end[sn]
+        states[t + 1, alive], actions[t, alive], observations[t, alive] = sn, a, o
+        steps[alive[done]] = t + 1
+        block.advance(a, o, ~done)
+        alive, s = alive[~done], sn[~done]
+    if return_beliefs:
+        return states, actions, observations, steps, (block.b if alive.size else np.zeros((0, S)))
+    return states, actions, observations, steps
+
+
 class _HostBeliefBlock:
     """Belief block of the parallel simulator held in NumPy (reference CPU statements, ``:3029``, ``:3306-3311``)."""
 
@@ -1324,11 +1429,19 @@ class Agent:
     def run_n_simulations_parallel(self, n: int = 1000, simulator_set: Union[SimulationSet, None] = None,
                                    max_steps: int = 1000, start_states: Union[list, int, None] = None,
                                    initial_beliefs=None, reward_discount: float = 0.99,
-                                   print_progress: bool = True, print_stats: bool = True):
+                                   print_progress: bool = True, print_stats: bool = True,
+                                   device_rng_seed: Union[int, None] = None):
         """n simulations advanced in lock-step (``src/pomdp.py:3203-3380``).  Per step: best α per belief
         (GEMM + first-max), host simulator draw, Bayes update of every belief, done-filter.  With the value
         function on the GPU the belief block lives in the HIP engine for the whole run; only the ``[n]`` index,
-        action and observation vectors cross the boundary each step."""
+        action and observation vectors cross the boundary each step.
+
+        ``device_rng_seed=None`` (default): the draws are NumPy's global stream in the reference's call order, so a seeded
+        run reproduces the reference's trajectories.  An integer: the counter-based rollout instead (``rollout_numpy``'s
+        definition; simulation ``i`` draws ``rollout_uniform(seed, i, t)`` at step ``t``) -- the whole step loop runs in
+        the HIP engine (``pbvi_rollout``) when the value function is on the GPU, on the host otherwise, and the
+        trajectories do not depend on which, up to exact ties between actions.  Only the start states, when none are
+        given, still come from NumPy's stream."""
         vf = self.value_function
         assert vf is not None, "No value function, training probably has to be run..."
         on_gpu = vf.is_on_gpu
@@ -1345,6 +1458,9 @@ class Agent:
 
         simulator_set = SimulationSet(model) if simulator_set is None else simulator_set
         start_state_array = simulator_set.initialize_simulations(n, start_states)
+        if device_rng_seed is not None:
+            return self._run_counter_rollouts(model, simulator_set, b0, np.asarray(start_state_array), int(device_rng_seed),
+                                              max_steps, reward_discount, print_stats)
         block = (_DeviceBeliefBlock if on_gpu else _HostBeliefBlock)(model, vf, b0)
 
         done_at_step = np.full(n, -1, dtype=int)
@@ -1396,6 +1512,56 @@ class Agent:
             print(f'All {n} simulations done in {(datetime.now() - t0).total_seconds():.3f}s:')
             print(f'\t- Simulations reached goal: {n_done}/{n} ({n - n_done} failures)')
             print(f'\t- Average step count: {steps_sum / n}')
+            print(f'\t- Average total rewards: {np.sum(rewards_history) / n}')
+            print(f'\t- Average discounted rewards (ADR): {np.sum(discounted_history) / n}')
+        return RewardSet(np.sum(rewards_history, axis=0).tolist()), histories
+
+    ROLLOUT_CHUNK = 65535            # simulations per ``pbvi_rollout`` call: the engine's belief block limit
+
+    def _run_counter_rollouts(self, model: Model, simulator_set: SimulationSet, b0: np.ndarray, start_states: np.ndarray,
+                              seed: int, max_steps: int, reward_discount: float, print_stats: bool):
+        """``run_n_simulations_parallel(device_rng_seed=seed)``: the trajectories from ``pbvi_rollout`` (value function on
+        the GPU; more than ``ROLLOUT_CHUNK`` simulations in chunks with ``first_sim_id`` advanced) or ``rollout_numpy``,
+        the rewards from the recorded ``(s, a, s', o)`` afterwards, the result in ``run_n_simulations_parallel``'s form."""
+        vf = self.value_function
+        n, T = b0.shape[0], int(max_steps)
+        t0 = datetime.now()
+        if vf.is_on_gpu:
+            eng = model.engine
+            eng.sync_rows('alpha', vf.alpha_vector_list, lambda v: v.values)
+            end_mask = np.zeros(model.state_count, dtype=np.uint8)
+            end_mask[np.asarray(model.end_states, dtype=np.int64)] = 1
+            parts = []
+            for i0 in range(0, n, self.ROLLOUT_CHUNK):
+                eng.set_beliefs(b0[i0:i0 + self.ROLLOUT_CHUNK])
+                parts.append(eng.rollout(vf.actions, start_states[i0:i0 + self.ROLLOUT_CHUNK], end_mask, seed, T,
+                                         first_sim_id=i0, lookahead=self.lookahead, gamma=self.gamma))
+            states, actions, observations = (np.concatenate([p[k] for p in parts], axis=1) for k in range(3))
+            steps = np.concatenate([p[3] for p in parts])
+        else:
+            states, actions, observations, steps = rollout_numpy(model, vf.alpha_vector_array, vf.actions, b0, start_states,
+                                                                 seed, 0, T, self.lookahead, self.gamma)
+        ran = actions >= 0                                       # [T, n] steps that were taken
+        rewards_history = np.zeros((T, n))
+        if ran.any():
+            rewards_history[ran] = simulator_set._step_rewards(states[:-1][ran].astype(np.int64), actions[ran].astype(np.int64),
+                                                               states[1:][ran].astype(np.int64), observations[ran].astype(np.int64))
+        discounted_history = rewards_history * (reward_discount ** np.arange(1, T + 1))[:, None]
+        histories = []
+        b_start = Belief(model)
+        for i in range(n):
+            h = SimulationHistory(self.model, int(start_states[i]), b_start)
+            last = int(steps[i])
+            h.states = states[:last + 1, i].tolist()
+            h.actions = actions[:last, i].tolist()
+            h.observations = observations[:last, i].tolist()
+            h.rewards = rewards_history[:last, i].tolist()
+            histories.append(h)
+        n_done = int(np.sum(np.isin(states[steps, np.arange(n)], model.end_states)))
+        if print_stats:
+            print(f'All {n} simulations done in {(datetime.now() - t0).total_seconds():.3f}s:')
+            print(f'\t- Simulations reached goal: {n_done}/{n} ({n - n_done} failures)')
+            print(f'\t- Average step count: {int(np.sum(steps)) / n}')
             print(f'\t- Average total rewards: {np.sum(rewards_history) / n}')
             print(f'\t- Average discounted rewards (ADR): {np.sum(discounted_history) / n}')
         return RewardSet(np.sum(rewards_history, axis=0).tolist()), histories
