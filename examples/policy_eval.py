@@ -6,6 +6,7 @@ The reference publishes one timing for this step (sim_runtime_test.ipynb:223, BA
 
     python examples/policy_eval.py --expansions 60 --n 1000 --max-steps 300
     python examples/policy_eval.py --reach 5 --device-sim 7      # stochastic moves, simulator on the device too
+    python examples/policy_eval.py --policy infotaxis --device-sim 7   # the infotaxis baseline (no solve), on the device
 """
 import argparse
 import os
@@ -17,7 +18,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 from pomdp_pbvi_exploration_amd import FSVI_Solver, Model, set_quiet, synth   # noqa: E402
-from pomdp_pbvi_exploration_amd.pomdp import Agent                            # noqa: E402
+from pomdp_pbvi_exploration_amd.pomdp import Agent, Infotaxis_Agent           # noqa: E402
 from pomdp_pbvi_exploration_amd.mdp import VI_Solver                         # noqa: E402
 
 
@@ -37,6 +38,9 @@ def main():
     ap.add_argument('--device-sim', type=int, default=None, metavar='SEED',
                     help='counter-based simulator draws with this seed: the whole step loop runs in the engine '
                          '(pbvi_rollout) instead of drawing on the host from NumPy\'s stream')
+    ap.add_argument('--policy', default='value', choices=['value', 'infotaxis'],
+                    help='value: solve with FSVI and follow the value function; infotaxis: no solve, every step takes the '
+                         'action with the smallest expected entropy of the next belief (pbvi_infotaxis)')
     ap.add_argument('--repeat', type=int, default=1, help='run the evaluation this many times (the first one warms up)')
     args = ap.parse_args()
     set_quiet(True)
@@ -48,24 +52,29 @@ def main():
         model.reachable_probabilities = m.reachable_probabilities
         model.reachable_transitional_observation_table = m.rto
         model.expected_rewards_table = m.expected_rewards
-    # MDP value iteration that seeds FSVI: device sweeps vs the host NumPy loop (same result, see tests)
-    t0 = time.perf_counter()
-    mdp_dev, h_dev = VI_Solver(gamma=m.gamma, eps=1e-6).solve(model, use_gpu=True, print_progress=False)
-    t_dev = time.perf_counter() - t0
-    t0 = time.perf_counter()
-    mdp_host, h_host = VI_Solver(gamma=m.gamma, eps=1e-6).solve(model, use_gpu=False, print_progress=False)
-    t_host = time.perf_counter() - t0
-    print(f'value iteration: {len(h_dev.iteration_times)} sweeps  device {t_dev:.3f}s  host NumPy {t_host:.3f}s  '
-          f'identical rows: {np.array_equal(mdp_dev.alpha_vector_array, mdp_host.alpha_vector_array)}', flush=True)
+    if args.policy == 'infotaxis':
+        agent = Infotaxis_Agent(model.to_gpu(args.dtype))
+        policy = 'infotaxis'
+    else:
+        # MDP value iteration that seeds FSVI: device sweeps vs the host NumPy loop (same result, see tests)
+        t0 = time.perf_counter()
+        mdp_dev, h_dev = VI_Solver(gamma=m.gamma, eps=1e-6).solve(model, use_gpu=True, print_progress=False)
+        t_dev = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        mdp_host, h_host = VI_Solver(gamma=m.gamma, eps=1e-6).solve(model, use_gpu=False, print_progress=False)
+        t_host = time.perf_counter() - t0
+        print(f'value iteration: {len(h_dev.iteration_times)} sweeps  device {t_dev:.3f}s  host NumPy {t_host:.3f}s  '
+              f'identical rows: {np.array_equal(mdp_dev.alpha_vector_array, mdp_host.alpha_vector_array)}', flush=True)
 
-    np.random.seed(0)
-    random.seed(0)
-    t0 = time.perf_counter()
-    vf, hist = FSVI_Solver(gamma=m.gamma, eps=1e-6, mdp_policy=mdp_dev).solve(model, expansions=args.expansions, max_belief_growth=args.growth,
-                                                          use_gpu=True, engine_dtype=args.dtype, print_progress=False)
-    print(f'solve: S={m.S} expansions={len(hist.expansion_times)} |V|={len(vf)} in {time.perf_counter() - t0:.2f}s', flush=True)
+        np.random.seed(0)
+        random.seed(0)
+        t0 = time.perf_counter()
+        vf, hist = FSVI_Solver(gamma=m.gamma, eps=1e-6, mdp_policy=mdp_dev).solve(model, expansions=args.expansions, max_belief_growth=args.growth,
+                                                              use_gpu=True, engine_dtype=args.dtype, print_progress=False)
+        print(f'solve: S={m.S} expansions={len(hist.expansion_times)} |V|={len(vf)} in {time.perf_counter() - t0:.2f}s', flush=True)
 
-    agent = Agent(vf.model, vf, lookahead=args.lookahead, gamma=m.gamma)
+        agent = Agent(vf.model, vf, lookahead=args.lookahead, gamma=m.gamma)
+        policy = f'|V|={len(vf)}'
     sim = 'host simulator' if args.device_sim is None else f'device simulator, seed {args.device_sim}'
     for rep in range(args.repeat):
         np.random.seed(1)
@@ -75,12 +84,12 @@ def main():
         wall = time.perf_counter() - t0
         steps = sum(len(h.actions) for h in hists)
         lock_steps = max(len(h.actions) for h in hists)
-        print(f'gpu ({args.dtype}, R={args.reach}, {sim}): n={args.n} max_steps={args.max_steps} |V|={len(vf)} wall={wall:.3f}s '
+        print(f'gpu ({args.dtype}, R={args.reach}, {sim}): n={args.n} max_steps={args.max_steps} {policy} wall={wall:.3f}s '
               f'lock-steps={lock_steps} ({1e3 * wall / lock_steps:.3f} ms/step) belief-steps={steps} '
               f'({steps / wall:.0f} belief-steps/s)  reference CuPy: 41.8 s for 1000 x 300', flush=True)
 
     if args.cpu_steps > 0:
-        host_agent = Agent(model, vf.to_cpu(), lookahead=args.lookahead, gamma=m.gamma)
+        host_agent = Infotaxis_Agent(model) if args.policy == 'infotaxis' else Agent(model, vf.to_cpu(), lookahead=args.lookahead, gamma=m.gamma)
         np.random.seed(1)
         t0 = time.perf_counter()
         _, hh = host_agent.run_n_simulations_parallel(n=args.n, max_steps=args.cpu_steps, print_progress=False,

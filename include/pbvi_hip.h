@@ -442,6 +442,56 @@ int pbvi_rollout(pbvi_engine_t* e, const int32_t* alpha_actions /* [V] */, int l
                  int32_t* out_observations /* [T][B] */, int32_t* out_steps /* [B] */);
 
 /*
+ * Infotaxis: the expected entropy of the next belief, for every belief of the resident block and every action -- the greedy
+ * information-gathering policy a solved olfactory-search policy is judged against.  No alpha set is needed or read.
+ * For a belief row b, action a and observation o, over the table the engine was created with (an fp32 engine's fp32 values
+ * widened to fp64; never the pbvi_engine_set_rto_f64 copy):
+ *   u[s']   = sum over (s, r) with reach_states[s, a, r] == s' of (double) b[s] * (double) RTO[s, a, o, r], in fp64, entries in
+ *             ascending s * R + r order (np.bincount's order; the sum pbvi_belief_update normalises)
+ *   Z[a, o] = sum_s' u[s']                      ( = P(o | b, a) )
+ *   N[a, o] = sum_s' u[s'] * ln u[s']            (terms with u[s'] == 0 add 0)
+ *   G[b, a] = sum_o (Z * ln Z - N)              (terms with Z == 0 add 0; sequential over o)
+ *           = sum_o P(o | b, a) * H(update(b, a, o)),  H the Shannon entropy in nats
+ *   H[b]    = - sum_s b[s] * ln b[s]            (the entropy of the belief itself; terms with b[s] == 0 add 0)
+ *   a*[b]   = the first a whose G[b, a] is strictly smaller than every earlier one; a NaN never wins and a row of NaNs gives 0:
+ *             np.argmin(np.where(np.isnan(G), np.inf, G), axis=1).  It is taken from the row of out_g that is returned, so
+ *             out_action[b] equals that argmin of out_g[b] exactly.
+ * ln is the fp64 logarithm.  The sums over s' are taken in an order that differs from NumPy's but is fixed and uses no
+ * atomics: a belief's results have the same bits from call to call, whatever other beliefs share the block and wherever
+ * the belief stands in it.
+ *   out_g [B][A] double (required); out_action [B] int32, out_p_obs [B][A][O] double ( = Z), out_entropy [B] double: may be
+ *   NULL.  Host (or device) memory, caller's belief order.
+ * The resident block, the alpha set and both row stores are untouched, and so are the backup's stage buffers.  Works on
+ * PBVI_SPARSE and PBVI_DENSE engines and on both number formats: it needs what pbvi_belief_update needs.
+ * PBVI_EINVAL: no resident belief block, or out_g == NULL.  PBVI_ENOMEM as everywhere (pbvi_engine_after_oom): the partial
+ * sums, ceil(S / 2048) * B * A * O * 2 doubles, and the results are device memory of the engine and count against
+ * pbvi_debug_alloc_limit.
+ */
+int pbvi_infotaxis(pbvi_engine_t* e, double* out_g /* [B][A], required */, int32_t* out_action /* [B], may be NULL */,
+                   double* out_p_obs /* [B][A][O], may be NULL */, double* out_entropy /* [B], may be NULL */);
+
+/*
+ * Device-resident infotaxis rollout: pbvi_rollout with the action of every step taken from pbvi_infotaxis' a*[b] instead of
+ * the alpha set -- a = the first argmin_a G(b, a) of the simulation's current belief.  Everything else is pbvi_rollout's:
+ * the uniform u(i, t) = uniform01(splitmix64(seed, i), t) of simulation i = first_sim_id + b, the (o, s') draw from
+ * RTO[s, a, :, :] by sequential fp64 prefix sums, the done rule (end_mask[s'] != 0 finishes the simulation at step t:
+ * out_steps[i] = t + 1, later entries -1, otherwise out_steps[i] = T), the Bayes step, the dropping of finished rows after
+ * every step, the layout of the trajectory buffers (out_states [T+1][B] with row 0 = start_states, out_actions [T][B],
+ * out_observations [T][B], out_steps [B], int32, caller order, any may be NULL) and the end state of the block (the
+ * beliefs of the simulations still running, in caller order; none resident when all finished).  No alpha set is needed.
+ * One difference in arithmetic: the Bayes step of this call adds a belief's per-block masses in block order instead of with
+ * atomic adds (the last bit of the normaliser then does not depend on arrival order), because infotaxis meets near-ties
+ * between actions: a trajectory is a function of (model tables, start belief, start state, seed, simulation id) alone.
+ * PBVI_EINVAL: no resident belief block, NULL start_states or end_mask, a start state outside [0, S), T < 1, or a model with
+ * a pair (s, a) whose RTO entries sum to 0.  PBVI_EUNSUPPORTED: (T + 1) * B beyond the int32 trajectory slot index.
+ * PBVI_ENOMEM as everywhere.
+ */
+int pbvi_rollout_infotaxis(pbvi_engine_t* e, const int32_t* start_states /* [B] */, const uint8_t* end_mask /* [S] */,
+                           uint64_t first_sim_id, uint64_t seed, int64_t T, int32_t* out_states /* [T+1][B] */,
+                           int32_t* out_actions /* [T][B] */, int32_t* out_observations /* [T][B] */,
+                           int32_t* out_steps /* [B] */);
+
+/*
  * MDP value iteration on the device (VI_Solver.solve, src/mdp.py:1442-1525; seeds FSVI / HSVI):
  *   rows[a][s] = ER[s,a] + gamma * sum_r P[s,a,r] * v[rs[s,a,r]];   v'[s] = max_a rows[a][s]
  * repeated from v0 until max_s |v' - v| < max_change_limit (the reference's eps * gamma / (1 - gamma)) or

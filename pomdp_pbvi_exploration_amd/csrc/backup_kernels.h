@@ -266,7 +266,9 @@ hipError_t launch_keep(const T* bel, int ldb, const T* uniq_rows, int ldo, int B
 template <typename T>
 hipError_t launch_belief_update(const T* bel, int ldb, int B, ModelView<T> mv, const int32_t* in_ptr, const int32_t* in_src,
                                 const int32_t* act, const int32_t* obs, const int32_t* out_row, double* unnorm,
-                                double* mass, T* out, int ldo, hipStream_t st);
+                                double* mass, T* out, int ldo, hipStream_t st, double* mass_part = nullptr);
+// mass_part [B][ceil(S / 256)] (or nullptr): the push kernel's blocks store their partial masses there and a fold kernel adds
+// them in block order, instead of atomicAdd on mass -- the same norm up to its last bit, but the same bits every time.
 
 // Simulator draw of the device-resident rollout (pbvi_rollout), one lane per live simulation in ENGINE row order i
 // (c = perm ? perm[i] : i is the row's place among the live simulations in caller order, og = orig[c] its trajectory row):
@@ -288,6 +290,21 @@ hipError_t launch_rollout_draw(int n, ModelView<T> mv, const int32_t* perm, cons
 hipError_t launch_rollout_compact(int n, const uint8_t* keep, const int32_t* perm, const int32_t* state_in,
                                   const int32_t* orig_in, int32_t* dst, int32_t* row_e, int32_t* state_out, int32_t* orig_out,
                                   int* count, hipStream_t st);
+
+// Infotaxis (pbvi_infotaxis): for every belief row b of `bel` (engine order; caller row d = perm ? perm[b] : b) and action a
+//   G[b,a] = sum_o (Z ln Z - N),  Z = sum_s' u[s'],  N = sum_s' u[s'] ln u[s']  (zero terms add 0; fp64 log),
+//   u[s']  = sum over the inverse list of (a, s') of (double) bel[b][s] * (double) RTO[s,a,o,r]  (launch_belief_update's sum)
+// = the expected entropy, in nats, of the belief after taking a.  Three kernels, no atomics, every sum in a fixed order:
+//   k_succ_entropy<T>   (Z, N) partials of each x-block (succ_entropy_xblocks(S) of them) into part [XB][B][A][O][2]
+//   k_infotaxis_finish  partials summed in x-block order -> g_out [B][A], pobs_out [B][A][O] = Z (or nullptr), action_out [B] =
+//                       the first a with G[b,a] strictly below every earlier one (a NaN never wins; all NaN -> 0), taken from
+//                       the row of g_out as written; all three in the caller's belief order
+//   k_row_entropy<T>    entropy_out [B] = -sum_s b[s] ln b[s] (or nullptr: not launched), caller order
+int succ_entropy_xblocks(int S);
+template <typename T>
+hipError_t launch_infotaxis(const T* bel, int ldb, int B, ModelView<T> mv, const int32_t* in_ptr, const int32_t* in_src,
+                            const int32_t* perm, double* part, double* g_out, int32_t* action_out, double* pobs_out,
+                            double* entropy_out, hipStream_t st);
 
 // one step of the belief walk: out64 [S] / out_store [S_pad] = normalised update of `base` (fp64 [S]) with (a, o);
 // unnorm [S], partial [ceil(S_pad/256)] fp64 scratch; rto64: fp64 copy of RTO in mv's layout, or nullptr = use mv.rto

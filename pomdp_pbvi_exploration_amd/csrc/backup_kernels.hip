@@ -2209,7 +2209,8 @@ template <typename T>
 __global__ void k_belief_push(const T* __restrict__ bel, int ldb, ModelView<T> mv, const int32_t* __restrict__ in_ptr,
                               const int32_t* __restrict__ in_src, const int32_t* __restrict__ act,
                               const int32_t* __restrict__ obs, const int32_t* __restrict__ out_row,
-                              double* __restrict__ unnorm, double* __restrict__ mass) {
+                              double* __restrict__ unnorm, double* __restrict__ mass,
+                              double* __restrict__ mass_part /* [B][gridDim.x], or nullptr: atomics on mass */) {
     __shared__ double red[4];
     const int b = blockIdx.y, sp = blockIdx.x * 256 + threadIdx.x;
     if (out_row && out_row[b] < 0) return;                 // dropped row (whole block leaves together)
@@ -2228,7 +2229,22 @@ __global__ void k_belief_push(const T* __restrict__ bel, int ldb, ModelView<T> m
         unnorm[(int64_t)b * mv.S + sp] = u;
     }
     const double tot = block_sum(u, red);
-    if (threadIdx.x == 0) atomicAdd(&mass[b], tot);        // <= S/256 adds per belief; order only affects the last bit of the norm
+    if (threadIdx.x == 0) {
+        if (mass_part != nullptr) mass_part[(int64_t)b * gridDim.x + blockIdx.x] = tot;   // folded in block order by k_mass_fold
+        else atomicAdd(&mass[b], tot);                     // <= S/256 adds per belief; order only affects the last bit of the norm
+    }
+}
+
+// mass[b] = the blocks' partial masses of k_belief_push added in block order: the norm without the atomics' order-dependent
+// last bit, for the callers whose next decision must not depend on it (the infotaxis rollout, whose policy meets near-ties
+// between actions on symmetric beliefs).  One thread per belief.
+__global__ void k_mass_fold(int B, int nblk, const int32_t* __restrict__ out_row, const double* __restrict__ mass_part,
+                            double* __restrict__ mass) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B || (out_row && out_row[b] < 0)) return;
+    double tot = 0.0;
+    for (int x = 0; x < nblk; ++x) tot += mass_part[(int64_t)b * nblk + x];
+    mass[b] = tot;
 }
 
 template <typename T>
@@ -2244,14 +2260,19 @@ __global__ void k_belief_norm(const double* __restrict__ unnorm, const double* _
 template <typename T>
 hipError_t launch_belief_update(const T* bel, int ldb, int B, ModelView<T> mv, const int32_t* in_ptr, const int32_t* in_src,
                                 const int32_t* act, const int32_t* obs, const int32_t* out_row, double* unnorm,
-                                double* mass, T* out, int ldo, hipStream_t st) {
+                                double* mass, T* out, int ldo, hipStream_t st, double* mass_part) {
     if (B <= 0) return hipSuccess;
     if (B > 65535) return hipErrorInvalidValue;
     dim3 grid((mv.S + 255) / 256, B);
     hipLaunchKernelGGL(k_belief_push<T>, grid, dim3(256), 0, st, bel, ldb, mv, in_ptr, in_src, act, obs, out_row, unnorm,
-                       mass);
+                       mass, mass_part);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    if (mass_part != nullptr) {
+        hipLaunchKernelGGL(k_mass_fold, dim3((B + 255) / 256), dim3(256), 0, st, B, (int)grid.x, out_row, mass_part, mass);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
     hipLaunchKernelGGL(k_belief_norm<T>, grid, dim3(256), 0, st, unnorm, mass, mv.S, out_row, out, ldo);
     return hipGetLastError();
 }
@@ -2670,8 +2691,185 @@ hipError_t launch_rollout_compact(int n, const uint8_t* keep, const int32_t* per
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------- //
+// Infotaxis (pbvi_infotaxis): expected entropy of the successor belief, for every belief of the block and every action.
+//   u[s']  = sum over (s, r) with rs[s,a,r] == s' of (double) b[s] * (double) RTO[s,a,o,r]     (k_belief_push's sum and order)
+//   Z[a,o] = sum_s' u[s'],   N[a,o] = sum_s' u[s'] ln u[s']   (u == 0 adds 0)
+//   G[b,a] = sum_o (Z ln Z - N)  =  sum_o P(o | b, a) H(update(b, a, o))   in nats;   a* = first minimum of G[b, :]
+// The successor beliefs are never stored: u lives in a register between its sum and its two reductions.  Every sum has a
+// fixed order -- the list order inside a thread, a thread's chunks in order, the xor butterfly of a wave, the block's four
+// waves in order, the x-blocks in order in the finish kernel -- and nothing is accumulated with atomics, so a belief's G has
+// the same bits whatever else is in the block and wherever it sits in it.
+// ------------------------------------------------------------------------- //
+constexpr int SE_NB = 4;   // beliefs per thread of k_succ_entropy (they share the list entries and weights)
+constexpr int SE_NT = 8;   // 256-state chunks per block
+constexpr int SE_NO = 4;   // observations per pass
+
+int succ_entropy_xblocks(int S) { return (S + 256 * SE_NT - 1) / (256 * SE_NT); }
+
+template <typename T>
+__global__ void __launch_bounds__(256) k_succ_entropy(const T* __restrict__ bel, int ldb, int B, ModelView<T> mv,
+                                                      const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ in_src,
+                                                      double* __restrict__ part /* [gridDim.x][B][A][O][2] */) {
+    // One thread per landing state s' and SE_NB beliefs, as k_push_project; a block walks SE_NT chunks of 256 states and
+    // reduces its (Z, N) partials once per pass over (up to) SE_NO observations.
+    __shared__ double red[4][2 * SE_NB * SE_NO];
+    const int b0 = blockIdx.y * SE_NB, a = blockIdx.z;
+    const int nb = B - b0 < SE_NB ? B - b0 : SE_NB;
+    const int32_t* ptr = in_ptr + (int64_t)a * (mv.S + 1);
+    const int32_t* src = in_src + (int64_t)a * mv.S * mv.R;
+    for (int o0 = 0; o0 < mv.O; o0 += SE_NO) {
+        const int no = mv.O - o0 < SE_NO ? mv.O - o0 : SE_NO;
+        double zs[SE_NB][SE_NO], ns[SE_NB][SE_NO];
+#pragma unroll
+        for (int k = 0; k < SE_NB; ++k)
+#pragma unroll
+            for (int q = 0; q < SE_NO; ++q) zs[k][q] = ns[k][q] = 0.0;
+        for (int c = 0; c < SE_NT; ++c) {
+            const int sp = (blockIdx.x * SE_NT + c) * 256 + threadIdx.x;
+            if (sp >= mv.S) break;
+            const int j0 = ptr[sp], j1 = ptr[sp + 1];
+            double acc[SE_NB][SE_NO];
+#pragma unroll
+            for (int k = 0; k < SE_NB; ++k)
+#pragma unroll
+                for (int q = 0; q < SE_NO; ++q) acc[k][q] = 0.0;
+            for (int j = j0; j < j1; ++j) {
+                const int e = src[j];                       // e = s * R + r
+                const int s = mv.R == 1 ? e : e / mv.R, r = e - s * mv.R;
+                double bs[SE_NB];
+                bool any = false;
+#pragma unroll
+                for (int k = 0; k < SE_NB; ++k) {
+                    bs[k] = k < nb ? (double)bel[(int64_t)(b0 + k) * ldb + s] : 0.0;
+                    any = any || bs[k] != 0.0;
+                }
+                if (any) {                                  // (an entry whose belief value is zero adds an exact zero)
+#pragma unroll
+                    for (int q = 0; q < SE_NO; ++q)
+                        if (q < no) {
+                            const double w = (double)mv.rto[((int64_t)(a * mv.O + o0 + q) * mv.R + r) * mv.S_pad + s];
+#pragma unroll
+                            for (int k = 0; k < SE_NB; ++k) acc[k][q] += bs[k] * w;
+                        }
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < SE_NB; ++k)
+#pragma unroll
+                for (int q = 0; q < SE_NO; ++q) {
+                    const double u = acc[k][q];
+                    if (u != 0.0) {
+                        zs[k][q] += u;
+                        ns[k][q] += u * log(u);
+                    }
+                }
+        }
+#pragma unroll
+        for (int k = 0; k < SE_NB; ++k)
+#pragma unroll
+            for (int q = 0; q < SE_NO; ++q) {
+                zs[k][q] = wave_sum(zs[k][q]);
+                ns[k][q] = wave_sum(ns[k][q]);
+            }
+        __syncthreads();                                    // red[] of the previous pass has been read
+        if ((threadIdx.x & 63) == 0) {
+            double* mine = red[threadIdx.x >> 6];
+#pragma unroll
+            for (int k = 0; k < SE_NB; ++k)
+#pragma unroll
+                for (int q = 0; q < SE_NO; ++q) {
+                    mine[(k * SE_NO + q) * 2] = zs[k][q];
+                    mine[(k * SE_NO + q) * 2 + 1] = ns[k][q];
+                }
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < 2 * SE_NB * SE_NO) {
+            const int i = threadIdx.x, k = i / (2 * SE_NO), q = (i >> 1) % SE_NO;
+            if (k < nb && q < no) {
+                const double v = ((red[0][i] + red[1][i]) + red[2][i]) + red[3][i];
+                part[((((int64_t)blockIdx.x * B + b0 + k) * mv.A + a) * mv.O + o0 + q) * 2 + (i & 1)] = v;
+            }
+        }
+    }
+}
+
+// One block per belief (engine row b, caller row d = perm[b]): lane a, a + 64, ... sums the partials of (b, a, o) in x-block
+// order, forms G[b, a] and writes it (and Z as p_obs) to the caller's row; thread 0 then takes the first minimum of the row
+// that was written -- a NaN never wins, a row of NaNs gives 0: np.argmin(np.where(np.isnan(G), np.inf, G)).
+__global__ void __launch_bounds__(64) k_infotaxis_finish(int B, int A, int O, int XB, const int32_t* __restrict__ perm /* or nullptr */,
+                                                         const double* __restrict__ part, double* g_o, int32_t* __restrict__ action_o,
+                                                         double* __restrict__ pobs_o /* or nullptr */) {
+    const int b = blockIdx.x;
+    const int64_t d = perm ? perm[b] : b;
+    for (int a = threadIdx.x; a < A; a += 64) {
+        double g = 0.0;
+        for (int o = 0; o < O; ++o) {
+            double Z = 0.0, N = 0.0;
+            for (int x = 0; x < XB; ++x) {
+                const double* p = part + ((((int64_t)x * B + b) * A + a) * O + o) * 2;
+                Z += p[0];
+                N += p[1];
+            }
+            if (pobs_o != nullptr) pobs_o[(d * A + a) * O + o] = Z;
+            if (Z != 0.0) g += Z * log(Z) - N;
+        }
+        g_o[d * A + a] = g;
+    }
+    __syncthreads();                                        // the row is complete (written by this block)
+    if (threadIdx.x == 0) {
+        const double* row = g_o + d * A;
+        int best = 0;
+        double bv = row[0];
+        if (bv != bv) bv = std::numeric_limits<double>::infinity();
+        for (int a = 1; a < A; ++a) {
+            const double x = row[a];
+            if (x < bv) {
+                bv = x;
+                best = a;
+            }
+        }
+        action_o[d] = best;
+    }
+}
+
+// H[b] = - sum_s b[s] ln b[s] (b[s] == 0 adds 0): thread t sums s = t, t + 256, ... in order, then block_sum's fixed order.
+template <typename T>
+__global__ void __launch_bounds__(256) k_row_entropy(const T* __restrict__ bel, int ldb, int S, const int32_t* __restrict__ perm,
+                                                     double* __restrict__ out) {
+    __shared__ double red[4];
+    const T* row = bel + (int64_t)blockIdx.x * ldb;
+    double acc = 0.0;
+    for (int s = threadIdx.x; s < S; s += 256) {
+        const double x = (double)row[s];
+        if (x != 0.0) acc += x * log(x);
+    }
+    const double tot = block_sum(acc, red);
+    if (threadIdx.x == 0) out[perm ? perm[blockIdx.x] : blockIdx.x] = -tot;
+}
+
+template <typename T>
+hipError_t launch_infotaxis(const T* bel, int ldb, int B, ModelView<T> mv, const int32_t* in_ptr, const int32_t* in_src,
+                            const int32_t* perm, double* part, double* g_out, int32_t* action_out, double* pobs_out,
+                            double* entropy_out, hipStream_t st) {
+    if (B <= 0) return hipSuccess;
+    if (B > 65535 || mv.A > 65535 || mv.S > ldb || part == nullptr || g_out == nullptr || action_out == nullptr) return hipErrorInvalidValue;
+    const int XB = succ_entropy_xblocks(mv.S);
+    hipLaunchKernelGGL(k_succ_entropy<T>, dim3(XB, (B + SE_NB - 1) / SE_NB, mv.A), dim3(256), 0, st, bel, ldb, B, mv, in_ptr, in_src,
+                       part);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_infotaxis_finish, dim3(B), dim3(64), 0, st, B, mv.A, mv.O, XB, perm, part, g_out, action_out, pobs_out);
+    e = hipGetLastError();
+    if (e != hipSuccess || entropy_out == nullptr) return e;
+    hipLaunchKernelGGL(k_row_entropy<T>, dim3(B), dim3(256), 0, st, bel, ldb, mv.S, perm, entropy_out);
+    return hipGetLastError();
+}
+
 // explicit instantiations
 #define PBVI_INST(T)                                                                                                   \
+    template hipError_t launch_infotaxis<T>(const T*, int, int, ModelView<T>, const int32_t*, const int32_t*,          \
+                                            const int32_t*, double*, double*, int32_t*, double*, double*, hipStream_t); \
     template hipError_t launch_rollout_draw<T>(int, ModelView<T>, const int32_t*, const int32_t*, const int32_t*, int,  \
                                                const int32_t*, const int32_t*, const uint8_t*, uint64_t, uint64_t, int, \
                                                int, int32_t*, int32_t*, int32_t*, uint8_t*, int32_t*, int32_t*,         \
@@ -2707,7 +2905,7 @@ hipError_t launch_rollout_compact(int n, const uint8_t* keep, const int32_t* per
                                        const int32_t*, uint8_t*, hipStream_t);                                         \
     template hipError_t launch_belief_update<T>(const T*, int, int, ModelView<T>, const int32_t*, const int32_t*,      \
                                                 const int32_t*, const int32_t*, const int32_t*, double*, double*, T*,  \
-                                                int, hipStream_t);                                                     \
+                                                int, hipStream_t, double*);                                            \
     template hipError_t launch_push_project<T>(const T*, int, int, ModelView<T>, const int32_t*, const int32_t*,       \
                                                double, const T*, T*, int, double*, hipStream_t, uint8_t*);                      \
     template hipError_t launch_rdot<T>(const T*, int, int, ModelView<T>, const int32_t*, const int32_t*, double*,      \

@@ -724,6 +724,13 @@ struct ScoreStage {
     int chunks;                       // alpha side: chunks Gamma was tiled into (1 = held whole or compact); 0 = belief side
 };
 
+// Where the step loop of the device-resident rollouts takes its action from (EngineT::rollout)
+enum RolloutSource {
+    ROLLOUT_VALUE_MAX = 0,            // alpha_actions[first argmax_v b.alpha_v]       (pbvi_rollout, lookahead 0)
+    ROLLOUT_Q = 1,                    // first argmax_a Q(b, a)                        (pbvi_rollout, lookahead 1)
+    ROLLOUT_INFOTAXIS = 2,            // first argmin_a of the expected successor entropy (pbvi_rollout_infotaxis)
+};
+
 class EngineBase {
    public:
     virtual ~EngineBase() {}
@@ -774,9 +781,11 @@ class EngineBase {
     virtual int walk_keys(int64_t n, uint64_t* out_keys) = 0;
     virtual int backup_value_max(double* out_value) = 0;
     virtual int q_values(double gamma, double* out_q, int32_t* out_action, int32_t* out_best) = 0;
-    virtual int rollout(const int32_t* alpha_actions, int lookahead, double gamma, const int32_t* start_states,
+    // source: the policy of the step loop (RolloutSource); alpha_actions and gamma are read by the sources that need them
+    virtual int rollout(int source, const int32_t* alpha_actions, double gamma, const int32_t* start_states,
                         const uint8_t* end_mask, uint64_t first_sim_id, uint64_t seed, int64_t T, int32_t* out_states,
                         int32_t* out_actions, int32_t* out_observations, int32_t* out_steps) = 0;
+    virtual int infotaxis(double* out_g, int32_t* out_action, double* out_p_obs, double* out_entropy) = 0;
 };
 
 template <typename T>
@@ -863,6 +872,10 @@ class EngineT : public EngineBase {
     // row map (+ 1 int: the survivor count), alpha_actions [V], end mask [S]
     DevBuf ro_traj_, ro_state_[2], ro_orig_[2], ro_keep_, ro_dst_, ro_aact_, ro_end_;
     int64_t zero_row_ = -1;                                  // first s * A + a whose RTO[s, a, :, :] sums to 0 (-1: none)
+    // pbvi_infotaxis: the x-blocks' (Z, N) partials [XB][B][A][O][2]; G [B][A], its first argmin [B], P(o | b, a) [B][A][O]
+    // and the beliefs' own entropies [B], all four in the caller's belief order
+    DevBuf it_part_, it_g_, it_act_, it_pobs_, it_h_;
+    DevBuf bu_mpart_;                                        // advance_resident(fixed_order): the push blocks' partial masses [B][ceil(S/256)]
     DevBuf rf_q2_, rf_q2p_, rf_q2d_;                         // k_refine_split: entries / candidates, partial scores, arrival counters
     DevBuf rf_v_, rf_slot_, rf_sc_, rf_entry_, rf_n_, rf_tiles_, rf_ibv_, rf_ibi_, rf_cnt_, rf_W_, rf_Cx_, rf_nzW_, rf_klW_, rf_kcW_;   // refinement work list
     int formulation_ = 0;                                   // 0 auto, 1 project alpha-vectors, 2 project beliefs
@@ -952,7 +965,7 @@ class EngineT : public EngineBase {
                          &action_res_, &best_res_, &rep_, &uniq_, &inv_, &slot_, &out_full_, &btl_, &btc_, &val_exact_, &store_[0], &store_[1], &ids_, &in_ptr_, &in_src_, &bu_act_, &bu_obs_,
                          &bu_unnorm_, &bu_mass_, &bu_out_, &bu_row_, &walk64_, &rto64_, &bp_, &nzP_, &pmag_, &prd_, &keys_tmp_, &keys_act_, &keys_best_, &keys_rows_, &rf_v_, &rf_slot_, &rf_sc_, &rf_entry_, &rf_n_, &rf_tiles_,
                          &snz_, &sbtl_, &sbtc_, &vmax_bk_, &rf_ibv_, &rf_ibi_, &rf_cnt_, &rf_W_, &rf_Cx_, &rf_nzW_, &rf_klW_, &rf_kcW_,
-                         &dense_, &nzD_, &nzAlpha_, &prod_, &klistD_, &kcountD_, &nchunksD_, &mat_, &vlist_, &irr_, &rowflags_, &nzBw_, &scr_flag_, &ctile_, &acand_, &q_, &q_res_, &q_act_, &rf_q2_, &rf_q2p_, &rf_q2d_, &e_bv_, &e_bs_, &e_err_, &e_rdot_, &e_act_, &e_ares_, &e_bres_, &e_rep_, &e_uniq_, &e_inv_, &e_slotd_, &e_cnt_, &e_out_, &e_slot_, &scores_, &chain_max_, &ro_traj_, &ro_state_[0], &ro_state_[1], &ro_orig_[0], &ro_orig_[1], &ro_keep_, &ro_dst_, &ro_aact_, &ro_end_};
+                         &dense_, &nzD_, &nzAlpha_, &prod_, &klistD_, &kcountD_, &nchunksD_, &mat_, &vlist_, &irr_, &rowflags_, &nzBw_, &scr_flag_, &ctile_, &acand_, &q_, &q_res_, &q_act_, &rf_q2_, &rf_q2p_, &rf_q2d_, &e_bv_, &e_bs_, &e_err_, &e_rdot_, &e_act_, &e_ares_, &e_bres_, &e_rep_, &e_uniq_, &e_inv_, &e_slotd_, &e_cnt_, &e_out_, &e_slot_, &scores_, &chain_max_, &ro_traj_, &ro_state_[0], &ro_state_[1], &ro_orig_[0], &ro_orig_[1], &ro_keep_, &ro_dst_, &ro_aact_, &ro_end_, &it_part_, &it_g_, &it_act_, &it_pobs_, &it_h_, &bu_mpart_};
         // every call is checked only to name a failure when PBVI_DEBUG is set; the thread's sticky last-error is cleared at
         // the end either way, so that a later launch check does not report a stale error of this teardown
         static const bool dbg = getenv("PBVI_DEBUG") != nullptr;
@@ -1494,8 +1507,10 @@ class EngineT : public EngineBase {
     // The Bayes step + done-filter of beliefs_advance from arrays that are on the device already, in ENGINE row order:
     // bu_act_ / bu_obs_ [B_] = (action, observation) of each row, bu_row_ [B_] = its row among the nb survivors (caller
     // order) or -1.  Filled by an upload (beliefs_advance) or by the rollout's draw and filter kernels.
-    int advance_resident(int64_t nb, bool sync_before_finish) {
+    // fixed_order: the norm is summed in block order instead of with atomics (launch_belief_update's mass_part).
+    int advance_resident(int64_t nb, bool sync_before_finish, bool fixed_order = false) {
         int rc;
+        if (fixed_order && (rc = bu_mpart_.ensure((size_t)B_ * ((S_ + 255) / 256) * sizeof(double), &bytes_))) return rc;
         if ((rc = bu_unnorm_.ensure((size_t)B_ * S_ * sizeof(double), &bytes_))) return rc;
         if ((rc = bu_mass_.ensure((size_t)B_ * sizeof(double), &bytes_))) return rc;
         if ((rc = stage_.ensure((size_t)nb * S_pad_ * sizeof(T), &bytes_))) return rc;
@@ -1503,31 +1518,68 @@ class EngineT : public EngineBase {
         HIPCHK(hipMemsetAsync(stage_.p, 0, (size_t)nb * S_pad_ * sizeof(T), stream_));   // pad columns stay zero
         HIPCHK(launch_belief_update<T>(bel_.as<T>(), S_pad_, (int)B_, view(), in_ptr_.as<int32_t>(), in_src_.as<int32_t>(),
                                        bu_act_.as<int32_t>(), bu_obs_.as<int32_t>(), bu_row_.as<int32_t>(),
-                                       bu_unnorm_.as<double>(), bu_mass_.as<double>(), stage_.as<T>(), S_pad_, stream_));
+                                       bu_unnorm_.as<double>(), bu_mass_.as<double>(), stage_.as<T>(), S_pad_, stream_,
+                                       fixed_order ? bu_mpart_.as<double>() : nullptr));
         if (sync_before_finish) HIPCHK(hipStreamSynchronize(stream_));
         return beliefs_finish(nb, stage_.as<T>(), nullptr);
     }
 
-    // T lock-step simulation steps of the resident block against the resident alpha set, on the device (pbvi_rollout):
-    // per step the value-max or Q-value stage with its index left on the device, the simulator draw, the done-filter and
-    // the Bayes step of beliefs_advance.  Finished rows are dropped after EVERY step ("Device-resident
-    // rollouts"): the one host read per step is the survivor count, which sizes the next step's launches.
-    int rollout(const int32_t* alpha_actions, int lookahead, double gamma, const int32_t* start_states, const uint8_t* end_mask,
+    // Expected successor entropies of the resident block (pbvi_infotaxis) into it_g_ / it_act_ (/ it_pobs_ / it_h_), caller
+    // order, left on the device.  Reads the block and the model tables only.
+    int infotaxis_device(bool want_p_obs, bool want_entropy) {
+        if ((int64_t)S_ * R_ > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "infotaxis: S*R exceeds int32");
+        int rc = build_inverse_lists();
+        if (rc) return rc;
+        const size_t ba = (size_t)B_ * A_;
+        if ((rc = it_part_.ensure((size_t)succ_entropy_xblocks(S_) * ba * O_ * 2 * sizeof(double), &bytes_))) return rc;
+        if ((rc = it_g_.ensure(ba * sizeof(double), &bytes_))) return rc;
+        if ((rc = it_act_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
+        if (want_p_obs && (rc = it_pobs_.ensure(ba * O_ * sizeof(double), &bytes_))) return rc;
+        if (want_entropy && (rc = it_h_.ensure((size_t)B_ * sizeof(double), &bytes_))) return rc;
+        HIPCHK(launch_infotaxis<T>(bel_.as<T>(), S_pad_, (int)B_, view(), in_ptr_.as<int32_t>(), in_src_.as<int32_t>(),
+                                   sorted_ ? perm_.as<int32_t>() : nullptr, it_part_.as<double>(), it_g_.as<double>(),
+                                   it_act_.as<int32_t>(), want_p_obs ? it_pobs_.as<double>() : nullptr,
+                                   want_entropy ? it_h_.as<double>() : nullptr, stream_));
+        return PBVI_OK;
+    }
+
+    int infotaxis(double* out_g, int32_t* out_action, double* out_p_obs, double* out_entropy) override {
+        if (!out_g) FAIL(PBVI_EINVAL, "infotaxis: NULL out_g");
+        if (B_ <= 0) FAIL(PBVI_EINVAL, "infotaxis: no belief block resident (call pbvi_beliefs_set)");
+        HIPCHK(hipSetDevice(device_));
+        int rc = infotaxis_device(out_p_obs != nullptr, out_entropy != nullptr);
+        if (rc) return rc;
+        if ((rc = out_begin())) return rc;
+        if ((rc = out_add(out_g, it_g_.p, (size_t)B_ * A_ * sizeof(double)))) return rc;
+        if (out_action && (rc = out_add(out_action, it_act_.p, (size_t)B_ * sizeof(int32_t)))) return rc;
+        if (out_p_obs && (rc = out_add(out_p_obs, it_pobs_.p, (size_t)B_ * A_ * O_ * sizeof(double)))) return rc;
+        if (out_entropy && (rc = out_add(out_entropy, it_h_.p, (size_t)B_ * sizeof(double)))) return rc;
+        return out_finish();
+    }
+
+    // T lock-step simulation steps of the resident block on the device (pbvi_rollout, pbvi_rollout_infotaxis): per step the
+    // action source's stage with its index left on the device (value-max or Q-values against the resident alpha set, or
+    // the successor entropies of infotaxis_device), the simulator draw, the done-filter and the Bayes step of
+    // beliefs_advance.  Finished rows are dropped after EVERY step ("Device-resident rollouts"): the one host
+    // read per step is the survivor count, which sizes the next step's launches.
+    int rollout(int source, const int32_t* alpha_actions, double gamma, const int32_t* start_states, const uint8_t* end_mask,
                 uint64_t first_sim_id, uint64_t seed, int64_t n_steps, int32_t* out_states, int32_t* out_actions,
                 int32_t* out_observations, int32_t* out_steps) override {
-        if (V_ <= 0) FAIL(PBVI_EINVAL, "rollout: no alpha set resident (call pbvi_alpha_set)");
+        const bool uses_alpha = source != ROLLOUT_INFOTAXIS;
+        if (uses_alpha && V_ <= 0) FAIL(PBVI_EINVAL, "rollout: no alpha set resident (call pbvi_alpha_set)");
         if (B_ <= 0) FAIL(PBVI_EINVAL, "rollout: no belief block resident (call pbvi_beliefs_set)");
-        if (!alpha_actions || !start_states || !end_mask) FAIL(PBVI_EINVAL, "rollout: NULL argument");
-        if (lookahead != 0 && lookahead != 1) FAIL(PBVI_EINVAL, "rollout: lookahead must be 0 or 1");
+        if ((uses_alpha && !alpha_actions) || !start_states || !end_mask) FAIL(PBVI_EINVAL, "rollout: NULL argument");
+        if (source != ROLLOUT_VALUE_MAX && source != ROLLOUT_Q && source != ROLLOUT_INFOTAXIS)
+            FAIL(PBVI_EINVAL, "rollout: lookahead must be 0 or 1");
         if (n_steps < 1) FAIL(PBVI_EINVAL, "rollout: T must be at least 1");
-        if (lookahead == 1 && mode_ != PBVI_SPARSE)
+        if (source == ROLLOUT_Q && mode_ != PBVI_SPARSE)
             FAIL(PBVI_EUNSUPPORTED, "rollout: lookahead = 1 is not available on a PBVI_DENSE engine (create it with PBVI_SPARSE)");
         const int64_t n0 = B_;
         if (n_steps >= 0x7fffffff || (n_steps + 1) * n0 > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "rollout: T * B exceeds the int32 trajectory slot index");
         if ((int64_t)S_ * R_ > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "rollout: S*R exceeds int32");
         for (int64_t b = 0; b < n0; ++b)
             if (start_states[b] < 0 || start_states[b] >= S_) FAIL(PBVI_EINVAL, "rollout: start state out of range [0,S)");
-        for (int64_t v = 0; v < V_; ++v)
+        for (int64_t v = 0; uses_alpha && v < V_; ++v)
             if (alpha_actions[v] < 0 || alpha_actions[v] >= A_) FAIL(PBVI_EINVAL, "rollout: alpha_actions entry out of range [0,A)");
         if (zero_row_ >= 0)
             FAIL(PBVI_EINVAL, "rollout: RTO[s,a,:,:] sums to 0 for s = " + std::to_string(zero_row_ / A_) + ", a = " +
@@ -1542,7 +1594,7 @@ class EngineT : public EngineBase {
         }
         if ((rc = ro_keep_.ensure((size_t)n0, &bytes_))) return rc;
         if ((rc = ro_dst_.ensure((size_t)(n0 + 1) * sizeof(int32_t), &bytes_))) return rc;
-        if ((rc = ro_aact_.ensure((size_t)V_ * sizeof(int32_t), &bytes_))) return rc;
+        if (uses_alpha && (rc = ro_aact_.ensure((size_t)V_ * sizeof(int32_t), &bytes_))) return rc;
         if ((rc = ro_end_.ensure((size_t)S_, &bytes_))) return rc;
         if ((rc = bu_act_.ensure((size_t)n0 * sizeof(int32_t), &bytes_))) return rc;
         if ((rc = bu_obs_.ensure((size_t)n0 * sizeof(int32_t), &bytes_))) return rc;
@@ -1563,30 +1615,33 @@ class EngineT : public EngineBase {
             HIPCHK(hipMemcpyAsync(tr_steps, full.data(), (size_t)n0 * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
             HIPCHK(hipMemcpyAsync(ro_state_[0].p, start_states, (size_t)n0 * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
             HIPCHK(hipMemcpyAsync(ro_orig_[0].p, iota.data(), (size_t)n0 * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-            HIPCHK(hipMemcpyAsync(ro_aact_.p, alpha_actions, (size_t)V_ * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+            if (uses_alpha) HIPCHK(hipMemcpyAsync(ro_aact_.p, alpha_actions, (size_t)V_ * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
             HIPCHK(hipMemcpyAsync(ro_end_.p, end_mask, (size_t)S_, hipMemcpyHostToDevice, stream_));
             HIPCHK(hipStreamSynchronize(stream_));            // the caller's arrays and the two vectors are free again
         }
         int oc = 0;
         for (int64_t t = 0; t < n_steps; ++t) {
             const int32_t* index;
-            if (lookahead == 0) {
+            if (source == ROLLOUT_VALUE_MAX) {
                 if ((rc = value_max_device())) return rc;
-                index = bv2_.as<int32_t>();                   // engine row order
-            } else {
+                index = bv2_.as<int32_t>();                   // engine row order, an alpha row: mapped through alpha_actions
+            } else if (source == ROLLOUT_Q) {
                 q_only_ = true;
                 q_want_best_ = false;
                 rc = backup_run(gamma, 0, nullptr);
                 q_only_ = false;
                 have_result_ = have_bk_vmax_ = false;
                 if (rc) return rc;
-                index = q_act_.as<int32_t>();                 // caller row order
+                index = q_act_.as<int32_t>();                 // caller row order, an action
+            } else {
+                if ((rc = infotaxis_device(false, false))) return rc;
+                index = it_act_.as<int32_t>();                // caller row order, an action
             }
             const int n = (int)B_;
             const int32_t* perm = sorted_ ? perm_.as<int32_t>() : nullptr;
             // true states: live in ro_state_[0]; the draw leaves the next states in [1], row for row, and the filter moves
             // the survivors' back up into [0].  Trajectory rows: the filter moves them from one ro_orig_ buffer to the other.
-            HIPCHK(launch_rollout_draw<T>(n, view(), perm, index, lookahead == 0 ? ro_aact_.as<int32_t>() : nullptr, (int)V_,
+            HIPCHK(launch_rollout_draw<T>(n, view(), perm, index, source == ROLLOUT_VALUE_MAX ? ro_aact_.as<int32_t>() : nullptr, (int)V_,
                                           ro_state_[0].as<int32_t>(), ro_orig_[oc].as<int32_t>(), ro_end_.as<uint8_t>(), seed,
                                           first_sim_id, (int)t, (int)n0, bu_act_.as<int32_t>(), bu_obs_.as<int32_t>(),
                                           ro_state_[1].as<int32_t>(), ro_keep_.as<uint8_t>(), tr_states, tr_actions, tr_obs,
@@ -1607,7 +1662,9 @@ class EngineT : public EngineBase {
                 have_result_ = false;
                 break;
             }
-            if ((rc = advance_resident(nb, false))) return rc;
+            // (infotaxis meets near-ties between actions on symmetric beliefs: its trajectories must not hang on the
+            // arrival order of the norm's atomics, so its Bayes step sums the norm in a fixed order)
+            if ((rc = advance_resident(nb, false, source == ROLLOUT_INFOTAXIS))) return rc;
         }
         const int32_t* src[4] = {tr_states, tr_actions, tr_obs, tr_steps};
         int32_t* dsts[4] = {out_states, out_actions, out_observations, out_steps};
@@ -1876,7 +1933,7 @@ class EngineT : public EngineBase {
                           &bu_mass_, &bu_out_, &bu_row_, &walk64_, &bp_, &nzP_, &pmag_, &prd_, &keys_tmp_, &keys_act_, &keys_best_,
                           &keys_rows_, &rf_v_, &rf_slot_, &rf_sc_, &rf_entry_, &rf_n_, &rf_tiles_, &snz_, &sbtl_, &sbtc_, &vmax_bk_,
                           &rf_ibv_, &rf_ibi_, &rf_cnt_, &rf_W_, &rf_Cx_, &rf_nzW_, &rf_klW_, &rf_kcW_, &nzAlpha_, &prod_, &klistD_,
-                          &kcountD_, &nchunksD_, &mat_, &vlist_, &rowflags_, &ctile_, &acand_, &q_, &q_res_, &q_act_, &rf_q2_, &rf_q2p_, &rf_q2d_, &e_bv_, &e_bs_, &e_err_, &e_rdot_, &e_act_, &e_ares_, &e_bres_, &e_rep_, &e_uniq_, &e_inv_, &e_slotd_, &e_out_, &e_slot_, &scores_, &ro_traj_, &ro_state_[0], &ro_state_[1], &ro_orig_[0], &ro_orig_[1], &ro_keep_, &ro_dst_, &ro_aact_, &ro_end_};
+                          &kcountD_, &nchunksD_, &mat_, &vlist_, &rowflags_, &ctile_, &acand_, &q_, &q_res_, &q_act_, &rf_q2_, &rf_q2p_, &rf_q2d_, &e_bv_, &e_bs_, &e_err_, &e_rdot_, &e_act_, &e_ares_, &e_bres_, &e_rep_, &e_uniq_, &e_inv_, &e_slotd_, &e_out_, &e_slot_, &scores_, &ro_traj_, &ro_state_[0], &ro_state_[1], &ro_orig_[0], &ro_orig_[1], &ro_keep_, &ro_dst_, &ro_aact_, &ro_end_, &it_part_, &it_g_, &it_act_, &it_pobs_, &it_h_, &bu_mpart_};
         for (DevBuf* b : drop) {
             bytes_ -= (int64_t)b->cap;
             b->release();
@@ -4393,7 +4450,20 @@ int pbvi_rollout(pbvi_engine_t* e, const int32_t* alpha_actions, int lookahead, 
                  const uint8_t* end_mask, uint64_t first_sim_id, uint64_t seed, int64_t T, int32_t* out_states,
                  int32_t* out_actions, int32_t* out_observations, int32_t* out_steps) {
     NEED(e);
-    return e->impl->rollout(alpha_actions, lookahead, gamma, start_states, end_mask, first_sim_id, seed, T, out_states,
+    // (any other lookahead is refused by the step loop as a source it does not know)
+    const int source = lookahead == 0 ? pbvi::ROLLOUT_VALUE_MAX : lookahead == 1 ? pbvi::ROLLOUT_Q : -1;
+    return e->impl->rollout(source, alpha_actions, gamma, start_states, end_mask, first_sim_id, seed, T, out_states, out_actions,
+                            out_observations, out_steps);
+}
+int pbvi_infotaxis(pbvi_engine_t* e, double* out_g, int32_t* out_action, double* out_p_obs, double* out_entropy) {
+    NEED(e);
+    return e->impl->infotaxis(out_g, out_action, out_p_obs, out_entropy);
+}
+int pbvi_rollout_infotaxis(pbvi_engine_t* e, const int32_t* start_states, const uint8_t* end_mask, uint64_t first_sim_id,
+                           uint64_t seed, int64_t T, int32_t* out_states, int32_t* out_actions, int32_t* out_observations,
+                           int32_t* out_steps) {
+    NEED(e);
+    return e->impl->rollout(pbvi::ROLLOUT_INFOTAXIS, nullptr, 0.0, start_states, end_mask, first_sim_id, seed, T, out_states,
                             out_actions, out_observations, out_steps);
 }
 int pbvi_beliefs_fetch(pbvi_engine_t* e, void* out_beliefs) {

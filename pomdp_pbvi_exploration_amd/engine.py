@@ -35,7 +35,7 @@ EXPORTS = [
     'pbvi_backup_fetch_compact', 'pbvi_host_alloc', 'pbvi_host_free', 'pbvi_debug_gemm_dense',
     'pbvi_backup_fetch_exchange_padded', 'pbvi_assemble_rows_store', 'pbvi_exchange_merge', 'pbvi_backup_run_fetch', 'pbvi_debug_alloc_limit', 'pbvi_engine_after_oom', 'pbvi_set_f64_screen', 'pbvi_set_fused_projection', 'pbvi_backup_fetch_row_hashes', 'pbvi_set_score_split',
     'pbvi_set_gamma_tiling', 'pbvi_gamma_tiling_plan', 'pbvi_q_values', 'pbvi_prune_dominated_masked',
-    'pbvi_rollout',
+    'pbvi_rollout', 'pbvi_infotaxis', 'pbvi_rollout_infotaxis',
 ]
 
 
@@ -120,6 +120,8 @@ def load_library(path: str = LIB_PATH):
         'pbvi_beliefs_advance': (C.c_int, [vp, i32p, i32p, u8p, C.POINTER(C.c_int64)]),
         'pbvi_rollout': (C.c_int, [vp, i32p, C.c_int, C.c_double, i32p, u8p, C.c_uint64, C.c_uint64, C.c_int64,
                                    i32p, i32p, i32p, i32p]),
+        'pbvi_infotaxis': (C.c_int, [vp, f64p, i32p, f64p, f64p]),
+        'pbvi_rollout_infotaxis': (C.c_int, [vp, i32p, u8p, C.c_uint64, C.c_uint64, C.c_int64, i32p, i32p, i32p, i32p]),
         'pbvi_beliefs_fetch': (C.c_int, [vp, vp]),
         'pbvi_beliefs_count': (C.c_int64, [vp]),
         'pbvi_mdp_value_iteration': (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, i32p, f64p, f64p, f64p,
@@ -992,6 +994,26 @@ class Engine:
             return q, act.astype(np.int64), best.astype(np.int64)
         return q, act.astype(np.int64)
 
+    def infotaxis_resident(self, want_p_obs: bool = False, want_entropy: bool = False):
+        """Expected entropy of the next belief, for every belief of the resident block and every action (``pbvi_infotaxis``):
+        ``(G [B,A] f64, argmin_a G [B])`` with ``G[b,a] = sum_o P(o|b,a) H(update(b,a,o))`` in nats; ``want_p_obs`` appends
+        ``P(o|b,a) [B,A,O]``, ``want_entropy`` the beliefs' own entropies ``[B]``.  Needs no alpha set and leaves the block
+        where it is."""
+        f64p = C.POINTER(C.c_double)
+        g = np.empty((self.B, self.A), dtype=np.float64)
+        act = np.empty(self.B, dtype=np.int32)
+        p_obs = np.empty((self.B, self.A, self.O), dtype=np.float64) if want_p_obs else None
+        ent = np.empty(self.B, dtype=np.float64) if want_entropy else None
+        self._ck(self._lib.pbvi_infotaxis(self._h, g.ctypes.data_as(f64p), act.ctypes.data_as(C.POINTER(C.c_int32)),
+                                        p_obs.ctypes.data_as(f64p) if want_p_obs else None,
+                                        ent.ctypes.data_as(f64p) if want_entropy else None))
+        out = (g, act.astype(np.int64))
+        if want_p_obs:
+            out += (p_obs,)
+        if want_entropy:
+            out += (ent,)
+        return out
+
     def belief_update(self, beliefs: np.ndarray, actions, observations) -> np.ndarray:
         """Batched Bayes step: row b of the result is ``Belief(beliefs[b]).update(actions[b], observations[b])``
         (``src/pomdp.py:382-421``) computed on the device."""
@@ -1095,6 +1117,35 @@ class Engine:
                                         int(first_sim_id), int(seed), T, states.ctypes.data_as(i32p),
                                         actions.ctypes.data_as(i32p), observations.ctypes.data_as(i32p),
                                         steps.ctypes.data_as(i32p)))
+        self.B = int(self._lib.pbvi_beliefs_count(self._h))
+        return states, actions, observations, steps
+
+    def rollout_infotaxis(self, start_states, end_mask, seed: int, T: int, first_sim_id: int = 0):
+        """``rollout`` with the infotaxis policy (``pbvi_rollout_infotaxis``): every step takes the action with the smallest
+        expected entropy of the next belief (``infotaxis_resident``'s argmin) instead of asking an alpha set.  Same draws,
+        same done rule, same return value and same state of the resident block afterwards as ``rollout``."""
+        ss = np.ascontiguousarray(start_states, dtype=np.int32)
+        em = np.ascontiguousarray(end_mask, dtype=np.uint8)
+        if ss.shape != (self.B,):
+            raise ValueError('start_states must be [B]')
+        if em.shape != (self.S,):
+            raise ValueError('end_mask must be [S]')
+        if not (0 <= int(seed) < 1 << 64 and 0 <= int(first_sim_id) < 1 << 64):
+            raise ValueError('seed and first_sim_id must fit an unsigned 64-bit integer')
+        T, B = int(T), self.B
+        if T >= 1 and (T + 1) * B <= 0x7fffffff:
+            states = np.empty((T + 1, B), dtype=np.int32)
+            actions = np.empty((T, B), dtype=np.int32)
+            observations = np.empty((T, B), dtype=np.int32)
+        else:                                    # the call refuses these: nothing is written
+            states = actions = observations = np.empty((0, B), dtype=np.int32)
+        steps = np.empty(B, dtype=np.int32)
+        i32p = C.POINTER(C.c_int32)
+        self._resident['belief'] = None
+        self._ck(self._lib.pbvi_rollout_infotaxis(self._h, ss.ctypes.data_as(i32p), em.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                  int(first_sim_id), int(seed), T, states.ctypes.data_as(i32p),
+                                                  actions.ctypes.data_as(i32p), observations.ctypes.data_as(i32p),
+                                                  steps.ctypes.data_as(i32p)))
         self.B = int(self._lib.pbvi_beliefs_count(self._h))
         return states, actions, observations, steps
 

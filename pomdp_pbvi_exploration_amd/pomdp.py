@@ -1219,6 +1219,17 @@ def rollout_numpy(model, alpha, alpha_actions, beliefs, start_states, seed: int,
         raise ValueError('start_states must be [n] with entries in [0, S)')
     if acts.shape != (alpha.shape[0],) or acts.min() < 0 or acts.max() >= A:
         raise ValueError('alpha_actions must be [V] with entries in [0, A)')
+    block = _HostBeliefBlock(m, SimpleNamespace(alpha_vector_array=alpha), b)
+    choose = (lambda: block.best_actions(gamma)) if lookahead == 1 else (lambda: acts[block.best_vectors()])
+    return _rollout_loop(m, block, choose, s, seed, first_sim_id, T, table_dtype, return_beliefs)
+
+
+def _rollout_loop(m, block, choose, s, seed: int, first_sim_id: int, T: int, table_dtype, return_beliefs: bool):
+    """The step loop of the counter-based rollouts (``rollout_numpy``, ``rollout_infotaxis_numpy``): ``choose()`` gives the
+    actions of the beliefs ``block`` holds; the uniform, the draw, the done-filter and the Bayes step are the same for
+    every policy.  ``m``: ``_rollout_tables``' tables, ``s``: the validated start states."""
+    S, A, O, R = m.state_count, m.action_count, m.observation_count, m.reachable_state_count
+    n = s.shape[0]
     rto = np.ascontiguousarray(m.reachable_transitional_observation_table, dtype=table_dtype).astype(np.float64).reshape(S, A, O * R)
     if not np.all(np.cumsum(rto, axis=2)[:, :, -1] > 0):
         raise ValueError('a row of RTO[s, a, :, :] sums to 0: nothing can follow that state-action pair')
@@ -1231,12 +1242,11 @@ def rollout_numpy(model, alpha, alpha_actions, beliefs, start_states, seed: int,
     observations = np.full((T, n), -1, dtype=np.int32)
     steps = np.full(n, T, dtype=np.int32)
     states[0] = s
-    block = _HostBeliefBlock(m, SimpleNamespace(alpha_vector_array=alpha), b)
     alive = np.arange(n)
     for t in range(T):
         if alive.size == 0:
             break
-        a = block.best_actions(gamma) if lookahead == 1 else acts[block.best_vectors()]
+        a = choose()
         k = rollout_draw(rto[s, a], rollout_uniform(seed, ids[alive], t))
         o, sn = k // R, m.reachable_states[s, a, k % R]
         done = end[sn]
@@ -1249,11 +1259,98 @@ def rollout_numpy(model, alpha, alpha_actions, beliefs, start_states, seed: int,
     return states, actions, observations, steps
 
 
+# --------------------------------------------------------------------------- #
+# Infotaxis: the action with the smallest expected entropy of the next belief (what ``pbvi_infotaxis`` computes)
+# --------------------------------------------------------------------------- #
+def _xlogx(x: np.ndarray) -> np.ndarray:
+    """``x * ln x`` element by element, 0 where ``x == 0``."""
+    out = np.zeros_like(x, dtype=np.float64)
+    nz = x != 0
+    with np.errstate(invalid='ignore', divide='ignore'):
+        out[nz] = x[nz] * np.log(x[nz])
+    return out
+
+
+def _infotaxis_terms(model, beliefs, table_dtype=np.float64, rows_at_once: Union[int, None] = None):
+    """The sums of ``infotaxis_numpy`` and the magnitudes of their terms: ``(G [n,A], Z [n,A,O], H [n], M_G [n,A], M_H [n])``
+    with ``M_G = sum_o (|Z ln Z| + sum_s' |u ln u|)`` and ``M_H = sum_s |b ln b|`` (what a rounding-error bound for a
+    re-ordered evaluation of ``G`` and ``H`` scales with)."""
+    m = _rollout_tables(model)
+    S, A, O, R = m.state_count, m.action_count, m.observation_count, m.reachable_state_count
+    b = np.asarray(beliefs, dtype=np.float64)
+    if b.ndim != 2 or b.shape[1] != S:
+        raise ValueError(f'beliefs must be a [*, {S}] array')
+    n = b.shape[0]
+    rto = np.ascontiguousarray(m.reachable_transitional_observation_table, dtype=table_dtype).astype(np.float64)
+    rs = np.asarray(m.reachable_states).astype(np.int64)
+    G, MG, Z = np.zeros((n, A)), np.zeros((n, A)), np.zeros((n, A, O))
+    step = max(1, (1 << 22) // (S * R)) if rows_at_once is None else int(rows_at_once)     # ~32 MiB of weights at a time
+    for i0 in range(0, n, step):
+        bb = b[i0:i0 + step]
+        k = bb.shape[0]
+        base = np.arange(k)[:, None] * S
+        for a in range(A):
+            idx = (rs[:, a, :].reshape(1, S * R) + base).ravel()                 # entry s * R + r lands on rs[s, a, r]
+            for o in range(O):
+                w = (bb[:, :, None] * rto[None, :, a, o, :]).reshape(k, S * R)
+                u = np.bincount(idx, weights=w.ravel(), minlength=k * S).reshape(k, S)
+                ulu = _xlogx(u)
+                z = np.sum(u, axis=1)
+                zlz = _xlogx(z)
+                Z[i0:i0 + k, a, o] = z
+                G[i0:i0 + k, a] += zlz - np.sum(ulu, axis=1)
+                MG[i0:i0 + k, a] += np.abs(zlz) + np.sum(np.abs(ulu), axis=1)
+    blb = _xlogx(b)
+    return G, Z, -np.sum(blb, axis=1), MG, np.sum(np.abs(blb), axis=1)
+
+
+def infotaxis_first_argmin(G: np.ndarray) -> np.ndarray:
+    """The first action whose ``G`` is strictly smaller than every earlier one; a NaN never wins, a row of NaNs gives 0."""
+    return np.argmin(np.where(np.isnan(G), np.inf, G), axis=1)
+
+
+def infotaxis_numpy(model, beliefs, table_dtype=np.float64):
+    """Expected entropy of the next belief for every row of ``beliefs [n,S]`` and every action, on the host: what
+    ``pbvi_infotaxis`` computes on the device.  With ``u[s'] = sum_{(s,r): rs[s,a,r] = s'} b[s] RTO[s,a,o,r]`` (``np.bincount``,
+    the un-normalised ``Belief.update``; the table cast to ``table_dtype``, the engine's number format, and widened),
+    ``Z[a,o] = sum_s' u`` and ``N[a,o] = sum_s' u ln u``:
+
+        ``G[b,a] = sum_o (Z ln Z - N) = sum_o P(o|b,a) H(update(b,a,o))``   (nats; zero terms add 0)
+
+    Returns ``(G [n,A], action [n], p_obs [n,A,O], entropy [n])``: ``action`` is ``infotaxis_first_argmin(G)``, ``p_obs`` is
+    ``Z`` and ``entropy[b] = -sum_s b[s] ln b[s]``, the entropy of the belief itself."""
+    G, Z, H, _, _ = _infotaxis_terms(model, beliefs, table_dtype)
+    return G, infotaxis_first_argmin(G), Z, H
+
+
+def rollout_infotaxis_numpy(model, beliefs, start_states, seed: int, first_sim_id: int, T: int, table_dtype=np.float64,
+                            return_beliefs: bool = False):
+    """``rollout_numpy`` with the infotaxis policy, on the host: what ``pbvi_rollout_infotaxis`` computes on the device.
+    Per step and running simulation the action is ``infotaxis_numpy(model, b, table_dtype)``'s; the uniform, the draw, the
+    Bayes update, the done-filter and the return value are ``rollout_numpy``'s."""
+    m = _rollout_tables(model)
+    S = m.state_count
+    T = int(T)
+    if T < 1:
+        raise ValueError('T must be at least 1')
+    b = np.array(beliefs, dtype=np.float64)
+    s = np.asarray(start_states).astype(np.int64)
+    n = b.shape[0]
+    if b.ndim != 2 or b.shape[1] != S:
+        raise ValueError(f'beliefs must be a [*, {S}] array')
+    if s.shape != (n,) or (n and (s.min() < 0 or s.max() >= S)):
+        raise ValueError('start_states must be [n] with entries in [0, S)')
+    block = _HostBeliefBlock(m, None, b)
+    return _rollout_loop(m, block, lambda: block.infotaxis_actions(table_dtype), s, seed, first_sim_id, T, table_dtype,
+                         return_beliefs)
+
+
 class _HostBeliefBlock:
     """Belief block of the parallel simulator held in NumPy (reference CPU statements, ``:3029``, ``:3306-3311``)."""
 
     def __init__(self, model: Model, value_function: ValueFunction, beliefs: np.ndarray):
-        self.m, self.alpha, self.b = model, value_function.alpha_vector_array, beliefs
+        self.m, self.b = model, beliefs
+        self.alpha = None if value_function is None else value_function.alpha_vector_array      # (infotaxis has none)
 
     def best_vectors(self) -> np.ndarray:
         return np.argmax(np.matmul(self.b, self.alpha.T), axis=1)
@@ -1261,6 +1358,10 @@ class _HostBeliefBlock:
     def best_actions(self, gamma: float) -> np.ndarray:
         """One-step lookahead: ``argmax_a Q(b,a)`` of every belief of the block."""
         return np.argmax(_q_values_numpy(self.m, self.b, self.alpha, gamma), axis=1)
+
+    def infotaxis_actions(self, table_dtype=np.float64) -> np.ndarray:
+        """Infotaxis: the first ``argmin_a`` of the expected successor entropy of every belief of the block."""
+        return infotaxis_numpy(self.m, self.b, table_dtype)[1]
 
     def advance(self, actions: np.ndarray, observations: np.ndarray, keep: np.ndarray) -> None:
         m, n = self.m, self.b.shape[0]
@@ -1285,7 +1386,8 @@ class _DeviceBeliefBlock:
 
     def __init__(self, model: Model, value_function: ValueFunction, beliefs: np.ndarray):
         self.eng = model.engine
-        self.eng.sync_rows('alpha', value_function.alpha_vector_list, lambda v: v.values)
+        if value_function is not None:                          # (infotaxis has none)
+            self.eng.sync_rows('alpha', value_function.alpha_vector_list, lambda v: v.values)
         self.chunks = None
         if beliefs.shape[0] <= 65535:
             self.eng.set_beliefs(beliefs)
@@ -1310,6 +1412,17 @@ class _DeviceBeliefBlock:
         for c in self.chunks:
             self.eng.set_beliefs(c)
             out.append(self.eng.q_values_resident(gamma)[1])
+        return np.concatenate(out) if out else np.zeros(0, dtype=np.int64)
+
+    def infotaxis_actions(self) -> np.ndarray:
+        """Infotaxis: the first ``argmin_a`` of the expected successor entropy of every belief of the block
+        (``pbvi_infotaxis``; the resident block stays on the device)."""
+        if self.chunks is None:
+            return self.eng.infotaxis_resident()[1]
+        out = []
+        for c in self.chunks:
+            self.eng.set_beliefs(c)
+            out.append(self.eng.infotaxis_resident()[1])
         return np.concatenate(out) if out else np.zeros(0, dtype=np.int64)
 
     def advance(self, actions: np.ndarray, observations: np.ndarray, keep: np.ndarray) -> None:
@@ -1350,6 +1463,17 @@ class Agent:
         self.value_function, hist = solver.solve(self.model, expansions, horizon)
         return hist
 
+    def _on_gpu(self) -> bool:
+        """Whether this agent's policy is evaluated in the HIP engine."""
+        assert self.value_function is not None, "No value function, training probably has to be run..."
+        return self.value_function.is_on_gpu
+
+    def _block_actions(self, block) -> np.ndarray:
+        """The policy's actions for the beliefs of a belief block of the parallel simulator."""
+        if self.lookahead == 1:
+            return block.best_actions(self.gamma)
+        return self.value_function.actions[block.best_vectors()]
+
     def get_best_action(self, belief):
         """``actions[argmax_v b.alpha_v]`` for one ``Belief`` (returns int) or a ``[n,S]`` array (``:3005-3034``)."""
         vf = self.value_function
@@ -1378,8 +1502,7 @@ class Agent:
     def simulate(self, simulator: Union[Simulation, None] = None, max_steps: int = 1000,
                  start_state: Union[int, None] = None, initial_belief: Union[Belief, None] = None,
                  print_progress: bool = True, print_stats: bool = True) -> SimulationHistory:
-        assert self.value_function is not None, "No value function, training probably has to be run..."
-        self.model = self.model.gpu_model if self.value_function.is_on_gpu else self.model.cpu_model
+        self.model = self.model.gpu_model if self._on_gpu() else self.model.cpu_model
         simulator = Simulation(self.model) if simulator is None else simulator
         s = simulator.initialize_simulation(start_state=start_state)
         belief = Belief(self.model) if initial_belief is None else initial_belief
@@ -1442,9 +1565,8 @@ class Agent:
         the HIP engine (``pbvi_rollout``) when the value function is on the GPU, on the host otherwise, and the
         trajectories do not depend on which, up to exact ties between actions.  Only the start states, when none are
         given, still come from NumPy's stream."""
+        on_gpu = self._on_gpu()
         vf = self.value_function
-        assert vf is not None, "No value function, training probably has to be run..."
-        on_gpu = vf.is_on_gpu
         model = self.model.gpu_model if on_gpu else self.model.cpu_model
         assert (not isinstance(start_states, list)) or (len(start_states) == n), 'The size of the list of start states has to match n'
         assert (not isinstance(initial_beliefs, list)) or (len(initial_beliefs) == n), 'The size of the list of initial beliefs has to match n'
@@ -1475,7 +1597,7 @@ class Agent:
 
         t0 = datetime.now()
         for i in range(max_steps):
-            best_actions = block.best_actions(self.gamma) if self.lookahead == 1 else vf.actions[block.best_vectors()]
+            best_actions = self._block_actions(block)
             rewards, observations = simulator_set.run_actions(best_actions)
             finished = simulator_set.is_done
             block.advance(best_actions, observations, ~finished)
@@ -1518,14 +1640,10 @@ class Agent:
 
     ROLLOUT_CHUNK = 65535            # simulations per ``pbvi_rollout`` call: the engine's belief block limit
 
-    def _run_counter_rollouts(self, model: Model, simulator_set: SimulationSet, b0: np.ndarray, start_states: np.ndarray,
-                              seed: int, max_steps: int, reward_discount: float, print_stats: bool):
-        """``run_n_simulations_parallel(device_rng_seed=seed)``: the trajectories from ``pbvi_rollout`` (value function on
-        the GPU; more than ``ROLLOUT_CHUNK`` simulations in chunks with ``first_sim_id`` advanced) or ``rollout_numpy``,
-        the rewards from the recorded ``(s, a, s', o)`` afterwards, the result in ``run_n_simulations_parallel``'s form."""
+    def _counter_trajectories(self, model: Model, b0: np.ndarray, start_states: np.ndarray, seed: int, T: int):
+        """``(states, actions, observations, steps)`` of the counter-based rollout of this agent's policy."""
         vf = self.value_function
-        n, T = b0.shape[0], int(max_steps)
-        t0 = datetime.now()
+        n = b0.shape[0]
         if vf.is_on_gpu:
             eng = model.engine
             eng.sync_rows('alpha', vf.alpha_vector_list, lambda v: v.values)
@@ -1541,6 +1659,16 @@ class Agent:
         else:
             states, actions, observations, steps = rollout_numpy(model, vf.alpha_vector_array, vf.actions, b0, start_states,
                                                                  seed, 0, T, self.lookahead, self.gamma)
+        return states, actions, observations, steps
+
+    def _run_counter_rollouts(self, model: Model, simulator_set: SimulationSet, b0: np.ndarray, start_states: np.ndarray,
+                              seed: int, max_steps: int, reward_discount: float, print_stats: bool):
+        """``run_n_simulations_parallel(device_rng_seed=seed)``: the trajectories from ``pbvi_rollout`` (value function on
+        the GPU; more than ``ROLLOUT_CHUNK`` simulations in chunks with ``first_sim_id`` advanced) or ``rollout_numpy``,
+        the rewards from the recorded ``(s, a, s', o)`` afterwards, the result in ``run_n_simulations_parallel``'s form."""
+        n, T = b0.shape[0], int(max_steps)
+        t0 = datetime.now()
+        states, actions, observations, steps = self._counter_trajectories(model, b0, start_states, seed, T)
         ran = actions >= 0                                       # [T, n] steps that were taken
         rewards_history = np.zeros((T, n))
         if ran.any():
@@ -1565,6 +1693,52 @@ class Agent:
             print(f'\t- Average total rewards: {np.sum(rewards_history) / n}')
             print(f'\t- Average discounted rewards (ADR): {np.sum(discounted_history) / n}')
         return RewardSet(np.sum(rewards_history, axis=0).tolist()), histories
+
+
+class Infotaxis_Agent(Agent):
+    """Infotaxis: the greedy policy that takes the action with the smallest expected entropy of the next belief,
+    ``argmin_a sum_o P(o|b,a) H(update(b,a,o))`` (``infotaxis_numpy``) -- the baseline a solved olfactory-search policy is
+    judged against.  It takes no value function; a model on the GPU (``model.to_gpu()``) has the HIP engine evaluate it
+    (``pbvi_infotaxis``, ``pbvi_rollout_infotaxis``).  ``simulate``, ``run_n_simulations`` and
+    ``run_n_simulations_parallel(..., device_rng_seed=None)`` are ``Agent``'s with this policy."""
+
+    def __init__(self, model: Model) -> None:
+        super().__init__(model, None)
+
+    def _on_gpu(self) -> bool:
+        return bool(self.model.is_on_gpu)
+
+    def _block_actions(self, block) -> np.ndarray:
+        return block.infotaxis_actions()
+
+    def get_best_action(self, belief):
+        """The infotaxis action for one ``Belief`` (returns int) or a ``[n,S]`` array."""
+        single = isinstance(belief, Belief)
+        arr = belief.values[None, :] if single else belief
+        if self.model.is_on_gpu:
+            eng = self.model.engine
+            parts = []
+            for i0 in range(0, arr.shape[0], _DeviceBeliefBlock.CHUNK):      # the engine takes 65535 beliefs at a time
+                eng.set_beliefs(arr[i0:i0 + _DeviceBeliefBlock.CHUNK])
+                parts.append(eng.infotaxis_resident()[1])
+            acts = parts[0] if len(parts) == 1 else np.concatenate(parts)
+        else:
+            acts = infotaxis_numpy(self.model, arr)[1]
+        return int(acts[0]) if single else acts
+
+    def _counter_trajectories(self, model: Model, b0: np.ndarray, start_states: np.ndarray, seed: int, T: int):
+        n = b0.shape[0]
+        if not model.is_on_gpu:
+            return rollout_infotaxis_numpy(model, b0, start_states, seed, 0, T)
+        eng = model.engine
+        end_mask = np.zeros(model.state_count, dtype=np.uint8)
+        end_mask[np.asarray(model.end_states, dtype=np.int64)] = 1
+        parts = []
+        for i0 in range(0, n, self.ROLLOUT_CHUNK):
+            eng.set_beliefs(b0[i0:i0 + self.ROLLOUT_CHUNK])
+            parts.append(eng.rollout_infotaxis(start_states[i0:i0 + self.ROLLOUT_CHUNK], end_mask, seed, T, first_sim_id=i0))
+        states, actions, observations = (np.concatenate([p[k] for p in parts], axis=1) for k in range(3))
+        return states, actions, observations, np.concatenate([p[3] for p in parts])
 
 
 # --------------------------------------------------------------------------- #
