@@ -623,6 +623,10 @@ int pbvi_debug_poison(int enable);
  */
 int64_t pbvi_debug_alloc_limit(int64_t mb);
 int pbvi_engine_after_oom(pbvi_engine_t* e);
+/* Debug aid for tests of the engines' memory bookkeeping: the bytes of device buffers the library holds right now, over
+ * all engines of the process (allocated minus freed).  With one engine alive it equals that engine's pbvi_device_bytes;
+ * with none it is 0. */
+int64_t pbvi_debug_live_bytes(void);
 
 /* Benchmark / debug: list every K tile of every GEMM tile pair, zero or not -- the "dense backup" configuration of
  * BASELINE.json is measured this way (results are unchanged: skipped tiles only ever add +0).  Also enabled by

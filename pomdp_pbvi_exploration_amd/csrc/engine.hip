@@ -10,7 +10,9 @@
 //   scores  : [split_k][B_pad][N_pad] f32 partial slabs  (f64 engines: [B][N])
 //   results : out_alpha [B][S], action [B], best_v [B][A][O], keep [B]
 #include <algorithm>
+#include <atomic>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -127,9 +129,35 @@ private:
 };
 static void host_copy(void* dst, const void* src, size_t bytes) { CopyPool::get().copy(dst, src, bytes); }
 
-struct DevBuf {
+// What one owner -- an engine, or a call with device buffers of its own -- holds on the device: the bytes (what the cap of
+// pbvi_debug_alloc_limit is applied to) and the owning buffers, which enter the list when they are constructed.
+struct DevBuf;
+struct DevMem {
+    int64_t bytes = 0;
+    std::vector<DevBuf*> bufs;
+    static inline std::atomic<int64_t> live{0};             // the same over the whole process (pbvi_debug_live_bytes)
+};
+
+// Memory that somebody else owns: a pointer and the bytes behind it, nothing to allocate, release or count.
+struct DevView {
     void* p = nullptr;
     size_t cap = 0;
+    template <typename U>
+    U* as() const { return reinterpret_cast<U*>(p); }
+};
+
+// An owning device buffer, bound for life to the DevMem it is counted in.  Its lifetime class says what an engine's
+// after_oom() does with it: MODEL buffers (the model tables and what is derived from them alone) stay, WORKING buffers are
+// released.  A SCOPED buffer is a temporary outside the list; like every DevBuf it releases itself when it goes out of scope.
+struct DevBuf : DevView {
+    enum Life { MODEL, WORKING, SCOPED };
+    DevMem& mem;
+    const Life life;
+    DevBuf(DevMem& m, Life l = WORKING) : mem(m), life(l) {
+        if (l != SCOPED) m.bufs.push_back(this);
+    }
+    DevBuf(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
     // Deterministic out-of-memory for tests of the MemoryError contract (src/pomdp.py:2399-2401): an engine may hold at
     // most this many bytes of device buffers (pbvi_debug_alloc_limit / PBVI_ALLOC_LIMIT_MB; < 0 = no cap).
     static int64_t& limit_bytes() {
@@ -153,33 +181,23 @@ struct DevBuf {
     // grow-only; contents are NOT preserved on growth.  A buffer that grows again doubles (25 % if that fails): in a solve
     // loop the alpha set gains a few rows per backup, and re-allocating a multi-GB buffer (hipFree + hipMalloc,
     // both synchronising, hundreds of ms at 20 GB) on every call would dwarf the backup itself.
-    int ensure(size_t bytes, int64_t* total) {
+    int ensure(size_t bytes) {
         if (bytes <= cap) return PBVI_OK;
         const bool regrow = p != nullptr;
-        if (p) {
-            (void)hipFree(p);
-            *total -= (int64_t)cap;
-            p = nullptr;
-            cap = 0;
-        }
+        release();
         if (regrow) {
             for (const size_t want : {bytes * 2, bytes + bytes / 4}) {     // HBM is plentiful; re-allocations are not
-                if (!headroom_ok(*total, want)) continue;
+                if (!headroom_ok(mem.bytes, want)) continue;
                 if (hipMalloc(&p, want) == hipSuccess) {
-                    cap = want;
-                    *total += (int64_t)want;
-                    if (poison_enabled()) {
-                        if (hipMemset(p, 0xFF, want) != hipSuccess) (void)hipGetLastError();
-                        (void)hipDeviceSynchronize();
-                    }
+                    adopt(want);
                     return PBVI_OK;
                 }
                 (void)hipGetLastError();                 // no room for that much headroom: try less, then the exact size
                 p = nullptr;
             }
         }
-        if (over_limit(*total, bytes)) {
-            set_error("device allocation of " + std::to_string(bytes) + " bytes refused: the engine holds " + std::to_string(*total) +
+        if (over_limit(mem.bytes, bytes)) {
+            set_error("device allocation of " + std::to_string(bytes) + " bytes refused: the engine holds " + std::to_string(mem.bytes) +
                       " bytes and its cap is " + std::to_string(limit_bytes()) + " (pbvi_debug_alloc_limit)");
             return PBVI_ENOMEM;
         }
@@ -190,23 +208,119 @@ struct DevBuf {
             set_error("hipMalloc of " + std::to_string(bytes) + " bytes failed: " + hipGetErrorString(e));
             return PBVI_ENOMEM;
         }
+        adopt(bytes);
+        return PBVI_OK;
+    }
+    void release() {
+        if (p && !windowed) {
+            (void)hipFree(p);
+            mem.bytes -= (int64_t)cap;
+            DevMem::live -= (int64_t)cap;
+        }
+        p = nullptr;
+        cap = 0;
+    }
+    // this buffer := the allocation of `o`, which is left empty (both are counted in the same DevMem)
+    void take(DevBuf& o) {
+        release();
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+    }
+
+    // While a Window lives, its buffer stands for memory inside another buffer (value_max_store runs the pipeline of the
+    // resident block on windows of the belief store): ensure() finds it large enough whatever is asked, release() leaves
+    // the memory alone, and the buffer's own allocation is back when the Window goes out of scope.
+    class Window {
+        DevBuf& b_;
+        const DevView own_;
+       public:
+        explicit Window(DevBuf& b) : b_(b), own_(b) {}
+        void point(void* q) { b_.stand_for({q, ~(size_t)0 >> 1}, true); }
+        ~Window() { b_.stand_for(own_, false); }
+    };
+
+   private:
+    bool windowed = false;
+    void stand_for(const DevView& v, bool w) {
+        p = v.p;
+        cap = v.cap;
+        windowed = w;
+    }
+    // the fresh allocation at p is this buffer's
+    void adopt(size_t bytes) {
         cap = bytes;
-        *total += (int64_t)bytes;
+        mem.bytes += (int64_t)bytes;
+        DevMem::live += (int64_t)bytes;
         // Debug: fill fresh allocations with 0xFF (NaN floats, -1 ints) so any read of memory the engine did
         // not write shows up in the parity tests instead of hiding behind zero-filled fresh pages.
         if (poison_enabled()) {   // null-stream memset does not order against the engine's non-blocking streams: fence it
             if (hipMemset(p, 0xFF, bytes) != hipSuccess) (void)hipGetLastError();
             (void)hipDeviceSynchronize();
         }
-        return PBVI_OK;
     }
-    void release() {
-        if (p) (void)hipFree(p);
+};
+
+// A page-locked host buffer that enters its owner's list when it is constructed (the owner frees the list's buffers in its
+// teardown, naming `what` if that fails).
+struct PinnedBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    const char* const what;
+    PinnedBuf(std::vector<PinnedBuf*>& owner, const char* w) : what(w) { owner.push_back(this); }
+    PinnedBuf(const PinnedBuf&) = delete;
+    // At least `bytes`.  A buffer that is too small is freed and allocated again with `want` >= bytes bytes: the contents are
+    // lost, and the caller has made sure that no copy into or out of it is pending.  false: no memory (the buffer is empty).
+    bool ensure(size_t bytes, size_t want) {
+        if (bytes <= cap) return true;
+        (void)release();
+        if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            p = nullptr;
+            return false;
+        }
+        cap = want;
+        return true;
+    }
+    hipError_t release() {
+        const hipError_t e = p ? hipHostFree(p) : hipSuccess;
         p = nullptr;
         cap = 0;
+        return e;
     }
     template <typename U>
     U* as() const { return reinterpret_cast<U*>(p); }
+};
+
+// The engine's page-locked words, written by copies and by k_publish and read by the host once the stream is idle: flags
+// and counts that come back with a call's results (a stack variable would be written by the copy after an early error
+// return had released it).  One word per use, so that calls that nest (the rollout's step loop runs backups) cannot meet.
+struct PinnedWords {
+    int bad_key;              // assemble_keys / assemble_rows_store: keys out of range
+    int screen_overflow;      // fp64 engines: the screen's fp32 alpha copy holds an overflowed value (scr_flag_)
+    int unused2[2];
+    int early[3];             // run_fetch, e_cnt_: provisional keys, rows appended behind them, 1 = the slots overflowed
+    int unused7;
+    int provisional;          // run_fetch: the provisional row count, read in the middle of the pipeline
+    int unused9;
+    int survivors;            // rollout: the simulations that go on after the step
+    int unused11[5];
+    int counters[8];          // copy of counters_ (Counter)
+    int deferred[2];          // what the refinement's per-entry pass deferred to the grid-wide passes
+    int unused26[6];
+};
+static_assert(sizeof(PinnedWords) == 128 && offsetof(PinnedWords, screen_overflow) == 4 && offsetof(PinnedWords, early) == 16 &&
+                  offsetof(PinnedWords, counters) == 64,
+              "PinnedWords: the size, or one of the words k_publish writes, has changed");
+
+// the slots of an engine's device counters (counters_, zeroed at the start of every backup)
+enum Counter {
+    CNT_QUEUE = 0,            // near-tie queue of the first-max (qcount)
+    CNT_ACTION_QUEUE = 1,     // near-tie queue of the action stage (aqcount)
+    CNT_VALUE_MAX_QUEUE = 2,  // value_max's near-tie queue
+    CNT_UNIQUE = 3,           // distinct (a*, v*) keys (ucount)
+    CNT_REFINE_CAND = 4,      // candidates the refinement looked at
+    CNT_DEAD = 5,             // dead triples
+    CNT_SLOTS = 8,
 };
 
 // out[s] = max_v |alpha[v][s]| (out zeroed by the caller).  Row chunks of 128 run as separate blocks and meet in an
@@ -573,16 +687,16 @@ __global__ void k_unpermute(int B, int AO, const int32_t* __restrict__ perm, con
 __global__ void k_publish(int B, const int32_t* __restrict__ slot, const int32_t* __restrict__ index, const int32_t* __restrict__ action,
                           int32_t* __restrict__ h_slot, int32_t* __restrict__ h_index, int32_t* __restrict__ h_action,
                           const int* __restrict__ counters /* 8 */, const int* __restrict__ e_cnt /* 3 */,
-                          const int* __restrict__ scr_flag /* or nullptr */, int* __restrict__ h_flag) {
+                          const int* __restrict__ scr_flag /* or nullptr */, PinnedWords* __restrict__ words) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < B) {
         h_slot[i] = slot[i];
         h_index[i] = index[i];
         h_action[i] = action[i];
     }
-    if (blockIdx.x == 0 && threadIdx.x < 8) h_flag[16 + threadIdx.x] = counters[threadIdx.x];
-    if (blockIdx.x == 0 && threadIdx.x >= 8 && threadIdx.x < 11) h_flag[4 + threadIdx.x - 8] = e_cnt[threadIdx.x - 8];
-    if (blockIdx.x == 0 && threadIdx.x == 11 && scr_flag != nullptr) h_flag[1] = scr_flag[0];
+    if (blockIdx.x == 0 && threadIdx.x < 8) words->counters[threadIdx.x] = counters[threadIdx.x];
+    if (blockIdx.x == 0 && threadIdx.x >= 8 && threadIdx.x < 11) words->early[threadIdx.x - 8] = e_cnt[threadIdx.x - 8];
+    if (blockIdx.x == 0 && threadIdx.x == 11 && scr_flag != nullptr) words->screen_overflow = scr_flag[0];
 }
 
 // One block per distinct key u of the FINAL result: is it among the provisional keys (whose rows are on their way to the
@@ -796,10 +910,21 @@ class EngineT : public EngineBase {
     int device_ = 0;
     hipStream_t stream_ = nullptr;
     int S_ = 0, A_ = 0, O_ = 0, R_ = 0, S_pad_ = 0, mode_ = 0;
-    int64_t bytes_ = 0;
+    // What the engine owns, in front of every member that enters one of these lists when it is constructed: device
+    // buffers (with the bytes they hold), page-locked host buffers, events.  The destructor walks all three.
+    DevMem mem_;
+    std::vector<PinnedBuf*> pinned_;
+    std::vector<std::pair<hipEvent_t, const char*>> events_;
+    // *e := a new event that the engine destroys in its teardown (nothing to do if *e exists already)
+    hipError_t new_event(hipEvent_t* e, unsigned flags, const char* what) {
+        if (*e) return hipSuccess;
+        const hipError_t err = hipEventCreateWithFlags(e, flags);
+        if (err == hipSuccess) events_.push_back({*e, what});
+        return err;
+    }
     // bytes this engine may still allocate: what its cap leaves, or what the device reports free
     int64_t room() const {
-        if (DevBuf::limit_bytes() >= 0) return DevBuf::limit_bytes() - bytes_;
+        if (DevBuf::limit_bytes() >= 0) return DevBuf::limit_bytes() - mem_.bytes;
         size_t fr = 0, tot = 0;
         if (hipMemGetInfo(&fr, &tot) != hipSuccess) {
             (void)hipGetLastError();
@@ -809,8 +934,8 @@ class EngineT : public EngineBase {
     }
     double tie_rel_user_ = -1.0;
 
-    DevBuf rs_, rto_, er_, sup_;
-    // The working alpha set.  alpha_ is a VIEW (never allocated or released itself) of V_ data rows, the magnitude row and
+    DevBuf rs_{mem_, DevBuf::MODEL}, rto_{mem_, DevBuf::MODEL}, er_{mem_, DevBuf::MODEL}, sup_{mem_, DevBuf::MODEL};
+    // The working alpha set.  alpha_ is a VIEW of V_ data rows, the magnitude row and
     // zero rows up to the next multiple of 256 + 256, inside one of two allocations:
     //   alpha_buf_   -- the set as uploaded (alpha_set / alpha_append: view at row 0), or the PRIMARY set selected from the
     //                   alpha store, laid out with free rows in FRONT of it: the solve loop's next set is its new rows followed
@@ -821,7 +946,8 @@ class EngineT : public EngineBase {
     //                   copy for the screen of an fp64 engine another 0.09 s.)
     //   alpha_small_ -- a selection much smaller than the primary set (compute_change scores the rows an expansion added):
     //                   gathered here so that the primary set is still there for the next backup.
-    DevBuf alpha_, alpha_buf_, alpha_small_;
+    DevView alpha_;
+    DevBuf alpha_buf_{mem_}, alpha_small_{mem_};
     std::vector<int32_t> prim_ids_;                          // store ids of the primary set, view order
     int64_t prim_off_ = 0;                                   // first data row of the primary set inside alpha_buf_
     bool prim_valid_ = false, alpha_on_primary_ = false;
@@ -829,55 +955,54 @@ class EngineT : public EngineBase {
     uint64_t screen_layout_seen_ = 0;                        // fp64 engines: layout / first row the screen's copy reflects
     int64_t screen_off_seen_ = 0;
     int64_t V_ = 0;
-    DevBuf bel_;
+    DevBuf bel_{mem_};
     int64_t B_ = 0, B_pad_ = 0;
-    DevBuf belsp_;                                           // fp32: bel_'s split plane for the split score GEMM (split_bf16.h)
+    DevBuf belsp_{mem_};   // fp32: bel_'s split plane for the split score GEMM (split_bf16.h)
     uint64_t belsp_ver_ = 0;                                 // the bel_ version belsp_ holds (0: none)
-    DevBuf gam_, slabs_, best_v_, best_score_, err_, dead_, queue_, counters_, rdot_, action_, aqueue_, out_, keep_;
-    DevBuf bv2_, bs2_, err2_, queue2_, prune_cnt_;
+    DevBuf gam_{mem_}, slabs_{mem_}, best_v_{mem_}, best_score_{mem_}, err_{mem_}, dead_{mem_}, queue_{mem_}, counters_{mem_, DevBuf::MODEL}, rdot_{mem_}, action_{mem_}, aqueue_{mem_}, out_{mem_}, keep_{mem_};
+    DevBuf bv2_{mem_}, bs2_{mem_}, err2_{mem_}, queue2_{mem_}, prune_cnt_{mem_};
     // Gamma tiled over the alpha set (pbvi_set_gamma_tiling): 0 never, 1 when Gamma does not fit, 2 always; rows per chunk
     // (0 = planned); the full-width score matrix the chunks are folded into; the widest stream-K share size of the chunks'
     // GEMMs; events around each chunk's projection / GEMM / fold (statistics)
     int tiling_mode_ = 0;
     int64_t tiling_rows_ = 0;
-    DevBuf scores_, chain_max_;
+    DevBuf scores_{mem_}, chain_max_{mem_, DevBuf::MODEL};
     std::vector<hipEvent_t> tile_ev_;
     int tile_ev_chunks_ = 0;
-    DevBuf stage_, keys_, perm_, action_res_, best_res_;   // belief reordering (f32, B > 256)
-    DevBuf rep_, uniq_, inv_, slot_, out_full_;            // K6 key dedup: out_ holds the unique rows
-    DevBuf store_[2], ids_;                                // device row stores: [0] alpha-vectors, [1] beliefs
+    DevBuf stage_{mem_}, keys_{mem_}, perm_{mem_}, action_res_{mem_}, best_res_{mem_};   // belief reordering (f32, B > 256)
+    DevBuf rep_{mem_}, uniq_{mem_}, inv_{mem_}, slot_{mem_}, out_full_{mem_};   // K6 key dedup: out_ holds the unique rows
+    DevBuf store_[2]{{mem_}, {mem_}}, ids_{mem_};   // device row stores: [0] alpha-vectors, [1] beliefs
     int64_t store_rows_[2] = {0, 0};
-    DevBuf in_ptr_, in_src_, bu_act_, bu_obs_, bu_row_, bu_unnorm_, bu_mass_, bu_out_, walk64_, rto64_;   // batched belief update
+    DevBuf in_ptr_{mem_, DevBuf::MODEL}, in_src_{mem_, DevBuf::MODEL}, bu_act_{mem_}, bu_obs_{mem_}, bu_row_{mem_}, bu_unnorm_{mem_}, bu_mass_{mem_}, bu_out_{mem_}, walk64_{mem_}, rto64_{mem_, DevBuf::MODEL};   // batched belief update
     std::vector<int32_t> h_rs_;                                // host copy of rs [A][R][S_pad] for the lazy CSC build
-    DevBuf btl_, btc_, val_exact_;                         // per-belief non-zero tile lists; exact action values
-    DevBuf bp_, nzP_, pmag_, prd_;                          // belief-side formulation: projected beliefs, tile map, magnitudes, b.ER
+    DevBuf btl_{mem_}, btc_{mem_}, val_exact_{mem_};   // per-belief non-zero tile lists; exact action values
+    DevBuf bp_{mem_}, nzP_{mem_}, pmag_{mem_}, prd_{mem_};   // belief-side formulation: projected beliefs, tile map, magnitudes, b.ER
     bool btl_valid_ = false;                                // btl_/btc_ describe the resident belief block
     bool vmax_exact_ = true;                                // f32 engines: re-score value_max's maxima in fp64
     // belief store as a GEMM operand in place (value_max_store): zero maps and tile lists kept per store row, extended
     // as rows are appended
-    DevBuf snz_, sbtl_, sbtc_;
+    DevBuf snz_{mem_}, sbtl_{mem_}, sbtc_{mem_};
     int64_t snz_rows_ = 0, sbt_rows_ = 0;
     int64_t walk_rows_ = 0;
-    DevBuf vmax_bk_;                                        // max_v b.alpha_v of the last backup's beliefs (belief-side GEMM's extra rows)
+    DevBuf vmax_bk_{mem_};   // max_v b.alpha_v of the last backup's beliefs (belief-side GEMM's extra rows)
     bool have_bk_vmax_ = false;
     hipEvent_t walk_ev_[8] = {};                            // belief_walk: chain -> copy -> host hand-offs, per quarter                                 // rows the last belief_walk left in walk64_
-    void* host_stage_ = nullptr;                            // pinned bounce buffer for rows going to pageable host memory
-    size_t host_stage_cap_ = 0;
-    DevBuf keys_tmp_, keys_act_, keys_best_, keys_rows_;    // unique-row keys out / rows from keys in (multi-GPU exchange)
-    DevBuf acand_;                                           // [B][A] action inside the window (k_action_select -> k_refine_action)
-    DevBuf q_, q_res_, q_act_;                               // pbvi_q_values: q [B][A] in engine order / caller order, its argmax [B]
+    PinnedBuf host_stage_{pinned_, "hipHostFree(stage)"};   // bounce buffer for rows going to pageable host memory
+    DevBuf keys_tmp_{mem_}, keys_act_{mem_}, keys_best_{mem_}, keys_rows_{mem_};   // unique-row keys out / rows from keys in (multi-GPU exchange)
+    DevBuf acand_{mem_};   // [B][A] action inside the window (k_action_select -> k_refine_action)
+    DevBuf q_{mem_}, q_res_{mem_}, q_act_{mem_};   // pbvi_q_values: q [B][A] in engine order / caller order, its argmax [B]
     bool q_only_ = false, q_want_best_ = false;              // run_pipeline stops behind the refinement and runs launch_q_exact
     // pbvi_rollout: trajectories [T+1][n] states | [T][n] actions | [T][n] observations | [n] steps; the live simulations'
     // true states and trajectory rows (caller order, double-buffered across the done-filter), keep flags, the filter's
     // row map (+ 1 int: the survivor count), alpha_actions [V], end mask [S]
-    DevBuf ro_traj_, ro_state_[2], ro_orig_[2], ro_keep_, ro_dst_, ro_aact_, ro_end_;
+    DevBuf ro_traj_{mem_}, ro_state_[2]{{mem_}, {mem_}}, ro_orig_[2]{{mem_}, {mem_}}, ro_keep_{mem_}, ro_dst_{mem_}, ro_aact_{mem_}, ro_end_{mem_};
     int64_t zero_row_ = -1;                                  // first s * A + a whose RTO[s, a, :, :] sums to 0 (-1: none)
     // pbvi_infotaxis: the x-blocks' (Z, N) partials [XB][B][A][O][2]; G [B][A], its first argmin [B], P(o | b, a) [B][A][O]
     // and the beliefs' own entropies [B], all four in the caller's belief order
-    DevBuf it_part_, it_g_, it_act_, it_pobs_, it_h_;
-    DevBuf bu_mpart_;                                        // advance_resident(fixed_order): the push blocks' partial masses [B][ceil(S/256)]
-    DevBuf rf_q2_, rf_q2p_, rf_q2d_;                         // k_refine_split: entries / candidates, partial scores, arrival counters
-    DevBuf rf_v_, rf_slot_, rf_sc_, rf_entry_, rf_n_, rf_tiles_, rf_ibv_, rf_ibi_, rf_cnt_, rf_W_, rf_Cx_, rf_nzW_, rf_klW_, rf_kcW_;   // refinement work list
+    DevBuf it_part_{mem_}, it_g_{mem_}, it_act_{mem_}, it_pobs_{mem_}, it_h_{mem_};
+    DevBuf bu_mpart_{mem_};   // advance_resident(fixed_order): the push blocks' partial masses [B][ceil(S/256)]
+    DevBuf rf_q2_{mem_}, rf_q2p_{mem_}, rf_q2d_{mem_};   // k_refine_split: entries / candidates, partial scores, arrival counters
+    DevBuf rf_v_{mem_}, rf_slot_{mem_}, rf_sc_{mem_}, rf_entry_{mem_}, rf_n_{mem_}, rf_tiles_{mem_}, rf_ibv_{mem_}, rf_ibi_{mem_}, rf_cnt_{mem_}, rf_W_{mem_}, rf_Cx_{mem_}, rf_nzW_{mem_}, rf_klW_{mem_}, rf_kcW_{mem_};   // refinement work list
     int formulation_ = 0;                                   // 0 auto, 1 project alpha-vectors, 2 project beliefs
     int last_formulation_ = 1;
     int64_t f64_pairs_ = 0;                                 // tile pairs of the last fp64 MFMA GEMM (0: plain kernel)
@@ -890,13 +1015,12 @@ class EngineT : public EngineBase {
     bool sorted_ = false;
     const void* gam_pad_ptr_ = nullptr;                      // Gamma buffer / row count whose pad rows are zero
     int64_t gam_pad_N_ = -1;
-    DevBuf scr_flag_;                                        // fp64 engines: 1 = the screen's fp32 alpha copy holds an overflowed value
-    DevBuf rowflags_;                                        // [B][k_tiles] 1 = caller's belief row b has mass in K tile kt
+    DevBuf scr_flag_{mem_, DevBuf::MODEL};   // fp64 engines: 1 = the screen's fp32 alpha copy holds an overflowed value
+    DevBuf rowflags_{mem_};   // [B][k_tiles] 1 = caller's belief row b has mass in K tile kt
     uint64_t rowflags_ver_ = 0;                              // belief-block version rowflags_ describes
     uint64_t nzA_ver_ = 0;                                   // belief-block version ev_nzA_ was recorded for
-    void* ids_pin_ = nullptr;                                // pinned staging of the ids of a store selection
-    size_t ids_pin_cap_ = 0;
-    int* h_flag_ = nullptr;                                  // pinned: see pinned_flag()
+    PinnedBuf ids_pin_{pinned_, "hipHostFree(ids)"};         // staging of the ids of a store selection
+    PinnedBuf words_{pinned_, "hipHostFree(flag)"};          // one PinnedWords, allocated by init(): see words()
     // early rows (run_fetch): destination of the current call, buffers of the provisional decision pipeline
     void* early_rows_ = nullptr;
     int64_t early_cap_ = 0;
@@ -906,17 +1030,16 @@ class EngineT : public EngineBase {
         uint8_t* keep = nullptr;                                                         // synchronisation
         bool queued = false;
     } rf_dst_;
-    DevBuf e_bv_, e_bs_, e_err_, e_rdot_, e_act_, e_ares_, e_bres_, e_rep_, e_uniq_, e_inv_, e_slotd_, e_cnt_, e_out_, e_slot_;
+    DevBuf e_bv_{mem_}, e_bs_{mem_}, e_err_{mem_}, e_rdot_{mem_}, e_act_{mem_}, e_ares_{mem_}, e_bres_{mem_}, e_rep_{mem_}, e_uniq_{mem_}, e_inv_{mem_}, e_slotd_{mem_}, e_cnt_{mem_, DevBuf::MODEL}, e_out_{mem_}, e_slot_{mem_};
     hipEvent_t ev_early_[2] = {nullptr, nullptr};
     hipEvent_t ev_ids_ = nullptr;
     hipEvent_t ev_nzA_ = nullptr;                            // the resident block's zero map (nzA_) is complete
-    DevBuf nzBw_;                                            // [A*O][ceil(k_tiles/64)] support tiles of RTO as bit words
-    DevBuf nzB_, nzA_, klist_, kcount_, nchunks_, need_, skws_;   // zero-tile bookkeeping of the f32 score GEMM
-    DevBuf dense_, nzD_, nzAlpha_, prod_, klistD_, kcountD_, nchunksD_;   // dense projection mode
+    DevBuf nzBw_{mem_, DevBuf::MODEL};   // [A*O][ceil(k_tiles/64)] support tiles of RTO as bit words
+    DevBuf nzB_{mem_, DevBuf::MODEL}, nzA_{mem_}, klist_{mem_}, kcount_{mem_}, nchunks_{mem_}, need_{mem_}, skws_{mem_};   // zero-tile bookkeeping of the f32 score GEMM
+    DevBuf dense_{mem_, DevBuf::MODEL}, nzD_{mem_, DevBuf::MODEL}, nzAlpha_{mem_}, prod_{mem_}, klistD_{mem_}, kcountD_{mem_}, nchunksD_{mem_};   // dense projection mode
     int64_t rows_pad_s_ = 0, dense_pairs_ = 0;
     std::vector<int> h_kcountD_;
-    int* kc_pin_ = nullptr;                                   // page-locked landing area of the score GEMM's list lengths (statistics)
-    size_t kc_pin_cap_ = 0;
+    PinnedBuf kc_pin_{pinned_, "hipHostFree(kcount)"};        // landing area of the score GEMM's list lengths (statistics)
     hipStream_t stream2_ = nullptr;                  // belief-only kernels run beside projection + GEMM
     hipStream_t stream3_ = nullptr;                  // the score GEMM's tile lists / stream-K plan: beside both (a few us of
                                                      // work that the GEMM waits for must not queue behind k_dead's 100 us)
@@ -932,9 +1055,9 @@ class EngineT : public EngineBase {
     int fuse_project_ = 1;                                   // fp32: Gamma tiles generated inside the score GEMM; 0 never, 1 = where it
                                                              // is faster (R = 1), 2 = also for R = 2..7 (measured slower)
     double irr_frac_ = 0.0;                                  // share of (action, K tile) with non-consecutive successors
-    DevBuf irr_;                                             // [A][k_tiles] 1 = a 4-state chunk of the K tile has non-consecutive successors
-    DevBuf mat_, vlist_;                                     // [n-tiles] 1 = projected (straddles groups / tail), 0 = generated
-    DevBuf ctile_;                                           // [n-tiles] compact tile index of a projected tile (-1: generated)
+    DevBuf irr_{mem_, DevBuf::MODEL};   // [A][k_tiles] 1 = a 4-state chunk of the K tile has non-consecutive successors
+    DevBuf mat_{mem_}, vlist_{mem_};   // [n-tiles] 1 = projected (straddles groups / tail), 0 = generated
+    DevBuf ctile_{mem_};   // [n-tiles] compact tile index of a projected tile (-1: generated)
     std::vector<int32_t> h_ctile_;
     int n_mat_ = 0;                                          // projected tiles = tiles of Gamma that exist in memory when fused
     bool gam_pad_compact_ = false;
@@ -943,7 +1066,7 @@ class EngineT : public EngineBase {
     int64_t mat_V_ = -1;
     uint64_t dead_ver_ = 0;                                  // belief-block version dead_ / btl_ / btc_ describe
     int64_t dead_pairs_ = 0, dead_count_ = 0;
-    int* rf_counts_ = nullptr;                               // h_flag_[24..25]: what the refinement's per-entry pass deferred
+    int* rf_counts_ = nullptr;                               // PinnedWords::deferred of the current backup
     bool last_deferred_nothing_ = false;                     // (the first backup of an engine reads the counts mid-pipeline)
     bool owns_streams_ = true;                               // false: a screen running on its fp64 engine's streams
     EngineT<float>* screen_ = nullptr;                       // fp64 engines: the fp32 screen (see ensure_screen)
@@ -959,41 +1082,15 @@ class EngineT : public EngineBase {
             delete screen_;
             screen_ = nullptr;
         }
-        DevBuf* all[] = {&rs_, &rto_, &er_, &sup_, &alpha_buf_, &alpha_small_, &bel_, &belsp_, &gam_, &slabs_, &best_v_, &best_score_, &err_,
-                         &dead_, &queue_, &counters_, &rdot_, &action_, &aqueue_, &out_, &keep_, &bv2_, &bs2_,
-                         &err2_, &queue2_, &prune_cnt_, &nzB_, &nzA_, &klist_, &kcount_, &nchunks_, &need_, &skws_, &stage_, &keys_, &perm_,
-                         &action_res_, &best_res_, &rep_, &uniq_, &inv_, &slot_, &out_full_, &btl_, &btc_, &val_exact_, &store_[0], &store_[1], &ids_, &in_ptr_, &in_src_, &bu_act_, &bu_obs_,
-                         &bu_unnorm_, &bu_mass_, &bu_out_, &bu_row_, &walk64_, &rto64_, &bp_, &nzP_, &pmag_, &prd_, &keys_tmp_, &keys_act_, &keys_best_, &keys_rows_, &rf_v_, &rf_slot_, &rf_sc_, &rf_entry_, &rf_n_, &rf_tiles_,
-                         &snz_, &sbtl_, &sbtc_, &vmax_bk_, &rf_ibv_, &rf_ibi_, &rf_cnt_, &rf_W_, &rf_Cx_, &rf_nzW_, &rf_klW_, &rf_kcW_,
-                         &dense_, &nzD_, &nzAlpha_, &prod_, &klistD_, &kcountD_, &nchunksD_, &mat_, &vlist_, &irr_, &rowflags_, &nzBw_, &scr_flag_, &ctile_, &acand_, &q_, &q_res_, &q_act_, &rf_q2_, &rf_q2p_, &rf_q2d_, &e_bv_, &e_bs_, &e_err_, &e_rdot_, &e_act_, &e_ares_, &e_bres_, &e_rep_, &e_uniq_, &e_inv_, &e_slotd_, &e_cnt_, &e_out_, &e_slot_, &scores_, &chain_max_, &ro_traj_, &ro_state_[0], &ro_state_[1], &ro_orig_[0], &ro_orig_[1], &ro_keep_, &ro_dst_, &ro_aact_, &ro_end_, &it_part_, &it_g_, &it_act_, &it_pobs_, &it_h_, &bu_mpart_};
         // every call is checked only to name a failure when PBVI_DEBUG is set; the thread's sticky last-error is cleared at
         // the end either way, so that a later launch check does not report a stale error of this teardown
         static const bool dbg = getenv("PBVI_DEBUG") != nullptr;
         auto chk = [&](hipError_t e, const char* what) {
             if (e != hipSuccess && dbg) fprintf(stderr, "[pbvi] engine teardown: %s: %s\n", what, hipGetErrorString(e));
         };
-        for (auto& e : walk_ev_)
-            if (e) chk(hipEventDestroy(e), "hipEventDestroy(walk)");
-        for (DevBuf* b : all) b->release();
-        for (auto& e : tile_ev_)
-            if (e) chk(hipEventDestroy(e), "hipEventDestroy(tile)");
-        if (host_stage_) chk(hipHostFree(host_stage_), "hipHostFree(stage)");
-        if (ids_pin_) chk(hipHostFree(ids_pin_), "hipHostFree(ids)");
-        if (h_flag_) chk(hipHostFree(h_flag_), "hipHostFree(flag)");
-        if (kc_pin_) chk(hipHostFree(kc_pin_), "hipHostFree(kcount)");
-        for (hipEvent_t& ev : ev_early_)
-            if (ev) chk(hipEventDestroy(ev), "hipEventDestroy(early)");
-        if (ev_ids_) chk(hipEventDestroy(ev_ids_), "hipEventDestroy(ids)");
-        if (ev_nzA_) chk(hipEventDestroy(ev_nzA_), "hipEventDestroy(nzA)");
-        for (auto& e : ev_)
-            if (e) chk(hipEventDestroy(e), "hipEventDestroy(ev)");
-        for (auto& e : ev_pg_)
-            if (e) chk(hipEventDestroy(e), "hipEventDestroy(ev_pg)");
-        if (ev_fork_) chk(hipEventDestroy(ev_fork_), "hipEventDestroy(fork)");
-        if (ev_join_) chk(hipEventDestroy(ev_join_), "hipEventDestroy(join)");
-        if (ev_lists_) chk(hipEventDestroy(ev_lists_), "hipEventDestroy(lists)");
-        for (auto& e : ev_xr_)
-            if (e) chk(hipEventDestroy(e), "hipEventDestroy(xr)");
+        for (DevBuf* b : mem_.bufs) b->release();
+        for (PinnedBuf* b : pinned_) chk(b->release(), b->what);
+        for (const auto& e : events_) chk(hipEventDestroy(e.first), e.second);
         if (owns_streams_) {
             if (stream3_) chk(hipStreamDestroy(stream3_), "hipStreamDestroy(3)");
             if (stream2_) chk(hipStreamDestroy(stream2_), "hipStreamDestroy(2)");
@@ -1067,12 +1164,13 @@ class EngineT : public EngineBase {
                 HIPCHK(hipStreamCreateWithFlags(&stream3_, hipStreamNonBlocking));
             }
         }
-        for (auto& e : ev_) HIPCHK(hipEventCreate(&e));
-        for (auto& e : ev_pg_) HIPCHK(hipEventCreate(&e));
-        HIPCHK(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&ev_lists_, hipEventDisableTiming));
-        for (auto& e : ev_xr_) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        if (!words_.ensure(sizeof(PinnedWords), sizeof(PinnedWords))) FAIL(PBVI_ENOMEM, "engine_create: pinned flag words");
+        for (auto& e : ev_) HIPCHK(new_event(&e, hipEventDefault, "hipEventDestroy(ev)"));
+        for (auto& e : ev_pg_) HIPCHK(new_event(&e, hipEventDefault, "hipEventDestroy(ev_pg)"));
+        HIPCHK(new_event(&ev_fork_, hipEventDisableTiming, "hipEventDestroy(fork)"));
+        HIPCHK(new_event(&ev_join_, hipEventDisableTiming, "hipEventDestroy(join)"));
+        HIPCHK(new_event(&ev_lists_, hipEventDisableTiming, "hipEventDestroy(lists)"));
+        for (auto& e : ev_xr_) HIPCHK(new_event(&e, hipEventDisableTiming, "hipEventDestroy(xr)"));
 
         // re-tile the reference's [S][A][R] / [S][A][O][R] / [S][A] tables to s-contiguous planes
         const size_t n_rs = (size_t)A * R * S_pad_, n_rto = (size_t)A * O * R * S_pad_, n_er = (size_t)A * S_pad_;
@@ -1146,15 +1244,15 @@ class EngineT : public EngineBase {
             }
         }
         int rc;
-        if ((rc = rs_.ensure(n_rs * sizeof(int32_t), &bytes_))) return rc;
-        if ((rc = rto_.ensure(n_rto * sizeof(T), &bytes_))) return rc;
-        if ((rc = er_.ensure(n_er * sizeof(T), &bytes_))) return rc;
-        if ((rc = sup_.ensure((size_t)A * O * S_pad_, &bytes_))) return rc;
+        if ((rc = rs_.ensure(n_rs * sizeof(int32_t)))) return rc;
+        if ((rc = rto_.ensure(n_rto * sizeof(T)))) return rc;
+        if ((rc = er_.ensure(n_er * sizeof(T)))) return rc;
+        if ((rc = sup_.ensure((size_t)A * O * S_pad_))) return rc;
         HIPCHK(hipMemcpyAsync(rs_.p, h_rs.data(), n_rs * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
         HIPCHK(hipMemcpyAsync(rto_.p, h_rto.data(), n_rto * sizeof(T), hipMemcpyHostToDevice, stream_));
         HIPCHK(hipMemcpyAsync(er_.p, h_er.data(), n_er * sizeof(T), hipMemcpyHostToDevice, stream_));
         HIPCHK(launch_support<T>(view(), sup_.as<uint8_t>(), stream_));
-        if ((rc = counters_.ensure(8 * sizeof(int), &bytes_))) return rc;
+        if ((rc = counters_.ensure(CNT_SLOTS * sizeof(int)))) return rc;
         {   // nzB[(a,o)][kt] = 1 iff RTO[:,a,o,:] has support inside K tile kt (32 states)
             const int k_tiles = S_pad_ / GEMM_BK;
             // ... plus one extra row [A*O] for the support of ER (the reward rows in Gamma's tail tile)
@@ -1166,7 +1264,7 @@ class EngineT : public EngineBase {
             for (int a = 0; a < A; ++a)
                 for (int s = 0; s < S; ++s)
                     if (h_er[(size_t)a * S_pad_ + s] != T(0)) h_nz[(size_t)A * O * k_tiles + s / GEMM_BK] = 1;
-            if ((rc = nzB_.ensure(h_nz.size(), &bytes_))) return rc;
+            if ((rc = nzB_.ensure(h_nz.size()))) return rc;
             HIPCHK(hipMemcpyAsync(nzB_.p, h_nz.data(), h_nz.size(), hipMemcpyHostToDevice, stream_));
             // the same supports as bit words (bit t of word w = K tile 64 w + t), for the dead-triple test
             const int kw = (k_tiles + 63) / 64;
@@ -1174,7 +1272,7 @@ class EngineT : public EngineBase {
             for (int ao = 0; ao < A * O; ++ao)
                 for (int kt = 0; kt < k_tiles; ++kt)
                     if (h_nz[(size_t)ao * k_tiles + kt]) h_nzw[(size_t)ao * kw + kt / 64] |= 1ull << (kt & 63);
-            if ((rc = nzBw_.ensure(h_nzw.size() * sizeof(unsigned long long), &bytes_))) return rc;
+            if ((rc = nzBw_.ensure(h_nzw.size() * sizeof(unsigned long long)))) return rc;
             HIPCHK(hipMemcpyAsync(nzBw_.p, h_nzw.data(), h_nzw.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, stream_));
             std::vector<int32_t> h_irr;
             // For the fused score GEMM (gemm.hip, schedulers 2b / 2c): K tiles that hold a 4-state chunk whose successors
@@ -1197,7 +1295,7 @@ class EngineT : public EngineBase {
                 const double max_irr = getenv("PBVI_FUSE_MAX_IRR") ? atof(getenv("PBVI_FUSE_MAX_IRR")) : 0.30;
                 irr_frac_ = (double)n_irr / (double)h_irr.size();
                 if (R == 1 || irr_frac_ <= max_irr) {
-                    if ((rc = irr_.ensure(h_irr.size() * sizeof(int32_t), &bytes_))) return rc;
+                    if ((rc = irr_.ensure(h_irr.size() * sizeof(int32_t)))) return rc;
                     HIPCHK(hipMemcpyAsync(irr_.p, h_irr.data(), h_irr.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
                 }
             }
@@ -1206,7 +1304,7 @@ class EngineT : public EngineBase {
         if (mode_ == PBVI_DENSE) {   // D[ao] = dense |S| x |S| transition-observation matrices
             rows_pad_s_ = round_up(S, GEMM_BN);
             const size_t n = (size_t)A * O * rows_pad_s_ * S_pad_;
-            if ((rc = dense_.ensure(n * sizeof(T), &bytes_))) return rc;
+            if ((rc = dense_.ensure(n * sizeof(T)))) return rc;
             HIPCHK(hipMemsetAsync(dense_.p, 0, n * sizeof(T), stream_));
             hipLaunchKernelGGL(k_densify<T>, dim3((S + 255) / 256, A * O), dim3(256), 0, stream_, view(), dense_.as<T>(),
                                rows_pad_s_);
@@ -1214,7 +1312,7 @@ class EngineT : public EngineBase {
             if (kF32) {
                 const int k_tiles = S_pad_ / GEMM_BK;
                 const size_t per = (size_t)(rows_pad_s_ / GEMM_BN) * k_tiles;
-                if ((rc = nzD_.ensure((size_t)A * O * per, &bytes_))) return rc;
+                if ((rc = nzD_.ensure((size_t)A * O * per))) return rc;
                 for (int ao = 0; ao < A * O; ++ao)
                     HIPCHK(launch_tile_nonzero_f32((const float*)dense_.p + (size_t)ao * rows_pad_s_ * S_pad_, S_pad_,
                                                    (int)rows_pad_s_, k_tiles, nzD_.as<uint8_t>() + ao * per, stream_));
@@ -1228,7 +1326,7 @@ class EngineT : public EngineBase {
     // ---- alpha set ------------------------------------------------------- //
     size_t alpha_rows_cap(int64_t V) const { return (size_t)round_up(V + 1, GEMM_BN); }
 
-    void alpha_view(const DevBuf& own, int64_t row_off) {
+    void alpha_view(const DevView& own, int64_t row_off) {
         const size_t skip = (size_t)row_off * S_pad_ * sizeof(T);
         alpha_.p = static_cast<char*>(own.p) + skip;
         alpha_.cap = own.cap - skip;
@@ -1253,7 +1351,7 @@ class EngineT : public EngineBase {
         if (V <= 0 || alpha == nullptr) FAIL(PBVI_EINVAL, "alpha_set: need V > 0 and a non-null array");
         HIPCHK(hipSetDevice(device_));
         const size_t rows = alpha_rows_cap(V);
-        int rc = alpha_buf_.ensure(rows * S_pad_ * sizeof(T), &bytes_);
+        int rc = alpha_buf_.ensure(rows * S_pad_ * sizeof(T));
         if (rc) return rc;
         alpha_view(alpha_buf_, 0);
         prim_valid_ = alpha_on_primary_ = false;
@@ -1277,16 +1375,10 @@ class EngineT : public EngineBase {
         const size_t need = alpha_rows_cap(Vn) * S_pad_ * sizeof(T);
         const bool plain = alpha_.p == alpha_buf_.p;          // the view starts the allocation (no rows kept free in front)
         if (need > alpha_.cap || !plain) {   // grow (or move to a plain layout), preserving the resident rows
-            DevBuf nb;
-            int rc = nb.ensure(std::max(need, plain ? alpha_buf_.cap * 2 : need), &bytes_);
+            // (the rows are copied from the view: it may start inside alpha_buf_ or lie in alpha_small_)
+            int rc = grow_keep(alpha_buf_, need, (size_t)V_ * S_pad_ * sizeof(T), std::max(need, plain ? alpha_buf_.cap * 2 : need),
+                               alpha_.p, true);
             if (rc) return rc;
-            HIPCHK(hipMemsetAsync(nb.p, 0, nb.cap, stream_));
-            if (V_ > 0)
-                HIPCHK(hipMemcpyAsync(nb.p, alpha_.p, (size_t)V_ * S_pad_ * sizeof(T), hipMemcpyDeviceToDevice, stream_));
-            HIPCHK(hipStreamSynchronize(stream_));
-            bytes_ -= (int64_t)alpha_buf_.cap;
-            alpha_buf_.release();
-            alpha_buf_ = nb;
             alpha_view(alpha_buf_, 0);
         } else {
             // clear the old magnitude row's pad columns / content before it becomes a data row
@@ -1312,12 +1404,12 @@ class EngineT : public EngineBase {
     int beliefs_finish(int64_t B, const T* src, const int32_t* src_ids) {
         const int64_t Bp = round_up(B, GEMM_BM);
         const int k_tiles = S_pad_ / GEMM_BK;
-        int rc = bel_.ensure((size_t)Bp * S_pad_ * sizeof(T), &bytes_);
+        int rc = bel_.ensure((size_t)Bp * S_pad_ * sizeof(T));
         if (rc) return rc;
-        if ((rc = rowflags_.ensure((size_t)B * k_tiles, &bytes_))) return rc;
-        if ((rc = keys_.ensure((size_t)B * sizeof(int32_t), &bytes_))) return rc;
-        if ((rc = perm_.ensure((size_t)B * sizeof(int32_t), &bytes_))) return rc;
-        if ((rc = nzA_.ensure((size_t)(Bp / GEMM_BM) * k_tiles, &bytes_))) return rc;
+        if ((rc = rowflags_.ensure((size_t)B * k_tiles))) return rc;
+        if ((rc = keys_.ensure((size_t)B * sizeof(int32_t)))) return rc;
+        if ((rc = perm_.ensure((size_t)B * sizeof(int32_t)))) return rc;
+        if ((rc = nzA_.ensure((size_t)(Bp / GEMM_BM) * k_tiles))) return rc;
         if (Bp > B) HIPCHK(hipMemsetAsync(bel_.as<T>() + (size_t)B * S_pad_, 0, (size_t)(Bp - B) * S_pad_ * sizeof(T), stream_));
         // the split plane rides along with the gather once score_gemm has allocated it (the first split backup)
         uint32_t* plane = nullptr;
@@ -1349,7 +1441,7 @@ class EngineT : public EngineBase {
             HIPCHK(hipGetLastError());
             r0 += cnt;
         }
-        if (!ev_nzA_) HIPCHK(hipEventCreateWithFlags(&ev_nzA_, hipEventDisableTiming));
+        HIPCHK(new_event(&ev_nzA_, hipEventDisableTiming, "hipEventDestroy(nzA)"));
         HIPCHK(hipEventRecord(ev_nzA_, stream_));
         B_ = B;
         B_pad_ = Bp;
@@ -1363,15 +1455,7 @@ class EngineT : public EngineBase {
         return PBVI_OK;
     }
 
-    // one page-locked int for flags read back with the results (a stack variable would be written by the copy after an
-    // early error return had released it)
-    int* pinned_flag() {
-        if (!h_flag_ && hipHostMalloc((void**)&h_flag_, 128, hipHostMallocDefault) != hipSuccess) {   // 32 ints: [16..23] = run_fetch's counters, [24..25] = rf_counts_
-            (void)hipGetLastError();
-            h_flag_ = nullptr;
-        }
-        return h_flag_;
-    }
+    PinnedWords& words() const { return *words_.as<PinnedWords>(); }
 
     // h_perm_[i] = caller's index of engine row i (sorted blocks), for the host-side consumers of the order
     int host_perm() {
@@ -1387,7 +1471,7 @@ class EngineT : public EngineBase {
         if (B <= 0 || bel == nullptr) FAIL(PBVI_EINVAL, "beliefs_set: need B > 0 and a non-null array");
         if (B > 65535) FAIL(PBVI_EUNSUPPORTED, "beliefs_set: at most 65535 beliefs per block");
         HIPCHK(hipSetDevice(device_));
-        int rc = stage_.ensure((size_t)B * S_pad_ * sizeof(T), &bytes_);
+        int rc = stage_.ensure((size_t)B * S_pad_ * sizeof(T));
         if (rc) return rc;
         HIPCHK(hipMemsetAsync(stage_.p, 0, (size_t)B * S_pad_ * sizeof(T), stream_));
         HIPCHK(hipMemcpy2DAsync(stage_.p, (size_t)S_pad_ * sizeof(T), bel, (size_t)S_ * sizeof(T), (size_t)S_ * sizeof(T),
@@ -1414,8 +1498,8 @@ class EngineT : public EngineBase {
                 for (int r = 0; r < R_; ++r) q[fill[h_rs_[((size_t)a * R_ + r) * S_pad_ + s]]++] = s * R_ + r;
         }
         int rc;
-        if ((rc = in_ptr_.ensure(ptr.size() * sizeof(int32_t), &bytes_))) return rc;
-        if ((rc = in_src_.ensure(src.size() * sizeof(int32_t), &bytes_))) return rc;
+        if ((rc = in_ptr_.ensure(ptr.size() * sizeof(int32_t)))) return rc;
+        if ((rc = in_src_.ensure(src.size() * sizeof(int32_t)))) return rc;
         HIPCHK(hipMemcpy(in_ptr_.p, ptr.data(), ptr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(in_src_.p, src.data(), src.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         return PBVI_OK;
@@ -1431,11 +1515,11 @@ class EngineT : public EngineBase {
         HIPCHK(hipSetDevice(device_));
         int rc = build_inverse_lists();
         if (rc) return rc;
-        if ((rc = bu_act_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
-        if ((rc = bu_obs_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
-        if ((rc = bu_unnorm_.ensure((size_t)B_ * S_ * sizeof(double), &bytes_))) return rc;
-        if ((rc = bu_mass_.ensure((size_t)B_ * sizeof(double), &bytes_))) return rc;
-        if ((rc = bu_out_.ensure((size_t)B_ * S_ * sizeof(T), &bytes_))) return rc;
+        if ((rc = bu_act_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+        if ((rc = bu_obs_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+        if ((rc = bu_unnorm_.ensure((size_t)B_ * S_ * sizeof(double)))) return rc;
+        if ((rc = bu_mass_.ensure((size_t)B_ * sizeof(double)))) return rc;
+        if ((rc = bu_out_.ensure((size_t)B_ * S_ * sizeof(T)))) return rc;
         // act/obs arrive in the caller's belief order; the resident block may be sorted
         if ((rc = host_perm())) return rc;
         std::vector<int32_t> ha((size_t)B_), ho((size_t)B_);
@@ -1487,9 +1571,9 @@ class EngineT : public EngineBase {
             have_result_ = false;
             return PBVI_OK;
         }
-        if ((rc = bu_act_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
-        if ((rc = bu_obs_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
-        if ((rc = bu_row_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
+        if ((rc = bu_act_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+        if ((rc = bu_obs_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+        if ((rc = bu_row_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
         if ((rc = host_perm())) return rc;
         std::vector<int32_t> ha((size_t)B_), ho((size_t)B_), hr((size_t)B_);
         for (int64_t i = 0; i < B_; ++i) {               // engine row i holds the caller's row c
@@ -1510,10 +1594,10 @@ class EngineT : public EngineBase {
     // fixed_order: the norm is summed in block order instead of with atomics (launch_belief_update's mass_part).
     int advance_resident(int64_t nb, bool sync_before_finish, bool fixed_order = false) {
         int rc;
-        if (fixed_order && (rc = bu_mpart_.ensure((size_t)B_ * ((S_ + 255) / 256) * sizeof(double), &bytes_))) return rc;
-        if ((rc = bu_unnorm_.ensure((size_t)B_ * S_ * sizeof(double), &bytes_))) return rc;
-        if ((rc = bu_mass_.ensure((size_t)B_ * sizeof(double), &bytes_))) return rc;
-        if ((rc = stage_.ensure((size_t)nb * S_pad_ * sizeof(T), &bytes_))) return rc;
+        if (fixed_order && (rc = bu_mpart_.ensure((size_t)B_ * ((S_ + 255) / 256) * sizeof(double)))) return rc;
+        if ((rc = bu_unnorm_.ensure((size_t)B_ * S_ * sizeof(double)))) return rc;
+        if ((rc = bu_mass_.ensure((size_t)B_ * sizeof(double)))) return rc;
+        if ((rc = stage_.ensure((size_t)nb * S_pad_ * sizeof(T)))) return rc;
         HIPCHK(hipMemsetAsync(bu_mass_.p, 0, (size_t)B_ * sizeof(double), stream_));
         HIPCHK(hipMemsetAsync(stage_.p, 0, (size_t)nb * S_pad_ * sizeof(T), stream_));   // pad columns stay zero
         HIPCHK(launch_belief_update<T>(bel_.as<T>(), S_pad_, (int)B_, view(), in_ptr_.as<int32_t>(), in_src_.as<int32_t>(),
@@ -1531,11 +1615,11 @@ class EngineT : public EngineBase {
         int rc = build_inverse_lists();
         if (rc) return rc;
         const size_t ba = (size_t)B_ * A_;
-        if ((rc = it_part_.ensure((size_t)succ_entropy_xblocks(S_) * ba * O_ * 2 * sizeof(double), &bytes_))) return rc;
-        if ((rc = it_g_.ensure(ba * sizeof(double), &bytes_))) return rc;
-        if ((rc = it_act_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
-        if (want_p_obs && (rc = it_pobs_.ensure(ba * O_ * sizeof(double), &bytes_))) return rc;
-        if (want_entropy && (rc = it_h_.ensure((size_t)B_ * sizeof(double), &bytes_))) return rc;
+        if ((rc = it_part_.ensure((size_t)succ_entropy_xblocks(S_) * ba * O_ * 2 * sizeof(double)))) return rc;
+        if ((rc = it_g_.ensure(ba * sizeof(double)))) return rc;
+        if ((rc = it_act_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+        if (want_p_obs && (rc = it_pobs_.ensure(ba * O_ * sizeof(double)))) return rc;
+        if (want_entropy && (rc = it_h_.ensure((size_t)B_ * sizeof(double)))) return rc;
         HIPCHK(launch_infotaxis<T>(bel_.as<T>(), S_pad_, (int)B_, view(), in_ptr_.as<int32_t>(), in_src_.as<int32_t>(),
                                    sorted_ ? perm_.as<int32_t>() : nullptr, it_part_.as<double>(), it_g_.as<double>(),
                                    it_act_.as<int32_t>(), want_p_obs ? it_pobs_.as<double>() : nullptr,
@@ -1587,22 +1671,20 @@ class EngineT : public EngineBase {
         HIPCHK(hipSetDevice(device_));
         int rc;
         const size_t n_st = (size_t)(n_steps + 1) * n0, n_ao = (size_t)n_steps * n0, n_traj = n_st + 2 * n_ao + (size_t)n0;
-        if ((rc = ro_traj_.ensure(n_traj * sizeof(int32_t), &bytes_))) return rc;
+        if ((rc = ro_traj_.ensure(n_traj * sizeof(int32_t)))) return rc;
         for (int k = 0; k < 2; ++k) {
-            if ((rc = ro_state_[k].ensure((size_t)n0 * sizeof(int32_t), &bytes_))) return rc;
-            if ((rc = ro_orig_[k].ensure((size_t)n0 * sizeof(int32_t), &bytes_))) return rc;
+            if ((rc = ro_state_[k].ensure((size_t)n0 * sizeof(int32_t)))) return rc;
+            if ((rc = ro_orig_[k].ensure((size_t)n0 * sizeof(int32_t)))) return rc;
         }
-        if ((rc = ro_keep_.ensure((size_t)n0, &bytes_))) return rc;
-        if ((rc = ro_dst_.ensure((size_t)(n0 + 1) * sizeof(int32_t), &bytes_))) return rc;
-        if (uses_alpha && (rc = ro_aact_.ensure((size_t)V_ * sizeof(int32_t), &bytes_))) return rc;
-        if ((rc = ro_end_.ensure((size_t)S_, &bytes_))) return rc;
-        if ((rc = bu_act_.ensure((size_t)n0 * sizeof(int32_t), &bytes_))) return rc;
-        if ((rc = bu_obs_.ensure((size_t)n0 * sizeof(int32_t), &bytes_))) return rc;
-        if ((rc = bu_row_.ensure((size_t)n0 * sizeof(int32_t), &bytes_))) return rc;
+        if ((rc = ro_keep_.ensure((size_t)n0))) return rc;
+        if ((rc = ro_dst_.ensure((size_t)(n0 + 1) * sizeof(int32_t)))) return rc;
+        if (uses_alpha && (rc = ro_aact_.ensure((size_t)V_ * sizeof(int32_t)))) return rc;
+        if ((rc = ro_end_.ensure((size_t)S_))) return rc;
+        if ((rc = bu_act_.ensure((size_t)n0 * sizeof(int32_t)))) return rc;
+        if ((rc = bu_obs_.ensure((size_t)n0 * sizeof(int32_t)))) return rc;
+        if ((rc = bu_row_.ensure((size_t)n0 * sizeof(int32_t)))) return rc;
         if ((rc = build_inverse_lists())) return rc;
-        int* h_count = pinned_flag();
-        if (!h_count) FAIL(PBVI_ENOMEM, "rollout: pinned flag");
-        h_count += 10;
+        int* h_count = &words().survivors;
         int32_t* tr_states = ro_traj_.as<int32_t>();
         int32_t* tr_actions = tr_states + n_st;
         int32_t* tr_obs = tr_actions + n_ao;
@@ -1672,10 +1754,10 @@ class EngineT : public EngineBase {
         // one transfer of the whole trajectory buffer into the pinned staging area, then host copies of the parts asked for
         if (out_states || out_actions || out_observations || out_steps) {
             if ((rc = stage_reserve(n_traj * sizeof(int32_t)))) return rc;
-            HIPCHK(hipMemcpyAsync(host_stage_, ro_traj_.p, n_traj * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+            HIPCHK(hipMemcpyAsync(host_stage_.p, ro_traj_.p, n_traj * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
             HIPCHK(hipStreamSynchronize(stream_));
             for (int k = 0; k < 4; ++k)
-                if (dsts[k]) host_copy(dsts[k], (const char*)host_stage_ + (size_t)(src[k] - tr_states) * sizeof(int32_t), len[k] * sizeof(int32_t));
+                if (dsts[k]) host_copy(dsts[k], host_stage_.as<char>() + (size_t)(src[k] - tr_states) * sizeof(int32_t), len[k] * sizeof(int32_t));
         } else {
             HIPCHK(hipStreamSynchronize(stream_));
         }
@@ -1707,22 +1789,11 @@ class EngineT : public EngineBase {
     int64_t store_append(int which, const void* rows, int64_t n) override {
         if (which < 0 || which > 1 || n < 0 || (n > 0 && rows == nullptr)) FAIL(PBVI_EINVAL, "store_append: bad arguments");
         if (hipSetDevice(device_) != hipSuccess) FAIL(PBVI_ERUNTIME, "hipSetDevice failed");
-        DevBuf& st = store_[which];
         const int64_t have = store_rows_[which];
-        const size_t need = (size_t)(have + n) * S_pad_ * sizeof(T);
-        if (need > st.cap) {   // grow geometrically, keep the stored rows
-            DevBuf nb;
-            int rc = nb.ensure(std::max(need, st.cap * 2), &bytes_);
-            if (rc) return rc;
-            if (have > 0 && hipMemcpyAsync(nb.p, st.p, (size_t)have * S_pad_ * sizeof(T), hipMemcpyDeviceToDevice, stream_) != hipSuccess)
-                FAIL(PBVI_ERUNTIME, "store_append: device copy failed");
-            if (hipStreamSynchronize(stream_) != hipSuccess) FAIL(PBVI_ERUNTIME, "store_append: sync failed");
-            bytes_ -= (int64_t)st.cap;
-            st.release();
-            st = nb;
-        }
+        T* dst = nullptr;
+        int rc = store_reserve(which, n, &dst);
+        if (rc) return rc;
         if (n > 0) {
-            T* dst = st.as<T>() + (size_t)have * S_pad_;
             if (hipMemsetAsync(dst, 0, (size_t)n * S_pad_ * sizeof(T), stream_) != hipSuccess ||
                 hipMemcpy2DAsync(dst, (size_t)S_pad_ * sizeof(T), rows, (size_t)S_ * sizeof(T), (size_t)S_ * sizeof(T),
                                  (size_t)n, hipMemcpyHostToDevice, stream_) != hipSuccess ||
@@ -1743,7 +1814,7 @@ class EngineT : public EngineBase {
         T* dst = nullptr;
         int rc = store_reserve(0, n, &dst);
         if (rc) return rc;
-        if ((rc = ids_.ensure((size_t)n * sizeof(int32_t), &bytes_))) return rc;
+        if ((rc = ids_.ensure((size_t)n * sizeof(int32_t)))) return rc;
         HIPCHK(hipMemcpyAsync(ids_.p, unique_idx, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
         if (S_pad_ > S_) HIPCHK(hipMemsetAsync(dst, 0, (size_t)n * S_pad_ * sizeof(T), stream_));   // pad columns stay zero
         hipLaunchKernelGGL(k_gather_rows_ld<T>, dim3((S_ + 255) / 256, (unsigned)n), dim3(256), 0, stream_, out_.as<T>(), S_,
@@ -1760,16 +1831,8 @@ class EngineT : public EngineBase {
         DevBuf& st = store_[which];
         const int64_t have = store_rows_[which];
         const size_t need = (size_t)(have + n) * S_pad_ * sizeof(T);
-        if (need > st.cap) {
-            DevBuf nb;
-            int rc = nb.ensure(std::max(need, st.cap * 2), &bytes_);
-            if (rc) return rc;
-            if (have > 0) HIPCHK(hipMemcpyAsync(nb.p, st.p, (size_t)have * S_pad_ * sizeof(T), hipMemcpyDeviceToDevice, stream_));
-            HIPCHK(hipStreamSynchronize(stream_));
-            bytes_ -= (int64_t)st.cap;
-            st.release();
-            st = nb;
-        }
+        int rc = grow_keep(st, need, (size_t)have * S_pad_ * sizeof(T));
+        if (rc) return rc;
         *dst = st.as<T>() + (size_t)have * S_pad_;
         return PBVI_OK;
     }
@@ -1785,7 +1848,7 @@ class EngineT : public EngineBase {
                 for (int o = 0; o < O_; ++o)
                     for (int r = 0; r < R_; ++r)
                         h[(((size_t)a * O_ + o) * R_ + r) * S_pad_ + s] = rto[(((size_t)s * A_ + a) * O_ + o) * R_ + r];
-        int rc = rto64_.ensure(h.size() * sizeof(double), &bytes_);
+        int rc = rto64_.ensure(h.size() * sizeof(double));
         if (rc) return rc;
         HIPCHK(hipMemcpy(rto64_.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
         return PBVI_OK;
@@ -1803,9 +1866,9 @@ class EngineT : public EngineBase {
         int rc = build_inverse_lists();
         if (rc) return rc;
         const int blocks = (S_pad_ + 255) / 256;
-        if ((rc = walk64_.ensure((size_t)(n + 1) * S_ * sizeof(double), &bytes_))) return rc;      // row 0 = b0
-        if ((rc = bu_unnorm_.ensure((size_t)2 * S_ * sizeof(double), &bytes_))) return rc;          // ping-pong: raw row of step i
-        if ((rc = bu_mass_.ensure((size_t)2 * blocks * sizeof(double), &bytes_))) return rc;      // and its block partials
+        if ((rc = walk64_.ensure((size_t)(n + 1) * S_ * sizeof(double)))) return rc;      // row 0 = b0
+        if ((rc = bu_unnorm_.ensure((size_t)2 * S_ * sizeof(double)))) return rc;          // ping-pong: raw row of step i
+        if ((rc = bu_mass_.ensure((size_t)2 * blocks * sizeof(double)))) return rc;      // and its block partials
         T* dst = nullptr;
         if ((rc = store_reserve(1, n, &dst))) return rc;
         double* rows = walk64_.as<double>();
@@ -1822,8 +1885,7 @@ class EngineT : public EngineBase {
         if (to_host && n >= 2 * kChunks) {
             if ((rc = out_begin())) return rc;                                   // (nothing of an earlier call is staged)
             if ((rc = stage_reserve((size_t)n * S_ * sizeof(double)))) return rc;
-            for (auto& e : walk_ev_)
-                if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            for (auto& e : walk_ev_) HIPCHK(new_event(&e, hipEventDisableTiming, "hipEventDestroy(walk)"));
             n_chunks = kChunks;
             for (int c = 0; c < kChunks; ++c) chunk_end[c] = n * (c + 1) / kChunks;
         }
@@ -1835,7 +1897,7 @@ class EngineT : public EngineBase {
             const int64_t r0 = c ? chunk_end[c - 1] : 0, r1 = chunk_end[c];
             HIPCHK(hipEventRecord(walk_ev_[2 * c], stream_));
             HIPCHK(hipStreamWaitEvent(stream2_, walk_ev_[2 * c], 0));
-            HIPCHK(hipMemcpyAsync((char*)host_stage_ + (size_t)r0 * S_ * sizeof(double), rows + (size_t)(r0 + 1) * S_,
+            HIPCHK(hipMemcpyAsync(host_stage_.as<char>() + (size_t)r0 * S_ * sizeof(double), rows + (size_t)(r0 + 1) * S_,
                                   (size_t)(r1 - r0) * S_ * sizeof(double), hipMemcpyDeviceToHost, stream2_));
             HIPCHK(hipEventRecord(walk_ev_[2 * c + 1], stream2_));
             return PBVI_OK;
@@ -1876,7 +1938,7 @@ class EngineT : public EngineBase {
             for (int c = 0; c < n_chunks; ++c) {
                 const int64_t r0 = c ? chunk_end[c - 1] : 0;
                 HIPCHK(hipEventSynchronize(walk_ev_[2 * c + 1]));
-                host_copy((char*)out + (size_t)r0 * S_ * sizeof(double), (const char*)host_stage_ + (size_t)r0 * S_ * sizeof(double),
+                host_copy((char*)out + (size_t)r0 * S_ * sizeof(double), host_stage_.as<char>() + (size_t)r0 * S_ * sizeof(double),
                             (size_t)(chunk_end[c] - r0) * S_ * sizeof(double));
             }
             HIPCHK(hipStreamSynchronize(stream_));
@@ -1908,7 +1970,7 @@ class EngineT : public EngineBase {
     int walk_keys(int64_t n, uint64_t* out_keys) override {
         if (n <= 0 || n != walk_rows_ || !out_keys) FAIL(PBVI_EINVAL, "belief_walk_keys: n must be the length of the last walk");
         HIPCHK(hipSetDevice(device_));
-        int rc = keys_tmp_.ensure((size_t)n * sizeof(uint64_t), &bytes_);
+        int rc = keys_tmp_.ensure((size_t)n * sizeof(uint64_t));
         if (rc) return rc;
         hipLaunchKernelGGL(k_row_hash<double>, dim3((unsigned)n), dim3(256), 0, stream_, walk64_.as<double>() + S_, S_, S_,
                            keys_tmp_.as<unsigned long long>());
@@ -1926,19 +1988,9 @@ class EngineT : public EngineBase {
         (void)hipStreamSynchronize(stream_);
         if (stream2_) (void)hipStreamSynchronize(stream2_);
         if (stream3_) (void)hipStreamSynchronize(stream3_);
-        DevBuf* drop[] = {&alpha_buf_, &alpha_small_, &bel_, &belsp_, &gam_, &slabs_, &best_v_, &best_score_, &err_, &dead_, &queue_, &rdot_,
-                          &action_, &aqueue_, &out_, &keep_, &bv2_, &bs2_, &err2_, &queue2_, &prune_cnt_, &nzA_, &klist_, &kcount_,
-                          &nchunks_, &need_, &skws_, &stage_, &keys_, &perm_, &action_res_, &best_res_, &rep_, &uniq_, &inv_, &slot_,
-                          &out_full_, &btl_, &btc_, &val_exact_, &store_[0], &store_[1], &ids_, &bu_act_, &bu_obs_, &bu_unnorm_,
-                          &bu_mass_, &bu_out_, &bu_row_, &walk64_, &bp_, &nzP_, &pmag_, &prd_, &keys_tmp_, &keys_act_, &keys_best_,
-                          &keys_rows_, &rf_v_, &rf_slot_, &rf_sc_, &rf_entry_, &rf_n_, &rf_tiles_, &snz_, &sbtl_, &sbtc_, &vmax_bk_,
-                          &rf_ibv_, &rf_ibi_, &rf_cnt_, &rf_W_, &rf_Cx_, &rf_nzW_, &rf_klW_, &rf_kcW_, &nzAlpha_, &prod_, &klistD_,
-                          &kcountD_, &nchunksD_, &mat_, &vlist_, &rowflags_, &ctile_, &acand_, &q_, &q_res_, &q_act_, &rf_q2_, &rf_q2p_, &rf_q2d_, &e_bv_, &e_bs_, &e_err_, &e_rdot_, &e_act_, &e_ares_, &e_bres_, &e_rep_, &e_uniq_, &e_inv_, &e_slotd_, &e_out_, &e_slot_, &scores_, &ro_traj_, &ro_state_[0], &ro_state_[1], &ro_orig_[0], &ro_orig_[1], &ro_keep_, &ro_dst_, &ro_aact_, &ro_end_, &it_part_, &it_g_, &it_act_, &it_pobs_, &it_h_, &bu_mpart_};
-        for (DevBuf* b : drop) {
-            bytes_ -= (int64_t)b->cap;
-            b->release();
-        }
-        alpha_ = DevBuf{};                                   // a view into alpha_buf_ / alpha_small_
+        for (DevBuf* b : mem_.bufs)
+            if (b->life == DevBuf::WORKING) b->release();
+        alpha_ = DevView{};                                  // (it pointed into alpha_buf_ / alpha_small_)
         V_ = 0;
         B_ = B_pad_ = 0;
         prim_valid_ = alpha_on_primary_ = false;
@@ -1982,26 +2034,19 @@ class EngineT : public EngineBase {
         for (int64_t i = 0; i < n; ++i)
             if (ids[i] < 0 || ids[i] >= store_rows_[which]) FAIL(PBVI_EINVAL, "store_select: id out of range");
         HIPCHK(hipSetDevice(device_));
-        int rc = ids_.ensure((size_t)n * sizeof(int32_t), &bytes_);
+        int rc = ids_.ensure((size_t)n * sizeof(int32_t));
         if (rc) return rc;
         if (which == 1) {   // not synchronised below: the ids travel through a pinned buffer of the engine's own
             const size_t bytes = (size_t)n * sizeof(int32_t);
-            if (ids_pin_cap_ < bytes) {
+            if (ids_pin_.cap < bytes) {
                 HIPCHK(hipStreamSynchronize(stream_));
-                if (ids_pin_) (void)hipHostFree(ids_pin_);
-                ids_pin_ = nullptr;
-                ids_pin_cap_ = 0;
-                if (hipHostMalloc(&ids_pin_, std::max<size_t>(bytes, 65536), hipHostMallocDefault) != hipSuccess) {
-                    (void)hipGetLastError();
-                    FAIL(PBVI_ENOMEM, "store_select: pinned staging for the ids");
-                }
-                ids_pin_cap_ = std::max<size_t>(bytes, 65536);
+                if (!ids_pin_.ensure(bytes, std::max<size_t>(bytes, 65536))) FAIL(PBVI_ENOMEM, "store_select: pinned staging for the ids");
             } else if (ev_ids_) {
                 HIPCHK(hipEventSynchronize(ev_ids_));        // the previous selection's copy has left the buffer
             }
-            std::memcpy(ids_pin_, ids, bytes);
-            HIPCHK(hipMemcpyAsync(ids_.p, ids_pin_, bytes, hipMemcpyHostToDevice, stream_));
-            if (!ev_ids_) HIPCHK(hipEventCreateWithFlags(&ev_ids_, hipEventDisableTiming));
+            std::memcpy(ids_pin_.p, ids, bytes);
+            HIPCHK(hipMemcpyAsync(ids_.p, ids_pin_.p, bytes, hipMemcpyHostToDevice, stream_));
+            HIPCHK(new_event(&ev_ids_, hipEventDisableTiming, "hipEventDestroy(ids)"));
             HIPCHK(hipEventRecord(ev_ids_, stream_));
         } else {
             HIPCHK(hipMemcpyAsync(ids_.p, ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
@@ -2039,7 +2084,7 @@ class EngineT : public EngineBase {
             // (2) a selection much smaller than the primary set: beside it
             if (!no_prepend && prim_valid_ && n <= 4096 && 4 * n <= pv) {
                 const size_t rows = alpha_rows_cap(n);
-                if ((rc = alpha_small_.ensure(rows * S_pad_ * sizeof(T), &bytes_))) return rc;
+                if ((rc = alpha_small_.ensure(rows * S_pad_ * sizeof(T)))) return rc;
                 alpha_view(alpha_small_, 0);
                 alpha_on_primary_ = false;
                 HIPCHK(hipMemsetAsync(alpha_.as<T>() + (size_t)n * S_pad_, 0, (rows - (size_t)n) * S_pad_ * sizeof(T), stream_));
@@ -2056,7 +2101,7 @@ class EngineT : public EngineBase {
             // view starts earlier)
             const int64_t front = no_prepend ? 0 : std::max<int64_t>(512, n / 2);
             const size_t rows = (size_t)front + alpha_rows_cap(n) + (no_prepend ? 0 : GEMM_BN);
-            if ((rc = alpha_buf_.ensure(rows * S_pad_ * sizeof(T), &bytes_))) return rc;
+            if ((rc = alpha_buf_.ensure(rows * S_pad_ * sizeof(T)))) return rc;
             prim_off_ = front;
             alpha_view(alpha_buf_, prim_off_);
             HIPCHK(hipMemsetAsync(alpha_.as<T>() + (size_t)n * S_pad_, 0, (rows - (size_t)front - (size_t)n) * S_pad_ * sizeof(T), stream_));
@@ -2114,7 +2159,7 @@ class EngineT : public EngineBase {
     // per-belief alpha' matrix [B][S] (the reference seam) expanded from the unique rows on first use
     int ensure_full() {
         if (full_valid_) return PBVI_OK;
-        int rc = out_full_.ensure((size_t)res_B_ * S_ * sizeof(T), &bytes_);
+        int rc = out_full_.ensure((size_t)res_B_ * S_ * sizeof(T));
         if (rc) return rc;
         HIPCHK(launch_expand_rows<T>(out_.as<T>(), inv_.as<int32_t>(), out_full_.as<T>(), (int)res_B_, S_, stream_));
         full_valid_ = true;
@@ -2168,8 +2213,8 @@ class EngineT : public EngineBase {
         if (rc) return rc;
         const size_t B = (size_t)res_B_;
         int64_t used = res_unique_;
-        const bool early_ok = early_used_ && h_flag_ && !h_flag_[6];
-        if (early_ok) used = (int64_t)h_flag_[4] + h_flag_[5];
+        const bool early_ok = early_used_ && !words().early[2];
+        if (early_ok) used = (int64_t)words().early[0] + words().early[1];
         if (queued) {                                        // the small arrays came with the pipeline's last read-back
             if ((rc = out_flush())) return rc;               // (host-side copies of staged items; the stream is idle)
             if (!early_ok) {                                 // the slots overflowed: rows in the plain order
@@ -2226,7 +2271,7 @@ class EngineT : public EngineBase {
     }
     int out_flush() {
         HIPCHK(hipStreamSynchronize(stream_));
-        for (const OutItem& it : out_items_) host_copy(it.dst, (const char*)host_stage_ + it.off, it.bytes);
+        for (const OutItem& it : out_items_) host_copy(it.dst, host_stage_.as<char>() + it.off, it.bytes);
         out_items_.clear();
         out_used_ = 0;
         return PBVI_OK;
@@ -2242,24 +2287,12 @@ class EngineT : public EngineBase {
             return PBVI_OK;
         }
         const size_t need = (out_used_ + 255) / 256 * 256 + bytes;
-        if (need > host_stage_cap_) {
-            int rc = out_flush();                            // nothing staged may be lost when the buffer moves
+        if (need > host_stage_.cap) {
+            int rc = stage_reserve(bytes);                   // (flushes first: nothing staged may be lost when the buffer moves)
             if (rc) return rc;
-            if (bytes > host_stage_cap_) {
-                if (host_stage_) (void)hipHostFree(host_stage_);
-                host_stage_ = nullptr;
-                host_stage_cap_ = 0;
-                const size_t want = std::max<size_t>(bytes * 2, (size_t)64 << 20);
-                if (hipHostMalloc(&host_stage_, want, hipHostMallocDefault) != hipSuccess) {
-                    (void)hipGetLastError();
-                    host_stage_ = nullptr;
-                    FAIL(PBVI_ENOMEM, "pinned staging allocation failed");
-                }
-                host_stage_cap_ = want;
-            }
         }
         const size_t off = (out_used_ + 255) / 256 * 256;
-        HIPCHK(hipMemcpyAsync((char*)host_stage_ + off, src_dev, bytes, hipMemcpyDeviceToHost, stream_));
+        HIPCHK(hipMemcpyAsync(host_stage_.as<char>() + off, src_dev, bytes, hipMemcpyDeviceToHost, stream_));
         out_items_.push_back({dst, off, bytes});
         out_used_ = off + bytes;
         return PBVI_OK;
@@ -2269,18 +2302,7 @@ class EngineT : public EngineBase {
     int stage_reserve(size_t bytes) {
         int rc = out_flush();
         if (rc) return rc;
-        if (bytes > host_stage_cap_) {
-            if (host_stage_) (void)hipHostFree(host_stage_);
-            host_stage_ = nullptr;
-            host_stage_cap_ = 0;
-            const size_t want = std::max<size_t>(bytes * 2, (size_t)64 << 20);
-            if (hipHostMalloc(&host_stage_, want, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError();
-                host_stage_ = nullptr;
-                FAIL(PBVI_ENOMEM, "pinned staging allocation failed");
-            }
-            host_stage_cap_ = want;
-        }
+        if (!host_stage_.ensure(bytes, std::max<size_t>(bytes * 2, (size_t)64 << 20))) FAIL(PBVI_ENOMEM, "pinned staging allocation failed");
         return PBVI_OK;
     }
 
@@ -2290,7 +2312,7 @@ class EngineT : public EngineBase {
         if (!out) FAIL(PBVI_EINVAL, "backup_fetch_row_hashes: NULL destination");
         if (res_unique_ <= 0) return PBVI_OK;
         HIPCHK(hipSetDevice(device_));
-        int rc = keys_tmp_.ensure((size_t)res_unique_ * sizeof(uint64_t), &bytes_);
+        int rc = keys_tmp_.ensure((size_t)res_unique_ * sizeof(uint64_t));
         if (rc) return rc;
         hipLaunchKernelGGL(k_row_hash<T>, dim3((unsigned)res_unique_), dim3(256), 0, stream_, out_.as<T>(), S_, S_,
                            keys_tmp_.as<unsigned long long>());
@@ -2306,7 +2328,7 @@ class EngineT : public EngineBase {
         if (!out_keys) FAIL(PBVI_EINVAL, "backup_fetch_unique_keys: NULL destination");
         if (res_unique_ <= 0) return PBVI_OK;
         HIPCHK(hipSetDevice(device_));
-        int rc = keys_tmp_.ensure((size_t)res_unique_ * (1 + O_) * sizeof(int32_t), &bytes_);
+        int rc = keys_tmp_.ensure((size_t)res_unique_ * (1 + O_) * sizeof(int32_t));
         if (rc) return rc;
         hipLaunchKernelGGL(k_gather_keys, dim3((unsigned)((res_unique_ + 63) / 64)), dim3(64), 0, stream_, (int)res_unique_, A_, O_,
                            uniq_.as<int32_t>(), res_action_, res_best_, keys_tmp_.as<int32_t>());
@@ -2326,7 +2348,7 @@ class EngineT : public EngineBase {
         int32_t* dst = out;
         const bool direct = is_device_pointer(out);
         if (!direct) {
-            int rc = keys_tmp_.ensure(n * sizeof(int32_t), &bytes_);
+            int rc = keys_tmp_.ensure(n * sizeof(int32_t));
             if (rc) return rc;
             dst = keys_tmp_.as<int32_t>();
         }
@@ -2346,10 +2368,10 @@ class EngineT : public EngineBase {
         if (n <= 0 || n > 65535 || !keys || !out_rows) FAIL(PBVI_EINVAL, "assemble_keys: bad arguments (1 <= n <= 65535)");
         HIPCHK(hipSetDevice(device_));
         int rc;
-        if ((rc = keys_tmp_.ensure((size_t)n * (1 + O_) * sizeof(int32_t), &bytes_))) return rc;
-        if ((rc = keys_act_.ensure((size_t)(n + 1) * sizeof(int32_t), &bytes_))) return rc;      // [n] actions + 1 error counter
-        if ((rc = keys_best_.ensure((size_t)n * A_ * O_ * sizeof(int32_t), &bytes_))) return rc;
-        if ((rc = keys_rows_.ensure((size_t)n * S_ * sizeof(T), &bytes_))) return rc;
+        if ((rc = keys_tmp_.ensure((size_t)n * (1 + O_) * sizeof(int32_t)))) return rc;
+        if ((rc = keys_act_.ensure((size_t)(n + 1) * sizeof(int32_t)))) return rc;      // [n] actions + 1 error counter
+        if ((rc = keys_best_.ensure((size_t)n * A_ * O_ * sizeof(int32_t)))) return rc;
+        if ((rc = keys_rows_.ensure((size_t)n * S_ * sizeof(T)))) return rc;
         int* bad = keys_act_.as<int>() + n;
         HIPCHK(hipMemcpyAsync(keys_tmp_.p, keys, (size_t)n * (1 + O_) * sizeof(int32_t), hipMemcpyDefault, stream_));
         HIPCHK(hipMemsetAsync(bad, 0, sizeof(int), stream_));
@@ -2358,8 +2380,7 @@ class EngineT : public EngineBase {
         HIPCHK(hipGetLastError());
         HIPCHK(launch_assemble<T>(alpha_.as<T>(), S_pad_, view(), gamma, keys_act_.as<int32_t>(), keys_best_.as<int32_t>(), nullptr,
                                   nullptr, (int)n, keys_rows_.as<T>(), S_, stream_));
-        int* h_bad = pinned_flag();
-        if (!h_bad) FAIL(PBVI_ENOMEM, "assemble_keys: pinned flag");
+        int* h_bad = &words().bad_key;
         *h_bad = 0;
         HIPCHK(hipMemcpyAsync(h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, stream_));
         HIPCHK(hipMemcpyAsync(out_rows, keys_rows_.p, (size_t)n * S_ * sizeof(T), hipMemcpyDefault, stream_));
@@ -2375,9 +2396,9 @@ class EngineT : public EngineBase {
         if (n <= 0 || n > 65535 || !keys) FAIL(PBVI_EINVAL, "assemble_rows_store: bad arguments (1 <= n <= 65535)");
         HIPCHK(hipSetDevice(device_));
         int rc;
-        if ((rc = keys_tmp_.ensure((size_t)n * (1 + O_) * sizeof(int32_t), &bytes_))) return rc;
-        if ((rc = keys_act_.ensure((size_t)(n + 1) * sizeof(int32_t), &bytes_))) return rc;
-        if ((rc = keys_best_.ensure((size_t)n * A_ * O_ * sizeof(int32_t), &bytes_))) return rc;
+        if ((rc = keys_tmp_.ensure((size_t)n * (1 + O_) * sizeof(int32_t)))) return rc;
+        if ((rc = keys_act_.ensure((size_t)(n + 1) * sizeof(int32_t)))) return rc;
+        if ((rc = keys_best_.ensure((size_t)n * A_ * O_ * sizeof(int32_t)))) return rc;
         T* dst = nullptr;
         if ((rc = store_reserve(0, n, &dst))) return rc;
         int* bad = keys_act_.as<int>() + n;
@@ -2389,8 +2410,7 @@ class EngineT : public EngineBase {
         if (S_pad_ > S_) HIPCHK(hipMemsetAsync(dst, 0, (size_t)n * S_pad_ * sizeof(T), stream_));   // pad columns stay zero
         HIPCHK(launch_assemble<T>(alpha_.as<T>(), S_pad_, view(), gamma, keys_act_.as<int32_t>(), keys_best_.as<int32_t>(), nullptr,
                                   nullptr, (int)n, dst, S_pad_, stream_));
-        int* h_bad = pinned_flag();
-        if (!h_bad) FAIL(PBVI_ENOMEM, "assemble_rows_store: pinned flag");
+        int* h_bad = &words().bad_key;
         *h_bad = 0;
         HIPCHK(hipMemcpyAsync(h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, stream_));
         if (out_rows) {
@@ -2398,7 +2418,7 @@ class EngineT : public EngineBase {
                 HIPCHK(hipMemcpy2DAsync(out_rows, (size_t)S_ * sizeof(T), dst, (size_t)S_pad_ * sizeof(T), (size_t)S_ * sizeof(T),
                                         (size_t)n, hipMemcpyDefault, stream_));
             } else {   // pageable destination: compact on the device, then through the pinned bounce buffer
-                if ((rc = keys_rows_.ensure((size_t)n * S_ * sizeof(T), &bytes_))) return rc;
+                if ((rc = keys_rows_.ensure((size_t)n * S_ * sizeof(T)))) return rc;
                 HIPCHK(hipMemcpy2DAsync(keys_rows_.p, (size_t)S_ * sizeof(T), dst, (size_t)S_pad_ * sizeof(T), (size_t)S_ * sizeof(T),
                                         (size_t)n, hipMemcpyDeviceToDevice, stream_));
                 if ((rc = out_begin())) return rc;
@@ -2431,7 +2451,7 @@ class EngineT : public EngineBase {
         if (!keep) FAIL(PBVI_EINVAL, "prune_dominated: keep is NULL");
         if (V_ > 4 * 65535) FAIL(PBVI_EUNSUPPORTED, "prune_dominated: at most 262140 alpha-vectors");   // grid.y = ceil(V / 4)
         HIPCHK(hipSetDevice(device_));
-        int rc = prune_cnt_.ensure((size_t)V_ * sizeof(int), &bytes_);
+        int rc = prune_cnt_.ensure((size_t)V_ * sizeof(int));
         if (rc) return rc;
         HIPCHK(hipMemsetAsync(prune_cnt_.p, 0, (size_t)V_ * sizeof(int), stream_));
         HIPCHK(launch_dominated<T>(alpha_.as<T>(), S_pad_, (int)V_, S_, prune_cnt_.as<int>(), stream_));
@@ -2459,10 +2479,10 @@ class EngineT : public EngineBase {
             return PBVI_OK;
         }
         HIPCHK(hipSetDevice(device_));
-        int rc = prune_cnt_.ensure((size_t)2 * V * sizeof(int), &bytes_);
+        int rc = prune_cnt_.ensure((size_t)2 * V * sizeof(int));
         if (rc) return rc;
         if ((rc = stage_reserve((size_t)3 * V * sizeof(int)))) return rc;
-        int* h_cnt = static_cast<int*>(host_stage_);
+        int* h_cnt = host_stage_.as<int>();
         int32_t* h_rows = h_cnt + V;
         int* h_out = h_rows + V;
         const int n_old = V - n_new;
@@ -2535,17 +2555,20 @@ class EngineT : public EngineBase {
 
     int64_t store_count(int which) const override { return (which == 0 || which == 1) ? store_rows_[which] : -1; }
 
-    // grow a buffer to `need` bytes keeping its first `used` bytes
-    int grow_keep(DevBuf& b, size_t need, size_t used) {
-        if (need <= b.cap) return PBVI_OK;
-        DevBuf nb;
-        int rc = nb.ensure(std::max(need, b.cap * 2), &bytes_);
+    // Grow a buffer to `need` bytes, at least doubling it, keeping its first `used` bytes.  The new allocation is a scoped
+    // owner until the kept bytes have arrived: a failure on the way releases it and leaves the buffer and the engine's
+    // byte count as they were.  For alpha_append: `alloc` != 0 moves to a new allocation of exactly that size even where the
+    // buffer is large enough, the kept bytes come from `src` (default: the start of the buffer), `zero` clears the new
+    // allocation first.
+    int grow_keep(DevBuf& b, size_t need, size_t used, size_t alloc = 0, const void* src = nullptr, bool zero = false) {
+        if (alloc == 0 && need <= b.cap) return PBVI_OK;
+        DevBuf nb(mem_, DevBuf::SCOPED);
+        int rc = nb.ensure(alloc ? alloc : std::max(need, b.cap * 2));
         if (rc) return rc;
-        if (used > 0) HIPCHK(hipMemcpyAsync(nb.p, b.p, used, hipMemcpyDeviceToDevice, stream_));
+        if (zero) HIPCHK(hipMemsetAsync(nb.p, 0, nb.cap, stream_));
+        if (used > 0) HIPCHK(hipMemcpyAsync(nb.p, src ? src : b.p, used, hipMemcpyDeviceToDevice, stream_));
         HIPCHK(hipStreamSynchronize(stream_));
-        bytes_ -= (int64_t)b.cap;
-        b.release();
-        b = nb;
+        b.take(nb);
         return PBVI_OK;
     }
 
@@ -2593,25 +2616,25 @@ class EngineT : public EngineBase {
             sbt_rows_ = have;
         }
         // run value_max_device on windows of the store: the block members point into the store for the duration
-        struct Saved {
-            DevBuf bel, nzA, btl, btc;
-            int64_t B, B_pad;
-            bool sorted, btl_valid, have_result;
-        } sv{bel_, nzA_, btl_, btc_, B_, B_pad_, sorted_, btl_valid_, have_result_};
-        auto restore = [&]() {
-            bel_ = sv.bel; nzA_ = sv.nzA; btl_ = sv.btl; btc_ = sv.btc;
-            B_ = sv.B; B_pad_ = sv.B_pad; sorted_ = sv.sorted; btl_valid_ = sv.btl_valid; have_result_ = sv.have_result;
-        };
-        const size_t huge = ~(size_t)0 >> 1;              // aliased buffers must never look too small to ensure()
+        // (put back when `win` goes out of scope, on every return path)
+        struct Windows {
+            EngineT& e;
+            DevBuf::Window bel{e.bel_}, nzA{e.nzA_}, btl{e.btl_}, btc{e.btc_};
+            const int64_t B = e.B_, B_pad = e.B_pad_;
+            const bool sorted = e.sorted_, btl_valid = e.btl_valid_, have_result = e.have_result_;
+            ~Windows() {
+                e.B_ = B; e.B_pad_ = B_pad; e.sorted_ = sorted; e.btl_valid_ = btl_valid; e.have_result_ = have_result;
+            }
+        } win{*this};
         const int64_t window = 32768;
         rc = PBVI_OK;
         for (int64_t r0 = 0; r0 < n && rc == PBVI_OK; r0 += window) {
             const int64_t cnt = std::min<int64_t>(window, n - r0);
-            bel_.p = base + (size_t)r0 * S_pad_;                       bel_.cap = huge;
-            nzA_.p = snz_.as<uint8_t>() + (size_t)(r0 / GEMM_BM) * k_tiles;   nzA_.cap = huge;
+            win.bel.point(base + (size_t)r0 * S_pad_);
+            win.nzA.point(snz_.as<uint8_t>() + (size_t)(r0 / GEMM_BM) * k_tiles);
             if (kF32 && !vmax_skinny()) {
-                btl_.p = sbtl_.as<int32_t>() + (size_t)r0 * k_tiles;   btl_.cap = huge;
-                btc_.p = sbtc_.as<int32_t>() + r0;                     btc_.cap = huge;
+                win.btl.point(sbtl_.as<int32_t>() + (size_t)r0 * k_tiles);
+                win.btc.point(sbtc_.as<int32_t>() + r0);
             }
             B_ = cnt;
             B_pad_ = round_up(cnt, GEMM_BM);
@@ -2624,7 +2647,6 @@ class EngineT : public EngineBase {
             if (rc == PBVI_OK) rc = out_finish();
         }
         if (rc != PBVI_OK) (void)hipStreamSynchronize(stream_);
-        restore();
         return rc;
     }
 
@@ -2648,16 +2670,16 @@ class EngineT : public EngineBase {
         if (const char* c = getenv("PBVI_REFINE_SLOT_CAP")) slots = std::max<int64_t>(1, atoll(c));   // overflow paths
         if (items <= 0 || slots <= 0) return PBVI_OK;
         int rc;
-        if ((rc = rf_v_.ensure((size_t)items * sizeof(int32_t), &bytes_))) return rc;
-        if ((rc = rf_slot_.ensure((size_t)items * sizeof(int32_t), &bytes_))) return rc;
-        if ((rc = rf_sc_.ensure((size_t)items * sizeof(double), &bytes_))) return rc;
-        if ((rc = rf_entry_.ensure((size_t)slots * sizeof(int32_t), &bytes_))) return rc;
-        if ((rc = rf_n_.ensure((size_t)slots * sizeof(int32_t), &bytes_))) return rc;
-        if ((rc = rf_tiles_.ensure((size_t)slots * k_tiles * sizeof(int32_t), &bytes_))) return rc;
+        if ((rc = rf_v_.ensure((size_t)items * sizeof(int32_t)))) return rc;
+        if ((rc = rf_slot_.ensure((size_t)items * sizeof(int32_t)))) return rc;
+        if ((rc = rf_sc_.ensure((size_t)items * sizeof(double)))) return rc;
+        if ((rc = rf_entry_.ensure((size_t)slots * sizeof(int32_t)))) return rc;
+        if ((rc = rf_n_.ensure((size_t)slots * sizeof(int32_t)))) return rc;
+        if ((rc = rf_tiles_.ensure((size_t)slots * k_tiles * sizeof(int32_t)))) return rc;
         const size_t zero_bytes = 16 + (size_t)slots * (sizeof(unsigned long long) + sizeof(int32_t));
-        if ((rc = rf_cnt_.ensure(zero_bytes, &bytes_))) return rc;      // [cnt: 16 B][emax][eidx]
-        if ((rc = rf_ibv_.ensure((size_t)slots * sizeof(double), &bytes_))) return rc;
-        if ((rc = rf_ibi_.ensure((size_t)slots * sizeof(int32_t), &bytes_))) return rc;
+        if ((rc = rf_cnt_.ensure(zero_bytes))) return rc;      // [cnt: 16 B][emax][eidx]
+        if ((rc = rf_ibv_.ensure((size_t)slots * sizeof(double)))) return rc;
+        if ((rc = rf_ibi_.ensure((size_t)slots * sizeof(int32_t)))) return rc;
         w->items_v = rf_v_.as<int32_t>();
         w->items_slot = rf_slot_.as<int32_t>();
         w->scores = rf_sc_.as<double>();
@@ -2674,10 +2696,10 @@ class EngineT : public EngineBase {
             int64_t q2 = std::min<int64_t>(max_entries, 16384);
             if (const char* c = getenv("PBVI_REFINE_Q2_CAP")) q2 = std::max<int64_t>(1, std::min<int64_t>(q2, atoll(c)));   // tests: force the hand-over's overflow path
             const size_t need = (size_t)q2 * (2 + 8) * sizeof(int32_t);
-            if ((rc = rf_q2_.ensure(need, &bytes_))) return rc;
-            if ((rc = rf_q2p_.ensure((size_t)q2 * 16 * 8 * sizeof(double), &bytes_))) return rc;
+            if ((rc = rf_q2_.ensure(need))) return rc;
+            if ((rc = rf_q2p_.ensure((size_t)q2 * 16 * 8 * sizeof(double)))) return rc;
             if (rf_q2d_.cap < (size_t)q2 * sizeof(int)) {
-                if ((rc = rf_q2d_.ensure((size_t)q2 * sizeof(int), &bytes_))) return rc;
+                if ((rc = rf_q2d_.ensure((size_t)q2 * sizeof(int)))) return rc;
                 HIPCHK(hipMemsetAsync(rf_q2d_.p, 0, rf_q2d_.cap, stream_));      // arrival counters: zero between launches
             }
             w->q2_entry = rf_q2_.as<int32_t>();
@@ -2697,11 +2719,11 @@ class EngineT : public EngineBase {
         if (w_slots > 0) {
             if ((rc = build_inverse_lists())) return rc;
             const int kt32 = S_pad_ / GEMM_BK;
-            if ((rc = rf_W_.ensure((size_t)w_slots * S_pad_ * sizeof(double), &bytes_))) return rc;
-            if ((rc = rf_Cx_.ensure((size_t)w_slots * V * sizeof(double), &bytes_))) return rc;
-            if ((rc = rf_nzW_.ensure((size_t)((w_slots + 255) / 256) * kt32, &bytes_))) return rc;
-            if ((rc = rf_klW_.ensure(gemm_f64_klist_ints((int)w_slots, (int)V, kt32) * sizeof(int), &bytes_))) return rc;
-            if ((rc = rf_kcW_.ensure(gemm_f64_kcount_ints((int)w_slots, (int)V, kt32) * sizeof(int), &bytes_))) return rc;
+            if ((rc = rf_W_.ensure((size_t)w_slots * S_pad_ * sizeof(double)))) return rc;
+            if ((rc = rf_Cx_.ensure((size_t)w_slots * V * sizeof(double)))) return rc;
+            if ((rc = rf_nzW_.ensure((size_t)((w_slots + 255) / 256) * kt32))) return rc;
+            if ((rc = rf_klW_.ensure(gemm_f64_klist_ints((int)w_slots, (int)V, kt32) * sizeof(int)))) return rc;
+            if ((rc = rf_kcW_.ensure(gemm_f64_kcount_ints((int)w_slots, (int)V, kt32) * sizeof(int)))) return rc;
             w->W = rf_W_.as<double>();
             w->Cx = rf_Cx_.as<double>();
             w->nzW = rf_nzW_.as<uint8_t>();
@@ -2732,7 +2754,7 @@ class EngineT : public EngineBase {
         const size_t bytes = (size_t)B_pad_ * S_pad_ * sizeof(float);
         if (bytes == 0 || S_pad_ > (1 << 22)) return false;
         if (belsp_.cap < bytes) {
-            if (!DevBuf::headroom_ok(bytes_, bytes) || belsp_.ensure(bytes, &bytes_) != PBVI_OK) return false;
+            if (!DevBuf::headroom_ok(mem_.bytes, bytes) || belsp_.ensure(bytes) != PBVI_OK) return false;
             belsp_ver_ = 0;
         }
         if (belsp_ver_ != bel_ver_) {
@@ -2813,7 +2835,7 @@ class EngineT : public EngineBase {
             prev = tile_ev_[(size_t)3 * c + 2];
         }
     }
-    int64_t device_bytes() const override { return bytes_ + (screen_ ? screen_->bytes_ : 0); }
+    int64_t device_bytes() const override { return mem_.bytes + (screen_ ? screen_->mem_.bytes : 0); }
 };
 
 template <typename T>
@@ -2833,11 +2855,11 @@ int EngineT<T>::score_gemm(const T* Y, int64_t rows_y, const uint8_t* nzB, int G
         if (m_pad > 0x7fffffff || n_pad > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "score_gemm: operand rows exceed int32");
         plan_ = make_gemm_plan((int)m_pad, (int)n_pad, S_pad_);
         const size_t pairs = (size_t)plan_.tiles_m * plan_.tiles_n;
-        if ((rc = slabs_.ensure((size_t)plan_.c_floats * sizeof(float), &bytes_))) return rc;
-        if ((rc = klist_.ensure(pairs * plan_.k_tiles * sizeof(int), &bytes_))) return rc;
-        if ((rc = kcount_.ensure(pairs * sizeof(int), &bytes_))) return rc;
-        if ((rc = nchunks_.ensure(pairs * sizeof(int), &bytes_))) return rc;
-        if ((rc = skws_.ensure(streamk_workspace_ints(plan_) * sizeof(int), &bytes_))) return rc;
+        if ((rc = slabs_.ensure((size_t)plan_.c_floats * sizeof(float)))) return rc;
+        if ((rc = klist_.ensure(pairs * plan_.k_tiles * sizeof(int)))) return rc;
+        if ((rc = kcount_.ensure(pairs * sizeof(int)))) return rc;
+        if ((rc = nchunks_.ensure(pairs * sizeof(int)))) return rc;
+        if ((rc = skws_.ensure(streamk_workspace_ints(plan_) * sizeof(int)))) return rc;
         int sp = split != nullptr && *split && plan_.streamk && (fused == nullptr || fused->R == 1) ? 1 : 0;
         if (sp && (!own_block || !split_plane())) sp = 0;      // no plane: the fp32 GEMM (same outputs)
         if (split != nullptr) *split = sp;
@@ -2857,15 +2879,15 @@ int EngineT<T>::score_gemm(const T* Y, int64_t rows_y, const uint8_t* nzB, int G
     } else {
         const int kt32s = S_pad_ / GEMM_BK;
         const int split = f64_uses_mfma(m_rows, rows_y) ? gemm_f64_split((int)m_rows, (int)rows_y, kt32s) : 1;
-        if ((rc = slabs_.ensure((size_t)split * m_rows * rows_y * sizeof(T), &bytes_))) return rc;
+        if ((rc = slabs_.ensure((size_t)split * m_rows * rows_y * sizeof(T)))) return rc;
         f64_pairs_ = 0;
         if (!f64_uses_mfma(m_rows, rows_y)) {
             HIPCHK(launch_gemm_nt_simple<T>(X, S_pad_, Y, S_pad_, slabs_.as<T>(), (int)rows_y, (int)m_rows, (int)rows_y,
                                             S_, stream_));
         } else {
             const int kt32 = S_pad_ / GEMM_BK;
-            if ((rc = klist_.ensure(gemm_f64_klist_ints((int)m_rows, (int)rows_y, kt32) * sizeof(int), &bytes_))) return rc;
-            if ((rc = kcount_.ensure(gemm_f64_kcount_ints((int)m_rows, (int)rows_y, kt32) * sizeof(int), &bytes_))) return rc;
+            if ((rc = klist_.ensure(gemm_f64_klist_ints((int)m_rows, (int)rows_y, kt32) * sizeof(int)))) return rc;
+            if ((rc = kcount_.ensure(gemm_f64_kcount_ints((int)m_rows, (int)rows_y, kt32) * sizeof(int)))) return rc;
             HIPCHK(launch_gemm_nt_f64((const double*)X, S_pad_, (int)m_rows, (const double*)Y, S_pad_, (int)rows_y,
                                       slabs_.as<double>(), (int)rows_y, S_pad_, nzX, nzB, G, v_group, klist_.as<int>(),
                                       kcount_.as<int>(), stream_, split, m_rows * rows_y));
@@ -2893,11 +2915,11 @@ int EngineT<T>::project_dense(double gamma) {
         const size_t pairs = (size_t)pl.tiles_m * pl.tiles_n;
         ld_prod = n_pad;
         batch_stride = Vt_pad * n_pad;
-        if ((rc = prod_.ensure((size_t)AO * batch_stride * sizeof(float), &bytes_))) return rc;
-        if ((rc = nzAlpha_.ensure((size_t)pl.tiles_m * pl.k_tiles, &bytes_))) return rc;
-        if ((rc = klistD_.ensure((size_t)AO * pairs * pl.k_tiles * sizeof(int), &bytes_))) return rc;
-        if ((rc = kcountD_.ensure((size_t)AO * pairs * sizeof(int), &bytes_))) return rc;
-        if ((rc = nchunksD_.ensure((size_t)AO * pairs * sizeof(int), &bytes_))) return rc;
+        if ((rc = prod_.ensure((size_t)AO * batch_stride * sizeof(float)))) return rc;
+        if ((rc = nzAlpha_.ensure((size_t)pl.tiles_m * pl.k_tiles))) return rc;
+        if ((rc = klistD_.ensure((size_t)AO * pairs * pl.k_tiles * sizeof(int)))) return rc;
+        if ((rc = kcountD_.ensure((size_t)AO * pairs * sizeof(int)))) return rc;
+        if ((rc = nchunksD_.ensure((size_t)AO * pairs * sizeof(int)))) return rc;
         dense_pairs_ = (int64_t)AO * pairs;
         HIPCHK(hipMemsetAsync(prod_.p, 0, (size_t)AO * batch_stride * sizeof(float), stream_));   // pairs with empty lists
         HIPCHK(launch_tile_nonzero_f32((const float*)alpha_.p, S_pad_, (int)Vt_pad, pl.k_tiles, nzAlpha_.as<uint8_t>(), stream_));
@@ -2908,7 +2930,7 @@ int EngineT<T>::project_dense(double gamma) {
     } else {
         ld_prod = S_;
         batch_stride = Vt * S_;
-        if ((rc = prod_.ensure((size_t)AO * batch_stride * sizeof(T), &bytes_))) return rc;
+        if ((rc = prod_.ensure((size_t)AO * batch_stride * sizeof(T)))) return rc;
         for (int ao = 0; ao < AO; ++ao)
             HIPCHK(launch_gemm_nt_simple<T>(alpha_.as<T>(), S_pad_, dense_.as<T>() + (size_t)ao * rows_pad_s_ * S_pad_, S_pad_,
                                             prod_.as<T>() + (size_t)ao * batch_stride, (int)ld_prod, (int)Vt, S_, S_, stream_));
@@ -2927,11 +2949,11 @@ template <typename T>
 int EngineT<T>::value_max_device() {
     int rc;
     const int64_t Vt = V_ + 1;   // + magnitude row
-    if ((rc = bv2_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
-    if ((rc = bs2_.ensure((size_t)B_ * sizeof(double), &bytes_))) return rc;
-    if ((rc = err2_.ensure((size_t)B_ * sizeof(double), &bytes_))) return rc;
-    if ((rc = queue2_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
-    int* qc = counters_.as<int>() + 2;
+    if ((rc = bv2_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+    if ((rc = bs2_.ensure((size_t)B_ * sizeof(double)))) return rc;
+    if ((rc = err2_.ensure((size_t)B_ * sizeof(double)))) return rc;
+    if ((rc = queue2_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+    int* qc = counters_.as<int>() + CNT_VALUE_MAX_QUEUE;
     HIPCHK(hipMemsetAsync(qc, 0, sizeof(int), stream_));
     if constexpr (kF32) {
         if (vmax_skinny()) {
@@ -2943,9 +2965,9 @@ int EngineT<T>::value_max_device() {
             const int kt32 = S_pad_ / GEMM_BK;
             const int split = gemm_f64_split((int)B_, (int)V_, kt32);
             const int64_t slab = B_ * V_;
-            if ((rc = slabs_.ensure((size_t)split * slab * sizeof(double), &bytes_))) return rc;
-            if ((rc = klist_.ensure(gemm_f64_klist_ints((int)B_, (int)V_, kt32) * sizeof(int), &bytes_))) return rc;
-            if ((rc = kcount_.ensure(gemm_f64_kcount_ints((int)B_, (int)V_, kt32) * sizeof(int), &bytes_))) return rc;
+            if ((rc = slabs_.ensure((size_t)split * slab * sizeof(double)))) return rc;
+            if ((rc = klist_.ensure(gemm_f64_klist_ints((int)B_, (int)V_, kt32) * sizeof(int)))) return rc;
+            if ((rc = kcount_.ensure(gemm_f64_kcount_ints((int)B_, (int)V_, kt32) * sizeof(int)))) return rc;
             HIPCHK(launch_gemm_nt_f64_ff32((const float*)bel_.p, S_pad_, (int)B_, (const float*)alpha_.p, S_pad_, (int)V_,
                                            slabs_.as<double>(), (int)V_, S_pad_, nzA_.as<uint8_t>(), klist_.as<int>(),
                                            kcount_.as<int>(), stream_, split, slab));
@@ -2972,8 +2994,8 @@ int EngineT<T>::value_max_device() {
     if (rescore) {
         if (!btl_valid_) {   // tile lists of the resident block (the backup's k_dead builds them too)
             const int k_tiles = S_pad_ / GEMM_BK;
-            if ((rc = btl_.ensure((size_t)B_ * k_tiles * sizeof(int32_t), &bytes_))) return rc;
-            if ((rc = btc_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
+            if ((rc = btl_.ensure((size_t)B_ * k_tiles * sizeof(int32_t)))) return rc;
+            if ((rc = btc_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
             HIPCHK(launch_belief_tiles<T>(bel_.as<T>(), S_pad_, (int)B_, S_, k_tiles, btl_.as<int32_t>(), btc_.as<int32_t>(),
                                           stream_));
             btl_valid_ = true;
@@ -3105,9 +3127,9 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
                     for (int64_t v = vb * 4; v < vb * 4 + 4 && v < V_ && !hit; ++v) hit = h_mat_[(size_t)((ao * V_ + v) >> 8)] != 0;
                 if (hit) h_vlist_.push_back((int)vb);
             }
-            if ((rc = mat_.ensure((size_t)tiles_n, &bytes_))) return rc;
-            if ((rc = ctile_.ensure((size_t)tiles_n * sizeof(int32_t), &bytes_))) return rc;
-            if ((rc = vlist_.ensure(h_vlist_.size() * sizeof(int), &bytes_))) return rc;
+            if ((rc = mat_.ensure((size_t)tiles_n))) return rc;
+            if ((rc = ctile_.ensure((size_t)tiles_n * sizeof(int32_t)))) return rc;
+            if ((rc = vlist_.ensure(h_vlist_.size() * sizeof(int)))) return rc;
             HIPCHK(hipMemcpyAsync(mat_.p, h_mat_.data(), (size_t)tiles_n, hipMemcpyHostToDevice, stream_));
             HIPCHK(hipMemcpyAsync(ctile_.p, h_ctile_.data(), (size_t)tiles_n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
             HIPCHK(hipMemcpyAsync(vlist_.p, h_vlist_.data(), h_vlist_.size() * sizeof(int), hipMemcpyHostToDevice, stream_));
@@ -3141,7 +3163,7 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
     }
     if (!use_push) {
         const int64_t rows_held = compact ? (int64_t)n_mat_ * GEMM_BN : n_rows_alloc;
-        if ((rc = gam_.ensure((size_t)rows_held * S_pad_ * sizeof(T), &bytes_))) return rc;
+        if ((rc = gam_.ensure((size_t)rows_held * S_pad_ * sizeof(T)))) return rc;
         // zero the Gamma pad rows the GEMM tiles read -- once per (buffer, row count, layout): nothing writes rows >= N,
         // and the fill of up to 255 rows (27 MB, 39 us at |S| = 30000) sat in front of every backup's score GEMM
         if (n_rows_alloc > N && (gam_pad_ptr_ != gam_.p || gam_pad_N_ != N || gam_pad_compact_ != compact || mode_ == PBVI_DENSE)) {
@@ -3165,9 +3187,9 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
         // compute_change's max_v b.alpha_v of these beliefs against this alpha set (pbvi_backup_fetch_value_max)
         // rides in the M padding (1800 + 100 rows of 2048 in a solve loop).
         const int64_t M = (int64_t)AO * B_, Mx = M + B_, M_pad = round_up(Mx, GEMM_BM);
-        if ((rc = bp_.ensure((size_t)M_pad * S_pad_ * sizeof(T), &bytes_))) return rc;
-        if ((rc = pmag_.ensure((size_t)pairs * sizeof(double), &bytes_))) return rc;
-        if ((rc = nzP_.ensure((size_t)(M_pad / GEMM_BM) * k_tiles, &bytes_))) return rc;
+        if ((rc = bp_.ensure((size_t)M_pad * S_pad_ * sizeof(T)))) return rc;
+        if ((rc = pmag_.ensure((size_t)pairs * sizeof(double)))) return rc;
+        if ((rc = nzP_.ensure((size_t)(M_pad / GEMM_BM) * k_tiles))) return rc;
         HIPCHK(hipMemsetAsync(pmag_.p, 0, (size_t)pairs * sizeof(double), stream_));
         HIPCHK(hipMemcpyAsync(bp_.as<T>() + (size_t)M * S_pad_, bel_.p, (size_t)B_ * S_pad_ * sizeof(T), hipMemcpyDeviceToDevice, stream_));
         if (M_pad > Mx)
@@ -3207,7 +3229,7 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
         // (a fused engine projects one or two tiles' worth of rows -- the tiles that straddle groups, the tail: all of their K
         // tiles are written, and the 12 us of k_need_tiles leave the front of every backup)
         if ((kF32 || f64_uses_mfma(B_, N)) && !(will_fuse && R_ == 1)) {
-            if ((rc = need_.ensure((size_t)AO * k_tiles, &bytes_))) return rc;
+            if ((rc = need_.ensure((size_t)AO * k_tiles))) return rc;
             HIPCHK(launch_need_tiles(nzA_.as<uint8_t>(), (int)(B_pad_ / GEMM_BM), nzB_.as<uint8_t>(), AO, (int)V_, k_tiles,
                                      need_.as<uint8_t>(), stream_));
             need = need_.as<uint8_t>();
@@ -3275,10 +3297,9 @@ template <typename T>
 int EngineT<T>::ensure_exact(DevBuf& b, size_t bytes) {
     if (bytes > b.cap && b.p != nullptr) {
         HIPCHK(hipStreamSynchronize(stream_));
-        bytes_ -= (int64_t)b.cap;
         b.release();
     }
-    return b.ensure(bytes, &bytes_);
+    return b.ensure(bytes);
 }
 
 // The alpha-side scoring stage with Gamma tiled over the alpha set (pbvi_set_gamma_tiling): n_chunks chunks of Vc alpha
@@ -3308,16 +3329,13 @@ int EngineT<T>::stage_scores_tiled(double gamma, const ScoreIO& io, int want_spl
         const int sp = f64_uses_mfma(B_, n_big) ? gemm_f64_split((int)B_, (int)n_big, k_tiles) : 1;
         if ((rc = ensure_exact(slabs_, (size_t)sp * B_ * n_big * sizeof(T)))) return rc;
     }
-    if ((rc = need_.ensure((size_t)AO * k_tiles, &bytes_))) return rc;
-    if ((rc = chain_max_.ensure(sizeof(int), &bytes_))) return rc;
+    if ((rc = need_.ensure((size_t)AO * k_tiles))) return rc;
+    if ((rc = chain_max_.ensure(sizeof(int)))) return rc;
     HIPCHK(hipMemsetAsync(chain_max_.p, 0, sizeof(int), stream_));
     tile_ev_chunks_ = 0;
     if (io.stats) {
-        while ((int64_t)tile_ev_.size() < 3 * n_chunks) {
-            hipEvent_t e = nullptr;
-            HIPCHK(hipEventCreate(&e));
-            tile_ev_.push_back(e);
-        }
+        if ((int64_t)tile_ev_.size() < 3 * n_chunks) tile_ev_.resize((size_t)(3 * n_chunks), nullptr);
+        for (auto& e : tile_ev_) HIPCHK(new_event(&e, hipEventDefault, "hipEventDestroy(tile)"));
         tile_ev_chunks_ = (int)n_chunks;
     }
     double tol = 0.0;
@@ -3421,7 +3439,7 @@ int EngineT<T>::sync_screen() {
         int rc;
         if (screen_alpha_seen_ != alpha_ver_) {
             if (!scr_flag_.p) {
-                if ((rc = scr_flag_.ensure(sizeof(int), &bytes_))) return rc;
+                if ((rc = scr_flag_.ensure(sizeof(int)))) return rc;
                 HIPCHK(hipMemsetAsync(scr_flag_.p, 0, sizeof(int), stream_));
             }
             auto narrow = [&](const double* src, float* dst, int64_t rows) -> int {
@@ -3444,7 +3462,7 @@ int EngineT<T>::sync_screen() {
                 if ((rc = narrow(alpha_.as<double>(), sc->alpha_.template as<float>(), k))) return rc;
                 if ((rc = sc->merge_magnitude_row(sc->alpha_.template as<float>(), k))) return rc;
             } else {
-                if ((rc = sc->alpha_buf_.ensure(rows_total * S_pad_ * sizeof(float), &sc->bytes_))) return rc;
+                if ((rc = sc->alpha_buf_.ensure(rows_total * S_pad_ * sizeof(float)))) return rc;
                 sc->alpha_view(sc->alpha_buf_, off);
                 sc->V_ = V_;
                 HIPCHK(hipMemsetAsync(scr_flag_.p, 0, sizeof(int), stream_));        // a fresh copy: no row has overflowed yet
@@ -3461,8 +3479,8 @@ int EngineT<T>::sync_screen() {
         }
         if (screen_bel_seen_ != bel_ver_) {
             const int k_tiles = S_pad_ / GEMM_BK;
-            if ((rc = sc->bel_.ensure((size_t)B_pad_ * S_pad_ * sizeof(float), &sc->bytes_))) return rc;
-            if ((rc = sc->nzA_.ensure((size_t)(B_pad_ / GEMM_BM) * k_tiles, &sc->bytes_))) return rc;
+            if ((rc = sc->bel_.ensure((size_t)B_pad_ * S_pad_ * sizeof(float)))) return rc;
+            if ((rc = sc->nzA_.ensure((size_t)(B_pad_ / GEMM_BM) * k_tiles))) return rc;
             const int64_t n = (int64_t)B_pad_ * S_pad_;      // same row order as this engine's block (pad rows are zero)
             hipLaunchKernelGGL(k_narrow, dim3((unsigned)((n / 4 + 255) / 256 + 1)), dim3(256), 0, stream_, bel_.as<double>(),
                                sc->bel_.template as<float>(), n, (int*)nullptr);
@@ -3497,10 +3515,10 @@ int EngineT<T>::backup_run(double gamma, int flags, pbvi_stats_t* st) {
             int rc = ensure_screen();
             if (rc) return rc;
             if ((rc = sync_screen())) return rc;
-            if (int* f = pinned_flag()) f[1] = 0;
+            words().screen_overflow = 0;
             if ((rc = run_pipeline<float>(*screen_, gamma, flags, st))) return rc;
             // |alpha| beyond FLT_MAX became inf in the screen's copy (NaN scores follow): the fp64 pipeline decides alone
-            if (h_flag_ && h_flag_[1]) return run_pipeline<T>(*this, gamma, flags, st);
+            if (words().screen_overflow) return run_pipeline<T>(*this, gamma, flags, st);
             return PBVI_OK;
         }
     }
@@ -3523,21 +3541,21 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
     const ModelView<T> mv = view();
     const bool use_push = scorer.choose_push(N);
     last_formulation_ = use_push ? 2 : 1;
-    if ((rc = best_v_.ensure((size_t)pairs * sizeof(int32_t), &bytes_))) return rc;
-    if ((rc = best_score_.ensure((size_t)pairs * sizeof(double), &bytes_))) return rc;
-    if ((rc = err_.ensure((size_t)pairs * sizeof(double), &bytes_))) return rc;
-    if ((rc = queue_.ensure((size_t)pairs * sizeof(int32_t), &bytes_))) return rc;
-    if ((rc = dead_.ensure((size_t)pairs, &bytes_))) return rc;
-    if ((rc = rdot_.ensure((size_t)B_ * A_ * 2 * sizeof(double), &bytes_))) return rc;
-    if ((rc = action_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
-    if ((rc = aqueue_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
-    if ((rc = acand_.ensure((size_t)B_ * A_, &bytes_))) return rc;
-    if (!q_only_ && (rc = out_.ensure((size_t)B_ * S_ * sizeof(T), &bytes_))) return rc;
-    if ((rc = keep_.ensure((size_t)B_, &bytes_))) return rc;
-    int* qcount = counters_.as<int>();
-    int* aqcount = counters_.as<int>() + 1;
+    if ((rc = best_v_.ensure((size_t)pairs * sizeof(int32_t)))) return rc;
+    if ((rc = best_score_.ensure((size_t)pairs * sizeof(double)))) return rc;
+    if ((rc = err_.ensure((size_t)pairs * sizeof(double)))) return rc;
+    if ((rc = queue_.ensure((size_t)pairs * sizeof(int32_t)))) return rc;
+    if ((rc = dead_.ensure((size_t)pairs))) return rc;
+    if ((rc = rdot_.ensure((size_t)B_ * A_ * 2 * sizeof(double)))) return rc;
+    if ((rc = action_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+    if ((rc = aqueue_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+    if ((rc = acand_.ensure((size_t)B_ * A_))) return rc;
+    if (!q_only_ && (rc = out_.ensure((size_t)B_ * S_ * sizeof(T)))) return rc;
+    if ((rc = keep_.ensure((size_t)B_))) return rc;
+    int* qcount = counters_.as<int>() + CNT_QUEUE;
+    int* aqcount = counters_.as<int>() + CNT_ACTION_QUEUE;
     if (windows && (rc = stage_reserve(256))) return rc;      // the pinned bounce buffer of the fetches that follow, allocated while the stream is idle
-    HIPCHK(hipMemsetAsync(counters_.p, 0, 8 * sizeof(int), stream_));
+    HIPCHK(hipMemsetAsync(counters_.p, 0, CNT_SLOTS * sizeof(int), stream_));
 
     HIPCHK(hipEventRecord(ev_[0], stream_));
     // Belief-only work (dead triples, b.ER: ~0.1 ms each) on the side stream, beside the projection.
@@ -3553,9 +3571,9 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
     if (lists != nullptr && lists != side)
         HIPCHK(hipStreamWaitEvent(lists, (!screened && ev_nzA_ != nullptr && nzA_ver_ == bel_ver_) ? ev_nzA_ : ev_fork_, 0));
     if (windows) {   // exact, from the supports of the ORIGINAL operands (an fp32 copy may have flushed tiny values to zero)
-        if ((rc = btl_.ensure((size_t)B_ * k_tiles * sizeof(int32_t), &bytes_))) return rc;
-        if ((rc = btc_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
-        if ((rc = val_exact_.ensure((size_t)B_ * A_ * (1 + O_) * ACTION_SPLIT * sizeof(double), &bytes_))) return rc;
+        if ((rc = btl_.ensure((size_t)B_ * k_tiles * sizeof(int32_t)))) return rc;
+        if ((rc = btc_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+        if ((rc = val_exact_.ensure((size_t)B_ * A_ * (1 + O_) * ACTION_SPLIT * sizeof(double)))) return rc;
         // Dead triples and the per-belief tile lists are a function of the belief block and the model alone: computed on
         // the first backup of a block, kept for the following ones (a solve backs a block up once; update_passes > 1,
         // the belief-dominance loops of the notebooks and the benchmark back the same block up again and again).  Like
@@ -3564,7 +3582,7 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
         if (dead_ver_ != bel_ver_ || !btl_valid_ || dead_pairs_ != pairs || no_cache) {
             const bool have_flags = rowflags_ver_ == bel_ver_ && rowflags_.p != nullptr;   // left by the block's indexing pass
             HIPCHK(launch_dead<T>(bel_.as<T>(), S_pad_, (int)B_, mv, nzBw_.as<unsigned long long>(), k_tiles, dead_.as<uint8_t>(),
-                                  btl_.as<int32_t>(), btc_.as<int32_t>(), counters_.as<int>() + 5, side,
+                                  btl_.as<int32_t>(), btc_.as<int32_t>(), counters_.as<int>() + CNT_DEAD, side,
                                   have_flags ? rowflags_.as<uint8_t>() : nullptr,
                                   have_flags && sorted_ ? perm_.as<int32_t>() : nullptr));
             btl_valid_ = true;
@@ -3574,14 +3592,14 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
         }
     }
     if (use_push) {   // b . ER[:,a] in f64 (the alpha-side gets it from Gamma's reward rows)
-        if ((rc = prd_.ensure((size_t)B_ * A_ * sizeof(double), &bytes_))) return rc;
+        if ((rc = prd_.ensure((size_t)B_ * A_ * sizeof(double)))) return rc;
         HIPCHK(launch_rdot<T>(bel_.as<T>(), S_pad_, (int)B_, mv, windows ? btl_.as<int32_t>() : nullptr,
                               windows ? btc_.as<int32_t>() : nullptr, prd_.as<double>(), side));
     }
     // (run_fetch's provisional pipeline: its counters are cleared here, beside the projection, not in front of its kernels)
     const bool early_wanted = windows && !q_only_ && early_rows_ != nullptr && !(flags & PBVI_BELIEF_DOMINANCE) && early_cap_ >= B_ && !no_side;
     if (early_wanted) {
-        if ((rc = e_cnt_.ensure(4 * sizeof(int), &bytes_))) return rc;
+        if ((rc = e_cnt_.ensure(4 * sizeof(int)))) return rc;
         HIPCHK(hipMemsetAsync(e_cnt_.p, 0, 4 * sizeof(int), side));
     }
     HIPCHK(hipEventRecord(ev_join_, side));
@@ -3614,7 +3632,7 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
         // beside the refinement, on the side stream: a wave per belief row over V scores is 0.1 ms that nothing in this
         // call waits for (the slabs stay as they are until the next GEMM; K5 is not run with this formulation's extras
         // pending -- it joins first, below)
-        if ((rc = vmax_bk_.ensure((size_t)B_ * sizeof(double), &bytes_))) return rc;
+        if ((rc = vmax_bk_.ensure((size_t)B_ * sizeof(double)))) return rc;
         hipStream_t xs = no_side ? stream_ : stream2_;
         if (xs != stream_) {
             HIPCHK(hipEventRecord(ev_xr_[0], stream_));
@@ -3636,19 +3654,10 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
     const int64_t f64_pairs = sc.f64_pairs;
     if (st && (windows || f64_pairs > 0)) {
         n_kcount = windows ? (size_t)plan.tiles_m * plan.tiles_n : (size_t)f64_pairs;
-        if (n_kcount > kc_pin_cap_) {
-            if (kc_pin_) (void)hipHostFree(kc_pin_);         // (no copy into it is pending: every call ends synchronised)
-            kc_pin_ = nullptr;
-            kc_pin_cap_ = 0;
-            const size_t want = std::max<size_t>(n_kcount * 2, 4096);
-            if (hipHostMalloc((void**)&kc_pin_, want * sizeof(int), hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError();
-                kc_pin_ = nullptr;
-                FAIL(PBVI_ENOMEM, "pinned buffer for the list lengths");
-            }
-            kc_pin_cap_ = want;
-        }
-        h_kcount = kc_pin_;                                  // (the copy itself is enqueued behind the refinement, below)
+        // (no copy into it is pending: every call ends synchronised)
+        if (!kc_pin_.ensure(n_kcount * sizeof(int), std::max<size_t>(n_kcount * 2, 4096) * sizeof(int)))
+            FAIL(PBVI_ENOMEM, "pinned buffer for the list lengths");
+        h_kcount = kc_pin_.as<int>();                                 // (the copy itself is enqueued behind the refinement, below)
     }
     // fp64 re-decision of near-ties.  The per-entry pass hands entries with many tied candidates on to grid-wide
     // passes whose launch needs the host to know how many there are -- a read-back in the middle of the pipeline
@@ -3665,20 +3674,19 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
     early_used_ = false;
     if (early_wanted) {
         int rc2;
-        if ((rc2 = e_bv_.ensure((size_t)pairs * sizeof(int32_t), &bytes_))) return rc2;
-        if ((rc2 = e_rdot_.ensure((size_t)B_ * A_ * 2 * sizeof(double), &bytes_))) return rc2;
-        if ((rc2 = e_act_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc2;
-        if ((rc2 = e_ares_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc2;
-        if ((rc2 = e_bres_.ensure((size_t)pairs * sizeof(int32_t), &bytes_))) return rc2;
-        if ((rc2 = e_rep_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc2;
-        if ((rc2 = e_uniq_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc2;
-        if ((rc2 = e_inv_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc2;
-        if ((rc2 = e_slotd_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc2;
-        if ((rc2 = e_slot_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc2;
-        if ((rc2 = e_cnt_.ensure(4 * sizeof(int), &bytes_))) return rc2;
-        if ((rc2 = e_out_.ensure((size_t)B_ * S_ * sizeof(T), &bytes_))) return rc2;
-        for (hipEvent_t& ev : ev_early_)
-            if (!ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        if ((rc2 = e_bv_.ensure((size_t)pairs * sizeof(int32_t)))) return rc2;
+        if ((rc2 = e_rdot_.ensure((size_t)B_ * A_ * 2 * sizeof(double)))) return rc2;
+        if ((rc2 = e_act_.ensure((size_t)B_ * sizeof(int32_t)))) return rc2;
+        if ((rc2 = e_ares_.ensure((size_t)B_ * sizeof(int32_t)))) return rc2;
+        if ((rc2 = e_bres_.ensure((size_t)pairs * sizeof(int32_t)))) return rc2;
+        if ((rc2 = e_rep_.ensure((size_t)B_ * sizeof(int32_t)))) return rc2;
+        if ((rc2 = e_uniq_.ensure((size_t)B_ * sizeof(int32_t)))) return rc2;
+        if ((rc2 = e_inv_.ensure((size_t)B_ * sizeof(int32_t)))) return rc2;
+        if ((rc2 = e_slotd_.ensure((size_t)B_ * sizeof(int32_t)))) return rc2;
+        if ((rc2 = e_slot_.ensure((size_t)B_ * sizeof(int32_t)))) return rc2;
+        if ((rc2 = e_cnt_.ensure(4 * sizeof(int)))) return rc2;
+        if ((rc2 = e_out_.ensure((size_t)B_ * S_ * sizeof(T)))) return rc2;
+        for (hipEvent_t& ev : ev_early_) HIPCHK(new_event(&ev, hipEventDisableTiming, "hipEventDestroy(early)"));
         // The provisional decision itself is 40 us of small kernels: they run HERE, on the main stream in front of the
         // refinement (which rewrites best_v / best_score in place), and only the copy -- 8 MB over PCIe, ~150 us, few blocks
         // -- goes to the side stream.  (Snapshots of the three arrays + the whole provisional pipeline beside the
@@ -3709,9 +3717,7 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
         // link's rate (54.7 GB/s, profiles/microbench/pcie_store.hip) -- but beside it k_refine took 0.24 ms instead of 0.14
         // whatever its grid (8 .. 1024 blocks): the runtime's copy disturbs the refinement far less (0.15 ms).
         early_dma_pending_ = true;
-        int* f = pinned_flag();
-        if (!f) FAIL(PBVI_ENOMEM, "run_fetch: pinned flag");
-        HIPCHK(hipMemcpyAsync(f + 8, e_cnt_.p, sizeof(int), hipMemcpyDeviceToHost, es));
+        HIPCHK(hipMemcpyAsync(&words().provisional, e_cnt_.p, sizeof(int), hipMemcpyDeviceToHost, es));
         HIPCHK(hipEventRecord(ev_early_[0], es));
         early_used_ = true;
     }
@@ -3732,9 +3738,7 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
         }
         // the counts land in two of the engine's pinned flag words -- not in the staging buffer: run_fetch stages results
         // through that one before the counts are read, and out_add may reset or reallocate it
-        rf_counts_ = pinned_flag();
-        if (!rf_counts_) FAIL(PBVI_ENOMEM, "backup_run: pinned flag");
-        rf_counts_ += 24;
+        rf_counts_ = words().deferred;
         rf_counts_[0] = rf_counts_[1] = 0;
         static const bool no_spec = getenv("PBVI_NO_SPECULATION") != nullptr;      // debug / A-B only
         // (not with the belief-dominance test: its own value-max refinement re-uses the work-list buffers, so the
@@ -3744,7 +3748,7 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
         HIPCHK((launch_refine_scan<T, TS>(true, sv, (int)V_, AO, (int)pairs, queue_.as<int32_t>(), qcount, bel_.as<T>(), S_pad_,
                                           alpha_.as<T>(), S_pad_, mv, gamma, btl_.as<int32_t>(), btc_.as<int32_t>(),
                                           nzB_.as<uint8_t>(), best_v_.as<int32_t>(), best_score_.as<double>(), err_.as<double>(),
-                                          counters_.as<int>() + 4, work, rf_counts_, stream_)));
+                                          counters_.as<int>() + CNT_REFINE_CAND, work, rf_counts_, stream_)));
         if (!speculate && work.items_v != nullptr) {
             HIPCHK(hipStreamSynchronize(stream_));
             last_deferred_nothing_ = rf_counts_[0] == 0 && rf_counts_[1] == 0;
@@ -3755,44 +3759,43 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
     }
     if (early_used_ && early_dma_pending_) {   // the refinement is enqueued: now the host can wait for the provisional count
         HIPCHK(hipEventSynchronize(ev_early_[0]));
-        const int np = h_flag_[8];
+        const int np = words().provisional;
         if (np > 0)
             HIPCHK(hipMemcpyAsync(early_rows_, e_out_.p, (size_t)np * S_ * sizeof(T), hipMemcpyDeviceToHost, stream2_));
         HIPCHK(hipEventRecord(ev_early_[1], stream2_));
         early_dma_pending_ = false;
     }
     if (h_kcount != nullptr)   // statistics: not in front of the provisional decision and the refinement (K5 re-uses kcount_ later)
-        HIPCHK(hipMemcpyAsync(kc_pin_, scorer.kcount_.p, n_kcount * sizeof(int), hipMemcpyDeviceToHost, stream_));
+        HIPCHK(hipMemcpyAsync(kc_pin_.p, scorer.kcount_.p, n_kcount * sizeof(int), hipMemcpyDeviceToHost, stream_));
     HIPCHK(hipEventRecord(ev_[4], stream_));
     const int32_t* perm = sorted_ ? perm_.as<int32_t>() : nullptr;
     if (q_only_) {   // pbvi_q_values: best_v is final; exact Q of every (belief, action) from it, and nothing else
         if (xr_pending) HIPCHK(hipStreamWaitEvent(stream_, ev_xr_[1], 0));       // (the side stream still reads this call's slabs)
         if (!btl_valid_) {   // pure fp64 scoring: k_dead did not run; the same lists from the beliefs alone
-            if ((rc = btl_.ensure((size_t)B_ * k_tiles * sizeof(int32_t), &bytes_))) return rc;
-            if ((rc = btc_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
+            if ((rc = btl_.ensure((size_t)B_ * k_tiles * sizeof(int32_t)))) return rc;
+            if ((rc = btc_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
             HIPCHK(launch_belief_tiles<T>(bel_.as<T>(), S_pad_, (int)B_, S_, k_tiles, btl_.as<int32_t>(), btc_.as<int32_t>(), stream_));
             btl_valid_ = true;
         }
-        if ((rc = q_.ensure((size_t)B_ * A_ * sizeof(double), &bytes_))) return rc;
-        if ((rc = q_res_.ensure((size_t)B_ * A_ * sizeof(double), &bytes_))) return rc;
-        if ((rc = q_act_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
-        if (q_want_best_ && (rc = best_res_.ensure((size_t)pairs * sizeof(int32_t), &bytes_))) return rc;
+        if ((rc = q_.ensure((size_t)B_ * A_ * sizeof(double)))) return rc;
+        if ((rc = q_res_.ensure((size_t)B_ * A_ * sizeof(double)))) return rc;
+        if ((rc = q_act_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+        if (q_want_best_ && (rc = best_res_.ensure((size_t)pairs * sizeof(int32_t)))) return rc;
         HIPCHK(launch_q_exact<T>(bel_.as<T>(), S_pad_, (int)B_, alpha_.as<T>(), S_pad_, (int)V_, mv, gamma, btl_.as<int32_t>(),
                                  btc_.as<int32_t>(), best_v_.as<int32_t>(), windows ? dead_.as<uint8_t>() : nullptr, perm,
                                  q_.as<double>(), q_res_.as<double>(), q_act_.as<int32_t>(),
                                  q_want_best_ ? best_res_.as<int32_t>() : nullptr, stream_));
-        int* f = pinned_flag();
-        if (!f) FAIL(PBVI_ENOMEM, "q_values: pinned flag");
-        HIPCHK(hipMemcpyAsync(f + 16, counters_.p, 8 * sizeof(int), hipMemcpyDeviceToHost, stream_));
+        PinnedWords* w = &words();
+        HIPCHK(hipMemcpyAsync(w->counters, counters_.p, sizeof(w->counters), hipMemcpyDeviceToHost, stream_));
         if constexpr (screened) {
-            if (scr_flag_.p) HIPCHK(hipMemcpyAsync(f + 1, scr_flag_.p, sizeof(int), hipMemcpyDeviceToHost, stream_));
+            if (scr_flag_.p) HIPCHK(hipMemcpyAsync(&w->screen_overflow, scr_flag_.p, sizeof(int), hipMemcpyDeviceToHost, stream_));
         }
         HIPCHK(hipStreamSynchronize(stream_));
-        if (windows && dead_count_ < 0) dead_count_ = f[16 + 5];    // k_dead counted this block's dead triples in this call
+        if (windows && dead_count_ < 0) dead_count_ = w->counters[CNT_DEAD];    // k_dead counted this block's dead triples in this call
         return PBVI_OK;
     }
-    int* ucount = counters_.as<int>() + 3;
-    int h_cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // all counters in the one read-back that precedes the final sync
+    int* ucount = counters_.as<int>() + CNT_UNIQUE;
+    int h_cnt[CNT_SLOTS] = {0, 0, 0, 0, 0, 0, 0, 0};      // all counters in the one read-back that precedes the final sync
     auto later_stages = [&]() -> int {
         bool publish = false;
         // K4: action
@@ -3811,8 +3814,8 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
         // results to the caller's belief order, then K6: dedup by (a*, v*) key
         if (sorted_) {
             int rc2;
-            if ((rc2 = action_res_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc2;
-            if ((rc2 = best_res_.ensure((size_t)pairs * sizeof(int32_t), &bytes_))) return rc2;
+            if ((rc2 = action_res_.ensure((size_t)B_ * sizeof(int32_t)))) return rc2;
+            if ((rc2 = best_res_.ensure((size_t)pairs * sizeof(int32_t)))) return rc2;
             hipLaunchKernelGGL(k_unpermute, dim3((unsigned)B_), dim3(64), 0, stream_, (int)B_, AO, perm, action_.as<int32_t>(),
                                best_v_.as<int32_t>(), action_res_.as<int32_t>(), best_res_.as<int32_t>());
             HIPCHK(hipGetLastError());
@@ -3836,12 +3839,10 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
                                uniq_.as<int32_t>(), res_action_, res_best_, e_uniq_.as<int32_t>(), pa, pb, e_cnt_.as<int>(),
                                (int)early_cap_, e_slot_.as<int32_t>(), out_.as<T>(), (T*)early_rows_, (int64_t)S_);
             HIPCHK(hipGetLastError());
-            int* f = pinned_flag();
-            if (!f) FAIL(PBVI_ENOMEM, "run_fetch: pinned flag");
             publish = rf_dst_.slot != nullptr && !(flags & PBVI_BELIEF_DOMINANCE) && rf_dst_.best == nullptr && rf_dst_.keep == nullptr &&
                       is_pinned_host_pointer(rf_dst_.slot) && is_pinned_host_pointer(rf_dst_.index) &&
                       is_pinned_host_pointer(rf_dst_.action);
-            if (!publish) HIPCHK(hipMemcpyAsync(f + 4, e_cnt_.p, 3 * sizeof(int), hipMemcpyDeviceToHost, stream_));
+            if (!publish) HIPCHK(hipMemcpyAsync(words().early, e_cnt_.p, sizeof(words().early), hipMemcpyDeviceToHost, stream_));
         }
         HIPCHK(hipEventRecord(ev_[6], stream_));
         if (xr_pending) {                            // the extra rows' maxima read the slabs K5's GEMM is about to overwrite
@@ -3859,15 +3860,14 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
         }
         rf_dst_.queued = false;
         if (publish) {                                       // run_fetch into page-locked arrays: one kernel stores everything small
-            int* f = pinned_flag();
             hipLaunchKernelGGL(k_publish, dim3((unsigned)((B_ + 255) / 256)), dim3(256), 0, stream_, (int)B_, e_slot_.as<int32_t>(),
                                inv_.as<int32_t>(), res_action_, (int32_t*)rf_dst_.slot, (int32_t*)rf_dst_.index, (int32_t*)rf_dst_.action,
-                               counters_.as<int>(), e_cnt_.as<int>(), (screened && scr_flag_.p) ? scr_flag_.as<int>() : nullptr, f);
+                               counters_.as<int>(), e_cnt_.as<int>(), (screened && scr_flag_.p) ? scr_flag_.as<int>() : nullptr, &words());
             HIPCHK(hipGetLastError());
             rf_dst_.queued = true;
             HIPCHK(hipEventRecord(ev_[7], stream_));
             HIPCHK(hipStreamSynchronize(stream_));
-            std::memcpy(h_cnt, f + 16, sizeof(h_cnt));
+            std::memcpy(h_cnt, words().counters, sizeof(h_cnt));
             return PBVI_OK;
         }
         if (early_used_ && rf_dst_.slot != nullptr) {        // run_fetch: slots, index, actions (best, keep) with this read-back
@@ -3880,21 +3880,20 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
             if (rf_dst_.keep && (rc2 = out_add(rf_dst_.keep, keep_.p, (size_t)B_))) return rc2;
             rf_dst_.queued = true;
         }
-        int* fc = pinned_flag();                             // (page-locked words: a copy into the stack array is staged by the runtime)
-        HIPCHK(hipMemcpyAsync(fc ? (void*)(fc + 16) : (void*)h_cnt, counters_.p, sizeof(h_cnt), hipMemcpyDeviceToHost, stream_));
+        // (into the page-locked words: a copy into the stack array is staged by the runtime)
+        HIPCHK(hipMemcpyAsync(words().counters, counters_.p, sizeof(h_cnt), hipMemcpyDeviceToHost, stream_));
         if constexpr (screened) {   // did an alpha value leave the fp32 range when the screen's copy was made?
-            int* f = pinned_flag();
-            if (f && scr_flag_.p) HIPCHK(hipMemcpyAsync(f + 1, scr_flag_.p, sizeof(int), hipMemcpyDeviceToHost, stream_));
+            if (scr_flag_.p) HIPCHK(hipMemcpyAsync(&words().screen_overflow, scr_flag_.p, sizeof(int), hipMemcpyDeviceToHost, stream_));
         }
         HIPCHK(hipEventRecord(ev_[7], stream_));
         HIPCHK(hipStreamSynchronize(stream_));
-        if (fc) std::memcpy(h_cnt, fc + 16, sizeof(h_cnt));
+        std::memcpy(h_cnt, words().counters, sizeof(h_cnt));
         return PBVI_OK;
     };
-    if ((rc = rep_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
-    if ((rc = uniq_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
-    if ((rc = inv_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
-    if ((rc = slot_.ensure((size_t)B_ * sizeof(int32_t), &bytes_))) return rc;
+    if ((rc = rep_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+    if ((rc = uniq_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+    if ((rc = inv_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+    if ((rc = slot_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
     if ((rc = later_stages())) return rc;
     if (speculate) {
         last_deferred_nothing_ = rf_counts_[0] == 0 && rf_counts_[1] == 0;
@@ -3902,18 +3901,18 @@ int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_
             HIPCHK(launch_refine_deferred<T>(true, (int)V_, AO, bel_.as<T>(), S_pad_, alpha_.as<T>(), S_pad_, mv, gamma,
                                              best_v_.as<int32_t>(), best_score_.as<double>(), err_.as<double>(), work,
                                              rf_counts_[0], rf_counts_[1], stream_));
-            HIPCHK(hipMemsetAsync(counters_.as<int>() + 1, 0, sizeof(int), stream_));       // aqcount
-            HIPCHK(hipMemsetAsync(counters_.as<int>() + 3, 0, sizeof(int), stream_));       // ucount (value_max's counter [2] is reset there)
+            HIPCHK(hipMemsetAsync(counters_.as<int>() + CNT_ACTION_QUEUE, 0, sizeof(int), stream_));
+            HIPCHK(hipMemsetAsync(counters_.as<int>() + CNT_UNIQUE, 0, sizeof(int), stream_));   // (value_max resets its own queue)
             if ((rc = later_stages())) return rc;
         }
     }
-    if (windows && dead_count_ < 0) dead_count_ = h_cnt[5];
+    if (windows && dead_count_ < 0) dead_count_ = h_cnt[CNT_DEAD];
     full_valid_ = false;
     res_sorted_ = sorted_;
     have_result_ = true;
     have_bk_vmax_ = use_push && !screened;
     res_B_ = B_;
-    const int h_ucount = h_cnt[3];
+    const int h_ucount = h_cnt[CNT_UNIQUE];
     res_unique_ = h_ucount;
 
     if (st) {
@@ -4048,24 +4047,22 @@ static int mdp_value_iteration(int device, int S, int A, int R, const int32_t* r
             }
         }
     HIPCHK(hipSetDevice(device));
-    int64_t bytes = 0;
-    DevBuf d_rs, d_p, d_er, d_v[2], d_rows, d_ch;
-    struct Guard {
-        DevBuf* b[7];
+    struct Guard {                                           // (in front of the buffers: they are released first)
         hipStream_t st = nullptr;
         ~Guard() {
-            for (DevBuf* x : b) x->release();
             if (st) (void)hipStreamDestroy(st);
         }
-    } guard{{&d_rs, &d_p, &d_er, &d_v[0], &d_v[1], &d_rows, &d_ch}};
+    } guard;
+    DevMem mem;
+    DevBuf d_rs{mem}, d_p{mem}, d_er{mem}, d_v[2]{{mem}, {mem}}, d_rows{mem}, d_ch{mem};
     int rc;
-    if ((rc = d_rs.ensure(n * sizeof(int32_t), &bytes))) return rc;
-    if ((rc = d_p.ensure(n * sizeof(double), &bytes))) return rc;
-    if ((rc = d_er.ensure((size_t)S * A * sizeof(double), &bytes))) return rc;
-    if ((rc = d_v[0].ensure((size_t)S * sizeof(double), &bytes))) return rc;
-    if ((rc = d_v[1].ensure((size_t)S * sizeof(double), &bytes))) return rc;
-    if ((rc = d_rows.ensure((size_t)S * A * sizeof(double), &bytes))) return rc;
-    if ((rc = d_ch.ensure((size_t)std::max(horizon, 1) * sizeof(double), &bytes))) return rc;
+    if ((rc = d_rs.ensure(n * sizeof(int32_t)))) return rc;
+    if ((rc = d_p.ensure(n * sizeof(double)))) return rc;
+    if ((rc = d_er.ensure((size_t)S * A * sizeof(double)))) return rc;
+    if ((rc = d_v[0].ensure((size_t)S * sizeof(double)))) return rc;
+    if ((rc = d_v[1].ensure((size_t)S * sizeof(double)))) return rc;
+    if ((rc = d_rows.ensure((size_t)S * A * sizeof(double)))) return rc;
+    if ((rc = d_ch.ensure((size_t)std::max(horizon, 1) * sizeof(double)))) return rc;
     HIPCHK(hipStreamCreateWithFlags(&guard.st, hipStreamNonBlocking));
     hipStream_t st = guard.st;
     HIPCHK(hipMemcpyAsync(d_rs.p, h_rs.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -4128,6 +4125,7 @@ int64_t pbvi_debug_alloc_limit(int64_t mb) {
     pbvi::DevBuf::limit_bytes() = mb < 0 ? -1 : mb << 20;
     return prev < 0 ? -1 : prev >> 20;
 }
+int64_t pbvi_debug_live_bytes(void) { return pbvi::DevMem::live.load(); }
 
 
 int pbvi_device_count(void) {

@@ -33,7 +33,7 @@ EXPORTS = [
     'pbvi_value_max_store', 'pbvi_belief_store_count', 'pbvi_alpha_store_count', 'pbvi_set_value_max_exact', 'pbvi_alpha_layout',
     'pbvi_belief_walk_keys', 'pbvi_backup_fetch_value_max',
     'pbvi_backup_fetch_compact', 'pbvi_host_alloc', 'pbvi_host_free', 'pbvi_debug_gemm_dense',
-    'pbvi_backup_fetch_exchange_padded', 'pbvi_assemble_rows_store', 'pbvi_exchange_merge', 'pbvi_backup_run_fetch', 'pbvi_debug_alloc_limit', 'pbvi_engine_after_oom', 'pbvi_set_f64_screen', 'pbvi_set_fused_projection', 'pbvi_backup_fetch_row_hashes', 'pbvi_set_score_split',
+    'pbvi_backup_fetch_exchange_padded', 'pbvi_assemble_rows_store', 'pbvi_exchange_merge', 'pbvi_backup_run_fetch', 'pbvi_debug_alloc_limit', 'pbvi_debug_live_bytes', 'pbvi_engine_after_oom', 'pbvi_set_f64_screen', 'pbvi_set_fused_projection', 'pbvi_backup_fetch_row_hashes', 'pbvi_set_score_split',
     'pbvi_set_gamma_tiling', 'pbvi_gamma_tiling_plan', 'pbvi_q_values', 'pbvi_prune_dominated_masked',
     'pbvi_rollout', 'pbvi_infotaxis', 'pbvi_rollout_infotaxis',
 ]
@@ -144,6 +144,7 @@ def load_library(path: str = LIB_PATH):
         'pbvi_backup_run_fetch': (C.c_int, [vp, C.c_double, C.c_int, sp, vp, C.c_int64, i32p, i32p, i32p, i32p, u8p,
                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         'pbvi_debug_alloc_limit': (C.c_int64, [C.c_int64]),
+        'pbvi_debug_live_bytes': (C.c_int64, []),
         'pbvi_engine_after_oom': (C.c_int, [vp]),
         'pbvi_exchange_merge': (C.c_int64, [vp, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int64, vp, vp, vp, vp]),
         'pbvi_set_tie_window': (C.c_int, [vp, C.c_double]),
@@ -166,6 +167,12 @@ def debug_alloc_limit(mb: int) -> int:
     """Cap (MiB; < 0: none) on the device bytes one engine may hold (``pbvi_debug_alloc_limit``): a deterministic
     out-of-memory for tests of the ``MemoryError`` contract of ``PBVI_Solver.solve``.  Returns the previous cap."""
     return int(load_library().pbvi_debug_alloc_limit(int(mb)))
+
+
+def debug_live_bytes() -> int:
+    """Bytes of device buffers the library holds right now over all engines of the process (``pbvi_debug_live_bytes``):
+    equal to ``device_bytes`` of the one engine alive, 0 once every engine is closed."""
+    return int(load_library().pbvi_debug_live_bytes())
 
 
 def gamma_tiling_plan(S: int, A: int, O: int, V: int, B: int, dtype: str = 'f32', budget_bytes: int = 0,
