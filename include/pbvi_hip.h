@@ -632,6 +632,21 @@ int64_t pbvi_debug_live_bytes(void);
  * BASELINE.json is measured this way (results are unchanged: skipped tiles only ever add +0).  Also enabled by
  * PBVI_GEMM_DENSE=1 in the environment.  Process-wide; returns the previous state. */
 int pbvi_debug_gemm_dense(int enable);
+/* Tests only: which K-step schedule the split score GEMM (bf16 MFMAs) runs.  0 (default): each MFMA group
+ * reads its LDS fragments right before its MFMAs; 1: fragment reads one MFMA group ahead of their use, behind counted
+ * waits.  Same plan, lists, LDS image and accumulation order, so the slabs are bit-identical; the test holds them so.
+ * Other values change nothing.  Process-wide; returns the previous schedule.  Not a tuning knob: time a schedule in a
+ * build of its own. */
+int pbvi_debug_split_schedule(int schedule);
+/* Tests only: the raw score slab buffer as the last backup's score GEMM left it (partial slabs in the GEMM plan's layout,
+ * padding and parts no block wrote included), copied to host memory.  out == NULL: returns the buffer's size in bytes;
+ * else copies that many bytes to out (cap_bytes: the room there) and returns the count.  A stage that runs a GEMM of its
+ * own after the scores (belief dominance, the value maxima) re-uses the buffer.  PBVI_EINVAL (negative) when no score GEMM
+ * has run or cap_bytes is too small. */
+int64_t pbvi_debug_slabs(pbvi_engine_t* e, void* out, int64_t cap_bytes);
+/* Tests only: set every byte of that buffer to `byte` (its low 8 bits), so that a test can tell what the next score GEMM
+ * wrote from what an earlier one left there.  PBVI_EINVAL when no score GEMM has run. */
+int pbvi_debug_slabs_fill(pbvi_engine_t* e, int byte);
 
 /* Bytes of device memory currently held by the handle. */
 int64_t pbvi_device_bytes(const pbvi_engine_t* e);

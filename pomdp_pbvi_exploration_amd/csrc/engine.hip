@@ -895,6 +895,8 @@ class EngineBase {
     virtual int walk_keys(int64_t n, uint64_t* out_keys) = 0;
     virtual int backup_value_max(double* out_value) = 0;
     virtual int q_values(double gamma, double* out_q, int32_t* out_action, int32_t* out_best) = 0;
+    virtual int64_t debug_slabs(void* out, int64_t cap_bytes) = 0;
+    virtual int debug_slabs_fill(int byte) = 0;
     // source: the policy of the step loop (RolloutSource); alpha_actions and gamma are read by the sources that need them
     virtual int rollout(int source, const int32_t* alpha_actions, double gamma, const int32_t* start_states,
                         const uint8_t* end_mask, uint64_t first_sim_id, uint64_t seed, int64_t T, int32_t* out_states,
@@ -1045,6 +1047,7 @@ class EngineT : public EngineBase {
                                                      // work that the GEMM waits for must not queue behind k_dead's 100 us)
     hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr, ev_lists_ = nullptr, ev_xr_[2] = {nullptr, nullptr};
     GemmPlan plan_ = {};
+    int64_t slab_bytes_ = 0;                  // what the last score_gemm asked of slabs_ (debug_slabs)
     hipEvent_t ev_[9] = {};
     hipEvent_t ev_pg_[2] = {};                       // around the dense projection's GEMM kernel
     bool have_result_ = false, res_sorted_ = false;
@@ -1761,6 +1764,27 @@ class EngineT : public EngineBase {
         } else {
             HIPCHK(hipStreamSynchronize(stream_));
         }
+        return PBVI_OK;
+    }
+
+    // The raw slab buffer as the last score_gemm's kernel left it (pbvi_debug_slabs); out == nullptr: the size only
+    int64_t debug_slabs(void* out, int64_t cap_bytes) override {
+        if (slab_bytes_ <= 0 || slabs_.p == nullptr || (int64_t)slabs_.cap < slab_bytes_)
+            FAIL(PBVI_EINVAL, "debug_slabs: no score GEMM has run");
+        if (!out) return slab_bytes_;
+        if (cap_bytes < slab_bytes_) FAIL(PBVI_EINVAL, "debug_slabs: the output array is smaller than the slab buffer");
+        HIPCHK(hipSetDevice(device_));
+        HIPCHK(hipMemcpyAsync(out, slabs_.p, (size_t)slab_bytes_, hipMemcpyDeviceToHost, stream_));
+        HIPCHK(hipStreamSynchronize(stream_));
+        return slab_bytes_;
+    }
+    // Every byte of that buffer set to `byte` (pbvi_debug_slabs_fill): what a later GEMM does not write stays so
+    int debug_slabs_fill(int byte) override {
+        if (slab_bytes_ <= 0 || slabs_.p == nullptr || (int64_t)slabs_.cap < slab_bytes_)
+            FAIL(PBVI_EINVAL, "debug_slabs_fill: no score GEMM has run");
+        HIPCHK(hipSetDevice(device_));
+        HIPCHK(hipMemsetAsync(slabs_.p, byte & 0xff, (size_t)slab_bytes_, stream_));
+        HIPCHK(hipStreamSynchronize(stream_));
         return PBVI_OK;
     }
 
@@ -2856,6 +2880,7 @@ int EngineT<T>::score_gemm(const T* Y, int64_t rows_y, const uint8_t* nzB, int G
         plan_ = make_gemm_plan((int)m_pad, (int)n_pad, S_pad_);
         const size_t pairs = (size_t)plan_.tiles_m * plan_.tiles_n;
         if ((rc = slabs_.ensure((size_t)plan_.c_floats * sizeof(float)))) return rc;
+        slab_bytes_ = (int64_t)plan_.c_floats * (int64_t)sizeof(float);
         if ((rc = klist_.ensure(pairs * plan_.k_tiles * sizeof(int)))) return rc;
         if ((rc = kcount_.ensure(pairs * sizeof(int)))) return rc;
         if ((rc = nchunks_.ensure(pairs * sizeof(int)))) return rc;
@@ -2880,6 +2905,7 @@ int EngineT<T>::score_gemm(const T* Y, int64_t rows_y, const uint8_t* nzB, int G
         const int kt32s = S_pad_ / GEMM_BK;
         const int split = f64_uses_mfma(m_rows, rows_y) ? gemm_f64_split((int)m_rows, (int)rows_y, kt32s) : 1;
         if ((rc = slabs_.ensure((size_t)split * m_rows * rows_y * sizeof(T)))) return rc;
+        slab_bytes_ = (int64_t)split * m_rows * rows_y * (int64_t)sizeof(T);
         f64_pairs_ = 0;
         if (!f64_uses_mfma(m_rows, rows_y)) {
             HIPCHK(launch_gemm_nt_simple<T>(X, S_pad_, Y, S_pad_, slabs_.as<T>(), (int)rows_y, (int)m_rows, (int)rows_y,
@@ -4364,6 +4390,15 @@ void pbvi_host_free(void* p) {
     if (p && hipHostFree(p) != hipSuccess) (void)hipGetLastError();
 }
 int pbvi_debug_gemm_dense(int enable) { return pbvi::set_gemm_force_dense(enable); }
+int pbvi_debug_split_schedule(int schedule) { return pbvi::set_gemm_split_schedule(schedule); }
+int64_t pbvi_debug_slabs(pbvi_engine_t* e, void* out, int64_t cap_bytes) {
+    NEED(e);
+    return e->impl->debug_slabs(out, cap_bytes);
+}
+int pbvi_debug_slabs_fill(pbvi_engine_t* e, int byte) {
+    NEED(e);
+    return e->impl->debug_slabs_fill(byte);
+}
 int pbvi_backup(pbvi_engine_t* e, const void* beliefs, int64_t B, double gamma, int flags, void* out_alpha,
                 int32_t* out_action, int32_t* out_best_alpha, uint8_t* out_keep, pbvi_stats_t* stats) {
     NEED(e);

@@ -772,6 +772,11 @@ __device__ __forceinline__ void split_store(float* lop, int row, int kg, const f
     *(i32x4*)(lop + row * GEMM_BK + ((4 + kg) ^ sw) * 4) = lo;
 }
 
+// K-step schedules of tile_run_split (pbvi_debug_split_schedule).  The parent one reads each group's fragments right
+// before its MFMAs and is the default; the pipelined one reads them a group ahead behind counted waits.  Bit-identical
+// slabs.  Measurements of both: profiles/split_lds_pipeline.md.
+constexpr int SPLIT_SCHED_PARENT = 0, SPLIT_SCHED_PIPELINED = 1;
+
 // Fragments of one k-half of the staged tile pair: the hi and lo chunks of the wave's 4 A rows and 2 B rows
 struct SplitFrag {
     i32x4 ah[4], al[4], bh[2], bl[2];
@@ -811,6 +816,71 @@ __device__ __forceinline__ void split_group(const TileThread& t, const float* ld
         }
 }
 
+// The pipelined schedule's fragment slots: two A slots (4 rows) and two B slots (2 rows); which part sits in which slot
+// is fixed at compile time (see tile_run_split).
+struct SplitSlots {
+    i32x4 a[2][4], b[2][2];
+};
+// The fragment reads of the pipelined schedule are inline assembly, so that the waits in front of the MFMA groups can
+// count them: the compiler drains lgkmcnt to 0 at every use of an LDS read while an LDS-DMA load is in flight, which in
+// this loop is always.  LDS operations retire in order; split_wait_*(N, ..) lets the N youngest stay in flight and takes the
+// registers it releases as operands, so nothing reads or copies them earlier.  (A scalar load that shares the counter
+// and returns out of order can only make such a wait stricter.)
+__device__ __forceinline__ void lds_read16(i32x4& dst, uint32_t addr, int offset) {
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(offset) : "memory");
+}
+__device__ __forceinline__ uint32_t lds_addr(const float* p) {
+    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) float*)p;
+}
+// The hi (lo = false) or lo chunks of k-half kk of the wave's A rows / B rows: the same LDS words split_group reads.
+// All six rows of a lane share i = lane & 31 and with it the swizzle, so an address is a wave-uniform part (buffer,
+// operand, the wave's first row) plus one of four lane parts that serve both operands, plus an immediate per row.
+__device__ __forceinline__ uint32_t split_lane_part(const TileThread& t, int kk, bool lo) {
+    const int c = (lo ? 4 : 0) + 2 * kk + t.h, sw = (t.i >> 1) & 7;
+    return (uint32_t)(t.i * GEMM_BK + (c ^ sw) * 4) * 4u;
+}
+__device__ __forceinline__ void split_read_a(const TileThread& t, const float* lds, int buf, int kk, bool lo, i32x4 (&a)[4]) {
+    const uint32_t addr = lds_addr(lds + buf * 2 * TILE_FLOATS + t.wr * 128 * GEMM_BK) + split_lane_part(t, kk, lo);
+    lds_read16(a[0], addr, 0);
+    lds_read16(a[1], addr, 32 * GEMM_BK * 4);
+    lds_read16(a[2], addr, 64 * GEMM_BK * 4);
+    lds_read16(a[3], addr, 96 * GEMM_BK * 4);
+}
+__device__ __forceinline__ void split_read_b(const TileThread& t, const float* lds, int buf, int kk, bool lo, i32x4 (&b)[2]) {
+    const uint32_t addr = lds_addr(lds + buf * 2 * TILE_FLOATS + TILE_FLOATS + t.wc * 64 * GEMM_BK) + split_lane_part(t, kk, lo);
+    lds_read16(b[0], addr, 0);
+    lds_read16(b[1], addr, 32 * GEMM_BK * 4);
+}
+// Wait until at most N LDS operations are in flight, for an A slot, a B slot or both
+#define PBVI_SPLIT_WAIT(N) "s_waitcnt lgkmcnt(" #N ")"
+#define PBVI_SPLIT_A(a) "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3])
+#define PBVI_SPLIT_B(b) "+v"(b[0]), "+v"(b[1])
+// (the MFMAs touch no memory, so only a scheduling barrier keeps them behind the wait)
+#define split_wait_ab(N, a, b)                                                            \
+    do {                                                                                  \
+        asm volatile(PBVI_SPLIT_WAIT(N) : PBVI_SPLIT_A(a), PBVI_SPLIT_B(b)::"memory");    \
+        __builtin_amdgcn_sched_barrier(0);                                                \
+    } while (0)
+#define split_wait_a(N, a)                                              \
+    do {                                                                \
+        asm volatile(PBVI_SPLIT_WAIT(N) : PBVI_SPLIT_A(a)::"memory");   \
+        __builtin_amdgcn_sched_barrier(0);                              \
+    } while (0)
+#define split_wait_b(N, b)                                              \
+    do {                                                                \
+        asm volatile(PBVI_SPLIT_WAIT(N) : PBVI_SPLIT_B(b)::"memory");   \
+        __builtin_amdgcn_sched_barrier(0);                              \
+    } while (0)
+// One term over the wave's 8 blocks, in split_group's block order
+__device__ __forceinline__ void split_mfma8(const i32x4 (&a)[4], const i32x4 (&b)[2], f32x16 (&acc)[4][2]) {
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[mi]), __builtin_bit_cast(bf16x8, b[ni]),
+                                                                  acc[mi][ni], 0, 0, 0);
+}
+
 // Multiply list entries [i0, i1) of one pair.  Aplane: the belief rows' split plane (split_bf16.h), staged by LDS-DMA
 // exactly like an fp32 operand (tile_stage's source swizzle), so the A image needs no register pass.  gen: the B tile is
 // generated (rsrow / rtorow: the group's successor and RTO rows; arow0: alpha row of this thread's first staging row;
@@ -824,6 +894,7 @@ __device__ __forceinline__ void split_group(const TileThread& t, const float* ld
 //         B rows 0-127 | kk1 t1 | B rows 128-255 | kk1 t2 | barrier
 //   else: B rows, A DMA | kk0 t0 | kk0 t1 | kk0 t2 | kk1 t0 | wait B rows; B rows 0-127 | kk1 t1 | B rows 128-255 | kk1 t2 |
 //         barrier
+template <int SCHED>
 __device__ __forceinline__ void tile_run_split(const TileThread& t, float* lds, const float* Aplane, int lda, const float* Bblk,
                                                int ldb, bool gen, const int32_t* __restrict__ rsrow,
                                                const float* __restrict__ rtorow, const float* __restrict__ arow0,
@@ -896,6 +967,17 @@ __device__ __forceinline__ void tile_run_split(const TileThread& t, float* lds, 
         else
             split_store(lb, it * 128 + r0, kg, xb[it][0], xb[it][1]);
     };
+    // The next tile's B operand has arrived: split and store its rows 0-127.  The waits take the loaded registers as
+    // operands, so nothing copies them before they arrive; a wait must not depend on a run-time condition (two asm
+    // statements would get operand copies placed ahead of the wait).
+    auto wait_and_store_b0 = [&](int buf) {
+        if (gen)                                          // alphas + weights in; the indices and the DMA may not be
+            asm volatile("s_waitcnt vmcnt(6)" : "+v"(xb[0][0]), "+v"(xb[0][1]), "+v"(xb[1][0]), "+v"(xb[1][1]), "+v"(w[0]),
+                         "+v"(w[1])::"memory");
+        else                                              // the B rows in; the DMA may not be
+            asm volatile("s_waitcnt vmcnt(4)" : "+v"(xb[0][0]), "+v"(xb[0][1]), "+v"(xb[1][0]), "+v"(xb[1][1])::"memory");
+        store_b(buf, 0);
+    };
     // first tile of the segment: nothing to overlap with
     {
         const int e0 = kl[i0];
@@ -936,24 +1018,50 @@ __device__ __forceinline__ void tile_run_split(const TileThread& t, float* lds, 
             stage_a(buf ^ 1, k_next);
             if (it + 3 < i1) k_after2 = kl[it + 3];
         }
-        SplitFrag f;
-        split_group(t, lds, buf, 0, 0, f, acc);
-        split_group(t, lds, buf, 0, 1, f, acc);
-        split_group(t, lds, buf, 0, 2, f, acc);
-        split_group(t, lds, buf, 1, 0, f, acc);
-        // The waits take the loaded registers as operands, so nothing copies them before they arrive; a wait must not
-        // depend on a run-time condition (two asm statements would get operand copies placed ahead of the wait).
-        if (more) {
-            if (gen)                                      // alphas + weights in; the indices and the DMA may not be
-                asm volatile("s_waitcnt vmcnt(6)" : "+v"(xb[0][0]), "+v"(xb[0][1]), "+v"(xb[1][0]), "+v"(xb[1][1]), "+v"(w[0]),
-                             "+v"(w[1])::"memory");
-            else                                          // the B rows in; the DMA may not be
-                asm volatile("s_waitcnt vmcnt(4)" : "+v"(xb[0][0]), "+v"(xb[0][1]), "+v"(xb[1][0]), "+v"(xb[1][1])::"memory");
-            store_b(buf ^ 1, 0);
+        if constexpr (SCHED == SPLIT_SCHED_PIPELINED) {
+            // Fragment reads run one MFMA group ahead of their use, and the wait in front of a group is counted: it
+            // retires that group's reads and leaves the next group's in flight under the matrix pipe.  Four slots: hi A in
+            // a[0], lo A in a[1]; the B slots swap roles every k-half.  A slot is read again once the last group that uses
+            // it has issued.  Terms, blocks and operand bits are split_group's, so the sums are bit-identical.
+            SplitSlots f;
+            split_read_a(t, lds, buf, 0, false, f.a[0]);
+            split_read_b(t, lds, buf, 0, false, f.b[0]);
+            split_read_b(t, lds, buf, 0, true, f.b[1]);
+            split_wait_ab(2, f.a[0], f.b[0]);
+            split_mfma8(f.a[0], f.b[0], acc);                 // k-half 0: bh gh
+            __builtin_amdgcn_sched_barrier(0);
+            split_read_a(t, lds, buf, 0, true, f.a[1]);
+            split_wait_b(4, f.b[1]);
+            split_mfma8(f.a[0], f.b[1], acc);                 //           bh gl
+            __builtin_amdgcn_sched_barrier(0);
+            split_read_a(t, lds, buf, 1, false, f.a[0]);
+            split_read_b(t, lds, buf, 1, false, f.b[1]);
+            split_wait_a(6, f.a[1]);
+            split_mfma8(f.a[1], f.b[0], acc);                 //           bl gh
+            __builtin_amdgcn_sched_barrier(0);
+            split_read_b(t, lds, buf, 1, true, f.b[0]);
+            split_wait_ab(2, f.a[0], f.b[1]);
+            split_mfma8(f.a[0], f.b[1], acc);                 // k-half 1: bh gh
+            __builtin_amdgcn_sched_barrier(0);
+            split_read_a(t, lds, buf, 1, true, f.a[1]);
+            split_wait_b(4, f.b[0]);
+            if (more) wait_and_store_b0(buf ^ 1);
+            split_mfma8(f.a[0], f.b[0], acc);                 //           bh gl
+            __builtin_amdgcn_sched_barrier(0);
+            split_wait_a(0, f.a[1]);                          // the last reads, and the B stores if any: they count too
+            if (more) store_b(buf ^ 1, 1);
+            split_mfma8(f.a[1], f.b[1], acc);                 //           bl gh
+        } else {
+            SplitFrag f;
+            split_group(t, lds, buf, 0, 0, f, acc);
+            split_group(t, lds, buf, 0, 1, f, acc);
+            split_group(t, lds, buf, 0, 2, f, acc);
+            split_group(t, lds, buf, 1, 0, f, acc);
+            if (more) wait_and_store_b0(buf ^ 1);
+            split_group(t, lds, buf, 1, 1, f, acc);
+            if (more) store_b(buf ^ 1, 1);
+            split_group(t, lds, buf, 1, 2, f, acc);
         }
-        split_group(t, lds, buf, 1, 1, f, acc);
-        if (more) store_b(buf ^ 1, 1);
-        split_group(t, lds, buf, 1, 2, f, acc);
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(idx[0]), "+v"(idx[1])::"memory");
         __syncthreads();
         buf ^= 1;
@@ -964,7 +1072,8 @@ __device__ __forceinline__ void tile_run_split(const TileThread& t, float* lds, 
 
 // A: the belief block's split plane.  fb.mat == nullptr: every B tile is read from fp32 rows (the projected route); else
 // scheduler 2b's tiles (R = 1).
-__global__ __launch_bounds__(512) void k_gemm_split_streamk(
+template <int SCHED>
+__device__ __forceinline__ void gemm_split_streamk_body(
     const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb, FusedB fb, float* __restrict__ C, int ldc,
     int64_t slab_stride, int tiles_m, int pairs, int k_tiles, const int* __restrict__ klist, const int* __restrict__ kcount,
     const int* __restrict__ prefix, const int* __restrict__ start_pair, const int* __restrict__ first_block,
@@ -1003,14 +1112,14 @@ __global__ __launch_bounds__(512) void k_gemm_split_streamk(
             const float* Ablk = A + (int64_t)tm * 256 * lda;
             if (fb.mat == nullptr || fb.mat[tn]) {       // block-uniform: fp32 rows from B
                 const int bt = (fb.mat != nullptr && fb.ctile != nullptr) ? fb.ctile[tn] : tn;
-                tile_run_split(t, lds, Ablk, lda, B + (int64_t)bt * 256 * ldb, ldb, false, nullptr, nullptr, nullptr, 0, 0.f,
-                               klist + (int64_t)p * k_tiles, lo, hi, acc);
+                tile_run_split<SCHED>(t, lds, Ablk, lda, B + (int64_t)bt * 256 * ldb, ldb, false, nullptr, nullptr, nullptr, 0,
+                                      0.f, klist + (int64_t)p * k_tiles, lo, hi, acc);
             } else {
                 const int r0 = tn * 256;
                 const int g = r0 / fb.V, v0 = r0 - g * fb.V;
-                tile_run_split(t, lds, Ablk, lda, nullptr, 0, true, fb.rs + (int64_t)(g / fb.O) * fb.S_pad,
-                               fb.rto + (int64_t)g * fb.S_pad, fb.alpha + (int64_t)(v0 + (threadIdx.x >> 2)) * fb.lda,
-                               (int64_t)128 * fb.lda, fb.gamma, klist + (int64_t)p * k_tiles, lo, hi, acc);
+                tile_run_split<SCHED>(t, lds, Ablk, lda, nullptr, 0, true, fb.rs + (int64_t)(g / fb.O) * fb.S_pad,
+                                      fb.rto + (int64_t)g * fb.S_pad, fb.alpha + (int64_t)(v0 + (threadIdx.x >> 2)) * fb.lda,
+                                      (int64_t)128 * fb.lda, fb.gamma, klist + (int64_t)p * k_tiles, lo, hi, acc);
             }
             const bool cont = L != first_block[p];
             tile_store(t, cont ? C + slab_stride + (int64_t)L * (256 * 256) : C, cont ? 256 : ldc, cont ? 0 : tm, cont ? 0 : tn, acc);
@@ -1019,6 +1128,22 @@ __global__ __launch_bounds__(512) void k_gemm_split_streamk(
         ++p;
     }
 }
+
+#define PBVI_SPLIT_KERNEL_ARGS                                                                                              \
+    const float *__restrict__ A, int lda, const float *__restrict__ B, int ldb, FusedB fb, float *__restrict__ C, int ldc,      \
+        int64_t slab_stride, int tiles_m, int pairs, int k_tiles, const int *__restrict__ klist,                               \
+        const int *__restrict__ kcount, const int *__restrict__ prefix, const int *__restrict__ start_pair,                    \
+        const int *__restrict__ first_block, const int *__restrict__ plan, int ovh
+__global__ __launch_bounds__(512) void k_gemm_split_streamk(PBVI_SPLIT_KERNEL_ARGS) {
+    gemm_split_streamk_body<SPLIT_SCHED_PARENT>(A, lda, B, ldb, fb, C, ldc, slab_stride, tiles_m, pairs, k_tiles, klist, kcount,
+                                                prefix, start_pair, first_block, plan, ovh);
+}
+// The pipelined K-step schedule on the same plan, lists and slabs (pbvi_debug_split_schedule)
+__global__ __launch_bounds__(512) void k_gemm_split_streamk_pipelined(PBVI_SPLIT_KERNEL_ARGS) {
+    gemm_split_streamk_body<SPLIT_SCHED_PIPELINED>(A, lda, B, ldb, fb, C, ldc, slab_stride, tiles_m, pairs, k_tiles, klist, kcount,
+                                                   prefix, start_pair, first_block, plan, ovh);
+}
+#undef PBVI_SPLIT_KERNEL_ARGS
 
 // One wave: does the split path keep subnormal lo parts and subnormal products?  out[0] = 1 if
 //   x = (1 + 2^-7) 2^-120 + 2^-132 (a bf16-subnormal lo) times 1 comes back as x, and 2^-100 * 2^-30 as 2^-130.
@@ -1176,6 +1301,15 @@ int set_gemm_force_dense(int enable) {
     return prev;
 }
 
+// Which K-step schedule the split score GEMM runs (pbvi_debug_split_schedule): process-wide, for the test that holds
+// the two schedules' slabs bit-equal.  Not a tuning knob.
+static int g_split_schedule = SPLIT_SCHED_PARENT;
+int set_gemm_split_schedule(int schedule) {
+    const int prev = g_split_schedule;
+    if (schedule == SPLIT_SCHED_PARENT || schedule == SPLIT_SCHED_PIPELINED) g_split_schedule = schedule;
+    return prev;
+}
+
 int choose_chunk_len(int tiles_mn, int k_tiles) {
     if (const char* env = getenv("PBVI_GEMM_CHUNK")) {
         const int v = atoi(env);
@@ -1220,6 +1354,8 @@ static hipError_t set_lds_attr() {
                             GEMM_LDS_BYTES);
     if (e != hipSuccess) return e;
     e = hipFuncSetAttribute((const void*)k_gemm_split_streamk, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute((const void*)k_gemm_split_streamk_pipelined, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
     if (e != hipSuccess) return e;
 #define PBVI_FUSED_R_ATTR(RR)                                                                                          \
     e = hipFuncSetAttribute((const void*)k_gemm_nt_f32_streamk_fused_r<RR>, hipFuncAttributeMaxDynamicSharedMemorySize, \
@@ -1269,9 +1405,9 @@ hipError_t launch_gemm_nt_f32(const float* A, int lda, const float* B, int ldb, 
         if (split) {
             FusedB fb{};
             if (fused != nullptr) fb = *fused;           // (else fb.mat == nullptr: every B tile from fp32 rows)
-            hipLaunchKernelGGL(k_gemm_split_streamk, dim3(pl.nblocks), dim3(512), GEMM_LDS_BYTES, stream, A, lda, B, ldb, fb, C,
-                               pl.ldc, pl.slab_stride, pl.tiles_m, pairs, pl.k_tiles, klist, kcount, prefix, start_pair,
-                               first_block, plan, ovh);
+            hipLaunchKernelGGL(g_split_schedule == SPLIT_SCHED_PIPELINED ? k_gemm_split_streamk_pipelined : k_gemm_split_streamk,
+                               dim3(pl.nblocks), dim3(512), GEMM_LDS_BYTES, stream, A, lda, B, ldb, fb, C, pl.ldc, pl.slab_stride,
+                               pl.tiles_m, pairs, pl.k_tiles, klist, kcount, prefix, start_pair, first_block, plan, ovh);
         } else if (fused != nullptr && fused->R > 1) {
             switch (fused->R) {
 #define PBVI_FUSED_R_CASE(RR)                                                                                                   \

@@ -37,6 +37,7 @@ struct GemmPlan {
     int64_t c_floats;
 };
 int set_gemm_force_dense(int enable);   // returns the previous setting (see gemm.hip)
+int set_gemm_split_schedule(int schedule);   // K-step schedule of the split score GEMM: 0 parent (default), 1 pipelined; returns the previous one
 int gemm_force_dense();
 size_t streamk_workspace_ints(const GemmPlan& pl);   // ints of device workspace the stream-K plan needs
 // B operand generated inside the stream-K GEMM instead of read from HBM (gemm.hip, "scheduler 2b"): row (g, v) of an

@@ -35,7 +35,8 @@ EXPORTS = [
     'pbvi_backup_fetch_compact', 'pbvi_host_alloc', 'pbvi_host_free', 'pbvi_debug_gemm_dense',
     'pbvi_backup_fetch_exchange_padded', 'pbvi_assemble_rows_store', 'pbvi_exchange_merge', 'pbvi_backup_run_fetch', 'pbvi_debug_alloc_limit', 'pbvi_debug_live_bytes', 'pbvi_engine_after_oom', 'pbvi_set_f64_screen', 'pbvi_set_fused_projection', 'pbvi_backup_fetch_row_hashes', 'pbvi_set_score_split',
     'pbvi_set_gamma_tiling', 'pbvi_gamma_tiling_plan', 'pbvi_q_values', 'pbvi_prune_dominated_masked',
-    'pbvi_rollout', 'pbvi_infotaxis', 'pbvi_rollout_infotaxis',
+    'pbvi_rollout', 'pbvi_infotaxis', 'pbvi_rollout_infotaxis', 'pbvi_debug_split_schedule', 'pbvi_debug_slabs',
+    'pbvi_debug_slabs_fill',
 ]
 
 
@@ -95,6 +96,9 @@ def load_library(path: str = LIB_PATH):
         'pbvi_host_alloc': (vp, [C.c_size_t]),
         'pbvi_host_free': (None, [vp]),
         'pbvi_debug_gemm_dense': (C.c_int, [C.c_int]),
+        'pbvi_debug_split_schedule': (C.c_int, [C.c_int]),
+        'pbvi_debug_slabs': (C.c_int64, [vp, vp, C.c_int64]),
+        'pbvi_debug_slabs_fill': (C.c_int, [vp, C.c_int]),
         'pbvi_backup_store_unique': (C.c_int64, [vp, i32p, C.c_int64]),
         'pbvi_backup_device_results': (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
         'pbvi_backup': (C.c_int, [vp, vp, C.c_int64, C.c_double, C.c_int, vp, i32p, i32p, u8p, sp]),
@@ -196,6 +200,17 @@ def debug_gemm_dense(enable: bool) -> bool:
     """List every GEMM tile, zero or not (``pbvi_debug_gemm_dense``: BASELINE's "dense backup" measurement);
     returns the previous setting."""
     return bool(load_library().pbvi_debug_gemm_dense(1 if enable else 0))
+
+
+SPLIT_SCHEDULES = {'parent': 0, 'pipelined': 1}
+
+
+def debug_split_schedule(schedule: str) -> str:
+    """Tests only: the K-step schedule of the split score GEMM, ``'parent'`` (default) or ``'pipelined'`` (LDS fragment
+    reads a group ahead of the MFMAs; bit-identical slabs).  Process-wide (``pbvi_debug_split_schedule``); returns the
+    previous schedule."""
+    prev = int(load_library().pbvi_debug_split_schedule(SPLIT_SCHEDULES[schedule]))
+    return {v: k for k, v in SPLIT_SCHEDULES.items()}[prev]
 
 
 def device_count() -> int:
@@ -1191,6 +1206,21 @@ class Engine:
         """fp32 engines: backup scores from bf16 MFMAs on a three-term operand split with a widened tie window (same
         results): ``'off'``, ``'auto'`` (when the score GEMM is large; default) or ``'always'`` (``pbvi_set_score_split``)."""
         self._ck(self._lib.pbvi_set_score_split(self._h, {'off': 0, 'auto': 1, 'always': 2}[mode]))
+
+    def debug_slabs(self) -> np.ndarray:
+        """Tests only: the raw score slab buffer as the last backup's score GEMM left it, as bytes (``pbvi_debug_slabs``)."""
+        n = int(self._lib.pbvi_debug_slabs(self._h, None, 0))
+        if n < 0:
+            self._ck(n)
+        out = np.empty(n, dtype=np.uint8)
+        got = int(self._lib.pbvi_debug_slabs(self._h, _ptr(out), n))
+        if got < 0:
+            self._ck(got)
+        return out
+
+    def debug_slabs_fill(self, byte: int) -> None:
+        """Tests only: set every byte of the score slab buffer to ``byte`` (``pbvi_debug_slabs_fill``)."""
+        self._ck(self._lib.pbvi_debug_slabs_fill(self._h, int(byte)))
 
     def set_gamma_tiling(self, mode: str = 'off', chunk_rows: int = 0) -> None:
         """Alpha-side backups whose Gamma is projected into HBM (R > 1, fp64 scoring, unfused R = 1): walk the alpha set in
