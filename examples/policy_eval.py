@@ -7,6 +7,8 @@ The reference publishes one timing for this step (sim_runtime_test.ipynb:223, BA
     python examples/policy_eval.py --expansions 60 --n 1000 --max-steps 300
     python examples/policy_eval.py --reach 5 --device-sim 7      # stochastic moves, simulator on the device too
     python examples/policy_eval.py --policy infotaxis --device-sim 7   # the infotaxis baseline (no solve), on the device
+    python examples/policy_eval.py --device-sim 1 --environment frames    # observations from recorded frames (pbvi_rollout_env)
+    python examples/policy_eval.py --device-sim 1 --environment table --env-flip 0.1   # a sensor that errs 10 % more often
 """
 import argparse
 import os
@@ -18,7 +20,8 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 from pomdp_pbvi_exploration_amd import FSVI_Solver, Model, set_quiet, synth   # noqa: E402
-from pomdp_pbvi_exploration_amd.pomdp import Agent, Infotaxis_Agent           # noqa: E402
+from pomdp_pbvi_exploration_amd.pomdp import (Agent, FrameEnvironment, Infotaxis_Agent, TableEnvironment,   # noqa: E402
+                                              record_frames)
 from pomdp_pbvi_exploration_amd.mdp import VI_Solver                         # noqa: E402
 
 
@@ -41,6 +44,13 @@ def main():
     ap.add_argument('--policy', default='value', choices=['value', 'infotaxis'],
                     help='value: solve with FSVI and follow the value function; infotaxis: no solve, every step takes the '
                          'action with the smallest expected entropy of the next belief (pbvi_infotaxis)')
+    ap.add_argument('--environment', default=None, choices=['frames', 'table'],
+                    help='where the observations come from (needs --device-sim): frames = a recorded movie, max-steps + 100 '
+                         'frames drawn from the observation table by record_frames, every simulation starting at its own '
+                         'frame; table = the observation table itself as a second law')
+    ap.add_argument('--env-flip', type=float, default=0.0, metavar='P',
+                    help='perturb the environment\'s table: each row becomes (1 - P) * row + P * (row reversed over the '
+                         'observations), a sensor that reports the opposite reading with probability P')
     ap.add_argument('--repeat', type=int, default=1, help='run the evaluation this many times (the first one warms up)')
     args = ap.parse_args()
     set_quiet(True)
@@ -76,17 +86,34 @@ def main():
         agent = Agent(vf.model, vf, lookahead=args.lookahead, gamma=m.gamma)
         policy = f'|V|={len(vf)}'
     sim = 'host simulator' if args.device_sim is None else f'device simulator, seed {args.device_sim}'
+    env = None
+    if args.environment is not None:
+        if args.device_sim is None:
+            ap.error('--environment needs --device-sim SEED')
+        table = (1.0 - args.env_flip) * m.observation_table + args.env_flip * m.observation_table[:, :, ::-1]
+        if args.environment == 'frames':
+            frames = record_frames(table, args.max_steps + 100, args.device_sim)
+            env = FrameEnvironment(frames, np.arange(m.A), shifts=np.arange(args.n) % 101)
+            sim += f', {frames.shape[0]} recorded frames ({frames.nbytes / 2 ** 20:.1f} MiB)'
+        else:
+            env = TableEnvironment(table)
+            sim += ', observation table environment'
+        if args.env_flip:
+            sim += f', flipped with P = {args.env_flip}'
     for rep in range(args.repeat):
         np.random.seed(1)
         t0 = time.perf_counter()
         totals, hists = agent.run_n_simulations_parallel(n=args.n, max_steps=args.max_steps, print_progress=False,
-                                                         print_stats=rep == args.repeat - 1, device_rng_seed=args.device_sim)
+                                                         print_stats=rep == args.repeat - 1, device_rng_seed=args.device_sim,
+                                                         **({} if env is None else {'environment': env}))
         wall = time.perf_counter() - t0
         steps = sum(len(h.actions) for h in hists)
         lock_steps = max(len(h.actions) for h in hists)
         print(f'gpu ({args.dtype}, R={args.reach}, {sim}): n={args.n} max_steps={args.max_steps} {policy} wall={wall:.3f}s '
               f'lock-steps={lock_steps} ({1e3 * wall / lock_steps:.3f} ms/step) belief-steps={steps} '
               f'({steps / wall:.0f} belief-steps/s)  reference CuPy: 41.8 s for 1000 x 300', flush=True)
+        if env is not None:
+            print(f'lost (met an observation the model gives probability 0): {sum(h.lost for h in hists)} of {args.n}', flush=True)
 
     if args.cpu_steps > 0:
         host_agent = Infotaxis_Agent(model) if args.policy == 'infotaxis' else Agent(model, vf.to_cpu(), lookahead=args.lookahead, gamma=m.gamma)

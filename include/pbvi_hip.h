@@ -492,6 +492,61 @@ int pbvi_rollout_infotaxis(pbvi_engine_t* e, const int32_t* start_states /* [B] 
                            int32_t* out_steps /* [B] */);
 
 /*
+ * Environments: where the observations of pbvi_rollout_env come from.  The rollouts above simulate the world the agent
+ * believes in (successor and observation both from the engine's RTO); an evaluation against recorded data or a mismatched
+ * sensor replaces the observation source and keeps the agent's model for the Bayes step.  One environment per engine, held
+ * in device memory of the engine (counted against pbvi_debug_alloc_limit, PBVI_ENOMEM as everywhere; released by
+ * pbvi_engine_after_oom, after which no environment is set).  Setting one kind replaces the other.
+ *   pbvi_env_set_frames  frames [F][C][S] uint8: frames[f][c][s] = the observation id emitted in frame f, channel c, at state s;
+ *                        channel_of_action [A] int32: the channel an action reads (nose / ground data: C = 2).
+ *                        PBVI_EINVAL: NULL, F or C < 1, a channel outside [0, C), a frame entry >= O.
+ *                        PBVI_EUNSUPPORTED: O > 255 (one byte per entry).
+ *   pbvi_env_set_table   obs_prob [S][A][O] double: obs_prob[s', a, :] = the law of the observation after landing in s' with
+ *                        action a (need not be normalised).  PBVI_EINVAL: NULL, an entry negative or not finite, a row that
+ *                        sums to 0.
+ *   pbvi_env_clear       no environment; the bytes are returned.
+ * All three validate on the host, leave a pbvi_last_error text, and do not touch the belief block, the alpha set or the stores.
+ */
+int pbvi_env_set_frames(pbvi_engine_t* e, const uint8_t* frames /* [F][C][S] */, int64_t F, int64_t C,
+                        const int32_t* channel_of_action /* [A] */);
+int pbvi_env_set_table(pbvi_engine_t* e, const double* obs_prob /* [S][A][O] */);
+int pbvi_env_clear(pbvi_engine_t* e);
+
+/*
+ * Device-resident rollout against the environment: pbvi_rollout's loop, trajectory layout (-1 padding included) and end state of
+ * the block, with the policy chosen by number and the observation taken from the environment.
+ *   policy   0: a = alpha_actions[first argmax_v b.alpha_v];  1: a = first argmax_a Q(b, a) (discount gamma; PBVI_SPARSE
+ *            engines);  2: infotaxis, a = first argmin_a G(b, a) (alpha_actions may be NULL, no alpha set needed)
+ * For simulation i = first_sim_id + b at step t, in state s, with that action a:
+ *   successor    w[r] = sum_o (double) RTO[s, a, o, r], o ascending, sequential fp64 adds ( = P(r | s, a) from the table the
+ *                engine scores with);  c[r] = c[r-1] + w[r];  r* = the first r with u1 * c[R-1] < c[r], else the last r with
+ *                w[r] > 0;  u1 = uniform01(splitmix64(seed, i), t), pbvi_rollout's uniform;  s' = reach_states[s, a, r*].
+ *                A model with a pair (s, a) whose RTO entries sum to 0 is refused, as by pbvi_rollout.
+ *   observation  o = end_observation                               if end_observation >= 0 and end_mask[s'];
+ *                o = frames[shift_i + t][channel_of_action[a]][s']   with a frame environment (shift_i = shifts[b], 0 if NULL);
+ *                o drawn from obs_prob[s', a, :] by the same sequential-prefix rule with a second uniform
+ *                  u2 = uniform01(splitmix64(seed, i), 2^32 + t)   with a table environment (t < 2^31: the streams never meet)
+ *   done         end_mask[s'] != 0 finishes the simulation: out_steps[i] = t + 1, out_lost[i] = 0, no belief update
+ *   lost         otherwise, with u the un-normalised Bayes step of (b, a, o) and Z = sum_s' u[s']: if Z == 0 or Z is not finite,
+ *                the observation was impossible under the agent's model and the simulation stops at this step:
+ *                out_steps[i] = t + 1, out_lost[i] = 1.  Its step-t action, observation and s' are recorded, its row is
+ *                dropped like a finished one, and no NaN belief is ever formed.  Z is a sum of non-negative products, so
+ *                Z == 0 does not depend on the order of the sum.
+ *   belief       otherwise b <- u / Z, with Z summed in block order (no atomics) for every policy
+ * A trajectory is a function of (model tables, alpha set, environment, start belief, start state, shift, seed, id) alone: not
+ * of B, of the other simulations in the block, or of how a run is cut into calls.
+ *   shifts [B] int64 or NULL (frames only); out_lost [B] uint8, may be NULL; the rest as pbvi_rollout.
+ * Every check is made on the host before the first launch.  PBVI_EINVAL beyond pbvi_rollout's: no environment set, policy not
+ * 0, 1 or 2, end_observation >= O, shifts given with a table environment, a negative shift, or max(shift) + T > F (the
+ * reference would index past its data).  PBVI_ENOMEM as everywhere.
+ */
+int pbvi_rollout_env(pbvi_engine_t* e, int policy, const int32_t* alpha_actions /* [V] */, double gamma,
+                     const int32_t* start_states /* [B] */, const uint8_t* end_mask /* [S] */, int end_observation,
+                     const int64_t* shifts /* [B] or NULL */, uint64_t first_sim_id, uint64_t seed, int64_t T,
+                     int32_t* out_states /* [T+1][B] */, int32_t* out_actions /* [T][B] */,
+                     int32_t* out_observations /* [T][B] */, int32_t* out_steps /* [B] */, uint8_t* out_lost /* [B] */);
+
+/*
  * MDP value iteration on the device (VI_Solver.solve, src/mdp.py:1442-1525; seeds FSVI / HSVI):
  *   rows[a][s] = ER[s,a] + gamma * sum_r P[s,a,r] * v[rs[s,a,r]];   v'[s] = max_a rows[a][s]
  * repeated from v0 until max_s |v' - v| < max_change_limit (the reference's eps * gamma / (1 - gamma)) or

@@ -291,6 +291,41 @@ hipError_t launch_rollout_compact(int n, const uint8_t* keep, const int32_t* per
                                   const int32_t* orig_in, int32_t* dst, int32_t* row_e, int32_t* state_out, int32_t* orig_out,
                                   int* count, hipStream_t st);
 
+// launch_belief_update in two halves, for a caller that drops rows between them (pbvi_rollout_env's lost rule):
+//   launch_belief_push_fold  k_belief_push + k_mass_fold: unnorm [B][S] and mass [B] of the rows with out_row[b] >= 0 (or all),
+//                            the mass ALWAYS summed in block order through mass_part [B][ceil(S / 256)]
+//   launch_belief_norm       k_belief_norm: out[out_row[b]] = unnorm[b] / mass[b] for the rows with out_row[b] >= 0
+// out_row may differ between the two (a provisional one for the push, the final one for the norm).
+template <typename T>
+hipError_t launch_belief_push_fold(const T* bel, int ldb, int B, ModelView<T> mv, const int32_t* in_ptr, const int32_t* in_src,
+                                   const int32_t* act, const int32_t* obs, const int32_t* out_row, double* unnorm, double* mass,
+                                   double* mass_part, hipStream_t st);
+template <typename T>
+hipError_t launch_belief_norm(int B, int S, const double* unnorm, const double* mass, const int32_t* out_row, T* out, int ldo,
+                              hipStream_t st);
+
+// Simulator draw of a rollout against an environment (pbvi_rollout_env); launch_rollout_draw's lanes, indexing and action.
+//   w[r] = sum_o (double) RTO[state[c], a, o, r] (o ascending), r* = first r with u1 * c[R-1] < c[r], c = prefix sums of w,
+//          else the last r with w[r] > 0;  u1 = uniform01(splitmix64(seed, first_id + og), t);  s' = rs[state[c], a, r*]
+//   o    = end_observation                                  if end_observation >= 0 and end_mask[s']
+//        = frames[(shift[og] + t) * C * S + channel[a] * S + s']   (frames != nullptr: uint8 [F][C][S], 64-bit offsets; the
+//                                                            caller has checked shift[og] + t < F and channel[a] in [0, C))
+//        = drawn from table[s', a, :] (fp64 [S][A][O]) by the same prefix rule with
+//          u2 = uniform01(splitmix64(seed, first_id + og), 2^32 + t)               (table != nullptr)
+// Exactly one of frames / table is given.  Writes what launch_rollout_draw writes and row_e[i] = done ? -1 : i, the
+// provisional out_row of launch_belief_push_fold.
+template <typename T>
+hipError_t launch_rollout_draw_env(int n, ModelView<T> mv, const int32_t* perm, const int32_t* index, const int32_t* alpha_actions,
+                                   int V, const int32_t* state, const int32_t* orig, const uint8_t* end_mask, int end_observation,
+                                   const uint8_t* frames, int C, const int32_t* channel, const int64_t* shift, const double* table,
+                                   uint64_t seed, uint64_t first_id, int t, int n0, int32_t* act_e, int32_t* obs_e, int32_t* row_e,
+                                   int32_t* next_state, uint8_t* keep, int32_t* tr_states, int32_t* tr_actions, int32_t* tr_obs,
+                                   int32_t* steps, hipStream_t st);
+// The lost rule, one lane per engine row i (c = perm ? perm[i] : i): a kept row whose mass[i] is 0 or not finite gets
+// keep[c] = 0, steps[orig[c]] = t + 1, lost[orig[c]] = 1.  Runs between launch_belief_push_fold and launch_rollout_compact.
+hipError_t launch_rollout_lost(int n, const int32_t* perm, const int32_t* orig, const double* mass, int t, uint8_t* keep,
+                               int32_t* steps, uint8_t* lost, hipStream_t st);
+
 // Infotaxis (pbvi_infotaxis): for every belief row b of `bel` (engine order; caller row d = perm ? perm[b] : b) and action a
 //   G[b,a] = sum_o (Z ln Z - N),  Z = sum_s' u[s'],  N = sum_s' u[s'] ln u[s']  (zero terms add 0; fp64 log),
 //   u[s']  = sum over the inverse list of (a, s') of (double) bel[b][s] * (double) RTO[s,a,o,r]  (launch_belief_update's sum)

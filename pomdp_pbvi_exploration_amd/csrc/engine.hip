@@ -902,6 +902,14 @@ class EngineBase {
                         const uint8_t* end_mask, uint64_t first_sim_id, uint64_t seed, int64_t T, int32_t* out_states,
                         int32_t* out_actions, int32_t* out_observations, int32_t* out_steps) = 0;
     virtual int infotaxis(double* out_g, int32_t* out_action, double* out_p_obs, double* out_entropy) = 0;
+    // the observation source of rollout_env: recorded frames or another observation law (setting one replaces the other)
+    virtual int env_set_frames(const uint8_t* frames, int64_t F, int64_t C, const int32_t* channel_of_action) = 0;
+    virtual int env_set_table(const double* obs_prob) = 0;
+    virtual int env_clear() = 0;
+    virtual int rollout_env(int source, const int32_t* alpha_actions, double gamma, const int32_t* start_states,
+                            const uint8_t* end_mask, int end_observation, const int64_t* shifts, uint64_t first_sim_id,
+                            uint64_t seed, int64_t T, int32_t* out_states, int32_t* out_actions, int32_t* out_observations,
+                            int32_t* out_steps, uint8_t* out_lost) = 0;
 };
 
 template <typename T>
@@ -1003,6 +1011,13 @@ class EngineT : public EngineBase {
     // and the beliefs' own entropies [B], all four in the caller's belief order
     DevBuf it_part_{mem_}, it_g_{mem_}, it_act_{mem_}, it_pobs_{mem_}, it_h_{mem_};
     DevBuf bu_mpart_{mem_};   // advance_resident(fixed_order): the push blocks' partial masses [B][ceil(S/256)]
+    // pbvi_env_set_*: the observation source of pbvi_rollout_env.  Frames: env_frames_ uint8 [F][C][S] + env_chan_ int32 [A];
+    // table: env_table_ fp64 [S][A][O].  Working buffers: after_oom() releases them and the engine has no environment again.
+    enum EnvKind { ENV_NONE = 0, ENV_FRAMES = 1, ENV_TABLE = 2 };
+    DevBuf env_frames_{mem_}, env_chan_{mem_}, env_table_{mem_};
+    int env_kind_ = ENV_NONE;
+    int64_t env_F_ = 0, env_C_ = 0;
+    DevBuf env_shift_{mem_}, ro_lost_{mem_};   // pbvi_rollout_env: the call's shifts int64 [n] and lost flags uint8 [n]
     DevBuf rf_q2_{mem_}, rf_q2p_{mem_}, rf_q2d_{mem_};   // k_refine_split: entries / candidates, partial scores, arrival counters
     DevBuf rf_v_{mem_}, rf_slot_{mem_}, rf_sc_{mem_}, rf_entry_{mem_}, rf_n_{mem_}, rf_tiles_{mem_}, rf_ibv_{mem_}, rf_ibi_{mem_}, rf_cnt_{mem_}, rf_W_{mem_}, rf_Cx_{mem_}, rf_nzW_{mem_}, rf_klW_{mem_}, rf_kcW_{mem_};   // refinement work list
     int formulation_ = 0;                                   // 0 auto, 1 project alpha-vectors, 2 project beliefs
@@ -1652,7 +1667,92 @@ class EngineT : public EngineBase {
     int rollout(int source, const int32_t* alpha_actions, double gamma, const int32_t* start_states, const uint8_t* end_mask,
                 uint64_t first_sim_id, uint64_t seed, int64_t n_steps, int32_t* out_states, int32_t* out_actions,
                 int32_t* out_observations, int32_t* out_steps) override {
+        return rollout_loop(source, alpha_actions, gamma, start_states, end_mask, first_sim_id, seed, n_steps, out_states,
+                            out_actions, out_observations, out_steps, false, -1, nullptr, nullptr);
+    }
+    int rollout_env(int source, const int32_t* alpha_actions, double gamma, const int32_t* start_states, const uint8_t* end_mask,
+                    int end_observation, const int64_t* shifts, uint64_t first_sim_id, uint64_t seed, int64_t n_steps,
+                    int32_t* out_states, int32_t* out_actions, int32_t* out_observations, int32_t* out_steps,
+                    uint8_t* out_lost) override {
+        return rollout_loop(source, alpha_actions, gamma, start_states, end_mask, first_sim_id, seed, n_steps, out_states,
+                            out_actions, out_observations, out_steps, true, end_observation, shifts, out_lost);
+    }
+
+    // ---- environments (pbvi_env_set_frames / pbvi_env_set_table / pbvi_env_clear) ---- //
+    int env_clear() override {
+        HIPCHK(hipSetDevice(device_));
+        HIPCHK(hipStreamSynchronize(stream_));
+        env_frames_.release();
+        env_chan_.release();
+        env_table_.release();
+        env_kind_ = ENV_NONE;
+        env_F_ = env_C_ = 0;
+        return PBVI_OK;
+    }
+    int env_set_frames(const uint8_t* frames, int64_t F, int64_t C, const int32_t* channel) override {
+        if (!frames || !channel) FAIL(PBVI_EINVAL, "env_set_frames: NULL argument");
+        if (F < 1 || C < 1) FAIL(PBVI_EINVAL, "env_set_frames: F and C must be at least 1");
+        if (O_ > 255) FAIL(PBVI_EUNSUPPORTED, "env_set_frames: frames hold one byte per observation, so O must be at most 255");
+        if (C > 0x7fffffff || F > INT64_MAX / C / S_) FAIL(PBVI_EUNSUPPORTED, "env_set_frames: F * C * S exceeds int64");
+        for (int a = 0; a < A_; ++a)
+            if (channel[a] < 0 || channel[a] >= C)
+                FAIL(PBVI_EINVAL, "env_set_frames: channel_of_action[" + std::to_string(a) + "] is outside [0, C)");
+        const size_t bytes = (size_t)F * (size_t)C * (size_t)S_;
+        for (size_t k = 0; k < bytes; ++k)
+            if (frames[k] >= O_)
+                FAIL(PBVI_EINVAL, "env_set_frames: frame entry " + std::to_string(k) + " is " + std::to_string((int)frames[k]) +
+                                      ", not an observation in [0, O)");
+        int rc = env_clear();                                // (exact sizes: a released buffer does not grow with headroom)
+        if (rc) return rc;
+        if ((rc = env_frames_.ensure(bytes)) || (rc = env_chan_.ensure((size_t)A_ * sizeof(int32_t)))) {
+            env_frames_.release();                            // (the error text is the failed allocation's)
+            env_chan_.release();
+            return rc;
+        }
+        HIPCHK(hipMemcpy(env_frames_.p, frames, bytes, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(env_chan_.p, channel, (size_t)A_ * sizeof(int32_t), hipMemcpyHostToDevice));
+        env_kind_ = ENV_FRAMES;
+        env_F_ = F;
+        env_C_ = C;
+        return PBVI_OK;
+    }
+    int env_set_table(const double* obs_prob) override {
+        if (!obs_prob) FAIL(PBVI_EINVAL, "env_set_table: NULL argument");
+        const size_t rows = (size_t)S_ * A_;
+        for (size_t k = 0; k < rows; ++k) {
+            double tot = 0.0;
+            for (int o = 0; o < O_; ++o) {
+                const double p = obs_prob[k * O_ + o];
+                if (!(p >= 0.0) || !std::isfinite(p))
+                    FAIL(PBVI_EINVAL, "env_set_table: obs_prob[s', a, o] is negative or not finite at s' = " + std::to_string(k / A_) +
+                                          ", a = " + std::to_string(k % A_) + ", o = " + std::to_string(o));
+                tot += p;
+            }
+            if (!(tot > 0.0) || !std::isfinite(tot))
+                FAIL(PBVI_EINVAL, "env_set_table: obs_prob[s', a, :] sums to 0 (or overflows) at s' = " + std::to_string(k / A_) +
+                                      ", a = " + std::to_string(k % A_));
+        }
+        int rc = env_clear();
+        if (rc) return rc;
+        if ((rc = env_table_.ensure(rows * O_ * sizeof(double)))) return rc;
+        HIPCHK(hipMemcpy(env_table_.p, obs_prob, rows * O_ * sizeof(double), hipMemcpyHostToDevice));
+        env_kind_ = ENV_TABLE;
+        return PBVI_OK;
+    }
+
+    // The step loop of pbvi_rollout / pbvi_rollout_infotaxis (env == false: the model's own joint draw, the done-filter, the
+    // Bayes step) and of pbvi_rollout_env (env == true: successor from the model, observation from the environment, the Bayes
+    // step cut in two around the lost rule; the norm always summed in block order).
+    int rollout_loop(int source, const int32_t* alpha_actions, double gamma, const int32_t* start_states, const uint8_t* end_mask,
+                     uint64_t first_sim_id, uint64_t seed, int64_t n_steps, int32_t* out_states, int32_t* out_actions,
+                     int32_t* out_observations, int32_t* out_steps, bool env, int end_observation, const int64_t* shifts,
+                     uint8_t* out_lost) {
         const bool uses_alpha = source != ROLLOUT_INFOTAXIS;
+        if (env && source != ROLLOUT_VALUE_MAX && source != ROLLOUT_Q && source != ROLLOUT_INFOTAXIS)
+            FAIL(PBVI_EINVAL, "rollout_env: policy must be 0 (value-max), 1 (Q) or 2 (infotaxis)");
+        if (env && env_kind_ == ENV_NONE) FAIL(PBVI_EINVAL, "rollout_env: no environment set (call pbvi_env_set_frames or pbvi_env_set_table)");
+        if (env && end_observation >= O_) FAIL(PBVI_EINVAL, "rollout_env: end_observation is not below O");
+        if (env && shifts && env_kind_ != ENV_FRAMES) FAIL(PBVI_EINVAL, "rollout_env: shifts are for a frame environment, and a table is set");
         if (uses_alpha && V_ <= 0) FAIL(PBVI_EINVAL, "rollout: no alpha set resident (call pbvi_alpha_set)");
         if (B_ <= 0) FAIL(PBVI_EINVAL, "rollout: no belief block resident (call pbvi_beliefs_set)");
         if ((uses_alpha && !alpha_actions) || !start_states || !end_mask) FAIL(PBVI_EINVAL, "rollout: NULL argument");
@@ -1671,8 +1771,30 @@ class EngineT : public EngineBase {
         if (zero_row_ >= 0)
             FAIL(PBVI_EINVAL, "rollout: RTO[s,a,:,:] sums to 0 for s = " + std::to_string(zero_row_ / A_) + ", a = " +
                                   std::to_string(zero_row_ % A_) + ": nothing can follow that state-action pair");
+        if (env && env_kind_ == ENV_FRAMES) {                 // the reference would index past its data: refused before any launch
+            int64_t top = 0;
+            for (int64_t b = 0; shifts && b < n0; ++b) {
+                if (shifts[b] < 0) FAIL(PBVI_EINVAL, "rollout_env: negative shift");
+                top = std::max(top, shifts[b]);
+            }
+            if (top > env_F_ || n_steps > env_F_ - top)
+                FAIL(PBVI_EINVAL, "rollout_env: max(shift) + T = " + std::to_string(top) + " + " + std::to_string(n_steps) +
+                                      " exceeds the " + std::to_string(env_F_) + " frames of the environment");
+        }
         HIPCHK(hipSetDevice(device_));
         int rc;
+        if (env) {
+            if ((rc = ro_lost_.ensure((size_t)n0))) return rc;
+            if ((rc = bu_mpart_.ensure((size_t)n0 * ((S_ + 255) / 256) * sizeof(double)))) return rc;
+            if ((rc = bu_unnorm_.ensure((size_t)n0 * S_ * sizeof(double)))) return rc;
+            if ((rc = bu_mass_.ensure((size_t)n0 * sizeof(double)))) return rc;
+            HIPCHK(hipMemsetAsync(ro_lost_.p, 0, (size_t)n0, stream_));
+            if (env_kind_ == ENV_FRAMES) {
+                if ((rc = env_shift_.ensure((size_t)n0 * sizeof(int64_t)))) return rc;
+                if (shifts) HIPCHK(hipMemcpyAsync(env_shift_.p, shifts, (size_t)n0 * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
+                else HIPCHK(hipMemsetAsync(env_shift_.p, 0, (size_t)n0 * sizeof(int64_t), stream_));
+            }
+        }
         const size_t n_st = (size_t)(n_steps + 1) * n0, n_ao = (size_t)n_steps * n0, n_traj = n_st + 2 * n_ao + (size_t)n0;
         if ((rc = ro_traj_.ensure(n_traj * sizeof(int32_t)))) return rc;
         for (int k = 0; k < 2; ++k) {
@@ -1726,11 +1848,29 @@ class EngineT : public EngineBase {
             const int32_t* perm = sorted_ ? perm_.as<int32_t>() : nullptr;
             // true states: live in ro_state_[0]; the draw leaves the next states in [1], row for row, and the filter moves
             // the survivors' back up into [0].  Trajectory rows: the filter moves them from one ro_orig_ buffer to the other.
-            HIPCHK(launch_rollout_draw<T>(n, view(), perm, index, source == ROLLOUT_VALUE_MAX ? ro_aact_.as<int32_t>() : nullptr, (int)V_,
-                                          ro_state_[0].as<int32_t>(), ro_orig_[oc].as<int32_t>(), ro_end_.as<uint8_t>(), seed,
-                                          first_sim_id, (int)t, (int)n0, bu_act_.as<int32_t>(), bu_obs_.as<int32_t>(),
-                                          ro_state_[1].as<int32_t>(), ro_keep_.as<uint8_t>(), tr_states, tr_actions, tr_obs,
-                                          tr_steps, stream_));
+            if (!env) {
+                HIPCHK(launch_rollout_draw<T>(n, view(), perm, index, source == ROLLOUT_VALUE_MAX ? ro_aact_.as<int32_t>() : nullptr, (int)V_,
+                                              ro_state_[0].as<int32_t>(), ro_orig_[oc].as<int32_t>(), ro_end_.as<uint8_t>(), seed,
+                                              first_sim_id, (int)t, (int)n0, bu_act_.as<int32_t>(), bu_obs_.as<int32_t>(),
+                                              ro_state_[1].as<int32_t>(), ro_keep_.as<uint8_t>(), tr_states, tr_actions, tr_obs,
+                                              tr_steps, stream_));
+            } else {
+                // draw (bu_row_: provisional, -1 = done), push and fold of the rows not done, then the lost rule on their masses
+                const bool fr = env_kind_ == ENV_FRAMES;
+                HIPCHK(launch_rollout_draw_env<T>(n, view(), perm, index, source == ROLLOUT_VALUE_MAX ? ro_aact_.as<int32_t>() : nullptr,
+                                                  (int)V_, ro_state_[0].as<int32_t>(), ro_orig_[oc].as<int32_t>(), ro_end_.as<uint8_t>(),
+                                                  end_observation, fr ? env_frames_.as<uint8_t>() : nullptr, (int)env_C_,
+                                                  fr ? env_chan_.as<int32_t>() : nullptr, fr ? env_shift_.as<int64_t>() : nullptr,
+                                                  fr ? nullptr : env_table_.as<double>(), seed, first_sim_id, (int)t, (int)n0,
+                                                  bu_act_.as<int32_t>(), bu_obs_.as<int32_t>(), bu_row_.as<int32_t>(),
+                                                  ro_state_[1].as<int32_t>(), ro_keep_.as<uint8_t>(), tr_states, tr_actions, tr_obs,
+                                                  tr_steps, stream_));
+                HIPCHK(launch_belief_push_fold<T>(bel_.as<T>(), S_pad_, n, view(), in_ptr_.as<int32_t>(), in_src_.as<int32_t>(),
+                                                  bu_act_.as<int32_t>(), bu_obs_.as<int32_t>(), bu_row_.as<int32_t>(),
+                                                  bu_unnorm_.as<double>(), bu_mass_.as<double>(), bu_mpart_.as<double>(), stream_));
+                HIPCHK(launch_rollout_lost(n, perm, ro_orig_[oc].as<int32_t>(), bu_mass_.as<double>(), (int)t, ro_keep_.as<uint8_t>(),
+                                           tr_steps, ro_lost_.as<uint8_t>(), stream_));
+            }
             HIPCHK(launch_rollout_compact(n, ro_keep_.as<uint8_t>(), perm, ro_state_[1].as<int32_t>(),
                                           ro_orig_[oc].as<int32_t>(), ro_dst_.as<int32_t>(), bu_row_.as<int32_t>(),
                                           ro_state_[0].as<int32_t>(), ro_orig_[oc ^ 1].as<int32_t>(),
@@ -1749,8 +1889,17 @@ class EngineT : public EngineBase {
             }
             // (infotaxis meets near-ties between actions on symmetric beliefs: its trajectories must not hang on the
             // arrival order of the norm's atomics, so its Bayes step sums the norm in a fixed order)
-            if ((rc = advance_resident(nb, false, source == ROLLOUT_INFOTAXIS))) return rc;
+            if (!env) {
+                if ((rc = advance_resident(nb, false, source == ROLLOUT_INFOTAXIS))) return rc;
+            } else {                                          // the norm of the rows that go on (bu_row_: now the filter's rows)
+                if ((rc = stage_.ensure((size_t)nb * S_pad_ * sizeof(T)))) return rc;
+                HIPCHK(hipMemsetAsync(stage_.p, 0, (size_t)nb * S_pad_ * sizeof(T), stream_));   // pad columns stay zero
+                HIPCHK(launch_belief_norm<T>(n, S_, bu_unnorm_.as<double>(), bu_mass_.as<double>(), bu_row_.as<int32_t>(),
+                                             stage_.as<T>(), S_pad_, stream_));
+                if ((rc = beliefs_finish(nb, stage_.as<T>(), nullptr))) return rc;
+            }
         }
+        if (env && out_lost) HIPCHK(hipMemcpyAsync(out_lost, ro_lost_.p, (size_t)n0, hipMemcpyDeviceToHost, stream_));
         const int32_t* src[4] = {tr_states, tr_actions, tr_obs, tr_steps};
         int32_t* dsts[4] = {out_states, out_actions, out_observations, out_steps};
         const size_t len[4] = {n_st, n_ao, n_ao, (size_t)n0};
@@ -2015,6 +2164,8 @@ class EngineT : public EngineBase {
         for (DevBuf* b : mem_.bufs)
             if (b->life == DevBuf::WORKING) b->release();
         alpha_ = DevView{};                                  // (it pointed into alpha_buf_ / alpha_small_)
+        env_kind_ = ENV_NONE;                                // (its buffers were working buffers)
+        env_F_ = env_C_ = 0;
         V_ = 0;
         B_ = B_pad_ = 0;
         prim_valid_ = alpha_on_primary_ = false;
@@ -4498,6 +4649,26 @@ int pbvi_rollout_infotaxis(pbvi_engine_t* e, const int32_t* start_states, const 
     NEED(e);
     return e->impl->rollout(pbvi::ROLLOUT_INFOTAXIS, nullptr, 0.0, start_states, end_mask, first_sim_id, seed, T, out_states,
                             out_actions, out_observations, out_steps);
+}
+int pbvi_env_set_frames(pbvi_engine_t* e, const uint8_t* frames, int64_t F, int64_t C, const int32_t* channel_of_action) {
+    NEED(e);
+    return e->impl->env_set_frames(frames, F, C, channel_of_action);
+}
+int pbvi_env_set_table(pbvi_engine_t* e, const double* obs_prob) {
+    NEED(e);
+    return e->impl->env_set_table(obs_prob);
+}
+int pbvi_env_clear(pbvi_engine_t* e) {
+    NEED(e);
+    return e->impl->env_clear();
+}
+int pbvi_rollout_env(pbvi_engine_t* e, int policy, const int32_t* alpha_actions, double gamma, const int32_t* start_states,
+                     const uint8_t* end_mask, int end_observation, const int64_t* shifts, uint64_t first_sim_id, uint64_t seed,
+                     int64_t T, int32_t* out_states, int32_t* out_actions, int32_t* out_observations, int32_t* out_steps,
+                     uint8_t* out_lost) {
+    NEED(e);
+    return e->impl->rollout_env(policy, alpha_actions, gamma, start_states, end_mask, end_observation, shifts, first_sim_id, seed,
+                                T, out_states, out_actions, out_observations, out_steps, out_lost);
 }
 int pbvi_beliefs_fetch(pbvi_engine_t* e, void* out_beliefs) {
     NEED(e);

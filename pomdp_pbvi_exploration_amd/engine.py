@@ -36,7 +36,7 @@ EXPORTS = [
     'pbvi_backup_fetch_exchange_padded', 'pbvi_assemble_rows_store', 'pbvi_exchange_merge', 'pbvi_backup_run_fetch', 'pbvi_debug_alloc_limit', 'pbvi_debug_live_bytes', 'pbvi_engine_after_oom', 'pbvi_set_f64_screen', 'pbvi_set_fused_projection', 'pbvi_backup_fetch_row_hashes', 'pbvi_set_score_split',
     'pbvi_set_gamma_tiling', 'pbvi_gamma_tiling_plan', 'pbvi_q_values', 'pbvi_prune_dominated_masked',
     'pbvi_rollout', 'pbvi_infotaxis', 'pbvi_rollout_infotaxis', 'pbvi_debug_split_schedule', 'pbvi_debug_slabs',
-    'pbvi_debug_slabs_fill',
+    'pbvi_debug_slabs_fill', 'pbvi_env_set_frames', 'pbvi_env_set_table', 'pbvi_env_clear', 'pbvi_rollout_env',
 ]
 
 
@@ -126,6 +126,11 @@ def load_library(path: str = LIB_PATH):
                                    i32p, i32p, i32p, i32p]),
         'pbvi_infotaxis': (C.c_int, [vp, f64p, i32p, f64p, f64p]),
         'pbvi_rollout_infotaxis': (C.c_int, [vp, i32p, u8p, C.c_uint64, C.c_uint64, C.c_int64, i32p, i32p, i32p, i32p]),
+        'pbvi_env_set_frames': (C.c_int, [vp, u8p, C.c_int64, C.c_int64, i32p]),
+        'pbvi_env_set_table': (C.c_int, [vp, f64p]),
+        'pbvi_env_clear': (C.c_int, [vp]),
+        'pbvi_rollout_env': (C.c_int, [vp, C.c_int, i32p, C.c_double, i32p, u8p, C.c_int, C.POINTER(C.c_int64), C.c_uint64,
+                                       C.c_uint64, C.c_int64, i32p, i32p, i32p, i32p, u8p]),
         'pbvi_beliefs_fetch': (C.c_int, [vp, vp]),
         'pbvi_beliefs_count': (C.c_int64, [vp]),
         'pbvi_mdp_value_iteration': (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, i32p, f64p, f64p, f64p,
@@ -456,6 +461,7 @@ class Engine:
         self.last_stats = {}                    # pbvi_stats_t of the last run()
         self._store_epoch = {'alpha': 0, 'belief': 0}
         self._resident = {'alpha': None, 'belief': None}     # store ids of the working alpha set / belief block
+        self._env_held = None                   # hold_environment: (array, channel map) that are the engine's environment
         self.B = 0
         self._vmax_cache, self._vmax_epochs = [], None
         self._arena = HostArena(first_block_bytes=128 * self.S * 8)
@@ -500,6 +506,7 @@ class Engine:
         that the replicas number their rows alike again (``dist.sharded_backup``)."""
         self._lib.pbvi_engine_after_oom(self._h)
         self._resident = {'alpha': None, 'belief': None}
+        self._env_held = None
         for k in self._store_epoch:                  # residency tags of AlphaVector / Belief objects no longer match
             self._store_epoch[k] += 1
         self._vmax_cache, self._vmax_epochs = [], None
@@ -1170,6 +1177,100 @@ class Engine:
                                                   steps.ctypes.data_as(i32p)))
         self.B = int(self._lib.pbvi_beliefs_count(self._h))
         return states, actions, observations, steps
+
+    def set_environment_frames(self, frames, channel_of_action) -> None:
+        """The observation source of ``rollout_env``: recorded frames ``[F, C, S]`` uint8 (``frames[f, c, s]`` = the observation
+        id emitted in frame ``f``, channel ``c``, at state ``s``) and the channel each action reads, ``[A]``
+        (``pbvi_env_set_frames``).  Replaces a table environment.  The bytes are device memory of the engine."""
+        fr = np.ascontiguousarray(frames, dtype=np.uint8)
+        ch = np.ascontiguousarray(channel_of_action, dtype=np.int32)
+        if fr.ndim != 3 or fr.shape[2] != self.S:
+            raise ValueError(f'frames must be [F, C, {self.S}]')
+        if ch.shape != (self.A,):
+            raise ValueError('channel_of_action must be [A]')
+        self._env_held = None
+        self._ck(self._lib.pbvi_env_set_frames(self._h, fr.ctypes.data_as(C.POINTER(C.c_uint8)), fr.shape[0], fr.shape[1],
+                                               ch.ctypes.data_as(C.POINTER(C.c_int32))))
+
+    def set_environment_table(self, obs_prob) -> None:
+        """The observation source of ``rollout_env``: another observation law, ``obs_prob[s', a, :]`` ``[S, A, O]`` fp64
+        (``pbvi_env_set_table``).  Replaces a frame environment."""
+        tb = np.ascontiguousarray(obs_prob, dtype=np.float64)
+        if tb.shape != (self.S, self.A, self.O):
+            raise ValueError(f'obs_prob must be [{self.S}, {self.A}, {self.O}]')
+        self._env_held = None
+        self._ck(self._lib.pbvi_env_set_table(self._h, tb.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def clear_environment(self) -> None:
+        """No environment; its device memory is returned (``pbvi_env_clear``)."""
+        self._env_held = None
+        self._ck(self._lib.pbvi_env_clear(self._h))
+
+    def hold_environment(self, env) -> None:
+        """``set_environment_frames`` / ``set_environment_table`` for a ``FrameEnvironment`` / ``TableEnvironment``, once: while
+        the holder's array (``env.frames`` / ``env.obs_prob``) is the one uploaded last, and -- for frames -- the channel map
+        equals the one uploaded with it, nothing is validated or moved again: an evaluation from every start cell calls
+        the agent many times with one movie.  Another channel map over the same frames is a new environment.  The
+        environment stays on the device until another is set, ``clear_environment`` or ``close``; the arrays are taken as
+        immutable once held (one changed in place has to be set anew with ``set_environment_*``)."""
+        frames = hasattr(env, 'frames')
+        payload = env.frames if frames else env.obs_prob
+        channels = np.array(env.channel_of_action, dtype=np.int32) if frames else None      # a copy: what was uploaded
+        if self._env_held is not None and self._env_held[0] is payload and (
+                not frames or (self._env_held[1] is not None and np.array_equal(self._env_held[1], channels))):
+            return
+        if frames:
+            self.set_environment_frames(payload, channels)
+        else:
+            self.set_environment_table(payload)
+        self._env_held = (payload, channels)
+
+    def rollout_env(self, policy: int, alpha_actions, start_states, end_mask, seed: int, T: int, first_sim_id: int = 0,
+                    gamma: float = 0.99, shifts=None, end_observation: int = -1):
+        """``rollout`` against the environment set with ``set_environment_*`` (``pbvi_rollout_env``): the successor is drawn
+        from the model, the observation comes from the environment, and a simulation whose observation the model gives
+        probability 0 stops there as lost.  ``policy``: 0 value-max, 1 Q, 2 infotaxis (``alpha_actions`` may be ``None``).
+        ``shifts`` ``[B]``: the frame each simulation starts at (frames only).  Returns ``(states, actions, observations,
+        steps, lost)``: ``rollout``'s four arrays and ``lost [B]`` uint8."""
+        policy = int(policy)
+        ss = np.ascontiguousarray(start_states, dtype=np.int32)
+        em = np.ascontiguousarray(end_mask, dtype=np.uint8)
+        i32p, u8p = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+        aap = None
+        if alpha_actions is not None:
+            aa = np.ascontiguousarray(alpha_actions, dtype=np.int32)
+            if policy != 2 and aa.shape != (self.alpha_count,):
+                raise ValueError('alpha_actions must be [V]')
+            aap = aa.ctypes.data_as(i32p)
+        if ss.shape != (self.B,):
+            raise ValueError('start_states must be [B]')
+        if em.shape != (self.S,):
+            raise ValueError('end_mask must be [S]')
+        if not (0 <= int(seed) < 1 << 64 and 0 <= int(first_sim_id) < 1 << 64):
+            raise ValueError('seed and first_sim_id must fit an unsigned 64-bit integer')
+        shp = None
+        if shifts is not None:
+            sh = np.ascontiguousarray(shifts, dtype=np.int64)
+            if sh.shape != (self.B,):
+                raise ValueError('shifts must be [B]')
+            shp = sh.ctypes.data_as(C.POINTER(C.c_int64))
+        T, B = int(T), self.B
+        if T >= 1 and (T + 1) * B <= 0x7fffffff:
+            states = np.empty((T + 1, B), dtype=np.int32)
+            actions = np.empty((T, B), dtype=np.int32)
+            observations = np.empty((T, B), dtype=np.int32)
+        else:                                    # the call refuses these: nothing is written
+            states = actions = observations = np.empty((0, B), dtype=np.int32)
+        steps = np.empty(B, dtype=np.int32)
+        lost = np.empty(B, dtype=np.uint8)
+        self._resident['belief'] = None
+        self._ck(self._lib.pbvi_rollout_env(self._h, policy, aap, float(gamma), ss.ctypes.data_as(i32p), em.ctypes.data_as(u8p),
+                                            int(end_observation), shp, int(first_sim_id), int(seed), T,
+                                            states.ctypes.data_as(i32p), actions.ctypes.data_as(i32p),
+                                            observations.ctypes.data_as(i32p), steps.ctypes.data_as(i32p),
+                                            lost.ctypes.data_as(u8p)))
+        self.B = int(self._lib.pbvi_beliefs_count(self._h))
+        return states, actions, observations, steps, lost
 
     def fetch_beliefs(self) -> np.ndarray:
         """The resident belief block, ``[B,S]`` in caller order."""

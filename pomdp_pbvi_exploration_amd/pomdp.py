@@ -1001,6 +1001,7 @@ class SimulationHistory(MDP_SimulationHistory):
         super().__init__(model, start_state)
         self._beliefs = [start_belief]
         self.observations = []
+        self.lost = False          # run against an environment: stopped at an observation the model gives probability 0
 
     @property
     def beliefs(self) -> list:
@@ -1224,15 +1225,26 @@ def rollout_numpy(model, alpha, alpha_actions, beliefs, start_states, seed: int,
     return _rollout_loop(m, block, choose, s, seed, first_sim_id, T, table_dtype, return_beliefs)
 
 
-def _rollout_loop(m, block, choose, s, seed: int, first_sim_id: int, T: int, table_dtype, return_beliefs: bool):
-    """The step loop of the counter-based rollouts (``rollout_numpy``, ``rollout_infotaxis_numpy``): ``choose()`` gives the
-    actions of the beliefs ``block`` holds; the uniform, the draw, the done-filter and the Bayes step are the same for
-    every policy.  ``m``: ``_rollout_tables``' tables, ``s``: the validated start states."""
+def _rollout_loop(m, block, choose, s, seed: int, first_sim_id: int, T: int, table_dtype, return_beliefs: bool,
+                  observe=None):
+    """The step loop of the counter-based rollouts (``rollout_numpy``, ``rollout_infotaxis_numpy``, ``rollout_env_numpy``):
+    ``choose()`` gives the actions of the beliefs ``block`` holds; the uniform, the done-filter and the Bayes step are the
+    same for every policy.  ``m``: ``_rollout_tables``' tables, ``s``: the validated start states.
+
+    ``observe=None``: the ``(observation, successor)`` pair comes from the model's joint row ``RTO[s, a, :, :]`` and a belief
+    is always normalised -- ``pbvi_rollout``'s step.  ``observe(t, rows, ids, a, sn, done)``: ``pbvi_rollout_env``'s step --
+    the successor from the marginal ``w[r] = sum_o RTO[s, a, o, r]`` (``o`` ascending, sequential adds), the observation of
+    the running simulations ``rows`` (global ids ``ids``) from the hook, and the lost rule (``advance_or_lose``); the
+    return value then ends with ``lost [n]`` uint8."""
     S, A, O, R = m.state_count, m.action_count, m.observation_count, m.reachable_state_count
     n = s.shape[0]
     rto = np.ascontiguousarray(m.reachable_transitional_observation_table, dtype=table_dtype).astype(np.float64).reshape(S, A, O * R)
     if not np.all(np.cumsum(rto, axis=2)[:, :, -1] > 0):
         raise ValueError('a row of RTO[s, a, :, :] sums to 0: nothing can follow that state-action pair')
+    if observe is not None:
+        marginal = np.zeros((S, A, R))
+        for o in range(O):
+            marginal += rto[:, :, o * R:(o + 1) * R]
     end = np.zeros(S, dtype=bool)
     end[m.end_states] = True
     with np.errstate(over='ignore'):
@@ -1241,22 +1253,199 @@ def _rollout_loop(m, block, choose, s, seed: int, first_sim_id: int, T: int, tab
     actions = np.full((T, n), -1, dtype=np.int32)
     observations = np.full((T, n), -1, dtype=np.int32)
     steps = np.full(n, T, dtype=np.int32)
+    lost = np.zeros(n, dtype=np.uint8)
     states[0] = s
     alive = np.arange(n)
     for t in range(T):
         if alive.size == 0:
             break
         a = choose()
-        k = rollout_draw(rto[s, a], rollout_uniform(seed, ids[alive], t))
-        o, sn = k // R, m.reachable_states[s, a, k % R]
-        done = end[sn]
+        if observe is None:
+            k = rollout_draw(rto[s, a], rollout_uniform(seed, ids[alive], t))
+            o, sn = k // R, m.reachable_states[s, a, k % R]
+            done = end[sn]
+        else:
+            sn = m.reachable_states[s, a, rollout_draw(marginal[s, a], rollout_uniform(seed, ids[alive], t))]
+            done = end[sn]
+            o = observe(t, alive, ids[alive], a, sn, done)
         states[t + 1, alive], actions[t, alive], observations[t, alive] = sn, a, o
         steps[alive[done]] = t + 1
-        block.advance(a, o, ~done)
-        alive, s = alive[~done], sn[~done]
+        go = ~done
+        if observe is None:
+            block.advance(a, o, go)
+        else:
+            gone = block.advance_or_lose(a, o, go)
+            steps[alive[gone]] = t + 1
+            lost[alive[gone]] = 1
+            go = go & ~gone
+        alive, s = alive[go], sn[go]
+    out = (states, actions, observations, steps)
     if return_beliefs:
-        return states, actions, observations, steps, (block.b if alive.size else np.zeros((0, S)))
-    return states, actions, observations, steps
+        out += (block.b if alive.size else np.zeros((0, S)),)
+    return out + (lost,) if observe is not None else out
+
+
+# --------------------------------------------------------------------------- #
+# Environments: the observation source of ``rollout_env_numpy`` / ``pbvi_rollout_env``
+# --------------------------------------------------------------------------- #
+class FrameEnvironment:
+    """Recorded observations: ``frames[f, c, s]`` (uint8 ``[F, C, S]``) is the observation id emitted in frame ``f``, channel
+    ``c``, at state ``s``; action ``a`` reads channel ``channel_of_action[a]``.  Simulation ``b`` reads frame
+    ``shifts[b] + t`` at step ``t`` (``shifts``: one integer for all, or one per simulation).  ``end_observation >= 0``:
+    the observation on landing in an end state, whatever the frame says.  A plain data holder: the reference's plume
+    movies (``RealSimulationSetAlt``: nose and ground data, ``C = 2``) in the form the engine takes.  The frames are taken
+    as immutable once the holder is built: they are scanned once, here (``largest``), a contiguous uint8 array is kept
+    without a copy, and an engine that holds them does not upload them again -- build a new holder for edited frames."""
+
+    def __init__(self, frames, channel_of_action, shifts=0, end_observation: int = -1):
+        raw = np.asarray(frames)
+        if raw.ndim != 3 or raw.shape[0] < 1 or raw.shape[1] < 1:
+            raise ValueError('frames must be a [F, C, S] array with F, C >= 1')
+        if raw.dtype != np.uint8 and (raw.min() < 0 or raw.max() > 255):
+            raise ValueError('frame entries must fit one byte')
+        self.frames = np.ascontiguousarray(raw, dtype=np.uint8)
+        self.channel_of_action = np.ascontiguousarray(channel_of_action, dtype=np.int32)
+        self.shifts = np.asarray(shifts, dtype=np.int64)
+        self.end_observation = int(end_observation)
+        self.largest = int(self.frames.max())                  # scanned once: check() is called per rollout
+        C = self.frames.shape[1]
+        if self.channel_of_action.ndim != 1 or self.channel_of_action.min() < 0 or self.channel_of_action.max() >= C:
+            raise ValueError('channel_of_action must be [A] with entries in [0, C)')
+        if self.shifts.ndim > 1 or (self.shifts.size and self.shifts.min() < 0):
+            raise ValueError('shifts must be one non-negative integer or a [n] array of them')
+
+    def check(self, S: int, A: int, O: int, n: int, T: int) -> np.ndarray:
+        """Raises ``ValueError`` where ``pbvi_env_set_frames`` / ``pbvi_rollout_env`` refuse; returns the ``[n]`` shifts."""
+        if O > 255:
+            raise ValueError('frames hold one byte per observation, so O must be at most 255')
+        if self.frames.shape[2] != S or self.channel_of_action.shape != (A,):
+            raise ValueError(f'frames must be [F, C, {S}] and channel_of_action [{A}]')
+        if self.largest >= O or self.end_observation >= O:
+            raise ValueError(f'a frame entry (or end_observation) is not an observation in [0, {O})')
+        if self.shifts.ndim == 1 and self.shifts.shape != (n,):
+            raise ValueError(f'shifts must be one integer or [{n}]')
+        sh = np.broadcast_to(self.shifts, (n,))
+        if (int(sh.max()) if n else 0) + T > self.frames.shape[0]:
+            raise ValueError(f'max(shift) + T exceeds the {self.frames.shape[0]} frames of the environment')
+        return sh
+
+    def rows(self, lo: int, hi: int) -> 'FrameEnvironment':
+        """The environment of simulations ``lo:hi`` (the frames are shared, per-simulation shifts are sliced)."""
+        import copy
+        part = copy.copy(self)                                  # (no second scan of the frames)
+        part.shifts = self.shifts[lo:hi] if self.shifts.ndim else self.shifts
+        return part
+
+
+class TableEnvironment:
+    """Another observation law: ``obs_prob[s', a, :]`` (``[S, A, O]``, non-negative, every row with mass) is the law of the
+    observation after landing in ``s'`` with action ``a`` -- the reference's ``SimulationSetAltProb``.
+    ``end_observation >= 0``: the observation on landing in an end state."""
+
+    def __init__(self, obs_prob, end_observation: int = -1):
+        self.obs_prob = np.ascontiguousarray(obs_prob, dtype=np.float64)
+        self.end_observation = int(end_observation)
+        if self.obs_prob.ndim != 3:
+            raise ValueError('obs_prob must be a [S, A, O] array')
+        if not np.all(np.isfinite(self.obs_prob)) or self.obs_prob.min() < 0:
+            raise ValueError('obs_prob has a negative or non-finite entry')
+        if not np.all(np.cumsum(self.obs_prob, axis=2)[:, :, -1] > 0):
+            raise ValueError('a row obs_prob[s, a, :] sums to 0')
+
+    def check(self, S: int, A: int, O: int, n: int, T: int) -> None:
+        if self.obs_prob.shape != (S, A, O):
+            raise ValueError(f'obs_prob must be [{S}, {A}, {O}]')
+        if self.end_observation >= O:
+            raise ValueError(f'end_observation is not an observation in [0, {O})')
+
+    def rows(self, lo: int, hi: int) -> 'TableEnvironment':
+        return self
+
+
+def record_frames(obs_table, F: int, seed: int) -> np.ndarray:
+    """``F`` frames drawn from an observation table ``[S, A, O]``: uint8 ``[F, A, S]`` (one channel per action, so
+    ``channel_of_action = arange(A)``) with ``frames[f, a, s]`` drawn from ``obs_table[s, a, :]`` by ``rollout_draw``'s prefix
+    rule with the uniform ``synth.uniform01(seed, (f * A + a) * S + s)``.  A deterministic stand-in for an intermittent plume
+    movie whose law is the model's own."""
+    from . import synth
+    tab = np.asarray(obs_table, dtype=np.float64)
+    if tab.ndim != 3 or tab.shape[2] > 255:
+        raise ValueError('obs_table must be [S, A, O] with O <= 255')
+    F = int(F)
+    if F < 1:
+        raise ValueError('F must be at least 1')
+    if not 0 <= int(seed) < 1 << 64:
+        raise ValueError('seed must fit an unsigned 64-bit integer')
+    S, A, O = tab.shape
+    rows = np.ascontiguousarray(tab.transpose(1, 0, 2)).reshape(A * S, O)          # row a * S + s
+    c = np.cumsum(rows, axis=1)
+    if not np.all(c[:, -1] > 0):
+        raise ValueError('a row obs_table[s, a, :] sums to 0')
+    last_pos = O - 1 - np.argmax(rows[:, ::-1] > 0, axis=1)
+    cell = np.arange(A * S, dtype=np.uint64)
+    frames = np.empty((F, A, S), dtype=np.uint8)
+    for f in range(F):
+        u = synth.uniform01(int(seed), np.uint64(f * A * S) + cell)
+        hit = (u * c[:, -1])[:, None] < c
+        frames[f] = np.where(hit.any(axis=1), np.argmax(hit, axis=1), last_pos).reshape(A, S)
+    return frames
+
+
+def rollout_env_numpy(model, env, policy: int, alpha, alpha_actions, beliefs, start_states, seed: int, first_sim_id: int,
+                      T: int, gamma: float = 0.99, table_dtype=np.float64, return_beliefs: bool = False):
+    """``T`` lock-step steps against an environment, on the host: what ``pbvi_rollout_env`` computes on the device.
+
+    ``policy``: 0 ``alpha_actions[argmax_v b.alpha_v]``, 1 ``argmax_a Q(b, a)``, 2 infotaxis (``alpha`` and ``alpha_actions``
+    may be ``None``).  Per step ``t`` and running simulation ``i`` in state ``s`` with action ``a``: the successor ``s'`` is
+    drawn from ``w[r] = sum_o RTO[s, a, o, r]`` with ``u1 = rollout_uniform(seed, i, t)``; the observation is
+    ``env.end_observation`` on landing in an end state when that is ``>= 0``, else ``frames[shift_i + t, channel[a], s']``
+    (``FrameEnvironment``) or drawn from ``obs_prob[s', a, :]`` with the second uniform ``u2 = rollout_uniform(seed, i,
+    2**32 + t)`` (``TableEnvironment``); an end state finishes the simulation; otherwise a Bayes step whose un-normalised
+    mass is 0 or not finite -- an observation impossible under the model -- stops it as LOST at this step (``steps = t + 1``,
+    recorded ``a``, ``o``, ``s'``, no NaN belief), and any other is normalised.  ``env.shifts`` belong to the rows given.
+    Returns ``rollout_numpy``'s arrays and then ``lost [n]`` uint8."""
+    from types import SimpleNamespace
+    m = _rollout_tables(model)
+    S, A, O = m.state_count, m.action_count, m.observation_count
+    if policy not in (0, 1, 2):
+        raise ValueError(f'policy must be 0 (value-max), 1 (Q) or 2 (infotaxis), not {policy!r}')
+    if not isinstance(env, (FrameEnvironment, TableEnvironment)):
+        raise ValueError('env must be a FrameEnvironment or a TableEnvironment')
+    T = int(T)
+    if T < 1:
+        raise ValueError('T must be at least 1')
+    if T >= 1 << 31:
+        raise ValueError('T must be below 2**31')
+    b = np.array(beliefs, dtype=np.float64)
+    s = np.asarray(start_states).astype(np.int64)
+    n = b.shape[0]
+    if b.ndim != 2 or b.shape[1] != S:
+        raise ValueError(f'beliefs must be a [*, {S}] array')
+    if s.shape != (n,) or (n and (s.min() < 0 or s.max() >= S)):
+        raise ValueError('start_states must be [n] with entries in [0, S)')
+    if policy == 2:
+        block = _HostBeliefBlock(m, None, b)
+        choose = lambda: block.infotaxis_actions(table_dtype)
+    else:
+        alpha = np.asarray(alpha, dtype=np.float64)
+        acts = np.asarray(alpha_actions).astype(np.int64)
+        if alpha.ndim != 2 or alpha.shape[1] != S:
+            raise ValueError(f'alpha must be a [*, {S}] array')
+        if acts.shape != (alpha.shape[0],) or acts.min() < 0 or acts.max() >= A:
+            raise ValueError('alpha_actions must be [V] with entries in [0, A)')
+        block = _HostBeliefBlock(m, SimpleNamespace(alpha_vector_array=alpha), b)
+        choose = (lambda: block.best_actions(gamma)) if policy == 1 else (lambda: acts[block.best_vectors()])
+    shifts = env.check(S, A, O, n, T)
+    end_obs = env.end_observation
+
+    def observe(t, rows, ids, a, sn, done):
+        if isinstance(env, FrameEnvironment):
+            o = env.frames[shifts[rows] + t, env.channel_of_action[a], sn].astype(np.int64)
+        else:
+            o = rollout_draw(env.obs_prob[sn, a], rollout_uniform(seed, ids, (1 << 32) + t))
+        return np.where(done, end_obs, o) if end_obs >= 0 else o
+
+    return _rollout_loop(m, block, choose, s, seed, first_sim_id, T, table_dtype, return_beliefs, observe)
 
 
 # --------------------------------------------------------------------------- #
@@ -1363,16 +1552,31 @@ class _HostBeliefBlock:
         """Infotaxis: the first ``argmin_a`` of the expected successor entropy of every belief of the block."""
         return infotaxis_numpy(self.m, self.b, table_dtype)[1]
 
-    def advance(self, actions: np.ndarray, observations: np.ndarray, keep: np.ndarray) -> None:
+    def _push(self, actions: np.ndarray, observations: np.ndarray) -> np.ndarray:
+        """The un-normalised Bayes step of every row: ``u[b, s'] = sum_{(s,r): rs[s,a,r] = s'} b[s] RTO[s,a,o,r]``."""
         m, n = self.m, self.b.shape[0]
         S = m.state_count
         w = m.reachable_transitional_observation_table[:, actions, observations, :] * self.b.T[:, :, None]   # [S,n,R]
         tgt = m.reachable_states[:, actions, :]                                                             # [S,n,R]
         flat = (n, S * m.reachable_state_count)
         idx = tgt.swapaxes(0, 1).reshape(flat) + (np.arange(n)[:, None] * S)
-        nb = np.bincount(idx.ravel(), weights=w.swapaxes(0, 1).reshape(flat).ravel(), minlength=n * S).reshape((-1, S))
+        return np.bincount(idx.ravel(), weights=w.swapaxes(0, 1).reshape(flat).ravel(), minlength=n * S).reshape((-1, S))
+
+    def advance(self, actions: np.ndarray, observations: np.ndarray, keep: np.ndarray) -> None:
+        nb = self._push(actions, observations)
         nb /= np.sum(nb, axis=1)[:, None]
         self.b = nb[keep]
+
+    def advance_or_lose(self, actions: np.ndarray, observations: np.ndarray, keep: np.ndarray) -> np.ndarray:
+        """``advance`` with the lost rule of ``rollout_env_numpy``: a kept row whose un-normalised mass ``Z`` is 0 or not
+        finite (an observation the model gives no probability) is dropped too, before any division.  Returns the ``[n]``
+        mask of the rows lost."""
+        nb = self._push(actions, observations)
+        z = np.sum(nb, axis=1)
+        lost = keep & ((z == 0) | ~np.isfinite(z))
+        go = keep & ~lost
+        self.b = nb[go] / z[go][:, None]
+        return lost
 
 
 class _DeviceBeliefBlock:
@@ -1553,7 +1757,7 @@ class Agent:
                                    max_steps: int = 1000, start_states: Union[list, int, None] = None,
                                    initial_beliefs=None, reward_discount: float = 0.99,
                                    print_progress: bool = True, print_stats: bool = True,
-                                   device_rng_seed: Union[int, None] = None):
+                                   device_rng_seed: Union[int, None] = None, environment=None):
         """n simulations advanced in lock-step (``src/pomdp.py:3203-3380``).  Per step: best α per belief
         (GEMM + first-max), host simulator draw, Bayes update of every belief, done-filter.  With the value
         function on the GPU the belief block lives in the HIP engine for the whole run; only the ``[n]`` index,
@@ -1564,7 +1768,14 @@ class Agent:
         definition; simulation ``i`` draws ``rollout_uniform(seed, i, t)`` at step ``t``) -- the whole step loop runs in
         the HIP engine (``pbvi_rollout``) when the value function is on the GPU, on the host otherwise, and the
         trajectories do not depend on which, up to exact ties between actions.  Only the start states, when none are
-        given, still come from NumPy's stream."""
+        given, still come from NumPy's stream.
+
+        ``environment`` (a ``FrameEnvironment`` or ``TableEnvironment``; needs ``device_rng_seed``): the observations come
+        from it instead of the model (``rollout_env_numpy``'s definition, ``pbvi_rollout_env`` on the GPU), per-simulation
+        shifts are ``[n]``, and every returned ``SimulationHistory`` says in ``lost`` whether it stopped at an observation the
+        model gives probability 0."""
+        if environment is not None and device_rng_seed is None:
+            raise ValueError('environment needs device_rng_seed: the NumPy-stream path simulates the model itself')
         on_gpu = self._on_gpu()
         vf = self.value_function
         model = self.model.gpu_model if on_gpu else self.model.cpu_model
@@ -1582,7 +1793,7 @@ class Agent:
         start_state_array = simulator_set.initialize_simulations(n, start_states)
         if device_rng_seed is not None:
             return self._run_counter_rollouts(model, simulator_set, b0, np.asarray(start_state_array), int(device_rng_seed),
-                                              max_steps, reward_discount, print_stats)
+                                              max_steps, reward_discount, print_stats, environment)
         block = (_DeviceBeliefBlock if on_gpu else _HostBeliefBlock)(model, vf, b0)
 
         done_at_step = np.full(n, -1, dtype=int)
@@ -1661,14 +1872,47 @@ class Agent:
                                                                  seed, 0, T, self.lookahead, self.gamma)
         return states, actions, observations, steps
 
+    def _env_policy(self) -> int:
+        """This agent's policy as ``pbvi_rollout_env`` numbers it."""
+        return self.lookahead
+
+    def _env_trajectories(self, model: Model, b0: np.ndarray, start_states: np.ndarray, seed: int, T: int, env):
+        """``(states, actions, observations, steps, lost)`` of the counter-based rollout of this agent's policy against
+        ``env``: on the device when the agent is, ``ROLLOUT_CHUNK`` simulations per call with the shifts sliced alongside."""
+        policy, vf, n = self._env_policy(), self.value_function, b0.shape[0]
+        alpha, acts = (None, None) if policy == 2 else (vf.alpha_vector_array, vf.actions)
+        if not self._on_gpu():
+            return rollout_env_numpy(model, env, policy, alpha, acts, b0, start_states, seed, 0, T, self.gamma)
+        env.check(model.state_count, model.action_count, model.observation_count, n, T)
+        eng = model.engine
+        if policy != 2:
+            eng.sync_rows('alpha', vf.alpha_vector_list, lambda v: v.values)
+        end_mask = np.zeros(model.state_count, dtype=np.uint8)
+        end_mask[np.asarray(model.end_states, dtype=np.int64)] = 1
+        frames = isinstance(env, FrameEnvironment)
+        eng.hold_environment(env)                               # uploaded once; later calls with the same arrays find it there
+        parts = []
+        for i0 in range(0, n, self.ROLLOUT_CHUNK):
+            i1 = min(n, i0 + self.ROLLOUT_CHUNK)
+            eng.set_beliefs(b0[i0:i1])
+            shifts = np.broadcast_to(env.rows(i0, i1).shifts, (i1 - i0,)) if frames else None
+            parts.append(eng.rollout_env(policy, acts, start_states[i0:i1], end_mask, seed, T, first_sim_id=i0,
+                                         gamma=self.gamma, shifts=shifts, end_observation=env.end_observation))
+        states, actions, observations = (np.concatenate([p[k] for p in parts], axis=1) for k in range(3))
+        return states, actions, observations, np.concatenate([p[3] for p in parts]), np.concatenate([p[4] for p in parts])
+
     def _run_counter_rollouts(self, model: Model, simulator_set: SimulationSet, b0: np.ndarray, start_states: np.ndarray,
-                              seed: int, max_steps: int, reward_discount: float, print_stats: bool):
+                              seed: int, max_steps: int, reward_discount: float, print_stats: bool, environment=None):
         """``run_n_simulations_parallel(device_rng_seed=seed)``: the trajectories from ``pbvi_rollout`` (value function on
         the GPU; more than ``ROLLOUT_CHUNK`` simulations in chunks with ``first_sim_id`` advanced) or ``rollout_numpy``,
         the rewards from the recorded ``(s, a, s', o)`` afterwards, the result in ``run_n_simulations_parallel``'s form."""
         n, T = b0.shape[0], int(max_steps)
         t0 = datetime.now()
-        states, actions, observations, steps = self._counter_trajectories(model, b0, start_states, seed, T)
+        lost = np.zeros(n, dtype=np.uint8)
+        if environment is None:
+            states, actions, observations, steps = self._counter_trajectories(model, b0, start_states, seed, T)
+        else:
+            states, actions, observations, steps, lost = self._env_trajectories(model, b0, start_states, seed, T, environment)
         ran = actions >= 0                                       # [T, n] steps that were taken
         rewards_history = np.zeros((T, n))
         if ran.any():
@@ -1684,6 +1928,7 @@ class Agent:
             h.actions = actions[:last, i].tolist()
             h.observations = observations[:last, i].tolist()
             h.rewards = rewards_history[:last, i].tolist()
+            h.lost = bool(lost[i])
             histories.append(h)
         n_done = int(np.sum(np.isin(states[steps, np.arange(n)], model.end_states)))
         if print_stats:
@@ -1710,6 +1955,9 @@ class Infotaxis_Agent(Agent):
 
     def _block_actions(self, block) -> np.ndarray:
         return block.infotaxis_actions()
+
+    def _env_policy(self) -> int:
+        return 2
 
     def get_best_action(self, belief):
         """The infotaxis action for one ``Belief`` (returns int) or a ``[n,S]`` array."""
