@@ -702,6 +702,32 @@ int64_t pbvi_debug_slabs(pbvi_engine_t* e, void* out, int64_t cap_bytes);
 /* Tests only: set every byte of that buffer to `byte` (its low 8 bits), so that a test can tell what the next score GEMM
  * wrote from what an earlier one left there.  PBVI_EINVAL when no score GEMM has run. */
 int pbvi_debug_slabs_fill(pbvi_engine_t* e, int byte);
+/*
+ * Tests only: the score probe.  Off by default (one untaken branch in the scoring stage).  While enabled, the scoring
+ * stage of every backup (pbvi_backup_run and what is built on it) ends with a copy -- on the pipeline's stream, behind the
+ * argmax and in front of the refinement, which rewrites best_v / best_score / E in place -- of what the argmax read and
+ * wrote, for the resident B beliefs IN ENGINE ORDER, the G = A * O groups (g = a * O + o) and the V alpha rows:
+ *   score      [B][G][V] double  the score the argmax read, through the same slab view (belief-side rows, split-K slabs,
+ *                                stream-K continuation tiles, the folded matrix of a Gamma-tiled call)
+ *   mag        [B][G]    double  the magnitude score that scales the tie window
+ *   E          [B][G]    double  the window, best_v [B][G] int32 and best_score [B][G] double as the argmax wrote them
+ *   queue      [qcount]  int32   the near-tie queue as the argmax left it (entries b * G + g, slot order not defined)
+ *   dead       [B][G]    uint8   the dead-triple flags the argmax was given (all 0 when it was given none)
+ *   perm       [B]       int32   caller's row of engine row b (the resident block's order: fetch before replacing the block)
+ *   dims       [8]       int64   B, G, V, qcount, belief-side formulation (0/1), tile pairs of the fp64 MFMA GEMM (0: the
+ *                                plain kernel or an fp32 GEMM), its K parts, Gamma chunks (ScoreStage: 0 = belief side)
+ *   scalars    [4]       double  split (0/1), chain_steps[0] (-1: none), the tol_rel passed to the argmax (< 0: derived
+ *                                on the device from chain_steps), tol_extra
+ * An fp64 engine behind its fp32 screen captures the screen's stage (the one whose window decides what is re-decided); a
+ * pure fp64 engine its own: E = 0, no queue.  The buffers are working buffers of the engine (pbvi_device_bytes,
+ * pbvi_debug_alloc_limit, released by pbvi_engine_after_oom and by disabling the probe).  A backup with
+ * B * G * V > 2^24 fails with PBVI_EINVAL while the probe is on.  The value-max, Q-value and infotaxis GEMMs are not covered.
+ * pbvi_debug_score_probe_fetch copies the last capture to host arrays; any pointer may be NULL (call it with dims alone
+ * to size the rest).  PBVI_EINVAL when nothing was captured since the probe was enabled.
+ */
+int pbvi_debug_score_probe(pbvi_engine_t* e, int enable);
+int pbvi_debug_score_probe_fetch(pbvi_engine_t* e, int64_t* dims, double* scalars, double* score, double* mag, double* E,
+                                 int32_t* best_v, double* best_score, int32_t* queue, uint8_t* dead, int32_t* perm);
 
 /* Bytes of device memory currently held by the handle. */
 int64_t pbvi_device_bytes(const pbvi_engine_t* e);

@@ -140,6 +140,11 @@ template <typename T>
 hipError_t launch_fold_chunk(SlabView<T> sv, int B, int G, int Vc, int V, int v0, int tail_cols, T* dst, int64_t ldd,
                              const int* chain, int* chain_max, hipStream_t st);
 
+// Test-only score probe (pbvi_debug_score_probe): score [B][G][V] = (double) sv.score(b, g, V, v) and mag [B][G] =
+// sv.magnitude(b, g, G, V), read through the SlabView the argmax was given.  B * G * V <= 2^24.
+template <typename T>
+hipError_t launch_score_probe(SlabView<T> sv, int V, int G, int B, double* score, double* mag, hipStream_t st);
+
 // Work list of the refinement: entries with many near-tied candidates hand their (entry, candidate) pairs to a
 // grid-wide pass instead of scoring them one block per entry (device memory; items_v == nullptr: all in-block).
 struct RefineWork {

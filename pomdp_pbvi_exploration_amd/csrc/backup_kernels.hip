@@ -919,6 +919,32 @@ hipError_t launch_fold_chunk(SlabView<T> sv, int B, int G, int Vc, int V, int v0
 }
 
 // ------------------------------------------------------------------------- //
+// Test-only score probe (pbvi_debug_score_probe): every score and magnitude k_argmax was given, read element by element
+// through the same SlabView (SlabView::score / magnitude: push rows, split-K slabs, stream-K continuation tiles, the
+// folded matrix of the tiled route) and widened to double.  One thread per (b, g, v); the thread of v == 0 also
+// writes the pair's magnitude.  Not on any default path.
+// ------------------------------------------------------------------------- //
+template <typename T>
+__global__ void k_score_probe(SlabView<T> sv, int V, int G, int B, double* __restrict__ score, double* __restrict__ mag) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)B * G * V) return;
+    const int v = (int)(i % V);
+    const int64_t gw = i / V;
+    const int b = (int)(gw / G), g = (int)(gw % G);
+    score[i] = (double)sv.score(b, g, V, v);
+    if (v == 0) mag[gw] = sv.magnitude(b, g, G, V);
+}
+
+template <typename T>
+hipError_t launch_score_probe(SlabView<T> sv, int V, int G, int B, double* score, double* mag, hipStream_t st) {
+    const int64_t n = (int64_t)B * G * V;
+    if (n <= 0) return hipSuccess;
+    if (n > ((int64_t)1 << 24)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_score_probe<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, sv, V, G, B, score, mag);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------- //
 // fp64 re-decision of a queued (belief, group): every candidate whose f32 score is
 // within the error window of the f32 maximum is re-scored exactly (f32 x f32 products
 // are exact in f64) and the first maximum of the exact scores wins.
@@ -3064,6 +3090,7 @@ hipError_t launch_infotaxis(const T* bel, int ldb, int B, ModelView<T> mv, const
                                          int32_t*, double*, double*, int32_t*, int*, hipStream_t, double, int);        \
     template hipError_t launch_fold_chunk<T>(SlabView<T>, int, int, int, int, int, int, T*, int64_t, const int*, int*,   \
                                              hipStream_t);                                                             \
+    template hipError_t launch_score_probe<T>(SlabView<T>, int, int, int, double*, double*, hipStream_t);              \
     template hipError_t launch_refine<T, T>(bool, SlabView<T>, int, int, int, const int32_t*, const int*, const T*, int, \
                                          const T*, int, ModelView<T>, double, const int32_t*, const int32_t*,          \
                                          const uint8_t*, int32_t*, double*, double*, int*, RefineWork, hipStream_t);   \

@@ -897,6 +897,9 @@ class EngineBase {
     virtual int q_values(double gamma, double* out_q, int32_t* out_action, int32_t* out_best) = 0;
     virtual int64_t debug_slabs(void* out, int64_t cap_bytes) = 0;
     virtual int debug_slabs_fill(int byte) = 0;
+    virtual int debug_score_probe(int enable) = 0;
+    virtual int debug_score_probe_fetch(int64_t* dims, double* scalars, double* score, double* mag, double* err,
+                                        int32_t* best_v, double* best_score, int32_t* queue, uint8_t* dead, int32_t* perm) = 0;
     // source: the policy of the step loop (RolloutSource); alpha_actions and gamma are read by the sources that need them
     virtual int rollout(int source, const int32_t* alpha_actions, double gamma, const int32_t* start_states,
                         const uint8_t* end_mask, uint64_t first_sim_id, uint64_t seed, int64_t T, int32_t* out_states,
@@ -1023,6 +1026,18 @@ class EngineT : public EngineBase {
     int formulation_ = 0;                                   // 0 auto, 1 project alpha-vectors, 2 project beliefs
     int last_formulation_ = 1;
     int64_t f64_pairs_ = 0;                                 // tile pairs of the last fp64 MFMA GEMM (0: plain kernel)
+    int f64_split_ = 1;                                     // its K parts
+    // Test-only score probe (pbvi_debug_score_probe): the scoring stage of THIS engine (an fp64 engine's screen has its
+    // own) copies what its argmax read and wrote into these buffers before any later stage touches them.
+    bool probe_on_ = false;
+    uint64_t probe_seq_ = 0;                                // order of the capture among all engines' captures; 0 = none
+    DevBuf probe_score_{mem_}, probe_mag_{mem_}, probe_err_{mem_}, probe_bv_{mem_}, probe_bs_{mem_}, probe_queue_{mem_}, probe_dead_{mem_}, probe_words_{mem_};
+    struct ProbeInfo {
+        int64_t B = 0, G = 0, V = 0, f64_pairs = 0;
+        int push = 0, split = 0, chunks = 0, f64_split = 1;
+        bool has_chain = false;
+        double tol_rel = 0.0, tol_extra = 0.0;
+    } probe_info_;
     const int32_t* res_action_ = nullptr;                  // results in caller order
     const int32_t* res_best_ = nullptr;
     int64_t res_unique_ = 0;
@@ -1937,6 +1952,121 @@ class EngineT : public EngineBase {
         return PBVI_OK;
     }
 
+    // ---- test-only score probe (pbvi_debug_score_probe / _fetch) ---- //
+    static uint64_t next_probe_seq() {
+        static std::atomic<uint64_t> seq{0};
+        return ++seq;
+    }
+    void probe_release() {
+        for (DevBuf* b : {&probe_score_, &probe_mag_, &probe_err_, &probe_bv_, &probe_bs_, &probe_queue_, &probe_dead_, &probe_words_})
+            b->release();
+        probe_seq_ = 0;
+    }
+    int debug_score_probe(int enable) override {
+        HIPCHK(hipSetDevice(device_));
+        HIPCHK(hipStreamSynchronize(stream_));
+        probe_on_ = enable != 0;
+        probe_seq_ = 0;                                      // a capture counts from the moment the probe was enabled
+        if (!probe_on_) probe_release();
+        if (screen_) {
+            screen_->probe_on_ = probe_on_;
+            screen_->probe_seq_ = 0;
+            if (!probe_on_) screen_->probe_release();
+        }
+        return PBVI_OK;
+    }
+    // End of the scoring stage, behind launch_argmax and in front of every later stage, on the pipeline's stream: what the
+    // argmax read (scores and magnitudes through its SlabView) and what it wrote (windows, first maxima, queue).
+    int probe_capture(const SlabView<T>& sv, const ScoreIO& io, const ScoreStage<T>& out) {
+        int rc;
+        const int64_t G = (int64_t)A_ * O_, pairs = B_ * G, n = pairs * V_;
+        probe_seq_ = 0;                                      // (a stage that fails below leaves nothing to fetch)
+        if (n > ((int64_t)1 << 24))
+            FAIL(PBVI_EINVAL, "score probe: B * A * O * V = " + std::to_string(n) + " exceeds 2^24 (the probe is for tests)");
+        if ((rc = probe_score_.ensure((size_t)n * sizeof(double)))) return rc;
+        if ((rc = probe_mag_.ensure((size_t)pairs * sizeof(double)))) return rc;
+        if ((rc = probe_err_.ensure((size_t)pairs * sizeof(double)))) return rc;
+        if ((rc = probe_bs_.ensure((size_t)pairs * sizeof(double)))) return rc;
+        if ((rc = probe_bv_.ensure((size_t)pairs * sizeof(int32_t)))) return rc;
+        if ((rc = probe_queue_.ensure((size_t)pairs * sizeof(int32_t)))) return rc;
+        if ((rc = probe_dead_.ensure((size_t)pairs))) return rc;
+        if ((rc = probe_words_.ensure(2 * sizeof(int)))) return rc;
+        HIPCHK(launch_score_probe<T>(sv, (int)V_, (int)G, (int)B_, probe_score_.as<double>(), probe_mag_.as<double>(), stream_));
+        HIPCHK(hipMemcpyAsync(probe_err_.p, io.err, (size_t)pairs * sizeof(double), hipMemcpyDeviceToDevice, stream_));
+        HIPCHK(hipMemcpyAsync(probe_bs_.p, io.best_score, (size_t)pairs * sizeof(double), hipMemcpyDeviceToDevice, stream_));
+        HIPCHK(hipMemcpyAsync(probe_bv_.p, io.best_v, (size_t)pairs * sizeof(int32_t), hipMemcpyDeviceToDevice, stream_));
+        if (io.queue != nullptr) {
+            HIPCHK(hipMemcpyAsync(probe_queue_.p, io.queue, (size_t)pairs * sizeof(int32_t), hipMemcpyDeviceToDevice, stream_));
+            HIPCHK(hipMemcpyAsync(probe_words_.p, io.qcount, sizeof(int), hipMemcpyDeviceToDevice, stream_));
+        } else {
+            HIPCHK(hipMemsetAsync(probe_words_.p, 0, sizeof(int), stream_));
+        }
+        if (io.dead != nullptr) HIPCHK(hipMemcpyAsync(probe_dead_.p, io.dead, (size_t)pairs, hipMemcpyDeviceToDevice, stream_));
+        else HIPCHK(hipMemsetAsync(probe_dead_.p, 0, (size_t)pairs, stream_));
+        if (out.chain != nullptr)
+            HIPCHK(hipMemcpyAsync(probe_words_.as<int>() + 1, out.chain, sizeof(int), hipMemcpyDeviceToDevice, stream_));
+        probe_info_.B = B_;
+        probe_info_.G = G;
+        probe_info_.V = V_;
+        probe_info_.f64_pairs = out.f64_pairs;
+        probe_info_.f64_split = f64_split_;
+        probe_info_.push = sv.push;
+        probe_info_.split = out.split;
+        probe_info_.chunks = out.chunks;
+        probe_info_.has_chain = out.chain != nullptr;
+        probe_info_.tol_rel = out.tol_rel;
+        probe_info_.tol_extra = io.tol_extra;
+        probe_seq_ = next_probe_seq();
+        return PBVI_OK;
+    }
+    // The capture of THIS engine to host arrays (any of them may be nullptr); perm is the caller's (debug_score_probe_fetch)
+    int probe_copy_out(int64_t* dims, double* scalars, double* score, double* mag, double* err, int32_t* best_v,
+                       double* best_score, int32_t* queue, uint8_t* dead) {
+        const ProbeInfo& pi = probe_info_;
+        const int64_t pairs = pi.B * pi.G;
+        HIPCHK(hipSetDevice(device_));
+        HIPCHK(hipStreamSynchronize(stream_));
+        int w[2] = {0, -1};
+        HIPCHK(hipMemcpy(w, probe_words_.p, (pi.has_chain ? 2 : 1) * sizeof(int), hipMemcpyDeviceToHost));
+        if (w[0] < 0 || w[0] > pairs) FAIL(PBVI_ERUNTIME, "score probe: queue count out of range");
+        if (dims) {
+            const int64_t d[8] = {pi.B, pi.G, pi.V, w[0], pi.push, pi.f64_pairs, pi.f64_split, pi.chunks};
+            std::copy(d, d + 8, dims);
+        }
+        if (scalars) {
+            scalars[0] = (double)pi.split;
+            scalars[1] = pi.has_chain ? (double)w[1] : -1.0;
+            scalars[2] = pi.tol_rel;
+            scalars[3] = pi.tol_extra;
+        }
+        if (score) HIPCHK(hipMemcpy(score, probe_score_.p, (size_t)pairs * pi.V * sizeof(double), hipMemcpyDeviceToHost));
+        if (mag) HIPCHK(hipMemcpy(mag, probe_mag_.p, (size_t)pairs * sizeof(double), hipMemcpyDeviceToHost));
+        if (err) HIPCHK(hipMemcpy(err, probe_err_.p, (size_t)pairs * sizeof(double), hipMemcpyDeviceToHost));
+        if (best_score) HIPCHK(hipMemcpy(best_score, probe_bs_.p, (size_t)pairs * sizeof(double), hipMemcpyDeviceToHost));
+        if (best_v) HIPCHK(hipMemcpy(best_v, probe_bv_.p, (size_t)pairs * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (queue && w[0] > 0) HIPCHK(hipMemcpy(queue, probe_queue_.p, (size_t)w[0] * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (dead) HIPCHK(hipMemcpy(dead, probe_dead_.p, (size_t)pairs, hipMemcpyDeviceToHost));
+        return PBVI_OK;
+    }
+    int debug_score_probe_fetch(int64_t* dims, double* scalars, double* score, double* mag, double* err, int32_t* best_v,
+                                double* best_score, int32_t* queue, uint8_t* dead, int32_t* perm) override {
+        // an fp64 engine: the stage that ran last -- its screen's, or its own (screen off, or the screen overflowed)
+        const bool on_screen = screen_ != nullptr && screen_->probe_seq_ > probe_seq_;
+        const uint64_t seq = on_screen ? screen_->probe_seq_ : probe_seq_;
+        const int64_t Bc = on_screen ? screen_->probe_info_.B : probe_info_.B;
+        if (seq == 0 || (on_screen ? screen_->probe_score_.p : probe_score_.p) == nullptr)
+            FAIL(PBVI_EINVAL, "score probe: nothing captured since the probe was enabled");
+        int rc = on_screen ? screen_->probe_copy_out(dims, scalars, score, mag, err, best_v, best_score, queue, dead)
+                           : probe_copy_out(dims, scalars, score, mag, err, best_v, best_score, queue, dead);
+        if (rc) return rc;
+        if (perm) {                                          // caller's row of engine row i (the order is this engine's)
+            if (Bc != B_) FAIL(PBVI_EINVAL, "score probe: the belief block changed since the capture");
+            if ((rc = host_perm())) return rc;
+            for (int64_t i = 0; i < B_; ++i) perm[i] = sorted_ ? h_perm_[(size_t)i] : (int32_t)i;
+        }
+        return PBVI_OK;
+    }
+
     // resident belief block back to the host (or a device buffer), caller order: [B][S] T
     int beliefs_fetch(void* out) override {
         if (B_ <= 0) FAIL(PBVI_EINVAL, "beliefs_fetch: no belief block resident");
@@ -2181,6 +2311,7 @@ class EngineT : public EngineBase {
         mat_V_ = -1;
         gam_pad_ptr_ = nullptr;
         last_deferred_nothing_ = false;
+        probe_seq_ = 0;                                      // (the capture's buffers were working buffers)
         ++alpha_ver_;
         ++bel_ver_;
         belsp_ver_ = 0;
@@ -3058,6 +3189,7 @@ int EngineT<T>::score_gemm(const T* Y, int64_t rows_y, const uint8_t* nzB, int G
         if ((rc = slabs_.ensure((size_t)split * m_rows * rows_y * sizeof(T)))) return rc;
         slab_bytes_ = (int64_t)split * m_rows * rows_y * (int64_t)sizeof(T);
         f64_pairs_ = 0;
+        f64_split_ = split;
         if (!f64_uses_mfma(m_rows, rows_y)) {
             HIPCHK(launch_gemm_nt_simple<T>(X, S_pad_, Y, S_pad_, slabs_.as<T>(), (int)rows_y, (int)m_rows, (int)rows_y,
                                             S_, stream_));
@@ -3463,6 +3595,7 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
     out->f64_pairs = f64_pairs_;
     HIPCHK(launch_argmax<T>(sv, (int)V_, AO, (int)B_, io.dead, out->tol_rel, 0.0, out->chain, 0, io.best_v, io.best_score,
                             io.err, io.queue, io.qcount, stream_, io.tol_extra, out->split));
+    if (probe_on_ && (rc = probe_capture(sv, io, *out))) return rc;      // tests only (pbvi_debug_score_probe)
     HIPCHK(hipEventRecord(io.ev[3], stream_));
     out->sv = sv;
     return PBVI_OK;
@@ -3574,6 +3707,7 @@ int EngineT<T>::stage_scores_tiled(double gamma, const ScoreIO& io, int want_spl
     out->chunks = (int)n_chunks;
     HIPCHK(launch_argmax<T>(full, (int)V_, AO, (int)B_, io.dead, out->tol_rel, 0.0, out->chain, 0, io.best_v, io.best_score,
                             io.err, io.queue, io.qcount, stream_, io.tol_extra, out->split));
+    if (probe_on_ && (rc = probe_capture(full, io, *out))) return rc;    // tests only (pbvi_debug_score_probe)
     HIPCHK(hipEventRecord(io.ev[3], stream_));
     out->sv = full;
     return PBVI_OK;
@@ -3602,6 +3736,7 @@ int EngineT<T>::ensure_screen() {
         }
         e->formulation_ = formulation_;
         e->fuse_project_ = fuse_project_;
+        e->probe_on_ = probe_on_;
         screen_ = e;
         return PBVI_OK;
     }
@@ -4549,6 +4684,15 @@ int64_t pbvi_debug_slabs(pbvi_engine_t* e, void* out, int64_t cap_bytes) {
 int pbvi_debug_slabs_fill(pbvi_engine_t* e, int byte) {
     NEED(e);
     return e->impl->debug_slabs_fill(byte);
+}
+int pbvi_debug_score_probe(pbvi_engine_t* e, int enable) {
+    NEED(e);
+    return e->impl->debug_score_probe(enable);
+}
+int pbvi_debug_score_probe_fetch(pbvi_engine_t* e, int64_t* dims, double* scalars, double* score, double* mag, double* err,
+                                 int32_t* best_v, double* best_score, int32_t* queue, uint8_t* dead, int32_t* perm) {
+    NEED(e);
+    return e->impl->debug_score_probe_fetch(dims, scalars, score, mag, err, best_v, best_score, queue, dead, perm);
 }
 int pbvi_backup(pbvi_engine_t* e, const void* beliefs, int64_t B, double gamma, int flags, void* out_alpha,
                 int32_t* out_action, int32_t* out_best_alpha, uint8_t* out_keep, pbvi_stats_t* stats) {

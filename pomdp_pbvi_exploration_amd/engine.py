@@ -37,6 +37,7 @@ EXPORTS = [
     'pbvi_set_gamma_tiling', 'pbvi_gamma_tiling_plan', 'pbvi_q_values', 'pbvi_prune_dominated_masked',
     'pbvi_rollout', 'pbvi_infotaxis', 'pbvi_rollout_infotaxis', 'pbvi_debug_split_schedule', 'pbvi_debug_slabs',
     'pbvi_debug_slabs_fill', 'pbvi_env_set_frames', 'pbvi_env_set_table', 'pbvi_env_clear', 'pbvi_rollout_env',
+    'pbvi_debug_score_probe', 'pbvi_debug_score_probe_fetch',
 ]
 
 
@@ -99,6 +100,8 @@ def load_library(path: str = LIB_PATH):
         'pbvi_debug_split_schedule': (C.c_int, [C.c_int]),
         'pbvi_debug_slabs': (C.c_int64, [vp, vp, C.c_int64]),
         'pbvi_debug_slabs_fill': (C.c_int, [vp, C.c_int]),
+        'pbvi_debug_score_probe': (C.c_int, [vp, C.c_int]),
+        'pbvi_debug_score_probe_fetch': (C.c_int, [vp] + [vp] * 10),
         'pbvi_backup_store_unique': (C.c_int64, [vp, i32p, C.c_int64]),
         'pbvi_backup_device_results': (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
         'pbvi_backup': (C.c_int, [vp, vp, C.c_int64, C.c_double, C.c_int, vp, i32p, i32p, u8p, sp]),
@@ -1322,6 +1325,37 @@ class Engine:
     def debug_slabs_fill(self, byte: int) -> None:
         """Tests only: set every byte of the score slab buffer to ``byte`` (``pbvi_debug_slabs_fill``)."""
         self._ck(self._lib.pbvi_debug_slabs_fill(self._h, int(byte)))
+
+    def debug_score_probe(self, enable: bool = True) -> None:
+        """Tests only: while enabled, the scoring stage of every backup keeps a copy of what its argmax read and wrote,
+        taken before the refinement (``pbvi_debug_score_probe``; off by default)."""
+        self._ck(self._lib.pbvi_debug_score_probe(self._h, int(bool(enable))))
+
+    def debug_score_probe_fetch(self) -> dict:
+        """Tests only: the last capture of the score probe (``pbvi_debug_score_probe_fetch``), beliefs in ENGINE order
+        (``perm[b]`` = caller's row of engine row ``b``), groups ``g = a * O + o``:
+        ``score [B,G,V]``, ``mag / E / best_v / best_score / dead [B,G]``, ``queue [qcount]`` (entries ``b * G + g`` in
+        the argmax's slot order), ``qcount``, the scalars ``split``, ``chain_steps`` (-1: none), ``tol_rel`` (< 0: derived
+        on the device from ``chain_steps``), ``tol_extra`` and the route taken: ``push`` (belief-side formulation),
+        ``f64_pairs`` (tile pairs of the fp64 MFMA GEMM, 0 = plain kernel or fp32 scoring), ``f64_split`` (its K parts)
+        and ``chunks`` (Gamma chunks; 0 on the belief side)."""
+        dims = np.zeros(8, dtype=np.int64)
+        self._ck(self._lib.pbvi_debug_score_probe_fetch(self._h, _ptr(dims), *([None] * 9)))
+        B, G, V, qc = (int(x) for x in dims[:4])
+        scal = np.zeros(4, dtype=np.float64)
+        out = {'score': np.empty((B, G, V), np.float64), 'mag': np.empty((B, G), np.float64),
+               'E': np.empty((B, G), np.float64), 'best_v': np.empty((B, G), np.int32),
+               'best_score': np.empty((B, G), np.float64), 'queue': np.empty(max(qc, 1), np.int32),
+               'dead': np.empty((B, G), np.uint8), 'perm': np.empty(B, np.int32)}
+        self._ck(self._lib.pbvi_debug_score_probe_fetch(
+            self._h, _ptr(dims), _ptr(scal), _ptr(out['score']), _ptr(out['mag']), _ptr(out['E']), _ptr(out['best_v']),
+            _ptr(out['best_score']), _ptr(out['queue']), _ptr(out['dead']), _ptr(out['perm'])))
+        if int(dims[3]) != qc:
+            raise RuntimeError('score probe: the capture changed between the two fetches')
+        out['queue'] = out['queue'][:qc]
+        out.update(qcount=qc, split=int(scal[0]), chain_steps=int(scal[1]), tol_rel=float(scal[2]), tol_extra=float(scal[3]),
+                   push=int(dims[4]), f64_pairs=int(dims[5]), f64_split=int(dims[6]), chunks=int(dims[7]))
+        return out
 
     def set_gamma_tiling(self, mode: str = 'off', chunk_rows: int = 0) -> None:
         """Alpha-side backups whose Gamma is projected into HBM (R > 1, fp64 scoring, unfused R = 1): walk the alpha set in
