@@ -54,6 +54,14 @@ struct SlabView {
     int push_B = 0, push_A = 1, push_O = 1;
     const double* aux_mag = nullptr;   // [B][G]  sum_s' |bp[g,b,s']| * max_v|alpha[v,s']|
     const double* aux_rd = nullptr;    // [B][A]  b . ER[:,a], accumulated in f64
+    // one plain row-major matrix: a single slab, nothing left to add to it
+    static SlabView single(const T* p, int ldc) {
+        SlabView v{};                 // no slab stride, no chunk counts
+        v.slabs = p;
+        v.ldc = ldc;
+        v.fixed = 1;
+        return v;
+    }
     __device__ __forceinline__ T at(int64_t row, int64_t col) const {
         const T* p = slabs + row * ldc + col;
         const int64_t pair = nchunks ? (col >> 8) * tiles_m + (row >> 8) : 0;

@@ -838,6 +838,30 @@ struct ScoreStage {
     int chunks;                       // alpha side: chunks Gamma was tiled into (1 = held whole or compact); 0 = belief side
 };
 
+// The buffers of one decision: per-belief actions and (a*, v*) keys -> caller order -> distinct keys -> their alpha' rows
+// (EngineT::decision_tail).  An engine holds two: the backup's result, and run_fetch's provisional decision.
+struct Decision {
+    DevBuf act;                       // [B] action per belief, engine order
+    DevBuf act_res, best_res;         // [B] actions / [B][A][O] best_v in caller order (a sorted block, or a snapshot)
+    DevBuf rep, uniq, inv, slot;      // [B] key dedup: representative, distinct keys' beliefs, belief -> distinct key, hash slots
+    DevBuf rows;                      // [distinct][S] the distinct keys' rows
+    DevBuf& counts;                   // the count of distinct keys is word `word` of this buffer
+    const int word;
+    // actions / keys in caller order, where the tail left them (valid while the buffers are: nothing grows them inside a call)
+    const int32_t *res_act = nullptr, *res_best = nullptr;
+    Decision(DevMem& m, DevBuf& c, int w) : act(m), act_res(m), best_res(m), rep(m), uniq(m), inv(m), slot(m), rows(m), counts(c), word(w) {}
+    int* count() const { return counts.as<int>() + word; }
+    // for B beliefs with `pairs` keys and rows of row_bytes; caller_order: act_res / best_res will be written
+    int ensure(int64_t B, int64_t pairs, size_t row_bytes, bool caller_order) {
+        int rc;
+        for (DevBuf* b : {&act, &rep, &uniq, &inv, &slot})
+            if ((rc = b->ensure((size_t)B * sizeof(int32_t)))) return rc;
+        if (caller_order && (rc = act_res.ensure((size_t)B * sizeof(int32_t)))) return rc;
+        if (caller_order && (rc = best_res.ensure((size_t)pairs * sizeof(int32_t)))) return rc;
+        return rows.ensure((size_t)B * row_bytes);
+    }
+};
+
 // Where the step loop of the device-resident rollouts takes its action from (EngineT::rollout)
 enum RolloutSource {
     ROLLOUT_VALUE_MAX = 0,            // alpha_actions[first argmax_v b.alpha_v]       (pbvi_rollout, lookahead 0)
@@ -972,7 +996,9 @@ class EngineT : public EngineBase {
     int64_t B_ = 0, B_pad_ = 0;
     DevBuf belsp_{mem_};   // fp32: bel_'s split plane for the split score GEMM (split_bf16.h)
     uint64_t belsp_ver_ = 0;                                 // the bel_ version belsp_ holds (0: none)
-    DevBuf gam_{mem_}, slabs_{mem_}, best_v_{mem_}, best_score_{mem_}, err_{mem_}, dead_{mem_}, queue_{mem_}, counters_{mem_, DevBuf::MODEL}, rdot_{mem_}, action_{mem_}, aqueue_{mem_}, out_{mem_}, keep_{mem_};
+    DevBuf gam_{mem_}, slabs_{mem_}, best_v_{mem_}, best_score_{mem_}, err_{mem_}, dead_{mem_}, queue_{mem_}, counters_{mem_, DevBuf::MODEL}, rdot_{mem_}, aqueue_{mem_}, keep_{mem_};
+    // the backup's decision: actions, the belief reordering undone (f32, B > 256), K6 key dedup; fin_.rows holds the unique rows
+    Decision fin_{mem_, counters_, CNT_UNIQUE};
     DevBuf bv2_{mem_}, bs2_{mem_}, err2_{mem_}, queue2_{mem_}, prune_cnt_{mem_};
     // Gamma tiled over the alpha set (pbvi_set_gamma_tiling): 0 never, 1 when Gamma does not fit, 2 always; rows per chunk
     // (0 = planned); the full-width score matrix the chunks are folded into; the widest stream-K share size of the chunks'
@@ -982,8 +1008,8 @@ class EngineT : public EngineBase {
     DevBuf scores_{mem_}, chain_max_{mem_, DevBuf::MODEL};
     std::vector<hipEvent_t> tile_ev_;
     int tile_ev_chunks_ = 0;
-    DevBuf stage_{mem_}, keys_{mem_}, perm_{mem_}, action_res_{mem_}, best_res_{mem_};   // belief reordering (f32, B > 256)
-    DevBuf rep_{mem_}, uniq_{mem_}, inv_{mem_}, slot_{mem_}, out_full_{mem_};   // K6 key dedup: out_ holds the unique rows
+    DevBuf stage_{mem_}, keys_{mem_}, perm_{mem_};   // belief reordering (f32, B > 256)
+    DevBuf out_full_{mem_};   // the per-belief alpha' matrix expanded from fin_.rows (ensure_full)
     DevBuf store_[2]{{mem_}, {mem_}}, ids_{mem_};   // device row stores: [0] alpha-vectors, [1] beliefs
     int64_t store_rows_[2] = {0, 0};
     DevBuf in_ptr_{mem_, DevBuf::MODEL}, in_src_{mem_, DevBuf::MODEL}, bu_act_{mem_}, bu_obs_{mem_}, bu_row_{mem_}, bu_unnorm_{mem_}, bu_mass_{mem_}, bu_out_{mem_}, walk64_{mem_}, rto64_{mem_, DevBuf::MODEL};   // batched belief update
@@ -1053,17 +1079,25 @@ class EngineT : public EngineBase {
     uint64_t nzA_ver_ = 0;                                   // belief-block version ev_nzA_ was recorded for
     PinnedBuf ids_pin_{pinned_, "hipHostFree(ids)"};         // staging of the ids of a store selection
     PinnedBuf words_{pinned_, "hipHostFree(flag)"};          // one PinnedWords, allocated by init(): see words()
-    // early rows (run_fetch): destination of the current call, buffers of the provisional decision pipeline
-    void* early_rows_ = nullptr;
-    int64_t early_cap_ = 0;
-    bool early_used_ = false, early_dma_pending_ = false;
     struct RunFetchDst {                                     // run_fetch: the small per-belief results travel with the pipeline's
         int32_t *slot = nullptr, *index = nullptr, *action = nullptr, *best = nullptr;   // last read-back, not behind a second
         uint8_t* keep = nullptr;                                                         // synchronisation
         bool queued = false;
-    } rf_dst_;
-    DevBuf e_bv_{mem_}, e_bs_{mem_}, e_err_{mem_}, e_rdot_{mem_}, e_act_{mem_}, e_ares_{mem_}, e_bres_{mem_}, e_rep_{mem_}, e_uniq_{mem_}, e_inv_{mem_}, e_slotd_{mem_}, e_cnt_{mem_, DevBuf::MODEL}, e_out_{mem_}, e_slot_{mem_};
-    hipEvent_t ev_early_[2] = {nullptr, nullptr};
+    };
+    // early rows: what run_fetch hands to the pipeline (set before backup_run, taken back after it) and what the pipeline
+    // tells run_fetch in return
+    struct EarlyRows {
+        void* rows = nullptr;                                // page-locked destination of the distinct rows (nullptr: no run_fetch)
+        int64_t cap = 0;                                     // rows it has room for
+        RunFetchDst dst;
+        bool used = false;                                   // this call's provisional rows went (or are going) to `rows`
+        bool dma_pending = false;                            // their copy waits for the provisional count
+        hipEvent_t ev[2] = {nullptr, nullptr};               // the provisional decision / its rows' copy are complete
+    } early_;
+    // the provisional decision's buffers (fin_ is the final one's): action values, the slots k_match_rows gives the final
+    // keys, the counts {provisional keys, rows appended behind them, 1 = the slots overflowed} (PinnedWords::early)
+    DevBuf e_rdot_{mem_}, e_slot_{mem_}, e_cnt_{mem_, DevBuf::MODEL};
+    Decision prov_{mem_, e_cnt_, 0};
     hipEvent_t ev_ids_ = nullptr;
     hipEvent_t ev_nzA_ = nullptr;                            // the resident block's zero map (nzA_) is complete
     DevBuf nzBw_{mem_, DevBuf::MODEL};   // [A*O][ceil(k_tiles/64)] support tiles of RTO as bit words
@@ -2120,7 +2154,7 @@ class EngineT : public EngineBase {
         if ((rc = ids_.ensure((size_t)n * sizeof(int32_t)))) return rc;
         HIPCHK(hipMemcpyAsync(ids_.p, unique_idx, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
         if (S_pad_ > S_) HIPCHK(hipMemsetAsync(dst, 0, (size_t)n * S_pad_ * sizeof(T), stream_));   // pad columns stay zero
-        hipLaunchKernelGGL(k_gather_rows_ld<T>, dim3((S_ + 255) / 256, (unsigned)n), dim3(256), 0, stream_, out_.as<T>(), S_,
+        hipLaunchKernelGGL(k_gather_rows_ld<T>, dim3((S_ + 255) / 256, (unsigned)n), dim3(256), 0, stream_, fin_.rows.as<T>(), S_,
                            dst, S_pad_, S_, ids_.as<int32_t>());
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(stream_));            // unique_idx is the caller's host memory
@@ -2457,8 +2491,530 @@ class EngineT : public EngineBase {
     int stage_scores(double gamma, bool use_push, const ScoreIO& io, ScoreStage<T>* out);
     int stage_scores_tiled(double gamma, const ScoreIO& io, int want_split, int64_t Vc, int64_t n_chunks, ScoreStage<T>* out);
     int ensure_exact(DevBuf& b, size_t bytes);
+
+    // ---- one backup, stage by stage; TS is the scorer's precision ---- //
+    // What the stages share: each field is set by the stage named and read by the later ones.
     template <typename TS>
-    int run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_stats_t* st);
+    struct Call {
+        static constexpr bool windows = sizeof(TS) == 4;              // fp32 scores: tie windows + fp64 re-decision
+        static constexpr bool screened = sizeof(TS) != sizeof(T);
+        EngineT<TS>& scorer;              // this engine, or its fp32 screen
+        double gamma;
+        int flags;
+        int64_t pairs;                    // B * A * O
+        bool use_push, stats;             // belief-side formulation; the caller wants pbvi_stats_t
+        bool no_side = false;             // side_stream_work: PBVI_NO_SIDE_STREAM
+        hipStream_t lists = nullptr;      // side_stream_work: where the GEMM's tile lists may be built, or nullptr
+        bool early_wanted = false;        // side_stream_work: run_fetch's provisional decision applies to this call
+        ScoreIO io;                       // score
+        ScoreStage<TS> sc;
+        const int* h_kcount = nullptr;    // score: the page-locked landing area of the GEMM's list lengths, and how many
+        size_t n_kcount = 0;
+        bool xr_pending = false;          // extra_row_maxima: ev_xr_[1] is still to be waited for
+        RefineWork work;                  // refine
+        bool speculate = false;           // refine: the deferred counts are read at the end of the call
+        int h_cnt[CNT_SLOTS] = {0, 0, 0, 0, 0, 0, 0, 0};      // all counters in the one read-back that precedes the final sync
+    };
+
+    // One backup: `scorer` (this engine, or its fp32 screen) produces scores and first maxima; this engine, which owns
+    // the operands in their original precision, decides near-ties, actions and assembles the rows.  The stages follow in the
+    // order in which run_pipeline calls them.
+    template <typename TS>
+    int run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_stats_t* st) {
+        int rc;
+        const int64_t N = (int64_t)A_ * O_ * (V_ + 1) + 2 * A_;   // per (a, o): alpha rows + magnitude row
+        const int64_t pairs = B_ * A_ * O_;
+        if (N > 0x7fffffff || pairs > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "backup_run: A*O*(V+1) or B*A*O exceeds int32");
+        Call<TS> c{scorer, gamma, flags, pairs, scorer.choose_push(N), st != nullptr};
+        last_formulation_ = c.use_push ? 2 : 1;
+        if ((rc = prepare_backup(c))) return rc;
+        if ((rc = side_stream_work(c))) return rc;
+        if ((rc = score(c))) return rc;
+        if ((rc = extra_row_maxima(c))) return rc;
+        if ((rc = provisional_decision(c))) return rc;
+        if ((rc = refine(c))) return rc;
+        if ((rc = hand_over_early_rows(c))) return rc;
+        if (q_only_) return finish_q_values(c);
+        if ((rc = decide(c))) return rc;
+        if ((rc = speculative_repeat(c))) return rc;
+        // 11. what the fetches and the next call need to know about this result
+        if (c.windows && dead_count_ < 0) dead_count_ = c.h_cnt[CNT_DEAD];
+        full_valid_ = false;
+        res_sorted_ = sorted_;
+        have_result_ = true;
+        have_bk_vmax_ = c.use_push && !c.screened;
+        res_B_ = B_;
+        res_unique_ = c.h_cnt[CNT_UNIQUE];
+        if (st) fill_stats(c, st);
+        return PBVI_OK;
+    }
+
+    // 1. The buffers of the stages up to the refinement; counters cleared.
+    template <typename TS>
+    int prepare_backup(Call<TS>& c) {
+        int rc;
+        if ((rc = best_v_.ensure((size_t)c.pairs * sizeof(int32_t)))) return rc;
+        if ((rc = best_score_.ensure((size_t)c.pairs * sizeof(double)))) return rc;
+        if ((rc = err_.ensure((size_t)c.pairs * sizeof(double)))) return rc;
+        if ((rc = queue_.ensure((size_t)c.pairs * sizeof(int32_t)))) return rc;
+        if ((rc = dead_.ensure((size_t)c.pairs))) return rc;
+        if ((rc = rdot_.ensure((size_t)B_ * A_ * 2 * sizeof(double)))) return rc;
+        if ((rc = aqueue_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+        if ((rc = acand_.ensure((size_t)B_ * A_))) return rc;
+        // (the decision's buffers too in front of the scoring stage, which plans Gamma tiling with what is free)
+        if (!q_only_ && (rc = fin_.ensure(B_, c.pairs, (size_t)S_ * sizeof(T), sorted_))) return rc;
+        if ((rc = keep_.ensure((size_t)B_))) return rc;
+        if (c.windows && (rc = stage_reserve(256))) return rc;      // the pinned bounce buffer of the fetches that follow, allocated while the stream is idle
+        HIPCHK(hipMemsetAsync(counters_.p, 0, CNT_SLOTS * sizeof(int), stream_));
+        HIPCHK(hipEventRecord(ev_[0], stream_));
+        return PBVI_OK;
+    }
+
+    // 2. Belief-only work (dead triples, b.ER: ~0.1 ms each) on the side stream, beside the projection.
+    // (Beside the persistent stream-K GEMM they starve: k_rdot took 3.1 ms there instead of 0.1.)
+    template <typename TS>
+    int side_stream_work(Call<TS>& c) {
+        int rc;
+        static const bool no_side = getenv("PBVI_NO_SIDE_STREAM") != nullptr;      // debug / A-B only
+        c.no_side = no_side;
+        hipStream_t side = no_side ? stream_ : stream2_;
+        const int k_tiles = S_pad_ / GEMM_BK;
+        HIPCHK(hipEventRecord(ev_fork_, stream_));
+        HIPCHK(hipStreamWaitEvent(side, ev_fork_, 0));
+        static const bool lists_on_side = getenv("PBVI_LISTS_ON_SIDE") != nullptr;      // debug / A-B only: lists behind k_dead
+        c.lists = no_side ? nullptr : (lists_on_side ? side : stream3_);
+        // (the tile lists need the block's zero map only: where the block was indexed just now they do not wait for its gather)
+        if (c.lists != nullptr && c.lists != side)
+            HIPCHK(hipStreamWaitEvent(c.lists, (!c.screened && ev_nzA_ != nullptr && nzA_ver_ == bel_ver_) ? ev_nzA_ : ev_fork_, 0));
+        if (c.windows) {   // exact, from the supports of the ORIGINAL operands (an fp32 copy may have flushed tiny values to zero)
+            if ((rc = btl_.ensure((size_t)B_ * k_tiles * sizeof(int32_t)))) return rc;
+            if ((rc = btc_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+            if ((rc = val_exact_.ensure((size_t)B_ * A_ * (1 + O_) * ACTION_SPLIT * sizeof(double)))) return rc;
+            // Dead triples and the per-belief tile lists are a function of the belief block and the model alone: computed on
+            // the first backup of a block, kept for the following ones (a solve backs a block up once; update_passes > 1,
+            // the belief-dominance loops of the notebooks and the benchmark back the same block up again and again).  Like
+            // the block's sort order and zero-tile map they index the INPUT; nothing of a backup's result is kept.
+            static const bool no_cache = getenv("PBVI_NO_DEAD_CACHE") != nullptr;       // debug / A-B only
+            if (dead_ver_ != bel_ver_ || !btl_valid_ || dead_pairs_ != c.pairs || no_cache) {
+                const bool have_flags = rowflags_ver_ == bel_ver_ && rowflags_.p != nullptr;   // left by the block's indexing pass
+                HIPCHK(launch_dead<T>(bel_.as<T>(), S_pad_, (int)B_, view(), nzBw_.as<unsigned long long>(), k_tiles, dead_.as<uint8_t>(),
+                                      btl_.as<int32_t>(), btc_.as<int32_t>(), counters_.as<int>() + CNT_DEAD, side,
+                                      have_flags ? rowflags_.as<uint8_t>() : nullptr,
+                                      have_flags && sorted_ ? perm_.as<int32_t>() : nullptr));
+                btl_valid_ = true;
+                dead_ver_ = bel_ver_;
+                dead_pairs_ = c.pairs;
+                dead_count_ = -1;                                // read back with this call's counters
+            }
+        }
+        if (c.use_push) {   // b . ER[:,a] in f64 (the alpha-side gets it from Gamma's reward rows)
+            if ((rc = prd_.ensure((size_t)B_ * A_ * sizeof(double)))) return rc;
+            HIPCHK(launch_rdot<T>(bel_.as<T>(), S_pad_, (int)B_, view(), c.windows ? btl_.as<int32_t>() : nullptr,
+                                  c.windows ? btc_.as<int32_t>() : nullptr, prd_.as<double>(), side));
+        }
+        // (run_fetch's provisional pipeline: its counters are cleared here, beside the projection, not in front of its kernels)
+        c.early_wanted = c.windows && !q_only_ && early_.rows != nullptr && !(c.flags & PBVI_BELIEF_DOMINANCE) && early_.cap >= B_ && !no_side;
+        if (c.early_wanted) {
+            if ((rc = e_cnt_.ensure(4 * sizeof(int)))) return rc;
+            HIPCHK(hipMemsetAsync(e_cnt_.p, 0, 4 * sizeof(int), side));
+        }
+        HIPCHK(hipEventRecord(ev_join_, side));
+        return PBVI_OK;
+    }
+
+    // 3. K1, K2 and the first maxima, on the scorer (stage_scores).
+    template <typename TS>
+    int score(Call<TS>& c) {
+        int rc;
+        ScoreIO& io = c.io;
+        io.best_v = best_v_.as<int32_t>();
+        io.best_score = best_score_.as<double>();
+        io.err = err_.as<double>();
+        io.queue = c.windows ? queue_.as<int32_t>() : nullptr;
+        io.qcount = counters_.as<int>() + CNT_QUEUE;
+        io.dead = c.windows ? dead_.as<uint8_t>() : nullptr;
+        io.prd = c.use_push ? prd_.as<double>() : nullptr;
+        io.join = ev_join_;
+        io.side = c.lists;
+        io.ev = ev_;
+        io.stats = c.stats;
+        // a screen multiplies operands rounded to fp32 (alpha, belief, RTO: 2^-24 relative each) and gamma in fp32
+        io.tol_extra = c.screened ? 4.0 * 5.9604644775390625e-08 : 0.0;
+        io.allow_split = !c.screened;
+        if (c.windows && !c.use_push && c.scorer.tiling_mode_ != 0) {   // Gamma tiling plans with what is free: the refinement's work
+            RefineWork reserve;                                       // lists (the largest buffers of the later stages) come first
+            if ((rc = refine_work(c.pairs, V_, &reserve))) return rc;
+        }
+        if ((rc = c.scorer.stage_scores(c.gamma, c.use_push, io, &c.sc))) return rc;
+        // List lengths of this GEMM, for the statistics (K5 rebuilds the lists for its own GEMM later): into PAGE-LOCKED memory.
+        // (The copy used to land in a std::vector: a device-to-pageable copy is staged by the runtime and holds the host until
+        // the GEMM and the argmax in front of it have finished, so nothing behind the argmax was enqueued before then.)
+        if (c.stats && (c.windows || c.sc.f64_pairs > 0)) {
+            c.n_kcount = c.windows ? (size_t)c.sc.plan.tiles_m * c.sc.plan.tiles_n : (size_t)c.sc.f64_pairs;
+            // (no copy into it is pending: every call ends synchronised)
+            if (!kc_pin_.ensure(c.n_kcount * sizeof(int), std::max<size_t>(c.n_kcount * 2, 4096) * sizeof(int)))
+                FAIL(PBVI_ENOMEM, "pinned buffer for the list lengths");
+            c.h_kcount = kc_pin_.as<int>();                                 // (the copy itself is enqueued behind the refinement: hand_over_early_rows)
+        }
+        return PBVI_OK;
+    }
+
+    // 4. Belief side: max_v b.alpha_v of these beliefs from the GEMM's extra rows (exact engines only).
+    template <typename TS>
+    int extra_row_maxima(Call<TS>& c) {
+        if (!c.use_push || c.screened) return PBVI_OK;
+        // beside the refinement, on the side stream: a wave per belief row over V scores is 0.1 ms that nothing in this
+        // call waits for (the slabs stay as they are until the next GEMM; K5 is not run with this formulation's extras
+        // pending -- it joins first, below)
+        int rc;
+        if ((rc = vmax_bk_.ensure((size_t)B_ * sizeof(double)))) return rc;
+        hipStream_t xs = c.no_side ? stream_ : stream2_;
+        if (xs != stream_) {
+            HIPCHK(hipEventRecord(ev_xr_[0], stream_));
+            HIPCHK(hipStreamWaitEvent(xs, ev_xr_[0], 0));
+        }
+        hipLaunchKernelGGL(k_extra_rowmax<TS>, dim3((unsigned)((B_ + 3) / 4)), dim3(256), 0, xs, c.sc.sv, c.sc.extra_row0, (int)B_,
+                           (int)V_, sorted_ ? perm_.as<int32_t>() : nullptr, vmax_bk_.as<double>());
+        HIPCHK(hipGetLastError());
+        if (xs != stream_) {
+            HIPCHK(hipEventRecord(ev_xr_[1], xs));
+            c.xr_pending = true;
+        }
+        return PBVI_OK;
+    }
+
+    // caller order -> key dedup -> the distinct keys' rows, for the actions in d.act and the keys in best_v_ as they are now.
+    // snapshot: best_v_ of an unsorted block is copied, not aliased (the provisional decision: the refinement rewrites it in
+    // place).  d.res_act / d.res_best are the actions and keys in caller order.
+    int decision_tail(Decision& d, double gamma, bool snapshot) {
+        const int AO = A_ * O_;
+        d.res_act = d.act.as<int32_t>();
+        d.res_best = best_v_.as<int32_t>();
+        // results to the caller's belief order, then K6: dedup by (a*, v*) key
+        if (sorted_) {
+            hipLaunchKernelGGL(k_unpermute, dim3((unsigned)B_), dim3(64), 0, stream_, (int)B_, AO, perm_.as<int32_t>(), d.act.as<int32_t>(),
+                               best_v_.as<int32_t>(), d.act_res.as<int32_t>(), d.best_res.as<int32_t>());
+            HIPCHK(hipGetLastError());
+            d.res_act = d.act_res.as<int32_t>();
+            d.res_best = d.best_res.as<int32_t>();
+        } else if (snapshot) {                                   // (one row block: the keys as they are now)
+            HIPCHK(hipMemcpyAsync(d.best_res.p, best_v_.p, (size_t)B_ * AO * sizeof(int32_t), hipMemcpyDeviceToDevice, stream_));
+            d.res_best = d.best_res.as<int32_t>();
+        }
+        HIPCHK(launch_dedup((int)B_, A_, O_, d.res_act, d.res_best, d.rep.as<int32_t>(), d.uniq.as<int32_t>(), d.inv.as<int32_t>(),
+                            d.slot.as<int32_t>(), d.count(), stream_));
+        // K3: alpha' rows of the unique keys only
+        HIPCHK(launch_assemble<T>(alpha_.as<T>(), S_pad_, view(), gamma, d.res_act, d.res_best, d.uniq.as<int32_t>(), d.count(), (int)B_,
+                                  d.rows.as<T>(), S_, stream_));
+        return PBVI_OK;
+    }
+
+    // 5. Early rows (pbvi_backup_run_fetch): the first maxima and the action values they give decide MOST beliefs' keys for
+    // good -- the refinement re-decides near-ties only -- so the distinct rows of that provisional decision are assembled
+    // and written to the caller's page-locked buffer on the side stream NOW, under the refinement, the action stage and
+    // the dedup (the 8 MB of rows used to cross PCIe after all of them: 0.17 ms of a 3 ms backup).  Afterwards the final
+    // keys are matched against the provisional ones (k_match_rows): rows already on the host keep their slot, the few
+    // that the refinement changed are appended.  Snapshots, because the refinement rewrites best_v / best_score in place.
+    template <typename TS>
+    int provisional_decision(Call<TS>& c) {
+        early_.used = false;
+        if (!c.early_wanted) return PBVI_OK;
+        int rc;
+        if ((rc = prov_.ensure(B_, c.pairs, (size_t)S_ * sizeof(T), true))) return rc;
+        if ((rc = e_rdot_.ensure((size_t)B_ * A_ * 2 * sizeof(double)))) return rc;
+        if ((rc = e_slot_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+        for (hipEvent_t& ev : early_.ev) HIPCHK(new_event(&ev, hipEventDisableTiming, "hipEventDestroy(early)"));
+        // The provisional decision itself is 40 us of small kernels: they run HERE, on the main stream in front of the
+        // refinement (which rewrites best_v / best_score in place), and only the copy -- 8 MB over PCIe, ~150 us, few blocks
+        // -- goes to the side stream.  (Snapshots of the three arrays + the whole provisional pipeline beside the
+        // refinement cost it 0.13 ms: a net loss.)
+        HIPCHK(launch_action<TS>((int)B_, c.scorer.view(), c.sc.sv, c.sc.rd_col0, c.sc.tol_rel, c.sc.chain, best_score_.as<double>(), err_.as<double>(),
+                                 e_rdot_.as<double>(), e_rdot_.as<double>() + (size_t)B_ * A_, prov_.act.as<int32_t>(), nullptr, nullptr, stream_,
+                                 c.io.tol_extra, nullptr, c.sc.split));
+        if ((rc = decision_tail(prov_, c.gamma, true))) return rc;
+        HIPCHK(hipEventRecord(early_.ev[0], stream_));
+        hipStream_t es = stream2_;
+        HIPCHK(hipStreamWaitEvent(es, early_.ev[0], 0));
+        // The copy is a plain hipMemcpyAsync on the side stream, sized by the host: it waits (hand_over_early_rows, once the
+        // refinement is enqueued) for this 4-byte count.  A copy KERNEL storing to the page-locked buffer needs no host and reaches the
+        // link's rate (54.7 GB/s, profiles/microbench/pcie_store.hip) -- but beside it k_refine took 0.24 ms instead of 0.14
+        // whatever its grid (8 .. 1024 blocks): the runtime's copy disturbs the refinement far less (0.15 ms).
+        early_.dma_pending = true;
+        HIPCHK(hipMemcpyAsync(&words().provisional, e_cnt_.p, sizeof(int), hipMemcpyDeviceToHost, es));
+        HIPCHK(hipEventRecord(early_.ev[0], es));
+        early_.used = true;
+        return PBVI_OK;
+    }
+
+    // the grid-wide passes over what the per-entry pass deferred (rf_counts_, read by the host)
+    int refine_deferred(double gamma, const RefineWork& work) {
+        HIPCHK(launch_refine_deferred<T>(true, (int)V_, A_ * O_, bel_.as<T>(), S_pad_, alpha_.as<T>(), S_pad_, view(), gamma,
+                                         best_v_.as<int32_t>(), best_score_.as<double>(), err_.as<double>(), work,
+                                         rf_counts_[0], rf_counts_[1], stream_));
+        return PBVI_OK;
+    }
+
+    // 6. fp64 re-decision of near-ties.  The per-entry pass hands entries with many tied candidates on to grid-wide
+    // passes whose launch needs the host to know how many there are -- a read-back in the middle of the pipeline
+    // (~30 us of idle device).  A value function either has such ties (absorbing goals, unexplored regions: every backup
+    // of a solve loop) or it has not (the synthetic sets): after a backup that deferred nothing the next one SPECULATES
+    // that it will not either -- the later stages are enqueued at once, the counts are read at the end, and if there was
+    // deferred work after all it runs then and the later stages are repeated (speculative_repeat).
+    template <typename TS>
+    int refine(Call<TS>& c) {
+        if (!c.windows) return PBVI_OK;
+        int rc;
+        RefineWork& work = c.work;
+        if ((rc = refine_work(c.pairs, V_, &work))) return rc;   // (reserved by `score` already in a tiled call)
+        if constexpr (kF32 && !Call<TS>::screened) {
+            // Gamma is in HBM as the GEMM read it (projection kernel, not the fused GEMM): the per-entry pass first
+            // separates candidates by fp64 sums over those fp32 rows (backup_kernels.h, RefineWork::gam)
+            static const bool no_l1 = getenv("PBVI_NO_L1_SCREEN") != nullptr;      // debug / A-B only
+            // (not in a tiled call: a chunk's rows are gone by now)
+            if (!no_l1 && !c.use_push && !c.sc.fused && c.sc.chunks <= 1 && mode_ == PBVI_SPARSE) {
+                work.gam = (const float*)gam_.p;
+                work.ldg = S_pad_;
+                work.l1_rel = (double)(R_ + 4) * 5.9604644775390625e-08;
+            }
+        }
+        // the counts land in two of the engine's pinned flag words -- not in the staging buffer: run_fetch stages results
+        // through that one before the counts are read, and out_add may reset or reallocate it
+        rf_counts_ = words().deferred;
+        rf_counts_[0] = rf_counts_[1] = 0;
+        static const bool no_spec = getenv("PBVI_NO_SPECULATION") != nullptr;      // debug / A-B only
+        // (not with the belief-dominance test: its own value-max refinement re-uses the work-list buffers, so the
+        // deferred entries of this one have to be finished first)
+        // (nor for pbvi_q_values, whose one stage behind the refinement needs the final best_v)
+        c.speculate = !no_spec && !q_only_ && last_deferred_nothing_ && work.items_v != nullptr && !(c.flags & PBVI_BELIEF_DOMINANCE);
+        HIPCHK((launch_refine_scan<T, TS>(true, c.sc.sv, (int)V_, A_ * O_, (int)c.pairs, queue_.as<int32_t>(), c.io.qcount, bel_.as<T>(), S_pad_,
+                                          alpha_.as<T>(), S_pad_, view(), c.gamma, btl_.as<int32_t>(), btc_.as<int32_t>(),
+                                          nzB_.as<uint8_t>(), best_v_.as<int32_t>(), best_score_.as<double>(), err_.as<double>(),
+                                          counters_.as<int>() + CNT_REFINE_CAND, work, rf_counts_, stream_)));
+        if (!c.speculate && work.items_v != nullptr) {
+            HIPCHK(hipStreamSynchronize(stream_));
+            last_deferred_nothing_ = rf_counts_[0] == 0 && rf_counts_[1] == 0;
+            if ((rc = refine_deferred(c.gamma, work))) return rc;
+        }
+        return PBVI_OK;
+    }
+
+    // 7. The refinement is enqueued: now the host can wait for the provisional count and send the early rows on their way.
+    // Then the list lengths' copy, and the end of the refinement's time.
+    template <typename TS>
+    int hand_over_early_rows(Call<TS>& c) {
+        if (early_.used && early_.dma_pending) {
+            HIPCHK(hipEventSynchronize(early_.ev[0]));
+            const int np = words().provisional;
+            if (np > 0)
+                HIPCHK(hipMemcpyAsync(early_.rows, prov_.rows.p, (size_t)np * S_ * sizeof(T), hipMemcpyDeviceToHost, stream2_));
+            HIPCHK(hipEventRecord(early_.ev[1], stream2_));
+            early_.dma_pending = false;
+        }
+        if (c.h_kcount != nullptr)   // statistics: not in front of the provisional decision and the refinement (K5 re-uses kcount_ later)
+            HIPCHK(hipMemcpyAsync(kc_pin_.p, c.scorer.kcount_.p, c.n_kcount * sizeof(int), hipMemcpyDeviceToHost, stream_));
+        HIPCHK(hipEventRecord(ev_[4], stream_));
+        return PBVI_OK;
+    }
+
+    // the tile lists of the resident block (btl_ / btc_) exist: from the beliefs alone, where k_dead did not leave them
+    int ensure_belief_tiles() {
+        if (btl_valid_) return PBVI_OK;
+        int rc;
+        const int k_tiles = S_pad_ / GEMM_BK;
+        if ((rc = btl_.ensure((size_t)B_ * k_tiles * sizeof(int32_t)))) return rc;
+        if ((rc = btc_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+        HIPCHK(launch_belief_tiles<T>(bel_.as<T>(), S_pad_, (int)B_, S_, k_tiles, btl_.as<int32_t>(), btc_.as<int32_t>(), stream_));
+        btl_valid_ = true;
+        return PBVI_OK;
+    }
+
+    // The end of every call: the counters (and the overflow flag of a screen) into the page-locked words, one
+    // synchronisation, the counters into the call's array.  published: k_publish has stored the words itself, no copy;
+    // timed: ev_[7] ends the stage times (pbvi_q_values keeps none).
+    int end_call(bool screened, bool published, bool timed, int* h_cnt) {
+        PinnedWords* w = &words();
+        if (!published) {
+            // (into the page-locked words: a copy into the stack array is staged by the runtime)
+            HIPCHK(hipMemcpyAsync(w->counters, counters_.p, sizeof(w->counters), hipMemcpyDeviceToHost, stream_));
+            // did an alpha value leave the fp32 range when the screen's copy was made?
+            if (screened && scr_flag_.p) HIPCHK(hipMemcpyAsync(&w->screen_overflow, scr_flag_.p, sizeof(int), hipMemcpyDeviceToHost, stream_));
+        }
+        if (timed) HIPCHK(hipEventRecord(ev_[7], stream_));
+        HIPCHK(hipStreamSynchronize(stream_));
+        std::memcpy(h_cnt, w->counters, sizeof(w->counters));
+        return PBVI_OK;
+    }
+
+    // 8. pbvi_q_values: best_v is final; exact Q of every (belief, action) from it, and nothing else
+    template <typename TS>
+    int finish_q_values(Call<TS>& c) {
+        int rc;
+        if (c.xr_pending) HIPCHK(hipStreamWaitEvent(stream_, ev_xr_[1], 0));       // (the side stream still reads this call's slabs)
+        if ((rc = ensure_belief_tiles())) return rc;   // pure fp64 scoring: k_dead did not run; the same lists from the beliefs alone
+        if ((rc = q_.ensure((size_t)B_ * A_ * sizeof(double)))) return rc;
+        if ((rc = q_res_.ensure((size_t)B_ * A_ * sizeof(double)))) return rc;
+        if ((rc = q_act_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+        if (q_want_best_ && (rc = fin_.best_res.ensure((size_t)c.pairs * sizeof(int32_t)))) return rc;
+        HIPCHK(launch_q_exact<T>(bel_.as<T>(), S_pad_, (int)B_, alpha_.as<T>(), S_pad_, (int)V_, view(), c.gamma, btl_.as<int32_t>(),
+                                 btc_.as<int32_t>(), best_v_.as<int32_t>(), c.windows ? dead_.as<uint8_t>() : nullptr,
+                                 sorted_ ? perm_.as<int32_t>() : nullptr, q_.as<double>(), q_res_.as<double>(), q_act_.as<int32_t>(),
+                                 q_want_best_ ? fin_.best_res.as<int32_t>() : nullptr, stream_));
+        if ((rc = end_call(c.screened, false, false, c.h_cnt))) return rc;
+        if (c.windows && dead_count_ < 0) dead_count_ = c.h_cnt[CNT_DEAD];    // k_dead counted this block's dead triples in this call
+        return PBVI_OK;
+    }
+
+    // 9. The stages behind the refinement: K4 actions, the decision tail (K6, K3), run_fetch's key matching, K5 belief
+    // dominance, the small results published or staged, the end of the call.  Run again by speculative_repeat.
+    template <typename TS>
+    int decide(Call<TS>& c) {
+        int rc;
+        const int AO = A_ * O_;
+        const ScoreStage<TS>& sc = c.sc;
+        int* aqcount = counters_.as<int>() + CNT_ACTION_QUEUE;
+        bool publish = false;
+        // K4: action
+        double* rdot_err = rdot_.as<double>() + (size_t)B_ * A_;
+        HIPCHK(launch_action<TS>((int)B_, c.scorer.view(), sc.sv, sc.rd_col0, sc.tol_rel, sc.chain, best_score_.as<double>(),
+                                 err_.as<double>(), rdot_.as<double>(), rdot_err, fin_.act.as<int32_t>(),
+                                 c.windows ? aqueue_.as<int32_t>() : nullptr, aqcount, stream_, c.io.tol_extra,
+                                 c.windows ? acand_.as<uint8_t>() : nullptr, sc.split));
+        if (c.windows)
+            HIPCHK(launch_refine_action<T>(bel_.as<T>(), S_pad_, (int)B_, alpha_.as<T>(), S_pad_, view(), c.gamma,
+                                           btl_.as<int32_t>(), btc_.as<int32_t>(), aqueue_.as<int32_t>(), aqcount, rdot_.as<double>(), rdot_err, best_v_.as<int32_t>(),
+                                           best_score_.as<double>(), err_.as<double>(), val_exact_.as<double>(),
+                                           fin_.act.as<int32_t>(), stream_, acand_.as<uint8_t>()));
+        HIPCHK(hipEventRecord(ev_[5], stream_));
+        if ((rc = decision_tail(fin_, c.gamma, false))) return rc;
+        res_action_ = fin_.res_act;
+        res_best_ = fin_.res_best;
+        if (early_.used) {   // final keys against the provisional ones whose rows are on their way (or there) already
+            HIPCHK(hipStreamWaitEvent(stream_, early_.ev[1], 0));          // (the provisional count and rows are complete)
+            HIPCHK(hipMemsetAsync(e_cnt_.as<int>() + 1, 0, 2 * sizeof(int), stream_));
+            hipLaunchKernelGGL(k_match_rows<T>, dim3((unsigned)std::min<int64_t>(B_, 2048)), dim3(256), 0, stream_, AO, O_, fin_.count(),
+                               fin_.uniq.as<int32_t>(), res_action_, res_best_, prov_.uniq.as<int32_t>(), prov_.res_act, prov_.res_best,
+                               e_cnt_.as<int>(), (int)early_.cap, e_slot_.as<int32_t>(), fin_.rows.as<T>(), (T*)early_.rows, (int64_t)S_);
+            HIPCHK(hipGetLastError());
+            const RunFetchDst& d = early_.dst;
+            publish = d.slot != nullptr && !(c.flags & PBVI_BELIEF_DOMINANCE) && d.best == nullptr && d.keep == nullptr &&
+                      is_pinned_host_pointer(d.slot) && is_pinned_host_pointer(d.index) && is_pinned_host_pointer(d.action);
+            if (!publish) HIPCHK(hipMemcpyAsync(words().early, e_cnt_.p, sizeof(words().early), hipMemcpyDeviceToHost, stream_));
+        }
+        HIPCHK(hipEventRecord(ev_[6], stream_));
+        if (c.xr_pending) {                            // the extra rows' maxima read the slabs K5's GEMM is about to overwrite
+            HIPCHK(hipStreamWaitEvent(stream_, ev_xr_[1], 0));
+            c.xr_pending = false;
+        }
+        // K5: belief dominance (keep is written in caller order)
+        if (c.flags & PBVI_BELIEF_DOMINANCE) {
+            if ((rc = value_max_device())) return rc;
+            HIPCHK(launch_keep<T>(bel_.as<T>(), S_pad_, fin_.rows.as<T>(), S_, (int)B_, S_, bs2_.as<double>(), fin_.inv.as<int32_t>(),
+                                  sorted_ ? perm_.as<int32_t>() : nullptr, keep_.as<uint8_t>(), stream_));
+        } else {
+            HIPCHK(hipMemsetAsync(keep_.p, 1, (size_t)B_, stream_));
+        }
+        RunFetchDst& dst = early_.dst;
+        dst.queued = false;
+        if (publish) {                                       // run_fetch into page-locked arrays: one kernel stores everything small
+            hipLaunchKernelGGL(k_publish, dim3((unsigned)((B_ + 255) / 256)), dim3(256), 0, stream_, (int)B_, e_slot_.as<int32_t>(),
+                               fin_.inv.as<int32_t>(), res_action_, (int32_t*)dst.slot, (int32_t*)dst.index, (int32_t*)dst.action,
+                               counters_.as<int>(), e_cnt_.as<int>(), (c.screened && scr_flag_.p) ? scr_flag_.as<int>() : nullptr, &words());
+            HIPCHK(hipGetLastError());
+            dst.queued = true;
+        } else if (early_.used && dst.slot != nullptr) {     // run_fetch: slots, index, actions (best, keep) with this read-back
+            if ((rc = out_begin())) return rc;
+            if ((rc = out_add(dst.slot, e_slot_.p, (size_t)B_ * sizeof(int32_t)))) return rc;
+            if ((rc = out_add_small((size_t)B_, dst.index, dst.action, dst.best, dst.keep))) return rc;
+            dst.queued = true;
+        }
+        return end_call(c.screened, publish, true, c.h_cnt);
+    }
+
+    // 10. A speculating call reads the refinement's counts now: there was deferred work after all -- do it, then the later
+    // stages again.
+    template <typename TS>
+    int speculative_repeat(Call<TS>& c) {
+        if (!c.speculate) return PBVI_OK;
+        last_deferred_nothing_ = rf_counts_[0] == 0 && rf_counts_[1] == 0;
+        if (last_deferred_nothing_) return PBVI_OK;
+        int rc;
+        if ((rc = refine_deferred(c.gamma, c.work))) return rc;
+        HIPCHK(hipMemsetAsync(counters_.as<int>() + CNT_ACTION_QUEUE, 0, sizeof(int), stream_));
+        HIPCHK(hipMemsetAsync(counters_.as<int>() + CNT_UNIQUE, 0, sizeof(int), stream_));   // (value_max resets its own queue)
+        return decide(c);
+    }
+
+    // 12. pbvi_stats_t of the call: stage times from ev_[0..7], counters, the GEMM's tile counts.
+    template <typename TS>
+    void fill_stats(const Call<TS>& c, pbvi_stats_t* st) const {
+        const int AO = A_ * O_;
+        const int64_t N = (int64_t)AO * (V_ + 1) + 2 * A_;
+        const ScoreStage<TS>& sc = c.sc;
+        const GemmPlan& plan = sc.plan;
+        std::memset(st, 0, sizeof(*st));
+        auto el = [&](int i, int j) {
+            float t = 0.f;
+            (void)hipEventElapsedTime(&t, ev_[i], ev_[j]);
+            return (double)t;
+        };
+        st->ms_project = el(0, 1);
+        st->ms_score = el(1, 2);
+        st->ms_argmax = el(2, 3);
+        st->ms_refine = el(3, 4);
+        st->ms_action = el(4, 5);
+        st->ms_assemble = el(5, 6);
+        st->ms_dominance = el(6, 7);
+        st->ms_total = el(0, 7);
+        st->n_pairs = c.pairs;
+        const int* h = c.h_cnt;
+        st->n_refine_candidates = h[4];
+        st->n_refined = h[0];
+        st->n_refined_actions = h[1];
+        st->n_unique = h[CNT_UNIQUE];
+        st->formulation = last_formulation_;
+        st->n_dead = c.windows ? dead_count_ : 0;              // counted by k_dead (when the block was first backed up)
+        if (mode_ == PBVI_DENSE) {
+            if (kF32) {
+                float t = 0.f;
+                (void)hipEventElapsedTime(&t, ev_pg_[0], ev_pg_[1]);
+                st->ms_project_gemm = (double)t;
+            }
+            st->project_flops = 2LL * AO * V_ * (int64_t)S_ * S_;
+            st->project_flops_executed = st->project_flops;
+            if (kF32) {
+                int64_t kt_sum = 0;
+                for (int64_t i = 0; i < dense_pairs_ && i < (int64_t)h_kcountD_.size(); ++i) kt_sum += h_kcountD_[(size_t)i];
+                st->project_flops_executed = kt_sum * 2LL * GEMM_BM * GEMM_BN * GEMM_BK;
+            }
+        }
+        st->score_flops = 2 * B_ * (int64_t)S_ * AO * V_;
+        int64_t kt_sum = 0;                                  // the GEMM's list lengths (none where it kept no lists)
+        for (size_t i = 0; i < c.n_kcount; ++i) kt_sum += c.h_kcount[i];
+        if (c.windows) {
+            st->score_flops_executed = kt_sum * 2LL * GEMM_BM * GEMM_BN * GEMM_BK;
+            st->score_tiles_dense = (int64_t)plan.tiles_m * plan.tiles_n * plan.k_tiles;
+            st->score_tiles_run = kt_sum;
+            st->split_k = plan.max_chunks;
+        } else if (sc.f64_pairs > 0) {   // fp64 MFMA path: 128 x 128 tiles, lists in 32-column steps
+            st->score_flops_executed = kt_sum * 2LL * 128 * gemm_f64_bn((int)std::min<int64_t>(c.use_push ? V_ : N, 0x7fffffff)) * 32;
+            st->score_tiles_dense = sc.f64_pairs * (S_pad_ / GEMM_BK);
+            st->score_tiles_run = kt_sum;
+            st->split_k = 1;
+        } else {
+            st->score_flops_executed = st->score_flops;
+            st->split_k = 1;
+        }
+        st->screened = c.screened ? 1 : 0;
+        st->fused_projection = sc.fused ? 1 : 0;
+        st->score_split = sc.split;
+        st->gamma_chunks = sc.chunks;
+        if (sc.chunks > 1) {                                 // sums over the chunks; the folds count with the argmax
+            double fold = 0.0;
+            c.scorer.tile_times(ev_[0], &st->ms_project, &st->ms_score, &fold);
+            st->ms_argmax = fold + el(2, 3);
+        }
+    }
+
     int ensure_screen();
     int sync_screen();
 
@@ -2467,7 +3023,7 @@ class EngineT : public EngineBase {
         if (full_valid_) return PBVI_OK;
         int rc = out_full_.ensure((size_t)res_B_ * S_ * sizeof(T));
         if (rc) return rc;
-        HIPCHK(launch_expand_rows<T>(out_.as<T>(), inv_.as<int32_t>(), out_full_.as<T>(), (int)res_B_, S_, stream_));
+        HIPCHK(launch_expand_rows<T>(fin_.rows.as<T>(), fin_.inv.as<int32_t>(), out_full_.as<T>(), (int)res_B_, S_, stream_));
         full_valid_ = true;
         return PBVI_OK;
     }
@@ -2482,10 +3038,19 @@ class EngineT : public EngineBase {
             if ((rc = ensure_full())) return rc;
             if ((rc = out_add(out_alpha, out_full_.p, B * S_ * sizeof(T)))) return rc;
         }
-        if (out_action && (rc = out_add(out_action, res_action_, B * sizeof(int32_t)))) return rc;
-        if (out_best && (rc = out_add(out_best, res_best_, B * A_ * O_ * sizeof(int32_t)))) return rc;
-        if (out_keep && (rc = out_add(out_keep, keep_.p, B))) return rc;
+        if ((rc = out_add_small(B, nullptr, out_action, out_best, out_keep))) return rc;
         return out_finish();
+    }
+
+    // the small per-belief results of the decision, each to where the caller wants it (NULL: not wanted): index into the
+    // distinct rows, actions, best_alpha_ind, keep mask
+    int out_add_small(size_t B, int32_t* index, int32_t* action, int32_t* best, uint8_t* keep) {
+        int rc;
+        if (index && (rc = out_add(index, fin_.inv.p, B * sizeof(int32_t)))) return rc;
+        if (action && (rc = out_add(action, res_action_, B * sizeof(int32_t)))) return rc;
+        if (best && (rc = out_add(best, res_best_, B * A_ * O_ * sizeof(int32_t)))) return rc;
+        if (keep && (rc = out_add(keep, keep_.p, B))) return rc;
+        return PBVI_OK;
     }
 
     int64_t unique_count() const override { return have_result_ ? res_unique_ : -1; }
@@ -2495,8 +3060,8 @@ class EngineT : public EngineBase {
         HIPCHK(hipSetDevice(device_));
         int rc;
         if ((rc = out_begin())) return rc;
-        if (out_rows && (rc = out_add(out_rows, out_.p, (size_t)res_unique_ * S_ * sizeof(T)))) return rc;
-        if (out_index && (rc = out_add(out_index, inv_.p, (size_t)res_B_ * sizeof(int32_t)))) return rc;
+        if (out_rows && (rc = out_add(out_rows, fin_.rows.p, (size_t)res_unique_ * S_ * sizeof(T)))) return rc;
+        if (out_index && (rc = out_add(out_index, fin_.inv.p, (size_t)res_B_ * sizeof(int32_t)))) return rc;
         return out_finish();
     }
 
@@ -2509,53 +3074,40 @@ class EngineT : public EngineBase {
         if (!out_rows || !out_slot || !out_index || !out_action) FAIL(PBVI_EINVAL, "backup_run_fetch: NULL destination");
         if (cap_rows < B_) FAIL(PBVI_EINVAL, "backup_run_fetch: out_rows must have room for one row per belief");
         if (!is_pinned_host_pointer(out_rows)) FAIL(PBVI_EINVAL, "backup_run_fetch: out_rows must be page-locked host memory (pbvi_host_alloc)");
-        early_rows_ = out_rows;
-        early_cap_ = cap_rows;
-        rf_dst_ = RunFetchDst{out_slot, out_index, out_action, out_best, out_keep, false};
+        early_.rows = out_rows;
+        early_.cap = cap_rows;
+        early_.dst = RunFetchDst{out_slot, out_index, out_action, out_best, out_keep, false};
         int rc = backup_run(gamma, flags, st);
-        early_rows_ = nullptr;
-        const bool queued = rf_dst_.queued;
-        rf_dst_ = RunFetchDst{};
+        const bool queued = early_.dst.queued;
+        early_.rows = nullptr;                               // (whether or not the backup failed; `used` stays for what follows)
+        early_.dst = RunFetchDst{};
         if (rc) return rc;
-        const size_t B = (size_t)res_B_;
         int64_t used = res_unique_;
-        const bool early_ok = early_used_ && !words().early[2];
+        const bool early_ok = early_.used && !words().early[2];
         if (early_ok) used = (int64_t)words().early[0] + words().early[1];
-        if (queued) {                                        // the small arrays came with the pipeline's last read-back
-            if ((rc = out_flush())) return rc;               // (host-side copies of staged items; the stream is idle)
-            if (!early_ok) {                                 // the slots overflowed: rows in the plain order
-                if ((rc = out_begin())) return rc;
-                if ((rc = out_add(out_rows, out_.p, (size_t)res_unique_ * S_ * sizeof(T)))) return rc;
-                if ((rc = out_finish())) return rc;
-            }
-        } else {                                             // the early path did not apply: everything now
+        // the small arrays came with the pipeline's last read-back (host-side copies of staged items; the stream is idle)
+        if (queued && (rc = out_flush())) return rc;
+        if (!queued || !early_ok) {   // the early path did not apply: everything now; the slots overflowed: rows in the plain order
             if ((rc = out_begin())) return rc;
-            if ((rc = out_add(out_rows, out_.p, (size_t)res_unique_ * S_ * sizeof(T)))) return rc;
-            if ((rc = out_add(out_index, inv_.p, B * sizeof(int32_t)))) return rc;
-            if ((rc = out_add(out_action, res_action_, B * sizeof(int32_t)))) return rc;
-            if (out_best && (rc = out_add(out_best, res_best_, B * A_ * O_ * sizeof(int32_t)))) return rc;
-            if (out_keep && (rc = out_add(out_keep, keep_.p, B))) return rc;
+            if ((rc = out_add(out_rows, fin_.rows.p, (size_t)res_unique_ * S_ * sizeof(T)))) return rc;
+            if (!queued && (rc = out_add_small((size_t)res_B_, out_index, out_action, out_best, out_keep))) return rc;
             if ((rc = out_finish())) return rc;
         }
         if (!early_ok)
             for (int64_t u = 0; u < res_unique_; ++u) out_slot[u] = (int32_t)u;
         if (n_unique) *n_unique = res_unique_;
         if (n_slots) *n_slots = used;
-        early_used_ = false;
+        early_.used = false;
         return PBVI_OK;
     }
 
     int fetch_compact(void* out_rows, int32_t* out_index, int32_t* out_action, int32_t* out_best, uint8_t* out_keep) override {
         if (!have_result_) FAIL(PBVI_EINVAL, "backup_fetch_compact: no backup result resident");
         HIPCHK(hipSetDevice(device_));
-        const size_t B = (size_t)res_B_;
         int rc;
         if ((rc = out_begin())) return rc;
-        if (out_rows && (rc = out_add(out_rows, out_.p, (size_t)res_unique_ * S_ * sizeof(T)))) return rc;
-        if (out_index && (rc = out_add(out_index, inv_.p, B * sizeof(int32_t)))) return rc;
-        if (out_action && (rc = out_add(out_action, res_action_, B * sizeof(int32_t)))) return rc;
-        if (out_best && (rc = out_add(out_best, res_best_, B * A_ * O_ * sizeof(int32_t)))) return rc;
-        if (out_keep && (rc = out_add(out_keep, keep_.p, B))) return rc;
+        if (out_rows && (rc = out_add(out_rows, fin_.rows.p, (size_t)res_unique_ * S_ * sizeof(T)))) return rc;
+        if ((rc = out_add_small((size_t)res_B_, out_index, out_action, out_best, out_keep))) return rc;
         return out_finish();
     }
 
@@ -2620,7 +3172,7 @@ class EngineT : public EngineBase {
         HIPCHK(hipSetDevice(device_));
         int rc = keys_tmp_.ensure((size_t)res_unique_ * sizeof(uint64_t));
         if (rc) return rc;
-        hipLaunchKernelGGL(k_row_hash<T>, dim3((unsigned)res_unique_), dim3(256), 0, stream_, out_.as<T>(), S_, S_,
+        hipLaunchKernelGGL(k_row_hash<T>, dim3((unsigned)res_unique_), dim3(256), 0, stream_, fin_.rows.as<T>(), S_, S_,
                            keys_tmp_.as<unsigned long long>());
         HIPCHK(hipGetLastError());
         if ((rc = out_begin())) return rc;
@@ -2637,7 +3189,7 @@ class EngineT : public EngineBase {
         int rc = keys_tmp_.ensure((size_t)res_unique_ * (1 + O_) * sizeof(int32_t));
         if (rc) return rc;
         hipLaunchKernelGGL(k_gather_keys, dim3((unsigned)((res_unique_ + 63) / 64)), dim3(64), 0, stream_, (int)res_unique_, A_, O_,
-                           uniq_.as<int32_t>(), res_action_, res_best_, keys_tmp_.as<int32_t>());
+                           fin_.uniq.as<int32_t>(), res_action_, res_best_, keys_tmp_.as<int32_t>());
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(out_keys, keys_tmp_.p, (size_t)res_unique_ * (1 + O_) * sizeof(int32_t), hipMemcpyDefault, stream_));
         HIPCHK(hipStreamSynchronize(stream_));
@@ -2659,7 +3211,7 @@ class EngineT : public EngineBase {
             dst = keys_tmp_.as<int32_t>();
         }
         hipLaunchKernelGGL(k_pack_exchange, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, stream_, (int)res_B_, (int)per,
-                           (int)res_unique_, A_, O_, inv_.as<int32_t>(), res_action_, keep_.as<uint8_t>(), uniq_.as<int32_t>(),
+                           (int)res_unique_, A_, O_, fin_.inv.as<int32_t>(), res_action_, keep_.as<uint8_t>(), fin_.uniq.as<int32_t>(),
                            res_best_, dst);
         HIPCHK(hipGetLastError());
         if (!direct) HIPCHK(hipMemcpyAsync(out, dst, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
@@ -2855,7 +3407,7 @@ class EngineT : public EngineBase {
         if ((rc = out_begin())) return rc;
         if ((rc = out_add(out_q, q_res_.p, (size_t)B_ * A_ * sizeof(double)))) return rc;
         if (out_action && (rc = out_add(out_action, q_act_.p, (size_t)B_ * sizeof(int32_t)))) return rc;
-        if (out_best && (rc = out_add(out_best, best_res_.p, (size_t)B_ * A_ * O_ * sizeof(int32_t)))) return rc;
+        if (out_best && (rc = out_add(out_best, fin_.best_res.p, (size_t)B_ * A_ * O_ * sizeof(int32_t)))) return rc;
         return out_finish();
     }
 
@@ -3280,13 +3832,7 @@ int EngineT<T>::value_max_device() {
             HIPCHK(launch_gemm_nt_f64_ff32((const float*)bel_.p, S_pad_, (int)B_, (const float*)alpha_.p, S_pad_, (int)V_,
                                            slabs_.as<double>(), (int)V_, S_pad_, nzA_.as<uint8_t>(), klist_.as<int>(),
                                            kcount_.as<int>(), stream_, split, slab));
-            SlabView<double> svd;
-            svd.slabs = slabs_.as<double>();
-            svd.slab_stride = 0;              // K parts folded into the first slab by the launcher
-            svd.ldc = (int)V_;
-            svd.nchunks = nullptr;
-            svd.tiles_m = 0;
-            svd.fixed = 1;
+            const SlabView<double> svd = SlabView<double>::single(slabs_.as<double>(), (int)V_);   // K parts folded into the first slab by the launcher
             HIPCHK(launch_argmax<double>(svd, (int)V_, 1, (int)B_, nullptr, 0.0, 0.0, nullptr, 0, bv2_.as<int32_t>(),
                                          bs2_.as<double>(), err2_.as<double>(), nullptr, qc, stream_));
             return PBVI_OK;
@@ -3301,14 +3847,7 @@ int EngineT<T>::value_max_device() {
     HIPCHK(launch_argmax<T>(sv, (int)V_, 1, (int)B_, nullptr, tie_window(k_chunk), 0.0, chain_steps(), 1, bv2_.as<int32_t>(),
                             bs2_.as<double>(), err2_.as<double>(), rescore ? queue2_.as<int32_t>() : nullptr, qc, stream_));
     if (rescore) {
-        if (!btl_valid_) {   // tile lists of the resident block (the backup's k_dead builds them too)
-            const int k_tiles = S_pad_ / GEMM_BK;
-            if ((rc = btl_.ensure((size_t)B_ * k_tiles * sizeof(int32_t)))) return rc;
-            if ((rc = btc_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
-            HIPCHK(launch_belief_tiles<T>(bel_.as<T>(), S_pad_, (int)B_, S_, k_tiles, btl_.as<int32_t>(), btc_.as<int32_t>(),
-                                          stream_));
-            btl_valid_ = true;
-        }
+        if ((rc = ensure_belief_tiles())) return rc;   // tile lists of the resident block (the backup's k_dead builds them too)
         RefineWork work;
         if ((rc = refine_work(B_, V_, &work))) return rc;
         HIPCHK(launch_refine<T>(false, sv, (int)V_, 1, (int)B_, queue2_.as<int32_t>(), qc, bel_.as<T>(), S_pad_,
@@ -3690,13 +4229,7 @@ int EngineT<T>::stage_scores_tiled(double gamma, const ScoreIO& io, int want_spl
     }
     HIPCHK(hipEventRecord(io.ev[2], stream_));
     HIPCHK(hipStreamWaitEvent(stream_, io.join, 0));       // dead flags + rdot ready
-    SlabView<T> full;
-    full.slabs = scores_.as<T>();
-    full.slab_stride = 0;
-    full.ldc = (int)ldd;
-    full.nchunks = nullptr;
-    full.tiles_m = 0;
-    full.fixed = 1;
+    const SlabView<T> full = SlabView<T>::single(scores_.as<T>(), (int)ldd);
     out->plan = plan_;                                     // (the last chunk's: statistics)
     out->tol_rel = on_device ? -1.0 : tol;                 // the widest window over the chunks
     out->chain = on_device ? chain_max_.as<int>() : nullptr;
@@ -3835,465 +4368,6 @@ int EngineT<T>::backup_run(double gamma, int flags, pbvi_stats_t* st) {
         }
     }
     return run_pipeline<T>(*this, gamma, flags, st);
-}
-
-// One backup: `scorer` (this engine, or its fp32 screen) produces scores and first maxima; this engine, which owns
-// the operands in their original precision, decides near-ties, actions and assembles the rows.
-template <typename T>
-template <typename TS>
-int EngineT<T>::run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_stats_t* st) {
-    constexpr bool windows = sizeof(TS) == 4;              // fp32 scores: tie windows + fp64 re-decision
-    constexpr bool screened = sizeof(TS) != sizeof(T);
-    int rc;
-    const int AO = A_ * O_;
-    const int64_t Vt = V_ + 1;                 // alpha rows + magnitude row
-    const int64_t N = (int64_t)AO * Vt + 2 * A_;
-    const int64_t pairs = B_ * AO;
-    if (N > 0x7fffffff || pairs > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "backup_run: A*O*(V+1) or B*A*O exceeds int32");
-    const ModelView<T> mv = view();
-    const bool use_push = scorer.choose_push(N);
-    last_formulation_ = use_push ? 2 : 1;
-    if ((rc = best_v_.ensure((size_t)pairs * sizeof(int32_t)))) return rc;
-    if ((rc = best_score_.ensure((size_t)pairs * sizeof(double)))) return rc;
-    if ((rc = err_.ensure((size_t)pairs * sizeof(double)))) return rc;
-    if ((rc = queue_.ensure((size_t)pairs * sizeof(int32_t)))) return rc;
-    if ((rc = dead_.ensure((size_t)pairs))) return rc;
-    if ((rc = rdot_.ensure((size_t)B_ * A_ * 2 * sizeof(double)))) return rc;
-    if ((rc = action_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
-    if ((rc = aqueue_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
-    if ((rc = acand_.ensure((size_t)B_ * A_))) return rc;
-    if (!q_only_ && (rc = out_.ensure((size_t)B_ * S_ * sizeof(T)))) return rc;
-    if ((rc = keep_.ensure((size_t)B_))) return rc;
-    int* qcount = counters_.as<int>() + CNT_QUEUE;
-    int* aqcount = counters_.as<int>() + CNT_ACTION_QUEUE;
-    if (windows && (rc = stage_reserve(256))) return rc;      // the pinned bounce buffer of the fetches that follow, allocated while the stream is idle
-    HIPCHK(hipMemsetAsync(counters_.p, 0, CNT_SLOTS * sizeof(int), stream_));
-
-    HIPCHK(hipEventRecord(ev_[0], stream_));
-    // Belief-only work (dead triples, b.ER: ~0.1 ms each) on the side stream, beside the projection.
-    // (Beside the persistent stream-K GEMM they starve: k_rdot took 3.1 ms there instead of 0.1.)
-    static const bool no_side = getenv("PBVI_NO_SIDE_STREAM") != nullptr;      // debug / A-B only
-    hipStream_t side = no_side ? stream_ : stream2_;
-    const int k_tiles = S_pad_ / GEMM_BK;
-    HIPCHK(hipEventRecord(ev_fork_, stream_));
-    HIPCHK(hipStreamWaitEvent(side, ev_fork_, 0));
-    static const bool lists_on_side = getenv("PBVI_LISTS_ON_SIDE") != nullptr;      // debug / A-B only: lists behind k_dead
-    hipStream_t lists = no_side ? nullptr : (lists_on_side ? side : stream3_);
-    // (the tile lists need the block's zero map only: where the block was indexed just now they do not wait for its gather)
-    if (lists != nullptr && lists != side)
-        HIPCHK(hipStreamWaitEvent(lists, (!screened && ev_nzA_ != nullptr && nzA_ver_ == bel_ver_) ? ev_nzA_ : ev_fork_, 0));
-    if (windows) {   // exact, from the supports of the ORIGINAL operands (an fp32 copy may have flushed tiny values to zero)
-        if ((rc = btl_.ensure((size_t)B_ * k_tiles * sizeof(int32_t)))) return rc;
-        if ((rc = btc_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
-        if ((rc = val_exact_.ensure((size_t)B_ * A_ * (1 + O_) * ACTION_SPLIT * sizeof(double)))) return rc;
-        // Dead triples and the per-belief tile lists are a function of the belief block and the model alone: computed on
-        // the first backup of a block, kept for the following ones (a solve backs a block up once; update_passes > 1,
-        // the belief-dominance loops of the notebooks and the benchmark back the same block up again and again).  Like
-        // the block's sort order and zero-tile map they index the INPUT; nothing of a backup's result is kept.
-        static const bool no_cache = getenv("PBVI_NO_DEAD_CACHE") != nullptr;       // debug / A-B only
-        if (dead_ver_ != bel_ver_ || !btl_valid_ || dead_pairs_ != pairs || no_cache) {
-            const bool have_flags = rowflags_ver_ == bel_ver_ && rowflags_.p != nullptr;   // left by the block's indexing pass
-            HIPCHK(launch_dead<T>(bel_.as<T>(), S_pad_, (int)B_, mv, nzBw_.as<unsigned long long>(), k_tiles, dead_.as<uint8_t>(),
-                                  btl_.as<int32_t>(), btc_.as<int32_t>(), counters_.as<int>() + CNT_DEAD, side,
-                                  have_flags ? rowflags_.as<uint8_t>() : nullptr,
-                                  have_flags && sorted_ ? perm_.as<int32_t>() : nullptr));
-            btl_valid_ = true;
-            dead_ver_ = bel_ver_;
-            dead_pairs_ = pairs;
-            dead_count_ = -1;                                // read back with this call's counters
-        }
-    }
-    if (use_push) {   // b . ER[:,a] in f64 (the alpha-side gets it from Gamma's reward rows)
-        if ((rc = prd_.ensure((size_t)B_ * A_ * sizeof(double)))) return rc;
-        HIPCHK(launch_rdot<T>(bel_.as<T>(), S_pad_, (int)B_, mv, windows ? btl_.as<int32_t>() : nullptr,
-                              windows ? btc_.as<int32_t>() : nullptr, prd_.as<double>(), side));
-    }
-    // (run_fetch's provisional pipeline: its counters are cleared here, beside the projection, not in front of its kernels)
-    const bool early_wanted = windows && !q_only_ && early_rows_ != nullptr && !(flags & PBVI_BELIEF_DOMINANCE) && early_cap_ >= B_ && !no_side;
-    if (early_wanted) {
-        if ((rc = e_cnt_.ensure(4 * sizeof(int)))) return rc;
-        HIPCHK(hipMemsetAsync(e_cnt_.p, 0, 4 * sizeof(int), side));
-    }
-    HIPCHK(hipEventRecord(ev_join_, side));
-
-    ScoreIO io;
-    io.best_v = best_v_.as<int32_t>();
-    io.best_score = best_score_.as<double>();
-    io.err = err_.as<double>();
-    io.queue = windows ? queue_.as<int32_t>() : nullptr;
-    io.qcount = qcount;
-    io.dead = windows ? dead_.as<uint8_t>() : nullptr;
-    io.prd = use_push ? prd_.as<double>() : nullptr;
-    io.join = ev_join_;
-    io.side = lists;
-    io.ev = ev_;
-    io.stats = st != nullptr;
-    // a screen multiplies operands rounded to fp32 (alpha, belief, RTO: 2^-24 relative each) and gamma in fp32
-    io.tol_extra = screened ? 4.0 * 5.9604644775390625e-08 : 0.0;
-    io.allow_split = !screened;
-    if (windows && !use_push && scorer.tiling_mode_ != 0) {   // Gamma tiling plans with what is free: the refinement's work
-        RefineWork reserve;                                   // lists (the largest buffers of the later stages) come first
-        if ((rc = refine_work(pairs, V_, &reserve))) return rc;
-    }
-    ScoreStage<TS> sc;
-    if ((rc = scorer.stage_scores(gamma, use_push, io, &sc))) return rc;
-    const SlabView<TS>& sv = sc.sv;
-    const GemmPlan plan = sc.plan;
-    bool xr_pending = false;
-    if (use_push && !screened) {   // max_v b.alpha_v of these beliefs from the GEMM's extra rows (exact engines only)
-        // beside the refinement, on the side stream: a wave per belief row over V scores is 0.1 ms that nothing in this
-        // call waits for (the slabs stay as they are until the next GEMM; K5 is not run with this formulation's extras
-        // pending -- it joins first, below)
-        if ((rc = vmax_bk_.ensure((size_t)B_ * sizeof(double)))) return rc;
-        hipStream_t xs = no_side ? stream_ : stream2_;
-        if (xs != stream_) {
-            HIPCHK(hipEventRecord(ev_xr_[0], stream_));
-            HIPCHK(hipStreamWaitEvent(xs, ev_xr_[0], 0));
-        }
-        hipLaunchKernelGGL(k_extra_rowmax<TS>, dim3((unsigned)((B_ + 3) / 4)), dim3(256), 0, xs, sv, sc.extra_row0, (int)B_,
-                           (int)V_, sorted_ ? perm_.as<int32_t>() : nullptr, vmax_bk_.as<double>());
-        HIPCHK(hipGetLastError());
-        if (xs != stream_) {
-            HIPCHK(hipEventRecord(ev_xr_[1], xs));
-            xr_pending = true;
-        }
-    }
-    // List lengths of this GEMM, for the statistics (K5 rebuilds the lists for its own GEMM later): into PAGE-LOCKED memory.
-    // (The copy used to land in a std::vector: a device-to-pageable copy is staged by the runtime and holds the host until
-    // the GEMM and the argmax in front of it have finished, so nothing behind the argmax was enqueued before then.)
-    const int* h_kcount = nullptr;
-    size_t n_kcount = 0;
-    const int64_t f64_pairs = sc.f64_pairs;
-    if (st && (windows || f64_pairs > 0)) {
-        n_kcount = windows ? (size_t)plan.tiles_m * plan.tiles_n : (size_t)f64_pairs;
-        // (no copy into it is pending: every call ends synchronised)
-        if (!kc_pin_.ensure(n_kcount * sizeof(int), std::max<size_t>(n_kcount * 2, 4096) * sizeof(int)))
-            FAIL(PBVI_ENOMEM, "pinned buffer for the list lengths");
-        h_kcount = kc_pin_.as<int>();                                 // (the copy itself is enqueued behind the refinement, below)
-    }
-    // fp64 re-decision of near-ties.  The per-entry pass hands entries with many tied candidates on to grid-wide
-    // passes whose launch needs the host to know how many there are -- a read-back in the middle of the pipeline
-    // (~30 us of idle device).  A value function either has such ties (absorbing goals, unexplored regions: every backup
-    // of a solve loop) or it has not (the synthetic sets): after a backup that deferred nothing the next one SPECULATES
-    // that it will not either -- the later stages are enqueued at once, the counts are read at the end, and if there was
-    // deferred work after all it runs then and the later stages are repeated.
-    // Early rows (pbvi_backup_run_fetch): the first maxima and the action values they give decide MOST beliefs' keys for
-    // good -- the refinement re-decides near-ties only -- so the distinct rows of that provisional decision are assembled
-    // and written to the caller's page-locked buffer on the side stream NOW, under the refinement, the action stage and
-    // the dedup (the 8 MB of rows used to cross PCIe after all of them: 0.17 ms of a 3 ms backup).  Afterwards the final
-    // keys are matched against the provisional ones (k_match_rows): rows already on the host keep their slot, the few
-    // that the refinement changed are appended.  Snapshots, because the refinement rewrites best_v / best_score in place.
-    early_used_ = false;
-    if (early_wanted) {
-        int rc2;
-        if ((rc2 = e_bv_.ensure((size_t)pairs * sizeof(int32_t)))) return rc2;
-        if ((rc2 = e_rdot_.ensure((size_t)B_ * A_ * 2 * sizeof(double)))) return rc2;
-        if ((rc2 = e_act_.ensure((size_t)B_ * sizeof(int32_t)))) return rc2;
-        if ((rc2 = e_ares_.ensure((size_t)B_ * sizeof(int32_t)))) return rc2;
-        if ((rc2 = e_bres_.ensure((size_t)pairs * sizeof(int32_t)))) return rc2;
-        if ((rc2 = e_rep_.ensure((size_t)B_ * sizeof(int32_t)))) return rc2;
-        if ((rc2 = e_uniq_.ensure((size_t)B_ * sizeof(int32_t)))) return rc2;
-        if ((rc2 = e_inv_.ensure((size_t)B_ * sizeof(int32_t)))) return rc2;
-        if ((rc2 = e_slotd_.ensure((size_t)B_ * sizeof(int32_t)))) return rc2;
-        if ((rc2 = e_slot_.ensure((size_t)B_ * sizeof(int32_t)))) return rc2;
-        if ((rc2 = e_cnt_.ensure(4 * sizeof(int)))) return rc2;
-        if ((rc2 = e_out_.ensure((size_t)B_ * S_ * sizeof(T)))) return rc2;
-        for (hipEvent_t& ev : ev_early_) HIPCHK(new_event(&ev, hipEventDisableTiming, "hipEventDestroy(early)"));
-        // The provisional decision itself is 40 us of small kernels: they run HERE, on the main stream in front of the
-        // refinement (which rewrites best_v / best_score in place), and only the copy -- 8 MB over PCIe, ~150 us, few blocks
-        // -- goes to the side stream.  (Snapshots of the three arrays + the whole provisional pipeline beside the
-        // refinement cost it 0.13 ms: a net loss.)
-        HIPCHK(launch_action<TS>((int)B_, scorer.view(), sv, sc.rd_col0, sc.tol_rel, sc.chain, best_score_.as<double>(), err_.as<double>(),
-                                 e_rdot_.as<double>(), e_rdot_.as<double>() + (size_t)B_ * A_, e_act_.as<int32_t>(), nullptr, nullptr, stream_,
-                                 io.tol_extra, nullptr, sc.split));
-        const int32_t* pa = e_act_.as<int32_t>();
-        const int32_t* pb = e_bv_.as<int32_t>();
-        if (sorted_) {
-            hipLaunchKernelGGL(k_unpermute, dim3((unsigned)B_), dim3(64), 0, stream_, (int)B_, AO, perm_.as<int32_t>(), e_act_.as<int32_t>(),
-                               best_v_.as<int32_t>(), e_ares_.as<int32_t>(), e_bres_.as<int32_t>());
-            HIPCHK(hipGetLastError());
-            pa = e_ares_.as<int32_t>();
-            pb = e_bres_.as<int32_t>();
-        } else {                                             // (one row block: the keys as they are now)
-            HIPCHK(hipMemcpyAsync(e_bv_.p, best_v_.p, (size_t)pairs * sizeof(int32_t), hipMemcpyDeviceToDevice, stream_));
-        }
-        HIPCHK(launch_dedup((int)B_, A_, O_, pa, pb, e_rep_.as<int32_t>(), e_uniq_.as<int32_t>(), e_inv_.as<int32_t>(),
-                            e_slotd_.as<int32_t>(), e_cnt_.as<int>(), stream_));
-        HIPCHK(launch_assemble<T>(alpha_.as<T>(), S_pad_, mv, gamma, pa, pb, e_uniq_.as<int32_t>(), e_cnt_.as<int>(), (int)B_,
-                                  e_out_.as<T>(), S_, stream_));
-        HIPCHK(hipEventRecord(ev_early_[0], stream_));
-        hipStream_t es = stream2_;
-        HIPCHK(hipStreamWaitEvent(es, ev_early_[0], 0));
-        // The copy is a plain hipMemcpyAsync on the side stream, sized by the host: it waits (below, once the refinement is
-        // enqueued) for this 4-byte count.  A copy KERNEL storing to the page-locked buffer needs no host and reaches the
-        // link's rate (54.7 GB/s, profiles/microbench/pcie_store.hip) -- but beside it k_refine took 0.24 ms instead of 0.14
-        // whatever its grid (8 .. 1024 blocks): the runtime's copy disturbs the refinement far less (0.15 ms).
-        early_dma_pending_ = true;
-        HIPCHK(hipMemcpyAsync(&words().provisional, e_cnt_.p, sizeof(int), hipMemcpyDeviceToHost, es));
-        HIPCHK(hipEventRecord(ev_early_[0], es));
-        early_used_ = true;
-    }
-    RefineWork work;
-    bool speculate = false;
-    if (windows) {
-        if ((rc = refine_work(pairs, V_, &work))) return rc;
-        if constexpr (kF32 && !screened) {
-            // Gamma is in HBM as the GEMM read it (projection kernel, not the fused GEMM): the per-entry pass first
-            // separates candidates by fp64 sums over those fp32 rows (backup_kernels.h, RefineWork::gam)
-            static const bool no_l1 = getenv("PBVI_NO_L1_SCREEN") != nullptr;      // debug / A-B only
-            // (not in a tiled call: a chunk's rows are gone by now)
-            if (!no_l1 && !use_push && !sc.fused && sc.chunks <= 1 && mode_ == PBVI_SPARSE) {
-                work.gam = (const float*)gam_.p;
-                work.ldg = S_pad_;
-                work.l1_rel = (double)(R_ + 4) * 5.9604644775390625e-08;
-            }
-        }
-        // the counts land in two of the engine's pinned flag words -- not in the staging buffer: run_fetch stages results
-        // through that one before the counts are read, and out_add may reset or reallocate it
-        rf_counts_ = words().deferred;
-        rf_counts_[0] = rf_counts_[1] = 0;
-        static const bool no_spec = getenv("PBVI_NO_SPECULATION") != nullptr;      // debug / A-B only
-        // (not with the belief-dominance test: its own value-max refinement re-uses the work-list buffers, so the
-        // deferred entries of this one have to be finished first)
-        // (nor for pbvi_q_values, whose one stage behind the refinement needs the final best_v)
-        speculate = !no_spec && !q_only_ && last_deferred_nothing_ && work.items_v != nullptr && !(flags & PBVI_BELIEF_DOMINANCE);
-        HIPCHK((launch_refine_scan<T, TS>(true, sv, (int)V_, AO, (int)pairs, queue_.as<int32_t>(), qcount, bel_.as<T>(), S_pad_,
-                                          alpha_.as<T>(), S_pad_, mv, gamma, btl_.as<int32_t>(), btc_.as<int32_t>(),
-                                          nzB_.as<uint8_t>(), best_v_.as<int32_t>(), best_score_.as<double>(), err_.as<double>(),
-                                          counters_.as<int>() + CNT_REFINE_CAND, work, rf_counts_, stream_)));
-        if (!speculate && work.items_v != nullptr) {
-            HIPCHK(hipStreamSynchronize(stream_));
-            last_deferred_nothing_ = rf_counts_[0] == 0 && rf_counts_[1] == 0;
-            HIPCHK(launch_refine_deferred<T>(true, (int)V_, AO, bel_.as<T>(), S_pad_, alpha_.as<T>(), S_pad_, mv, gamma,
-                                             best_v_.as<int32_t>(), best_score_.as<double>(), err_.as<double>(), work,
-                                             rf_counts_[0], rf_counts_[1], stream_));
-        }
-    }
-    if (early_used_ && early_dma_pending_) {   // the refinement is enqueued: now the host can wait for the provisional count
-        HIPCHK(hipEventSynchronize(ev_early_[0]));
-        const int np = words().provisional;
-        if (np > 0)
-            HIPCHK(hipMemcpyAsync(early_rows_, e_out_.p, (size_t)np * S_ * sizeof(T), hipMemcpyDeviceToHost, stream2_));
-        HIPCHK(hipEventRecord(ev_early_[1], stream2_));
-        early_dma_pending_ = false;
-    }
-    if (h_kcount != nullptr)   // statistics: not in front of the provisional decision and the refinement (K5 re-uses kcount_ later)
-        HIPCHK(hipMemcpyAsync(kc_pin_.p, scorer.kcount_.p, n_kcount * sizeof(int), hipMemcpyDeviceToHost, stream_));
-    HIPCHK(hipEventRecord(ev_[4], stream_));
-    const int32_t* perm = sorted_ ? perm_.as<int32_t>() : nullptr;
-    if (q_only_) {   // pbvi_q_values: best_v is final; exact Q of every (belief, action) from it, and nothing else
-        if (xr_pending) HIPCHK(hipStreamWaitEvent(stream_, ev_xr_[1], 0));       // (the side stream still reads this call's slabs)
-        if (!btl_valid_) {   // pure fp64 scoring: k_dead did not run; the same lists from the beliefs alone
-            if ((rc = btl_.ensure((size_t)B_ * k_tiles * sizeof(int32_t)))) return rc;
-            if ((rc = btc_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
-            HIPCHK(launch_belief_tiles<T>(bel_.as<T>(), S_pad_, (int)B_, S_, k_tiles, btl_.as<int32_t>(), btc_.as<int32_t>(), stream_));
-            btl_valid_ = true;
-        }
-        if ((rc = q_.ensure((size_t)B_ * A_ * sizeof(double)))) return rc;
-        if ((rc = q_res_.ensure((size_t)B_ * A_ * sizeof(double)))) return rc;
-        if ((rc = q_act_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
-        if (q_want_best_ && (rc = best_res_.ensure((size_t)pairs * sizeof(int32_t)))) return rc;
-        HIPCHK(launch_q_exact<T>(bel_.as<T>(), S_pad_, (int)B_, alpha_.as<T>(), S_pad_, (int)V_, mv, gamma, btl_.as<int32_t>(),
-                                 btc_.as<int32_t>(), best_v_.as<int32_t>(), windows ? dead_.as<uint8_t>() : nullptr, perm,
-                                 q_.as<double>(), q_res_.as<double>(), q_act_.as<int32_t>(),
-                                 q_want_best_ ? best_res_.as<int32_t>() : nullptr, stream_));
-        PinnedWords* w = &words();
-        HIPCHK(hipMemcpyAsync(w->counters, counters_.p, sizeof(w->counters), hipMemcpyDeviceToHost, stream_));
-        if constexpr (screened) {
-            if (scr_flag_.p) HIPCHK(hipMemcpyAsync(&w->screen_overflow, scr_flag_.p, sizeof(int), hipMemcpyDeviceToHost, stream_));
-        }
-        HIPCHK(hipStreamSynchronize(stream_));
-        if (windows && dead_count_ < 0) dead_count_ = w->counters[CNT_DEAD];    // k_dead counted this block's dead triples in this call
-        return PBVI_OK;
-    }
-    int* ucount = counters_.as<int>() + CNT_UNIQUE;
-    int h_cnt[CNT_SLOTS] = {0, 0, 0, 0, 0, 0, 0, 0};      // all counters in the one read-back that precedes the final sync
-    auto later_stages = [&]() -> int {
-        bool publish = false;
-        // K4: action
-        double* rdot_err = rdot_.as<double>() + (size_t)B_ * A_;
-        HIPCHK(launch_action<TS>((int)B_, scorer.view(), sv, sc.rd_col0, sc.tol_rel, sc.chain, best_score_.as<double>(),
-                                 err_.as<double>(), rdot_.as<double>(), rdot_err, action_.as<int32_t>(),
-                                 windows ? aqueue_.as<int32_t>() : nullptr, aqcount, stream_, io.tol_extra,
-                                 windows ? acand_.as<uint8_t>() : nullptr, sc.split));
-        if (windows)
-            HIPCHK(launch_refine_action<T>(bel_.as<T>(), S_pad_, (int)B_, alpha_.as<T>(), S_pad_, mv, gamma,
-                                           btl_.as<int32_t>(), btc_.as<int32_t>(),
-                                           aqueue_.as<int32_t>(), aqcount, rdot_.as<double>(), rdot_err, best_v_.as<int32_t>(),
-                                           best_score_.as<double>(), err_.as<double>(), val_exact_.as<double>(),
-                                           action_.as<int32_t>(), stream_, acand_.as<uint8_t>()));
-        HIPCHK(hipEventRecord(ev_[5], stream_));
-        // results to the caller's belief order, then K6: dedup by (a*, v*) key
-        if (sorted_) {
-            int rc2;
-            if ((rc2 = action_res_.ensure((size_t)B_ * sizeof(int32_t)))) return rc2;
-            if ((rc2 = best_res_.ensure((size_t)pairs * sizeof(int32_t)))) return rc2;
-            hipLaunchKernelGGL(k_unpermute, dim3((unsigned)B_), dim3(64), 0, stream_, (int)B_, AO, perm, action_.as<int32_t>(),
-                               best_v_.as<int32_t>(), action_res_.as<int32_t>(), best_res_.as<int32_t>());
-            HIPCHK(hipGetLastError());
-            res_action_ = action_res_.as<int32_t>();
-            res_best_ = best_res_.as<int32_t>();
-        } else {
-            res_action_ = action_.as<int32_t>();
-            res_best_ = best_v_.as<int32_t>();
-        }
-        HIPCHK(launch_dedup((int)B_, A_, O_, res_action_, res_best_, rep_.as<int32_t>(), uniq_.as<int32_t>(),
-                            inv_.as<int32_t>(), slot_.as<int32_t>(), ucount, stream_));
-        // K3: alpha' rows of the unique keys only
-        HIPCHK(launch_assemble<T>(alpha_.as<T>(), S_pad_, mv, gamma, res_action_, res_best_, uniq_.as<int32_t>(), ucount,
-                                  (int)B_, out_.as<T>(), S_, stream_));
-        if (early_used_) {   // final keys against the provisional ones whose rows are on their way (or there) already
-            HIPCHK(hipStreamWaitEvent(stream_, ev_early_[1], 0));          // (the provisional count and rows are complete)
-            HIPCHK(hipMemsetAsync(e_cnt_.as<int>() + 1, 0, 2 * sizeof(int), stream_));
-            const int32_t* pa = sorted_ ? e_ares_.as<int32_t>() : e_act_.as<int32_t>();
-            const int32_t* pb = sorted_ ? e_bres_.as<int32_t>() : e_bv_.as<int32_t>();
-            hipLaunchKernelGGL(k_match_rows<T>, dim3((unsigned)std::min<int64_t>(B_, 2048)), dim3(256), 0, stream_, AO, O_, ucount,
-                               uniq_.as<int32_t>(), res_action_, res_best_, e_uniq_.as<int32_t>(), pa, pb, e_cnt_.as<int>(),
-                               (int)early_cap_, e_slot_.as<int32_t>(), out_.as<T>(), (T*)early_rows_, (int64_t)S_);
-            HIPCHK(hipGetLastError());
-            publish = rf_dst_.slot != nullptr && !(flags & PBVI_BELIEF_DOMINANCE) && rf_dst_.best == nullptr && rf_dst_.keep == nullptr &&
-                      is_pinned_host_pointer(rf_dst_.slot) && is_pinned_host_pointer(rf_dst_.index) &&
-                      is_pinned_host_pointer(rf_dst_.action);
-            if (!publish) HIPCHK(hipMemcpyAsync(words().early, e_cnt_.p, sizeof(words().early), hipMemcpyDeviceToHost, stream_));
-        }
-        HIPCHK(hipEventRecord(ev_[6], stream_));
-        if (xr_pending) {                            // the extra rows' maxima read the slabs K5's GEMM is about to overwrite
-            HIPCHK(hipStreamWaitEvent(stream_, ev_xr_[1], 0));
-            xr_pending = false;
-        }
-        // K5: belief dominance (keep is written in caller order)
-        if (flags & PBVI_BELIEF_DOMINANCE) {
-            int rc2;
-            if ((rc2 = value_max_device())) return rc2;
-            HIPCHK(launch_keep<T>(bel_.as<T>(), S_pad_, out_.as<T>(), S_, (int)B_, S_, bs2_.as<double>(), inv_.as<int32_t>(),
-                                  perm, keep_.as<uint8_t>(), stream_));
-        } else {
-            HIPCHK(hipMemsetAsync(keep_.p, 1, (size_t)B_, stream_));
-        }
-        rf_dst_.queued = false;
-        if (publish) {                                       // run_fetch into page-locked arrays: one kernel stores everything small
-            hipLaunchKernelGGL(k_publish, dim3((unsigned)((B_ + 255) / 256)), dim3(256), 0, stream_, (int)B_, e_slot_.as<int32_t>(),
-                               inv_.as<int32_t>(), res_action_, (int32_t*)rf_dst_.slot, (int32_t*)rf_dst_.index, (int32_t*)rf_dst_.action,
-                               counters_.as<int>(), e_cnt_.as<int>(), (screened && scr_flag_.p) ? scr_flag_.as<int>() : nullptr, &words());
-            HIPCHK(hipGetLastError());
-            rf_dst_.queued = true;
-            HIPCHK(hipEventRecord(ev_[7], stream_));
-            HIPCHK(hipStreamSynchronize(stream_));
-            std::memcpy(h_cnt, words().counters, sizeof(h_cnt));
-            return PBVI_OK;
-        }
-        if (early_used_ && rf_dst_.slot != nullptr) {        // run_fetch: slots, index, actions (best, keep) with this read-back
-            int rc2;
-            if ((rc2 = out_begin())) return rc2;
-            if ((rc2 = out_add(rf_dst_.slot, e_slot_.p, (size_t)B_ * sizeof(int32_t)))) return rc2;
-            if ((rc2 = out_add(rf_dst_.index, inv_.p, (size_t)B_ * sizeof(int32_t)))) return rc2;
-            if ((rc2 = out_add(rf_dst_.action, res_action_, (size_t)B_ * sizeof(int32_t)))) return rc2;
-            if (rf_dst_.best && (rc2 = out_add(rf_dst_.best, res_best_, (size_t)pairs * sizeof(int32_t)))) return rc2;
-            if (rf_dst_.keep && (rc2 = out_add(rf_dst_.keep, keep_.p, (size_t)B_))) return rc2;
-            rf_dst_.queued = true;
-        }
-        // (into the page-locked words: a copy into the stack array is staged by the runtime)
-        HIPCHK(hipMemcpyAsync(words().counters, counters_.p, sizeof(h_cnt), hipMemcpyDeviceToHost, stream_));
-        if constexpr (screened) {   // did an alpha value leave the fp32 range when the screen's copy was made?
-            if (scr_flag_.p) HIPCHK(hipMemcpyAsync(&words().screen_overflow, scr_flag_.p, sizeof(int), hipMemcpyDeviceToHost, stream_));
-        }
-        HIPCHK(hipEventRecord(ev_[7], stream_));
-        HIPCHK(hipStreamSynchronize(stream_));
-        std::memcpy(h_cnt, words().counters, sizeof(h_cnt));
-        return PBVI_OK;
-    };
-    if ((rc = rep_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
-    if ((rc = uniq_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
-    if ((rc = inv_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
-    if ((rc = slot_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
-    if ((rc = later_stages())) return rc;
-    if (speculate) {
-        last_deferred_nothing_ = rf_counts_[0] == 0 && rf_counts_[1] == 0;
-        if (!last_deferred_nothing_) {   // there was deferred work after all: do it, then the later stages again
-            HIPCHK(launch_refine_deferred<T>(true, (int)V_, AO, bel_.as<T>(), S_pad_, alpha_.as<T>(), S_pad_, mv, gamma,
-                                             best_v_.as<int32_t>(), best_score_.as<double>(), err_.as<double>(), work,
-                                             rf_counts_[0], rf_counts_[1], stream_));
-            HIPCHK(hipMemsetAsync(counters_.as<int>() + CNT_ACTION_QUEUE, 0, sizeof(int), stream_));
-            HIPCHK(hipMemsetAsync(counters_.as<int>() + CNT_UNIQUE, 0, sizeof(int), stream_));   // (value_max resets its own queue)
-            if ((rc = later_stages())) return rc;
-        }
-    }
-    if (windows && dead_count_ < 0) dead_count_ = h_cnt[CNT_DEAD];
-    full_valid_ = false;
-    res_sorted_ = sorted_;
-    have_result_ = true;
-    have_bk_vmax_ = use_push && !screened;
-    res_B_ = B_;
-    const int h_ucount = h_cnt[CNT_UNIQUE];
-    res_unique_ = h_ucount;
-
-    if (st) {
-        std::memset(st, 0, sizeof(*st));
-        auto el = [&](int i, int j) {
-            float t = 0.f;
-            (void)hipEventElapsedTime(&t, ev_[i], ev_[j]);
-            return (double)t;
-        };
-        st->ms_project = el(0, 1);
-        st->ms_score = el(1, 2);
-        st->ms_argmax = el(2, 3);
-        st->ms_refine = el(3, 4);
-        st->ms_action = el(4, 5);
-        st->ms_assemble = el(5, 6);
-        st->ms_dominance = el(6, 7);
-        st->ms_total = el(0, 7);
-        st->n_pairs = pairs;
-        const int* h = h_cnt;
-        st->n_refine_candidates = h[4];
-        st->n_refined = h[0];
-        st->n_refined_actions = h[1];
-        st->n_unique = h_ucount;
-        st->formulation = last_formulation_;
-        st->n_dead = windows ? dead_count_ : 0;              // counted by k_dead (when the block was first backed up)
-        if (mode_ == PBVI_DENSE) {
-            if (kF32) {
-                float t = 0.f;
-                (void)hipEventElapsedTime(&t, ev_pg_[0], ev_pg_[1]);
-                st->ms_project_gemm = (double)t;
-            }
-            st->project_flops = 2LL * AO * V_ * (int64_t)S_ * S_;
-            st->project_flops_executed = st->project_flops;
-            if (kF32) {
-                int64_t kt_sum = 0;
-                for (int64_t i = 0; i < dense_pairs_ && i < (int64_t)h_kcountD_.size(); ++i) kt_sum += h_kcountD_[(size_t)i];
-                st->project_flops_executed = kt_sum * 2LL * GEMM_BM * GEMM_BN * GEMM_BK;
-            }
-        }
-        st->score_flops = 2 * B_ * (int64_t)S_ * AO * V_;
-        if (windows) {
-            int64_t kt_sum = 0;
-            for (size_t i = 0; i < n_kcount; ++i) kt_sum += h_kcount[i];
-            st->score_flops_executed = kt_sum * 2LL * GEMM_BM * GEMM_BN * GEMM_BK;
-            st->score_tiles_dense = (int64_t)plan.tiles_m * plan.tiles_n * plan.k_tiles;
-            st->score_tiles_run = kt_sum;
-            st->split_k = plan.max_chunks;
-        } else if (f64_pairs > 0) {   // fp64 MFMA path: 128 x 128 tiles, lists in 32-column steps
-            int64_t kt_sum = 0;
-            for (size_t i = 0; i < n_kcount; ++i) kt_sum += h_kcount[i];
-            st->score_flops_executed = kt_sum * 2LL * 128 * gemm_f64_bn((int)std::min<int64_t>(use_push ? V_ : N, 0x7fffffff)) * 32;
-            st->score_tiles_dense = f64_pairs * (S_pad_ / GEMM_BK);
-            st->score_tiles_run = kt_sum;
-            st->split_k = 1;
-        } else {
-            st->score_flops_executed = st->score_flops;
-            st->split_k = 1;
-        }
-        st->screened = screened ? 1 : 0;
-        st->fused_projection = sc.fused ? 1 : 0;
-        st->score_split = sc.split;
-        st->gamma_chunks = sc.chunks;
-        if (sc.chunks > 1) {                                 // sums over the chunks; the folds count with the argmax
-            double fold = 0.0;
-            scorer.tile_times(ev_[0], &st->ms_project, &st->ms_score, &fold);
-            st->ms_argmax = fold + el(2, 3);
-        }
-    }
-    return PBVI_OK;
 }
 
 // --------------------------------------------------------------------------- //
