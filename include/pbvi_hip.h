@@ -728,6 +728,18 @@ int pbvi_debug_slabs_fill(pbvi_engine_t* e, int byte);
 int pbvi_debug_score_probe(pbvi_engine_t* e, int enable);
 int pbvi_debug_score_probe_fetch(pbvi_engine_t* e, int64_t* dims, double* scalars, double* score, double* mag, double* E,
                                  int32_t* best_v, double* best_score, int32_t* queue, uint8_t* dead, int32_t* perm);
+/*
+ * Tests only: the bookkeeping of the engine's most recent refinement pass (the fp64 re-decision of the near-tie queue
+ * of a backup, or of the value maxima of an fp32 engine), so that a test can tell which of its paths ran:
+ *   out[0]  candidates reserved on the item list                     (RefineWork::cnt[0]; uncapped: > out[3] = overflow)
+ *   out[1]  slots reserved for entries handed to the grid-wide passes (cnt[1]; uncapped: > out[4] = overflow)
+ *   out[2]  entries handed to k_refine_split by the level-1 screen    (cnt[2]; uncapped: > out[6] = overflow)
+ *   out[3]  item_cap, out[4] slot_cap, out[5] w_slot_cap (slots below it take the GEMM path), out[6] q2_cap,
+ *   out[7]  defer_min -- the capacities that pass ran with (all 0 with PBVI_REFINE_INBLOCK: no work list).
+ * One 12-byte copy from the counter buffer behind a synchronisation; nothing is recorded per call.  Valid until the
+ * next call that refines.  PBVI_EINVAL before the first such pass or once its work list has been released.
+ */
+int pbvi_debug_refine_counts(pbvi_engine_t* e, int64_t out[8]);
 
 /* Bytes of device memory currently held by the handle. */
 int64_t pbvi_device_bytes(const pbvi_engine_t* e);

@@ -1125,7 +1125,9 @@ __global__ void k_refine(SlabView<TS> sv, int V, int G, const int32_t* __restric
         }
         const int n1 = n1_sh;
         constexpr bool l1 = L1 && PROJ && sizeof(T) == 4;   // (two instantiations: each carries one of the two paths only)
-        if (n1 > 0 && n1 <= L1_CAP && (l1 || n1 <= FAST_CAP)) {
+        // (defer_min < 0, PBVI_REFINE_DEFER_MIN=-1: every candidate goes to the grid-wide passes, these few too)
+        const bool defer_all = work.items_v != nullptr && work.defer_min < 0;
+        if (!defer_all && n1 > 0 && n1 <= L1_CAP && (l1 || n1 <= FAST_CAP)) {
             if (tid == 0 && cand_total != nullptr) atomicAdd(cand_total, n1);
             const TileList tl{L, n_tiles};
             int n2 = n1;
@@ -1179,8 +1181,41 @@ __global__ void k_refine(SlabView<TS> sv, int V, int G, const int32_t* __restric
                         }
                         __syncthreads();
                         if (sh_slot >= 0) return;
-                        if (tid == 0) sh_slot = -1;           // (no room: scored here, as before)
-                        __syncthreads();
+                        // No room: scored here -- over the same REFINE_SPLIT parts of the tile list, the parts added in
+                        // k_refine_split's order, so that an entry's exact score has the same bits on either side of
+                        // the capacity.  (Which entries find room is a race; with one whole-list sum here, scores that
+                        // are equal -- those of duplicate actions -- differed in the last bit from entry to entry, and
+                        // k_action_final's first maximum went to the later action.)
+                        for (int c0 = 0; c0 < n2; c0 += 4) {
+                            const T* rows[4];
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) rows[j] = alpha + (int64_t)c1[c0 + j < n2 ? c0 + j : c0] * lda;
+                            double sum[4] = {0.0, 0.0, 0.0, 0.0};
+                            for (int part = 0; part < REFINE_SPLIT; ++part) {
+                                const int lo = (int)((int64_t)n_tiles * part / REFINE_SPLIT);
+                                const int hi = (int)((int64_t)n_tiles * (part + 1) / REFINE_SPLIT);
+                                const TileList pl{L + lo, hi - lo, lo};
+                                double d[4];
+                                exact_dots4<T, PROJ>(brow, rows, n2 - c0 < 4 ? n2 - c0 : 4, mv, a, o, gamma, pl, d, l1red);
+#pragma unroll
+                                for (int j = 0; j < 4; ++j) sum[j] += d[j];
+                            }
+                            if (tid == 0)
+                                for (int j = 0; j < 4 && c0 + j < n2; ++j) s1[c0 + j] = sum[j];
+                        }
+                        if (tid == 0) {                      // candidates ascend: first maximum
+                            double bv = s1[0];
+                            int bi = c1[0];
+                            for (int c = 1; c < n2; ++c)
+                                if (s1[c] > bv) {
+                                    bv = s1[c];
+                                    bi = c1[c];
+                                }
+                            best_v[e] = bi;
+                            best_score[e] = bv;
+                            err[e] = 0.0;
+                        }
+                        return;
                     }
                 }
             }

@@ -922,6 +922,7 @@ class EngineBase {
     virtual int64_t debug_slabs(void* out, int64_t cap_bytes) = 0;
     virtual int debug_slabs_fill(int byte) = 0;
     virtual int debug_score_probe(int enable) = 0;
+    virtual int debug_refine_counts(int64_t* out) = 0;
     virtual int debug_score_probe_fetch(int64_t* dims, double* scalars, double* score, double* mag, double* err,
                                         int32_t* best_v, double* best_score, int32_t* queue, uint8_t* dead, int32_t* perm) = 0;
     // source: the policy of the step loop (RolloutSource); alpha_actions and gamma are read by the sources that need them
@@ -1135,6 +1136,8 @@ class EngineT : public EngineBase {
     int64_t dead_pairs_ = 0, dead_count_ = 0;
     int* rf_counts_ = nullptr;                               // PinnedWords::deferred of the current backup
     bool last_deferred_nothing_ = false;                     // (the first backup of an engine reads the counts mid-pipeline)
+    RefineWork last_work_;                                   // the work list of the most recent refinement pass ...
+    bool have_last_work_ = false;                            // ... if there was one (pbvi_debug_refine_counts)
     bool owns_streams_ = true;                               // false: a screen running on its fp64 engine's streams
     EngineT<float>* screen_ = nullptr;                       // fp64 engines: the fp32 screen (see ensure_screen)
     std::vector<int32_t> h_reach_ref_;                       // fp64 engines: the tables in the reference's layout, kept
@@ -1986,6 +1989,32 @@ class EngineT : public EngineBase {
         return PBVI_OK;
     }
 
+    // The bookkeeping of the most recent refinement pass (pbvi_debug_refine_counts): the three words of RefineWork::cnt as
+    // that pass left them (uncapped) and the capacities it ran with.  A copy on request; nothing is kept per call but the
+    // RefineWork itself.
+    int debug_refine_counts(int64_t* out) override {
+        if (!out) FAIL(PBVI_EINVAL, "debug_refine_counts: out is NULL");
+        if (!have_last_work_) FAIL(PBVI_EINVAL, "debug_refine_counts: no refinement has run");
+        const RefineWork& w = last_work_;
+        int cnt[3] = {0, 0, 0};
+        if (w.cnt != nullptr) {                              // (nullptr: PBVI_REFINE_INBLOCK, no work list at all)
+            if (rf_cnt_.p == nullptr || w.cnt != rf_cnt_.as<int>())
+                FAIL(PBVI_EINVAL, "debug_refine_counts: the work list of that pass has been released");
+            HIPCHK(hipSetDevice(device_));
+            HIPCHK(hipStreamSynchronize(stream_));
+            HIPCHK(hipMemcpy(cnt, w.cnt, sizeof(cnt), hipMemcpyDeviceToHost));
+        }
+        out[0] = cnt[0];
+        out[1] = cnt[1];
+        out[2] = cnt[2];
+        out[3] = w.item_cap;
+        out[4] = w.slot_cap;
+        out[5] = w.w_slot_cap;
+        out[6] = w.q2_cap;
+        out[7] = w.defer_min;
+        return PBVI_OK;
+    }
+
     // ---- test-only score probe (pbvi_debug_score_probe / _fetch) ---- //
     static uint64_t next_probe_seq() {
         static std::atomic<uint64_t> seq{0};
@@ -2345,6 +2374,7 @@ class EngineT : public EngineBase {
         mat_V_ = -1;
         gam_pad_ptr_ = nullptr;
         last_deferred_nothing_ = false;
+        have_last_work_ = false;                             // (its lists were working buffers)
         probe_seq_ = 0;                                      // (the capture's buffers were working buffers)
         ++alpha_ver_;
         ++bel_ver_;
@@ -2781,6 +2811,8 @@ class EngineT : public EngineBase {
         // through that one before the counts are read, and out_add may reset or reallocate it
         rf_counts_ = words().deferred;
         rf_counts_[0] = rf_counts_[1] = 0;
+        last_work_ = work;                                       // (pbvi_debug_refine_counts)
+        have_last_work_ = true;
         static const bool no_spec = getenv("PBVI_NO_SPECULATION") != nullptr;      // debug / A-B only
         // (not with the belief-dominance test: its own value-max refinement re-uses the work-list buffers, so the
         // deferred entries of this one have to be finished first)
@@ -3850,6 +3882,8 @@ int EngineT<T>::value_max_device() {
         if ((rc = ensure_belief_tiles())) return rc;   // tile lists of the resident block (the backup's k_dead builds them too)
         RefineWork work;
         if ((rc = refine_work(B_, V_, &work))) return rc;
+        last_work_ = work;                                       // (pbvi_debug_refine_counts)
+        have_last_work_ = true;
         HIPCHK(launch_refine<T>(false, sv, (int)V_, 1, (int)B_, queue2_.as<int32_t>(), qc, bel_.as<T>(), S_pad_,
                                 alpha_.as<T>(), S_pad_, view(), 0.0, btl_.as<int32_t>(), btc_.as<int32_t>(), nullptr,
                                 bv2_.as<int32_t>(), bs2_.as<double>(), err2_.as<double>(), nullptr, work, stream_));
@@ -4762,6 +4796,10 @@ int pbvi_debug_slabs_fill(pbvi_engine_t* e, int byte) {
 int pbvi_debug_score_probe(pbvi_engine_t* e, int enable) {
     NEED(e);
     return e->impl->debug_score_probe(enable);
+}
+int pbvi_debug_refine_counts(pbvi_engine_t* e, int64_t out[8]) {
+    NEED(e);
+    return e->impl->debug_refine_counts(out);
 }
 int pbvi_debug_score_probe_fetch(pbvi_engine_t* e, int64_t* dims, double* scalars, double* score, double* mag, double* err,
                                  int32_t* best_v, double* best_score, int32_t* queue, uint8_t* dead, int32_t* perm) {

@@ -37,7 +37,7 @@ EXPORTS = [
     'pbvi_set_gamma_tiling', 'pbvi_gamma_tiling_plan', 'pbvi_q_values', 'pbvi_prune_dominated_masked',
     'pbvi_rollout', 'pbvi_infotaxis', 'pbvi_rollout_infotaxis', 'pbvi_debug_split_schedule', 'pbvi_debug_slabs',
     'pbvi_debug_slabs_fill', 'pbvi_env_set_frames', 'pbvi_env_set_table', 'pbvi_env_clear', 'pbvi_rollout_env',
-    'pbvi_debug_score_probe', 'pbvi_debug_score_probe_fetch',
+    'pbvi_debug_score_probe', 'pbvi_debug_score_probe_fetch', 'pbvi_debug_refine_counts',
 ]
 
 
@@ -102,6 +102,7 @@ def load_library(path: str = LIB_PATH):
         'pbvi_debug_slabs_fill': (C.c_int, [vp, C.c_int]),
         'pbvi_debug_score_probe': (C.c_int, [vp, C.c_int]),
         'pbvi_debug_score_probe_fetch': (C.c_int, [vp] + [vp] * 10),
+        'pbvi_debug_refine_counts': (C.c_int, [vp, vp]),
         'pbvi_backup_store_unique': (C.c_int64, [vp, i32p, C.c_int64]),
         'pbvi_backup_device_results': (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
         'pbvi_backup': (C.c_int, [vp, vp, C.c_int64, C.c_double, C.c_int, vp, i32p, i32p, u8p, sp]),
@@ -1356,6 +1357,16 @@ class Engine:
         out.update(qcount=qc, split=int(scal[0]), chain_steps=int(scal[1]), tol_rel=float(scal[2]), tol_extra=float(scal[3]),
                    push=int(dims[4]), f64_pairs=int(dims[5]), f64_split=int(dims[6]), chunks=int(dims[7]))
         return out
+
+    def debug_refine_counts(self) -> dict:
+        """Tests only: the bookkeeping of the most recent refinement pass (``pbvi_debug_refine_counts``): ``items``,
+        ``slots`` and ``q2`` as the pass reserved them (uncapped: more than the capacity means the overflow path ran) and
+        the capacities ``item_cap``, ``slot_cap``, ``w_slot_cap``, ``q2_cap``, ``defer_min`` it ran with.  Valid until
+        the next call that refines."""
+        out = np.zeros(8, dtype=np.int64)
+        self._ck(self._lib.pbvi_debug_refine_counts(self._h, _ptr(out)))
+        names = ('items', 'slots', 'q2', 'item_cap', 'slot_cap', 'w_slot_cap', 'q2_cap', 'defer_min')
+        return {k: int(v) for k, v in zip(names, out)}
 
     def set_gamma_tiling(self, mode: str = 'off', chunk_rows: int = 0) -> None:
         """Alpha-side backups whose Gamma is projected into HBM (R > 1, fp64 scoring, unfused R = 1): walk the alpha set in
