@@ -940,6 +940,15 @@ class EngineBase {
                             int32_t* out_steps, uint8_t* out_lost) = 0;
 };
 
+// Order of a score-probe capture among the captures of ALL engines of the process.  One counter, not one per element type:
+// an fp64 engine compares its own captures with its fp32 screen's (debug_score_probe_fetch), and a counter kept as a static
+// of the class template would be two counters -- the screen's ahead by every capture of every other fp32 engine, so that
+// an older capture of the screen was handed out for a newer one of the engine itself.
+inline uint64_t next_probe_seq() {
+    static std::atomic<uint64_t> seq{0};
+    return ++seq;
+}
+
 template <typename T>
 class EngineT : public EngineBase {
    public:
@@ -2016,10 +2025,6 @@ class EngineT : public EngineBase {
     }
 
     // ---- test-only score probe (pbvi_debug_score_probe / _fetch) ---- //
-    static uint64_t next_probe_seq() {
-        static std::atomic<uint64_t> seq{0};
-        return ++seq;
-    }
     void probe_release() {
         for (DevBuf* b : {&probe_score_, &probe_mag_, &probe_err_, &probe_bv_, &probe_bs_, &probe_queue_, &probe_dead_, &probe_words_})
             b->release();
@@ -2511,7 +2516,8 @@ class EngineT : public EngineBase {
     // scores of X rows (default: the resident belief block) against the rows of Y
     int score_gemm(const T* Y, int64_t rows_y, const uint8_t* nzB, int G, int v_group, SlabView<T>* sv,
                    const T* X = nullptr, int64_t x_rows = 0, const uint8_t* nzX = nullptr, hipStream_t list_stream = nullptr,
-                   const FusedB* fused = nullptr, int* split = nullptr /* in: wanted, out: done (scheduler 2d) */);
+                   const FusedB* fused = nullptr, int* split = nullptr /* in: wanted, out: done (scheduler 2d) */,
+                   int f64_route = -1 /* fp64 scoring: -1 by this GEMM's shape, 0 the plain kernel, n the MFMA tiles in n K parts */);
 
     int project_dense(double gamma);   // K1-dense: Gamma = gamma * alpha . D_ao^T as A*O (batched) GEMMs
     int backup_run(double gamma, int flags, pbvi_stats_t* st) override;
@@ -3731,7 +3737,7 @@ class EngineT : public EngineBase {
 template <typename T>
 int EngineT<T>::score_gemm(const T* Y, int64_t rows_y, const uint8_t* nzB, int G, int v_group, SlabView<T>* sv,
                            const T* X, int64_t x_rows, const uint8_t* nzX, hipStream_t list_stream, const FusedB* fused,
-                           int* split) {
+                           int* split, int f64_route) {
     int rc;
     const int64_t m_rows = X ? x_rows : B_;
     const int64_t m_pad = X ? round_up(x_rows, GEMM_BM) : B_pad_;
@@ -3769,12 +3775,13 @@ int EngineT<T>::score_gemm(const T* Y, int64_t rows_y, const uint8_t* nzB, int G
         sv->first_block = plan_.streamk ? skws_.as<int>() + (pairs + 1) + plan_.nblocks : nullptr;
     } else {
         const int kt32s = S_pad_ / GEMM_BK;
-        const int split = f64_uses_mfma(m_rows, rows_y) ? gemm_f64_split((int)m_rows, (int)rows_y, kt32s) : 1;
+        const bool mfma = f64_route < 0 ? f64_uses_mfma(m_rows, rows_y) : f64_route > 0;
+        const int split = !mfma ? 1 : f64_route > 0 ? f64_route : gemm_f64_split((int)m_rows, (int)rows_y, kt32s);
         if ((rc = slabs_.ensure((size_t)split * m_rows * rows_y * sizeof(T)))) return rc;
         slab_bytes_ = (int64_t)split * m_rows * rows_y * (int64_t)sizeof(T);
         f64_pairs_ = 0;
         f64_split_ = split;
-        if (!f64_uses_mfma(m_rows, rows_y)) {
+        if (!mfma) {
             HIPCHK(launch_gemm_nt_simple<T>(X, S_pad_, Y, S_pad_, slabs_.as<T>(), (int)rows_y, (int)m_rows, (int)rows_y,
                                             S_, stream_));
         } else {
@@ -4047,7 +4054,10 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
         const int64_t rows_held = compact ? (int64_t)n_mat_ * GEMM_BN : n_rows_alloc;
         if ((rc = gam_.ensure((size_t)rows_held * S_pad_ * sizeof(T)))) return rc;
         // zero the Gamma pad rows the GEMM tiles read -- once per (buffer, row count, layout): nothing writes rows >= N,
-        // and the fill of up to 255 rows (27 MB, 39 us at |S| = 30000) sat in front of every backup's score GEMM
+        // and the fill of up to 255 rows (27 MB, 39 us at |S| = 30000) sat in front of every backup's score GEMM.
+        // (Defensive: the pad rows become score columns >= N, which neither k_argmax nor k_fold_chunk reads; a build
+        // without the row count in the key answered every sequence of tests/test_engine_sequences.py alike.  The key keeps
+        // the rows finite and zero for a reader that may come.)
         if (n_rows_alloc > N && (gam_pad_ptr_ != gam_.p || gam_pad_N_ != N || gam_pad_compact_ != compact || mode_ == PBVI_DENSE)) {
             // (the pad rows are the end of the last tile, which is always a projected one: contiguous in either layout)
             const int64_t first = compact ? (int64_t)(n_mat_ - 1) * GEMM_BN + (N - (n_rows_alloc - GEMM_BN)) : N;
@@ -4212,6 +4222,12 @@ int EngineT<T>::stage_scores_tiled(double gamma, const ScoreIO& io, int want_spl
         const int sp = f64_uses_mfma(B_, n_big) ? gemm_f64_split((int)B_, (int)n_big, k_tiles) : 1;
         if ((rc = ensure_exact(slabs_, (size_t)sp * B_ * n_big * sizeof(T)))) return rc;
     }
+    // fp64 scoring has no tie window: copies of an alpha row get equal bits because every column is summed in one order,
+    // and the first of them wins.  Left to its own shape, a ragged last chunk may be small enough for the plain kernel, or
+    // for another K split, than the chunks before it; a copy behind that seam then differs in its last bits and can win.
+    // So the route of the largest chunk is the route of every chunk of the call.
+    const bool f64_mfma = !kF32 && f64_uses_mfma(B_, n_big);
+    const int f64_route = kF32 ? -1 : f64_mfma ? gemm_f64_split((int)B_, (int)n_big, k_tiles) : 0;
     if ((rc = need_.ensure((size_t)AO * k_tiles))) return rc;
     if ((rc = chain_max_.ensure(sizeof(int)))) return rc;
     HIPCHK(hipMemsetAsync(chain_max_.p, 0, sizeof(int), stream_));
@@ -4236,7 +4252,7 @@ int EngineT<T>::stage_scores_tiled(double gamma, const ScoreIO& io, int want_spl
             gam_pad_compact_ = false;
         }
         const uint8_t* need = nullptr;
-        if (kF32 || f64_uses_mfma(B_, n_c)) {
+        if (kF32 || f64_mfma) {
             HIPCHK(launch_need_tiles(nzA_.as<uint8_t>(), (int)(B_pad_ / GEMM_BM), nzB_.as<uint8_t>(), AO, (int)vc, k_tiles,
                                      need_.as<uint8_t>(), stream_));
             need = need_.as<uint8_t>();
@@ -4249,7 +4265,8 @@ int EngineT<T>::stage_scores_tiled(double gamma, const ScoreIO& io, int want_spl
         // (tile lists and stream-K plan on the main stream: the list buffers are the previous chunk's GEMM's)
         SlabView<T> sv;
         int split = want_split;
-        if ((rc = score_gemm(gam_.as<T>(), n_c, nzB_.as<uint8_t>(), AO, (int)vc, &sv, nullptr, 0, nullptr, nullptr, nullptr, &split)))
+        if ((rc = score_gemm(gam_.as<T>(), n_c, nzB_.as<uint8_t>(), AO, (int)vc, &sv, nullptr, 0, nullptr, nullptr, nullptr, &split,
+                             f64_route)))
             return rc;
         if (io.stats) HIPCHK(hipEventRecord(tile_ev_[(size_t)3 * c + 1], stream_));
         if (c > 0 && split != out->split) FAIL(PBVI_ERUNTIME, "gamma tiling: the chunks' GEMMs disagree about the operand split");

@@ -1,0 +1,1919 @@
+"""Sequences of engine calls, their shadow state and their references (no tests here, no GPU needed).
+
+The invariant ``tests/test_engine_sequences.py`` states: what a call of an ``Engine`` returns is a function of the engine's
+LOGICAL state -- tables, working alpha set, belief block, row stores, switches -- and not of the calls that produced that
+state.  This module holds everything of that test that is plain Python:
+
+* two small models (``model('G')``, ``model('I')``) from the generators of ``test_score_window.py`` / ``model_cases.py``;
+* seeded recipes for alpha sets (exact duplicates, ~100 exact ties per triple, near-duplicates) and belief blocks;
+* ``Shadow``: the logical state as NumPy arrays in the engine's precision;
+* the operations (a name and a dict of arguments) and ``Runner``, which applies a list of them to an engine and to the
+  shadow, and after every query compares the engine with (a) the fp64 host statements evaluated on the shadow and (b) a
+  fresh engine brought to the shadow's state by ``set_alpha`` / ``set_beliefs``;
+* ``HostEngine``: a NumPy stand-in with ``Engine``'s method names built on the oracle and the ``*_numpy`` statements, and
+  five subclasses with one planted carry-over bug each;
+* the scripted sequences (literal lists), the seeded generator and the coverage accounting.
+
+Index comparisons follow the rule of the issue: an entry is compared where fp64 can decide it -- the runner-up is an
+identical row (the lowest index is expected) or lies further than 2^-40 x ``ref_magnitude`` below the maximum -- and the
+share of undecided entries of a query may not exceed 0.5 % (the committed sequences have none).
+"""
+import functools
+import hashlib
+from types import SimpleNamespace
+
+import numpy as np
+
+import model_cases as mc
+import test_score_window as sw
+from oracle import pbvi_oracle as orc
+from pomdp_pbvi_exploration_amd import pomdp as P
+from pomdp_pbvi_exploration_amd.mdp import _row_hash
+
+GAMMA = sw.GAMMA
+TOL = {'f64': 1e-12, 'f32': 1e-6}                      # rows, value maxima, q (fuzz_engine.py, test_q_values.py)
+UPDATE_RTOL = {'f64': 1e-12, 'f32': 2e-6}              # Bayes step (test_bayes_step.py)
+UPDATE_ATOL = 1e-12
+WALK_TOL = {'f64': 1e-13, 'f32': 1e-6}
+BELIEF_TOL = {'f64': 1e-10, 'f32': 1e-5}               # rollout survivors (test_device_rollout.py)
+DECIDE = 2.0 ** -40
+MAX_SKIP_SHARE = 0.005
+B_EDGES = (1, 3, 128, 129, 256, 257, 300)
+V_EDGES = (1, 5, 255, 256, 257, 600)
+MODELS = ('G', 'I')
+DTYPES = ('f32', 'f64')
+N_SEEDS = 8
+N_RANDOM_OPS = 30
+MAX_SIMS = 64
+
+f32r = sw.f32r
+
+
+# --------------------------------------------------------------------------------------------------------------------- #
+# models and data recipes
+# --------------------------------------------------------------------------------------------------------------------- #
+@functools.lru_cache(maxsize=None)
+def model(name):
+    """G: S = 1000, A = O = 2, R = 1, consecutive successors (``test_score_window``'s ``fused1`` variant: fused projection and
+    the split GEMM are legal).  I: S = 333, A = O = R = 3, random successors, sparse RTO with one all-zero (a, o) group.
+    Tables rounded to fp32, so both engine types hold exactly these numbers."""
+    rng = np.random.default_rng(sw.seed_of('sequences', name))
+    if name == 'G':
+        S, A, O, R = 1000, 2, 2, 1
+        rs, rto = sw.successors(rng, S, A, R, True), sw.sparse_rto(rng, S, A, O, R)
+    else:
+        S, A, O, R = 333, 3, 3, 3
+        rs, rto = sw.successors(rng, S, A, R, False), sw.sparse_rto(rng, S, A, O, R)
+        rto[:, 1, 1, :] = 0.0                                    # (a, o) = (1, 1) never happens: dead for every belief
+        rto /= rto.sum(axis=(2, 3), keepdims=True)
+    rto, er = f32r(rto), f32r(rng.normal(size=(S, A)))
+    ends = [7, S // 2]
+    tables = SimpleNamespace(state_count=S, action_count=A, observation_count=O, reachable_state_count=R,
+                             reachable_states=rs, reachable_transitional_observation_table=rto, expected_rewards_table=er,
+                             end_states=ends)
+    end_mask = np.zeros(S, dtype=np.uint8)
+    end_mask[ends] = 1
+    return SimpleNamespace(name=name, S=S, A=A, O=O, R=R, rs=rs, rto=rto, er=er, tables=tables, end_mask=end_mask,
+                           obs_prob=mc._observation_table(rng, S, A, O))
+
+
+def alpha_rows(mname, V, seed, ties=0, near=0, scale=4.0, huge=False):
+    """[V,S] fp32-representable rows.  Every set of at least 4 rows holds exact duplicates (first-max goes to the lowest
+    index; the refinement runs); ``ties``: that many copies of one row that is the maximum of every triple; ``near``: pairs
+    that differ by ~1e-6 relative (decidable in fp64, inside an fp32 tie window); ``huge`` (fp64 engines): the last row
+    holds a value beyond FLT_MAX at one state of the upper half and is -100 elsewhere, so it never wins."""
+    S = model(mname).S
+    rng = np.random.default_rng([int(seed), int(V), 17])
+    a = rng.normal(scale=scale, size=(V, S))
+    if V >= 4:
+        a[V - 1] = a[1]
+        a[V // 2] = a[0]
+    if V >= 12:
+        a[rng.integers(3, V - 1, 3)] = a[2]
+    for i in range(min(near, max(0, (V - 4) // 2))):
+        a[V - 2 - i] = a[3 + i] * (1.0 + 1e-6 * (1.0 + np.abs(rng.normal(size=S))))      # (no entry rounds back to equal)
+    if ties and V >= 8:
+        dom = 12.0 * scale + rng.normal(size=S)
+        a[rng.choice(V, size=min(ties, V // 2), replace=False)] = dom
+    a = f32r(a)
+    if huge:
+        a[V - 1] = -100.0
+        a[V - 1, (3 * S) // 4] = 1e39
+    return a
+
+
+def alpha_labels(rows, A):
+    """Action label of an alpha row, a function of its content (exact duplicates share it)."""
+    return (np.floor(np.abs(np.asarray(rows)[:, 0]) * 997.0).astype(np.int64) + 1) % A
+
+
+def belief_rows(mname, B, seed, win=None, onehot=False):
+    """[B,S] fp32-representable rows with exact zeros; ``win = (lo, hi)`` as fractions of S: no mass outside ``[lo S, hi S)``;
+    ``onehot``: every seventh row is one state only (dead triples where the model gives that state no (a, o))."""
+    S = model(mname).S
+    rng = np.random.default_rng([int(seed), int(B), 29])
+    lo, hi = (0, S) if win is None else (int(win[0] * S), max(int(win[0] * S) + 1, int(win[1] * S)))
+    b = np.zeros((B, S))
+    b[:, lo:hi] = mc.sparse_beliefs(rng, B, hi - lo, density=(0.05, 0.3, 1.0)[int(seed) % 3])
+    if onehot:
+        one = np.arange(B) % 7 == 3
+        b[one] = 0.0
+        b[one, rng.integers(lo, hi, int(one.sum()))] = 1.0
+    return f32r(b)
+
+
+def digest(*arrays):
+    h = hashlib.blake2b(digest_size=16)
+    for a in arrays:
+        a = np.ascontiguousarray(a)
+        h.update(str(a.shape).encode())
+        h.update(a.tobytes())
+    return h.hexdigest()
+
+
+# --------------------------------------------------------------------------------------------------------------------- #
+# reference (a): the host statements in fp64, memoised on the content of their inputs
+# --------------------------------------------------------------------------------------------------------------------- #
+_MEMO = {}
+
+
+def memo(fn):
+    @functools.wraps(fn)
+    def wrapped(mname, *arrays, **kw):
+        key = (fn.__name__, mname, digest(*arrays), tuple(sorted(kw.items())))
+        if key not in _MEMO:
+            if len(_MEMO) > 256:
+                _MEMO.clear()
+            _MEMO[key] = fn(mname, *arrays, **kw)
+        return _MEMO[key]
+    return wrapped
+
+
+def canon_index(alpha):
+    """[V]: the lowest index of a row with the same bytes."""
+    first, out = {}, np.empty(alpha.shape[0], dtype=np.int64)
+    for v, row in enumerate(alpha):
+        out[v] = first.setdefault(row.tobytes(), v)
+    return out
+
+
+def decide_first_max(scores, mag, canon):
+    """``(index, decided)`` over the last axis of ``scores``: the candidates are the entries within 2^-40 x mag of the
+    maximum; decided where they are all copies of one row (index: the lowest of them) or where mag == 0 (a dead row: 0)."""
+    V = scores.shape[-1]
+    top = scores.max(axis=-1)
+    cand = scores >= (top - DECIDE * mag)[..., None]
+    lo = np.where(cand, canon, V).min(axis=-1)
+    hi = np.where(cand, canon, -1).max(axis=-1)
+    dead = mag == 0
+    return np.where(dead, 0, lo), (lo == hi) | dead, top
+
+
+@memo
+def backup_ref(mname, alpha, bel, tol=1e-12):
+    """``orc.backup_core`` / ``orc.belief_dominance_mask`` with the decidability of every choice, the keys and the dedup."""
+    m = model(mname)
+    B, A, O = bel.shape[0], m.A, m.O
+    g = orc.gamma_projection(alpha, m.rs, m.rto, GAMMA)                              # A,O,V,S
+    sc = np.tensordot(bel, g, (1, 3))                                                # B,A,O,V
+    mag = sw.ref_magnitude(alpha, bel, m.rs, m.rto, GAMMA).reshape(B, A, O)
+    best, decided, top = decide_first_max(sc, mag, canon_index(alpha))
+    picked = g[np.arange(A)[None, :, None], np.arange(O)[None, None, :], best]       # B,A,O,S
+    alpha_a = m.er.T[None] + picked.sum(axis=2)                                      # B,A,S
+    val = np.einsum('bas,bs->ba', alpha_a, bel)
+    act = np.argmax(val, axis=1)
+    scale = np.abs(val).max(axis=1) + mag.sum(axis=2).max(axis=1)
+    if A > 1:
+        srt = np.sort(val, axis=1)
+        act_ok = (srt[:, -1] - srt[:, -2]) > DECIDE * scale
+    else:
+        act_ok = np.ones(B, dtype=bool)
+    rows = alpha_a[np.arange(B), act]
+    new_v = val[np.arange(B), act]
+    old_v = (bel @ alpha.T).max(axis=1)
+    keep = new_v > old_v
+    # an engine's row carries its own rounding (`tol` relative to the terms of the dot): nearer than that, fp64 cannot say
+    # on which side the engine's own row lies
+    keep_ok = np.abs(new_v - old_v) > 4.0 * tol * (scale + np.abs(old_v))
+    keys = np.concatenate([act[:, None], best[np.arange(B), act]], axis=1)           # B,1+O
+    seen, index, firsts = {}, np.empty(B, dtype=np.int64), []
+    for b in range(B):
+        k = keys[b].tobytes()
+        if k not in seen:
+            seen[k] = len(firsts)
+            firsts.append(b)
+        index[b] = seen[k]
+    firsts = np.array(firsts, dtype=np.int64)
+    q = bel @ m.er + top.sum(axis=2)
+    return SimpleNamespace(best=best, decided=decided, act=act, row_ok=decided.all(axis=(1, 2)) & act_ok, rows=rows, keep=keep,
+                           keep_ok=keep_ok, keys=keys[firsts], index=index, urows=rows[firsts], q=q, mag=mag, g=g, sc=sc, top=top)
+
+
+@memo
+def vmax_ref(mname, alpha, bel):
+    sc = bel @ alpha.T
+    mag = np.abs(bel) @ np.abs(alpha).max(axis=0)
+    idx, ok, top = decide_first_max(sc, mag, canon_index(alpha))
+    return SimpleNamespace(val=top, idx=idx, ok=ok, sc=sc)
+
+
+@memo
+def prune_ref(mname, alpha):
+    return orc.prune_dominated_mask(alpha)
+
+
+@memo
+def infotaxis_ref(mname, bel, f32=False):
+    m = model(mname)
+    G, Z, H, MG, MH = P._infotaxis_terms(m.tables, bel, np.float32 if f32 else np.float64)
+    return SimpleNamespace(G=G, act=P.infotaxis_first_argmin(G), bound=np.maximum(8.0 * m.S * 2.0 ** -53 * MG, 1e-15))
+
+
+def update_ref(m, bel, acts, obs):
+    return np.stack([orc.belief_update(bel[i], int(acts[i]), int(obs[i]), m.rs, m.rto) for i in range(bel.shape[0])])
+
+
+def possible_steps(m, bel, rng):
+    """A random action per row and the lowest observation it can be followed by."""
+    acts = rng.integers(0, m.A, bel.shape[0])
+    obs = np.array([mc.first_possible_observation(bel[i], acts[i], m.rs, m.rto)[0] for i in range(bel.shape[0])])
+    assert obs.min() >= 0
+    return acts.astype(np.int64), obs.astype(np.int64)
+
+
+def walk_plan(m, b0, n, rng):
+    """``(actions, observations, rows)`` of an n-step chain of ``orc.belief_update`` from ``b0``, every step possible."""
+    acts, obs, rows, b = [], [], [], b0
+    for _ in range(n):
+        a = int(rng.integers(0, m.A))
+        o, nb = mc.first_possible_observation(b, a, m.rs, m.rto)
+        assert o >= 0
+        acts.append(a), obs.append(o), rows.append(nb)
+        b = nb
+    return np.array(acts), np.array(obs), np.stack(rows)
+
+
+# --------------------------------------------------------------------------------------------------------------------- #
+# shadow state
+# --------------------------------------------------------------------------------------------------------------------- #
+SWITCH_DEFAULTS = {'formulation': 'auto', 'f64_screen': 'auto', 'fused_projection': 1, 'score_split': 'auto',
+                   'gamma_tiling': ('off', 0), 'tie_window': -1.0, 'value_max_exact': True, 'score_probe': False}
+SWITCH_VALUES = {'formulation': ('auto', 'alpha', 'belief'), 'f64_screen': ('auto', 'off', 'always'),
+                 'fused_projection': (0, 1, 2), 'score_split': ('off', 'auto', 'always'),
+                 'gamma_tiling': (('off', 0), ('always', 100), ('always', 256), ('always', 64)),
+                 'tie_window': (-1.0, 1e-3), 'value_max_exact': (True, False), 'score_probe': (False, True)}
+
+
+def apply_switch(eng, name, value):
+    if name == 'formulation':
+        eng.set_formulation(value)
+    elif name == 'f64_screen':
+        eng.set_f64_screen(value)
+    elif name == 'fused_projection':
+        eng.set_fused_projection(value)
+    elif name == 'score_split':
+        eng.set_score_split(value)
+    elif name == 'gamma_tiling':
+        eng.set_gamma_tiling(value[0], value[1])
+    elif name == 'tie_window':
+        eng.set_tie_window(value)
+    elif name == 'value_max_exact':
+        eng.set_value_max_exact(value)
+    elif name == 'score_probe':
+        eng.debug_score_probe(value)
+    else:
+        raise KeyError(name)
+
+
+class Shadow:
+    """The engine's logical state.  Arrays are float64 holding values of the engine's precision; ``None`` = nothing
+    resident.  ``prim_ids`` / ``prim_free`` restate the bookkeeping of ``store_select``'s three branches, only to name the
+    form a selection takes (coverage accounting); nothing compared depends on them."""
+
+    def __init__(self, mname, dtype):
+        self.mname, self.dtype = mname, dtype
+        self.switches = dict(SWITCH_DEFAULTS)
+        self.empty()
+
+    def empty(self):
+        self.alpha = self.alpha_ids = None
+        self.bel = self.bel_ids = None
+        self.astore, self.bstore = [], []
+        self.result = None                      # None, or the belief-dominance flag of the fetchable backup
+        self.prim_ids, self.prim_free = None, 0
+
+    @property
+    def V(self):
+        return 0 if self.alpha is None else self.alpha.shape[0]
+
+    @property
+    def B(self):
+        return 0 if self.bel is None else self.bel.shape[0]
+
+    def put_alpha(self, rows, ids=None):
+        self.alpha, self.alpha_ids, self.result = np.ascontiguousarray(rows, dtype=np.float64), ids, None
+        if ids is None:                          # an uploaded set: the primary layout is given up
+            self.prim_ids = None
+
+    def put_beliefs(self, rows, ids=None):
+        self.bel = None if rows is None or len(rows) == 0 else np.ascontiguousarray(rows, dtype=np.float64)
+        self.bel_ids, self.result = ids, None
+
+    def select_form(self, ids):
+        """The branch of ``store_select`` these ids take: 'extend' / 'primary' (k = 0) / 'small' / 'fresh' ('exhaust': an
+        extension that found too few free rows and started a fresh layout)."""
+        ids = [int(i) for i in ids]
+        n, pv = len(ids), None if self.prim_ids is None else len(self.prim_ids)
+        if pv is not None and n >= pv and ids[n - pv:] == self.prim_ids:
+            if n - pv <= self.prim_free:
+                self.prim_free -= n - pv
+                self.prim_ids = ids
+                return 'extend' if n > pv else 'primary'
+            form = 'exhaust'
+        elif pv is not None and n <= 4096 and 4 * n <= pv:
+            return 'small'
+        else:
+            form = 'fresh'
+        self.prim_ids, self.prim_free = ids, max(512, n // 2)
+        return form
+
+
+# --------------------------------------------------------------------------------------------------------------------- #
+# operations
+# --------------------------------------------------------------------------------------------------------------------- #
+ALPHA_MUTATIONS = ('set_alpha', 'append_alpha', 'store_alpha', 'extend_alpha', 'select_alpha', 'store_unique', 'reset_alpha_store')
+BELIEF_MUTATIONS = ('set_beliefs', 'store_beliefs', 'select_beliefs', 'advance_beliefs', 'belief_walk', 'rollout',
+                    'rollout_infotaxis', 'rollout_env', 'reset_belief_store_append')
+RESETS = ('after_oom', 'oom_call')
+MUTATIONS = ALPHA_MUTATIONS + BELIEF_MUTATIONS + RESETS
+QUERIES = ('run_fetch', 'run_prune_fetch', 'run_fetch_into', 'fetch_compact_into', 'keys_assemble', 'row_hashes', 'q_values',
+           'vmax_resident', 'vmax_store', 'infotaxis', 'fetch_beliefs', 'prune_dominated', 'prune_masked', 'belief_update',
+           'fetch_refused')
+HARNESS = ('remember', 'same_as')
+# calls of the Python layer that answer AND move the working sets (counted, but outside the mutation -> query pairs)
+COMPOUND = ('vmax_objects', 'clear_environment')
+VOCABULARY = MUTATIONS + ('switch',) + QUERIES + COMPOUND
+VALUE_QUERIES = tuple(q for q in QUERIES if q != 'fetch_refused')
+BACKUPS = ('run_fetch', 'run_prune_fetch', 'run_fetch_into', 'q_values')
+
+
+def legal(name, args, sh):
+    """Whether the operation can run in the shadow's state."""
+    V, B, res = sh.V, sh.B, sh.result is not None
+    if name in ('run_fetch', 'run_prune_fetch', 'run_fetch_into', 'q_values', 'vmax_resident'):
+        return V > 0 and B > 0
+    if name in ('fetch_compact_into', 'keys_assemble', 'row_hashes', 'store_unique'):
+        return res
+    if name == 'fetch_refused':
+        return not res
+    if name == 'vmax_store':
+        return V > 0 and len(sh.bstore) > 0
+    if name in ('infotaxis', 'fetch_beliefs', 'belief_update', 'advance_beliefs'):
+        return B > 0
+    if name in ('prune_dominated', 'prune_masked', 'append_alpha'):
+        return V > 0
+    if name == 'extend_alpha':
+        return sh.alpha_ids is not None
+    if name == 'select_alpha':
+        how = args['how']
+        if how == 'primary':
+            return sh.prim_ids is not None and all(i < len(sh.astore) for i in sh.prim_ids)
+        if how == 'small':
+            return sh.prim_ids is not None and len(sh.prim_ids) >= 4 and len(sh.astore) > 0
+        return len(sh.astore) > 0
+    if name == 'select_beliefs':
+        return len(sh.bstore) > 0 and (args['how'] != 'same' or sh.bel_ids is not None)
+    if name in ('rollout', 'rollout_env'):
+        needs_alpha = name == 'rollout' or args.get('policy', 0) != 2
+        return 0 < B <= MAX_SIMS and (V > 0 or not needs_alpha)
+    if name == 'rollout_infotaxis':
+        return 0 < B <= MAX_SIMS
+    if name == 'reset_belief_store_append':
+        return len(sh.bstore) > 0
+    return True
+
+
+class Mismatch(AssertionError):
+    pass
+
+
+class Runner:
+    """Applies operations to ``eng`` and to the shadow; after every query compares with the host statements (a) and with
+    a fresh engine from ``make_engine()`` (b).  ``alloc(shape, dtype)`` gives the arrays ``run_fetch_into`` writes (page-locked
+    for a device engine); ``provoke_oom(eng)`` makes one call of ``eng`` fail with ``MemoryError``."""
+
+    def __init__(self, mname, dtype, make_engine, alloc=None, provoke_oom=None):
+        self.m, self.mname, self.dtype = model(mname), mname, dtype
+        self.f32 = dtype == 'f32'
+        self.npdt = np.float32 if self.f32 else np.float64
+        self.make_engine, self.alloc = make_engine, alloc or (lambda shape, dt: np.empty(shape, dtype=dt))
+        self.provoke_oom = provoke_oom
+        self.sh = Shadow(mname, dtype)
+        self.eng = make_engine()
+        self.entries = self.skipped = 0
+        self.vmax_bits = []                     # per value-max query: equal to the fresh engine's bit for bit?
+        self.score_bits = []                    # per probed backup: best_score equal to the fresh engine's bit for bit?
+        self.score_ratio = 0.0                  # largest |best_score - reference| / bar seen
+        self.objs, self.envs = None, {}         # AlphaVector / Belief stand-ins and environment holders that live on
+        self.forms, self.last, self.kept, self.where = [], None, {}, ''
+
+    def close(self):
+        self.eng.close()
+
+    def cast(self, x):
+        return f32r(x) if self.f32 else np.asarray(x, dtype=np.float64)
+
+    # -- running --------------------------------------------------------------------------------------------------- #
+    def run(self, ops):
+        for i, (name, args) in enumerate(ops):
+            self.where = f'op {i} {name} {args}'
+            if name not in HARNESS and not legal(name, args, self.sh):
+                raise Mismatch(f'{self.where}: not legal in the shadow\'s state')
+            try:
+                getattr(self, 'op_' + name)(**args)
+            except ValueError as e:                           # an argument error of the engine: say where
+                raise ValueError(f'{self.where}: {e}') from e
+        return self
+
+    def fail(self, what):
+        raise Mismatch(f'{self.where}: {what}')
+
+    def same(self, got, want, what):
+        got, want = np.asarray(got), np.asarray(want)
+        if got.shape != want.shape or not np.array_equal(got, want):
+            n = int(np.sum(got != want)) if got.shape == want.shape else -1
+            self.fail(f'{what}: {n} entries differ (shapes {got.shape}, {want.shape})')
+
+    def close_to(self, got, want, rtol, atol, what):
+        got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+        if got.shape != want.shape:
+            self.fail(f'{what}: shapes {got.shape}, {want.shape}')
+        err = np.abs(got - want) - (atol + rtol * np.abs(want))
+        if got.size and not np.all(err <= 0):                   # (a NaN fails)
+            self.fail(f'{what}: off by up to {np.nanmax(np.abs(got - want)):.3e} (rtol {rtol:g}, atol {np.max(atol):.3e})')
+
+    def rows_close(self, got, want, what):
+        """The bar of ``fuzz_engine.py``: rtol = tol, atol = tol x the largest |entry| of the reference rows."""
+        tol = TOL[self.dtype]
+        self.close_to(got, want, tol, tol * (np.abs(want).max() + 1e-30) if np.size(want) else 0.0, what)
+
+    def count(self, ok, what):
+        """Book the undecided entries of an index comparison; more than 0.5 % of them fails."""
+        ok = np.asarray(ok)
+        self.entries += ok.size
+        self.skipped += int(ok.size - np.count_nonzero(ok))
+        if ok.size and (ok.size - np.count_nonzero(ok)) > MAX_SKIP_SHARE * ok.size:
+            self.fail(f'{what}: {ok.size - np.count_nonzero(ok)} of {ok.size} entries undecidable in fp64')
+
+    def fresh(self, with_store=False, run_flag=None):
+        """A new engine in the shadow's state by the shortest route."""
+        sh, e = self.sh, self.make_engine()
+        for k, v in sh.switches.items():
+            if v != SWITCH_DEFAULTS[k]:
+                apply_switch(e, k, v)
+        if sh.alpha is not None:
+            e.set_alpha(sh.alpha.astype(self.npdt))
+        if with_store and sh.bstore:
+            e.store_rows('belief', np.stack(sh.bstore).astype(self.npdt))
+        if sh.bel is not None:
+            e.set_beliefs(sh.bel.astype(self.npdt))
+        if run_flag is not None:
+            e.run(GAMMA, run_flag)
+        return e
+
+    def both(self, call, with_store=False, run_flag=None):
+        """``call(engine)`` on the engine under test and on a fresh one, which is closed afterwards."""
+        got = call(self.eng)
+        f = self.fresh(with_store, run_flag)
+        try:
+            want = call(f)
+        finally:
+            f.close()
+        return got, want
+
+    def done(self, **outputs):
+        self.last = {k: np.array(v) for k, v in outputs.items()}
+
+    # -- harness ---------------------------------------------------------------------------------------------------- #
+    def op_remember(self, tag):
+        self.kept[tag] = self.last
+
+    def op_same_as(self, tag):
+        for k, v in self.kept[tag].items():
+            self.same(self.last[k], v, f'{k} against the call remembered as {tag!r}')
+
+    # -- switches and resets ---------------------------------------------------------------------------------------- #
+    def op_switch(self, name, value):
+        value = tuple(value) if isinstance(value, list) else value
+        apply_switch(self.eng, name, value)
+        self.sh.switches[name] = value
+
+    def op_after_oom(self):
+        self.eng.after_oom()
+        self.sh.empty()
+
+    def op_oom_call(self):
+        if self.provoke_oom is None:
+            self.eng.debug_fail_next_call()
+            try:
+                self.eng.store_rows('alpha', np.zeros((1, self.m.S)))
+            except MemoryError:
+                pass
+            else:
+                self.fail('no MemoryError')
+        else:
+            self.provoke_oom(self.eng)
+        if self.eng.alpha_count != 0 or self.eng.B != 0:
+            self.fail('the failed call left a working set behind')
+        self.eng.after_oom()
+        self.sh.empty()
+
+    # -- alpha set -------------------------------------------------------------------------------------------------- #
+    def op_set_alpha(self, **recipe):
+        rows = alpha_rows(self.mname, **recipe)
+        self.eng.set_alpha(rows.astype(self.npdt))
+        self.sh.put_alpha(rows)
+
+    def op_append_alpha(self, **recipe):
+        rows = alpha_rows(self.mname, **recipe)
+        self.eng.append_alpha(rows.astype(self.npdt))
+        self.sh.put_alpha(np.concatenate([self.sh.alpha, rows]))
+
+    def _store_alpha(self, rows):
+        first = self.eng.store_rows('alpha', rows.astype(self.npdt))
+        if first != len(self.sh.astore):
+            self.fail(f'store_rows returned id {first}, the store holds {len(self.sh.astore)} rows')
+        self.sh.astore.extend(rows)
+        return np.arange(first, first + len(rows))
+
+    def _select_alpha(self, ids):
+        ids = np.asarray(ids, dtype=np.int64)
+        self.forms.append(self.sh.select_form(ids))
+        self.eng.select_alpha(ids)
+        self.sh.put_alpha(np.stack([self.sh.astore[i] for i in ids]), ids)
+
+    def op_store_alpha(self, **recipe):
+        self._store_alpha(alpha_rows(self.mname, **recipe))
+
+    def op_extend_alpha(self, **recipe):
+        old = self.sh.alpha_ids
+        self._select_alpha(np.concatenate([self._store_alpha(alpha_rows(self.mname, **recipe)), old]))
+
+    def op_select_alpha(self, how, seed=0):
+        sh, rng = self.sh, np.random.default_rng([int(seed), 41])
+        n = len(sh.astore)
+        if how == 'primary':
+            ids = np.array(sh.prim_ids)
+        elif how == 'small':
+            ids = rng.integers(0, n, max(1, min(len(sh.prim_ids) // 4, 4096, 40)))
+        elif how == 'all':
+            ids = np.arange(n)[::-1]
+        else:
+            ids = rng.permutation(n)[:max(1, (n + 1) // 2)]
+        self._select_alpha(ids)
+
+    def op_store_unique(self):
+        sh = self.sh
+        res = self.eng.fetch()
+        want = backup_ref(self.mname, sh.alpha, sh.bel, tol=TOL[self.dtype])
+        if want.row_ok.all():
+            self.rows_close(res.unique_alpha, want.urows, 'unique rows handed to the store')
+        U = res.unique_alpha.shape[0]
+        first = self.eng.store_unique(np.arange(U))
+        if first != len(sh.astore):
+            self.fail(f'store_unique returned id {first}, the store holds {len(sh.astore)} rows')
+        sh.astore.extend(np.asarray(res.unique_alpha, dtype=np.float64))        # the engine's own rows become state
+        new = np.arange(first, first + U)
+        self._select_alpha(new if sh.alpha_ids is None else np.concatenate([new, sh.alpha_ids]))
+
+    def op_reset_alpha_store(self):
+        self.eng.reset_store('alpha')
+        self.sh.astore, self.sh.alpha_ids, self.sh.prim_ids = [], None, None
+
+    # -- belief block ----------------------------------------------------------------------------------------------- #
+    def op_set_beliefs(self, **recipe):
+        rows = belief_rows(self.mname, **recipe)
+        self.eng.set_beliefs(rows.astype(self.npdt))
+        self.sh.put_beliefs(rows)
+
+    def _store_beliefs(self, rows):
+        first = self.eng.store_rows('belief', rows.astype(self.npdt))
+        if first != len(self.sh.bstore):
+            self.fail(f'store_rows returned id {first}, the store holds {len(self.sh.bstore)} rows')
+        self.sh.bstore.extend(rows)
+
+    def op_store_beliefs(self, **recipe):
+        self._store_beliefs(belief_rows(self.mname, **recipe))
+
+    def op_select_beliefs(self, how, B=0, seed=0):
+        sh, n = self.sh, len(self.sh.bstore)
+        if how == 'same':
+            ids = sh.bel_ids
+        elif how == 'last':
+            ids = np.arange(max(0, n - B), n)
+        else:
+            ids = np.random.default_rng([int(seed), 43]).permutation(n)[:min(B, n)]
+        self.eng.select_beliefs(ids)
+        sh.put_beliefs(np.stack([sh.bstore[i] for i in ids]), np.array(ids))
+
+    def op_reset_belief_store_append(self, **recipe):
+        n = len(self.sh.bstore)
+        self.eng.reset_store('belief')
+        self.sh.bstore, self.sh.bel_ids = [], None
+        self._store_beliefs(belief_rows(self.mname, B=n, **recipe))
+
+    def _adopt_block(self, want, rtol, atol, what):
+        """The resident block is the engine's own output: check it at the bar, then take its bits into the shadow."""
+        if self.eng.B != want.shape[0]:
+            self.fail(f'{what}: {self.eng.B} rows resident, the host statement has {want.shape[0]}')
+        if want.shape[0] == 0:
+            self.sh.put_beliefs(None)
+            return
+        got = self.eng.fetch_beliefs()
+        self.close_to(got, want, rtol, atol, what)
+        self.sh.put_beliefs(np.asarray(got, dtype=np.float64))
+
+    def op_advance_beliefs(self, keep, seed):
+        sh, rng = self.sh, np.random.default_rng([int(seed), 47])
+        acts, obs = possible_steps(self.m, sh.bel, rng)
+        mask = None
+        if keep:
+            mask = rng.random(sh.B) < 0.7
+            mask[int(rng.integers(0, sh.B))] = True
+        want = update_ref(self.m, sh.bel, acts, obs)
+        args = (acts, obs, None if mask is None else mask.astype(np.uint8))
+        nb, nb_fresh = self.both(lambda e: e.advance_beliefs(*args))
+        self.same(nb, nb_fresh, 'rows left by advance_beliefs')
+        self._adopt_block(want if mask is None else want[mask], UPDATE_RTOL[self.dtype], UPDATE_ATOL, 'advanced beliefs')
+
+    def op_belief_walk(self, n, seed):
+        sh, rng = self.sh, np.random.default_rng([int(seed), 53])
+        b0 = belief_rows(self.mname, 1, seed)[0]
+        b0 = b0 / b0.sum()
+        acts, obs, want = walk_plan(self.m, b0, n, rng)
+        rows, first = self.eng.belief_walk(b0, acts, obs)
+        if first != len(sh.bstore):
+            self.fail(f'belief_walk returned id {first}, the store holds {len(sh.bstore)} rows')
+        tol = WALK_TOL[self.dtype]
+        self.close_to(rows, want, tol, tol * 1e-3, 'rows of the walk')
+        sh.bstore.extend(np.asarray(rows).astype(self.npdt).astype(np.float64))  # the store holds them in the engine's type
+
+    def _rollout(self, call, values, what, observe=None):
+        """A device rollout as mutation and query: trajectories byte for byte against a fresh engine in the state before
+        it, and against the host's step loop (``pomdp._rollout_loop``, the loop of the three ``rollout_*_numpy`` statements).
+        ``values(b) -> ([n,A] larger is better, [n] margin)``: where the host's best two actions lie nearer than the margin
+        (the engine's own rounding), fp64 cannot decide the step: the recorded action is taken, provided it is worth the
+        host's maximum within the margin.  The survivors are checked at the bar and adopted."""
+        sh, m = self.sh, self.m
+        seed, first_id, T, s0 = self._ro
+        got, fresh = self.both(call)
+        names = ('states', 'actions', 'observations', 'steps', 'lost')[:len(got)]
+        for k, name in enumerate(names):
+            self.same(got[k], fresh[k], f'{what} {name} against the fresh engine')
+        dev_actions, block, step = got[1], P._HostBeliefBlock(m.tables, None, sh.bel.copy()), [0]
+
+        def choose():
+            t = step[0]
+            step[0] += 1
+            vals, margin = values(block.b)
+            alive = np.flatnonzero(dev_actions[t] >= 0)
+            if alive.size != vals.shape[0]:
+                self.fail(f'{what}: {alive.size} simulations run at step {t}, the host statement has {vals.shape[0]}')
+            dev, best = dev_actions[t, alive].astype(np.int64), np.argmax(vals, axis=1)
+            if m.A == 1:
+                return best
+            srt = np.sort(vals, axis=1)
+            unsure = (srt[:, -1] - srt[:, -2]) <= margin
+            worth = vals[np.arange(len(dev)), np.clip(dev, 0, m.A - 1)] >= srt[:, -1] - margin
+            if not np.all(worth[unsure]):
+                self.fail(f'{what}: an action recorded at step {t} is not worth the host maximum')
+            return np.where(unsure, dev, best)
+
+        td = np.float32 if self.f32 else np.float64
+        want = P._rollout_loop(m.tables, block, choose, s0.astype(np.int64), seed, first_id, T, td, True, observe)
+        for k, name in enumerate(names[:4]):
+            self.same(got[k], want[k], f'{what} {name} against the host statement')
+        if observe is not None:
+            self.same(got[4], want[5], f'{what} lost against the host statement')
+        tol = BELIEF_TOL[self.dtype]
+        self._adopt_block(want[4], tol, tol, f'survivors of {what}')
+        self.done(**{f'out{k}': v for k, v in enumerate(got)})
+
+    def _starts(self, seed):
+        """True start states inside each belief's support (an observation the belief rules out has no Bayes step)."""
+        rng = np.random.default_rng([int(seed), 59])
+        w = (self.sh.bel > 0) & (self.m.end_mask == 0)[None, :]
+        w[~w.any(axis=1), 0] = True
+        return np.array([int(rng.choice(np.flatnonzero(row))) for row in w])
+
+    def _policy_values(self, policy, acts):
+        """``values`` of ``_rollout`` for policy 0 (value-max through the labels), 1 (Q) and 2 (infotaxis)."""
+        sh, m, tol = self.sh, self.m, TOL[self.dtype]
+        if policy == 2:
+            def values(b):
+                G, _, _, MG, _ = P._infotaxis_terms(m.tables, b, np.float32 if self.f32 else np.float64)
+                return -G, tol * MG.max(axis=1) + 1e-15
+        elif policy == 1:
+            def values(b):
+                q = P._q_values_numpy(m.tables, b, sh.alpha, GAMMA)
+                return q, tol * np.abs(q).max(axis=1)
+        else:
+            amax = np.abs(sh.alpha).max(axis=0)
+
+            def values(b):
+                sc = b @ sh.alpha.T
+                per = np.stack([np.where(acts == a, sc, -np.inf).max(axis=1) for a in range(m.A)], axis=1)
+                return per, tol * (np.abs(b) @ amax)
+        return values
+
+    def op_rollout(self, T, seed, lookahead=0):
+        sh, m = self.sh, self.m
+        acts, s0 = alpha_labels(sh.alpha, m.A), self._starts(seed)
+        self._ro = (seed, 1000 * seed, T, s0)
+        self._rollout(lambda e: e.rollout(acts, s0, m.end_mask, seed, T, first_sim_id=1000 * seed, lookahead=lookahead, gamma=GAMMA),
+                      self._policy_values(lookahead, acts), 'rollout')
+
+    def op_rollout_infotaxis(self, T, seed):
+        m, s0 = self.m, self._starts(seed)
+        self._ro = (seed, 1000 * seed, T, s0)
+        self._rollout(lambda e: e.rollout_infotaxis(s0, m.end_mask, seed, T, first_sim_id=1000 * seed),
+                      self._policy_values(2, None), 'rollout_infotaxis')
+
+    def _env(self, env, env_seed):
+        """The environment holder (pomdp.TableEnvironment / FrameEnvironment) of a kind and seed; one object per runner, so
+        that ``hold_environment`` meets the same holder again."""
+        if (env, env_seed) not in self.envs:
+            m = self.m
+            table = m.obs_prob if env_seed == 0 else mc._observation_table(np.random.default_rng([int(env_seed), 71]), m.S, m.A, m.O)
+            self.envs[env, env_seed] = P.TableEnvironment(table) if env == 'table' else \
+                P.FrameEnvironment(P.record_frames(table, 8, int(env_seed)), np.arange(m.A))
+        return self.envs[env, env_seed]
+
+    def op_rollout_env(self, T, seed, policy=0, env='table', env_seed=0, hold=False):
+        sh, m, s0 = self.sh, self.m, self._starts(seed)
+        acts = None if sh.alpha is None else alpha_labels(sh.alpha, m.A)
+        self._ro = (seed, 1000 * seed, T, s0)
+        holder = self._env(env, env_seed)
+
+        def call(e):
+            if hold:
+                e.hold_environment(holder)
+            elif env == 'table':
+                e.set_environment_table(holder.obs_prob)
+            else:
+                e.set_environment_frames(holder.frames, holder.channel_of_action)
+            return e.rollout_env(policy, acts, s0, m.end_mask, seed, T, first_sim_id=1000 * seed, gamma=GAMMA)
+
+        def observe(t, rows, ids, a, sn, done):              # (rollout_env_numpy's hook, shifts = 0, no end observation)
+            if env == 'table':
+                return P.rollout_draw(holder.obs_prob[sn, a], P.rollout_uniform(seed, ids, (1 << 32) + t))
+            return holder.frames[t, holder.channel_of_action[a], sn].astype(np.int64)
+        self._rollout(call, self._policy_values(policy, acts), 'rollout_env', observe)
+
+    def op_clear_environment(self):
+        self.eng.clear_environment()
+
+    # -- the Python layer's own memory: row ids on objects, cached value maxima ----------------------------------------------- #
+    def op_vmax_objects(self, V=12, B=40, seed=1, keep=False, grow=0):
+        """``Engine.max_value_objects`` over lists of objects that carry their store ids (``_dev``, tagged with engine and
+        store epoch) -- new lists, or (``keep``) the lists of the call before, whose tags and cached maxima may by now
+        belong to a store that was reset; ``grow``: that many new alpha objects in front (the cache's subset route).
+        Which selections the call leaves behind depends on what it found cached, so the harness selects the objects'
+        rows afterwards: the logical state is defined again."""
+        sh = self.sh
+        mk = lambda rows: [SimpleNamespace(values=r.astype(self.npdt)) for r in rows]
+        if not keep or self.objs is None:
+            self.objs = (mk(alpha_rows(self.mname, V, seed)), mk(belief_rows(self.mname, B, seed)))
+        if grow:
+            self.objs = (mk(alpha_rows(self.mname, grow, seed + 500, scale=8.0)) + self.objs[0], self.objs[1])
+        aobj, bobj = self.objs
+        val_of = lambda o: o.values
+        A64, B64 = (np.stack([o.values for o in lst]).astype(np.float64) for lst in (aobj, bobj))
+        vals = self.eng.max_value_objects(aobj, bobj, val_of, val_of)
+        f = self.fresh()
+        try:
+            fvals = f.max_value_objects(mk(A64), mk(B64), val_of, val_of)
+        finally:
+            f.close()
+        tol = TOL[self.dtype]
+        self.close_to(vals, vmax_ref(self.mname, A64, B64).val, tol, 0.0, 'max_value_objects against the host statement')
+        self.close_to(vals, fvals, tol, 0.0, 'max_value_objects against the fresh engine')
+        self.vmax_bits.append(bool(np.array_equal(vals, fvals)))
+        ids = {}
+        for which, objs, rows, store in (('alpha', aobj, A64, sh.astore), ('belief', bobj, B64, sh.bstore)):
+            tag = self.eng.store_tag(which)
+            if any(o._dev[0] != tag for o in objs):
+                self.fail(f'max_value_objects left a {which} object with the tag of another engine or store epoch')
+            ids[which] = np.array([o._dev[1] for o in objs], dtype=np.int64)
+            for i in np.argsort(ids[which], kind='stable'):
+                k = int(ids[which][i])
+                if k == len(store):
+                    store.append(rows[i])                     # uploaded by this call
+                elif k > len(store) or not np.array_equal(store[k], rows[i]):
+                    self.fail(f'max_value_objects: {which} id {k} does not name the object\'s row in the store')
+        self._select_alpha(ids['alpha'])
+        self.eng.select_beliefs(ids['belief'])
+        sh.put_beliefs(B64, ids['belief'])
+        self.done(val=vals)
+
+    # -- queries ---------------------------------------------------------------------------------------------------- #
+    def _check_backup(self, got, prune, what):
+        """A BackupResult-like namespace against ``backup_ref``."""
+        sh = self.sh
+        want = backup_ref(self.mname, sh.alpha, sh.bel, tol=TOL[self.dtype])
+        self.count(want.decided, f'{what} best_alpha_ind')
+        self.count(want.row_ok, f'{what} actions')
+        if not np.array_equal(got.best[want.decided], want.best[want.decided]):
+            self.fail(f'{what}: {int(np.sum(got.best[want.decided] != want.best[want.decided]))} indices differ from the host statement')
+        ok = want.row_ok
+        self.same(got.actions[ok], want.act[ok], f'{what} actions against the host statement')
+        self.rows_close(np.asarray(got.rows)[ok], want.rows[ok], f'{what} rows against the host statement')
+        if ok.all():
+            self.same(got.index, want.index, f'{what} index against the host statement')
+        if prune:
+            kok = ok & want.keep_ok
+            # (not booked as skipped: new_v == old_v is where a solve converges to, not a flaw of the inputs)
+            self.same(got.keep[kok], want.keep[kok], f'{what} keep against the host statement')
+        elif got.keep is not None and not np.all(got.keep):
+            self.fail(f'{what}: keep mask not all true without the belief-dominance prune')
+
+    def _compare_results(self, got, want, what):
+        for f in ('best', 'actions', 'index', 'keep', 'unique'):
+            if getattr(got, f) is not None:
+                self.same(getattr(got, f), getattr(want, f), f'{what} {f} against the fresh engine')
+
+    @staticmethod
+    def _result(res):
+        return SimpleNamespace(best=res.best_alpha_ind, actions=res.actions, index=res.index, keep=res.keep,
+                               unique=res.unique_alpha, rows=res.unique_alpha[res.index])
+
+    def _run_fetch(self, prune):
+        probed = self.sh.switches['score_probe']
+
+        def call(e):
+            e.run(GAMMA, prune)
+            res = self._result(e.fetch())
+            res.probe = self._probe(e) if probed else None
+            return res
+        got, fresh = self.both(call)
+        self.sh.result = prune
+        self._check_backup(got, prune, 'run + fetch')
+        self._compare_results(got, fresh, 'run + fetch')
+        if probed:
+            self._check_probe(got.probe, fresh.probe)
+        self.done(best=got.best, actions=got.actions, index=got.index, keep=got.keep, unique=got.unique)
+
+    def _probe(self, e):
+        """The score probe's first maxima in caller order: what the argmax saw before any refinement."""
+        p = e.debug_score_probe_fetch()
+        perm = np.asarray(p['perm'], dtype=np.int64)
+        B, G = p['best_score'].shape
+        queued = np.zeros(B * G, dtype=bool)
+        queued[np.asarray(p['queue'], dtype=np.int64)] = True
+        out = SimpleNamespace(split=int(p['split']), screened=p['tol_extra'] > 0.0)
+        for name, arr in (('best_score', p['best_score']), ('best_v', p['best_v']), ('E', p['E']), ('queued', queued.reshape(B, G))):
+            caller = np.empty_like(arr)
+            caller[perm] = arr
+            setattr(out, name, caller)
+        return out
+
+    def _check_probe(self, got, fresh):
+        """best_score against the reference's maxima at the bar of the arithmetic that scored -- 1e-12 of the magnitude
+        for fp64 scores, 1e-6 for fp32 scores (fp32 engines, and the fp32 screen of an fp64 engine, whose decisions the
+        fp64 refinement finishes); the split bf16 GEMM's scores are only promised inside its own window E (3.1 2^-16 of the
+        magnitude; tests/test_score_window.py holds E to its formula), so there the bar is E.  First maxima that
+        the argmax did not queue for refinement are final: compared where fp64 can decide them."""
+        sh = self.sh
+        want = backup_ref(self.mname, sh.alpha, sh.bel, tol=TOL[self.dtype])
+        shape = got.best_score.shape
+        top, mag = want.top.reshape(shape), want.mag.reshape(shape)
+        tol = 1e-12 if (not self.f32 and not got.screened) else 1e-6
+        bar = np.maximum(tol * mag, got.E if got.split else 0.0)
+        err = np.abs(got.best_score - top)
+        live = bar > 0
+        if live.any():
+            self.score_ratio = max(self.score_ratio, float((err[live] / bar[live]).max()))
+        if not np.all(err <= bar):
+            self.fail(f'best_score off by up to {self.score_ratio:.3f} bars (bar {tol:g} of the magnitude)')
+        if not np.all(np.abs(got.best_score - fresh.best_score) <= bar):
+            self.fail('best_score differs from the fresh engine\'s by more than the bar')
+        self.score_bits.append(bool(np.array_equal(got.best_score, fresh.best_score)))
+        final = want.decided.reshape(shape) & ~got.queued
+        self.same(got.best_v[final], want.best.reshape(shape)[final], 'probe best_v (not queued) against the host statement')
+
+    def op_run_fetch(self):
+        self._run_fetch(False)
+
+    def op_run_prune_fetch(self):
+        self._run_fetch(True)
+
+    def _compact(self, e, run_first):
+        B, m = self.sh.B, self.m
+        rows = self.alloc((B, m.S), self.npdt)
+        index, actions = np.empty(B, np.int32), np.empty(B, np.int32)
+        best, keep = np.empty((B, m.A, m.O), np.int32), np.empty(B, np.uint8)
+        if run_first:
+            slot = np.empty(B, np.int32)
+            _, U, used = e.run_fetch_into(GAMMA, rows, slot, index, actions, best, keep)
+            if not (0 < U <= used <= B) or slot[:U].min() < 0 or slot[:U].max() >= B or len(set(slot[:U].tolist())) != U:
+                self.fail(f'run_fetch_into: U {U}, slots used {used}, slots {slot[:U]}')
+            unique = np.array(rows[slot[:U]])
+        else:
+            U = e.fetch_compact_into(rows, index, actions, best, keep)
+            unique = np.array(rows[:U])
+        if index.min() < 0 or index.max() >= U:
+            self.fail(f'index outside [0, {U})')
+        return SimpleNamespace(best=best.astype(np.int64), actions=actions.astype(np.int64), index=index.astype(np.int64),
+                               keep=keep.astype(bool), unique=unique, rows=unique[index])
+
+    def op_run_fetch_into(self):
+        got, fresh = self.both(lambda e: self._compact(e, True))
+        self.sh.result = False
+        self._check_backup(got, False, 'run_fetch_into')
+        self._compare_results(got, fresh, 'run_fetch_into')
+        self.done(best=got.best, actions=got.actions, index=got.index, keep=got.keep, unique=got.unique)
+
+    def op_fetch_compact_into(self):
+        prune = self.sh.result
+        got, fresh = self.both(lambda e: self._compact(e, False), run_flag=prune)
+        self._check_backup(got, prune, 'fetch_compact_into')
+        self._compare_results(got, fresh, 'fetch_compact_into')
+        self.done(best=got.best, actions=got.actions, index=got.index, keep=got.keep, unique=got.unique)
+
+    def op_keys_assemble(self):
+        sh = self.sh
+
+        def call(e):
+            keys = e.fetch_unique_keys()
+            return keys, e.assemble_rows(keys, GAMMA)
+        (keys, rows), (fkeys, frows) = self.both(call, run_flag=sh.result)
+        self.same(keys, fkeys, 'unique keys against the fresh engine')
+        self.same(rows, frows, 'assembled rows against the fresh engine')
+        want = backup_ref(self.mname, sh.alpha, sh.bel, tol=TOL[self.dtype])
+        self.count(want.row_ok, 'unique keys')
+        if want.row_ok.all():
+            self.same(keys, want.keys, 'unique keys against the host statement')
+            self.rows_close(rows, want.urows, 'assembled rows against the host statement')
+        self.done(keys=keys, rows=rows)
+
+    def op_row_hashes(self):
+        def call(e):
+            return e.fetch_row_hashes(), e.fetch().unique_alpha
+        (h, rows), (fh, _) = self.both(call, run_flag=self.sh.result)
+        self.same(h, fh, 'row hashes against the fresh engine')
+        self.same(h, np.array([_row_hash(r) for r in rows], dtype=np.uint64), 'row hashes against the host hash of the rows')
+        self.done(hashes=h)
+
+    def op_fetch_refused(self):
+        try:
+            self.eng.fetch()
+        except ValueError:
+            self.done()
+            return
+        self.fail('fetch answered although no backup result is resident')
+
+    def op_q_values(self):
+        sh, tol = self.sh, TOL[self.dtype]
+        (q, act, best), (fq, fact, fbest) = self.both(lambda e: e.q_values_resident(GAMMA, want_best=True))
+        sh.result = None                                                          # (q_values overwrites the stage buffers)
+        for g, f, name in ((q, fq, 'q'), (act, fact, 'q actions'), (best, fbest, 'q best_alpha_ind')):
+            self.same(g, f, f'{name} against the fresh engine')
+        want = backup_ref(self.mname, sh.alpha, sh.bel, tol=tol)
+        err = np.abs(q - want.q).max(axis=1) / np.maximum(np.abs(want.q).max(axis=1), 1e-300)
+        if not np.all(err <= tol):
+            self.fail(f'q off by {err.max():.3e} of the row\'s largest |Q| (bar {tol:g})')
+        self.count(want.decided, 'q best_alpha_ind')
+        self.same(best[want.decided], want.best[want.decided], 'q best_alpha_ind against the host statement')
+        srt = np.sort(want.q, axis=1)
+        ok = (srt[:, -1] - srt[:, -2]) > tol * np.abs(want.q).max(axis=1) if self.m.A > 1 else np.ones(sh.B, dtype=bool)
+        self.count(ok, 'q actions')
+        self.same(act[ok], np.argmax(want.q, axis=1)[ok], 'q actions against the host statement')
+        self.done(q=q, act=act, best=best)
+
+    def _check_vmax(self, got, fresh, bel, what):
+        (val, idx), (fval, fidx) = got, fresh
+        tol, exact = TOL[self.dtype], self.sh.switches['value_max_exact'] or not self.f32
+        want = vmax_ref(self.mname, self.sh.alpha, bel)
+        self.close_to(val, want.val, tol, 0.0, f'{what} values against the host statement')
+        self.close_to(val, fval, tol, 0.0, f'{what} values against the fresh engine')
+        self.vmax_bits.append(bool(np.array_equal(val, fval)))
+        if exact:
+            self.count(want.ok, f'{what} indices')
+            self.same(np.asarray(idx)[want.ok], want.idx[want.ok], f'{what} indices against the host statement')
+            self.same(idx, fidx, f'{what} indices against the fresh engine')
+        else:                                       # fp32 maxima as they are: the index is a maximiser within the bar
+            self.close_to(want.sc[np.arange(len(idx)), idx], want.val, tol, 0.0, f'{what}: score of the returned index')
+        self.done(val=val, idx=idx)
+
+    def op_vmax_resident(self):
+        got, fresh = self.both(lambda e: e.max_value_resident())
+        self._check_vmax(got, fresh, self.sh.bel, 'max_value_resident')
+
+    def op_vmax_store(self):
+        got, fresh = self.both(lambda e: e.max_value_store(), with_store=True)
+        self._check_vmax(got, fresh, np.stack(self.sh.bstore), 'max_value_store')
+
+    def op_infotaxis(self):
+        (g, act), (fg, fact) = self.both(lambda e: e.infotaxis_resident())
+        self.same(g, fg, 'infotaxis G against the fresh engine')
+        self.same(act, fact, 'infotaxis actions against the fresh engine')
+        want = infotaxis_ref(self.mname, self.sh.bel, f32=self.f32)
+        if not np.all(np.abs(g - want.G) <= want.bound):
+            self.fail(f'infotaxis G off by up to {np.max(np.abs(g - want.G) / want.bound):.2f} bounds')
+        self.same(act, P.infotaxis_first_argmin(g), 'infotaxis actions against the first argmin of the returned G')
+        if self.m.A > 1:
+            srt, bnd = np.sort(want.G, axis=1), want.bound.max(axis=1)
+            ok = (srt[:, 1] - srt[:, 0]) > 2.0 * bnd
+            self.same(act[ok], want.act[ok], 'infotaxis actions against the host statement')
+        self.done(g=g, act=act)
+
+    def op_fetch_beliefs(self):
+        got, fresh = self.both(lambda e: e.fetch_beliefs())
+        self.same(got, fresh, 'fetch_beliefs against the fresh engine')
+        self.same(got, self.sh.bel.astype(self.npdt), 'fetch_beliefs against the shadow')
+        self.done(bel=got)
+
+    def op_prune_dominated(self):
+        sh = self.sh
+        rows = sh.alpha.astype(self.npdt)
+        got, fresh = self.both(lambda e: e.prune_dominated(rows))
+        sh.put_alpha(sh.alpha)                                                    # (re-uploaded: no selection any more)
+        self.same(got, fresh, 'prune_dominated against the fresh engine')
+        self.same(got, prune_ref(self.mname, sh.alpha), 'prune_dominated against the host statement')
+        self.done(keep=got)
+
+    def op_prune_masked(self, seed=0):
+        sh = self.sh
+        full = prune_ref(self.mname, sh.alpha)
+        # the rows called old are kept by the full prune, hence free of domination among themselves (the precondition)
+        is_new = ~full | (np.random.default_rng([int(seed), 61]).random(sh.V) < 0.3)
+        rows = sh.alpha.astype(self.npdt)
+        got, fresh = self.both(lambda e: e.prune_dominated_masked(rows, is_new))
+        sh.put_alpha(sh.alpha)
+        self.same(got, fresh, 'prune_dominated_masked against the fresh engine')
+        self.same(got, full, 'prune_dominated_masked against the host statement')
+        self.done(keep=got)
+
+    def op_belief_update(self, seed=0):
+        sh = self.sh
+        acts, obs = possible_steps(self.m, sh.bel, np.random.default_rng([int(seed), 67]))
+        rows = sh.bel.astype(self.npdt)
+        got, fresh = self.both(lambda e: e.belief_update(rows, acts, obs))
+        sh.put_beliefs(sh.bel)                                                    # (re-uploaded; the block itself is unchanged)
+        want = update_ref(self.m, sh.bel, acts, obs)
+        self.close_to(got, want, UPDATE_RTOL[self.dtype], UPDATE_ATOL, 'belief_update against the host statement')
+        self.close_to(got, fresh, UPDATE_RTOL[self.dtype], UPDATE_ATOL, 'belief_update against the fresh engine')
+        self.done(rows=got)
+
+
+# --------------------------------------------------------------------------------------------------------------------- #
+# HostEngine: Engine's method names over the host statements
+# --------------------------------------------------------------------------------------------------------------------- #
+class _HostResult:
+    def __init__(self, unique_alpha, index, actions, best_alpha_ind, keep):
+        self.unique_alpha, self.index, self.actions, self.best_alpha_ind, self.keep = unique_alpha, index, actions, best_alpha_ind, keep
+
+
+class HostEngine:
+    """What an ``Engine`` computes, from ``backup_ref`` and the ``*_numpy`` statements, with results rounded to the engine's
+    type where the engine stores them in it.  Switches are recorded and change nothing."""
+
+    def __init__(self, mname, dtype):
+        self.mname, self.m, self.dtype = mname, model(mname), dtype
+        self.np_dtype = np.float32 if dtype == 'f32' else np.float64
+        self.switches = {}
+        self._fail_next = False
+        self.after_oom()
+
+    def _rows(self, x):
+        return np.ascontiguousarray(np.asarray(x, dtype=self.np_dtype), dtype=np.float64)
+
+    def close(self):
+        pass
+
+    def after_oom(self):
+        self.alpha = self.bel = self.res = None
+        self.astore, self.bstore = [], []
+        self.env = self.probe_ref = None
+        self.epoch = {k: v + 1 for k, v in getattr(self, 'epoch', {'alpha': 0, 'belief': 0}).items()}
+
+    def debug_fail_next_call(self):
+        self._fail_next = True
+
+    def _maybe_fail(self):
+        if self._fail_next:
+            self._fail_next = False
+            self.after_oom()
+            raise MemoryError('stand-in: allocation refused')
+
+    @property
+    def alpha_count(self):
+        return 0 if self.alpha is None else self.alpha.shape[0]
+
+    @property
+    def B(self):
+        return 0 if self.bel is None else self.bel.shape[0]
+
+    # residency
+    def _alpha_changed(self):
+        self.res = None
+
+    def _beliefs_changed(self):
+        self.res = None
+
+    def set_alpha(self, a):
+        self.alpha = self._rows(a)
+        self._alpha_changed()
+
+    def append_alpha(self, a):
+        self.alpha = np.concatenate([self.alpha, self._rows(a)])
+        self._alpha_changed()
+
+    def set_beliefs(self, b):
+        self.bel = self._rows(b)
+        self._beliefs_changed()
+
+    def store_rows(self, which, rows):
+        self._maybe_fail()
+        store = self.astore if which == 'alpha' else self.bstore
+        store.extend(self._rows(rows))
+        return len(store) - len(rows)
+
+    def store_unique(self, idx):
+        rows = np.asarray(self.res.unique_alpha, dtype=np.float64)[np.asarray(idx)]
+        self.astore.extend(rows)
+        return len(self.astore) - len(rows)
+
+    def select_alpha(self, ids):
+        self.alpha = np.stack([self.astore[int(i)] for i in ids])
+        self._alpha_changed()
+
+    def select_beliefs(self, ids):
+        self.bel = np.stack([self.bstore[int(i)] for i in ids])
+        self._beliefs_changed()
+
+    def reset_store(self, which):
+        if which == 'alpha':
+            self.astore = []
+        else:
+            self.bstore = []
+        self.epoch[which] += 1
+
+    # switches
+    def set_formulation(self, v):
+        self.switches['formulation'] = v
+
+    def set_f64_screen(self, v):
+        self.switches['f64_screen'] = v
+
+    def set_fused_projection(self, v):
+        self.switches['fused_projection'] = v
+
+    def set_score_split(self, v):
+        self.switches['score_split'] = v
+
+    def set_gamma_tiling(self, mode, rows=0):
+        self.switches['gamma_tiling'] = (mode, rows)
+
+    def set_tie_window(self, v):
+        self.switches['tie_window'] = v
+
+    def set_value_max_exact(self, v):
+        self.switches['value_max_exact'] = v
+
+    def debug_score_probe(self, v=True):
+        self.switches['score_probe'] = v
+
+    # the backup
+    def _decisions(self, ref):
+        """``(best [B,A,O], order)``: hooks of the defective stand-ins."""
+        return ref.best, None
+
+    def _backup(self):
+        m, ref = self.m, backup_ref(self.mname, self.alpha, self.bel, tol=TOL[self.dtype])
+        self.probe_ref = ref if self.switches.get('score_probe') else None
+        best, order = self._decisions(ref)
+        if best is ref.best:
+            act, rows, keep, index, firsts_keys = ref.act, ref.rows, ref.keep, ref.index, ref.keys
+            urows = ref.urows
+        else:                                                 # a defective stand-in changed a decision: redo the tail
+            B = self.B
+            picked = ref.g[np.arange(m.A)[None, :, None], np.arange(m.O)[None, None, :], best]
+            alpha_a = m.er.T[None] + picked.sum(axis=2)
+            val = np.einsum('bas,bs->ba', alpha_a, self.bel)
+            act = np.argmax(val, axis=1)
+            rows = alpha_a[np.arange(B), act]
+            keep = val[np.arange(B), act] > (self.bel @ self.alpha.T).max(axis=1)
+            keys = np.concatenate([act[:, None], best[np.arange(B), act]], axis=1)
+            seen, index, firsts = {}, np.empty(B, dtype=np.int64), []
+            for b in range(B):
+                k = keys[b].tobytes()
+                if k not in seen:
+                    seen[k] = len(firsts)
+                    firsts.append(b)
+                index[b] = seen[k]
+            firsts_keys, urows = keys[firsts], rows[firsts]
+        out = SimpleNamespace(best=best, act=act, keep=keep, index=index, keys=firsts_keys, urows=urows.astype(self.np_dtype))
+        if order is not None:                                 # results delivered in another block's caller order
+            out.best, out.act, out.keep, out.index = best[order], act[order], keep[order], index[order]
+        return out
+
+    def run(self, gamma, belief_dominance_prune=False):
+        assert gamma == GAMMA
+        self.res_flag = bool(belief_dominance_prune)
+        r = self._backup()
+        keep = r.keep if belief_dominance_prune else np.ones(self.B, dtype=bool)
+        self.res = _HostResult(r.urows, r.index.copy(), r.act.copy(), r.best.copy(), keep.copy())
+        self.res_keys = r.keys
+        return {}
+
+    def fetch(self):
+        if self.res is None:
+            raise ValueError('no backup result resident')
+        return self.res
+
+    def fetch_compact_into(self, rows, index, actions, best=None, keep=None):
+        r = self.fetch()
+        U = r.unique_alpha.shape[0]
+        rows[:U], index[:], actions[:] = r.unique_alpha, r.index, r.actions
+        if best is not None:
+            best[:] = r.best_alpha_ind
+        if keep is not None:
+            keep[:] = r.keep
+        return U
+
+    def run_fetch_into(self, gamma, rows, slot, index, actions, best=None, keep=None, belief_dominance_prune=False):
+        self.run(gamma, belief_dominance_prune)
+        U = self.fetch_compact_into(rows, index, actions, best, keep)
+        slot[:U] = np.arange(U)
+        return {}, U, U
+
+    def fetch_unique_keys(self):
+        self.fetch()
+        return self.res_keys.astype(np.int32)
+
+    def assemble_rows(self, keys, gamma):
+        m = self.m
+        g = backup_ref(self.mname, self.alpha, self.bel, tol=TOL[self.dtype]).g
+        out = np.stack([m.er[:, k[0]] + sum(g[k[0], o, k[1 + o]] for o in range(m.O)) for k in np.asarray(keys)])
+        return out.astype(self.np_dtype)
+
+    def fetch_row_hashes(self):
+        return np.array([_row_hash(r) for r in self.fetch().unique_alpha], dtype=np.uint64)
+
+    def q_values_resident(self, gamma, want_best=False):
+        r = backup_ref(self.mname, self.alpha, self.bel, tol=TOL[self.dtype])
+        self.res = None
+        return (r.q, np.argmax(r.q, axis=1), r.best) if want_best else (r.q, np.argmax(r.q, axis=1))
+
+    def _vmax(self, bel):
+        r = vmax_ref(self.mname, self.alpha, bel)
+        return r.val, r.idx
+
+    def max_value_resident(self):
+        return self._vmax(self.bel)
+
+    def max_value_store(self, n=-1):
+        return self._vmax(np.stack(self.bstore if n < 0 else self.bstore[:n]))
+
+    def infotaxis_resident(self):
+        r = infotaxis_ref(self.mname, self.bel, f32=self.dtype == 'f32')
+        return r.G, r.act
+
+    def fetch_beliefs(self):
+        return self.bel.astype(self.np_dtype)
+
+    def prune_dominated(self, alpha):
+        self.set_alpha(alpha)
+        return prune_ref(self.mname, self.alpha)
+
+    def prune_dominated_masked(self, alpha, is_new):
+        return self.prune_dominated(alpha)
+
+    def belief_update(self, beliefs, actions, observations):
+        self.set_beliefs(beliefs)
+        return update_ref(self.m, self.bel, actions, observations).astype(self.np_dtype)
+
+    def advance_beliefs(self, actions, observations, keep=None):
+        nb = update_ref(self.m, self.bel, actions, observations)
+        self.bel = self._rows(nb if keep is None else nb[np.asarray(keep).astype(bool)])
+        self._beliefs_changed()
+        return self.B
+
+    def belief_walk(self, b0, actions, observations, restart=None):
+        rows, b = [], np.asarray(b0, dtype=np.float64)
+        for a, o in zip(actions, observations):
+            b = orc.belief_update(b, int(a), int(o), self.m.rs, self.m.rto)
+            rows.append(b)
+        self.bstore.extend(self._rows(np.stack(rows)))
+        return np.stack(rows), len(self.bstore) - len(rows)
+
+    def _survivors(self, out, beliefs):
+        self.bel = self._rows(beliefs) if len(beliefs) else None
+        self._beliefs_changed()
+        return out
+
+    def _td(self):
+        return np.float32 if self.dtype == 'f32' else np.float64
+
+    def rollout(self, alpha_actions, start_states, end_mask, seed, T, first_sim_id=0, lookahead=0, gamma=0.99):
+        out = P.rollout_numpy(self.m.tables, self.alpha, alpha_actions, self.bel, start_states, seed, first_sim_id, T,
+                              lookahead=lookahead, gamma=gamma, table_dtype=self._td(), return_beliefs=True)
+        return self._survivors(out[:4], out[4])
+
+    def rollout_infotaxis(self, start_states, end_mask, seed, T, first_sim_id=0):
+        out = P.rollout_infotaxis_numpy(self.m.tables, self.bel, start_states, seed, first_sim_id, T, table_dtype=self._td(),
+                                        return_beliefs=True)
+        return self._survivors(out[:4], out[4])
+
+    def set_environment_table(self, obs_prob):
+        self.env = P.TableEnvironment(obs_prob)
+
+    def set_environment_frames(self, frames, channel_of_action):
+        self.env = P.FrameEnvironment(frames, channel_of_action)
+
+    def hold_environment(self, env):
+        self.env = env
+
+    def clear_environment(self):
+        self.env = None
+
+    def store_tag(self, which):
+        return (id(self), which, self.epoch[which])
+
+    def max_value_objects(self, alpha_objects, belief_objects, alpha_values, belief_values):
+        for which, objs, val_of, store in (('alpha', alpha_objects, alpha_values, self.astore),
+                                           ('belief', belief_objects, belief_values, self.bstore)):
+            tag = self.store_tag(which)
+            for o in objs:
+                if getattr(o, '_dev', (None, -1))[0] != tag:
+                    store.append(self._rows(val_of(o)[None, :])[0])
+                    o._dev = (tag, len(store) - 1)
+        self.select_alpha([o._dev[1] for o in alpha_objects])
+        self.select_beliefs([o._dev[1] for o in belief_objects])
+        return self.max_value_resident()[0]
+
+    def debug_score_probe_fetch(self):
+        if not self.switches.get('score_probe') or self.probe_ref is None:
+            raise ValueError('nothing captured')
+        r = self.probe_ref
+        B, G = r.top.shape[0], self.m.A * self.m.O
+        return {'best_score': r.top.reshape(B, G), 'best_v': r.best.reshape(B, G), 'E': np.zeros((B, G)), 'queue': np.zeros(0, np.int32),
+                'perm': np.arange(B), 'split': 0, 'tol_extra': 0.0}
+
+    def rollout_env(self, policy, alpha_actions, start_states, end_mask, seed, T, first_sim_id=0, gamma=0.99):
+        out = P.rollout_env_numpy(self.m.tables, self.env, policy, self.alpha, alpha_actions, self.bel, start_states, seed,
+                                  first_sim_id, T, gamma=gamma, table_dtype=self._td(), return_beliefs=True)
+        return self._survivors(out[:4] + (out[5],), out[4])
+
+
+# -- five planted carry-over bugs ------------------------------------------------------------------------------------------ #
+def dead_map(m, bel):
+    """[B,A,O]: triples whose belief gives (a, o) no mass at all."""
+    return (np.abs(bel) @ np.abs(m.rto).sum(axis=3).reshape(m.S, m.A * m.O)).reshape(-1, m.A, m.O) == 0
+
+
+class DeadMapKept(HostEngine):
+    """The dead-triple map of the previous block answers for a selected block of the same size."""
+
+    def select_beliefs(self, ids):
+        old = None if self.bel is None else dead_map(self.m, self.bel)
+        super().select_beliefs(ids)
+        self.stale_dead = old if old is not None and old.shape[0] == self.B else None
+
+    def _beliefs_changed(self):
+        super()._beliefs_changed()
+        self.stale_dead = None
+
+    def _decisions(self, ref):
+        dead = getattr(self, 'stale_dead', None)
+        if dead is None or not np.any(dead & (ref.best != 0)):
+            return ref.best, None
+        return np.where(dead, 0, ref.best), None
+
+
+class MagnitudeNotMerged(HostEngine):
+    """A prepend extension leaves the magnitude row as it was: the tie window follows the old set's max |alpha|, and
+    the near-ties it no longer catches are decided by the fp32 scores (here: the fp64 scores plus a fixed pattern of at
+    most half a window)."""
+
+    def select_alpha(self, ids):
+        old = None if self.alpha is None else self.alpha
+        super().select_alpha(ids)
+        k = 0 if old is None else len(ids) - old.shape[0]
+        if old is not None and k > 0 and np.array_equal(self.alpha[k:], old):
+            self.stale_amax = getattr(self, 'stale_amax', None)
+            if self.stale_amax is None:
+                self.stale_amax = np.abs(old).max(axis=0)
+        else:
+            self.stale_amax = None
+
+    def set_alpha(self, a):
+        super().set_alpha(a)
+        self.stale_amax = None
+
+    def _decisions(self, ref):
+        amax = getattr(self, 'stale_amax', None)
+        if amax is None:
+            return ref.best, None
+        m = self.m
+        mag_stale = sw.ref_scores(amax[None, :], np.abs(self.bel), m.rs, np.abs(m.rto), GAMMA)[:, :, 0].reshape(ref.mag.shape)
+        E, E_stale = 8.0 * sw.U24 * ref.mag, 8.0 * sw.U24 * mag_stale
+        noise = (((np.arange(ref.sc.size) * 2654435761) % 1000) / 1000.0 - 0.5).reshape(ref.sc.shape) * E[..., None]
+        noisy = ref.sc + noise
+        top2 = np.sort(noisy, axis=-1)[..., -2:] if noisy.shape[-1] > 1 else None
+        if top2 is None:
+            return ref.best, None
+        queued = (top2[..., 1] - top2[..., 0]) <= 2.0 * E_stale                  # what the stale window still refines
+        wrong = ~queued & (np.argmax(noisy, axis=-1) != ref.best)
+        return (np.where(wrong, np.argmax(noisy, axis=-1), ref.best), None) if wrong.any() else (ref.best, None)
+
+
+def sort_order(bel):
+    """The engine's block order in spirit: rows by their first non-zero state (stable)."""
+    return np.argsort(np.argmax(bel != 0, axis=1), kind='stable')
+
+
+class PreviousCallerOrder(HostEngine):
+    """A sorted block (more than one row block of the GEMM) hands its results back in the order of the previous sorted
+    block of the same size."""
+
+    def _beliefs_changed(self):
+        super()._beliefs_changed()
+        thr = 256 if self.dtype == 'f32' else 128
+        cur = sort_order(self.bel) if self.bel is not None and self.B > thr else None
+        prev = getattr(self, 'cur_perm', None)
+        self.stale_perm = prev if cur is not None and prev is not None and len(prev) == len(cur) else None
+        self.cur_perm = cur
+
+    def _decisions(self, ref):
+        if getattr(self, 'stale_perm', None) is None:
+            return ref.best, None
+        order = np.empty(self.B, dtype=np.int64)
+        order[self.stale_perm] = self.cur_perm                                   # engine row i goes to the OLD caller row
+        return ref.best, (None if np.array_equal(order, np.arange(self.B)) else order)
+
+
+class FetchAfterSetAlpha(HostEngine):
+    """``set_alpha`` leaves the previous backup fetchable."""
+
+    def set_alpha(self, a):
+        keep = self.res
+        super().set_alpha(a)
+        self.res = keep
+
+
+class StoreZeroMapsKept(HostEngine):
+    """``reset_store('belief')`` keeps the zero maps of the complete 256-row blocks that ``max_value_store`` has seen: rows
+    appended afterwards are scored through the old blocks' maps (K tiles of 32 states)."""
+
+    def _tile_map(self, rows):
+        S = self.m.S
+        pad = np.zeros((rows.shape[0], -(-S // 32) * 32))
+        pad[:, :S] = rows
+        return (pad.reshape(rows.shape[0], -1, 32) != 0).any(axis=2).any(axis=0)
+
+    def max_value_store(self, n=-1):
+        rows = np.stack(self.bstore)
+        maps, seen = getattr(self, 'maps', []), getattr(self, 'seen', 0)
+        maps = maps[:seen // 256]
+        for blk in range(len(maps), -(-len(rows) // 256)):
+            maps.append(self._tile_map(rows[blk * 256:(blk + 1) * 256]))
+        self.maps, self.seen = maps, len(rows)
+        masked = rows.copy()
+        for blk, mp in enumerate(maps):
+            masked[blk * 256:(blk + 1) * 256] *= np.repeat(mp, 32)[:self.m.S]
+        return self._vmax(masked)
+
+    def after_oom(self):
+        super().after_oom()
+        self.maps, self.seen = [], 0
+
+
+DEFECTS = {'dead_map_kept': DeadMapKept, 'magnitude_not_merged': MagnitudeNotMerged, 'previous_caller_order': PreviousCallerOrder,
+           'fetch_after_set_alpha': FetchAfterSetAlpha, 'store_zero_maps_kept': StoreZeroMapsKept}
+
+
+# --------------------------------------------------------------------------------------------------------------------- #
+# scripted sequences: one per carry-over of the issue's table, as literal lists
+# --------------------------------------------------------------------------------------------------------------------- #
+def op(name, **args):
+    return (name, args)
+
+
+def sw_(name, value):
+    return ('switch', {'name': name, 'value': value})
+
+
+LOW, HIGH = (0.0, 0.25), (0.5, 1.0)
+
+# name -> (models, dtypes, operations)
+SCRIPTED = {
+    # dead_, btl_, btc_: two blocks of the same B with different dead triples and supports, each selected twice; behind the
+    # later selections the value maxima come first (they build the new block's tile lists and leave dead_ to the backup)
+    'dead_triples_and_tile_lists': (MODELS, DTYPES, [
+        op('set_alpha', V=257, seed=1), sw_('formulation', 'alpha'),
+        op('store_beliefs', B=129, seed=1, win=LOW, onehot=True), op('store_beliefs', B=129, seed=2, win=HIGH, onehot=True),
+        op('select_beliefs', how='random', B=129, seed=1), op('run_fetch'), op('vmax_resident'),
+        op('select_beliefs', how='last', B=129), op('run_fetch'), op('q_values'), op('fetch_refused'),
+        op('select_beliefs', how='same'), op('run_prune_fetch'), op('remember', tag='second'),
+        op('select_beliefs', how='random', B=129, seed=3), op('vmax_resident'), op('run_fetch'), op('vmax_resident'),
+        op('select_beliefs', how='last', B=129), op('vmax_resident'), op('run_prune_fetch'), op('same_as', tag='second'),
+        op('fetch_beliefs'), op('set_beliefs', B=129, seed=3, win=LOW, onehot=True), op('vmax_resident'), op('q_values'),
+        op('run_fetch')]),
+    # rowflags_, nzA_, perm_, h_perm_, sorted_, res_sorted_: sorted blocks of one size, an unsorted one in between
+    'sorted_blocks_of_one_size': (MODELS, DTYPES, [
+        op('set_alpha', V=5, seed=2), op('set_beliefs', B=300, seed=1), op('run_fetch'), op('vmax_resident'),
+        op('set_beliefs', B=300, seed=2, win=HIGH), op('run_fetch'), op('fetch_compact_into'), op('keys_assemble'),
+        op('row_hashes'), op('vmax_resident'), op('q_values'), op('set_beliefs', B=3, seed=3), op('run_fetch'),
+        op('set_beliefs', B=300, seed=4, win=LOW), op('run_fetch_into'), op('infotaxis'), op('fetch_beliefs'),
+        op('set_beliefs', B=257, seed=5), op('run_prune_fetch'), op('set_beliefs', B=256, seed=6), op('run_fetch'),
+        op('vmax_resident')]),
+    # belsp_: a block put in place while the split is off, then a split run; blocks of one size through the store
+    'split_plane_of_another_block': (('G',), ('f32',), [
+        op('set_alpha', V=600, seed=3), sw_('formulation', 'alpha'), sw_('score_split', 'always'),
+        op('store_beliefs', B=300, seed=1, win=LOW), op('store_beliefs', B=300, seed=2, win=HIGH),
+        op('select_beliefs', how='random', B=300, seed=2), op('run_fetch'), op('remember', tag='split'),
+        sw_('score_split', 'off'), op('run_fetch'), op('same_as', tag='split'),
+        op('select_beliefs', how='last', B=300), op('run_fetch'), op('remember', tag='plain'),
+        sw_('score_split', 'always'), op('run_fetch'), op('same_as', tag='plain'),
+        op('select_beliefs', how='random', B=300, seed=2), op('run_prune_fetch'), op('set_beliefs', B=128, seed=3),
+        op('run_fetch'), sw_('score_split', 'auto'), op('run_fetch')]),
+    # primary layout, alpha_small_, magnitude row: the four forms of a selection, larger rows prepended
+    'alpha_layouts_and_magnitude_row': (MODELS, DTYPES, [
+        op('set_beliefs', B=129, seed=4), sw_('formulation', 'alpha'), op('store_alpha', V=5, seed=1),
+        op('select_alpha', how='all'), op('run_fetch'),
+        op('extend_alpha', V=250, seed=2, near=40, scale=40.0), op('run_fetch'), op('vmax_resident'),
+        op('extend_alpha', V=1, seed=3, scale=400.0), op('run_fetch'), op('q_values'),
+        op('select_alpha', how='small', seed=1), op('run_fetch'), op('vmax_resident'),
+        op('select_alpha', how='primary'), op('run_fetch'), op('prune_masked', seed=1),
+        op('select_alpha', how='all'), op('extend_alpha', V=1, seed=4), op('run_fetch'),
+        op('extend_alpha', V=343, seed=5, near=40, scale=40.0, ties=100), op('run_prune_fetch'),
+        op('extend_alpha', V=520, seed=6), op('run_fetch'), op('vmax_resident'),
+        op('reset_alpha_store'), op('run_fetch'), op('store_alpha', V=5, seed=7), op('select_alpha', how='all'),
+        op('run_fetch'), op('prune_dominated')]),
+    # the fp32 screen's mirror: a set grown at the front three times under the screen, a value beyond FLT_MAX, a set without
+    'f64_screen_mirror_and_overflow': (('G',), ('f64',), [
+        sw_('f64_screen', 'always'), sw_('formulation', 'alpha'), op('set_beliefs', B=129, seed=5, win=(0.0, 0.5)),
+        op('store_alpha', V=255, seed=1), op('select_alpha', how='all'), op('run_fetch'),
+        op('extend_alpha', V=1, seed=2), op('run_fetch'), op('extend_alpha', V=1, seed=3, scale=40.0), op('run_fetch'),
+        op('extend_alpha', V=5, seed=4, near=1), op('run_prune_fetch'),
+        # (fresh layouts with as many free rows in front as the one the screen mirrors: nothing of its copy may stay --
+        # before the row that overflows, behind which the screen is not asked)
+        op('select_alpha', how='fresh', seed=3), op('run_fetch'), op('select_alpha', how='fresh', seed=4), op('run_prune_fetch'),
+        op('extend_alpha', V=5, seed=5, huge=True), op('run_fetch'), op('q_values'), op('run_fetch'),
+        op('select_alpha', how='small', seed=2), op('run_fetch'), op('select_alpha', how='all'), op('run_fetch'),
+        op('set_alpha', V=257, seed=6), op('run_fetch'), op('remember', tag='screened'),
+        sw_('f64_screen', 'off'), op('run_fetch'), op('same_as', tag='screened'),
+        sw_('f64_screen', 'always'), op('set_alpha', V=5, seed=7, huge=True), op('run_fetch'), op('set_alpha', V=5, seed=8),
+        op('run_fetch')]),
+    # gam_pad_*: a tiled call whose chunk has as many rows as an earlier untiled call's set; tiling off -> always -> off
+    'gamma_pad_rows': (MODELS, DTYPES, [
+        sw_('formulation', 'alpha'), sw_('fused_projection', 0), op('set_beliefs', B=128, seed=6),
+        op('set_alpha', V=256, seed=1), op('run_fetch'),
+        op('set_alpha', V=600, seed=2, ties=100), op('run_fetch'), op('remember', tag='untiled'),
+        sw_('gamma_tiling', ('always', 256)), op('run_fetch'), op('same_as', tag='untiled'),
+        sw_('gamma_tiling', ('off', 0)), op('run_fetch'), op('same_as', tag='untiled'),
+        sw_('gamma_tiling', ('always', 100)), op('set_alpha', V=255, seed=3), op('run_fetch'), op('q_values'),
+        op('set_alpha', V=100, seed=4), op('run_prune_fetch'), sw_('gamma_tiling', ('off', 0)), op('set_alpha', V=257, seed=5),
+        op('run_fetch'), sw_('fused_projection', 1), op('run_fetch')]),
+    # found by 'switches_both_ways': fp64 scoring has no tie window, and a ragged last chunk small enough for the plain
+    # fp64 kernel (here: one row, a copy of the winner) summed in another order than the MFMA chunks before it, so the
+    # copy's score differed in its last bits and the later index won.  257 = 4 x 64 + 1 = 2 x 128 + 1 = 256 + 1.
+    'tiled_fp64_chunks_of_two_kernels': (MODELS, DTYPES, [
+        sw_('formulation', 'alpha'), sw_('f64_screen', 'off'), op('set_alpha', V=257, seed=1, ties=100, near=20),
+        op('set_beliefs', B=129, seed=24), op('run_fetch'), op('remember', tag='untiled'),
+        sw_('gamma_tiling', ('always', 64)), op('run_fetch'), op('same_as', tag='untiled'),
+        sw_('gamma_tiling', ('always', 128)), op('run_prune_fetch'), sw_('gamma_tiling', ('always', 256)), op('run_fetch'),
+        op('same_as', tag='untiled'), op('q_values'), sw_('gamma_tiling', ('always', 100)), op('run_fetch'),
+        op('same_as', tag='untiled'), sw_('gamma_tiling', ('off', 0)), op('run_fetch'), op('same_as', tag='untiled')]),
+    # mat_, vlist_, ctile_, mat_V_: fused on -> off -> on with V changing in between
+    'fused_tile_map': (('G',), ('f32',), [
+        sw_('formulation', 'alpha'), op('set_beliefs', B=257, seed=7), op('set_alpha', V=600, seed=1), op('run_fetch'),
+        op('remember', tag='fused'), sw_('fused_projection', 0), op('run_fetch'), op('same_as', tag='fused'),
+        op('set_alpha', V=257, seed=2), op('run_fetch'), sw_('fused_projection', 1), op('run_fetch'),
+        op('set_alpha', V=600, seed=3), op('run_fetch'), sw_('fused_projection', 2), op('set_alpha', V=600, seed=1),
+        op('run_fetch'), op('same_as', tag='fused'), op('set_alpha', V=1, seed=4), op('run_fetch')]),
+    # plan_, nchunks_, klist_ (control): the shapes change with every call
+    'plans_rebuilt_per_call': (MODELS, DTYPES, [
+        op('set_alpha', V=256, seed=1), op('set_beliefs', B=256, seed=8), op('run_fetch'), op('set_beliefs', B=1, seed=9),
+        op('run_fetch'), op('vmax_resident'), op('set_alpha', V=1, seed=2), op('run_fetch'), op('q_values'),
+        op('set_beliefs', B=257, seed=10), op('run_fetch'), op('set_alpha', V=255, seed=3), op('run_prune_fetch'),
+        op('append_alpha', V=2, seed=4), op('run_fetch'), op('vmax_resident')]),
+    # snz_, sbtl_, sbtc_: the belief store as an operand, reset and refilled with as many rows of another support
+    'belief_store_zero_maps': (MODELS, DTYPES, [
+        op('set_alpha', V=129, seed=1), op('store_beliefs', B=300, seed=1, win=LOW), op('vmax_store'),
+        op('store_beliefs', B=3, seed=2), op('vmax_store'), op('reset_belief_store_append', seed=3, win=HIGH),
+        op('vmax_store'), op('belief_walk', n=9, seed=1), op('vmax_store'), op('set_alpha', V=5, seed=2), op('vmax_store'),
+        op('select_beliefs', how='last', B=40), op('vmax_resident'), op('vmax_store'), op('run_fetch'), op('vmax_store'),
+        op('fetch_compact_into')]),
+    # last_deferred_nothing_: sets without ties and with ~100 exact ties per triple, alternating
+    'speculation_both_ways': (MODELS, DTYPES, [
+        sw_('formulation', 'alpha'), op('set_beliefs', B=129, seed=11), op('set_alpha', V=257, seed=1), op('run_fetch'),
+        op('set_alpha', V=257, seed=2, ties=100), op('run_fetch'), op('set_alpha', V=257, seed=3), op('run_fetch'),
+        op('run_fetch'), op('set_alpha', V=257, seed=4, ties=100), op('run_prune_fetch'), op('q_values'),
+        op('set_alpha', V=256, seed=5), op('q_values'), op('run_fetch')]),
+    # have_result_, have_bk_vmax_, full_valid_, vmax_bk_: what is fetchable after what
+    'results_of_an_earlier_backup': (MODELS, DTYPES, [
+        op('fetch_refused'), op('store_beliefs', B=3, seed=1), op('set_alpha', V=5, seed=1), op('set_beliefs', B=128, seed=12),
+        op('fetch_refused'),
+        sw_('formulation', 'belief'), op('run_fetch'), op('vmax_resident'), op('fetch_compact_into'), op('vmax_store'),
+        op('set_alpha', V=5, seed=2), op('fetch_refused'), op('run_prune_fetch'), op('infotaxis'), op('keys_assemble'),
+        op('row_hashes'), op('q_values'), op('fetch_refused'), op('run_fetch'), op('set_beliefs', B=128, seed=13),
+        op('fetch_refused'), op('run_fetch'), op('store_unique'), op('fetch_refused'), op('run_fetch'),
+        op('belief_update', seed=1), op('fetch_refused'), op('run_fetch'), op('prune_dominated'), op('fetch_refused'),
+        op('vmax_resident'), op('run_fetch'), op('vmax_resident'), op('fetch_compact_into'), sw_('formulation', 'auto')]),
+    # environment, walk64_ (control) and the blocks rollouts leave behind
+    'rollouts_leave_their_survivors': (MODELS, DTYPES, [
+        op('set_alpha', V=129, seed=1), op('set_beliefs', B=40, seed=14), op('rollout', T=3, seed=1), op('run_fetch'),
+        op('vmax_resident'), op('set_beliefs', B=40, seed=15), op('rollout', T=2, seed=2, lookahead=1), op('q_values'),
+        op('set_beliefs', B=3, seed=16), op('rollout_infotaxis', T=3, seed=3), op('infotaxis'), op('fetch_beliefs'),
+        op('set_beliefs', B=40, seed=17), op('rollout_env', T=3, seed=4, policy=0), op('run_fetch'),
+        op('set_beliefs', B=40, seed=18), op('rollout_env', T=2, seed=5, policy=2), op('fetch_beliefs'),
+        op('advance_beliefs', keep=True, seed=1), op('run_fetch'), op('advance_beliefs', keep=False, seed=2),
+        op('vmax_resident'), op('belief_walk', n=5, seed=2), op('select_beliefs', how='last', B=5), op('run_fetch')]),
+    # Python side: _vmax_cache, object tags under _store_epoch, _alpha_token, _env_held -- max_value_objects and
+    # hold_environment asked again after the state they remember has died (store reset, after_oom, a grown alpha set,
+    # env_clear, another holder); frames and tables take turns as the environment (env_kind_)
+    'python_side_caches': (MODELS, DTYPES, [
+        op('vmax_objects', V=12, B=40, seed=1), op('vmax_objects', keep=True), op('run_fetch'),
+        op('vmax_objects', keep=True, grow=3), op('vmax_resident'), op('reset_alpha_store'), op('vmax_objects', keep=True),
+        op('run_prune_fetch'), op('reset_belief_store_append', seed=2), op('vmax_objects', keep=True), op('vmax_store'),
+        op('set_alpha', V=5, seed=2), op('vmax_objects', keep=True), op('q_values'), op('after_oom'),
+        op('vmax_objects', keep=True), op('run_fetch'), op('oom_call'), op('vmax_objects', keep=True, grow=2),
+        op('vmax_objects', V=5, B=3, seed=3), op('run_fetch'),
+        op('set_beliefs', B=40, seed=30), op('rollout_env', T=3, seed=1, policy=0, env='frames', env_seed=1, hold=True),
+        op('set_beliefs', B=40, seed=31), op('rollout_env', T=3, seed=2, policy=1, env='frames', env_seed=1, hold=True),
+        op('clear_environment'), op('set_beliefs', B=40, seed=32),
+        op('rollout_env', T=3, seed=3, policy=2, env='frames', env_seed=1, hold=True), op('after_oom'),
+        op('set_alpha', V=12, seed=3), op('set_beliefs', B=40, seed=33),
+        op('rollout_env', T=3, seed=4, policy=0, env='frames', env_seed=1, hold=True),
+        op('set_beliefs', B=40, seed=34), op('rollout_env', T=3, seed=5, policy=0, env='frames', env_seed=2, hold=True),
+        op('set_beliefs', B=40, seed=35), op('rollout_env', T=3, seed=6, policy=0, env='table', env_seed=3, hold=True),
+        op('set_beliefs', B=40, seed=36), op('rollout_env', T=2, seed=7, policy=1, env='frames', env_seed=2),
+        op('set_beliefs', B=40, seed=37), op('rollout_env', T=3, seed=8, policy=0, env='table', env_seed=3, hold=True),
+        op('run_fetch'), op('clear_environment')]),
+    # best_score: what the argmax saw before any refinement, through the score probe, on every scoring route
+    # (found here: behind a screened backup an fp64 engine kept handing out its screen's old capture for its own newer
+    # ones -- the captures' order was counted per element type -- until the block size changed and the fetch refused)
+    'best_score_through_the_probe': (MODELS, DTYPES, [
+        sw_('score_probe', True), op('set_alpha', V=257, seed=1, ties=100, near=20), op('set_beliefs', B=129, seed=40, onehot=True),
+        sw_('formulation', 'alpha'), op('run_fetch'), sw_('score_split', 'always'), op('run_fetch'), sw_('score_split', 'off'),
+        sw_('f64_screen', 'always'), op('run_fetch'), sw_('f64_screen', 'off'), op('run_prune_fetch'),
+        sw_('formulation', 'belief'), op('run_fetch'), sw_('f64_screen', 'always'), op('run_fetch'), sw_('formulation', 'alpha'),
+        sw_('fused_projection', 0), sw_('gamma_tiling', ('always', 100)), op('run_fetch'), sw_('score_split', 'always'),
+        op('run_fetch'), sw_('gamma_tiling', ('off', 0)), sw_('fused_projection', 1), sw_('score_split', 'auto'),
+        sw_('f64_screen', 'auto'), op('set_beliefs', B=300, seed=41, win=HIGH), op('run_fetch'), op('set_alpha', V=5, seed=2),
+        op('run_fetch'), sw_('score_probe', False), op('run_fetch'), sw_('score_probe', True), op('set_beliefs', B=3, seed=42),
+        op('run_fetch')]),
+    # _resident, _store_epoch, and the state after a failed allocation
+    'resets_and_refused_allocations': (MODELS, DTYPES, [
+        op('store_alpha', V=5, seed=1), op('select_alpha', how='all'), op('store_beliefs', B=3, seed=19),
+        op('select_beliefs', how='last', B=3), op('run_fetch'), op('after_oom'), op('fetch_refused'),
+        op('store_alpha', V=5, seed=2), op('select_alpha', how='all'), op('store_beliefs', B=3, seed=20),
+        op('select_beliefs', how='last', B=3), op('run_fetch'), op('oom_call'), op('fetch_refused'),
+        op('store_alpha', V=5, seed=3), op('select_alpha', how='all'), op('set_beliefs', B=3, seed=21), op('run_fetch'),
+        op('reset_alpha_store'), op('store_alpha', V=5, seed=4), op('select_alpha', how='all'), op('run_fetch'),
+        op('vmax_resident')]),
+    # the solve loop's shape: backup, store the new rows, select new-then-old, value-max on both sides, again
+    'solve_loop': (MODELS, DTYPES, [
+        op('store_alpha', V=5, seed=1), op('select_alpha', how='all'), op('store_beliefs', B=40, seed=22),
+        op('select_beliefs', how='last', B=40), op('vmax_store'), op('run_prune_fetch'), op('store_unique'), op('vmax_store'),
+        op('vmax_resident'), op('store_beliefs', B=40, seed=23), op('select_beliefs', how='random', B=80, seed=4),
+        op('run_prune_fetch'), op('store_unique'), op('vmax_store'), op('prune_masked', seed=2), op('run_fetch'),
+        op('store_unique'), op('vmax_resident'), op('q_values')]),
+    # every switch both ways around unchanged operands: the same answers
+    'switches_both_ways': (MODELS, DTYPES, [
+        op('set_alpha', V=257, seed=1, ties=100, near=20), op('set_beliefs', B=129, seed=24), op('run_fetch'),
+        op('remember', tag='r'), op('vmax_resident'), op('remember', tag='v'),
+        sw_('score_probe', True), op('run_fetch'), op('same_as', tag='r'), sw_('score_probe', False), op('run_fetch'),
+        op('same_as', tag='r'), sw_('tie_window', 1e-3), op('run_fetch'), op('same_as', tag='r'), sw_('tie_window', -1.0),
+        op('run_fetch'), op('same_as', tag='r'), sw_('value_max_exact', False), op('vmax_resident'),
+        sw_('value_max_exact', True), op('vmax_resident'), op('same_as', tag='v'),
+        sw_('formulation', 'belief'), op('run_fetch'), op('same_as', tag='r'), sw_('formulation', 'alpha'), op('run_fetch'),
+        op('same_as', tag='r'), sw_('formulation', 'auto'), op('run_fetch'), op('same_as', tag='r'),
+        sw_('score_split', 'always'), op('run_fetch'), op('same_as', tag='r'), sw_('score_split', 'off'), op('run_fetch'),
+        op('same_as', tag='r'), sw_('score_split', 'auto'), sw_('f64_screen', 'always'), op('run_fetch'), op('same_as', tag='r'),
+        sw_('f64_screen', 'off'), op('run_fetch'), op('same_as', tag='r'), sw_('f64_screen', 'auto'),
+        sw_('fused_projection', 0), op('run_fetch'), op('same_as', tag='r'), sw_('fused_projection', 2), op('run_fetch'),
+        op('same_as', tag='r'), sw_('fused_projection', 1), sw_('gamma_tiling', ('always', 64)), op('run_fetch'),
+        op('same_as', tag='r'), sw_('gamma_tiling', ('off', 0)), op('run_fetch'), op('same_as', tag='r')]),
+}
+
+
+def pair_sequence(mutation):
+    """Set-up, one mutation, then every query that is legal behind it (a backup in between where a query needs one)."""
+    setup = [op('store_alpha', V=12, seed=1), op('select_alpha', how='all'), op('store_beliefs', B=40, seed=1),
+             op('select_beliefs', how='last', B=40), op('run_fetch')]
+    mut = {'set_alpha': [op('set_alpha', V=12, seed=2)], 'append_alpha': [op('append_alpha', V=3, seed=3)],
+           'store_alpha': [op('store_alpha', V=3, seed=4)], 'extend_alpha': [op('extend_alpha', V=3, seed=5)],
+           'select_alpha': [op('select_alpha', how='fresh', seed=6)], 'store_unique': [op('store_unique')],
+           'reset_alpha_store': [op('reset_alpha_store')], 'set_beliefs': [op('set_beliefs', B=40, seed=7)],
+           'store_beliefs': [op('store_beliefs', B=3, seed=8)], 'select_beliefs': [op('select_beliefs', how='random', B=40, seed=9)],
+           'advance_beliefs': [op('advance_beliefs', keep=True, seed=10)], 'belief_walk': [op('belief_walk', n=3, seed=11)],
+           'rollout': [op('rollout', T=2, seed=12)], 'rollout_infotaxis': [op('rollout_infotaxis', T=2, seed=13)],
+           'rollout_env': [op('rollout_env', T=2, seed=14, policy=1)],
+           'reset_belief_store_append': [op('reset_belief_store_append', seed=15)],
+           'after_oom': [op('after_oom')], 'oom_call': [op('oom_call')]}[mutation]
+    if mutation in RESETS:
+        return setup + mut + [op('fetch_refused')]
+    first = [] if mutation in ('store_alpha', 'store_beliefs', 'belief_walk', 'reset_alpha_store', 'reset_belief_store_append') \
+        else [op('fetch_refused')]
+    tail = [op('fetch_beliefs'), op('infotaxis'), op('vmax_resident'), op('vmax_store'), op('run_fetch'), op('fetch_compact_into'),
+            op('keys_assemble'), op('row_hashes'), op('run_prune_fetch'), op('run_fetch_into'), op('q_values'),
+            op('belief_update', seed=1), op('prune_masked', seed=1), op('prune_dominated')]
+    if mutation in ('store_alpha', 'store_beliefs', 'belief_walk', 'reset_alpha_store', 'reset_belief_store_append'):
+        tail = tail + [op('q_values'), op('fetch_refused')]                       # these leave the result where it is
+    return setup + mut + first + tail
+
+
+for _i, _m in enumerate(MUTATIONS):
+    SCRIPTED['after_' + _m] = ((MODELS[_i % 2],), (DTYPES[(_i // 2) % 2],), pair_sequence(_m))
+
+# which scripted sequence aims at which planted bug of the stand-ins (each must fail there)
+DEFECT_SCRIPTS = {'dead_map_kept': 'dead_triples_and_tile_lists', 'magnitude_not_merged': 'alpha_layouts_and_magnitude_row',
+                  'previous_caller_order': 'sorted_blocks_of_one_size', 'fetch_after_set_alpha': 'results_of_an_earlier_backup',
+                  'store_zero_maps_kept': 'belief_store_zero_maps'}
+
+
+def scripted_cases():
+    return [(name, mname, dtype) for name, (models, dtypes, _) in SCRIPTED.items() for mname in models for dtype in dtypes]
+
+
+# --------------------------------------------------------------------------------------------------------------------- #
+# seeded random sequences
+# --------------------------------------------------------------------------------------------------------------------- #
+QUERY_WEIGHTS = {'run_fetch': 4, 'run_prune_fetch': 2, 'vmax_resident': 2, 'vmax_store': 2, 'q_values': 2, 'run_fetch_into': 2}
+MUTATION_WEIGHTS = {'after_oom': 0.2, 'oom_call': 0.2}            # (a reset empties the engine: rare, and re-populated at once)
+ECHOED = ('set_alpha', 'set_beliefs', 'select_beliefs', 'extend_alpha', 'reset_belief_store_append')
+MIN_VALUE_QUERIES, MIN_BACKUPS = 8, 3                           # per seeded sequence (fetch_refused compares no value)
+
+
+def draw_op(rng, sh, kind, last=None):
+    """One operation of ``kind`` ('query', 'mutation', 'switch') drawn for the shadow's state (legality is the caller's).
+    ``last``: the most recent mutation.  Carry-overs show when the same kind of state comes again with other content, so
+    four times in ten a mutation repeats the last one's kind and sizes with another seed and window; queries lean towards
+    the backup, and towards the store scan behind a change of the belief store."""
+    pick = lambda xs: xs[int(rng.integers(0, len(xs)))]
+    seed = int(rng.integers(1, 1000))
+    if kind == 'query':
+        w = np.array([QUERY_WEIGHTS.get(q, 1) for q in QUERIES], dtype=np.float64)
+        if last is not None and last[0] in ('store_beliefs', 'reset_belief_store_append', 'belief_walk'):
+            w[QUERIES.index('vmax_store')] *= 6
+        name = QUERIES[int(rng.choice(len(QUERIES), p=w / w.sum()))]
+        return op(name, seed=seed) if name in ('prune_masked', 'belief_update') else op(name)
+    if kind == 'switch':
+        name = pick(sorted(SWITCH_VALUES))
+        value = pick([v for v in SWITCH_VALUES[name] if v != sh.switches[name]])
+        return sw_(name, value)
+    win = pick((None, LOW, HIGH, (0.25, 0.75)))
+    if last is not None and last[0] in ECHOED and rng.random() < 0.4:
+        args = dict(last[1], seed=seed)
+        if 'win' in args:
+            args['win'] = win
+        return (last[0], args)
+    names = MUTATIONS + COMPOUND
+    w = np.array([MUTATION_WEIGHTS.get(n, 1.0) for n in names])
+    name = names[int(rng.choice(len(names), p=w / w.sum()))]
+    small = rng.random() < 0.6                                    # most sets are small; every edge still comes up
+    V = int(pick((5, 12, 40) if small else V_EDGES))
+    B = int(pick((3, 40, 64) if small else B_EDGES))
+    if name in ('set_alpha', 'store_alpha'):
+        return op(name, V=V, seed=seed, ties=int(pick((0, 0, 100))), near=int(pick((0, 4))))
+    if name in ('append_alpha', 'extend_alpha'):
+        return op(name, V=int(pick((1, 3, 5, 12, 250, 600))), seed=seed, scale=float(pick((4.0, 40.0))), near=int(pick((0, 4, 40))))
+    if name == 'select_alpha':
+        return op(name, how=pick(('small', 'primary', 'all', 'fresh')), seed=seed)
+    if name in ('set_beliefs', 'store_beliefs'):
+        return op(name, B=B, seed=seed, win=win, onehot=bool(rng.random() < 0.3))
+    if name == 'select_beliefs':
+        return op(name, how=pick(('same', 'last', 'random', 'random')), B=B, seed=seed)
+    if name == 'advance_beliefs':
+        return op(name, keep=bool(rng.random() < 0.5), seed=seed)
+    if name == 'belief_walk':
+        return op(name, n=int(pick((1, 3, 9))), seed=seed)
+    if name == 'rollout':
+        return op(name, T=int(pick((1, 3, 5))), seed=seed, lookahead=int(pick((0, 1))))
+    if name == 'rollout_infotaxis':
+        return op(name, T=int(pick((1, 3, 5))), seed=seed)
+    if name == 'rollout_env':
+        return op(name, T=int(pick((1, 3, 5))), seed=seed, policy=int(pick((0, 1, 2))), env=pick(('table', 'frames')),
+                  env_seed=int(pick((0, 1, 2))), hold=bool(rng.random() < 0.5))
+    if name == 'reset_belief_store_append':
+        return op(name, seed=seed, win=win)
+    if name == 'vmax_objects':
+        return op(name, V=int(pick((5, 12))), B=int(pick((3, 40))), seed=seed, keep=bool(rng.random() < 0.6), grow=int(pick((0, 0, 3))))
+    return op(name)
+
+
+def generate(mname, dtype, seed, n_ops=N_RANDOM_OPS):
+    """``n_ops`` operations, about one in three a query that compares a value (more often behind a mutation than behind a
+    query), each legal in the state the ones before it leave.  The state is followed with a ``HostEngine`` (rollouts and
+    keep masks decide how many rows stay), so the list depends on nothing but the arguments.  It starts from selections
+    out of both stores, the state a solve is in; a reset, or a rollout that nobody survives, is followed at once by new
+    working sets, so the walk does not sit in an empty engine."""
+    rng = np.random.default_rng([sw.seed_of('sequence', mname, dtype), int(seed)])
+    r = Runner(mname, dtype, lambda: HostEngine(mname, dtype))
+    B0 = int((40, 257, 129, 300)[int(seed) % 4])
+    ops = [op('store_alpha', V=12, seed=int(seed) + 1), op('select_alpha', how='all'),
+           op('store_beliefs', B=B0, seed=int(seed) + 1, win=LOW, onehot=True), op('select_beliefs', how='last', B=B0)]
+    r.run(ops)
+    last, prev_kind = ops[2], 'mutation'
+
+    def add(cand):
+        r.run([cand])
+        ops.append(cand)
+
+    while len(ops) < n_ops:
+        if r.sh.V == 0:
+            add(op('store_alpha', V=12, seed=int(rng.integers(1, 1000))))
+            add(op('select_alpha', how='all'))
+            continue
+        if r.sh.B == 0:
+            last = op('set_beliefs', B=40, seed=int(rng.integers(1, 1000)), win=None, onehot=False)
+            add(last)
+            prev_kind = 'mutation'
+            continue
+        p_query = {'mutation': 0.6, 'switch': 0.5, 'query': 0.15}[prev_kind]
+        u = rng.random()
+        kind = 'query' if u < p_query else ('switch' if u < p_query + 0.15 else 'mutation')
+        for _ in range(100):
+            cand = draw_op(rng, r.sh, kind, last)
+            if not legal(cand[0], cand[1], r.sh):
+                continue
+            if cand[0] in ('append_alpha', 'extend_alpha') and r.sh.V + cand[1]['V'] > 1300:
+                continue
+            if cand[0] == 'store_beliefs' and len(r.sh.bstore) + cand[1]['B'] > 700:
+                continue
+            break
+        else:
+            raise AssertionError(f'no legal {kind} in this state')
+        add(cand)
+        prev_kind = kind
+        if kind == 'mutation':
+            last = cand
+    ops = ops[:n_ops]
+    assert r.skipped == 0, f'seed {seed}: {r.skipped} undecidable entries'
+    n_value, n_backup = (sum(name in group for name, _ in ops) for group in (VALUE_QUERIES, BACKUPS))
+    assert n_value >= MIN_VALUE_QUERIES and n_backup >= MIN_BACKUPS, f'seed {seed}: {n_value} value queries, {n_backup} backups'
+    return ops
+
+
+# the committed seeds: out of 0 .. 39, sequences without an undecidable entry and with the minimum of value queries and
+# backups, taken so that every planted bug of the stand-ins fails at least one of them
+# (tests/golden/engine_sequences.json holds their operation lists)
+SEEDS = {('G', 'f32'): (0, 2, 3, 5, 7, 15, 34, 37), ('G', 'f64'): (0, 1, 2, 3, 4, 5, 24, 25),
+         ('I', 'f32'): (0, 2, 4, 6, 10, 18, 19, 25), ('I', 'f64'): (0, 1, 2, 3, 6, 16, 19, 20)}
+
+
+def seeded_cases():
+    return [(mname, dtype, seed) for mname in MODELS for dtype in DTYPES for seed in SEEDS[mname, dtype]]
+
+
+def to_json(ops):
+    return [[name, {k: (list(v) if isinstance(v, tuple) else v) for k, v in args.items()}] for name, args in ops]
+
+
+def from_json(ops):
+    return [(name, {k: (tuple(v) if isinstance(v, list) else v) for k, v in args.items()}) for name, args in ops]
+
+
+# --------------------------------------------------------------------------------------------------------------------- #
+# coverage accounting over lists of operations
+# --------------------------------------------------------------------------------------------------------------------- #
+NEVER_LEGAL_AFTER_A_RESET = {(m, q) for m in RESETS for q in QUERIES if q != 'fetch_refused'}
+
+
+def coverage(sequences):
+    """Counts over ``[(mname, dtype, ops)]``: operations, (most recent mutation -> query) pairs, switch values, B and V."""
+    counts = {n: 0 for n in VOCABULARY}
+    pairs, switch_values, Bs, Vs, hows, returned, envs = set(), set(), set(), set(), set(), set(), set()
+    for _, _, ops in sequences:
+        last, now, left = None, dict(SWITCH_DEFAULTS), set()
+        for name, args in ops:
+            if name in HARNESS:
+                continue
+            counts[name] += 1
+            if name in MUTATIONS:
+                last = name
+            elif name in QUERIES and last is not None:
+                pairs.add((last, name))
+            if name == 'switch':
+                v = args['value']
+                v = tuple(v) if isinstance(v, list) else v
+                switch_values.add((args['name'], v))
+                if v != SWITCH_DEFAULTS[args['name']]:
+                    left.add(args['name'])
+                elif args['name'] in left and now[args['name']] != v:
+                    returned.add(args['name'])                   # away from the default and back within this sequence
+                now[args['name']] = v
+            if name == 'rollout_env':
+                envs.add((args.get('env', 'table'), bool(args.get('hold', False))))
+            if name in ('set_beliefs', 'store_beliefs', 'select_beliefs') and 'B' in args:
+                Bs.add(args['B'])
+            if name in ('set_alpha', 'store_alpha'):
+                Vs.add(args['V'])
+            if name == 'select_alpha':
+                hows.add(args['how'])
+    return SimpleNamespace(counts=counts, pairs=pairs, switch_values=switch_values, Bs=Bs, Vs=Vs, hows=hows, returned=returned,
+                           envs=envs)
