@@ -2500,8 +2500,7 @@ class EngineT : public EngineBase {
     // device pointer to the stream-K share size (K-tile steps of the longest f32 chain) or nullptr
     const int* chain_steps() const {
         if (!kF32 || !plan_.streamk) return nullptr;
-        const size_t pairs = (size_t)plan_.tiles_m * plan_.tiles_n;
-        return skws_.as<int>() + (pairs + 1) + plan_.nblocks + pairs;
+        return streamk_workspace(plan_, skws_.as<int>()).plan;
     }
     double tie_window(int k_chunk) const {
         if (!kF32) return 0.0;
@@ -3760,19 +3759,34 @@ int EngineT<T>::score_gemm(const T* Y, int64_t rows_y, const uint8_t* nzB, int G
         int sp = split != nullptr && *split && plan_.streamk && (fused == nullptr || fused->R == 1) ? 1 : 0;
         if (sp && (!own_block || !split_plane())) sp = 0;      // no plane: the fp32 GEMM (same outputs)
         if (split != nullptr) *split = sp;
-        HIPCHK(launch_gemm_nt_f32(sp ? belsp_.as<float>() : (const float*)X, S_pad_, (const float*)Y, S_pad_, slabs_.as<float>(), plan_,
-                                  nzX, nzB, G, v_group, (int)rows_y, klist_.as<int>(), kcount_.as<int>(),
-                                  nchunks_.as<int>(), stream_, 1, 0, 0, skws_.as<int>(), list_stream, ev_lists_, nullptr, nullptr,
-                                  fused, sp));
+        ScoreGemmArgs g;
+        g.A = sp ? belsp_.as<float>() : (const float*)X;
+        g.B = (const float*)Y;
+        g.lda = g.ldb = S_pad_;
+        g.C = slabs_.as<float>();
+        g.plan = plan_;
+        g.nzA = nzX;
+        g.nzB = nzB;
+        g.G = G;
+        g.v_group = v_group;
+        g.n_rows = (int)rows_y;
+        g.klist = klist_.as<int>();
+        g.kcount = kcount_.as<int>();
+        g.nchunks = nchunks_.as<int>();
+        g.stream = stream_;
+        g.streamk_ws = skws_.as<int>();
+        g.list_stream = list_stream;
+        g.list_event = ev_lists_;
+        g.fused = fused;
+        g.split = sp;
+        HIPCHK(launch_score_gemm_f32(g));
         sv->slabs = slabs_.as<T>();
         sv->slab_stride = plan_.slab_stride;
         sv->ldc = plan_.ldc;
         sv->nchunks = nchunks_.as<int>();
         sv->tiles_m = plan_.tiles_m;
         sv->fixed = 0;
-        // (the stream-K plan's first_block array: launch_gemm_nt_f32 lays the workspace out as prefix[pairs + 1],
-        // start_pair[nblocks], first_block[pairs], plan[2])
-        sv->first_block = plan_.streamk ? skws_.as<int>() + (pairs + 1) + plan_.nblocks : nullptr;
+        sv->first_block = plan_.streamk ? streamk_workspace(plan_, skws_.as<int>()).first_block : nullptr;
     } else {
         const int kt32s = S_pad_ / GEMM_BK;
         const bool mfma = f64_route < 0 ? f64_uses_mfma(m_rows, rows_y) : f64_route > 0;
@@ -3823,10 +3837,25 @@ int EngineT<T>::project_dense(double gamma) {
         dense_pairs_ = (int64_t)AO * pairs;
         HIPCHK(hipMemsetAsync(prod_.p, 0, (size_t)AO * batch_stride * sizeof(float), stream_));   // pairs with empty lists
         HIPCHK(launch_tile_nonzero_f32((const float*)alpha_.p, S_pad_, (int)Vt_pad, pl.k_tiles, nzAlpha_.as<uint8_t>(), stream_));
-        HIPCHK(launch_gemm_nt_f32((const float*)alpha_.p, S_pad_, (const float*)dense_.p, S_pad_, prod_.as<float>(), pl,
-                                  nzAlpha_.as<uint8_t>(), nzD_.as<uint8_t>(), 0, 0, S_, klistD_.as<int>(),
-                                  kcountD_.as<int>(), nchunksD_.as<int>(), stream_, AO, rows_pad_s_ * (int64_t)S_pad_,
-                                  batch_stride, nullptr, nullptr, nullptr, ev_pg_[0], ev_pg_[1]));
+        BatchedGemmArgs g;
+        g.A = (const float*)alpha_.p;
+        g.B = (const float*)dense_.p;
+        g.lda = g.ldb = S_pad_;
+        g.C = prod_.as<float>();
+        g.plan = pl;
+        g.nzA = nzAlpha_.as<uint8_t>();
+        g.nzB = nzD_.as<uint8_t>();       // per n-tile flags
+        g.n_rows = S_;
+        g.klist = klistD_.as<int>();
+        g.kcount = kcountD_.as<int>();
+        g.nchunks = nchunksD_.as<int>();
+        g.stream = stream_;
+        g.batch = AO;
+        g.batch_stride_b = rows_pad_s_ * (int64_t)S_pad_;
+        g.batch_stride_c = batch_stride;
+        g.ev_before = ev_pg_[0];
+        g.ev_after = ev_pg_[1];
+        HIPCHK(launch_batched_gemm_f32(g));
     } else {
         ld_prod = S_;
         batch_stride = Vt * S_;

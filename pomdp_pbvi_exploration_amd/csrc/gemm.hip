@@ -263,13 +263,24 @@ __global__ void k_streamk_plan(const int* __restrict__ kcount, int pairs, int nb
     }
 }
 
-__global__ __launch_bounds__(512) void k_gemm_nt_f32_streamk(
-    const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb, float* __restrict__ C, int ldc,
-    int64_t slab_stride, int tiles_m, int pairs, int k_tiles, const int* __restrict__ klist,
-    const int* __restrict__ kcount, const int* __restrict__ prefix, const int* __restrict__ start_pair,
-    const int* __restrict__ first_block, const int* __restrict__ plan, int ovh) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    // XCD-contiguous logical ids: consecutive shares (which walk the same n-tile's pairs) on one XCD.
+// Named arguments of the stream-K kernels: the tile lists with the plan k_streamk_plan made of them, and where the slabs go.
+struct StreamKView {
+    const int *klist, *kcount, *prefix, *start_pair, *first_block, *plan;
+    int tiles_m, pairs, k_tiles, ovh;
+};
+struct SlabOut {
+    float* C;
+    int ldc;
+    int64_t slab_stride;
+};
+
+// The share walk of every stream-K kernel.  Block ids are made XCD-contiguous first: consecutive shares (which walk the
+// same n-tile's pairs) sit on one XCD.  Share L covers cost units [L q, (L + 1) q) of the concatenated lists (units and
+// `ovh`: see k_streamk_plan); part(t, p, tm, tn, lo, hi, acc) multiplies entries [lo, hi) of pair p's list into the zeroed
+// accumulators.  The first chunk of a pair is stored into the full slab; a continuation into this block's own tile behind
+// it (GemmPlan::c_floats).  Arguments by value: by reference two kernels gain an SGPR spill (profiles/streamk_walk.md).
+template <typename Part>
+__device__ __forceinline__ void streamk_walk(const StreamKView v, const SlabOut out, Part part) {
     const int nb = gridDim.x;
     int L;
     {
@@ -277,38 +288,53 @@ __global__ __launch_bounds__(512) void k_gemm_nt_f32_streamk(
         const int base = (xcd < r) ? xcd * (qq + 1) : r * (qq + 1) + (xcd - r) * qq;
         L = base + (bid >> 3);
     }
-    const int q = plan[0], T = plan[1];
+    const int q = v.plan[0], T = v.plan[1];
     int64_t pos = (int64_t)L * q;
     if (pos >= T) return;
     const int64_t end = (pos + q < T) ? pos + q : T;
-    int p = start_pair[L];
+    int p = v.start_pair[L];
     if (p < 0) return;                                   // cannot happen when pos < T; defensive
     TileThread t;
     t.init();
-    while (pos < end && p < pairs) {
-        const int cnt = kcount[p];
+    while (pos < end && p < v.pairs) {
+        const int cnt = v.kcount[p];
         if (cnt == 0) {                                  // block-uniform
             ++p;
             continue;
         }
-        const int u_lo = (int)(pos - prefix[p]);         // cost units of this pair inside the share
+        const int u_lo = (int)(pos - v.prefix[p]);       // cost units of this pair inside the share
         const int64_t room = end - pos;
-        const int u_hi = (u_lo + room < cnt + ovh) ? (int)(u_lo + room) : cnt + ovh;
-        const int lo = u_lo > ovh ? u_lo - ovh : 0;
-        const int hi = u_hi > ovh ? u_hi - ovh : 0;
+        const int u_hi = (u_lo + room < cnt + v.ovh) ? (int)(u_lo + room) : cnt + v.ovh;
+        const int lo = u_lo > v.ovh ? u_lo - v.ovh : 0;
+        const int hi = u_hi > v.ovh ? u_hi - v.ovh : 0;
         if (hi > lo) {
-            const int tm = p % tiles_m, tn = p / tiles_m;
+            const int tm = p % v.tiles_m, tn = p / v.tiles_m;
             f32x16 acc[4][2];
             tile_zero(acc);
-            tile_run(t, lds, A + (int64_t)tm * 256 * lda, lda, B + (int64_t)tn * 256 * ldb, ldb,
-                     klist + (int64_t)p * k_tiles, lo, hi, acc);
-            // first chunk of the pair: the full slab; a continuation: this block's tile behind it (GemmPlan::c_floats)
-            const bool cont = L != first_block[p];
-            tile_store(t, cont ? C + slab_stride + (int64_t)L * (256 * 256) : C, cont ? 256 : ldc, cont ? 0 : tm, cont ? 0 : tn, acc);
+            part(t, p, tm, tn, lo, hi, acc);
+            const bool cont = L != v.first_block[p];
+            tile_store(t, cont ? out.C + out.slab_stride + (int64_t)L * (256 * 256) : out.C, cont ? 256 : out.ldc, cont ? 0 : tm,
+                       cont ? 0 : tn, acc);
         }
         pos += u_hi - u_lo;
         ++p;
     }
+}
+
+// Every stream-K kernel takes these arguments (one signature: the kernel table below).  Flat, not the two structs: only a
+// __restrict__ kernel argument makes the uniform reads of the lists and the plan scalar loads (profiles/streamk_walk.md).
+// This kernel reads every B tile and ignores its FusedB.
+__global__ __launch_bounds__(512) void k_gemm_nt_f32_streamk(
+    const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb, FusedB, float* __restrict__ C, int ldc,
+    int64_t slab_stride, int tiles_m, int pairs, int k_tiles, const int* __restrict__ klist, const int* __restrict__ kcount,
+    const int* __restrict__ prefix, const int* __restrict__ start_pair, const int* __restrict__ first_block,
+    const int* __restrict__ plan, int ovh) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const StreamKView v{klist, kcount, prefix, start_pair, first_block, plan, tiles_m, pairs, k_tiles, ovh};
+    streamk_walk(v, SlabOut{C, ldc, slab_stride}, [&](const TileThread& t, int p, int tm, int tn, int lo, int hi, auto& acc) {
+        tile_run(t, lds, A + (int64_t)tm * 256 * lda, lda, B + (int64_t)tn * 256 * ldb, ldb, klist + (int64_t)p * k_tiles,
+                 lo, hi, acc);
+    });
 }
 
 // --------------------------------------------------------------------------- //
@@ -325,9 +351,6 @@ __global__ __launch_bounds__(512) void k_gemm_nt_f32_streamk(
 // writes and the 0.3 ms kernel that makes them.  Tiles flagged in `mat` (those that straddle two groups, and the tail
 // tile with the magnitude / reward rows) are projected as before and take the LDS-DMA path from B.
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-#ifndef PBVI_FUSED_EXP
-#define PBVI_FUSED_EXP 0      // diagnosis builds only: 1 = no alpha loads, 2 = no LDS stores (wrong results, timing only)
-#endif
 
 // Loads of the generated operand are issued as inline assembly and waited for with explicit s_waitcnt: vector
 // memory operations return in issue order, so "vmcnt(n)" means "all but the last n issued have arrived".  Left to the
@@ -394,20 +417,12 @@ __device__ __forceinline__ void tile_run_fused(const TileThread& t, float* lds, 
                              : "memory");
             }
         } else {
-#if PBVI_FUSED_EXP == 1
-#pragma unroll
-            for (int it = 0; it < 4; ++it) av[it] = w;
-#else
 #pragma unroll
             for (int it = 0; it < 4; ++it) ld16(av[it], arow0 + it * a_step + idx[0]);
-#endif
         }
     };
     auto store_b = [&](int buf) {
         float* lb = lds + buf * 2 * TILE_FLOATS + TILE_FLOATS;
-#if PBVI_FUSED_EXP == 2
-        if (gamma == 12345.f)
-#endif
 #pragma unroll
         for (int it = 0; it < 4; ++it) *(f32x4*)(lb + (it * 512 + tid) * 4) = fused_value(gamma, w, av[it]);
     };
@@ -454,55 +469,20 @@ __global__ __launch_bounds__(512) void k_gemm_nt_f32_streamk_fused(
     const int* __restrict__ prefix, const int* __restrict__ start_pair, const int* __restrict__ first_block,
     const int* __restrict__ plan, int ovh) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int nb = gridDim.x;
-    int L;
-    {
-        const int bid = blockIdx.x, xcd = bid & 7, qq = nb >> 3, r = nb & 7;
-        const int base = (xcd < r) ? xcd * (qq + 1) : r * (qq + 1) + (xcd - r) * qq;
-        L = base + (bid >> 3);
-    }
-    const int q = plan[0], T = plan[1];
-    int64_t pos = (int64_t)L * q;
-    if (pos >= T) return;
-    const int64_t end = (pos + q < T) ? pos + q : T;
-    int p = start_pair[L];
-    if (p < 0) return;
-    TileThread t;
-    t.init();
-    while (pos < end && p < pairs) {
-        const int cnt = kcount[p];
-        if (cnt == 0) {                                  // block-uniform
-            ++p;
-            continue;
+    const StreamKView v{klist, kcount, prefix, start_pair, first_block, plan, tiles_m, pairs, k_tiles, ovh};
+    streamk_walk(v, SlabOut{C, ldc, slab_stride}, [&](const TileThread& t, int p, int tm, int tn, int lo, int hi, auto& acc) {
+        if (fb.mat[tn]) {                                // block-uniform: projected rows, the LDS-DMA path
+            const int bt = fb.ctile != nullptr ? fb.ctile[tn] : tn;          // (compact layout: only these tiles exist)
+            tile_run(t, lds, A + (int64_t)tm * 256 * lda, lda, B + (int64_t)bt * 256 * ldb, ldb,
+                     klist + (int64_t)p * k_tiles, lo, hi, acc);
+        } else {
+            const int r0 = tn * 256;
+            const int g = r0 / fb.V, v0 = r0 - g * fb.V;                     // scalar: all 256 rows belong to group g
+            tile_run_fused(t, lds, A + (int64_t)tm * 256 * lda, lda, fb.rs + (int64_t)(g / fb.O) * fb.S_pad,
+                           fb.rto + (int64_t)g * fb.S_pad, fb.alpha + (int64_t)(v0 + t.srow[0]) * fb.lda,
+                           (int64_t)64 * fb.lda, fb.gamma, klist + (int64_t)p * k_tiles, lo, hi, acc);
         }
-        const int u_lo = (int)(pos - prefix[p]);
-        const int64_t room = end - pos;
-        const int u_hi = (u_lo + room < cnt + ovh) ? (int)(u_lo + room) : cnt + ovh;
-        const int lo = u_lo > ovh ? u_lo - ovh : 0;
-        const int hi = u_hi > ovh ? u_hi - ovh : 0;
-        if (hi > lo) {
-            const int tm = p % tiles_m, tn = p / tiles_m;
-            f32x16 acc[4][2];
-            tile_zero(acc);
-            if (fb.mat[tn]) {                            // block-uniform: projected rows, the LDS-DMA path
-                const int bt = fb.ctile != nullptr ? fb.ctile[tn] : tn;      // (compact layout: only these tiles exist)
-                tile_run(t, lds, A + (int64_t)tm * 256 * lda, lda, B + (int64_t)bt * 256 * ldb, ldb,
-                         klist + (int64_t)p * k_tiles, lo, hi, acc);
-            } else {
-                const int r0 = tn * 256;
-                const int g = r0 / fb.V, v0 = r0 - g * fb.V;                 // scalar: all 256 rows belong to group g
-                tile_run_fused(t, lds, A + (int64_t)tm * 256 * lda, lda, fb.rs + (int64_t)(g / fb.O) * fb.S_pad,
-                               fb.rto + (int64_t)g * fb.S_pad, fb.alpha + (int64_t)(v0 + t.srow[0]) * fb.lda,
-                               (int64_t)64 * fb.lda, fb.gamma,
-                               klist + (int64_t)p * k_tiles, lo, hi, acc);
-            }
-            // first chunk of the pair: the full slab; a continuation: this block's tile behind it (GemmPlan::c_floats)
-            const bool cont = L != first_block[p];
-            tile_store(t, cont ? C + slab_stride + (int64_t)L * (256 * 256) : C, cont ? 256 : ldc, cont ? 0 : tm, cont ? 0 : tn, acc);
-        }
-        pos += u_hi - u_lo;
-        ++p;
-    }
+    });
 }
 
 // --------------------------------------------------------------------------- //
@@ -603,11 +583,7 @@ __device__ __forceinline__ void tile_run_fused_r(const TileThread& t, float* lds
     auto unit_issue = [&](int u, int slot, int tb) {
         const int hh = u >= R ? 1 : 0, r = u - hh * R;     // compile-time at the unrolled issue points
         const i32x4 idx = *(const i32x4*)(tabi + tb * TAB_WORDS + r * GEMM_BK + scol0);
-#if PBVI_FUSED_EXP == 3      // diagnosis: every load from the row's first line (wrong results, timing only)
-        const float* p0 = arow0 + (int64_t)(2 * hh) * a_step + (idx[0] & 3);
-#else
         const float* p0 = arow0 + (int64_t)(2 * hh) * a_step + idx[0];
-#endif
         ld16(av[slot][0], p0);
         ld16(av[slot][1], p0 + a_step);
     };
@@ -691,54 +667,20 @@ __global__ __launch_bounds__(512) void k_gemm_nt_f32_streamk_fused_r(
     const int* __restrict__ prefix, const int* __restrict__ start_pair, const int* __restrict__ first_block,
     const int* __restrict__ plan, int ovh) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int nb = gridDim.x;
-    int L;
-    {
-        const int bid = blockIdx.x, xcd = bid & 7, qq = nb >> 3, r = nb & 7;
-        const int base = (xcd < r) ? xcd * (qq + 1) : r * (qq + 1) + (xcd - r) * qq;
-        L = base + (bid >> 3);
-    }
-    const int q = plan[0], T = plan[1];
-    int64_t pos = (int64_t)L * q;
-    if (pos >= T) return;
-    const int64_t end = (pos + q < T) ? pos + q : T;
-    int p = start_pair[L];
-    if (p < 0) return;
-    TileThread t;
-    t.init();
-    while (pos < end && p < pairs) {
-        const int cnt = kcount[p];
-        if (cnt == 0) {                                  // block-uniform
-            ++p;
-            continue;
+    const StreamKView v{klist, kcount, prefix, start_pair, first_block, plan, tiles_m, pairs, k_tiles, ovh};
+    streamk_walk(v, SlabOut{C, ldc, slab_stride}, [&](const TileThread& t, int p, int tm, int tn, int lo, int hi, auto& acc) {
+        if (fb.mat[tn]) {                                // block-uniform: projected rows, the LDS-DMA path
+            tile_run(t, lds, A + (int64_t)tm * 256 * lda, lda, B + (int64_t)tn * 256 * ldb, ldb,
+                     klist + (int64_t)p * k_tiles, lo, hi, acc);
+        } else {
+            const int r0 = tn * 256;
+            const int g = r0 / fb.V, v0 = r0 - g * fb.V;                     // scalar: all 256 rows belong to group g
+            tile_run_fused_r<R>(t, lds, A + (int64_t)tm * 256 * lda, lda, B + (int64_t)tn * 256 * ldb, ldb,
+                                fb.rs + (int64_t)(g / fb.O) * R * fb.S_pad, fb.rto + (int64_t)g * R * fb.S_pad, fb.S_pad,
+                                fb.alpha + (int64_t)(v0 + t.srow[0]) * fb.lda, (int64_t)64 * fb.lda, fb.gamma,
+                                klist + (int64_t)p * k_tiles, lo, hi, acc);
         }
-        const int u_lo = (int)(pos - prefix[p]);
-        const int64_t room = end - pos;
-        const int u_hi = (u_lo + room < cnt + ovh) ? (int)(u_lo + room) : cnt + ovh;
-        const int lo = u_lo > ovh ? u_lo - ovh : 0;
-        const int hi = u_hi > ovh ? u_hi - ovh : 0;
-        if (hi > lo) {
-            const int tm = p % tiles_m, tn = p / tiles_m;
-            f32x16 acc[4][2];
-            tile_zero(acc);
-            if (fb.mat[tn]) {                            // block-uniform: projected rows, the LDS-DMA path
-                tile_run(t, lds, A + (int64_t)tm * 256 * lda, lda, B + (int64_t)tn * 256 * ldb, ldb,
-                         klist + (int64_t)p * k_tiles, lo, hi, acc);
-            } else {
-                const int r0 = tn * 256;
-                const int g = r0 / fb.V, v0 = r0 - g * fb.V;                 // scalar: all 256 rows belong to group g
-                tile_run_fused_r<R>(t, lds, A + (int64_t)tm * 256 * lda, lda, B + (int64_t)tn * 256 * ldb, ldb,
-                                 fb.rs + (int64_t)(g / fb.O) * R * fb.S_pad, fb.rto + (int64_t)g * R * fb.S_pad,
-                                 fb.S_pad, fb.alpha + (int64_t)(v0 + t.srow[0]) * fb.lda, (int64_t)64 * fb.lda, fb.gamma,
-                                 klist + (int64_t)p * k_tiles, lo, hi, acc);
-            }
-            // first chunk of the pair: the full slab; a continuation: this block's tile behind it (GemmPlan::c_floats)
-            const bool cont = L != first_block[p];
-            tile_store(t, cont ? C + slab_stride + (int64_t)L * (256 * 256) : C, cont ? 256 : ldc, cont ? 0 : tm, cont ? 0 : tn, acc);
-        }
-        pos += u_hi - u_lo;
-        ++p;
-    }
+    });
 }
 
 // --------------------------------------------------------------------------- //
@@ -1073,77 +1015,42 @@ __device__ __forceinline__ void tile_run_split(const TileThread& t, float* lds, 
 // A: the belief block's split plane.  fb.mat == nullptr: every B tile is read from fp32 rows (the projected route); else
 // scheduler 2b's tiles (R = 1).
 template <int SCHED>
-__device__ __forceinline__ void gemm_split_streamk_body(
+__device__ __forceinline__ void gemm_split_streamk_body(const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb,
+                                                        FusedB fb, SlabOut out, StreamKView v) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    streamk_walk(v, out, [&](const TileThread& t, int p, int tm, int tn, int lo, int hi, auto& acc) {
+        const float* Ablk = A + (int64_t)tm * 256 * lda;
+        if (fb.mat == nullptr || fb.mat[tn]) {           // block-uniform: fp32 rows from B
+            const int bt = (fb.mat != nullptr && fb.ctile != nullptr) ? fb.ctile[tn] : tn;
+            tile_run_split<SCHED>(t, lds, Ablk, lda, B + (int64_t)bt * 256 * ldb, ldb, false, nullptr, nullptr, nullptr, 0,
+                                  0.f, v.klist + (int64_t)p * v.k_tiles, lo, hi, acc);
+        } else {
+            const int r0 = tn * 256;
+            const int g = r0 / fb.V, v0 = r0 - g * fb.V;
+            tile_run_split<SCHED>(t, lds, Ablk, lda, nullptr, 0, true, fb.rs + (int64_t)(g / fb.O) * fb.S_pad,
+                                  fb.rto + (int64_t)g * fb.S_pad, fb.alpha + (int64_t)(v0 + (threadIdx.x >> 2)) * fb.lda,
+                                  (int64_t)128 * fb.lda, fb.gamma, v.klist + (int64_t)p * v.k_tiles, lo, hi, acc);
+        }
+    });
+}
+
+__global__ __launch_bounds__(512) void k_gemm_split_streamk(
     const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb, FusedB fb, float* __restrict__ C, int ldc,
     int64_t slab_stride, int tiles_m, int pairs, int k_tiles, const int* __restrict__ klist, const int* __restrict__ kcount,
     const int* __restrict__ prefix, const int* __restrict__ start_pair, const int* __restrict__ first_block,
     const int* __restrict__ plan, int ovh) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int nb = gridDim.x;
-    int L;
-    {
-        const int bid = blockIdx.x, xcd = bid & 7, qq = nb >> 3, r = nb & 7;
-        const int base = (xcd < r) ? xcd * (qq + 1) : r * (qq + 1) + (xcd - r) * qq;
-        L = base + (bid >> 3);
-    }
-    const int q = plan[0], T = plan[1];
-    int64_t pos = (int64_t)L * q;
-    if (pos >= T) return;
-    const int64_t end = (pos + q < T) ? pos + q : T;
-    int p = start_pair[L];
-    if (p < 0) return;
-    TileThread t;
-    t.init();
-    while (pos < end && p < pairs) {
-        const int cnt = kcount[p];
-        if (cnt == 0) {                                  // block-uniform
-            ++p;
-            continue;
-        }
-        const int u_lo = (int)(pos - prefix[p]);
-        const int64_t room = end - pos;
-        const int u_hi = (u_lo + room < cnt + ovh) ? (int)(u_lo + room) : cnt + ovh;
-        const int lo = u_lo > ovh ? u_lo - ovh : 0;
-        const int hi = u_hi > ovh ? u_hi - ovh : 0;
-        if (hi > lo) {
-            const int tm = p % tiles_m, tn = p / tiles_m;
-            f32x16 acc[4][2];
-            tile_zero(acc);
-            const float* Ablk = A + (int64_t)tm * 256 * lda;
-            if (fb.mat == nullptr || fb.mat[tn]) {       // block-uniform: fp32 rows from B
-                const int bt = (fb.mat != nullptr && fb.ctile != nullptr) ? fb.ctile[tn] : tn;
-                tile_run_split<SCHED>(t, lds, Ablk, lda, B + (int64_t)bt * 256 * ldb, ldb, false, nullptr, nullptr, nullptr, 0,
-                                      0.f, klist + (int64_t)p * k_tiles, lo, hi, acc);
-            } else {
-                const int r0 = tn * 256;
-                const int g = r0 / fb.V, v0 = r0 - g * fb.V;
-                tile_run_split<SCHED>(t, lds, Ablk, lda, nullptr, 0, true, fb.rs + (int64_t)(g / fb.O) * fb.S_pad,
-                                      fb.rto + (int64_t)g * fb.S_pad, fb.alpha + (int64_t)(v0 + (threadIdx.x >> 2)) * fb.lda,
-                                      (int64_t)128 * fb.lda, fb.gamma, klist + (int64_t)p * k_tiles, lo, hi, acc);
-            }
-            const bool cont = L != first_block[p];
-            tile_store(t, cont ? C + slab_stride + (int64_t)L * (256 * 256) : C, cont ? 256 : ldc, cont ? 0 : tm, cont ? 0 : tn, acc);
-        }
-        pos += u_hi - u_lo;
-        ++p;
-    }
-}
-
-#define PBVI_SPLIT_KERNEL_ARGS                                                                                              \
-    const float *__restrict__ A, int lda, const float *__restrict__ B, int ldb, FusedB fb, float *__restrict__ C, int ldc,      \
-        int64_t slab_stride, int tiles_m, int pairs, int k_tiles, const int *__restrict__ klist,                               \
-        const int *__restrict__ kcount, const int *__restrict__ prefix, const int *__restrict__ start_pair,                    \
-        const int *__restrict__ first_block, const int *__restrict__ plan, int ovh
-__global__ __launch_bounds__(512) void k_gemm_split_streamk(PBVI_SPLIT_KERNEL_ARGS) {
-    gemm_split_streamk_body<SPLIT_SCHED_PARENT>(A, lda, B, ldb, fb, C, ldc, slab_stride, tiles_m, pairs, k_tiles, klist, kcount,
-                                                prefix, start_pair, first_block, plan, ovh);
+    gemm_split_streamk_body<SPLIT_SCHED_PARENT>(A, lda, B, ldb, fb, SlabOut{C, ldc, slab_stride},
+        StreamKView{klist, kcount, prefix, start_pair, first_block, plan, tiles_m, pairs, k_tiles, ovh});
 }
 // The pipelined K-step schedule on the same plan, lists and slabs (pbvi_debug_split_schedule)
-__global__ __launch_bounds__(512) void k_gemm_split_streamk_pipelined(PBVI_SPLIT_KERNEL_ARGS) {
-    gemm_split_streamk_body<SPLIT_SCHED_PIPELINED>(A, lda, B, ldb, fb, C, ldc, slab_stride, tiles_m, pairs, k_tiles, klist, kcount,
-                                                   prefix, start_pair, first_block, plan, ovh);
+__global__ __launch_bounds__(512) void k_gemm_split_streamk_pipelined(
+    const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb, FusedB fb, float* __restrict__ C, int ldc,
+    int64_t slab_stride, int tiles_m, int pairs, int k_tiles, const int* __restrict__ klist, const int* __restrict__ kcount,
+    const int* __restrict__ prefix, const int* __restrict__ start_pair, const int* __restrict__ first_block,
+    const int* __restrict__ plan, int ovh) {
+    gemm_split_streamk_body<SPLIT_SCHED_PIPELINED>(A, lda, B, ldb, fb, SlabOut{C, ldc, slab_stride},
+        StreamKView{klist, kcount, prefix, start_pair, first_block, plan, tiles_m, pairs, k_tiles, ovh});
 }
-#undef PBVI_SPLIT_KERNEL_ARGS
 
 // One wave: does the split path keep subnormal lo parts and subnormal products?  out[0] = 1 if
 //   x = (1 + 2^-7) 2^-120 + 2^-132 (a bf16-subnormal lo) times 1 comes back as x, and 2^-100 * 2^-30 as 2^-130.
@@ -1288,13 +1195,23 @@ __global__ void k_build_klists(const uint8_t* __restrict__ nzA, const uint8_t* _
     }
 }
 
-// Every K tile of every pair listed, zero or not (PBVI_GEMM_DENSE in the environment, or pbvi_debug_gemm_dense):
-// what BASELINE's "dense backup" configuration is measured with.  Results are unchanged (zero tiles add +0).
-static int g_force_dense = -1;
-int gemm_force_dense() {
-    if (g_force_dense < 0) g_force_dense = getenv("PBVI_GEMM_DENSE") ? (atoi(getenv("PBVI_GEMM_DENSE")) != 0) : 0;
-    return g_force_dense;
+// The process-wide environment knobs of the fp32 GEMM, read once
+struct GemmEnv {
+    int dense;        // PBVI_GEMM_DENSE=1: every K tile of every pair listed, zero or not (also pbvi_debug_gemm_dense): what
+                      // BASELINE's "dense backup" configuration is measured with.  Results are unchanged (zero tiles add +0).
+    int chunk;        // PBVI_GEMM_CHUNK=n: K chunk of the non-persistent scheduler, in tiles
+    int no_streamk;   // PBVI_GEMM_NO_STREAMK=1: the non-persistent scheduler for score GEMMs too
+    int ovh;          // PBVI_STREAMK_OVH=n: per-pair fixed cost of the stream-K plan, in tile-steps
+};
+static int env_int(const char* name, int dflt) { return getenv(name) ? atoi(getenv(name)) : dflt; }
+static const GemmEnv& gemm_env() {
+    static const GemmEnv env{env_int("PBVI_GEMM_DENSE", 0) != 0, env_int("PBVI_GEMM_CHUNK", 0), env_int("PBVI_GEMM_NO_STREAMK", 0),
+                             env_int("PBVI_STREAMK_OVH", 1)};
+    return env;
 }
+
+static int g_force_dense = -1;                     // set_gemm_force_dense overrides the environment
+int gemm_force_dense() { return g_force_dense < 0 ? gemm_env().dense : g_force_dense; }
 int set_gemm_force_dense(int enable) {
     const int prev = gemm_force_dense();
     g_force_dense = enable ? 1 : 0;
@@ -1311,10 +1228,7 @@ int set_gemm_split_schedule(int schedule) {
 }
 
 int choose_chunk_len(int tiles_mn, int k_tiles) {
-    if (const char* env = getenv("PBVI_GEMM_CHUNK")) {
-        const int v = atoi(env);
-        if (v > 0) return v < k_tiles ? v : k_tiles;
-    }
+    if (const int v = gemm_env().chunk; v > 0) return v < k_tiles ? v : k_tiles;
     const int64_t total = (int64_t)tiles_mn * k_tiles;
     int64_t len = total / (256 * 8);
     if (len < 8) len = 8;
@@ -1341,109 +1255,109 @@ hipError_t launch_tile_nonzero_f32(const float* X, int ld, int rows_pad, int k_t
     return hipGetLastError();
 }
 
+// The stream-K kernels: which one runs for (split, schedule, fused, R), and the dynamic LDS it needs.  ANY matches every
+// value; the first matching row counts.  set_lds_attr walks the same rows, so a kernel added here is also configured.
+using StreamKKernel = void (*)(const float*, int, const float*, int, FusedB, float*, int, int64_t, int, int, int, const int*,
+                               const int*, const int*, const int*, const int*, const int*, int);
+struct StreamKKernelRow {
+    int split, schedule, fused, R;
+    StreamKKernel kernel;
+    int lds_bytes;
+};
+constexpr int ANY = -1;
+static const StreamKKernelRow STREAMK_KERNELS[] = {
+    {1, SPLIT_SCHED_PARENT, ANY, ANY, k_gemm_split_streamk, GEMM_LDS_BYTES},
+    {1, SPLIT_SCHED_PIPELINED, ANY, ANY, k_gemm_split_streamk_pipelined, GEMM_LDS_BYTES},
+    {0, ANY, 0, ANY, k_gemm_nt_f32_streamk, GEMM_LDS_BYTES},
+    {0, ANY, 1, 1, k_gemm_nt_f32_streamk_fused, GEMM_LDS_BYTES},
+    {0, ANY, 1, 2, k_gemm_nt_f32_streamk_fused_r<2>, GEMM_LDS_BYTES_R},
+    {0, ANY, 1, 3, k_gemm_nt_f32_streamk_fused_r<3>, GEMM_LDS_BYTES_R},
+    {0, ANY, 1, 4, k_gemm_nt_f32_streamk_fused_r<4>, GEMM_LDS_BYTES_R},
+    {0, ANY, 1, 5, k_gemm_nt_f32_streamk_fused_r<5>, GEMM_LDS_BYTES_R},
+    {0, ANY, 1, 6, k_gemm_nt_f32_streamk_fused_r<6>, GEMM_LDS_BYTES_R},
+    {0, ANY, 1, 7, k_gemm_nt_f32_streamk_fused_r<7>, GEMM_LDS_BYTES_R},
+};
+// nullptr: no such kernel (a fused R outside 1..FUSED_R_MAX)
+static const StreamKKernelRow* streamk_kernel(int split, int schedule, int fused, int R) {
+    auto fits = [](int want, int have) { return want == ANY || want == have; };
+    for (const StreamKKernelRow& row : STREAMK_KERNELS)
+        if (fits(row.split, split) && fits(row.schedule, schedule) && fits(row.fused, fused) && fits(row.R, R)) return &row;
+    return nullptr;
+}
+
 static hipError_t set_lds_attr() {
     static bool done = false;
     if (done) return hipSuccess;
     hipError_t e = hipFuncSetAttribute((const void*)k_gemm_nt_f32_mfma, hipFuncAttributeMaxDynamicSharedMemorySize,
                                        GEMM_LDS_BYTES);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute((const void*)k_gemm_nt_f32_streamk, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            GEMM_LDS_BYTES);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute((const void*)k_gemm_nt_f32_streamk_fused, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            GEMM_LDS_BYTES);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute((const void*)k_gemm_split_streamk, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute((const void*)k_gemm_split_streamk_pipelined, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
-    if (e != hipSuccess) return e;
-#define PBVI_FUSED_R_ATTR(RR)                                                                                          \
-    e = hipFuncSetAttribute((const void*)k_gemm_nt_f32_streamk_fused_r<RR>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                            GEMM_LDS_BYTES_R);                                                                          \
-    if (e != hipSuccess) return e;
-    PBVI_FUSED_R_ATTR(2) PBVI_FUSED_R_ATTR(3) PBVI_FUSED_R_ATTR(4) PBVI_FUSED_R_ATTR(5) PBVI_FUSED_R_ATTR(6) PBVI_FUSED_R_ATTR(7)
-#undef PBVI_FUSED_R_ATTR
-    done = true;
-    return hipSuccess;
+    for (const StreamKKernelRow& row : STREAMK_KERNELS)
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)row.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, row.lds_bytes);
+    done = e == hipSuccess;
+    return e;
 }
 
-hipError_t launch_gemm_nt_f32(const float* A, int lda, const float* B, int ldb, float* C, const GemmPlan& pl,
-                              const uint8_t* nzA, const uint8_t* nzB, int G, int v_group, int n_rows, int* klist,
-                              int* kcount, int* nchunks, hipStream_t stream, int batch, int64_t batch_stride_b,
-                              int64_t batch_stride_c, int* streamk_ws, hipStream_t list_stream, hipEvent_t list_event,
-                              hipEvent_t ev_before, hipEvent_t ev_after, const FusedB* fused, int split) {
-    hipError_t e = set_lds_attr();
-    if (e != hipSuccess) return e;
+// The tile lists (and, for stream-K, the plan) depend on the zero maps only, not on the operands' values.
+static hipError_t build_klists(const GemmArgs& a, int batch, const FusedB* fused, hipStream_t ls) {
     if (batch < 1 || batch > 65535) return hipErrorInvalidValue;
-    const int pairs = pl.tiles_m * pl.tiles_n;
-    const int force_dense = gemm_force_dense();          // benchmark / debug: list every tile (a true-dense GEMM)
-    // The tile lists and the stream-K plan depend on the zero maps only, not on the operands' values: with a
-    // list_stream they are built beside whatever `stream` is still doing (the Gamma projection) and the GEMM waits.
-    hipStream_t ls = (list_stream != nullptr && list_event != nullptr) ? list_stream : stream;
-    if (fused != nullptr && !pl.streamk) return hipErrorInvalidValue;
-    if (split && (!pl.streamk || (fused != nullptr && fused->R != 1))) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_build_klists, dim3(pairs, batch), dim3(256), 0, ls, nzA, nzB, G, v_group, n_rows,
-                       pl.tiles_m, pl.k_tiles, pl.chunk_len, force_dense, klist, kcount, nchunks,
+    const GemmPlan& pl = a.plan;
+    hipLaunchKernelGGL(k_build_klists, dim3(pl.tiles_m * pl.tiles_n, batch), dim3(256), 0, ls, a.nzA, a.nzB, a.G, a.v_group,
+                       a.n_rows, pl.tiles_m, pl.k_tiles, pl.chunk_len, gemm_force_dense(), a.klist, a.kcount, a.nchunks,
                        fused != nullptr ? fused->irr : nullptr, fused != nullptr ? fused->O : 1);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if (pl.streamk) {
-        if (batch != 1 || streamk_ws == nullptr) return hipErrorInvalidValue;
-        int* prefix = streamk_ws;                        // [pairs+1]
-        int* start_pair = prefix + pairs + 1;            // [nblocks]
-        int* first_block = start_pair + pl.nblocks;      // [pairs]
-        int* plan = first_block + pairs;                 // [2]
-        static const int ovh = getenv("PBVI_STREAMK_OVH") ? atoi(getenv("PBVI_STREAMK_OVH")) : 1;   // per-pair fixed cost, in tile-steps
-        hipLaunchKernelGGL(k_streamk_plan, dim3(1), dim3(256), 0, ls, kcount, pairs, pl.nblocks, pl.k_tiles,
-                           pl.max_chunks - 1, ovh, prefix, start_pair, first_block, nchunks, plan);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        if (ls != stream) {
-            if ((e = hipEventRecord(list_event, ls)) != hipSuccess) return e;
-            if ((e = hipStreamWaitEvent(stream, list_event, 0)) != hipSuccess) return e;
-        }
-        if (split) {
-            FusedB fb{};
-            if (fused != nullptr) fb = *fused;           // (else fb.mat == nullptr: every B tile from fp32 rows)
-            hipLaunchKernelGGL(g_split_schedule == SPLIT_SCHED_PIPELINED ? k_gemm_split_streamk_pipelined : k_gemm_split_streamk,
-                               dim3(pl.nblocks), dim3(512), GEMM_LDS_BYTES, stream, A, lda, B, ldb, fb, C, pl.ldc, pl.slab_stride,
-                               pl.tiles_m, pairs, pl.k_tiles, klist, kcount, prefix, start_pair, first_block, plan, ovh);
-        } else if (fused != nullptr && fused->R > 1) {
-            switch (fused->R) {
-#define PBVI_FUSED_R_CASE(RR)                                                                                                   \
-    case RR:                                                                                                                    \
-        hipLaunchKernelGGL(k_gemm_nt_f32_streamk_fused_r<RR>, dim3(pl.nblocks), dim3(512), GEMM_LDS_BYTES_R, stream, A, lda, B, \
-                           ldb, *fused, C, pl.ldc, pl.slab_stride, pl.tiles_m, pairs, pl.k_tiles, klist, kcount, prefix,        \
-                           start_pair, first_block, plan, ovh);                                                                 \
-        break;
-                PBVI_FUSED_R_CASE(2) PBVI_FUSED_R_CASE(3) PBVI_FUSED_R_CASE(4) PBVI_FUSED_R_CASE(5) PBVI_FUSED_R_CASE(6) PBVI_FUSED_R_CASE(7)
-#undef PBVI_FUSED_R_CASE
-                default:
-                    return hipErrorInvalidValue;
-            }
-        } else if (fused != nullptr)
-            hipLaunchKernelGGL(k_gemm_nt_f32_streamk_fused, dim3(pl.nblocks), dim3(512), GEMM_LDS_BYTES, stream, A, lda, B, ldb,
-                               *fused, C, pl.ldc, pl.slab_stride, pl.tiles_m, pairs, pl.k_tiles, klist, kcount, prefix, start_pair,
-                               first_block, plan, ovh);
-        else
-            hipLaunchKernelGGL(k_gemm_nt_f32_streamk, dim3(pl.nblocks), dim3(512), GEMM_LDS_BYTES, stream, A, lda, B, ldb, C,
-                               pl.ldc, pl.slab_stride, pl.tiles_m, pairs, pl.k_tiles, klist, kcount, prefix, start_pair,
-                               first_block, plan, ovh);
-        return hipGetLastError();
-    }
-    if (ls != stream) {
-        if ((e = hipEventRecord(list_event, ls)) != hipSuccess) return e;
-        if ((e = hipStreamWaitEvent(stream, list_event, 0)) != hipSuccess) return e;
-    }
+    return hipGetLastError();
+}
+
+// scheduler 1 over built lists
+static hipError_t launch_mfma(const GemmArgs& a, int batch, int64_t batch_stride_b, int64_t batch_stride_c) {
+    const GemmPlan& pl = a.plan;
     const int64_t groups = ((int64_t)pl.tiles_n * pl.max_chunks + 7) / 8 * 8;
     const int64_t total = groups * pl.tiles_m;
     if (total <= 0 || total > 0x7fffffff) return hipErrorInvalidValue;
-    if (ev_before != nullptr && (e = hipEventRecord(ev_before, stream)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_gemm_nt_f32_mfma, dim3((unsigned)total, batch), dim3(512), GEMM_LDS_BYTES, stream, A, lda, B,
-                       ldb, C, pl.ldc, pl.slab_stride, pl.tiles_m, pl.tiles_n, pl.k_tiles, pl.chunk_len, pl.max_chunks,
-                       klist, kcount, batch_stride_b, batch_stride_c);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (ev_after != nullptr && (e = hipEventRecord(ev_after, stream)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_gemm_nt_f32_mfma, dim3((unsigned)total, batch), dim3(512), GEMM_LDS_BYTES, a.stream, a.A, a.lda, a.B,
+                       a.ldb, a.C, pl.ldc, pl.slab_stride, pl.tiles_m, pl.tiles_n, pl.k_tiles, pl.chunk_len, pl.max_chunks,
+                       a.klist, a.kcount, batch_stride_b, batch_stride_c);
+    return hipGetLastError();
+}
+
+hipError_t launch_score_gemm_f32(const ScoreGemmArgs& a) {
+    hipError_t e = set_lds_attr();
+    if (e != hipSuccess) return e;
+    const GemmPlan& pl = a.plan;
+    const int fused_R = a.fused != nullptr ? a.fused->R : 1;
+    if (pl.streamk ? a.streamk_ws == nullptr : (a.fused != nullptr || a.split)) return hipErrorInvalidValue;
+    if (a.split && fused_R != 1) return hipErrorInvalidValue;
+    // With a list stream the lists and the plan are built beside whatever `stream` is still doing (the Gamma projection)
+    // and the GEMM waits for them.
+    hipStream_t ls = (a.list_stream != nullptr && a.list_event != nullptr) ? a.list_stream : a.stream;
+    if ((e = build_klists(a, 1, a.fused, ls)) != hipSuccess) return e;
+    const int pairs = pl.tiles_m * pl.tiles_n, ovh = gemm_env().ovh;
+    const StreamKWorkspace ws = streamk_workspace(pl, a.streamk_ws);
+    if (pl.streamk) {
+        hipLaunchKernelGGL(k_streamk_plan, dim3(1), dim3(256), 0, ls, a.kcount, pairs, pl.nblocks, pl.k_tiles, pl.max_chunks - 1,
+                           ovh, ws.prefix, ws.start_pair, ws.first_block, a.nchunks, ws.plan);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    if (ls != a.stream) {
+        if ((e = hipEventRecord(a.list_event, ls)) != hipSuccess) return e;
+        if ((e = hipStreamWaitEvent(a.stream, a.list_event, 0)) != hipSuccess) return e;
+    }
+    if (!pl.streamk) return launch_mfma(a, 1, 0, 0);
+    const StreamKKernelRow* row = streamk_kernel(a.split ? 1 : 0, g_split_schedule, a.fused != nullptr, fused_R);
+    if (row == nullptr) return hipErrorInvalidValue;
+    const FusedB fb = a.fused != nullptr ? *a.fused : FusedB{};   // (no fused: fb.mat == nullptr, every B tile from fp32 rows)
+    hipLaunchKernelGGL(row->kernel, dim3(pl.nblocks), dim3(512), row->lds_bytes, a.stream, a.A, a.lda, a.B, a.ldb, fb, a.C, pl.ldc,
+                       pl.slab_stride, pl.tiles_m, pairs, pl.k_tiles, a.klist, a.kcount, ws.prefix, ws.start_pair, ws.first_block,
+                       ws.plan, ovh);
+    return hipGetLastError();
+}
+
+hipError_t launch_batched_gemm_f32(const BatchedGemmArgs& a) {
+    hipError_t e = set_lds_attr();
+    if (e != hipSuccess) return e;
+    if (a.plan.streamk) return hipErrorInvalidValue;
+    if ((e = build_klists(a, a.batch, nullptr, a.stream)) != hipSuccess) return e;
+    if (a.ev_before != nullptr && (e = hipEventRecord(a.ev_before, a.stream)) != hipSuccess) return e;
+    if ((e = launch_mfma(a, a.batch, a.batch_stride_b, a.batch_stride_c)) != hipSuccess) return e;
+    if (a.ev_after != nullptr && (e = hipEventRecord(a.ev_after, a.stream)) != hipSuccess) return e;
     return hipSuccess;
 }
 
@@ -1454,8 +1368,7 @@ GemmPlan make_gemm_plan(int M_pad, int N_pad, int K_pad, bool single_chunk) {
     pl.k_tiles = K_pad / GEMM_BK;
     pl.ldc = N_pad;
     pl.slab_stride = (int64_t)M_pad * N_pad;
-    static const int no_streamk = getenv("PBVI_GEMM_NO_STREAMK") ? atoi(getenv("PBVI_GEMM_NO_STREAMK")) : 0;
-    pl.streamk = !single_chunk && !no_streamk;
+    pl.streamk = !single_chunk && !gemm_env().no_streamk;
     pl.nblocks = device_cu_count();
     if (single_chunk) {
         pl.chunk_len = pl.k_tiles;
@@ -1473,11 +1386,6 @@ GemmPlan make_gemm_plan(int M_pad, int N_pad, int K_pad, bool single_chunk) {
     }
     pl.c_floats = (int64_t)pl.max_chunks * pl.slab_stride;
     return pl;
-}
-
-size_t streamk_workspace_ints(const GemmPlan& pl) {
-    const size_t pairs = (size_t)pl.tiles_m * pl.tiles_n;
-    return (pairs + 1) + (size_t)pl.nblocks + pairs + 2;
 }
 
 // --------------------------------------------------------------------------- //

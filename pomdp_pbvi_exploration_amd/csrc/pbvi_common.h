@@ -39,7 +39,28 @@ struct GemmPlan {
 int set_gemm_force_dense(int enable);   // returns the previous setting (see gemm.hip)
 int set_gemm_split_schedule(int schedule);   // K-step schedule of the split score GEMM: 0 parent (default), 1 pipelined; returns the previous one
 int gemm_force_dense();
-size_t streamk_workspace_ints(const GemmPlan& pl);   // ints of device workspace the stream-K plan needs
+// Device workspace of the stream-K plan (k_streamk_plan), laid out here and nowhere else:
+//   prefix[pairs + 1] | start_pair[nblocks] | first_block[pairs] | plan[2] = {cost units per block, total cost units}
+struct StreamKWorkspace {
+    int *prefix, *start_pair, *first_block, *plan;
+};
+inline StreamKWorkspace streamk_workspace(const GemmPlan& pl, int* ws, size_t* ints = nullptr) {
+    const size_t pairs = (size_t)pl.tiles_m * pl.tiles_n;
+    size_t off = 0;
+    auto take = [&](size_t n) {
+        int* p = ws != nullptr ? ws + off : nullptr;
+        off += n;
+        return p;
+    };
+    const StreamKWorkspace w{take(pairs + 1), take((size_t)pl.nblocks), take(pairs), take(2)};
+    if (ints != nullptr) *ints = off;
+    return w;
+}
+inline size_t streamk_workspace_ints(const GemmPlan& pl) {   // ints of device workspace the stream-K plan needs
+    size_t n = 0;
+    streamk_workspace(pl, nullptr, &n);
+    return n;
+}
 // B operand generated inside the stream-K GEMM instead of read from HBM (gemm.hip, "scheduler 2b"): row (g, v) of an
 // n-tile with mat[tile] == 0 -- all of whose 256 rows belong to one group g -- is gamma * rto[g][s] * alpha[v][rs[g / O][s]]
 // (one reachable state per (s, a)); tiles with mat[tile] != 0 are read from B as usual.
@@ -60,23 +81,44 @@ struct FusedB {
 // single_chunk: one K chunk per pair, i.e. slab 0 is the finished product (no split-K).
 GemmPlan make_gemm_plan(int M_pad, int N_pad, int K_pad, bool single_chunk = false);
 hipError_t launch_tile_nonzero_f32(const float* X, int ld, int rows_pad, int k_tiles, uint8_t* nz, hipStream_t stream);
-// nzB: G > 0 -> per row group [G][k_tiles]; G == 0 -> per n-tile [batch][tiles_n][k_tiles]; nullptr -> dense.
-// batch > 1 runs `batch` GEMMs sharing A (B, C and the tile lists advance by the batch strides).
-hipError_t launch_gemm_nt_f32(const float* A, int lda, const float* B, int ldb, float* C, const GemmPlan& pl,
-                              const uint8_t* nzA, const uint8_t* nzB, int G, int v_group, int n_rows, int* klist,
-                              int* kcount, int* nchunks, hipStream_t stream, int batch = 1,
-                              int64_t batch_stride_b = 0, int64_t batch_stride_c = 0, int* streamk_ws = nullptr,
-                              hipStream_t list_stream = nullptr, hipEvent_t list_event = nullptr,
-                              hipEvent_t ev_before = nullptr, hipEvent_t ev_after = nullptr,   // around the GEMM kernel (non-stream-K)
-                              const FusedB* fused = nullptr, int split = 0);
-// split: bf16 MFMAs on the three-term operand split (gemm.hip, scheduler 2d; stream-K only, fused R = 1 or none).  A is
-// then the split plane of the A rows (split_bf16.h), not their fp32 values; nzA still describes the fp32 rows.
-// gemm_split_supported(device): 1 when that path keeps subnormal lo parts and products on the device (probed once each).
+// What both launches of the fp32 GEMM take.  nzB: G > 0 -> per row group [G][k_tiles]; G == 0 -> per n-tile
+// [batch][tiles_n][k_tiles]; nullptr -> dense.
+struct GemmArgs {
+    const float* A = nullptr;
+    int lda = 0;
+    const float* B = nullptr;
+    int ldb = 0;
+    float* C = nullptr;
+    GemmPlan plan{};
+    const uint8_t* nzA = nullptr;
+    const uint8_t* nzB = nullptr;
+    int G = 0, v_group = 0, n_rows = 0;
+    int *klist = nullptr, *kcount = nullptr, *nchunks = nullptr;
+    hipStream_t stream = nullptr;
+};
+// A score GEMM: stream-K, or one block per (pair, chunk) when the plan says so (then neither fused nor split).
+struct ScoreGemmArgs : GemmArgs {
+    int* streamk_ws = nullptr;            // streamk_workspace_ints(plan) ints (stream-K plans)
+    // build the tile lists / stream-K plan on that stream (they need the zero maps only) and make `stream` wait for them
+    // before the GEMM kernel; both or neither
+    hipStream_t list_stream = nullptr;
+    hipEvent_t list_event = nullptr;
+    // generate the B tiles that lie inside one row group (stream-K only); the others are read from B
+    const FusedB* fused = nullptr;
+    // bf16 MFMAs on the three-term operand split (gemm.hip, scheduler 2d; stream-K only, fused R = 1 or none).  A is then
+    // the split plane of the A rows (split_bf16.h), not their fp32 values; nzA still describes the fp32 rows.
+    int split = 0;
+};
+hipError_t launch_score_gemm_f32(const ScoreGemmArgs& a);
+// `batch` single-chunk GEMMs sharing A (B, C and the tile lists advance by the batch strides): the dense projection.
+struct BatchedGemmArgs : GemmArgs {
+    int batch = 1;
+    int64_t batch_stride_b = 0, batch_stride_c = 0;
+    hipEvent_t ev_before = nullptr, ev_after = nullptr;   // recorded around the GEMM kernel
+};
+hipError_t launch_batched_gemm_f32(const BatchedGemmArgs& a);
+// gemm_split_supported(device): 1 when the split path keeps subnormal lo parts and products on the device (probed once each).
 int gemm_split_supported(int device);
-// fused: generate the B tiles that lie inside one row group (stream-K only); the others are read from B.
-// list_stream + list_event: build the tile lists / stream-K plan on that stream (they need the zero maps only) and
-// make `stream` wait for them before the GEMM kernel.
-// streamk_ws layout: prefix[pairs+1], start_pair[nblocks], first_block[pairs], plan[2] = {steps per block, total steps}
 // fp64 MFMA GEMM (gemm_f64.hip): C[M][N] = A[M][K_pad] * B[N][K_pad]^T, one dense result slab, zero-tile lists
 // built from 32-column maps: nzA [ceil(M/256)][K_pad/32] (or nullptr), nzB [G+1][K_pad/32] per row group (or nullptr).
 // klist: gemm_f64_klist_ints(M, N, K_pad/32) ints, kcount: gemm_f64_kcount_ints(...) ints of device workspace (the

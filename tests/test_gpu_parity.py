@@ -14,6 +14,7 @@ from model_cases import assert_backup_matches_oracle, random_case as _random_cas
 from oracle import pbvi_oracle as orc
 from pomdp_pbvi_exploration_amd import (Belief, BeliefSet, PBVI_Solver, ValueFunction, load_POMDP_file, synth)
 from pomdp_pbvi_exploration_amd.engine import Engine
+from score_cases import shifted_model
 
 pytestmark = pytest.mark.gpu
 
@@ -1131,19 +1132,7 @@ def test_fused_projection_with_several_reachable_states(S, A, O, R, V, B):
     projected and read, so generated and read K steps alternate inside one tile list -- and zero-probability pad slots as
     the reference's Model pads them (src/mdp.py:308-335)."""
     rng = np.random.default_rng(S + V + R)
-    shifts = rng.integers(-40, 41, size=(A, R))
-    rs = (np.arange(S)[:, None, None] + shifts[None]) % S
-    odd = rng.random((S // 4 + 1, A, R)) < 0.003                      # some 4-state chunks lose their regularity
-    odd = np.repeat(odd, 4, axis=0)[:S]
-    rs = np.where(odd, rng.integers(0, S, size=(S, A, R)), rs).astype(np.int64)
-    p = rng.random((S, A, O, R))
-    p[rng.random((S, A, O, R)) < 0.3] = 0.0
-    p[:, :, 0, 0] += 1e-3
-    pad = rng.random((S, A)) < 0.1                                      # (s, a) with fewer than R successors
-    p[pad, :, R - 1] = 0.0
-    rs[pad, R - 1] = 0
-    rto = (p / p.sum(axis=(2, 3), keepdims=True)).astype(np.float32).astype(np.float64)
-    er = rng.normal(size=(S, A)).astype(np.float32).astype(np.float64)
+    rs, rto, er = shifted_model(rng, S, A, O, R)
     alpha = rng.normal(scale=4.0, size=(V, S)).astype(np.float32).astype(np.float64)
     b = rng.random((B, S)) * (rng.random((B, S)) < 0.2)
     b[:, rng.integers(0, S, size=B)] += 1e-3

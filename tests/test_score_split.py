@@ -10,24 +10,12 @@ from conftest import GOLDEN
 from oracle import pbvi_oracle as orc
 from pomdp_pbvi_exploration_amd import synth
 from pomdp_pbvi_exploration_amd.engine import Engine
+from score_cases import random_model
 
 pytestmark = pytest.mark.gpu
 
 FUSION_ALLOWED = os.environ.get('PBVI_NO_FUSED_PROJECT') is None
 F32_RTOL = 2e-5
-
-
-def random_model(rng, S, A, O, regular):
-    if regular:
-        rs = ((np.arange(S)[:, None] + rng.integers(-5, 6, size=A)[None, :]) % S)[:, :, None].astype(np.int64)
-    else:
-        rs = rng.integers(0, S, size=(S, A, 1))
-    p = rng.random((S, A, O))
-    p[rng.random((S, A, O)) < 0.3] = 0.0
-    p[:, :, 0] += 1e-3
-    rto = (p / p.sum(axis=2, keepdims=True))[:, :, :, None].astype(np.float32).astype(np.float64)
-    er = rng.normal(size=(S, A)).astype(np.float32).astype(np.float64)
-    return rs, rto, er
 
 
 def beliefs(rng, B, S, density=0.2):

@@ -7,32 +7,11 @@ import numpy as np
 import pytest
 
 from pomdp_pbvi_exploration_amd.engine import Engine, debug_split_schedule
+from score_cases import beliefs, random_model
 
 pytestmark = pytest.mark.gpu
 
 COUNTERS = ('n_refined', 'n_refine_candidates', 'n_refined_actions', 'n_unique', 'score_tiles_run')
-
-
-def random_model(rng, S, A, O, regular):
-    if regular:
-        rs = ((np.arange(S)[:, None] + rng.integers(-5, 6, size=A)[None, :]) % S)[:, :, None].astype(np.int64)
-    else:
-        rs = rng.integers(0, S, size=(S, A, 1))
-    p = rng.random((S, A, O))
-    p[rng.random((S, A, O)) < 0.3] = 0.0
-    p[:, :, 0] += 1e-3
-    rto = (p / p.sum(axis=2, keepdims=True))[:, :, :, None].astype(np.float32).astype(np.float64)
-    er = rng.normal(size=(S, A)).astype(np.float32).astype(np.float64)
-    return rs, rto, er
-
-
-def beliefs(rng, B, S, density=0.2, support=None):
-    """Random sparse beliefs; support: only the first `support` states may be non-zero."""
-    n = S if support is None else support
-    b = np.zeros((B, S))
-    b[:, :n] = rng.random((B, n)) * (rng.random((B, n)) < density)
-    b[np.arange(B), rng.integers(0, n, size=B)] += 1e-3
-    return (b / b.sum(axis=1, keepdims=True)).astype(np.float32).astype(np.float64)
 
 
 FILL = 0xA5
