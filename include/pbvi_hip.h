@@ -721,7 +721,8 @@ int pbvi_debug_slabs_fill(pbvi_engine_t* e, int byte);
  * An fp64 engine behind its fp32 screen captures the screen's stage (the one whose window decides what is re-decided); a
  * pure fp64 engine its own: E = 0, no queue.  The buffers are working buffers of the engine (pbvi_device_bytes,
  * pbvi_debug_alloc_limit, released by pbvi_engine_after_oom and by disabling the probe).  A backup with
- * B * G * V > 2^24 fails with PBVI_EINVAL while the probe is on.  The value-max, Q-value and infotaxis GEMMs are not covered.
+ * B * G * V > 2^24 fails with PBVI_EINVAL while the probe is on.  The Q-value and infotaxis GEMMs are not covered; the value-max
+ * GEMMs are pinned from their results (tests/test_value_max.py) and report their route through pbvi_debug_value_max_route.
  * pbvi_debug_score_probe_fetch copies the last capture to host arrays; any pointer may be NULL (call it with dims alone
  * to size the rest).  PBVI_EINVAL when nothing was captured since the probe was enabled.
  */
@@ -740,6 +741,18 @@ int pbvi_debug_score_probe_fetch(pbvi_engine_t* e, int64_t* dims, double* scalar
  * next call that refines.  PBVI_EINVAL before the first such pass or once its work list has been released.
  */
 int pbvi_debug_refine_counts(pbvi_engine_t* e, int64_t out[8]);
+/*
+ * Tests only: the route of the engine's most recent value-max GEMM (pbvi_value_max, or the last 32768-row window of
+ * pbvi_value_max_store), so that a test can tell which kernels ran:
+ *   out[0]  route: 1 = fp32 skinny tile (fp64 accumulation, no window), 2 = fp32 score GEMM with every belief re-scored
+ *           in fp64, 3 = fp32 score GEMM as it is (pbvi_set_value_max_exact(0)), 4 = fp64 MFMA GEMM, 5 = fp64 plain kernel
+ *   out[1]  column-tile width of that GEMM (16 / 32 / 48 / 64 / 128; 256 for the fp32 score GEMM; 0 for the plain kernel)
+ *   out[2]  K parts of the fp64 tile engine (routes 1, 4; 1 for the plain kernel; 0 for the fp32 score GEMM's stream-K walk)
+ *   out[3]  belief rows and out[4] alpha rows of that call, out[5] its tile pairs (0 for the plain kernel)
+ *   out[6]  value-max GEMMs run since the engine was created (one per window of a store call), out[7] 0
+ * Host words only: nothing is read from or kept on the device.  PBVI_EINVAL before the first value-max call.
+ */
+int pbvi_debug_value_max_route(pbvi_engine_t* e, int64_t out[8]);
 
 /* Bytes of device memory currently held by the handle. */
 int64_t pbvi_device_bytes(const pbvi_engine_t* e);

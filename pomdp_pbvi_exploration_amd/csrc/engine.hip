@@ -923,6 +923,7 @@ class EngineBase {
     virtual int debug_slabs_fill(int byte) = 0;
     virtual int debug_score_probe(int enable) = 0;
     virtual int debug_refine_counts(int64_t* out) = 0;
+    virtual int debug_value_max_route(int64_t* out) = 0;
     virtual int debug_score_probe_fetch(int64_t* dims, double* scalars, double* score, double* mag, double* err,
                                         int32_t* best_v, double* best_score, int32_t* queue, uint8_t* dead, int32_t* perm) = 0;
     // source: the policy of the step loop (RolloutSource); alpha_actions and gamma are read by the sources that need them
@@ -1147,6 +1148,9 @@ class EngineT : public EngineBase {
     bool last_deferred_nothing_ = false;                     // (the first backup of an engine reads the counts mid-pipeline)
     RefineWork last_work_;                                   // the work list of the most recent refinement pass ...
     bool have_last_work_ = false;                            // ... if there was one (pbvi_debug_refine_counts)
+    // what the most recent value_max_device did (pbvi_debug_value_max_route): route, column-tile width, K parts, rows,
+    // alpha rows, tile pairs; [6] counts the runs since the engine was created
+    int64_t vmax_route_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     bool owns_streams_ = true;                               // false: a screen running on its fp64 engine's streams
     EngineT<float>* screen_ = nullptr;                       // fp64 engines: the fp32 screen (see ensure_screen)
     std::vector<int32_t> h_reach_ref_;                       // fp64 engines: the tables in the reference's layout, kept
@@ -2021,6 +2025,14 @@ class EngineT : public EngineBase {
         out[5] = w.w_slot_cap;
         out[6] = w.q2_cap;
         out[7] = w.defer_min;
+        return PBVI_OK;
+    }
+
+    // The route of the most recent value_max_device (pbvi_debug_value_max_route): host words only, nothing on the device.
+    int debug_value_max_route(int64_t* out) override {
+        if (!out) FAIL(PBVI_EINVAL, "debug_value_max_route: out is NULL");
+        if (vmax_route_[6] == 0) FAIL(PBVI_EINVAL, "debug_value_max_route: no value-max has run");
+        for (int i = 0; i < 8; ++i) out[i] = vmax_route_[i];
         return PBVI_OK;
     }
 
@@ -3398,6 +3410,15 @@ class EngineT : public EngineBase {
 
     // exact (f64-refined) max_v b.alpha_v of the resident blocks into bs2_/bv2_
     int value_max_device();
+    void note_vmax_route(int route, int bn, int k_parts, int64_t pairs) {
+        vmax_route_[0] = route;
+        vmax_route_[1] = bn;
+        vmax_route_[2] = k_parts;
+        vmax_route_[3] = B_;
+        vmax_route_[4] = V_;
+        vmax_route_[5] = pairs;
+        vmax_route_[6] += 1;
+    }
 
     int value_max(double* out_value, int32_t* out_index) override {
         if (V_ <= 0 || B_ <= 0) FAIL(PBVI_EINVAL, "value_max: need a resident alpha set and belief block");
@@ -3903,6 +3924,7 @@ int EngineT<T>::value_max_device() {
             const SlabView<double> svd = SlabView<double>::single(slabs_.as<double>(), (int)V_);   // K parts folded into the first slab by the launcher
             HIPCHK(launch_argmax<double>(svd, (int)V_, 1, (int)B_, nullptr, 0.0, 0.0, nullptr, 0, bv2_.as<int32_t>(),
                                          bs2_.as<double>(), err2_.as<double>(), nullptr, qc, stream_));
+            note_vmax_route(1, gemm_f64_bn((int)V_), split, (int64_t)gemm_f64_pairs((int)B_, (int)V_));
             return PBVI_OK;
         }
     }
@@ -3924,6 +3946,10 @@ int EngineT<T>::value_max_device() {
                                 alpha_.as<T>(), S_pad_, view(), 0.0, btl_.as<int32_t>(), btc_.as<int32_t>(), nullptr,
                                 bv2_.as<int32_t>(), bs2_.as<double>(), err2_.as<double>(), nullptr, work, stream_));
     }
+    if constexpr (kF32)
+        note_vmax_route(rescore ? 2 : 3, GEMM_BN, 0, (int64_t)plan_.tiles_m * plan_.tiles_n);
+    else
+        note_vmax_route(f64_pairs_ > 0 ? 4 : 5, f64_pairs_ > 0 ? gemm_f64_bn((int)Vt) : 0, f64_split_, f64_pairs_);
     return PBVI_OK;
 }
 
@@ -4846,6 +4872,10 @@ int pbvi_debug_score_probe(pbvi_engine_t* e, int enable) {
 int pbvi_debug_refine_counts(pbvi_engine_t* e, int64_t out[8]) {
     NEED(e);
     return e->impl->debug_refine_counts(out);
+}
+int pbvi_debug_value_max_route(pbvi_engine_t* e, int64_t out[8]) {
+    NEED(e);
+    return e->impl->debug_value_max_route(out);
 }
 int pbvi_debug_score_probe_fetch(pbvi_engine_t* e, int64_t* dims, double* scalars, double* score, double* mag, double* err,
                                  int32_t* best_v, double* best_score, int32_t* queue, uint8_t* dead, int32_t* perm) {

@@ -37,7 +37,7 @@ EXPORTS = [
     'pbvi_set_gamma_tiling', 'pbvi_gamma_tiling_plan', 'pbvi_q_values', 'pbvi_prune_dominated_masked',
     'pbvi_rollout', 'pbvi_infotaxis', 'pbvi_rollout_infotaxis', 'pbvi_debug_split_schedule', 'pbvi_debug_slabs',
     'pbvi_debug_slabs_fill', 'pbvi_env_set_frames', 'pbvi_env_set_table', 'pbvi_env_clear', 'pbvi_rollout_env',
-    'pbvi_debug_score_probe', 'pbvi_debug_score_probe_fetch', 'pbvi_debug_refine_counts',
+    'pbvi_debug_score_probe', 'pbvi_debug_score_probe_fetch', 'pbvi_debug_refine_counts', 'pbvi_debug_value_max_route',
 ]
 
 
@@ -103,6 +103,7 @@ def load_library(path: str = LIB_PATH):
         'pbvi_debug_score_probe': (C.c_int, [vp, C.c_int]),
         'pbvi_debug_score_probe_fetch': (C.c_int, [vp] + [vp] * 10),
         'pbvi_debug_refine_counts': (C.c_int, [vp, vp]),
+        'pbvi_debug_value_max_route': (C.c_int, [vp, vp]),
         'pbvi_backup_store_unique': (C.c_int64, [vp, i32p, C.c_int64]),
         'pbvi_backup_device_results': (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
         'pbvi_backup': (C.c_int, [vp, vp, C.c_int64, C.c_double, C.c_int, vp, i32p, i32p, u8p, sp]),
@@ -1367,6 +1368,19 @@ class Engine:
         self._ck(self._lib.pbvi_debug_refine_counts(self._h, _ptr(out)))
         names = ('items', 'slots', 'q2', 'item_cap', 'slot_cap', 'w_slot_cap', 'q2_cap', 'defer_min')
         return {k: int(v) for k, v in zip(names, out)}
+
+    _VMAX_ROUTES = ('none', 'f32_skinny', 'f32_wide_exact', 'f32_wide_fast', 'f64_mfma', 'f64_plain')
+
+    def debug_value_max_route(self) -> dict:
+        """Tests only: what the most recent value-max GEMM ran as (``pbvi_debug_value_max_route``): ``route`` (one of
+        ``_VMAX_ROUTES``), ``bn`` (column-tile width), ``k_parts``, ``rows`` / ``alpha_rows`` / ``pairs`` of that call
+        (the last window of a store call) and ``calls``, the value-max GEMMs run since the engine was created."""
+        out = np.zeros(8, dtype=np.int64)
+        self._ck(self._lib.pbvi_debug_value_max_route(self._h, _ptr(out)))
+        names = ('route', 'bn', 'k_parts', 'rows', 'alpha_rows', 'pairs', 'calls')
+        d = {k: int(v) for k, v in zip(names, out)}
+        d['route'] = self._VMAX_ROUTES[d['route']]
+        return d
 
     def set_gamma_tiling(self, mode: str = 'off', chunk_rows: int = 0) -> None:
         """Alpha-side backups whose Gamma is projected into HBM (R > 1, fp64 scoring, unfused R = 1): walk the alpha set in
