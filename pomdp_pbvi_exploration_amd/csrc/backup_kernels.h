@@ -274,75 +274,77 @@ template <typename T>
 hipError_t launch_keep(const T* bel, int ldb, const T* uniq_rows, int ldo, int B, int S, const double* oldmax,
                        const int32_t* inv, const int32_t* perm, uint8_t* keep, hipStream_t st);
 
-// Batched Bayes step: out[b] = normalise(scatter of b[b,s]*RTO[s,a_b,o_b,r] to rs[s,a_b,r]) via inverse lists
-// in_ptr [A][S+1], in_src [A][S*R] (entries s*R+r, ascending); unnorm [B][S] / mass [B] f64 scratch (mass zeroed).
-// out_row (may be null = identity): result row of belief b, -1 = drop it (the simulator's done-filter).
+// Batched Bayes step: out[b] = normalise(scatter of b[b,s]*RTO[s,a_b,o_b,r] to rs[s,a_b,r]) via inverse lists.
 template <typename T>
-hipError_t launch_belief_update(const T* bel, int ldb, int B, ModelView<T> mv, const int32_t* in_ptr, const int32_t* in_src,
-                                const int32_t* act, const int32_t* obs, const int32_t* out_row, double* unnorm,
-                                double* mass, T* out, int ldo, hipStream_t st, double* mass_part = nullptr);
-// mass_part [B][ceil(S / 256)] (or nullptr): the push kernel's blocks store their partial masses there and a fold kernel adds
-// them in block order, instead of atomicAdd on mass -- the same norm up to its last bit, but the same bits every time.
+struct BayesStep {
+    const T* bel;              // [B][ldb] the beliefs, engine order
+    int ldb, B;
+    const int32_t* in_ptr;     // [A][S+1] inverse transition lists ...
+    const int32_t* in_src;     // [A][S*R] ... entries s*R+r, ascending
+    const int32_t* act;        // [B] action and ...
+    const int32_t* obs;        // [B] ... observation of each belief
+    double* unnorm;            // [B][S] scratch: the un-normalised rows
+    double* mass;              // [B] their sums
+    double* mass_part;         // [B][ceil(S / 256)], or nullptr
+};
+// launch_belief_push  k_belief_push (+ k_mass_fold): unnorm and mass of the rows with out_row[b] >= 0 (out_row == nullptr: all).
+//                     mass_part == nullptr: the blocks add their partial masses to mass with atomicAdd (the caller has zeroed
+//                     it); otherwise they store them there and a fold kernel adds them in block order -- the same norm up to
+//                     its last bit, but the same bits every time.
+// launch_belief_norm  k_belief_norm: out[out_row[b]] = unnorm[b] / mass[b] for the rows with out_row[b] >= 0 (nullptr: row b).
+// out_row may differ between the two: a provisional one for the push, the done-filter's for the norm (-1 = drop the row).
+template <typename T>
+hipError_t launch_belief_push(const BayesStep<T>& bs, ModelView<T> mv, const int32_t* out_row, hipStream_t st);
+template <typename T>
+hipError_t launch_belief_norm(const BayesStep<T>& bs, int S, const int32_t* out_row, T* out, int ldo, hipStream_t st);
 
-// Simulator draw of the device-resident rollout (pbvi_rollout), one lane per live simulation in ENGINE row order i
-// (c = perm ? perm[i] : i is the row's place among the live simulations in caller order, og = orig[c] its trajectory row):
-//   a  = alpha_actions ? alpha_actions[index[i]] : index[c]       (index: [n] engine order / caller order respectively)
-//   u  = uniform01(splitmix64(seed, first_id + og), t)            (synth.py's hash: 53 bits * 2^-53)
-//   k  = first k with u * c[K-1] < c[k], c = sequential fp64 prefix sums of (double) RTO[state[c], a, :, :] (K = O * R
-//        entries, k = o * R + r); if rounding leaves none, the last k with a positive entry
-//   o = k / R, s' = rs[state[c], a, k % R];   done = end_mask[s'] != 0
-// Writes act_e[i] = a, obs_e[i] = o (what launch_belief_update reads), next_state[c] = s', keep[c] = !done, the trajectory
-// slots tr_actions / tr_obs [t][og], tr_states [t+1][og] (row length n0) and steps[og] = t + 1 when done.
+// One step of a device-resident rollout (pbvi_rollout, pbvi_rollout_infotaxis, pbvi_rollout_env): one lane per live simulation
+// in ENGINE row order i; c = perm ? perm[i] : i is the row's place among the live simulations in caller order, og = orig[c] its
+// trajectory row, id = first_id + og its stream.
+struct RolloutStep {
+    int n, n0, t, V;                  // live simulations, simulations of the call (the trajectory row length), step, alpha rows
+    uint64_t seed, first_id;
+    const int32_t* perm;              // [n] or nullptr
+    const int32_t* index;             // [n] a = alpha_actions ? alpha_actions[index[i]] : index[c]
+    const int32_t* alpha_actions;     // [V] or nullptr
+    const int32_t* state;             // [n] the true states, caller order
+    const int32_t* orig;              // [n]
+    const uint8_t* end_mask;          // [S]
+    int32_t *act_e, *obs_e, *row_e;   // [n] engine order: launch_belief_push's act / obs / out_row
+    int32_t* next_state;              // [n] caller order
+    uint8_t* keep;                    // [n] caller order: the simulation goes on
+    int32_t *tr_states, *tr_actions, *tr_obs, *steps;   // the trajectory: [T+1][n0], [T][n0], [T][n0], [n0]
+};
+// Where a rollout against an environment takes its observations from: exactly one of frames / table.
+struct RolloutEnv {
+    const uint8_t* frames;            // uint8 [F][C][S] read at frames[(shift[og] + t) * C * S + channel[a] * S + s'], 64-bit
+    const double* table;              // fp64 [S][A][O]  offsets; the caller has checked shift[og] + t < F and channel[a] in [0, C)
+    int C;
+    const int32_t* channel;           // [A]
+    const int64_t* shift;             // [n0]
+    int end_observation;              // >= 0: the observation on landing in an end state
+};
+// The simulator draw (k_rollout_draw's comment has the rule): with u1 = uniform01(splitmix64(seed, id), t) (synth.py's hash)
+//   env == nullptr   (o, r) = the pair drawn from the joint row RTO[state[c], a, :, :] (K = O * R entries, k = o * R + r)
+//   env              r drawn from w[r] = sum_o RTO[state[c], a, o, r]; o from the environment (the table with a second uniform
+//                    u2 = uniform01(splitmix64(seed, id), 2^32 + t))
+//   s' = rs[state[c], a, r];   done = end_mask[s'] != 0
+// Writes act_e[i] = a, obs_e[i] = o, row_e[i] = done ? -1 : i (the provisional out_row of launch_belief_push), next_state[c] =
+// s', keep[c] = !done, the trajectory slots tr_actions / tr_obs [t][og], tr_states [t+1][og] and steps[og] = t + 1 when done.
 template <typename T>
-hipError_t launch_rollout_draw(int n, ModelView<T> mv, const int32_t* perm, const int32_t* index, const int32_t* alpha_actions,
-                               int V, const int32_t* state, const int32_t* orig, const uint8_t* end_mask, uint64_t seed,
-                               uint64_t first_id, int t, int n0, int32_t* act_e, int32_t* obs_e, int32_t* next_state,
-                               uint8_t* keep, int32_t* tr_states, int32_t* tr_actions, int32_t* tr_obs, int32_t* steps,
-                               hipStream_t st);
-// Its done-filter (one block, n <= 65535): dst[c] = place of caller row c among the survivors or -1, row_e[i] = dst[perm[i]]
-// (launch_belief_update's out_row), state_out / orig_out = the survivors' entries moved up in caller order, *count = survivors.
-hipError_t launch_rollout_compact(int n, const uint8_t* keep, const int32_t* perm, const int32_t* state_in,
-                                  const int32_t* orig_in, int32_t* dst, int32_t* row_e, int32_t* state_out, int32_t* orig_out,
-                                  int* count, hipStream_t st);
-
-// launch_belief_update in two halves, for a caller that drops rows between them (pbvi_rollout_env's lost rule):
-//   launch_belief_push_fold  k_belief_push + k_mass_fold: unnorm [B][S] and mass [B] of the rows with out_row[b] >= 0 (or all),
-//                            the mass ALWAYS summed in block order through mass_part [B][ceil(S / 256)]
-//   launch_belief_norm       k_belief_norm: out[out_row[b]] = unnorm[b] / mass[b] for the rows with out_row[b] >= 0
-// out_row may differ between the two (a provisional one for the push, the final one for the norm).
-template <typename T>
-hipError_t launch_belief_push_fold(const T* bel, int ldb, int B, ModelView<T> mv, const int32_t* in_ptr, const int32_t* in_src,
-                                   const int32_t* act, const int32_t* obs, const int32_t* out_row, double* unnorm, double* mass,
-                                   double* mass_part, hipStream_t st);
-template <typename T>
-hipError_t launch_belief_norm(int B, int S, const double* unnorm, const double* mass, const int32_t* out_row, T* out, int ldo,
-                              hipStream_t st);
-
-// Simulator draw of a rollout against an environment (pbvi_rollout_env); launch_rollout_draw's lanes, indexing and action.
-//   w[r] = sum_o (double) RTO[state[c], a, o, r] (o ascending), r* = first r with u1 * c[R-1] < c[r], c = prefix sums of w,
-//          else the last r with w[r] > 0;  u1 = uniform01(splitmix64(seed, first_id + og), t);  s' = rs[state[c], a, r*]
-//   o    = end_observation                                  if end_observation >= 0 and end_mask[s']
-//        = frames[(shift[og] + t) * C * S + channel[a] * S + s']   (frames != nullptr: uint8 [F][C][S], 64-bit offsets; the
-//                                                            caller has checked shift[og] + t < F and channel[a] in [0, C))
-//        = drawn from table[s', a, :] (fp64 [S][A][O]) by the same prefix rule with
-//          u2 = uniform01(splitmix64(seed, first_id + og), 2^32 + t)               (table != nullptr)
-// Exactly one of frames / table is given.  Writes what launch_rollout_draw writes and row_e[i] = done ? -1 : i, the
-// provisional out_row of launch_belief_push_fold.
-template <typename T>
-hipError_t launch_rollout_draw_env(int n, ModelView<T> mv, const int32_t* perm, const int32_t* index, const int32_t* alpha_actions,
-                                   int V, const int32_t* state, const int32_t* orig, const uint8_t* end_mask, int end_observation,
-                                   const uint8_t* frames, int C, const int32_t* channel, const int64_t* shift, const double* table,
-                                   uint64_t seed, uint64_t first_id, int t, int n0, int32_t* act_e, int32_t* obs_e, int32_t* row_e,
-                                   int32_t* next_state, uint8_t* keep, int32_t* tr_states, int32_t* tr_actions, int32_t* tr_obs,
-                                   int32_t* steps, hipStream_t st);
-// The lost rule, one lane per engine row i (c = perm ? perm[i] : i): a kept row whose mass[i] is 0 or not finite gets
-// keep[c] = 0, steps[orig[c]] = t + 1, lost[orig[c]] = 1.  Runs between launch_belief_push_fold and launch_rollout_compact.
-hipError_t launch_rollout_lost(int n, const int32_t* perm, const int32_t* orig, const double* mass, int t, uint8_t* keep,
-                               int32_t* steps, uint8_t* lost, hipStream_t st);
+hipError_t launch_rollout_draw(const RolloutStep& rs, ModelView<T> mv, const RolloutEnv* env, hipStream_t st);
+// The lost rule, after launch_belief_push: a kept row whose mass[i] is 0 or not finite gets keep[c] = 0, steps[og] = t + 1,
+// lost[og] = 1.
+hipError_t launch_rollout_lost(const RolloutStep& rs, const double* mass, uint8_t* lost, hipStream_t st);
+// The done-filter (one block, n <= 65535): dst[c] = place of caller row c among the survivors or -1, row_e[i] = dst[perm[i]]
+// (launch_belief_norm's out_row), state_out / orig_out = next_state / orig of the survivors moved up in caller order,
+// *count = survivors.
+hipError_t launch_rollout_compact(const RolloutStep& rs, int32_t* dst, int32_t* state_out, int32_t* orig_out, int* count,
+                                  hipStream_t st);
 
 // Infotaxis (pbvi_infotaxis): for every belief row b of `bel` (engine order; caller row d = perm ? perm[b] : b) and action a
 //   G[b,a] = sum_o (Z ln Z - N),  Z = sum_s' u[s'],  N = sum_s' u[s'] ln u[s']  (zero terms add 0; fp64 log),
-//   u[s']  = sum over the inverse list of (a, s') of (double) bel[b][s] * (double) RTO[s,a,o,r]  (launch_belief_update's sum)
+//   u[s']  = sum over the inverse list of (a, s') of (double) bel[b][s] * (double) RTO[s,a,o,r]  (launch_belief_push's sum)
 // = the expected entropy, in nats, of the belief after taking a.  Three kernels, no atomics, every sum in a fixed order:
 //   k_succ_entropy<T>   (Z, N) partials of each x-block (succ_entropy_xblocks(S) of them) into part [XB][B][A][O][2]
 //   k_infotaxis_finish  partials summed in x-block order -> g_out [B][A], pobs_out [B][A][O] = Z (or nullptr), action_out [B] =

@@ -2318,49 +2318,26 @@ __global__ void k_belief_norm(const double* __restrict__ unnorm, const double* _
     out[(int64_t)row * ldo + s] = (T)(unnorm[(int64_t)b * S + s] / mass[b]);   // mass 0 -> NaN, as the reference's 0/0
 }
 
+// The one place that knows the grid of k_belief_push: one block per (256 landing states, belief).  With mass_part the blocks'
+// partial masses are folded in block order (k_mass_fold); without, they are added to the zeroed mass with atomics.
 template <typename T>
-hipError_t launch_belief_update(const T* bel, int ldb, int B, ModelView<T> mv, const int32_t* in_ptr, const int32_t* in_src,
-                                const int32_t* act, const int32_t* obs, const int32_t* out_row, double* unnorm,
-                                double* mass, T* out, int ldo, hipStream_t st, double* mass_part) {
-    if (B <= 0) return hipSuccess;
-    if (B > 65535) return hipErrorInvalidValue;
-    dim3 grid((mv.S + 255) / 256, B);
-    hipLaunchKernelGGL(k_belief_push<T>, grid, dim3(256), 0, st, bel, ldb, mv, in_ptr, in_src, act, obs, out_row, unnorm,
-                       mass, mass_part);
+hipError_t launch_belief_push(const BayesStep<T>& bs, ModelView<T> mv, const int32_t* out_row, hipStream_t st) {
+    if (bs.B <= 0) return hipSuccess;
+    if (bs.B > 65535) return hipErrorInvalidValue;
+    dim3 grid((mv.S + 255) / 256, bs.B);
+    hipLaunchKernelGGL(k_belief_push<T>, grid, dim3(256), 0, st, bs.bel, bs.ldb, mv, bs.in_ptr, bs.in_src, bs.act, bs.obs, out_row,
+                       bs.unnorm, bs.mass, bs.mass_part);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if (mass_part != nullptr) {
-        hipLaunchKernelGGL(k_mass_fold, dim3((B + 255) / 256), dim3(256), 0, st, B, (int)grid.x, out_row, mass_part, mass);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k_belief_norm<T>, grid, dim3(256), 0, st, unnorm, mass, mv.S, out_row, out, ldo);
-    return hipGetLastError();
-}
-
-// The two halves of launch_belief_update for a caller that decides between them which rows go on (pbvi_rollout_env: a row
-// whose mass is 0 is dropped before the norm).  The first half always sums the mass in block order.
-template <typename T>
-hipError_t launch_belief_push_fold(const T* bel, int ldb, int B, ModelView<T> mv, const int32_t* in_ptr, const int32_t* in_src,
-                                   const int32_t* act, const int32_t* obs, const int32_t* out_row, double* unnorm, double* mass,
-                                   double* mass_part, hipStream_t st) {
-    if (B <= 0) return hipSuccess;
-    if (B > 65535 || mass_part == nullptr) return hipErrorInvalidValue;
-    dim3 grid((mv.S + 255) / 256, B);
-    hipLaunchKernelGGL(k_belief_push<T>, grid, dim3(256), 0, st, bel, ldb, mv, in_ptr, in_src, act, obs, out_row, unnorm,
-                       mass, mass_part);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_mass_fold, dim3((B + 255) / 256), dim3(256), 0, st, B, (int)grid.x, out_row, mass_part, mass);
+    if (e != hipSuccess || bs.mass_part == nullptr) return e;
+    hipLaunchKernelGGL(k_mass_fold, dim3((bs.B + 255) / 256), dim3(256), 0, st, bs.B, (int)grid.x, out_row, bs.mass_part, bs.mass);
     return hipGetLastError();
 }
 
 template <typename T>
-hipError_t launch_belief_norm(int B, int S, const double* unnorm, const double* mass, const int32_t* out_row, T* out, int ldo,
-                              hipStream_t st) {
-    if (B <= 0) return hipSuccess;
-    if (B > 65535) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_belief_norm<T>, dim3((S + 255) / 256, B), dim3(256), 0, st, unnorm, mass, S, out_row, out, ldo);
+hipError_t launch_belief_norm(const BayesStep<T>& bs, int S, const int32_t* out_row, T* out, int ldo, hipStream_t st) {
+    if (bs.B <= 0) return hipSuccess;
+    if (bs.B > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_belief_norm<T>, dim3((S + 255) / 256, bs.B), dim3(256), 0, st, bs.unnorm, bs.mass, S, out_row, out, ldo);
     return hipGetLastError();
 }
 
@@ -2658,19 +2635,55 @@ __device__ __forceinline__ uint64_t rollout_mix(uint64_t seed, uint64_t idx) {  
     return z ^ (z >> 31);
 }
 
-// One lane per live simulation, in ENGINE row order i (the order act_e / obs_e feed k_belief_push in); c = perm[i] is the
-// row's place among the live simulations in the caller's order, og = orig[c] its row in the call's trajectory arrays.
-//   index: lookahead 0 -> [n] first argmax_v b.alpha_v per ENGINE row, mapped through alpha_actions [V];
-//          lookahead 1 -> [n] argmax_a Q per CALLER row (alpha_actions == nullptr)
-// The row is walked twice with the same sequential additions (total, then the first k with u * total < c[k]): no local
-// array, whatever O * R is.  An index outside its range (a NaN belief's argmax) is read as 0 rather than followed.
-template <typename T>
+__device__ __forceinline__ double rollout_uniform01(uint64_t key, uint64_t counter) {   // synth.uniform01: 53 bits * 2^-53
+    return (double)(rollout_mix(key, counter) >> 11) * (1.0 / 9007199254740992.0);
+}
+
+// The draw rule: the first k of [0, K) with u * c[K-1] < c[k], c the sequential fp64 prefix sums of weight(0 .. K-1); where
+// rounding leaves none, the last k with a positive weight.  The weights are walked twice with the same additions (the total,
+// then the prefix sums): no local array, whatever K is.
+template <typename W>
+__device__ __forceinline__ int rollout_pick(int K, double u, W weight) {
+    double total = 0.0;
+    for (int k = 0; k < K; ++k) total += weight(k);
+    const double thr = u * total;
+    double cum = 0.0;
+    int last_pos = 0;
+    for (int k = 0; k < K; ++k) {
+        const double w = weight(k);
+        cum += w;
+        if (w > 0.0) last_pos = k;
+        if (thr < cum) return k;
+    }
+    return last_pos;
+}
+
+// The simulator draw of every rollout.  One lane per live simulation, in ENGINE row order i (the order act_e / obs_e feed
+// k_belief_push in); c = perm[i] is the row's place among the live simulations in the caller's order, og = orig[c] its row in
+// the call's trajectory arrays.
+//   action:  value-max -> index [n] = first argmax_v b.alpha_v per ENGINE row, mapped through alpha_actions [V];
+//            otherwise (alpha_actions == nullptr) -> index [n] = the action per CALLER row.  An index outside its range (a NaN
+//            belief's argmax) is read as 0 rather than followed.
+//   ENV = false (pbvi_rollout, pbvi_rollout_infotaxis): ONE uniform u1 = uniform01(splitmix64(seed, id), t) picks the
+//            (observation, successor) pair k = o * R + r from the joint row RTO[s, a, :, :].
+//   ENV = true (pbvi_rollout_env): u1 picks the successor r from w[r] = sum_o (double) RTO[s,a,o,r] (o ascending; recomputed in
+//            each of the two walks, O strided loads per r, instead of kept).  The observation comes from somewhere else --
+//            end_observation if it is >= 0 and end_mask[s'];  else frames[shift[og] + t][channel[a]][s'], a recorded movie of
+//            observation ids (uint8 [F][C][S], one channel per action);  else drawn from another law, table[s',a,:] (fp64
+//            [S][A][O]), by the same rule with u2 = uniform01(splitmix64(seed, id), 2^32 + t).  Reference: the
+//            RealSimulationSet* / SimulationSetAltProb classes of the olfactory experiments, which override
+//            SimulationSet.run_actions' observation and keep the model for Belief.update.
+// row_e[i] is the PROVISIONAL out_row of the Bayes step that follows (-1 = done, no update; otherwise i).
+template <typename T, bool ENV>
 __global__ void k_rollout_draw(int n, ModelView<T> mv, const int32_t* __restrict__ perm, const int32_t* __restrict__ index,
                                const int32_t* __restrict__ alpha_actions, int V, const int32_t* __restrict__ state,
-                               const int32_t* __restrict__ orig, const uint8_t* __restrict__ end_mask, uint64_t seed,
+                               const int32_t* __restrict__ orig, const uint8_t* __restrict__ end_mask, int end_observation,
+                               const uint8_t* __restrict__ frames, int C, const int32_t* __restrict__ channel,
+                               const int64_t* __restrict__ shift, const double* __restrict__ table, uint64_t seed,
                                uint64_t first_id, int t, int n0, int32_t* __restrict__ act_e, int32_t* __restrict__ obs_e,
-                               int32_t* __restrict__ next_state, uint8_t* __restrict__ keep, int32_t* __restrict__ tr_states,
-                               int32_t* __restrict__ tr_actions, int32_t* __restrict__ tr_obs, int32_t* __restrict__ steps) {
+                               int32_t* __restrict__ row_e, int32_t* __restrict__ next_state, uint8_t* __restrict__ keep,
+                               int32_t* __restrict__ tr_states, int32_t* __restrict__ tr_actions,
+                               int32_t* __restrict__ tr_obs, int32_t* __restrict__ steps) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int c = perm ? perm[i] : i;
@@ -2684,30 +2697,37 @@ __global__ void k_rollout_draw(int n, ModelView<T> mv, const int32_t* __restrict
     }
     if (a < 0 || a >= mv.A) a = 0;
     const int s = state[c], og = orig[c];
-    const uint64_t bits = rollout_mix(rollout_mix(seed, first_id + (uint64_t)og), (uint64_t)t) >> 11;
-    const double u = (double)bits * (1.0 / 9007199254740992.0);
-    const T* row = mv.rto + (int64_t)a * mv.O * mv.R * mv.S_pad + s;      // entry k = o * R + r at row[k * S_pad]
-    const int K = mv.O * mv.R;
-    double total = 0.0;
-    for (int k = 0; k < K; ++k) total += (double)row[(int64_t)k * mv.S_pad];
-    const double thr = u * total;
-    double cum = 0.0;
-    int pick = -1, last_pos = 0;
-    for (int k = 0; k < K; ++k) {
-        const double w = (double)row[(int64_t)k * mv.S_pad];
-        cum += w;
-        if (w > 0.0) last_pos = k;
-        if (thr < cum) {
-            pick = k;
-            break;
-        }
+    const uint64_t key = rollout_mix(seed, first_id + (uint64_t)og);
+    const double u1 = rollout_uniform01(key, (uint64_t)t);
+    const T* row = mv.rto + (int64_t)a * mv.O * mv.R * mv.S_pad + s;      // entry (o, r) at row[(o * R + r) * S_pad]
+    int o, r;
+    if constexpr (ENV) {
+        r = rollout_pick(mv.R, u1, [&](int k) {
+            double w = 0.0;
+            for (int oo = 0; oo < mv.O; ++oo) w += (double)row[((int64_t)oo * mv.R + k) * mv.S_pad];
+            return w;
+        });
+    } else {
+        const int pick = rollout_pick(mv.O * mv.R, u1, [&](int k) { return (double)row[(int64_t)k * mv.S_pad]; });
+        o = pick / mv.R;
+        r = pick - o * mv.R;
     }
-    if (pick < 0) pick = last_pos;                          // rounding left none: the last entry with weight
-    const int o = pick / mv.R, r = pick - o * mv.R;
     const int sn = mv.rs[((int64_t)a * mv.R + r) * mv.S_pad + s];
     const bool done = end_mask[sn] != 0;
+    if constexpr (ENV) {
+        if (end_observation >= 0 && done) {
+            o = end_observation;
+        } else if (frames != nullptr) {
+            const int64_t f = shift[og] + (int64_t)t;                    // (max(shift) + T <= F was checked before the first launch)
+            o = (int)frames[(f * C + channel[a]) * (int64_t)mv.S + sn];
+        } else {
+            const double* p = table + ((int64_t)sn * mv.A + a) * mv.O;
+            o = rollout_pick(mv.O, rollout_uniform01(key, (1ull << 32) + (uint64_t)t), [&](int k) { return p[k]; });
+        }
+    }
     act_e[i] = a;
     obs_e[i] = o;
+    row_e[i] = done ? -1 : i;
     next_state[c] = sn;
     keep[c] = done ? 0 : 1;
     const int64_t slot = (int64_t)t * n0 + og;
@@ -2715,6 +2735,25 @@ __global__ void k_rollout_draw(int n, ModelView<T> mv, const int32_t* __restrict
     tr_obs[slot] = o;
     tr_states[slot + n0] = sn;
     if (done) steps[og] = t + 1;
+}
+
+// One lane per ENGINE row, after k_belief_push and k_mass_fold: a row that is still kept and whose un-normalised mass is 0
+// or not finite met an observation the agent's model gives no probability.  It stops here: keep cleared (k_rollout_compact
+// drops it like a finished one), steps = t + 1, lost = 1.  Its belief is never normalised.
+__global__ void k_rollout_lost(int n, const int32_t* __restrict__ perm, const int32_t* __restrict__ orig,
+                               const double* __restrict__ mass, int t, uint8_t* __restrict__ keep, int32_t* __restrict__ steps,
+                               uint8_t* __restrict__ lost) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int c = perm ? perm[i] : i;
+    if (keep[c] == 0) return;                                  // done: its mass was never written
+    const double z = mass[i];
+    if (z == 0.0 || !isfinite(z)) {
+        const int og = orig[c];
+        keep[c] = 0;
+        steps[og] = t + 1;
+        lost[og] = 1;
+    }
 }
 
 // The done-filter of the live simulations, one block: dst[c] = place of caller row c among the survivors (-1 = finished),
@@ -2756,168 +2795,34 @@ __global__ void __launch_bounds__(1024) k_rollout_compact(int n, const uint8_t* 
 }
 
 template <typename T>
-hipError_t launch_rollout_draw(int n, ModelView<T> mv, const int32_t* perm, const int32_t* index, const int32_t* alpha_actions,
-                               int V, const int32_t* state, const int32_t* orig, const uint8_t* end_mask, uint64_t seed,
-                               uint64_t first_id, int t, int n0, int32_t* act_e, int32_t* obs_e, int32_t* next_state,
-                               uint8_t* keep, int32_t* tr_states, int32_t* tr_actions, int32_t* tr_obs, int32_t* steps,
-                               hipStream_t st) {
-    if (n <= 0) return hipSuccess;
-    if (n > n0 || t < 0 || (int64_t)(t + 2) * n0 > 0x7fffffffll) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_rollout_draw<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, mv, perm, index, alpha_actions, V,
-                       state, orig, end_mask, seed, first_id, t, n0, act_e, obs_e, next_state, keep, tr_states, tr_actions,
-                       tr_obs, steps);
+hipError_t launch_rollout_draw(const RolloutStep& rs, ModelView<T> mv, const RolloutEnv* env, hipStream_t st) {
+    if (rs.n <= 0) return hipSuccess;
+    if (rs.n > rs.n0 || rs.t < 0 || (int64_t)(rs.t + 2) * rs.n0 > 0x7fffffffll) return hipErrorInvalidValue;
+    const RolloutEnv none{};
+    const RolloutEnv& e = env ? *env : none;
+    if (env) {
+        if ((e.frames == nullptr) == (e.table == nullptr) || e.end_observation >= mv.O) return hipErrorInvalidValue;
+        if (e.frames != nullptr && (e.C < 1 || e.channel == nullptr || e.shift == nullptr)) return hipErrorInvalidValue;
+    }
+    const auto kernel = env ? k_rollout_draw<T, true> : k_rollout_draw<T, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((rs.n + 255) / 256)), dim3(256), 0, st, rs.n, mv, rs.perm, rs.index, rs.alpha_actions, rs.V, rs.state, rs.orig, rs.end_mask, e.end_observation,
+                       e.frames, e.C, e.channel, e.shift, e.table, rs.seed, rs.first_id, rs.t, rs.n0, rs.act_e, rs.obs_e, rs.row_e,
+                       rs.next_state, rs.keep, rs.tr_states, rs.tr_actions, rs.tr_obs, rs.steps);
     return hipGetLastError();
 }
 
-hipError_t launch_rollout_compact(int n, const uint8_t* keep, const int32_t* perm, const int32_t* state_in,
-                                  const int32_t* orig_in, int32_t* dst, int32_t* row_e, int32_t* state_out, int32_t* orig_out,
-                                  int* count, hipStream_t st) {
-    if (n <= 0 || n > 65535) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_rollout_compact, dim3(1), dim3(1024), 0, st, n, keep, perm, state_in, orig_in, dst, row_e, state_out,
-                       orig_out, count);
+hipError_t launch_rollout_lost(const RolloutStep& rs, const double* mass, uint8_t* lost, hipStream_t st) {
+    if (rs.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_rollout_lost, dim3((unsigned)((rs.n + 255) / 256)), dim3(256), 0, st, rs.n, rs.perm, rs.orig, mass, rs.t,
+                       rs.keep, rs.steps, lost);
     return hipGetLastError();
 }
 
-// ------------------------------------------------------------------------- //
-// Rollout against an environment (pbvi_rollout_env): the successor still comes from the agent's own tables, the observation
-// from somewhere else -- a recorded movie of observation ids (frames [F][C][S], one channel per action) or another law
-// (table [S][A][O], fp64).  Reference: the RealSimulationSet* / SimulationSetAltProb classes of the olfactory experiments,
-// which override SimulationSet.run_actions' observation and keep the model for Belief.update.
-// ------------------------------------------------------------------------- //
-// One lane per live simulation in ENGINE row order, k_rollout_draw's indexing (i, c, og) and action rule.
-//   successor:   w[r] = sum_o (double) RTO[s,a,o,r] (o ascending), r* = first r with u1 * c[R-1] < c[r] (c = prefix sums of
-//                w), else the last r with w[r] > 0;  u1 = uniform01(splitmix64(seed, id), t);  s' = rs[s,a,r*]
-//   observation: end_observation if it is >= 0 and end_mask[s'];  else frames[shift[og] + t][channel[a]][s'];  else drawn from
-//                table[s',a,:] by the same rule with u2 = uniform01(splitmix64(seed, id), 2^32 + t)
-// w[r] is recomputed in each of the two walks (O strided loads per r) instead of kept: no per-thread array, whatever O and R.
-// row_e[i] is the PROVISIONAL out_row of the Bayes step that follows (-1 = done, no update; otherwise i).
-template <typename T>
-__global__ void k_rollout_draw_env(int n, ModelView<T> mv, const int32_t* __restrict__ perm, const int32_t* __restrict__ index,
-                                   const int32_t* __restrict__ alpha_actions, int V, const int32_t* __restrict__ state,
-                                   const int32_t* __restrict__ orig, const uint8_t* __restrict__ end_mask, int end_observation,
-                                   const uint8_t* __restrict__ frames, int C, const int32_t* __restrict__ channel,
-                                   const int64_t* __restrict__ shift, const double* __restrict__ table, uint64_t seed,
-                                   uint64_t first_id, int t, int n0, int32_t* __restrict__ act_e, int32_t* __restrict__ obs_e,
-                                   int32_t* __restrict__ row_e, int32_t* __restrict__ next_state, uint8_t* __restrict__ keep,
-                                   int32_t* __restrict__ tr_states, int32_t* __restrict__ tr_actions,
-                                   int32_t* __restrict__ tr_obs, int32_t* __restrict__ steps) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int c = perm ? perm[i] : i;
-    int a;
-    if (alpha_actions) {
-        int v = index[i];
-        if (v < 0 || v >= V) v = 0;
-        a = alpha_actions[v];
-    } else {
-        a = index[c];
-    }
-    if (a < 0 || a >= mv.A) a = 0;
-    const int s = state[c], og = orig[c];
-    const uint64_t key = rollout_mix(seed, first_id + (uint64_t)og);
-    const double u1 = (double)(rollout_mix(key, (uint64_t)t) >> 11) * (1.0 / 9007199254740992.0);
-    const T* row = mv.rto + (int64_t)a * mv.O * mv.R * mv.S_pad + s;      // entry (o, r) at row[(o * R + r) * S_pad]
-    double total = 0.0;
-    for (int r = 0; r < mv.R; ++r) {
-        double w = 0.0;
-        for (int o = 0; o < mv.O; ++o) w += (double)row[((int64_t)o * mv.R + r) * mv.S_pad];
-        total += w;
-    }
-    const double thr = u1 * total;
-    double cum = 0.0;
-    int pick = -1, last_pos = 0;
-    for (int r = 0; r < mv.R; ++r) {
-        double w = 0.0;
-        for (int o = 0; o < mv.O; ++o) w += (double)row[((int64_t)o * mv.R + r) * mv.S_pad];
-        cum += w;
-        if (w > 0.0) last_pos = r;
-        if (thr < cum) {
-            pick = r;
-            break;
-        }
-    }
-    if (pick < 0) pick = last_pos;
-    const int sn = mv.rs[((int64_t)a * mv.R + pick) * mv.S_pad + s];
-    const bool done = end_mask[sn] != 0;
-    int o;
-    if (end_observation >= 0 && done) {
-        o = end_observation;
-    } else if (frames != nullptr) {
-        const int64_t f = shift[og] + (int64_t)t;                        // (max(shift) + T <= F was checked before the first launch)
-        o = (int)frames[(f * C + channel[a]) * (int64_t)mv.S + sn];
-    } else {
-        const double u2 = (double)(rollout_mix(key, (1ull << 32) + (uint64_t)t) >> 11) * (1.0 / 9007199254740992.0);
-        const double* p = table + ((int64_t)sn * mv.A + a) * mv.O;
-        double tot = 0.0;
-        for (int k = 0; k < mv.O; ++k) tot += p[k];
-        const double th = u2 * tot;
-        double cu = 0.0;
-        int last = 0;
-        o = -1;
-        for (int k = 0; k < mv.O; ++k) {
-            const double w = p[k];
-            cu += w;
-            if (w > 0.0) last = k;
-            if (th < cu) {
-                o = k;
-                break;
-            }
-        }
-        if (o < 0) o = last;
-    }
-    act_e[i] = a;
-    obs_e[i] = o;
-    row_e[i] = done ? -1 : i;
-    next_state[c] = sn;
-    keep[c] = done ? 0 : 1;
-    const int64_t slot = (int64_t)t * n0 + og;
-    tr_actions[slot] = a;
-    tr_obs[slot] = o;
-    tr_states[slot + n0] = sn;
-    if (done) steps[og] = t + 1;
-}
-
-// One lane per ENGINE row, after k_belief_push and k_mass_fold: a row that is still kept and whose un-normalised mass is 0
-// or not finite met an observation the agent's model gives no probability.  It stops here: keep cleared (k_rollout_compact
-// drops it like a finished one), steps = t + 1, lost = 1.  Its belief is never normalised.
-__global__ void k_rollout_lost(int n, const int32_t* __restrict__ perm, const int32_t* __restrict__ orig,
-                               const double* __restrict__ mass, int t, uint8_t* __restrict__ keep, int32_t* __restrict__ steps,
-                               uint8_t* __restrict__ lost) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int c = perm ? perm[i] : i;
-    if (keep[c] == 0) return;                                  // done: its mass was never written
-    const double z = mass[i];
-    if (z == 0.0 || !isfinite(z)) {
-        const int og = orig[c];
-        keep[c] = 0;
-        steps[og] = t + 1;
-        lost[og] = 1;
-    }
-}
-
-template <typename T>
-hipError_t launch_rollout_draw_env(int n, ModelView<T> mv, const int32_t* perm, const int32_t* index, const int32_t* alpha_actions,
-                                   int V, const int32_t* state, const int32_t* orig, const uint8_t* end_mask, int end_observation,
-                                   const uint8_t* frames, int C, const int32_t* channel, const int64_t* shift, const double* table,
-                                   uint64_t seed, uint64_t first_id, int t, int n0, int32_t* act_e, int32_t* obs_e, int32_t* row_e,
-                                   int32_t* next_state, uint8_t* keep, int32_t* tr_states, int32_t* tr_actions, int32_t* tr_obs,
-                                   int32_t* steps, hipStream_t st) {
-    if (n <= 0) return hipSuccess;
-    if (n > n0 || t < 0 || (int64_t)(t + 2) * n0 > 0x7fffffffll) return hipErrorInvalidValue;
-    if ((frames == nullptr) == (table == nullptr) || end_observation >= mv.O) return hipErrorInvalidValue;
-    if (frames != nullptr && (C < 1 || channel == nullptr || shift == nullptr)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_rollout_draw_env<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, mv, perm, index, alpha_actions,
-                       V, state, orig, end_mask, end_observation, frames, C, channel, shift, table, seed, first_id, t, n0, act_e,
-                       obs_e, row_e, next_state, keep, tr_states, tr_actions, tr_obs, steps);
-    return hipGetLastError();
-}
-
-hipError_t launch_rollout_lost(int n, const int32_t* perm, const int32_t* orig, const double* mass, int t, uint8_t* keep,
-                               int32_t* steps, uint8_t* lost, hipStream_t st) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_rollout_lost, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, perm, orig, mass, t, keep, steps,
-                       lost);
+hipError_t launch_rollout_compact(const RolloutStep& rs, int32_t* dst, int32_t* state_out, int32_t* orig_out, int* count,
+                                  hipStream_t st) {
+    if (rs.n <= 0 || rs.n > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_rollout_compact, dim3(1), dim3(1024), 0, st, rs.n, rs.keep, rs.perm, rs.next_state, rs.orig, dst, rs.row_e,
+                       state_out, orig_out, count);
     return hipGetLastError();
 }
 
@@ -3100,20 +3005,9 @@ hipError_t launch_infotaxis(const T* bel, int ldb, int B, ModelView<T> mv, const
 #define PBVI_INST(T)                                                                                                   \
     template hipError_t launch_infotaxis<T>(const T*, int, int, ModelView<T>, const int32_t*, const int32_t*,          \
                                             const int32_t*, double*, double*, int32_t*, double*, double*, hipStream_t); \
-    template hipError_t launch_rollout_draw<T>(int, ModelView<T>, const int32_t*, const int32_t*, const int32_t*, int,  \
-                                               const int32_t*, const int32_t*, const uint8_t*, uint64_t, uint64_t, int, \
-                                               int, int32_t*, int32_t*, int32_t*, uint8_t*, int32_t*, int32_t*,         \
-                                               int32_t*, int32_t*, hipStream_t);                                       \
-    template hipError_t launch_rollout_draw_env<T>(int, ModelView<T>, const int32_t*, const int32_t*, const int32_t*, int, \
-                                                   const int32_t*, const int32_t*, const uint8_t*, int, const uint8_t*, int, \
-                                                   const int32_t*, const int64_t*, const double*, uint64_t, uint64_t, int, \
-                                                   int, int32_t*, int32_t*, int32_t*, int32_t*, uint8_t*, int32_t*,     \
-                                                   int32_t*, int32_t*, int32_t*, hipStream_t);                         \
-    template hipError_t launch_belief_push_fold<T>(const T*, int, int, ModelView<T>, const int32_t*, const int32_t*,   \
-                                                   const int32_t*, const int32_t*, const int32_t*, double*, double*,   \
-                                                   double*, hipStream_t);                                              \
-    template hipError_t launch_belief_norm<T>(int, int, const double*, const double*, const int32_t*, T*, int,         \
-                                              hipStream_t);                                                            \
+    template hipError_t launch_rollout_draw<T>(const RolloutStep&, ModelView<T>, const RolloutEnv*, hipStream_t);        \
+    template hipError_t launch_belief_push<T>(const BayesStep<T>&, ModelView<T>, const int32_t*, hipStream_t);         \
+    template hipError_t launch_belief_norm<T>(const BayesStep<T>&, int, const int32_t*, T*, int, hipStream_t);         \
     template hipError_t launch_support<T>(ModelView<T>, uint8_t*, hipStream_t);                                        \
     template hipError_t launch_project<T>(const T*, int, int, ModelView<T>, T, T*, int, const uint8_t*, int,           \
                                           hipStream_t, const uint8_t*, const int*, int, const int32_t*, const int32_t*); \
@@ -3144,9 +3038,6 @@ hipError_t launch_infotaxis(const T* bel, int ldb, int B, ModelView<T> mv, const
     template hipError_t launch_expand_rows<T>(const T*, const int32_t*, T*, int, int, hipStream_t);                    \
     template hipError_t launch_keep<T>(const T*, int, const T*, int, int, int, const double*, const int32_t*,          \
                                        const int32_t*, uint8_t*, hipStream_t);                                         \
-    template hipError_t launch_belief_update<T>(const T*, int, int, ModelView<T>, const int32_t*, const int32_t*,      \
-                                                const int32_t*, const int32_t*, const int32_t*, double*, double*, T*,  \
-                                                int, hipStream_t, double*);                                            \
     template hipError_t launch_push_project<T>(const T*, int, int, ModelView<T>, const int32_t*, const int32_t*,       \
                                                double, const T*, T*, int, double*, hipStream_t, uint8_t*);                      \
     template hipError_t launch_rdot<T>(const T*, int, int, ModelView<T>, const int32_t*, const int32_t*, double*,      \

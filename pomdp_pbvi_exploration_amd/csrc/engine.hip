@@ -869,6 +869,23 @@ enum RolloutSource {
     ROLLOUT_INFOTAXIS = 2,            // first argmin_a of the expected successor entropy (pbvi_rollout_infotaxis)
 };
 
+// One rollout call, as pbvi_rollout / pbvi_rollout_infotaxis / pbvi_rollout_env fill it
+struct RolloutCall {
+    int source;                                // RolloutSource (anything else is refused)
+    const int32_t* alpha_actions = nullptr;    // [V], read by ROLLOUT_VALUE_MAX
+    double gamma = 0.0;                        // read by ROLLOUT_Q
+    const int32_t* start_states;               // [B]
+    const uint8_t* end_mask;                   // [S]
+    uint64_t first_sim_id, seed;
+    int64_t T;
+    int32_t *out_states, *out_actions, *out_observations, *out_steps;   // [T+1][B], [T][B], [T][B], [B]; each may be NULL
+    // pbvi_rollout_env: the observations come from the environment set with pbvi_env_set_*, and a simulation can be lost
+    bool env = false;
+    int end_observation = -1;                  // >= 0: the observation on landing in an end state
+    const int64_t* shifts = nullptr;           // [B] first frame of each simulation, or NULL (frames only)
+    uint8_t* out_lost = nullptr;               // [B] or NULL
+};
+
 class EngineBase {
    public:
     virtual ~EngineBase() {}
@@ -926,19 +943,12 @@ class EngineBase {
     virtual int debug_value_max_route(int64_t* out) = 0;
     virtual int debug_score_probe_fetch(int64_t* dims, double* scalars, double* score, double* mag, double* err,
                                         int32_t* best_v, double* best_score, int32_t* queue, uint8_t* dead, int32_t* perm) = 0;
-    // source: the policy of the step loop (RolloutSource); alpha_actions and gamma are read by the sources that need them
-    virtual int rollout(int source, const int32_t* alpha_actions, double gamma, const int32_t* start_states,
-                        const uint8_t* end_mask, uint64_t first_sim_id, uint64_t seed, int64_t T, int32_t* out_states,
-                        int32_t* out_actions, int32_t* out_observations, int32_t* out_steps) = 0;
+    virtual int rollout(const RolloutCall& call) = 0;
     virtual int infotaxis(double* out_g, int32_t* out_action, double* out_p_obs, double* out_entropy) = 0;
     // the observation source of rollout_env: recorded frames or another observation law (setting one replaces the other)
     virtual int env_set_frames(const uint8_t* frames, int64_t F, int64_t C, const int32_t* channel_of_action) = 0;
     virtual int env_set_table(const double* obs_prob) = 0;
     virtual int env_clear() = 0;
-    virtual int rollout_env(int source, const int32_t* alpha_actions, double gamma, const int32_t* start_states,
-                            const uint8_t* end_mask, int end_observation, const int64_t* shifts, uint64_t first_sim_id,
-                            uint64_t seed, int64_t T, int32_t* out_states, int32_t* out_actions, int32_t* out_observations,
-                            int32_t* out_steps, uint8_t* out_lost) = 0;
 };
 
 // Order of a score-probe capture among the captures of ALL engines of the process.  One counter, not one per element type:
@@ -1050,7 +1060,7 @@ class EngineT : public EngineBase {
     // pbvi_infotaxis: the x-blocks' (Z, N) partials [XB][B][A][O][2]; G [B][A], its first argmin [B], P(o | b, a) [B][A][O]
     // and the beliefs' own entropies [B], all four in the caller's belief order
     DevBuf it_part_{mem_}, it_g_{mem_}, it_act_{mem_}, it_pobs_{mem_}, it_h_{mem_};
-    DevBuf bu_mpart_{mem_};   // advance_resident(fixed_order): the push blocks' partial masses [B][ceil(S/256)]
+    DevBuf bu_mpart_{mem_};   // bayes_push(fixed_order): the push blocks' partial masses [B][ceil(S/256)]
     // pbvi_env_set_*: the observation source of pbvi_rollout_env.  Frames: env_frames_ uint8 [F][C][S] + env_chan_ int32 [A];
     // table: env_table_ fp64 [S][A][O].  Working buffers: after_oom() releases them and the engine has no environment again.
     enum EnvKind { ENV_NONE = 0, ENV_FRAMES = 1, ENV_TABLE = 2 };
@@ -1080,6 +1090,7 @@ class EngineT : public EngineBase {
     int64_t res_unique_ = 0;
     bool full_valid_ = false;
     std::vector<int32_t> h_perm_;
+    std::vector<int32_t> h_bu_;                              // bayes_upload's host side: act | obs | row, engine order
     bool h_perm_valid_ = false;                              // h_perm_ mirrors perm_ (fetched on demand, see host_perm)
     bool sorted_ = false;
     const void* gam_pad_ptr_ = nullptr;                      // Gamma buffer / row count whose pad rows are zero
@@ -1588,37 +1599,100 @@ class EngineT : public EngineBase {
         return PBVI_OK;
     }
 
+    // No belief block is resident (every simulation finished, or the engine starts over)
+    void block_emptied() {
+        B_ = 0;
+        B_pad_ = 0;
+        sorted_ = false;
+        have_result_ = false;
+    }
+
+    // The Bayes step's buffers for `rows` beliefs; fixed_order: also the partial masses of a norm summed in block order
+    int bayes_ensure(int64_t rows, bool fixed_order) {
+        int rc;
+        if ((rc = bu_act_.ensure((size_t)rows * sizeof(int32_t)))) return rc;
+        if ((rc = bu_obs_.ensure((size_t)rows * sizeof(int32_t)))) return rc;
+        if ((rc = bu_row_.ensure((size_t)rows * sizeof(int32_t)))) return rc;
+        if ((rc = bu_unnorm_.ensure((size_t)rows * S_ * sizeof(double)))) return rc;
+        if ((rc = bu_mass_.ensure((size_t)rows * sizeof(double)))) return rc;
+        if (fixed_order && (rc = bu_mpart_.ensure((size_t)rows * ((S_ + 255) / 256) * sizeof(double)))) return rc;
+        return PBVI_OK;
+    }
+
+    // What belief_update and beliefs_advance refuse, in this order, and what both need before their first launch
+    int bayes_begin(const std::string& who, const int32_t* act, const int32_t* obs, bool other_null) {
+        if (B_ <= 0) FAIL(PBVI_EINVAL, who + ": no belief block resident");
+        if (!act || !obs || other_null) FAIL(PBVI_EINVAL, who + ": NULL argument");
+        if ((int64_t)S_ * R_ > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, who + ": S*R exceeds int32");
+        for (int64_t b = 0; b < B_; ++b)
+            if (act[b] < 0 || act[b] >= A_ || obs[b] < 0 || obs[b] >= O_) FAIL(PBVI_EINVAL, who + ": action / observation out of range");
+        HIPCHK(hipSetDevice(device_));
+        return build_inverse_lists();
+    }
+
+    // act / obs / row (row may be NULL) arrive in the caller's belief order and the resident block may be sorted: engine row i
+    // holds the caller's row c.  Into bu_act_ / bu_obs_ / bu_row_ in engine order; h_bu_ is read until the stream is synchronised.
+    int bayes_upload(const int32_t* act, const int32_t* obs, const int32_t* row) {
+        int rc = bayes_ensure(B_, false);
+        if (rc || (rc = host_perm())) return rc;
+        const size_t n = (size_t)B_;
+        h_bu_.resize(3 * n);
+        for (size_t i = 0; i < n; ++i) {
+            const size_t c = sorted_ ? (size_t)h_perm_[i] : i;
+            h_bu_[i] = act[c];
+            h_bu_[n + i] = obs[c];
+            h_bu_[2 * n + i] = row ? row[c] : (int32_t)i;
+        }
+        DevBuf* to[3] = {&bu_act_, &bu_obs_, &bu_row_};
+        for (int k = 0; k < (row ? 3 : 2); ++k)
+            HIPCHK(hipMemcpyAsync(to[k]->p, h_bu_.data() + k * n, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+        return PBVI_OK;
+    }
+
+    BayesStep<T> bayes_step(bool fixed_order) {
+        BayesStep<T> bs{};
+        bs.bel = bel_.as<T>();
+        bs.ldb = S_pad_;
+        bs.B = (int)B_;
+        bs.in_ptr = in_ptr_.as<int32_t>();
+        bs.in_src = in_src_.as<int32_t>();
+        bs.act = bu_act_.as<int32_t>();
+        bs.obs = bu_obs_.as<int32_t>();
+        bs.unnorm = bu_unnorm_.as<double>();
+        bs.mass = bu_mass_.as<double>();
+        bs.mass_part = fixed_order ? bu_mpart_.as<double>() : nullptr;
+        return bs;
+    }
+
+    // First half of the Bayes step on the resident block, from bu_act_ / bu_obs_ in ENGINE row order: the un-normalised rows and
+    // their masses, of the rows with out_row[b] >= 0 (nullptr: all).  fixed_order: the norm is summed in block order instead of
+    // with atomics on the zeroed masses.
+    int bayes_push(const int32_t* out_row, bool fixed_order) {
+        if (!fixed_order) HIPCHK(hipMemsetAsync(bu_mass_.p, 0, (size_t)B_ * sizeof(double), stream_));
+        HIPCHK(launch_belief_push<T>(bayes_step(fixed_order), view(), out_row, stream_));
+        return PBVI_OK;
+    }
+
+    // Second half: the rows with bu_row_[b] >= 0 normalised into row bu_row_[b] of the nb survivors (caller order), which
+    // become the resident block.  The beliefs never leave the device.
+    int bayes_norm_finish(int64_t nb, bool sync_before_finish) {
+        int rc = stage_.ensure((size_t)nb * S_pad_ * sizeof(T));
+        if (rc) return rc;
+        HIPCHK(hipMemsetAsync(stage_.p, 0, (size_t)nb * S_pad_ * sizeof(T), stream_));   // pad columns stay zero
+        HIPCHK(launch_belief_norm<T>(bayes_step(false), S_, bu_row_.as<int32_t>(), stage_.as<T>(), S_pad_, stream_));
+        if (sync_before_finish) HIPCHK(hipStreamSynchronize(stream_));
+        return beliefs_finish(nb, stage_.as<T>(), nullptr);
+    }
+
     // out[b] = Bayes update of the resident belief b with (act[b], obs[b]); out: [B][S] T, host or device
     int belief_update(const int32_t* act, const int32_t* obs, void* out) override {
-        if (B_ <= 0) FAIL(PBVI_EINVAL, "belief_update: no belief block resident");
-        if (!act || !obs || !out) FAIL(PBVI_EINVAL, "belief_update: NULL argument");
-        if ((int64_t)S_ * R_ > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "belief_update: S*R exceeds int32");
-        for (int64_t b = 0; b < B_; ++b)
-            if (act[b] < 0 || act[b] >= A_ || obs[b] < 0 || obs[b] >= O_) FAIL(PBVI_EINVAL, "belief_update: action / observation out of range");
-        HIPCHK(hipSetDevice(device_));
-        int rc = build_inverse_lists();
+        int rc = bayes_begin("belief_update", act, obs, !out);
         if (rc) return rc;
-        if ((rc = bu_act_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
-        if ((rc = bu_obs_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
-        if ((rc = bu_unnorm_.ensure((size_t)B_ * S_ * sizeof(double)))) return rc;
-        if ((rc = bu_mass_.ensure((size_t)B_ * sizeof(double)))) return rc;
         if ((rc = bu_out_.ensure((size_t)B_ * S_ * sizeof(T)))) return rc;
-        // act/obs arrive in the caller's belief order; the resident block may be sorted
-        if ((rc = host_perm())) return rc;
-        std::vector<int32_t> ha((size_t)B_), ho((size_t)B_);
-        for (int64_t i = 0; i < B_; ++i) {
-            const int64_t c = sorted_ ? h_perm_[(size_t)i] : i;
-            ha[(size_t)i] = act[c];
-            ho[(size_t)i] = obs[c];
-        }
-        HIPCHK(hipMemcpyAsync(bu_act_.p, ha.data(), (size_t)B_ * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-        HIPCHK(hipMemcpyAsync(bu_obs_.p, ho.data(), (size_t)B_ * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-        HIPCHK(hipMemsetAsync(bu_mass_.p, 0, (size_t)B_ * sizeof(double), stream_));
-        // results go to rows in caller order: kernel row i writes out row perm[i] via a row-pointer trick is not
-        // needed -- compute in engine order into stage, then gather back
-        HIPCHK(launch_belief_update<T>(bel_.as<T>(), S_pad_, (int)B_, view(), in_ptr_.as<int32_t>(), in_src_.as<int32_t>(),
-                                       bu_act_.as<int32_t>(), bu_obs_.as<int32_t>(), nullptr, bu_unnorm_.as<double>(),
-                                       bu_mass_.as<double>(), bu_out_.as<T>(), S_, stream_));
+        if ((rc = bayes_upload(act, obs, nullptr))) return rc;
+        // computed in engine order into bu_out_, then gathered back into the caller's order
+        if ((rc = bayes_push(nullptr, false))) return rc;
+        HIPCHK(launch_belief_norm<T>(bayes_step(false), S_, nullptr, bu_out_.as<T>(), S_, stream_));
         HIPCHK(hipStreamSynchronize(stream_));
         if (!sorted_) {
             HIPCHK(hipMemcpy(out, bu_out_.p, (size_t)B_ * S_ * sizeof(T), hipMemcpyDefault));
@@ -1633,62 +1707,27 @@ class EngineT : public EngineBase {
 
     // Simulator step on the resident block (src/pomdp.py:3305-3311 update, :3326-3329 done-filter): every belief is
     // updated with its own (a, o); rows with keep[b] == 0 are dropped and the survivors become the resident block,
-    // in the caller's order.  The beliefs never leave the device.
+    // in the caller's order.
     int beliefs_advance(const int32_t* act, const int32_t* obs, const uint8_t* keep, int64_t* out_B) override {
-        if (B_ <= 0) FAIL(PBVI_EINVAL, "beliefs_advance: no belief block resident");
-        if (!act || !obs) FAIL(PBVI_EINVAL, "beliefs_advance: NULL argument");
-        if ((int64_t)S_ * R_ > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "beliefs_advance: S*R exceeds int32");
-        for (int64_t b = 0; b < B_; ++b)
-            if (act[b] < 0 || act[b] >= A_ || obs[b] < 0 || obs[b] >= O_) FAIL(PBVI_EINVAL, "beliefs_advance: action / observation out of range");
-        HIPCHK(hipSetDevice(device_));
-        int rc = build_inverse_lists();
+        int rc = bayes_begin("beliefs_advance", act, obs, false);
         if (rc) return rc;
         std::vector<int32_t> dst((size_t)B_);           // caller row -> surviving row
         int64_t nb = 0;
         for (int64_t c = 0; c < B_; ++c) dst[(size_t)c] = (!keep || keep[c]) ? (int32_t)nb++ : -1;
         if (out_B) *out_B = nb;
         if (nb == 0) {                                   // every simulation finished
-            B_ = 0;
-            B_pad_ = 0;
-            sorted_ = false;
-            have_result_ = false;
+            block_emptied();
             return PBVI_OK;
         }
-        if ((rc = bu_act_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
-        if ((rc = bu_obs_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
-        if ((rc = bu_row_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
-        if ((rc = host_perm())) return rc;
-        std::vector<int32_t> ha((size_t)B_), ho((size_t)B_), hr((size_t)B_);
-        for (int64_t i = 0; i < B_; ++i) {               // engine row i holds the caller's row c
-            const int64_t c = sorted_ ? h_perm_[(size_t)i] : i;
-            ha[(size_t)i] = act[c];
-            ho[(size_t)i] = obs[c];
-            hr[(size_t)i] = dst[(size_t)c];
-        }
-        HIPCHK(hipMemcpyAsync(bu_act_.p, ha.data(), (size_t)B_ * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-        HIPCHK(hipMemcpyAsync(bu_obs_.p, ho.data(), (size_t)B_ * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-        HIPCHK(hipMemcpyAsync(bu_row_.p, hr.data(), (size_t)B_ * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-        return advance_resident(nb, true);               // (synchronises: ha/ho/hr are pageable host vectors)
+        if ((rc = bayes_upload(act, obs, dst.data()))) return rc;
+        return advance_resident(nb);
     }
 
-    // The Bayes step + done-filter of beliefs_advance from arrays that are on the device already, in ENGINE row order:
-    // bu_act_ / bu_obs_ [B_] = (action, observation) of each row, bu_row_ [B_] = its row among the nb survivors (caller
-    // order) or -1.  Filled by an upload (beliefs_advance) or by the rollout's draw and filter kernels.
-    // fixed_order: the norm is summed in block order instead of with atomics (launch_belief_update's mass_part).
-    int advance_resident(int64_t nb, bool sync_before_finish, bool fixed_order = false) {
-        int rc;
-        if (fixed_order && (rc = bu_mpart_.ensure((size_t)B_ * ((S_ + 255) / 256) * sizeof(double)))) return rc;
-        if ((rc = bu_unnorm_.ensure((size_t)B_ * S_ * sizeof(double)))) return rc;
-        if ((rc = bu_mass_.ensure((size_t)B_ * sizeof(double)))) return rc;
-        if ((rc = stage_.ensure((size_t)nb * S_pad_ * sizeof(T)))) return rc;
-        HIPCHK(hipMemsetAsync(bu_mass_.p, 0, (size_t)B_ * sizeof(double), stream_));
-        HIPCHK(hipMemsetAsync(stage_.p, 0, (size_t)nb * S_pad_ * sizeof(T), stream_));   // pad columns stay zero
-        HIPCHK(launch_belief_update<T>(bel_.as<T>(), S_pad_, (int)B_, view(), in_ptr_.as<int32_t>(), in_src_.as<int32_t>(),
-                                       bu_act_.as<int32_t>(), bu_obs_.as<int32_t>(), bu_row_.as<int32_t>(),
-                                       bu_unnorm_.as<double>(), bu_mass_.as<double>(), stage_.as<T>(), S_pad_, stream_,
-                                       fixed_order ? bu_mpart_.as<double>() : nullptr));
-        if (sync_before_finish) HIPCHK(hipStreamSynchronize(stream_));
-        return beliefs_finish(nb, stage_.as<T>(), nullptr);
+    // The Bayes step + done-filter of beliefs_advance from bu_act_ / bu_obs_ / bu_row_ on the device (synchronises before the
+    // new block is built: the upload's host side is free again)
+    int advance_resident(int64_t nb) {
+        int rc = bayes_push(bu_row_.as<int32_t>(), false);
+        return rc ? rc : bayes_norm_finish(nb, true);
     }
 
     // Expected successor entropies of the resident block (pbvi_infotaxis) into it_g_ / it_act_ (/ it_pobs_ / it_h_), caller
@@ -1722,25 +1761,6 @@ class EngineT : public EngineBase {
         if (out_p_obs && (rc = out_add(out_p_obs, it_pobs_.p, (size_t)B_ * A_ * O_ * sizeof(double)))) return rc;
         if (out_entropy && (rc = out_add(out_entropy, it_h_.p, (size_t)B_ * sizeof(double)))) return rc;
         return out_finish();
-    }
-
-    // T lock-step simulation steps of the resident block on the device (pbvi_rollout, pbvi_rollout_infotaxis): per step the
-    // action source's stage with its index left on the device (value-max or Q-values against the resident alpha set, or
-    // the successor entropies of infotaxis_device), the simulator draw, the done-filter and the Bayes step of
-    // beliefs_advance.  Finished rows are dropped after EVERY step ("Device-resident rollouts"): the one host
-    // read per step is the survivor count, which sizes the next step's launches.
-    int rollout(int source, const int32_t* alpha_actions, double gamma, const int32_t* start_states, const uint8_t* end_mask,
-                uint64_t first_sim_id, uint64_t seed, int64_t n_steps, int32_t* out_states, int32_t* out_actions,
-                int32_t* out_observations, int32_t* out_steps) override {
-        return rollout_loop(source, alpha_actions, gamma, start_states, end_mask, first_sim_id, seed, n_steps, out_states,
-                            out_actions, out_observations, out_steps, false, -1, nullptr, nullptr);
-    }
-    int rollout_env(int source, const int32_t* alpha_actions, double gamma, const int32_t* start_states, const uint8_t* end_mask,
-                    int end_observation, const int64_t* shifts, uint64_t first_sim_id, uint64_t seed, int64_t n_steps,
-                    int32_t* out_states, int32_t* out_actions, int32_t* out_observations, int32_t* out_steps,
-                    uint8_t* out_lost) override {
-        return rollout_loop(source, alpha_actions, gamma, start_states, end_mask, first_sim_id, seed, n_steps, out_states,
-                            out_actions, out_observations, out_steps, true, end_observation, shifts, out_lost);
     }
 
     // ---- environments (pbvi_env_set_frames / pbvi_env_set_table / pbvi_env_clear) ---- //
@@ -1805,22 +1825,25 @@ class EngineT : public EngineBase {
         return PBVI_OK;
     }
 
-    // The step loop of pbvi_rollout / pbvi_rollout_infotaxis (env == false: the model's own joint draw, the done-filter, the
-    // Bayes step) and of pbvi_rollout_env (env == true: successor from the model, observation from the environment, the Bayes
-    // step cut in two around the lost rule; the norm always summed in block order).
-    int rollout_loop(int source, const int32_t* alpha_actions, double gamma, const int32_t* start_states, const uint8_t* end_mask,
-                     uint64_t first_sim_id, uint64_t seed, int64_t n_steps, int32_t* out_states, int32_t* out_actions,
-                     int32_t* out_observations, int32_t* out_steps, bool env, int end_observation, const int64_t* shifts,
-                     uint8_t* out_lost) {
-        const bool uses_alpha = source != ROLLOUT_INFOTAXIS;
+    // T lock-step simulation steps of the resident block on the device (pbvi_rollout, pbvi_rollout_infotaxis, pbvi_rollout_env).
+    // Per step: the action source's stage with its index left on the device (value-max or Q-values against the resident alpha
+    // set, or the successor entropies of infotaxis_device); the simulator draw (the model's own joint draw, or the successor
+    // from the model and the observation from the environment); the first half of the Bayes step for the rows not done; with
+    // an environment the lost rule on their masses; the done-filter; the norm of the rows that go on.  Finished and lost rows
+    // are dropped after EVERY step ("Device-resident rollouts"): the one host read per step is the survivor count,
+    // which sizes the next step's launches.
+    int rollout(const RolloutCall& call) override {
+        const int source = call.source;
+        const bool env = call.env, uses_alpha = source != ROLLOUT_INFOTAXIS;
+        const int64_t n_steps = call.T;
         if (env && source != ROLLOUT_VALUE_MAX && source != ROLLOUT_Q && source != ROLLOUT_INFOTAXIS)
             FAIL(PBVI_EINVAL, "rollout_env: policy must be 0 (value-max), 1 (Q) or 2 (infotaxis)");
         if (env && env_kind_ == ENV_NONE) FAIL(PBVI_EINVAL, "rollout_env: no environment set (call pbvi_env_set_frames or pbvi_env_set_table)");
-        if (env && end_observation >= O_) FAIL(PBVI_EINVAL, "rollout_env: end_observation is not below O");
-        if (env && shifts && env_kind_ != ENV_FRAMES) FAIL(PBVI_EINVAL, "rollout_env: shifts are for a frame environment, and a table is set");
+        if (env && call.end_observation >= O_) FAIL(PBVI_EINVAL, "rollout_env: end_observation is not below O");
+        if (env && call.shifts && env_kind_ != ENV_FRAMES) FAIL(PBVI_EINVAL, "rollout_env: shifts are for a frame environment, and a table is set");
         if (uses_alpha && V_ <= 0) FAIL(PBVI_EINVAL, "rollout: no alpha set resident (call pbvi_alpha_set)");
         if (B_ <= 0) FAIL(PBVI_EINVAL, "rollout: no belief block resident (call pbvi_beliefs_set)");
-        if ((uses_alpha && !alpha_actions) || !start_states || !end_mask) FAIL(PBVI_EINVAL, "rollout: NULL argument");
+        if ((uses_alpha && !call.alpha_actions) || !call.start_states || !call.end_mask) FAIL(PBVI_EINVAL, "rollout: NULL argument");
         if (source != ROLLOUT_VALUE_MAX && source != ROLLOUT_Q && source != ROLLOUT_INFOTAXIS)
             FAIL(PBVI_EINVAL, "rollout: lookahead must be 0 or 1");
         if (n_steps < 1) FAIL(PBVI_EINVAL, "rollout: T must be at least 1");
@@ -1830,35 +1853,37 @@ class EngineT : public EngineBase {
         if (n_steps >= 0x7fffffff || (n_steps + 1) * n0 > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "rollout: T * B exceeds the int32 trajectory slot index");
         if ((int64_t)S_ * R_ > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "rollout: S*R exceeds int32");
         for (int64_t b = 0; b < n0; ++b)
-            if (start_states[b] < 0 || start_states[b] >= S_) FAIL(PBVI_EINVAL, "rollout: start state out of range [0,S)");
+            if (call.start_states[b] < 0 || call.start_states[b] >= S_) FAIL(PBVI_EINVAL, "rollout: start state out of range [0,S)");
         for (int64_t v = 0; uses_alpha && v < V_; ++v)
-            if (alpha_actions[v] < 0 || alpha_actions[v] >= A_) FAIL(PBVI_EINVAL, "rollout: alpha_actions entry out of range [0,A)");
+            if (call.alpha_actions[v] < 0 || call.alpha_actions[v] >= A_) FAIL(PBVI_EINVAL, "rollout: alpha_actions entry out of range [0,A)");
         if (zero_row_ >= 0)
             FAIL(PBVI_EINVAL, "rollout: RTO[s,a,:,:] sums to 0 for s = " + std::to_string(zero_row_ / A_) + ", a = " +
                                   std::to_string(zero_row_ % A_) + ": nothing can follow that state-action pair");
-        if (env && env_kind_ == ENV_FRAMES) {                 // the reference would index past its data: refused before any launch
+        const bool frames = env && env_kind_ == ENV_FRAMES;
+        if (frames) {                                         // the reference would index past its data: refused before any launch
             int64_t top = 0;
-            for (int64_t b = 0; shifts && b < n0; ++b) {
-                if (shifts[b] < 0) FAIL(PBVI_EINVAL, "rollout_env: negative shift");
-                top = std::max(top, shifts[b]);
+            for (int64_t b = 0; call.shifts && b < n0; ++b) {
+                if (call.shifts[b] < 0) FAIL(PBVI_EINVAL, "rollout_env: negative shift");
+                top = std::max(top, call.shifts[b]);
             }
             if (top > env_F_ || n_steps > env_F_ - top)
                 FAIL(PBVI_EINVAL, "rollout_env: max(shift) + T = " + std::to_string(top) + " + " + std::to_string(n_steps) +
                                       " exceeds the " + std::to_string(env_F_) + " frames of the environment");
         }
         HIPCHK(hipSetDevice(device_));
+        // Infotaxis meets near-ties between actions on symmetric beliefs, and a rollout against an environment promises the same
+        // bits however a run is cut into blocks: neither may hang on the arrival order of the norm's atomics, so their Bayes
+        // step sums the norm in a fixed order.
+        const bool fixed_order = env || source == ROLLOUT_INFOTAXIS;
         int rc;
         if (env) {
             if ((rc = ro_lost_.ensure((size_t)n0))) return rc;
-            if ((rc = bu_mpart_.ensure((size_t)n0 * ((S_ + 255) / 256) * sizeof(double)))) return rc;
-            if ((rc = bu_unnorm_.ensure((size_t)n0 * S_ * sizeof(double)))) return rc;
-            if ((rc = bu_mass_.ensure((size_t)n0 * sizeof(double)))) return rc;
             HIPCHK(hipMemsetAsync(ro_lost_.p, 0, (size_t)n0, stream_));
-            if (env_kind_ == ENV_FRAMES) {
-                if ((rc = env_shift_.ensure((size_t)n0 * sizeof(int64_t)))) return rc;
-                if (shifts) HIPCHK(hipMemcpyAsync(env_shift_.p, shifts, (size_t)n0 * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
-                else HIPCHK(hipMemsetAsync(env_shift_.p, 0, (size_t)n0 * sizeof(int64_t), stream_));
-            }
+        }
+        if (frames) {
+            if ((rc = env_shift_.ensure((size_t)n0 * sizeof(int64_t)))) return rc;
+            if (call.shifts) HIPCHK(hipMemcpyAsync(env_shift_.p, call.shifts, (size_t)n0 * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
+            else HIPCHK(hipMemsetAsync(env_shift_.p, 0, (size_t)n0 * sizeof(int64_t), stream_));
         }
         const size_t n_st = (size_t)(n_steps + 1) * n0, n_ao = (size_t)n_steps * n0, n_traj = n_st + 2 * n_ao + (size_t)n0;
         if ((rc = ro_traj_.ensure(n_traj * sizeof(int32_t)))) return rc;
@@ -1870,11 +1895,8 @@ class EngineT : public EngineBase {
         if ((rc = ro_dst_.ensure((size_t)(n0 + 1) * sizeof(int32_t)))) return rc;
         if (uses_alpha && (rc = ro_aact_.ensure((size_t)V_ * sizeof(int32_t)))) return rc;
         if ((rc = ro_end_.ensure((size_t)S_))) return rc;
-        if ((rc = bu_act_.ensure((size_t)n0 * sizeof(int32_t)))) return rc;
-        if ((rc = bu_obs_.ensure((size_t)n0 * sizeof(int32_t)))) return rc;
-        if ((rc = bu_row_.ensure((size_t)n0 * sizeof(int32_t)))) return rc;
+        if ((rc = bayes_ensure(n0, fixed_order))) return rc;
         if ((rc = build_inverse_lists())) return rc;
-        int* h_count = &words().survivors;
         int32_t* tr_states = ro_traj_.as<int32_t>();
         int32_t* tr_actions = tr_states + n_st;
         int32_t* tr_obs = tr_actions + n_ao;
@@ -1883,93 +1905,90 @@ class EngineT : public EngineBase {
             std::vector<int32_t> iota((size_t)n0), full((size_t)n0, (int32_t)n_steps);
             for (int64_t b = 0; b < n0; ++b) iota[(size_t)b] = (int32_t)b;
             HIPCHK(hipMemsetAsync(ro_traj_.p, 0xFF, (n_traj - (size_t)n0) * sizeof(int32_t), stream_));
-            HIPCHK(hipMemcpyAsync(tr_states, start_states, (size_t)n0 * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+            HIPCHK(hipMemcpyAsync(tr_states, call.start_states, (size_t)n0 * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
             HIPCHK(hipMemcpyAsync(tr_steps, full.data(), (size_t)n0 * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-            HIPCHK(hipMemcpyAsync(ro_state_[0].p, start_states, (size_t)n0 * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+            HIPCHK(hipMemcpyAsync(ro_state_[0].p, call.start_states, (size_t)n0 * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
             HIPCHK(hipMemcpyAsync(ro_orig_[0].p, iota.data(), (size_t)n0 * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-            if (uses_alpha) HIPCHK(hipMemcpyAsync(ro_aact_.p, alpha_actions, (size_t)V_ * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-            HIPCHK(hipMemcpyAsync(ro_end_.p, end_mask, (size_t)S_, hipMemcpyHostToDevice, stream_));
+            if (uses_alpha) HIPCHK(hipMemcpyAsync(ro_aact_.p, call.alpha_actions, (size_t)V_ * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+            HIPCHK(hipMemcpyAsync(ro_end_.p, call.end_mask, (size_t)S_, hipMemcpyHostToDevice, stream_));
             HIPCHK(hipStreamSynchronize(stream_));            // the caller's arrays and the two vectors are free again
         }
+        RolloutEnv renv{};
+        renv.end_observation = call.end_observation;
+        if (frames) {
+            renv.frames = env_frames_.as<uint8_t>();
+            renv.C = (int)env_C_;
+            renv.channel = env_chan_.as<int32_t>();
+            renv.shift = env_shift_.as<int64_t>();
+        } else if (env) {
+            renv.table = env_table_.as<double>();
+        }
+        // True states: live in ro_state_[0]; the draw leaves the next states in [1], row for row, and the filter moves the
+        // survivors' back up into [0].  Trajectory rows: the filter moves them from one ro_orig_ buffer to the other.
+        RolloutStep rs{};
+        rs.n0 = (int)n0;
+        rs.V = (int)V_;
+        rs.seed = call.seed;
+        rs.first_id = call.first_sim_id;
+        rs.alpha_actions = source == ROLLOUT_VALUE_MAX ? ro_aact_.as<int32_t>() : nullptr;
+        rs.state = ro_state_[0].as<int32_t>();
+        rs.end_mask = ro_end_.as<uint8_t>();
+        rs.act_e = bu_act_.as<int32_t>();
+        rs.obs_e = bu_obs_.as<int32_t>();
+        rs.row_e = bu_row_.as<int32_t>();
+        rs.next_state = ro_state_[1].as<int32_t>();
+        rs.keep = ro_keep_.as<uint8_t>();
+        rs.tr_states = tr_states;
+        rs.tr_actions = tr_actions;
+        rs.tr_obs = tr_obs;
+        rs.steps = tr_steps;
+        int* d_count = ro_dst_.as<int>() + n0;
         int oc = 0;
         for (int64_t t = 0; t < n_steps; ++t) {
-            const int32_t* index;
             if (source == ROLLOUT_VALUE_MAX) {
                 if ((rc = value_max_device())) return rc;
-                index = bv2_.as<int32_t>();                   // engine row order, an alpha row: mapped through alpha_actions
+                rs.index = bv2_.as<int32_t>();                // engine row order, an alpha row: mapped through alpha_actions
             } else if (source == ROLLOUT_Q) {
                 q_only_ = true;
                 q_want_best_ = false;
-                rc = backup_run(gamma, 0, nullptr);
+                rc = backup_run(call.gamma, 0, nullptr);
                 q_only_ = false;
                 have_result_ = have_bk_vmax_ = false;
                 if (rc) return rc;
-                index = q_act_.as<int32_t>();                 // caller row order, an action
+                rs.index = q_act_.as<int32_t>();              // caller row order, an action
             } else {
                 if ((rc = infotaxis_device(false, false))) return rc;
-                index = it_act_.as<int32_t>();                // caller row order, an action
+                rs.index = it_act_.as<int32_t>();             // caller row order, an action
             }
-            const int n = (int)B_;
-            const int32_t* perm = sorted_ ? perm_.as<int32_t>() : nullptr;
-            // true states: live in ro_state_[0]; the draw leaves the next states in [1], row for row, and the filter moves
-            // the survivors' back up into [0].  Trajectory rows: the filter moves them from one ro_orig_ buffer to the other.
-            if (!env) {
-                HIPCHK(launch_rollout_draw<T>(n, view(), perm, index, source == ROLLOUT_VALUE_MAX ? ro_aact_.as<int32_t>() : nullptr, (int)V_,
-                                              ro_state_[0].as<int32_t>(), ro_orig_[oc].as<int32_t>(), ro_end_.as<uint8_t>(), seed,
-                                              first_sim_id, (int)t, (int)n0, bu_act_.as<int32_t>(), bu_obs_.as<int32_t>(),
-                                              ro_state_[1].as<int32_t>(), ro_keep_.as<uint8_t>(), tr_states, tr_actions, tr_obs,
-                                              tr_steps, stream_));
-            } else {
-                // draw (bu_row_: provisional, -1 = done), push and fold of the rows not done, then the lost rule on their masses
-                const bool fr = env_kind_ == ENV_FRAMES;
-                HIPCHK(launch_rollout_draw_env<T>(n, view(), perm, index, source == ROLLOUT_VALUE_MAX ? ro_aact_.as<int32_t>() : nullptr,
-                                                  (int)V_, ro_state_[0].as<int32_t>(), ro_orig_[oc].as<int32_t>(), ro_end_.as<uint8_t>(),
-                                                  end_observation, fr ? env_frames_.as<uint8_t>() : nullptr, (int)env_C_,
-                                                  fr ? env_chan_.as<int32_t>() : nullptr, fr ? env_shift_.as<int64_t>() : nullptr,
-                                                  fr ? nullptr : env_table_.as<double>(), seed, first_sim_id, (int)t, (int)n0,
-                                                  bu_act_.as<int32_t>(), bu_obs_.as<int32_t>(), bu_row_.as<int32_t>(),
-                                                  ro_state_[1].as<int32_t>(), ro_keep_.as<uint8_t>(), tr_states, tr_actions, tr_obs,
-                                                  tr_steps, stream_));
-                HIPCHK(launch_belief_push_fold<T>(bel_.as<T>(), S_pad_, n, view(), in_ptr_.as<int32_t>(), in_src_.as<int32_t>(),
-                                                  bu_act_.as<int32_t>(), bu_obs_.as<int32_t>(), bu_row_.as<int32_t>(),
-                                                  bu_unnorm_.as<double>(), bu_mass_.as<double>(), bu_mpart_.as<double>(), stream_));
-                HIPCHK(launch_rollout_lost(n, perm, ro_orig_[oc].as<int32_t>(), bu_mass_.as<double>(), (int)t, ro_keep_.as<uint8_t>(),
-                                           tr_steps, ro_lost_.as<uint8_t>(), stream_));
-            }
-            HIPCHK(launch_rollout_compact(n, ro_keep_.as<uint8_t>(), perm, ro_state_[1].as<int32_t>(),
-                                          ro_orig_[oc].as<int32_t>(), ro_dst_.as<int32_t>(), bu_row_.as<int32_t>(),
-                                          ro_state_[0].as<int32_t>(), ro_orig_[oc ^ 1].as<int32_t>(),
-                                          ro_dst_.as<int>() + n0, stream_));
+            rs.n = (int)B_;
+            rs.t = (int)t;
+            rs.perm = sorted_ ? perm_.as<int32_t>() : nullptr;
+            rs.orig = ro_orig_[oc].as<int32_t>();
+            // draw (bu_row_: provisional, -1 = done), push of the rows not done, then the lost rule on their masses
+            HIPCHK(launch_rollout_draw<T>(rs, view(), env ? &renv : nullptr, stream_));
+            if ((rc = bayes_push(rs.row_e, fixed_order))) return rc;
+            if (env) HIPCHK(launch_rollout_lost(rs, bu_mass_.as<double>(), ro_lost_.as<uint8_t>(), stream_));
+            HIPCHK(launch_rollout_compact(rs, ro_dst_.as<int32_t>(), ro_state_[0].as<int32_t>(), ro_orig_[oc ^ 1].as<int32_t>(),
+                                          d_count, stream_));
             oc ^= 1;
-            HIPCHK(hipMemcpyAsync(h_count, ro_dst_.as<int>() + n0, sizeof(int), hipMemcpyDeviceToHost, stream_));
+            int* h_count = &words().survivors;
+            HIPCHK(hipMemcpyAsync(h_count, d_count, sizeof(int), hipMemcpyDeviceToHost, stream_));
             HIPCHK(hipStreamSynchronize(stream_));
             const int64_t nb = *h_count;
-            if (nb < 0 || nb > n) FAIL(PBVI_ERUNTIME, "rollout: survivor count out of range");
+            if (nb < 0 || nb > rs.n) FAIL(PBVI_ERUNTIME, "rollout: survivor count out of range");
             if (nb == 0) {                                    // every simulation finished
-                B_ = 0;
-                B_pad_ = 0;
-                sorted_ = false;
-                have_result_ = false;
+                block_emptied();
                 break;
             }
-            // (infotaxis meets near-ties between actions on symmetric beliefs: its trajectories must not hang on the
-            // arrival order of the norm's atomics, so its Bayes step sums the norm in a fixed order)
-            if (!env) {
-                if ((rc = advance_resident(nb, false, source == ROLLOUT_INFOTAXIS))) return rc;
-            } else {                                          // the norm of the rows that go on (bu_row_: now the filter's rows)
-                if ((rc = stage_.ensure((size_t)nb * S_pad_ * sizeof(T)))) return rc;
-                HIPCHK(hipMemsetAsync(stage_.p, 0, (size_t)nb * S_pad_ * sizeof(T), stream_));   // pad columns stay zero
-                HIPCHK(launch_belief_norm<T>(n, S_, bu_unnorm_.as<double>(), bu_mass_.as<double>(), bu_row_.as<int32_t>(),
-                                             stage_.as<T>(), S_pad_, stream_));
-                if ((rc = beliefs_finish(nb, stage_.as<T>(), nullptr))) return rc;
-            }
+            // the norm of the rows that go on (bu_row_: now the filter's rows)
+            if ((rc = bayes_norm_finish(nb, false))) return rc;
         }
-        if (env && out_lost) HIPCHK(hipMemcpyAsync(out_lost, ro_lost_.p, (size_t)n0, hipMemcpyDeviceToHost, stream_));
+        if (env && call.out_lost) HIPCHK(hipMemcpyAsync(call.out_lost, ro_lost_.p, (size_t)n0, hipMemcpyDeviceToHost, stream_));
         const int32_t* src[4] = {tr_states, tr_actions, tr_obs, tr_steps};
-        int32_t* dsts[4] = {out_states, out_actions, out_observations, out_steps};
+        int32_t* dsts[4] = {call.out_states, call.out_actions, call.out_observations, call.out_steps};
         const size_t len[4] = {n_st, n_ao, n_ao, (size_t)n0};
         // one transfer of the whole trajectory buffer into the pinned staging area, then host copies of the parts asked for
-        if (out_states || out_actions || out_observations || out_steps) {
+        if (dsts[0] || dsts[1] || dsts[2] || dsts[3]) {
             if ((rc = stage_reserve(n_traj * sizeof(int32_t)))) return rc;
             HIPCHK(hipMemcpyAsync(host_stage_.p, ro_traj_.p, n_traj * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
             HIPCHK(hipStreamSynchronize(stream_));
@@ -2377,16 +2396,15 @@ class EngineT : public EngineBase {
         env_kind_ = ENV_NONE;                                // (its buffers were working buffers)
         env_F_ = env_C_ = 0;
         V_ = 0;
-        B_ = B_pad_ = 0;
+        block_emptied();
         prim_valid_ = alpha_on_primary_ = false;
         prim_ids_.clear();
         prim_off_ = 0;
         store_rows_[0] = store_rows_[1] = 0;
         snz_rows_ = sbt_rows_ = 0;
         walk_rows_ = 0;
-        have_result_ = have_bk_vmax_ = false;
+        have_bk_vmax_ = false;
         btl_valid_ = false;
-        sorted_ = false;
         h_perm_valid_ = false;
         mat_V_ = -1;
         gam_pad_ptr_ = nullptr;
@@ -4962,14 +4980,33 @@ int pbvi_engine_set_rto_f64(pbvi_engine_t* e, const double* rto) {
     return e->impl->set_rto_f64(rto);
 }
 
+// What every rollout entry point takes: the simulations, the stream, the length and the trajectory arrays
+static pbvi::RolloutCall rollout_call(const int32_t* start_states, const uint8_t* end_mask, uint64_t first_sim_id, uint64_t seed,
+                                      int64_t T, int32_t* out_states, int32_t* out_actions, int32_t* out_observations,
+                                      int32_t* out_steps) {
+    pbvi::RolloutCall c{};
+    c.start_states = start_states;
+    c.end_mask = end_mask;
+    c.first_sim_id = first_sim_id;
+    c.seed = seed;
+    c.T = T;
+    c.out_states = out_states;
+    c.out_actions = out_actions;
+    c.out_observations = out_observations;
+    c.out_steps = out_steps;
+    return c;
+}
+
 int pbvi_rollout(pbvi_engine_t* e, const int32_t* alpha_actions, int lookahead, double gamma, const int32_t* start_states,
                  const uint8_t* end_mask, uint64_t first_sim_id, uint64_t seed, int64_t T, int32_t* out_states,
                  int32_t* out_actions, int32_t* out_observations, int32_t* out_steps) {
     NEED(e);
     // (any other lookahead is refused by the step loop as a source it does not know)
-    const int source = lookahead == 0 ? pbvi::ROLLOUT_VALUE_MAX : lookahead == 1 ? pbvi::ROLLOUT_Q : -1;
-    return e->impl->rollout(source, alpha_actions, gamma, start_states, end_mask, first_sim_id, seed, T, out_states, out_actions,
-                            out_observations, out_steps);
+    pbvi::RolloutCall c = rollout_call(start_states, end_mask, first_sim_id, seed, T, out_states, out_actions, out_observations, out_steps);
+    c.source = lookahead == 0 ? pbvi::ROLLOUT_VALUE_MAX : lookahead == 1 ? pbvi::ROLLOUT_Q : -1;
+    c.alpha_actions = alpha_actions;
+    c.gamma = gamma;
+    return e->impl->rollout(c);
 }
 int pbvi_infotaxis(pbvi_engine_t* e, double* out_g, int32_t* out_action, double* out_p_obs, double* out_entropy) {
     NEED(e);
@@ -4979,8 +5016,9 @@ int pbvi_rollout_infotaxis(pbvi_engine_t* e, const int32_t* start_states, const 
                            uint64_t seed, int64_t T, int32_t* out_states, int32_t* out_actions, int32_t* out_observations,
                            int32_t* out_steps) {
     NEED(e);
-    return e->impl->rollout(pbvi::ROLLOUT_INFOTAXIS, nullptr, 0.0, start_states, end_mask, first_sim_id, seed, T, out_states,
-                            out_actions, out_observations, out_steps);
+    pbvi::RolloutCall c = rollout_call(start_states, end_mask, first_sim_id, seed, T, out_states, out_actions, out_observations, out_steps);
+    c.source = pbvi::ROLLOUT_INFOTAXIS;
+    return e->impl->rollout(c);
 }
 int pbvi_env_set_frames(pbvi_engine_t* e, const uint8_t* frames, int64_t F, int64_t C, const int32_t* channel_of_action) {
     NEED(e);
@@ -4999,8 +5037,15 @@ int pbvi_rollout_env(pbvi_engine_t* e, int policy, const int32_t* alpha_actions,
                      int64_t T, int32_t* out_states, int32_t* out_actions, int32_t* out_observations, int32_t* out_steps,
                      uint8_t* out_lost) {
     NEED(e);
-    return e->impl->rollout_env(policy, alpha_actions, gamma, start_states, end_mask, end_observation, shifts, first_sim_id, seed,
-                                T, out_states, out_actions, out_observations, out_steps, out_lost);
+    pbvi::RolloutCall c = rollout_call(start_states, end_mask, first_sim_id, seed, T, out_states, out_actions, out_observations, out_steps);
+    c.source = policy;
+    c.alpha_actions = alpha_actions;
+    c.gamma = gamma;
+    c.env = true;
+    c.end_observation = end_observation;
+    c.shifts = shifts;
+    c.out_lost = out_lost;
+    return e->impl->rollout(c);
 }
 int pbvi_beliefs_fetch(pbvi_engine_t* e, void* out_beliefs) {
     NEED(e);

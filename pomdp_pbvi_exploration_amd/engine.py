@@ -1126,10 +1126,18 @@ class Engine:
         simulation's last step.  Afterwards the resident block holds the beliefs of the simulations still running
         (``self.B`` of them; ``fetch_beliefs``)."""
         aa = np.ascontiguousarray(alpha_actions, dtype=np.int32)
-        ss = np.ascontiguousarray(start_states, dtype=np.int32)
-        em = np.ascontiguousarray(end_mask, dtype=np.uint8)
         if aa.shape != (self.alpha_count,):
             raise ValueError('alpha_actions must be [V]')
+        aap = aa.ctypes.data_as(C.POINTER(C.c_int32))
+        return self._rollout_call(lambda ss, em, *tail: self._lib.pbvi_rollout(self._h, aap, int(lookahead), float(gamma), ss, em, *tail),
+                                  start_states, end_mask, seed, T, first_sim_id)
+
+    def _rollout_call(self, call, start_states, end_mask, seed: int, T: int, first_sim_id: int, with_lost: bool = False):
+        """What ``rollout``, ``rollout_infotaxis`` and ``rollout_env`` share: the checks of the simulations and the stream, the
+        trajectory arrays (none for a ``T`` the engine refuses), ``call(start_states, end_mask, first_sim_id, seed, T, *arrays)``
+        on their pointers, and the block that is resident afterwards."""
+        ss = np.ascontiguousarray(start_states, dtype=np.int32)
+        em = np.ascontiguousarray(end_mask, dtype=np.uint8)
         if ss.shape != (self.B,):
             raise ValueError('start_states must be [B]')
         if em.shape != (self.S,):
@@ -1143,45 +1151,20 @@ class Engine:
             observations = np.empty((T, B), dtype=np.int32)
         else:                                    # the call refuses these: nothing is written
             states = actions = observations = np.empty((0, B), dtype=np.int32)
-        steps = np.empty(B, dtype=np.int32)
-        i32p = C.POINTER(C.c_int32)
+        out = (states, actions, observations, np.empty(B, dtype=np.int32)) + ((np.empty(B, dtype=np.uint8),) if with_lost else ())
+        i32p, u8p = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
         self._resident['belief'] = None
-        self._ck(self._lib.pbvi_rollout(self._h, aa.ctypes.data_as(i32p), int(lookahead), float(gamma),
-                                        ss.ctypes.data_as(i32p), em.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                        int(first_sim_id), int(seed), T, states.ctypes.data_as(i32p),
-                                        actions.ctypes.data_as(i32p), observations.ctypes.data_as(i32p),
-                                        steps.ctypes.data_as(i32p)))
+        self._ck(call(ss.ctypes.data_as(i32p), em.ctypes.data_as(u8p), int(first_sim_id), int(seed), T,
+                      *[x.ctypes.data_as(u8p if x.dtype == np.uint8 else i32p) for x in out]))
         self.B = int(self._lib.pbvi_beliefs_count(self._h))
-        return states, actions, observations, steps
+        return out
 
     def rollout_infotaxis(self, start_states, end_mask, seed: int, T: int, first_sim_id: int = 0):
         """``rollout`` with the infotaxis policy (``pbvi_rollout_infotaxis``): every step takes the action with the smallest
         expected entropy of the next belief (``infotaxis_resident``'s argmin) instead of asking an alpha set.  Same draws,
         same done rule, same return value and same state of the resident block afterwards as ``rollout``."""
-        ss = np.ascontiguousarray(start_states, dtype=np.int32)
-        em = np.ascontiguousarray(end_mask, dtype=np.uint8)
-        if ss.shape != (self.B,):
-            raise ValueError('start_states must be [B]')
-        if em.shape != (self.S,):
-            raise ValueError('end_mask must be [S]')
-        if not (0 <= int(seed) < 1 << 64 and 0 <= int(first_sim_id) < 1 << 64):
-            raise ValueError('seed and first_sim_id must fit an unsigned 64-bit integer')
-        T, B = int(T), self.B
-        if T >= 1 and (T + 1) * B <= 0x7fffffff:
-            states = np.empty((T + 1, B), dtype=np.int32)
-            actions = np.empty((T, B), dtype=np.int32)
-            observations = np.empty((T, B), dtype=np.int32)
-        else:                                    # the call refuses these: nothing is written
-            states = actions = observations = np.empty((0, B), dtype=np.int32)
-        steps = np.empty(B, dtype=np.int32)
-        i32p = C.POINTER(C.c_int32)
-        self._resident['belief'] = None
-        self._ck(self._lib.pbvi_rollout_infotaxis(self._h, ss.ctypes.data_as(i32p), em.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                  int(first_sim_id), int(seed), T, states.ctypes.data_as(i32p),
-                                                  actions.ctypes.data_as(i32p), observations.ctypes.data_as(i32p),
-                                                  steps.ctypes.data_as(i32p)))
-        self.B = int(self._lib.pbvi_beliefs_count(self._h))
-        return states, actions, observations, steps
+        return self._rollout_call(lambda *args: self._lib.pbvi_rollout_infotaxis(self._h, *args), start_states, end_mask, seed, T,
+                                  first_sim_id)
 
     def set_environment_frames(self, frames, channel_of_action) -> None:
         """The observation source of ``rollout_env``: recorded frames ``[F, C, S]`` uint8 (``frames[f, c, s]`` = the observation
@@ -1238,44 +1221,20 @@ class Engine:
         ``shifts`` ``[B]``: the frame each simulation starts at (frames only).  Returns ``(states, actions, observations,
         steps, lost)``: ``rollout``'s four arrays and ``lost [B]`` uint8."""
         policy = int(policy)
-        ss = np.ascontiguousarray(start_states, dtype=np.int32)
-        em = np.ascontiguousarray(end_mask, dtype=np.uint8)
-        i32p, u8p = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
-        aap = None
+        aap = shp = None
         if alpha_actions is not None:
             aa = np.ascontiguousarray(alpha_actions, dtype=np.int32)
             if policy != 2 and aa.shape != (self.alpha_count,):
                 raise ValueError('alpha_actions must be [V]')
-            aap = aa.ctypes.data_as(i32p)
-        if ss.shape != (self.B,):
-            raise ValueError('start_states must be [B]')
-        if em.shape != (self.S,):
-            raise ValueError('end_mask must be [S]')
-        if not (0 <= int(seed) < 1 << 64 and 0 <= int(first_sim_id) < 1 << 64):
-            raise ValueError('seed and first_sim_id must fit an unsigned 64-bit integer')
-        shp = None
+            aap = aa.ctypes.data_as(C.POINTER(C.c_int32))
         if shifts is not None:
             sh = np.ascontiguousarray(shifts, dtype=np.int64)
             if sh.shape != (self.B,):
                 raise ValueError('shifts must be [B]')
             shp = sh.ctypes.data_as(C.POINTER(C.c_int64))
-        T, B = int(T), self.B
-        if T >= 1 and (T + 1) * B <= 0x7fffffff:
-            states = np.empty((T + 1, B), dtype=np.int32)
-            actions = np.empty((T, B), dtype=np.int32)
-            observations = np.empty((T, B), dtype=np.int32)
-        else:                                    # the call refuses these: nothing is written
-            states = actions = observations = np.empty((0, B), dtype=np.int32)
-        steps = np.empty(B, dtype=np.int32)
-        lost = np.empty(B, dtype=np.uint8)
-        self._resident['belief'] = None
-        self._ck(self._lib.pbvi_rollout_env(self._h, policy, aap, float(gamma), ss.ctypes.data_as(i32p), em.ctypes.data_as(u8p),
-                                            int(end_observation), shp, int(first_sim_id), int(seed), T,
-                                            states.ctypes.data_as(i32p), actions.ctypes.data_as(i32p),
-                                            observations.ctypes.data_as(i32p), steps.ctypes.data_as(i32p),
-                                            lost.ctypes.data_as(u8p)))
-        self.B = int(self._lib.pbvi_beliefs_count(self._h))
-        return states, actions, observations, steps, lost
+        return self._rollout_call(lambda ss, em, *tail: self._lib.pbvi_rollout_env(self._h, policy, aap, float(gamma), ss, em,
+                                                                                   int(end_observation), shp, *tail),
+                                  start_states, end_mask, seed, T, first_sim_id, with_lost=True)
 
     def fetch_beliefs(self) -> np.ndarray:
         """The resident belief block, ``[B,S]`` in caller order."""

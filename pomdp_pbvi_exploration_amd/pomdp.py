@@ -1189,6 +1189,37 @@ def rollout_draw(rows: np.ndarray, u: np.ndarray) -> np.ndarray:
     return k
 
 
+def _rollout_inputs(model, beliefs, start_states, T: int, alpha=None, alpha_actions=None, one_message: bool = False):
+    """The inputs every host rollout takes, validated: ``(tables, T, beliefs [n,S] fp64 (a copy), start states [n] int64, alpha
+    [V,S] fp64, alpha_actions [V] int64)``, the last two ``None`` when no alpha set is given.  ``one_message``:
+    ``rollout_numpy``'s wording for a wrong shape of ``beliefs`` or ``alpha``."""
+    m = _rollout_tables(model)
+    S, A = m.state_count, m.action_count
+    T = int(T)
+    if T < 1:
+        raise ValueError('T must be at least 1')
+    b = np.array(beliefs, dtype=np.float64)
+    s = np.asarray(start_states).astype(np.int64)
+    acts = None
+    if alpha is not None:
+        alpha = np.asarray(alpha, dtype=np.float64)
+        acts = np.asarray(alpha_actions).astype(np.int64)
+    n = b.shape[0]
+    bad_b = b.ndim != 2 or b.shape[1] != S
+    bad_alpha = alpha is not None and (alpha.ndim != 2 or alpha.shape[1] != S)
+    if one_message and (bad_b or bad_alpha):
+        raise ValueError(f'beliefs and alpha must be [*, {S}] arrays')
+    if bad_b:
+        raise ValueError(f'beliefs must be a [*, {S}] array')
+    if s.shape != (n,) or (n and (s.min() < 0 or s.max() >= S)):
+        raise ValueError('start_states must be [n] with entries in [0, S)')
+    if bad_alpha:
+        raise ValueError(f'alpha must be a [*, {S}] array')
+    if alpha is not None and (acts.shape != (alpha.shape[0],) or acts.min() < 0 or acts.max() >= A):
+        raise ValueError('alpha_actions must be [V] with entries in [0, A)')
+    return m, T, b, s, alpha, acts
+
+
 def rollout_numpy(model, alpha, alpha_actions, beliefs, start_states, seed: int, first_sim_id: int, T: int,
                   lookahead: int = 0, gamma: float = 0.99, table_dtype=np.float64, return_beliefs: bool = False):
     """``T`` lock-step simulation steps with counter-based draws, on the host: what ``pbvi_rollout`` computes on the device.
@@ -1202,24 +1233,9 @@ def rollout_numpy(model, alpha, alpha_actions, beliefs, start_states, seed: int,
     ``[n_running, S]`` beliefs of the simulations still running, in order.  A trajectory depends on its own row and id
     only, so a run cut into chunks (``first_sim_id`` advanced by the rows before) returns the same rows."""
     from types import SimpleNamespace
-    m = _rollout_tables(model)
-    S, A, O, R = m.state_count, m.action_count, m.observation_count, m.reachable_state_count
     if lookahead not in (0, 1):
         raise ValueError(f'lookahead must be 0 or 1, not {lookahead!r}')
-    T = int(T)
-    if T < 1:
-        raise ValueError('T must be at least 1')
-    alpha = np.asarray(alpha, dtype=np.float64)
-    acts = np.asarray(alpha_actions).astype(np.int64)
-    b = np.array(beliefs, dtype=np.float64)
-    s = np.asarray(start_states).astype(np.int64)
-    n = b.shape[0]
-    if b.ndim != 2 or b.shape[1] != S or alpha.ndim != 2 or alpha.shape[1] != S:
-        raise ValueError(f'beliefs and alpha must be [*, {S}] arrays')
-    if s.shape != (n,) or (n and (s.min() < 0 or s.max() >= S)):
-        raise ValueError('start_states must be [n] with entries in [0, S)')
-    if acts.shape != (alpha.shape[0],) or acts.min() < 0 or acts.max() >= A:
-        raise ValueError('alpha_actions must be [V] with entries in [0, A)')
+    m, T, b, s, alpha, acts = _rollout_inputs(model, beliefs, start_states, T, alpha, alpha_actions, one_message=True)
     block = _HostBeliefBlock(m, SimpleNamespace(alpha_vector_array=alpha), b)
     choose = (lambda: block.best_actions(gamma)) if lookahead == 1 else (lambda: acts[block.best_vectors()])
     return _rollout_loop(m, block, choose, s, seed, first_sim_id, T, table_dtype, return_beliefs)
@@ -1405,37 +1421,21 @@ def rollout_env_numpy(model, env, policy: int, alpha, alpha_actions, beliefs, st
     recorded ``a``, ``o``, ``s'``, no NaN belief), and any other is normalised.  ``env.shifts`` belong to the rows given.
     Returns ``rollout_numpy``'s arrays and then ``lost [n]`` uint8."""
     from types import SimpleNamespace
-    m = _rollout_tables(model)
-    S, A, O = m.state_count, m.action_count, m.observation_count
     if policy not in (0, 1, 2):
         raise ValueError(f'policy must be 0 (value-max), 1 (Q) or 2 (infotaxis), not {policy!r}')
     if not isinstance(env, (FrameEnvironment, TableEnvironment)):
         raise ValueError('env must be a FrameEnvironment or a TableEnvironment')
-    T = int(T)
-    if T < 1:
-        raise ValueError('T must be at least 1')
-    if T >= 1 << 31:
+    if int(T) >= 1 << 31:
         raise ValueError('T must be below 2**31')
-    b = np.array(beliefs, dtype=np.float64)
-    s = np.asarray(start_states).astype(np.int64)
-    n = b.shape[0]
-    if b.ndim != 2 or b.shape[1] != S:
-        raise ValueError(f'beliefs must be a [*, {S}] array')
-    if s.shape != (n,) or (n and (s.min() < 0 or s.max() >= S)):
-        raise ValueError('start_states must be [n] with entries in [0, S)')
+    m, T, b, s, alpha, acts = _rollout_inputs(model, beliefs, start_states, T,
+                                              None if policy == 2 else np.asarray(alpha, dtype=np.float64), alpha_actions)
     if policy == 2:
         block = _HostBeliefBlock(m, None, b)
         choose = lambda: block.infotaxis_actions(table_dtype)
     else:
-        alpha = np.asarray(alpha, dtype=np.float64)
-        acts = np.asarray(alpha_actions).astype(np.int64)
-        if alpha.ndim != 2 or alpha.shape[1] != S:
-            raise ValueError(f'alpha must be a [*, {S}] array')
-        if acts.shape != (alpha.shape[0],) or acts.min() < 0 or acts.max() >= A:
-            raise ValueError('alpha_actions must be [V] with entries in [0, A)')
         block = _HostBeliefBlock(m, SimpleNamespace(alpha_vector_array=alpha), b)
         choose = (lambda: block.best_actions(gamma)) if policy == 1 else (lambda: acts[block.best_vectors()])
-    shifts = env.check(S, A, O, n, T)
+    shifts = env.check(m.state_count, m.action_count, m.observation_count, b.shape[0], T)
     end_obs = env.end_observation
 
     def observe(t, rows, ids, a, sn, done):
@@ -1517,18 +1517,7 @@ def rollout_infotaxis_numpy(model, beliefs, start_states, seed: int, first_sim_i
     """``rollout_numpy`` with the infotaxis policy, on the host: what ``pbvi_rollout_infotaxis`` computes on the device.
     Per step and running simulation the action is ``infotaxis_numpy(model, b, table_dtype)``'s; the uniform, the draw, the
     Bayes update, the done-filter and the return value are ``rollout_numpy``'s."""
-    m = _rollout_tables(model)
-    S = m.state_count
-    T = int(T)
-    if T < 1:
-        raise ValueError('T must be at least 1')
-    b = np.array(beliefs, dtype=np.float64)
-    s = np.asarray(start_states).astype(np.int64)
-    n = b.shape[0]
-    if b.ndim != 2 or b.shape[1] != S:
-        raise ValueError(f'beliefs must be a [*, {S}] array')
-    if s.shape != (n,) or (n and (s.min() < 0 or s.max() >= S)):
-        raise ValueError('start_states must be [n] with entries in [0, S)')
+    m, T, b, s, _, _ = _rollout_inputs(model, beliefs, start_states, T)
     block = _HostBeliefBlock(m, None, b)
     return _rollout_loop(m, block, lambda: block.infotaxis_actions(table_dtype), s, seed, first_sim_id, T, table_dtype,
                          return_beliefs)
@@ -1851,55 +1840,55 @@ class Agent:
 
     ROLLOUT_CHUNK = 65535            # simulations per ``pbvi_rollout`` call: the engine's belief block limit
 
-    def _counter_trajectories(self, model: Model, b0: np.ndarray, start_states: np.ndarray, seed: int, T: int):
-        """``(states, actions, observations, steps)`` of the counter-based rollout of this agent's policy."""
-        vf = self.value_function
-        n = b0.shape[0]
-        if vf.is_on_gpu:
-            eng = model.engine
-            eng.sync_rows('alpha', vf.alpha_vector_list, lambda v: v.values)
-            end_mask = np.zeros(model.state_count, dtype=np.uint8)
-            end_mask[np.asarray(model.end_states, dtype=np.int64)] = 1
-            parts = []
-            for i0 in range(0, n, self.ROLLOUT_CHUNK):
-                eng.set_beliefs(b0[i0:i0 + self.ROLLOUT_CHUNK])
-                parts.append(eng.rollout(vf.actions, start_states[i0:i0 + self.ROLLOUT_CHUNK], end_mask, seed, T,
-                                         first_sim_id=i0, lookahead=self.lookahead, gamma=self.gamma))
-            states, actions, observations = (np.concatenate([p[k] for p in parts], axis=1) for k in range(3))
-            steps = np.concatenate([p[3] for p in parts])
-        else:
-            states, actions, observations, steps = rollout_numpy(model, vf.alpha_vector_array, vf.actions, b0, start_states,
-                                                                 seed, 0, T, self.lookahead, self.gamma)
-        return states, actions, observations, steps
-
     def _env_policy(self) -> int:
-        """This agent's policy as ``pbvi_rollout_env`` numbers it."""
+        """This agent's policy as ``pbvi_rollout_env`` numbers it: 0 value-max, 1 Q, 2 infotaxis."""
         return self.lookahead
 
-    def _env_trajectories(self, model: Model, b0: np.ndarray, start_states: np.ndarray, seed: int, T: int, env):
-        """``(states, actions, observations, steps, lost)`` of the counter-based rollout of this agent's policy against
-        ``env``: on the device when the agent is, ``ROLLOUT_CHUNK`` simulations per call with the shifts sliced alongside."""
-        policy, vf, n = self._env_policy(), self.value_function, b0.shape[0]
+    @staticmethod
+    def _end_mask(model: Model) -> np.ndarray:
+        mask = np.zeros(model.state_count, dtype=np.uint8)
+        mask[np.asarray(model.end_states, dtype=np.int64)] = 1
+        return mask
+
+    def _rollout_chunks(self, eng, b0: np.ndarray, start_states: np.ndarray, shifts, call):
+        """The chunk loop of the device rollouts: ``ROLLOUT_CHUNK`` simulations at a time become the engine's belief block and
+        ``call(start_states, first_sim_id, shifts)`` -- their rows of both, ``shifts`` may be ``None`` -- runs them; the 4 or 5
+        arrays of the chunks, joined along the simulations."""
+        parts = []
+        for i0 in range(0, b0.shape[0], self.ROLLOUT_CHUNK):
+            i1 = i0 + self.ROLLOUT_CHUNK
+            eng.set_beliefs(b0[i0:i1])
+            parts.append(call(start_states[i0:i1], i0, None if shifts is None else shifts[i0:i1]))
+        return tuple(np.concatenate([p[k] for p in parts], axis=-1) for k in range(len(parts[0])))
+
+    def _counter_trajectories(self, model: Model, b0: np.ndarray, start_states: np.ndarray, seed: int, T: int, env=None):
+        """``(states, actions, observations, steps)`` of the counter-based rollout of this agent's policy, against ``env`` with
+        ``lost`` behind them: on the device when the agent is (the environment uploaded once: later calls with the same arrays
+        find it there), else on the host."""
+        policy, vf = self._env_policy(), self.value_function
         alpha, acts = (None, None) if policy == 2 else (vf.alpha_vector_array, vf.actions)
         if not self._on_gpu():
-            return rollout_env_numpy(model, env, policy, alpha, acts, b0, start_states, seed, 0, T, self.gamma)
-        env.check(model.state_count, model.action_count, model.observation_count, n, T)
-        eng = model.engine
+            if env is not None:
+                return rollout_env_numpy(model, env, policy, alpha, acts, b0, start_states, seed, 0, T, self.gamma)
+            if policy == 2:
+                return rollout_infotaxis_numpy(model, b0, start_states, seed, 0, T)
+            return rollout_numpy(model, alpha, acts, b0, start_states, seed, 0, T, self.lookahead, self.gamma)
+        shifts = None
+        if env is not None:
+            shifts = env.check(model.state_count, model.action_count, model.observation_count, b0.shape[0], T)
+        eng, end_mask = model.engine, self._end_mask(model)
         if policy != 2:
             eng.sync_rows('alpha', vf.alpha_vector_list, lambda v: v.values)
-        end_mask = np.zeros(model.state_count, dtype=np.uint8)
-        end_mask[np.asarray(model.end_states, dtype=np.int64)] = 1
-        frames = isinstance(env, FrameEnvironment)
-        eng.hold_environment(env)                               # uploaded once; later calls with the same arrays find it there
-        parts = []
-        for i0 in range(0, n, self.ROLLOUT_CHUNK):
-            i1 = min(n, i0 + self.ROLLOUT_CHUNK)
-            eng.set_beliefs(b0[i0:i1])
-            shifts = np.broadcast_to(env.rows(i0, i1).shifts, (i1 - i0,)) if frames else None
-            parts.append(eng.rollout_env(policy, acts, start_states[i0:i1], end_mask, seed, T, first_sim_id=i0,
-                                         gamma=self.gamma, shifts=shifts, end_observation=env.end_observation))
-        states, actions, observations = (np.concatenate([p[k] for p in parts], axis=1) for k in range(3))
-        return states, actions, observations, np.concatenate([p[3] for p in parts]), np.concatenate([p[4] for p in parts])
+        if env is not None:
+            eng.hold_environment(env)
+            call = lambda s0, first, sh: eng.rollout_env(policy, acts, s0, end_mask, seed, T, first_sim_id=first, gamma=self.gamma,
+                                                         shifts=sh, end_observation=env.end_observation)
+        elif policy == 2:
+            call = lambda s0, first, sh: eng.rollout_infotaxis(s0, end_mask, seed, T, first_sim_id=first)
+        else:
+            call = lambda s0, first, sh: eng.rollout(acts, s0, end_mask, seed, T, first_sim_id=first, lookahead=self.lookahead,
+                                                     gamma=self.gamma)
+        return self._rollout_chunks(eng, b0, start_states, shifts, call)
 
     def _run_counter_rollouts(self, model: Model, simulator_set: SimulationSet, b0: np.ndarray, start_states: np.ndarray,
                               seed: int, max_steps: int, reward_discount: float, print_stats: bool, environment=None):
@@ -1908,11 +1897,9 @@ class Agent:
         the rewards from the recorded ``(s, a, s', o)`` afterwards, the result in ``run_n_simulations_parallel``'s form."""
         n, T = b0.shape[0], int(max_steps)
         t0 = datetime.now()
-        lost = np.zeros(n, dtype=np.uint8)
-        if environment is None:
-            states, actions, observations, steps = self._counter_trajectories(model, b0, start_states, seed, T)
-        else:
-            states, actions, observations, steps, lost = self._env_trajectories(model, b0, start_states, seed, T, environment)
+        out = self._counter_trajectories(model, b0, start_states, seed, T, environment)
+        states, actions, observations, steps = out[:4]
+        lost = out[4] if environment is not None else np.zeros(n, dtype=np.uint8)
         ran = actions >= 0                                       # [T, n] steps that were taken
         rewards_history = np.zeros((T, n))
         if ran.any():
@@ -1973,20 +1960,6 @@ class Infotaxis_Agent(Agent):
         else:
             acts = infotaxis_numpy(self.model, arr)[1]
         return int(acts[0]) if single else acts
-
-    def _counter_trajectories(self, model: Model, b0: np.ndarray, start_states: np.ndarray, seed: int, T: int):
-        n = b0.shape[0]
-        if not model.is_on_gpu:
-            return rollout_infotaxis_numpy(model, b0, start_states, seed, 0, T)
-        eng = model.engine
-        end_mask = np.zeros(model.state_count, dtype=np.uint8)
-        end_mask[np.asarray(model.end_states, dtype=np.int64)] = 1
-        parts = []
-        for i0 in range(0, n, self.ROLLOUT_CHUNK):
-            eng.set_beliefs(b0[i0:i0 + self.ROLLOUT_CHUNK])
-            parts.append(eng.rollout_infotaxis(start_states[i0:i0 + self.ROLLOUT_CHUNK], end_mask, seed, T, first_sim_id=i0))
-        states, actions, observations = (np.concatenate([p[k] for p in parts], axis=1) for k in range(3))
-        return states, actions, observations, np.concatenate([p[3] for p in parts])
 
 
 # --------------------------------------------------------------------------- #
