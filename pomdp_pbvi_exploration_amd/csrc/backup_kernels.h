@@ -132,12 +132,18 @@ hipError_t launch_rdot(const T* bel, int ldb, int B, ModelView<T> mv, const int3
 // first-max argmax over the V columns [g*V, (g+1)*V) of each (row b, group g) of the score matrix;
 // column G*V + g holds the magnitude score (b . Gamma of the max|alpha| row) that scales the tie
 // window.
+// Hand-over to the refinement: for a queued row the columns with (double)score >= best_score - 2 err -- the candidates
+// k_refine would collect -- go to hcand[row][QCAND] in ascending order (the first QCAND of them) and their number,
+// saturated at QCAND + 1, to hncand[row].  Rows that are not queued are not written.
+constexpr int QCAND = 8;              // k_refine scores up to this many candidates together (its FAST_CAP)
 template <typename T>
 hipError_t launch_argmax(SlabView<T> sv, int V, int G, int B, const uint8_t* dead, double tol_rel, double tol_abs,
                          const int* chain_steps /* device: K-tile steps of the longest f32 chain; used when tol_rel < 0 */,
                          int flag_all, int32_t* best_v, double* best_score, double* err, int32_t* queue, int* qcount,
                          hipStream_t st, double tol_extra = 0.0 /* added to the relative window: input rounding of a screen */,
-                         int split = 0 /* the scores came from the split bf16 GEMM: its window (score_window) */);
+                         int split = 0 /* the scores came from the split bf16 GEMM: its window (score_window) */,
+                         int32_t* hcand = nullptr /* out, or nullptr: [B * G][QCAND] candidates of the queued rows */,
+                         int32_t* hncand = nullptr /* out: [B * G] their number, saturated at QCAND + 1 */);
 
 // Gamma tiled over the alpha set: sums the split-K slabs of ONE chunk's score GEMM (sv: alpha rows [v0, v0 + Vc) scored as a
 // Vc-row alpha set, column g * Vc + v, then tail_cols = G + 2A magnitude / reward columns when this is the last chunk, else
@@ -195,6 +201,10 @@ struct RefineWork {
     const float* gam = nullptr;          // [A*O*V + ...][ldg] projected rows, group-major (row g * V + v); nullptr = off
     int ldg = 0;
     double l1_rel = 0.0;                 // (R + 4) * 2^-24: R products, R adds, the scale, gamma's own rounding, slack
+    // Candidates handed over by launch_argmax (hcand / hncand there), indexed by queue entry; nullptr: k_refine scans.
+    // An entry with hncand[e] <= QCAND takes its candidates from the list instead of walking its V scores again.
+    const int32_t* hcand = nullptr;
+    const int32_t* hncand = nullptr;
 };
 
 // fp64 re-decision of queued near-ties.  PROJ: scores are b . Gamma[a,o,v,:]; else b . alpha[v,:]

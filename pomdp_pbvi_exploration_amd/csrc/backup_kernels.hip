@@ -694,153 +694,253 @@ __device__ __forceinline__ double score_window(double tol_rel, const int* chain_
 }
 
 // ------------------------------------------------------------------------- //
-// argmax over alpha-vectors, one wavefront per (belief, group) row segment.
+// argmax over alpha-vectors, one wavefront per (belief, group) row.
 // np.argmax semantics: first maximum.  src/pomdp.py:1495 (argmax part)
 // ------------------------------------------------------------------------- //
+// A block takes ARGMAX_BLOCK_ROWS consecutive rows, one per wave.  The rows a block queues are collected in LDS and
+// appended with ONE atomicAdd(qcount, n) per block (it was one returning atomic per queued row, all on one word).  The
+// queue's order is arbitrary, as it was.  (Several rows per wave -- fewer blocks and appends still -- are slower: 0.095 ms
+// with 4 rows per wave, 0.116 ms with 8 against 0.081 ms at C4.  The kernel lives on the number of loads in flight, not
+// on the appends; profiles/argmax_refine_handover.md.)
+// The block's queued rows are then shared out among its waves, and a wave walks its row a second time (same loads, same
+// sums) and leaves the row's candidates -- the columns with (double)score >= m - 2E, what k_refine collects -- in
+// hcand[row][QCAND], ascending, the first QCAND of them, and their number, saturated at QCAND + 1, in hncand[row]
+// (hcand == nullptr: no second pass).  Only queued rows are written.
+constexpr int ARGMAX_BLOCK_ROWS = 16;
+
+typedef float ArgmaxF4 __attribute__((ext_vector_type(4)));
+
+// Where a (belief, group) row lies in the slabs -- alpha side: row b, columns g * V + v; belief side: row (o, a, b), columns v
+template <typename T>
+struct ArgmaxRow {
+    int64_t row, col0;
+    const float* rowp;
+    int tm;
+    __device__ __forceinline__ ArgmaxRow(const SlabView<T>& sv, int V, int b, int g) {
+        row = sv.push ? sv.push_row(b, g) : (int64_t)b;
+        col0 = sv.push ? 0 : (int64_t)g * V;
+        rowp = (const float*)sv.slabs + row * sv.ldc + col0;
+        tm = (int)(row >> 8);
+    }
+    // Fast path (alpha-side f32 slabs, groups aligned to 4 columns): a lane takes 4 consecutive columns per load
+    // (16 bytes per slab) and looks the pair's slab count up once per 4 columns instead of once per score.  acc[j] = the
+    // scores of columns c00 + 256 j + (0 .. 3) -- four 256-column steps at a time: their slab counts first, then their
+    // first slabs, then what further slabs there are -- two rounds of independent loads per 1024 columns instead of
+    // eight dependent ones.  (Steps at or behind column V give zeros.)
+    __device__ __forceinline__ void scores4(const SlabView<T>& sv, int V, int c00, ArgmaxF4* acc) const {
+        int n[4], fb[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c0 = c00 + 256 * j;
+            const int64_t pair = ((col0 + c0) >> 8) * sv.tiles_m + tm;
+            n[j] = c0 < V ? sv.nchunks[pair] : 0;
+            fb[j] = (c0 < V && sv.first_block != nullptr) ? sv.first_block[pair] : 0;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const ArgmaxF4 zero = {0.f, 0.f, 0.f, 0.f};
+            acc[j] = zero;
+            if (n[j] > 0) acc[j] = acc[j] + *(const ArgmaxF4*)(rowp + c00 + 256 * j);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (n[j] <= 1) continue;
+            if (sv.first_block != nullptr) {                 // continuation tiles behind the full slab (SlabView)
+                const float* x = (const float*)sv.slabs + sv.slab_stride + (int64_t)(fb[j] + 1) * (256 * 256) +
+                                 (row & 255) * 256 + ((col0 + c00 + 256 * j) & 255);
+                for (int z = 1; z < n[j]; ++z, x += 256 * 256) acc[j] = acc[j] + *(const ArgmaxF4*)x;
+            } else {
+                for (int z = 1; z < n[j]; ++z) acc[j] = acc[j] + *(const ArgmaxF4*)(rowp + c00 + 256 * j + (int64_t)z * sv.slab_stride);
+            }
+        }
+    }
+};
+
 template <typename T>
 __global__ void k_argmax(SlabView<T> sv, int V, int G, int B, const uint8_t* __restrict__ dead, double tol_rel,
-                         double tol_abs, double tol_extra, const int* __restrict__ chain_steps, int flag_all, int32_t* __restrict__ best_v, double* __restrict__ best_score,
-                         double* __restrict__ err, int32_t* __restrict__ queue, int* __restrict__ qcount, int split) {
-    const int lane = threadIdx.x & 63;
-    const int64_t gw = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (gw >= (int64_t)B * G) return;
-    const int b = (int)(gw / G), g = (int)(gw % G);
-    if (dead != nullptr && dead[gw]) {
-        if (lane == 0) {
-            best_v[gw] = 0;
-            best_score[gw] = 0.0;
-            err[gw] = 0.0;
-        }
-        return;
-    }
-    // one pass: running maximum (first index) and runner-up value per lane, merged across the wave
-    T m = -std::numeric_limits<T>::infinity(), m2 = -std::numeric_limits<T>::infinity();
-    int idx = 0x7fffffff;
-    // Fast path (alpha-side f32 slabs, groups aligned to 4 columns): a lane takes 4 consecutive columns per load
-    // (16 bytes per slab) and looks the pair's slab count up once per 4 columns instead of once per score; columns
-    // and chunks ascend per lane, so "first maximum" is unchanged.
+         double tol_abs, double tol_extra, const int* __restrict__ chain_steps, int flag_all, int32_t* __restrict__ best_v, double* __restrict__ best_score,
+         double* __restrict__ err, int32_t* __restrict__ queue, int* __restrict__ qcount, int split,
+         int32_t* __restrict__ hcand, int32_t* __restrict__ hncand) {
+    __shared__ int32_t qrows[ARGMAX_BLOCK_ROWS];
+    __shared__ double qthr[ARGMAX_BLOCK_ROWS];
+    __shared__ int qn, qbase;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if (threadIdx.x == 0) qn = 0;
+    __syncthreads();
+    const int64_t rows = (int64_t)B * G;
+    // (columns and chunks ascend per lane in either reader, so "first maximum" is the same)
     bool vec4 = false;
     if constexpr (sizeof(T) == 4) vec4 = sv.nchunks != nullptr && (sv.push || (V & 3) == 0) && (sv.ldc & 3) == 0;
-    if (vec4) {
-        typedef float F4 __attribute__((ext_vector_type(4)));
-        // alpha side: row b, columns g * V + v; belief side: row (o, a, b), columns v
-        const int64_t row = sv.push ? sv.push_row(b, g) : (int64_t)b;
-        const int64_t col0 = sv.push ? 0 : (int64_t)g * V;
-        const float* rowp = (const float*)sv.slabs + row * sv.ldc + col0;
-        const int tm = (int)(row >> 8);
-        // four 256-column steps at a time: their slab counts first, then their first slabs, then what further slabs
-        // there are -- two rounds of independent loads per 1024 columns instead of eight dependent ones
-        for (int c00 = lane * 4; c00 < V; c00 += 1024) {
-            int n[4], fb[4];
-            F4 acc[4];
+    // (no wave leaves before the barriers below)
+    const int64_t gw = (int64_t)blockIdx.x * ARGMAX_BLOCK_ROWS + wid;
+    const bool is_dead = gw < rows && dead != nullptr && dead[gw];
+    if (is_dead && lane == 0) {
+        best_v[gw] = 0;
+        best_score[gw] = 0.0;
+        err[gw] = 0.0;
+    }
+    if (gw < rows && !is_dead) {
+        const int b = (int)(gw / G), g = (int)(gw % G);
+        // one pass: running maximum (first index) and runner-up value per lane, merged across the wave
+        T m = -std::numeric_limits<T>::infinity(), m2 = -std::numeric_limits<T>::infinity();
+        int idx = 0x7fffffff;
+        if (vec4) {
+            const ArgmaxRow<T> ar(sv, V, b, g);
+            for (int c00 = lane * 4; c00 < V; c00 += 1024) {
+                ArgmaxF4 acc[4];
+                ar.scores4(sv, V, c00, acc);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int c0 = c00 + 256 * j;
-                const int64_t pair = ((col0 + c0) >> 8) * sv.tiles_m + tm;
-                n[j] = c0 < V ? sv.nchunks[pair] : 0;
-                fb[j] = (c0 < V && sv.first_block != nullptr) ? sv.first_block[pair] : 0;
-            }
+                for (int j = 0; j < 4; ++j) {
+                    const int c0 = c00 + 256 * j;
+                    if (c0 >= V) break;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const F4 zero = {0.f, 0.f, 0.f, 0.f};
-                acc[j] = zero;
-                if (n[j] > 0) acc[j] = acc[j] + *(const F4*)(rowp + c00 + 256 * j);
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (n[j] <= 1) continue;
-                if (sv.first_block != nullptr) {             // continuation tiles behind the full slab (SlabView)
-                    const float* x = (const float*)sv.slabs + sv.slab_stride + (int64_t)(fb[j] + 1) * (256 * 256) +
-                                     (row & 255) * 256 + ((col0 + c00 + 256 * j) & 255);
-                    for (int z = 1; z < n[j]; ++z, x += 256 * 256) acc[j] = acc[j] + *(const F4*)x;
-                } else {
-                    for (int z = 1; z < n[j]; ++z) acc[j] = acc[j] + *(const F4*)(rowp + c00 + 256 * j + (int64_t)z * sv.slab_stride);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int c0 = c00 + 256 * j;
-                if (c0 >= V) break;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const T sc = (T)acc[j][i];
-                    const int v = c0 + i;
-                    if (v >= V) break;                          // (belief side: V need not be a multiple of 4)
-                    if (sc > m || idx == 0x7fffffff) {
-                        m2 = (idx == 0x7fffffff) ? m2 : m;
-                        m = sc;
-                        idx = v;
-                    } else if (sc > m2) {
-                        m2 = sc;
+                    for (int i = 0; i < 4; ++i) {
+                        const T sc = (T)acc[j][i];
+                        const int v = c0 + i;
+                        if (v >= V) break;                      // (belief side: V need not be a multiple of 4)
+                        if (sc > m || idx == 0x7fffffff) {
+                            m2 = (idx == 0x7fffffff) ? m2 : m;
+                            m = sc;
+                            idx = v;
+                        } else if (sc > m2) {
+                            m2 = sc;
+                        }
                     }
                 }
             }
-        }
-    } else
-    for (int v0 = lane; v0 < V; v0 += 256) {               // four independent score reads in flight per lane
-        T sc4[4];
+        } else
+        for (int v0 = lane; v0 < V; v0 += 256) {           // four independent score reads in flight per lane
+            T sc4[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int v = v0 + 64 * j;
-            sc4[j] = v < V ? sv.score(b, g, V, v) : T(0);
+            for (int j = 0; j < 4; ++j) {
+                const int v = v0 + 64 * j;
+                sc4[j] = v < V ? sv.score(b, g, V, v) : T(0);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int v = v0 + 64 * j;
+                if (v >= V) break;
+                const T sc = sc4[j];
+                if (sc > m || idx == 0x7fffffff) {
+                    m2 = (idx == 0x7fffffff) ? m2 : m;
+                    m = sc;
+                    idx = v;
+                } else if (sc > m2) {
+                    m2 = sc;                                // includes sc == m (a later exact tie)
+                }
+            }
         }
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int v = v0 + 64 * j;
-            if (v >= V) break;
-            const T sc = sc4[j];
-            if (sc > m || idx == 0x7fffffff) {
-                m2 = (idx == 0x7fffffff) ? m2 : m;
-                m = sc;
-                idx = v;
-            } else if (sc > m2) {
-                m2 = sc;                                    // includes sc == m (a later exact tie)
+        for (int off = 32; off > 0; off >>= 1) {
+            const T om = __shfl_xor(m, off, 64), om2 = __shfl_xor(m2, off, 64);
+            const int oi = __shfl_xor(idx, off, 64);
+            const T lo = om < m ? om : m;                   // the loser of the two maxima is a runner-up
+            T n2 = m2 > om2 ? m2 : om2;
+            if (oi != 0x7fffffff && idx != 0x7fffffff) n2 = lo > n2 ? lo : n2;
+            if (om > m || (om == m && oi < idx)) {
+                m = om;
+                idx = oi;
+            }
+            m2 = n2;
+        }
+        double E = 0.0;
+        int push = 0;
+        if (queue != nullptr) {
+            const double mag = fmax(fabs((double)m), fabs(sv.magnitude(b, g, G, V)));
+            // f32 error model: 8 * 2^-24 * sqrt(longest fma chain) (+ slab sums); the chain length is the
+            // stream-K share size, known only on the device
+            const double tr = score_window(tol_rel, chain_steps, split) + (sv.push ? 2.0 * 5.9604644775390625e-08 : 0.0);
+            // (sv.push: bp is rounded once to f32 after its f64 accumulation)
+            E = (tr + tol_extra) * mag + tol_abs;           // tol_extra: input rounding of an fp32 screen of fp64 operands
+            push = (flag_all || (double)m2 >= (double)m - 2.0 * E) ? 1 : 0;
+        }
+        if (lane == 0) {
+            best_v[gw] = idx;
+            best_score[gw] = (double)m;
+            err[gw] = E;
+            if (push) {
+                const int slot = atomicAdd(&qn, 1);
+                qrows[slot] = (int32_t)gw;
+                qthr[slot] = (double)m - 2.0 * E;           // k_refine's threshold
             }
         }
     }
+    // the block's queued rows: one append
+    __syncthreads();
+    const int n_q = qn;
+    if (threadIdx.x == 0 && n_q > 0) qbase = atomicAdd(qcount, n_q);
+    __syncthreads();
+    if ((int)threadIdx.x < n_q) queue[qbase + threadIdx.x] = qrows[threadIdx.x];
+    if (hcand == nullptr) return;
+    // second pass over the queued rows (wave-uniform loops): candidates in ascending v.  The sums are those of the first
+    // pass (and of SlabView::at: 0 + slab 0 + slab 1 ...).
+    const unsigned long long below = (1ull << lane) - 1ull;
+    if (wid < n_q) {                                         // (at most one queued row per wave)
+        const int64_t qw = qrows[wid];
+        const double thr = qthr[wid];
+        const int b = (int)(qw / G), g = (int)(qw % G);
+        int32_t* hc = hcand + qw * QCAND;
+        int cnt = 0;
+        if (vec4) {
+            const ArgmaxRow<T> ar(sv, V, b, g);
+            for (int c0b = 0; c0b < V && cnt <= QCAND; c0b += 1024) {
+                const int c00 = c0b + lane * 4;
+                ArgmaxF4 acc[4];
+                ar.scores4(sv, V, c00, acc);
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const T om = __shfl_xor(m, off, 64), om2 = __shfl_xor(m2, off, 64);
-        const int oi = __shfl_xor(idx, off, 64);
-        const T lo = om < m ? om : m;                       // the loser of the two maxima is a runner-up
-        T n2 = m2 > om2 ? m2 : om2;
-        if (oi != 0x7fffffff && idx != 0x7fffffff) n2 = lo > n2 ? lo : n2;
-        if (om > m || (om == m && oi < idx)) {
-            m = om;
-            idx = oi;
+                for (int j = 0; j < 4; ++j) {                   // columns ascend with (j, lane, i)
+                    const int c0 = c00 + 256 * j;
+                    int f[4], pos = cnt, tot = 0;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        f[i] = (c0 + i < V && (double)(T)acc[j][i] >= thr) ? 1 : 0;
+                        const unsigned long long mask = __ballot(f[i]);
+                        pos += __popcll(mask & below);
+                        tot += __popcll(mask);
+                    }
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        if (f[i]) {
+                            if (pos < QCAND) hc[pos] = c0 + i;
+                            ++pos;
+                        }
+                    cnt += tot;
+                }
+            }
+        } else {
+            for (int v0b = 0; v0b < V && cnt <= QCAND; v0b += 256) {
+                T sc4[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int v = v0b + 64 * j + lane;
+                    sc4[j] = v < V ? sv.score(b, g, V, v) : T(0);
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {                   // columns ascend with (j, lane)
+                    const int v = v0b + 64 * j + lane;
+                    const int f = (v < V && (double)sc4[j] >= thr) ? 1 : 0;
+                    const unsigned long long mask = __ballot(f);
+                    const int pos = cnt + __popcll(mask & below);
+                    if (f && pos < QCAND) hc[pos] = v;
+                    cnt += __popcll(mask);
+                }
+            }
         }
-        m2 = n2;
-    }
-    double E = 0.0;
-    int push = 0;
-    if (queue != nullptr) {
-        const double mag = fmax(fabs((double)m), fabs(sv.magnitude(b, g, G, V)));
-        // f32 error model: 8 * 2^-24 * sqrt(longest fma chain) (+ slab sums); the chain length is the
-        // stream-K share size, known only on the device
-        const double tr = score_window(tol_rel, chain_steps, split) + (sv.push ? 2.0 * 5.9604644775390625e-08 : 0.0);
-        // (sv.push: bp is rounded once to f32 after its f64 accumulation)
-        E = (tr + tol_extra) * mag + tol_abs;               // tol_extra: input rounding of an fp32 screen of fp64 operands
-        push = (flag_all || (double)m2 >= (double)m - 2.0 * E) ? 1 : 0;
-    }
-    if (lane == 0) {
-        best_v[gw] = idx;
-        best_score[gw] = (double)m;
-        err[gw] = E;
-        if (push) {
-            const int slot = atomicAdd(qcount, 1);
-            queue[slot] = (int32_t)gw;
-        }
+        if (lane == 0) hncand[qw] = cnt < QCAND + 1 ? cnt : QCAND + 1;
     }
 }
 
 template <typename T>
 hipError_t launch_argmax(SlabView<T> sv, int V, int G, int B, const uint8_t* dead, double tol_rel, double tol_abs,
                          const int* chain_steps, int flag_all, int32_t* best_v, double* best_score, double* err,
-                         int32_t* queue, int* qcount, hipStream_t st, double tol_extra, int split) {
+                         int32_t* queue, int* qcount, hipStream_t st, double tol_extra, int split, int32_t* hcand,
+                         int32_t* hncand) {
     const int64_t rows = (int64_t)B * G;
     if (rows <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_argmax<T>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, sv, V, G, B, dead, tol_rel,
-                       tol_abs, tol_extra, chain_steps, flag_all, best_v, best_score, err, queue, qcount, split);
+    if (queue == nullptr || hncand == nullptr) hcand = nullptr;
+    hipLaunchKernelGGL(k_argmax<T>, dim3((unsigned)((rows + ARGMAX_BLOCK_ROWS - 1) / ARGMAX_BLOCK_ROWS)),
+                       dim3(ARGMAX_BLOCK_ROWS * 64), 0, st, sv, V, G, B, dead, tol_rel, tol_abs, tol_extra, chain_steps, flag_all,
+                       best_v, best_score, err, queue, qcount, split, hcand, hncand);
     return hipGetLastError();
 }
 
@@ -1027,6 +1127,8 @@ __global__ void k_refine(SlabView<TS> sv, int V, int G, const int32_t* __restric
     const int a = PROJ ? g / mv.O : 0, o = PROJ ? g % mv.O : 0;
     const double m = best_score[e], E = err[e];
     const double thr = m - 2.0 * E;
+    // candidates k_argmax left for this entry (RefineWork::hcand), if they all fit: no scan of the V scores below
+    const int n_handed = work.hncand != nullptr ? work.hncand[e] : QCAND + 1;
     const T* brow = bel + (int64_t)b * ldb;
     const int k_tiles = mv.S_pad >> 5;
     // -- tile list of this entry: belief tiles, filtered by the group's support tiles
@@ -1101,14 +1203,15 @@ __global__ void k_refine(SlabView<TS> sv, int V, int G, const int32_t* __restric
     if (!loverflow) {                                        // (an overflowed list names tiles nobody projected)
         // -- collect the entry's candidates over all chunks of V (ascending v); more than L1_CAP: the chunk loop below
         constexpr int L1_CAP = 32;
-        constexpr int FAST_CAP = 8;                          // candidates scored together, four per pass
+        constexpr int FAST_CAP = QCAND;                      // candidates scored together, four per pass
         __shared__ int c1[L1_CAP];
         __shared__ double s1[L1_CAP];
         __shared__ double l1red[16];
         __shared__ int n1_sh, n2_sh;
-        if (tid == 0) n1_sh = 0;
+        if (tid == 0) n1_sh = n_handed <= QCAND ? n_handed : 0;
+        if (n_handed <= QCAND && tid < n_handed) c1[tid] = work.hcand[(int64_t)e * QCAND + tid];
         __syncthreads();
-        for (int v0 = 0; v0 < V; v0 += 256) {
+        for (int v0 = 0; v0 < V && n_handed > QCAND; v0 += 256) {
             const int v = v0 + tid;
             int flag = 0;
             if (v < V) flag = ((double)sv.score(b, g, V, v) >= thr) ? 1 : 0;
@@ -3016,7 +3119,8 @@ hipError_t launch_infotaxis(const T* bel, int ldb, int B, ModelView<T> mv, const
                                        int32_t*, int*, hipStream_t, const uint8_t*, const int32_t*);                                                   \
     template hipError_t launch_belief_tiles<T>(const T*, int, int, int, int, int32_t*, int32_t*, hipStream_t);         \
     template hipError_t launch_argmax<T>(SlabView<T>, int, int, int, const uint8_t*, double, double, const int*, int,  \
-                                         int32_t*, double*, double*, int32_t*, int*, hipStream_t, double, int);        \
+                                         int32_t*, double*, double*, int32_t*, int*, hipStream_t, double, int, int32_t*, \
+                                         int32_t*);                                                                     \
     template hipError_t launch_fold_chunk<T>(SlabView<T>, int, int, int, int, int, int, T*, int64_t, const int*, int*,   \
                                              hipStream_t);                                                             \
     template hipError_t launch_score_probe<T>(SlabView<T>, int, int, int, double*, double*, hipStream_t);              \

@@ -817,6 +817,8 @@ struct ScoreIO {                      // the pipeline buffers the stage writes /
     double* err;
     int32_t* queue;                   // near-tie queue (nullptr: no windows, exact arithmetic)
     int* qcount;
+    int32_t* hcand;                   // candidates of the queued rows, for the refinement (launch_argmax), or nullptr
+    int32_t* hncand;
     const uint8_t* dead;              // exact dead-triple flags, or nullptr
     const double* prd;                // [B][A] b.ER in f64 for the belief-side formulation, or nullptr
     hipEvent_t join;                  // the side-stream work that produced dead / prd
@@ -1017,7 +1019,7 @@ class EngineT : public EngineBase {
     int64_t B_ = 0, B_pad_ = 0;
     DevBuf belsp_{mem_};   // fp32: bel_'s split plane for the split score GEMM (split_bf16.h)
     uint64_t belsp_ver_ = 0;                                 // the bel_ version belsp_ holds (0: none)
-    DevBuf gam_{mem_}, slabs_{mem_}, best_v_{mem_}, best_score_{mem_}, err_{mem_}, dead_{mem_}, queue_{mem_}, counters_{mem_, DevBuf::MODEL}, rdot_{mem_}, aqueue_{mem_}, keep_{mem_};
+    DevBuf gam_{mem_}, slabs_{mem_}, best_v_{mem_}, best_score_{mem_}, err_{mem_}, dead_{mem_}, queue_{mem_}, hcand_{mem_}, hncand_{mem_}, counters_{mem_, DevBuf::MODEL}, rdot_{mem_}, aqueue_{mem_}, keep_{mem_};
     // the backup's decision: actions, the belief reordering undone (f32, B > 256), K6 key dedup; fin_.rows holds the unique rows
     Decision fin_{mem_, counters_, CNT_UNIQUE};
     DevBuf bv2_{mem_}, bs2_{mem_}, err2_{mem_}, queue2_{mem_}, prune_cnt_{mem_};
@@ -2622,6 +2624,8 @@ class EngineT : public EngineBase {
         if ((rc = best_score_.ensure((size_t)c.pairs * sizeof(double)))) return rc;
         if ((rc = err_.ensure((size_t)c.pairs * sizeof(double)))) return rc;
         if ((rc = queue_.ensure((size_t)c.pairs * sizeof(int32_t)))) return rc;
+        if ((rc = hcand_.ensure((size_t)c.pairs * QCAND * sizeof(int32_t)))) return rc;
+        if ((rc = hncand_.ensure((size_t)c.pairs * sizeof(int32_t)))) return rc;
         if ((rc = dead_.ensure((size_t)c.pairs))) return rc;
         if ((rc = rdot_.ensure((size_t)B_ * A_ * 2 * sizeof(double)))) return rc;
         if ((rc = aqueue_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
@@ -2697,6 +2701,8 @@ class EngineT : public EngineBase {
         io.err = err_.as<double>();
         io.queue = c.windows ? queue_.as<int32_t>() : nullptr;
         io.qcount = counters_.as<int>() + CNT_QUEUE;
+        io.hcand = c.windows ? hcand_.as<int32_t>() : nullptr;
+        io.hncand = c.windows ? hncand_.as<int32_t>() : nullptr;
         io.dead = c.windows ? dead_.as<uint8_t>() : nullptr;
         io.prd = c.use_push ? prd_.as<double>() : nullptr;
         io.join = ev_join_;
@@ -2841,6 +2847,12 @@ class EngineT : public EngineBase {
                 work.ldg = S_pad_;
                 work.l1_rel = (double)(R_ + 4) * 5.9604644775390625e-08;
             }
+        }
+        // the candidates k_argmax left for the rows it queued (backup_kernels.h, RefineWork::hcand)
+        static const bool no_handover = getenv("PBVI_NO_CAND_HANDOVER") != nullptr;      // debug / A-B only: k_refine scans
+        if (!no_handover) {
+            work.hcand = c.io.hcand;
+            work.hncand = c.io.hncand;
         }
         // the counts land in two of the engine's pinned flag words -- not in the staging buffer: run_fetch stages results
         // through that one before the counts are read, and out_add may reset or reallocate it
@@ -4250,7 +4262,7 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
     out->rd_col0 = (int64_t)AO * Vt;
     out->f64_pairs = f64_pairs_;
     HIPCHK(launch_argmax<T>(sv, (int)V_, AO, (int)B_, io.dead, out->tol_rel, 0.0, out->chain, 0, io.best_v, io.best_score,
-                            io.err, io.queue, io.qcount, stream_, io.tol_extra, out->split));
+                            io.err, io.queue, io.qcount, stream_, io.tol_extra, out->split, io.hcand, io.hncand));
     if (probe_on_ && (rc = probe_capture(sv, io, *out))) return rc;      // tests only (pbvi_debug_score_probe)
     HIPCHK(hipEventRecord(io.ev[3], stream_));
     out->sv = sv;
@@ -4363,7 +4375,7 @@ int EngineT<T>::stage_scores_tiled(double gamma, const ScoreIO& io, int want_spl
     out->fused = false;
     out->chunks = (int)n_chunks;
     HIPCHK(launch_argmax<T>(full, (int)V_, AO, (int)B_, io.dead, out->tol_rel, 0.0, out->chain, 0, io.best_v, io.best_score,
-                            io.err, io.queue, io.qcount, stream_, io.tol_extra, out->split));
+                            io.err, io.queue, io.qcount, stream_, io.tol_extra, out->split, io.hcand, io.hncand));
     if (probe_on_ && (rc = probe_capture(full, io, *out))) return rc;    // tests only (pbvi_debug_score_probe)
     HIPCHK(hipEventRecord(io.ev[3], stream_));
     out->sv = full;
