@@ -770,7 +770,16 @@ class PBVI_Solver(Solver):
         return BeliefSet(model, seq)
 
     def expand(self, model, belief_set, max_generation: int, **params) -> BeliefSet:
-        """Dispatch by substring exactly like ``src/pomdp.py:2088-2136``."""
+        """Dispatch by substring exactly like ``src/pomdp.py:2088-2136``: ``self.expand_function`` is one of ``ra``,
+        ``ssra``, ``ssga``, ``ssea``, ``ger``, ``hsvi``, ``fsvi``, ``fsvi_eg``, ``perseus``, with or without the
+        ``expand_`` prefix; the order of the tests matters (``'ra'`` is also a substring of ``'expand_ssra'``, ``'fsvi'``
+        of ``'expand_fsvi_eg'``).
+
+        ``ssea`` and ``ger`` update every belief with every (action, observation), so they cannot run on a model with
+        an impossible observation -- one of probability 0 at every successor some belief reaches, as in 4x3.95,
+        cheese.95 and hallway: ``Belief.update`` divides by zero and the belief's check raises ``AssertionError: States
+        probabilities in belief must sum to 1 (found: nan)``.  They run on tiger and on any model whose observation
+        table is strictly positive.  This matches the reference, which raises the same way on the same models."""
         f = self.expand_function
         if f in 'expand_ra':
             return self.expand_ra(model, belief_set, max_generation)

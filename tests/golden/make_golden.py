@@ -3,7 +3,7 @@
 Run in the build container only (needs /root/reference, which never travels):
 
     MPLBACKEND=Agg python tests/golden/make_golden.py [small] [kat] [c2] [full] [full_r5] [c5] [sim] [models] [solve] [e2e]
-                                                      [hsvi] [prune] [limiter]
+                                                      [hsvi] [prune] [limiter] [strategies]
 
 (`full_r5`: the R = 5 variant at V = B = 1024, the size bench.py's secondary.c4_r5 runs at -- the reference's backup needs
 ~30 GB and 173 s for it here.)
@@ -620,7 +620,67 @@ def gen_limiter():
     print(f'[golden] limiter_fsvi.npz: |V| trajectory {counts.tolist()}')
 
 
+def gen_strategies():
+    """Seeded solves of the reference's ``PBVI_Solver`` with each of its nine expansion strategies (``tests/strategy_cases.py``
+    makes the calls, here on the reference's module): per (model, strategy, config) the belief-count, |V|, prune-count
+    and change trajectories, the final actions and the final alpha rows (gen600: their projections on 8 seeded probes
+    and their sums); that ``ssea`` / ``ger`` raise on the example models with an impossible observation; and one direct
+    ``expand_*`` call per strategy on gen70 (``ssga`` also with epsilon 0.5, as a call and as a solve: its random-action
+    branch does not run otherwise).  Asserted while recording: the all-successor strategies complete on the
+    generated models without a floating-point warning, and no generated-model case is vacuous."""
+    sys.path.insert(0, os.path.join(REPO, 'tests'))
+    import strategy_cases as sc
+    entries = {}
+    for name in sc.MODEL_NAMES:
+        for strategy in sc.STRATEGIES:
+            if (name, strategy) in sc.RAISING:
+                model = sc.build_model(ref, name)
+                try:
+                    with np.errstate(all='ignore'):
+                        sc.run_solve(ref, model, name, strategy, sc.CONFIGS[0])
+                except AssertionError as e:
+                    assert str(e).startswith(sc.RAISING_PREFIX), str(e)
+                    entries[f'raises/{name}/{strategy}'] = np.array([1])
+                else:
+                    raise AssertionError(f'{name} {strategy}: the reference was expected to raise')
+                continue
+            for config in sc.CONFIGS:
+                model = sc.build_model(ref, name)
+                strict = name in sc.GENERATED and strategy in ('ssea', 'ger')
+                with np.errstate(all='raise') if strict else contextlib.nullcontext():
+                    vf, hist = sc.run_solve(ref, model, name, strategy, config)
+                rec = sc.record(name, vf, hist)
+                if name in sc.GENERATED and config == sc.CONFIGS[0]:
+                    # (hsvi's descent stops at the bound gap: it converges on 17 beliefs on gen70 and on 9 on gen600)
+                    enough = 9 if strategy == 'hsvi' else 20
+                    assert len(rec['actions']) >= 6 and rec['beliefs_counts'][-1] >= enough, (name, strategy, rec['beliefs_counts'])
+                entries[sc.case_key(name, strategy, config) + '/config'] = np.array(config)
+                for k, v in rec.items():
+                    entries[sc.case_key(name, strategy, config) + '/' + k] = v
+                print(f'strategies {sc.case_key(name, strategy, config)}: |V|={len(rec["actions"])} '
+                      f'beliefs={int(rec["beliefs_counts"][-1])} prunes={rec["prune_counts"].tolist()}')
+    for strategy in sc.STRATEGIES:
+        entries[f'expand/{strategy}'] = sc.single_expansion(ref, sc.build_model(ref, 'gen70'), strategy)
+    # ssga's random-action branch: no draw of the seeded cases above falls under the default epsilon
+    name, strategy, config = sc.SSGA_EPSILON_CASE
+    eps = dict(epsilon=sc.SSGA_EPSILON)
+    entries['expand/ssga_epsilon'] = sc.single_expansion(ref, sc.build_model(ref, name), strategy, **eps)
+    greedy = sc.single_expansion(ref, sc.build_model(ref, name), strategy, epsilon=0.0)
+    assert np.array_equal(entries['expand/ssga'], greedy), 'a draw fell under 0.1 after all: say so in strategy_cases.py'
+    assert not np.array_equal(entries['expand/ssga_epsilon'], greedy), 'the random-action branch changed nothing'
+    vf, hist = sc.run_solve(ref, sc.build_model(ref, name), name, strategy, config, expand_params=eps)
+    rec = sc.record(name, vf, hist)
+    plain = entries[sc.case_key(name, strategy, config) + '/rows']
+    assert rec['rows'].shape != plain.shape or not np.array_equal(rec['rows'], plain)
+    assert len(rec['actions']) >= 6 and rec['beliefs_counts'][-1] >= 20, rec['beliefs_counts']
+    for k, v in rec.items():
+        entries[f'ssga_epsilon/{k}'] = v
+    path = os.path.join(HERE, sc.FIXTURE)
+    np.savez_compressed(path, **sc.pack(entries))
+    print(f'[golden] {sc.FIXTURE}: {len(entries)} arrays, {os.path.getsize(path)} bytes')
+
+
 if __name__ == '__main__':
     which = sys.argv[1:] or ['small', 'kat', 'c2']
     for w in which:
-        {'small': gen_small, 'kat': gen_kat, 'c2': gen_c2, 'full': gen_full, 'full_r5': gen_full_r5, 'sim': gen_sim, 'models': gen_models, 'solve': gen_solve, 'e2e': gen_e2e, 'hsvi': gen_hsvi, 'prune': gen_prune, 'limiter': gen_limiter, 'c5': gen_c5}[w]()
+        {'strategies': gen_strategies, 'small': gen_small, 'kat': gen_kat, 'c2': gen_c2, 'full': gen_full, 'full_r5': gen_full_r5, 'sim': gen_sim, 'models': gen_models, 'solve': gen_solve, 'e2e': gen_e2e, 'hsvi': gen_hsvi, 'prune': gen_prune, 'limiter': gen_limiter, 'c5': gen_c5}[w]()
