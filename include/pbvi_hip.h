@@ -184,7 +184,8 @@ int pbvi_backup_fetch(pbvi_engine_t* e, void* out_alpha, int32_t* out_action,
  * before any row is computed or moved.  U = pbvi_backup_unique_count():
  *   out_rows  [U][S] T     row u = alpha' of the first belief (in the caller's order) with that key
  *   out_index [B] int32    alpha'[b] == out_rows[out_index[b]]
- * Destinations may be host or device memory.  pbvi_backup_fetch(out_alpha) expands this to [B][S].
+ * Destinations may be host or device memory (pageable host destinations go through the engine's pinned bounce buffer,
+ * here and wherever a comment below says "host or device").  pbvi_backup_fetch(out_alpha) expands this to [B][S].
  */
 int64_t pbvi_backup_unique_count(const pbvi_engine_t* e);
 int pbvi_backup_fetch_unique(pbvi_engine_t* e, void* out_rows, int32_t* out_index);
@@ -247,6 +248,7 @@ int64_t pbvi_backup_store_unique(pbvi_engine_t* e, const int32_t* unique_idx, in
  *   pbvi_backup_fetch_unique_keys : out_keys [U][1+O] int32 of the last backup's U distinct rows (host or device)
  *   pbvi_assemble_rows            : out_rows [n][S] T (host or device) from n keys against the RESIDENT alpha set;
  *                                   byte-identical to the rows the producing rank holds.  1 <= n <= 65535.
+ * Pageable host destinations go through the pinned bounce buffer, page-locked ones and device memory are written directly.
  */
 int pbvi_backup_fetch_unique_keys(pbvi_engine_t* e, int32_t* out_keys);
 /* Everything a rank contributes to the exchange in one int32 buffer of 1 + 3B + B(1+O) entries (host or device):
@@ -258,7 +260,8 @@ int pbvi_backup_fetch_exchange_padded(pbvi_engine_t* e, int64_t per, int32_t* ou
 int pbvi_assemble_rows(pbvi_engine_t* e, double gamma, int64_t n, const int32_t* keys, void* out_rows);
 /* pbvi_assemble_rows whose rows also join the alpha store (ValueFunction.extend on every replica of a sharded
  * backup, src/pomdp.py:1521-1522 / src/mdp.py:763-779): returns the store id of the first of the n appended rows,
- * or a negative error code.  out_rows (host or device, [n][S] T) may be NULL. */
+ * or a negative error code.  out_rows (host or device, [n][S] T; pageable host memory through the pinned bounce buffer)
+ * may be NULL. */
 int64_t pbvi_assemble_rows_store(pbvi_engine_t* e, double gamma, int64_t n, const int32_t* keys, void* out_rows);
 /*
  * Host side of the key exchange of a belief-sharded backup (the step between the all-gather and
@@ -379,7 +382,8 @@ int pbvi_set_value_max_exact(pbvi_engine_t* e, int exact);
  * backup consumes.  Replaces Belief.update (src/pomdp.py:382-421) applied to B beliefs at once (the
  * reference's own batched form lives in its simulator, src/pomdp.py:3277-3310):
  *   out[b] = normalise( sum_{s,r} b[b,s] * RTO[s, actions[b], observations[b], r]  scattered to rs[s,a,r] )
- *   actions, observations [B] int32 (caller's belief order); out_beliefs [B][S] T, host or device memory.
+ *   actions, observations [B] int32 (caller's belief order); out_beliefs [B][S] T, host or device memory (pageable host
+ *   memory through the pinned bounce buffer).
  * A belief whose update has zero mass (impossible observation) yields NaNs, as the reference's 0/0 does.
  */
 int pbvi_belief_update(pbvi_engine_t* e, const int32_t* actions, const int32_t* observations, void* out_beliefs);
@@ -393,7 +397,8 @@ int pbvi_belief_update(pbvi_engine_t* e, const int32_t* actions, const int32_t* 
  *      (:3306-3311) and drops the rows with keep[b] == 0 (:3326-3329, the done-filter); survivors keep the
  *      caller's order.  keep may be NULL (keep all).  *out_B (may be NULL) receives the new row count; when it
  *      is 0 no belief block is resident any more.
- * pbvi_beliefs_fetch copies the resident block out, [B][S] T in caller order (host or device memory);
+ * pbvi_beliefs_fetch copies the resident block out, [B][S] T in caller order (host or device memory; pageable host
+ * memory through the pinned bounce buffer);
  * pbvi_beliefs_count returns B (0 = none, -1 = NULL handle).
  */
 int pbvi_beliefs_advance(pbvi_engine_t* e, const int32_t* actions, const int32_t* observations, const uint8_t* keep,

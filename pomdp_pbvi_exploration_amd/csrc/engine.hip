@@ -345,6 +345,121 @@ static bool is_pinned_host_pointer(const void* ptr) {
     return attr.type == hipMemoryTypeHost;
 }
 
+// How every result reaches the caller's memory, on the engine's main stream (DESIGN.md section 4 has the table).  Device
+// memory: one device-to-device copy.  The caller's page-locked memory: the DMA writes it.  Pageable memory: the DMA writes
+// the engine's pinned staging buffer (items at 256-byte alignment) and flush() moves them on with host_copy once the
+// stream is idle -- a DMA never targets memory the driver has to register first.  Rows in another order than the caller's
+// (perm) reach host memory of either kind through the staging buffer in one DMA; flush() puts them in order.
+// ONE transaction is open at a time: begin() drops what was queued, add() / add_rows() queue, finish() synchronises the
+// stream and completes the staged items.  An add after a failed add does nothing and returns the first error, which
+// finish() returns without synchronising: a sequence needs no check per item.  reserve() flushes first (nothing staged
+// may be lost when the buffer moves), so raw() hands out pinned memory with nothing staged in it (the belief walk's
+// side-stream copies, the prunes' counts, the rollout's trajectories).  What the backup pipeline queues with its last
+// read-back (decide) is still queued when backup_run returns: run_fetch completes it with flush(), the stream idle by then.
+struct Delivery {
+    struct Item {                 // deliver(): `bytes` of device memory `src` to `dst` (NULL: not wanted)
+        void* dst;
+        const void* src;
+        size_t bytes;
+    };
+    hipStream_t stream = nullptr;
+    explicit Delivery(std::vector<PinnedBuf*>& owner) : stage_(owner, "hipHostFree(stage)") {}
+
+    void begin() {
+        staged_.clear();
+        used_ = 0;
+        rc_ = PBVI_OK;
+    }
+    int add(void* dst, const void* src_dev, size_t bytes) { return add_rows(dst, src_dev, bytes, 1, bytes, nullptr); }
+    // n_rows rows of row_bytes, src_ld bytes apart on the device, packed at dst; row i becomes row perm[i] (nullptr: i).
+    // direct: the DMA targets a pageable destination too, as it always did for assemble_keys and fetch_exchange -- the two
+    // entries where the staged route measured slower than that (profiles/delivery_refactor.md); nothing else asks for it.
+    int add_rows(void* dst, const void* src_dev, size_t src_ld, size_t n_rows, size_t row_bytes, const int32_t* perm,
+                 bool direct = false) {
+        if (rc_ == PBVI_OK && dst != nullptr && n_rows * row_bytes > 0)
+            rc_ = queue(static_cast<char*>(dst), static_cast<const char*>(src_dev), src_ld, n_rows, row_bytes, perm, direct);
+        return rc_;
+    }
+    int finish() { return rc_ ? rc_ : flush(); }
+    int deliver(std::initializer_list<Item> items) {
+        begin();
+        for (const Item& it : items) add(it.dst, it.src, it.bytes);
+        return finish();
+    }
+    int flush() {
+        HIPCHK(hipStreamSynchronize(stream));
+        for (const Staged& it : staged_) {
+            const char* from = stage_.as<char>() + it.off;
+            if (!it.perm) {
+                host_copy(it.dst, from, it.n_rows * it.row_bytes);
+                continue;
+            }
+            for (size_t i = 0; i < it.n_rows; ++i)
+                host_copy(it.dst + (size_t)it.perm[i] * it.row_bytes, from + i * it.row_bytes, it.row_bytes);
+        }
+        staged_.clear();
+        used_ = 0;
+        return PBVI_OK;
+    }
+    // the staging buffer holds at least `bytes` and nothing is staged in it
+    int reserve(size_t bytes) {
+        int rc = flush();
+        if (rc) return rc;
+        if (!stage_.ensure(bytes, std::max<size_t>(bytes * 2, (size_t)64 << 20))) FAIL(PBVI_ENOMEM, "pinned staging allocation failed");
+        return PBVI_OK;
+    }
+    // ... as raw page-locked memory for the caller's own copies, done before the next transaction
+    template <typename U>
+    int raw(size_t bytes, U** p) {
+        int rc = reserve(bytes);
+        if (rc) return rc;
+        *p = stage_.as<U>();
+        return PBVI_OK;
+    }
+
+   private:
+    struct Staged {
+        char* dst;
+        size_t off, n_rows, row_bytes;
+        const int32_t* perm;      // the caller's array: alive until the flush
+    };
+    PinnedBuf stage_;
+    std::vector<Staged> staged_;
+    size_t used_ = 0;
+    int rc_ = PBVI_OK;
+
+    int queue(char* dst, const char* src, size_t src_ld, size_t n_rows, size_t row_bytes, const int32_t* perm, bool direct) {
+        const size_t bytes = n_rows * row_bytes;
+        const bool device = is_device_pointer(dst);
+        if (device && perm) {     // rare (no caller in the package asks for a sorted block in device memory): row by row
+            for (size_t i = 0; i < n_rows; ++i)
+                HIPCHK(hipMemcpyAsync(dst + (size_t)perm[i] * row_bytes, src + i * src_ld, row_bytes, hipMemcpyDeviceToDevice, stream));
+            return PBVI_OK;
+        }
+        const bool staged = !device && (perm || !(direct || is_pinned_host_pointer(dst)));
+        char* to = dst;
+        size_t off = 0;
+        if (staged) {
+            if ((used_ + 255) / 256 * 256 + bytes > stage_.cap) {
+                int rc = reserve(bytes);
+                if (rc) return rc;
+            }
+            off = (used_ + 255) / 256 * 256;
+            to = stage_.as<char>() + off;
+        }
+        const hipMemcpyKind kind = device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        if (src_ld == row_bytes)
+            HIPCHK(hipMemcpyAsync(to, src, bytes, kind, stream));
+        else
+            HIPCHK(hipMemcpy2DAsync(to, row_bytes, src, src_ld, row_bytes, n_rows, kind, stream));
+        if (staged) {
+            staged_.push_back({dst, off, n_rows, row_bytes, perm});
+            used_ = off + bytes;
+        }
+        return PBVI_OK;
+    }
+};
+
 // keys of the unique rows of the last backup: key[u] = (a*, v*[a*, 0..O-1]) of the u-th distinct (a*, v*) pair
 __global__ void k_gather_keys(int U, int A, int O, const int32_t* __restrict__ uniq, const int32_t* __restrict__ action,
                               const int32_t* __restrict__ best_v, int32_t* __restrict__ keys) {
@@ -1049,7 +1164,7 @@ class EngineT : public EngineBase {
     DevBuf vmax_bk_{mem_};   // max_v b.alpha_v of the last backup's beliefs (belief-side GEMM's extra rows)
     bool have_bk_vmax_ = false;
     hipEvent_t walk_ev_[8] = {};                            // belief_walk: chain -> copy -> host hand-offs, per quarter                                 // rows the last belief_walk left in walk64_
-    PinnedBuf host_stage_{pinned_, "hipHostFree(stage)"};   // bounce buffer for rows going to pageable host memory
+    Delivery out_{pinned_};   // every result's way to the caller's memory (owns the pinned staging buffer)
     DevBuf keys_tmp_{mem_}, keys_act_{mem_}, keys_best_{mem_}, keys_rows_{mem_};   // unique-row keys out / rows from keys in (multi-GPU exchange)
     DevBuf acand_{mem_};   // [B][A] action inside the window (k_action_select -> k_refine_action)
     DevBuf q_{mem_}, q_res_{mem_}, q_act_{mem_};   // pbvi_q_values: q [B][A] in engine order / caller order, its argmax [B]
@@ -1245,6 +1360,7 @@ class EngineT : public EngineBase {
         } else {
         HIPCHK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
         }
+        out_.stream = stream_;
         if (owns_streams_) {   // The side stream gets its own priority class.  Streams of one class share a small pool of hardware
             // queues, assigned round-robin at creation: once a RCCL communicator has created its streams, two
             // normal-priority streams made afterwards can land on one queue and the side work no longer overlaps
@@ -1562,6 +1678,8 @@ class EngineT : public EngineBase {
         h_perm_valid_ = true;
         return PBVI_OK;
     }
+    // ... as Delivery::add_rows takes it, after host_perm(): nullptr where the rows lie in the caller's order already
+    const int32_t* caller_order() const { return sorted_ ? h_perm_.data() : nullptr; }
 
     int beliefs_set(const void* bel, int64_t B) override {
         if (B <= 0 || bel == nullptr) FAIL(PBVI_EINVAL, "beliefs_set: need B > 0 and a non-null array");
@@ -1695,16 +1813,9 @@ class EngineT : public EngineBase {
         // computed in engine order into bu_out_, then gathered back into the caller's order
         if ((rc = bayes_push(nullptr, false))) return rc;
         HIPCHK(launch_belief_norm<T>(bayes_step(false), S_, nullptr, bu_out_.as<T>(), S_, stream_));
-        HIPCHK(hipStreamSynchronize(stream_));
-        if (!sorted_) {
-            HIPCHK(hipMemcpy(out, bu_out_.p, (size_t)B_ * S_ * sizeof(T), hipMemcpyDefault));
-        } else {   // row i of the engine order is the caller's row perm[i]
-            for (int64_t i = 0; i < B_; ++i)
-                HIPCHK(hipMemcpyAsync((char*)out + (size_t)h_perm_[(size_t)i] * S_ * sizeof(T),
-                                      bu_out_.as<T>() + (size_t)i * S_, (size_t)S_ * sizeof(T), hipMemcpyDefault, stream_));
-            HIPCHK(hipStreamSynchronize(stream_));
-        }
-        return PBVI_OK;
+        out_.begin();
+        out_.add_rows(out, bu_out_.p, (size_t)S_ * sizeof(T), (size_t)B_, (size_t)S_ * sizeof(T), caller_order());
+        return out_.finish();
     }
 
     // Simulator step on the resident block (src/pomdp.py:3305-3311 update, :3326-3329 done-filter): every belief is
@@ -1757,12 +1868,10 @@ class EngineT : public EngineBase {
         HIPCHK(hipSetDevice(device_));
         int rc = infotaxis_device(out_p_obs != nullptr, out_entropy != nullptr);
         if (rc) return rc;
-        if ((rc = out_begin())) return rc;
-        if ((rc = out_add(out_g, it_g_.p, (size_t)B_ * A_ * sizeof(double)))) return rc;
-        if (out_action && (rc = out_add(out_action, it_act_.p, (size_t)B_ * sizeof(int32_t)))) return rc;
-        if (out_p_obs && (rc = out_add(out_p_obs, it_pobs_.p, (size_t)B_ * A_ * O_ * sizeof(double)))) return rc;
-        if (out_entropy && (rc = out_add(out_entropy, it_h_.p, (size_t)B_ * sizeof(double)))) return rc;
-        return out_finish();
+        return out_.deliver({{out_g, it_g_.p, (size_t)B_ * A_ * sizeof(double)},
+                             {out_action, it_act_.p, (size_t)B_ * sizeof(int32_t)},
+                             {out_p_obs, it_pobs_.p, (size_t)B_ * A_ * O_ * sizeof(double)},
+                             {out_entropy, it_h_.p, (size_t)B_ * sizeof(double)}});
     }
 
     // ---- environments (pbvi_env_set_frames / pbvi_env_set_table / pbvi_env_clear) ---- //
@@ -1991,11 +2100,12 @@ class EngineT : public EngineBase {
         const size_t len[4] = {n_st, n_ao, n_ao, (size_t)n0};
         // one transfer of the whole trajectory buffer into the pinned staging area, then host copies of the parts asked for
         if (dsts[0] || dsts[1] || dsts[2] || dsts[3]) {
-            if ((rc = stage_reserve(n_traj * sizeof(int32_t)))) return rc;
-            HIPCHK(hipMemcpyAsync(host_stage_.p, ro_traj_.p, n_traj * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+            char* h_traj = nullptr;
+            if ((rc = out_.raw(n_traj * sizeof(int32_t), &h_traj))) return rc;
+            HIPCHK(hipMemcpyAsync(h_traj, ro_traj_.p, n_traj * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
             HIPCHK(hipStreamSynchronize(stream_));
             for (int k = 0; k < 4; ++k)
-                if (dsts[k]) host_copy(dsts[k], host_stage_.as<char>() + (size_t)(src[k] - tr_states) * sizeof(int32_t), len[k] * sizeof(int32_t));
+                if (dsts[k]) host_copy(dsts[k], h_traj + (size_t)(src[k] - tr_states) * sizeof(int32_t), len[k] * sizeof(int32_t));
         } else {
             HIPCHK(hipStreamSynchronize(stream_));
         }
@@ -2173,18 +2283,11 @@ class EngineT : public EngineBase {
         if (B_ <= 0) FAIL(PBVI_EINVAL, "beliefs_fetch: no belief block resident");
         if (!out) FAIL(PBVI_EINVAL, "beliefs_fetch: NULL argument");
         HIPCHK(hipSetDevice(device_));
-        if (!sorted_) {
-            HIPCHK(hipMemcpy2DAsync(out, (size_t)S_ * sizeof(T), bel_.p, (size_t)S_pad_ * sizeof(T), (size_t)S_ * sizeof(T),
-                                    (size_t)B_, hipMemcpyDefault, stream_));
-        } else {
-            int rc = host_perm();
-            if (rc) return rc;
-            for (int64_t i = 0; i < B_; ++i)
-                HIPCHK(hipMemcpyAsync((char*)out + (size_t)h_perm_[(size_t)i] * S_ * sizeof(T),
-                                      bel_.as<T>() + (size_t)i * S_pad_, (size_t)S_ * sizeof(T), hipMemcpyDefault, stream_));
-        }
-        HIPCHK(hipStreamSynchronize(stream_));
-        return PBVI_OK;
+        int rc = host_perm();
+        if (rc) return rc;
+        out_.begin();
+        out_.add_rows(out, bel_.p, (size_t)S_pad_ * sizeof(T), (size_t)B_, (size_t)S_ * sizeof(T), caller_order());
+        return out_.finish();
     }
 
     int64_t beliefs_count() const override { return B_; }
@@ -2193,7 +2296,6 @@ class EngineT : public EngineBase {
     int64_t store_append(int which, const void* rows, int64_t n) override {
         if (which < 0 || which > 1 || n < 0 || (n > 0 && rows == nullptr)) FAIL(PBVI_EINVAL, "store_append: bad arguments");
         if (hipSetDevice(device_) != hipSuccess) FAIL(PBVI_ERUNTIME, "hipSetDevice failed");
-        const int64_t have = store_rows_[which];
         T* dst = nullptr;
         int rc = store_reserve(which, n, &dst);
         if (rc) return rc;
@@ -2204,20 +2306,18 @@ class EngineT : public EngineBase {
                 hipStreamSynchronize(stream_) != hipSuccess)
                 FAIL(PBVI_ERUNTIME, "store_append: upload failed");
         }
-        store_rows_[which] = have + n;
-        return have;
+        return store_commit(which, n);
     }
 
     // distinct alpha' rows of the last backup -> alpha store, device to device (ids are consecutive from the return)
     int64_t store_append_unique(const int32_t* unique_idx, int64_t n) override {
-        if (!have_result_) FAIL(PBVI_EINVAL, "backup_store_unique: no backup result resident");
+        int rc = need_result("backup_store_unique");
+        if (rc) return rc;
         if (n <= 0 || n > 65535 || unique_idx == nullptr) FAIL(PBVI_EINVAL, "backup_store_unique: bad arguments (1 <= n <= 65535)");
         for (int64_t i = 0; i < n; ++i)
             if (unique_idx[i] < 0 || unique_idx[i] >= res_unique_) FAIL(PBVI_EINVAL, "backup_store_unique: row index out of range");
-        HIPCHK(hipSetDevice(device_));
         T* dst = nullptr;
-        int rc = store_reserve(0, n, &dst);
-        if (rc) return rc;
+        if ((rc = store_reserve(0, n, &dst))) return rc;
         if ((rc = ids_.ensure((size_t)n * sizeof(int32_t)))) return rc;
         HIPCHK(hipMemcpyAsync(ids_.p, unique_idx, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
         if (S_pad_ > S_) HIPCHK(hipMemsetAsync(dst, 0, (size_t)n * S_pad_ * sizeof(T), stream_));   // pad columns stay zero
@@ -2225,9 +2325,7 @@ class EngineT : public EngineBase {
                            dst, S_pad_, S_, ids_.as<int32_t>());
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(stream_));            // unique_idx is the caller's host memory
-        const int64_t first = store_rows_[0];
-        store_rows_[0] = first + n;
-        return first;
+        return store_commit(0, n);
     }
 
     // make room for n more rows in a store, keeping what is there; returns the destination of the new rows
@@ -2239,6 +2337,12 @@ class EngineT : public EngineBase {
         if (rc) return rc;
         *dst = st.as<T>() + (size_t)have * S_pad_;
         return PBVI_OK;
+    }
+    // the n rows written behind a store's rows are its rows now; returns the id of the first of them
+    int64_t store_commit(int which, int64_t n) {
+        const int64_t first = store_rows_[which];
+        store_rows_[which] = first + n;
+        return first;
     }
 
     // fp64 copy of RTO (reference layout [S][A][O][R]) for the belief walk of an f32 engine: the host mirror keeps
@@ -2286,9 +2390,10 @@ class EngineT : public EngineBase {
         constexpr int kChunks = 4;
         int64_t chunk_end[kChunks];
         int n_chunks = 0;
+        char* h_rows = nullptr;                                                  // the staging buffer as raw pinned memory
         if (to_host && n >= 2 * kChunks) {
-            if ((rc = out_begin())) return rc;                                   // (nothing of an earlier call is staged)
-            if ((rc = stage_reserve((size_t)n * S_ * sizeof(double)))) return rc;
+            out_.begin();                                                        // (nothing of an earlier call is staged)
+            if ((rc = out_.raw((size_t)n * S_ * sizeof(double), &h_rows))) return rc;
             for (auto& e : walk_ev_) HIPCHK(new_event(&e, hipEventDisableTiming, "hipEventDestroy(walk)"));
             n_chunks = kChunks;
             for (int c = 0; c < kChunks; ++c) chunk_end[c] = n * (c + 1) / kChunks;
@@ -2301,7 +2406,7 @@ class EngineT : public EngineBase {
             const int64_t r0 = c ? chunk_end[c - 1] : 0, r1 = chunk_end[c];
             HIPCHK(hipEventRecord(walk_ev_[2 * c], stream_));
             HIPCHK(hipStreamWaitEvent(stream2_, walk_ev_[2 * c], 0));
-            HIPCHK(hipMemcpyAsync(host_stage_.as<char>() + (size_t)r0 * S_ * sizeof(double), rows + (size_t)(r0 + 1) * S_,
+            HIPCHK(hipMemcpyAsync(h_rows + (size_t)r0 * S_ * sizeof(double), rows + (size_t)(r0 + 1) * S_,
                                   (size_t)(r1 - r0) * S_ * sizeof(double), hipMemcpyDeviceToHost, stream2_));
             HIPCHK(hipEventRecord(walk_ev_[2 * c + 1], stream2_));
             return PBVI_OK;
@@ -2342,19 +2447,15 @@ class EngineT : public EngineBase {
             for (int c = 0; c < n_chunks; ++c) {
                 const int64_t r0 = c ? chunk_end[c - 1] : 0;
                 HIPCHK(hipEventSynchronize(walk_ev_[2 * c + 1]));
-                host_copy((char*)out + (size_t)r0 * S_ * sizeof(double), host_stage_.as<char>() + (size_t)r0 * S_ * sizeof(double),
+                host_copy((char*)out + (size_t)r0 * S_ * sizeof(double), h_rows + (size_t)r0 * S_ * sizeof(double),
                             (size_t)(chunk_end[c] - r0) * S_ * sizeof(double));
             }
             HIPCHK(hipStreamSynchronize(stream_));
-        } else {
-            if ((rc = out_begin())) return rc;
-            if ((rc = out_add(out, rows + S_, (size_t)n * S_ * sizeof(double)))) return rc;
-            if ((rc = out_finish())) return rc;
+        } else if ((rc = out_.deliver({{out, rows + S_, (size_t)n * S_ * sizeof(double)}}))) {
+            return rc;
         }
-        const int64_t first = store_rows_[1];
-        store_rows_[1] = first + n;
         walk_rows_ = n;
-        return first;
+        return store_commit(1, n);
     }
 
     // max_v b.alpha_v of the last backup's beliefs against its alpha set, caller order (belief-side formulation only)
@@ -2363,10 +2464,7 @@ class EngineT : public EngineBase {
             FAIL(PBVI_EUNSUPPORTED, "backup_fetch_value_max: the last backup did not run in the belief-side formulation");
         if (!out_value) FAIL(PBVI_EINVAL, "backup_fetch_value_max: NULL destination");
         HIPCHK(hipSetDevice(device_));
-        int rc;
-        if ((rc = out_begin())) return rc;
-        if ((rc = out_add(out_value, vmax_bk_.p, (size_t)res_B_ * sizeof(double)))) return rc;
-        return out_finish();
+        return out_.deliver({{out_value, vmax_bk_.p, (size_t)res_B_ * sizeof(double)}});
     }
 
     // position-weighted bit-pattern hashes (k_row_hash) of the fp64 rows of the last walk (rows 1..n of walk64_), for the
@@ -2379,9 +2477,7 @@ class EngineT : public EngineBase {
         hipLaunchKernelGGL(k_row_hash<double>, dim3((unsigned)n), dim3(256), 0, stream_, walk64_.as<double>() + S_, S_, S_,
                            keys_tmp_.as<unsigned long long>());
         HIPCHK(hipGetLastError());
-        if ((rc = out_begin())) return rc;
-        if ((rc = out_add(out_keys, keys_tmp_.p, (size_t)n * sizeof(uint64_t)))) return rc;
-        return out_finish();
+        return out_.deliver({{out_keys, keys_tmp_.p, (size_t)n * sizeof(uint64_t)}});
     }
 
     // After a call returned PBVI_ENOMEM: back to the state of a fresh engine (model tables kept, every working set, row
@@ -2633,7 +2729,7 @@ class EngineT : public EngineBase {
         // (the decision's buffers too in front of the scoring stage, which plans Gamma tiling with what is free)
         if (!q_only_ && (rc = fin_.ensure(B_, c.pairs, (size_t)S_ * sizeof(T), sorted_))) return rc;
         if ((rc = keep_.ensure((size_t)B_))) return rc;
-        if (c.windows && (rc = stage_reserve(256))) return rc;      // the pinned bounce buffer of the fetches that follow, allocated while the stream is idle
+        if (c.windows && (rc = out_.reserve(256))) return rc;      // the pinned bounce buffer of the fetches that follow, allocated while the stream is idle
         HIPCHK(hipMemsetAsync(counters_.p, 0, CNT_SLOTS * sizeof(int), stream_));
         HIPCHK(hipEventRecord(ev_[0], stream_));
         return PBVI_OK;
@@ -2855,7 +2951,7 @@ class EngineT : public EngineBase {
             work.hncand = c.io.hncand;
         }
         // the counts land in two of the engine's pinned flag words -- not in the staging buffer: run_fetch stages results
-        // through that one before the counts are read, and out_add may reset or reallocate it
+        // through that one before the counts are read, and a Delivery::add may reset or reallocate it
         rf_counts_ = words().deferred;
         rf_counts_[0] = rf_counts_[1] = 0;
         last_work_ = work;                                       // (pbvi_debug_refine_counts)
@@ -3001,8 +3097,8 @@ class EngineT : public EngineBase {
             HIPCHK(hipGetLastError());
             dst.queued = true;
         } else if (early_.used && dst.slot != nullptr) {     // run_fetch: slots, index, actions (best, keep) with this read-back
-            if ((rc = out_begin())) return rc;
-            if ((rc = out_add(dst.slot, e_slot_.p, (size_t)B_ * sizeof(int32_t)))) return rc;
+            out_.begin();
+            out_.add(dst.slot, e_slot_.p, (size_t)B_ * sizeof(int32_t));
             if ((rc = out_add_small((size_t)B_, dst.index, dst.action, dst.best, dst.keep))) return rc;
             dst.queued = true;
         }
@@ -3107,41 +3203,40 @@ class EngineT : public EngineBase {
         return PBVI_OK;
     }
 
-    int backup_fetch(void* out_alpha, int32_t* out_action, int32_t* out_best, uint8_t* out_keep) override {
-        if (!have_result_) FAIL(PBVI_EINVAL, "backup_fetch: no backup result resident (call pbvi_backup_run first)");
+    // What every fetch of a backup's results begins with: fails unless one is resident -- with "<who>: no backup result
+    // resident", or with `text` where an entry words it differently -- and makes the engine's device current.
+    int need_result(const std::string& who, const std::string& text = "") {
+        if (!have_result_) FAIL(PBVI_EINVAL, text.empty() ? who + ": no backup result resident" : text);
         HIPCHK(hipSetDevice(device_));
-        const size_t B = (size_t)res_B_;
-        int rc;
-        if ((rc = out_begin())) return rc;
-        if (out_alpha) {
-            if ((rc = ensure_full())) return rc;
-            if ((rc = out_add(out_alpha, out_full_.p, B * S_ * sizeof(T)))) return rc;
-        }
-        if ((rc = out_add_small(B, nullptr, out_action, out_best, out_keep))) return rc;
-        return out_finish();
+        return PBVI_OK;
+    }
+
+    int backup_fetch(void* out_alpha, int32_t* out_action, int32_t* out_best, uint8_t* out_keep) override {
+        int rc = need_result("", "backup_fetch: no backup result resident (call pbvi_backup_run first)");
+        if (rc) return rc;
+        if (out_alpha && (rc = ensure_full())) return rc;
+        out_.begin();
+        out_.add(out_alpha, out_full_.p, (size_t)res_B_ * S_ * sizeof(T));
+        out_add_small((size_t)res_B_, nullptr, out_action, out_best, out_keep);
+        return out_.finish();
     }
 
     // the small per-belief results of the decision, each to where the caller wants it (NULL: not wanted): index into the
-    // distinct rows, actions, best_alpha_ind, keep mask
+    // distinct rows, actions, best_alpha_ind, keep mask.  Into the open transaction; returns its first error.
     int out_add_small(size_t B, int32_t* index, int32_t* action, int32_t* best, uint8_t* keep) {
-        int rc;
-        if (index && (rc = out_add(index, fin_.inv.p, B * sizeof(int32_t)))) return rc;
-        if (action && (rc = out_add(action, res_action_, B * sizeof(int32_t)))) return rc;
-        if (best && (rc = out_add(best, res_best_, B * A_ * O_ * sizeof(int32_t)))) return rc;
-        if (keep && (rc = out_add(keep, keep_.p, B))) return rc;
-        return PBVI_OK;
+        out_.add(index, fin_.inv.p, B * sizeof(int32_t));
+        out_.add(action, res_action_, B * sizeof(int32_t));
+        out_.add(best, res_best_, B * A_ * O_ * sizeof(int32_t));
+        return out_.add(keep, keep_.p, B);
     }
 
     int64_t unique_count() const override { return have_result_ ? res_unique_ : -1; }
 
     int fetch_unique(void* out_rows, int32_t* out_index) override {
-        if (!have_result_) FAIL(PBVI_EINVAL, "backup_fetch_unique: no backup result resident");
-        HIPCHK(hipSetDevice(device_));
-        int rc;
-        if ((rc = out_begin())) return rc;
-        if (out_rows && (rc = out_add(out_rows, fin_.rows.p, (size_t)res_unique_ * S_ * sizeof(T)))) return rc;
-        if (out_index && (rc = out_add(out_index, fin_.inv.p, (size_t)res_B_ * sizeof(int32_t)))) return rc;
-        return out_finish();
+        int rc = need_result("backup_fetch_unique");
+        if (rc) return rc;
+        return out_.deliver({{out_rows, fin_.rows.p, (size_t)res_unique_ * S_ * sizeof(T)},
+                             {out_index, fin_.inv.p, (size_t)res_B_ * sizeof(int32_t)}});
     }
 
     // everything a caller of backup() needs, in one staged transfer and one synchronisation: the U distinct rows, the
@@ -3165,12 +3260,12 @@ class EngineT : public EngineBase {
         const bool early_ok = early_.used && !words().early[2];
         if (early_ok) used = (int64_t)words().early[0] + words().early[1];
         // the small arrays came with the pipeline's last read-back (host-side copies of staged items; the stream is idle)
-        if (queued && (rc = out_flush())) return rc;
+        if (queued && (rc = out_.flush())) return rc;
         if (!queued || !early_ok) {   // the early path did not apply: everything now; the slots overflowed: rows in the plain order
-            if ((rc = out_begin())) return rc;
-            if ((rc = out_add(out_rows, fin_.rows.p, (size_t)res_unique_ * S_ * sizeof(T)))) return rc;
-            if (!queued && (rc = out_add_small((size_t)res_B_, out_index, out_action, out_best, out_keep))) return rc;
-            if ((rc = out_finish())) return rc;
+            out_.begin();
+            out_.add(out_rows, fin_.rows.p, (size_t)res_unique_ * S_ * sizeof(T));
+            if (!queued) out_add_small((size_t)res_B_, out_index, out_action, out_best, out_keep);
+            if ((rc = out_.finish())) return rc;
         }
         if (!early_ok)
             for (int64_t u = 0; u < res_unique_; ++u) out_slot[u] = (int32_t)u;
@@ -3181,120 +3276,89 @@ class EngineT : public EngineBase {
     }
 
     int fetch_compact(void* out_rows, int32_t* out_index, int32_t* out_action, int32_t* out_best, uint8_t* out_keep) override {
-        if (!have_result_) FAIL(PBVI_EINVAL, "backup_fetch_compact: no backup result resident");
-        HIPCHK(hipSetDevice(device_));
-        int rc;
-        if ((rc = out_begin())) return rc;
-        if (out_rows && (rc = out_add(out_rows, fin_.rows.p, (size_t)res_unique_ * S_ * sizeof(T)))) return rc;
-        if ((rc = out_add_small((size_t)res_B_, out_index, out_action, out_best, out_keep))) return rc;
-        return out_finish();
-    }
-
-    // ---- device -> host results ------------------------------------------------------------------------------------ //
-    // Results bound for ordinary (pageable) host memory go through one long-lived pinned buffer and a CPU memcpy:
-    // the DMA never targets memory the driver has to register first.  Device destinations are copied directly.
-    // (The caller should not map fresh host memory per call either: see HostArena in engine.py.)
-    struct OutItem {
-        void* dst;
-        size_t off, bytes;
-    };
-    std::vector<OutItem> out_items_;
-    size_t out_used_ = 0;
-
-    int out_begin() {
-        out_items_.clear();
-        out_used_ = 0;
-        return PBVI_OK;
-    }
-    int out_flush() {
-        HIPCHK(hipStreamSynchronize(stream_));
-        for (const OutItem& it : out_items_) host_copy(it.dst, host_stage_.as<char>() + it.off, it.bytes);
-        out_items_.clear();
-        out_used_ = 0;
-        return PBVI_OK;
-    }
-    int out_add(void* dst, const void* src_dev, size_t bytes) {
-        if (bytes == 0) return PBVI_OK;
-        if (is_device_pointer(dst)) {
-            HIPCHK(hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToDevice, stream_));
-            return PBVI_OK;
-        }
-        if (is_pinned_host_pointer(dst)) {                   // caller's page-locked buffer: DMA straight into it
-            HIPCHK(hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToHost, stream_));
-            return PBVI_OK;
-        }
-        const size_t need = (out_used_ + 255) / 256 * 256 + bytes;
-        if (need > host_stage_.cap) {
-            int rc = stage_reserve(bytes);                   // (flushes first: nothing staged may be lost when the buffer moves)
-            if (rc) return rc;
-        }
-        const size_t off = (out_used_ + 255) / 256 * 256;
-        HIPCHK(hipMemcpyAsync(host_stage_.as<char>() + off, src_dev, bytes, hipMemcpyDeviceToHost, stream_));
-        out_items_.push_back({dst, off, bytes});
-        out_used_ = off + bytes;
-        return PBVI_OK;
-    }
-    int out_finish() { return out_flush(); }
-    // pinned buffer of at least `bytes` with nothing staged in it
-    int stage_reserve(size_t bytes) {
-        int rc = out_flush();
+        int rc = need_result("backup_fetch_compact");
         if (rc) return rc;
-        if (!host_stage_.ensure(bytes, std::max<size_t>(bytes * 2, (size_t)64 << 20))) FAIL(PBVI_ENOMEM, "pinned staging allocation failed");
-        return PBVI_OK;
+        out_.begin();
+        out_.add(out_rows, fin_.rows.p, (size_t)res_unique_ * S_ * sizeof(T));
+        out_add_small((size_t)res_B_, out_index, out_action, out_best, out_keep);
+        return out_.finish();
     }
 
     // position-weighted bit-pattern hashes of the U distinct rows of the last backup (see k_row_hash)
     int fetch_row_hashes(uint64_t* out) override {
-        if (!have_result_) FAIL(PBVI_EINVAL, "backup_fetch_row_hashes: no backup result resident");
+        int rc = need_result("backup_fetch_row_hashes");
+        if (rc) return rc;
         if (!out) FAIL(PBVI_EINVAL, "backup_fetch_row_hashes: NULL destination");
         if (res_unique_ <= 0) return PBVI_OK;
-        HIPCHK(hipSetDevice(device_));
-        int rc = keys_tmp_.ensure((size_t)res_unique_ * sizeof(uint64_t));
-        if (rc) return rc;
+        if ((rc = keys_tmp_.ensure((size_t)res_unique_ * sizeof(uint64_t)))) return rc;
         hipLaunchKernelGGL(k_row_hash<T>, dim3((unsigned)res_unique_), dim3(256), 0, stream_, fin_.rows.as<T>(), S_, S_,
                            keys_tmp_.as<unsigned long long>());
         HIPCHK(hipGetLastError());
-        if ((rc = out_begin())) return rc;
-        if ((rc = out_add(out, keys_tmp_.p, (size_t)res_unique_ * sizeof(uint64_t)))) return rc;
-        return out_finish();
+        return out_.deliver({{out, keys_tmp_.p, (size_t)res_unique_ * sizeof(uint64_t)}});
     }
 
     // (a*, v*[a*,:]) of every unique row of the last backup: [U][1+O] int32, host or device destination
     int fetch_unique_keys(int32_t* out_keys) override {
-        if (!have_result_) FAIL(PBVI_EINVAL, "backup_fetch_unique_keys: no backup result resident");
+        int rc = need_result("backup_fetch_unique_keys");
+        if (rc) return rc;
         if (!out_keys) FAIL(PBVI_EINVAL, "backup_fetch_unique_keys: NULL destination");
         if (res_unique_ <= 0) return PBVI_OK;
-        HIPCHK(hipSetDevice(device_));
-        int rc = keys_tmp_.ensure((size_t)res_unique_ * (1 + O_) * sizeof(int32_t));
-        if (rc) return rc;
+        if ((rc = keys_tmp_.ensure((size_t)res_unique_ * (1 + O_) * sizeof(int32_t)))) return rc;
         hipLaunchKernelGGL(k_gather_keys, dim3((unsigned)((res_unique_ + 63) / 64)), dim3(64), 0, stream_, (int)res_unique_, A_, O_,
                            fin_.uniq.as<int32_t>(), res_action_, res_best_, keys_tmp_.as<int32_t>());
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(out_keys, keys_tmp_.p, (size_t)res_unique_ * (1 + O_) * sizeof(int32_t), hipMemcpyDefault, stream_));
-        HIPCHK(hipStreamSynchronize(stream_));
-        return PBVI_OK;
+        return out_.deliver({{out_keys, keys_tmp_.p, (size_t)res_unique_ * (1 + O_) * sizeof(int32_t)}});
     }
 
-    // one buffer with everything this rank contributes to the multi-GPU exchange (layout: k_pack_exchange)
+    // one buffer with everything this rank contributes to the multi-GPU exchange (layout: k_pack_exchange): the kernel
+    // writes a device destination itself, a host destination is delivered from keys_tmp_
     int fetch_exchange(int32_t* out, int64_t per) override {
-        if (!have_result_) FAIL(PBVI_EINVAL, "backup_fetch_exchange: no backup result resident");
+        int rc = need_result("backup_fetch_exchange");
+        if (rc) return rc;
         if (!out) FAIL(PBVI_EINVAL, "backup_fetch_exchange: NULL destination");
         if (per < res_B_ || per > 0x7fffffff) FAIL(PBVI_EINVAL, "backup_fetch_exchange: per must be >= the number of beliefs of the last backup");
-        HIPCHK(hipSetDevice(device_));
         const size_t n = 1 + 3 * (size_t)per + (size_t)per * (1 + O_);
-        int32_t* dst = out;
         const bool direct = is_device_pointer(out);
-        if (!direct) {
-            int rc = keys_tmp_.ensure(n * sizeof(int32_t));
-            if (rc) return rc;
-            dst = keys_tmp_.as<int32_t>();
-        }
+        if (!direct && (rc = keys_tmp_.ensure(n * sizeof(int32_t)))) return rc;
+        int32_t* dst = direct ? out : keys_tmp_.as<int32_t>();
         hipLaunchKernelGGL(k_pack_exchange, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, stream_, (int)res_B_, (int)per,
                            (int)res_unique_, A_, O_, fin_.inv.as<int32_t>(), res_action_, keep_.as<uint8_t>(), fin_.uniq.as<int32_t>(),
                            res_best_, dst);
         HIPCHK(hipGetLastError());
-        if (!direct) HIPCHK(hipMemcpyAsync(out, dst, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-        HIPCHK(hipStreamSynchronize(stream_));
+        out_.begin();               // a host destination of either kind by DMA, as it always was (direct: see Delivery::add_rows)
+        if (!direct) out_.add_rows(out, dst, n * sizeof(int32_t), 1, n * sizeof(int32_t), nullptr, true);
+        return out_.finish();
+    }
+
+    // The head the two assemble entries share: their buffers -- with room for the n rows behind the alpha store's (to_store)
+    // or in keys_rows_, *rows / *ld say where -- and the keys (host or device memory) uploaded and scattered into per-row
+    // decisions: keys_act_ / keys_best_, what launch_assemble reads; the word behind the n actions counts the keys out of range.
+    int keys_to_decisions(int64_t n, const int32_t* keys, bool to_store, T** rows, int* ld) {
+        HIPCHK(hipSetDevice(device_));
+        int rc;
+        if ((rc = keys_tmp_.ensure((size_t)n * (1 + O_) * sizeof(int32_t)))) return rc;
+        if ((rc = keys_act_.ensure((size_t)(n + 1) * sizeof(int32_t)))) return rc;      // [n] actions + 1 error counter
+        if ((rc = keys_best_.ensure((size_t)n * A_ * O_ * sizeof(int32_t)))) return rc;
+        if ((rc = to_store ? store_reserve(0, n, rows) : keys_rows_.ensure((size_t)n * S_ * sizeof(T)))) return rc;
+        if (!to_store) *rows = keys_rows_.as<T>();
+        *ld = to_store ? S_pad_ : S_;
+        int* bad = keys_act_.as<int>() + n;
+        HIPCHK(hipMemcpyAsync(keys_tmp_.p, keys, (size_t)n * (1 + O_) * sizeof(int32_t), hipMemcpyDefault, stream_));
+        HIPCHK(hipMemsetAsync(bad, 0, sizeof(int), stream_));
+        hipLaunchKernelGGL(k_scatter_keys, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream_, (int)n, A_, O_, (int)V_,
+                           keys_tmp_.as<int32_t>(), keys_act_.as<int32_t>(), keys_best_.as<int32_t>(), bad);
+        HIPCHK(hipGetLastError());
+        return PBVI_OK;
+    }
+    // ... and their tail: the n assembled rows (ld elements apart) to out_rows (NULL: not wanted), the count of bad keys with
+    // them (direct: see Delivery::add_rows), and the verdict on it
+    int deliver_assembled(const char* who, int64_t n, const T* rows, int64_t ld, void* out_rows, bool direct) {
+        out_.begin();
+        out_.add(&words().bad_key, keys_act_.as<int>() + n, sizeof(int));
+        out_.add_rows(out_rows, rows, (size_t)ld * sizeof(T), (size_t)n, (size_t)S_ * sizeof(T), nullptr, direct);
+        int rc = out_.finish();
+        if (rc) return rc;
+        if (words().bad_key) FAIL(PBVI_EINVAL, std::string(who) + ": action or alpha index out of range");
         return PBVI_OK;
     }
 
@@ -3303,27 +3367,13 @@ class EngineT : public EngineBase {
     int assemble_keys(double gamma, int64_t n, const int32_t* keys, void* out_rows) override {
         if (V_ <= 0) FAIL(PBVI_EINVAL, "assemble_keys: no alpha set resident");
         if (n <= 0 || n > 65535 || !keys || !out_rows) FAIL(PBVI_EINVAL, "assemble_keys: bad arguments (1 <= n <= 65535)");
-        HIPCHK(hipSetDevice(device_));
-        int rc;
-        if ((rc = keys_tmp_.ensure((size_t)n * (1 + O_) * sizeof(int32_t)))) return rc;
-        if ((rc = keys_act_.ensure((size_t)(n + 1) * sizeof(int32_t)))) return rc;      // [n] actions + 1 error counter
-        if ((rc = keys_best_.ensure((size_t)n * A_ * O_ * sizeof(int32_t)))) return rc;
-        if ((rc = keys_rows_.ensure((size_t)n * S_ * sizeof(T)))) return rc;
-        int* bad = keys_act_.as<int>() + n;
-        HIPCHK(hipMemcpyAsync(keys_tmp_.p, keys, (size_t)n * (1 + O_) * sizeof(int32_t), hipMemcpyDefault, stream_));
-        HIPCHK(hipMemsetAsync(bad, 0, sizeof(int), stream_));
-        hipLaunchKernelGGL(k_scatter_keys, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream_, (int)n, A_, O_, (int)V_,
-                           keys_tmp_.as<int32_t>(), keys_act_.as<int32_t>(), keys_best_.as<int32_t>(), bad);
-        HIPCHK(hipGetLastError());
+        T* rows = nullptr;
+        int ld = 0;
+        int rc = keys_to_decisions(n, keys, false, &rows, &ld);
+        if (rc) return rc;
         HIPCHK(launch_assemble<T>(alpha_.as<T>(), S_pad_, view(), gamma, keys_act_.as<int32_t>(), keys_best_.as<int32_t>(), nullptr,
-                                  nullptr, (int)n, keys_rows_.as<T>(), S_, stream_));
-        int* h_bad = &words().bad_key;
-        *h_bad = 0;
-        HIPCHK(hipMemcpyAsync(h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, stream_));
-        HIPCHK(hipMemcpyAsync(out_rows, keys_rows_.p, (size_t)n * S_ * sizeof(T), hipMemcpyDefault, stream_));
-        HIPCHK(hipStreamSynchronize(stream_));
-        if (*h_bad) FAIL(PBVI_EINVAL, "assemble_keys: action or alpha index out of range");
-        return PBVI_OK;
+                                  nullptr, (int)n, rows, ld, stream_));
+        return deliver_assembled("assemble_keys", n, rows, ld, out_rows, true);
     }
 
     // Same, and the rows also join the alpha store (ids consecutive from the return value): the sharded backup's
@@ -3331,50 +3381,22 @@ class EngineT : public EngineBase {
     int64_t assemble_keys_store(double gamma, int64_t n, const int32_t* keys, void* out_rows) override {
         if (V_ <= 0) FAIL(PBVI_EINVAL, "assemble_rows_store: no alpha set resident");
         if (n <= 0 || n > 65535 || !keys) FAIL(PBVI_EINVAL, "assemble_rows_store: bad arguments (1 <= n <= 65535)");
-        HIPCHK(hipSetDevice(device_));
-        int rc;
-        if ((rc = keys_tmp_.ensure((size_t)n * (1 + O_) * sizeof(int32_t)))) return rc;
-        if ((rc = keys_act_.ensure((size_t)(n + 1) * sizeof(int32_t)))) return rc;
-        if ((rc = keys_best_.ensure((size_t)n * A_ * O_ * sizeof(int32_t)))) return rc;
         T* dst = nullptr;
-        if ((rc = store_reserve(0, n, &dst))) return rc;
-        int* bad = keys_act_.as<int>() + n;
-        HIPCHK(hipMemcpyAsync(keys_tmp_.p, keys, (size_t)n * (1 + O_) * sizeof(int32_t), hipMemcpyDefault, stream_));
-        HIPCHK(hipMemsetAsync(bad, 0, sizeof(int), stream_));
-        hipLaunchKernelGGL(k_scatter_keys, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream_, (int)n, A_, O_, (int)V_,
-                           keys_tmp_.as<int32_t>(), keys_act_.as<int32_t>(), keys_best_.as<int32_t>(), bad);
-        HIPCHK(hipGetLastError());
+        int ld = 0;
+        int rc = keys_to_decisions(n, keys, true, &dst, &ld);
+        if (rc) return rc;
         if (S_pad_ > S_) HIPCHK(hipMemsetAsync(dst, 0, (size_t)n * S_pad_ * sizeof(T), stream_));   // pad columns stay zero
         HIPCHK(launch_assemble<T>(alpha_.as<T>(), S_pad_, view(), gamma, keys_act_.as<int32_t>(), keys_best_.as<int32_t>(), nullptr,
-                                  nullptr, (int)n, dst, S_pad_, stream_));
-        int* h_bad = &words().bad_key;
-        *h_bad = 0;
-        HIPCHK(hipMemcpyAsync(h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, stream_));
-        if (out_rows) {
-            if (is_device_pointer(out_rows) || is_pinned_host_pointer(out_rows)) {
-                HIPCHK(hipMemcpy2DAsync(out_rows, (size_t)S_ * sizeof(T), dst, (size_t)S_pad_ * sizeof(T), (size_t)S_ * sizeof(T),
-                                        (size_t)n, hipMemcpyDefault, stream_));
-            } else {   // pageable destination: compact on the device, then through the pinned bounce buffer
-                if ((rc = keys_rows_.ensure((size_t)n * S_ * sizeof(T)))) return rc;
-                HIPCHK(hipMemcpy2DAsync(keys_rows_.p, (size_t)S_ * sizeof(T), dst, (size_t)S_pad_ * sizeof(T), (size_t)S_ * sizeof(T),
-                                        (size_t)n, hipMemcpyDeviceToDevice, stream_));
-                if ((rc = out_begin())) return rc;
-                if ((rc = out_add(out_rows, keys_rows_.p, (size_t)n * S_ * sizeof(T)))) return rc;
-                if ((rc = out_finish())) return rc;
-            }
-        }
-        HIPCHK(hipStreamSynchronize(stream_));
-        if (*h_bad) FAIL(PBVI_EINVAL, "assemble_rows_store: action or alpha index out of range");
-        const int64_t first = store_rows_[0];
-        store_rows_[0] = first + n;
-        return first;
+                                  nullptr, (int)n, dst, ld, stream_));
+        if ((rc = deliver_assembled("assemble_rows_store", n, dst, ld, out_rows, false))) return rc;
+        return store_commit(0, n);
     }
 
     int device_results(void** d_alpha, int32_t** d_action, uint8_t** d_keep) override {
-        if (!have_result_) FAIL(PBVI_EINVAL, "no backup result resident");
+        int rc = need_result("", "no backup result resident");
+        if (rc) return rc;
         if (d_alpha) {
-            int rc = ensure_full();
-            if (rc) return rc;
+            if ((rc = ensure_full())) return rc;
             HIPCHK(hipStreamSynchronize(stream_));
             *d_alpha = out_full_.p;
         }
@@ -3390,12 +3412,17 @@ class EngineT : public EngineBase {
         HIPCHK(hipSetDevice(device_));
         int rc = prune_cnt_.ensure((size_t)V_ * sizeof(int));
         if (rc) return rc;
+        int* h_cnt = nullptr;
+        if ((rc = out_.raw((size_t)V_ * sizeof(int), &h_cnt))) return rc;
         HIPCHK(hipMemsetAsync(prune_cnt_.p, 0, (size_t)V_ * sizeof(int), stream_));
         HIPCHK(launch_dominated<T>(alpha_.as<T>(), S_pad_, (int)V_, S_, prune_cnt_.as<int>(), stream_));
-        std::vector<int> cnt((size_t)V_);
-        HIPCHK(hipMemcpyAsync(cnt.data(), prune_cnt_.p, (size_t)V_ * sizeof(int), hipMemcpyDeviceToHost, stream_));
+        return keep_from_counts(prune_cnt_.as<int>(), h_cnt, keep);
+    }
+    // Both prunes end here: the V_ domination counts into pinned memory, and a row is kept iff it was dominated once (by itself)
+    int keep_from_counts(const int* d_cnt, int* h_cnt, uint8_t* keep) {
+        HIPCHK(hipMemcpyAsync(h_cnt, d_cnt, (size_t)V_ * sizeof(int), hipMemcpyDeviceToHost, stream_));
         HIPCHK(hipStreamSynchronize(stream_));
-        for (int64_t i = 0; i < V_; ++i) keep[i] = (cnt[(size_t)i] == 1) ? 1 : 0;
+        for (int64_t i = 0; i < V_; ++i) keep[i] = (h_cnt[i] == 1) ? 1 : 0;
         return PBVI_OK;
     }
 
@@ -3418,8 +3445,8 @@ class EngineT : public EngineBase {
         HIPCHK(hipSetDevice(device_));
         int rc = prune_cnt_.ensure((size_t)2 * V * sizeof(int));
         if (rc) return rc;
-        if ((rc = stage_reserve((size_t)3 * V * sizeof(int)))) return rc;
-        int* h_cnt = host_stage_.as<int>();
+        int* h_cnt = nullptr;
+        if ((rc = out_.raw((size_t)3 * V * sizeof(int), &h_cnt))) return rc;
         int32_t* h_rows = h_cnt + V;
         int* h_out = h_rows + V;
         const int n_old = V - n_new;
@@ -3432,10 +3459,7 @@ class EngineT : public EngineBase {
         int piece = 65535;
         if (const char* c = getenv("PBVI_PRUNE_PIECE")) piece = (int)std::min<int64_t>(65535, std::max<int64_t>(1, atoll(c)));   // tests
         HIPCHK(launch_dominated_masked<T>(alpha_.as<T>(), S_pad_, S_, d_cnt + V, n_old, n_new, d_cnt, piece, stream_));
-        HIPCHK(hipMemcpyAsync(h_out, d_cnt, (size_t)V * sizeof(int), hipMemcpyDeviceToHost, stream_));
-        HIPCHK(hipStreamSynchronize(stream_));
-        for (int i = 0; i < V; ++i) keep[i] = (h_out[i] == 1) ? 1 : 0;
-        return PBVI_OK;
+        return keep_from_counts(d_cnt, h_out, keep);
     }
 
     // exact (f64-refined) max_v b.alpha_v of the resident blocks into bs2_/bv2_
@@ -3455,27 +3479,11 @@ class EngineT : public EngineBase {
         HIPCHK(hipSetDevice(device_));
         int rc = value_max_device();
         if (rc) return rc;
-        std::vector<double> tv;
-        std::vector<int32_t> ti;
-        double* dv = out_value;
-        int32_t* di = out_index;
-        if (sorted_) {                      // device results are in sorted belief order
-            if ((rc = host_perm())) return rc;
-            tv.resize((size_t)B_);
-            ti.resize((size_t)B_);
-            dv = tv.data();
-            di = ti.data();
-        }
-        if ((rc = out_begin())) return rc;
-        if (out_value && (rc = out_add(dv, bs2_.p, (size_t)B_ * sizeof(double)))) return rc;
-        if (out_index && (rc = out_add(di, bv2_.p, (size_t)B_ * sizeof(int32_t)))) return rc;
-        if ((rc = out_finish())) return rc;
-        if (sorted_)
-            for (int64_t i = 0; i < B_; ++i) {
-                if (out_value) out_value[h_perm_[(size_t)i]] = tv[(size_t)i];
-                if (out_index) out_index[h_perm_[(size_t)i]] = ti[(size_t)i];
-            }
-        return PBVI_OK;
+        if ((rc = host_perm())) return rc;  // device results are in sorted belief order
+        out_.begin();
+        out_.add_rows(out_value, bs2_.p, sizeof(double), (size_t)B_, sizeof(double), caller_order());
+        out_.add_rows(out_index, bv2_.p, sizeof(int32_t), (size_t)B_, sizeof(int32_t), caller_order());
+        return out_.finish();
     }
 
     // One-step lookahead values of the resident block against the working alpha set: the backup's pipeline up to best_v
@@ -3492,11 +3500,9 @@ class EngineT : public EngineBase {
         q_only_ = q_want_best_ = false;
         have_result_ = have_bk_vmax_ = false;
         if (rc) return rc;
-        if ((rc = out_begin())) return rc;
-        if ((rc = out_add(out_q, q_res_.p, (size_t)B_ * A_ * sizeof(double)))) return rc;
-        if (out_action && (rc = out_add(out_action, q_act_.p, (size_t)B_ * sizeof(int32_t)))) return rc;
-        if (out_best && (rc = out_add(out_best, fin_.best_res.p, (size_t)B_ * A_ * O_ * sizeof(int32_t)))) return rc;
-        return out_finish();
+        return out_.deliver({{out_q, q_res_.p, (size_t)B_ * A_ * sizeof(double)},
+                             {out_action, q_act_.p, (size_t)B_ * sizeof(int32_t)},
+                             {out_best, fin_.best_res.p, (size_t)B_ * A_ * O_ * sizeof(int32_t)}});
     }
 
     int64_t store_count(int which) const override { return (which == 0 || which == 1) ? store_rows_[which] : -1; }
@@ -3587,10 +3593,9 @@ class EngineT : public EngineBase {
             sorted_ = false;
             btl_valid_ = kF32 && !vmax_skinny();
             rc = value_max_device();
-            if (rc == PBVI_OK) rc = out_begin();
-            if (rc == PBVI_OK && out_value) rc = out_add(out_value + r0, bs2_.p, (size_t)cnt * sizeof(double));
-            if (rc == PBVI_OK && out_index) rc = out_add(out_index + r0, bv2_.p, (size_t)cnt * sizeof(int32_t));
-            if (rc == PBVI_OK) rc = out_finish();
+            if (rc == PBVI_OK)
+                rc = out_.deliver({{out_value ? out_value + r0 : nullptr, bs2_.p, (size_t)cnt * sizeof(double)},
+                                   {out_index ? out_index + r0 : nullptr, bv2_.p, (size_t)cnt * sizeof(int32_t)}});
         }
         if (rc != PBVI_OK) (void)hipStreamSynchronize(stream_);
         return rc;

@@ -295,11 +295,9 @@ def mdp_value_iteration(reach_states: np.ndarray, reach_prob: np.ndarray, exp_re
     rows = np.empty((A, S), dtype=np.float64)
     changes = np.zeros(max(int(horizon), 1), dtype=np.float64)
     its = C.c_int32(0)
-    f64p, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-    _check(lib.pbvi_mdp_value_iteration(int(device), S, A, R, rs.ctypes.data_as(i32p), p.ctypes.data_as(f64p),
-                                        er.ctypes.data_as(f64p), v.ctypes.data_as(f64p), float(gamma),
-                                        float(max_change_limit), int(horizon), rows.ctypes.data_as(f64p),
-                                        changes.ctypes.data_as(f64p), C.byref(its)))
+    _check(lib.pbvi_mdp_value_iteration(int(device), S, A, R, _p(rs, C.c_int32), _p(p, C.c_double), _p(er, C.c_double),
+                                        _p(v, C.c_double), float(gamma), float(max_change_limit), int(horizon),
+                                        _p(rows, C.c_double), _p(changes, C.c_double), C.byref(its)))
     return rows, changes[:its.value]
 
 
@@ -318,6 +316,11 @@ def _check(rc: int) -> None:
 
 def _ptr(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def _p(a, ctype):
+    """``a``'s data as a pointer to ``ctype``; ``None`` -- an output that is not wanted -- stays ``None``."""
+    return a.ctypes.data_as(C.POINTER(ctype)) if a is not None else None
 
 
 class HostArena:
@@ -452,7 +455,7 @@ class Engine:
         assert rto_c.shape == (S, A, O, R) and er_c.shape == (S, A)
         self._h = C.c_void_p()
         _check(lib.pbvi_engine_create(C.byref(self._h), device, S, A, O, R,
-                                      rs32.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(rto_c), _ptr(er_c),
+                                      _p(rs32, C.c_int32), _ptr(rto_c), _ptr(er_c),
                                       PBVI_F32 if dtype == 'f32' else PBVI_F64,
                                       PBVI_SPARSE if mode == 'sparse' else PBVI_DENSE))
         self._lib = lib
@@ -474,7 +477,7 @@ class Engine:
             # the belief walk returns fp64 belief values to the host containers: keep them independent of the
             # engine's arithmetic type by giving it the fp64 table too (a few MB)
             r64 = np.ascontiguousarray(rto, dtype=np.float64)
-            self._ck(lib.pbvi_engine_set_rto_f64(self._h, r64.ctypes.data_as(C.POINTER(C.c_double))))
+            self._ck(lib.pbvi_engine_set_rto_f64(self._h, _p(r64, C.c_double)))
 
     @classmethod
     def for_model(cls, model, dtype: str = 'f64', device: int = 0, mode: str = 'sparse') -> 'Engine':
@@ -561,7 +564,7 @@ class Engine:
         """Append rows ``unique_idx`` of the last backup's distinct alpha' rows to the alpha store, device to device
         (``pbvi_backup_store_unique``); returns the store id of the first one."""
         i = np.ascontiguousarray(unique_idx, dtype=np.int32)
-        first = int(self._lib.pbvi_backup_store_unique(self._h, i.ctypes.data_as(C.POINTER(C.c_int32)), i.shape[0]))
+        first = int(self._lib.pbvi_backup_store_unique(self._h, _p(i, C.c_int32), i.shape[0]))
         if first < 0:
             self._ck(first)
         return first
@@ -579,7 +582,7 @@ class Engine:
         if have is not None and have.shape == i.shape and np.array_equal(have, i):
             return
         self._resident['alpha'] = None
-        self._ck(self._lib.pbvi_alpha_select(self._h, i.ctypes.data_as(C.POINTER(C.c_int32)), i.shape[0]))
+        self._ck(self._lib.pbvi_alpha_select(self._h, _p(i, C.c_int32), i.shape[0]))
         self._resident['alpha'] = i.copy()
 
     def select_beliefs(self, ids) -> None:
@@ -588,7 +591,7 @@ class Engine:
         if have is not None and have.shape == i.shape and np.array_equal(have, i):
             return
         self._resident['belief'] = None
-        self._ck(self._lib.pbvi_beliefs_select(self._h, i.ctypes.data_as(C.POINTER(C.c_int32)), i.shape[0]))
+        self._ck(self._lib.pbvi_beliefs_select(self._h, _p(i, C.c_int32), i.shape[0]))
         self.B = i.shape[0]
         self._resident['belief'] = i.copy()
 
@@ -653,8 +656,7 @@ class Engine:
             n = int(self._lib.pbvi_belief_store_count(self._h))
         val = np.empty(n, dtype=np.float64)
         idx = np.empty(n, dtype=np.int32)
-        self._ck(self._lib.pbvi_value_max_store(self._h, n, val.ctypes.data_as(C.POINTER(C.c_double)),
-                                              idx.ctypes.data_as(C.POINTER(C.c_int32))))
+        self._ck(self._lib.pbvi_value_max_store(self._h, n, _p(val, C.c_double), _p(idx, C.c_int32)))
         return val, idx
 
     _STORE_SCAN_MIN = 2048      # beliefs from which scoring the store in place beats gathering a block
@@ -694,7 +696,7 @@ class Engine:
         ``max_value_objects`` will look, so ``compute_change`` does not run that GEMM again.  Returns False when the
         last backup has no such values (alpha-side formulation)."""
         vals = np.empty(self.B, dtype=np.float64)
-        rc = self._lib.pbvi_backup_fetch_value_max(self._h, vals.ctypes.data_as(C.POINTER(C.c_double)))
+        rc = self._lib.pbvi_backup_fetch_value_max(self._h, _p(vals, C.c_double))
         if rc == -4:
             return False
         self._ck(rc)
@@ -807,11 +809,28 @@ class Engine:
         act = np.empty(B, dtype=np.int32)
         best = np.empty((B, self.A, self.O), dtype=np.int32)
         keep = np.empty(B, dtype=np.uint8)
-        i32p = C.POINTER(C.c_int32)
-        self._ck(self._lib.pbvi_backup_fetch_compact(self._h, _ptr(rows), index.ctypes.data_as(i32p), act.ctypes.data_as(i32p),
-                                                   best.ctypes.data_as(i32p), keep.ctypes.data_as(C.POINTER(C.c_uint8))))
+        self._ck(self._lib.pbvi_backup_fetch_compact(self._h, _ptr(rows), _p(index, C.c_int32), _p(act, C.c_int32),
+                                                   _p(best, C.c_int32), _p(keep, C.c_uint8)))
         return BackupResult(rows, index.astype(np.int64), act.astype(np.int64), best.astype(np.int64),
                             keep.astype(bool), {})
+
+    def _out(self, name, a, shape, dtype=None, optional=False, at_least=False) -> None:
+        """Refuse ``a`` as a destination unless it is a C-contiguous array of ``shape`` and ``dtype`` (default: the
+        engine's); ``at_least``: it may have more rows than ``shape[0]``; ``optional``: it may be ``None``."""
+        if a is None and optional:
+            return
+        dt = np.dtype(dtype or self.np_dtype)
+        if (a is None or a.ndim != len(shape) or a.shape[1:] != tuple(shape[1:]) or a.dtype != dt or not a.flags.c_contiguous
+                or (a.shape[0] < shape[0] if at_least else a.shape[0] != shape[0])):
+            want = f"[{'>= ' if at_least else ''}{', '.join(map(str, shape))}] {self.dtype}" if dtype is None else f'{shape} {dt.name}'
+            raise ValueError(f'{name} must be a C-contiguous {want} array')
+
+    def _out_small(self, best=None, keep=None, **per_belief) -> None:
+        """The per-belief destinations of a fetch: the named int32 ``[B]`` arrays, optionally ``best`` and ``keep``."""
+        for name, a in per_belief.items():
+            self._out(name, a, (self.B,), np.int32)
+        self._out('best', best, (self.B, self.A, self.O), np.int32, optional=True)
+        self._out('keep', keep, (self.B,), np.uint8, optional=True)
 
     def fetch_compact_into(self, rows: np.ndarray, index: np.ndarray, actions: np.ndarray, best=None, keep=None) -> int:
         """Results of the last run into caller-owned arrays (``pbvi_backup_fetch_compact``; pinned arrays -- see
@@ -820,17 +839,10 @@ class Engine:
         U = int(self._lib.pbvi_backup_unique_count(self._h))
         if U < 0:
             raise ValueError('no backup result resident')
-        if rows.shape[0] < U or rows.shape[1] != self.S or rows.dtype != self.np_dtype or not rows.flags.c_contiguous:
-            raise ValueError(f'rows must be a C-contiguous [>= {U}, {self.S}] {self.dtype} array')
-        for name, a, shape, dt in (('index', index, (self.B,), np.int32), ('actions', actions, (self.B,), np.int32),
-                                   ('best', best, (self.B, self.A, self.O), np.int32), ('keep', keep, (self.B,), np.uint8)):
-            if a is not None and (a.shape != shape or a.dtype != dt or not a.flags.c_contiguous):
-                raise ValueError(f'{name} must be a C-contiguous {shape} {np.dtype(dt).name} array')
-        i32p = C.POINTER(C.c_int32)
-        self._ck(self._lib.pbvi_backup_fetch_compact(
-            self._h, _ptr(rows), index.ctypes.data_as(i32p), actions.ctypes.data_as(i32p),
-            best.ctypes.data_as(i32p) if best is not None else None,
-            keep.ctypes.data_as(C.POINTER(C.c_uint8)) if keep is not None else None))
+        self._out('rows', rows, (U, self.S), at_least=True)
+        self._out_small(index=index, actions=actions, best=best, keep=keep)
+        self._ck(self._lib.pbvi_backup_fetch_compact(self._h, _ptr(rows), _p(index, C.c_int32), _p(actions, C.c_int32),
+                                                   _p(best, C.c_int32), _p(keep, C.c_uint8)))
         return U
 
     def run_fetch_into(self, gamma: float, rows: np.ndarray, slot: np.ndarray, index: np.ndarray, actions: np.ndarray,
@@ -838,21 +850,14 @@ class Engine:
         """``run`` + ``fetch_compact_into`` in one call with the rows leaving early (``pbvi_backup_run_fetch``): ``rows`` must be
         page-locked (``PinnedBuffer``) with room for B rows; the row of distinct key ``u`` is ``rows[slot[u]]``, and
         ``alpha'[b] == rows[slot[index[b]]]``.  Returns ``(stats, U, slots_used)``."""
-        if rows.shape[0] < self.B or rows.shape[1] != self.S or rows.dtype != self.np_dtype or not rows.flags.c_contiguous:
-            raise ValueError(f'rows must be a C-contiguous [>= {self.B}, {self.S}] {self.dtype} array')
-        for name, a, shape, dt in (('slot', slot, (self.B,), np.int32), ('index', index, (self.B,), np.int32),
-                                   ('actions', actions, (self.B,), np.int32), ('best', best, (self.B, self.A, self.O), np.int32),
-                                   ('keep', keep, (self.B,), np.uint8)):
-            if a is not None and (a.shape != shape or a.dtype != dt or not a.flags.c_contiguous):
-                raise ValueError(f'{name} must be a C-contiguous {shape} {np.dtype(dt).name} array')
-        i32p = C.POINTER(C.c_int32)
+        self._out('rows', rows, (self.B, self.S), at_least=True)
+        self._out_small(slot=slot, index=index, actions=actions, best=best, keep=keep)
         st = PbviStats()
         nu, ns = C.c_int64(0), C.c_int64(0)
         self._ck(self._lib.pbvi_backup_run_fetch(
             self._h, float(gamma), PBVI_BELIEF_DOMINANCE if belief_dominance_prune else 0, C.byref(st), _ptr(rows), rows.shape[0],
-            slot.ctypes.data_as(i32p), index.ctypes.data_as(i32p), actions.ctypes.data_as(i32p),
-            best.ctypes.data_as(i32p) if best is not None else None,
-            keep.ctypes.data_as(C.POINTER(C.c_uint8)) if keep is not None else None, C.byref(nu), C.byref(ns)))
+            _p(slot, C.c_int32), _p(index, C.c_int32), _p(actions, C.c_int32), _p(best, C.c_int32), _p(keep, C.c_uint8),
+            C.byref(nu), C.byref(ns)))
         return st.as_dict(), int(nu.value), int(ns.value)
 
     def fetch_full(self, out=None) -> np.ndarray:
@@ -860,8 +865,7 @@ class Engine:
         C-contiguous [B,S] array of the engine's dtype to fill instead of a new one."""
         if out is None:
             out = np.empty((self.B, self.S), dtype=self.np_dtype)
-        elif out.shape != (self.B, self.S) or out.dtype != self.np_dtype or not out.flags.c_contiguous:
-            raise ValueError(f'out must be a C-contiguous [{self.B}, {self.S}] {self.dtype} array')
+        self._out('out', out, (self.B, self.S))
         self._ck(self._lib.pbvi_backup_fetch(self._h, _ptr(out), None, None, None))
         return out
 
@@ -880,7 +884,7 @@ class Engine:
         U = self.unique_count
         out = np.empty(max(U, 0), dtype=np.uint64)
         if U > 0:
-            self._ck(self._lib.pbvi_backup_fetch_row_hashes(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64))))
+            self._ck(self._lib.pbvi_backup_fetch_row_hashes(self._h, _p(out, C.c_uint64)))
         return out
 
     def fetch_unique_keys(self) -> np.ndarray:
@@ -971,7 +975,7 @@ class Engine:
     def prune_dominated(self, alpha: np.ndarray) -> np.ndarray:
         self._ensure_alpha(alpha)
         keep = np.empty(alpha.shape[0], dtype=np.uint8)
-        self._ck(self._lib.pbvi_prune_dominated(self._h, keep.ctypes.data_as(C.POINTER(C.c_uint8))))
+        self._ck(self._lib.pbvi_prune_dominated(self._h, _p(keep, C.c_uint8)))
         return keep.astype(bool)
 
     def _prune_masked_resident(self, n: int, is_new) -> np.ndarray:
@@ -979,8 +983,7 @@ class Engine:
         if new.shape != (n,):
             raise ValueError(f'is_new must be [{n}]')
         keep = np.empty(n, dtype=np.uint8)
-        u8 = C.POINTER(C.c_uint8)
-        self._ck(self._lib.pbvi_prune_dominated_masked(self._h, new.ctypes.data_as(u8), keep.ctypes.data_as(u8)))
+        self._ck(self._lib.pbvi_prune_dominated_masked(self._h, _p(new, C.c_uint8), _p(keep, C.c_uint8)))
         return keep.astype(bool)
 
     def prune_dominated_masked(self, alpha: np.ndarray, is_new) -> np.ndarray:
@@ -997,7 +1000,7 @@ class Engine:
         if is_new is not None:
             return self._prune_masked_resident(len(objects), is_new)
         keep = np.empty(len(objects), dtype=np.uint8)
-        self._ck(self._lib.pbvi_prune_dominated(self._h, keep.ctypes.data_as(C.POINTER(C.c_uint8))))
+        self._ck(self._lib.pbvi_prune_dominated(self._h, _p(keep, C.c_uint8)))
         return keep.astype(bool)
 
     def max_value(self, alpha: np.ndarray, beliefs: np.ndarray):
@@ -1010,8 +1013,7 @@ class Engine:
         """Same, for the working alpha set / belief block already selected on the device."""
         val = np.empty(self.B, dtype=np.float64)
         idx = np.empty(self.B, dtype=np.int32)
-        self._ck(self._lib.pbvi_value_max(self._h, val.ctypes.data_as(C.POINTER(C.c_double)),
-                                        idx.ctypes.data_as(C.POINTER(C.c_int32))))
+        self._ck(self._lib.pbvi_value_max(self._h, _p(val, C.c_double), _p(idx, C.c_int32)))
         return val, idx.astype(np.int64)
 
     def q_values_resident(self, gamma: float, want_best: bool = False):
@@ -1021,9 +1023,7 @@ class Engine:
         q = np.empty((self.B, self.A), dtype=np.float64)
         act = np.empty(self.B, dtype=np.int32)
         best = np.empty((self.B, self.A, self.O), dtype=np.int32) if want_best else None
-        self._ck(self._lib.pbvi_q_values(self._h, float(gamma), q.ctypes.data_as(C.POINTER(C.c_double)),
-                                       act.ctypes.data_as(C.POINTER(C.c_int32)),
-                                       best.ctypes.data_as(C.POINTER(C.c_int32)) if want_best else None))
+        self._ck(self._lib.pbvi_q_values(self._h, float(gamma), _p(q, C.c_double), _p(act, C.c_int32), _p(best, C.c_int32)))
         if want_best:
             return q, act.astype(np.int64), best.astype(np.int64)
         return q, act.astype(np.int64)
@@ -1033,14 +1033,12 @@ class Engine:
         ``(G [B,A] f64, argmin_a G [B])`` with ``G[b,a] = sum_o P(o|b,a) H(update(b,a,o))`` in nats; ``want_p_obs`` appends
         ``P(o|b,a) [B,A,O]``, ``want_entropy`` the beliefs' own entropies ``[B]``.  Needs no alpha set and leaves the block
         where it is."""
-        f64p = C.POINTER(C.c_double)
         g = np.empty((self.B, self.A), dtype=np.float64)
         act = np.empty(self.B, dtype=np.int32)
         p_obs = np.empty((self.B, self.A, self.O), dtype=np.float64) if want_p_obs else None
         ent = np.empty(self.B, dtype=np.float64) if want_entropy else None
-        self._ck(self._lib.pbvi_infotaxis(self._h, g.ctypes.data_as(f64p), act.ctypes.data_as(C.POINTER(C.c_int32)),
-                                        p_obs.ctypes.data_as(f64p) if want_p_obs else None,
-                                        ent.ctypes.data_as(f64p) if want_entropy else None))
+        self._ck(self._lib.pbvi_infotaxis(self._h, _p(g, C.c_double), _p(act, C.c_int32), _p(p_obs, C.c_double),
+                                        _p(ent, C.c_double)))
         out = (g, act.astype(np.int64))
         if want_p_obs:
             out += (p_obs,)
@@ -1057,8 +1055,7 @@ class Engine:
         if a.shape != (self.B,) or o.shape != (self.B,):
             raise ValueError('actions / observations must be [B]')
         out = np.empty((self.B, self.S), dtype=self.np_dtype)
-        self._ck(self._lib.pbvi_belief_update(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)),
-                                            o.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(out)))
+        self._ck(self._lib.pbvi_belief_update(self._h, _p(a, C.c_int32), _p(o, C.c_int32), _ptr(out)))
         return out
 
     def belief_walk(self, b0: np.ndarray, actions, observations, restart=None):
@@ -1077,11 +1074,10 @@ class Engine:
             r = np.ascontiguousarray(restart, dtype=np.uint8)
             if r.shape != (n,):
                 raise ValueError('restart must be [n]')
-            rp = r.ctypes.data_as(C.POINTER(C.c_uint8))
+            rp = _p(r, C.c_uint8)
         out = self._arena.empty((n, self.S), np.float64)           # kept by the caller as Belief values
-        f64p, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        first = int(self._lib.pbvi_belief_walk(self._h, start.ctypes.data_as(f64p), n, a.ctypes.data_as(i32p),
-                                               o.ctypes.data_as(i32p), rp, out.ctypes.data_as(f64p)))
+        first = int(self._lib.pbvi_belief_walk(self._h, _p(start, C.c_double), n, _p(a, C.c_int32),
+                                               _p(o, C.c_int32), rp, _p(out, C.c_double)))
         if first < 0:
             self._ck(first)
         return out, first
@@ -1090,7 +1086,7 @@ class Engine:
         """``[n]`` uint64: position-weighted bit-pattern hashes of the fp64 rows of the last ``belief_walk`` (what ``_RowKey`` computes on
         the host), from the device."""
         keys = np.empty(n, dtype=np.uint64)
-        self._ck(self._lib.pbvi_belief_walk_keys(self._h, n, keys.ctypes.data_as(C.POINTER(C.c_uint64))))
+        self._ck(self._lib.pbvi_belief_walk_keys(self._h, n, _p(keys, C.c_uint64)))
         return keys
 
     def belief_tag(self):
@@ -1109,11 +1105,10 @@ class Engine:
             k = np.ascontiguousarray(keep, dtype=np.uint8)
             if k.shape != (self.B,):
                 raise ValueError('keep must be [B]')
-            kp = k.ctypes.data_as(C.POINTER(C.c_uint8))
+            kp = _p(k, C.c_uint8)
         nb = C.c_int64(0)
         self._resident['belief'] = None
-        self._ck(self._lib.pbvi_beliefs_advance(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)),
-                                              o.ctypes.data_as(C.POINTER(C.c_int32)), kp, C.byref(nb)))
+        self._ck(self._lib.pbvi_beliefs_advance(self._h, _p(a, C.c_int32), _p(o, C.c_int32), kp, C.byref(nb)))
         self.B = int(nb.value)
         return self.B
 
@@ -1128,7 +1123,7 @@ class Engine:
         aa = np.ascontiguousarray(alpha_actions, dtype=np.int32)
         if aa.shape != (self.alpha_count,):
             raise ValueError('alpha_actions must be [V]')
-        aap = aa.ctypes.data_as(C.POINTER(C.c_int32))
+        aap = _p(aa, C.c_int32)
         return self._rollout_call(lambda ss, em, *tail: self._lib.pbvi_rollout(self._h, aap, int(lookahead), float(gamma), ss, em, *tail),
                                   start_states, end_mask, seed, T, first_sim_id)
 
@@ -1152,10 +1147,9 @@ class Engine:
         else:                                    # the call refuses these: nothing is written
             states = actions = observations = np.empty((0, B), dtype=np.int32)
         out = (states, actions, observations, np.empty(B, dtype=np.int32)) + ((np.empty(B, dtype=np.uint8),) if with_lost else ())
-        i32p, u8p = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
         self._resident['belief'] = None
-        self._ck(call(ss.ctypes.data_as(i32p), em.ctypes.data_as(u8p), int(first_sim_id), int(seed), T,
-                      *[x.ctypes.data_as(u8p if x.dtype == np.uint8 else i32p) for x in out]))
+        self._ck(call(_p(ss, C.c_int32), _p(em, C.c_uint8), int(first_sim_id), int(seed), T,
+                      *[_p(x, C.c_uint8 if x.dtype == np.uint8 else C.c_int32) for x in out]))
         self.B = int(self._lib.pbvi_beliefs_count(self._h))
         return out
 
@@ -1177,8 +1171,7 @@ class Engine:
         if ch.shape != (self.A,):
             raise ValueError('channel_of_action must be [A]')
         self._env_held = None
-        self._ck(self._lib.pbvi_env_set_frames(self._h, fr.ctypes.data_as(C.POINTER(C.c_uint8)), fr.shape[0], fr.shape[1],
-                                               ch.ctypes.data_as(C.POINTER(C.c_int32))))
+        self._ck(self._lib.pbvi_env_set_frames(self._h, _p(fr, C.c_uint8), fr.shape[0], fr.shape[1], _p(ch, C.c_int32)))
 
     def set_environment_table(self, obs_prob) -> None:
         """The observation source of ``rollout_env``: another observation law, ``obs_prob[s', a, :]`` ``[S, A, O]`` fp64
@@ -1187,7 +1180,7 @@ class Engine:
         if tb.shape != (self.S, self.A, self.O):
             raise ValueError(f'obs_prob must be [{self.S}, {self.A}, {self.O}]')
         self._env_held = None
-        self._ck(self._lib.pbvi_env_set_table(self._h, tb.ctypes.data_as(C.POINTER(C.c_double))))
+        self._ck(self._lib.pbvi_env_set_table(self._h, _p(tb, C.c_double)))
 
     def clear_environment(self) -> None:
         """No environment; its device memory is returned (``pbvi_env_clear``)."""
@@ -1226,12 +1219,12 @@ class Engine:
             aa = np.ascontiguousarray(alpha_actions, dtype=np.int32)
             if policy != 2 and aa.shape != (self.alpha_count,):
                 raise ValueError('alpha_actions must be [V]')
-            aap = aa.ctypes.data_as(C.POINTER(C.c_int32))
+            aap = _p(aa, C.c_int32)
         if shifts is not None:
             sh = np.ascontiguousarray(shifts, dtype=np.int64)
             if sh.shape != (self.B,):
                 raise ValueError('shifts must be [B]')
-            shp = sh.ctypes.data_as(C.POINTER(C.c_int64))
+            shp = _p(sh, C.c_int64)
         return self._rollout_call(lambda ss, em, *tail: self._lib.pbvi_rollout_env(self._h, policy, aap, float(gamma), ss, em,
                                                                                    int(end_observation), shp, *tail),
                                   start_states, end_mask, seed, T, first_sim_id, with_lost=True)
