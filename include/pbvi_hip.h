@@ -476,6 +476,62 @@ int pbvi_infotaxis(pbvi_engine_t* e, double* out_g /* [B][A], required */, int32
                    double* out_p_obs /* [B][A][O], may be NULL */, double* out_entropy /* [B], may be NULL */);
 
 /*
+ * HSVI upper bound: the sawtooth interpolation over (belief, value) points above the corner values
+ * (BeliefValueMapping.evaluate, src/pomdp.py:873-895), with the minimum restricted to the support of the point -- the
+ * reference divides over all states and returns NaN (0/0) for every belief that shares a zero with a point, which is every
+ * belief of a sparse model.  Where the reference's expression is finite the two agree.
+ * The point store: one per engine, append-only with a reset, rows kept sparse (CSR: int32 state, fp64 value) in device
+ * memory of the engine (counted against pbvi_debug_alloc_limit, PBVI_ENOMEM as everywhere; released by
+ * pbvi_engine_after_oom, after which the store is empty and no corner is set).
+ *   pbvi_upper_reset   empties the store and sets the corner values c [S] fp64 (finite).
+ *   pbvi_upper_append  n points behind the ones held: points [n][S] fp64 (entries finite and >= 0, not all zero), values [n]
+ *                      = v_i, gaps [n] = gap_i = v_i - p_i . c, computed ONCE by the caller so that host and device hold the
+ *                      same bits.  PBVI_EINVAL: no corner set, NULL, a bad entry, a NaN value or gap.
+ *   pbvi_upper_count   points held (-1: NULL handle).
+ * For a belief row b (an fp32 engine's rows widened to fp64) and points i:
+ *   v0     = sum_s b[s] * c[s]
+ *   r_i    = min over s with p_i[s] > 0 of b[s] / p_i[s]        (IEEE fp64 division; the minimum is exact, so order-free)
+ *   w_i    = v0 + gap_i * r_i                                    (one rounded multiply, one rounded add, never fused)
+ *   U(b)   = min(v0, min_{i < n_visible} w_i);   point = the first i attaining it, -1 when v0 <= every w_i
+ *   hit(b) = the first i < n_hit with p_i[s] == b[s] for every s, else -1   (equality on the support of p_i and
+ *            nnz(b) == nnz(p_i), which together are exact)
+ *   value  = v_hit if hit >= 0 (the reference's dictionary shortcut, :884), else U(b)
+ * A row that holds a NaN gives value NaN, point -1, hit -1.  n_visible <= n_hit <= count restate the reference's stale
+ * cache: its stacked arrays see the points of the last update(), its dictionary every add at once.
+ * v0 is summed in a fixed order that differs from NumPy's; nothing is accumulated with atomics: a belief's results have the
+ * same bits from call to call, whatever other beliefs share the block and wherever the belief stands in it.
+ *
+ * pbvi_upper_bound: the above for every belief of the resident block.  out_value [B] double (required); out_point [B],
+ * out_hit [B] int32 may be NULL.  Host (or device) memory, caller's belief order.
+ *
+ * pbvi_upper_q: the action values the HSVI descent is greedy for (expand_hsvi, src/pomdp.py:1768-1868), over the table the
+ * engine was created with (fp32 values widened; never the pbvi_engine_set_rto_f64 copy):
+ *   u[s']     = pbvi_infotaxis' sum;   Z[a, o] = sum_s' u[s'], the 256-state blocks' sums added in block order (the
+ *               fixed-order normaliser of pbvi_rollout_infotaxis, not the atomic one: the hit test needs successor bits that
+ *               repeat);   b_ao = (T)(u / Z), the successor as pbvi_belief_update rounds it
+ *   Q[b, a]   = sum_s b[s] * ER[s, a] + gamma * sum_o Z[a, o] * value(b_ao)      (sequential over o; Z == 0 adds 0)
+ *   a*[b]     = the first maximum of the row of out_q that is returned; a NaN never wins and a row of NaNs gives 0
+ *   out_q [B][A] double (required); out_action [B] int32, out_p_obs [B][A][O] double ( = Z), out_succ_value [B][A][O] double
+ *   ( = value(b_ao), NaN where Z == 0): may be NULL.  Caller's belief order.
+ * The successors are materialised in chunks of beliefs sized to half the memory the engine may still take (one belief at
+ * the least): (sizeof(double) + sizeof(T)) * S bytes per (belief, action, observation).
+ *
+ * Both calls leave the resident block, the alpha set, both row stores and the backup's stage buffers untouched (an earlier
+ * pbvi_backup_run's results can still be fetched), and work on PBVI_SPARSE and PBVI_DENSE engines and both number formats.
+ * PBVI_EINVAL: a NULL required output, no resident belief block, no corner set, n_visible > n_hit, n_hit > count.
+ * PBVI_EUNSUPPORTED (pbvi_upper_q): A * O > 65535.  PBVI_ENOMEM as everywhere (pbvi_engine_after_oom).
+ */
+int pbvi_upper_reset(pbvi_engine_t* e, const double* corner /* [S] */);
+int pbvi_upper_append(pbvi_engine_t* e, const double* points /* [n][S] */, const double* values /* [n] */,
+                      const double* gaps /* [n] */, int64_t n);
+int64_t pbvi_upper_count(const pbvi_engine_t* e);
+int pbvi_upper_bound(pbvi_engine_t* e, int64_t n_visible, int64_t n_hit, double* out_value /* [B], required */,
+                     int32_t* out_point /* [B], may be NULL */, int32_t* out_hit /* [B], may be NULL */);
+int pbvi_upper_q(pbvi_engine_t* e, double gamma, int64_t n_visible, int64_t n_hit, double* out_q /* [B][A], required */,
+                 int32_t* out_action /* [B], may be NULL */, double* out_p_obs /* [B][A][O], may be NULL */,
+                 double* out_succ_value /* [B][A][O], may be NULL */);
+
+/*
  * Device-resident infotaxis rollout: pbvi_rollout with the action of every step taken from pbvi_infotaxis' a*[b] instead of
  * the alpha set -- a = the first argmin_a G(b, a) of the simulation's current belief.  Everything else is pbvi_rollout's:
  * the uniform u(i, t) = uniform01(splitmix64(seed, i), t) of simulation i = first_sim_id + b, the (o, s') draw from

@@ -26,6 +26,7 @@
 
 #include "backup_kernels.h"
 #include "split_bf16.h"
+#include "upper_kernels.h"
 
 namespace pbvi {
 
@@ -1062,6 +1063,13 @@ class EngineBase {
                                         int32_t* best_v, double* best_score, int32_t* queue, uint8_t* dead, int32_t* perm) = 0;
     virtual int rollout(const RolloutCall& call) = 0;
     virtual int infotaxis(double* out_g, int32_t* out_action, double* out_p_obs, double* out_entropy) = 0;
+    // the HSVI upper bound: the device point store, its sawtooth on the resident block, the bound-greedy action values
+    virtual int upper_reset(const double* corner) = 0;
+    virtual int upper_append(const double* points, const double* values, const double* gaps, int64_t n) = 0;
+    virtual int64_t upper_count() const = 0;
+    virtual int upper_bound(int64_t n_visible, int64_t n_hit, double* out_value, int32_t* out_point, int32_t* out_hit) = 0;
+    virtual int upper_q(double gamma, int64_t n_visible, int64_t n_hit, double* out_q, int32_t* out_action, double* out_p_obs,
+                        double* out_succ_value) = 0;
     // the observation source of rollout_env: recorded frames or another observation law (setting one replaces the other)
     virtual int env_set_frames(const uint8_t* frames, int64_t F, int64_t C, const int32_t* channel_of_action) = 0;
     virtual int env_set_table(const double* obs_prob) = 0;
@@ -1178,6 +1186,17 @@ class EngineT : public EngineBase {
     // and the beliefs' own entropies [B], all four in the caller's belief order
     DevBuf it_part_{mem_}, it_g_{mem_}, it_act_{mem_}, it_pobs_{mem_}, it_h_{mem_};
     DevBuf bu_mpart_{mem_};   // bayes_push(fixed_order): the push blocks' partial masses [B][ceil(S/256)]
+    // pbvi_upper_*: the point store of the HSVI upper bound -- CSR rows (ub_ptr_ int64 [P+1], ub_idx_ int32 / ub_val_ fp64 [entries]),
+    // per point its entries, value and gap (ub_nnz_ int32, ub_v_ / ub_gap_ fp64 [P]), the corner values ub_c_ fp64 [S].  Working
+    // buffers: after_oom() releases them and the store is empty with no corner set.
+    DevBuf ub_ptr_{mem_}, ub_idx_{mem_}, ub_val_{mem_}, ub_nnz_{mem_}, ub_v_{mem_}, ub_gap_{mem_}, ub_c_{mem_};
+    int64_t ub_count_ = 0, ub_entries_ = 0;
+    bool ub_corner_ = false;
+    // one sawtooth evaluation's scratch (UpperScratch) and pbvi_upper_bound's results [B], caller order
+    DevBuf ub_v0_{mem_}, ub_bnnz_{mem_}, ub_pw_{mem_}, ub_pi_{mem_}, ub_ph_{mem_}, ub_rv_{mem_}, ub_rp_{mem_}, ub_rh_{mem_};
+    // pbvi_upper_q: a chunk's un-normalised successors, block masses and successors; every successor's mass and value
+    // [B][A][O], engine order; the results Q [B][A], its first argmax [B], p_obs and successor values [B][A][O], caller order
+    DevBuf uq_unnorm_{mem_}, uq_mpart_{mem_}, uq_succ_{mem_}, uq_mass_{mem_}, uq_val_{mem_}, uq_q_{mem_}, uq_act_{mem_}, uq_pobs_{mem_}, uq_sval_{mem_};
     // pbvi_env_set_*: the observation source of pbvi_rollout_env.  Frames: env_frames_ uint8 [F][C][S] + env_chan_ int32 [A];
     // table: env_table_ fp64 [S][A][O].  Working buffers: after_oom() releases them and the engine has no environment again.
     enum EnvKind { ENV_NONE = 0, ENV_FRAMES = 1, ENV_TABLE = 2 };
@@ -1874,6 +1893,168 @@ class EngineT : public EngineBase {
                              {out_entropy, it_h_.p, (size_t)B_ * sizeof(double)}});
     }
 
+    // ---- HSVI upper bound (pbvi_upper_reset / _append / _count / _bound / _q) ---- //
+    int upper_reset(const double* corner) override {
+        if (!corner) FAIL(PBVI_EINVAL, "upper_reset: NULL corner values");
+        for (int s = 0; s < S_; ++s)
+            if (!std::isfinite(corner[s])) FAIL(PBVI_EINVAL, "upper_reset: corner value " + std::to_string(s) + " is not finite");
+        HIPCHK(hipSetDevice(device_));
+        ub_count_ = ub_entries_ = 0;
+        ub_corner_ = false;
+        int rc = ub_c_.ensure((size_t)S_ * sizeof(double));
+        if (rc) return rc;
+        HIPCHK(hipMemcpy(ub_c_.p, corner, (size_t)S_ * sizeof(double), hipMemcpyHostToDevice));
+        ub_corner_ = true;
+        return PBVI_OK;
+    }
+
+    int64_t upper_count() const override { return ub_count_; }
+
+    // n points behind the store's: their non-zeros in ascending state order, found on the host (a point is a belief: every
+    // entry finite and >= 0, at least one > 0)
+    int upper_append(const double* points, const double* values, const double* gaps, int64_t n) override {
+        if (!ub_corner_) FAIL(PBVI_EINVAL, "upper_append: no corner values set (call pbvi_upper_reset)");
+        if (n < 0 || (n > 0 && (!points || !values || !gaps))) FAIL(PBVI_EINVAL, "upper_append: NULL argument");
+        if (n == 0) return PBVI_OK;
+        if (ub_count_ + n > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "upper_append: more than 2^31 - 1 points");
+        std::vector<int64_t> ptr((size_t)n + 1);
+        std::vector<int32_t> idx, nnz((size_t)n);
+        std::vector<double> val;
+        ptr[0] = ub_entries_;
+        for (int64_t i = 0; i < n; ++i) {
+            const double* row = points + (size_t)i * S_;
+            int32_t cnt = 0;
+            for (int s = 0; s < S_; ++s) {
+                const double x = row[s];
+                if (!(x >= 0.0) || !std::isfinite(x))
+                    FAIL(PBVI_EINVAL, "upper_append: point " + std::to_string(i) + " has a negative or non-finite entry at state " +
+                                          std::to_string(s));
+                if (x > 0.0) {
+                    idx.push_back(s);
+                    val.push_back(x);
+                    ++cnt;
+                }
+            }
+            if (cnt == 0) FAIL(PBVI_EINVAL, "upper_append: point " + std::to_string(i) + " is all zeros");
+            if (std::isnan(values[i]) || std::isnan(gaps[i])) FAIL(PBVI_EINVAL, "upper_append: NaN value or gap");
+            nnz[(size_t)i] = cnt;
+            ptr[(size_t)i + 1] = ptr[(size_t)i] + cnt;
+        }
+        HIPCHK(hipSetDevice(device_));
+        const size_t P = (size_t)ub_count_, E = (size_t)ub_entries_, ne = idx.size(), un = (size_t)n;
+        int rc;
+        if ((rc = grow_keep(ub_ptr_, (P + un + 1) * sizeof(int64_t), P ? (P + 1) * sizeof(int64_t) : 0))) return rc;
+        if ((rc = grow_keep(ub_idx_, (E + ne) * sizeof(int32_t), E * sizeof(int32_t)))) return rc;
+        if ((rc = grow_keep(ub_val_, (E + ne) * sizeof(double), E * sizeof(double)))) return rc;
+        if ((rc = grow_keep(ub_nnz_, (P + un) * sizeof(int32_t), P * sizeof(int32_t)))) return rc;
+        if ((rc = grow_keep(ub_v_, (P + un) * sizeof(double), P * sizeof(double)))) return rc;
+        if ((rc = grow_keep(ub_gap_, (P + un) * sizeof(double), P * sizeof(double)))) return rc;
+        HIPCHK(hipStreamSynchronize(stream_));               // (no earlier kernel still reads the store)
+        HIPCHK(hipMemcpy(ub_ptr_.as<int64_t>() + P, ptr.data(), (un + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(ub_idx_.as<int32_t>() + E, idx.data(), ne * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(ub_val_.as<double>() + E, val.data(), ne * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(ub_nnz_.as<int32_t>() + P, nnz.data(), un * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(ub_v_.as<double>() + P, values, un * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(ub_gap_.as<double>() + P, gaps, un * sizeof(double), hipMemcpyHostToDevice));
+        ub_count_ += n;
+        ub_entries_ += (int64_t)ne;
+        return PBVI_OK;
+    }
+
+    UpperStore upper_store() const {
+        return UpperStore{ub_ptr_.as<int64_t>(), ub_idx_.as<int32_t>(), ub_val_.as<double>(), ub_nnz_.as<int32_t>(),
+                          ub_v_.as<double>(), ub_gap_.as<double>(), ub_c_.as<double>()};
+    }
+
+    // What pbvi_upper_bound and pbvi_upper_q refuse, in this order
+    int upper_begin(const std::string& who, int64_t n_visible, int64_t n_hit, bool null_output) {
+        if (null_output) FAIL(PBVI_EINVAL, who + ": NULL required output");
+        if (B_ <= 0) FAIL(PBVI_EINVAL, who + ": no belief block resident (call pbvi_beliefs_set)");
+        if (!ub_corner_) FAIL(PBVI_EINVAL, who + ": no corner values set (call pbvi_upper_reset)");
+        if (n_visible < 0 || n_visible > n_hit) FAIL(PBVI_EINVAL, who + ": need 0 <= n_visible <= n_hit");
+        if (n_hit > ub_count_) FAIL(PBVI_EINVAL, who + ": n_hit exceeds the points in the store");
+        HIPCHK(hipSetDevice(device_));
+        return PBVI_OK;
+    }
+
+    // The scratch of a sawtooth evaluation of `rows` rows against n_hit points
+    int upper_scratch(int64_t rows, int64_t n_hit, UpperScratch* ws) {
+        const size_t cells = (size_t)rows * (size_t)std::max(1, upper_chunks(n_hit));
+        int rc;
+        if ((rc = ub_v0_.ensure((size_t)rows * sizeof(double)))) return rc;
+        if ((rc = ub_bnnz_.ensure((size_t)rows * sizeof(int32_t)))) return rc;
+        if ((rc = ub_pw_.ensure(cells * sizeof(double)))) return rc;
+        if ((rc = ub_pi_.ensure(cells * sizeof(int32_t)))) return rc;
+        if ((rc = ub_ph_.ensure(cells * sizeof(int32_t)))) return rc;
+        *ws = UpperScratch{ub_v0_.as<double>(), ub_bnnz_.as<int32_t>(), ub_pw_.as<double>(), ub_pi_.as<int32_t>(), ub_ph_.as<int32_t>()};
+        return PBVI_OK;
+    }
+
+    // The sawtooth of the resident block (pbvi_upper_bound).  Reads the block and the point store only.
+    int upper_bound(int64_t n_visible, int64_t n_hit, double* out_value, int32_t* out_point, int32_t* out_hit) override {
+        int rc = upper_begin("upper_bound", n_visible, n_hit, !out_value);
+        if (rc) return rc;
+        UpperScratch ws{};
+        if ((rc = upper_scratch(B_, n_hit, &ws))) return rc;
+        if ((rc = ub_rv_.ensure((size_t)B_ * sizeof(double)))) return rc;
+        if ((rc = ub_rp_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+        if ((rc = ub_rh_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+        HIPCHK(launch_upper_sawtooth<T>(bel_.as<T>(), S_pad_, (int)B_, S_, sorted_ ? perm_.as<int32_t>() : nullptr, upper_store(),
+                                        n_visible, n_hit, ws, ub_rv_.as<double>(), ub_rp_.as<int32_t>(), ub_rh_.as<int32_t>(),
+                                        stream_));
+        return out_.deliver({{out_value, ub_rv_.p, (size_t)B_ * sizeof(double)},
+                             {out_point, ub_rp_.p, (size_t)B_ * sizeof(int32_t)},
+                             {out_hit, ub_rh_.p, (size_t)B_ * sizeof(int32_t)}});
+    }
+
+    // The bound-greedy action values of the resident block (pbvi_upper_q): the normalised successors of every (belief, action,
+    // observation) are materialised as many beliefs at a time as half the memory still at hand holds (at least one), valued by
+    // the sawtooth kernels, and folded into Q per belief.  Reads the block, the model tables and the point store only.
+    int upper_q(double gamma, int64_t n_visible, int64_t n_hit, double* out_q, int32_t* out_action, double* out_p_obs,
+                double* out_succ_value) override {
+        int rc = upper_begin("upper_q", n_visible, n_hit, !out_q);
+        if (rc) return rc;
+        const int64_t AO = (int64_t)A_ * O_;
+        if ((int64_t)S_ * R_ > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "upper_q: S*R exceeds int32");
+        if (AO > 65535) FAIL(PBVI_EUNSUPPORTED, "upper_q: A*O exceeds 65535");
+        if ((rc = build_inverse_lists())) return rc;
+        const size_t all = (size_t)B_ * (size_t)AO;
+        if ((rc = uq_mass_.ensure(all * sizeof(double)))) return rc;
+        if ((rc = uq_val_.ensure(all * sizeof(double)))) return rc;
+        if ((rc = uq_q_.ensure((size_t)B_ * A_ * sizeof(double)))) return rc;
+        if ((rc = uq_act_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+        if (out_p_obs && (rc = uq_pobs_.ensure(all * sizeof(double)))) return rc;
+        if (out_succ_value && (rc = uq_sval_.ensure(all * sizeof(double)))) return rc;
+        // bytes one belief's successors take: un-normalised and normalised rows, block masses, the sawtooth's scratch
+        const int64_t nblk = (S_ + 255) / 256, chunks = std::max(1, upper_chunks(n_hit));
+        const int64_t per_belief = AO * ((int64_t)S_ * (int64_t)(sizeof(double) + sizeof(T)) + nblk * 8 + 12 + chunks * 16);
+        const int64_t held = (int64_t)(uq_unnorm_.cap + uq_succ_.cap + uq_mpart_.cap + ub_v0_.cap + ub_bnnz_.cap + ub_pw_.cap +
+                                       ub_pi_.cap + ub_ph_.cap);
+        const int64_t nb = std::max<int64_t>(1, std::min({B_, (int64_t)65535 / AO, (room() / 2 + held) / per_belief}));
+        const size_t rows = (size_t)nb * (size_t)AO;
+        if ((rc = uq_unnorm_.ensure(rows * S_ * sizeof(double)))) return rc;
+        if ((rc = uq_succ_.ensure(rows * S_ * sizeof(T)))) return rc;
+        if ((rc = uq_mpart_.ensure(rows * (size_t)nblk * sizeof(double)))) return rc;
+        UpperScratch ws{};
+        if ((rc = upper_scratch((int64_t)rows, n_hit, &ws))) return rc;
+        for (int64_t b0 = 0; b0 < B_; b0 += nb) {
+            const int cnt = (int)std::min(nb, B_ - b0);
+            double* mass = uq_mass_.as<double>() + b0 * AO;
+            HIPCHK(launch_upper_successors<T>(bel_.as<T>(), S_pad_, (int)b0, cnt, view(), in_ptr_.as<int32_t>(), in_src_.as<int32_t>(),
+                                              uq_unnorm_.as<double>(), uq_mpart_.as<double>(), mass, uq_succ_.as<T>(), stream_));
+            HIPCHK(launch_upper_sawtooth<T>(uq_succ_.as<T>(), S_, (int)(cnt * AO), S_, nullptr, upper_store(), n_visible, n_hit, ws,
+                                            uq_val_.as<double>() + b0 * AO, nullptr, nullptr, stream_));
+        }
+        HIPCHK(launch_upper_q_finish<T>(bel_.as<T>(), S_pad_, (int)B_, view(), sorted_ ? perm_.as<int32_t>() : nullptr, gamma,
+                                        uq_mass_.as<double>(), uq_val_.as<double>(), uq_q_.as<double>(), uq_act_.as<int32_t>(),
+                                        out_p_obs ? uq_pobs_.as<double>() : nullptr, out_succ_value ? uq_sval_.as<double>() : nullptr,
+                                        stream_));
+        return out_.deliver({{out_q, uq_q_.p, (size_t)B_ * A_ * sizeof(double)},
+                             {out_action, uq_act_.p, (size_t)B_ * sizeof(int32_t)},
+                             {out_p_obs, uq_pobs_.p, all * sizeof(double)},
+                             {out_succ_value, uq_sval_.p, all * sizeof(double)}});
+    }
+
     // ---- environments (pbvi_env_set_frames / pbvi_env_set_table / pbvi_env_clear) ---- //
     int env_clear() override {
         HIPCHK(hipSetDevice(device_));
@@ -2493,6 +2674,8 @@ class EngineT : public EngineBase {
         alpha_ = DevView{};                                  // (it pointed into alpha_buf_ / alpha_small_)
         env_kind_ = ENV_NONE;                                // (its buffers were working buffers)
         env_F_ = env_C_ = 0;
+        ub_count_ = ub_entries_ = 0;                         // (so were the point store's)
+        ub_corner_ = false;
         V_ = 0;
         block_emptied();
         prim_valid_ = alpha_on_primary_ = false;
@@ -5028,6 +5211,24 @@ int pbvi_rollout(pbvi_engine_t* e, const int32_t* alpha_actions, int lookahead, 
 int pbvi_infotaxis(pbvi_engine_t* e, double* out_g, int32_t* out_action, double* out_p_obs, double* out_entropy) {
     NEED(e);
     return e->impl->infotaxis(out_g, out_action, out_p_obs, out_entropy);
+}
+int pbvi_upper_reset(pbvi_engine_t* e, const double* corner) {
+    NEED(e);
+    return e->impl->upper_reset(corner);
+}
+int pbvi_upper_append(pbvi_engine_t* e, const double* points, const double* values, const double* gaps, int64_t n) {
+    NEED(e);
+    return e->impl->upper_append(points, values, gaps, n);
+}
+int64_t pbvi_upper_count(const pbvi_engine_t* e) { return (e && e->impl) ? e->impl->upper_count() : -1; }
+int pbvi_upper_bound(pbvi_engine_t* e, int64_t n_visible, int64_t n_hit, double* out_value, int32_t* out_point, int32_t* out_hit) {
+    NEED(e);
+    return e->impl->upper_bound(n_visible, n_hit, out_value, out_point, out_hit);
+}
+int pbvi_upper_q(pbvi_engine_t* e, double gamma, int64_t n_visible, int64_t n_hit, double* out_q, int32_t* out_action,
+                 double* out_p_obs, double* out_succ_value) {
+    NEED(e);
+    return e->impl->upper_q(gamma, n_visible, n_hit, out_q, out_action, out_p_obs, out_succ_value);
 }
 int pbvi_rollout_infotaxis(pbvi_engine_t* e, const int32_t* start_states, const uint8_t* end_mask, uint64_t first_sim_id,
                            uint64_t seed, int64_t T, int32_t* out_states, int32_t* out_actions, int32_t* out_observations,

@@ -38,6 +38,7 @@ EXPORTS = [
     'pbvi_rollout', 'pbvi_infotaxis', 'pbvi_rollout_infotaxis', 'pbvi_debug_split_schedule', 'pbvi_debug_slabs',
     'pbvi_debug_slabs_fill', 'pbvi_env_set_frames', 'pbvi_env_set_table', 'pbvi_env_clear', 'pbvi_rollout_env',
     'pbvi_debug_score_probe', 'pbvi_debug_score_probe_fetch', 'pbvi_debug_refine_counts', 'pbvi_debug_value_max_route',
+    'pbvi_upper_reset', 'pbvi_upper_append', 'pbvi_upper_count', 'pbvi_upper_bound', 'pbvi_upper_q',
 ]
 
 
@@ -131,6 +132,11 @@ def load_library(path: str = LIB_PATH):
                                    i32p, i32p, i32p, i32p]),
         'pbvi_infotaxis': (C.c_int, [vp, f64p, i32p, f64p, f64p]),
         'pbvi_rollout_infotaxis': (C.c_int, [vp, i32p, u8p, C.c_uint64, C.c_uint64, C.c_int64, i32p, i32p, i32p, i32p]),
+        'pbvi_upper_reset': (C.c_int, [vp, f64p]),
+        'pbvi_upper_append': (C.c_int, [vp, f64p, f64p, f64p, C.c_int64]),
+        'pbvi_upper_count': (C.c_int64, [vp]),
+        'pbvi_upper_bound': (C.c_int, [vp, C.c_int64, C.c_int64, f64p, i32p, i32p]),
+        'pbvi_upper_q': (C.c_int, [vp, C.c_double, C.c_int64, C.c_int64, f64p, i32p, f64p, f64p]),
         'pbvi_env_set_frames': (C.c_int, [vp, u8p, C.c_int64, C.c_int64, i32p]),
         'pbvi_env_set_table': (C.c_int, [vp, f64p]),
         'pbvi_env_clear': (C.c_int, [vp]),
@@ -470,6 +476,7 @@ class Engine:
         self._store_epoch = {'alpha': 0, 'belief': 0}
         self._resident = {'alpha': None, 'belief': None}     # store ids of the working alpha set / belief block
         self._env_held = None                   # hold_environment: (array, channel map) that are the engine's environment
+        self.upper_epoch = 0                    # bumped whenever the point store is emptied (upper_reset, after_oom)
         self.B = 0
         self._vmax_cache, self._vmax_epochs = [], None
         self._arena = HostArena(first_block_bytes=128 * self.S * 8)
@@ -515,6 +522,7 @@ class Engine:
         self._lib.pbvi_engine_after_oom(self._h)
         self._resident = {'alpha': None, 'belief': None}
         self._env_held = None
+        self.upper_epoch += 1                        # the point store of the upper bound is empty, no corner set
         for k in self._store_epoch:                  # residency tags of AlphaVector / Belief objects no longer match
             self._store_epoch[k] += 1
         self._vmax_cache, self._vmax_epochs = [], None
@@ -1044,6 +1052,68 @@ class Engine:
             out += (p_obs,)
         if want_entropy:
             out += (ent,)
+        return out
+
+    # -- HSVI upper bound: device point store, sawtooth, bound-greedy action values -------------------------------- #
+    def upper_reset(self, corner) -> None:
+        """Empty the point store of the upper bound and set the corner values ``c [S]`` (``pbvi_upper_reset``)."""
+        c = np.ascontiguousarray(corner, dtype=np.float64)
+        if c.shape != (self.S,):
+            raise ValueError(f'corner values must be [{self.S}]')
+        self.upper_epoch += 1
+        self._ck(self._lib.pbvi_upper_reset(self._h, _p(c, C.c_double)))
+
+    def upper_append(self, points, values, gaps) -> int:
+        """``n`` points behind the ones the store holds (``pbvi_upper_append``): ``points [n,S]`` fp64, ``values [n]``,
+        ``gaps [n] = values - points @ corner`` computed by the caller (host and device then hold the same bits).  Returns
+        the number of points held."""
+        p = np.ascontiguousarray(points, dtype=np.float64)
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        g = np.ascontiguousarray(gaps, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != self.S or v.shape != (p.shape[0],) or g.shape != (p.shape[0],):
+            raise ValueError(f'expected points [n, {self.S}], values [n], gaps [n]')
+        self._ck(self._lib.pbvi_upper_append(self._h, _p(p, C.c_double), _p(v, C.c_double), _p(g, C.c_double), p.shape[0]))
+        return self.upper_count
+
+    @property
+    def upper_count(self) -> int:
+        return int(self._lib.pbvi_upper_count(self._h))
+
+    def _upper_window(self, n_visible, n_hit):
+        n_hit = self.upper_count if n_hit is None else int(n_hit)
+        return (n_hit if n_visible is None else int(n_visible)), n_hit
+
+    def upper_bound_resident(self, n_visible=None, n_hit=None):
+        """Support-restricted sawtooth of the resident belief block over the point store (``pbvi_upper_bound``):
+        ``(value [B] f64, point [B], hit [B])`` -- ``point`` the first point attaining the minimum (-1: the corner
+        interpolation), ``hit`` the first of the first ``n_hit`` points equal to the belief (-1: none; its value is returned
+        when there is one).  Only the first ``n_visible`` points lower the bound; both default to every point held."""
+        n_visible, n_hit = self._upper_window(n_visible, n_hit)
+        val = np.empty(self.B, dtype=np.float64)
+        point = np.empty(self.B, dtype=np.int32)
+        hit = np.empty(self.B, dtype=np.int32)
+        self._ck(self._lib.pbvi_upper_bound(self._h, n_visible, n_hit, _p(val, C.c_double), _p(point, C.c_int32),
+                                            _p(hit, C.c_int32)))
+        return val, point.astype(np.int64), hit.astype(np.int64)
+
+    def upper_q_resident(self, gamma: float, n_visible=None, n_hit=None, want_p_obs: bool = False,
+                         want_succ_value: bool = False):
+        """Action values the HSVI descent is greedy for (``pbvi_upper_q``): ``(Q [B,A] f64, argmax_a Q [B])`` with
+        ``Q[b,a] = b.ER[:,a] + gamma * sum_o P(o|b,a) * value(update(b,a,o))``, ``value`` the sawtooth of
+        ``upper_bound_resident``; ``want_p_obs`` appends ``P(o|b,a) [B,A,O]``, ``want_succ_value`` the successors' values
+        ``[B,A,O]`` (NaN at impossible observations, which add 0)."""
+        n_visible, n_hit = self._upper_window(n_visible, n_hit)
+        q = np.empty((self.B, self.A), dtype=np.float64)
+        act = np.empty(self.B, dtype=np.int32)
+        p_obs = np.empty((self.B, self.A, self.O), dtype=np.float64) if want_p_obs else None
+        sval = np.empty((self.B, self.A, self.O), dtype=np.float64) if want_succ_value else None
+        self._ck(self._lib.pbvi_upper_q(self._h, float(gamma), n_visible, n_hit, _p(q, C.c_double), _p(act, C.c_int32),
+                                        _p(p_obs, C.c_double), _p(sval, C.c_double)))
+        out = (q, act.astype(np.int64))
+        if want_p_obs:
+            out += (p_obs,)
+        if want_succ_value:
+            out += (sval,)
         return out
 
     def belief_update(self, beliefs: np.ndarray, actions, observations) -> np.ndarray:

@@ -253,31 +253,198 @@ class BeliefSet:
         return BeliefSet(cm, [Belief(cm, b.values) for b in self.belief_list])
 
 
+# --------------------------------------------------------------------------- #
+# HSVI upper bound: the support-restricted sawtooth and the bound-greedy action values (what ``pbvi_upper_bound`` and
+# ``pbvi_upper_q`` compute on the device)
+# --------------------------------------------------------------------------- #
+def sawtooth_numpy(points, values, gaps, corner, beliefs, n_visible: Union[int, None] = None, n_hit: Union[int, None] = None):
+    """Sawtooth upper bound of every row of ``beliefs [n,S]`` over the points ``points [P,S]`` with values ``values [P]`` and
+    gaps ``gaps [P]`` (``= values - points @ corner``, computed once by the caller) above the corner values ``corner [S]``,
+    on the host: what ``pbvi_upper_bound`` computes on the device.
+
+        ``v0 = b . corner;  r_i = min_{s: p_i[s] > 0} b[s] / p_i[s];  w_i = v0 + gap_i * r_i``
+        ``U = min(v0, min_{i < n_visible} w_i);  point`` = the first ``i`` attaining it, -1 when ``v0 <= `` every ``w_i``
+        ``hit`` = the first ``i < n_hit`` with ``p_i == b``, else -1;  ``value = values[hit] if hit >= 0 else U``
+
+    The minimum runs over the SUPPORT of the point: ``BeliefValueMapping.evaluate``'s reference form divides over all states
+    and is NaN (0/0) wherever belief and point share a zero; where that form is finite the two agree.  ``n_visible <= n_hit
+    <= P`` (defaults: all) restate the reference's stale cache.  A row that holds a NaN gives NaN, -1, -1.
+    Returns ``(value [n] f64, point [n], hit [n])``."""
+    c = np.asarray(corner, dtype=np.float64)
+    S = c.shape[0]
+    p = np.asarray(points, dtype=np.float64).reshape(-1, S)
+    v = np.asarray(values, dtype=np.float64).reshape(-1)
+    g = np.asarray(gaps, dtype=np.float64).reshape(-1)
+    b = np.asarray(beliefs, dtype=np.float64)
+    if b.ndim != 2 or b.shape[1] != S:
+        raise ValueError(f'beliefs must be a [*, {S}] array')
+    P = p.shape[0]
+    n_hit = P if n_hit is None else int(n_hit)
+    n_visible = n_hit if n_visible is None else int(n_visible)
+    if not 0 <= n_visible <= n_hit <= P or v.shape[0] < n_hit or g.shape[0] < n_hit:
+        raise ValueError('need 0 <= n_visible <= n_hit <= P points, each with a value and a gap')
+    n = b.shape[0]
+    v0 = np.dot(b, c)
+    value = v0.copy()
+    point = np.full(n, -1, dtype=np.int64)
+    hit = np.full(n, -1, dtype=np.int64)
+    nnz_b = np.count_nonzero(b, axis=1)
+    with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        for i in range(n_hit):
+            s = np.flatnonzero(p[i] > 0)
+            cols = b[:, s]
+            if i < n_visible:
+                r = np.min(cols / p[i, s], axis=1) if s.size else np.full(n, np.inf)
+                w = v0 + g[i] * r
+                better = w < value                              # strictly: the first point attaining the minimum keeps it
+                value[better] = w[better]
+                point[better] = i
+            same = (hit < 0) & (nnz_b == s.size) & np.all(cols == p[i, s], axis=1)
+            hit[same] = i
+    bad = np.isnan(b).any(axis=1)
+    value = np.where(hit >= 0, v[np.maximum(hit, 0)] if P else value, value)
+    value[bad] = np.nan
+    point[bad] = -1
+    hit[bad] = -1
+    return value, point, hit
+
+
+def upper_q_first_argmax(Q: np.ndarray) -> np.ndarray:
+    """The first action whose ``Q`` is strictly larger than every earlier one; a NaN never wins, a row of NaNs gives 0."""
+    return np.argmax(np.where(np.isnan(Q), -np.inf, Q), axis=1)
+
+
+def upper_q_numpy(model, points, values, gaps, corner, beliefs, gamma: float, n_visible: Union[int, None] = None,
+                  n_hit: Union[int, None] = None, table_dtype=np.float64):
+    """The action values the HSVI descent is greedy for, on the host: what ``pbvi_upper_q`` computes on the device.  With
+    ``u`` and ``Z = sum_s' u`` as in ``infotaxis_numpy`` (tables cast to ``table_dtype``, the engine's number format, and
+    widened) and ``b_ao = (u / Z)`` rounded to ``table_dtype``, the successor as the engine holds it:
+
+        ``Q[b,a] = b . ER[:,a] + gamma * sum_o Z[a,o] * value(b_ao)``   (sequential over ``o``; ``Z == 0`` adds 0)
+
+    ``value`` is ``sawtooth_numpy``'s.  Returns ``(Q [n,A], action [n], p_obs [n,A,O], succ_value [n,A,O], succ_hit
+    [n,A,O])``: ``action`` is ``upper_q_first_argmax(Q)``, ``p_obs`` is ``Z``; at an impossible observation the successor's
+    value is NaN and its hit -1."""
+    m = _rollout_tables(model)
+    S, A, O, R = m.state_count, m.action_count, m.observation_count, m.reachable_state_count
+    b = np.asarray(beliefs, dtype=np.float64)
+    if b.ndim != 2 or b.shape[1] != S:
+        raise ValueError(f'beliefs must be a [*, {S}] array')
+    n = b.shape[0]
+    rto = np.ascontiguousarray(m.reachable_transitional_observation_table, dtype=table_dtype).astype(np.float64)
+    er = np.ascontiguousarray(m.expected_rewards_table, dtype=table_dtype).astype(np.float64)
+    rs = np.asarray(m.reachable_states).astype(np.int64)
+    Q = np.dot(b, er)
+    Z = np.zeros((n, A, O))
+    sval = np.full((n, A, O), np.nan)
+    shit = np.full((n, A, O), -1, dtype=np.int64)
+    base = np.arange(n)[:, None] * S
+    for a in range(A):
+        idx = (rs[:, a, :].reshape(1, S * R) + base).ravel()                     # entry s * R + r lands on rs[s, a, r]
+        tail = np.zeros(n)
+        for o in range(O):
+            w = (b[:, :, None] * rto[None, :, a, o, :]).reshape(n, S * R)
+            u = np.bincount(idx, weights=w.ravel(), minlength=n * S).reshape(n, S)
+            z = np.sum(u, axis=1)
+            Z[:, a, o] = z
+            ok = z != 0
+            if ok.any():
+                succ = (u[ok] / z[ok, None]).astype(table_dtype).astype(np.float64)
+                sval[ok, a, o], _, shit[ok, a, o] = sawtooth_numpy(points, values, gaps, corner, succ, n_visible, n_hit)
+                tail[ok] += z[ok] * sval[ok, a, o]
+        Q[:, a] += gamma * tail
+    return Q, upper_q_first_argmax(Q), Z, sval, shit
+
+
 class BeliefValueMapping:
     """Upper bound of the value function as (belief, value) points over the corner values, evaluated with the
-    sawtooth interpolation (``src/pomdp.py:786-895``; used by the HSVI expansion only).  Host-side: the points
-    are a few hundred rows at most."""
+    sawtooth interpolation (``src/pomdp.py:786-895``; used by the HSVI expansion only).
 
-    def __init__(self, model, corner_belief_values: ValueFunction) -> None:
+    ``sawtooth='reference'`` (the default) is the reference bit for bit, host-side: its minimum over ALL states is NaN (0/0)
+    for every belief that shares a zero with a point.  ``sawtooth='support'`` restricts the minimum to the support of the
+    point (``sawtooth_numpy``), adds ``evaluate_block`` for many beliefs at once, and can keep its points in an engine's
+    device point store (``pbvi_upper_append``): per engine a cursor remembers how many points it already holds, so only the
+    new ones travel."""
+
+    def __init__(self, model, corner_belief_values: ValueFunction, sawtooth: str = 'reference') -> None:
+        if sawtooth not in ('reference', 'support'):
+            raise ValueError("sawtooth must be 'reference' or 'support'")
         self.model = model
         self.corner_belief_values = corner_belief_values
         self.corner_values = np.max(corner_belief_values.alpha_vector_array, axis=0)
+        self.sawtooth = sawtooth
         self.beliefs = []
         self.belief_value_mapping = {}
         self._belief_array = None
         self._value_array = None
+        # 'support' only: gap_i = v_i - p_i . corner, computed once when the point is added; the points the cached arrays of
+        # the reference would hold (its stale cache); the stacked points; per engine serial (store epoch, points appended)
+        self.gaps = []
+        self._n_visible = None
+        self._rows = np.zeros((0, len(self.corner_values)))
+        self._cursor = {}
 
     def add(self, b: Belief, v: float) -> None:
         """Record ``v`` at ``b``; a belief that is already a point keeps its first value."""
         if b.bytes_repr not in self.belief_value_mapping:
             self.beliefs.append(b)
             self.belief_value_mapping[b.bytes_repr] = v
+            if self.sawtooth == 'support':
+                self.gaps.append(float(v) - float(np.dot(np.asarray(b.values, dtype=np.float64), self.corner_values)))
 
     def update(self) -> None:
         """Re-stack the cached point arrays (``evaluate`` reads the cache, so points added since the last call
         are not seen until this runs -- the reference's behaviour, ``src/pomdp.py:863-870``)."""
+        if self.sawtooth == 'support':                       # (the cache is a count: the stacked points only grow)
+            self._n_visible = len(self.beliefs)
+            return
         self._belief_array = np.array([b.values for b in self.beliefs])
         self._value_array = np.array(list(self.belief_value_mapping.values()))
+
+    # -- 'support' mode ------------------------------------------------------------------------------------------- #
+    def window(self) -> Tuple[int, int]:
+        """``(n_visible, n_hit)``: the points the reference's cached arrays would hold at this moment -- those of the last
+        ``update()``, or of the first evaluation that found a point -- and the points its dictionary holds (all)."""
+        if self._n_visible is None and self.beliefs:
+            self._n_visible = len(self.beliefs)
+        return (self._n_visible or 0), len(self.beliefs)
+
+    def point_arrays(self):
+        """``(points [P,S], values [P], gaps [P])`` of every point, fp64 (the stack is extended, not rebuilt)."""
+        if self._rows.shape[0] < len(self.beliefs):
+            fresh = [np.asarray(b.values, dtype=np.float64) for b in self.beliefs[self._rows.shape[0]:]]
+            self._rows = np.concatenate([self._rows, np.array(fresh)])
+        return self._rows, np.array(list(self.belief_value_mapping.values()), dtype=np.float64), np.array(self.gaps)
+
+    def sync_engine(self, eng) -> None:
+        """Bring ``eng``'s device point store up to this mapping's points: a reset with the corner values when the store
+        is not (or no longer) this mapping's, then only the points added since the last call."""
+        if self.sawtooth != 'support':
+            raise ValueError("the device point store needs sawtooth='support'")
+        epoch, done = self._cursor.get(eng.serial, (None, 0))
+        if epoch != eng.upper_epoch or getattr(eng, '_upper_owner', None) is not self or done != eng.upper_count:
+            eng.upper_reset(self.corner_values)
+            eng._upper_owner = self
+            done = 0
+        if done < len(self.beliefs):
+            rows, values, gaps = self.point_arrays()
+            eng.upper_append(rows[done:], values[done:], gaps[done:])
+            done = len(self.beliefs)
+        self._cursor[eng.serial] = (eng.upper_epoch, done)
+
+    def evaluate_block(self, beliefs, engine=None) -> np.ndarray:
+        """``evaluate`` for every row of ``beliefs [n,S]`` (``'support'`` only): through ``engine``'s ``pbvi_upper_bound``
+        when one is given, else ``sawtooth_numpy``."""
+        if self.sawtooth != 'support':
+            raise ValueError("evaluate_block needs sawtooth='support'")
+        arr = np.asarray(beliefs, dtype=np.float64)
+        n_visible, n_hit = self.window()
+        if engine is not None:
+            self.sync_engine(engine)
+            engine.set_beliefs(arr)
+            return engine.upper_bound_resident(n_visible, n_hit)[0]
+        rows, values, gaps = self.point_arrays()
+        return sawtooth_numpy(rows, values, gaps, self.corner_values, arr, n_visible, n_hit)[0]
 
     @property
     def belief_array(self) -> np.ndarray:
@@ -295,6 +462,8 @@ class BeliefValueMapping:
         hit = self.belief_value_mapping.get(belief.bytes_repr)
         if hit is not None:
             return hit
+        if self.sawtooth == 'support':
+            return float(self.evaluate_block(np.asarray(belief.values)[None, :])[0])
         v0 = np.dot(belief.values, self.corner_values)
         if len(self.beliefs) == 0:
             return float(v0)
@@ -660,11 +829,27 @@ class PBVI_Solver(Solver):
         return BeliefSet(model, succ[b_i[:, None], a_i[:, None], o_i[:, None], model.states[None, :]])
 
     def expand_hsvi(self, model, b: Belief, value_function: ValueFunction, upper_bound_belief_value_map: BeliefValueMapping,
-                    conv_term: Union[float, None] = None, max_generation: int = 10) -> BeliefSet:
+                    conv_term: Union[float, None] = None, max_generation: int = 10, sawtooth: Union[str, None] = None,
+                    trace: Union[list, None] = None) -> BeliefSet:
         """HSVI descent (``src/pomdp.py:1768-1868``): from ``b`` take the action that is greedy for the upper bound,
         then the observation with the largest probability-weighted gap between the bounds, until the gap falls under
         ``eps / gamma^depth`` or ``max_generation`` beliefs are out.  The deepest belief comes first in the result.
-        The lower bound ``max_v alpha_v . b`` is one small matrix-vector product per observation and stays on the host."""
+        The lower bound ``max_v alpha_v . b`` is one small matrix-vector product per observation and stays on the host.
+
+        ``sawtooth`` (default: the mapping's own mode) ``'reference'`` is the reference bit for bit -- on a belief with
+        zeros its upper bound is NaN and the chain is the start belief's first successor alone.  ``'support'`` evaluates
+        the bound with ``sawtooth_numpy``'s definition, lets an impossible observation add 0 and never chooses one, and
+        runs on the engine when the value function is on the GPU (``_expand_hsvi_support``).  ``trace``, a list, receives
+        one dict per step of a ``'support'`` descent: the action values, the chosen (action, observation), the
+        observations' scores and gaps, and the hits met."""
+        mode = upper_bound_belief_value_map.sawtooth if sawtooth is None else sawtooth
+        if mode not in ('reference', 'support'):
+            raise ValueError("sawtooth must be 'reference' or 'support'")
+        if mode != upper_bound_belief_value_map.sawtooth:
+            raise ValueError(f"the upper bound mapping was built with sawtooth={upper_bound_belief_value_map.sawtooth!r}")
+        if mode == 'support':
+            return self._expand_hsvi_support(model, b, value_function, upper_bound_belief_value_map, conv_term, max_generation,
+                                             trace)
         rto = model.reachable_transitional_observation_table
         alpha = value_function.alpha_vector_array
         conv = self.eps if conv_term is None else conv_term
@@ -691,6 +876,74 @@ class PBVI_Solver(Solver):
             if gap_at_top < conv or max_generation <= 1:
                 break
             upper_bound_belief_value_map.add(b, best_q)
+            b = nxt
+            max_generation -= 1
+        return BeliefSet(model, chain[::-1])
+
+    def _expand_hsvi_support(self, model, b: Belief, value_function: ValueFunction, ub: BeliefValueMapping,
+                             conv_term: Union[float, None], max_generation: int, trace: Union[list, None]) -> BeliefSet:
+        """``expand_hsvi`` over the support-restricted sawtooth.  Per step: the action values of ``b`` under the upper bound
+        (``pbvi_upper_q`` / ``upper_q_numpy``) and their first maximum; the successors of that action under every POSSIBLE
+        observation (an impossible one has no successor, adds 0 and is never chosen); their lower bound ``max_v alpha_v .
+        b'`` and upper bound; the first largest ``P(o) * gap``.  With the value function on the GPU the three stages are engine
+        calls on the resident block (``upper_q``, then ``belief_update`` + ``max_value`` + ``upper_bound`` on the successors) and
+        the point store takes only the point each step adds; otherwise they are the NumPy restatements."""
+        conv = self.eps if conv_term is None else conv_term
+        on_gpu = bool(getattr(value_function, 'is_on_gpu', False))
+        if on_gpu:
+            eng = model.engine
+            eng.sync_rows('alpha', value_function.alpha_vector_list, lambda v: v.values)
+        else:
+            alpha = value_function.alpha_vector_array
+        chain = []
+        while True:
+            conv /= self.gamma
+            n_visible, n_hit = ub.window()
+            row = np.asarray(b.values, dtype=np.float64)[None, :]
+            if on_gpu:
+                ub.sync_engine(eng)
+                eng.set_beliefs(row)
+                q, act, p_obs = eng.upper_q_resident(self.gamma, n_visible, n_hit, want_p_obs=True)
+                hits = 0
+            else:
+                rows, values, gaps = ub.point_arrays()
+                q, act, p_obs, _, succ_hit = upper_q_numpy(model, rows, values, gaps, ub.corner_values, row, self.gamma,
+                                                           n_visible, n_hit)
+                hits = int(np.sum(succ_hit >= 0))
+            best_a = int(act[0])
+            best_q = float(q[0, best_a])
+            p_o = p_obs[0, best_a]
+            obs = np.flatnonzero(p_o > 0)
+            if on_gpu:
+                succ = eng.belief_update(np.repeat(row, len(obs), axis=0), np.full(len(obs), best_a), obs).astype(np.float64)
+                eng.set_beliefs(succ)
+                low = eng.max_value_resident()[0]
+                up, _, hit = eng.upper_bound_resident(n_visible, n_hit)
+                hits += int(np.sum(hit >= 0))
+                successors = []
+                for k in range(len(obs)):
+                    nb = Belief.__new__(Belief)
+                    nb.model = b.model
+                    nb._values = succ[k]
+                    successors.append(nb)
+            else:
+                successors = [b.update(best_a, int(o)) for o in obs]
+                hits += sum(1 for s in successors if s.bytes_repr in ub.belief_value_mapping)
+                low = np.array([np.max(np.dot(alpha, s.values)) for s in successors])
+                up = np.array([ub.evaluate(s) for s in successors])
+            gap = up - low
+            score = p_o[obs] * gap
+            top, gap_at_top, nxt, chosen = -np.inf, -np.inf, b, -1
+            for k in range(len(obs)):
+                if score[k] > top:
+                    top, gap_at_top, nxt, chosen = score[k], gap[k], successors[k], int(obs[k])
+            if trace is not None:
+                trace.append(dict(q=np.array(q[0]), action=best_a, observations=obs, scores=score, gaps=gap, observation=chosen,
+                                  hits=hits, belief=row[0]))
+            chain.append(nxt)
+            if gap_at_top < conv or max_generation <= 1:
+                break
+            ub.add(b, best_q)
             b = nxt
             max_generation -= 1
         return BeliefSet(model, chain[::-1])
@@ -794,7 +1047,7 @@ class PBVI_Solver(Solver):
             return self.expand_ger(model, belief_set, params['value_function'], max_generation)
         if f in 'expand_hsvi':
             if not hasattr(self, '_upper_bound'):          # kept on the solver across calls, like src/pomdp.py:2112-2115
-                self._upper_bound = BeliefValueMapping(model, params['mdp_policy'])
+                self._upper_bound = BeliefValueMapping(model, params['mdp_policy'], sawtooth=params.get('sawtooth', 'reference'))
             else:
                 self._upper_bound.update()
             return self.expand_hsvi(model, belief_set.belief_list[0], params['value_function'], self._upper_bound,
@@ -981,10 +1234,16 @@ class FSVI_EG_Solver(FSVI_Solver):
 
 
 class HSVI_Solver(PBVI_Solver):
-    """Heuristic Search Value Iteration preset (``src/pomdp.py:2416-2478``)."""
+    """Heuristic Search Value Iteration preset (``src/pomdp.py:2416-2478``).  ``sawtooth='reference'`` (the default) keeps
+    the reference's upper bound bit for bit, NaN on sparse beliefs included; ``sawtooth='support'`` evaluates it over the
+    support of each point (``sawtooth_numpy``), on the engine when the solve runs on the GPU (``expand_hsvi``)."""
 
-    def __init__(self, gamma: float = 0.99, eps: float = 0.001, mdp_solution: Union[ValueFunction, None] = None):
-        super().__init__(gamma, eps, 'hsvi', mdp_policy=mdp_solution)
+    def __init__(self, gamma: float = 0.99, eps: float = 0.001, mdp_solution: Union[ValueFunction, None] = None,
+                 sawtooth: str = 'reference'):
+        if sawtooth not in ('reference', 'support'):
+            raise ValueError("sawtooth must be 'reference' or 'support'")
+        extra = {} if sawtooth == 'reference' else {'sawtooth': sawtooth}
+        super().__init__(gamma, eps, 'hsvi', mdp_policy=mdp_solution, **extra)
 
     def solve(self, model, expansions, max_belief_growth: int = 10, initial_belief=None, initial_value_function=None,
               prune_level: int = 1, prune_interval: int = 10, limit_value_function_size: int = -1, use_gpu: bool = False,
