@@ -119,7 +119,8 @@ hipError_t launch_dead(const T* bel, int ldb, int B, ModelView<T> mv,
 
 // Belief-side projection: bp[((o*A + a)*B + b)][s'] = gamma * sum_{(s,r): rs[s,a,r] = s'} b[b][s] * RTO[s,a,o,r]  (g = a*O+o), so
 // that bp[g,b,:] . alpha[v,:] == b . Gamma[a,o,v,:] re-associated; accumulated in f64, rounded once to T.
-// mag [B][G] (zeroed by the caller) receives sum_s' |bp| * amax[s'].  in_ptr / in_src: inverse transition lists.
+// mag [B][G] (zeroed by the caller) receives sum_s' |bp| * amax[s'].  in_ptr / in_src: inverse transition lists; the sum is
+// successor.h's successor_tile, four beliefs and four observations per thread.
 template <typename T>
 hipError_t launch_push_project(const T* bel, int ldb, int B, ModelView<T> mv, const int32_t* in_ptr,
                                const int32_t* in_src, double gamma, const T* amax, T* bp, int ldp, double* mag,
@@ -192,7 +193,7 @@ struct RefineWork {
     uint8_t* nzW = nullptr;              // [ceil(w_slot_cap / 256)][S_pad / 32]
     int* klistW = nullptr;               // workspace of launch_gemm_nt_f64_bf32
     int* kcountW = nullptr;
-    const int32_t* in_ptr = nullptr;     // inverse transition lists (engine.hip::build_inverse_lists)
+    const int32_t* in_ptr = nullptr;     // inverse transition lists (engine.hip::build_inverse_lists), read by successor_pull
     const int32_t* in_src = nullptr;
     // Level-1 screen of the per-entry pass (PROJ, fp32 engines whose Gamma rows are in HBM): the candidates' scores
     // are first re-summed in fp64 from the PROJECTED fp32 rows the GEMM read -- |Gamma_f32 - Gamma| <= l1_rel * Gamma(max|alpha|)
@@ -296,8 +297,12 @@ struct BayesStep {
     double* unnorm;            // [B][S] scratch: the un-normalised rows
     double* mass;              // [B] their sums
     double* mass_part;         // [B][ceil(S / 256)], or nullptr
+    // >= 0: the B = nb * A * O rows are every (a, o) of the beliefs [every_ao_from, every_ao_from + nb) of bel instead: row j is
+    // belief every_ao_from + j / (A * O) under action (j / O) % A and observation j % O; act / obs are not read.
+    int every_ao_from = -1;
 };
-// launch_belief_push  k_belief_push (+ k_mass_fold): unnorm and mass of the rows with out_row[b] >= 0 (out_row == nullptr: all).
+// launch_belief_push  k_belief_push (+ k_mass_fold): unnorm and mass of the rows with out_row[b] >= 0 (out_row == nullptr: all);
+//                     unnorm is u of successor.h (successor_pull), one block per (256 landing states, row).
 //                     mass_part == nullptr: the blocks add their partial masses to mass with atomicAdd (the caller has zeroed
 //                     it); otherwise they store them there and a fold kernel adds them in block order -- the same norm up to
 //                     its last bit, but the same bits every time.
@@ -354,7 +359,7 @@ hipError_t launch_rollout_compact(const RolloutStep& rs, int32_t* dst, int32_t* 
 
 // Infotaxis (pbvi_infotaxis): for every belief row b of `bel` (engine order; caller row d = perm ? perm[b] : b) and action a
 //   G[b,a] = sum_o (Z ln Z - N),  Z = sum_s' u[s'],  N = sum_s' u[s'] ln u[s']  (zero terms add 0; fp64 log),
-//   u[s']  = sum over the inverse list of (a, s') of (double) bel[b][s] * (double) RTO[s,a,o,r]  (launch_belief_push's sum)
+//   u[s']  = sum over the inverse list of (a, s') of (double) bel[b][s] * (double) RTO[s,a,o,r]  (successor.h: successor_tile)
 // = the expected entropy, in nats, of the belief after taking a.  Three kernels, no atomics, every sum in a fixed order:
 //   k_succ_entropy<T>   (Z, N) partials of each x-block (succ_entropy_xblocks(S) of them) into part [XB][B][A][O][2]
 //   k_infotaxis_finish  partials summed in x-block order -> g_out [B][A], pobs_out [B][A][O] = Z (or nullptr), action_out [B] =
@@ -369,7 +374,8 @@ hipError_t launch_infotaxis(const T* bel, int ldb, int B, ModelView<T> mv, const
 
 // one step of the belief walk: out64 [S] / out_store [S_pad] = normalised update of `base` (fp64 [S]) with (a, o);
 // unnorm [S], partial [ceil(S_pad/256)] fp64 scratch; rto64: fp64 copy of RTO in mv's layout, or nullptr = use mv.rto
-// one kernel per step: pushes belief i and writes belief i (normalising the previous raw result on the fly); see the kernel
+// one kernel per step: pushes belief i and writes belief i (normalising the previous raw result on the fly); see the kernel.
+// The un-normalised row is successor.h's successor_pull with the product rounded before it is added (NumPy's doubles).
 template <typename T>
 hipError_t launch_walk_fused(const double* plain_base, const double* prev_unnorm, const double* prev_partial, double* prev_out64,
                              T* prev_out_store, ModelView<T> mv, const double* rto64, const int32_t* in_ptr, const int32_t* in_src,

@@ -7,6 +7,7 @@
 // along s, 64-wide wavefronts) and reduce with wave shuffles in a fixed order, so
 // results are deterministic run to run.
 #include "backup_kernels.h"
+#include "successor.h"
 
 #include <algorithm>
 #include <cstdint>
@@ -18,22 +19,7 @@ namespace pbvi {
 // ------------------------------------------------------------------------- //
 // helpers
 // ------------------------------------------------------------------------- //
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// Sum over the block (blockDim.x = 256); every thread gets the result.  sh: >= 4 doubles.
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) sh[wid] = v;
-    __syncthreads();
-    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-
+// (wave_sum / block_sum: successor.h)
 // Tile list of one belief: the K tiles (32 states) that hold belief mass; list == nullptr means every tile.
 struct TileList {
     const int32_t* list;
@@ -1600,9 +1586,8 @@ __global__ void k_refine_merge(RefineWork work, int32_t* __restrict__ best_v, do
     }
 }
 
-// GEMM path, step 1: the fp64 weight row of each slot's entry.  PROJ: w[s'] = gamma * sum_{(s,r)->s'} b[s] * RTO[s,a,o,r]
-// (pull over the inverse lists; products of fp32 values are exact in fp64), so that w . alpha_v is the entry's exact
-// score of alpha_v; plain: w = b.
+// GEMM path, step 1: the fp64 weight row of each slot's entry.  PROJ: w[s'] = gamma * u[s'] (successor_pull; products of
+// fp32 values are exact in fp64), so that w . alpha_v is the entry's exact score of alpha_v; plain: w = b.
 template <typename T, bool PROJ>
 __global__ void k_refine_weights(int G, const T* __restrict__ bel, int ldb, ModelView<T> mv, double gamma, RefineWork work) {
     const int sl = blockIdx.y, sp = blockIdx.x * 256 + threadIdx.x;
@@ -1613,15 +1598,8 @@ __global__ void k_refine_weights(int G, const T* __restrict__ bel, int ldb, Mode
     double w = 0.0;
     if (sp < mv.S) {
         if constexpr (PROJ) {
-            const int a = g / mv.O, o = g % mv.O;
-            const int32_t* ptr = work.in_ptr + (int64_t)a * (mv.S + 1);
-            const int32_t* src = work.in_src + (int64_t)a * mv.S * mv.R;
-            const T* rto = mv.rto + (int64_t)(a * mv.O + o) * mv.R * mv.S_pad;
-            for (int j = ptr[sp]; j < ptr[sp + 1]; ++j) {
-                const int en = src[j];
-                const int s = en / mv.R, r = en - s * mv.R;
-                w += (double)brow[s] * (double)rto[(int64_t)r * mv.S_pad + s];
-            }
+            w = successor_pull<false>(work.in_ptr, work.in_src, mv.rto, mv.S, mv.S_pad, mv.O, mv.R, g / mv.O, g % mv.O, sp,
+                                      [&](int s) { return (double)brow[s]; });
             w *= gamma;
         } else {
             w = (double)brow[sp];
@@ -2369,7 +2347,8 @@ hipError_t launch_dominated_masked(const T* alpha, int lda, int S, const int32_t
 // Pull form over inverse transition lists (CSC built at engine creation, entries in ascending (s, r) order =
 // bincount's accumulation order), so the sums are deterministic and need no atomics.
 // ------------------------------------------------------------------------- //
-template <typename T>
+// EVERY_AO: row b is belief b / (A * O) of `bel` under action (b / O) % A and observation b % O; act / obs are not read.
+template <typename T, bool EVERY_AO>
 __global__ void k_belief_push(const T* __restrict__ bel, int ldb, ModelView<T> mv, const int32_t* __restrict__ in_ptr,
                               const int32_t* __restrict__ in_src, const int32_t* __restrict__ act,
                               const int32_t* __restrict__ obs, const int32_t* __restrict__ out_row,
@@ -2378,18 +2357,12 @@ __global__ void k_belief_push(const T* __restrict__ bel, int ldb, ModelView<T> m
     __shared__ double red[4];
     const int b = blockIdx.y, sp = blockIdx.x * 256 + threadIdx.x;
     if (out_row && out_row[b] < 0) return;                 // dropped row (whole block leaves together)
-    const int a = act[b], o = obs[b];
+    const int a = EVERY_AO ? (b / mv.O) % mv.A : act[b], o = EVERY_AO ? b % mv.O : obs[b];
     double u = 0.0;
     if (sp < mv.S) {
-        const int32_t* ptr = in_ptr + (int64_t)a * (mv.S + 1);
-        const int32_t* src = in_src + (int64_t)a * mv.S * mv.R;
-        const T* rto = mv.rto + (int64_t)(a * mv.O + o) * mv.R * mv.S_pad;
-        const T* brow = bel + (int64_t)b * ldb;
-        for (int j = ptr[sp]; j < ptr[sp + 1]; ++j) {
-            const int e = src[j];                           // e = s * R + r
-            const int s = e / mv.R, r = e - s * mv.R;
-            u += (double)brow[s] * (double)rto[(int64_t)r * mv.S_pad + s];
-        }
+        const T* brow = bel + (int64_t)(EVERY_AO ? b / (mv.O * mv.A) : b) * ldb;
+        u = successor_pull<false>(in_ptr, in_src, mv.rto, mv.S, mv.S_pad, mv.O, mv.R, a, o, sp,
+                                  [&](int s) { return (double)brow[s]; });
         unnorm[(int64_t)b * mv.S + sp] = u;
     }
     const double tot = block_sum(u, red);
@@ -2428,8 +2401,12 @@ hipError_t launch_belief_push(const BayesStep<T>& bs, ModelView<T> mv, const int
     if (bs.B <= 0) return hipSuccess;
     if (bs.B > 65535) return hipErrorInvalidValue;
     dim3 grid((mv.S + 255) / 256, bs.B);
-    hipLaunchKernelGGL(k_belief_push<T>, grid, dim3(256), 0, st, bs.bel, bs.ldb, mv, bs.in_ptr, bs.in_src, bs.act, bs.obs, out_row,
-                       bs.unnorm, bs.mass, bs.mass_part);
+    if (bs.every_ao_from >= 0)
+        hipLaunchKernelGGL((k_belief_push<T, true>), grid, dim3(256), 0, st, bs.bel + (int64_t)bs.every_ao_from * bs.ldb, bs.ldb, mv,
+                           bs.in_ptr, bs.in_src, nullptr, nullptr, out_row, bs.unnorm, bs.mass, bs.mass_part);
+    else
+        hipLaunchKernelGGL((k_belief_push<T, false>), grid, dim3(256), 0, st, bs.bel, bs.ldb, mv, bs.in_ptr, bs.in_src, bs.act, bs.obs,
+                           out_row, bs.unnorm, bs.mass, bs.mass_part);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || bs.mass_part == nullptr) return e;
     hipLaunchKernelGGL(k_mass_fold, dim3((bs.B + 255) / 256), dim3(256), 0, st, bs.B, (int)grid.x, out_row, bs.mass_part, bs.mass);
@@ -2451,67 +2428,40 @@ hipError_t launch_belief_norm(const BayesStep<T>& bs, int S, const int32_t* out_
 //   score[b,a,o,v] = bp[g,b,:] . alpha[v,:]   ( = b . Gamma[a,o,v,:] of src/pomdp.py:1489-1495, re-associated)
 // Pull form over the inverse transition lists (no atomics on bp), f64 accumulation, one rounding to T.
 // ------------------------------------------------------------------------- //
-constexpr int PUSH_NB = 4;   // beliefs per thread of k_push_project
-constexpr int PUSH_NT = 8;   // 256-state chunks per block
 template <typename T>
 __global__ void k_push_project(const T* __restrict__ bel, int ldb, int B, ModelView<T> mv,
                                const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ in_src, double gamma,
                                const T* __restrict__ amax, T* __restrict__ bp, int ldp, double* __restrict__ mag,
                                uint8_t* __restrict__ nzP /* [rows / 256][ldp / 32], zeroed by the caller: set where a projected
                                                             row has a non-zero in the K tile (or nullptr) */) {
-    // One thread per target state s' and PUSH_NB beliefs: the inverse list of (a, s') and the weights of its entries do not
-    // depend on the belief, so they are read once for the four.  A block walks PUSH_NT chunks of 256 states and reduces the
-    // magnitudes once at its end: with one chunk per block the per-thread work (one or two list entries) was a tenth of the
-    // block's reduction and its atomics -- 0.89 ms for 100 beliefs at the Sea-Robin shape whether or not anything was
-    // gathered or stored.  Per (belief, observation) the sum runs over the list in order, as before: an entry whose belief
-    // value is zero adds an exact zero.
-    __shared__ double red[PUSH_NB][16];
-    const int b0 = blockIdx.y * PUSH_NB, a = blockIdx.z;
-    const int nb = B - b0 < PUSH_NB ? B - b0 : PUSH_NB;
+    // One thread per target state s' and TILE_NB beliefs (successor_tile).  A block walks TILE_NT chunks of 256 states and
+    // reduces the magnitudes once at its end: with one chunk per block the per-thread work (one or two list entries) was a
+    // tenth of the block's reduction and its atomics -- 0.89 ms for 100 beliefs at the Sea-Robin shape whether or not
+    // anything was gathered or stored.
+    __shared__ double red[TILE_NB][4 * TILE_NO];
+    const int b0 = blockIdx.y * TILE_NB, a = blockIdx.z;
+    const int nb = B - b0 < TILE_NB ? B - b0 : TILE_NB;
     const int G = mv.A * mv.O;
     const int32_t* ptr = in_ptr + (int64_t)a * (mv.S + 1);
     const int32_t* src = in_src + (int64_t)a * mv.S * mv.R;
-    for (int o0 = 0; o0 < mv.O; o0 += 4) {
-        const int no = mv.O - o0 < 4 ? mv.O - o0 : 4;
-        double mg[PUSH_NB][4];
+    for (int o0 = 0; o0 < mv.O; o0 += TILE_NO) {
+        const int no = mv.O - o0 < TILE_NO ? mv.O - o0 : TILE_NO;
+        double mg[TILE_NB][TILE_NO];
 #pragma unroll
-        for (int k = 0; k < PUSH_NB; ++k)
+        for (int k = 0; k < TILE_NB; ++k)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) mg[k][q] = 0.0;
-        for (int c = 0; c < PUSH_NT; ++c) {
-            const int sp = (blockIdx.x * PUSH_NT + c) * 256 + threadIdx.x;
+            for (int q = 0; q < TILE_NO; ++q) mg[k][q] = 0.0;
+        for (int c = 0; c < TILE_NT; ++c) {
+            const int sp = (blockIdx.x * TILE_NT + c) * 256 + threadIdx.x;
             if (sp >= ldp) break;                           // (whole waves: ldp is a multiple of 32, chunks of 256)
             const int j0 = sp < mv.S ? ptr[sp] : 0, j1 = sp < mv.S ? ptr[sp + 1] : 0;
             const double am = sp < mv.S ? fabs((double)amax[sp]) : 0.0;
-            double acc[PUSH_NB][4];
+            double acc[TILE_NB][TILE_NO];
+            successor_tile(bel, ldb, b0, nb, mv, src, j0, j1, a, o0, no, acc);
 #pragma unroll
-            for (int k = 0; k < PUSH_NB; ++k)
+            for (int k = 0; k < TILE_NB; ++k)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) acc[k][q] = 0.0;
-            for (int j = j0; j < j1; ++j) {
-                const int e = src[j];                       // e = s * R + r
-                const int s = mv.R == 1 ? e : e / mv.R, r = e - s * mv.R;
-                double bs[PUSH_NB];
-                bool any = false;
-#pragma unroll
-                for (int k = 0; k < PUSH_NB; ++k) {
-                    bs[k] = k < nb ? (double)bel[(int64_t)(b0 + k) * ldb + s] : 0.0;
-                    any = any || bs[k] != 0.0;
-                }
-                if (any) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        if (q < no) {
-                            const double w = (double)mv.rto[((int64_t)(a * mv.O + o0 + q) * mv.R + r) * mv.S_pad + s];
-#pragma unroll
-                            for (int k = 0; k < PUSH_NB; ++k) acc[k][q] += bs[k] * w;
-                        }
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < PUSH_NB; ++k)
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
+                for (int q = 0; q < TILE_NO; ++q)
                     if (q < no && k < nb) {                 // uniform across the block
                         const T val = (T)(gamma * acc[k][q]);
                         const int64_t row = push_row_index(o0 + q, a, b0 + k, mv.A, B);      // see SlabView
@@ -2527,20 +2477,20 @@ __global__ void k_push_project(const T* __restrict__ bel, int ldb, int B, ModelV
         }
         // magnitudes: one barrier for all beliefs and (up to four) observations of this pass
 #pragma unroll
-        for (int k = 0; k < PUSH_NB; ++k)
+        for (int k = 0; k < TILE_NB; ++k)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) mg[k][q] = wave_sum(mg[k][q]);
+            for (int q = 0; q < TILE_NO; ++q) mg[k][q] = wave_sum(mg[k][q]);
         __syncthreads();                                    // red[] of the previous pass has been read
         if ((threadIdx.x & 63) == 0) {
 #pragma unroll
-            for (int k = 0; k < PUSH_NB; ++k)
+            for (int k = 0; k < TILE_NB; ++k)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) red[k][(threadIdx.x >> 6) * 4 + q] = mg[k][q];
+                for (int q = 0; q < TILE_NO; ++q) red[k][(threadIdx.x >> 6) * TILE_NO + q] = mg[k][q];
         }
         __syncthreads();
         if ((int)threadIdx.x < no * nb) {
             const int k = threadIdx.x / no, q = threadIdx.x % no;
-            const double part = ((red[k][q] + red[k][4 + q]) + red[k][8 + q]) + red[k][12 + q];
+            const double part = ((red[k][q] + red[k][TILE_NO + q]) + red[k][2 * TILE_NO + q]) + red[k][3 * TILE_NO + q];
             if (part != 0.0) atomicAdd(&mag[(int64_t)(b0 + k) * G + a * mv.O + o0 + q], part);
         }
     }
@@ -2552,8 +2502,8 @@ hipError_t launch_push_project(const T* bel, int ldb, int B, ModelView<T> mv, co
                                hipStream_t st, uint8_t* nzP) {
     if (B <= 0) return hipSuccess;
     if (B > 65535 || mv.A > 65535) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_push_project<T>, dim3((ldp + 256 * PUSH_NT - 1) / (256 * PUSH_NT), (B + PUSH_NB - 1) / PUSH_NB, mv.A), dim3(256), 0, st, bel, ldb, B, mv, in_ptr,
-                       in_src, gamma, amax, bp, ldp, mag, nzP);
+    hipLaunchKernelGGL(k_push_project<T>, dim3((ldp + 256 * TILE_NT - 1) / (256 * TILE_NT), (B + TILE_NB - 1) / TILE_NB, mv.A), dim3(256),
+                       0, st, bel, ldb, B, mv, in_ptr, in_src, gamma, amax, bp, ldp, mag, nzP);
     return hipGetLastError();
 }
 
@@ -2586,27 +2536,20 @@ hipError_t launch_rdot(const T* bel, int ldb, int B, ModelView<T> mv, const int3
 // in fp64 whatever the engine's T (the host mirror keeps fp64 belief values).  One step = k_walk_push (pull over
 // the inverse lists in bincount's accumulation order, per-block partial masses) + k_walk_norm (every block sums
 // the partials in the same fixed order, so the normaliser is deterministic; writes the fp64 row and the T row of
-// the device store).  Products and sums are not fused so the un-normalised values equal NumPy's bincount.
+// the device store).  Products and sums are not fused (successor_pull<true>) so the un-normalised values equal NumPy's
+// bincount.
 // ------------------------------------------------------------------------- //
 // TT: type of the RTO table the walk reads (an f32 engine may hold an fp64 copy for it), T: type of the store rows
 template <typename TT>
 __global__ void k_walk_push(const double* __restrict__ base, const TT* __restrict__ rto_all, int S, int S_pad, int O, int R,
                             const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ in_src, int a, int o,
                             double* __restrict__ unnorm, double* __restrict__ partial) {
-#pragma clang fp contract(off)
+#pragma clang fp contract(off)   // (the pragma is lexical: the sum itself is successor_pull<true>'s)
     __shared__ double red[4];
     const int sp = blockIdx.x * 256 + threadIdx.x;
     double u = 0.0;
     if (sp < S) {
-        const int32_t* ptr = in_ptr + (int64_t)a * (S + 1);
-        const int32_t* src = in_src + (int64_t)a * S * R;
-        const TT* rto = rto_all + (int64_t)(a * O + o) * R * S_pad;
-        for (int j = ptr[sp]; j < ptr[sp + 1]; ++j) {
-            const int e = src[j];
-            const int s = e / R, r = e - s * R;
-            const double w = (double)rto[(int64_t)r * S_pad + s] * base[s];
-            u = u + w;
-        }
+        u = successor_pull<true>(in_ptr, in_src, rto_all, S, S_pad, O, R, a, o, sp, [&](int s) { return base[s]; });
         unnorm[sp] = u;
     }
     const double tot = block_sum(u, red);
@@ -2618,7 +2561,7 @@ __global__ void k_walk_push(const double* __restrict__ base, const TT* __restric
 __device__ __forceinline__ double partials_sum(const double* __restrict__ partial, int n, double* red /* [4] shared */) {
     double m = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) m += partial[i];
-    for (int off = 32; off > 0; off >>= 1) m += __shfl_xor(m, off, 64);
+    m = wave_sum(m);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
     const double tot = ((red[0] + red[1]) + red[2]) + red[3];
@@ -2626,14 +2569,12 @@ __device__ __forceinline__ double partials_sum(const double* __restrict__ partia
     return tot;
 }
 
+// Column s of a normalised walk row: the fp64 value for the host, its rounding for the store, zeros in the pad columns.
 template <typename T>
-__global__ void k_walk_norm(const double* __restrict__ unnorm, const double* __restrict__ partial, int n_partial, int S,
-                            int S_pad, double* __restrict__ out64, T* __restrict__ out_store) {
-    __shared__ double red_m[4];
-    const double mass_sh = partials_sum(partial, n_partial, red_m);
-    const int s = blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void walk_store(const double* __restrict__ unnorm, double mass, int s, int S, int S_pad,
+                                           double* __restrict__ out64, T* __restrict__ out_store) {
     if (s < S) {
-        const double v = unnorm[s] / mass_sh;
+        const double v = unnorm[s] / mass;
         out64[s] = v;
         out_store[s] = (T)v;
     } else if (s < S_pad) {
@@ -2641,9 +2582,17 @@ __global__ void k_walk_norm(const double* __restrict__ unnorm, const double* __r
     }
 }
 
+template <typename T>
+__global__ void k_walk_norm(const double* __restrict__ unnorm, const double* __restrict__ partial, int n_partial, int S,
+                            int S_pad, double* __restrict__ out64, T* __restrict__ out_store) {
+    __shared__ double red_m[4];
+    const double mass_sh = partials_sum(partial, n_partial, red_m);
+    walk_store(unnorm, mass_sh, blockIdx.x * 256 + threadIdx.x, S, S_pad, out64, out_store);
+}
+
 // One kernel per step of a chain: step i pushes belief i through (a, o) AND writes belief i itself, normalising the
 // previous step's raw result on the fly (every block re-adds the previous step's block partials in the same order, so
-// all blocks divide by the same mass; a gathered value prev_unnorm[s] / mass is the very double k_walk_norm would have
+// all blocks divide by the same mass; a gathered value prev_unnorm[s] / mass is the very double walk_store has
 // stored).  Halves the dependent launches of a walk, which is what its time consists of (~6 us each).
 //   plain_base : belief to push when it is already normalised (b0: first step and restarts), else nullptr
 //   prev_*     : previous step's raw row / partial sums / destinations of its normalised row (all nullptr at step 0)
@@ -2657,52 +2606,46 @@ __global__ void k_walk_fused(const double* __restrict__ plain_base, const double
     __shared__ double red[4];
     const double mass = prev_unnorm != nullptr ? partials_sum(prev_partial, n_partial, red) : 1.0;
     const int sp = blockIdx.x * 256 + threadIdx.x;
-    if (prev_out64 != nullptr) {                         // the previous belief, normalised (k_walk_norm's statement)
-        if (sp < S) {
-            const double v = prev_unnorm[sp] / mass;
-            prev_out64[sp] = v;
-            prev_out_store[sp] = (T)v;
-        } else if (sp < S_pad) {
-            prev_out_store[sp] = T(0);
-        }
-    }
+    if (prev_out64 != nullptr) walk_store(prev_unnorm, mass, sp, S, S_pad, prev_out64, prev_out_store);   // the previous belief
     double u = 0.0;
     if (sp < S) {
-        const int32_t* ptr = in_ptr + (int64_t)a * (S + 1);
-        const int32_t* src = in_src + (int64_t)a * S * R;
-        const TT* rto = rto_all + (int64_t)(a * O + o) * R * S_pad;
-        for (int j = ptr[sp]; j < ptr[sp + 1]; ++j) {
-            const int e = src[j];
-            const int s = e / R, r = e - s * R;
-            const double bs = plain_base != nullptr ? plain_base[s] : prev_unnorm[s] / mass;
-            const double w = (double)rto[(int64_t)r * S_pad + s] * bs;
-            u = u + w;
-        }
+        u = successor_pull<true>(in_ptr, in_src, rto_all, S, S_pad, O, R, a, o, sp,
+                                 [&](int s) { return plain_base != nullptr ? plain_base[s] : prev_unnorm[s] / mass; });
         unnorm[sp] = u;
     }
     const double tot = block_sum(u, red);
     if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
 
+// The walk's grid: one block per 256 columns of a store row, which is also the number of block partials of a step.
+template <typename T>
+int walk_blocks(ModelView<T> mv) {
+    return (mv.S_pad + 255) / 256;
+}
+
+// The walk's table: the fp64 copy of RTO where the engine holds one, else the engine's own.  launch(rto, blocks).
+template <typename T, typename Launch>
+hipError_t walk_launch(ModelView<T> mv, const double* rto64, Launch launch) {
+    if (rto64 != nullptr) launch(rto64, walk_blocks(mv));
+    else launch(mv.rto, walk_blocks(mv));
+    return hipGetLastError();
+}
+
 template <typename T>
 hipError_t launch_walk_fused(const double* plain_base, const double* prev_unnorm, const double* prev_partial, double* prev_out64,
                              T* prev_out_store, ModelView<T> mv, const double* rto64, const int32_t* in_ptr, const int32_t* in_src,
                              int a, int o, double* unnorm, double* partial, hipStream_t st) {
-    const int blocks = (mv.S_pad + 255) / 256;
-    if (rto64 != nullptr)
-        hipLaunchKernelGGL((k_walk_fused<double, T>), dim3(blocks), dim3(256), 0, st, plain_base, prev_unnorm, prev_partial, blocks,
-                           prev_out64, prev_out_store, rto64, mv.S, mv.S_pad, mv.O, mv.R, in_ptr, in_src, a, o, unnorm, partial);
-    else
-        hipLaunchKernelGGL((k_walk_fused<T, T>), dim3(blocks), dim3(256), 0, st, plain_base, prev_unnorm, prev_partial, blocks,
-                           prev_out64, prev_out_store, mv.rto, mv.S, mv.S_pad, mv.O, mv.R, in_ptr, in_src, a, o, unnorm, partial);
-    return hipGetLastError();
+    return walk_launch(mv, rto64, [&](auto* rto, int blocks) {
+        hipLaunchKernelGGL(k_walk_fused, dim3(blocks), dim3(256), 0, st, plain_base, prev_unnorm, prev_partial, blocks, prev_out64,
+                           prev_out_store, rto, mv.S, mv.S_pad, mv.O, mv.R, in_ptr, in_src, a, o, unnorm, partial);
+    });
 }
 
 // the last belief of a chain: only the normalisation is left
 template <typename T>
 hipError_t launch_walk_finish(const double* unnorm, const double* partial, ModelView<T> mv, double* out64, T* out_store,
                               hipStream_t st) {
-    const int blocks = (mv.S_pad + 255) / 256;
+    const int blocks = walk_blocks(mv);
     hipLaunchKernelGGL(k_walk_norm<T>, dim3(blocks), dim3(256), 0, st, unnorm, partial, blocks, mv.S, mv.S_pad, out64, out_store);
     return hipGetLastError();
 }
@@ -2711,18 +2654,11 @@ template <typename T>
 hipError_t launch_walk_step(const double* base, ModelView<T> mv, const double* rto64, const int32_t* in_ptr,
                             const int32_t* in_src, int a, int o, double* unnorm, double* partial, double* out64,
                             T* out_store, hipStream_t st) {
-    const int blocks = (mv.S_pad + 255) / 256;
-    if (rto64 != nullptr)
-        hipLaunchKernelGGL(k_walk_push<double>, dim3(blocks), dim3(256), 0, st, base, rto64, mv.S, mv.S_pad, mv.O, mv.R,
-                           in_ptr, in_src, a, o, unnorm, partial);
-    else
-        hipLaunchKernelGGL(k_walk_push<T>, dim3(blocks), dim3(256), 0, st, base, mv.rto, mv.S, mv.S_pad, mv.O, mv.R, in_ptr,
-                           in_src, a, o, unnorm, partial);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_walk_norm<T>, dim3(blocks), dim3(256), 0, st, unnorm, partial, blocks, mv.S, mv.S_pad, out64,
-                       out_store);
-    return hipGetLastError();
+    const hipError_t e = walk_launch(mv, rto64, [&](auto* rto, int blocks) {
+        hipLaunchKernelGGL(k_walk_push, dim3(blocks), dim3(256), 0, st, base, rto, mv.S, mv.S_pad, mv.O, mv.R, in_ptr, in_src, a, o,
+                           unnorm, partial);
+    });
+    return e != hipSuccess ? e : launch_walk_finish(unnorm, partial, mv, out64, out_store, st);
 }
 
 // ------------------------------------------------------------------------- //
@@ -2931,7 +2867,7 @@ hipError_t launch_rollout_compact(const RolloutStep& rs, int32_t* dst, int32_t* 
 
 // ------------------------------------------------------------------------- //
 // Infotaxis (pbvi_infotaxis): expected entropy of the successor belief, for every belief of the block and every action.
-//   u[s']  = sum over (s, r) with rs[s,a,r] == s' of (double) b[s] * (double) RTO[s,a,o,r]     (k_belief_push's sum and order)
+//   u[s']  = sum over (s, r) with rs[s,a,r] == s' of (double) b[s] * (double) RTO[s,a,o,r]     (successor.h)
 //   Z[a,o] = sum_s' u[s'],   N[a,o] = sum_s' u[s'] ln u[s']   (u == 0 adds 0)
 //   G[b,a] = sum_o (Z ln Z - N)  =  sum_o P(o | b, a) H(update(b, a, o))   in nats;   a* = first minimum of G[b, :]
 // The successor beliefs are never stored: u lives in a register between its sum and its two reductions.  Every sum has a
@@ -2939,63 +2875,36 @@ hipError_t launch_rollout_compact(const RolloutStep& rs, int32_t* dst, int32_t* 
 // waves in order, the x-blocks in order in the finish kernel -- and nothing is accumulated with atomics, so a belief's G has
 // the same bits whatever else is in the block and wherever it sits in it.
 // ------------------------------------------------------------------------- //
-constexpr int SE_NB = 4;   // beliefs per thread of k_succ_entropy (they share the list entries and weights)
-constexpr int SE_NT = 8;   // 256-state chunks per block
-constexpr int SE_NO = 4;   // observations per pass
-
-int succ_entropy_xblocks(int S) { return (S + 256 * SE_NT - 1) / (256 * SE_NT); }
+int succ_entropy_xblocks(int S) { return (S + 256 * TILE_NT - 1) / (256 * TILE_NT); }
 
 template <typename T>
 __global__ void __launch_bounds__(256) k_succ_entropy(const T* __restrict__ bel, int ldb, int B, ModelView<T> mv,
                                                       const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ in_src,
                                                       double* __restrict__ part /* [gridDim.x][B][A][O][2] */) {
-    // One thread per landing state s' and SE_NB beliefs, as k_push_project; a block walks SE_NT chunks of 256 states and
-    // reduces its (Z, N) partials once per pass over (up to) SE_NO observations.
-    __shared__ double red[4][2 * SE_NB * SE_NO];
-    const int b0 = blockIdx.y * SE_NB, a = blockIdx.z;
-    const int nb = B - b0 < SE_NB ? B - b0 : SE_NB;
+    // One thread per landing state s' and TILE_NB beliefs (successor_tile); a block walks TILE_NT chunks of 256 states and
+    // reduces its (Z, N) partials once per pass over (up to) TILE_NO observations.
+    __shared__ double red[4][2 * TILE_NB * TILE_NO];
+    const int b0 = blockIdx.y * TILE_NB, a = blockIdx.z;
+    const int nb = B - b0 < TILE_NB ? B - b0 : TILE_NB;
     const int32_t* ptr = in_ptr + (int64_t)a * (mv.S + 1);
     const int32_t* src = in_src + (int64_t)a * mv.S * mv.R;
-    for (int o0 = 0; o0 < mv.O; o0 += SE_NO) {
-        const int no = mv.O - o0 < SE_NO ? mv.O - o0 : SE_NO;
-        double zs[SE_NB][SE_NO], ns[SE_NB][SE_NO];
+    for (int o0 = 0; o0 < mv.O; o0 += TILE_NO) {
+        const int no = mv.O - o0 < TILE_NO ? mv.O - o0 : TILE_NO;
+        double zs[TILE_NB][TILE_NO], ns[TILE_NB][TILE_NO];
 #pragma unroll
-        for (int k = 0; k < SE_NB; ++k)
+        for (int k = 0; k < TILE_NB; ++k)
 #pragma unroll
-            for (int q = 0; q < SE_NO; ++q) zs[k][q] = ns[k][q] = 0.0;
-        for (int c = 0; c < SE_NT; ++c) {
-            const int sp = (blockIdx.x * SE_NT + c) * 256 + threadIdx.x;
+            for (int q = 0; q < TILE_NO; ++q) zs[k][q] = ns[k][q] = 0.0;
+        for (int c = 0; c < TILE_NT; ++c) {
+            const int sp = (blockIdx.x * TILE_NT + c) * 256 + threadIdx.x;
             if (sp >= mv.S) break;
             const int j0 = ptr[sp], j1 = ptr[sp + 1];
-            double acc[SE_NB][SE_NO];
+            double acc[TILE_NB][TILE_NO];
+            successor_tile(bel, ldb, b0, nb, mv, src, j0, j1, a, o0, no, acc);
 #pragma unroll
-            for (int k = 0; k < SE_NB; ++k)
+            for (int k = 0; k < TILE_NB; ++k)
 #pragma unroll
-                for (int q = 0; q < SE_NO; ++q) acc[k][q] = 0.0;
-            for (int j = j0; j < j1; ++j) {
-                const int e = src[j];                       // e = s * R + r
-                const int s = mv.R == 1 ? e : e / mv.R, r = e - s * mv.R;
-                double bs[SE_NB];
-                bool any = false;
-#pragma unroll
-                for (int k = 0; k < SE_NB; ++k) {
-                    bs[k] = k < nb ? (double)bel[(int64_t)(b0 + k) * ldb + s] : 0.0;
-                    any = any || bs[k] != 0.0;
-                }
-                if (any) {                                  // (an entry whose belief value is zero adds an exact zero)
-#pragma unroll
-                    for (int q = 0; q < SE_NO; ++q)
-                        if (q < no) {
-                            const double w = (double)mv.rto[((int64_t)(a * mv.O + o0 + q) * mv.R + r) * mv.S_pad + s];
-#pragma unroll
-                            for (int k = 0; k < SE_NB; ++k) acc[k][q] += bs[k] * w;
-                        }
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < SE_NB; ++k)
-#pragma unroll
-                for (int q = 0; q < SE_NO; ++q) {
+                for (int q = 0; q < TILE_NO; ++q) {
                     const double u = acc[k][q];
                     if (u != 0.0) {
                         zs[k][q] += u;
@@ -3004,9 +2913,9 @@ __global__ void __launch_bounds__(256) k_succ_entropy(const T* __restrict__ bel,
                 }
         }
 #pragma unroll
-        for (int k = 0; k < SE_NB; ++k)
+        for (int k = 0; k < TILE_NB; ++k)
 #pragma unroll
-            for (int q = 0; q < SE_NO; ++q) {
+            for (int q = 0; q < TILE_NO; ++q) {
                 zs[k][q] = wave_sum(zs[k][q]);
                 ns[k][q] = wave_sum(ns[k][q]);
             }
@@ -3014,16 +2923,16 @@ __global__ void __launch_bounds__(256) k_succ_entropy(const T* __restrict__ bel,
         if ((threadIdx.x & 63) == 0) {
             double* mine = red[threadIdx.x >> 6];
 #pragma unroll
-            for (int k = 0; k < SE_NB; ++k)
+            for (int k = 0; k < TILE_NB; ++k)
 #pragma unroll
-                for (int q = 0; q < SE_NO; ++q) {
-                    mine[(k * SE_NO + q) * 2] = zs[k][q];
-                    mine[(k * SE_NO + q) * 2 + 1] = ns[k][q];
+                for (int q = 0; q < TILE_NO; ++q) {
+                    mine[(k * TILE_NO + q) * 2] = zs[k][q];
+                    mine[(k * TILE_NO + q) * 2 + 1] = ns[k][q];
                 }
         }
         __syncthreads();
-        if ((int)threadIdx.x < 2 * SE_NB * SE_NO) {
-            const int i = threadIdx.x, k = i / (2 * SE_NO), q = (i >> 1) % SE_NO;
+        if ((int)threadIdx.x < 2 * TILE_NB * TILE_NO) {
+            const int i = threadIdx.x, k = i / (2 * TILE_NO), q = (i >> 1) % TILE_NO;
             if (k < nb && q < no) {
                 const double v = ((red[0][i] + red[1][i]) + red[2][i]) + red[3][i];
                 part[((((int64_t)blockIdx.x * B + b0 + k) * mv.A + a) * mv.O + o0 + q) * 2 + (i & 1)] = v;
@@ -3093,7 +3002,7 @@ hipError_t launch_infotaxis(const T* bel, int ldb, int B, ModelView<T> mv, const
     if (B <= 0) return hipSuccess;
     if (B > 65535 || mv.A > 65535 || mv.S > ldb || part == nullptr || g_out == nullptr || action_out == nullptr) return hipErrorInvalidValue;
     const int XB = succ_entropy_xblocks(mv.S);
-    hipLaunchKernelGGL(k_succ_entropy<T>, dim3(XB, (B + SE_NB - 1) / SE_NB, mv.A), dim3(256), 0, st, bel, ldb, B, mv, in_ptr, in_src,
+    hipLaunchKernelGGL(k_succ_entropy<T>, dim3(XB, (B + TILE_NB - 1) / TILE_NB, mv.A), dim3(256), 0, st, bel, ldb, B, mv, in_ptr, in_src,
                        part);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

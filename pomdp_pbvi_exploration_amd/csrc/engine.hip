@@ -2037,11 +2037,17 @@ class EngineT : public EngineBase {
         if ((rc = uq_mpart_.ensure(rows * (size_t)nblk * sizeof(double)))) return rc;
         UpperScratch ws{};
         if ((rc = upper_scratch((int64_t)rows, n_hit, &ws))) return rc;
+        BayesStep<T> bs = bayes_step(true);                 // the Bayes step of every (a, o), norm in block order, over uq_*
+        bs.act = bs.obs = nullptr;
+        bs.unnorm = uq_unnorm_.as<double>();
+        bs.mass_part = uq_mpart_.as<double>();
         for (int64_t b0 = 0; b0 < B_; b0 += nb) {
             const int cnt = (int)std::min(nb, B_ - b0);
-            double* mass = uq_mass_.as<double>() + b0 * AO;
-            HIPCHK(launch_upper_successors<T>(bel_.as<T>(), S_pad_, (int)b0, cnt, view(), in_ptr_.as<int32_t>(), in_src_.as<int32_t>(),
-                                              uq_unnorm_.as<double>(), uq_mpart_.as<double>(), mass, uq_succ_.as<T>(), stream_));
+            bs.every_ao_from = (int)b0;
+            bs.B = (int)(cnt * AO);
+            bs.mass = uq_mass_.as<double>() + b0 * AO;
+            HIPCHK(launch_belief_push<T>(bs, view(), nullptr, stream_));
+            HIPCHK(launch_belief_norm<T>(bs, S_, nullptr, uq_succ_.as<T>(), S_, stream_));
             HIPCHK(launch_upper_sawtooth<T>(uq_succ_.as<T>(), S_, (int)(cnt * AO), S_, nullptr, upper_store(), n_visible, n_hit, ws,
                                             uq_val_.as<double>() + b0 * AO, nullptr, nullptr, stream_));
         }

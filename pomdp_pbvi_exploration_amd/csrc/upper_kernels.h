@@ -40,15 +40,9 @@ hipError_t launch_upper_sawtooth(const T* rows, int ld, int n, int S, const int3
                                  int64_t n_hit, UpperScratch ws, double* out_value, int32_t* out_point, int32_t* out_hit,
                                  hipStream_t st);
 
-// Successor beliefs of engine rows [b0, b0 + nb) of `bel` for every (a, o): row j = ((b - b0) * A + a) * O + o of
-//   unnorm [nb*A*O][S]   u[s'] = sum over the inverse list of (a, s') of (double) b[s] * (double) RTO[s,a,o,r]  (k_belief_push's sum)
-//   mass   [nb*A*O]      the 256-state blocks' sums added in block order (launch_belief_push's fixed-order normaliser)
-//   succ   [nb*A*O][S]   (T)(u / mass): NaN rows where mass == 0, as pbvi_belief_update
-// mass_part [nb*A*O][ceil(S/256)] is scratch.  nb * A * O <= 65535.
-template <typename T>
-hipError_t launch_upper_successors(const T* bel, int ldb, int b0, int nb, ModelView<T> mv, const int32_t* in_ptr,
-                                   const int32_t* in_src, double* unnorm, double* mass_part, double* mass, T* succ, hipStream_t st);
-
+// The successors of pbvi_upper_q are rows of the Bayes step (backup_kernels.h: a BayesStep with every_ao_from, pushed with the
+// fixed-order norm and normalised with out_row == nullptr into [rows][S]): mass [B][A][O] is launch_belief_push's, value
+// [B][A][O] the sawtooth of the normalised rows.
 // Q[b,a] = sum_s b[s] ER[s,a] + gamma * sum_o mass[b,a,o] * value[b,a,o] (sequential over o; mass == 0 adds 0) for engine rows
 // b < B, written with p_obs = mass and succ_value = value to the caller's row perm[b]; action = first maximum of the row of Q
 // as written (a NaN never wins, a row of NaNs gives 0).  out_action / out_pobs / out_sval may be nullptr.

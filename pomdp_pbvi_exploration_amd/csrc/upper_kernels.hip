@@ -7,6 +7,7 @@
 // against one belief row, the point's entries read coalesced (int32 state, fp64 value), the row gathered at those states.
 // No atomics anywhere; every reduction has a fixed order, so a row's results do not depend on what else is in the launch.
 #include "upper_kernels.h"
+#include "successor.h"
 
 #include <cstdint>
 #include <limits>
@@ -14,22 +15,6 @@
 namespace pbvi {
 
 namespace {
-
-__device__ __forceinline__ double ub_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// Sum over the block (blockDim.x = 256) in a fixed order; every thread gets the result.  sh: >= 4 doubles.
-__device__ __forceinline__ double ub_block_sum(double v, double* sh) {
-    v = ub_wave_sum(v);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) sh[wid] = v;
-    __syncthreads();
-    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
 
 // v0 + gap * r with both roundings (never one fused multiply-add): the host restatement rounds twice
 __device__ __forceinline__ double ub_two_roundings(double v0, double gap, double r) {
@@ -56,9 +41,9 @@ __global__ void __launch_bounds__(256) k_ub_row(const T* __restrict__ rows, int 
         if (x != 0.0) cnt += 1.0;
         if (x != x) bad += 1.0;
     }
-    const double tot = ub_block_sum(acc, red);
-    const double n = ub_block_sum(cnt, red);                // (counts below 2^53 are exact in fp64)
-    const double nbad = ub_block_sum(bad, red);
+    const double tot = block_sum(acc, red);
+    const double n = block_sum(cnt, red);                // (counts below 2^53 are exact in fp64)
+    const double nbad = block_sum(bad, red);
     if (threadIdx.x == 0) {
         v0[blockIdx.x] = tot;
         bnnz[blockIdx.x] = nbad != 0.0 ? -1 : (int32_t)n;
@@ -187,67 +172,9 @@ hipError_t launch_upper_sawtooth(const T* rows, int ld, int n, int S, const int3
 }
 
 // ------------------------------------------------------------------------- //
-// pbvi_upper_q: the successors of every (belief, action, observation), materialised a chunk of beliefs at a time
+// pbvi_upper_q: the successors come from the Bayes-step launchers (launch_belief_push over every (a, o), launch_belief_norm);
+// their values from the sawtooth above; this folds them into Q.
 // ------------------------------------------------------------------------- //
-// k_belief_push with the (belief, action, observation) of a row read off its index: one block per (256 landing states, row).
-template <typename T>
-__global__ void __launch_bounds__(256) k_ub_succ_push(const T* __restrict__ bel, int ldb, int b0, ModelView<T> mv,
-                                                      const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ in_src,
-                                                      double* __restrict__ unnorm, double* __restrict__ mass_part) {
-    __shared__ double red[4];
-    const int j = blockIdx.y, sp = blockIdx.x * 256 + threadIdx.x;
-    const int o = j % mv.O, a = (j / mv.O) % mv.A, b = b0 + j / (mv.O * mv.A);
-    double u = 0.0;
-    if (sp < mv.S) {
-        const int32_t* ptr = in_ptr + (int64_t)a * (mv.S + 1);
-        const int32_t* src = in_src + (int64_t)a * mv.S * mv.R;
-        const T* rto = mv.rto + (int64_t)(a * mv.O + o) * mv.R * mv.S_pad;
-        const T* brow = bel + (int64_t)b * ldb;
-        for (int k = ptr[sp]; k < ptr[sp + 1]; ++k) {
-            const int e = src[k];                           // e = s * R + r
-            const int s = e / mv.R, r = e - s * mv.R;
-            u += (double)brow[s] * (double)rto[(int64_t)r * mv.S_pad + s];
-        }
-        unnorm[(int64_t)j * mv.S + sp] = u;
-    }
-    const double tot = ub_block_sum(u, red);
-    if (threadIdx.x == 0) mass_part[(int64_t)j * gridDim.x + blockIdx.x] = tot;
-}
-
-// mass[j] = the blocks' partial masses in block order (k_mass_fold's sum).  One thread per row.
-__global__ void __launch_bounds__(256) k_ub_succ_fold(int rows, int nblk, const double* __restrict__ mass_part,
-                                                      double* __restrict__ mass) {
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= rows) return;
-    double tot = 0.0;
-    for (int x = 0; x < nblk; ++x) tot += mass_part[(int64_t)j * nblk + x];
-    mass[j] = tot;
-}
-
-template <typename T>
-__global__ void __launch_bounds__(256) k_ub_succ_norm(const double* __restrict__ unnorm, const double* __restrict__ mass, int S,
-                                                      T* __restrict__ succ) {
-    const int j = blockIdx.y, s = blockIdx.x * 256 + threadIdx.x;
-    if (s >= S) return;
-    succ[(int64_t)j * S + s] = (T)(unnorm[(int64_t)j * S + s] / mass[j]);   // mass 0 -> NaN, as k_belief_norm
-}
-
-template <typename T>
-hipError_t launch_upper_successors(const T* bel, int ldb, int b0, int nb, ModelView<T> mv, const int32_t* in_ptr,
-                                   const int32_t* in_src, double* unnorm, double* mass_part, double* mass, T* succ, hipStream_t st) {
-    const int64_t rows = (int64_t)nb * mv.A * mv.O;
-    if (rows <= 0) return hipSuccess;
-    if (rows > 65535 || mv.S > ldb) return hipErrorInvalidValue;
-    const dim3 grid((mv.S + 255) / 256, (unsigned)rows);
-    hipLaunchKernelGGL(k_ub_succ_push<T>, grid, dim3(256), 0, st, bel, ldb, b0, mv, in_ptr, in_src, unnorm, mass_part);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_ub_succ_fold, dim3(((int)rows + 255) / 256), dim3(256), 0, st, (int)rows, (int)grid.x, mass_part, mass);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_ub_succ_norm<T>, grid, dim3(256), 0, st, unnorm, mass, mv.S, succ);
-    return hipGetLastError();
-}
-
 // One block per belief (engine row b, caller row d = perm[b]).  Per action the immediate reward b . ER[:, a] in the block's
 // fixed order, then thread 0 adds the observations in order and writes the row; it takes the row's first maximum last.
 template <typename T>
@@ -264,7 +191,7 @@ __global__ void __launch_bounds__(256) k_upper_q_finish(const T* __restrict__ be
         const T* er = mv.er + (int64_t)a * mv.S_pad;
         double acc = 0.0;
         for (int s = threadIdx.x; s < mv.S; s += 256) acc += (double)row[s] * (double)er[s];
-        const double rew = ub_block_sum(acc, red);
+        const double rew = block_sum(acc, red);
         if (threadIdx.x == 0) {
             double tail = 0.0;
             for (int o = 0; o < mv.O; ++o) {
@@ -305,8 +232,6 @@ hipError_t launch_upper_q_finish(const T* bel, int ldb, int B, ModelView<T> mv, 
 #define PBVI_UPPER_INST(T)                                                                                                   \
     template hipError_t launch_upper_sawtooth<T>(const T*, int, int, int, const int32_t*, UpperStore, int64_t, int64_t,      \
                                                  UpperScratch, double*, int32_t*, int32_t*, hipStream_t);                    \
-    template hipError_t launch_upper_successors<T>(const T*, int, int, int, ModelView<T>, const int32_t*, const int32_t*,    \
-                                                   double*, double*, double*, T*, hipStream_t);                              \
     template hipError_t launch_upper_q_finish<T>(const T*, int, int, ModelView<T>, const int32_t*, double, const double*,    \
                                                  const double*, double*, int32_t*, double*, double*, hipStream_t);
 PBVI_UPPER_INST(float)

@@ -314,6 +314,21 @@ def upper_q_first_argmax(Q: np.ndarray) -> np.ndarray:
     return np.argmax(np.where(np.isnan(Q), -np.inf, Q), axis=1)
 
 
+def _successor_rows(b, rs, rto):
+    """The un-normalised Bayes successors of the rows of ``b [n,S]`` (fp64), one ``(a, o, u [n,S])`` per action and
+    observation in that order: ``u[i,s'] = sum_{(s,r): rs[s,a,r] = s'} b[i,s] rto[s,a,o,r]`` with ``np.bincount``, whose
+    accumulation order (ascending ``s * R + r``) is the order of the device's inverse lists.  ``rs [S,A,R]`` int64,
+    ``rto [S,A,O,R]`` already cast to the engine's number format and widened."""
+    n, S = b.shape
+    R = rs.shape[2]
+    base = np.arange(n)[:, None] * S
+    for a in range(rs.shape[1]):
+        idx = (rs[:, a, :].reshape(1, S * R) + base).ravel()                     # entry s * R + r lands on rs[s, a, r]
+        for o in range(rto.shape[2]):
+            w = (b[:, :, None] * rto[None, :, a, o, :]).reshape(n, S * R)
+            yield a, o, np.bincount(idx, weights=w.ravel(), minlength=n * S).reshape(n, S)
+
+
 def upper_q_numpy(model, points, values, gaps, corner, beliefs, gamma: float, n_visible: Union[int, None] = None,
                   n_hit: Union[int, None] = None, table_dtype=np.float64):
     """The action values the HSVI descent is greedy for, on the host: what ``pbvi_upper_q`` computes on the device.  With
@@ -338,21 +353,16 @@ def upper_q_numpy(model, points, values, gaps, corner, beliefs, gamma: float, n_
     Z = np.zeros((n, A, O))
     sval = np.full((n, A, O), np.nan)
     shit = np.full((n, A, O), -1, dtype=np.int64)
-    base = np.arange(n)[:, None] * S
-    for a in range(A):
-        idx = (rs[:, a, :].reshape(1, S * R) + base).ravel()                     # entry s * R + r lands on rs[s, a, r]
-        tail = np.zeros(n)
-        for o in range(O):
-            w = (b[:, :, None] * rto[None, :, a, o, :]).reshape(n, S * R)
-            u = np.bincount(idx, weights=w.ravel(), minlength=n * S).reshape(n, S)
-            z = np.sum(u, axis=1)
-            Z[:, a, o] = z
-            ok = z != 0
-            if ok.any():
-                succ = (u[ok] / z[ok, None]).astype(table_dtype).astype(np.float64)
-                sval[ok, a, o], _, shit[ok, a, o] = sawtooth_numpy(points, values, gaps, corner, succ, n_visible, n_hit)
-                tail[ok] += z[ok] * sval[ok, a, o]
-        Q[:, a] += gamma * tail
+    tail = np.zeros((n, A))
+    for a, o, u in _successor_rows(b, rs, rto):
+        z = np.sum(u, axis=1)
+        Z[:, a, o] = z
+        ok = z != 0
+        if ok.any():
+            succ = (u[ok] / z[ok, None]).astype(table_dtype).astype(np.float64)
+            sval[ok, a, o], _, shit[ok, a, o] = sawtooth_numpy(points, values, gaps, corner, succ, n_visible, n_hit)
+            tail[ok, a] += z[ok] * sval[ok, a, o]
+    Q += gamma * tail
     return Q, upper_q_first_argmax(Q), Z, sval, shit
 
 
@@ -1743,20 +1753,14 @@ def _infotaxis_terms(model, beliefs, table_dtype=np.float64, rows_at_once: Union
     G, MG, Z = np.zeros((n, A)), np.zeros((n, A)), np.zeros((n, A, O))
     step = max(1, (1 << 22) // (S * R)) if rows_at_once is None else int(rows_at_once)     # ~32 MiB of weights at a time
     for i0 in range(0, n, step):
-        bb = b[i0:i0 + step]
-        k = bb.shape[0]
-        base = np.arange(k)[:, None] * S
-        for a in range(A):
-            idx = (rs[:, a, :].reshape(1, S * R) + base).ravel()                 # entry s * R + r lands on rs[s, a, r]
-            for o in range(O):
-                w = (bb[:, :, None] * rto[None, :, a, o, :]).reshape(k, S * R)
-                u = np.bincount(idx, weights=w.ravel(), minlength=k * S).reshape(k, S)
-                ulu = _xlogx(u)
-                z = np.sum(u, axis=1)
-                zlz = _xlogx(z)
-                Z[i0:i0 + k, a, o] = z
-                G[i0:i0 + k, a] += zlz - np.sum(ulu, axis=1)
-                MG[i0:i0 + k, a] += np.abs(zlz) + np.sum(np.abs(ulu), axis=1)
+        i1 = min(i0 + step, n)
+        for a, o, u in _successor_rows(b[i0:i1], rs, rto):
+            ulu = _xlogx(u)
+            z = np.sum(u, axis=1)
+            zlz = _xlogx(z)
+            Z[i0:i1, a, o] = z
+            G[i0:i1, a] += zlz - np.sum(ulu, axis=1)
+            MG[i0:i1, a] += np.abs(zlz) + np.sum(np.abs(ulu), axis=1)
     blb = _xlogx(b)
     return G, Z, -np.sum(blb, axis=1), MG, np.sum(np.abs(blb), axis=1)
 
