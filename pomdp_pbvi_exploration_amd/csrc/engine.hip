@@ -213,7 +213,7 @@ struct DevBuf : DevView {
         return PBVI_OK;
     }
     void release() {
-        if (p && !windowed) {
+        if (p) {
             (void)hipFree(p);
             mem.bytes -= (int64_t)cap;
             DevMem::live -= (int64_t)cap;
@@ -228,25 +228,7 @@ struct DevBuf : DevView {
         std::swap(cap, o.cap);
     }
 
-    // While a Window lives, its buffer stands for memory inside another buffer (value_max_store runs the pipeline of the
-    // resident block on windows of the belief store): ensure() finds it large enough whatever is asked, release() leaves
-    // the memory alone, and the buffer's own allocation is back when the Window goes out of scope.
-    class Window {
-        DevBuf& b_;
-        const DevView own_;
-       public:
-        explicit Window(DevBuf& b) : b_(b), own_(b) {}
-        void point(void* q) { b_.stand_for({q, ~(size_t)0 >> 1}, true); }
-        ~Window() { b_.stand_for(own_, false); }
-    };
-
    private:
-    bool windowed = false;
-    void stand_for(const DevView& v, bool w) {
-        p = v.p;
-        cap = v.cap;
-        windowed = w;
-    }
     // the fresh allocation at p is this buffer's
     void adopt(size_t bytes) {
         cap = bytes;
@@ -1004,6 +986,33 @@ struct RolloutCall {
     uint8_t* out_lost = nullptr;               // [B] or NULL
 };
 
+// The resident belief block and what is derived from it.  `ver` names the rows the block holds: replaced() is the one
+// place that moves it (an emptied block is a replaced one), and every derived datum is stamped with the version it
+// describes (0: none).  New rows therefore make everything derived stale at once; nobody keeps a list of what to reset.
+struct BeliefBlock {
+    DevBuf rows;                      // [B_pad][S_pad] the beliefs in engine order; the pad rows are zero
+    DevBuf keys, perm;                // [B] sort keys; caller's row of engine row i (sorted blocks)
+    DevBuf rowflags;                  // [B][k_tiles] 1 = caller's belief row b has mass in K tile kt
+    DevBuf nzA;                       // [B_pad / 256][k_tiles] zero map of the score GEMM's row blocks
+    DevBuf plane;                     // fp32: the rows' split plane for the split score GEMM (split_bf16.h)
+    DevBuf btl, btc;                  // [B][k_tiles], [B] per-belief non-zero tile lists and their lengths
+    int64_t B = 0, B_pad = 0;
+    bool sorted = false;              // the rows are reordered (more than one row block of the score GEMM)
+    std::vector<int32_t> h_perm;      // the host's copy of perm, fetched on demand (EngineT::host_perm)
+    hipEvent_t ev_nzA = nullptr;      // recorded behind the pass that stamped nzA_ver: nzA is complete
+    uint64_t ver = 1;
+    // rowflags, nzA + ev_nzA, plane, btl / btc, the engine's dead triples (dead_), h_perm
+    uint64_t rowflags_ver = 0, nzA_ver = 0, plane_ver = 0, tiles_ver = 0, dead_ver = 0, host_perm_ver = 0;
+    explicit BeliefBlock(DevMem& m) : rows(m), keys(m), perm(m), rowflags(m), nzA(m), plane(m), btl(m), btc(m) {}
+    void replaced(int64_t b, int64_t b_pad, bool reordered) {
+        B = b;
+        B_pad = b_pad;
+        sorted = reordered;
+        ++ver;
+    }
+    void emptied() { replaced(0, 0, false); }
+};
+
 class EngineBase {
    public:
     virtual ~EngineBase() {}
@@ -1138,10 +1147,7 @@ class EngineT : public EngineBase {
     uint64_t screen_layout_seen_ = 0;                        // fp64 engines: layout / first row the screen's copy reflects
     int64_t screen_off_seen_ = 0;
     int64_t V_ = 0;
-    DevBuf bel_{mem_};
-    int64_t B_ = 0, B_pad_ = 0;
-    DevBuf belsp_{mem_};   // fp32: bel_'s split plane for the split score GEMM (split_bf16.h)
-    uint64_t belsp_ver_ = 0;                                 // the bel_ version belsp_ holds (0: none)
+    BeliefBlock blk_{mem_};                                  // the resident belief block and what is derived from it
     DevBuf gam_{mem_}, slabs_{mem_}, best_v_{mem_}, best_score_{mem_}, err_{mem_}, dead_{mem_}, queue_{mem_}, hcand_{mem_}, hncand_{mem_}, counters_{mem_, DevBuf::MODEL}, rdot_{mem_}, aqueue_{mem_}, keep_{mem_};
     // the backup's decision: actions, the belief reordering undone (f32, B > 256), K6 key dedup; fin_.rows holds the unique rows
     Decision fin_{mem_, counters_, CNT_UNIQUE};
@@ -1154,15 +1160,14 @@ class EngineT : public EngineBase {
     DevBuf scores_{mem_}, chain_max_{mem_, DevBuf::MODEL};
     std::vector<hipEvent_t> tile_ev_;
     int tile_ev_chunks_ = 0;
-    DevBuf stage_{mem_}, keys_{mem_}, perm_{mem_};   // belief reordering (f32, B > 256)
+    DevBuf stage_{mem_};   // beliefs_set: the caller's rows, padded, in front of the reordering
     DevBuf out_full_{mem_};   // the per-belief alpha' matrix expanded from fin_.rows (ensure_full)
     DevBuf store_[2]{{mem_}, {mem_}}, ids_{mem_};   // device row stores: [0] alpha-vectors, [1] beliefs
     int64_t store_rows_[2] = {0, 0};
     DevBuf in_ptr_{mem_, DevBuf::MODEL}, in_src_{mem_, DevBuf::MODEL}, bu_act_{mem_}, bu_obs_{mem_}, bu_row_{mem_}, bu_unnorm_{mem_}, bu_mass_{mem_}, bu_out_{mem_}, walk64_{mem_}, rto64_{mem_, DevBuf::MODEL};   // batched belief update
     std::vector<int32_t> h_rs_;                                // host copy of rs [A][R][S_pad] for the lazy CSC build
-    DevBuf btl_{mem_}, btc_{mem_}, val_exact_{mem_};   // per-belief non-zero tile lists; exact action values
+    DevBuf val_exact_{mem_};   // exact action values
     DevBuf bp_{mem_}, nzP_{mem_}, pmag_{mem_}, prd_{mem_};   // belief-side formulation: projected beliefs, tile map, magnitudes, b.ER
-    bool btl_valid_ = false;                                // btl_/btc_ describe the resident belief block
     bool vmax_exact_ = true;                                // f32 engines: re-score value_max's maxima in fp64
     // belief store as a GEMM operand in place (value_max_store): zero maps and tile lists kept per store row, extended
     // as rows are appended
@@ -1176,7 +1181,6 @@ class EngineT : public EngineBase {
     DevBuf keys_tmp_{mem_}, keys_act_{mem_}, keys_best_{mem_}, keys_rows_{mem_};   // unique-row keys out / rows from keys in (multi-GPU exchange)
     DevBuf acand_{mem_};   // [B][A] action inside the window (k_action_select -> k_refine_action)
     DevBuf q_{mem_}, q_res_{mem_}, q_act_{mem_};   // pbvi_q_values: q [B][A] in engine order / caller order, its argmax [B]
-    bool q_only_ = false, q_want_best_ = false;              // run_pipeline stops behind the refinement and runs launch_q_exact
     // pbvi_rollout: trajectories [T+1][n] states | [T][n] actions | [T][n] observations | [n] steps; the live simulations'
     // true states and trajectory rows (caller order, double-buffered across the done-filter), keep flags, the filter's
     // row map (+ 1 int: the survivor count), alpha_actions [V], end mask [S]
@@ -1225,16 +1229,10 @@ class EngineT : public EngineBase {
     const int32_t* res_best_ = nullptr;
     int64_t res_unique_ = 0;
     bool full_valid_ = false;
-    std::vector<int32_t> h_perm_;
     std::vector<int32_t> h_bu_;                              // bayes_upload's host side: act | obs | row, engine order
-    bool h_perm_valid_ = false;                              // h_perm_ mirrors perm_ (fetched on demand, see host_perm)
-    bool sorted_ = false;
     const void* gam_pad_ptr_ = nullptr;                      // Gamma buffer / row count whose pad rows are zero
     int64_t gam_pad_N_ = -1;
     DevBuf scr_flag_{mem_, DevBuf::MODEL};   // fp64 engines: 1 = the screen's fp32 alpha copy holds an overflowed value
-    DevBuf rowflags_{mem_};   // [B][k_tiles] 1 = caller's belief row b has mass in K tile kt
-    uint64_t rowflags_ver_ = 0;                              // belief-block version rowflags_ describes
-    uint64_t nzA_ver_ = 0;                                   // belief-block version ev_nzA_ was recorded for
     PinnedBuf ids_pin_{pinned_, "hipHostFree(ids)"};         // staging of the ids of a store selection
     PinnedBuf words_{pinned_, "hipHostFree(flag)"};          // one PinnedWords, allocated by init(): see words()
     struct RunFetchDst {                                     // run_fetch: the small per-belief results travel with the pipeline's
@@ -1257,9 +1255,8 @@ class EngineT : public EngineBase {
     DevBuf e_rdot_{mem_}, e_slot_{mem_}, e_cnt_{mem_, DevBuf::MODEL};
     Decision prov_{mem_, e_cnt_, 0};
     hipEvent_t ev_ids_ = nullptr;
-    hipEvent_t ev_nzA_ = nullptr;                            // the resident block's zero map (nzA_) is complete
     DevBuf nzBw_{mem_, DevBuf::MODEL};   // [A*O][ceil(k_tiles/64)] support tiles of RTO as bit words
-    DevBuf nzB_{mem_, DevBuf::MODEL}, nzA_{mem_}, klist_{mem_}, kcount_{mem_}, nchunks_{mem_}, need_{mem_}, skws_{mem_};   // zero-tile bookkeeping of the f32 score GEMM
+    DevBuf nzB_{mem_, DevBuf::MODEL}, klist_{mem_}, kcount_{mem_}, nchunks_{mem_}, need_{mem_}, skws_{mem_};   // zero-tile bookkeeping of the f32 score GEMM
     DevBuf dense_{mem_, DevBuf::MODEL}, nzD_{mem_, DevBuf::MODEL}, nzAlpha_{mem_}, prod_{mem_}, klistD_{mem_}, kcountD_{mem_}, nchunksD_{mem_};   // dense projection mode
     int64_t rows_pad_s_ = 0, dense_pairs_ = 0;
     std::vector<int> h_kcountD_;
@@ -1289,7 +1286,6 @@ class EngineT : public EngineBase {
     std::vector<uint8_t> h_mat_;
     std::vector<int> h_vlist_;
     int64_t mat_V_ = -1;
-    uint64_t dead_ver_ = 0;                                  // belief-block version dead_ / btl_ / btc_ describe
     int64_t dead_pairs_ = 0, dead_count_ = 0;
     int* rf_counts_ = nullptr;                               // PinnedWords::deferred of the current backup
     bool last_deferred_nothing_ = false;                     // (the first backup of an engine reads the counts mid-pipeline)
@@ -1302,8 +1298,8 @@ class EngineT : public EngineBase {
     EngineT<float>* screen_ = nullptr;                       // fp64 engines: the fp32 screen (see ensure_screen)
     std::vector<int32_t> h_reach_ref_;                       // fp64 engines: the tables in the reference's layout, kept
     std::vector<double> h_rto_ref_, h_er_ref_;               //   to build the screen on first use
-    uint64_t alpha_ver_ = 1, bel_ver_ = 1;                   // bumped whenever alpha_ / bel_ change
-    uint64_t screen_alpha_seen_ = 0, screen_bel_seen_ = 0;
+    uint64_t alpha_ver_ = 1;                                 // bumped whenever alpha_ changes
+    uint64_t screen_alpha_seen_ = 0, screen_bel_seen_ = 0;   // the alpha_ver_ / blk_.ver the screen's copies reflect
 
     ~EngineT() override {
         (void)hipSetDevice(device_);
@@ -1631,34 +1627,34 @@ class EngineT : public EngineBase {
 
     // Belief block from rows on the device -- `src` [.][S_pad], row b of the block = src row (src_ids ? src_ids[b] : b) --
     // reordered, padded to the GEMM's 256-row blocks, with its zero-tile map.  Stream-ordered, no host synchronisation:
-    // the host's copy of the order (h_perm_) is fetched when a host-side consumer asks for it (host_perm).
+    // the host's copy of the order (blk_.h_perm) is fetched when a host-side consumer asks for it (host_perm).
     int beliefs_finish(int64_t B, const T* src, const int32_t* src_ids) {
         const int64_t Bp = round_up(B, GEMM_BM);
         const int k_tiles = S_pad_ / GEMM_BK;
-        int rc = bel_.ensure((size_t)Bp * S_pad_ * sizeof(T));
+        int rc = blk_.rows.ensure((size_t)Bp * S_pad_ * sizeof(T));
         if (rc) return rc;
-        if ((rc = rowflags_.ensure((size_t)B * k_tiles))) return rc;
-        if ((rc = keys_.ensure((size_t)B * sizeof(int32_t)))) return rc;
-        if ((rc = perm_.ensure((size_t)B * sizeof(int32_t)))) return rc;
-        if ((rc = nzA_.ensure((size_t)(Bp / GEMM_BM) * k_tiles))) return rc;
-        if (Bp > B) HIPCHK(hipMemsetAsync(bel_.as<T>() + (size_t)B * S_pad_, 0, (size_t)(Bp - B) * S_pad_ * sizeof(T), stream_));
+        if ((rc = blk_.rowflags.ensure((size_t)B * k_tiles))) return rc;
+        if ((rc = blk_.keys.ensure((size_t)B * sizeof(int32_t)))) return rc;
+        if ((rc = blk_.perm.ensure((size_t)B * sizeof(int32_t)))) return rc;
+        if ((rc = blk_.nzA.ensure((size_t)(Bp / GEMM_BM) * k_tiles))) return rc;
+        if (Bp > B) HIPCHK(hipMemsetAsync(blk_.rows.as<T>() + (size_t)B * S_pad_, 0, (size_t)(Bp - B) * S_pad_ * sizeof(T), stream_));
         // the split plane rides along with the gather once score_gemm has allocated it (the first split backup)
         uint32_t* plane = nullptr;
-        if (kF32 && split_mode_ != 0 && split_supported_ && belsp_.cap >= (size_t)Bp * S_pad_ * sizeof(float)) {
-            plane = belsp_.as<uint32_t>();
+        if (kF32 && split_mode_ != 0 && split_supported_ && blk_.plane.cap >= (size_t)Bp * S_pad_ * sizeof(float)) {
+            plane = blk_.plane.as<uint32_t>();
             if (Bp > B) HIPCHK(hipMemsetAsync(plane + (size_t)B * S_pad_, 0, (size_t)(Bp - B) * S_pad_ * sizeof(float), stream_));
         }
         static const bool no_sort = getenv("PBVI_NO_BELIEF_SORT") != nullptr;     // debug / A-B only
-        sorted_ = B > (kF32 ? GEMM_BM : 128) && !no_sort;     // more than one row block of the score GEMM
+        const bool sorted = B > (kF32 ? GEMM_BM : 128) && !no_sort;     // more than one row block of the score GEMM
         hipLaunchKernelGGL(k_row_flags<T>, dim3((unsigned)B), dim3(256), 0, stream_, src, S_pad_, src_ids, S_pad_, k_tiles,
-                           rowflags_.as<uint8_t>(), keys_.as<int32_t>());
+                           blk_.rowflags.as<uint8_t>(), blk_.keys.as<int32_t>());
         HIPCHK(hipGetLastError());
         const int32_t* perm = nullptr;
-        if (sorted_) {
-            hipLaunchKernelGGL(k_rank_sort, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, stream_, keys_.as<int32_t>(), (int)B,
-                               perm_.as<int32_t>());
+        if (sorted) {
+            hipLaunchKernelGGL(k_rank_sort, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, stream_, blk_.keys.as<int32_t>(), (int)B,
+                               blk_.perm.as<int32_t>());
             HIPCHK(hipGetLastError());
-            perm = perm_.as<int32_t>();
+            perm = blk_.perm.as<int32_t>();
         }
         // the zero map (the first rows of the grid) and the rows in that order, one launch
         constexpr int NS = 16 / (int)sizeof(T);
@@ -1667,38 +1663,33 @@ class EngineT : public EngineBase {
         for (int64_t r0 = 0, orr = or_rows; r0 < B; orr = 0) {
             const int64_t cnt = std::min<int64_t>(B - r0, 65535 - orr);
             hipLaunchKernelGGL(k_gather_rows_v<T>, dim3((S_pad_ / NS + 255) / 256, (unsigned)(cnt + orr)), dim3(256), 0, stream_, src,
-                               bel_.as<T>(), S_pad_, perm, src_ids, rowflags_.as<uint8_t>(), (int)B, k_tiles, nzA_.as<uint8_t>(), (int)orr,
+                               blk_.rows.as<T>(), S_pad_, perm, src_ids, blk_.rowflags.as<uint8_t>(), (int)B, k_tiles, blk_.nzA.as<uint8_t>(), (int)orr,
                                plane, (int)r0);
             HIPCHK(hipGetLastError());
             r0 += cnt;
         }
-        HIPCHK(new_event(&ev_nzA_, hipEventDisableTiming, "hipEventDestroy(nzA)"));
-        HIPCHK(hipEventRecord(ev_nzA_, stream_));
-        B_ = B;
-        B_pad_ = Bp;
-        ++bel_ver_;
-        rowflags_ver_ = bel_ver_;
-        nzA_ver_ = bel_ver_;
-        belsp_ver_ = plane != nullptr ? bel_ver_ : 0;
-        h_perm_valid_ = false;
+        HIPCHK(new_event(&blk_.ev_nzA, hipEventDisableTiming, "hipEventDestroy(nzA)"));
+        HIPCHK(hipEventRecord(blk_.ev_nzA, stream_));
+        blk_.replaced(B, Bp, sorted);
+        blk_.rowflags_ver = blk_.nzA_ver = blk_.ver;         // what this pass left beside the rows
+        blk_.plane_ver = plane != nullptr ? blk_.ver : 0;
         have_result_ = false;
-        btl_valid_ = false;
         return PBVI_OK;
     }
 
     PinnedWords& words() const { return *words_.as<PinnedWords>(); }
 
-    // h_perm_[i] = caller's index of engine row i (sorted blocks), for the host-side consumers of the order
+    // blk_.h_perm[i] = caller's index of engine row i (sorted blocks), for the host-side consumers of the order
     int host_perm() {
-        if (!sorted_ || h_perm_valid_) return PBVI_OK;
-        h_perm_.resize((size_t)B_);
-        HIPCHK(hipMemcpyAsync(h_perm_.data(), perm_.p, (size_t)B_ * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+        if (!blk_.sorted || blk_.host_perm_ver == blk_.ver) return PBVI_OK;
+        blk_.h_perm.resize((size_t)blk_.B);
+        HIPCHK(hipMemcpyAsync(blk_.h_perm.data(), blk_.perm.p, (size_t)blk_.B * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
         HIPCHK(hipStreamSynchronize(stream_));
-        h_perm_valid_ = true;
+        blk_.host_perm_ver = blk_.ver;
         return PBVI_OK;
     }
     // ... as Delivery::add_rows takes it, after host_perm(): nullptr where the rows lie in the caller's order already
-    const int32_t* caller_order() const { return sorted_ ? h_perm_.data() : nullptr; }
+    const int32_t* caller_order() const { return blk_.sorted ? blk_.h_perm.data() : nullptr; }
 
     int beliefs_set(const void* bel, int64_t B) override {
         if (B <= 0 || bel == nullptr) FAIL(PBVI_EINVAL, "beliefs_set: need B > 0 and a non-null array");
@@ -1740,9 +1731,7 @@ class EngineT : public EngineBase {
 
     // No belief block is resident (every simulation finished, or the engine starts over)
     void block_emptied() {
-        B_ = 0;
-        B_pad_ = 0;
-        sorted_ = false;
+        blk_.emptied();
         have_result_ = false;
     }
 
@@ -1760,10 +1749,10 @@ class EngineT : public EngineBase {
 
     // What belief_update and beliefs_advance refuse, in this order, and what both need before their first launch
     int bayes_begin(const std::string& who, const int32_t* act, const int32_t* obs, bool other_null) {
-        if (B_ <= 0) FAIL(PBVI_EINVAL, who + ": no belief block resident");
+        if (blk_.B <= 0) FAIL(PBVI_EINVAL, who + ": no belief block resident");
         if (!act || !obs || other_null) FAIL(PBVI_EINVAL, who + ": NULL argument");
         if ((int64_t)S_ * R_ > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, who + ": S*R exceeds int32");
-        for (int64_t b = 0; b < B_; ++b)
+        for (int64_t b = 0; b < blk_.B; ++b)
             if (act[b] < 0 || act[b] >= A_ || obs[b] < 0 || obs[b] >= O_) FAIL(PBVI_EINVAL, who + ": action / observation out of range");
         HIPCHK(hipSetDevice(device_));
         return build_inverse_lists();
@@ -1772,12 +1761,12 @@ class EngineT : public EngineBase {
     // act / obs / row (row may be NULL) arrive in the caller's belief order and the resident block may be sorted: engine row i
     // holds the caller's row c.  Into bu_act_ / bu_obs_ / bu_row_ in engine order; h_bu_ is read until the stream is synchronised.
     int bayes_upload(const int32_t* act, const int32_t* obs, const int32_t* row) {
-        int rc = bayes_ensure(B_, false);
+        int rc = bayes_ensure(blk_.B, false);
         if (rc || (rc = host_perm())) return rc;
-        const size_t n = (size_t)B_;
+        const size_t n = (size_t)blk_.B;
         h_bu_.resize(3 * n);
         for (size_t i = 0; i < n; ++i) {
-            const size_t c = sorted_ ? (size_t)h_perm_[i] : i;
+            const size_t c = blk_.sorted ? (size_t)blk_.h_perm[i] : i;
             h_bu_[i] = act[c];
             h_bu_[n + i] = obs[c];
             h_bu_[2 * n + i] = row ? row[c] : (int32_t)i;
@@ -1790,9 +1779,9 @@ class EngineT : public EngineBase {
 
     BayesStep<T> bayes_step(bool fixed_order) {
         BayesStep<T> bs{};
-        bs.bel = bel_.as<T>();
+        bs.bel = blk_.rows.as<T>();
         bs.ldb = S_pad_;
-        bs.B = (int)B_;
+        bs.B = (int)blk_.B;
         bs.in_ptr = in_ptr_.as<int32_t>();
         bs.in_src = in_src_.as<int32_t>();
         bs.act = bu_act_.as<int32_t>();
@@ -1807,7 +1796,7 @@ class EngineT : public EngineBase {
     // their masses, of the rows with out_row[b] >= 0 (nullptr: all).  fixed_order: the norm is summed in block order instead of
     // with atomics on the zeroed masses.
     int bayes_push(const int32_t* out_row, bool fixed_order) {
-        if (!fixed_order) HIPCHK(hipMemsetAsync(bu_mass_.p, 0, (size_t)B_ * sizeof(double), stream_));
+        if (!fixed_order) HIPCHK(hipMemsetAsync(bu_mass_.p, 0, (size_t)blk_.B * sizeof(double), stream_));
         HIPCHK(launch_belief_push<T>(bayes_step(fixed_order), view(), out_row, stream_));
         return PBVI_OK;
     }
@@ -1827,13 +1816,13 @@ class EngineT : public EngineBase {
     int belief_update(const int32_t* act, const int32_t* obs, void* out) override {
         int rc = bayes_begin("belief_update", act, obs, !out);
         if (rc) return rc;
-        if ((rc = bu_out_.ensure((size_t)B_ * S_ * sizeof(T)))) return rc;
+        if ((rc = bu_out_.ensure((size_t)blk_.B * S_ * sizeof(T)))) return rc;
         if ((rc = bayes_upload(act, obs, nullptr))) return rc;
         // computed in engine order into bu_out_, then gathered back into the caller's order
         if ((rc = bayes_push(nullptr, false))) return rc;
         HIPCHK(launch_belief_norm<T>(bayes_step(false), S_, nullptr, bu_out_.as<T>(), S_, stream_));
         out_.begin();
-        out_.add_rows(out, bu_out_.p, (size_t)S_ * sizeof(T), (size_t)B_, (size_t)S_ * sizeof(T), caller_order());
+        out_.add_rows(out, bu_out_.p, (size_t)S_ * sizeof(T), (size_t)blk_.B, (size_t)S_ * sizeof(T), caller_order());
         return out_.finish();
     }
 
@@ -1843,9 +1832,9 @@ class EngineT : public EngineBase {
     int beliefs_advance(const int32_t* act, const int32_t* obs, const uint8_t* keep, int64_t* out_B) override {
         int rc = bayes_begin("beliefs_advance", act, obs, false);
         if (rc) return rc;
-        std::vector<int32_t> dst((size_t)B_);           // caller row -> surviving row
+        std::vector<int32_t> dst((size_t)blk_.B);           // caller row -> surviving row
         int64_t nb = 0;
-        for (int64_t c = 0; c < B_; ++c) dst[(size_t)c] = (!keep || keep[c]) ? (int32_t)nb++ : -1;
+        for (int64_t c = 0; c < blk_.B; ++c) dst[(size_t)c] = (!keep || keep[c]) ? (int32_t)nb++ : -1;
         if (out_B) *out_B = nb;
         if (nb == 0) {                                   // every simulation finished
             block_emptied();
@@ -1868,14 +1857,14 @@ class EngineT : public EngineBase {
         if ((int64_t)S_ * R_ > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "infotaxis: S*R exceeds int32");
         int rc = build_inverse_lists();
         if (rc) return rc;
-        const size_t ba = (size_t)B_ * A_;
+        const size_t ba = (size_t)blk_.B * A_;
         if ((rc = it_part_.ensure((size_t)succ_entropy_xblocks(S_) * ba * O_ * 2 * sizeof(double)))) return rc;
         if ((rc = it_g_.ensure(ba * sizeof(double)))) return rc;
-        if ((rc = it_act_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+        if ((rc = it_act_.ensure((size_t)blk_.B * sizeof(int32_t)))) return rc;
         if (want_p_obs && (rc = it_pobs_.ensure(ba * O_ * sizeof(double)))) return rc;
-        if (want_entropy && (rc = it_h_.ensure((size_t)B_ * sizeof(double)))) return rc;
-        HIPCHK(launch_infotaxis<T>(bel_.as<T>(), S_pad_, (int)B_, view(), in_ptr_.as<int32_t>(), in_src_.as<int32_t>(),
-                                   sorted_ ? perm_.as<int32_t>() : nullptr, it_part_.as<double>(), it_g_.as<double>(),
+        if (want_entropy && (rc = it_h_.ensure((size_t)blk_.B * sizeof(double)))) return rc;
+        HIPCHK(launch_infotaxis<T>(blk_.rows.as<T>(), S_pad_, (int)blk_.B, view(), in_ptr_.as<int32_t>(), in_src_.as<int32_t>(),
+                                   blk_.sorted ? blk_.perm.as<int32_t>() : nullptr, it_part_.as<double>(), it_g_.as<double>(),
                                    it_act_.as<int32_t>(), want_p_obs ? it_pobs_.as<double>() : nullptr,
                                    want_entropy ? it_h_.as<double>() : nullptr, stream_));
         return PBVI_OK;
@@ -1883,14 +1872,14 @@ class EngineT : public EngineBase {
 
     int infotaxis(double* out_g, int32_t* out_action, double* out_p_obs, double* out_entropy) override {
         if (!out_g) FAIL(PBVI_EINVAL, "infotaxis: NULL out_g");
-        if (B_ <= 0) FAIL(PBVI_EINVAL, "infotaxis: no belief block resident (call pbvi_beliefs_set)");
+        if (blk_.B <= 0) FAIL(PBVI_EINVAL, "infotaxis: no belief block resident (call pbvi_beliefs_set)");
         HIPCHK(hipSetDevice(device_));
         int rc = infotaxis_device(out_p_obs != nullptr, out_entropy != nullptr);
         if (rc) return rc;
-        return out_.deliver({{out_g, it_g_.p, (size_t)B_ * A_ * sizeof(double)},
-                             {out_action, it_act_.p, (size_t)B_ * sizeof(int32_t)},
-                             {out_p_obs, it_pobs_.p, (size_t)B_ * A_ * O_ * sizeof(double)},
-                             {out_entropy, it_h_.p, (size_t)B_ * sizeof(double)}});
+        return out_.deliver({{out_g, it_g_.p, (size_t)blk_.B * A_ * sizeof(double)},
+                             {out_action, it_act_.p, (size_t)blk_.B * sizeof(int32_t)},
+                             {out_p_obs, it_pobs_.p, (size_t)blk_.B * A_ * O_ * sizeof(double)},
+                             {out_entropy, it_h_.p, (size_t)blk_.B * sizeof(double)}});
     }
 
     // ---- HSVI upper bound (pbvi_upper_reset / _append / _count / _bound / _q) ---- //
@@ -1969,7 +1958,7 @@ class EngineT : public EngineBase {
     // What pbvi_upper_bound and pbvi_upper_q refuse, in this order
     int upper_begin(const std::string& who, int64_t n_visible, int64_t n_hit, bool null_output) {
         if (null_output) FAIL(PBVI_EINVAL, who + ": NULL required output");
-        if (B_ <= 0) FAIL(PBVI_EINVAL, who + ": no belief block resident (call pbvi_beliefs_set)");
+        if (blk_.B <= 0) FAIL(PBVI_EINVAL, who + ": no belief block resident (call pbvi_beliefs_set)");
         if (!ub_corner_) FAIL(PBVI_EINVAL, who + ": no corner values set (call pbvi_upper_reset)");
         if (n_visible < 0 || n_visible > n_hit) FAIL(PBVI_EINVAL, who + ": need 0 <= n_visible <= n_hit");
         if (n_hit > ub_count_) FAIL(PBVI_EINVAL, who + ": n_hit exceeds the points in the store");
@@ -1995,16 +1984,16 @@ class EngineT : public EngineBase {
         int rc = upper_begin("upper_bound", n_visible, n_hit, !out_value);
         if (rc) return rc;
         UpperScratch ws{};
-        if ((rc = upper_scratch(B_, n_hit, &ws))) return rc;
-        if ((rc = ub_rv_.ensure((size_t)B_ * sizeof(double)))) return rc;
-        if ((rc = ub_rp_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
-        if ((rc = ub_rh_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
-        HIPCHK(launch_upper_sawtooth<T>(bel_.as<T>(), S_pad_, (int)B_, S_, sorted_ ? perm_.as<int32_t>() : nullptr, upper_store(),
+        if ((rc = upper_scratch(blk_.B, n_hit, &ws))) return rc;
+        if ((rc = ub_rv_.ensure((size_t)blk_.B * sizeof(double)))) return rc;
+        if ((rc = ub_rp_.ensure((size_t)blk_.B * sizeof(int32_t)))) return rc;
+        if ((rc = ub_rh_.ensure((size_t)blk_.B * sizeof(int32_t)))) return rc;
+        HIPCHK(launch_upper_sawtooth<T>(blk_.rows.as<T>(), S_pad_, (int)blk_.B, S_, blk_.sorted ? blk_.perm.as<int32_t>() : nullptr, upper_store(),
                                         n_visible, n_hit, ws, ub_rv_.as<double>(), ub_rp_.as<int32_t>(), ub_rh_.as<int32_t>(),
                                         stream_));
-        return out_.deliver({{out_value, ub_rv_.p, (size_t)B_ * sizeof(double)},
-                             {out_point, ub_rp_.p, (size_t)B_ * sizeof(int32_t)},
-                             {out_hit, ub_rh_.p, (size_t)B_ * sizeof(int32_t)}});
+        return out_.deliver({{out_value, ub_rv_.p, (size_t)blk_.B * sizeof(double)},
+                             {out_point, ub_rp_.p, (size_t)blk_.B * sizeof(int32_t)},
+                             {out_hit, ub_rh_.p, (size_t)blk_.B * sizeof(int32_t)}});
     }
 
     // The bound-greedy action values of the resident block (pbvi_upper_q): the normalised successors of every (belief, action,
@@ -2018,11 +2007,11 @@ class EngineT : public EngineBase {
         if ((int64_t)S_ * R_ > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "upper_q: S*R exceeds int32");
         if (AO > 65535) FAIL(PBVI_EUNSUPPORTED, "upper_q: A*O exceeds 65535");
         if ((rc = build_inverse_lists())) return rc;
-        const size_t all = (size_t)B_ * (size_t)AO;
+        const size_t all = (size_t)blk_.B * (size_t)AO;
         if ((rc = uq_mass_.ensure(all * sizeof(double)))) return rc;
         if ((rc = uq_val_.ensure(all * sizeof(double)))) return rc;
-        if ((rc = uq_q_.ensure((size_t)B_ * A_ * sizeof(double)))) return rc;
-        if ((rc = uq_act_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+        if ((rc = uq_q_.ensure((size_t)blk_.B * A_ * sizeof(double)))) return rc;
+        if ((rc = uq_act_.ensure((size_t)blk_.B * sizeof(int32_t)))) return rc;
         if (out_p_obs && (rc = uq_pobs_.ensure(all * sizeof(double)))) return rc;
         if (out_succ_value && (rc = uq_sval_.ensure(all * sizeof(double)))) return rc;
         // bytes one belief's successors take: un-normalised and normalised rows, block masses, the sawtooth's scratch
@@ -2030,7 +2019,7 @@ class EngineT : public EngineBase {
         const int64_t per_belief = AO * ((int64_t)S_ * (int64_t)(sizeof(double) + sizeof(T)) + nblk * 8 + 12 + chunks * 16);
         const int64_t held = (int64_t)(uq_unnorm_.cap + uq_succ_.cap + uq_mpart_.cap + ub_v0_.cap + ub_bnnz_.cap + ub_pw_.cap +
                                        ub_pi_.cap + ub_ph_.cap);
-        const int64_t nb = std::max<int64_t>(1, std::min({B_, (int64_t)65535 / AO, (room() / 2 + held) / per_belief}));
+        const int64_t nb = std::max<int64_t>(1, std::min({blk_.B, (int64_t)65535 / AO, (room() / 2 + held) / per_belief}));
         const size_t rows = (size_t)nb * (size_t)AO;
         if ((rc = uq_unnorm_.ensure(rows * S_ * sizeof(double)))) return rc;
         if ((rc = uq_succ_.ensure(rows * S_ * sizeof(T)))) return rc;
@@ -2041,8 +2030,8 @@ class EngineT : public EngineBase {
         bs.act = bs.obs = nullptr;
         bs.unnorm = uq_unnorm_.as<double>();
         bs.mass_part = uq_mpart_.as<double>();
-        for (int64_t b0 = 0; b0 < B_; b0 += nb) {
-            const int cnt = (int)std::min(nb, B_ - b0);
+        for (int64_t b0 = 0; b0 < blk_.B; b0 += nb) {
+            const int cnt = (int)std::min(nb, blk_.B - b0);
             bs.every_ao_from = (int)b0;
             bs.B = (int)(cnt * AO);
             bs.mass = uq_mass_.as<double>() + b0 * AO;
@@ -2051,12 +2040,12 @@ class EngineT : public EngineBase {
             HIPCHK(launch_upper_sawtooth<T>(uq_succ_.as<T>(), S_, (int)(cnt * AO), S_, nullptr, upper_store(), n_visible, n_hit, ws,
                                             uq_val_.as<double>() + b0 * AO, nullptr, nullptr, stream_));
         }
-        HIPCHK(launch_upper_q_finish<T>(bel_.as<T>(), S_pad_, (int)B_, view(), sorted_ ? perm_.as<int32_t>() : nullptr, gamma,
+        HIPCHK(launch_upper_q_finish<T>(blk_.rows.as<T>(), S_pad_, (int)blk_.B, view(), blk_.sorted ? blk_.perm.as<int32_t>() : nullptr, gamma,
                                         uq_mass_.as<double>(), uq_val_.as<double>(), uq_q_.as<double>(), uq_act_.as<int32_t>(),
                                         out_p_obs ? uq_pobs_.as<double>() : nullptr, out_succ_value ? uq_sval_.as<double>() : nullptr,
                                         stream_));
-        return out_.deliver({{out_q, uq_q_.p, (size_t)B_ * A_ * sizeof(double)},
-                             {out_action, uq_act_.p, (size_t)B_ * sizeof(int32_t)},
+        return out_.deliver({{out_q, uq_q_.p, (size_t)blk_.B * A_ * sizeof(double)},
+                             {out_action, uq_act_.p, (size_t)blk_.B * sizeof(int32_t)},
                              {out_p_obs, uq_pobs_.p, all * sizeof(double)},
                              {out_succ_value, uq_sval_.p, all * sizeof(double)}});
     }
@@ -2140,14 +2129,14 @@ class EngineT : public EngineBase {
         if (env && call.end_observation >= O_) FAIL(PBVI_EINVAL, "rollout_env: end_observation is not below O");
         if (env && call.shifts && env_kind_ != ENV_FRAMES) FAIL(PBVI_EINVAL, "rollout_env: shifts are for a frame environment, and a table is set");
         if (uses_alpha && V_ <= 0) FAIL(PBVI_EINVAL, "rollout: no alpha set resident (call pbvi_alpha_set)");
-        if (B_ <= 0) FAIL(PBVI_EINVAL, "rollout: no belief block resident (call pbvi_beliefs_set)");
+        if (blk_.B <= 0) FAIL(PBVI_EINVAL, "rollout: no belief block resident (call pbvi_beliefs_set)");
         if ((uses_alpha && !call.alpha_actions) || !call.start_states || !call.end_mask) FAIL(PBVI_EINVAL, "rollout: NULL argument");
         if (source != ROLLOUT_VALUE_MAX && source != ROLLOUT_Q && source != ROLLOUT_INFOTAXIS)
             FAIL(PBVI_EINVAL, "rollout: lookahead must be 0 or 1");
         if (n_steps < 1) FAIL(PBVI_EINVAL, "rollout: T must be at least 1");
         if (source == ROLLOUT_Q && mode_ != PBVI_SPARSE)
             FAIL(PBVI_EUNSUPPORTED, "rollout: lookahead = 1 is not available on a PBVI_DENSE engine (create it with PBVI_SPARSE)");
-        const int64_t n0 = B_;
+        const int64_t n0 = blk_.B;
         if (n_steps >= 0x7fffffff || (n_steps + 1) * n0 > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "rollout: T * B exceeds the int32 trajectory slot index");
         if ((int64_t)S_ * R_ > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "rollout: S*R exceeds int32");
         for (int64_t b = 0; b < n0; ++b)
@@ -2244,23 +2233,18 @@ class EngineT : public EngineBase {
         int oc = 0;
         for (int64_t t = 0; t < n_steps; ++t) {
             if (source == ROLLOUT_VALUE_MAX) {
-                if ((rc = value_max_device())) return rc;
+                if ((rc = value_max_device(resident()))) return rc;
                 rs.index = bv2_.as<int32_t>();                // engine row order, an alpha row: mapped through alpha_actions
             } else if (source == ROLLOUT_Q) {
-                q_only_ = true;
-                q_want_best_ = false;
-                rc = backup_run(call.gamma, 0, nullptr);
-                q_only_ = false;
-                have_result_ = have_bk_vmax_ = false;
-                if (rc) return rc;
+                if ((rc = run_q(call.gamma, false))) return rc;
                 rs.index = q_act_.as<int32_t>();              // caller row order, an action
             } else {
                 if ((rc = infotaxis_device(false, false))) return rc;
                 rs.index = it_act_.as<int32_t>();             // caller row order, an action
             }
-            rs.n = (int)B_;
+            rs.n = (int)blk_.B;
             rs.t = (int)t;
-            rs.perm = sorted_ ? perm_.as<int32_t>() : nullptr;
+            rs.perm = blk_.sorted ? blk_.perm.as<int32_t>() : nullptr;
             rs.orig = ro_orig_[oc].as<int32_t>();
             // draw (bu_row_: provisional, -1 = done), push of the rows not done, then the lost rule on their masses
             HIPCHK(launch_rollout_draw<T>(rs, view(), env ? &renv : nullptr, stream_));
@@ -2377,7 +2361,7 @@ class EngineT : public EngineBase {
     // argmax read (scores and magnitudes through its SlabView) and what it wrote (windows, first maxima, queue).
     int probe_capture(const SlabView<T>& sv, const ScoreIO& io, const ScoreStage<T>& out) {
         int rc;
-        const int64_t G = (int64_t)A_ * O_, pairs = B_ * G, n = pairs * V_;
+        const int64_t G = (int64_t)A_ * O_, pairs = blk_.B * G, n = pairs * V_;
         probe_seq_ = 0;                                      // (a stage that fails below leaves nothing to fetch)
         if (n > ((int64_t)1 << 24))
             FAIL(PBVI_EINVAL, "score probe: B * A * O * V = " + std::to_string(n) + " exceeds 2^24 (the probe is for tests)");
@@ -2389,7 +2373,7 @@ class EngineT : public EngineBase {
         if ((rc = probe_queue_.ensure((size_t)pairs * sizeof(int32_t)))) return rc;
         if ((rc = probe_dead_.ensure((size_t)pairs))) return rc;
         if ((rc = probe_words_.ensure(2 * sizeof(int)))) return rc;
-        HIPCHK(launch_score_probe<T>(sv, (int)V_, (int)G, (int)B_, probe_score_.as<double>(), probe_mag_.as<double>(), stream_));
+        HIPCHK(launch_score_probe<T>(sv, (int)V_, (int)G, (int)blk_.B, probe_score_.as<double>(), probe_mag_.as<double>(), stream_));
         HIPCHK(hipMemcpyAsync(probe_err_.p, io.err, (size_t)pairs * sizeof(double), hipMemcpyDeviceToDevice, stream_));
         HIPCHK(hipMemcpyAsync(probe_bs_.p, io.best_score, (size_t)pairs * sizeof(double), hipMemcpyDeviceToDevice, stream_));
         HIPCHK(hipMemcpyAsync(probe_bv_.p, io.best_v, (size_t)pairs * sizeof(int32_t), hipMemcpyDeviceToDevice, stream_));
@@ -2403,7 +2387,7 @@ class EngineT : public EngineBase {
         else HIPCHK(hipMemsetAsync(probe_dead_.p, 0, (size_t)pairs, stream_));
         if (out.chain != nullptr)
             HIPCHK(hipMemcpyAsync(probe_words_.as<int>() + 1, out.chain, sizeof(int), hipMemcpyDeviceToDevice, stream_));
-        probe_info_.B = B_;
+        probe_info_.B = blk_.B;
         probe_info_.G = G;
         probe_info_.V = V_;
         probe_info_.f64_pairs = out.f64_pairs;
@@ -2458,26 +2442,26 @@ class EngineT : public EngineBase {
                            : probe_copy_out(dims, scalars, score, mag, err, best_v, best_score, queue, dead);
         if (rc) return rc;
         if (perm) {                                          // caller's row of engine row i (the order is this engine's)
-            if (Bc != B_) FAIL(PBVI_EINVAL, "score probe: the belief block changed since the capture");
+            if (Bc != blk_.B) FAIL(PBVI_EINVAL, "score probe: the belief block changed since the capture");
             if ((rc = host_perm())) return rc;
-            for (int64_t i = 0; i < B_; ++i) perm[i] = sorted_ ? h_perm_[(size_t)i] : (int32_t)i;
+            for (int64_t i = 0; i < blk_.B; ++i) perm[i] = blk_.sorted ? blk_.h_perm[(size_t)i] : (int32_t)i;
         }
         return PBVI_OK;
     }
 
     // resident belief block back to the host (or a device buffer), caller order: [B][S] T
     int beliefs_fetch(void* out) override {
-        if (B_ <= 0) FAIL(PBVI_EINVAL, "beliefs_fetch: no belief block resident");
+        if (blk_.B <= 0) FAIL(PBVI_EINVAL, "beliefs_fetch: no belief block resident");
         if (!out) FAIL(PBVI_EINVAL, "beliefs_fetch: NULL argument");
         HIPCHK(hipSetDevice(device_));
         int rc = host_perm();
         if (rc) return rc;
         out_.begin();
-        out_.add_rows(out, bel_.p, (size_t)S_pad_ * sizeof(T), (size_t)B_, (size_t)S_ * sizeof(T), caller_order());
+        out_.add_rows(out, blk_.rows.p, (size_t)S_pad_ * sizeof(T), (size_t)blk_.B, (size_t)S_ * sizeof(T), caller_order());
         return out_.finish();
     }
 
-    int64_t beliefs_count() const override { return B_; }
+    int64_t beliefs_count() const override { return blk_.B; }
 
     // ---- device row stores ------------------------------------------------ //
     int64_t store_append(int which, const void* rows, int64_t n) override {
@@ -2691,16 +2675,12 @@ class EngineT : public EngineBase {
         snz_rows_ = sbt_rows_ = 0;
         walk_rows_ = 0;
         have_bk_vmax_ = false;
-        btl_valid_ = false;
-        h_perm_valid_ = false;
         mat_V_ = -1;
         gam_pad_ptr_ = nullptr;
         last_deferred_nothing_ = false;
         have_last_work_ = false;                             // (its lists were working buffers)
         probe_seq_ = 0;                                      // (the capture's buffers were working buffers)
         ++alpha_ver_;
-        ++bel_ver_;
-        belsp_ver_ = 0;
         if (screen_) {
             screen_alpha_seen_ = screen_bel_seen_ = 0;
             screen_layout_seen_ = 0;
@@ -2836,7 +2816,17 @@ class EngineT : public EngineBase {
                    int f64_route = -1 /* fp64 scoring: -1 by this GEMM's shape, 0 the plain kernel, n the MFMA tiles in n K parts */);
 
     int project_dense(double gamma);   // K1-dense: Gamma = gamma * alpha . D_ao^T as A*O (batched) GEMMs
-    int backup_run(double gamma, int flags, pbvi_stats_t* st) override;
+    // What the pipeline ends with: the backup's decision, or (pbvi_q_values, the rollout's lookahead) the exact Q values
+    // behind the refinement -- with the keys in caller order too where the caller asked for them
+    enum Mode { MODE_BACKUP, MODE_Q, MODE_Q_BEST };
+    int run_backup(double gamma, int flags, pbvi_stats_t* st, Mode mode);
+    int backup_run(double gamma, int flags, pbvi_stats_t* st) override { return run_backup(gamma, flags, st, MODE_BACKUP); }
+    // The Q mode: it overwrites the stage buffers of an earlier backup, whose result is no longer fetchable afterwards
+    int run_q(double gamma, bool want_best) {
+        const int rc = run_backup(gamma, 0, nullptr, want_best ? MODE_Q_BEST : MODE_Q);
+        have_result_ = have_bk_vmax_ = false;
+        return rc;
+    }
 
     // ---- the scoring stage (K1, K2, first-max), runnable on this engine or on an fp64 engine's fp32 screen ---- //
     bool choose_push(int64_t N) const;
@@ -2855,6 +2845,7 @@ class EngineT : public EngineBase {
         int flags;
         int64_t pairs;                    // B * A * O
         bool use_push, stats;             // belief-side formulation; the caller wants pbvi_stats_t
+        bool q_only, q_best;              // MODE_Q / MODE_Q_BEST: finish_q_values ends the call; it writes the keys too
         bool no_side = false;             // side_stream_work: PBVI_NO_SIDE_STREAM
         hipStream_t lists = nullptr;      // side_stream_work: where the GEMM's tile lists may be built, or nullptr
         bool early_wanted = false;        // side_stream_work: run_fetch's provisional decision applies to this call
@@ -2872,12 +2863,12 @@ class EngineT : public EngineBase {
     // the operands in their original precision, decides near-ties, actions and assembles the rows.  The stages follow in the
     // order in which run_pipeline calls them.
     template <typename TS>
-    int run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_stats_t* st) {
+    int run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_stats_t* st, Mode mode) {
         int rc;
         const int64_t N = (int64_t)A_ * O_ * (V_ + 1) + 2 * A_;   // per (a, o): alpha rows + magnitude row
-        const int64_t pairs = B_ * A_ * O_;
+        const int64_t pairs = blk_.B * A_ * O_;
         if (N > 0x7fffffff || pairs > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "backup_run: A*O*(V+1) or B*A*O exceeds int32");
-        Call<TS> c{scorer, gamma, flags, pairs, scorer.choose_push(N), st != nullptr};
+        Call<TS> c{scorer, gamma, flags, pairs, scorer.choose_push(N), st != nullptr, mode != MODE_BACKUP, mode == MODE_Q_BEST};
         last_formulation_ = c.use_push ? 2 : 1;
         if ((rc = prepare_backup(c))) return rc;
         if ((rc = side_stream_work(c))) return rc;
@@ -2886,16 +2877,16 @@ class EngineT : public EngineBase {
         if ((rc = provisional_decision(c))) return rc;
         if ((rc = refine(c))) return rc;
         if ((rc = hand_over_early_rows(c))) return rc;
-        if (q_only_) return finish_q_values(c);
+        if (c.q_only) return finish_q_values(c);
         if ((rc = decide(c))) return rc;
         if ((rc = speculative_repeat(c))) return rc;
         // 11. what the fetches and the next call need to know about this result
         if (c.windows && dead_count_ < 0) dead_count_ = c.h_cnt[CNT_DEAD];
         full_valid_ = false;
-        res_sorted_ = sorted_;
+        res_sorted_ = blk_.sorted;
         have_result_ = true;
         have_bk_vmax_ = c.use_push && !c.screened;
-        res_B_ = B_;
+        res_B_ = blk_.B;
         res_unique_ = c.h_cnt[CNT_UNIQUE];
         if (st) fill_stats(c, st);
         return PBVI_OK;
@@ -2912,12 +2903,12 @@ class EngineT : public EngineBase {
         if ((rc = hcand_.ensure((size_t)c.pairs * QCAND * sizeof(int32_t)))) return rc;
         if ((rc = hncand_.ensure((size_t)c.pairs * sizeof(int32_t)))) return rc;
         if ((rc = dead_.ensure((size_t)c.pairs))) return rc;
-        if ((rc = rdot_.ensure((size_t)B_ * A_ * 2 * sizeof(double)))) return rc;
-        if ((rc = aqueue_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
-        if ((rc = acand_.ensure((size_t)B_ * A_))) return rc;
+        if ((rc = rdot_.ensure((size_t)blk_.B * A_ * 2 * sizeof(double)))) return rc;
+        if ((rc = aqueue_.ensure((size_t)blk_.B * sizeof(int32_t)))) return rc;
+        if ((rc = acand_.ensure((size_t)blk_.B * A_))) return rc;
         // (the decision's buffers too in front of the scoring stage, which plans Gamma tiling with what is free)
-        if (!q_only_ && (rc = fin_.ensure(B_, c.pairs, (size_t)S_ * sizeof(T), sorted_))) return rc;
-        if ((rc = keep_.ensure((size_t)B_))) return rc;
+        if (!c.q_only && (rc = fin_.ensure(blk_.B, c.pairs, (size_t)S_ * sizeof(T), blk_.sorted))) return rc;
+        if ((rc = keep_.ensure((size_t)blk_.B))) return rc;
         if (c.windows && (rc = out_.reserve(256))) return rc;      // the pinned bounce buffer of the fetches that follow, allocated while the stream is idle
         HIPCHK(hipMemsetAsync(counters_.p, 0, CNT_SLOTS * sizeof(int), stream_));
         HIPCHK(hipEventRecord(ev_[0], stream_));
@@ -2939,35 +2930,34 @@ class EngineT : public EngineBase {
         c.lists = no_side ? nullptr : (lists_on_side ? side : stream3_);
         // (the tile lists need the block's zero map only: where the block was indexed just now they do not wait for its gather)
         if (c.lists != nullptr && c.lists != side)
-            HIPCHK(hipStreamWaitEvent(c.lists, (!c.screened && ev_nzA_ != nullptr && nzA_ver_ == bel_ver_) ? ev_nzA_ : ev_fork_, 0));
+            HIPCHK(hipStreamWaitEvent(c.lists, (!c.screened && blk_.ev_nzA != nullptr && blk_.nzA_ver == blk_.ver) ? blk_.ev_nzA : ev_fork_, 0));
         if (c.windows) {   // exact, from the supports of the ORIGINAL operands (an fp32 copy may have flushed tiny values to zero)
-            if ((rc = btl_.ensure((size_t)B_ * k_tiles * sizeof(int32_t)))) return rc;
-            if ((rc = btc_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
-            if ((rc = val_exact_.ensure((size_t)B_ * A_ * (1 + O_) * ACTION_SPLIT * sizeof(double)))) return rc;
+            if ((rc = blk_.btl.ensure((size_t)blk_.B * k_tiles * sizeof(int32_t)))) return rc;
+            if ((rc = blk_.btc.ensure((size_t)blk_.B * sizeof(int32_t)))) return rc;
+            if ((rc = val_exact_.ensure((size_t)blk_.B * A_ * (1 + O_) * ACTION_SPLIT * sizeof(double)))) return rc;
             // Dead triples and the per-belief tile lists are a function of the belief block and the model alone: computed on
             // the first backup of a block, kept for the following ones (a solve backs a block up once; update_passes > 1,
             // the belief-dominance loops of the notebooks and the benchmark back the same block up again and again).  Like
             // the block's sort order and zero-tile map they index the INPUT; nothing of a backup's result is kept.
             static const bool no_cache = getenv("PBVI_NO_DEAD_CACHE") != nullptr;       // debug / A-B only
-            if (dead_ver_ != bel_ver_ || !btl_valid_ || dead_pairs_ != c.pairs || no_cache) {
-                const bool have_flags = rowflags_ver_ == bel_ver_ && rowflags_.p != nullptr;   // left by the block's indexing pass
-                HIPCHK(launch_dead<T>(bel_.as<T>(), S_pad_, (int)B_, view(), nzBw_.as<unsigned long long>(), k_tiles, dead_.as<uint8_t>(),
-                                      btl_.as<int32_t>(), btc_.as<int32_t>(), counters_.as<int>() + CNT_DEAD, side,
-                                      have_flags ? rowflags_.as<uint8_t>() : nullptr,
-                                      have_flags && sorted_ ? perm_.as<int32_t>() : nullptr));
-                btl_valid_ = true;
-                dead_ver_ = bel_ver_;
+            if (blk_.dead_ver != blk_.ver || blk_.tiles_ver != blk_.ver || dead_pairs_ != c.pairs || no_cache) {
+                const bool have_flags = blk_.rowflags_ver == blk_.ver && blk_.rowflags.p != nullptr;   // left by the block's indexing pass
+                HIPCHK(launch_dead<T>(blk_.rows.as<T>(), S_pad_, (int)blk_.B, view(), nzBw_.as<unsigned long long>(), k_tiles, dead_.as<uint8_t>(),
+                                      blk_.btl.as<int32_t>(), blk_.btc.as<int32_t>(), counters_.as<int>() + CNT_DEAD, side,
+                                      have_flags ? blk_.rowflags.as<uint8_t>() : nullptr,
+                                      have_flags && blk_.sorted ? blk_.perm.as<int32_t>() : nullptr));
+                blk_.tiles_ver = blk_.dead_ver = blk_.ver;
                 dead_pairs_ = c.pairs;
                 dead_count_ = -1;                                // read back with this call's counters
             }
         }
         if (c.use_push) {   // b . ER[:,a] in f64 (the alpha-side gets it from Gamma's reward rows)
-            if ((rc = prd_.ensure((size_t)B_ * A_ * sizeof(double)))) return rc;
-            HIPCHK(launch_rdot<T>(bel_.as<T>(), S_pad_, (int)B_, view(), c.windows ? btl_.as<int32_t>() : nullptr,
-                                  c.windows ? btc_.as<int32_t>() : nullptr, prd_.as<double>(), side));
+            if ((rc = prd_.ensure((size_t)blk_.B * A_ * sizeof(double)))) return rc;
+            HIPCHK(launch_rdot<T>(blk_.rows.as<T>(), S_pad_, (int)blk_.B, view(), c.windows ? blk_.btl.as<int32_t>() : nullptr,
+                                  c.windows ? blk_.btc.as<int32_t>() : nullptr, prd_.as<double>(), side));
         }
         // (run_fetch's provisional pipeline: its counters are cleared here, beside the projection, not in front of its kernels)
-        c.early_wanted = c.windows && !q_only_ && early_.rows != nullptr && !(c.flags & PBVI_BELIEF_DOMINANCE) && early_.cap >= B_ && !no_side;
+        c.early_wanted = c.windows && !c.q_only && early_.rows != nullptr && !(c.flags & PBVI_BELIEF_DOMINANCE) && early_.cap >= blk_.B && !no_side;
         if (c.early_wanted) {
             if ((rc = e_cnt_.ensure(4 * sizeof(int)))) return rc;
             HIPCHK(hipMemsetAsync(e_cnt_.p, 0, 4 * sizeof(int), side));
@@ -3023,14 +3013,14 @@ class EngineT : public EngineBase {
         // call waits for (the slabs stay as they are until the next GEMM; K5 is not run with this formulation's extras
         // pending -- it joins first, below)
         int rc;
-        if ((rc = vmax_bk_.ensure((size_t)B_ * sizeof(double)))) return rc;
+        if ((rc = vmax_bk_.ensure((size_t)blk_.B * sizeof(double)))) return rc;
         hipStream_t xs = c.no_side ? stream_ : stream2_;
         if (xs != stream_) {
             HIPCHK(hipEventRecord(ev_xr_[0], stream_));
             HIPCHK(hipStreamWaitEvent(xs, ev_xr_[0], 0));
         }
-        hipLaunchKernelGGL(k_extra_rowmax<TS>, dim3((unsigned)((B_ + 3) / 4)), dim3(256), 0, xs, c.sc.sv, c.sc.extra_row0, (int)B_,
-                           (int)V_, sorted_ ? perm_.as<int32_t>() : nullptr, vmax_bk_.as<double>());
+        hipLaunchKernelGGL(k_extra_rowmax<TS>, dim3((unsigned)((blk_.B + 3) / 4)), dim3(256), 0, xs, c.sc.sv, c.sc.extra_row0, (int)blk_.B,
+                           (int)V_, blk_.sorted ? blk_.perm.as<int32_t>() : nullptr, vmax_bk_.as<double>());
         HIPCHK(hipGetLastError());
         if (xs != stream_) {
             HIPCHK(hipEventRecord(ev_xr_[1], xs));
@@ -3047,20 +3037,20 @@ class EngineT : public EngineBase {
         d.res_act = d.act.as<int32_t>();
         d.res_best = best_v_.as<int32_t>();
         // results to the caller's belief order, then K6: dedup by (a*, v*) key
-        if (sorted_) {
-            hipLaunchKernelGGL(k_unpermute, dim3((unsigned)B_), dim3(64), 0, stream_, (int)B_, AO, perm_.as<int32_t>(), d.act.as<int32_t>(),
+        if (blk_.sorted) {
+            hipLaunchKernelGGL(k_unpermute, dim3((unsigned)blk_.B), dim3(64), 0, stream_, (int)blk_.B, AO, blk_.perm.as<int32_t>(), d.act.as<int32_t>(),
                                best_v_.as<int32_t>(), d.act_res.as<int32_t>(), d.best_res.as<int32_t>());
             HIPCHK(hipGetLastError());
             d.res_act = d.act_res.as<int32_t>();
             d.res_best = d.best_res.as<int32_t>();
         } else if (snapshot) {                                   // (one row block: the keys as they are now)
-            HIPCHK(hipMemcpyAsync(d.best_res.p, best_v_.p, (size_t)B_ * AO * sizeof(int32_t), hipMemcpyDeviceToDevice, stream_));
+            HIPCHK(hipMemcpyAsync(d.best_res.p, best_v_.p, (size_t)blk_.B * AO * sizeof(int32_t), hipMemcpyDeviceToDevice, stream_));
             d.res_best = d.best_res.as<int32_t>();
         }
-        HIPCHK(launch_dedup((int)B_, A_, O_, d.res_act, d.res_best, d.rep.as<int32_t>(), d.uniq.as<int32_t>(), d.inv.as<int32_t>(),
+        HIPCHK(launch_dedup((int)blk_.B, A_, O_, d.res_act, d.res_best, d.rep.as<int32_t>(), d.uniq.as<int32_t>(), d.inv.as<int32_t>(),
                             d.slot.as<int32_t>(), d.count(), stream_));
         // K3: alpha' rows of the unique keys only
-        HIPCHK(launch_assemble<T>(alpha_.as<T>(), S_pad_, view(), gamma, d.res_act, d.res_best, d.uniq.as<int32_t>(), d.count(), (int)B_,
+        HIPCHK(launch_assemble<T>(alpha_.as<T>(), S_pad_, view(), gamma, d.res_act, d.res_best, d.uniq.as<int32_t>(), d.count(), (int)blk_.B,
                                   d.rows.as<T>(), S_, stream_));
         return PBVI_OK;
     }
@@ -3076,16 +3066,16 @@ class EngineT : public EngineBase {
         early_.used = false;
         if (!c.early_wanted) return PBVI_OK;
         int rc;
-        if ((rc = prov_.ensure(B_, c.pairs, (size_t)S_ * sizeof(T), true))) return rc;
-        if ((rc = e_rdot_.ensure((size_t)B_ * A_ * 2 * sizeof(double)))) return rc;
-        if ((rc = e_slot_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+        if ((rc = prov_.ensure(blk_.B, c.pairs, (size_t)S_ * sizeof(T), true))) return rc;
+        if ((rc = e_rdot_.ensure((size_t)blk_.B * A_ * 2 * sizeof(double)))) return rc;
+        if ((rc = e_slot_.ensure((size_t)blk_.B * sizeof(int32_t)))) return rc;
         for (hipEvent_t& ev : early_.ev) HIPCHK(new_event(&ev, hipEventDisableTiming, "hipEventDestroy(early)"));
         // The provisional decision itself is 40 us of small kernels: they run HERE, on the main stream in front of the
         // refinement (which rewrites best_v / best_score in place), and only the copy -- 8 MB over PCIe, ~150 us, few blocks
         // -- goes to the side stream.  (Snapshots of the three arrays + the whole provisional pipeline beside the
         // refinement cost it 0.13 ms: a net loss.)
-        HIPCHK(launch_action<TS>((int)B_, c.scorer.view(), c.sc.sv, c.sc.rd_col0, c.sc.tol_rel, c.sc.chain, best_score_.as<double>(), err_.as<double>(),
-                                 e_rdot_.as<double>(), e_rdot_.as<double>() + (size_t)B_ * A_, prov_.act.as<int32_t>(), nullptr, nullptr, stream_,
+        HIPCHK(launch_action<TS>((int)blk_.B, c.scorer.view(), c.sc.sv, c.sc.rd_col0, c.sc.tol_rel, c.sc.chain, best_score_.as<double>(), err_.as<double>(),
+                                 e_rdot_.as<double>(), e_rdot_.as<double>() + (size_t)blk_.B * A_, prov_.act.as<int32_t>(), nullptr, nullptr, stream_,
                                  c.io.tol_extra, nullptr, c.sc.split));
         if ((rc = decision_tail(prov_, c.gamma, true))) return rc;
         HIPCHK(hipEventRecord(early_.ev[0], stream_));
@@ -3104,7 +3094,7 @@ class EngineT : public EngineBase {
 
     // the grid-wide passes over what the per-entry pass deferred (rf_counts_, read by the host)
     int refine_deferred(double gamma, const RefineWork& work) {
-        HIPCHK(launch_refine_deferred<T>(true, (int)V_, A_ * O_, bel_.as<T>(), S_pad_, alpha_.as<T>(), S_pad_, view(), gamma,
+        HIPCHK(launch_refine_deferred<T>(true, (int)V_, A_ * O_, blk_.rows.as<T>(), S_pad_, alpha_.as<T>(), S_pad_, view(), gamma,
                                          best_v_.as<int32_t>(), best_score_.as<double>(), err_.as<double>(), work,
                                          rf_counts_[0], rf_counts_[1], stream_));
         return PBVI_OK;
@@ -3149,9 +3139,9 @@ class EngineT : public EngineBase {
         // (not with the belief-dominance test: its own value-max refinement re-uses the work-list buffers, so the
         // deferred entries of this one have to be finished first)
         // (nor for pbvi_q_values, whose one stage behind the refinement needs the final best_v)
-        c.speculate = !no_spec && !q_only_ && last_deferred_nothing_ && work.items_v != nullptr && !(c.flags & PBVI_BELIEF_DOMINANCE);
-        HIPCHK((launch_refine_scan<T, TS>(true, c.sc.sv, (int)V_, A_ * O_, (int)c.pairs, queue_.as<int32_t>(), c.io.qcount, bel_.as<T>(), S_pad_,
-                                          alpha_.as<T>(), S_pad_, view(), c.gamma, btl_.as<int32_t>(), btc_.as<int32_t>(),
+        c.speculate = !no_spec && !c.q_only && last_deferred_nothing_ && work.items_v != nullptr && !(c.flags & PBVI_BELIEF_DOMINANCE);
+        HIPCHK((launch_refine_scan<T, TS>(true, c.sc.sv, (int)V_, A_ * O_, (int)c.pairs, queue_.as<int32_t>(), c.io.qcount, blk_.rows.as<T>(), S_pad_,
+                                          alpha_.as<T>(), S_pad_, view(), c.gamma, blk_.btl.as<int32_t>(), blk_.btc.as<int32_t>(),
                                           nzB_.as<uint8_t>(), best_v_.as<int32_t>(), best_score_.as<double>(), err_.as<double>(),
                                           counters_.as<int>() + CNT_REFINE_CAND, work, rf_counts_, stream_)));
         if (!c.speculate && work.items_v != nullptr) {
@@ -3180,15 +3170,15 @@ class EngineT : public EngineBase {
         return PBVI_OK;
     }
 
-    // the tile lists of the resident block (btl_ / btc_) exist: from the beliefs alone, where k_dead did not leave them
+    // the tile lists of the resident block (blk_.btl / blk_.btc) exist: from the beliefs alone, where k_dead did not leave them
     int ensure_belief_tiles() {
-        if (btl_valid_) return PBVI_OK;
+        if (blk_.tiles_ver == blk_.ver) return PBVI_OK;
         int rc;
         const int k_tiles = S_pad_ / GEMM_BK;
-        if ((rc = btl_.ensure((size_t)B_ * k_tiles * sizeof(int32_t)))) return rc;
-        if ((rc = btc_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
-        HIPCHK(launch_belief_tiles<T>(bel_.as<T>(), S_pad_, (int)B_, S_, k_tiles, btl_.as<int32_t>(), btc_.as<int32_t>(), stream_));
-        btl_valid_ = true;
+        if ((rc = blk_.btl.ensure((size_t)blk_.B * k_tiles * sizeof(int32_t)))) return rc;
+        if ((rc = blk_.btc.ensure((size_t)blk_.B * sizeof(int32_t)))) return rc;
+        HIPCHK(launch_belief_tiles<T>(blk_.rows.as<T>(), S_pad_, (int)blk_.B, S_, k_tiles, blk_.btl.as<int32_t>(), blk_.btc.as<int32_t>(), stream_));
+        blk_.tiles_ver = blk_.ver;
         return PBVI_OK;
     }
 
@@ -3215,14 +3205,14 @@ class EngineT : public EngineBase {
         int rc;
         if (c.xr_pending) HIPCHK(hipStreamWaitEvent(stream_, ev_xr_[1], 0));       // (the side stream still reads this call's slabs)
         if ((rc = ensure_belief_tiles())) return rc;   // pure fp64 scoring: k_dead did not run; the same lists from the beliefs alone
-        if ((rc = q_.ensure((size_t)B_ * A_ * sizeof(double)))) return rc;
-        if ((rc = q_res_.ensure((size_t)B_ * A_ * sizeof(double)))) return rc;
-        if ((rc = q_act_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
-        if (q_want_best_ && (rc = fin_.best_res.ensure((size_t)c.pairs * sizeof(int32_t)))) return rc;
-        HIPCHK(launch_q_exact<T>(bel_.as<T>(), S_pad_, (int)B_, alpha_.as<T>(), S_pad_, (int)V_, view(), c.gamma, btl_.as<int32_t>(),
-                                 btc_.as<int32_t>(), best_v_.as<int32_t>(), c.windows ? dead_.as<uint8_t>() : nullptr,
-                                 sorted_ ? perm_.as<int32_t>() : nullptr, q_.as<double>(), q_res_.as<double>(), q_act_.as<int32_t>(),
-                                 q_want_best_ ? fin_.best_res.as<int32_t>() : nullptr, stream_));
+        if ((rc = q_.ensure((size_t)blk_.B * A_ * sizeof(double)))) return rc;
+        if ((rc = q_res_.ensure((size_t)blk_.B * A_ * sizeof(double)))) return rc;
+        if ((rc = q_act_.ensure((size_t)blk_.B * sizeof(int32_t)))) return rc;
+        if (c.q_best && (rc = fin_.best_res.ensure((size_t)c.pairs * sizeof(int32_t)))) return rc;
+        HIPCHK(launch_q_exact<T>(blk_.rows.as<T>(), S_pad_, (int)blk_.B, alpha_.as<T>(), S_pad_, (int)V_, view(), c.gamma, blk_.btl.as<int32_t>(),
+                                 blk_.btc.as<int32_t>(), best_v_.as<int32_t>(), c.windows ? dead_.as<uint8_t>() : nullptr,
+                                 blk_.sorted ? blk_.perm.as<int32_t>() : nullptr, q_.as<double>(), q_res_.as<double>(), q_act_.as<int32_t>(),
+                                 c.q_best ? fin_.best_res.as<int32_t>() : nullptr, stream_));
         if ((rc = end_call(c.screened, false, false, c.h_cnt))) return rc;
         if (c.windows && dead_count_ < 0) dead_count_ = c.h_cnt[CNT_DEAD];    // k_dead counted this block's dead triples in this call
         return PBVI_OK;
@@ -3238,14 +3228,14 @@ class EngineT : public EngineBase {
         int* aqcount = counters_.as<int>() + CNT_ACTION_QUEUE;
         bool publish = false;
         // K4: action
-        double* rdot_err = rdot_.as<double>() + (size_t)B_ * A_;
-        HIPCHK(launch_action<TS>((int)B_, c.scorer.view(), sc.sv, sc.rd_col0, sc.tol_rel, sc.chain, best_score_.as<double>(),
+        double* rdot_err = rdot_.as<double>() + (size_t)blk_.B * A_;
+        HIPCHK(launch_action<TS>((int)blk_.B, c.scorer.view(), sc.sv, sc.rd_col0, sc.tol_rel, sc.chain, best_score_.as<double>(),
                                  err_.as<double>(), rdot_.as<double>(), rdot_err, fin_.act.as<int32_t>(),
                                  c.windows ? aqueue_.as<int32_t>() : nullptr, aqcount, stream_, c.io.tol_extra,
                                  c.windows ? acand_.as<uint8_t>() : nullptr, sc.split));
         if (c.windows)
-            HIPCHK(launch_refine_action<T>(bel_.as<T>(), S_pad_, (int)B_, alpha_.as<T>(), S_pad_, view(), c.gamma,
-                                           btl_.as<int32_t>(), btc_.as<int32_t>(), aqueue_.as<int32_t>(), aqcount, rdot_.as<double>(), rdot_err, best_v_.as<int32_t>(),
+            HIPCHK(launch_refine_action<T>(blk_.rows.as<T>(), S_pad_, (int)blk_.B, alpha_.as<T>(), S_pad_, view(), c.gamma,
+                                           blk_.btl.as<int32_t>(), blk_.btc.as<int32_t>(), aqueue_.as<int32_t>(), aqcount, rdot_.as<double>(), rdot_err, best_v_.as<int32_t>(),
                                            best_score_.as<double>(), err_.as<double>(), val_exact_.as<double>(),
                                            fin_.act.as<int32_t>(), stream_, acand_.as<uint8_t>()));
         HIPCHK(hipEventRecord(ev_[5], stream_));
@@ -3255,7 +3245,7 @@ class EngineT : public EngineBase {
         if (early_.used) {   // final keys against the provisional ones whose rows are on their way (or there) already
             HIPCHK(hipStreamWaitEvent(stream_, early_.ev[1], 0));          // (the provisional count and rows are complete)
             HIPCHK(hipMemsetAsync(e_cnt_.as<int>() + 1, 0, 2 * sizeof(int), stream_));
-            hipLaunchKernelGGL(k_match_rows<T>, dim3((unsigned)std::min<int64_t>(B_, 2048)), dim3(256), 0, stream_, AO, O_, fin_.count(),
+            hipLaunchKernelGGL(k_match_rows<T>, dim3((unsigned)std::min<int64_t>(blk_.B, 2048)), dim3(256), 0, stream_, AO, O_, fin_.count(),
                                fin_.uniq.as<int32_t>(), res_action_, res_best_, prov_.uniq.as<int32_t>(), prov_.res_act, prov_.res_best,
                                e_cnt_.as<int>(), (int)early_.cap, e_slot_.as<int32_t>(), fin_.rows.as<T>(), (T*)early_.rows, (int64_t)S_);
             HIPCHK(hipGetLastError());
@@ -3271,24 +3261,24 @@ class EngineT : public EngineBase {
         }
         // K5: belief dominance (keep is written in caller order)
         if (c.flags & PBVI_BELIEF_DOMINANCE) {
-            if ((rc = value_max_device())) return rc;
-            HIPCHK(launch_keep<T>(bel_.as<T>(), S_pad_, fin_.rows.as<T>(), S_, (int)B_, S_, bs2_.as<double>(), fin_.inv.as<int32_t>(),
-                                  sorted_ ? perm_.as<int32_t>() : nullptr, keep_.as<uint8_t>(), stream_));
+            if ((rc = value_max_device(resident()))) return rc;
+            HIPCHK(launch_keep<T>(blk_.rows.as<T>(), S_pad_, fin_.rows.as<T>(), S_, (int)blk_.B, S_, bs2_.as<double>(), fin_.inv.as<int32_t>(),
+                                  blk_.sorted ? blk_.perm.as<int32_t>() : nullptr, keep_.as<uint8_t>(), stream_));
         } else {
-            HIPCHK(hipMemsetAsync(keep_.p, 1, (size_t)B_, stream_));
+            HIPCHK(hipMemsetAsync(keep_.p, 1, (size_t)blk_.B, stream_));
         }
         RunFetchDst& dst = early_.dst;
         dst.queued = false;
         if (publish) {                                       // run_fetch into page-locked arrays: one kernel stores everything small
-            hipLaunchKernelGGL(k_publish, dim3((unsigned)((B_ + 255) / 256)), dim3(256), 0, stream_, (int)B_, e_slot_.as<int32_t>(),
+            hipLaunchKernelGGL(k_publish, dim3((unsigned)((blk_.B + 255) / 256)), dim3(256), 0, stream_, (int)blk_.B, e_slot_.as<int32_t>(),
                                fin_.inv.as<int32_t>(), res_action_, (int32_t*)dst.slot, (int32_t*)dst.index, (int32_t*)dst.action,
                                counters_.as<int>(), e_cnt_.as<int>(), (c.screened && scr_flag_.p) ? scr_flag_.as<int>() : nullptr, &words());
             HIPCHK(hipGetLastError());
             dst.queued = true;
         } else if (early_.used && dst.slot != nullptr) {     // run_fetch: slots, index, actions (best, keep) with this read-back
             out_.begin();
-            out_.add(dst.slot, e_slot_.p, (size_t)B_ * sizeof(int32_t));
-            if ((rc = out_add_small((size_t)B_, dst.index, dst.action, dst.best, dst.keep))) return rc;
+            out_.add(dst.slot, e_slot_.p, (size_t)blk_.B * sizeof(int32_t));
+            if ((rc = out_add_small((size_t)blk_.B, dst.index, dst.action, dst.best, dst.keep))) return rc;
             dst.queued = true;
         }
         return end_call(c.screened, publish, true, c.h_cnt);
@@ -3351,7 +3341,7 @@ class EngineT : public EngineBase {
                 st->project_flops_executed = kt_sum * 2LL * GEMM_BM * GEMM_BN * GEMM_BK;
             }
         }
-        st->score_flops = 2 * B_ * (int64_t)S_ * AO * V_;
+        st->score_flops = 2 * blk_.B * (int64_t)S_ * AO * V_;
         int64_t kt_sum = 0;                                  // the GEMM's list lengths (none where it kept no lists)
         for (size_t i = 0; i < c.n_kcount; ++i) kt_sum += c.h_kcount[i];
         if (c.windows) {
@@ -3435,7 +3425,7 @@ class EngineT : public EngineBase {
     int run_fetch(double gamma, int flags, pbvi_stats_t* st, void* out_rows, int64_t cap_rows, int32_t* out_slot, int32_t* out_index,
                   int32_t* out_action, int32_t* out_best, uint8_t* out_keep, int64_t* n_unique, int64_t* n_slots) override {
         if (!out_rows || !out_slot || !out_index || !out_action) FAIL(PBVI_EINVAL, "backup_run_fetch: NULL destination");
-        if (cap_rows < B_) FAIL(PBVI_EINVAL, "backup_run_fetch: out_rows must have room for one row per belief");
+        if (cap_rows < blk_.B) FAIL(PBVI_EINVAL, "backup_run_fetch: out_rows must have room for one row per belief");
         if (!is_pinned_host_pointer(out_rows)) FAIL(PBVI_EINVAL, "backup_run_fetch: out_rows must be page-locked host memory (pbvi_host_alloc)");
         early_.rows = out_rows;
         early_.cap = cap_rows;
@@ -3651,47 +3641,53 @@ class EngineT : public EngineBase {
         return keep_from_counts(d_cnt, h_out, keep);
     }
 
-    // exact (f64-refined) max_v b.alpha_v of the resident blocks into bs2_/bv2_
-    int value_max_device();
-    void note_vmax_route(int route, int bn, int k_parts, int64_t pairs) {
+    // What value_max_device scores: B rows (the GEMM reads zero rows up to the next multiple of its row block behind
+    // them) with their zero map, and the rows' tile lists for the fp64 re-scoring -- nullptr: the resident block's, built
+    // where they are missing (ensure_belief_tiles)
+    struct Operand {
+        const T* rows;
+        int64_t B;
+        const uint8_t* nzA;
+        const int32_t *btl, *btc;
+    };
+    Operand resident() const { return {blk_.rows.as<T>(), blk_.B, blk_.nzA.as<uint8_t>(), nullptr, nullptr}; }
+    // exact (f64-refined) max_v b.alpha_v of the operand's rows into bs2_/bv2_
+    int value_max_device(const Operand& x);
+    void note_vmax_route(int route, int bn, int k_parts, int64_t rows, int64_t pairs) {
         vmax_route_[0] = route;
         vmax_route_[1] = bn;
         vmax_route_[2] = k_parts;
-        vmax_route_[3] = B_;
+        vmax_route_[3] = rows;
         vmax_route_[4] = V_;
         vmax_route_[5] = pairs;
         vmax_route_[6] += 1;
     }
 
     int value_max(double* out_value, int32_t* out_index) override {
-        if (V_ <= 0 || B_ <= 0) FAIL(PBVI_EINVAL, "value_max: need a resident alpha set and belief block");
+        if (V_ <= 0 || blk_.B <= 0) FAIL(PBVI_EINVAL, "value_max: need a resident alpha set and belief block");
         HIPCHK(hipSetDevice(device_));
-        int rc = value_max_device();
+        int rc = value_max_device(resident());
         if (rc) return rc;
         if ((rc = host_perm())) return rc;  // device results are in sorted belief order
         out_.begin();
-        out_.add_rows(out_value, bs2_.p, sizeof(double), (size_t)B_, sizeof(double), caller_order());
-        out_.add_rows(out_index, bv2_.p, sizeof(int32_t), (size_t)B_, sizeof(int32_t), caller_order());
+        out_.add_rows(out_value, bs2_.p, sizeof(double), (size_t)blk_.B, sizeof(double), caller_order());
+        out_.add_rows(out_index, bv2_.p, sizeof(int32_t), (size_t)blk_.B, sizeof(int32_t), caller_order());
         return out_.finish();
     }
 
     // One-step lookahead values of the resident block against the working alpha set: the backup's pipeline up to best_v
-    // (run_pipeline with q_only_), launch_q_exact behind it, results copied out in the caller's belief order.  best_v_ and
+    // (run_q), launch_q_exact behind it, results copied out in the caller's belief order.  best_v_ and
     // the other stage buffers are overwritten, so an earlier backup's results are no longer fetchable afterwards.
     int q_values(double gamma, double* out_q, int32_t* out_action, int32_t* out_best) override {
         if (!out_q) FAIL(PBVI_EINVAL, "q_values: NULL out_q");
         if (V_ <= 0) FAIL(PBVI_EINVAL, "q_values: no alpha set resident (call pbvi_alpha_set)");
-        if (B_ <= 0) FAIL(PBVI_EINVAL, "q_values: no belief block resident (call pbvi_beliefs_set)");
+        if (blk_.B <= 0) FAIL(PBVI_EINVAL, "q_values: no belief block resident (call pbvi_beliefs_set)");
         if (mode_ != PBVI_SPARSE) FAIL(PBVI_EUNSUPPORTED, "q_values: not available on a PBVI_DENSE engine (create it with PBVI_SPARSE)");
-        q_only_ = true;
-        q_want_best_ = out_best != nullptr;
-        int rc = backup_run(gamma, 0, nullptr);
-        q_only_ = q_want_best_ = false;
-        have_result_ = have_bk_vmax_ = false;
+        int rc = run_q(gamma, out_best != nullptr);
         if (rc) return rc;
-        return out_.deliver({{out_q, q_res_.p, (size_t)B_ * A_ * sizeof(double)},
-                             {out_action, q_act_.p, (size_t)B_ * sizeof(int32_t)},
-                             {out_best, fin_.best_res.p, (size_t)B_ * A_ * O_ * sizeof(int32_t)}});
+        return out_.deliver({{out_q, q_res_.p, (size_t)blk_.B * A_ * sizeof(double)},
+                             {out_action, q_act_.p, (size_t)blk_.B * sizeof(int32_t)},
+                             {out_best, fin_.best_res.p, (size_t)blk_.B * A_ * O_ * sizeof(int32_t)}});
     }
 
     int64_t store_count(int which) const override { return (which == 0 || which == 1) ? store_rows_[which] : -1; }
@@ -3746,7 +3742,8 @@ class EngineT : public EngineBase {
             }
             snz_rows_ = have;
         }
-        if (kF32 && !vmax_skinny()) {   // per-row tile lists for the f64 refinement
+        const bool lists = kF32 && !vmax_skinny();   // per-row tile lists for the f64 refinement
+        if (lists) {
             if ((rc = grow_keep(sbtl_, (size_t)have * k_tiles * sizeof(int32_t), (size_t)sbt_rows_ * k_tiles * sizeof(int32_t)))) return rc;
             if ((rc = grow_keep(sbtc_, (size_t)have * sizeof(int32_t), (size_t)sbt_rows_ * sizeof(int32_t)))) return rc;
             for (int64_t r0 = sbt_rows_; r0 < have; r0 += 32768) {
@@ -3756,32 +3753,14 @@ class EngineT : public EngineBase {
             }
             sbt_rows_ = have;
         }
-        // run value_max_device on windows of the store: the block members point into the store for the duration
-        // (put back when `win` goes out of scope, on every return path)
-        struct Windows {
-            EngineT& e;
-            DevBuf::Window bel{e.bel_}, nzA{e.nzA_}, btl{e.btl_}, btc{e.btc_};
-            const int64_t B = e.B_, B_pad = e.B_pad_;
-            const bool sorted = e.sorted_, btl_valid = e.btl_valid_, have_result = e.have_result_;
-            ~Windows() {
-                e.B_ = B; e.B_pad_ = B_pad; e.sorted_ = sorted; e.btl_valid_ = btl_valid; e.have_result_ = have_result;
-            }
-        } win{*this};
+        // value_max_device on windows of the store: each window is the operand, the resident block is not touched
         const int64_t window = 32768;
         rc = PBVI_OK;
         for (int64_t r0 = 0; r0 < n && rc == PBVI_OK; r0 += window) {
             const int64_t cnt = std::min<int64_t>(window, n - r0);
-            win.bel.point(base + (size_t)r0 * S_pad_);
-            win.nzA.point(snz_.as<uint8_t>() + (size_t)(r0 / GEMM_BM) * k_tiles);
-            if (kF32 && !vmax_skinny()) {
-                win.btl.point(sbtl_.as<int32_t>() + (size_t)r0 * k_tiles);
-                win.btc.point(sbtc_.as<int32_t>() + r0);
-            }
-            B_ = cnt;
-            B_pad_ = round_up(cnt, GEMM_BM);
-            sorted_ = false;
-            btl_valid_ = kF32 && !vmax_skinny();
-            rc = value_max_device();
+            rc = value_max_device({base + (size_t)r0 * S_pad_, cnt, snz_.as<uint8_t>() + (size_t)(r0 / GEMM_BM) * k_tiles,
+                                   lists ? sbtl_.as<int32_t>() + (size_t)r0 * k_tiles : nullptr,
+                                   lists ? sbtc_.as<int32_t>() + r0 : nullptr});
             if (rc == PBVI_OK)
                 rc = out_.deliver({{out_value ? out_value + r0 : nullptr, bs2_.p, (size_t)cnt * sizeof(double)},
                                    {out_index ? out_index + r0 : nullptr, bv2_.p, (size_t)cnt * sizeof(int32_t)}});
@@ -3884,25 +3863,25 @@ class EngineT : public EngineBase {
     // automatic score split: from this many dense 256x256x32 tile-steps of the padded score GEMM (C4: 274k)
     static constexpr int64_t kSplitMinSteps = 16384;
     bool split_pays(int64_t n_rows_alloc, int k_tiles) const {
-        const int64_t dense_steps = (B_pad_ / GEMM_BM) * (n_rows_alloc / GEMM_BN) * (int64_t)k_tiles;
+        const int64_t dense_steps = (blk_.B_pad / GEMM_BM) * (n_rows_alloc / GEMM_BN) * (int64_t)k_tiles;
         return dense_steps >= kSplitMinSteps;
     }
-    // fp32: bring the resident block's split plane up to date (allocated on first use, rebuilt from bel_ when a path that
-    // changes bel_ did not write it).  false: it does not fit (the caller keeps the fp32 GEMM).  The split kernel addresses
+    // fp32: bring the resident block's split plane up to date (allocated on first use, rebuilt from blk_.rows when a path that
+    // changes blk_.rows did not write it).  false: it does not fit (the caller keeps the fp32 GEMM).  The split kernel addresses
     // 256 rows of the plane with 32-bit byte offsets, hence the bound on S_pad.
     bool split_plane() {
-        const size_t bytes = (size_t)B_pad_ * S_pad_ * sizeof(float);
+        const size_t bytes = (size_t)blk_.B_pad * S_pad_ * sizeof(float);
         if (bytes == 0 || S_pad_ > (1 << 22)) return false;
-        if (belsp_.cap < bytes) {
-            if (!DevBuf::headroom_ok(mem_.bytes, bytes) || belsp_.ensure(bytes) != PBVI_OK) return false;
-            belsp_ver_ = 0;
+        if (blk_.plane.cap < bytes) {
+            if (!DevBuf::headroom_ok(mem_.bytes, bytes) || blk_.plane.ensure(bytes) != PBVI_OK) return false;
+            blk_.plane_ver = 0;
         }
-        if (belsp_ver_ != bel_ver_) {
-            const int64_t n = (int64_t)B_pad_ * S_pad_;
-            hipLaunchKernelGGL(k_split_plane, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, stream_, bel_.as<float>(),
-                               belsp_.as<uint32_t>(), n);
+        if (blk_.plane_ver != blk_.ver) {
+            const int64_t n = (int64_t)blk_.B_pad * S_pad_;
+            hipLaunchKernelGGL(k_split_plane, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, stream_, blk_.rows.as<float>(),
+                               blk_.plane.as<uint32_t>(), n);
             if (hipGetLastError() != hipSuccess) return false;
-            belsp_ver_ = bel_ver_;
+            blk_.plane_ver = blk_.ver;
         }
         return true;
     }
@@ -3983,12 +3962,12 @@ int EngineT<T>::score_gemm(const T* Y, int64_t rows_y, const uint8_t* nzB, int G
                            const T* X, int64_t x_rows, const uint8_t* nzX, hipStream_t list_stream, const FusedB* fused,
                            int* split, int f64_route) {
     int rc;
-    const int64_t m_rows = X ? x_rows : B_;
-    const int64_t m_pad = X ? round_up(x_rows, GEMM_BM) : B_pad_;
+    const int64_t m_rows = X ? x_rows : blk_.B;
+    const int64_t m_pad = X ? round_up(x_rows, GEMM_BM) : blk_.B_pad;
     const bool own_block = X == nullptr;
     if (!X) {
-        X = bel_.as<T>();
-        nzX = nzA_.as<uint8_t>();
+        X = blk_.rows.as<T>();
+        nzX = blk_.nzA.as<uint8_t>();
     }
     if constexpr (kF32) {
         const int64_t n_pad = round_up(rows_y, GEMM_BN);
@@ -4005,7 +3984,7 @@ int EngineT<T>::score_gemm(const T* Y, int64_t rows_y, const uint8_t* nzB, int G
         if (sp && (!own_block || !split_plane())) sp = 0;      // no plane: the fp32 GEMM (same outputs)
         if (split != nullptr) *split = sp;
         ScoreGemmArgs g;
-        g.A = sp ? belsp_.as<float>() : (const float*)X;
+        g.A = sp ? blk_.plane.as<float>() : (const float*)X;
         g.B = (const float*)Y;
         g.lda = g.ldb = S_pad_;
         g.C = slabs_.as<float>();
@@ -4120,13 +4099,14 @@ int EngineT<T>::project_dense(double gamma) {
 }
 
 template <typename T>
-int EngineT<T>::value_max_device() {
+int EngineT<T>::value_max_device(const Operand& x) {
     int rc;
+    const int64_t B = x.B;
     const int64_t Vt = V_ + 1;   // + magnitude row
-    if ((rc = bv2_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
-    if ((rc = bs2_.ensure((size_t)B_ * sizeof(double)))) return rc;
-    if ((rc = err2_.ensure((size_t)B_ * sizeof(double)))) return rc;
-    if ((rc = queue2_.ensure((size_t)B_ * sizeof(int32_t)))) return rc;
+    if ((rc = bv2_.ensure((size_t)B * sizeof(int32_t)))) return rc;
+    if ((rc = bs2_.ensure((size_t)B * sizeof(double)))) return rc;
+    if ((rc = err2_.ensure((size_t)B * sizeof(double)))) return rc;
+    if ((rc = queue2_.ensure((size_t)B * sizeof(int32_t)))) return rc;
     int* qc = counters_.as<int>() + CNT_VALUE_MAX_QUEUE;
     HIPCHK(hipMemsetAsync(qc, 0, sizeof(int), stream_));
     if constexpr (kF32) {
@@ -4137,43 +4117,44 @@ int EngineT<T>::value_max_device() {
             // the belief block once instead -- and its scores are exact products summed in fp64, so there is no tie window
             // and nothing to re-score.
             const int kt32 = S_pad_ / GEMM_BK;
-            const int split = gemm_f64_split((int)B_, (int)V_, kt32);
-            const int64_t slab = B_ * V_;
+            const int split = gemm_f64_split((int)B, (int)V_, kt32);
+            const int64_t slab = B * V_;
             if ((rc = slabs_.ensure((size_t)split * slab * sizeof(double)))) return rc;
-            if ((rc = klist_.ensure(gemm_f64_klist_ints((int)B_, (int)V_, kt32) * sizeof(int)))) return rc;
-            if ((rc = kcount_.ensure(gemm_f64_kcount_ints((int)B_, (int)V_, kt32) * sizeof(int)))) return rc;
-            HIPCHK(launch_gemm_nt_f64_ff32((const float*)bel_.p, S_pad_, (int)B_, (const float*)alpha_.p, S_pad_, (int)V_,
-                                           slabs_.as<double>(), (int)V_, S_pad_, nzA_.as<uint8_t>(), klist_.as<int>(),
+            if ((rc = klist_.ensure(gemm_f64_klist_ints((int)B, (int)V_, kt32) * sizeof(int)))) return rc;
+            if ((rc = kcount_.ensure(gemm_f64_kcount_ints((int)B, (int)V_, kt32) * sizeof(int)))) return rc;
+            HIPCHK(launch_gemm_nt_f64_ff32((const float*)x.rows, S_pad_, (int)B, (const float*)alpha_.p, S_pad_, (int)V_,
+                                           slabs_.as<double>(), (int)V_, S_pad_, x.nzA, klist_.as<int>(),
                                            kcount_.as<int>(), stream_, split, slab));
             const SlabView<double> svd = SlabView<double>::single(slabs_.as<double>(), (int)V_);   // K parts folded into the first slab by the launcher
-            HIPCHK(launch_argmax<double>(svd, (int)V_, 1, (int)B_, nullptr, 0.0, 0.0, nullptr, 0, bv2_.as<int32_t>(),
+            HIPCHK(launch_argmax<double>(svd, (int)V_, 1, (int)B, nullptr, 0.0, 0.0, nullptr, 0, bv2_.as<int32_t>(),
                                          bs2_.as<double>(), err2_.as<double>(), nullptr, qc, stream_));
-            note_vmax_route(1, gemm_f64_bn((int)V_), split, (int64_t)gemm_f64_pairs((int)B_, (int)V_));
+            note_vmax_route(1, gemm_f64_bn((int)V_), split, B, (int64_t)gemm_f64_pairs((int)B, (int)V_));
             return PBVI_OK;
         }
     }
     SlabView<T> sv;
-    if ((rc = score_gemm(alpha_.as<T>(), Vt, nullptr, 1, (int)V_, &sv))) return rc;
+    if ((rc = score_gemm(alpha_.as<T>(), Vt, nullptr, 1, (int)V_, &sv, x.rows, B, x.nzA))) return rc;
     const int k_chunk = kF32 ? plan_.chunk_len * GEMM_BK : S_pad_;
     // every belief is re-scored exactly in f32 engines (flag_all): the comparison that
     // follows (new value > old best value) is strict and must not see GEMM rounding
     const bool rescore = kF32 && vmax_exact_;
-    HIPCHK(launch_argmax<T>(sv, (int)V_, 1, (int)B_, nullptr, tie_window(k_chunk), 0.0, chain_steps(), 1, bv2_.as<int32_t>(),
+    HIPCHK(launch_argmax<T>(sv, (int)V_, 1, (int)B, nullptr, tie_window(k_chunk), 0.0, chain_steps(), 1, bv2_.as<int32_t>(),
                             bs2_.as<double>(), err2_.as<double>(), rescore ? queue2_.as<int32_t>() : nullptr, qc, stream_));
     if (rescore) {
-        if ((rc = ensure_belief_tiles())) return rc;   // tile lists of the resident block (the backup's k_dead builds them too)
+        if (x.btl == nullptr && (rc = ensure_belief_tiles())) return rc;   // (the backup's k_dead builds them too)
+        const int32_t *btl = x.btl ? x.btl : blk_.btl.as<int32_t>(), *btc = x.btl ? x.btc : blk_.btc.as<int32_t>();
         RefineWork work;
-        if ((rc = refine_work(B_, V_, &work))) return rc;
+        if ((rc = refine_work(B, V_, &work))) return rc;
         last_work_ = work;                                       // (pbvi_debug_refine_counts)
         have_last_work_ = true;
-        HIPCHK(launch_refine<T>(false, sv, (int)V_, 1, (int)B_, queue2_.as<int32_t>(), qc, bel_.as<T>(), S_pad_,
-                                alpha_.as<T>(), S_pad_, view(), 0.0, btl_.as<int32_t>(), btc_.as<int32_t>(), nullptr,
+        HIPCHK(launch_refine<T>(false, sv, (int)V_, 1, (int)B, queue2_.as<int32_t>(), qc, x.rows, S_pad_,
+                                alpha_.as<T>(), S_pad_, view(), 0.0, btl, btc, nullptr,
                                 bv2_.as<int32_t>(), bs2_.as<double>(), err2_.as<double>(), nullptr, work, stream_));
     }
     if constexpr (kF32)
-        note_vmax_route(rescore ? 2 : 3, GEMM_BN, 0, (int64_t)plan_.tiles_m * plan_.tiles_n);
+        note_vmax_route(rescore ? 2 : 3, GEMM_BN, 0, B, (int64_t)plan_.tiles_m * plan_.tiles_n);
     else
-        note_vmax_route(f64_pairs_ > 0 ? 4 : 5, f64_pairs_ > 0 ? gemm_f64_bn((int)Vt) : 0, f64_split_, f64_pairs_);
+        note_vmax_route(f64_pairs_ > 0 ? 4 : 5, f64_pairs_ > 0 ? gemm_f64_bn((int)Vt) : 0, f64_split_, B, f64_pairs_);
     return PBVI_OK;
 }
 
@@ -4205,7 +4186,7 @@ bool EngineT<T>::choose_push(int64_t N) const {
     // The belief side wins when B << V (the solve loop: ~100 new beliefs against thousands of alpha-vectors):
     // fewer rows to project and far less tile padding.  Sparse mode only.
     const int AO = A_ * O_;
-    if (mode_ == PBVI_DENSE || (int64_t)B_ * AO > 0x7fffffff || !(kF32 || f64_uses_mfma(B_ * AO, V_))) return false;
+    if (mode_ == PBVI_DENSE || (int64_t)blk_.B * AO > 0x7fffffff || !(kF32 || f64_uses_mfma(blk_.B * AO, V_))) return false;
     const int64_t bm = kF32 ? GEMM_BM : 128;                       // GEMM tile edge and sustained rate per dtype
     const double rate = kF32 ? 130e12 : 45e12;
     // projection cost per row, measured at C4: the alpha side writes only the Gamma tiles the GEMM will read
@@ -4215,7 +4196,7 @@ bool EngineT<T>::choose_push(int64_t N) const {
         const double tiles = (double)((m_rows + bm - 1) / bm) * (double)((n_rows + bm - 1) / bm);
         return tiles * S_pad_ * (2.0 * bm * bm / rate) + (double)proj_rows * S_pad_ * sizeof(T) / proj_rate;
     };
-    const double c_pull = cost(B_, N, N, 6e12), c_push = cost(B_ * AO, V_, B_ * AO, 1e12);
+    const double c_pull = cost(blk_.B, N, N, 6e12), c_push = cost(blk_.B * AO, V_, blk_.B * AO, 1e12);
     if (formulation_ != 0) return formulation_ == 2;
     // Memory before speed: Gamma[A,O,V,S] is what the reference's CuPy path dies allocating (Sea_Robin_Real.ipynb:913,
     // 21.95 GB at |V| = 1386).  Where this engine would have to hold all of it (no fused generation: R > 1, fp64 scoring)
@@ -4224,7 +4205,7 @@ bool EngineT<T>::choose_push(int64_t N) const {
     // belief block on MemoryError), not with V.
     const bool gamma_compact = kF32 && R_ == 1 && fuse_project_ >= 1 && irr_.p != nullptr;
     const int64_t row = (int64_t)S_pad_ * (int64_t)sizeof(T);
-    const int64_t n_pull = kF32 ? round_up(N, GEMM_BN) : N, m_push = round_up((int64_t)B_ * AO + B_, GEMM_BM);
+    const int64_t n_pull = kF32 ? round_up(N, GEMM_BN) : N, m_push = round_up((int64_t)blk_.B * AO + blk_.B, GEMM_BM);
     const int64_t gam_new = gamma_compact ? 0 : std::max<int64_t>(0, n_pull * row - (int64_t)gam_.cap);
     // (with Gamma tiling on, the alpha side fits whatever |V| is: the cost model alone decides)
     if (gam_new > ((int64_t)1 << 28) && tiling_mode_ == 0) {
@@ -4233,9 +4214,9 @@ bool EngineT<T>::choose_push(int64_t N) const {
             if constexpr (kF32) return make_gemm_plan((int)round_up(m, GEMM_BM), (int)round_up(n, GEMM_BN), S_pad_).c_floats * 4;
             else return (int64_t)gemm_f64_split((int)m, (int)n, S_pad_ / GEMM_BK) * m * n * 8;
         };
-        const int64_t pull = gam_new + std::max<int64_t>(0, slabs(B_, N) - (int64_t)slabs_.cap);
+        const int64_t pull = gam_new + std::max<int64_t>(0, slabs(blk_.B, N) - (int64_t)slabs_.cap);
         const int64_t push = std::max<int64_t>(0, m_push * row - (int64_t)bp_.cap) +
-                             std::max<int64_t>(0, slabs((int64_t)B_ * AO + B_, V_) - (int64_t)slabs_.cap);
+                             std::max<int64_t>(0, slabs((int64_t)blk_.B * AO + blk_.B, V_) - (int64_t)slabs_.cap);
         if (push < pull && pull > room()) return true;
     }
     return c_push < 0.8 * c_pull;
@@ -4250,7 +4231,7 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
     const int AO = A_ * O_;
     const int64_t Vt = V_ + 1;                 // alpha rows + magnitude row
     const int64_t N = (int64_t)AO * Vt + 2 * A_;   // Gamma rows: alpha groups, A*O magnitude rows, A reward + A |reward| rows
-    const int64_t pairs = B_ * AO;
+    const int64_t pairs = blk_.B * AO;
     const ModelView<T> mv = view();
     const int k_tiles = S_pad_ / GEMM_BK;
     const int64_t n_rows_alloc = kF32 ? round_up(N, GEMM_BN) : N;
@@ -4313,14 +4294,14 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
         const int64_t held = (int64_t)(gam_.cap + slabs_.cap + scores_.cap + klist_.cap);
         const int64_t free_now = room();
         const int64_t avail = free_now > INT64_MAX - held ? INT64_MAX : free_now + held;
-        const int64_t reserve = avail / 16 + 2 * B_ * (int64_t)S_pad_ * (int64_t)sizeof(T) +
-                                (B_pad_ * round_up(Vt, GEMM_BN) + (int64_t)512 * 256 * 256) * (int64_t)sizeof(T);
+        const int64_t reserve = avail / 16 + 2 * blk_.B * (int64_t)S_pad_ * (int64_t)sizeof(T) +
+                                (blk_.B_pad * round_up(Vt, GEMM_BN) + (int64_t)512 * 256 * 256) * (int64_t)sizeof(T);
         const int64_t budget = std::max<int64_t>(0, avail - reserve);
         TilingPlan tp;
         bool plan = tiling_mode_ == 2;
-        if (tiling_mode_ == 1) plan = tiling_chunk_bytes(S_pad_, AO, A_, B_, kF32, V_) > budget;
+        if (tiling_mode_ == 1) plan = tiling_chunk_bytes(S_pad_, AO, A_, blk_.B, kF32, V_) > budget;
         if (plan) {
-            rc = tiling_plan(S_, A_, O_, V_, B_, kF32, budget, tiling_rows_, &tp);
+            rc = tiling_plan(S_, A_, O_, V_, blk_.B, kF32, budget, tiling_rows_, &tp);
             if (rc == PBVI_EINVAL) FAIL(PBVI_EINVAL, "gamma tiling: shape out of range");
             if (rc == PBVI_ENOMEM && tiling_rows_ == 0)
                 FAIL(PBVI_ENOMEM, "gamma tiling: a 4-row chunk and the score matrix need " + std::to_string(tp.bytes) +
@@ -4357,19 +4338,19 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
         // B extra rows behind the projected ones: the beliefs themselves, so the same GEMM also yields b . alpha_v --
         // compute_change's max_v b.alpha_v of these beliefs against this alpha set (pbvi_backup_fetch_value_max)
         // rides in the M padding (1800 + 100 rows of 2048 in a solve loop).
-        const int64_t M = (int64_t)AO * B_, Mx = M + B_, M_pad = round_up(Mx, GEMM_BM);
+        const int64_t M = (int64_t)AO * blk_.B, Mx = M + blk_.B, M_pad = round_up(Mx, GEMM_BM);
         if ((rc = bp_.ensure((size_t)M_pad * S_pad_ * sizeof(T)))) return rc;
         if ((rc = pmag_.ensure((size_t)pairs * sizeof(double)))) return rc;
         if ((rc = nzP_.ensure((size_t)(M_pad / GEMM_BM) * k_tiles))) return rc;
         HIPCHK(hipMemsetAsync(pmag_.p, 0, (size_t)pairs * sizeof(double), stream_));
-        HIPCHK(hipMemcpyAsync(bp_.as<T>() + (size_t)M * S_pad_, bel_.p, (size_t)B_ * S_pad_ * sizeof(T), hipMemcpyDeviceToDevice, stream_));
+        HIPCHK(hipMemcpyAsync(bp_.as<T>() + (size_t)M * S_pad_, blk_.rows.p, (size_t)blk_.B * S_pad_ * sizeof(T), hipMemcpyDeviceToDevice, stream_));
         if (M_pad > Mx)
             HIPCHK(hipMemsetAsync(bp_.as<T>() + (size_t)Mx * S_pad_, 0, (size_t)(M_pad - Mx) * S_pad_ * sizeof(T), stream_));
         // the GEMM's zero-tile map of bp: the projection marks the tiles of its own rows while it writes them; only the row
         // tiles that also hold the belief rows / the pad are scanned afterwards (a pass over all of bp was 0.18 ms at the
         // Sea-Robin shape)
         HIPCHK(hipMemsetAsync(nzP_.p, 0, (size_t)(M_pad / GEMM_BM) * k_tiles, stream_));
-        HIPCHK(launch_push_project<T>(bel_.as<T>(), S_pad_, (int)B_, mv, in_ptr_.as<int32_t>(), in_src_.as<int32_t>(), gamma,
+        HIPCHK(launch_push_project<T>(blk_.rows.as<T>(), S_pad_, (int)blk_.B, mv, in_ptr_.as<int32_t>(), in_src_.as<int32_t>(), gamma,
                                       alpha_.as<T>() + (size_t)V_ * S_pad_, bp_.as<T>(), S_pad_, pmag_.as<double>(), stream_,
                                       nzP_.as<uint8_t>()));
         {
@@ -4385,7 +4366,7 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
         if ((rc = score_gemm(alpha_.as<T>(), V_, nullptr, 1, (int)V_, &sv, bp_.as<T>(), Mx, nzP_.as<uint8_t>()))) return rc;
         out->extra_row0 = M;
         sv.push = 1;
-        sv.push_B = (int)B_;
+        sv.push_B = (int)blk_.B;
         sv.push_A = A_;
         sv.push_O = O_;
         sv.aux_mag = pmag_.as<double>();
@@ -4399,9 +4380,9 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
         // the plain kernel (tiny problems) reads every Gamma element and needs them all written.
         // (a fused engine projects one or two tiles' worth of rows -- the tiles that straddle groups, the tail: all of their K
         // tiles are written, and the 12 us of k_need_tiles leave the front of every backup)
-        if ((kF32 || f64_uses_mfma(B_, N)) && !(will_fuse && R_ == 1)) {
+        if ((kF32 || f64_uses_mfma(blk_.B, N)) && !(will_fuse && R_ == 1)) {
             if ((rc = need_.ensure((size_t)AO * k_tiles))) return rc;
-            HIPCHK(launch_need_tiles(nzA_.as<uint8_t>(), (int)(B_pad_ / GEMM_BM), nzB_.as<uint8_t>(), AO, (int)V_, k_tiles,
+            HIPCHK(launch_need_tiles(blk_.nzA.as<uint8_t>(), (int)(blk_.B_pad / GEMM_BM), nzB_.as<uint8_t>(), AO, (int)V_, k_tiles,
                                      need_.as<uint8_t>(), stream_));
             need = need_.as<uint8_t>();
         }
@@ -4455,7 +4436,7 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
     out->chain = chain_steps();
     out->rd_col0 = (int64_t)AO * Vt;
     out->f64_pairs = f64_pairs_;
-    HIPCHK(launch_argmax<T>(sv, (int)V_, AO, (int)B_, io.dead, out->tol_rel, 0.0, out->chain, 0, io.best_v, io.best_score,
+    HIPCHK(launch_argmax<T>(sv, (int)V_, AO, (int)blk_.B, io.dead, out->tol_rel, 0.0, out->chain, 0, io.best_v, io.best_score,
                             io.err, io.queue, io.qcount, stream_, io.tol_extra, out->split, io.hcand, io.hncand));
     if (probe_on_ && (rc = probe_capture(sv, io, *out))) return rc;      // tests only (pbvi_debug_score_probe)
     HIPCHK(hipEventRecord(io.ev[3], stream_));
@@ -4492,21 +4473,21 @@ int EngineT<T>::stage_scores_tiled(double gamma, const ScoreIO& io, int want_spl
     const int64_t ldd = round_up(N, 4);
     if (ldd > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "gamma tiling: score matrix wider than int32");
     // the fold target first (the chunk size was planned beside it), then the buffers of the largest chunk
-    if ((rc = ensure_exact(scores_, (size_t)B_ * ldd * sizeof(T)))) return rc;
+    if ((rc = ensure_exact(scores_, (size_t)blk_.B * ldd * sizeof(T)))) return rc;
     const int64_t n_big = (int64_t)AO * (Vc + 1) + 2 * A_, rows_big = kF32 ? round_up(n_big, GEMM_BN) : n_big;
     if ((rc = ensure_exact(gam_, (size_t)rows_big * S_pad_ * sizeof(T)))) return rc;
     if constexpr (kF32) {
-        if ((rc = ensure_exact(slabs_, (size_t)make_gemm_plan((int)B_pad_, (int)rows_big, S_pad_).c_floats * sizeof(float)))) return rc;
+        if ((rc = ensure_exact(slabs_, (size_t)make_gemm_plan((int)blk_.B_pad, (int)rows_big, S_pad_).c_floats * sizeof(float)))) return rc;
     } else {
-        const int sp = f64_uses_mfma(B_, n_big) ? gemm_f64_split((int)B_, (int)n_big, k_tiles) : 1;
-        if ((rc = ensure_exact(slabs_, (size_t)sp * B_ * n_big * sizeof(T)))) return rc;
+        const int sp = f64_uses_mfma(blk_.B, n_big) ? gemm_f64_split((int)blk_.B, (int)n_big, k_tiles) : 1;
+        if ((rc = ensure_exact(slabs_, (size_t)sp * blk_.B * n_big * sizeof(T)))) return rc;
     }
     // fp64 scoring has no tie window: copies of an alpha row get equal bits because every column is summed in one order,
     // and the first of them wins.  Left to its own shape, a ragged last chunk may be small enough for the plain kernel, or
     // for another K split, than the chunks before it; a copy behind that seam then differs in its last bits and can win.
     // So the route of the largest chunk is the route of every chunk of the call.
-    const bool f64_mfma = !kF32 && f64_uses_mfma(B_, n_big);
-    const int f64_route = kF32 ? -1 : f64_mfma ? gemm_f64_split((int)B_, (int)n_big, k_tiles) : 0;
+    const bool f64_mfma = !kF32 && f64_uses_mfma(blk_.B, n_big);
+    const int f64_route = kF32 ? -1 : f64_mfma ? gemm_f64_split((int)blk_.B, (int)n_big, k_tiles) : 0;
     if ((rc = need_.ensure((size_t)AO * k_tiles))) return rc;
     if ((rc = chain_max_.ensure(sizeof(int)))) return rc;
     HIPCHK(hipMemsetAsync(chain_max_.p, 0, sizeof(int), stream_));
@@ -4532,7 +4513,7 @@ int EngineT<T>::stage_scores_tiled(double gamma, const ScoreIO& io, int want_spl
         }
         const uint8_t* need = nullptr;
         if (kF32 || f64_mfma) {
-            HIPCHK(launch_need_tiles(nzA_.as<uint8_t>(), (int)(B_pad_ / GEMM_BM), nzB_.as<uint8_t>(), AO, (int)vc, k_tiles,
+            HIPCHK(launch_need_tiles(blk_.nzA.as<uint8_t>(), (int)(blk_.B_pad / GEMM_BM), nzB_.as<uint8_t>(), AO, (int)vc, k_tiles,
                                      need_.as<uint8_t>(), stream_));
             need = need_.as<uint8_t>();
         }
@@ -4553,7 +4534,7 @@ int EngineT<T>::stage_scores_tiled(double gamma, const ScoreIO& io, int want_spl
         const double t = tie_window(kF32 ? plan_.chunk_len * GEMM_BK : S_pad_);
         if (t < 0.0) on_device = true;
         else tol = std::max(tol, t);
-        HIPCHK(launch_fold_chunk<T>(sv, (int)B_, AO, (int)vc, (int)V_, (int)v0, last ? AO + 2 * A_ : 0, scores_.as<T>(), ldd,
+        HIPCHK(launch_fold_chunk<T>(sv, (int)blk_.B, AO, (int)vc, (int)V_, (int)v0, last ? AO + 2 * A_ : 0, scores_.as<T>(), ldd,
                                     chain_steps(), chain_max_.as<int>(), stream_));
         if (io.stats) HIPCHK(hipEventRecord(tile_ev_[(size_t)3 * c + 2], stream_));
     }
@@ -4568,7 +4549,7 @@ int EngineT<T>::stage_scores_tiled(double gamma, const ScoreIO& io, int want_spl
     out->f64_pairs = f64_pairs_;
     out->fused = false;
     out->chunks = (int)n_chunks;
-    HIPCHK(launch_argmax<T>(full, (int)V_, AO, (int)B_, io.dead, out->tol_rel, 0.0, out->chain, 0, io.best_v, io.best_score,
+    HIPCHK(launch_argmax<T>(full, (int)V_, AO, (int)blk_.B, io.dead, out->tol_rel, 0.0, out->chain, 0, io.best_v, io.best_score,
                             io.err, io.queue, io.qcount, stream_, io.tol_extra, out->split, io.hcand, io.hncand));
     if (probe_on_ && (rc = probe_capture(full, io, *out))) return rc;    // tests only (pbvi_debug_score_probe)
     HIPCHK(hipEventRecord(io.ev[3], stream_));
@@ -4652,21 +4633,18 @@ int EngineT<T>::sync_screen() {
             sc->have_result_ = false;
             screen_alpha_seen_ = alpha_ver_;
         }
-        if (screen_bel_seen_ != bel_ver_) {
+        if (screen_bel_seen_ != blk_.ver) {
             const int k_tiles = S_pad_ / GEMM_BK;
-            if ((rc = sc->bel_.ensure((size_t)B_pad_ * S_pad_ * sizeof(float)))) return rc;
-            if ((rc = sc->nzA_.ensure((size_t)(B_pad_ / GEMM_BM) * k_tiles))) return rc;
-            const int64_t n = (int64_t)B_pad_ * S_pad_;      // same row order as this engine's block (pad rows are zero)
-            hipLaunchKernelGGL(k_narrow, dim3((unsigned)((n / 4 + 255) / 256 + 1)), dim3(256), 0, stream_, bel_.as<double>(),
-                               sc->bel_.template as<float>(), n, (int*)nullptr);
+            if ((rc = sc->blk_.rows.ensure((size_t)blk_.B_pad * S_pad_ * sizeof(float)))) return rc;
+            if ((rc = sc->blk_.nzA.ensure((size_t)(blk_.B_pad / GEMM_BM) * k_tiles))) return rc;
+            const int64_t n = (int64_t)blk_.B_pad * S_pad_;      // same row order as this engine's block (pad rows are zero)
+            hipLaunchKernelGGL(k_narrow, dim3((unsigned)((n / 4 + 255) / 256 + 1)), dim3(256), 0, stream_, blk_.rows.as<double>(),
+                               sc->blk_.rows.template as<float>(), n, (int*)nullptr);
             HIPCHK(hipGetLastError());
-            HIPCHK(launch_tile_nonzero_f32(sc->bel_.template as<float>(), S_pad_, (int)B_pad_, k_tiles, sc->nzA_.template as<uint8_t>(), stream_));
-            sc->B_ = B_;
-            sc->B_pad_ = B_pad_;
-            sc->sorted_ = false;
-            sc->btl_valid_ = false;
+            HIPCHK(launch_tile_nonzero_f32(sc->blk_.rows.template as<float>(), S_pad_, (int)blk_.B_pad, k_tiles, sc->blk_.nzA.template as<uint8_t>(), stream_));
+            sc->blk_.replaced(blk_.B, blk_.B_pad, false);
             sc->have_result_ = false;
-            screen_bel_seen_ = bel_ver_;
+            screen_bel_seen_ = blk_.ver;
         }
         sc->formulation_ = formulation_;
         sc->tie_rel_user_ = tie_rel_user_;
@@ -4677,27 +4655,27 @@ int EngineT<T>::sync_screen() {
 }
 
 template <typename T>
-int EngineT<T>::backup_run(double gamma, int flags, pbvi_stats_t* st) {
+int EngineT<T>::run_backup(double gamma, int flags, pbvi_stats_t* st, Mode mode) {
     if (V_ <= 0) FAIL(PBVI_EINVAL, "backup_run: no alpha set resident (call pbvi_alpha_set)");
-    if (B_ <= 0) FAIL(PBVI_EINVAL, "backup_run: no belief block resident (call pbvi_beliefs_set)");
+    if (blk_.B <= 0) FAIL(PBVI_EINVAL, "backup_run: no belief block resident (call pbvi_beliefs_set)");
     HIPCHK(hipSetDevice(device_));
     if constexpr (!kF32) {
         const int64_t N = (int64_t)A_ * O_ * (V_ + 1) + 2 * A_;
         // worth it once the score GEMM is more than a few tiles (tiger, the 4x3 grid, S = 600 models stay pure fp64)
-        const double gemm_flops = 2.0 * (double)round_up(B_, 128) * (double)N * (double)S_pad_;   // ~0.4 ms of fp64 MFMA
-        const bool want = screen_mode_ == 2 || (screen_mode_ == 1 && f64_uses_mfma(B_, N) && gemm_flops >= 2e10);
+        const double gemm_flops = 2.0 * (double)round_up(blk_.B, 128) * (double)N * (double)S_pad_;   // ~0.4 ms of fp64 MFMA
+        const bool want = screen_mode_ == 2 || (screen_mode_ == 1 && f64_uses_mfma(blk_.B, N) && gemm_flops >= 2e10);
         if (want && mode_ == PBVI_SPARSE && !h_rto_ref_.empty()) {
             int rc = ensure_screen();
             if (rc) return rc;
             if ((rc = sync_screen())) return rc;
             words().screen_overflow = 0;
-            if ((rc = run_pipeline<float>(*screen_, gamma, flags, st))) return rc;
+            if ((rc = run_pipeline<float>(*screen_, gamma, flags, st, mode))) return rc;
             // |alpha| beyond FLT_MAX became inf in the screen's copy (NaN scores follow): the fp64 pipeline decides alone
-            if (words().screen_overflow) return run_pipeline<T>(*this, gamma, flags, st);
+            if (words().screen_overflow) return run_pipeline<T>(*this, gamma, flags, st, mode);
             return PBVI_OK;
         }
     }
-    return run_pipeline<T>(*this, gamma, flags, st);
+    return run_pipeline<T>(*this, gamma, flags, st, mode);
 }
 
 // --------------------------------------------------------------------------- //

@@ -1509,7 +1509,7 @@ LOW, HIGH = (0.0, 0.25), (0.5, 1.0)
 
 # name -> (models, dtypes, operations)
 SCRIPTED = {
-    # dead_, btl_, btc_: two blocks of the same B with different dead triples and supports, each selected twice; behind the
+    # dead_, blk_.btl, blk_.btc: two blocks of the same B with different dead triples and supports, each selected twice; behind the
     # later selections the value maxima come first (they build the new block's tile lists and leave dead_ to the backup)
     'dead_triples_and_tile_lists': (MODELS, DTYPES, [
         op('set_alpha', V=257, seed=1), sw_('formulation', 'alpha'),
@@ -1521,7 +1521,7 @@ SCRIPTED = {
         op('select_beliefs', how='last', B=129), op('vmax_resident'), op('run_prune_fetch'), op('same_as', tag='second'),
         op('fetch_beliefs'), op('set_beliefs', B=129, seed=3, win=LOW, onehot=True), op('vmax_resident'), op('q_values'),
         op('run_fetch')]),
-    # rowflags_, nzA_, perm_, h_perm_, sorted_, res_sorted_: sorted blocks of one size, an unsorted one in between
+    # blk_.rowflags, .nzA, .perm, .h_perm, .sorted, res_sorted_: sorted blocks of one size, an unsorted one in between
     'sorted_blocks_of_one_size': (MODELS, DTYPES, [
         op('set_alpha', V=5, seed=2), op('set_beliefs', B=300, seed=1), op('run_fetch'), op('vmax_resident'),
         op('set_beliefs', B=300, seed=2, win=HIGH), op('run_fetch'), op('fetch_compact_into'), op('keys_assemble'),
@@ -1529,7 +1529,7 @@ SCRIPTED = {
         op('set_beliefs', B=300, seed=4, win=LOW), op('run_fetch_into'), op('infotaxis'), op('fetch_beliefs'),
         op('set_beliefs', B=257, seed=5), op('run_prune_fetch'), op('set_beliefs', B=256, seed=6), op('run_fetch'),
         op('vmax_resident')]),
-    # belsp_: a block put in place while the split is off, then a split run; blocks of one size through the store
+    # blk_.plane: a block put in place while the split is off, then a split run; blocks of one size through the store
     'split_plane_of_another_block': (('G',), ('f32',), [
         op('set_alpha', V=600, seed=3), sw_('formulation', 'alpha'), sw_('score_split', 'always'),
         op('store_beliefs', B=300, seed=1, win=LOW), op('store_beliefs', B=300, seed=2, win=HIGH),
@@ -1623,6 +1623,17 @@ SCRIPTED = {
         op('fetch_refused'), op('run_fetch'), op('store_unique'), op('fetch_refused'), op('run_fetch'),
         op('belief_update', seed=1), op('fetch_refused'), op('run_fetch'), op('prune_dominated'), op('fetch_refused'),
         op('vmax_resident'), op('run_fetch'), op('vmax_resident'), op('fetch_compact_into'), sw_('formulation', 'auto')]),
+    # the store as value_max's operand and the Q mode beside a SORTED resident block with a fetchable result: neither may
+    # touch the block (rows, order, tile lists, zero map) or, the store query, the result
+    'store_operand_beside_a_sorted_block': (MODELS, DTYPES, [
+        op('set_alpha', V=129, seed=1), op('store_beliefs', B=300, seed=1, win=LOW), op('store_beliefs', B=300, seed=2, win=HIGH),
+        op('select_beliefs', how='random', B=300, seed=1), op('run_fetch'), op('vmax_store'), op('fetch_compact_into'),
+        op('vmax_resident'), op('run_prune_fetch'), op('remember', tag='sorted'), op('vmax_store'), op('q_values'),
+        op('fetch_refused'), op('vmax_store'), op('infotaxis'), op('run_prune_fetch'), op('same_as', tag='sorted'),
+        op('keys_assemble'), op('vmax_store'), op('belief_update', seed=1), op('fetch_beliefs'),
+        op('set_beliefs', B=40, seed=19), op('rollout', T=2, seed=6, lookahead=1), op('vmax_store'), op('q_values'),
+        op('vmax_resident'), op('run_fetch'), op('after_oom'), op('set_alpha', V=5, seed=2), op('store_beliefs', B=257, seed=3),
+        op('select_beliefs', how='last', B=257), op('vmax_store'), op('run_fetch'), op('vmax_resident')]),
     # environment, walk64_ (control) and the blocks rollouts leave behind
     'rollouts_leave_their_survivors': (MODELS, DTYPES, [
         op('set_alpha', V=129, seed=1), op('set_beliefs', B=40, seed=14), op('rollout', T=3, seed=1), op('run_fetch'),

@@ -141,6 +141,20 @@ def test_a_switch_toggled_back_is_remembered_and_compared():
     assert fails('I', 'f64', Drifting, ops)
 
 
+@pytest.mark.parametrize('mname', sc.MODELS)
+@pytest.mark.parametrize('dtype', sc.DTYPES)
+def test_a_store_window_left_as_the_resident_block_is_caught(mname, dtype):
+    """``store_operand_beside_a_sorted_block`` is aimed at a ``max_value_store`` that scores the store's windows through the
+    resident block's own fields: a stand-in that leaves the last window there fails it, on every model and engine type."""
+    class WindowLeft(sc.HostEngine):
+        def max_value_store(self, n=-1):
+            out = super().max_value_store(n)
+            self.bel = np.stack(self.bstore)[-32768:]
+            return out
+    ops = sc.SCRIPTED['store_operand_beside_a_sorted_block'][2]
+    assert fails(mname, dtype, WindowLeft, ops)
+
+
 # --------------------------------------------------------------------------------------------------------------------- #
 # the HIP engine
 # --------------------------------------------------------------------------------------------------------------------- #
