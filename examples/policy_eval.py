@@ -7,6 +7,8 @@ The reference publishes one timing for this step (sim_runtime_test.ipynb:223, BA
     python examples/policy_eval.py --expansions 60 --n 1000 --max-steps 300
     python examples/policy_eval.py --reach 5 --device-sim 7      # stochastic moves, simulator on the device too
     python examples/policy_eval.py --policy infotaxis --device-sim 7   # the infotaxis baseline (no solve), on the device
+    python examples/policy_eval.py --policy space-aware --device-sim 7   # space-aware infotaxis (pbvi_rollout_space_aware)
+    python examples/policy_eval.py --policy expected-distance --device-sim 7   # greedy for the expected distance to the source
     python examples/policy_eval.py --device-sim 1 --environment frames    # observations from recorded frames (pbvi_rollout_env)
     python examples/policy_eval.py --device-sim 1 --environment table --env-flip 0.1   # a sensor that errs 10 % more often
 """
@@ -20,8 +22,8 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 from pomdp_pbvi_exploration_amd import FSVI_Solver, Model, set_quiet, synth   # noqa: E402
-from pomdp_pbvi_exploration_amd.pomdp import (Agent, FrameEnvironment, Infotaxis_Agent, TableEnvironment,   # noqa: E402
-                                              record_frames)
+from pomdp_pbvi_exploration_amd.pomdp import (Agent, FrameEnvironment, Infotaxis_Agent, SpaceAware_Agent,   # noqa: E402
+                                              TableEnvironment, record_frames)
 from pomdp_pbvi_exploration_amd.mdp import VI_Solver                         # noqa: E402
 
 
@@ -41,9 +43,11 @@ def main():
     ap.add_argument('--device-sim', type=int, default=None, metavar='SEED',
                     help='counter-based simulator draws with this seed: the whole step loop runs in the engine '
                          '(pbvi_rollout) instead of drawing on the host from NumPy\'s stream')
-    ap.add_argument('--policy', default='value', choices=['value', 'infotaxis'],
+    ap.add_argument('--policy', default='value', choices=['value', 'infotaxis', 'space-aware', 'expected-distance'],
                     help='value: solve with FSVI and follow the value function; infotaxis: no solve, every step takes the '
-                         'action with the smallest expected entropy of the next belief (pbvi_infotaxis)')
+                         'action with the smallest expected entropy of the next belief (pbvi_infotaxis); space-aware: no '
+                         'solve, greedy for log2(D + 2^(H-1) - 1/2) of the next belief, D its expected Manhattan distance to '
+                         'the source and H its entropy in bits (pbvi_space_aware); expected-distance: greedy for D alone')
     ap.add_argument('--environment', default=None, choices=['frames', 'table'],
                     help='where the observations come from (needs --device-sim): frames = a recorded movie, max-steps + 100 '
                          'frames drawn from the observation table by record_frames, every simulation starting at its own '
@@ -65,6 +69,12 @@ def main():
     if args.policy == 'infotaxis':
         agent = Infotaxis_Agent(model.to_gpu(args.dtype))
         policy = 'infotaxis'
+    elif args.policy in ('space-aware', 'expected-distance'):
+        cell = np.arange(m.S)                                  # state = row * W + column; the distance ignores wrap-around
+        distance = (np.abs(cell // W - m.goal // W) + np.abs(cell % W - m.goal % W)).astype(np.float64)
+        agent = SpaceAware_Agent(model.to_gpu(args.dtype), weights=distance,
+                                 objective='space_aware' if args.policy == 'space-aware' else 'expected_weight')
+        policy = args.policy
     else:
         # MDP value iteration that seeds FSVI: device sweeps vs the host NumPy loop (same result, see tests)
         t0 = time.perf_counter()
@@ -116,7 +126,12 @@ def main():
             print(f'lost (met an observation the model gives probability 0): {sum(h.lost for h in hists)} of {args.n}', flush=True)
 
     if args.cpu_steps > 0:
-        host_agent = Infotaxis_Agent(model) if args.policy == 'infotaxis' else Agent(model, vf.to_cpu(), lookahead=args.lookahead, gamma=m.gamma)
+        if args.policy == 'infotaxis':
+            host_agent = Infotaxis_Agent(model)
+        elif args.policy in ('space-aware', 'expected-distance'):
+            host_agent = SpaceAware_Agent(model, weights=agent.weights, objective=agent.objective)
+        else:
+            host_agent = Agent(model, vf.to_cpu(), lookahead=args.lookahead, gamma=m.gamma)
         np.random.seed(1)
         t0 = time.perf_counter()
         _, hh = host_agent.run_n_simulations_parallel(n=args.n, max_steps=args.cpu_steps, print_progress=False,

@@ -608,6 +608,69 @@ int pbvi_rollout_env(pbvi_engine_t* e, int policy, const int32_t* alpha_actions 
                      int32_t* out_observations /* [T][B] */, int32_t* out_steps /* [B] */, uint8_t* out_lost /* [B] */);
 
 /*
+ * Space-aware infotaxis (Loisy & Eloy 2022): the greedy policy for J(b) = log2(D(b) + 2^(H(b) - 1) - 1/2), D the expected
+ * distance to the source and H the entropy in bits -- the baseline the olfactory-search literature judges solved policies
+ * against.  The distance enters as one vector of state weights, so the same call gives a second baseline, the expected
+ * weight of the successor ("greedy distance" with a distance, a QMDP-style policy with w = -V_MDP shifted to >= 0).
+ *
+ * State weights: one vector per engine, w [S] fp64, every entry finite and >= 0 (checked on the host).
+ *   pbvi_state_weights_set    sets it (PBVI_EINVAL with a pbvi_last_error text: NULL, or an entry negative or not finite).
+ *   pbvi_state_weights_clear  removes it; the bytes are returned.
+ * The vector is device memory of the engine, S doubles exactly, counted against pbvi_debug_alloc_limit (PBVI_ENOMEM as
+ * everywhere) and released by pbvi_engine_after_oom, after which no weights are set.  Setting or clearing weights touches
+ * nothing else: not the belief block, the alpha set, the stores, the environment or any result.
+ *
+ * For a belief row b, action a and observation o, u[s'], Z[a, o] and N[a, o] are exactly pbvi_infotaxis' (the table the
+ * engine was created with, an fp32 engine's values widened to fp64; never the pbvi_engine_set_rto_f64 copy), and
+ *   D[a, o] = sum_s' u[s'] * w[s']                  (terms with u[s'] == 0 add 0)
+ * Per (a, o) with Z != 0:
+ *   H = max(0, ln Z - N / Z)                        the entropy of the successor belief, in nats
+ *   d = D / Z                                       its expected weight
+ *   x = max(1, d + (exp(H) - 1) / 2)                ( = d + 2^(H_bits - 1) - 1/2 )
+ *   J = log2(x)
+ * Both clamps are part of the definition (max as C's fmax).  Rounding can make ln Z - N / Z slightly negative: the first
+ * removes that.  The second gives J >= 0: a successor known to sit on the source (H = 0, d = 0) gives J = 0, the paper's
+ * value for "found".  Neither -inf nor NaN can arise from finite inputs.
+ *   objective 0 (space-aware):     F[b, a] = sum_o Z * J
+ *   objective 1 (expected weight): F[b, a] = sum_o D
+ * Both sums run sequentially over o; an observation with Z == 0 adds 0.
+ *   a*[b] = the first a whose F[b, a] is strictly below every earlier one; a NaN never wins and a row of NaNs gives 0.  It is
+ *           taken from the row of out_f that is returned, so out_action[b] equals that argmin of out_f[b] exactly.
+ * ln, exp and log2 are the fp64 functions.  The sums over s' are taken in pbvi_infotaxis' order -- fixed, no atomics: a
+ * belief's results have the same bits from call to call, whatever other beliefs share the block and wherever it stands.
+ *
+ * pbvi_space_aware: the above for every belief of the resident block.
+ *   out_f [B][A] double (required); out_action [B] int32, out_terms [B][A][O][3] double = (Z, N, D): may be NULL.  Host (or
+ *   device) memory, caller's belief order.
+ * The resident block, the alpha set, both row stores, the backup's stage buffers and pbvi_infotaxis' results are untouched.
+ * Works on PBVI_SPARSE and PBVI_DENSE engines and on both number formats.
+ * PBVI_EINVAL: no resident belief block, no weights set, out_f == NULL, or an objective other than 0 or 1.  PBVI_ENOMEM as
+ * everywhere (pbvi_engine_after_oom): the partial sums, ceil(S / 2048) * B * A * O * 3 doubles, and the results are device
+ * memory of the engine and count against pbvi_debug_alloc_limit.
+ *
+ * pbvi_rollout_space_aware: the step loop of the rollouts above with a fourth action source, a = a*[b] of the simulation's
+ * current belief under `objective`.
+ *   use_env = 0  the model's world, as pbvi_rollout_infotaxis: draws, done rule, trajectory layout and end state of the
+ *                block are pbvi_rollout's.  end_observation must be -1 and shifts NULL; out_lost, if given, is all 0.
+ *   use_env = 1  the successor draw, observation source, lost rule and checks of pbvi_rollout_env, against the environment
+ *                set with pbvi_env_set_*.
+ * In both cases the Bayes step's mass is summed in block order, with no atomics, as for infotaxis: a trajectory is a function
+ * of (model tables, weights, objective, environment, start belief, start state, shift, seed, id) alone.  No alpha set is
+ * needed.  PBVI_EINVAL beyond those of pbvi_rollout_infotaxis / pbvi_rollout_env: no weights set, an objective other than 0 or
+ * 1, use_env other than 0 or 1, end_observation or shifts given with use_env = 0.  pbvi_rollout_env itself keeps refusing
+ * policy numbers other than 0, 1 and 2: this source is reachable through this entry point only.
+ */
+int pbvi_state_weights_set(pbvi_engine_t* e, const double* weights /* [S] */);
+int pbvi_state_weights_clear(pbvi_engine_t* e);
+int pbvi_space_aware(pbvi_engine_t* e, int objective, double* out_f /* [B][A], required */,
+                     int32_t* out_action /* [B], may be NULL */, double* out_terms /* [B][A][O][3], may be NULL */);
+int pbvi_rollout_space_aware(pbvi_engine_t* e, int objective, int use_env, const int32_t* start_states /* [B] */,
+                             const uint8_t* end_mask /* [S] */, int end_observation, const int64_t* shifts /* [B] or NULL */,
+                             uint64_t first_sim_id, uint64_t seed, int64_t T, int32_t* out_states /* [T+1][B] */,
+                             int32_t* out_actions /* [T][B] */, int32_t* out_observations /* [T][B] */,
+                             int32_t* out_steps /* [B] */, uint8_t* out_lost /* [B] */);
+
+/*
  * MDP value iteration on the device (VI_Solver.solve, src/mdp.py:1442-1525; seeds FSVI / HSVI):
  *   rows[a][s] = ER[s,a] + gamma * sum_r P[s,a,r] * v[rs[s,a,r]];   v'[s] = max_a rows[a][s]
  * repeated from v0 until max_s |v' - v| < max_change_limit (the reference's eps * gamma / (1 - gamma)) or

@@ -372,6 +372,18 @@ hipError_t launch_infotaxis(const T* bel, int ldb, int B, ModelView<T> mv, const
                             const int32_t* perm, double* part, double* g_out, int32_t* action_out, double* pobs_out,
                             double* entropy_out, hipStream_t st);
 
+// Space-aware infotaxis (pbvi_space_aware): u, Z and N as above and D = sum_s' u[s'] * wgt[s'] (wgt [S] fp64, u == 0 adds 0).
+//   H = max(0, ln Z - N / Z),  x = max(1, D / Z + (exp(H) - 1) / 2),  J = log2(x)       per (a, o) with Z != 0
+//   objective 0: F[b,a] = sum_o Z * J;   objective 1: F[b,a] = sum_o D                   (sequential over o)
+// Two kernels, no atomics, every sum in a fixed order:
+//   k_succ_weighted<T>    k_succ_entropy's walk with a third accumulator set: (Z, N, D) partials into part [XB][B][A][O][3]
+//   k_space_aware_finish  partials summed in x-block order -> f_out [B][A], terms_out [B][A][O][3] = (Z, N, D) (or nullptr),
+//                         action_out [B] = the first minimum of the row of f_out as written; caller's belief order
+template <typename T>
+hipError_t launch_space_aware(const T* bel, int ldb, int B, ModelView<T> mv, const int32_t* in_ptr, const int32_t* in_src,
+                              const double* wgt, const int32_t* perm, double* part, int objective, double* f_out,
+                              int32_t* action_out, double* terms_out, hipStream_t st);
+
 // one step of the belief walk: out64 [S] / out_store [S_pad] = normalised update of `base` (fp64 [S]) with (a, o);
 // unnorm [S], partial [ceil(S_pad/256)] fp64 scratch; rto64: fp64 copy of RTO in mv's layout, or nullptr = use mv.rto
 // one kernel per step: pushes belief i and writes belief i (normalising the previous raw result on the fly); see the kernel.

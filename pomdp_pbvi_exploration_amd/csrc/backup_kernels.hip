@@ -2877,28 +2877,37 @@ hipError_t launch_rollout_compact(const RolloutStep& rs, int32_t* dst, int32_t* 
 // ------------------------------------------------------------------------- //
 int succ_entropy_xblocks(int S) { return (S + 256 * TILE_NT - 1) / (256 * TILE_NT); }
 
-template <typename T>
-__global__ void __launch_bounds__(256) k_succ_entropy(const T* __restrict__ bel, int ldb, int B, ModelView<T> mv,
-                                                      const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ in_src,
-                                                      double* __restrict__ part /* [gridDim.x][B][A][O][2] */) {
+// The body of k_succ_entropy and k_succ_weighted.  NTERM = 2: (Z, N);  NTERM = 3: (Z, N, D) with D = sum_s' u[s'] * wgt[s'] (u == 0
+// adds 0), the third sum of pbvi_space_aware, reduced like the other two.
+template <typename T, int NTERM>
+__device__ __forceinline__ void succ_sums(const T* __restrict__ bel, int ldb, int B, ModelView<T> mv,
+                                          const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ in_src,
+                                          const double* __restrict__ wgt /* [S], read when NTERM == 3 */,
+                                          double* __restrict__ part /* [gridDim.x][B][A][O][NTERM] */) {
     // One thread per landing state s' and TILE_NB beliefs (successor_tile); a block walks TILE_NT chunks of 256 states and
-    // reduces its (Z, N) partials once per pass over (up to) TILE_NO observations.
-    __shared__ double red[4][2 * TILE_NB * TILE_NO];
+    // reduces its partials once per pass over (up to) TILE_NO observations.
+    constexpr bool WEIGHTED = NTERM == 3;
+    __shared__ double red[4][NTERM * TILE_NB * TILE_NO];
     const int b0 = blockIdx.y * TILE_NB, a = blockIdx.z;
     const int nb = B - b0 < TILE_NB ? B - b0 : TILE_NB;
     const int32_t* ptr = in_ptr + (int64_t)a * (mv.S + 1);
     const int32_t* src = in_src + (int64_t)a * mv.S * mv.R;
     for (int o0 = 0; o0 < mv.O; o0 += TILE_NO) {
         const int no = mv.O - o0 < TILE_NO ? mv.O - o0 : TILE_NO;
-        double zs[TILE_NB][TILE_NO], ns[TILE_NB][TILE_NO];
+        double zs[TILE_NB][TILE_NO], ns[TILE_NB][TILE_NO], ds[WEIGHTED ? TILE_NB : 1][WEIGHTED ? TILE_NO : 1];
 #pragma unroll
         for (int k = 0; k < TILE_NB; ++k)
 #pragma unroll
-            for (int q = 0; q < TILE_NO; ++q) zs[k][q] = ns[k][q] = 0.0;
+            for (int q = 0; q < TILE_NO; ++q) {
+                zs[k][q] = ns[k][q] = 0.0;
+                if constexpr (WEIGHTED) ds[k][q] = 0.0;
+            }
         for (int c = 0; c < TILE_NT; ++c) {
             const int sp = (blockIdx.x * TILE_NT + c) * 256 + threadIdx.x;
             if (sp >= mv.S) break;
             const int j0 = ptr[sp], j1 = ptr[sp + 1];
+            double w_sp = 0.0;
+            if constexpr (WEIGHTED) w_sp = wgt[sp];          // one coalesced load per thread and chunk
             double acc[TILE_NB][TILE_NO];
             successor_tile(bel, ldb, b0, nb, mv, src, j0, j1, a, o0, no, acc);
 #pragma unroll
@@ -2909,6 +2918,7 @@ __global__ void __launch_bounds__(256) k_succ_entropy(const T* __restrict__ bel,
                     if (u != 0.0) {
                         zs[k][q] += u;
                         ns[k][q] += u * log(u);
+                        if constexpr (WEIGHTED) ds[k][q] += u * w_sp;
                     }
                 }
         }
@@ -2918,6 +2928,7 @@ __global__ void __launch_bounds__(256) k_succ_entropy(const T* __restrict__ bel,
             for (int q = 0; q < TILE_NO; ++q) {
                 zs[k][q] = wave_sum(zs[k][q]);
                 ns[k][q] = wave_sum(ns[k][q]);
+                if constexpr (WEIGHTED) ds[k][q] = wave_sum(ds[k][q]);
             }
         __syncthreads();                                    // red[] of the previous pass has been read
         if ((threadIdx.x & 63) == 0) {
@@ -2926,19 +2937,37 @@ __global__ void __launch_bounds__(256) k_succ_entropy(const T* __restrict__ bel,
             for (int k = 0; k < TILE_NB; ++k)
 #pragma unroll
                 for (int q = 0; q < TILE_NO; ++q) {
-                    mine[(k * TILE_NO + q) * 2] = zs[k][q];
-                    mine[(k * TILE_NO + q) * 2 + 1] = ns[k][q];
+                    mine[(k * TILE_NO + q) * NTERM] = zs[k][q];
+                    mine[(k * TILE_NO + q) * NTERM + 1] = ns[k][q];
+                    if constexpr (WEIGHTED) mine[(k * TILE_NO + q) * NTERM + 2] = ds[k][q];
                 }
         }
         __syncthreads();
-        if ((int)threadIdx.x < 2 * TILE_NB * TILE_NO) {
-            const int i = threadIdx.x, k = i / (2 * TILE_NO), q = (i >> 1) % TILE_NO;
+        if ((int)threadIdx.x < NTERM * TILE_NB * TILE_NO) {
+            const int i = threadIdx.x, k = i / (NTERM * TILE_NO), q = (i / NTERM) % TILE_NO;
             if (k < nb && q < no) {
                 const double v = ((red[0][i] + red[1][i]) + red[2][i]) + red[3][i];
-                part[((((int64_t)blockIdx.x * B + b0 + k) * mv.A + a) * mv.O + o0 + q) * 2 + (i & 1)] = v;
+                part[((((int64_t)blockIdx.x * B + b0 + k) * mv.A + a) * mv.O + o0 + q) * NTERM + (i % NTERM)] = v;
             }
         }
     }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) k_succ_entropy(const T* __restrict__ bel, int ldb, int B, ModelView<T> mv,
+                                                      const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ in_src,
+                                                      double* __restrict__ part /* [gridDim.x][B][A][O][2] */) {
+    succ_sums<T, 2>(bel, ldb, B, mv, in_ptr, in_src, nullptr, part);
+}
+
+// The weighted instantiation (pbvi_space_aware): the same walk with the third accumulator set.  48 fp64 accumulators beside
+// the tile's 16 cost a wave of occupancy (2 per SIMD instead of 3) and no scratch.
+template <typename T>
+__global__ void __launch_bounds__(256) k_succ_weighted(const T* __restrict__ bel, int ldb, int B, ModelView<T> mv,
+                                                       const int32_t* __restrict__ in_ptr, const int32_t* __restrict__ in_src,
+                                                       const double* __restrict__ wgt /* [S] */,
+                                                       double* __restrict__ part /* [gridDim.x][B][A][O][3] */) {
+    succ_sums<T, 3>(bel, ldb, B, mv, in_ptr, in_src, wgt, part);
 }
 
 // One block per belief (engine row b, caller row d = perm[b]): lane a, a + 64, ... sums the partials of (b, a, o) in x-block
@@ -3013,8 +3042,87 @@ hipError_t launch_infotaxis(const T* bel, int ldb, int B, ModelView<T> mv, const
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------- //
+// Space-aware infotaxis (pbvi_space_aware): greedy for J = log2(D + 2^(H-1) - 1/2) of the successor belief, D its expected
+// weight (a distance to the source) and H its entropy in bits.  Per (a, o), from the x-blocks' (Z, N, D) partials:
+//   H = max(0, ln Z - N / Z) nats,  d = D / Z,  x = max(1, d + (exp(H) - 1) / 2),  J = log2(x)
+//   objective 0: F[b,a] = sum_o Z * J;   objective 1: F[b,a] = sum_o D      (sequential over o; Z == 0 adds 0)
+// One block per belief, as k_infotaxis_finish: lane a, a + 64, ... adds the partials in x-block order and writes F (and the
+// terms) to the caller's row; thread 0 then takes the first minimum of the row that was written.
+// ------------------------------------------------------------------------- //
+__global__ void __launch_bounds__(64) k_space_aware_finish(int B, int A, int O, int XB, const int32_t* __restrict__ perm /* or nullptr */,
+                                                           const double* __restrict__ part, int objective, double* f_o,
+                                                           int32_t* __restrict__ action_o, double* __restrict__ terms_o /* or nullptr */) {
+    const int b = blockIdx.x;
+    const int64_t d = perm ? perm[b] : b;
+    for (int a = threadIdx.x; a < A; a += 64) {
+        double f = 0.0;
+        for (int o = 0; o < O; ++o) {
+            double Z = 0.0, N = 0.0, D = 0.0;
+            for (int x = 0; x < XB; ++x) {
+                const double* p = part + ((((int64_t)x * B + b) * A + a) * O + o) * 3;
+                Z += p[0];
+                N += p[1];
+                D += p[2];
+            }
+            if (terms_o != nullptr) {
+                double* t = terms_o + ((d * A + a) * O + o) * 3;
+                t[0] = Z;
+                t[1] = N;
+                t[2] = D;
+            }
+            if (Z != 0.0) {
+                if (objective == 1) {
+                    f += D;
+                } else {
+                    const double H = fmax(0.0, log(Z) - N / Z);
+                    const double x = fmax(1.0, D / Z + (exp(H) - 1.0) * 0.5);
+                    f += Z * log2(x);
+                }
+            }
+        }
+        f_o[d * A + a] = f;
+    }
+    __syncthreads();                                        // the row is complete (written by this block)
+    if (threadIdx.x == 0) {
+        const double* row = f_o + d * A;
+        int best = 0;
+        double bv = row[0];
+        if (bv != bv) bv = std::numeric_limits<double>::infinity();
+        for (int a = 1; a < A; ++a) {
+            const double x = row[a];
+            if (x < bv) {
+                bv = x;
+                best = a;
+            }
+        }
+        action_o[d] = best;
+    }
+}
+
+template <typename T>
+hipError_t launch_space_aware(const T* bel, int ldb, int B, ModelView<T> mv, const int32_t* in_ptr, const int32_t* in_src,
+                              const double* wgt, const int32_t* perm, double* part, int objective, double* f_out,
+                              int32_t* action_out, double* terms_out, hipStream_t st) {
+    if (B <= 0) return hipSuccess;
+    if (B > 65535 || mv.A > 65535 || mv.S > ldb || wgt == nullptr || part == nullptr || f_out == nullptr || action_out == nullptr ||
+        (objective != 0 && objective != 1))
+        return hipErrorInvalidValue;
+    const int XB = succ_entropy_xblocks(mv.S);
+    hipLaunchKernelGGL(k_succ_weighted<T>, dim3(XB, (B + TILE_NB - 1) / TILE_NB, mv.A), dim3(256), 0, st, bel, ldb, B, mv, in_ptr, in_src,
+                       wgt, part);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_space_aware_finish, dim3(B), dim3(64), 0, st, B, mv.A, mv.O, XB, perm, part, objective, f_out, action_out,
+                       terms_out);
+    return hipGetLastError();
+}
+
 // explicit instantiations
 #define PBVI_INST(T)                                                                                                   \
+    template hipError_t launch_space_aware<T>(const T*, int, int, ModelView<T>, const int32_t*, const int32_t*,        \
+                                              const double*, const int32_t*, double*, int, double*, int32_t*, double*, \
+                                              hipStream_t);                                                            \
     template hipError_t launch_infotaxis<T>(const T*, int, int, ModelView<T>, const int32_t*, const int32_t*,          \
                                             const int32_t*, double*, double*, int32_t*, double*, double*, hipStream_t); \
     template hipError_t launch_rollout_draw<T>(const RolloutStep&, ModelView<T>, const RolloutEnv*, hipStream_t);        \

@@ -967,13 +967,15 @@ enum RolloutSource {
     ROLLOUT_VALUE_MAX = 0,            // alpha_actions[first argmax_v b.alpha_v]       (pbvi_rollout, lookahead 0)
     ROLLOUT_Q = 1,                    // first argmax_a Q(b, a)                        (pbvi_rollout, lookahead 1)
     ROLLOUT_INFOTAXIS = 2,            // first argmin_a of the expected successor entropy (pbvi_rollout_infotaxis)
+    ROLLOUT_SPACE_AWARE = 3,          // first argmin_a of pbvi_space_aware's F, RolloutCall::objective (pbvi_rollout_space_aware)
 };
 
-// One rollout call, as pbvi_rollout / pbvi_rollout_infotaxis / pbvi_rollout_env fill it
+// One rollout call, as pbvi_rollout / pbvi_rollout_infotaxis / pbvi_rollout_env / pbvi_rollout_space_aware fill it
 struct RolloutCall {
     int source;                                // RolloutSource (anything else is refused)
     const int32_t* alpha_actions = nullptr;    // [V], read by ROLLOUT_VALUE_MAX
     double gamma = 0.0;                        // read by ROLLOUT_Q
+    int objective = 0;                         // read by ROLLOUT_SPACE_AWARE: 0 space-aware, 1 expected weight
     const int32_t* start_states;               // [B]
     const uint8_t* end_mask;                   // [S]
     uint64_t first_sim_id, seed;
@@ -1072,6 +1074,9 @@ class EngineBase {
                                         int32_t* best_v, double* best_score, int32_t* queue, uint8_t* dead, int32_t* perm) = 0;
     virtual int rollout(const RolloutCall& call) = 0;
     virtual int infotaxis(double* out_g, int32_t* out_action, double* out_p_obs, double* out_entropy) = 0;
+    virtual int state_weights_set(const double* w) = 0;
+    virtual int state_weights_clear() = 0;
+    virtual int space_aware(int objective, double* out_f, int32_t* out_action, double* out_terms) = 0;
     // the HSVI upper bound: the device point store, its sawtooth on the resident block, the bound-greedy action values
     virtual int upper_reset(const double* corner) = 0;
     virtual int upper_append(const double* points, const double* values, const double* gaps, int64_t n) = 0;
@@ -1189,6 +1194,11 @@ class EngineT : public EngineBase {
     // pbvi_infotaxis: the x-blocks' (Z, N) partials [XB][B][A][O][2]; G [B][A], its first argmin [B], P(o | b, a) [B][A][O]
     // and the beliefs' own entropies [B], all four in the caller's belief order
     DevBuf it_part_{mem_}, it_g_{mem_}, it_act_{mem_}, it_pobs_{mem_}, it_h_{mem_};
+    // pbvi_state_weights_set: w [S] fp64 (a working buffer: after_oom() releases it and no weights are set).  pbvi_space_aware:
+    // the x-blocks' (Z, N, D) partials [XB][B][A][O][3]; F [B][A], its first argmin [B] and the terms [B][A][O][3], caller order
+    DevBuf sw_{mem_};
+    bool sw_set_ = false;
+    DevBuf sa_part_{mem_}, sa_f_{mem_}, sa_act_{mem_}, sa_terms_{mem_};
     DevBuf bu_mpart_{mem_};   // bayes_push(fixed_order): the push blocks' partial masses [B][ceil(S/256)]
     // pbvi_upper_*: the point store of the HSVI upper bound -- CSR rows (ub_ptr_ int64 [P+1], ub_idx_ int32 / ub_val_ fp64 [entries]),
     // per point its entries, value and gap (ub_nnz_ int32, ub_v_ / ub_gap_ fp64 [P]), the corner values ub_c_ fp64 [S].  Working
@@ -1882,6 +1892,60 @@ class EngineT : public EngineBase {
                              {out_entropy, it_h_.p, (size_t)blk_.B * sizeof(double)}});
     }
 
+    // ---- space-aware infotaxis (pbvi_state_weights_set / _clear, pbvi_space_aware) ---- //
+    int state_weights_set(const double* w) override {
+        if (!w) FAIL(PBVI_EINVAL, "state_weights_set: NULL weights");
+        for (int s = 0; s < S_; ++s)
+            if (!std::isfinite(w[s]) || w[s] < 0.0)
+                FAIL(PBVI_EINVAL, "state_weights_set: weight " + std::to_string(s) + " is negative or not finite");
+        HIPCHK(hipSetDevice(device_));
+        HIPCHK(hipStreamSynchronize(stream_));               // a kernel of an earlier call may still read the old weights
+        sw_set_ = false;
+        int rc = sw_.ensure((size_t)S_ * sizeof(double));
+        if (rc) return rc;
+        HIPCHK(hipMemcpy(sw_.p, w, (size_t)S_ * sizeof(double), hipMemcpyHostToDevice));
+        sw_set_ = true;
+        return PBVI_OK;
+    }
+    int state_weights_clear() override {
+        HIPCHK(hipSetDevice(device_));
+        HIPCHK(hipStreamSynchronize(stream_));
+        sw_.release();
+        sw_set_ = false;
+        return PBVI_OK;
+    }
+
+    // pbvi_space_aware's F of the resident block into sa_f_ / sa_act_ (/ sa_terms_), caller order, left on the device.  Reads
+    // the block, the model tables and the weights only.
+    int space_aware_device(int objective, bool want_terms) {
+        if (objective != 0 && objective != 1) FAIL(PBVI_EINVAL, "space_aware: objective must be 0 (space-aware) or 1 (expected weight)");
+        if (!sw_set_) FAIL(PBVI_EINVAL, "space_aware: no state weights set (call pbvi_state_weights_set)");
+        if ((int64_t)S_ * R_ > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "space_aware: S*R exceeds int32");
+        int rc = build_inverse_lists();
+        if (rc) return rc;
+        const size_t ba = (size_t)blk_.B * A_;
+        if ((rc = sa_part_.ensure((size_t)succ_entropy_xblocks(S_) * ba * O_ * 3 * sizeof(double)))) return rc;
+        if ((rc = sa_f_.ensure(ba * sizeof(double)))) return rc;
+        if ((rc = sa_act_.ensure((size_t)blk_.B * sizeof(int32_t)))) return rc;
+        if (want_terms && (rc = sa_terms_.ensure(ba * O_ * 3 * sizeof(double)))) return rc;
+        HIPCHK(launch_space_aware<T>(blk_.rows.as<T>(), S_pad_, (int)blk_.B, view(), in_ptr_.as<int32_t>(), in_src_.as<int32_t>(),
+                                     sw_.as<double>(), blk_.sorted ? blk_.perm.as<int32_t>() : nullptr, sa_part_.as<double>(),
+                                     objective, sa_f_.as<double>(), sa_act_.as<int32_t>(),
+                                     want_terms ? sa_terms_.as<double>() : nullptr, stream_));
+        return PBVI_OK;
+    }
+
+    int space_aware(int objective, double* out_f, int32_t* out_action, double* out_terms) override {
+        if (!out_f) FAIL(PBVI_EINVAL, "space_aware: NULL out_f");
+        if (blk_.B <= 0) FAIL(PBVI_EINVAL, "space_aware: no belief block resident (call pbvi_beliefs_set)");
+        HIPCHK(hipSetDevice(device_));
+        int rc = space_aware_device(objective, out_terms != nullptr);
+        if (rc) return rc;
+        return out_.deliver({{out_f, sa_f_.p, (size_t)blk_.B * A_ * sizeof(double)},
+                             {out_action, sa_act_.p, (size_t)blk_.B * sizeof(int32_t)},
+                             {out_terms, sa_terms_.p, (size_t)blk_.B * A_ * O_ * 3 * sizeof(double)}});
+    }
+
     // ---- HSVI upper bound (pbvi_upper_reset / _append / _count / _bound / _q) ---- //
     int upper_reset(const double* corner) override {
         if (!corner) FAIL(PBVI_EINVAL, "upper_reset: NULL corner values");
@@ -2112,27 +2176,29 @@ class EngineT : public EngineBase {
         return PBVI_OK;
     }
 
-    // T lock-step simulation steps of the resident block on the device (pbvi_rollout, pbvi_rollout_infotaxis, pbvi_rollout_env).
-    // Per step: the action source's stage with its index left on the device (value-max or Q-values against the resident alpha
-    // set, or the successor entropies of infotaxis_device); the simulator draw (the model's own joint draw, or the successor
-    // from the model and the observation from the environment); the first half of the Bayes step for the rows not done; with
+    // T lock-step simulation steps of the resident block on the device (pbvi_rollout, pbvi_rollout_infotaxis, pbvi_rollout_env,
+    // pbvi_rollout_space_aware).  Per step: the action source's stage with its index left on the device (value-max or Q-values
+    // against the resident alpha set, the successor entropies of infotaxis_device, or space_aware_device's F); the simulator
+    // draw (the model's own joint draw, or the successor from the model and the observation from the environment); the first half of the Bayes step for the rows not done; with
     // an environment the lost rule on their masses; the done-filter; the norm of the rows that go on.  Finished and lost rows
     // are dropped after EVERY step ("Device-resident rollouts"): the one host read per step is the survivor count,
     // which sizes the next step's launches.
     int rollout(const RolloutCall& call) override {
         const int source = call.source;
-        const bool env = call.env, uses_alpha = source != ROLLOUT_INFOTAXIS;
+        const bool env = call.env, uses_alpha = source != ROLLOUT_INFOTAXIS && source != ROLLOUT_SPACE_AWARE;
         const int64_t n_steps = call.T;
-        if (env && source != ROLLOUT_VALUE_MAX && source != ROLLOUT_Q && source != ROLLOUT_INFOTAXIS)
-            FAIL(PBVI_EINVAL, "rollout_env: policy must be 0 (value-max), 1 (Q) or 2 (infotaxis)");
         if (env && env_kind_ == ENV_NONE) FAIL(PBVI_EINVAL, "rollout_env: no environment set (call pbvi_env_set_frames or pbvi_env_set_table)");
         if (env && call.end_observation >= O_) FAIL(PBVI_EINVAL, "rollout_env: end_observation is not below O");
         if (env && call.shifts && env_kind_ != ENV_FRAMES) FAIL(PBVI_EINVAL, "rollout_env: shifts are for a frame environment, and a table is set");
         if (uses_alpha && V_ <= 0) FAIL(PBVI_EINVAL, "rollout: no alpha set resident (call pbvi_alpha_set)");
         if (blk_.B <= 0) FAIL(PBVI_EINVAL, "rollout: no belief block resident (call pbvi_beliefs_set)");
         if ((uses_alpha && !call.alpha_actions) || !call.start_states || !call.end_mask) FAIL(PBVI_EINVAL, "rollout: NULL argument");
-        if (source != ROLLOUT_VALUE_MAX && source != ROLLOUT_Q && source != ROLLOUT_INFOTAXIS)
+        if (source != ROLLOUT_VALUE_MAX && source != ROLLOUT_Q && source != ROLLOUT_INFOTAXIS && source != ROLLOUT_SPACE_AWARE)
             FAIL(PBVI_EINVAL, "rollout: lookahead must be 0 or 1");
+        if (source == ROLLOUT_SPACE_AWARE && call.objective != 0 && call.objective != 1)
+            FAIL(PBVI_EINVAL, "rollout_space_aware: objective must be 0 (space-aware) or 1 (expected weight)");
+        if (source == ROLLOUT_SPACE_AWARE && !sw_set_)
+            FAIL(PBVI_EINVAL, "rollout_space_aware: no state weights set (call pbvi_state_weights_set)");
         if (n_steps < 1) FAIL(PBVI_EINVAL, "rollout: T must be at least 1");
         if (source == ROLLOUT_Q && mode_ != PBVI_SPARSE)
             FAIL(PBVI_EUNSUPPORTED, "rollout: lookahead = 1 is not available on a PBVI_DENSE engine (create it with PBVI_SPARSE)");
@@ -2158,10 +2224,10 @@ class EngineT : public EngineBase {
                                       " exceeds the " + std::to_string(env_F_) + " frames of the environment");
         }
         HIPCHK(hipSetDevice(device_));
-        // Infotaxis meets near-ties between actions on symmetric beliefs, and a rollout against an environment promises the same
-        // bits however a run is cut into blocks: neither may hang on the arrival order of the norm's atomics, so their Bayes
-        // step sums the norm in a fixed order.
-        const bool fixed_order = env || source == ROLLOUT_INFOTAXIS;
+        // Infotaxis (plain or space-aware) meets near-ties between actions on symmetric beliefs, and a rollout against an
+        // environment promises the same bits however a run is cut into blocks: neither may hang on the arrival order of the
+        // norm's atomics, so their Bayes step sums the norm in a fixed order.
+        const bool fixed_order = env || source == ROLLOUT_INFOTAXIS || source == ROLLOUT_SPACE_AWARE;
         int rc;
         if (env) {
             if ((rc = ro_lost_.ensure((size_t)n0))) return rc;
@@ -2238,9 +2304,12 @@ class EngineT : public EngineBase {
             } else if (source == ROLLOUT_Q) {
                 if ((rc = run_q(call.gamma, false))) return rc;
                 rs.index = q_act_.as<int32_t>();              // caller row order, an action
-            } else {
+            } else if (source == ROLLOUT_INFOTAXIS) {
                 if ((rc = infotaxis_device(false, false))) return rc;
                 rs.index = it_act_.as<int32_t>();             // caller row order, an action
+            } else {
+                if ((rc = space_aware_device(call.objective, false))) return rc;
+                rs.index = sa_act_.as<int32_t>();             // caller row order, an action
             }
             rs.n = (int)blk_.B;
             rs.t = (int)t;
@@ -2666,6 +2735,7 @@ class EngineT : public EngineBase {
         env_F_ = env_C_ = 0;
         ub_count_ = ub_entries_ = 0;                         // (so were the point store's)
         ub_corner_ = false;
+        sw_set_ = false;                                     // (the weights were a working buffer)
         V_ = 0;
         block_emptied();
         prim_valid_ = alpha_on_primary_ = false;
@@ -5238,7 +5308,11 @@ int pbvi_rollout_env(pbvi_engine_t* e, int policy, const int32_t* alpha_actions,
                      const uint8_t* end_mask, int end_observation, const int64_t* shifts, uint64_t first_sim_id, uint64_t seed,
                      int64_t T, int32_t* out_states, int32_t* out_actions, int32_t* out_observations, int32_t* out_steps,
                      uint8_t* out_lost) {
+    using namespace pbvi;
     NEED(e);
+    // (the step loop knows a fourth source, pbvi_rollout_space_aware's: this entry point's numbers are refused here)
+    if (policy != pbvi::ROLLOUT_VALUE_MAX && policy != pbvi::ROLLOUT_Q && policy != pbvi::ROLLOUT_INFOTAXIS)
+        FAIL(PBVI_EINVAL, "rollout_env: policy must be 0 (value-max), 1 (Q) or 2 (infotaxis)");
     pbvi::RolloutCall c = rollout_call(start_states, end_mask, first_sim_id, seed, T, out_states, out_actions, out_observations, out_steps);
     c.source = policy;
     c.alpha_actions = alpha_actions;
@@ -5248,6 +5322,39 @@ int pbvi_rollout_env(pbvi_engine_t* e, int policy, const int32_t* alpha_actions,
     c.shifts = shifts;
     c.out_lost = out_lost;
     return e->impl->rollout(c);
+}
+int pbvi_state_weights_set(pbvi_engine_t* e, const double* weights) {
+    NEED(e);
+    return e->impl->state_weights_set(weights);
+}
+int pbvi_state_weights_clear(pbvi_engine_t* e) {
+    NEED(e);
+    return e->impl->state_weights_clear();
+}
+int pbvi_space_aware(pbvi_engine_t* e, int objective, double* out_f, int32_t* out_action, double* out_terms) {
+    NEED(e);
+    return e->impl->space_aware(objective, out_f, out_action, out_terms);
+}
+int pbvi_rollout_space_aware(pbvi_engine_t* e, int objective, int use_env, const int32_t* start_states, const uint8_t* end_mask,
+                             int end_observation, const int64_t* shifts, uint64_t first_sim_id, uint64_t seed, int64_t T,
+                             int32_t* out_states, int32_t* out_actions, int32_t* out_observations, int32_t* out_steps,
+                             uint8_t* out_lost) {
+    using namespace pbvi;
+    NEED(e);
+    if (use_env != 0 && use_env != 1) FAIL(PBVI_EINVAL, "rollout_space_aware: use_env must be 0 (the model's world) or 1 (the environment)");
+    if (!use_env && (end_observation != -1 || shifts != nullptr))
+        FAIL(PBVI_EINVAL, "rollout_space_aware: end_observation and shifts belong to an environment (use_env = 0 takes -1 and NULL)");
+    pbvi::RolloutCall c = rollout_call(start_states, end_mask, first_sim_id, seed, T, out_states, out_actions, out_observations, out_steps);
+    c.source = pbvi::ROLLOUT_SPACE_AWARE;
+    c.objective = objective;
+    c.env = use_env != 0;
+    c.end_observation = end_observation;
+    c.shifts = shifts;
+    c.out_lost = use_env ? out_lost : nullptr;
+    const int64_t n0 = e->impl->beliefs_count();
+    const int rc = e->impl->rollout(c);
+    if (rc == PBVI_OK && !use_env && out_lost && n0 > 0) memset(out_lost, 0, (size_t)n0);   // nothing is lost in the model's world
+    return rc;
 }
 int pbvi_beliefs_fetch(pbvi_engine_t* e, void* out_beliefs) {
     NEED(e);

@@ -39,6 +39,7 @@ EXPORTS = [
     'pbvi_debug_slabs_fill', 'pbvi_env_set_frames', 'pbvi_env_set_table', 'pbvi_env_clear', 'pbvi_rollout_env',
     'pbvi_debug_score_probe', 'pbvi_debug_score_probe_fetch', 'pbvi_debug_refine_counts', 'pbvi_debug_value_max_route',
     'pbvi_upper_reset', 'pbvi_upper_append', 'pbvi_upper_count', 'pbvi_upper_bound', 'pbvi_upper_q',
+    'pbvi_state_weights_set', 'pbvi_state_weights_clear', 'pbvi_space_aware', 'pbvi_rollout_space_aware',
 ]
 
 
@@ -142,6 +143,11 @@ def load_library(path: str = LIB_PATH):
         'pbvi_env_clear': (C.c_int, [vp]),
         'pbvi_rollout_env': (C.c_int, [vp, C.c_int, i32p, C.c_double, i32p, u8p, C.c_int, C.POINTER(C.c_int64), C.c_uint64,
                                        C.c_uint64, C.c_int64, i32p, i32p, i32p, i32p, u8p]),
+        'pbvi_state_weights_set': (C.c_int, [vp, f64p]),
+        'pbvi_state_weights_clear': (C.c_int, [vp]),
+        'pbvi_space_aware': (C.c_int, [vp, C.c_int, f64p, i32p, f64p]),
+        'pbvi_rollout_space_aware': (C.c_int, [vp, C.c_int, C.c_int, i32p, u8p, C.c_int, C.POINTER(C.c_int64), C.c_uint64,
+                                               C.c_uint64, C.c_int64, i32p, i32p, i32p, i32p, u8p]),
         'pbvi_beliefs_fetch': (C.c_int, [vp, vp]),
         'pbvi_beliefs_count': (C.c_int64, [vp]),
         'pbvi_mdp_value_iteration': (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, i32p, f64p, f64p, f64p,
@@ -1054,6 +1060,32 @@ class Engine:
             out += (ent,)
         return out
 
+    # -- space-aware infotaxis: state weights, F of the resident block ------------------------------------------------ #
+    def set_state_weights(self, w) -> None:
+        """The state weights of ``space_aware_resident`` / ``rollout_space_aware``: ``w [S]`` fp64, every entry finite and
+        ``>= 0`` (``pbvi_state_weights_set``) -- a distance to the source for space-aware infotaxis.  Touches nothing else."""
+        ww = np.ascontiguousarray(w, dtype=np.float64)
+        if ww.shape != (self.S,):
+            raise ValueError('weights must be [S]')
+        self._ck(self._lib.pbvi_state_weights_set(self._h, _p(ww, C.c_double)))
+
+    def clear_state_weights(self) -> None:
+        """No state weights; their device memory is returned (``pbvi_state_weights_clear``)."""
+        self._ck(self._lib.pbvi_state_weights_clear(self._h))
+
+    def space_aware_resident(self, objective: int = 0, want_terms: bool = False):
+        """Space-aware infotaxis for every belief of the resident block and every action (``pbvi_space_aware``): ``(F [B,A]
+        f64, argmin_a F [B])``.  ``objective=0``: ``F = sum_o Z log2(max(1, D/Z + (exp(H) - 1)/2))`` with ``H`` the entropy
+        (nats) and ``D/Z`` the expected weight of the successor; ``objective=1``: ``F = sum_o D``, the expected weight itself.
+        ``want_terms`` appends ``(Z, N, D) [B,A,O,3]``.  Needs weights (``set_state_weights``), no alpha set, and leaves the
+        block where it is."""
+        f = np.empty((self.B, self.A), dtype=np.float64)
+        act = np.empty(self.B, dtype=np.int32)
+        terms = np.empty((self.B, self.A, self.O, 3), dtype=np.float64) if want_terms else None
+        self._ck(self._lib.pbvi_space_aware(self._h, int(objective), _p(f, C.c_double), _p(act, C.c_int32), _p(terms, C.c_double)))
+        out = (f, act.astype(np.int64))
+        return out + (terms,) if want_terms else out
+
     # -- HSVI upper bound: device point store, sawtooth, bound-greedy action values -------------------------------- #
     def upper_reset(self, corner) -> None:
         """Empty the point store of the upper bound and set the corner values ``c [S]`` (``pbvi_upper_reset``)."""
@@ -1298,6 +1330,23 @@ class Engine:
         return self._rollout_call(lambda ss, em, *tail: self._lib.pbvi_rollout_env(self._h, policy, aap, float(gamma), ss, em,
                                                                                    int(end_observation), shp, *tail),
                                   start_states, end_mask, seed, T, first_sim_id, with_lost=True)
+
+    def rollout_space_aware(self, start_states, end_mask, seed: int, T: int, first_sim_id: int = 0, objective: int = 0,
+                            use_env: bool = False, shifts=None, end_observation: int = -1):
+        """``rollout`` with the space-aware policy (``pbvi_rollout_space_aware``): every step takes
+        ``space_aware_resident(objective)``'s argmin.  ``use_env=False``: the model's world, as ``rollout_infotaxis``
+        (``shifts`` and ``end_observation`` stay ``None`` / ``-1``).  ``use_env=True``: against the environment set with
+        ``set_environment_*``, with ``rollout_env``'s draw and lost rule.  Returns ``(states, actions, observations, steps,
+        lost)``; ``lost`` is all 0 in the model's world."""
+        shp = None
+        if shifts is not None:
+            sh = np.ascontiguousarray(shifts, dtype=np.int64)
+            if sh.shape != (self.B,):
+                raise ValueError('shifts must be [B]')
+            shp = _p(sh, C.c_int64)
+        return self._rollout_call(lambda ss, em, *tail: self._lib.pbvi_rollout_space_aware(
+            self._h, int(objective), int(bool(use_env)), ss, em, int(end_observation), shp, *tail),
+            start_states, end_mask, seed, T, first_sim_id, with_lost=True)
 
     def fetch_beliefs(self) -> np.ndarray:
         """The resident belief block, ``[B,S]`` in caller order."""

@@ -1713,7 +1713,14 @@ def rollout_env_numpy(model, env, policy: int, alpha, alpha_actions, beliefs, st
     else:
         block = _HostBeliefBlock(m, SimpleNamespace(alpha_vector_array=alpha), b)
         choose = (lambda: block.best_actions(gamma)) if policy == 1 else (lambda: acts[block.best_vectors()])
-    shifts = env.check(m.state_count, m.action_count, m.observation_count, b.shape[0], T)
+    return _rollout_env_loop(m, env, block, choose, s, seed, first_sim_id, T, table_dtype, return_beliefs)
+
+
+def _rollout_env_loop(m, env, block, choose, s, seed: int, first_sim_id: int, T: int, table_dtype, return_beliefs: bool):
+    """``_rollout_loop`` against ``env``, for whatever policy ``choose`` is (``rollout_env_numpy``,
+    ``rollout_space_aware_numpy``): the environment's checks, then the observation hook -- the frame of the simulation's
+    shift, or a draw from the table's row with the second uniform; ``env.end_observation`` on landing in an end state."""
+    shifts = env.check(m.state_count, m.action_count, m.observation_count, s.shape[0], T)
     end_obs = env.end_observation
 
     def observe(t, rows, ids, a, sn, done):
@@ -1795,6 +1802,151 @@ def rollout_infotaxis_numpy(model, beliefs, start_states, seed: int, first_sim_i
                          return_beliefs)
 
 
+# --------------------------------------------------------------------------- #
+# Space-aware infotaxis (Loisy & Eloy 2022): greedy for J = log2(D + 2^(H-1) - 1/2) of the next belief, D its expected
+# distance to the source and H its entropy in bits (what ``pbvi_space_aware`` computes)
+# --------------------------------------------------------------------------- #
+SPACE_AWARE_OBJECTIVES = {'space_aware': 0, 'expected_weight': 1}
+
+
+def _state_weights(S: int, weights) -> np.ndarray:
+    """``weights`` as the engine takes them: ``[S]`` fp64, every entry finite and ``>= 0``."""
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.shape != (S,):
+        raise ValueError(f'weights must be [{S}]')
+    if not np.all(np.isfinite(w)) or np.any(w < 0):
+        raise ValueError('weights must be finite and >= 0')
+    return w
+
+
+def _space_aware_objective(objective) -> int:
+    objective = SPACE_AWARE_OBJECTIVES.get(objective, objective)
+    if isinstance(objective, bool) or objective not in (0, 1):
+        raise ValueError(f"objective must be 0 / 'space_aware' or 1 / 'expected_weight', not {objective!r}")
+    return int(objective)
+
+
+def manhattan_to_end_states(model) -> np.ndarray:
+    """``w [S]``: for every state the smallest ``|d row| + |d col|`` on ``model.state_grid`` to any end state -- the distance
+    space-aware infotaxis uses.  Wrap-around is ignored: on a grid whose moves wrap, the distance is still measured inside
+    the rectangle.  ``ValueError`` without end states, or with a state that is not on the grid."""
+    m = model.cpu_model if getattr(model, 'is_on_gpu', False) else model
+    S = int(m.state_count)
+    ends = np.asarray(m.end_states, dtype=np.int64).ravel()
+    if ends.size == 0:
+        raise ValueError('the model has no end states: there is nothing to measure a distance to')
+    grid = np.asarray(m.state_grid)
+    pos = np.full((S, 2), -1, dtype=np.int64)
+    rows, cols = np.indices(grid.shape)
+    on = (grid >= 0) & (grid < S)
+    pos[grid[on], 0], pos[grid[on], 1] = rows[on], cols[on]
+    if np.any(pos < 0):
+        raise ValueError('every state must have a cell on state_grid')
+    best = np.full(S, np.iinfo(np.int64).max, dtype=np.int64)
+    step = max(1, (1 << 22) // S)                                 # [S, step] int64 at a time: ~32 MiB
+    for i0 in range(0, ends.size, step):
+        e = pos[ends[i0:i0 + step]]
+        dist = np.abs(pos[:, None, 0] - e[None, :, 0]) + np.abs(pos[:, None, 1] - e[None, :, 1])
+        best = np.minimum(best, dist.min(axis=1))
+    return best.astype(np.float64)
+
+
+def space_aware_terms(model, beliefs, weights, table_dtype=np.float64, rows_at_once: Union[int, None] = None):
+    """The three sums ``pbvi_space_aware`` forms per (belief, action, observation), on the host, and the magnitudes of their
+    terms: ``(Z, N, D, M_Z, M_N, M_D)``, each ``[n,A,O]``.  With ``u`` the un-normalised successor of ``infotaxis_numpy``
+    (``_successor_rows``: ``np.bincount``'s order; the table cast to ``table_dtype`` and widened):
+
+        ``Z = sum_s' u``,   ``N = sum_s' u ln u``,   ``D = sum_s' u w``        (``u == 0`` adds 0)
+
+    ``M_Z = Z``, ``M_N = sum_s' |u ln u|`` and ``M_D = D`` (the terms of ``Z`` and ``D`` are non-negative) are what a
+    rounding-error bound for a re-ordered evaluation of each sum scales with."""
+    m = _rollout_tables(model)
+    S, A, O, R = m.state_count, m.action_count, m.observation_count, m.reachable_state_count
+    b = np.asarray(beliefs, dtype=np.float64)
+    if b.ndim != 2 or b.shape[1] != S:
+        raise ValueError(f'beliefs must be a [*, {S}] array')
+    w = _state_weights(S, weights)
+    n = b.shape[0]
+    rto = np.ascontiguousarray(m.reachable_transitional_observation_table, dtype=table_dtype).astype(np.float64)
+    rs = np.asarray(m.reachable_states).astype(np.int64)
+    Z, N, D, MN = (np.zeros((n, A, O)) for _ in range(4))
+    step = max(1, (1 << 22) // (S * R)) if rows_at_once is None else int(rows_at_once)
+    for i0 in range(0, n, step):
+        i1 = min(i0 + step, n)
+        for a, o, u in _successor_rows(b[i0:i1], rs, rto):
+            ulu = _xlogx(u)
+            Z[i0:i1, a, o] = np.sum(u, axis=1)
+            N[i0:i1, a, o] = np.sum(ulu, axis=1)
+            MN[i0:i1, a, o] = np.sum(np.abs(ulu), axis=1)
+            D[i0:i1, a, o] = np.sum(u * w[None, :], axis=1)
+    return Z, N, D, Z, MN, D
+
+
+def space_aware_j(Z, N, D) -> np.ndarray:
+    """``J = log2(max(1, D/Z + (exp(H) - 1)/2))`` with ``H = max(0, ln Z - N/Z)``, element by element; 0 where ``Z == 0``.
+    Both clamps are part of the definition (``max`` as C's ``fmax``): rounding can leave ``ln Z - N/Z`` slightly negative,
+    and a successor known to sit on the source has ``J = 0``."""
+    Z, N, D = (np.asarray(x, dtype=np.float64) for x in (Z, N, D))
+    ok = Z != 0
+    J = np.zeros(Z.shape)
+    with np.errstate(all='ignore'):
+        z, nn, d = Z[ok], N[ok], D[ok]
+        H = np.fmax(0.0, np.log(z) - nn / z)
+        J[ok] = np.log2(np.fmax(1.0, d / z + (np.exp(H) - 1.0) * 0.5))
+    return J
+
+
+def space_aware_from_terms(Z, N, D, objective=0) -> np.ndarray:
+    """``F [..., A]`` from the terms ``[..., A, O]``: objective 0 ``sum_o Z J`` (``space_aware_j``), objective 1 ``sum_o D``;
+    both sums sequential over ``o``, an observation with ``Z == 0`` adds 0."""
+    objective = _space_aware_objective(objective)
+    Z, D = np.asarray(Z, dtype=np.float64), np.asarray(D, dtype=np.float64)
+    with np.errstate(all='ignore'):
+        terms = np.where(Z != 0, D if objective == 1 else Z * space_aware_j(Z, N, D), 0.0)
+    F = np.zeros(Z.shape[:-1])
+    for o in range(Z.shape[-1]):
+        F = F + terms[..., o]
+    return F
+
+
+def space_aware_numpy(model, beliefs, weights, objective=0, table_dtype=np.float64):
+    """Space-aware infotaxis for every row of ``beliefs [n,S]`` and every action, on the host: what ``pbvi_space_aware``
+    computes on the device.  ``weights [S]``: finite, ``>= 0`` -- the distance of every state to the source.  Per (a, o), with
+    ``space_aware_terms``' sums, ``H = max(0, ln Z - N/Z)`` is the entropy of the successor belief (nats) and ``D/Z`` its
+    expected weight;
+
+        objective 0 / ``'space_aware'``:      ``F[b,a] = sum_o Z log2(max(1, D/Z + (exp(H) - 1)/2))``
+        objective 1 / ``'expected_weight'``:  ``F[b,a] = sum_o D``
+
+    Returns ``(F [n,A], action [n], terms [n,A,O,3])``: ``action`` is ``infotaxis_first_argmin(F)``, ``terms`` holds
+    ``(Z, N, D)``."""
+    Z, N, D, _, _, _ = space_aware_terms(model, beliefs, weights, table_dtype)
+    F = space_aware_from_terms(Z, N, D, objective)
+    return F, infotaxis_first_argmin(F), np.stack([Z, N, D], axis=-1)
+
+
+def rollout_space_aware_numpy(model, beliefs, start_states, weights, seed: int, first_sim_id: int, T: int, objective=0,
+                              table_dtype=np.float64, return_beliefs: bool = False, env=None):
+    """``rollout_numpy`` with the space-aware policy, on the host: what ``pbvi_rollout_space_aware`` computes on the device.
+    Per step and running simulation the action is ``space_aware_numpy(model, b, weights, objective, table_dtype)``'s.
+    ``env=None``: the model's world -- the uniform, the draw, the Bayes update, the done-filter and the return value are
+    ``rollout_numpy``'s.  ``env`` (a ``FrameEnvironment`` or ``TableEnvironment``): the successor draw, the observation, the
+    lost rule and the return value (``lost [n]`` last) are ``rollout_env_numpy``'s."""
+    objective = _space_aware_objective(objective)
+    if env is not None:
+        if not isinstance(env, (FrameEnvironment, TableEnvironment)):
+            raise ValueError('env must be a FrameEnvironment or a TableEnvironment')
+        if int(T) >= 1 << 31:
+            raise ValueError('T must be below 2**31')
+    m, T, b, s, _, _ = _rollout_inputs(model, beliefs, start_states, T)
+    w = _state_weights(m.state_count, weights)
+    block = _HostBeliefBlock(m, None, b)
+    choose = lambda: block.space_aware_actions(w, objective, table_dtype)
+    if env is None:
+        return _rollout_loop(m, block, choose, s, seed, first_sim_id, T, table_dtype, return_beliefs)
+    return _rollout_env_loop(m, env, block, choose, s, seed, first_sim_id, T, table_dtype, return_beliefs)
+
+
 class _HostBeliefBlock:
     """Belief block of the parallel simulator held in NumPy (reference CPU statements, ``:3029``, ``:3306-3311``)."""
 
@@ -1812,6 +1964,10 @@ class _HostBeliefBlock:
     def infotaxis_actions(self, table_dtype=np.float64) -> np.ndarray:
         """Infotaxis: the first ``argmin_a`` of the expected successor entropy of every belief of the block."""
         return infotaxis_numpy(self.m, self.b, table_dtype)[1]
+
+    def space_aware_actions(self, weights, objective: int = 0, table_dtype=np.float64) -> np.ndarray:
+        """Space-aware infotaxis: the first ``argmin_a`` of ``space_aware_numpy``'s ``F`` of every belief of the block."""
+        return space_aware_numpy(self.m, self.b, weights, objective, table_dtype)[1]
 
     def _push(self, actions: np.ndarray, observations: np.ndarray) -> np.ndarray:
         """The un-normalised Bayes step of every row: ``u[b, s'] = sum_{(s,r): rs[s,a,r] = s'} b[s] RTO[s,a,o,r]``."""
@@ -1888,6 +2044,20 @@ class _DeviceBeliefBlock:
         for c in self.chunks:
             self.eng.set_beliefs(c)
             out.append(self.eng.infotaxis_resident()[1])
+        return np.concatenate(out) if out else np.zeros(0, dtype=np.int64)
+
+    def space_aware_actions(self, weights, objective: int = 0) -> np.ndarray:
+        """Space-aware infotaxis: the first ``argmin_a`` of ``pbvi_space_aware``'s ``F`` of every belief of the block (the
+        weights are uploaded once per block; the resident block stays on the device)."""
+        if getattr(self, '_weights', None) is not weights:
+            self.eng.set_state_weights(weights)
+            self._weights = weights
+        if self.chunks is None:
+            return self.eng.space_aware_resident(objective)[1]
+        out = []
+        for c in self.chunks:
+            self.eng.set_beliefs(c)
+            out.append(self.eng.space_aware_resident(objective)[1])
         return np.concatenate(out) if out else np.zeros(0, dtype=np.int64)
 
     def advance(self, actions: np.ndarray, observations: np.ndarray, keep: np.ndarray) -> None:
@@ -2232,6 +2402,62 @@ class Infotaxis_Agent(Agent):
         else:
             acts = infotaxis_numpy(self.model, arr)[1]
         return int(acts[0]) if single else acts
+
+
+class SpaceAware_Agent(Agent):
+    """Space-aware infotaxis (Loisy & Eloy 2022): the greedy policy for ``J(b) = log2(D(b) + 2^(H(b) - 1) - 1/2)`` of the next
+    belief, ``D`` its expected distance to the source and ``H`` its entropy in bits (``space_aware_numpy``) -- the baseline
+    that beats infotaxis and comes close to solved policies.  ``weights [S]``: the distance of every state to the source,
+    by default ``manhattan_to_end_states(model)``.  ``objective='expected_weight'``: greedy for the expected weight of the
+    next belief alone (greedy distance; with ``weights = max(V_MDP) - V_MDP`` a QMDP-style policy).  It takes no value
+    function; a model on the GPU (``model.to_gpu()``) has the HIP engine evaluate it (``pbvi_space_aware``,
+    ``pbvi_rollout_space_aware``).  ``simulate``, ``run_n_simulations`` and ``run_n_simulations_parallel(...,
+    device_rng_seed=, environment=)`` are ``Agent``'s with this policy."""
+
+    def __init__(self, model: Model, weights=None, objective='space_aware') -> None:
+        super().__init__(model, None)
+        self.objective = _space_aware_objective(objective)
+        self.weights = _state_weights(model.state_count, manhattan_to_end_states(model) if weights is None else weights)
+
+    def _on_gpu(self) -> bool:
+        return bool(self.model.is_on_gpu)
+
+    def _block_actions(self, block) -> np.ndarray:
+        return block.space_aware_actions(self.weights, self.objective)
+
+    def get_best_action(self, belief):
+        """The space-aware action for one ``Belief`` (returns int) or a ``[n,S]`` array."""
+        single = isinstance(belief, Belief)
+        arr = belief.values[None, :] if single else belief
+        if self.model.is_on_gpu:
+            eng = self.model.engine
+            eng.set_state_weights(self.weights)
+            parts = []
+            for i0 in range(0, arr.shape[0], _DeviceBeliefBlock.CHUNK):      # the engine takes 65535 beliefs at a time
+                eng.set_beliefs(arr[i0:i0 + _DeviceBeliefBlock.CHUNK])
+                parts.append(eng.space_aware_resident(self.objective)[1])
+            acts = parts[0] if len(parts) == 1 else np.concatenate(parts)
+        else:
+            acts = space_aware_numpy(self.model, arr, self.weights, self.objective)[1]
+        return int(acts[0]) if single else acts
+
+    def _counter_trajectories(self, model: Model, b0: np.ndarray, start_states: np.ndarray, seed: int, T: int, env=None):
+        """``Agent._counter_trajectories`` for this policy: ``pbvi_rollout_space_aware`` when the model is on the GPU (weights
+        and environment uploaded first), ``rollout_space_aware_numpy`` otherwise."""
+        if not self._on_gpu():
+            return rollout_space_aware_numpy(model, b0, start_states, self.weights, seed, 0, T, self.objective, env=env)
+        shifts = None
+        if env is not None:
+            shifts = env.check(model.state_count, model.action_count, model.observation_count, b0.shape[0], T)
+        eng, end_mask = model.engine, self._end_mask(model)
+        eng.set_state_weights(self.weights)
+        if env is not None:
+            eng.hold_environment(env)
+        end_obs = -1 if env is None else env.end_observation
+        call = lambda s0, first, sh: eng.rollout_space_aware(s0, end_mask, seed, T, first_sim_id=first, objective=self.objective,
+                                                             use_env=env is not None, shifts=sh, end_observation=end_obs)
+        out = self._rollout_chunks(eng, b0, start_states, shifts, call)
+        return out if env is not None else out[:4]
 
 
 # --------------------------------------------------------------------------- #
