@@ -357,32 +357,41 @@ hipError_t launch_rollout_lost(const RolloutStep& rs, const double* mass, uint8_
 hipError_t launch_rollout_compact(const RolloutStep& rs, int32_t* dst, int32_t* state_out, int32_t* orig_out, int* count,
                                   hipStream_t st);
 
-// Infotaxis (pbvi_infotaxis): for every belief row b of `bel` (engine order; caller row d = perm ? perm[b] : b) and action a
-//   G[b,a] = sum_o (Z ln Z - N),  Z = sum_s' u[s'],  N = sum_s' u[s'] ln u[s']  (zero terms add 0; fp64 log),
-//   u[s']  = sum over the inverse list of (a, s') of (double) bel[b][s] * (double) RTO[s,a,o,r]  (successor.h: successor_tile)
-// = the expected entropy, in nats, of the belief after taking a.  Three kernels, no atomics, every sum in a fixed order:
-//   k_succ_entropy<T>   (Z, N) partials of each x-block (succ_entropy_xblocks(S) of them) into part [XB][B][A][O][2]
-//   k_infotaxis_finish  partials summed in x-block order -> g_out [B][A], pobs_out [B][A][O] = Z (or nullptr), action_out [B] =
-//                       the first a with G[b,a] strictly below every earlier one (a NaN never wins; all NaN -> 0), taken from
-//                       the row of g_out as written; all three in the caller's belief order
+// The greedy successor policies (pbvi_infotaxis, pbvi_space_aware): for every belief row b of `bel` (engine order; caller row
+// d = perm ? perm[b] : b), action a and observation o
+//   u[s'] = sum over the inverse list of (a, s') of (double) bel[b][s] * (double) RTO[s,a,o,r]  (successor.h: successor_tile)
+//   Z = sum_s' u[s'],   N = sum_s' u[s'] ln u[s'],   D = sum_s' u[s'] * wgt[s']      (zero terms add 0; fp64 log)
+// and a score per (b, a), summed sequentially over o; an observation with Z == 0 adds 0:
+//   SUCC_ENTROPY          sum_o (Z ln Z - N): the expected entropy, in nats, of the belief after taking a
+//   SUCC_SPACE_AWARE      sum_o Z * log2(max(1, D / Z + (exp(H) - 1) / 2)),  H = max(0, ln Z - N / Z)
+//   SUCC_EXPECTED_WEIGHT  sum_o D
+// No atomics, every sum in a fixed order:
+//   k_succ_entropy<T>   (Z, N) partials of each x-block (succ_entropy_xblocks(S) of them) into part [XB][B][A][O][2]   (SUCC_ENTROPY)
+//   k_succ_weighted<T>  the same walk with a third accumulator set: (Z, N, D) partials into part [XB][B][A][O][3]     (the other two)
+//   k_succ_finish<2|3>  partials summed in x-block order -> score_out [B][A]; extra_out (or nullptr) = the summed terms, Z alone
+//                       [B][A][O] for SUCC_ENTROPY, (Z, N, D) [B][A][O][3] otherwise; action_out [B] = the first a whose score is
+//                       strictly below every earlier one (a NaN never wins; all NaN -> 0), taken from the row of score_out as
+//                       written; all three in the caller's belief order
 //   k_row_entropy<T>    entropy_out [B] = -sum_s b[s] ln b[s] (or nullptr: not launched), caller order
+enum SuccObjective { SUCC_SPACE_AWARE = 0, SUCC_EXPECTED_WEIGHT = 1, SUCC_ENTROPY = 2 };   // 0 / 1: pbvi_space_aware's numbers
 int succ_entropy_xblocks(int S);
+inline int succ_terms(int objective) { return objective == SUCC_ENTROPY ? 2 : 3; }        // doubles per (x-block, b, a, o) of part
 template <typename T>
-hipError_t launch_infotaxis(const T* bel, int ldb, int B, ModelView<T> mv, const int32_t* in_ptr, const int32_t* in_src,
-                            const int32_t* perm, double* part, double* g_out, int32_t* action_out, double* pobs_out,
-                            double* entropy_out, hipStream_t st);
-
-// Space-aware infotaxis (pbvi_space_aware): u, Z and N as above and D = sum_s' u[s'] * wgt[s'] (wgt [S] fp64, u == 0 adds 0).
-//   H = max(0, ln Z - N / Z),  x = max(1, D / Z + (exp(H) - 1) / 2),  J = log2(x)       per (a, o) with Z != 0
-//   objective 0: F[b,a] = sum_o Z * J;   objective 1: F[b,a] = sum_o D                   (sequential over o)
-// Two kernels, no atomics, every sum in a fixed order:
-//   k_succ_weighted<T>    k_succ_entropy's walk with a third accumulator set: (Z, N, D) partials into part [XB][B][A][O][3]
-//   k_space_aware_finish  partials summed in x-block order -> f_out [B][A], terms_out [B][A][O][3] = (Z, N, D) (or nullptr),
-//                         action_out [B] = the first minimum of the row of f_out as written; caller's belief order
+struct SuccScores {
+    const T* bel;                     // [B][ldb] the block's rows, engine order
+    int ldb, B;
+    const int32_t* perm;              // [B] or nullptr
+    double* part;                     // [XB][B][A][O][succ_terms(objective)]
+    const double* wgt;                // [S] fp64; nullptr for SUCC_ENTROPY, which reads none
+    int objective;                    // SuccObjective
+    double* score_out;                // [B][A]
+    int32_t* action_out;              // [B]
+    double* extra_out;                // or nullptr
+    double* entropy_out;              // or nullptr
+};
 template <typename T>
-hipError_t launch_space_aware(const T* bel, int ldb, int B, ModelView<T> mv, const int32_t* in_ptr, const int32_t* in_src,
-                              const double* wgt, const int32_t* perm, double* part, int objective, double* f_out,
-                              int32_t* action_out, double* terms_out, hipStream_t st);
+hipError_t launch_successor_scores(const SuccScores<T>& ss, ModelView<T> mv, const int32_t* in_ptr, const int32_t* in_src,
+                                   hipStream_t st);
 
 // one step of the belief walk: out64 [S] / out_store [S_pad] = normalised update of `base` (fp64 [S]) with (a, o);
 // unnorm [S], partial [ceil(S_pad/256)] fp64 scratch; rto64: fp64 copy of RTO in mv's layout, or nullptr = use mv.rto

@@ -2970,43 +2970,70 @@ __global__ void __launch_bounds__(256) k_succ_weighted(const T* __restrict__ bel
     succ_sums<T, 3>(bel, ldb, B, mv, in_ptr, in_src, wgt, part);
 }
 
-// One block per belief (engine row b, caller row d = perm[b]): lane a, a + 64, ... sums the partials of (b, a, o) in x-block
-// order, forms G[b, a] and writes it (and Z as p_obs) to the caller's row; thread 0 then takes the first minimum of the row
-// that was written -- a NaN never wins, a row of NaNs gives 0: np.argmin(np.where(np.isnan(G), np.inf, G)).
-__global__ void __launch_bounds__(64) k_infotaxis_finish(int B, int A, int O, int XB, const int32_t* __restrict__ perm /* or nullptr */,
-                                                         const double* __restrict__ part, double* g_o, int32_t* __restrict__ action_o,
-                                                         double* __restrict__ pobs_o /* or nullptr */) {
+// What one observation with Z != 0 adds to the score of its (belief, action), one function per SuccObjective (backup_kernels.h).
+__device__ __forceinline__ double succ_term_entropy(double Z, double N) { return Z * log(Z) - N; }
+__device__ __forceinline__ double succ_term_space_aware(double Z, double N, double D) {
+    const double H = fmax(0.0, log(Z) - N / Z);
+    const double x = fmax(1.0, D / Z + (exp(H) - 1.0) * 0.5);
+    return Z * log2(x);
+}
+__device__ __forceinline__ double succ_term_expected_weight(double D) { return D; }
+
+// The first a with row[a] strictly below every earlier one -- a NaN never wins, a row of NaNs gives 0:
+// np.argmin(np.where(np.isnan(row), np.inf, row)).  The first-MAXIMUM tails of this file (k_q_finish, k_action_final, the action
+// tail of the decision kernels, k_upper_q_finish) are not this function mirrored: they follow np.argmax (a NaN wins), start
+// from -inf or decide inside an error window, and tests pin each of those rules.  Do not fold them in here.
+__device__ __forceinline__ int first_minimum(const double* row, int A) {
+    int best = 0;
+    double bv = row[0];
+    if (bv != bv) bv = std::numeric_limits<double>::infinity();
+    for (int a = 1; a < A; ++a) {
+        const double x = row[a];
+        if (x < bv) {
+            bv = x;
+            best = a;
+        }
+    }
+    return best;
+}
+
+// One block per belief (engine row b, caller row d = perm[b]): lane a, a + 64, ... sums the NTERM partials of (b, a, o) in
+// x-block order -- (Z, N) of k_succ_entropy, (Z, N, D) of k_succ_weighted --, adds the objective's term to the score of (b, a),
+// sequentially over o, and writes it (and the summed terms: Z alone as p_obs for NTERM == 2, all three otherwise) to the
+// caller's row; thread 0 then takes the first minimum of the row that was written.
+template <int NTERM>
+__global__ void __launch_bounds__(64) k_succ_finish(int B, int A, int O, int XB, const int32_t* __restrict__ perm /* or nullptr */,
+                                                    const double* __restrict__ part, int objective, double* score_o,
+                                                    int32_t* __restrict__ action_o, double* __restrict__ extra_o /* or nullptr */) {
+    constexpr int NEXTRA = NTERM == 2 ? 1 : NTERM;
     const int b = blockIdx.x;
     const int64_t d = perm ? perm[b] : b;
     for (int a = threadIdx.x; a < A; a += 64) {
-        double g = 0.0;
+        double score = 0.0;
         for (int o = 0; o < O; ++o) {
-            double Z = 0.0, N = 0.0;
+            double t[NTERM] = {};                           // Z, N (, D)
             for (int x = 0; x < XB; ++x) {
-                const double* p = part + ((((int64_t)x * B + b) * A + a) * O + o) * 2;
-                Z += p[0];
-                N += p[1];
+                const double* p = part + ((((int64_t)x * B + b) * A + a) * O + o) * NTERM;
+#pragma unroll
+                for (int k = 0; k < NTERM; ++k) t[k] += p[k];
             }
-            if (pobs_o != nullptr) pobs_o[(d * A + a) * O + o] = Z;
-            if (Z != 0.0) g += Z * log(Z) - N;
+            if (extra_o != nullptr) {
+#pragma unroll
+                for (int k = 0; k < NEXTRA; ++k) extra_o[((d * A + a) * O + o) * NEXTRA + k] = t[k];
+            }
+            if (t[0] != 0.0) {
+                if constexpr (NTERM == 2)
+                    score += succ_term_entropy(t[0], t[1]);
+                else if (objective == SUCC_EXPECTED_WEIGHT)
+                    score += succ_term_expected_weight(t[2]);
+                else
+                    score += succ_term_space_aware(t[0], t[1], t[2]);
+            }
         }
-        g_o[d * A + a] = g;
+        score_o[d * A + a] = score;
     }
     __syncthreads();                                        // the row is complete (written by this block)
-    if (threadIdx.x == 0) {
-        const double* row = g_o + d * A;
-        int best = 0;
-        double bv = row[0];
-        if (bv != bv) bv = std::numeric_limits<double>::infinity();
-        for (int a = 1; a < A; ++a) {
-            const double x = row[a];
-            if (x < bv) {
-                bv = x;
-                best = a;
-            }
-        }
-        action_o[d] = best;
-    }
+    if (threadIdx.x == 0) action_o[d] = first_minimum(score_o + d * A, A);
 }
 
 // H[b] = - sum_s b[s] ln b[s] (b[s] == 0 adds 0): thread t sums s = t, t + 256, ... in order, then block_sum's fixed order.
@@ -3024,107 +3051,35 @@ __global__ void __launch_bounds__(256) k_row_entropy(const T* __restrict__ bel, 
     if (threadIdx.x == 0) out[perm ? perm[blockIdx.x] : blockIdx.x] = -tot;
 }
 
+// k_succ_entropy or k_succ_weighted by the objective's term count, k_succ_finish, and k_row_entropy where it is asked for.
 template <typename T>
-hipError_t launch_infotaxis(const T* bel, int ldb, int B, ModelView<T> mv, const int32_t* in_ptr, const int32_t* in_src,
-                            const int32_t* perm, double* part, double* g_out, int32_t* action_out, double* pobs_out,
-                            double* entropy_out, hipStream_t st) {
-    if (B <= 0) return hipSuccess;
-    if (B > 65535 || mv.A > 65535 || mv.S > ldb || part == nullptr || g_out == nullptr || action_out == nullptr) return hipErrorInvalidValue;
-    const int XB = succ_entropy_xblocks(mv.S);
-    hipLaunchKernelGGL(k_succ_entropy<T>, dim3(XB, (B + TILE_NB - 1) / TILE_NB, mv.A), dim3(256), 0, st, bel, ldb, B, mv, in_ptr, in_src,
-                       part);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_infotaxis_finish, dim3(B), dim3(64), 0, st, B, mv.A, mv.O, XB, perm, part, g_out, action_out, pobs_out);
-    e = hipGetLastError();
-    if (e != hipSuccess || entropy_out == nullptr) return e;
-    hipLaunchKernelGGL(k_row_entropy<T>, dim3(B), dim3(256), 0, st, bel, ldb, mv.S, perm, entropy_out);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------------- //
-// Space-aware infotaxis (pbvi_space_aware): greedy for J = log2(D + 2^(H-1) - 1/2) of the successor belief, D its expected
-// weight (a distance to the source) and H its entropy in bits.  Per (a, o), from the x-blocks' (Z, N, D) partials:
-//   H = max(0, ln Z - N / Z) nats,  d = D / Z,  x = max(1, d + (exp(H) - 1) / 2),  J = log2(x)
-//   objective 0: F[b,a] = sum_o Z * J;   objective 1: F[b,a] = sum_o D      (sequential over o; Z == 0 adds 0)
-// One block per belief, as k_infotaxis_finish: lane a, a + 64, ... adds the partials in x-block order and writes F (and the
-// terms) to the caller's row; thread 0 then takes the first minimum of the row that was written.
-// ------------------------------------------------------------------------- //
-__global__ void __launch_bounds__(64) k_space_aware_finish(int B, int A, int O, int XB, const int32_t* __restrict__ perm /* or nullptr */,
-                                                           const double* __restrict__ part, int objective, double* f_o,
-                                                           int32_t* __restrict__ action_o, double* __restrict__ terms_o /* or nullptr */) {
-    const int b = blockIdx.x;
-    const int64_t d = perm ? perm[b] : b;
-    for (int a = threadIdx.x; a < A; a += 64) {
-        double f = 0.0;
-        for (int o = 0; o < O; ++o) {
-            double Z = 0.0, N = 0.0, D = 0.0;
-            for (int x = 0; x < XB; ++x) {
-                const double* p = part + ((((int64_t)x * B + b) * A + a) * O + o) * 3;
-                Z += p[0];
-                N += p[1];
-                D += p[2];
-            }
-            if (terms_o != nullptr) {
-                double* t = terms_o + ((d * A + a) * O + o) * 3;
-                t[0] = Z;
-                t[1] = N;
-                t[2] = D;
-            }
-            if (Z != 0.0) {
-                if (objective == 1) {
-                    f += D;
-                } else {
-                    const double H = fmax(0.0, log(Z) - N / Z);
-                    const double x = fmax(1.0, D / Z + (exp(H) - 1.0) * 0.5);
-                    f += Z * log2(x);
-                }
-            }
-        }
-        f_o[d * A + a] = f;
-    }
-    __syncthreads();                                        // the row is complete (written by this block)
-    if (threadIdx.x == 0) {
-        const double* row = f_o + d * A;
-        int best = 0;
-        double bv = row[0];
-        if (bv != bv) bv = std::numeric_limits<double>::infinity();
-        for (int a = 1; a < A; ++a) {
-            const double x = row[a];
-            if (x < bv) {
-                bv = x;
-                best = a;
-            }
-        }
-        action_o[d] = best;
-    }
-}
-
-template <typename T>
-hipError_t launch_space_aware(const T* bel, int ldb, int B, ModelView<T> mv, const int32_t* in_ptr, const int32_t* in_src,
-                              const double* wgt, const int32_t* perm, double* part, int objective, double* f_out,
-                              int32_t* action_out, double* terms_out, hipStream_t st) {
-    if (B <= 0) return hipSuccess;
-    if (B > 65535 || mv.A > 65535 || mv.S > ldb || wgt == nullptr || part == nullptr || f_out == nullptr || action_out == nullptr ||
-        (objective != 0 && objective != 1))
+hipError_t launch_successor_scores(const SuccScores<T>& ss, ModelView<T> mv, const int32_t* in_ptr, const int32_t* in_src,
+                                   hipStream_t st) {
+    if (ss.B <= 0) return hipSuccess;
+    const bool weighted = ss.objective == SUCC_SPACE_AWARE || ss.objective == SUCC_EXPECTED_WEIGHT;
+    if (ss.B > 65535 || mv.A > 65535 || mv.S > ss.ldb || ss.part == nullptr || ss.score_out == nullptr || ss.action_out == nullptr ||
+        (!weighted && ss.objective != SUCC_ENTROPY) || (weighted && ss.wgt == nullptr))
         return hipErrorInvalidValue;
     const int XB = succ_entropy_xblocks(mv.S);
-    hipLaunchKernelGGL(k_succ_weighted<T>, dim3(XB, (B + TILE_NB - 1) / TILE_NB, mv.A), dim3(256), 0, st, bel, ldb, B, mv, in_ptr, in_src,
-                       wgt, part);
+    const dim3 grid(XB, (ss.B + TILE_NB - 1) / TILE_NB, mv.A);
+    if (weighted)
+        hipLaunchKernelGGL(k_succ_weighted<T>, grid, dim3(256), 0, st, ss.bel, ss.ldb, ss.B, mv, in_ptr, in_src, ss.wgt, ss.part);
+    else
+        hipLaunchKernelGGL(k_succ_entropy<T>, grid, dim3(256), 0, st, ss.bel, ss.ldb, ss.B, mv, in_ptr, in_src, ss.part);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_space_aware_finish, dim3(B), dim3(64), 0, st, B, mv.A, mv.O, XB, perm, part, objective, f_out, action_out,
-                       terms_out);
+    hipLaunchKernelGGL(weighted ? k_succ_finish<3> : k_succ_finish<2>, dim3(ss.B), dim3(64), 0, st, ss.B, mv.A, mv.O, XB, ss.perm,
+                       ss.part, ss.objective, ss.score_out, ss.action_out, ss.extra_out);
+    e = hipGetLastError();
+    if (e != hipSuccess || ss.entropy_out == nullptr) return e;
+    hipLaunchKernelGGL(k_row_entropy<T>, dim3(ss.B), dim3(256), 0, st, ss.bel, ss.ldb, mv.S, ss.perm, ss.entropy_out);
     return hipGetLastError();
 }
 
 // explicit instantiations
 #define PBVI_INST(T)                                                                                                   \
-    template hipError_t launch_space_aware<T>(const T*, int, int, ModelView<T>, const int32_t*, const int32_t*,        \
-                                              const double*, const int32_t*, double*, int, double*, int32_t*, double*, \
-                                              hipStream_t);                                                            \
-    template hipError_t launch_infotaxis<T>(const T*, int, int, ModelView<T>, const int32_t*, const int32_t*,          \
-                                            const int32_t*, double*, double*, int32_t*, double*, double*, hipStream_t); \
+    template hipError_t launch_successor_scores<T>(const SuccScores<T>&, ModelView<T>, const int32_t*, const int32_t*, \
+                                                   hipStream_t);                                                       \
     template hipError_t launch_rollout_draw<T>(const RolloutStep&, ModelView<T>, const RolloutEnv*, hipStream_t);        \
     template hipError_t launch_belief_push<T>(const BayesStep<T>&, ModelView<T>, const int32_t*, hipStream_t);         \
     template hipError_t launch_belief_norm<T>(const BayesStep<T>&, int, const int32_t*, T*, int, hipStream_t);         \

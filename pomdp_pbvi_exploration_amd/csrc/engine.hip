@@ -969,6 +969,27 @@ enum RolloutSource {
     ROLLOUT_INFOTAXIS = 2,            // first argmin_a of the expected successor entropy (pbvi_rollout_infotaxis)
     ROLLOUT_SPACE_AWARE = 3,          // first argmin_a of pbvi_space_aware's F, RolloutCall::objective (pbvi_rollout_space_aware)
 };
+// What the step loop has to know about a source; its stage is EngineT::rollout_stage.  A number that is no source reads as
+// value-max until EngineT::rollout refuses it (`known`), which keeps the refusals before that one in their order.
+struct RolloutSourceInfo {
+    bool known;
+    bool needs_alpha;                 // a resident alpha set and alpha_actions [V]
+    bool needs_weights;               // pbvi_state_weights_set, and RolloutCall::objective 0 or 1
+    // The Bayes step sums the norm in block order, not with atomics: infotaxis (plain or space-aware) meets near-ties between
+    // actions on symmetric beliefs, which must not hang on the arrival order of the atomics.  (A rollout against an environment
+    // promises the same bits however a run is cut into blocks, and sums in block order whatever its source.)
+    bool fixed_order;
+    const char* who;                  // the entry point named in the refusals of what only this source needs
+};
+inline RolloutSourceInfo rollout_source_info(int source) {
+    switch (source) {
+        case ROLLOUT_VALUE_MAX: return {true, true, false, false, "rollout"};
+        case ROLLOUT_Q: return {true, true, false, false, "rollout"};
+        case ROLLOUT_INFOTAXIS: return {true, false, false, true, "rollout_infotaxis"};
+        case ROLLOUT_SPACE_AWARE: return {true, false, true, true, "rollout_space_aware"};
+        default: return {false, true, false, false, "rollout"};
+    }
+}
 
 // One rollout call, as pbvi_rollout / pbvi_rollout_infotaxis / pbvi_rollout_env / pbvi_rollout_space_aware fill it
 struct RolloutCall {
@@ -1191,14 +1212,14 @@ class EngineT : public EngineBase {
     // row map (+ 1 int: the survivor count), alpha_actions [V], end mask [S]
     DevBuf ro_traj_{mem_}, ro_state_[2]{{mem_}, {mem_}}, ro_orig_[2]{{mem_}, {mem_}}, ro_keep_{mem_}, ro_dst_{mem_}, ro_aact_{mem_}, ro_end_{mem_};
     int64_t zero_row_ = -1;                                  // first s * A + a whose RTO[s, a, :, :] sums to 0 (-1: none)
-    // pbvi_infotaxis: the x-blocks' (Z, N) partials [XB][B][A][O][2]; G [B][A], its first argmin [B], P(o | b, a) [B][A][O]
-    // and the beliefs' own entropies [B], all four in the caller's belief order
-    DevBuf it_part_{mem_}, it_g_{mem_}, it_act_{mem_}, it_pobs_{mem_}, it_h_{mem_};
-    // pbvi_state_weights_set: w [S] fp64 (a working buffer: after_oom() releases it and no weights are set).  pbvi_space_aware:
-    // the x-blocks' (Z, N, D) partials [XB][B][A][O][3]; F [B][A], its first argmin [B] and the terms [B][A][O][3], caller order
+    // successor_scores (pbvi_infotaxis, pbvi_space_aware; one call's results are delivered before the next call starts, so the
+    // objectives share the buffers): the x-blocks' partials [XB][B][A][O][2 or 3]; the score [B][A] (G or F), its first argmin
+    // [B], the summed terms (P(o | b, a) [B][A][O], or (Z, N, D) [B][A][O][3]) and the beliefs' own entropies [B], the last four
+    // in the caller's belief order
+    DevBuf gs_part_{mem_}, gs_score_{mem_}, gs_act_{mem_}, gs_extra_{mem_}, gs_h_{mem_};
+    // pbvi_state_weights_set: w [S] fp64 (a working buffer: after_oom() releases it and no weights are set)
     DevBuf sw_{mem_};
     bool sw_set_ = false;
-    DevBuf sa_part_{mem_}, sa_f_{mem_}, sa_act_{mem_}, sa_terms_{mem_};
     DevBuf bu_mpart_{mem_};   // bayes_push(fixed_order): the push blocks' partial masses [B][ceil(S/256)]
     // pbvi_upper_*: the point store of the HSVI upper bound -- CSR rows (ub_ptr_ int64 [P+1], ub_idx_ int32 / ub_val_ fp64 [entries]),
     // per point its entries, value and gap (ub_nnz_ int32, ub_v_ / ub_gap_ fp64 [P]), the corner values ub_c_ fp64 [S].  Working
@@ -1861,35 +1882,62 @@ class EngineT : public EngineBase {
         return rc ? rc : bayes_norm_finish(nb, true);
     }
 
-    // Expected successor entropies of the resident block (pbvi_infotaxis) into it_g_ / it_act_ (/ it_pobs_ / it_h_), caller
-    // order, left on the device.  Reads the block and the model tables only.
-    int infotaxis_device(bool want_p_obs, bool want_entropy) {
-        if ((int64_t)S_ * R_ > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "infotaxis: S*R exceeds int32");
+    // The greedy successor policies' scores of the resident block -- SUCC_ENTROPY: pbvi_infotaxis' G; SUCC_SPACE_AWARE /
+    // SUCC_EXPECTED_WEIGHT: pbvi_space_aware's F -- into gs_score_ / gs_act_ (/ gs_extra_ / gs_h_), caller order, left on the
+    // device.  Reads the block, the model tables and, for the weighted objectives, the weights only.
+    int successor_scores(int objective, bool want_extra, bool want_entropy) {
+        const bool weighted = objective != SUCC_ENTROPY;
+        const std::string who = weighted ? "space_aware" : "infotaxis";
+        if (weighted && !sw_set_) FAIL(PBVI_EINVAL, who + ": no state weights set (call pbvi_state_weights_set)");
+        if ((int64_t)S_ * R_ > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, who + ": S*R exceeds int32");
         int rc = build_inverse_lists();
         if (rc) return rc;
-        const size_t ba = (size_t)blk_.B * A_;
-        if ((rc = it_part_.ensure((size_t)succ_entropy_xblocks(S_) * ba * O_ * 2 * sizeof(double)))) return rc;
-        if ((rc = it_g_.ensure(ba * sizeof(double)))) return rc;
-        if ((rc = it_act_.ensure((size_t)blk_.B * sizeof(int32_t)))) return rc;
-        if (want_p_obs && (rc = it_pobs_.ensure(ba * O_ * sizeof(double)))) return rc;
-        if (want_entropy && (rc = it_h_.ensure((size_t)blk_.B * sizeof(double)))) return rc;
-        HIPCHK(launch_infotaxis<T>(blk_.rows.as<T>(), S_pad_, (int)blk_.B, view(), in_ptr_.as<int32_t>(), in_src_.as<int32_t>(),
-                                   blk_.sorted ? blk_.perm.as<int32_t>() : nullptr, it_part_.as<double>(), it_g_.as<double>(),
-                                   it_act_.as<int32_t>(), want_p_obs ? it_pobs_.as<double>() : nullptr,
-                                   want_entropy ? it_h_.as<double>() : nullptr, stream_));
+        // Exact sizes: a buffer that one objective sized and the other outgrows is allocated anew, not doubled (the headroom
+        // of DevBuf::ensure is for buffers that grow call after call), so an engine that runs both holds what the larger needs.
+        auto fit = [](DevBuf& buf, size_t bytes) {
+            if (bytes > buf.cap) buf.release();
+            return buf.ensure(bytes);
+        };
+        const size_t ba = (size_t)blk_.B * A_, terms = (size_t)succ_terms(objective);
+        if ((rc = fit(gs_part_, (size_t)succ_entropy_xblocks(S_) * ba * O_ * terms * sizeof(double)))) return rc;
+        if ((rc = fit(gs_score_, ba * sizeof(double)))) return rc;
+        if ((rc = fit(gs_act_, (size_t)blk_.B * sizeof(int32_t)))) return rc;
+        if (want_extra && (rc = fit(gs_extra_, extra_bytes(objective)))) return rc;
+        if (want_entropy && (rc = fit(gs_h_, (size_t)blk_.B * sizeof(double)))) return rc;
+        SuccScores<T> ss{};
+        ss.bel = blk_.rows.as<T>();
+        ss.ldb = S_pad_;
+        ss.B = (int)blk_.B;
+        ss.perm = blk_.sorted ? blk_.perm.as<int32_t>() : nullptr;
+        ss.part = gs_part_.as<double>();
+        ss.wgt = weighted ? sw_.as<double>() : nullptr;
+        ss.objective = objective;
+        ss.score_out = gs_score_.as<double>();
+        ss.action_out = gs_act_.as<int32_t>();
+        ss.extra_out = want_extra ? gs_extra_.as<double>() : nullptr;
+        ss.entropy_out = want_entropy ? gs_h_.as<double>() : nullptr;
+        HIPCHK(launch_successor_scores<T>(ss, view(), in_ptr_.as<int32_t>(), in_src_.as<int32_t>(), stream_));
         return PBVI_OK;
+    }
+    // gs_extra_ of the resident block: Z [B][A][O] for SUCC_ENTROPY, (Z, N, D) [B][A][O][3] for the weighted objectives
+    size_t extra_bytes(int objective) const {
+        return (size_t)blk_.B * A_ * O_ * (objective == SUCC_ENTROPY ? 1 : 3) * sizeof(double);
+    }
+    // successor_scores for a caller: the score and whichever of the other arrays are asked for (NULL: not computed)
+    int successor_scores_deliver(int objective, double* out_score, int32_t* out_action, double* out_extra, double* out_entropy) {
+        HIPCHK(hipSetDevice(device_));
+        int rc = successor_scores(objective, out_extra != nullptr, out_entropy != nullptr);
+        if (rc) return rc;
+        return out_.deliver({{out_score, gs_score_.p, (size_t)blk_.B * A_ * sizeof(double)},
+                             {out_action, gs_act_.p, (size_t)blk_.B * sizeof(int32_t)},
+                             {out_extra, gs_extra_.p, extra_bytes(objective)},
+                             {out_entropy, gs_h_.p, (size_t)blk_.B * sizeof(double)}});
     }
 
     int infotaxis(double* out_g, int32_t* out_action, double* out_p_obs, double* out_entropy) override {
         if (!out_g) FAIL(PBVI_EINVAL, "infotaxis: NULL out_g");
         if (blk_.B <= 0) FAIL(PBVI_EINVAL, "infotaxis: no belief block resident (call pbvi_beliefs_set)");
-        HIPCHK(hipSetDevice(device_));
-        int rc = infotaxis_device(out_p_obs != nullptr, out_entropy != nullptr);
-        if (rc) return rc;
-        return out_.deliver({{out_g, it_g_.p, (size_t)blk_.B * A_ * sizeof(double)},
-                             {out_action, it_act_.p, (size_t)blk_.B * sizeof(int32_t)},
-                             {out_p_obs, it_pobs_.p, (size_t)blk_.B * A_ * O_ * sizeof(double)},
-                             {out_entropy, it_h_.p, (size_t)blk_.B * sizeof(double)}});
+        return successor_scores_deliver(SUCC_ENTROPY, out_g, out_action, out_p_obs, out_entropy);
     }
 
     // ---- space-aware infotaxis (pbvi_state_weights_set / _clear, pbvi_space_aware) ---- //
@@ -1915,35 +1963,12 @@ class EngineT : public EngineBase {
         return PBVI_OK;
     }
 
-    // pbvi_space_aware's F of the resident block into sa_f_ / sa_act_ (/ sa_terms_), caller order, left on the device.  Reads
-    // the block, the model tables and the weights only.
-    int space_aware_device(int objective, bool want_terms) {
-        if (objective != 0 && objective != 1) FAIL(PBVI_EINVAL, "space_aware: objective must be 0 (space-aware) or 1 (expected weight)");
-        if (!sw_set_) FAIL(PBVI_EINVAL, "space_aware: no state weights set (call pbvi_state_weights_set)");
-        if ((int64_t)S_ * R_ > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "space_aware: S*R exceeds int32");
-        int rc = build_inverse_lists();
-        if (rc) return rc;
-        const size_t ba = (size_t)blk_.B * A_;
-        if ((rc = sa_part_.ensure((size_t)succ_entropy_xblocks(S_) * ba * O_ * 3 * sizeof(double)))) return rc;
-        if ((rc = sa_f_.ensure(ba * sizeof(double)))) return rc;
-        if ((rc = sa_act_.ensure((size_t)blk_.B * sizeof(int32_t)))) return rc;
-        if (want_terms && (rc = sa_terms_.ensure(ba * O_ * 3 * sizeof(double)))) return rc;
-        HIPCHK(launch_space_aware<T>(blk_.rows.as<T>(), S_pad_, (int)blk_.B, view(), in_ptr_.as<int32_t>(), in_src_.as<int32_t>(),
-                                     sw_.as<double>(), blk_.sorted ? blk_.perm.as<int32_t>() : nullptr, sa_part_.as<double>(),
-                                     objective, sa_f_.as<double>(), sa_act_.as<int32_t>(),
-                                     want_terms ? sa_terms_.as<double>() : nullptr, stream_));
-        return PBVI_OK;
-    }
-
     int space_aware(int objective, double* out_f, int32_t* out_action, double* out_terms) override {
         if (!out_f) FAIL(PBVI_EINVAL, "space_aware: NULL out_f");
         if (blk_.B <= 0) FAIL(PBVI_EINVAL, "space_aware: no belief block resident (call pbvi_beliefs_set)");
-        HIPCHK(hipSetDevice(device_));
-        int rc = space_aware_device(objective, out_terms != nullptr);
-        if (rc) return rc;
-        return out_.deliver({{out_f, sa_f_.p, (size_t)blk_.B * A_ * sizeof(double)},
-                             {out_action, sa_act_.p, (size_t)blk_.B * sizeof(int32_t)},
-                             {out_terms, sa_terms_.p, (size_t)blk_.B * A_ * O_ * 3 * sizeof(double)}});
+        if (objective != SUCC_SPACE_AWARE && objective != SUCC_EXPECTED_WEIGHT)
+            FAIL(PBVI_EINVAL, "space_aware: objective must be 0 (space-aware) or 1 (expected weight)");
+        return successor_scores_deliver(objective, out_f, out_action, out_terms, nullptr);
     }
 
     // ---- HSVI upper bound (pbvi_upper_reset / _append / _count / _bound / _q) ---- //
@@ -2176,16 +2201,38 @@ class EngineT : public EngineBase {
         return PBVI_OK;
     }
 
+    // The stage of a rollout call's action source on the resident block; *index = what it leaves on the device for the draw:
+    // for ROLLOUT_VALUE_MAX an alpha row per belief in ENGINE row order (the draw maps it through RolloutStep::alpha_actions),
+    // for every other source an action per belief in CALLER row order.
+    int rollout_stage(const RolloutCall& call, const int32_t** index) {
+        int rc;
+        switch (call.source) {
+            case ROLLOUT_VALUE_MAX:
+                rc = value_max_device(resident());
+                *index = bv2_.as<int32_t>();
+                return rc;
+            case ROLLOUT_Q:
+                rc = run_q(call.gamma, false);
+                *index = q_act_.as<int32_t>();
+                return rc;
+            default:                                          // the two that score the successors
+                rc = successor_scores(call.source == ROLLOUT_INFOTAXIS ? (int)SUCC_ENTROPY : call.objective, false, false);
+                *index = gs_act_.as<int32_t>();
+                return rc;
+        }
+    }
+
     // T lock-step simulation steps of the resident block on the device (pbvi_rollout, pbvi_rollout_infotaxis, pbvi_rollout_env,
     // pbvi_rollout_space_aware).  Per step: the action source's stage with its index left on the device (value-max or Q-values
-    // against the resident alpha set, the successor entropies of infotaxis_device, or space_aware_device's F); the simulator
+    // against the resident alpha set, or successor_scores' G or F: rollout_stage); the simulator
     // draw (the model's own joint draw, or the successor from the model and the observation from the environment); the first half of the Bayes step for the rows not done; with
     // an environment the lost rule on their masses; the done-filter; the norm of the rows that go on.  Finished and lost rows
     // are dropped after EVERY step ("Device-resident rollouts"): the one host read per step is the survivor count,
     // which sizes the next step's launches.
     int rollout(const RolloutCall& call) override {
         const int source = call.source;
-        const bool env = call.env, uses_alpha = source != ROLLOUT_INFOTAXIS && source != ROLLOUT_SPACE_AWARE;
+        const RolloutSourceInfo info = rollout_source_info(source);
+        const bool env = call.env, uses_alpha = info.needs_alpha;
         const int64_t n_steps = call.T;
         if (env && env_kind_ == ENV_NONE) FAIL(PBVI_EINVAL, "rollout_env: no environment set (call pbvi_env_set_frames or pbvi_env_set_table)");
         if (env && call.end_observation >= O_) FAIL(PBVI_EINVAL, "rollout_env: end_observation is not below O");
@@ -2193,12 +2240,10 @@ class EngineT : public EngineBase {
         if (uses_alpha && V_ <= 0) FAIL(PBVI_EINVAL, "rollout: no alpha set resident (call pbvi_alpha_set)");
         if (blk_.B <= 0) FAIL(PBVI_EINVAL, "rollout: no belief block resident (call pbvi_beliefs_set)");
         if ((uses_alpha && !call.alpha_actions) || !call.start_states || !call.end_mask) FAIL(PBVI_EINVAL, "rollout: NULL argument");
-        if (source != ROLLOUT_VALUE_MAX && source != ROLLOUT_Q && source != ROLLOUT_INFOTAXIS && source != ROLLOUT_SPACE_AWARE)
-            FAIL(PBVI_EINVAL, "rollout: lookahead must be 0 or 1");
-        if (source == ROLLOUT_SPACE_AWARE && call.objective != 0 && call.objective != 1)
-            FAIL(PBVI_EINVAL, "rollout_space_aware: objective must be 0 (space-aware) or 1 (expected weight)");
-        if (source == ROLLOUT_SPACE_AWARE && !sw_set_)
-            FAIL(PBVI_EINVAL, "rollout_space_aware: no state weights set (call pbvi_state_weights_set)");
+        if (!info.known) FAIL(PBVI_EINVAL, "rollout: lookahead must be 0 or 1");
+        if (info.needs_weights && call.objective != SUCC_SPACE_AWARE && call.objective != SUCC_EXPECTED_WEIGHT)
+            FAIL(PBVI_EINVAL, std::string(info.who) + ": objective must be 0 (space-aware) or 1 (expected weight)");
+        if (info.needs_weights && !sw_set_) FAIL(PBVI_EINVAL, std::string(info.who) + ": no state weights set (call pbvi_state_weights_set)");
         if (n_steps < 1) FAIL(PBVI_EINVAL, "rollout: T must be at least 1");
         if (source == ROLLOUT_Q && mode_ != PBVI_SPARSE)
             FAIL(PBVI_EUNSUPPORTED, "rollout: lookahead = 1 is not available on a PBVI_DENSE engine (create it with PBVI_SPARSE)");
@@ -2224,10 +2269,7 @@ class EngineT : public EngineBase {
                                       " exceeds the " + std::to_string(env_F_) + " frames of the environment");
         }
         HIPCHK(hipSetDevice(device_));
-        // Infotaxis (plain or space-aware) meets near-ties between actions on symmetric beliefs, and a rollout against an
-        // environment promises the same bits however a run is cut into blocks: neither may hang on the arrival order of the
-        // norm's atomics, so their Bayes step sums the norm in a fixed order.
-        const bool fixed_order = env || source == ROLLOUT_INFOTAXIS || source == ROLLOUT_SPACE_AWARE;
+        const bool fixed_order = env || info.fixed_order;      // (RolloutSourceInfo says why)
         int rc;
         if (env) {
             if ((rc = ro_lost_.ensure((size_t)n0))) return rc;
@@ -2298,19 +2340,7 @@ class EngineT : public EngineBase {
         int* d_count = ro_dst_.as<int>() + n0;
         int oc = 0;
         for (int64_t t = 0; t < n_steps; ++t) {
-            if (source == ROLLOUT_VALUE_MAX) {
-                if ((rc = value_max_device(resident()))) return rc;
-                rs.index = bv2_.as<int32_t>();                // engine row order, an alpha row: mapped through alpha_actions
-            } else if (source == ROLLOUT_Q) {
-                if ((rc = run_q(call.gamma, false))) return rc;
-                rs.index = q_act_.as<int32_t>();              // caller row order, an action
-            } else if (source == ROLLOUT_INFOTAXIS) {
-                if ((rc = infotaxis_device(false, false))) return rc;
-                rs.index = it_act_.as<int32_t>();             // caller row order, an action
-            } else {
-                if ((rc = space_aware_device(call.objective, false))) return rc;
-                rs.index = sa_act_.as<int32_t>();             // caller row order, an action
-            }
+            if ((rc = rollout_stage(call, &rs.index))) return rc;
             rs.n = (int)blk_.B;
             rs.t = (int)t;
             rs.perm = blk_.sorted ? blk_.perm.as<int32_t>() : nullptr;

@@ -1230,9 +1230,9 @@ class Engine:
                                   start_states, end_mask, seed, T, first_sim_id)
 
     def _rollout_call(self, call, start_states, end_mask, seed: int, T: int, first_sim_id: int, with_lost: bool = False):
-        """What ``rollout``, ``rollout_infotaxis`` and ``rollout_env`` share: the checks of the simulations and the stream, the
-        trajectory arrays (none for a ``T`` the engine refuses), ``call(start_states, end_mask, first_sim_id, seed, T, *arrays)``
-        on their pointers, and the block that is resident afterwards."""
+        """What ``rollout``, ``rollout_infotaxis``, ``rollout_env`` and ``rollout_space_aware`` share: the checks of the
+        simulations and the stream, the trajectory arrays (none for a ``T`` the engine refuses), ``call(start_states, end_mask,
+        first_sim_id, seed, T, *arrays)`` on their pointers, and the block that is resident afterwards."""
         ss = np.ascontiguousarray(start_states, dtype=np.int32)
         em = np.ascontiguousarray(end_mask, dtype=np.uint8)
         if ss.shape != (self.B,):
@@ -1254,6 +1254,16 @@ class Engine:
                       *[_p(x, C.c_uint8 if x.dtype == np.uint8 else C.c_int32) for x in out]))
         self.B = int(self._lib.pbvi_beliefs_count(self._h))
         return out
+
+    def _shifts_pointer(self, shifts):
+        """``shifts [B]`` (the first frame of every simulation of ``rollout_env`` / ``rollout_space_aware``) as the int64 pointer
+        the engine takes; ``None`` stays ``None``."""
+        if shifts is None:
+            return None
+        sh = np.ascontiguousarray(shifts, dtype=np.int64)
+        if sh.shape != (self.B,):
+            raise ValueError('shifts must be [B]')
+        return _p(sh, C.c_int64)
 
     def rollout_infotaxis(self, start_states, end_mask, seed: int, T: int, first_sim_id: int = 0):
         """``rollout`` with the infotaxis policy (``pbvi_rollout_infotaxis``): every step takes the action with the smallest
@@ -1316,17 +1326,13 @@ class Engine:
         ``shifts`` ``[B]``: the frame each simulation starts at (frames only).  Returns ``(states, actions, observations,
         steps, lost)``: ``rollout``'s four arrays and ``lost [B]`` uint8."""
         policy = int(policy)
-        aap = shp = None
+        aap = None
         if alpha_actions is not None:
             aa = np.ascontiguousarray(alpha_actions, dtype=np.int32)
             if policy != 2 and aa.shape != (self.alpha_count,):
                 raise ValueError('alpha_actions must be [V]')
             aap = _p(aa, C.c_int32)
-        if shifts is not None:
-            sh = np.ascontiguousarray(shifts, dtype=np.int64)
-            if sh.shape != (self.B,):
-                raise ValueError('shifts must be [B]')
-            shp = _p(sh, C.c_int64)
+        shp = self._shifts_pointer(shifts)
         return self._rollout_call(lambda ss, em, *tail: self._lib.pbvi_rollout_env(self._h, policy, aap, float(gamma), ss, em,
                                                                                    int(end_observation), shp, *tail),
                                   start_states, end_mask, seed, T, first_sim_id, with_lost=True)
@@ -1338,12 +1344,7 @@ class Engine:
         (``shifts`` and ``end_observation`` stay ``None`` / ``-1``).  ``use_env=True``: against the environment set with
         ``set_environment_*``, with ``rollout_env``'s draw and lost rule.  Returns ``(states, actions, observations, steps,
         lost)``; ``lost`` is all 0 in the model's world."""
-        shp = None
-        if shifts is not None:
-            sh = np.ascontiguousarray(shifts, dtype=np.int64)
-            if sh.shape != (self.B,):
-                raise ValueError('shifts must be [B]')
-            shp = _p(sh, C.c_int64)
+        shp = self._shifts_pointer(shifts)
         return self._rollout_call(lambda ss, em, *tail: self._lib.pbvi_rollout_space_aware(
             self._h, int(objective), int(bool(use_env)), ss, em, int(end_observation), shp, *tail),
             start_states, end_mask, seed, T, first_sim_id, with_lost=True)

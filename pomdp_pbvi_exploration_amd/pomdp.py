@@ -1685,6 +1685,9 @@ def record_frames(obs_table, F: int, seed: int) -> np.ndarray:
     return frames
 
 
+ENV_POLICY_INFOTAXIS = 2               # ``rollout_env`` / ``pbvi_rollout_env`` number the policies: 0 value-max, 1 Q, 2 infotaxis
+
+
 def rollout_env_numpy(model, env, policy: int, alpha, alpha_actions, beliefs, start_states, seed: int, first_sim_id: int,
                       T: int, gamma: float = 0.99, table_dtype=np.float64, return_beliefs: bool = False):
     """``T`` lock-step steps against an environment, on the host: what ``pbvi_rollout_env`` computes on the device.
@@ -1699,15 +1702,16 @@ def rollout_env_numpy(model, env, policy: int, alpha, alpha_actions, beliefs, st
     recorded ``a``, ``o``, ``s'``, no NaN belief), and any other is normalised.  ``env.shifts`` belong to the rows given.
     Returns ``rollout_numpy``'s arrays and then ``lost [n]`` uint8."""
     from types import SimpleNamespace
-    if policy not in (0, 1, 2):
+    if policy not in (0, 1, ENV_POLICY_INFOTAXIS):
         raise ValueError(f'policy must be 0 (value-max), 1 (Q) or 2 (infotaxis), not {policy!r}')
     if not isinstance(env, (FrameEnvironment, TableEnvironment)):
         raise ValueError('env must be a FrameEnvironment or a TableEnvironment')
     if int(T) >= 1 << 31:
         raise ValueError('T must be below 2**31')
+    infotaxis = policy == ENV_POLICY_INFOTAXIS
     m, T, b, s, alpha, acts = _rollout_inputs(model, beliefs, start_states, T,
-                                              None if policy == 2 else np.asarray(alpha, dtype=np.float64), alpha_actions)
-    if policy == 2:
+                                              None if infotaxis else np.asarray(alpha, dtype=np.float64), alpha_actions)
+    if infotaxis:
         block = _HostBeliefBlock(m, None, b)
         choose = lambda: block.infotaxis_actions(table_dtype)
     else:
@@ -1745,29 +1749,49 @@ def _xlogx(x: np.ndarray) -> np.ndarray:
     return out
 
 
-def _infotaxis_terms(model, beliefs, table_dtype=np.float64, rows_at_once: Union[int, None] = None):
-    """The sums of ``infotaxis_numpy`` and the magnitudes of their terms: ``(G [n,A], Z [n,A,O], H [n], M_G [n,A], M_H [n])``
-    with ``M_G = sum_o (|Z ln Z| + sum_s' |u ln u|)`` and ``M_H = sum_s |b ln b|`` (what a rounding-error bound for a
-    re-ordered evaluation of ``G`` and ``H`` scales with)."""
+def _successor_terms(model, beliefs, weights=None, table_dtype=np.float64, rows_at_once: Union[int, None] = None):
+    """The sums over the un-normalised successor ``u`` (``_successor_rows``: ``np.bincount``'s order; the table cast to
+    ``table_dtype``, the engine's number format, and widened) that the greedy successor policies are made of, and the checks of
+    their arguments: ``(b [n,S] fp64, Z, N, M_N, D)``, the last four ``[n,A,O]``:
+
+        ``Z = sum_s' u``,   ``N = sum_s' u ln u``,   ``M_N = sum_s' |u ln u|``,   ``D = sum_s' u w``     (``u == 0`` adds 0)
+
+    ``D`` is ``None`` without ``weights``.  ``rows_at_once`` beliefs are expanded at a time (by default ~32 MiB of products)."""
     m = _rollout_tables(model)
     S, A, O, R = m.state_count, m.action_count, m.observation_count, m.reachable_state_count
     b = np.asarray(beliefs, dtype=np.float64)
     if b.ndim != 2 or b.shape[1] != S:
         raise ValueError(f'beliefs must be a [*, {S}] array')
+    w = None if weights is None else _state_weights(S, weights)
     n = b.shape[0]
     rto = np.ascontiguousarray(m.reachable_transitional_observation_table, dtype=table_dtype).astype(np.float64)
     rs = np.asarray(m.reachable_states).astype(np.int64)
-    G, MG, Z = np.zeros((n, A)), np.zeros((n, A)), np.zeros((n, A, O))
-    step = max(1, (1 << 22) // (S * R)) if rows_at_once is None else int(rows_at_once)     # ~32 MiB of weights at a time
+    Z, N, MN = (np.zeros((n, A, O)) for _ in range(3))
+    D = None if w is None else np.zeros((n, A, O))
+    step = max(1, (1 << 22) // (S * R)) if rows_at_once is None else int(rows_at_once)
     for i0 in range(0, n, step):
         i1 = min(i0 + step, n)
         for a, o, u in _successor_rows(b[i0:i1], rs, rto):
             ulu = _xlogx(u)
-            z = np.sum(u, axis=1)
-            zlz = _xlogx(z)
-            Z[i0:i1, a, o] = z
-            G[i0:i1, a] += zlz - np.sum(ulu, axis=1)
-            MG[i0:i1, a] += np.abs(zlz) + np.sum(np.abs(ulu), axis=1)
+            Z[i0:i1, a, o] = np.sum(u, axis=1)
+            N[i0:i1, a, o] = np.sum(ulu, axis=1)
+            MN[i0:i1, a, o] = np.sum(np.abs(ulu), axis=1)
+            if w is not None:
+                D[i0:i1, a, o] = np.sum(u * w[None, :], axis=1)
+    return b, Z, N, MN, D
+
+
+def _infotaxis_terms(model, beliefs, table_dtype=np.float64, rows_at_once: Union[int, None] = None):
+    """The sums of ``infotaxis_numpy`` and the magnitudes of their terms: ``(G [n,A], Z [n,A,O], H [n], M_G [n,A], M_H [n])``
+    with ``M_G = sum_o (|Z ln Z| + sum_s' |u ln u|)`` and ``M_H = sum_s |b ln b|`` (what a rounding-error bound for a
+    re-ordered evaluation of ``G`` and ``H`` scales with).  ``G`` and ``M_G`` start from zero and take one term per observation,
+    in the order of the observations."""
+    b, Z, N, MN, _ = _successor_terms(model, beliefs, None, table_dtype, rows_at_once)
+    G, MG = np.zeros(Z.shape[:2]), np.zeros(Z.shape[:2])
+    for o in range(Z.shape[2]):
+        zlz = _xlogx(Z[:, :, o])
+        G += zlz - N[:, :, o]
+        MG += np.abs(zlz) + MN[:, :, o]
     blb = _xlogx(b)
     return G, Z, -np.sum(blb, axis=1), MG, np.sum(np.abs(blb), axis=1)
 
@@ -1860,25 +1884,8 @@ def space_aware_terms(model, beliefs, weights, table_dtype=np.float64, rows_at_o
 
     ``M_Z = Z``, ``M_N = sum_s' |u ln u|`` and ``M_D = D`` (the terms of ``Z`` and ``D`` are non-negative) are what a
     rounding-error bound for a re-ordered evaluation of each sum scales with."""
-    m = _rollout_tables(model)
-    S, A, O, R = m.state_count, m.action_count, m.observation_count, m.reachable_state_count
-    b = np.asarray(beliefs, dtype=np.float64)
-    if b.ndim != 2 or b.shape[1] != S:
-        raise ValueError(f'beliefs must be a [*, {S}] array')
-    w = _state_weights(S, weights)
-    n = b.shape[0]
-    rto = np.ascontiguousarray(m.reachable_transitional_observation_table, dtype=table_dtype).astype(np.float64)
-    rs = np.asarray(m.reachable_states).astype(np.int64)
-    Z, N, D, MN = (np.zeros((n, A, O)) for _ in range(4))
-    step = max(1, (1 << 22) // (S * R)) if rows_at_once is None else int(rows_at_once)
-    for i0 in range(0, n, step):
-        i1 = min(i0 + step, n)
-        for a, o, u in _successor_rows(b[i0:i1], rs, rto):
-            ulu = _xlogx(u)
-            Z[i0:i1, a, o] = np.sum(u, axis=1)
-            N[i0:i1, a, o] = np.sum(ulu, axis=1)
-            MN[i0:i1, a, o] = np.sum(np.abs(ulu), axis=1)
-            D[i0:i1, a, o] = np.sum(u * w[None, :], axis=1)
+    # (``None`` is no weight vector here: as an array it has no shape ``[S]``, and is refused as one)
+    _, Z, N, MN, D = _successor_terms(model, beliefs, np.asarray(weights, dtype=np.float64), table_dtype, rows_at_once)
     return Z, N, D, Z, MN, D
 
 
@@ -2005,60 +2012,47 @@ class _DeviceBeliefBlock:
 
     CHUNK = 32768
 
-    def __init__(self, model: Model, value_function: ValueFunction, beliefs: np.ndarray):
+    def __init__(self, model: Model, value_function: ValueFunction, beliefs: np.ndarray, resident_rows: int = 65535):
+        """``resident_rows``: the largest block that is set as one (``get_best_action`` chunks above ``CHUNK`` already)."""
         self.eng = model.engine
         if value_function is not None:                          # (infotaxis has none)
             self.eng.sync_rows('alpha', value_function.alpha_vector_list, lambda v: v.values)
         self.chunks = None
-        if beliefs.shape[0] <= 65535:
+        if beliefs.shape[0] <= resident_rows:
             self.eng.set_beliefs(beliefs)
         else:
             self.chunks = [np.ascontiguousarray(beliefs[i:i + self.CHUNK]) for i in range(0, beliefs.shape[0], self.CHUNK)]
 
-    def best_vectors(self) -> np.ndarray:
+    def each(self, call) -> np.ndarray:
+        """``call()`` -- an engine call that returns one entry per belief of the resident block, which stays on the device --
+        for every belief of this block: once if it is resident, else on each chunk made resident in turn, joined."""
         if self.chunks is None:
-            return self.eng.max_value_resident()[1]
+            return call()
         out = []
         for c in self.chunks:
             self.eng.set_beliefs(c)
-            out.append(self.eng.max_value_resident()[1])
+            out.append(call())
         return np.concatenate(out) if out else np.zeros(0, dtype=np.int64)
 
+    def best_vectors(self) -> np.ndarray:
+        return self.each(lambda: self.eng.max_value_resident()[1])
+
     def best_actions(self, gamma: float) -> np.ndarray:
-        """One-step lookahead: ``argmax_a Q(b,a)`` of every belief of the block (``pbvi_q_values``; the resident block
-        stays on the device)."""
-        if self.chunks is None:
-            return self.eng.q_values_resident(gamma)[1]
-        out = []
-        for c in self.chunks:
-            self.eng.set_beliefs(c)
-            out.append(self.eng.q_values_resident(gamma)[1])
-        return np.concatenate(out) if out else np.zeros(0, dtype=np.int64)
+        """One-step lookahead: ``argmax_a Q(b,a)`` of every belief of the block (``pbvi_q_values``)."""
+        return self.each(lambda: self.eng.q_values_resident(gamma)[1])
 
     def infotaxis_actions(self) -> np.ndarray:
         """Infotaxis: the first ``argmin_a`` of the expected successor entropy of every belief of the block
-        (``pbvi_infotaxis``; the resident block stays on the device)."""
-        if self.chunks is None:
-            return self.eng.infotaxis_resident()[1]
-        out = []
-        for c in self.chunks:
-            self.eng.set_beliefs(c)
-            out.append(self.eng.infotaxis_resident()[1])
-        return np.concatenate(out) if out else np.zeros(0, dtype=np.int64)
+        (``pbvi_infotaxis``)."""
+        return self.each(lambda: self.eng.infotaxis_resident()[1])
 
     def space_aware_actions(self, weights, objective: int = 0) -> np.ndarray:
         """Space-aware infotaxis: the first ``argmin_a`` of ``pbvi_space_aware``'s ``F`` of every belief of the block (the
-        weights are uploaded once per block; the resident block stays on the device)."""
+        weights are uploaded once per block)."""
         if getattr(self, '_weights', None) is not weights:
             self.eng.set_state_weights(weights)
             self._weights = weights
-        if self.chunks is None:
-            return self.eng.space_aware_resident(objective)[1]
-        out = []
-        for c in self.chunks:
-            self.eng.set_beliefs(c)
-            out.append(self.eng.space_aware_resident(objective)[1])
-        return np.concatenate(out) if out else np.zeros(0, dtype=np.int64)
+        return self.each(lambda: self.eng.space_aware_resident(objective)[1])
 
     def advance(self, actions: np.ndarray, observations: np.ndarray, keep: np.ndarray) -> None:
         if self.chunks is None:
@@ -2110,28 +2104,18 @@ class Agent:
         return self.value_function.actions[block.best_vectors()]
 
     def get_best_action(self, belief):
-        """``actions[argmax_v b.alpha_v]`` for one ``Belief`` (returns int) or a ``[n,S]`` array (``:3005-3034``)."""
-        vf = self.value_function
-        assert vf is not None, "No value function, training probably has to be run..."
+        """This agent's action -- ``Agent``: ``actions[argmax_v b.alpha_v]`` (``:3005-3034``), or ``argmax_a Q(b,a)`` with
+        ``lookahead=1`` -- for one ``Belief`` (returns int) or a ``[n,S]`` array: ``_block_actions`` of the array as a belief
+        block, in the HIP engine (``_DeviceBeliefBlock.CHUNK`` beliefs at a time) when the agent is on the GPU."""
+        on_gpu, vf = self._on_gpu(), self.value_function
         single = isinstance(belief, Belief)
         arr = belief.values[None, :] if single else belief
-        if self.lookahead == 1:
-            if vf.is_on_gpu:
-                acts = _q_values_device(vf, arr, self.gamma)[1]
-            else:
-                acts = np.argmax(_q_values_numpy(vf.model, arr, vf.alpha_vector_array, self.gamma), axis=1)
-            return int(acts[0]) if single else acts
-        if vf.is_on_gpu:
-            eng = vf.model.engine
-            eng.sync_rows('alpha', vf.alpha_vector_list, lambda v: v.values)
-            parts = []
-            for i0 in range(0, arr.shape[0], _DeviceBeliefBlock.CHUNK):      # the engine takes 65535 beliefs at a time
-                eng.set_beliefs(arr[i0:i0 + _DeviceBeliefBlock.CHUNK])
-                parts.append(eng.max_value_resident()[1])
-            best = parts[0] if len(parts) == 1 else np.concatenate(parts)
+        model = self.model if vf is None else vf.model
+        if on_gpu:
+            block = _DeviceBeliefBlock(model, vf, arr, resident_rows=_DeviceBeliefBlock.CHUNK)
         else:
-            best = np.argmax(np.matmul(arr, vf.alpha_vector_array.T), axis=1)
-        acts = vf.actions[best]
+            block = _HostBeliefBlock(model, vf, arr)
+        acts = self._block_actions(block)
         return int(acts[0]) if single else acts
 
     def simulate(self, simulator: Union[Simulation, None] = None, max_steps: int = 1000,
@@ -2282,10 +2266,6 @@ class Agent:
 
     ROLLOUT_CHUNK = 65535            # simulations per ``pbvi_rollout`` call: the engine's belief block limit
 
-    def _env_policy(self) -> int:
-        """This agent's policy as ``pbvi_rollout_env`` numbers it: 0 value-max, 1 Q, 2 infotaxis."""
-        return self.lookahead
-
     @staticmethod
     def _end_mask(model: Model) -> np.ndarray:
         mask = np.zeros(model.state_count, dtype=np.uint8)
@@ -2303,34 +2283,42 @@ class Agent:
             parts.append(call(start_states[i0:i1], i0, None if shifts is None else shifts[i0:i1]))
         return tuple(np.concatenate([p[k] for p in parts], axis=-1) for k in range(len(parts[0])))
 
+    # What the counter-based rollouts need to know of the policy, beside ``_block_actions``: three hooks.
+    def _upload(self, eng) -> None:
+        """What the engine needs resident before this policy's device rollout: the alpha rows."""
+        eng.sync_rows('alpha', self.value_function.alpha_vector_list, lambda v: v.values)
+
+    def _host_rollout(self, model: Model, b0: np.ndarray, start_states: np.ndarray, seed: int, T: int, env):
+        vf = self.value_function
+        if env is not None:
+            return rollout_env_numpy(model, env, self.lookahead, vf.alpha_vector_array, vf.actions, b0, start_states, seed, 0, T,
+                                     self.gamma)
+        return rollout_numpy(model, vf.alpha_vector_array, vf.actions, b0, start_states, seed, 0, T, self.lookahead, self.gamma)
+
+    def _device_rollout(self, eng, end_mask: np.ndarray, seed: int, T: int, env):
+        """``call(start_states, first_sim_id, shifts)`` of ``_rollout_chunks``: this policy's rollout of the resident block."""
+        acts = self.value_function.actions
+        if env is not None:
+            return lambda s0, first, sh: eng.rollout_env(self.lookahead, acts, s0, end_mask, seed, T, first_sim_id=first,
+                                                         gamma=self.gamma, shifts=sh, end_observation=env.end_observation)
+        return lambda s0, first, sh: eng.rollout(acts, s0, end_mask, seed, T, first_sim_id=first, lookahead=self.lookahead,
+                                                 gamma=self.gamma)
+
     def _counter_trajectories(self, model: Model, b0: np.ndarray, start_states: np.ndarray, seed: int, T: int, env=None):
         """``(states, actions, observations, steps)`` of the counter-based rollout of this agent's policy, against ``env`` with
-        ``lost`` behind them: on the device when the agent is (the environment uploaded once: later calls with the same arrays
-        find it there), else on the host."""
-        policy, vf = self._env_policy(), self.value_function
-        alpha, acts = (None, None) if policy == 2 else (vf.alpha_vector_array, vf.actions)
+        ``lost`` behind them: on the device when the agent is (what the policy needs uploaded first, then the environment,
+        once: later calls with the same arrays find it there), else on the host."""
         if not self._on_gpu():
-            if env is not None:
-                return rollout_env_numpy(model, env, policy, alpha, acts, b0, start_states, seed, 0, T, self.gamma)
-            if policy == 2:
-                return rollout_infotaxis_numpy(model, b0, start_states, seed, 0, T)
-            return rollout_numpy(model, alpha, acts, b0, start_states, seed, 0, T, self.lookahead, self.gamma)
+            return self._host_rollout(model, b0, start_states, seed, T, env)
         shifts = None
         if env is not None:
             shifts = env.check(model.state_count, model.action_count, model.observation_count, b0.shape[0], T)
-        eng, end_mask = model.engine, self._end_mask(model)
-        if policy != 2:
-            eng.sync_rows('alpha', vf.alpha_vector_list, lambda v: v.values)
+        eng = model.engine
+        self._upload(eng)
         if env is not None:
             eng.hold_environment(env)
-            call = lambda s0, first, sh: eng.rollout_env(policy, acts, s0, end_mask, seed, T, first_sim_id=first, gamma=self.gamma,
-                                                         shifts=sh, end_observation=env.end_observation)
-        elif policy == 2:
-            call = lambda s0, first, sh: eng.rollout_infotaxis(s0, end_mask, seed, T, first_sim_id=first)
-        else:
-            call = lambda s0, first, sh: eng.rollout(acts, s0, end_mask, seed, T, first_sim_id=first, lookahead=self.lookahead,
-                                                     gamma=self.gamma)
-        return self._rollout_chunks(eng, b0, start_states, shifts, call)
+        out = self._rollout_chunks(eng, b0, start_states, shifts, self._device_rollout(eng, self._end_mask(model), seed, T, env))
+        return out if env is not None else out[:4]
 
     def _run_counter_rollouts(self, model: Model, simulator_set: SimulationSet, b0: np.ndarray, start_states: np.ndarray,
                               seed: int, max_steps: int, reward_discount: float, print_stats: bool, environment=None):
@@ -2385,23 +2373,19 @@ class Infotaxis_Agent(Agent):
     def _block_actions(self, block) -> np.ndarray:
         return block.infotaxis_actions()
 
-    def _env_policy(self) -> int:
-        return 2
+    def _upload(self, eng) -> None:
+        pass
 
-    def get_best_action(self, belief):
-        """The infotaxis action for one ``Belief`` (returns int) or a ``[n,S]`` array."""
-        single = isinstance(belief, Belief)
-        arr = belief.values[None, :] if single else belief
-        if self.model.is_on_gpu:
-            eng = self.model.engine
-            parts = []
-            for i0 in range(0, arr.shape[0], _DeviceBeliefBlock.CHUNK):      # the engine takes 65535 beliefs at a time
-                eng.set_beliefs(arr[i0:i0 + _DeviceBeliefBlock.CHUNK])
-                parts.append(eng.infotaxis_resident()[1])
-            acts = parts[0] if len(parts) == 1 else np.concatenate(parts)
-        else:
-            acts = infotaxis_numpy(self.model, arr)[1]
-        return int(acts[0]) if single else acts
+    def _host_rollout(self, model: Model, b0: np.ndarray, start_states: np.ndarray, seed: int, T: int, env):
+        if env is not None:
+            return rollout_env_numpy(model, env, ENV_POLICY_INFOTAXIS, None, None, b0, start_states, seed, 0, T, self.gamma)
+        return rollout_infotaxis_numpy(model, b0, start_states, seed, 0, T)
+
+    def _device_rollout(self, eng, end_mask: np.ndarray, seed: int, T: int, env):
+        if env is not None:
+            return lambda s0, first, sh: eng.rollout_env(ENV_POLICY_INFOTAXIS, None, s0, end_mask, seed, T, first_sim_id=first,
+                                                         gamma=self.gamma, shifts=sh, end_observation=env.end_observation)
+        return lambda s0, first, sh: eng.rollout_infotaxis(s0, end_mask, seed, T, first_sim_id=first)
 
 
 class SpaceAware_Agent(Agent):
@@ -2425,39 +2409,16 @@ class SpaceAware_Agent(Agent):
     def _block_actions(self, block) -> np.ndarray:
         return block.space_aware_actions(self.weights, self.objective)
 
-    def get_best_action(self, belief):
-        """The space-aware action for one ``Belief`` (returns int) or a ``[n,S]`` array."""
-        single = isinstance(belief, Belief)
-        arr = belief.values[None, :] if single else belief
-        if self.model.is_on_gpu:
-            eng = self.model.engine
-            eng.set_state_weights(self.weights)
-            parts = []
-            for i0 in range(0, arr.shape[0], _DeviceBeliefBlock.CHUNK):      # the engine takes 65535 beliefs at a time
-                eng.set_beliefs(arr[i0:i0 + _DeviceBeliefBlock.CHUNK])
-                parts.append(eng.space_aware_resident(self.objective)[1])
-            acts = parts[0] if len(parts) == 1 else np.concatenate(parts)
-        else:
-            acts = space_aware_numpy(self.model, arr, self.weights, self.objective)[1]
-        return int(acts[0]) if single else acts
-
-    def _counter_trajectories(self, model: Model, b0: np.ndarray, start_states: np.ndarray, seed: int, T: int, env=None):
-        """``Agent._counter_trajectories`` for this policy: ``pbvi_rollout_space_aware`` when the model is on the GPU (weights
-        and environment uploaded first), ``rollout_space_aware_numpy`` otherwise."""
-        if not self._on_gpu():
-            return rollout_space_aware_numpy(model, b0, start_states, self.weights, seed, 0, T, self.objective, env=env)
-        shifts = None
-        if env is not None:
-            shifts = env.check(model.state_count, model.action_count, model.observation_count, b0.shape[0], T)
-        eng, end_mask = model.engine, self._end_mask(model)
+    def _upload(self, eng) -> None:
         eng.set_state_weights(self.weights)
-        if env is not None:
-            eng.hold_environment(env)
+
+    def _host_rollout(self, model: Model, b0: np.ndarray, start_states: np.ndarray, seed: int, T: int, env):
+        return rollout_space_aware_numpy(model, b0, start_states, self.weights, seed, 0, T, self.objective, env=env)
+
+    def _device_rollout(self, eng, end_mask: np.ndarray, seed: int, T: int, env):
         end_obs = -1 if env is None else env.end_observation
-        call = lambda s0, first, sh: eng.rollout_space_aware(s0, end_mask, seed, T, first_sim_id=first, objective=self.objective,
+        return lambda s0, first, sh: eng.rollout_space_aware(s0, end_mask, seed, T, first_sim_id=first, objective=self.objective,
                                                              use_env=env is not None, shifts=sh, end_observation=end_obs)
-        out = self._rollout_chunks(eng, b0, start_states, shifts, call)
-        return out if env is not None else out[:4]
 
 
 # --------------------------------------------------------------------------- #
