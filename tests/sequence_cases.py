@@ -1,8 +1,8 @@
 """Sequences of engine calls, their shadow state and their references (no tests here, no GPU needed).
 
 The invariant ``tests/test_engine_sequences.py`` states: what a call of an ``Engine`` returns is a function of the engine's
-LOGICAL state -- tables, working alpha set, belief block, row stores, switches -- and not of the calls that produced that
-state.  This module holds everything of that test that is plain Python:
+LOGICAL state -- tables, working alpha set, belief block, row stores, state weights, the point store of the upper bound,
+switches -- and not of the calls that produced that state.  This module holds everything of that test that is plain Python:
 
 * two small models (``model('G')``, ``model('I')``) from the generators of ``test_score_window.py`` / ``model_cases.py``;
 * seeded recipes for alpha sets (exact duplicates, ~100 exact ties per triple, near-duplicates) and belief blocks;
@@ -11,7 +11,7 @@ state.  This module holds everything of that test that is plain Python:
   shadow, and after every query compares the engine with (a) the fp64 host statements evaluated on the shadow and (b) a
   fresh engine brought to the shadow's state by ``set_alpha`` / ``set_beliefs``;
 * ``HostEngine``: a NumPy stand-in with ``Engine``'s method names built on the oracle and the ``*_numpy`` statements, and
-  five subclasses with one planted carry-over bug each;
+  ten subclasses with one planted carry-over bug each;
 * the scripted sequences (literal lists), the seeded generator and the coverage accounting.
 
 Index comparisons follow the rule of the issue: an entry is compared where fp64 can decide it -- the runner-up is an
@@ -24,8 +24,11 @@ from types import SimpleNamespace
 
 import numpy as np
 
+import hsvi_cases as hc
 import model_cases as mc
+import test_infotaxis as tit
 import test_score_window as sw
+import test_space_aware as tsa
 from oracle import pbvi_oracle as orc
 from pomdp_pbvi_exploration_amd import pomdp as P
 from pomdp_pbvi_exploration_amd.mdp import _row_hash
@@ -226,7 +229,61 @@ def prune_ref(mname, alpha):
 def infotaxis_ref(mname, bel, f32=False):
     m = model(mname)
     G, Z, H, MG, MH = P._infotaxis_terms(m.tables, bel, np.float32 if f32 else np.float64)
-    return SimpleNamespace(G=G, act=P.infotaxis_first_argmin(G), bound=np.maximum(8.0 * m.S * 2.0 ** -53 * MG, 1e-15))
+    return SimpleNamespace(G=G, act=P.infotaxis_first_argmin(G), bound=np.maximum(8.0 * m.S * 2.0 ** -53 * MG, 1e-15), Z=Z, H=H, MH=MH)
+
+
+@memo
+def space_aware_ref(mname, bel, w, f32=False):
+    """``space_aware_terms`` on the values the engine holds: the terms, their re-ordering bounds (``test_infotaxis.bound``), F of
+    both objectives and ``test_space_aware.f_magnitude``'s ``M_F``."""
+    m = model(mname)
+    Z, N, D, MZ, MN, MD = P.space_aware_terms(m.tables, bel, w, np.float32 if f32 else np.float64)
+    return SimpleNamespace(terms=np.stack([Z, N, D], axis=-1), tb=np.stack([tit.bound(m.S, M) for M in (MZ, MN, MD)], axis=-1),
+                           F={obj: P.space_aware_from_terms(Z, N, D, obj) for obj in (0, 1)}, MF=tsa.f_magnitude(m.tables, bel, w)[2])
+
+
+def space_aware_margin(terms, MF, objective, tau):
+    """[n]: what separates two actions' F beyond doubt when the terms are known to ``tau`` of their magnitudes: ``f_bound`` (the
+    formula on given terms) plus ``tau * M_F`` (``f_magnitude``: what a relative perturbation of the terms moves F by)."""
+    return (tsa.f_bound(terms, objective) + tau * MF).max(axis=1)
+
+
+@memo
+def sawtooth_ref(mname, pts, vals, gaps, corner, bel, nv=0, nh=0):
+    value, point, hit = P.sawtooth_numpy(pts, vals, gaps, corner, bel, nv, nh)
+    v0, _, M = hc.w_matrix(pts, gaps, corner, bel, nv)
+    return SimpleNamespace(value=value, point=point, hit=hit, bound=hc.sawtooth_bound(bel.shape[1], corner, bel, v0, M))
+
+
+@memo
+def upper_q_ref(mname, pts, vals, gaps, corner, bel, nv=0, nh=0, f32=False):
+    m = model(mname)
+    host = P.upper_q_numpy(m.tables, pts, vals, gaps, corner, bel, GAMMA, nv, nh, table_dtype=np.float32 if f32 else np.float64)
+    tq, tz, tv = hc.successor_bounds(m.tables, 'f32' if f32 else 'f64', pts, gaps, corner, bel, GAMMA, nv, host)
+    return SimpleNamespace(Q=host[0], act=host[1], Z=host[2], sval=host[3], tq=tq, tz=tz, tv=tv)
+
+
+WINDOWS = ('all', 'stale', 'hits_only', 'none')
+
+
+def window_of(kind, n):
+    """``(n_visible, n_hit)`` of a store of n points: every point; the stale cache of a mapping; hits only; nothing."""
+    return {'all': (n, n), 'stale': (n // 2, n - n // 4), 'hits_only': (0, n), 'none': (0, 0)}[kind]
+
+
+def with_hits(rows, points, hits, seed):
+    """After ``hsvi_cases.make_rows``: ``rows`` with ``hits`` of them (spread over the block, row 0 among them) replaced by
+    copies of stored points -- the last, the first, the middle one, then random ones -- and, where a row is left for it, the
+    uniform belief last."""
+    rows, (B, S), n = rows.copy(), rows.shape, points.shape[0]
+    rng = np.random.default_rng([int(seed), n, 83])
+    ids = [n - 1, 0, n // 2] + [int(i) for i in rng.integers(0, n, max(0, hits - 3))]
+    k = min(hits, B)
+    for j in range(k):
+        rows[(j * B) // k] = points[ids[j]]
+    if B > k:
+        rows[B - 1] = 1.0 / S
+    return f32r(rows)
 
 
 def update_ref(m, bel, acts, obs):
@@ -287,7 +344,7 @@ def apply_switch(eng, name, value):
 
 class Shadow:
     """The engine's logical state.  Arrays are float64 holding values of the engine's precision; ``None`` = nothing
-    resident.  ``prim_ids`` / ``prim_free`` restate the bookkeeping of ``store_select``'s three branches, only to name the
+    resident.  The point store keeps the boundaries of the appends it came in (``bounds``); gaps are the caller's, computed once.  ``prim_ids`` / ``prim_free`` restate the bookkeeping of ``store_select``'s three branches, only to name the
     form a selection takes (coverage accounting); nothing compared depends on them."""
 
     def __init__(self, mname, dtype):
@@ -301,6 +358,25 @@ class Shadow:
         self.astore, self.bstore = [], []
         self.result = None                      # None, or the belief-dominance flag of the fetchable backup
         self.prim_ids, self.prim_free = None, 0
+        self.weights = None                     # None, or the state weights [S]
+        self.store = None                       # None (no corner set), or the point store: corner, pts, vals, gaps, bounds
+
+    @property
+    def n_points(self):
+        return 0 if self.store is None else self.store.pts.shape[0]
+
+    def put_store(self, corner, pts=None, vals=None, gaps=None):
+        S = len(corner)
+        self.store = SimpleNamespace(corner=np.array(corner, dtype=np.float64), pts=np.zeros((0, S)), vals=np.zeros(0),
+                                     gaps=np.zeros(0), bounds=[0])
+        if pts is not None:
+            self.append_points(pts, vals, gaps)
+
+    def append_points(self, pts, vals, gaps):
+        st = self.store
+        st.pts, st.vals, st.gaps = (np.concatenate([a, np.asarray(b, dtype=np.float64)]) for a, b in
+                                    ((st.pts, pts), (st.vals, vals), (st.gaps, gaps)))
+        st.bounds.append(st.pts.shape[0])
 
     @property
     def V(self):
@@ -345,23 +421,46 @@ ALPHA_MUTATIONS = ('set_alpha', 'append_alpha', 'store_alpha', 'extend_alpha', '
 BELIEF_MUTATIONS = ('set_beliefs', 'store_beliefs', 'select_beliefs', 'advance_beliefs', 'belief_walk', 'rollout',
                     'rollout_infotaxis', 'rollout_env', 'reset_belief_store_append')
 RESETS = ('after_oom', 'oom_call')
-MUTATIONS = ALPHA_MUTATIONS + BELIEF_MUTATIONS + RESETS
-QUERIES = ('run_fetch', 'run_prune_fetch', 'run_fetch_into', 'fetch_compact_into', 'keys_assemble', 'row_hashes', 'q_values',
-           'vmax_resident', 'vmax_store', 'infotaxis', 'fetch_beliefs', 'prune_dominated', 'prune_masked', 'belief_update',
-           'fetch_refused')
+# state weights, the point store of the upper bound, the space-aware rollout (a belief mutation); behind the older names, so
+# that those keep their places (the seeded lists of the first vocabulary are drawn from them by position)
+GREEDY_MUTATIONS = ('set_state_weights', 'clear_state_weights', 'upper_reset', 'upper_append', 'rollout_space_aware')
+MUTATIONS_V1 = ALPHA_MUTATIONS + BELIEF_MUTATIONS + RESETS
+MUTATIONS = MUTATIONS_V1 + GREEDY_MUTATIONS
+QUERIES_V1 = ('run_fetch', 'run_prune_fetch', 'run_fetch_into', 'fetch_compact_into', 'keys_assemble', 'row_hashes', 'q_values',
+              'vmax_resident', 'vmax_store', 'infotaxis', 'fetch_beliefs', 'prune_dominated', 'prune_masked', 'belief_update',
+              'fetch_refused')
+REFUSALS = ('fetch_refused', 'weights_refused', 'upper_refused')
+QUERIES = QUERIES_V1 + ('space_aware', 'upper_bound', 'upper_q', 'weights_refused', 'upper_refused')
 HARNESS = ('remember', 'same_as')
-# calls of the Python layer that answer AND move the working sets (counted, but outside the mutation -> query pairs)
-COMPOUND = ('vmax_objects', 'clear_environment')
+# calls of the Python layer that answer AND move the working sets (counted, but outside the mutation -> query pairs);
+# 'run_only' is a backup that nobody fetches yet
+COMPOUND_V1 = ('vmax_objects', 'clear_environment')
+COMPOUND = COMPOUND_V1 + ('mapping_evaluate', 'run_only')
 VOCABULARY = MUTATIONS + ('switch',) + QUERIES + COMPOUND
-VALUE_QUERIES = tuple(q for q in QUERIES if q != 'fetch_refused')
+VALUE_QUERIES = tuple(q for q in QUERIES if q not in REFUSALS)
 BACKUPS = ('run_fetch', 'run_prune_fetch', 'run_fetch_into', 'q_values')
+MAX_POINTS = 300
 
 
 def legal(name, args, sh):
     """Whether the operation can run in the shadow's state."""
     V, B, res = sh.V, sh.B, sh.result is not None
-    if name in ('run_fetch', 'run_prune_fetch', 'run_fetch_into', 'q_values', 'vmax_resident'):
+    if name in ('run_fetch', 'run_prune_fetch', 'run_fetch_into', 'q_values', 'vmax_resident', 'run_only'):
         return V > 0 and B > 0
+    if name == 'space_aware':
+        return sh.weights is not None and B > 0
+    if name == 'rollout_space_aware':
+        return sh.weights is not None and 0 < B <= MAX_SIMS
+    if name == 'weights_refused':
+        return sh.weights is None
+    if name in ('upper_bound', 'upper_q'):
+        return sh.store is not None and B > 0
+    if name == 'upper_refused':
+        return sh.store is None
+    if name == 'upper_append':
+        return sh.store is not None and sh.n_points + args['P'] <= MAX_POINTS
+    if name == 'set_beliefs' and args.get('hits', 0):
+        return sh.n_points > 0
     if name in ('fetch_compact_into', 'keys_assemble', 'row_hashes', 'store_unique'):
         return res
     if name == 'fetch_refused':
@@ -415,6 +514,7 @@ class Runner:
         self.score_bits = []                    # per probed backup: best_score equal to the fresh engine's bit for bit?
         self.score_ratio = 0.0                  # largest |best_score - reference| / bar seen
         self.objs, self.envs = None, {}         # AlphaVector / Belief stand-ins and environment holders that live on
+        self.maps = {}                          # BeliefValueMapping objects that live on (their cursors per engine)
         self.forms, self.last, self.kept, self.where = [], None, {}, ''
 
     def close(self):
@@ -443,6 +543,18 @@ class Runner:
         if got.shape != want.shape or not np.array_equal(got, want):
             n = int(np.sum(got != want)) if got.shape == want.shape else -1
             self.fail(f'{what}: {n} entries differ (shapes {got.shape}, {want.shape})')
+
+    def same_bits(self, got, want, what):
+        """``same`` for floating-point arrays that may hold NaNs: the bytes."""
+        got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
+        if got.shape != want.shape or got.dtype != want.dtype or got.tobytes() != want.tobytes():
+            n = int(np.sum(~((got == want) | (np.isnan(got) & np.isnan(want))))) if got.shape == want.shape else -1
+            self.fail(f'{what}: {n} entries differ (shapes {got.shape}, {want.shape}; {got.dtype}, {want.dtype})')
+
+    def within(self, got, want, bound, what):
+        err = np.abs(np.asarray(got, dtype=np.float64) - want)
+        if np.shape(got) != np.shape(want) or not np.all(err <= bound):                     # (a NaN fails)
+            self.fail(f'{what}: off by up to {np.nanmax(err / np.maximum(bound, 1e-300)):.3g} bounds')
 
     def close_to(self, got, want, rtol, atol, what):
         got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
@@ -477,6 +589,12 @@ class Runner:
             e.store_rows('belief', np.stack(sh.bstore).astype(self.npdt))
         if sh.bel is not None:
             e.set_beliefs(sh.bel.astype(self.npdt))
+        if sh.weights is not None:
+            e.set_state_weights(sh.weights)
+        if sh.store is not None:                               # one append of every point, however they came
+            e.upper_reset(sh.store.corner)
+            if e.upper_append(sh.store.pts, sh.store.vals, sh.store.gaps) != sh.n_points:
+                self.fail('the fresh engine counts other points than the shadow')
         if run_flag is not None:
             e.run(GAMMA, run_flag)
         return e
@@ -500,7 +618,8 @@ class Runner:
 
     def op_same_as(self, tag):
         for k, v in self.kept[tag].items():
-            self.same(self.last[k], v, f'{k} against the call remembered as {tag!r}')
+            compare = self.same_bits if v.dtype.kind == 'f' and np.isnan(v).any() else self.same      # (successor values hold NaNs)
+            compare(self.last[k], v, f'{k} against the call remembered as {tag!r}')
 
     # -- switches and resets ---------------------------------------------------------------------------------------- #
     def op_switch(self, name, value):
@@ -591,8 +710,10 @@ class Runner:
         self.sh.astore, self.sh.alpha_ids, self.sh.prim_ids = [], None, None
 
     # -- belief block ----------------------------------------------------------------------------------------------- #
-    def op_set_beliefs(self, **recipe):
+    def op_set_beliefs(self, hits=0, **recipe):
         rows = belief_rows(self.mname, **recipe)
+        if hits:                                               # copies of stored points: the hit test has something to find
+            rows = with_hits(rows, self.sh.store.pts, hits, recipe['seed'])
         self.eng.set_beliefs(rows.astype(self.npdt))
         self.sh.put_beliefs(rows)
 
@@ -1013,11 +1134,17 @@ class Runner:
         got, fresh = self.both(lambda e: e.max_value_store(), with_store=True)
         self._check_vmax(got, fresh, np.stack(self.sh.bstore), 'max_value_store')
 
-    def op_infotaxis(self):
-        (g, act), (fg, fact) = self.both(lambda e: e.infotaxis_resident())
+    def op_infotaxis(self, extras=False):
+        got, fresh = self.both(lambda e: e.infotaxis_resident(want_p_obs=extras, want_entropy=extras))
+        (g, act), (fg, fact) = got[:2], fresh[:2]
         self.same(g, fg, 'infotaxis G against the fresh engine')
         self.same(act, fact, 'infotaxis actions against the fresh engine')
         want = infotaxis_ref(self.mname, self.sh.bel, f32=self.f32)
+        if extras:
+            self.same_bits(got[2], fresh[2], 'infotaxis p_obs against the fresh engine')
+            self.same_bits(got[3], fresh[3], 'infotaxis entropies against the fresh engine')
+            self.within(got[2], want.Z, tit.bound(self.m.S, want.Z), 'infotaxis p_obs against the host statement')
+            self.within(got[3], want.H, tit.bound(self.m.S, want.MH), 'infotaxis entropies against the host statement')
         if not np.all(np.abs(g - want.G) <= want.bound):
             self.fail(f'infotaxis G off by up to {np.max(np.abs(g - want.G) / want.bound):.2f} bounds')
         self.same(act, P.infotaxis_first_argmin(g), 'infotaxis actions against the first argmin of the returned G')
@@ -1065,6 +1192,188 @@ class Runner:
         self.close_to(got, fresh, UPDATE_RTOL[self.dtype], UPDATE_ATOL, 'belief_update against the fresh engine')
         self.done(rows=got)
 
+    # -- state weights and space-aware infotaxis ------------------------------------------------------------------------------ #
+    def op_set_state_weights(self, kind, seed):
+        w = tsa.make_weights(kind, self.m.S, int(seed), self.m.tables.end_states)
+        self.eng.set_state_weights(w)
+        self.sh.weights = w
+
+    def op_clear_state_weights(self):
+        self.eng.clear_state_weights()
+        self.sh.weights = None
+
+    def op_weights_refused(self):
+        try:                                                   # (without a block it is refused for that, before anything else)
+            self.eng.space_aware_resident(0)
+        except ValueError:
+            self.done()
+            return
+        self.fail('space_aware answered although no state weights are set')
+
+    def op_space_aware(self, objective, terms=False):
+        """F, action and terms byte for byte against the fresh engine (which is always asked for the terms: the short form
+        must give the long form's F); the terms within the re-ordering bound of the host's; F within ``f_bound`` of the
+        formula on the device's own terms; the action the first argmin of the returned row, and the host's where the host's
+        two best lie more than two margins apart (an exact tie of the host's is booked as decided: what remains to compare
+        there is the first argmin of the returned row)."""
+        sh, m = self.sh, self.m
+        got = self.eng.space_aware_resident(objective, want_terms=terms)
+        f = self.fresh()
+        try:
+            fF, fact, T = f.space_aware_resident(objective, want_terms=True)
+        finally:
+            f.close()
+        F, act = got[0], got[1]
+        self.same_bits(F, fF, 'space_aware F against the fresh engine')
+        self.same(act, fact, 'space_aware actions against the fresh engine')
+        if terms:
+            self.same_bits(got[2], T, 'space_aware terms against the fresh engine')
+        ref = space_aware_ref(self.mname, sh.bel, sh.weights, f32=self.f32)
+        self.within(T, ref.terms, ref.tb, 'space_aware terms against the host statement')
+        own = P.space_aware_from_terms(T[..., 0], T[..., 1], T[..., 2], objective)
+        self.within(F, own, tsa.f_bound(T, objective), 'space_aware F against the formula on the returned terms')
+        self.same(act, P.infotaxis_first_argmin(F), 'space_aware actions against the first argmin of the returned F')
+        if m.A > 1:
+            srt = np.sort(ref.F[objective], axis=1)
+            gap = srt[:, 1] - srt[:, 0]
+            ok = gap > 2.0 * space_aware_margin(ref.terms, ref.MF, objective, 8.0 * m.S * hc.EPS)
+            self.count(ok | (gap == 0), 'space_aware actions')
+            self.same(act[ok], P.infotaxis_first_argmin(ref.F[objective])[ok], 'space_aware actions against the host statement')
+        self.done(**({'F': F, 'act': act, 'terms': got[2]} if terms else {'F': F, 'act': act}))
+
+    def op_rollout_space_aware(self, T, seed, objective=0, env=None, env_seed=0, hold=False):
+        sh, m, s0 = self.sh, self.m, self._starts(seed)
+        self._ro = (seed, 1000 * seed, T, s0)
+        w, tol, td = sh.weights, TOL[self.dtype], np.float32 if self.f32 else np.float64
+        holder = None if env is None else self._env(env, env_seed)
+
+        def values(b):
+            Z, N, D, _, _, _ = P.space_aware_terms(m.tables, b, w, td)
+            margin = space_aware_margin(np.stack([Z, N, D], axis=-1), tsa.f_magnitude(m.tables, b, w)[2], objective, tol)
+            return -P.space_aware_from_terms(Z, N, D, objective), margin + 1e-15
+
+        def call(e):
+            if holder is not None and hold:
+                e.hold_environment(holder)
+            elif env == 'table':
+                e.set_environment_table(holder.obs_prob)
+            elif env == 'frames':
+                e.set_environment_frames(holder.frames, holder.channel_of_action)
+            return e.rollout_space_aware(s0, m.end_mask, seed, T, first_sim_id=1000 * seed, objective=objective,
+                                         use_env=holder is not None)
+
+        def observe(t, rows, ids, a, sn, done):              # (op_rollout_env's hook)
+            if env == 'table':
+                return P.rollout_draw(holder.obs_prob[sn, a], P.rollout_uniform(seed, ids, (1 << 32) + t))
+            return holder.frames[t, holder.channel_of_action[a], sn].astype(np.int64)
+        self._rollout(call, values, 'rollout_space_aware', None if holder is None else observe)
+        if holder is None and np.any(self.last['out4']):
+            self.fail('rollout_space_aware: a simulation lost in the model\'s world')
+
+    # -- the point store of the upper bound ------------------------------------------------------------------------------------ #
+    def op_upper_reset(self, seed):
+        corner = hc.corner_values(np.random.default_rng([int(seed), 79]), self.m.S)
+        self.eng.upper_reset(corner)
+        self.sh.put_store(corner)
+
+    def op_upper_append(self, P, seed, supports=hc.SUPPORTS):
+        sh = self.sh
+        pts, vals, gaps = hc.make_points(np.random.default_rng([int(seed), int(P), 73]), self.m.S, P, sh.store.corner, tuple(supports))
+        held = self.eng.upper_append(pts, vals, gaps)
+        sh.append_points(pts, vals, gaps)
+        if held != sh.n_points:
+            self.fail(f'upper_append returned {held}, the store holds {sh.n_points} points')
+
+    def op_upper_refused(self):
+        S = self.m.S
+        calls = [lambda: self.eng.upper_append(np.zeros((0, S)), np.zeros(0), np.zeros(0))]
+        if self.sh.B > 0:
+            calls += [lambda: self.eng.upper_bound_resident(0, 0), lambda: self.eng.upper_q_resident(GAMMA, 0, 0)]
+        for call in calls:
+            try:
+                call()
+            except ValueError:
+                continue
+            self.fail('the point store answered although no corner values are set')
+        self.done()
+
+    def _check_upper_bound(self, got, fresh, nv, nh, what):
+        st = self.sh.store
+        for k, name in enumerate(('value', 'point', 'hit')):
+            self.same_bits(got[k], fresh[k], f'{what} {name} against the fresh engine')
+        ref = sawtooth_ref(self.mname, st.pts, st.vals, st.gaps, st.corner, self.sh.bel, nv=nv, nh=nh)
+        self.count(np.ones(ref.hit.shape, dtype=bool), f'{what} hits')           # (equality of rows: fp64 decides every one)
+        self.same(got[2], ref.hit, f'{what} hits against the host statement')
+        self.within(got[0], ref.value, ref.bound, f'{what} value against the host statement')
+        if got[1].min() < -1 or got[1].max() >= nv:
+            self.fail(f'{what}: a point outside the {nv} visible ones')
+
+    def op_upper_bound(self, window='all'):
+        nv, nh = window_of(window, self.sh.n_points)
+        got, fresh = self.both(lambda e: e.upper_bound_resident(nv, nh))
+        self._check_upper_bound(got, fresh, nv, nh, 'upper_bound')
+        self.done(value=got[0], point=got[1], hit=got[2])
+
+    def op_upper_q(self, window='all', extras=False):
+        sh, st = self.sh, self.sh.store
+        nv, nh = window_of(window, sh.n_points)
+        got, fresh = self.both(lambda e: e.upper_q_resident(GAMMA, nv, nh, want_p_obs=extras, want_succ_value=extras))
+        names = ('Q', 'action', 'p_obs', 'succ_value')[:len(got)]
+        for k, name in enumerate(names):
+            self.same_bits(got[k], fresh[k], f'upper_q {name} against the fresh engine')
+        ref = upper_q_ref(self.mname, st.pts, st.vals, st.gaps, st.corner, sh.bel, nv=nv, nh=nh, f32=self.f32)
+        self.within(got[0], ref.Q, ref.tq, 'upper_q Q against the host statement')
+        self.same(got[1], P.upper_q_first_argmax(got[0]), 'upper_q actions against the first maximum of the returned Q')
+        if extras:
+            self.within(got[2], ref.Z, ref.tz, 'upper_q p_obs against the host statement')
+            dead = np.isnan(ref.sval)
+            self.same(np.isnan(got[3]), dead, 'upper_q successor values: NaN at the impossible observations')
+            self.within(np.where(dead, 0.0, got[3]), np.where(dead, 0.0, ref.sval), ref.tv, 'upper_q successor values against the host statement')
+        self.done(**dict(zip(names, got)))
+
+    def op_run_only(self, prune=False):
+        """A backup whose result stays on the device for now (``fetch_compact_into`` / ``keys_assemble`` / ``row_hashes`` later)."""
+        self.eng.run(GAMMA, prune)
+        self.sh.result = prune
+        self.done()
+
+    def op_mapping_evaluate(self, which=0, add=0, seed=1, B=3, update=False):
+        """``BeliefValueMapping(sawtooth='support').evaluate_block(rows, engine=eng)`` of one of the mappings that live in the
+        runner, after ``add`` new points and / or ``update()``.  ``sync_engine`` re-sends the points after a reset with the
+        mapping's corner values when the store is not (or no longer) the mapping's, else appends the new ones; the block
+        becomes ``rows``: the shadow takes the mapping's points and the rows.  Compared with the mapping on the host
+        (``np.allclose(rtol=1e-12)``, tests/test_hsvi_device.py), with the host statement at its bound, and with a fresh engine
+        byte for byte."""
+        sh, m = self.sh, self.m
+        if which not in self.maps:
+            corner = hc.corner_values(np.random.default_rng([int(which), 89]), m.S)
+            self.maps[which] = P.BeliefValueMapping(m.tables, SimpleNamespace(alpha_vector_array=corner[None, :]), sawtooth='support')
+        ub = self.maps[which]
+        if add:
+            pts, vals, _ = hc.make_points(np.random.default_rng([int(seed), int(add), 97]), m.S, add, ub.corner_values)
+            for row, v in zip(pts, vals):
+                ub.add(SimpleNamespace(values=row, bytes_repr=row.tobytes()), float(v))
+        if update:
+            ub.update()
+        rows = belief_rows(self.mname, B, seed)
+        if ub.beliefs:
+            rows = with_hits(rows, ub.point_arrays()[0], min(3, B), seed)
+        got = ub.evaluate_block(rows, engine=self.eng)
+        pts, vals, gaps = ub.point_arrays()
+        if self.eng.upper_count != len(ub.beliefs):
+            self.fail(f'the engine holds {self.eng.upper_count} points, the mapping {len(ub.beliefs)}')
+        sh.put_store(ub.corner_values, pts, vals, gaps)
+        sh.put_beliefs(rows)
+        self.close_to(got, ub.evaluate_block(rows), 1e-12, 1e-8, 'evaluate_block through the engine against the mapping on the host')
+        nv, nh = ub.window()
+        f = self.fresh()
+        try:
+            fresh = f.upper_bound_resident(nv, nh)
+        finally:
+            f.close()
+        self._check_upper_bound((got,) + tuple(self.eng.upper_bound_resident(nv, nh)[1:]), fresh, nv, nh, 'evaluate_block')
+        self.done(value=got)
+
 
 # --------------------------------------------------------------------------------------------------------------------- #
 # HostEngine: Engine's method names over the host statements
@@ -1077,12 +1386,14 @@ class _HostResult:
 class HostEngine:
     """What an ``Engine`` computes, from ``backup_ref`` and the ``*_numpy`` statements, with results rounded to the engine's
     type where the engine stores them in it.  Switches are recorded and change nothing."""
+    _serials = iter(range(1, 1 << 62))
 
     def __init__(self, mname, dtype):
         self.mname, self.m, self.dtype = mname, model(mname), dtype
         self.np_dtype = np.float32 if dtype == 'f32' else np.float64
         self.switches = {}
         self._fail_next = False
+        self.serial = ('host', id(self), next(HostEngine._serials))
         self.after_oom()
 
     def _rows(self, x):
@@ -1096,6 +1407,9 @@ class HostEngine:
         self.astore, self.bstore = [], []
         self.env = self.probe_ref = None
         self.epoch = {k: v + 1 for k, v in getattr(self, 'epoch', {'alpha': 0, 'belief': 0}).items()}
+        self.weights = self.corner = None
+        self.points = []
+        self.upper_epoch = getattr(self, 'upper_epoch', 0) + 1
 
     def debug_fail_next_call(self):
         self._fail_next = True
@@ -1276,9 +1590,87 @@ class HostEngine:
     def max_value_store(self, n=-1):
         return self._vmax(np.stack(self.bstore if n < 0 else self.bstore[:n]))
 
-    def infotaxis_resident(self):
+    def infotaxis_resident(self, want_p_obs=False, want_entropy=False):
         r = infotaxis_ref(self.mname, self.bel, f32=self.dtype == 'f32')
-        return r.G, r.act
+        return (r.G, r.act) + ((r.Z,) if want_p_obs else ()) + ((r.H,) if want_entropy else ())
+
+    # state weights, space-aware infotaxis
+    def set_state_weights(self, w):
+        self.weights = np.array(w, dtype=np.float64)
+
+    def clear_state_weights(self):
+        self.weights = None
+
+    def _query_weights(self):
+        """Hook of the defective stand-ins: the weights a query reads."""
+        return self.weights
+
+    def _query_terms(self, terms):
+        """Hook of the defective stand-ins: the terms a query scores."""
+        return terms
+
+    def space_aware_resident(self, objective=0, want_terms=False):
+        if self.bel is None:
+            raise ValueError('no belief block resident')
+        if self.weights is None:
+            raise ValueError('no state weights set')
+        ref = space_aware_ref(self.mname, self.bel, self._query_weights(), f32=self.dtype == 'f32')
+        terms = self._query_terms(ref.terms)
+        F = ref.F[objective] if terms is ref.terms else P.space_aware_from_terms(terms[..., 0], terms[..., 1], terms[..., 2], objective)
+        return (F, P.infotaxis_first_argmin(F)) + ((terms.copy(),) if want_terms else ())
+
+    def rollout_space_aware(self, start_states, end_mask, seed, T, first_sim_id=0, objective=0, use_env=False, shifts=None,
+                            end_observation=-1):
+        if self.weights is None:
+            raise ValueError('no state weights set')
+        out = P.rollout_space_aware_numpy(self.m.tables, self.bel, start_states, self._query_weights(), seed, first_sim_id, T, objective,
+                                          table_dtype=self._td(), return_beliefs=True, env=self.env if use_env else None)
+        lost = out[5] if use_env else np.zeros(len(start_states), dtype=np.uint8)
+        return self._survivors(out[:4] + (lost,), out[4])
+
+    # the point store of the upper bound
+    def upper_reset(self, corner):
+        self.upper_epoch += 1
+        self.corner, self.points = np.array(corner, dtype=np.float64), []
+
+    def upper_append(self, points, values, gaps):
+        if self.corner is None:
+            raise ValueError('no corner values set')
+        self.points.extend(zip(np.array(points, dtype=np.float64), np.asarray(values, dtype=np.float64), np.asarray(gaps, dtype=np.float64)))
+        return self.upper_count
+
+    @property
+    def upper_count(self):
+        return len(self.points)
+
+    def _point_arrays(self):
+        """``(points, values, gaps)`` as the queries read them: hook of the defective stand-ins."""
+        S = self.m.S
+        if not self.points:
+            return np.zeros((0, S)), np.zeros(0), np.zeros(0)
+        return tuple(np.array(x) for x in zip(*self.points))
+
+    def _upper_begin(self, n_visible, n_hit):
+        if self.bel is None:
+            raise ValueError('no belief block resident')
+        if self.corner is None:
+            raise ValueError('no corner values set')
+        n_hit = self.upper_count if n_hit is None else int(n_hit)
+        n_visible = n_hit if n_visible is None else int(n_visible)
+        if not 0 <= n_visible <= n_hit <= self.upper_count:
+            raise ValueError('need 0 <= n_visible <= n_hit <= points held')
+        return n_visible, n_hit
+
+    def upper_bound_resident(self, n_visible=None, n_hit=None):
+        nv, nh = self._upper_begin(n_visible, n_hit)
+        r = sawtooth_ref(self.mname, *self._point_arrays(), self.corner, self.bel, nv=nv, nh=nh)
+        return r.value, r.point, r.hit
+
+    def upper_q_resident(self, gamma, n_visible=None, n_hit=None, want_p_obs=False, want_succ_value=False):
+        assert gamma == GAMMA
+        nv, nh = self._upper_begin(n_visible, n_hit)
+        r = upper_q_ref(self.mname, *self._point_arrays(), self.corner, self.bel, nv=nv, nh=nh, f32=self.dtype == 'f32')
+        return (r.Q, r.act) + ((r.Z,) if want_p_obs else ()) + ((r.sval,) if want_succ_value else ())
 
     def fetch_beliefs(self):
         return self.bel.astype(self.np_dtype)
@@ -1367,7 +1759,7 @@ class HostEngine:
         return self._survivors(out[:4] + (out[5],), out[4])
 
 
-# -- five planted carry-over bugs ------------------------------------------------------------------------------------------ #
+# -- planted carry-over bugs ------------------------------------------------------------------------------------------------ #
 def dead_map(m, bel):
     """[B,A,O]: triples whose belief gives (a, o) no mass at all."""
     return (np.abs(bel) @ np.abs(m.rto).sum(axis=3).reshape(m.S, m.A * m.O)).reshape(-1, m.A, m.O) == 0
@@ -1490,8 +1882,108 @@ class StoreZeroMapsKept(HostEngine):
         self.maps, self.seen = [], 0
 
 
+class WeightsSurviveAReset(HostEngine):
+    """``after_oom`` keeps the old weights (``sw_set_`` not cleared): a query that must be refused answers."""
+
+    def after_oom(self):
+        keep = getattr(self, 'weights', None)
+        super().after_oom()
+        self.weights = keep
+
+
+class OldWeightsRead(HostEngine):
+    """A second ``set_state_weights`` is not seen by the next query (the upload is skipped while a buffer is held)."""
+
+    def set_state_weights(self, w):
+        self.stale_w = self.weights
+        super().set_state_weights(w)
+
+    def clear_state_weights(self):
+        super().clear_state_weights()
+        self.stale_w = None
+
+    def after_oom(self):
+        super().after_oom()
+        self.stale_w = None
+
+    def _query_weights(self):
+        w, self.stale_w = getattr(self, 'stale_w', None), None
+        return self.weights if w is None else w
+
+
+class ExtraOfTheOtherObjective(HostEngine):
+    """After infotaxis with ``p_obs`` (1 term per cell in the shared extra buffer) the next space-aware call reads that
+    buffer as if it held its own 3 terms per cell."""
+
+    def infotaxis_resident(self, want_p_obs=False, want_entropy=False):
+        out = super().infotaxis_resident(want_p_obs, want_entropy)
+        self.stale_extra = out[2].ravel() if want_p_obs else getattr(self, 'stale_extra', None)
+        return out
+
+    def _query_terms(self, terms):
+        old, self.stale_extra = getattr(self, 'stale_extra', None), None
+        if old is None:
+            return terms
+        out = terms.copy()
+        n = min(old.size, out.size)
+        out.reshape(-1)[:n] = old[:n]
+        return out
+
+
+class AppendOffsetsRestart(HostEngine):
+    """The second non-empty ``upper_append`` after a reset writes its entries from offset 0 of the entry arrays, while its row
+    pointers continue behind the first append's: the first points read the new entries, the new points what the memory held."""
+
+    def upper_reset(self, corner):
+        super().upper_reset(corner)
+        self.appends, self.ent_idx, self.ent_val, self.ptr = 0, np.zeros(0, dtype=np.int64), np.zeros(0), [0]
+
+    def after_oom(self):
+        super().after_oom()
+        self.appends = 0
+
+    def upper_append(self, points, values, gaps):
+        pts = np.array(points, dtype=np.float64)
+        if len(pts):
+            self.appends += 1
+            rows, cols = np.nonzero(pts)
+            E = len(self.ent_idx)
+            self.ent_idx = np.concatenate([self.ent_idx, np.zeros(len(cols), dtype=np.int64)])
+            self.ent_val = np.concatenate([self.ent_val, np.ones(len(cols))])     # (whatever the memory held)
+            at = 0 if self.appends == 2 else E
+            self.ent_idx[at:at + len(cols)], self.ent_val[at:at + len(cols)] = cols, pts[rows, cols]
+            self.ptr.extend(self.ptr[-1] + np.cumsum(np.count_nonzero(pts, axis=1)))
+        return super().upper_append(points, values, gaps)
+
+    def _point_arrays(self):
+        pts, vals, gaps = super()._point_arrays()
+        if getattr(self, 'appends', 0) < 2:
+            return pts, vals, gaps
+        out = np.zeros_like(pts)
+        for i in range(len(pts)):
+            e = slice(self.ptr[i], self.ptr[i + 1])
+            np.add.at(out[i], self.ent_idx[e], self.ent_val[e])
+        return out, vals, gaps
+
+
+class WindowSticks(HostEngine):
+    """``upper_bound`` uses the ``n_visible`` of the call before."""
+
+    def upper_bound_resident(self, n_visible=None, n_hit=None):
+        nv, nh = self._upper_begin(n_visible, n_hit)
+        old, self.prev_nv = getattr(self, 'prev_nv', None), nv
+        return super().upper_bound_resident(nv if old is None else min(old, nh), nh)
+
+    def upper_reset(self, corner):
+        super().upper_reset(corner)
+        self.prev_nv = None
+
+
 DEFECTS = {'dead_map_kept': DeadMapKept, 'magnitude_not_merged': MagnitudeNotMerged, 'previous_caller_order': PreviousCallerOrder,
-           'fetch_after_set_alpha': FetchAfterSetAlpha, 'store_zero_maps_kept': StoreZeroMapsKept}
+           'fetch_after_set_alpha': FetchAfterSetAlpha, 'store_zero_maps_kept': StoreZeroMapsKept,
+           'weights_survive_a_reset': WeightsSurviveAReset, 'old_weights_read': OldWeightsRead,
+           'extra_of_the_other_objective': ExtraOfTheOtherObjective, 'append_offsets_restart': AppendOffsetsRestart,
+           'window_sticks': WindowSticks}
 
 
 # --------------------------------------------------------------------------------------------------------------------- #
@@ -1709,7 +2201,111 @@ SCRIPTED = {
         sw_('fused_projection', 0), op('run_fetch'), op('same_as', tag='r'), sw_('fused_projection', 2), op('run_fetch'),
         op('same_as', tag='r'), sw_('fused_projection', 1), sw_('gamma_tiling', ('always', 64)), op('run_fetch'),
         op('same_as', tag='r'), sw_('gamma_tiling', ('off', 0)), op('run_fetch'), op('same_as', tag='r')]),
+    # gs_part_, gs_score_, gs_act_, gs_extra_, gs_h_: one buffer family for infotaxis and both space-aware objectives, released
+    # and reallocated when outgrown, gs_extra_ with 1 or 3 terms per cell: large, small, large again, with and without extras
+    'successor_score_buffers': (MODELS, DTYPES, [
+        op('set_state_weights', kind='random', seed=1), op('set_beliefs', B=300, seed=50), op('space_aware', objective=0, terms=True),
+        op('remember', tag='first'), op('set_beliefs', B=3, seed=51), op('infotaxis'), op('set_beliefs', B=257, seed=52),
+        op('space_aware', objective=1), op('infotaxis', extras=True), op('set_beliefs', B=1, seed=53),
+        op('space_aware', objective=0), op('infotaxis', extras=True), op('space_aware', objective=1, terms=True),
+        op('set_beliefs', B=300, seed=50), op('space_aware', objective=0, terms=True), op('same_as', tag='first'),
+        op('infotaxis', extras=True), op('space_aware', objective=1, terms=True), op('infotaxis'),
+        op('space_aware', objective=0, terms=True), op('same_as', tag='first')]),
+    # sw_, sw_set_: set, replaced by every kind, cleared, set again, dropped by both resets
+    'weights_lifecycle': (MODELS, DTYPES, [
+        op('set_beliefs', B=40, seed=54), op('weights_refused'), op('set_state_weights', kind='random', seed=1),
+        op('space_aware', objective=0, terms=True), op('remember', tag='first'), op('set_state_weights', kind='big', seed=2),
+        op('space_aware', objective=0, terms=True), op('space_aware', objective=1), op('set_state_weights', kind='zero', seed=3),
+        op('space_aware', objective=1, terms=True), op('space_aware', objective=0), op('set_state_weights', kind='single', seed=4),
+        op('space_aware', objective=0, terms=True), op('set_state_weights', kind='zero_ends', seed=5),
+        op('space_aware', objective=1, terms=True), op('clear_state_weights'), op('weights_refused'),
+        op('set_state_weights', kind='random', seed=1), op('space_aware', objective=0, terms=True), op('same_as', tag='first'),
+        op('after_oom'), op('weights_refused'), op('set_beliefs', B=40, seed=54), op('weights_refused'),
+        op('set_state_weights', kind='random', seed=6), op('space_aware', objective=0, terms=True), op('oom_call'),
+        op('set_beliefs', B=3, seed=55), op('weights_refused'), op('set_state_weights', kind='random', seed=1),
+        op('space_aware', objective=1)]),
+    # ub_ptr_, ub_entries_, ub_count_, ub_corner_ and the sawtooth's partials (one chunk = 64 points): 63, 64, 65 and 200 points
+    # in pieces (one of them empty), the windows largest first, a reset, other points, a refused allocation
+    'point_store_lifecycle': (MODELS, DTYPES, [
+        op('set_beliefs', B=40, seed=56), op('upper_refused'), op('upper_reset', seed=1), op('upper_bound', window='all'),
+        op('upper_append', P=63, seed=1), op('upper_append', P=0, seed=2), op('set_beliefs', B=40, seed=56, hits=5),
+        op('upper_bound', window='all'), op('upper_q', window='all', extras=True), op('upper_append', P=1, seed=3, supports=(64,)),
+        op('upper_bound', window='all'), op('upper_append', P=1, seed=4, supports=(None,)), op('upper_bound', window='all'),
+        op('upper_append', P=135, seed=5), op('set_beliefs', B=40, seed=57, hits=6), op('upper_bound', window='all'),
+        op('upper_bound', window='stale'), op('upper_bound', window='hits_only'), op('upper_bound', window='none'),
+        op('set_beliefs', B=3, seed=58, hits=2), op('upper_q', window='all'), op('upper_q', window='stale', extras=True),
+        op('upper_q', window='none'), op('upper_reset', seed=2), op('upper_bound', window='all'), op('upper_q', window='all', extras=True),
+        op('upper_append', P=40, seed=6, supports=(65, None)), op('set_beliefs', B=129, seed=59, hits=6),
+        op('upper_bound', window='all'), op('upper_bound', window='stale'), op('oom_call'), op('upper_refused'), op('fetch_refused'),
+        op('set_beliefs', B=3, seed=60), op('upper_refused'), op('upper_reset', seed=3), op('upper_append', P=5, seed=7),
+        op('set_beliefs', B=3, seed=60, hits=2), op('upper_bound', window='all'), op('upper_q', window='all', extras=True)]),
+    # have_result_ and the stage buffers: a backup nobody has fetched yet, the greedy calls, then the fetches
+    'upper_calls_leave_a_backup_fetchable': (MODELS, DTYPES, [
+        op('set_alpha', V=12, seed=1), op('set_state_weights', kind='zero_ends', seed=1), op('upper_reset', seed=1),
+        op('upper_append', P=5, seed=1), op('set_beliefs', B=129, seed=61, hits=3), op('run_fetch'), op('fetch_compact_into'),
+        op('remember', tag='fetched'), op('run_only'), op('upper_bound', window='all'), op('upper_q', window='all', extras=True),
+        op('space_aware', objective=0, terms=True), op('infotaxis', extras=True), op('fetch_compact_into'), op('same_as', tag='fetched'),
+        op('keys_assemble'), op('row_hashes'), op('run_only', prune=True), op('upper_q', window='stale'), op('space_aware', objective=1),
+        op('upper_bound', window='hits_only'), op('set_state_weights', kind='big', seed=2), op('upper_append', P=3, seed=2),
+        op('keys_assemble'), op('row_hashes'), op('fetch_compact_into')]),
+    # blk_.perm, .sorted and the block's version: a sorted block, a small unsorted one, a selection, a masked advance, a walk
+    'blocks_under_the_bound': (MODELS, DTYPES, [
+        op('upper_reset', seed=1), op('upper_append', P=12, seed=1), op('store_beliefs', B=40, seed=62),
+        op('set_beliefs', B=300, seed=63, hits=6), op('upper_bound', window='all'), op('upper_q', window='all'),
+        op('set_beliefs', B=3, seed=64, hits=2), op('upper_bound', window='all'), op('upper_q', window='all', extras=True),
+        op('select_beliefs', how='last', B=40), op('upper_bound', window='stale'), op('upper_q', window='stale'),
+        op('advance_beliefs', keep=True, seed=3), op('upper_bound', window='all'), op('upper_q', window='all', extras=True),
+        op('belief_walk', n=5, seed=3), op('upper_bound', window='all'), op('upper_q', window='hits_only'),
+        op('set_beliefs', B=257, seed=65, hits=5), op('upper_bound', window='stale'), op('set_beliefs', B=3, seed=66),
+        op('upper_bound', window='all'), op('upper_q', window='all')]),
+    # the fourth rollout source: its survivors are the resident block, in the model's world and against both environments
+    'space_aware_rollouts_leave_their_survivors': (MODELS, DTYPES, [
+        op('set_alpha', V=12, seed=1), op('set_state_weights', kind='zero_ends', seed=1), op('upper_reset', seed=1),
+        op('upper_append', P=5, seed=1), op('set_beliefs', B=40, seed=67), op('rollout_space_aware', T=3, seed=1, objective=0),
+        op('run_fetch'), op('vmax_resident'), op('upper_bound', window='all'), op('space_aware', objective=0, terms=True),
+        op('set_beliefs', B=40, seed=68), op('rollout_space_aware', T=3, seed=2, objective=1, env='table'), op('run_fetch'),
+        op('vmax_resident'), op('upper_bound', window='all'), op('space_aware', objective=1),
+        op('set_beliefs', B=40, seed=69), op('rollout_infotaxis', T=2, seed=3), op('space_aware', objective=0),
+        op('set_beliefs', B=40, seed=70), op('rollout_space_aware', T=2, seed=4, objective=0, env='frames', env_seed=1, hold=True),
+        op('run_fetch'), op('vmax_resident'), op('upper_bound', window='all'), op('space_aware', objective=0, terms=True),
+        op('set_beliefs', B=40, seed=71), op('rollout_env', T=2, seed=5, policy=0), op('space_aware', objective=1, terms=True),
+        op('set_beliefs', B=40, seed=72), op('rollout_space_aware', T=2, seed=6, objective=1, env='frames', env_seed=1),
+        op('fetch_beliefs'), op('upper_q', window='all'),
+        op('set_beliefs', B=40, seed=73), op('rollout_space_aware', T=2, seed=7, objective=1), op('run_fetch'),
+        op('space_aware', objective=1, terms=True),
+        op('set_beliefs', B=40, seed=75), op('rollout_space_aware', T=2, seed=8, objective=0, env='table', env_seed=2, hold=True),
+        op('upper_bound', window='stale'), op('space_aware', objective=0)]),
+    # two mappings' cursors on one engine, a direct reset and an after_oom between their calls, a chunk crossed by an append
+    'mapping_cursor': (MODELS, DTYPES, [
+        op('mapping_evaluate', which=0, add=5, seed=1, B=40, update=True), op('mapping_evaluate', which=1, add=3, seed=2, B=3, update=True),
+        op('mapping_evaluate', which=0, add=2, seed=3, B=40), op('upper_bound', window='all'),
+        op('mapping_evaluate', which=0, update=True, seed=4, B=3), op('upper_reset', seed=5), op('upper_append', P=7, seed=5),
+        op('mapping_evaluate', which=0, add=1, seed=6, B=40), op('upper_q', window='stale'), op('upper_append', P=2, seed=6),
+        op('mapping_evaluate', which=0, add=2, seed=7, B=3), op('after_oom'), op('upper_refused'),
+        op('mapping_evaluate', which=1, update=True, seed=8, B=3), op('mapping_evaluate', which=0, add=60, seed=9, B=40),
+        op('upper_q', window='all', extras=True), op('mapping_evaluate', which=0, update=True, seed=10, B=129),
+        op('mapping_evaluate', which=1, add=1, seed=11, B=3)]),
 }
+
+
+def _greedy_calls_under_switches():
+    """Every switch away from its default and back, the greedy calls after every toggle: the same answers."""
+    calls = [('space_aware', dict(objective=0, terms=True)), ('upper_bound', dict(window='stale')),
+             ('upper_q', dict(window='all', extras=True))]
+    ops = [op('set_alpha', V=12, seed=1), op('set_state_weights', kind='random', seed=1), op('upper_reset', seed=1),
+           op('upper_append', P=70, seed=1), op('set_beliefs', B=40, seed=74, hits=4)]
+    for name, args in calls:
+        ops += [(name, args), op('remember', tag=name)]
+    for i, switch in enumerate(sorted(SWITCH_VALUES)):
+        for value in [v for v in SWITCH_VALUES[switch] if v != SWITCH_DEFAULTS[switch]] + [SWITCH_DEFAULTS[switch]]:
+            ops.append(sw_(switch, value))
+            back = value == SWITCH_DEFAULTS[switch]                  # (all three under the other value, one of them after it)
+            for name, args in calls[i % 3:i % 3 + 1] if back else calls:
+                ops += [(name, args), op('same_as', tag=name)]
+    return ops
+
+
+SCRIPTED['switches_do_not_reach_the_greedy_calls'] = (MODELS, DTYPES, _greedy_calls_under_switches())
 
 
 def pair_sequence(mutation):
@@ -1725,17 +2321,31 @@ def pair_sequence(mutation):
            'rollout': [op('rollout', T=2, seed=12)], 'rollout_infotaxis': [op('rollout_infotaxis', T=2, seed=13)],
            'rollout_env': [op('rollout_env', T=2, seed=14, policy=1)],
            'reset_belief_store_append': [op('reset_belief_store_append', seed=15)],
-           'after_oom': [op('after_oom')], 'oom_call': [op('oom_call')]}[mutation]
+           'after_oom': [op('after_oom')], 'oom_call': [op('oom_call')],
+           'set_state_weights': [op('set_state_weights', kind='big', seed=16)], 'clear_state_weights': [op('clear_state_weights')],
+           'upper_reset': [op('upper_reset', seed=17)], 'upper_append': [op('upper_append', P=3, seed=18)],
+           'rollout_space_aware': [op('rollout_space_aware', T=2, seed=19, objective=0)]}[mutation]
+    # the greedy calls' state: weights and a store of points, some of them rows of the block
+    greedy = [op('set_state_weights', kind='zero_ends', seed=1), op('upper_reset', seed=1), op('upper_append', P=5, seed=1)]
     if mutation in RESETS:
-        return setup + mut + [op('fetch_refused')]
-    first = [] if mutation in ('store_alpha', 'store_beliefs', 'belief_walk', 'reset_alpha_store', 'reset_belief_store_append') \
-        else [op('fetch_refused')]
-    tail = [op('fetch_beliefs'), op('infotaxis'), op('vmax_resident'), op('vmax_store'), op('run_fetch'), op('fetch_compact_into'),
+        return setup + greedy + mut + [op(q) for q in REFUSALS]
+    keeps_result = ('store_alpha', 'store_beliefs', 'belief_walk', 'reset_alpha_store', 'reset_belief_store_append') + \
+        tuple(m for m in GREEDY_MUTATIONS if m != 'rollout_space_aware')
+    first = [] if mutation in keeps_result else [op('fetch_refused')]
+    tail = [op('fetch_beliefs'), op('infotaxis'), op('space_aware', objective=0, terms=True), op('upper_bound', window='stale'),
+            op('upper_q', window='all', extras=True), op('vmax_resident'), op('vmax_store'), op('run_fetch'), op('fetch_compact_into'),
             op('keys_assemble'), op('row_hashes'), op('run_prune_fetch'), op('run_fetch_into'), op('q_values'),
             op('belief_update', seed=1), op('prune_masked', seed=1), op('prune_dominated')]
-    if mutation in ('store_alpha', 'store_beliefs', 'belief_walk', 'reset_alpha_store', 'reset_belief_store_append'):
+    if mutation == 'clear_state_weights':
+        tail = [t for t in tail if t[0] != 'space_aware']
+    if mutation in keeps_result:
         tail = tail + [op('q_values'), op('fetch_refused')]                       # these leave the result where it is
-    return setup + mut + first + tail
+    # ... and the same mutation in an engine without weights and without a corner, for the two refusals (where the mutation
+    # itself does not give the engine what they miss)
+    needs = {'rollout_space_aware': greedy[:1], 'upper_append': greedy[1:2]}.get(mutation, [])
+    refusals = [op(q) for q, givers in (('weights_refused', ('set_state_weights', 'rollout_space_aware')),
+                                        ('upper_refused', ('upper_reset', 'upper_append'))) if mutation not in givers]
+    return setup + greedy + mut + first + tail + [op('after_oom')] + setup + needs + mut + refusals
 
 
 for _i, _m in enumerate(MUTATIONS):
@@ -1744,7 +2354,9 @@ for _i, _m in enumerate(MUTATIONS):
 # which scripted sequence aims at which planted bug of the stand-ins (each must fail there)
 DEFECT_SCRIPTS = {'dead_map_kept': 'dead_triples_and_tile_lists', 'magnitude_not_merged': 'alpha_layouts_and_magnitude_row',
                   'previous_caller_order': 'sorted_blocks_of_one_size', 'fetch_after_set_alpha': 'results_of_an_earlier_backup',
-                  'store_zero_maps_kept': 'belief_store_zero_maps'}
+                  'store_zero_maps_kept': 'belief_store_zero_maps', 'weights_survive_a_reset': 'weights_lifecycle',
+                  'old_weights_read': 'weights_lifecycle', 'extra_of_the_other_objective': 'successor_score_buffers',
+                  'append_offsets_restart': 'point_store_lifecycle', 'window_sticks': 'point_store_lifecycle'}
 
 
 def scripted_cases():
@@ -1754,37 +2366,59 @@ def scripted_cases():
 # --------------------------------------------------------------------------------------------------------------------- #
 # seeded random sequences
 # --------------------------------------------------------------------------------------------------------------------- #
-QUERY_WEIGHTS = {'run_fetch': 4, 'run_prune_fetch': 2, 'vmax_resident': 2, 'vmax_store': 2, 'q_values': 2, 'run_fetch_into': 2}
+QUERY_WEIGHTS = {'run_fetch': 4, 'run_prune_fetch': 2, 'vmax_resident': 2, 'vmax_store': 2, 'q_values': 2, 'run_fetch_into': 2,
+                 'space_aware': 4, 'upper_bound': 4, 'upper_q': 4}        # (the greedy calls: the weight a backup has)
 MUTATION_WEIGHTS = {'after_oom': 0.2, 'oom_call': 0.2}            # (a reset empties the engine: rare, and re-populated at once)
 ECHOED = ('set_alpha', 'set_beliefs', 'select_beliefs', 'extend_alpha', 'reset_belief_store_append')
+ECHOED_V2 = ECHOED + ('set_state_weights', 'upper_append')
 MIN_VALUE_QUERIES, MIN_BACKUPS = 8, 3                           # per seeded sequence (fetch_refused compares no value)
+MAX_UPPER_Q_ROWS = 64                                           # (the host's bounds walk every successor in Python)
+SUPPORT_CHOICES = (hc.SUPPORTS, hc.SUPPORTS[1:], (65, None))
 
 
-def draw_op(rng, sh, kind, last=None):
+def draw_op(rng, sh, kind, last=None, vocabulary=1):
     """One operation of ``kind`` ('query', 'mutation', 'switch') drawn for the shadow's state (legality is the caller's).
     ``last``: the most recent mutation.  Carry-overs show when the same kind of state comes again with other content, so
     four times in ten a mutation repeats the last one's kind and sizes with another seed and window; queries lean towards
-    the backup, and towards the store scan behind a change of the belief store."""
+    the backup, and towards the store scan behind a change of the belief store.  ``vocabulary``: 1 -- the names before the
+    greedy calls came (the first committed lists are drawn from them, draw for draw); 2 -- every name."""
     pick = lambda xs: xs[int(rng.integers(0, len(xs)))]
     seed = int(rng.integers(1, 1000))
+    v2 = vocabulary >= 2
+    queries = QUERIES if v2 else QUERIES_V1
     if kind == 'query':
-        w = np.array([QUERY_WEIGHTS.get(q, 1) for q in QUERIES], dtype=np.float64)
+        w = np.array([QUERY_WEIGHTS.get(q, 1) for q in queries], dtype=np.float64)
         if last is not None and last[0] in ('store_beliefs', 'reset_belief_store_append', 'belief_walk'):
-            w[QUERIES.index('vmax_store')] *= 6
-        name = QUERIES[int(rng.choice(len(QUERIES), p=w / w.sum()))]
+            w[queries.index('vmax_store')] *= 6
+        name = queries[int(rng.choice(len(queries), p=w / w.sum()))]
+        if name == 'space_aware':
+            return op(name, objective=int(pick((0, 1))), terms=bool(rng.random() < 0.5))
+        if name == 'upper_bound':
+            return op(name, window=pick(WINDOWS))
+        if name == 'upper_q':
+            return op(name, window=pick(WINDOWS), extras=bool(rng.random() < 0.5))
+        if name == 'infotaxis' and v2:
+            return op(name, extras=bool(rng.random() < 0.5))
         return op(name, seed=seed) if name in ('prune_masked', 'belief_update') else op(name)
     if kind == 'switch':
         name = pick(sorted(SWITCH_VALUES))
         value = pick([v for v in SWITCH_VALUES[name] if v != sh.switches[name]])
         return sw_(name, value)
     win = pick((None, LOW, HIGH, (0.25, 0.75)))
-    if last is not None and last[0] in ECHOED and rng.random() < 0.4:
+    if last is not None and last[0] in (ECHOED_V2 if v2 else ECHOED) and rng.random() < 0.4:
         args = dict(last[1], seed=seed)
         if 'win' in args:
             args['win'] = win
+        if 'kind' in args:
+            args['kind'] = pick(tsa.WEIGHT_KINDS)
         return (last[0], args)
-    names = MUTATIONS + COMPOUND
+    names = MUTATIONS + COMPOUND if v2 else MUTATIONS_V1 + COMPOUND_V1
     w = np.array([MUTATION_WEIGHTS.get(n, 1.0) for n in names])
+    if v2:                                                        # the greedy calls need their state: it comes back soon
+        w[names.index('set_state_weights')] = 2.0 if sh.weights is None else 1.0
+        w[names.index('upper_reset')] = 2.0 if sh.store is None else 0.4
+        w[names.index('upper_append')] = 2.0
+        w[names.index('clear_state_weights')] = 0.4
     name = names[int(rng.choice(len(names), p=w / w.sum()))]
     small = rng.random() < 0.6                                    # most sets are small; every edge still comes up
     V = int(pick((5, 12, 40) if small else V_EDGES))
@@ -1795,8 +2429,25 @@ def draw_op(rng, sh, kind, last=None):
         return op(name, V=int(pick((1, 3, 5, 12, 250, 600))), seed=seed, scale=float(pick((4.0, 40.0))), near=int(pick((0, 4, 40))))
     if name == 'select_alpha':
         return op(name, how=pick(('small', 'primary', 'all', 'fresh')), seed=seed)
+    if name == 'set_beliefs' and v2:
+        hits = int(pick((0, 4, 4)))
+        return op(name, B=B, seed=seed, win=win, onehot=bool(rng.random() < 0.3), hits=hits if sh.n_points else 0)
     if name in ('set_beliefs', 'store_beliefs'):
         return op(name, B=B, seed=seed, win=win, onehot=bool(rng.random() < 0.3))
+    if name == 'set_state_weights':
+        return op(name, kind=pick(tsa.WEIGHT_KINDS), seed=seed)
+    if name == 'upper_reset':
+        return op(name, seed=seed)
+    if name == 'upper_append':
+        return op(name, P=int(pick((0, 1, 5, 40, 64, 65))), seed=seed, supports=pick(SUPPORT_CHOICES))
+    if name == 'rollout_space_aware':
+        return op(name, T=int(pick((1, 3, 5))), seed=seed, objective=int(pick((0, 1))), env=pick((None, 'table', 'frames')),
+                  env_seed=int(pick((0, 1, 2))), hold=bool(rng.random() < 0.5))
+    if name == 'mapping_evaluate':
+        add = int(pick((0, 1, 5)))
+        return op(name, which=int(pick((0, 1))), add=add, seed=seed, B=int(pick((3, 40))), update=bool(add == 0 or rng.random() < 0.5))
+    if name == 'run_only':
+        return op(name, prune=bool(rng.random() < 0.3))
     if name == 'select_beliefs':
         return op(name, how=pick(('same', 'last', 'random', 'random')), B=B, seed=seed)
     if name == 'advance_beliefs':
@@ -1817,19 +2468,31 @@ def draw_op(rng, sh, kind, last=None):
     return op(name)
 
 
+def seed_parts(seed):
+    """``(vocabulary, number)`` of a committed seed: a plain number (the first vocabulary) or ``'v2-<number>'``."""
+    if isinstance(seed, str):
+        v, n = seed.split('-')
+        return int(v[1:]), int(n)
+    return 1, int(seed)
+
+
 def generate(mname, dtype, seed, n_ops=N_RANDOM_OPS):
     """``n_ops`` operations, about one in three a query that compares a value (more often behind a mutation than behind a
     query), each legal in the state the ones before it leave.  The state is followed with a ``HostEngine`` (rollouts and
     keep masks decide how many rows stay), so the list depends on nothing but the arguments.  It starts from selections
     out of both stores, the state a solve is in; a reset, or a rollout that nobody survives, is followed at once by new
     working sets, so the walk does not sit in an empty engine."""
-    rng = np.random.default_rng([sw.seed_of('sequence', mname, dtype), int(seed)])
+    vocabulary, seed = seed_parts(seed)
+    rng = np.random.default_rng([sw.seed_of('sequence', mname, dtype), int(seed)] + ([vocabulary] if vocabulary > 1 else []))
     r = Runner(mname, dtype, lambda: HostEngine(mname, dtype))
     B0 = int((40, 257, 129, 300)[int(seed) % 4])
     ops = [op('store_alpha', V=12, seed=int(seed) + 1), op('select_alpha', how='all'),
            op('store_beliefs', B=B0, seed=int(seed) + 1, win=LOW, onehot=True), op('select_beliefs', how='last', B=B0)]
+    if vocabulary > 1:                                            # ... and with weights and a point store
+        ops = [op('set_state_weights', kind=tsa.WEIGHT_KINDS[int(seed) % 5], seed=int(seed) + 1), op('upper_reset', seed=int(seed) + 1),
+               op('upper_append', P=int((5, 63, 64, 70)[int(seed) % 4]), seed=int(seed) + 1)] + ops
     r.run(ops)
-    last, prev_kind = ops[2], 'mutation'
+    last, prev_kind = ops[-2], 'mutation'
 
     def add(cand):
         r.run([cand])
@@ -1849,8 +2512,12 @@ def generate(mname, dtype, seed, n_ops=N_RANDOM_OPS):
         u = rng.random()
         kind = 'query' if u < p_query else ('switch' if u < p_query + 0.15 else 'mutation')
         for _ in range(100):
-            cand = draw_op(rng, r.sh, kind, last)
+            cand = draw_op(rng, r.sh, kind, last, vocabulary)
             if not legal(cand[0], cand[1], r.sh):
+                continue
+            if cand[0] == 'upper_q' and r.sh.B > MAX_UPPER_Q_ROWS:
+                continue
+            if cand[0] == 'mapping_evaluate' and len(r.maps.get(cand[1]['which'], SimpleNamespace(beliefs=())).beliefs) + cand[1]['add'] > MAX_POINTS:
                 continue
             if cand[0] in ('append_alpha', 'extend_alpha') and r.sh.V + cand[1]['V'] > 1300:
                 continue
@@ -1877,8 +2544,14 @@ SEEDS = {('G', 'f32'): (0, 2, 3, 5, 7, 15, 34, 37), ('G', 'f64'): (0, 1, 2, 3, 4
          ('I', 'f32'): (0, 2, 4, 6, 10, 18, 19, 25), ('I', 'f64'): (0, 1, 2, 3, 6, 16, 19, 20)}
 
 
+# the seeds of the full vocabulary: chosen the same way, every stand-in of the greedy calls failing at least one of them
+SEEDS_V2 = {('G', 'f32'): (1, 4, 5, 7, 10, 21, 25, 28), ('G', 'f64'): (1, 3, 6, 15, 18, 19, 28, 34),
+            ('I', 'f32'): (0, 3, 8, 10, 12, 17, 26, 33), ('I', 'f64'): (2, 3, 8, 9, 10, 17, 29, 37)}
+
+
 def seeded_cases():
-    return [(mname, dtype, seed) for mname in MODELS for dtype in DTYPES for seed in SEEDS[mname, dtype]]
+    return [(mname, dtype, seed) for mname in MODELS for dtype in DTYPES for seed in SEEDS[mname, dtype]] + \
+        [(mname, dtype, f'v2-{seed}') for mname in MODELS for dtype in DTYPES for seed in SEEDS_V2[mname, dtype]]
 
 
 def to_json(ops):
@@ -1892,13 +2565,18 @@ def from_json(ops):
 # --------------------------------------------------------------------------------------------------------------------- #
 # coverage accounting over lists of operations
 # --------------------------------------------------------------------------------------------------------------------- #
-NEVER_LEGAL_AFTER_A_RESET = {(m, q) for m in RESETS for q in QUERIES if q != 'fetch_refused'}
+NEVER_LEGAL_AFTER_A_RESET = {(m, q) for m in RESETS for q in QUERIES if q not in REFUSALS}
+# a refusal is never legal right behind the mutation that gives the engine what the call misses, nor the call behind the
+# mutation that takes it away
+NEVER_LEGAL_BY_CONSTRUCTION = {('set_state_weights', 'weights_refused'), ('rollout_space_aware', 'weights_refused'),
+                               ('clear_state_weights', 'space_aware'), ('upper_reset', 'upper_refused'), ('upper_append', 'upper_refused')}
 
 
 def coverage(sequences):
     """Counts over ``[(mname, dtype, ops)]``: operations, (most recent mutation -> query) pairs, switch values, B and V."""
     counts = {n: 0 for n in VOCABULARY}
     pairs, switch_values, Bs, Vs, hows, returned, envs = set(), set(), set(), set(), set(), set(), set()
+    greedy = {k: set() for k in ('kinds', 'windows', 'q_windows', 'appends', 'supports', 'space_aware', 'sa_rollouts', 'hit_blocks', 'mapping')}
     for _, _, ops in sequences:
         last, now, left = None, dict(SWITCH_DEFAULTS), set()
         for name, args in ops:
@@ -1926,5 +2604,22 @@ def coverage(sequences):
                 Vs.add(args['V'])
             if name == 'select_alpha':
                 hows.add(args['how'])
+            if name == 'set_state_weights':
+                greedy['kinds'].add(args['kind'])
+            if name == 'upper_bound':
+                greedy['windows'].add(args.get('window', 'all'))
+            if name == 'upper_q':
+                greedy['q_windows'].add((args.get('window', 'all'), bool(args.get('extras', False))))
+            if name == 'upper_append':
+                greedy['appends'].add(args['P'])
+                greedy['supports'] |= set(args.get('supports', hc.SUPPORTS))
+            if name == 'space_aware':
+                greedy['space_aware'].add((args['objective'], bool(args.get('terms', False))))
+            if name == 'rollout_space_aware':
+                greedy['sa_rollouts'].add((args.get('objective', 0), args.get('env')))
+            if name == 'set_beliefs' and args.get('hits', 0):
+                greedy['hit_blocks'].add(args['B'])
+            if name == 'mapping_evaluate':
+                greedy['mapping'].add((args.get('which', 0), bool(args.get('add', 0)), bool(args.get('update', False))))
     return SimpleNamespace(counts=counts, pairs=pairs, switch_values=switch_values, Bs=Bs, Vs=Vs, hows=hows, returned=returned,
-                           envs=envs)
+                           envs=envs, **greedy)

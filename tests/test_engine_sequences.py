@@ -10,12 +10,13 @@ fused tile map, the belief store's zero maps, the speculation about the refineme
 ``sequence_cases.py`` holds the sequences (scripted ones aimed at one carry-over each, seeded random ones), the shadow of
 the logical state and the ``Runner`` that, after every query, compares the engine with (a) the fp64 host statements on the
 shadow's arrays and (b) a fresh engine brought to that state by ``set_alpha`` / ``set_beliefs``: indices, actions, masks,
-unique rows, keys, hashes, ``q``, infotaxis, ``fetch_beliefs`` and rollout trajectories byte for byte, value maxima (also
+unique rows, keys, hashes, ``q``, infotaxis, space-aware infotaxis, the sawtooth bound and its action values (over a point
+store the fresh engine receives in ONE append), ``fetch_beliefs`` and rollout trajectories byte for byte, value maxima (also
 through ``max_value_objects``) and, where the score probe is on, ``best_score`` at the bar.  Where the engine's own output becomes state (``advance_beliefs``, ``belief_walk``, rollout survivors, ``store_unique``)
 it is checked against the host statement at the bar and its bits are adopted into the shadow.
 
 CPU tests: every sequence runs against ``HostEngine`` (the host statements under ``Engine``'s method names) with no entry
-skipped as undecidable; five stand-ins with one planted carry-over bug each fail a scripted and a seeded sequence; the
+skipped as undecidable; ten stand-ins with one planted carry-over bug each fail a scripted and a seeded sequence; the
 operation lists cover the vocabulary.  GPU tests: the same sequences on the HIP engine, both models, both engine types.
 """
 import functools
@@ -93,7 +94,7 @@ def test_the_sequences_cover_the_vocabulary():
     cov = sc.coverage(all_sequences())
     rare = {k: v for k, v in cov.counts.items() if v < 5}
     assert not rare, rare
-    missing = {(m, q) for m in sc.MUTATIONS for q in sc.QUERIES} - sc.NEVER_LEGAL_AFTER_A_RESET - cov.pairs
+    missing = {(m, q) for m in sc.MUTATIONS for q in sc.QUERIES} - sc.NEVER_LEGAL_AFTER_A_RESET - sc.NEVER_LEGAL_BY_CONSTRUCTION - cov.pairs
     assert not missing, sorted(missing)
     for name, values in sc.SWITCH_VALUES.items():                      # every listed value; away from the default and back
         seen = {v for n, v in cov.switch_values if n == name}
@@ -102,6 +103,16 @@ def test_the_sequences_cover_the_vocabulary():
     assert cov.envs >= {('table', False), ('table', True), ('frames', False), ('frames', True)}, cov.envs
     assert set(sc.B_EDGES) <= cov.Bs and set(sc.V_EDGES) <= cov.Vs, (cov.Bs, cov.Vs)
     assert cov.hows >= {'small', 'primary', 'all', 'fresh'}
+    # the greedy calls: every kind of weights, every window, both objectives with and without terms, in the model's world and
+    # against both environments; appends of 0, 1 and several points, supports on both sides of a wavefront, point counts
+    # below, at and above one chunk of the sawtooth, hits in blocks on both sides of the sorted-block threshold
+    assert cov.kinds >= set(sc.tsa.WEIGHT_KINDS), cov.kinds
+    assert cov.windows >= set(sc.WINDOWS) and cov.q_windows >= {(w, e) for w in sc.WINDOWS for e in (False, True)}, (cov.windows, cov.q_windows)
+    assert cov.space_aware >= {(o, t) for o in (0, 1) for t in (False, True)}, cov.space_aware
+    assert cov.sa_rollouts >= {(o, e) for o in (0, 1) for e in (None, 'table', 'frames')}, cov.sa_rollouts
+    assert cov.appends >= {0, 1, 63, 64, 65} and cov.supports >= set(sc.hc.SUPPORTS), (cov.appends, cov.supports)
+    assert cov.hit_blocks >= {3, 257, 300}, cov.hit_blocks
+    assert cov.mapping >= {(w, a, u) for w in (0, 1) for a, u in ((True, True), (True, False), (False, True))}, cov.mapping
     # the four forms a selection of alpha rows takes, named by the shadow's restatement of the engine's bookkeeping
     forms = set()
     for mname, dtype, ops in all_sequences()[:len(sc.scripted_cases())]:
