@@ -1036,6 +1036,89 @@ struct BeliefBlock {
     void emptied() { replaced(0, 0, false); }
 };
 
+// The working alpha set.  `view` holds V data rows, the magnitude row (column-wise max |alpha|) and zero rows up to the next
+// multiple of 256 + 256, inside one of two allocations:
+//   buf   -- the set as uploaded (alpha_set / alpha_append: view at row 0), or the PRIMARY set selected from the alpha store,
+//            laid out with `off` free rows in FRONT of it: the solve loop's next set is its new rows followed by the previous
+//            set (ValueFunction.extend: new-then-old, and first-max ties go to the lower index, so the order is part of the
+//            result) -- those rows are gathered into the free rows just before the view, which then starts k rows earlier;
+//            nothing else moves, the magnitude row takes the maximum with the new rows.  (Re-gathering 10^4 rows per backup
+//            was 0.1 s of a 300-expansion solve, the fp32 copy for the screen of an fp64 engine another 0.09 s.)
+//   small -- a selection much smaller than the primary set (compute_change scores the rows an expansion added): gathered
+//            here so that the primary set is still there for the next backup.
+// `ver` names the rows the view holds; placed() is the one place that moves view, V and ver.  Where the view lies is `place`,
+// and whether a selection can still extend the primary layout follows from it: NONE no set; PLAIN uploaded; PRIMARY row `off`
+// of buf, `ids` name its rows; BESIDE in `small`, the primary layout waits in buf; the ORPHANs are the same two once the ids
+// name nothing any more (the alpha store was reset; also what an fp32 screen holds of its engine's primary layout).
+template <typename T>
+struct AlphaSet {
+    enum Place { NONE, PLAIN, PRIMARY, BESIDE, PRIMARY_ORPHAN, BESIDE_ORPHAN };
+    DevBuf buf, small;
+    DevView view;
+    int64_t V = 0, ld = 0;            // data rows; elements per row (S_pad, set when the engine is initialised)
+    uint64_t ver = 1;
+    Place place = NONE;
+    std::vector<int32_t> ids;         // store ids of the primary set, view order
+    int64_t off = 0;                  // first data row of the primary set inside buf
+    uint64_t layout_ver = 0;          // counts the fresh layouts of a selected set (an fp64 engine's screen mirrors them)
+    explicit AlphaSet(DevMem& m) : buf(m), small(m) {}
+
+    T* rows() const { return view.template as<T>(); }
+    T* mag_row() const { return rows() + (size_t)V * ld; }
+    size_t row_bytes() const { return (size_t)ld * sizeof(T); }
+    static size_t rows_cap(int64_t v) { return (size_t)round_up(v + 1, GEMM_BN); }
+    bool on_primary() const { return place == PRIMARY || place == PRIMARY_ORPHAN; }
+    bool primary_alive() const { return place == PRIMARY || place == BESIDE; }
+    // no rows are kept free in front of the view (true also of a primary layout whose free rows are used up)
+    bool starts_allocation() const { return place == PLAIN || (on_primary() && off == 0); }
+
+    // the set is now `v` rows from row `first` of its allocation (BESIDE: of `small`); a primary layout's `off` moves with it
+    void placed(Place where, int64_t first, int64_t v) {
+        const DevView& own = (where == BESIDE || where == BESIDE_ORPHAN) ? small : buf;
+        const size_t skip = (size_t)first * row_bytes();
+        place = where;
+        if (on_primary()) off = first;
+        view.p = static_cast<char*>(own.p) + skip;
+        view.cap = own.cap - skip;
+        V = v;
+        ++ver;
+    }
+    // the allocations are gone (after_oom)
+    void emptied() {
+        view = DevView{};
+        place = NONE;
+        V = off = 0;
+        ids.clear();
+        ++ver;
+    }
+    // the ids of the primary layout name store rows that are gone; the view stays
+    void primary_given_up() {
+        ids.clear();
+        if (place == PRIMARY) place = PRIMARY_ORPHAN;
+        if (place == BESIDE) place = BESIDE_ORPHAN;
+    }
+
+    // What a selection of store rows `id[0, n)` does to the layout (prepend = false: always a fresh, plain one).  `rows` --
+    // EXTEND: new rows in front of the primary set (0: the primary set again); FRESH: rows kept free in front.
+    struct Selection {
+        enum Kind { EXTEND, SMALL, FRESH } kind;
+        int64_t rows;
+    };
+    Selection selection(const int32_t* id, int64_t n, bool prepend) const {
+        const int64_t pv = (int64_t)ids.size();
+        if (prepend && primary_alive()) {
+            if (n >= pv && n - pv <= off && std::equal(ids.begin(), ids.end(), id + (n - pv))) return {Selection::EXTEND, n - pv};
+            if (n <= 4096 && 4 * n <= pv) return {Selection::SMALL, 0};      // much smaller than the primary set: beside it
+        }
+        return {Selection::FRESH, prepend ? std::max<int64_t>(512, n / 2) : 0};
+    }
+    // the selection's ids enter the primary layout's record
+    void selected(const Selection& s, const int32_t* id, int64_t n) {
+        if (s.kind != Selection::SMALL) ids.assign(id, id + n);          // (an extension: the new ids in front of the old ones)
+        if (s.kind == Selection::FRESH) ++layout_ver;
+    }
+};
+
 class EngineBase {
    public:
     virtual ~EngineBase() {}
@@ -1153,26 +1236,7 @@ class EngineT : public EngineBase {
     double tie_rel_user_ = -1.0;
 
     DevBuf rs_{mem_, DevBuf::MODEL}, rto_{mem_, DevBuf::MODEL}, er_{mem_, DevBuf::MODEL}, sup_{mem_, DevBuf::MODEL};
-    // The working alpha set.  alpha_ is a VIEW of V_ data rows, the magnitude row and
-    // zero rows up to the next multiple of 256 + 256, inside one of two allocations:
-    //   alpha_buf_   -- the set as uploaded (alpha_set / alpha_append: view at row 0), or the PRIMARY set selected from the
-    //                   alpha store, laid out with free rows in FRONT of it: the solve loop's next set is its new rows followed
-    //                   by the previous set (ValueFunction.extend: new-then-old, and first-max ties go to the lower index, so
-    //                   the order is part of the result) -- those rows are gathered into the free rows just before the
-    //                   view, which then starts k rows earlier; nothing else moves, the magnitude row takes the maximum
-    //                   with the new rows.  (Re-gathering 10^4 rows per backup was 0.1 s of a 300-expansion solve, the fp32
-    //                   copy for the screen of an fp64 engine another 0.09 s.)
-    //   alpha_small_ -- a selection much smaller than the primary set (compute_change scores the rows an expansion added):
-    //                   gathered here so that the primary set is still there for the next backup.
-    DevView alpha_;
-    DevBuf alpha_buf_{mem_}, alpha_small_{mem_};
-    std::vector<int32_t> prim_ids_;                          // store ids of the primary set, view order
-    int64_t prim_off_ = 0;                                   // first data row of the primary set inside alpha_buf_
-    bool prim_valid_ = false, alpha_on_primary_ = false;
-    uint64_t prim_layout_ver_ = 0;                           // a fresh layout of the primary set (the screen mirrors it)
-    uint64_t screen_layout_seen_ = 0;                        // fp64 engines: layout / first row the screen's copy reflects
-    int64_t screen_off_seen_ = 0;
-    int64_t V_ = 0;
+    AlphaSet<T> al_{mem_};                                   // the working alpha set, its placement and the primary layout's record
     BeliefBlock blk_{mem_};                                  // the resident belief block and what is derived from it
     DevBuf gam_{mem_}, slabs_{mem_}, best_v_{mem_}, best_score_{mem_}, err_{mem_}, dead_{mem_}, queue_{mem_}, hcand_{mem_}, hncand_{mem_}, counters_{mem_, DevBuf::MODEL}, rdot_{mem_}, aqueue_{mem_}, keep_{mem_};
     // the backup's decision: actions, the belief reordering undone (f32, B > 256), K6 key dedup; fin_.rows holds the unique rows
@@ -1199,10 +1263,10 @@ class EngineT : public EngineBase {
     // as rows are appended
     DevBuf snz_{mem_}, sbtl_{mem_}, sbtc_{mem_};
     int64_t snz_rows_ = 0, sbt_rows_ = 0;
-    int64_t walk_rows_ = 0;
+    int64_t walk_rows_ = 0;                                  // rows the last belief_walk left in walk64_
     DevBuf vmax_bk_{mem_};   // max_v b.alpha_v of the last backup's beliefs (belief-side GEMM's extra rows)
     bool have_bk_vmax_ = false;
-    hipEvent_t walk_ev_[8] = {};                            // belief_walk: chain -> copy -> host hand-offs, per quarter                                 // rows the last belief_walk left in walk64_
+    hipEvent_t walk_ev_[8] = {};                            // belief_walk: chain -> copy -> host hand-offs, per quarter
     Delivery out_{pinned_};   // every result's way to the caller's memory (owns the pinned staging buffer)
     DevBuf keys_tmp_{mem_}, keys_act_{mem_}, keys_best_{mem_}, keys_rows_{mem_};   // unique-row keys out / rows from keys in (multi-GPU exchange)
     DevBuf acand_{mem_};   // [B][A] action inside the window (k_action_select -> k_refine_action)
@@ -1329,8 +1393,9 @@ class EngineT : public EngineBase {
     EngineT<float>* screen_ = nullptr;                       // fp64 engines: the fp32 screen (see ensure_screen)
     std::vector<int32_t> h_reach_ref_;                       // fp64 engines: the tables in the reference's layout, kept
     std::vector<double> h_rto_ref_, h_er_ref_;               //   to build the screen on first use
-    uint64_t alpha_ver_ = 1;                                 // bumped whenever alpha_ changes
-    uint64_t screen_alpha_seen_ = 0, screen_bel_seen_ = 0;   // the alpha_ver_ / blk_.ver the screen's copies reflect
+    // fp64 engines, what the screen's copies reflect: al_.ver, the primary layout mirrored (0: none), its first row; blk_.ver
+    struct { uint64_t ver = 0, layout_ver = 0; int64_t off = 0; } screen_alpha_seen_;
+    uint64_t screen_bel_seen_ = 0;
 
     ~EngineT() override {
         (void)hipSetDevice(device_);
@@ -1379,6 +1444,7 @@ class EngineT : public EngineBase {
         R_ = R;
         mode_ = mode;
         S_pad_ = (int)round_up(S, GEMM_BK);
+        al_.ld = S_pad_;
         if (const char* f = getenv("PBVI_F64_SCREEN")) {      // initial setting (tests run the whole suite with the screen forced)
             const std::string v(f);
             screen_mode_ = (v == "off" || v == "0") ? 0 : (v == "always" || v == "2") ? 2 : 1;
@@ -1582,79 +1648,61 @@ class EngineT : public EngineBase {
     }
 
     // ---- alpha set ------------------------------------------------------- //
-    size_t alpha_rows_cap(int64_t V) const { return (size_t)round_up(V + 1, GEMM_BN); }
-
-    void alpha_view(const DevView& own, int64_t row_off) {
-        const size_t skip = (size_t)row_off * S_pad_ * sizeof(T);
-        alpha_.p = static_cast<char*>(own.p) + skip;
-        alpha_.cap = own.cap - skip;
-    }
-
-    // magnitude row (row V_ of the view) := column-wise max |alpha| of the view's rows
-    int refresh_magnitude_row() {
-        T* base = alpha_.as<T>();
-        HIPCHK(hipMemsetAsync(base + (size_t)V_ * S_pad_, 0, (size_t)S_pad_ * sizeof(T), stream_));
-        return merge_magnitude_row(base, V_);
-    }
-    // ... := max(itself, column-wise max |.| of `n` rows at `rows`)
-    int merge_magnitude_row(const T* rows, int64_t n) {
-        if (n <= 0) return PBVI_OK;
-        hipLaunchKernelGGL(k_col_absmax<T>, dim3((S_pad_ + 255) / 256, (unsigned)((n + 127) / 128)), dim3(256), 0, stream_,
-                           rows, S_pad_, (int)n, S_pad_, alpha_.as<T>() + (size_t)V_ * S_pad_);
-        HIPCHK(hipGetLastError());
+    // Every writer of the working set ends here, al_ placed() and the rows on their way in stream_.  The magnitude row catches
+    // up with the new rows: all of the view's (grown == nullptr: zeroed, then their column maximum) or `n` at `grown` (merged
+    // into it).  The caller's arrays have been read when this returns -- a screen's copy is installed in the middle of its
+    // fp64 engine's backup, on the streams they share, and does not wait -- and no result of another set can be fetched.
+    int alpha_installed(const T* grown = nullptr, int64_t n = 0) {
+        if (!grown) {
+            HIPCHK(hipMemsetAsync(al_.mag_row(), 0, al_.row_bytes(), stream_));
+            grown = al_.rows();
+            n = al_.V;
+        }
+        if (n > 0) {
+            hipLaunchKernelGGL(k_col_absmax<T>, dim3((S_pad_ + 255) / 256, (unsigned)((n + 127) / 128)), dim3(256), 0, stream_,
+                               grown, S_pad_, (int)n, S_pad_, al_.mag_row());
+            HIPCHK(hipGetLastError());
+        }
+        if (owns_streams_) HIPCHK(hipStreamSynchronize(stream_));
+        have_result_ = false;
         return PBVI_OK;
     }
 
     int alpha_set(const void* alpha, int64_t V) override {
         if (V <= 0 || alpha == nullptr) FAIL(PBVI_EINVAL, "alpha_set: need V > 0 and a non-null array");
         HIPCHK(hipSetDevice(device_));
-        const size_t rows = alpha_rows_cap(V);
-        int rc = alpha_buf_.ensure(rows * S_pad_ * sizeof(T));
+        int rc = al_.buf.ensure(al_.rows_cap(V) * al_.row_bytes());
         if (rc) return rc;
-        alpha_view(alpha_buf_, 0);
-        prim_valid_ = alpha_on_primary_ = false;
-        HIPCHK(hipMemsetAsync(alpha_.p, 0, alpha_.cap, stream_));
-        HIPCHK(hipMemcpy2DAsync(alpha_.p, (size_t)S_pad_ * sizeof(T), alpha, (size_t)S_ * sizeof(T),
-                                (size_t)S_ * sizeof(T), (size_t)V, hipMemcpyHostToDevice, stream_));
-        V_ = V;
-        ++alpha_ver_;
-        rc = refresh_magnitude_row();
-        if (rc) return rc;
-        HIPCHK(hipStreamSynchronize(stream_));
-        have_result_ = false;
-        return PBVI_OK;
+        al_.placed(al_.PLAIN, 0, V);
+        HIPCHK(hipMemsetAsync(al_.view.p, 0, al_.view.cap, stream_));
+        HIPCHK(hipMemcpy2DAsync(al_.view.p, al_.row_bytes(), alpha, (size_t)S_ * sizeof(T), (size_t)S_ * sizeof(T), (size_t)V,
+                                hipMemcpyHostToDevice, stream_));
+        return alpha_installed();
     }
 
     int alpha_append(const void* alpha, int64_t n) override {
         if (n < 0 || (n > 0 && alpha == nullptr)) FAIL(PBVI_EINVAL, "alpha_append: bad arguments");
         if (n == 0) return PBVI_OK;
         HIPCHK(hipSetDevice(device_));
-        const int64_t Vn = V_ + n;
-        const size_t need = alpha_rows_cap(Vn) * S_pad_ * sizeof(T);
-        const bool plain = alpha_.p == alpha_buf_.p;          // the view starts the allocation (no rows kept free in front)
-        if (need > alpha_.cap || !plain) {   // grow (or move to a plain layout), preserving the resident rows
-            // (the rows are copied from the view: it may start inside alpha_buf_ or lie in alpha_small_)
-            int rc = grow_keep(alpha_buf_, need, (size_t)V_ * S_pad_ * sizeof(T), std::max(need, plain ? alpha_buf_.cap * 2 : need),
-                               alpha_.p, true);
+        const int64_t Vn = al_.V + n;
+        const size_t need = al_.rows_cap(Vn) * al_.row_bytes();
+        const bool plain = al_.starts_allocation();
+        if (need > al_.view.cap || !plain) {   // grow (or move to a plain layout), preserving the resident rows
+            // (the rows are copied from the view: it may start inside al_.buf or lie in al_.small)
+            int rc = grow_keep(al_.buf, need, (size_t)al_.V * al_.row_bytes(), std::max(need, plain ? al_.buf.cap * 2 : need),
+                               al_.view.p, true);
             if (rc) return rc;
-            alpha_view(alpha_buf_, 0);
         } else {
             // clear the old magnitude row's pad columns / content before it becomes a data row
-            HIPCHK(hipMemsetAsync(alpha_.as<T>() + (size_t)V_ * S_pad_, 0, (size_t)S_pad_ * sizeof(T), stream_));
+            HIPCHK(hipMemsetAsync(al_.mag_row(), 0, al_.row_bytes(), stream_));
         }
-        prim_valid_ = alpha_on_primary_ = false;
-        HIPCHK(hipMemcpy2DAsync(alpha_.as<T>() + (size_t)V_ * S_pad_, (size_t)S_pad_ * sizeof(T), alpha,
-                                (size_t)S_ * sizeof(T), (size_t)S_ * sizeof(T), (size_t)n, hipMemcpyHostToDevice, stream_));
-        V_ = Vn;
-        ++alpha_ver_;
-        int rc = refresh_magnitude_row();
-        if (rc) return rc;
-        HIPCHK(hipStreamSynchronize(stream_));
-        have_result_ = false;
-        return PBVI_OK;
+        al_.placed(al_.PLAIN, 0, Vn);                         // (a primary layout is given up with it)
+        HIPCHK(hipMemcpy2DAsync(al_.rows() + (size_t)(Vn - n) * S_pad_, al_.row_bytes(), alpha, (size_t)S_ * sizeof(T),
+                                (size_t)S_ * sizeof(T), (size_t)n, hipMemcpyHostToDevice, stream_));
+        return alpha_installed();
     }
 
-    int64_t alpha_count() const override { return V_; }
+    int64_t alpha_count() const override { return al_.V; }
 
     // Belief block from rows on the device -- `src` [.][S_pad], row b of the block = src row (src_ids ? src_ids[b] : b) --
     // reordered, padded to the GEMM's 256-row blocks, with its zero-tile map.  Stream-ordered, no host synchronisation:
@@ -2237,7 +2285,7 @@ class EngineT : public EngineBase {
         if (env && env_kind_ == ENV_NONE) FAIL(PBVI_EINVAL, "rollout_env: no environment set (call pbvi_env_set_frames or pbvi_env_set_table)");
         if (env && call.end_observation >= O_) FAIL(PBVI_EINVAL, "rollout_env: end_observation is not below O");
         if (env && call.shifts && env_kind_ != ENV_FRAMES) FAIL(PBVI_EINVAL, "rollout_env: shifts are for a frame environment, and a table is set");
-        if (uses_alpha && V_ <= 0) FAIL(PBVI_EINVAL, "rollout: no alpha set resident (call pbvi_alpha_set)");
+        if (uses_alpha && al_.V <= 0) FAIL(PBVI_EINVAL, "rollout: no alpha set resident (call pbvi_alpha_set)");
         if (blk_.B <= 0) FAIL(PBVI_EINVAL, "rollout: no belief block resident (call pbvi_beliefs_set)");
         if ((uses_alpha && !call.alpha_actions) || !call.start_states || !call.end_mask) FAIL(PBVI_EINVAL, "rollout: NULL argument");
         if (!info.known) FAIL(PBVI_EINVAL, "rollout: lookahead must be 0 or 1");
@@ -2252,7 +2300,7 @@ class EngineT : public EngineBase {
         if ((int64_t)S_ * R_ > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "rollout: S*R exceeds int32");
         for (int64_t b = 0; b < n0; ++b)
             if (call.start_states[b] < 0 || call.start_states[b] >= S_) FAIL(PBVI_EINVAL, "rollout: start state out of range [0,S)");
-        for (int64_t v = 0; uses_alpha && v < V_; ++v)
+        for (int64_t v = 0; uses_alpha && v < al_.V; ++v)
             if (call.alpha_actions[v] < 0 || call.alpha_actions[v] >= A_) FAIL(PBVI_EINVAL, "rollout: alpha_actions entry out of range [0,A)");
         if (zero_row_ >= 0)
             FAIL(PBVI_EINVAL, "rollout: RTO[s,a,:,:] sums to 0 for s = " + std::to_string(zero_row_ / A_) + ", a = " +
@@ -2288,7 +2336,7 @@ class EngineT : public EngineBase {
         }
         if ((rc = ro_keep_.ensure((size_t)n0))) return rc;
         if ((rc = ro_dst_.ensure((size_t)(n0 + 1) * sizeof(int32_t)))) return rc;
-        if (uses_alpha && (rc = ro_aact_.ensure((size_t)V_ * sizeof(int32_t)))) return rc;
+        if (uses_alpha && (rc = ro_aact_.ensure((size_t)al_.V * sizeof(int32_t)))) return rc;
         if ((rc = ro_end_.ensure((size_t)S_))) return rc;
         if ((rc = bayes_ensure(n0, fixed_order))) return rc;
         if ((rc = build_inverse_lists())) return rc;
@@ -2304,7 +2352,7 @@ class EngineT : public EngineBase {
             HIPCHK(hipMemcpyAsync(tr_steps, full.data(), (size_t)n0 * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
             HIPCHK(hipMemcpyAsync(ro_state_[0].p, call.start_states, (size_t)n0 * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
             HIPCHK(hipMemcpyAsync(ro_orig_[0].p, iota.data(), (size_t)n0 * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-            if (uses_alpha) HIPCHK(hipMemcpyAsync(ro_aact_.p, call.alpha_actions, (size_t)V_ * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+            if (uses_alpha) HIPCHK(hipMemcpyAsync(ro_aact_.p, call.alpha_actions, (size_t)al_.V * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
             HIPCHK(hipMemcpyAsync(ro_end_.p, call.end_mask, (size_t)S_, hipMemcpyHostToDevice, stream_));
             HIPCHK(hipStreamSynchronize(stream_));            // the caller's arrays and the two vectors are free again
         }
@@ -2322,7 +2370,7 @@ class EngineT : public EngineBase {
         // survivors' back up into [0].  Trajectory rows: the filter moves them from one ro_orig_ buffer to the other.
         RolloutStep rs{};
         rs.n0 = (int)n0;
-        rs.V = (int)V_;
+        rs.V = (int)al_.V;
         rs.seed = call.seed;
         rs.first_id = call.first_sim_id;
         rs.alpha_actions = source == ROLLOUT_VALUE_MAX ? ro_aact_.as<int32_t>() : nullptr;
@@ -2460,7 +2508,7 @@ class EngineT : public EngineBase {
     // argmax read (scores and magnitudes through its SlabView) and what it wrote (windows, first maxima, queue).
     int probe_capture(const SlabView<T>& sv, const ScoreIO& io, const ScoreStage<T>& out) {
         int rc;
-        const int64_t G = (int64_t)A_ * O_, pairs = blk_.B * G, n = pairs * V_;
+        const int64_t G = (int64_t)A_ * O_, pairs = blk_.B * G, n = pairs * al_.V;
         probe_seq_ = 0;                                      // (a stage that fails below leaves nothing to fetch)
         if (n > ((int64_t)1 << 24))
             FAIL(PBVI_EINVAL, "score probe: B * A * O * V = " + std::to_string(n) + " exceeds 2^24 (the probe is for tests)");
@@ -2472,7 +2520,7 @@ class EngineT : public EngineBase {
         if ((rc = probe_queue_.ensure((size_t)pairs * sizeof(int32_t)))) return rc;
         if ((rc = probe_dead_.ensure((size_t)pairs))) return rc;
         if ((rc = probe_words_.ensure(2 * sizeof(int)))) return rc;
-        HIPCHK(launch_score_probe<T>(sv, (int)V_, (int)G, (int)blk_.B, probe_score_.as<double>(), probe_mag_.as<double>(), stream_));
+        HIPCHK(launch_score_probe<T>(sv, (int)al_.V, (int)G, (int)blk_.B, probe_score_.as<double>(), probe_mag_.as<double>(), stream_));
         HIPCHK(hipMemcpyAsync(probe_err_.p, io.err, (size_t)pairs * sizeof(double), hipMemcpyDeviceToDevice, stream_));
         HIPCHK(hipMemcpyAsync(probe_bs_.p, io.best_score, (size_t)pairs * sizeof(double), hipMemcpyDeviceToDevice, stream_));
         HIPCHK(hipMemcpyAsync(probe_bv_.p, io.best_v, (size_t)pairs * sizeof(int32_t), hipMemcpyDeviceToDevice, stream_));
@@ -2488,7 +2536,7 @@ class EngineT : public EngineBase {
             HIPCHK(hipMemcpyAsync(probe_words_.as<int>() + 1, out.chain, sizeof(int), hipMemcpyDeviceToDevice, stream_));
         probe_info_.B = blk_.B;
         probe_info_.G = G;
-        probe_info_.V = V_;
+        probe_info_.V = al_.V;
         probe_info_.f64_pairs = out.f64_pairs;
         probe_info_.f64_split = f64_split_;
         probe_info_.push = sv.push;
@@ -2760,17 +2808,13 @@ class EngineT : public EngineBase {
         if (stream3_) (void)hipStreamSynchronize(stream3_);
         for (DevBuf* b : mem_.bufs)
             if (b->life == DevBuf::WORKING) b->release();
-        alpha_ = DevView{};                                  // (it pointed into alpha_buf_ / alpha_small_)
+        al_.emptied();                                       // (its view pointed into a working buffer)
         env_kind_ = ENV_NONE;                                // (its buffers were working buffers)
         env_F_ = env_C_ = 0;
         ub_count_ = ub_entries_ = 0;                         // (so were the point store's)
         ub_corner_ = false;
         sw_set_ = false;                                     // (the weights were a working buffer)
-        V_ = 0;
         block_emptied();
-        prim_valid_ = alpha_on_primary_ = false;
-        prim_ids_.clear();
-        prim_off_ = 0;
         store_rows_[0] = store_rows_[1] = 0;
         snz_rows_ = sbt_rows_ = 0;
         walk_rows_ = 0;
@@ -2780,10 +2824,9 @@ class EngineT : public EngineBase {
         last_deferred_nothing_ = false;
         have_last_work_ = false;                             // (its lists were working buffers)
         probe_seq_ = 0;                                      // (the capture's buffers were working buffers)
-        ++alpha_ver_;
         if (screen_) {
-            screen_alpha_seen_ = screen_bel_seen_ = 0;
-            screen_layout_seen_ = 0;
+            screen_alpha_seen_ = {};
+            screen_bel_seen_ = 0;
             return screen_->after_oom();
         }
         return PBVI_OK;
@@ -2793,10 +2836,7 @@ class EngineT : public EngineBase {
         if (which < 0 || which > 1) FAIL(PBVI_EINVAL, "store_reset: bad store");
         store_rows_[which] = 0;
         if (which == 1) snz_rows_ = sbt_rows_ = 0;
-        if (which == 0) {                                    // the ids of the primary working set name rows that are gone
-            prim_valid_ = false;
-            prim_ids_.clear();
-        }
+        if (which == 0) al_.primary_given_up();
         return PBVI_OK;
     }
 
@@ -2806,92 +2846,55 @@ class EngineT : public EngineBase {
         for (int64_t i = 0; i < n; ++i)
             if (ids[i] < 0 || ids[i] >= store_rows_[which]) FAIL(PBVI_EINVAL, "store_select: id out of range");
         HIPCHK(hipSetDevice(device_));
-        int rc = ids_.ensure((size_t)n * sizeof(int32_t));
+        const int rc = ids_.ensure((size_t)n * sizeof(int32_t));
         if (rc) return rc;
-        if (which == 1) {   // not synchronised below: the ids travel through a pinned buffer of the engine's own
-            const size_t bytes = (size_t)n * sizeof(int32_t);
-            if (ids_pin_.cap < bytes) {
-                HIPCHK(hipStreamSynchronize(stream_));
-                if (!ids_pin_.ensure(bytes, std::max<size_t>(bytes, 65536))) FAIL(PBVI_ENOMEM, "store_select: pinned staging for the ids");
-            } else if (ev_ids_) {
-                HIPCHK(hipEventSynchronize(ev_ids_));        // the previous selection's copy has left the buffer
-            }
-            std::memcpy(ids_pin_.p, ids, bytes);
-            HIPCHK(hipMemcpyAsync(ids_.p, ids_pin_.p, bytes, hipMemcpyHostToDevice, stream_));
-            HIPCHK(new_event(&ev_ids_, hipEventDisableTiming, "hipEventDestroy(ids)"));
-            HIPCHK(hipEventRecord(ev_ids_, stream_));
-        } else {
-            HIPCHK(hipMemcpyAsync(ids_.p, ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-        }
-        if (which == 0) {   // working alpha set := stored rows in the caller's order
-            static const bool no_prepend = getenv("PBVI_NO_ALPHA_PREPEND") != nullptr;      // debug / A-B only
-            auto gather = [&](T* dst, int64_t first, int64_t cnt) -> int {             // ids [first, first + cnt) -> dst rows
-                for (int64_t r0 = 0; r0 < cnt; r0 += 65535) {
-                    const unsigned c = (unsigned)std::min<int64_t>(65535, cnt - r0);
-                    hipLaunchKernelGGL(k_gather_rows<T>, dim3((S_pad_ + 255) / 256, c), dim3(256), 0, stream_, store_[0].as<T>(),
-                                       dst + (size_t)r0 * S_pad_, S_pad_, ids_.as<int32_t>() + first + r0);
-                    HIPCHK(hipGetLastError());
-                }
-                return PBVI_OK;
-            };
-            const int64_t pv = (int64_t)prim_ids_.size();
-            // (1) the primary set with k new rows in front of it (k = 0: the primary set again, after a small selection)
-            if (!no_prepend && prim_valid_ && n >= pv && n - pv <= prim_off_ &&
-                std::equal(prim_ids_.begin(), prim_ids_.end(), ids + (n - pv))) {
-                const int64_t k = n - pv;
-                prim_off_ -= k;
-                alpha_view(alpha_buf_, prim_off_);
-                V_ = n;                                           // the magnitude row stays where it is: row n of the new view
-                if (k > 0) {
-                    if ((rc = gather(alpha_.as<T>(), 0, k))) return rc;
-                    if ((rc = merge_magnitude_row(alpha_.as<T>(), k))) return rc;
-                    prim_ids_.insert(prim_ids_.begin(), ids, ids + k);
-                }
-                alpha_on_primary_ = true;
-                ++alpha_ver_;
-                HIPCHK(hipStreamSynchronize(stream_));
-                have_result_ = false;
-                return PBVI_OK;
-            }
-            // (2) a selection much smaller than the primary set: beside it
-            if (!no_prepend && prim_valid_ && n <= 4096 && 4 * n <= pv) {
-                const size_t rows = alpha_rows_cap(n);
-                if ((rc = alpha_small_.ensure(rows * S_pad_ * sizeof(T)))) return rc;
-                alpha_view(alpha_small_, 0);
-                alpha_on_primary_ = false;
-                HIPCHK(hipMemsetAsync(alpha_.as<T>() + (size_t)n * S_pad_, 0, (rows - (size_t)n) * S_pad_ * sizeof(T), stream_));
-                if ((rc = gather(alpha_.as<T>(), 0, n))) return rc;
-                V_ = n;
-                ++alpha_ver_;
-                if ((rc = refresh_magnitude_row())) return rc;
-                HIPCHK(hipStreamSynchronize(stream_));
-                have_result_ = false;
-                return PBVI_OK;
-            }
-            // (3) a new primary set: free rows in front (half its size again, for the sets that will extend it), the data,
-            // the magnitude row, and 256 + padding zero rows behind (the view's 256-row padding reaches further back as the
-            // view starts earlier)
-            const int64_t front = no_prepend ? 0 : std::max<int64_t>(512, n / 2);
-            const size_t rows = (size_t)front + alpha_rows_cap(n) + (no_prepend ? 0 : GEMM_BN);
-            if ((rc = alpha_buf_.ensure(rows * S_pad_ * sizeof(T)))) return rc;
-            prim_off_ = front;
-            alpha_view(alpha_buf_, prim_off_);
-            HIPCHK(hipMemsetAsync(alpha_.as<T>() + (size_t)n * S_pad_, 0, (rows - (size_t)front - (size_t)n) * S_pad_ * sizeof(T), stream_));
-            if ((rc = gather(alpha_.as<T>(), 0, n))) return rc;
-            V_ = n;
-            prim_ids_.assign(ids, ids + n);
-            prim_valid_ = !no_prepend;
-            alpha_on_primary_ = !no_prepend;
-            ++prim_layout_ver_;
-            ++alpha_ver_;
-            if ((rc = refresh_magnitude_row())) return rc;
+        return which == 0 ? select_alpha(ids, n) : select_beliefs(ids, n);
+    }
+
+    // Resident block := stored beliefs, gathered straight from the store rows in sorted order (no staging copy).  The ids travel
+    // through a pinned buffer of the engine's own, so nothing here waits for the device: the backup is enqueued behind it.
+    int select_beliefs(const int32_t* ids, int64_t n) {
+        const size_t bytes = (size_t)n * sizeof(int32_t);
+        if (ids_pin_.cap < bytes) {
             HIPCHK(hipStreamSynchronize(stream_));
-            have_result_ = false;
-            return PBVI_OK;
+            if (!ids_pin_.ensure(bytes, std::max<size_t>(bytes, 65536))) FAIL(PBVI_ENOMEM, "store_select: pinned staging for the ids");
+        } else if (ev_ids_) {
+            HIPCHK(hipEventSynchronize(ev_ids_));        // the previous selection's copy has left the buffer
         }
-        // the block is gathered straight from the store rows, in sorted order (no staging copy); nothing here waits for the
-        // device: the backup that follows is enqueued behind it
+        std::memcpy(ids_pin_.p, ids, bytes);
+        HIPCHK(hipMemcpyAsync(ids_.p, ids_pin_.p, bytes, hipMemcpyHostToDevice, stream_));
+        HIPCHK(new_event(&ev_ids_, hipEventDisableTiming, "hipEventDestroy(ids)"));
+        HIPCHK(hipEventRecord(ev_ids_, stream_));
         return beliefs_finish(n, store_[1].as<T>(), ids_.as<int32_t>());
+    }
+
+    // Working alpha set := stored rows in the caller's order, laid out as AlphaSet::selection says.  EXTEND: the new rows go
+    // into the free rows in front of the primary set; the magnitude row stays where it is, row n of the new view.  SMALL: into
+    // al_.small.  FRESH: free rows in front, the data, the magnitude row, and 256 + padding zero rows behind (the view's
+    // 256-row padding reaches further back as the view starts earlier).
+    int select_alpha(const int32_t* ids, int64_t n) {
+        static const bool no_prepend = getenv("PBVI_NO_ALPHA_PREPEND") != nullptr;      // debug / A-B only
+        HIPCHK(hipMemcpyAsync(ids_.p, ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+        const auto sel = al_.selection(ids, n, !no_prepend);
+        if (sel.kind == sel.EXTEND) {
+            al_.placed(al_.PRIMARY, al_.off - sel.rows, n);
+        } else {
+            const bool small = sel.kind == sel.SMALL;
+            const size_t rows = (size_t)sel.rows + al_.rows_cap(n) + (small || no_prepend ? 0 : GEMM_BN);
+            const int rc = (small ? al_.small : al_.buf).ensure(rows * al_.row_bytes());
+            if (rc) return rc;
+            al_.placed(small ? al_.BESIDE : no_prepend ? al_.PLAIN : al_.PRIMARY, sel.rows, n);
+            HIPCHK(hipMemsetAsync(al_.mag_row(), 0, (rows - (size_t)sel.rows - (size_t)n) * al_.row_bytes(), stream_));
+        }
+        const int64_t fresh = sel.kind == sel.EXTEND ? sel.rows : n;       // rows to gather: they lead the view
+        for (int64_t r0 = 0; r0 < fresh; r0 += 65535) {
+            const unsigned c = (unsigned)std::min<int64_t>(65535, fresh - r0);
+            hipLaunchKernelGGL(k_gather_rows<T>, dim3((S_pad_ + 255) / 256, c), dim3(256), 0, stream_, store_[0].as<T>(),
+                               al_.rows() + (size_t)r0 * S_pad_, S_pad_, ids_.as<int32_t>() + r0);
+            HIPCHK(hipGetLastError());
+        }
+        al_.selected(sel, ids, n);
+        return sel.kind == sel.EXTEND ? alpha_installed(al_.rows(), fresh) : alpha_installed();
     }
 
     // device pointer to the stream-K share size (K-tile steps of the longest f32 chain) or nullptr
@@ -2965,7 +2968,7 @@ class EngineT : public EngineBase {
     template <typename TS>
     int run_pipeline(EngineT<TS>& scorer, double gamma, int flags, pbvi_stats_t* st, Mode mode) {
         int rc;
-        const int64_t N = (int64_t)A_ * O_ * (V_ + 1) + 2 * A_;   // per (a, o): alpha rows + magnitude row
+        const int64_t N = (int64_t)A_ * O_ * (al_.V + 1) + 2 * A_;   // per (a, o): alpha rows + magnitude row
         const int64_t pairs = blk_.B * A_ * O_;
         if (N > 0x7fffffff || pairs > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "backup_run: A*O*(V+1) or B*A*O exceeds int32");
         Call<TS> c{scorer, gamma, flags, pairs, scorer.choose_push(N), st != nullptr, mode != MODE_BACKUP, mode == MODE_Q_BEST};
@@ -3089,7 +3092,7 @@ class EngineT : public EngineBase {
         io.allow_split = !c.screened;
         if (c.windows && !c.use_push && c.scorer.tiling_mode_ != 0) {   // Gamma tiling plans with what is free: the refinement's work
             RefineWork reserve;                                       // lists (the largest buffers of the later stages) come first
-            if ((rc = refine_work(c.pairs, V_, &reserve))) return rc;
+            if ((rc = refine_work(c.pairs, al_.V, &reserve))) return rc;
         }
         if ((rc = c.scorer.stage_scores(c.gamma, c.use_push, io, &c.sc))) return rc;
         // List lengths of this GEMM, for the statistics (K5 rebuilds the lists for its own GEMM later): into PAGE-LOCKED memory.
@@ -3120,7 +3123,7 @@ class EngineT : public EngineBase {
             HIPCHK(hipStreamWaitEvent(xs, ev_xr_[0], 0));
         }
         hipLaunchKernelGGL(k_extra_rowmax<TS>, dim3((unsigned)((blk_.B + 3) / 4)), dim3(256), 0, xs, c.sc.sv, c.sc.extra_row0, (int)blk_.B,
-                           (int)V_, blk_.sorted ? blk_.perm.as<int32_t>() : nullptr, vmax_bk_.as<double>());
+                           (int)al_.V, blk_.sorted ? blk_.perm.as<int32_t>() : nullptr, vmax_bk_.as<double>());
         HIPCHK(hipGetLastError());
         if (xs != stream_) {
             HIPCHK(hipEventRecord(ev_xr_[1], xs));
@@ -3150,7 +3153,7 @@ class EngineT : public EngineBase {
         HIPCHK(launch_dedup((int)blk_.B, A_, O_, d.res_act, d.res_best, d.rep.as<int32_t>(), d.uniq.as<int32_t>(), d.inv.as<int32_t>(),
                             d.slot.as<int32_t>(), d.count(), stream_));
         // K3: alpha' rows of the unique keys only
-        HIPCHK(launch_assemble<T>(alpha_.as<T>(), S_pad_, view(), gamma, d.res_act, d.res_best, d.uniq.as<int32_t>(), d.count(), (int)blk_.B,
+        HIPCHK(launch_assemble<T>(al_.rows(), S_pad_, view(), gamma, d.res_act, d.res_best, d.uniq.as<int32_t>(), d.count(), (int)blk_.B,
                                   d.rows.as<T>(), S_, stream_));
         return PBVI_OK;
     }
@@ -3194,7 +3197,7 @@ class EngineT : public EngineBase {
 
     // the grid-wide passes over what the per-entry pass deferred (rf_counts_, read by the host)
     int refine_deferred(double gamma, const RefineWork& work) {
-        HIPCHK(launch_refine_deferred<T>(true, (int)V_, A_ * O_, blk_.rows.as<T>(), S_pad_, alpha_.as<T>(), S_pad_, view(), gamma,
+        HIPCHK(launch_refine_deferred<T>(true, (int)al_.V, A_ * O_, blk_.rows.as<T>(), S_pad_, al_.rows(), S_pad_, view(), gamma,
                                          best_v_.as<int32_t>(), best_score_.as<double>(), err_.as<double>(), work,
                                          rf_counts_[0], rf_counts_[1], stream_));
         return PBVI_OK;
@@ -3211,7 +3214,7 @@ class EngineT : public EngineBase {
         if (!c.windows) return PBVI_OK;
         int rc;
         RefineWork& work = c.work;
-        if ((rc = refine_work(c.pairs, V_, &work))) return rc;   // (reserved by `score` already in a tiled call)
+        if ((rc = refine_work(c.pairs, al_.V, &work))) return rc;   // (reserved by `score` already in a tiled call)
         if constexpr (kF32 && !Call<TS>::screened) {
             // Gamma is in HBM as the GEMM read it (projection kernel, not the fused GEMM): the per-entry pass first
             // separates candidates by fp64 sums over those fp32 rows (backup_kernels.h, RefineWork::gam)
@@ -3240,8 +3243,8 @@ class EngineT : public EngineBase {
         // deferred entries of this one have to be finished first)
         // (nor for pbvi_q_values, whose one stage behind the refinement needs the final best_v)
         c.speculate = !no_spec && !c.q_only && last_deferred_nothing_ && work.items_v != nullptr && !(c.flags & PBVI_BELIEF_DOMINANCE);
-        HIPCHK((launch_refine_scan<T, TS>(true, c.sc.sv, (int)V_, A_ * O_, (int)c.pairs, queue_.as<int32_t>(), c.io.qcount, blk_.rows.as<T>(), S_pad_,
-                                          alpha_.as<T>(), S_pad_, view(), c.gamma, blk_.btl.as<int32_t>(), blk_.btc.as<int32_t>(),
+        HIPCHK((launch_refine_scan<T, TS>(true, c.sc.sv, (int)al_.V, A_ * O_, (int)c.pairs, queue_.as<int32_t>(), c.io.qcount, blk_.rows.as<T>(), S_pad_,
+                                          al_.rows(), S_pad_, view(), c.gamma, blk_.btl.as<int32_t>(), blk_.btc.as<int32_t>(),
                                           nzB_.as<uint8_t>(), best_v_.as<int32_t>(), best_score_.as<double>(), err_.as<double>(),
                                           counters_.as<int>() + CNT_REFINE_CAND, work, rf_counts_, stream_)));
         if (!c.speculate && work.items_v != nullptr) {
@@ -3309,7 +3312,7 @@ class EngineT : public EngineBase {
         if ((rc = q_res_.ensure((size_t)blk_.B * A_ * sizeof(double)))) return rc;
         if ((rc = q_act_.ensure((size_t)blk_.B * sizeof(int32_t)))) return rc;
         if (c.q_best && (rc = fin_.best_res.ensure((size_t)c.pairs * sizeof(int32_t)))) return rc;
-        HIPCHK(launch_q_exact<T>(blk_.rows.as<T>(), S_pad_, (int)blk_.B, alpha_.as<T>(), S_pad_, (int)V_, view(), c.gamma, blk_.btl.as<int32_t>(),
+        HIPCHK(launch_q_exact<T>(blk_.rows.as<T>(), S_pad_, (int)blk_.B, al_.rows(), S_pad_, (int)al_.V, view(), c.gamma, blk_.btl.as<int32_t>(),
                                  blk_.btc.as<int32_t>(), best_v_.as<int32_t>(), c.windows ? dead_.as<uint8_t>() : nullptr,
                                  blk_.sorted ? blk_.perm.as<int32_t>() : nullptr, q_.as<double>(), q_res_.as<double>(), q_act_.as<int32_t>(),
                                  c.q_best ? fin_.best_res.as<int32_t>() : nullptr, stream_));
@@ -3334,7 +3337,7 @@ class EngineT : public EngineBase {
                                  c.windows ? aqueue_.as<int32_t>() : nullptr, aqcount, stream_, c.io.tol_extra,
                                  c.windows ? acand_.as<uint8_t>() : nullptr, sc.split));
         if (c.windows)
-            HIPCHK(launch_refine_action<T>(blk_.rows.as<T>(), S_pad_, (int)blk_.B, alpha_.as<T>(), S_pad_, view(), c.gamma,
+            HIPCHK(launch_refine_action<T>(blk_.rows.as<T>(), S_pad_, (int)blk_.B, al_.rows(), S_pad_, view(), c.gamma,
                                            blk_.btl.as<int32_t>(), blk_.btc.as<int32_t>(), aqueue_.as<int32_t>(), aqcount, rdot_.as<double>(), rdot_err, best_v_.as<int32_t>(),
                                            best_score_.as<double>(), err_.as<double>(), val_exact_.as<double>(),
                                            fin_.act.as<int32_t>(), stream_, acand_.as<uint8_t>()));
@@ -3402,7 +3405,7 @@ class EngineT : public EngineBase {
     template <typename TS>
     void fill_stats(const Call<TS>& c, pbvi_stats_t* st) const {
         const int AO = A_ * O_;
-        const int64_t N = (int64_t)AO * (V_ + 1) + 2 * A_;
+        const int64_t N = (int64_t)AO * (al_.V + 1) + 2 * A_;
         const ScoreStage<TS>& sc = c.sc;
         const GemmPlan& plan = sc.plan;
         std::memset(st, 0, sizeof(*st));
@@ -3433,7 +3436,7 @@ class EngineT : public EngineBase {
                 (void)hipEventElapsedTime(&t, ev_pg_[0], ev_pg_[1]);
                 st->ms_project_gemm = (double)t;
             }
-            st->project_flops = 2LL * AO * V_ * (int64_t)S_ * S_;
+            st->project_flops = 2LL * AO * al_.V * (int64_t)S_ * S_;
             st->project_flops_executed = st->project_flops;
             if (kF32) {
                 int64_t kt_sum = 0;
@@ -3441,7 +3444,7 @@ class EngineT : public EngineBase {
                 st->project_flops_executed = kt_sum * 2LL * GEMM_BM * GEMM_BN * GEMM_BK;
             }
         }
-        st->score_flops = 2 * blk_.B * (int64_t)S_ * AO * V_;
+        st->score_flops = 2 * blk_.B * (int64_t)S_ * AO * al_.V;
         int64_t kt_sum = 0;                                  // the GEMM's list lengths (none where it kept no lists)
         for (size_t i = 0; i < c.n_kcount; ++i) kt_sum += c.h_kcount[i];
         if (c.windows) {
@@ -3450,7 +3453,7 @@ class EngineT : public EngineBase {
             st->score_tiles_run = kt_sum;
             st->split_k = plan.max_chunks;
         } else if (sc.f64_pairs > 0) {   // fp64 MFMA path: 128 x 128 tiles, lists in 32-column steps
-            st->score_flops_executed = kt_sum * 2LL * 128 * gemm_f64_bn((int)std::min<int64_t>(c.use_push ? V_ : N, 0x7fffffff)) * 32;
+            st->score_flops_executed = kt_sum * 2LL * 128 * gemm_f64_bn((int)std::min<int64_t>(c.use_push ? al_.V : N, 0x7fffffff)) * 32;
             st->score_tiles_dense = sc.f64_pairs * (S_pad_ / GEMM_BK);
             st->score_tiles_run = kt_sum;
             st->split_k = 1;
@@ -3624,7 +3627,7 @@ class EngineT : public EngineBase {
         int* bad = keys_act_.as<int>() + n;
         HIPCHK(hipMemcpyAsync(keys_tmp_.p, keys, (size_t)n * (1 + O_) * sizeof(int32_t), hipMemcpyDefault, stream_));
         HIPCHK(hipMemsetAsync(bad, 0, sizeof(int), stream_));
-        hipLaunchKernelGGL(k_scatter_keys, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream_, (int)n, A_, O_, (int)V_,
+        hipLaunchKernelGGL(k_scatter_keys, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream_, (int)n, A_, O_, (int)al_.V,
                            keys_tmp_.as<int32_t>(), keys_act_.as<int32_t>(), keys_best_.as<int32_t>(), bad);
         HIPCHK(hipGetLastError());
         return PBVI_OK;
@@ -3644,13 +3647,13 @@ class EngineT : public EngineBase {
     // alpha' rows from keys against the RESIDENT alpha set (K3 of src/pomdp.py:1497-1506 for given winners): what a
     // rank needs to rebuild the rows other ranks found, since the alpha set and the model are replicated.
     int assemble_keys(double gamma, int64_t n, const int32_t* keys, void* out_rows) override {
-        if (V_ <= 0) FAIL(PBVI_EINVAL, "assemble_keys: no alpha set resident");
+        if (al_.V <= 0) FAIL(PBVI_EINVAL, "assemble_keys: no alpha set resident");
         if (n <= 0 || n > 65535 || !keys || !out_rows) FAIL(PBVI_EINVAL, "assemble_keys: bad arguments (1 <= n <= 65535)");
         T* rows = nullptr;
         int ld = 0;
         int rc = keys_to_decisions(n, keys, false, &rows, &ld);
         if (rc) return rc;
-        HIPCHK(launch_assemble<T>(alpha_.as<T>(), S_pad_, view(), gamma, keys_act_.as<int32_t>(), keys_best_.as<int32_t>(), nullptr,
+        HIPCHK(launch_assemble<T>(al_.rows(), S_pad_, view(), gamma, keys_act_.as<int32_t>(), keys_best_.as<int32_t>(), nullptr,
                                   nullptr, (int)n, rows, ld, stream_));
         return deliver_assembled("assemble_keys", n, rows, ld, out_rows, true);
     }
@@ -3658,14 +3661,14 @@ class EngineT : public EngineBase {
     // Same, and the rows also join the alpha store (ids consecutive from the return value): the sharded backup's
     // "every replica appends the same rows" step, device to device.  out_rows may be NULL.
     int64_t assemble_keys_store(double gamma, int64_t n, const int32_t* keys, void* out_rows) override {
-        if (V_ <= 0) FAIL(PBVI_EINVAL, "assemble_rows_store: no alpha set resident");
+        if (al_.V <= 0) FAIL(PBVI_EINVAL, "assemble_rows_store: no alpha set resident");
         if (n <= 0 || n > 65535 || !keys) FAIL(PBVI_EINVAL, "assemble_rows_store: bad arguments (1 <= n <= 65535)");
         T* dst = nullptr;
         int ld = 0;
         int rc = keys_to_decisions(n, keys, true, &dst, &ld);
         if (rc) return rc;
         if (S_pad_ > S_) HIPCHK(hipMemsetAsync(dst, 0, (size_t)n * S_pad_ * sizeof(T), stream_));   // pad columns stay zero
-        HIPCHK(launch_assemble<T>(alpha_.as<T>(), S_pad_, view(), gamma, keys_act_.as<int32_t>(), keys_best_.as<int32_t>(), nullptr,
+        HIPCHK(launch_assemble<T>(al_.rows(), S_pad_, view(), gamma, keys_act_.as<int32_t>(), keys_best_.as<int32_t>(), nullptr,
                                   nullptr, (int)n, dst, ld, stream_));
         if ((rc = deliver_assembled("assemble_rows_store", n, dst, ld, out_rows, false))) return rc;
         return store_commit(0, n);
@@ -3685,23 +3688,23 @@ class EngineT : public EngineBase {
     }
 
     int prune_dominated(uint8_t* keep) override {
-        if (V_ <= 0) FAIL(PBVI_EINVAL, "prune_dominated: no alpha set resident");
+        if (al_.V <= 0) FAIL(PBVI_EINVAL, "prune_dominated: no alpha set resident");
         if (!keep) FAIL(PBVI_EINVAL, "prune_dominated: keep is NULL");
-        if (V_ > 4 * 65535) FAIL(PBVI_EUNSUPPORTED, "prune_dominated: at most 262140 alpha-vectors");   // grid.y = ceil(V / 4)
+        if (al_.V > 4 * 65535) FAIL(PBVI_EUNSUPPORTED, "prune_dominated: at most 262140 alpha-vectors");   // grid.y = ceil(V / 4)
         HIPCHK(hipSetDevice(device_));
-        int rc = prune_cnt_.ensure((size_t)V_ * sizeof(int));
+        int rc = prune_cnt_.ensure((size_t)al_.V * sizeof(int));
         if (rc) return rc;
         int* h_cnt = nullptr;
-        if ((rc = out_.raw((size_t)V_ * sizeof(int), &h_cnt))) return rc;
-        HIPCHK(hipMemsetAsync(prune_cnt_.p, 0, (size_t)V_ * sizeof(int), stream_));
-        HIPCHK(launch_dominated<T>(alpha_.as<T>(), S_pad_, (int)V_, S_, prune_cnt_.as<int>(), stream_));
+        if ((rc = out_.raw((size_t)al_.V * sizeof(int), &h_cnt))) return rc;
+        HIPCHK(hipMemsetAsync(prune_cnt_.p, 0, (size_t)al_.V * sizeof(int), stream_));
+        HIPCHK(launch_dominated<T>(al_.rows(), S_pad_, (int)al_.V, S_, prune_cnt_.as<int>(), stream_));
         return keep_from_counts(prune_cnt_.as<int>(), h_cnt, keep);
     }
-    // Both prunes end here: the V_ domination counts into pinned memory, and a row is kept iff it was dominated once (by itself)
+    // Both prunes end here: the V domination counts into pinned memory, and a row is kept iff it was dominated once (by itself)
     int keep_from_counts(const int* d_cnt, int* h_cnt, uint8_t* keep) {
-        HIPCHK(hipMemcpyAsync(h_cnt, d_cnt, (size_t)V_ * sizeof(int), hipMemcpyDeviceToHost, stream_));
+        HIPCHK(hipMemcpyAsync(h_cnt, d_cnt, (size_t)al_.V * sizeof(int), hipMemcpyDeviceToHost, stream_));
         HIPCHK(hipStreamSynchronize(stream_));
-        for (int64_t i = 0; i < V_; ++i) keep[i] = (h_cnt[i] == 1) ? 1 : 0;
+        for (int64_t i = 0; i < al_.V; ++i) keep[i] = (h_cnt[i] == 1) ? 1 : 0;
         return PBVI_OK;
     }
 
@@ -3710,11 +3713,11 @@ class EngineT : public EngineBase {
     // start counts (1 for an old row, which never meets itself; 0 for a new one, which does, once) are built here and
     // travel through the pinned staging buffer in one copy; the counts come back into the same buffer.
     int prune_dominated_masked(const uint8_t* is_new, uint8_t* keep) override {
-        if (V_ <= 0) FAIL(PBVI_EINVAL, "prune_dominated_masked: no alpha set resident");
+        if (al_.V <= 0) FAIL(PBVI_EINVAL, "prune_dominated_masked: no alpha set resident");
         if (!is_new) FAIL(PBVI_EINVAL, "prune_dominated_masked: is_new is NULL");
         if (!keep) FAIL(PBVI_EINVAL, "prune_dominated_masked: keep is NULL");
-        if (V_ > 4 * 65535) FAIL(PBVI_EUNSUPPORTED, "prune_dominated_masked: at most 262140 alpha-vectors");   // as prune_dominated
-        const int V = (int)V_;
+        if (al_.V > 4 * 65535) FAIL(PBVI_EUNSUPPORTED, "prune_dominated_masked: at most 262140 alpha-vectors");   // as prune_dominated
+        const int V = (int)al_.V;
         int n_new = 0;
         for (int i = 0; i < V; ++i) n_new += is_new[i] ? 1 : 0;
         if (n_new == 0) {                                    // no pair to test: nothing is launched
@@ -3737,7 +3740,7 @@ class EngineT : public EngineBase {
         HIPCHK(hipMemcpyAsync(d_cnt, h_cnt, (size_t)2 * V * sizeof(int), hipMemcpyHostToDevice, stream_));
         int piece = 65535;
         if (const char* c = getenv("PBVI_PRUNE_PIECE")) piece = (int)std::min<int64_t>(65535, std::max<int64_t>(1, atoll(c)));   // tests
-        HIPCHK(launch_dominated_masked<T>(alpha_.as<T>(), S_pad_, S_, d_cnt + V, n_old, n_new, d_cnt, piece, stream_));
+        HIPCHK(launch_dominated_masked<T>(al_.rows(), S_pad_, S_, d_cnt + V, n_old, n_new, d_cnt, piece, stream_));
         return keep_from_counts(d_cnt, h_out, keep);
     }
 
@@ -3758,13 +3761,13 @@ class EngineT : public EngineBase {
         vmax_route_[1] = bn;
         vmax_route_[2] = k_parts;
         vmax_route_[3] = rows;
-        vmax_route_[4] = V_;
+        vmax_route_[4] = al_.V;
         vmax_route_[5] = pairs;
         vmax_route_[6] += 1;
     }
 
     int value_max(double* out_value, int32_t* out_index) override {
-        if (V_ <= 0 || blk_.B <= 0) FAIL(PBVI_EINVAL, "value_max: need a resident alpha set and belief block");
+        if (al_.V <= 0 || blk_.B <= 0) FAIL(PBVI_EINVAL, "value_max: need a resident alpha set and belief block");
         HIPCHK(hipSetDevice(device_));
         int rc = value_max_device(resident());
         if (rc) return rc;
@@ -3780,7 +3783,7 @@ class EngineT : public EngineBase {
     // the other stage buffers are overwritten, so an earlier backup's results are no longer fetchable afterwards.
     int q_values(double gamma, double* out_q, int32_t* out_action, int32_t* out_best) override {
         if (!out_q) FAIL(PBVI_EINVAL, "q_values: NULL out_q");
-        if (V_ <= 0) FAIL(PBVI_EINVAL, "q_values: no alpha set resident (call pbvi_alpha_set)");
+        if (al_.V <= 0) FAIL(PBVI_EINVAL, "q_values: no alpha set resident (call pbvi_alpha_set)");
         if (blk_.B <= 0) FAIL(PBVI_EINVAL, "q_values: no belief block resident (call pbvi_beliefs_set)");
         if (mode_ != PBVI_SPARSE) FAIL(PBVI_EUNSUPPORTED, "q_values: not available on a PBVI_DENSE engine (create it with PBVI_SPARSE)");
         int rc = run_q(gamma, out_best != nullptr);
@@ -3815,7 +3818,7 @@ class EngineT : public EngineBase {
     // grows, and its rows already sit in the store in arrival order (a walk's successive beliefs overlap heavily, so
     // 256-row blocks of the store have tight joint support without sorting).
     int value_max_store(int64_t n, double* out_value, int32_t* out_index) override {
-        if (V_ <= 0) FAIL(PBVI_EINVAL, "value_max_store: no alpha set resident");
+        if (al_.V <= 0) FAIL(PBVI_EINVAL, "value_max_store: no alpha set resident");
         if (n <= 0 || n > store_rows_[1] || (!out_value && !out_index)) FAIL(PBVI_EINVAL, "value_max_store: bad arguments");
         HIPCHK(hipSetDevice(device_));
         int rc;
@@ -3958,7 +3961,7 @@ class EngineT : public EngineBase {
     // fp32 engines: value-max GEMMs against at most 64 alpha rows take the skinny fp64-accumulating tile (value_max_device)
     bool vmax_skinny() const {
         static const bool off = getenv("PBVI_NO_SKINNY") != nullptr;      // debug / A-B only
-        return kF32 && !off && V_ > 0 && V_ <= 64 && mode_ == PBVI_SPARSE;
+        return kF32 && !off && al_.V > 0 && al_.V <= 64 && mode_ == PBVI_SPARSE;
     }
     // automatic score split: from this many dense 256x256x32 tile-steps of the padded score GEMM (C4: 274k)
     static constexpr int64_t kSplitMinSteps = 16384;
@@ -4019,9 +4022,9 @@ class EngineT : public EngineBase {
         return PBVI_OK;
     }
     int alpha_layout(int64_t* free_rows, int64_t* layouts) override {
-        if (free_rows) *free_rows = alpha_on_primary_ ? prim_off_ : 0;
-        if (layouts) *layouts = (int64_t)prim_layout_ver_;
-        return alpha_on_primary_ ? 1 : 0;
+        if (free_rows) *free_rows = al_.on_primary() ? al_.off : 0;
+        if (layouts) *layouts = (int64_t)al_.layout_ver;
+        return al_.on_primary() ? 1 : 0;
     }
 
     int set_tie_window(double rel) override {
@@ -4145,7 +4148,7 @@ template <typename T>
 int EngineT<T>::project_dense(double gamma) {
     int rc;
     const int AO = A_ * O_;
-    const int64_t Vt = V_, Vt_pad = round_up(Vt, GEMM_BM);   // the magnitude row is projected separately below
+    const int64_t Vt = al_.V, Vt_pad = round_up(Vt, GEMM_BM);   // the magnitude row is projected separately below
     int64_t ld_prod, batch_stride;
     if constexpr (kF32) {
         const int64_t n_pad = rows_pad_s_;
@@ -4160,9 +4163,9 @@ int EngineT<T>::project_dense(double gamma) {
         if ((rc = nchunksD_.ensure((size_t)AO * pairs * sizeof(int)))) return rc;
         dense_pairs_ = (int64_t)AO * pairs;
         HIPCHK(hipMemsetAsync(prod_.p, 0, (size_t)AO * batch_stride * sizeof(float), stream_));   // pairs with empty lists
-        HIPCHK(launch_tile_nonzero_f32((const float*)alpha_.p, S_pad_, (int)Vt_pad, pl.k_tiles, nzAlpha_.as<uint8_t>(), stream_));
+        HIPCHK(launch_tile_nonzero_f32((const float*)al_.view.p, S_pad_, (int)Vt_pad, pl.k_tiles, nzAlpha_.as<uint8_t>(), stream_));
         BatchedGemmArgs g;
-        g.A = (const float*)alpha_.p;
+        g.A = (const float*)al_.view.p;
         g.B = (const float*)dense_.p;
         g.lda = g.ldb = S_pad_;
         g.C = prod_.as<float>();
@@ -4185,15 +4188,15 @@ int EngineT<T>::project_dense(double gamma) {
         batch_stride = Vt * S_;
         if ((rc = prod_.ensure((size_t)AO * batch_stride * sizeof(T)))) return rc;
         for (int ao = 0; ao < AO; ++ao)
-            HIPCHK(launch_gemm_nt_simple<T>(alpha_.as<T>(), S_pad_, dense_.as<T>() + (size_t)ao * rows_pad_s_ * S_pad_, S_pad_,
+            HIPCHK(launch_gemm_nt_simple<T>(al_.rows(), S_pad_, dense_.as<T>() + (size_t)ao * rows_pad_s_ * S_pad_, S_pad_,
                                             prod_.as<T>() + (size_t)ao * batch_stride, (int)ld_prod, (int)Vt, S_, S_, stream_));
     }
     dim3 grid((S_ + 255) / 256, (unsigned)Vt, AO);
-    hipLaunchKernelGGL(k_scale_rows<T>, grid, dim3(256), 0, stream_, prod_.as<T>(), batch_stride, (int)ld_prod, (int)V_,
+    hipLaunchKernelGGL(k_scale_rows<T>, grid, dim3(256), 0, stream_, prod_.as<T>(), batch_stride, (int)ld_prod, (int)al_.V,
                        (T)gamma, gam_.as<T>(), S_pad_, S_);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_project_mag<T>, dim3((S_pad_ + 255) / 256, AO), dim3(256), 0, stream_,
-                       alpha_.as<T>() + (size_t)V_ * S_pad_, view(), (T)gamma, gam_.as<T>() + (size_t)AO * V_ * S_pad_, S_pad_);
+                       al_.mag_row(), view(), (T)gamma, gam_.as<T>() + (size_t)AO * al_.V * S_pad_, S_pad_);
     HIPCHK(hipGetLastError());
     return PBVI_OK;
 }
@@ -4202,7 +4205,7 @@ template <typename T>
 int EngineT<T>::value_max_device(const Operand& x) {
     int rc;
     const int64_t B = x.B;
-    const int64_t Vt = V_ + 1;   // + magnitude row
+    const int64_t Vt = al_.V + 1;   // + magnitude row
     if ((rc = bv2_.ensure((size_t)B * sizeof(int32_t)))) return rc;
     if ((rc = bs2_.ensure((size_t)B * sizeof(double)))) return rc;
     if ((rc = err2_.ensure((size_t)B * sizeof(double)))) return rc;
@@ -4217,38 +4220,38 @@ int EngineT<T>::value_max_device(const Operand& x) {
             // the belief block once instead -- and its scores are exact products summed in fp64, so there is no tie window
             // and nothing to re-score.
             const int kt32 = S_pad_ / GEMM_BK;
-            const int split = gemm_f64_split((int)B, (int)V_, kt32);
-            const int64_t slab = B * V_;
+            const int split = gemm_f64_split((int)B, (int)al_.V, kt32);
+            const int64_t slab = B * al_.V;
             if ((rc = slabs_.ensure((size_t)split * slab * sizeof(double)))) return rc;
-            if ((rc = klist_.ensure(gemm_f64_klist_ints((int)B, (int)V_, kt32) * sizeof(int)))) return rc;
-            if ((rc = kcount_.ensure(gemm_f64_kcount_ints((int)B, (int)V_, kt32) * sizeof(int)))) return rc;
-            HIPCHK(launch_gemm_nt_f64_ff32((const float*)x.rows, S_pad_, (int)B, (const float*)alpha_.p, S_pad_, (int)V_,
-                                           slabs_.as<double>(), (int)V_, S_pad_, x.nzA, klist_.as<int>(),
+            if ((rc = klist_.ensure(gemm_f64_klist_ints((int)B, (int)al_.V, kt32) * sizeof(int)))) return rc;
+            if ((rc = kcount_.ensure(gemm_f64_kcount_ints((int)B, (int)al_.V, kt32) * sizeof(int)))) return rc;
+            HIPCHK(launch_gemm_nt_f64_ff32((const float*)x.rows, S_pad_, (int)B, (const float*)al_.view.p, S_pad_, (int)al_.V,
+                                           slabs_.as<double>(), (int)al_.V, S_pad_, x.nzA, klist_.as<int>(),
                                            kcount_.as<int>(), stream_, split, slab));
-            const SlabView<double> svd = SlabView<double>::single(slabs_.as<double>(), (int)V_);   // K parts folded into the first slab by the launcher
-            HIPCHK(launch_argmax<double>(svd, (int)V_, 1, (int)B, nullptr, 0.0, 0.0, nullptr, 0, bv2_.as<int32_t>(),
+            const SlabView<double> svd = SlabView<double>::single(slabs_.as<double>(), (int)al_.V);   // K parts folded into the first slab by the launcher
+            HIPCHK(launch_argmax<double>(svd, (int)al_.V, 1, (int)B, nullptr, 0.0, 0.0, nullptr, 0, bv2_.as<int32_t>(),
                                          bs2_.as<double>(), err2_.as<double>(), nullptr, qc, stream_));
-            note_vmax_route(1, gemm_f64_bn((int)V_), split, B, (int64_t)gemm_f64_pairs((int)B, (int)V_));
+            note_vmax_route(1, gemm_f64_bn((int)al_.V), split, B, (int64_t)gemm_f64_pairs((int)B, (int)al_.V));
             return PBVI_OK;
         }
     }
     SlabView<T> sv;
-    if ((rc = score_gemm(alpha_.as<T>(), Vt, nullptr, 1, (int)V_, &sv, x.rows, B, x.nzA))) return rc;
+    if ((rc = score_gemm(al_.rows(), Vt, nullptr, 1, (int)al_.V, &sv, x.rows, B, x.nzA))) return rc;
     const int k_chunk = kF32 ? plan_.chunk_len * GEMM_BK : S_pad_;
     // every belief is re-scored exactly in f32 engines (flag_all): the comparison that
     // follows (new value > old best value) is strict and must not see GEMM rounding
     const bool rescore = kF32 && vmax_exact_;
-    HIPCHK(launch_argmax<T>(sv, (int)V_, 1, (int)B, nullptr, tie_window(k_chunk), 0.0, chain_steps(), 1, bv2_.as<int32_t>(),
+    HIPCHK(launch_argmax<T>(sv, (int)al_.V, 1, (int)B, nullptr, tie_window(k_chunk), 0.0, chain_steps(), 1, bv2_.as<int32_t>(),
                             bs2_.as<double>(), err2_.as<double>(), rescore ? queue2_.as<int32_t>() : nullptr, qc, stream_));
     if (rescore) {
         if (x.btl == nullptr && (rc = ensure_belief_tiles())) return rc;   // (the backup's k_dead builds them too)
         const int32_t *btl = x.btl ? x.btl : blk_.btl.as<int32_t>(), *btc = x.btl ? x.btc : blk_.btc.as<int32_t>();
         RefineWork work;
-        if ((rc = refine_work(B, V_, &work))) return rc;
+        if ((rc = refine_work(B, al_.V, &work))) return rc;
         last_work_ = work;                                       // (pbvi_debug_refine_counts)
         have_last_work_ = true;
-        HIPCHK(launch_refine<T>(false, sv, (int)V_, 1, (int)B, queue2_.as<int32_t>(), qc, x.rows, S_pad_,
-                                alpha_.as<T>(), S_pad_, view(), 0.0, btl, btc, nullptr,
+        HIPCHK(launch_refine<T>(false, sv, (int)al_.V, 1, (int)B, queue2_.as<int32_t>(), qc, x.rows, S_pad_,
+                                al_.rows(), S_pad_, view(), 0.0, btl, btc, nullptr,
                                 bv2_.as<int32_t>(), bs2_.as<double>(), err2_.as<double>(), nullptr, work, stream_));
     }
     if constexpr (kF32)
@@ -4286,7 +4289,7 @@ bool EngineT<T>::choose_push(int64_t N) const {
     // The belief side wins when B << V (the solve loop: ~100 new beliefs against thousands of alpha-vectors):
     // fewer rows to project and far less tile padding.  Sparse mode only.
     const int AO = A_ * O_;
-    if (mode_ == PBVI_DENSE || (int64_t)blk_.B * AO > 0x7fffffff || !(kF32 || f64_uses_mfma(blk_.B * AO, V_))) return false;
+    if (mode_ == PBVI_DENSE || (int64_t)blk_.B * AO > 0x7fffffff || !(kF32 || f64_uses_mfma(blk_.B * AO, al_.V))) return false;
     const int64_t bm = kF32 ? GEMM_BM : 128;                       // GEMM tile edge and sustained rate per dtype
     const double rate = kF32 ? 130e12 : 45e12;
     // projection cost per row, measured at C4: the alpha side writes only the Gamma tiles the GEMM will read
@@ -4296,7 +4299,7 @@ bool EngineT<T>::choose_push(int64_t N) const {
         const double tiles = (double)((m_rows + bm - 1) / bm) * (double)((n_rows + bm - 1) / bm);
         return tiles * S_pad_ * (2.0 * bm * bm / rate) + (double)proj_rows * S_pad_ * sizeof(T) / proj_rate;
     };
-    const double c_pull = cost(blk_.B, N, N, 6e12), c_push = cost(blk_.B * AO, V_, blk_.B * AO, 1e12);
+    const double c_pull = cost(blk_.B, N, N, 6e12), c_push = cost(blk_.B * AO, al_.V, blk_.B * AO, 1e12);
     if (formulation_ != 0) return formulation_ == 2;
     // Memory before speed: Gamma[A,O,V,S] is what the reference's CuPy path dies allocating (Sea_Robin_Real.ipynb:913,
     // 21.95 GB at |V| = 1386).  Where this engine would have to hold all of it (no fused generation: R > 1, fp64 scoring)
@@ -4316,7 +4319,7 @@ bool EngineT<T>::choose_push(int64_t N) const {
         };
         const int64_t pull = gam_new + std::max<int64_t>(0, slabs(blk_.B, N) - (int64_t)slabs_.cap);
         const int64_t push = std::max<int64_t>(0, m_push * row - (int64_t)bp_.cap) +
-                             std::max<int64_t>(0, slabs((int64_t)blk_.B * AO + blk_.B, V_) - (int64_t)slabs_.cap);
+                             std::max<int64_t>(0, slabs((int64_t)blk_.B * AO + blk_.B, al_.V) - (int64_t)slabs_.cap);
         if (push < pull && pull > room()) return true;
     }
     return c_push < 0.8 * c_pull;
@@ -4329,7 +4332,7 @@ template <typename T>
 int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, ScoreStage<T>* out) {
     int rc;
     const int AO = A_ * O_;
-    const int64_t Vt = V_ + 1;                 // alpha rows + magnitude row
+    const int64_t Vt = al_.V + 1;                 // alpha rows + magnitude row
     const int64_t N = (int64_t)AO * Vt + 2 * A_;   // Gamma rows: alpha groups, A*O magnitude rows, A reward + A |reward| rows
     const int64_t pairs = blk_.B * AO;
     const ModelView<T> mv = view();
@@ -4358,22 +4361,22 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
     const bool compact = will_fuse && R_ == 1 && !no_compact;
     if (will_fuse) {
         const int tiles_n = (int)(n_rows_alloc / GEMM_BN);
-        if (mat_V_ != V_ || (int)h_mat_.size() != tiles_n) {
+        if (mat_V_ != al_.V || (int)h_mat_.size() != tiles_n) {
             h_mat_.assign((size_t)tiles_n, 0);
             h_ctile_.assign((size_t)tiles_n, -1);
             n_mat_ = 0;
             for (int tn = 0; tn < tiles_n; ++tn) {
                 const int64_t r0 = (int64_t)tn * 256, r1 = r0 + 255;
-                h_mat_[(size_t)tn] = (r1 >= (int64_t)AO * V_ || r0 / V_ != r1 / V_) ? 1 : 0;
+                h_mat_[(size_t)tn] = (r1 >= (int64_t)AO * al_.V || r0 / al_.V != r1 / al_.V) ? 1 : 0;
                 if (h_mat_[(size_t)tn]) h_ctile_[(size_t)tn] = n_mat_++;
             }
             // the 4-row blocks of alpha rows the projection still has to visit: those with a row in a
             // projected tile for some group, and the block that holds the magnitude row
             h_vlist_.clear();
             for (int64_t vb = 0; vb * 4 < Vt; ++vb) {
-                bool hit = vb * 4 + 4 > V_;
+                bool hit = vb * 4 + 4 > al_.V;
                 for (int ao = 0; ao < AO && !hit; ++ao)
-                    for (int64_t v = vb * 4; v < vb * 4 + 4 && v < V_ && !hit; ++v) hit = h_mat_[(size_t)((ao * V_ + v) >> 8)] != 0;
+                    for (int64_t v = vb * 4; v < vb * 4 + 4 && v < al_.V && !hit; ++v) hit = h_mat_[(size_t)((ao * al_.V + v) >> 8)] != 0;
                 if (hit) h_vlist_.push_back((int)vb);
             }
             if ((rc = mat_.ensure((size_t)tiles_n))) return rc;
@@ -4382,7 +4385,7 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
             HIPCHK(hipMemcpyAsync(mat_.p, h_mat_.data(), (size_t)tiles_n, hipMemcpyHostToDevice, stream_));
             HIPCHK(hipMemcpyAsync(ctile_.p, h_ctile_.data(), (size_t)tiles_n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
             HIPCHK(hipMemcpyAsync(vlist_.p, h_vlist_.data(), h_vlist_.size() * sizeof(int), hipMemcpyHostToDevice, stream_));
-            mat_V_ = V_;
+            mat_V_ = al_.V;
             gam_pad_ptr_ = nullptr;                          // the pad rows sit elsewhere now
         }
     }
@@ -4399,9 +4402,9 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
         const int64_t budget = std::max<int64_t>(0, avail - reserve);
         TilingPlan tp;
         bool plan = tiling_mode_ == 2;
-        if (tiling_mode_ == 1) plan = tiling_chunk_bytes(S_pad_, AO, A_, blk_.B, kF32, V_) > budget;
+        if (tiling_mode_ == 1) plan = tiling_chunk_bytes(S_pad_, AO, A_, blk_.B, kF32, al_.V) > budget;
         if (plan) {
-            rc = tiling_plan(S_, A_, O_, V_, blk_.B, kF32, budget, tiling_rows_, &tp);
+            rc = tiling_plan(S_, A_, O_, al_.V, blk_.B, kF32, budget, tiling_rows_, &tp);
             if (rc == PBVI_EINVAL) FAIL(PBVI_EINVAL, "gamma tiling: shape out of range");
             if (rc == PBVI_ENOMEM && tiling_rows_ == 0)
                 FAIL(PBVI_ENOMEM, "gamma tiling: a 4-row chunk and the score matrix need " + std::to_string(tp.bytes) +
@@ -4451,7 +4454,7 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
         // Sea-Robin shape)
         HIPCHK(hipMemsetAsync(nzP_.p, 0, (size_t)(M_pad / GEMM_BM) * k_tiles, stream_));
         HIPCHK(launch_push_project<T>(blk_.rows.as<T>(), S_pad_, (int)blk_.B, mv, in_ptr_.as<int32_t>(), in_src_.as<int32_t>(), gamma,
-                                      alpha_.as<T>() + (size_t)V_ * S_pad_, bp_.as<T>(), S_pad_, pmag_.as<double>(), stream_,
+                                      al_.mag_row(), bp_.as<T>(), S_pad_, pmag_.as<double>(), stream_,
                                       nzP_.as<uint8_t>()));
         {
             const int64_t t0 = M / GEMM_BM;                  // first row tile with a row that is not a projected one
@@ -4463,7 +4466,7 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
                 HIPCHK(launch_tile_nonzero_f64((const double*)from, S_pad_, (int)(M_pad - t0 * GEMM_BM), k_tiles, to, stream_));
         }
         HIPCHK(hipEventRecord(io.ev[1], stream_));
-        if ((rc = score_gemm(alpha_.as<T>(), V_, nullptr, 1, (int)V_, &sv, bp_.as<T>(), Mx, nzP_.as<uint8_t>()))) return rc;
+        if ((rc = score_gemm(al_.rows(), al_.V, nullptr, 1, (int)al_.V, &sv, bp_.as<T>(), Mx, nzP_.as<uint8_t>()))) return rc;
         out->extra_row0 = M;
         sv.push = 1;
         sv.push_B = (int)blk_.B;
@@ -4482,7 +4485,7 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
         // tiles are written, and the 12 us of k_need_tiles leave the front of every backup)
         if ((kF32 || f64_uses_mfma(blk_.B, N)) && !(will_fuse && R_ == 1)) {
             if ((rc = need_.ensure((size_t)AO * k_tiles))) return rc;
-            HIPCHK(launch_need_tiles(blk_.nzA.as<uint8_t>(), (int)(blk_.B_pad / GEMM_BM), nzB_.as<uint8_t>(), AO, (int)V_, k_tiles,
+            HIPCHK(launch_need_tiles(blk_.nzA.as<uint8_t>(), (int)(blk_.B_pad / GEMM_BM), nzB_.as<uint8_t>(), AO, (int)al_.V, k_tiles,
                                      need_.as<uint8_t>(), stream_));
             need = need_.as<uint8_t>();
         }
@@ -4498,13 +4501,13 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
         } else {
             if constexpr (kF32) {
                 if (will_fuse) {
-                    fb.alpha = (const float*)alpha_.p;
+                    fb.alpha = (const float*)al_.view.p;
                     fb.lda = S_pad_;
                     fb.rs = rs_.as<int32_t>();
                     fb.rto = (const float*)rto_.p;
                     fb.S_pad = S_pad_;
                     fb.O = O_;
-                    fb.V = (int)V_;
+                    fb.V = (int)al_.V;
                     fb.R = R_;
                     fb.gamma = (float)gamma;
                     fb.mat = mat_.as<uint8_t>();
@@ -4513,7 +4516,7 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
                     fused = &fb;
                 }
             }
-            HIPCHK(launch_project<T>(alpha_.as<T>(), S_pad_, (int)Vt, mv, (T)gamma, gam_.as<T>(), S_pad_, need, k_tiles, stream_,
+            HIPCHK(launch_project<T>(al_.rows(), S_pad_, (int)Vt, mv, (T)gamma, gam_.as<T>(), S_pad_, need, k_tiles, stream_,
                                      fused ? mat_.as<uint8_t>() : nullptr, fused && R_ == 1 ? vlist_.as<int>() : nullptr,
                                      fused && R_ == 1 ? (int)h_vlist_.size() : 0,
                                      fused && R_ > 1 ? irr_.as<int32_t>() : nullptr, ctile));
@@ -4523,7 +4526,7 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
         // K2: scores
         // (its tile lists and stream-K plan are built on the side stream, beside the projection)
         int split = want_split;
-        if ((rc = score_gemm(gam_.as<T>(), N, nzB_.as<uint8_t>(), AO, (int)V_, &sv, nullptr, 0, nullptr, io.side, fused, &split)))
+        if ((rc = score_gemm(gam_.as<T>(), N, nzB_.as<uint8_t>(), AO, (int)al_.V, &sv, nullptr, 0, nullptr, io.side, fused, &split)))
             return rc;
         out->split = split;
         out->fused = fused != nullptr;
@@ -4536,7 +4539,7 @@ int EngineT<T>::stage_scores(double gamma, bool use_push, const ScoreIO& io, Sco
     out->chain = chain_steps();
     out->rd_col0 = (int64_t)AO * Vt;
     out->f64_pairs = f64_pairs_;
-    HIPCHK(launch_argmax<T>(sv, (int)V_, AO, (int)blk_.B, io.dead, out->tol_rel, 0.0, out->chain, 0, io.best_v, io.best_score,
+    HIPCHK(launch_argmax<T>(sv, (int)al_.V, AO, (int)blk_.B, io.dead, out->tol_rel, 0.0, out->chain, 0, io.best_v, io.best_score,
                             io.err, io.queue, io.qcount, stream_, io.tol_extra, out->split, io.hcand, io.hncand));
     if (probe_on_ && (rc = probe_capture(sv, io, *out))) return rc;      // tests only (pbvi_debug_score_probe)
     HIPCHK(hipEventRecord(io.ev[3], stream_));
@@ -4557,7 +4560,7 @@ int EngineT<T>::ensure_exact(DevBuf& b, size_t bytes) {
 
 // The alpha-side scoring stage with Gamma tiled over the alpha set (pbvi_set_gamma_tiling): n_chunks chunks of Vc alpha
 // rows (the last one ragged).  A chunk of Gamma is exactly the Gamma of a smaller alpha set -- rows [v0, v0 + vc) of
-// alpha_ followed by one more row that k_project takes for the magnitude row: the NEXT chunk's first row, whose scores
+// the view followed by one more row that k_project takes for the magnitude row: the NEXT chunk's first row, whose scores
 // nobody reads, or, behind the last chunk, the true max_v |alpha| row over the whole set -- so projection, need map and
 // GEMM run as they are on one chunk-sized Gamma buffer, and k_fold_chunk sums each chunk's partial slabs into the
 // full-width score matrix.  First-max, tie windows, refinement and the action stage then see ONE matrix: ties across
@@ -4567,7 +4570,7 @@ int EngineT<T>::stage_scores_tiled(double gamma, const ScoreIO& io, int want_spl
                                    ScoreStage<T>* out) {
     int rc;
     const int AO = A_ * O_;
-    const int64_t Vt = V_ + 1, N = (int64_t)AO * Vt + 2 * A_;
+    const int64_t Vt = al_.V + 1, N = (int64_t)AO * Vt + 2 * A_;
     const ModelView<T> mv = view();
     const int k_tiles = S_pad_ / GEMM_BK;
     const int64_t ldd = round_up(N, 4);
@@ -4601,7 +4604,7 @@ int EngineT<T>::stage_scores_tiled(double gamma, const ScoreIO& io, int want_spl
     bool on_device = false;                                  // some chunk's window comes from its stream-K share size
     out->split = 0;
     for (int64_t c = 0; c < n_chunks; ++c) {
-        const int64_t v0 = c * Vc, vc = std::min<int64_t>(Vc, V_ - v0);
+        const int64_t v0 = c * Vc, vc = std::min<int64_t>(Vc, al_.V - v0);
         const bool last = c == n_chunks - 1;
         const int64_t n_c = (int64_t)AO * (vc + 1) + 2 * A_, rows_c = kF32 ? round_up(n_c, GEMM_BN) : n_c;
         // pad rows of this chunk's shape: the (buffer, row count, layout) key covers the ragged last chunk
@@ -4617,7 +4620,7 @@ int EngineT<T>::stage_scores_tiled(double gamma, const ScoreIO& io, int want_spl
                                      need_.as<uint8_t>(), stream_));
             need = need_.as<uint8_t>();
         }
-        HIPCHK(launch_project<T>(alpha_.as<T>() + (size_t)v0 * S_pad_, S_pad_, (int)(vc + 1), mv, (T)gamma, gam_.as<T>(), S_pad_,
+        HIPCHK(launch_project<T>(al_.rows() + (size_t)v0 * S_pad_, S_pad_, (int)(vc + 1), mv, (T)gamma, gam_.as<T>(), S_pad_,
                                  need, k_tiles, stream_));
         HIPCHK(launch_tail_rows<T>(mv, gam_.as<T>(), (int64_t)AO * (vc + 1), S_pad_, stream_, nullptr));
         if (c == 0) HIPCHK(hipEventRecord(io.ev[1], stream_));
@@ -4634,7 +4637,7 @@ int EngineT<T>::stage_scores_tiled(double gamma, const ScoreIO& io, int want_spl
         const double t = tie_window(kF32 ? plan_.chunk_len * GEMM_BK : S_pad_);
         if (t < 0.0) on_device = true;
         else tol = std::max(tol, t);
-        HIPCHK(launch_fold_chunk<T>(sv, (int)blk_.B, AO, (int)vc, (int)V_, (int)v0, last ? AO + 2 * A_ : 0, scores_.as<T>(), ldd,
+        HIPCHK(launch_fold_chunk<T>(sv, (int)blk_.B, AO, (int)vc, (int)al_.V, (int)v0, last ? AO + 2 * A_ : 0, scores_.as<T>(), ldd,
                                     chain_steps(), chain_max_.as<int>(), stream_));
         if (io.stats) HIPCHK(hipEventRecord(tile_ev_[(size_t)3 * c + 2], stream_));
     }
@@ -4649,7 +4652,7 @@ int EngineT<T>::stage_scores_tiled(double gamma, const ScoreIO& io, int want_spl
     out->f64_pairs = f64_pairs_;
     out->fused = false;
     out->chunks = (int)n_chunks;
-    HIPCHK(launch_argmax<T>(full, (int)V_, AO, (int)blk_.B, io.dead, out->tol_rel, 0.0, out->chain, 0, io.best_v, io.best_score,
+    HIPCHK(launch_argmax<T>(full, (int)al_.V, AO, (int)blk_.B, io.dead, out->tol_rel, 0.0, out->chain, 0, io.best_v, io.best_score,
                             io.err, io.queue, io.qcount, stream_, io.tol_extra, out->split, io.hcand, io.hncand));
     if (probe_on_ && (rc = probe_capture(full, io, *out))) return rc;    // tests only (pbvi_debug_score_probe)
     HIPCHK(hipEventRecord(io.ev[3], stream_));
@@ -4693,45 +4696,40 @@ int EngineT<T>::sync_screen() {
     } else {
         EngineT<float>* sc = screen_;
         int rc;
-        if (screen_alpha_seen_ != alpha_ver_) {
+        if (screen_alpha_seen_.ver != al_.ver) {
             if (!scr_flag_.p) {
                 if ((rc = scr_flag_.ensure(sizeof(int)))) return rc;
                 HIPCHK(hipMemsetAsync(scr_flag_.p, 0, sizeof(int), stream_));
             }
-            auto narrow = [&](const double* src, float* dst, int64_t rows) -> int {
+            auto narrow = [&](int64_t rows) -> int {             // the view's first `rows` rows -> the screen's view
                 const int64_t n = rows * S_pad_;
                 if (n <= 0) return PBVI_OK;
-                hipLaunchKernelGGL(k_narrow, dim3((unsigned)((n / 4 + 255) / 256 + 1)), dim3(256), 0, stream_, src, dst, n,
+                hipLaunchKernelGGL(k_narrow, dim3((unsigned)((n / 4 + 255) / 256 + 1)), dim3(256), 0, stream_, al_.rows(), sc->al_.rows(), n,
                                    scr_flag_.as<int>());
                 HIPCHK(hipGetLastError());
                 return PBVI_OK;
             };
             // The screen's copy mirrors this engine's layout row for row (same free rows in front of a primary set), so a
-            // set that grew at the front costs the fp32 copy its new rows only.
-            const int64_t off = alpha_on_primary_ ? prim_off_ : 0;
-            const size_t rows_total = alpha_on_primary_ ? alpha_buf_.cap / ((size_t)S_pad_ * sizeof(double)) : alpha_rows_cap(V_);
-            if (alpha_on_primary_ && screen_layout_seen_ == prim_layout_ver_ && screen_off_seen_ >= off &&
-                sc->alpha_buf_.cap >= rows_total * S_pad_ * sizeof(float)) {
-                const int64_t k = screen_off_seen_ - off;
-                sc->alpha_view(sc->alpha_buf_, off);
-                sc->V_ = V_;
-                if ((rc = narrow(alpha_.as<double>(), sc->alpha_.template as<float>(), k))) return rc;
-                if ((rc = sc->merge_magnitude_row(sc->alpha_.template as<float>(), k))) return rc;
+            // set that grew at the front costs the fp32 copy its new rows only.  (The screen never selects by itself.)
+            const bool prim = al_.on_primary();
+            const int64_t off = prim ? al_.off : 0, V = al_.V;
+            const auto where = prim ? sc->al_.PRIMARY_ORPHAN : sc->al_.PLAIN;
+            const size_t rows_total = prim ? al_.buf.cap / al_.row_bytes() : al_.rows_cap(V);
+            if (prim && screen_alpha_seen_.layout_ver == al_.layout_ver && screen_alpha_seen_.off >= off &&
+                sc->al_.buf.cap >= rows_total * sc->al_.row_bytes()) {
+                const int64_t k = screen_alpha_seen_.off - off;
+                sc->al_.placed(where, off, V);
+                if ((rc = narrow(k))) return rc;
+                if ((rc = sc->alpha_installed(sc->al_.rows(), k))) return rc;
             } else {
-                if ((rc = sc->alpha_buf_.ensure(rows_total * S_pad_ * sizeof(float)))) return rc;
-                sc->alpha_view(sc->alpha_buf_, off);
-                sc->V_ = V_;
+                if ((rc = sc->al_.buf.ensure(rows_total * sc->al_.row_bytes()))) return rc;
+                sc->al_.placed(where, off, V);
                 HIPCHK(hipMemsetAsync(scr_flag_.p, 0, sizeof(int), stream_));        // a fresh copy: no row has overflowed yet
-                if ((rc = narrow(alpha_.as<double>(), sc->alpha_.template as<float>(), V_))) return rc;
-                HIPCHK(hipMemsetAsync(sc->alpha_.template as<float>() + (size_t)V_ * S_pad_, 0,
-                                      (rows_total - (size_t)off - (size_t)V_) * S_pad_ * sizeof(float), stream_));
-                if ((rc = sc->refresh_magnitude_row())) return rc;
+                if ((rc = narrow(V))) return rc;
+                HIPCHK(hipMemsetAsync(sc->al_.mag_row(), 0, (rows_total - (size_t)off - (size_t)V) * sc->al_.row_bytes(), stream_));
+                if ((rc = sc->alpha_installed())) return rc;
             }
-            screen_layout_seen_ = alpha_on_primary_ ? prim_layout_ver_ : 0;      // 0: no primary layout is mirrored
-            screen_off_seen_ = off;
-            sc->prim_valid_ = sc->alpha_on_primary_ = false;                     // (the screen never selects by itself)
-            sc->have_result_ = false;
-            screen_alpha_seen_ = alpha_ver_;
+            screen_alpha_seen_ = {al_.ver, prim ? al_.layout_ver : 0, off};      // layout 0: no primary layout is mirrored
         }
         if (screen_bel_seen_ != blk_.ver) {
             const int k_tiles = S_pad_ / GEMM_BK;
@@ -4756,11 +4754,11 @@ int EngineT<T>::sync_screen() {
 
 template <typename T>
 int EngineT<T>::run_backup(double gamma, int flags, pbvi_stats_t* st, Mode mode) {
-    if (V_ <= 0) FAIL(PBVI_EINVAL, "backup_run: no alpha set resident (call pbvi_alpha_set)");
+    if (al_.V <= 0) FAIL(PBVI_EINVAL, "backup_run: no alpha set resident (call pbvi_alpha_set)");
     if (blk_.B <= 0) FAIL(PBVI_EINVAL, "backup_run: no belief block resident (call pbvi_beliefs_set)");
     HIPCHK(hipSetDevice(device_));
     if constexpr (!kF32) {
-        const int64_t N = (int64_t)A_ * O_ * (V_ + 1) + 2 * A_;
+        const int64_t N = (int64_t)A_ * O_ * (al_.V + 1) + 2 * A_;
         // worth it once the score GEMM is more than a few tiles (tiger, the 4x3 grid, S = 600 models stay pure fp64)
         const double gemm_flops = 2.0 * (double)round_up(blk_.B, 128) * (double)N * (double)S_pad_;   // ~0.4 ms of fp64 MFMA
         const bool want = screen_mode_ == 2 || (screen_mode_ == 1 && f64_uses_mfma(blk_.B, N) && gemm_flops >= 2e10);

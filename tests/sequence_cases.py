@@ -358,6 +358,7 @@ class Shadow:
         self.astore, self.bstore = [], []
         self.result = None                      # None, or the belief-dominance flag of the fetchable backup
         self.prim_ids, self.prim_free = None, 0
+        self.sel_ids, self.sel_store = None, 0  # the ids of the last selection of alpha rows, the store's length then
         self.weights = None                     # None, or the state weights [S]
         self.store = None                       # None (no corner set), or the point store: corner, pts, vals, gaps, bounds
 
@@ -431,7 +432,7 @@ QUERIES_V1 = ('run_fetch', 'run_prune_fetch', 'run_fetch_into', 'fetch_compact_i
               'fetch_refused')
 REFUSALS = ('fetch_refused', 'weights_refused', 'upper_refused')
 QUERIES = QUERIES_V1 + ('space_aware', 'upper_bound', 'upper_q', 'weights_refused', 'upper_refused')
-HARNESS = ('remember', 'same_as')
+HARNESS = ('remember', 'same_as', 'layout')
 # calls of the Python layer that answer AND move the working sets (counted, but outside the mutation -> query pairs);
 # 'run_only' is a backup that nobody fetches yet
 COMPOUND_V1 = ('vmax_objects', 'clear_environment')
@@ -479,6 +480,8 @@ def legal(name, args, sh):
             return sh.prim_ids is not None and all(i < len(sh.astore) for i in sh.prim_ids)
         if how == 'small':
             return sh.prim_ids is not None and len(sh.prim_ids) >= 4 and len(sh.astore) > 0
+        if how == 'again':
+            return sh.sel_ids is not None
         return len(sh.astore) > 0
     if name == 'select_beliefs':
         return len(sh.bstore) > 0 and (args['how'] != 'same' or sh.bel_ids is not None)
@@ -621,6 +624,13 @@ class Runner:
             compare = self.same_bits if v.dtype.kind == 'f' and np.isnan(v).any() else self.same      # (successor values hold NaNs)
             compare(self.last[k], v, f'{k} against the call remembered as {tag!r}')
 
+    def op_layout(self, **want):
+        """``alpha_layout()`` of an engine that lays its set out: the named fields (``extendable``, ``free``, ``layouts``)."""
+        if hasattr(self.eng, 'alpha_layout'):
+            got = dict(zip(('extendable', 'free', 'layouts'), self.eng.alpha_layout()))
+            if any(got[k] != v for k, v in want.items()):
+                self.fail(f'alpha_layout() is {got}, expected {want}')
+
     # -- switches and resets ---------------------------------------------------------------------------------------- #
     def op_switch(self, name, value):
         value = tuple(value) if isinstance(value, list) else value
@@ -670,6 +680,7 @@ class Runner:
         self.forms.append(self.sh.select_form(ids))
         self.eng.select_alpha(ids)
         self.sh.put_alpha(np.stack([self.sh.astore[i] for i in ids]), ids)
+        self.sh.sel_ids, self.sh.sel_store = ids, len(self.sh.astore)
 
     def op_store_alpha(self, **recipe):
         self._store_alpha(alpha_rows(self.mname, **recipe))
@@ -687,6 +698,8 @@ class Runner:
             ids = rng.integers(0, n, max(1, min(len(sh.prim_ids) // 4, 4096, 40)))
         elif how == 'all':
             ids = np.arange(n)[::-1]
+        elif how == 'again':                                   # the last selection's ids behind the rows stored since: an
+            ids = np.concatenate([np.arange(sh.sel_store, n), sh.sel_ids])      # extension, whatever was uploaded in between
         else:
             ids = rng.permutation(n)[:max(1, (n + 1) // 2)]
         self._select_alpha(ids)
@@ -707,7 +720,7 @@ class Runner:
 
     def op_reset_alpha_store(self):
         self.eng.reset_store('alpha')
-        self.sh.astore, self.sh.alpha_ids, self.sh.prim_ids = [], None, None
+        self.sh.astore, self.sh.alpha_ids, self.sh.prim_ids, self.sh.sel_ids = [], None, None, None
 
     # -- belief block ----------------------------------------------------------------------------------------------- #
     def op_set_beliefs(self, hits=0, **recipe):
@@ -1979,11 +1992,43 @@ class WindowSticks(HostEngine):
         self.prev_nv = None
 
 
+class GivenUpPrimaryAnswers(HostEngine):
+    """``append_alpha`` does not give the primary layout up: a later selection whose ids end in that layout's ids is taken
+    for an extension of it, and where the old view pointed the regrown, zero-filled buffer holds zero rows."""
+
+    def select_alpha(self, ids):
+        ids = [int(i) for i in ids]
+        prim, stale = getattr(self, 'prim', None), getattr(self, 'stale_prim', None)
+        super().select_alpha(ids)
+        if stale is not None and len(ids) >= len(stale) and ids[len(ids) - len(stale):] == stale:
+            self.alpha[len(ids) - len(stale):] = 0.0
+        elif prim is not None and len(ids) <= 4096 and 4 * len(ids) <= len(prim):
+            return                                                               # beside the primary set, which stays
+        self.prim, self.stale_prim = ids, None
+
+    def append_alpha(self, a):
+        super().append_alpha(a)
+        self.prim, self.stale_prim = None, getattr(self, 'prim', None) or getattr(self, 'stale_prim', None)
+
+    def set_alpha(self, a):
+        super().set_alpha(a)
+        self.prim = self.stale_prim = None
+
+    def reset_store(self, which):
+        super().reset_store(which)
+        if which == 'alpha':
+            self.prim = self.stale_prim = None
+
+    def after_oom(self):
+        super().after_oom()
+        self.prim = self.stale_prim = None
+
+
 DEFECTS = {'dead_map_kept': DeadMapKept, 'magnitude_not_merged': MagnitudeNotMerged, 'previous_caller_order': PreviousCallerOrder,
            'fetch_after_set_alpha': FetchAfterSetAlpha, 'store_zero_maps_kept': StoreZeroMapsKept,
            'weights_survive_a_reset': WeightsSurviveAReset, 'old_weights_read': OldWeightsRead,
            'extra_of_the_other_objective': ExtraOfTheOtherObjective, 'append_offsets_restart': AppendOffsetsRestart,
-           'window_sticks': WindowSticks}
+           'window_sticks': WindowSticks, 'given_up_primary_answers': GivenUpPrimaryAnswers}
 
 
 # --------------------------------------------------------------------------------------------------------------------- #
@@ -2307,6 +2352,27 @@ def _greedy_calls_under_switches():
 
 SCRIPTED['switches_do_not_reach_the_greedy_calls'] = (MODELS, DTYPES, _greedy_calls_under_switches())
 
+# The placement of the working alpha set, through the transitions no sequence above reaches: a primary layout given up by an
+# upload and then asked for by its own ids (a fresh layout: the one given up must not answer); a small set beside the
+# primary layout appended to (its rows move into the primary's buffer) and then the old primary's ids (fresh again); a primary
+# layout extended by exactly its free rows, appended to where it stands, and then extended by one row (no free rows: fresh).
+# 'layout' names what alpha_layout() says on the way: extendable, free rows, fresh layouts so far.
+_ALPHA_PLACEMENTS = [
+    op('set_beliefs', B=129, seed=4), sw_('formulation', 'alpha'),
+    op('store_alpha', V=20, seed=1), op('select_alpha', how='all'), op('layout', extendable=True, free=512, layouts=1), op('run_fetch'),
+    op('append_alpha', V=3, seed=2, scale=40.0), op('layout', extendable=False), op('run_fetch'), op('vmax_resident'),
+    op('select_alpha', how='again'), op('layout', extendable=True, free=512, layouts=2), op('run_fetch'), op('vmax_resident'),
+    op('select_alpha', how='small', seed=1), op('layout', extendable=False, layouts=2), op('run_fetch'),
+    op('append_alpha', V=2, seed=3, scale=40.0), op('layout', extendable=False), op('run_fetch'), op('vmax_resident'),
+    op('select_alpha', how='all'), op('layout', extendable=True, free=512, layouts=3), op('run_fetch'), op('prune_masked', seed=1),
+    op('reset_alpha_store'), op('store_alpha', V=5, seed=4), op('select_alpha', how='all'),
+    op('extend_alpha', V=512, seed=5, near=40), op('layout', extendable=True, free=0, layouts=4), op('run_fetch'), op('vmax_resident'),
+    op('append_alpha', V=1, seed=6, scale=40.0), op('layout', extendable=False), op('run_fetch'), op('vmax_resident'),
+    op('store_alpha', V=1, seed=7), op('select_alpha', how='again'), op('layout', extendable=True, free=512, layouts=5),
+    op('run_fetch'), op('prune_dominated')]
+SCRIPTED['alpha_placements'] = (MODELS, DTYPES, _ALPHA_PLACEMENTS)
+SCRIPTED['alpha_placements_under_the_screen'] = (MODELS, ('f64',), [sw_('f64_screen', 'always')] + _ALPHA_PLACEMENTS)
+
 
 def pair_sequence(mutation):
     """Set-up, one mutation, then every query that is legal behind it (a backup in between where a query needs one)."""
@@ -2356,7 +2422,8 @@ DEFECT_SCRIPTS = {'dead_map_kept': 'dead_triples_and_tile_lists', 'magnitude_not
                   'previous_caller_order': 'sorted_blocks_of_one_size', 'fetch_after_set_alpha': 'results_of_an_earlier_backup',
                   'store_zero_maps_kept': 'belief_store_zero_maps', 'weights_survive_a_reset': 'weights_lifecycle',
                   'old_weights_read': 'weights_lifecycle', 'extra_of_the_other_objective': 'successor_score_buffers',
-                  'append_offsets_restart': 'point_store_lifecycle', 'window_sticks': 'point_store_lifecycle'}
+                  'append_offsets_restart': 'point_store_lifecycle', 'window_sticks': 'point_store_lifecycle',
+                  'given_up_primary_answers': 'alpha_placements'}
 
 
 def scripted_cases():

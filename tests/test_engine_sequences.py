@@ -16,7 +16,7 @@ through ``max_value_objects``) and, where the score probe is on, ``best_score`` 
 it is checked against the host statement at the bar and its bits are adopted into the shadow.
 
 CPU tests: every sequence runs against ``HostEngine`` (the host statements under ``Engine``'s method names) with no entry
-skipped as undecidable; ten stand-ins with one planted carry-over bug each fail a scripted and a seeded sequence; the
+skipped as undecidable; eleven stand-ins with one planted carry-over bug each fail a scripted and a seeded sequence; the
 operation lists cover the vocabulary.  GPU tests: the same sequences on the HIP engine, both models, both engine types.
 """
 import functools
