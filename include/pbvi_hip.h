@@ -817,6 +817,11 @@ int pbvi_debug_gemm_dense(int enable);
  * Other values change nothing.  Process-wide; returns the previous schedule.  Not a tuning knob: time a schedule in a
  * build of its own. */
 int pbvi_debug_split_schedule(int schedule);
+/* Tests and A/B only: whether schedule 0 runs with the block's two wave halves staggered by role (waves 4-7 stage the
+ * next tile first and multiply last).  1 (default) or 0; PBVI_NO_SPLIT_STAGGER=1 in the environment starts a
+ * process at 0.  Same terms, order and LDS image, so the slabs are bit-identical; the test holds them so.  Schedule 1 has
+ * no staggered form and ignores the switch.  Process-wide; returns the previous value. */
+int pbvi_debug_split_stagger(int on);
 /* Tests only: the raw score slab buffer as the last backup's score GEMM left it (partial slabs in the GEMM plan's layout,
  * padding and parts no block wrote included), copied to host memory.  out == NULL: returns the buffer's size in bytes;
  * else copies that many bytes to out (cap_bytes: the room there) and returns the count.  A stage that runs a GEMM of its

@@ -5157,6 +5157,7 @@ void pbvi_host_free(void* p) {
 }
 int pbvi_debug_gemm_dense(int enable) { return pbvi::set_gemm_force_dense(enable); }
 int pbvi_debug_split_schedule(int schedule) { return pbvi::set_gemm_split_schedule(schedule); }
+int pbvi_debug_split_stagger(int on) { return pbvi::set_gemm_split_stagger(on); }
 int64_t pbvi_debug_slabs(pbvi_engine_t* e, void* out, int64_t cap_bytes) {
     NEED(e);
     return e->impl->debug_slabs(out, cap_bytes);

@@ -29,6 +29,7 @@
 #include "split_bf16.h"
 
 #include <cstdlib>
+#include <type_traits>
 #include <map>
 #include <mutex>
 
@@ -836,13 +837,19 @@ __device__ __forceinline__ void split_mfma8(const i32x4 (&a)[4], const i32x4 (&b
 //         B rows 0-127 | kk1 t1 | B rows 128-255 | kk1 t2 | barrier
 //   else: B rows, A DMA | kk0 t0 | kk0 t1 | kk0 t2 | kk1 t0 | wait B rows; B rows 0-127 | kk1 t1 | B rows 128-255 | kk1 t2 |
 //         barrier
-template <int SCHED>
+// STAG (parent schedule only): waves 0-3 run the step above, waves 4-7 the same terms with the staging first:
+//   B rows 0-255 of tile k+1 (registers landed a step earlier), A DMA (k+1), register loads of tile k+2 (indices: k+3) |
+//   kk0 t0 | kk0 t1 | kk0 t2 | kk1 t0 | kk1 t1 | kk1 t2 | wait all | barrier
+template <int SCHED, bool STAG>
 __device__ __forceinline__ void tile_run_split(const TileThread& t, float* lds, const float* Aplane, int lda, const float* Bblk,
                                                int ldb, bool gen, const int32_t* __restrict__ rsrow,
                                                const float* __restrict__ rtorow, const float* __restrict__ arow0,
                                                int64_t a_step, float gamma, const int* __restrict__ kl, int i0, int i1,
                                                f32x16 (&acc)[4][2]) {
-    const int tid = threadIdx.x;
+    int tid = threadIdx.x;
+    // (staggered kernel: the per-thread staging addresses are worked out per segment, not kept for the whole kernel --
+    // its loops leave no VGPR for them, and they would go to scratch)
+    if constexpr (STAG) asm volatile("" : "+v"(tid));
     const int kg = tid & 3, r0 = tid >> 2;
     f32x4 xb[2][2];
     i32x4 idx[2];
@@ -941,8 +948,68 @@ __device__ __forceinline__ void tile_run_split(const TileThread& t, float* lds, 
     // list entries are read ahead of their use
     int k_next = (i0 + 1 < i1) ? kl[i0 + 1] : 0;
     int k_after = (i0 + 2 < i1) ? kl[i0 + 2] : 0;
-    __syncthreads();
     int buf = 0;
+    if (STAG && t.wid >= 4) {                             // (by half, not by parity: profiles/split_stagger.md)
+        // The late half of a staggered block.  Between two barriers every LDS read goes to buf and every write to buf ^ 1,
+        // so a wave may order its own interval freely: this half stages first and multiplies last, and its SIMD partner
+        // (wave wid - 4) does the reverse.  In interval `it` it scales, splits and stores tile it+1 from registers that
+        // landed during interval it-1, issues tile it+1's A DMA and the register loads of tile it+2 (indices: it+3), and
+        // then runs the six groups on buf.  The end wait names every staging register, so only landed values cross the
+        // barrier.  The steps are peeled by what is left of the list (no run-time condition between a load and its wait):
+        // (true, true) while it+2 < i1, (true, false) for it+2 == i1, (false, false) for the last tile.
+        int k_after2 = (i0 + 3 < i1) ? kl[i0 + 3] : 0;
+        if (i0 + 1 < i1) {                                // tile i0+1's B operand, and the indices of tile i0+2
+            if (gen) {
+                alphas(k_next);
+                weights(k_next);
+                indices(k_after);
+            } else {
+                load_rows(k_next);
+            }
+            asm volatile("s_waitcnt vmcnt(0)" : "+v"(xb[0][0]), "+v"(xb[0][1]), "+v"(xb[1][0]), "+v"(xb[1][1]), "+v"(w[0]),
+                         "+v"(w[1]), "+v"(idx[0]), "+v"(idx[1])::"memory");
+        }
+        __syncthreads();
+        int it = i0;
+        auto late_step = [&](auto store, auto load) {
+            const int k_after3 = (it + 4 < i1) ? kl[it + 4] : 0;
+            if constexpr (decltype(store)::value) {
+                store_b(buf ^ 1, 0);
+                store_b(buf ^ 1, 1);
+                stage_a(buf ^ 1, k_next);
+            }
+            if constexpr (decltype(load)::value) {
+                if (gen) {
+                    alphas(k_after);
+                    weights(k_after);
+                    indices(k_after2);                    // K tile 0 past the list's end: unused, but always 2 loads
+                } else {
+                    load_rows(k_after);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);            // staging first: no fragment read moves up into it
+            SplitFrag f;
+            split_group(t, lds, buf, 0, 0, f, acc);
+            split_group(t, lds, buf, 0, 1, f, acc);
+            split_group(t, lds, buf, 0, 2, f, acc);
+            split_group(t, lds, buf, 1, 0, f, acc);
+            split_group(t, lds, buf, 1, 1, f, acc);
+            split_group(t, lds, buf, 1, 2, f, acc);
+            asm volatile("s_waitcnt vmcnt(0)" : "+v"(xb[0][0]), "+v"(xb[0][1]), "+v"(xb[1][0]), "+v"(xb[1][1]), "+v"(w[0]),
+                         "+v"(w[1]), "+v"(idx[0]), "+v"(idx[1])::"memory");
+            __syncthreads();
+            buf ^= 1;
+            k_next = k_after;
+            k_after = k_after2;
+            k_after2 = k_after3;
+            ++it;
+        };
+        while (it + 2 < i1) late_step(std::true_type{}, std::true_type{});
+        if (it + 1 < i1) late_step(std::true_type{}, std::false_type{});
+        late_step(std::false_type{}, std::false_type{});
+        return;
+    }
+    __syncthreads();
     for (int it = i0; it < i1; ++it) {
         int k_after2 = 0;
         const bool more = it + 1 < i1;                    // block-uniform
@@ -1014,7 +1081,7 @@ __device__ __forceinline__ void tile_run_split(const TileThread& t, float* lds, 
 
 // A: the belief block's split plane.  fb.mat == nullptr: every B tile is read from fp32 rows (the projected route); else
 // scheduler 2b's tiles (R = 1).
-template <int SCHED>
+template <int SCHED, bool STAG>
 __device__ __forceinline__ void gemm_split_streamk_body(const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb,
                                                         FusedB fb, SlabOut out, StreamKView v) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -1022,12 +1089,12 @@ __device__ __forceinline__ void gemm_split_streamk_body(const float* __restrict_
         const float* Ablk = A + (int64_t)tm * 256 * lda;
         if (fb.mat == nullptr || fb.mat[tn]) {           // block-uniform: fp32 rows from B
             const int bt = (fb.mat != nullptr && fb.ctile != nullptr) ? fb.ctile[tn] : tn;
-            tile_run_split<SCHED>(t, lds, Ablk, lda, B + (int64_t)bt * 256 * ldb, ldb, false, nullptr, nullptr, nullptr, 0,
+            tile_run_split<SCHED, STAG>(t, lds, Ablk, lda, B + (int64_t)bt * 256 * ldb, ldb, false, nullptr, nullptr, nullptr, 0,
                                   0.f, v.klist + (int64_t)p * v.k_tiles, lo, hi, acc);
         } else {
             const int r0 = tn * 256;
             const int g = r0 / fb.V, v0 = r0 - g * fb.V;
-            tile_run_split<SCHED>(t, lds, Ablk, lda, nullptr, 0, true, fb.rs + (int64_t)(g / fb.O) * fb.S_pad,
+            tile_run_split<SCHED, STAG>(t, lds, Ablk, lda, nullptr, 0, true, fb.rs + (int64_t)(g / fb.O) * fb.S_pad,
                                   fb.rto + (int64_t)g * fb.S_pad, fb.alpha + (int64_t)(v0 + (threadIdx.x >> 2)) * fb.lda,
                                   (int64_t)128 * fb.lda, fb.gamma, v.klist + (int64_t)p * v.k_tiles, lo, hi, acc);
         }
@@ -1039,7 +1106,7 @@ __global__ __launch_bounds__(512) void k_gemm_split_streamk(
     int64_t slab_stride, int tiles_m, int pairs, int k_tiles, const int* __restrict__ klist, const int* __restrict__ kcount,
     const int* __restrict__ prefix, const int* __restrict__ start_pair, const int* __restrict__ first_block,
     const int* __restrict__ plan, int ovh) {
-    gemm_split_streamk_body<SPLIT_SCHED_PARENT>(A, lda, B, ldb, fb, SlabOut{C, ldc, slab_stride},
+    gemm_split_streamk_body<SPLIT_SCHED_PARENT, false>(A, lda, B, ldb, fb, SlabOut{C, ldc, slab_stride},
         StreamKView{klist, kcount, prefix, start_pair, first_block, plan, tiles_m, pairs, k_tiles, ovh});
 }
 // The pipelined K-step schedule on the same plan, lists and slabs (pbvi_debug_split_schedule)
@@ -1048,7 +1115,18 @@ __global__ __launch_bounds__(512) void k_gemm_split_streamk_pipelined(
     int64_t slab_stride, int tiles_m, int pairs, int k_tiles, const int* __restrict__ klist, const int* __restrict__ kcount,
     const int* __restrict__ prefix, const int* __restrict__ start_pair, const int* __restrict__ first_block,
     const int* __restrict__ plan, int ovh) {
-    gemm_split_streamk_body<SPLIT_SCHED_PIPELINED>(A, lda, B, ldb, fb, SlabOut{C, ldc, slab_stride},
+    gemm_split_streamk_body<SPLIT_SCHED_PIPELINED, false>(A, lda, B, ldb, fb, SlabOut{C, ldc, slab_stride},
+        StreamKView{klist, kcount, prefix, start_pair, first_block, plan, tiles_m, pairs, k_tiles, ovh});
+}
+
+// The parent schedule with the block's two wave halves staggered by role (pbvi_debug_split_stagger): waves 0-3 run the
+// parent step, waves 4-7 stage first and multiply last.  Same plan, lists, LDS image and slabs.
+__global__ __launch_bounds__(512) void k_gemm_split_streamk_staggered(
+    const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb, FusedB fb, float* __restrict__ C, int ldc,
+    int64_t slab_stride, int tiles_m, int pairs, int k_tiles, const int* __restrict__ klist, const int* __restrict__ kcount,
+    const int* __restrict__ prefix, const int* __restrict__ start_pair, const int* __restrict__ first_block,
+    const int* __restrict__ plan, int ovh) {
+    gemm_split_streamk_body<SPLIT_SCHED_PARENT, true>(A, lda, B, ldb, fb, SlabOut{C, ldc, slab_stride},
         StreamKView{klist, kcount, prefix, start_pair, first_block, plan, tiles_m, pairs, k_tiles, ovh});
 }
 
@@ -1202,11 +1280,12 @@ struct GemmEnv {
     int chunk;        // PBVI_GEMM_CHUNK=n: K chunk of the non-persistent scheduler, in tiles
     int no_streamk;   // PBVI_GEMM_NO_STREAMK=1: the non-persistent scheduler for score GEMMs too
     int ovh;          // PBVI_STREAMK_OVH=n: per-pair fixed cost of the stream-K plan, in tile-steps
+    int no_stagger;   // PBVI_NO_SPLIT_STAGGER=1: the split score GEMM's lockstep kernel (debugging and A/B only)
 };
 static int env_int(const char* name, int dflt) { return getenv(name) ? atoi(getenv(name)) : dflt; }
 static const GemmEnv& gemm_env() {
     static const GemmEnv env{env_int("PBVI_GEMM_DENSE", 0) != 0, env_int("PBVI_GEMM_CHUNK", 0), env_int("PBVI_GEMM_NO_STREAMK", 0),
-                             env_int("PBVI_STREAMK_OVH", 1)};
+                             env_int("PBVI_STREAMK_OVH", 1), env_int("PBVI_NO_SPLIT_STAGGER", 0) != 0};
     return env;
 }
 
@@ -1224,6 +1303,16 @@ static int g_split_schedule = SPLIT_SCHED_PARENT;
 int set_gemm_split_schedule(int schedule) {
     const int prev = g_split_schedule;
     if (schedule == SPLIT_SCHED_PARENT || schedule == SPLIT_SCHED_PIPELINED) g_split_schedule = schedule;
+    return prev;
+}
+
+// Whether the parent schedule runs with its wave halves staggered (pbvi_debug_split_stagger): a second, independent
+// switch, process-wide.  Bit-identical slabs (tests/test_split_stagger.py); measurements: profiles/split_stagger.md.
+static int g_split_stagger = -1;                   // set_gemm_split_stagger overrides the environment
+static int gemm_split_stagger() { return g_split_stagger < 0 ? !gemm_env().no_stagger : g_split_stagger; }
+int set_gemm_split_stagger(int on) {
+    const int prev = gemm_split_stagger();
+    g_split_stagger = on ? 1 : 0;
     return prev;
 }
 
@@ -1255,33 +1344,37 @@ hipError_t launch_tile_nonzero_f32(const float* X, int ld, int rows_pad, int k_t
     return hipGetLastError();
 }
 
-// The stream-K kernels: which one runs for (split, schedule, fused, R), and the dynamic LDS it needs.  ANY matches every
-// value; the first matching row counts.  set_lds_attr walks the same rows, so a kernel added here is also configured.
+// The stream-K kernels: which one runs for (split, schedule, stagger, fused, R), and the dynamic LDS it needs.  ANY
+// matches every value; the first matching row counts.  The stagger exists for the parent schedule only: with the
+// pipelined schedule selected the lockstep pipelined kernel runs whatever the stagger switch says.  set_lds_attr walks
+// the same rows, so a kernel added here is also configured.
 using StreamKKernel = void (*)(const float*, int, const float*, int, FusedB, float*, int, int64_t, int, int, int, const int*,
                                const int*, const int*, const int*, const int*, const int*, int);
 struct StreamKKernelRow {
-    int split, schedule, fused, R;
+    int split, schedule, stagger, fused, R;
     StreamKKernel kernel;
     int lds_bytes;
 };
 constexpr int ANY = -1;
 static const StreamKKernelRow STREAMK_KERNELS[] = {
-    {1, SPLIT_SCHED_PARENT, ANY, ANY, k_gemm_split_streamk, GEMM_LDS_BYTES},
-    {1, SPLIT_SCHED_PIPELINED, ANY, ANY, k_gemm_split_streamk_pipelined, GEMM_LDS_BYTES},
-    {0, ANY, 0, ANY, k_gemm_nt_f32_streamk, GEMM_LDS_BYTES},
-    {0, ANY, 1, 1, k_gemm_nt_f32_streamk_fused, GEMM_LDS_BYTES},
-    {0, ANY, 1, 2, k_gemm_nt_f32_streamk_fused_r<2>, GEMM_LDS_BYTES_R},
-    {0, ANY, 1, 3, k_gemm_nt_f32_streamk_fused_r<3>, GEMM_LDS_BYTES_R},
-    {0, ANY, 1, 4, k_gemm_nt_f32_streamk_fused_r<4>, GEMM_LDS_BYTES_R},
-    {0, ANY, 1, 5, k_gemm_nt_f32_streamk_fused_r<5>, GEMM_LDS_BYTES_R},
-    {0, ANY, 1, 6, k_gemm_nt_f32_streamk_fused_r<6>, GEMM_LDS_BYTES_R},
-    {0, ANY, 1, 7, k_gemm_nt_f32_streamk_fused_r<7>, GEMM_LDS_BYTES_R},
+    {1, SPLIT_SCHED_PARENT, 1, ANY, ANY, k_gemm_split_streamk_staggered, GEMM_LDS_BYTES},
+    {1, SPLIT_SCHED_PARENT, 0, ANY, ANY, k_gemm_split_streamk, GEMM_LDS_BYTES},
+    {1, SPLIT_SCHED_PIPELINED, ANY, ANY, ANY, k_gemm_split_streamk_pipelined, GEMM_LDS_BYTES},
+    {0, ANY, ANY, 0, ANY, k_gemm_nt_f32_streamk, GEMM_LDS_BYTES},
+    {0, ANY, ANY, 1, 1, k_gemm_nt_f32_streamk_fused, GEMM_LDS_BYTES},
+    {0, ANY, ANY, 1, 2, k_gemm_nt_f32_streamk_fused_r<2>, GEMM_LDS_BYTES_R},
+    {0, ANY, ANY, 1, 3, k_gemm_nt_f32_streamk_fused_r<3>, GEMM_LDS_BYTES_R},
+    {0, ANY, ANY, 1, 4, k_gemm_nt_f32_streamk_fused_r<4>, GEMM_LDS_BYTES_R},
+    {0, ANY, ANY, 1, 5, k_gemm_nt_f32_streamk_fused_r<5>, GEMM_LDS_BYTES_R},
+    {0, ANY, ANY, 1, 6, k_gemm_nt_f32_streamk_fused_r<6>, GEMM_LDS_BYTES_R},
+    {0, ANY, ANY, 1, 7, k_gemm_nt_f32_streamk_fused_r<7>, GEMM_LDS_BYTES_R},
 };
 // nullptr: no such kernel (a fused R outside 1..FUSED_R_MAX)
-static const StreamKKernelRow* streamk_kernel(int split, int schedule, int fused, int R) {
+static const StreamKKernelRow* streamk_kernel(int split, int schedule, int stagger, int fused, int R) {
     auto fits = [](int want, int have) { return want == ANY || want == have; };
     for (const StreamKKernelRow& row : STREAMK_KERNELS)
-        if (fits(row.split, split) && fits(row.schedule, schedule) && fits(row.fused, fused) && fits(row.R, R)) return &row;
+        if (fits(row.split, split) && fits(row.schedule, schedule) && fits(row.stagger, stagger) &&
+            fits(row.fused, fused) && fits(row.R, R)) return &row;
     return nullptr;
 }
 
@@ -1341,7 +1434,7 @@ hipError_t launch_score_gemm_f32(const ScoreGemmArgs& a) {
         if ((e = hipStreamWaitEvent(a.stream, a.list_event, 0)) != hipSuccess) return e;
     }
     if (!pl.streamk) return launch_mfma(a, 1, 0, 0);
-    const StreamKKernelRow* row = streamk_kernel(a.split ? 1 : 0, g_split_schedule, a.fused != nullptr, fused_R);
+    const StreamKKernelRow* row = streamk_kernel(a.split ? 1 : 0, g_split_schedule, gemm_split_stagger(), a.fused != nullptr, fused_R);
     if (row == nullptr) return hipErrorInvalidValue;
     const FusedB fb = a.fused != nullptr ? *a.fused : FusedB{};   // (no fused: fb.mat == nullptr, every B tile from fp32 rows)
     hipLaunchKernelGGL(row->kernel, dim3(pl.nblocks), dim3(512), row->lds_bytes, a.stream, a.A, a.lda, a.B, a.ldb, fb, a.C, pl.ldc,

@@ -37,6 +37,7 @@ struct GemmPlan {
     int64_t c_floats;
 };
 int set_gemm_force_dense(int enable);   // returns the previous setting (see gemm.hip)
+int set_gemm_split_stagger(int on);          // parent schedule with the block's wave halves staggered by role (default on); returns the previous value
 int set_gemm_split_schedule(int schedule);   // K-step schedule of the split score GEMM: 0 parent (default), 1 pipelined; returns the previous one
 int gemm_force_dense();
 // Device workspace of the stream-K plan (k_streamk_plan), laid out here and nowhere else:

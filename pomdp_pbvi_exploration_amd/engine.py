@@ -35,7 +35,7 @@ EXPORTS = [
     'pbvi_backup_fetch_compact', 'pbvi_host_alloc', 'pbvi_host_free', 'pbvi_debug_gemm_dense',
     'pbvi_backup_fetch_exchange_padded', 'pbvi_assemble_rows_store', 'pbvi_exchange_merge', 'pbvi_backup_run_fetch', 'pbvi_debug_alloc_limit', 'pbvi_debug_live_bytes', 'pbvi_engine_after_oom', 'pbvi_set_f64_screen', 'pbvi_set_fused_projection', 'pbvi_backup_fetch_row_hashes', 'pbvi_set_score_split',
     'pbvi_set_gamma_tiling', 'pbvi_gamma_tiling_plan', 'pbvi_q_values', 'pbvi_prune_dominated_masked',
-    'pbvi_rollout', 'pbvi_infotaxis', 'pbvi_rollout_infotaxis', 'pbvi_debug_split_schedule', 'pbvi_debug_slabs',
+    'pbvi_rollout', 'pbvi_infotaxis', 'pbvi_rollout_infotaxis', 'pbvi_debug_split_schedule', 'pbvi_debug_split_stagger', 'pbvi_debug_slabs',
     'pbvi_debug_slabs_fill', 'pbvi_env_set_frames', 'pbvi_env_set_table', 'pbvi_env_clear', 'pbvi_rollout_env',
     'pbvi_debug_score_probe', 'pbvi_debug_score_probe_fetch', 'pbvi_debug_refine_counts', 'pbvi_debug_value_max_route',
     'pbvi_upper_reset', 'pbvi_upper_append', 'pbvi_upper_count', 'pbvi_upper_bound', 'pbvi_upper_q',
@@ -100,6 +100,7 @@ def load_library(path: str = LIB_PATH):
         'pbvi_host_free': (None, [vp]),
         'pbvi_debug_gemm_dense': (C.c_int, [C.c_int]),
         'pbvi_debug_split_schedule': (C.c_int, [C.c_int]),
+        'pbvi_debug_split_stagger': (C.c_int, [C.c_int]),
         'pbvi_debug_slabs': (C.c_int64, [vp, vp, C.c_int64]),
         'pbvi_debug_slabs_fill': (C.c_int, [vp, C.c_int]),
         'pbvi_debug_score_probe': (C.c_int, [vp, C.c_int]),
@@ -233,6 +234,13 @@ def debug_split_schedule(schedule: str) -> str:
     previous schedule."""
     prev = int(load_library().pbvi_debug_split_schedule(SPLIT_SCHEDULES[schedule]))
     return {v: k for k, v in SPLIT_SCHEDULES.items()}[prev]
+
+
+def debug_split_stagger(on: bool) -> bool:
+    """Tests and A/B only: whether the parent schedule of the split score GEMM runs with its two wave halves staggered
+    by role (default on; bit-identical slabs).  Process-wide (``pbvi_debug_split_stagger``); returns the previous
+    value."""
+    return bool(load_library().pbvi_debug_split_stagger(1 if on else 0))
 
 
 def device_count() -> int:
