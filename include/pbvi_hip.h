@@ -374,6 +374,9 @@ int64_t pbvi_alpha_store_count(const pbvi_engine_t* e);
  * compares it with eps * gamma / (1 - gamma) (src/pomdp.py:2167-2169, :2372): exact = 0 skips the re-scoring and
  * returns the fp32 GEMM's maxima (relative error ~1e-7, within the 1e-6 bar of fp32 engines); indices are then the
  * fp32 argmax.  Default 1.  No effect on f64 engines.
+ * The setting covers those two calls only.  A backup with PBVI_BELIEF_DOMINANCE compares b.alpha'[b] > max_v b.alpha_v
+ * strictly (src/pomdp.py:1510-1512): its maxima are re-scored in fp64 whatever this setting says, so the keep mask does
+ * not depend on it (pbvi_debug_value_max_route reports route 2, or route 1, for that GEMM).
  */
 int pbvi_set_value_max_exact(pbvi_engine_t* e, int exact);
 

@@ -3364,7 +3364,7 @@ class EngineT : public EngineBase {
         }
         // K5: belief dominance (keep is written in caller order)
         if (c.flags & PBVI_BELIEF_DOMINANCE) {
-            if ((rc = value_max_device(resident()))) return rc;
+            if ((rc = value_max_device(resident(), true))) return rc;
             HIPCHK(launch_keep<T>(blk_.rows.as<T>(), S_pad_, fin_.rows.as<T>(), S_, (int)blk_.B, S_, bs2_.as<double>(), fin_.inv.as<int32_t>(),
                                   blk_.sorted ? blk_.perm.as<int32_t>() : nullptr, keep_.as<uint8_t>(), stream_));
         } else {
@@ -3754,8 +3754,9 @@ class EngineT : public EngineBase {
         const int32_t *btl, *btc;
     };
     Operand resident() const { return {blk_.rows.as<T>(), blk_.B, blk_.nzA.as<uint8_t>(), nullptr, nullptr}; }
-    // exact (f64-refined) max_v b.alpha_v of the operand's rows into bs2_/bv2_
-    int value_max_device(const Operand& x);
+    // exact (f64-refined) max_v b.alpha_v of the operand's rows into bs2_/bv2_.  need_exact: the caller compares the maxima
+    // strictly (K5's keep mask), so an f32 engine re-scores them in fp64 whatever pbvi_set_value_max_exact says
+    int value_max_device(const Operand& x, bool need_exact = false);
     void note_vmax_route(int route, int bn, int k_parts, int64_t rows, int64_t pairs) {
         vmax_route_[0] = route;
         vmax_route_[1] = bn;
@@ -4016,7 +4017,8 @@ class EngineT : public EngineBase {
     }
     // f32 engines: value_max / value_max_store return the fp32 GEMM's maxima as they are (relative error of the order
     // of 1e-7, bounded by the tie window) instead of re-scoring every belief's candidates in fp64.  For callers that
-    // only compare values against a tolerance (compute_change); argmax users keep the default.
+    // only compare values against a tolerance (compute_change); argmax users keep the default.  K5 of a backup is not
+    // covered: it passes need_exact to value_max_device.
     int set_value_max_exact(int exact) override {
         vmax_exact_ = exact != 0;
         return PBVI_OK;
@@ -4202,7 +4204,7 @@ int EngineT<T>::project_dense(double gamma) {
 }
 
 template <typename T>
-int EngineT<T>::value_max_device(const Operand& x) {
+int EngineT<T>::value_max_device(const Operand& x, bool need_exact) {
     int rc;
     const int64_t B = x.B;
     const int64_t Vt = al_.V + 1;   // + magnitude row
@@ -4239,8 +4241,9 @@ int EngineT<T>::value_max_device(const Operand& x) {
     if ((rc = score_gemm(al_.rows(), Vt, nullptr, 1, (int)al_.V, &sv, x.rows, B, x.nzA))) return rc;
     const int k_chunk = kF32 ? plan_.chunk_len * GEMM_BK : S_pad_;
     // every belief is re-scored exactly in f32 engines (flag_all): the comparison that
-    // follows (new value > old best value) is strict and must not see GEMM rounding
-    const bool rescore = kF32 && vmax_exact_;
+    // follows (new value > old best value) is strict and must not see GEMM rounding.  pbvi_set_value_max_exact(0)
+    // lifts that for pbvi_value_max / pbvi_value_max_store only: K5 (need_exact) keeps it
+    const bool rescore = kF32 && (vmax_exact_ || need_exact);
     HIPCHK(launch_argmax<T>(sv, (int)al_.V, 1, (int)B, nullptr, tie_window(k_chunk), 0.0, chain_steps(), 1, bv2_.as<int32_t>(),
                             bs2_.as<double>(), err2_.as<double>(), rescore ? queue2_.as<int32_t>() : nullptr, qc, stream_));
     if (rescore) {

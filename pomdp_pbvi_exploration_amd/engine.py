@@ -744,7 +744,8 @@ class Engine:
         return True
 
     def set_value_max_exact(self, exact: bool) -> None:
-        """f32 engines: fp64 re-scoring of ``max_value_*`` results on (default) or off (``pbvi_set_value_max_exact``)."""
+        """f32 engines: fp64 re-scoring of ``max_value_*`` results on (default) or off (``pbvi_set_value_max_exact``).  The
+        ``keep`` mask of a belief-dominance backup does not depend on it: K5 always compares against re-scored maxima."""
         self._ck(self._lib.pbvi_set_value_max_exact(self._h, 1 if exact else 0))
 
     def max_value_objects(self, alpha_objects, belief_objects, alpha_values, belief_values, alpha_owner=None,

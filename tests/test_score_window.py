@@ -6,6 +6,8 @@ already right.  The score probe (``Engine.debug_score_probe``) captures, at the 
 refinement, what ``k_argmax`` read (scores, magnitudes, through its own slab view) and wrote (windows, first maxima,
 queue).  For every pipeline and input family below:
 
+0. dead map   the probe's dead triples are supp(b) n supp(RTO[:, a, o, :]) = {} on the inputs as the engine holds them
+              (``mask_cases.dead_ref``), before anything below is restricted to the live ones;
 1. values     |score_dev - score_ref| <= E_dev  (pure fp64: <= (n + 2) 2^-53 mag_ref, n = non-zero products of the dot);
 2. window     E_dev is the documented formula applied to the reference's magnitude, within its own relative width;
 3. argmax     from score_dev and E_dev alone, ``ref_argmax`` reproduces best_v and best_score bit for bit and the set of
@@ -21,6 +23,7 @@ import functools
 import numpy as np
 import pytest
 
+from mask_cases import dead_ref
 from oracle import pbvi_oracle as orc
 
 U24 = 2.0 ** -24
@@ -211,6 +214,7 @@ class Case:
         self.er = f32r(np.random.default_rng(S + A).normal(size=(S, A)))
         self.scores = ref_scores(alpha, b, rs, rto, GAMMA, np.longdouble if longdouble else np.float64)
         self.mag = ref_magnitude(alpha, b, rs, rto, GAMMA)
+        self.dead = dead_ref(b, rto)                         # [B][G]: the dead-triple map from its definition
         assert np.isfinite(self.scores.astype(np.float64)).all()
 
     def engine(self, dtype, mode='sparse'):
@@ -395,6 +399,9 @@ def check_capture(p, case, tag, pure_f64=False, gamma=GAMMA):
     ref = case.scores[perm] if gamma == GAMMA else ref_scores(case.alpha, case.b, case.rs, case.rto, gamma)[perm]
     mag_ref = case.mag[perm] if gamma == GAMMA else ref_magnitude(case.alpha, case.b, case.rs, case.rto, gamma)[perm]
     dev, E, dead = p['score'], p['E'], p['dead'].astype(bool)
+    if not pure_f64:                                         # the map is checked, not trusted: everything below runs on `live`
+        wrong = np.argwhere(dead != case.dead[perm])
+        assert wrong.size == 0, (tag, 'dead map differs at (engine row, group)', wrong[:10].tolist())
     live = ~dead
     assert np.isfinite(dev).all() and np.isfinite(E).all(), tag
     err = np.abs((dev.astype(ref.dtype) - ref)).astype(np.float64)
