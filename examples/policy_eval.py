@@ -9,6 +9,8 @@ The reference publishes one timing for this step (sim_runtime_test.ipynb:223, BA
     python examples/policy_eval.py --policy infotaxis --device-sim 7   # the infotaxis baseline (no solve), on the device
     python examples/policy_eval.py --policy space-aware --device-sim 7   # space-aware infotaxis (pbvi_rollout_space_aware)
     python examples/policy_eval.py --policy expected-distance --device-sim 7   # greedy for the expected distance to the source
+    python examples/policy_eval.py --policy fib --reach 5 --device-sim 7   # follow the Fast Informed Bound's rows (no FSVI solve)
+    python examples/policy_eval.py --policy qmdp --reach 5 --device-sim 7  # ... or the MDP solution's (QMDP)
     python examples/policy_eval.py --device-sim 1 --environment frames    # observations from recorded frames (pbvi_rollout_env)
     python examples/policy_eval.py --device-sim 1 --environment table --env-flip 0.1   # a sensor that errs 10 % more often
 """
@@ -21,7 +23,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
-from pomdp_pbvi_exploration_amd import FSVI_Solver, Model, set_quiet, synth   # noqa: E402
+from pomdp_pbvi_exploration_amd import FIB_Solver, FSVI_Solver, Model, set_quiet, synth   # noqa: E402
 from pomdp_pbvi_exploration_amd.pomdp import (Agent, FrameEnvironment, Infotaxis_Agent, SpaceAware_Agent,   # noqa: E402
                                               TableEnvironment, record_frames)
 from pomdp_pbvi_exploration_amd.mdp import VI_Solver                         # noqa: E402
@@ -43,8 +45,9 @@ def main():
     ap.add_argument('--device-sim', type=int, default=None, metavar='SEED',
                     help='counter-based simulator draws with this seed: the whole step loop runs in the engine '
                          '(pbvi_rollout) instead of drawing on the host from NumPy\'s stream')
-    ap.add_argument('--policy', default='value', choices=['value', 'infotaxis', 'space-aware', 'expected-distance'],
-                    help='value: solve with FSVI and follow the value function; infotaxis: no solve, every step takes the '
+    ap.add_argument('--policy', default='value', choices=['value', 'infotaxis', 'space-aware', 'expected-distance', 'qmdp', 'fib'],
+                    help='value: solve with FSVI and follow the value function; qmdp / fib: no FSVI solve, follow the A rows of '
+                         'MDP value iteration / of the Fast Informed Bound (pbvi_fib_value_iteration); infotaxis: no solve, every step takes the '
                          'action with the smallest expected entropy of the next belief (pbvi_infotaxis); space-aware: no '
                          'solve, greedy for log2(D + 2^(H-1) - 1/2) of the next belief, D its expected Manhattan distance to '
                          'the source and H its entropy in bits (pbvi_space_aware); expected-distance: greedy for D alone')
@@ -75,6 +78,17 @@ def main():
         agent = SpaceAware_Agent(model.to_gpu(args.dtype), weights=distance,
                                  objective='space_aware' if args.policy == 'space-aware' else 'expected_weight')
         policy = args.policy
+    elif args.policy in ('qmdp', 'fib'):
+        t0 = time.perf_counter()
+        vf, h = VI_Solver(gamma=m.gamma, eps=1e-6).solve(model, use_gpu=True, print_progress=False)
+        policy = f'qmdp ({len(h.iteration_times)} sweeps)'
+        if args.policy == 'fib':
+            vf, h = FIB_Solver(gamma=m.gamma, eps=1e-6).solve(model, mdp_solution=vf, use_gpu=True, print_progress=False)
+            policy += f' + fib ({len(h.iteration_times)} sweeps)'
+        print(f'{policy}: {len(vf)} rows in {time.perf_counter() - t0:.3f}s', flush=True)
+        model.to_gpu(args.dtype)
+        vf = vf.to_gpu()
+        agent = Agent(vf.model, vf, lookahead=args.lookahead, gamma=m.gamma)
     else:
         # MDP value iteration that seeds FSVI: device sweeps vs the host NumPy loop (same result, see tests)
         t0 = time.perf_counter()
@@ -85,6 +99,17 @@ def main():
         t_host = time.perf_counter() - t0
         print(f'value iteration: {len(h_dev.iteration_times)} sweeps  device {t_dev:.3f}s  host NumPy {t_host:.3f}s  '
               f'identical rows: {np.array_equal(mdp_dev.alpha_vector_array, mdp_host.alpha_vector_array)}', flush=True)
+
+        # the Fast Informed Bound from that solution: the device entry against its NumPy restatement (the same rows for
+        # R = 1, where FIB is the MDP solution again after a sweep or two; a tighter bound with --reach 5)
+        t0 = time.perf_counter()
+        fib_dev, f_dev = FIB_Solver(gamma=m.gamma, eps=1e-6).solve(model, mdp_solution=mdp_dev, use_gpu=True, print_progress=False)
+        t_dev = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        fib_host, _ = FIB_Solver(gamma=m.gamma, eps=1e-6).solve(model, mdp_solution=mdp_dev, use_gpu=False, print_progress=False)
+        t_host = time.perf_counter() - t0
+        print(f'fast informed bound: {len(f_dev.iteration_times)} sweeps  device {t_dev:.3f}s  host NumPy {t_host:.3f}s  '
+              f'identical rows: {np.array_equal(fib_dev.alpha_vector_array, fib_host.alpha_vector_array)}', flush=True)
 
         np.random.seed(0)
         random.seed(0)
@@ -131,7 +156,7 @@ def main():
         elif args.policy in ('space-aware', 'expected-distance'):
             host_agent = SpaceAware_Agent(model, weights=agent.weights, objective=agent.objective)
         else:
-            host_agent = Agent(model, vf.to_cpu(), lookahead=args.lookahead, gamma=m.gamma)
+            host_agent = Agent(model, vf.to_cpu(), lookahead=args.lookahead, gamma=m.gamma)   # (value, qmdp, fib)
         np.random.seed(1)
         t0 = time.perf_counter()
         _, hh = host_agent.run_n_simulations_parallel(n=args.n, max_steps=args.cpu_steps, print_progress=False,

@@ -688,6 +688,29 @@ int pbvi_mdp_value_iteration(int device, int32_t S, int32_t A, int32_t R, const 
                              int32_t* out_iterations);
 
 /*
+ * Fast Informed Bound on the device (Hauskrecht 2000; FIB_Solver.solve, the initial upper bound of HSVI with
+ * upper_init='fib'): the MDP sweep with the observation kept inside the maximisation,
+ *   Q'[s][a] = ER[s,a] + gamma * sum_o max_a' sum_r RTO[s,a,o,r] * Q[rs[s,a,r]][a']
+ * repeated from q0 until max_{s,a} |Q' - Q| < max_change_limit (eps * gamma / (1 - gamma)) or `horizon` sweeps.  From the
+ * same start it is never above the MDP rows (sum_o RTO = P) and still an upper bound of the POMDP value; with one
+ * successor per (s, a) it equals them.  Always fp64.  Not tied to an engine handle.
+ * One sweep, operation for operation (products and sums un-fused; pomdp.fib_numpy is the same statement in NumPy, and
+ * rows and changes agree with it bit for bit on finite inputs):
+ *   for o = 0..O-1:  acc[a'] = RTO[s,a,o,0] * Q[rs[s,a,0]][a'], then acc[a'] += RTO[s,a,o,r] * Q[rs[s,a,r]][a'], r = 1..R-1;
+ *                    m_o = max_a' acc[a'];   tot = m_0, then tot += m_o in order;
+ *   Q'[s][a] = ER[s,a] + gamma * tot.
+ *   reach_states [S][A][R] int32, rto [S][A][O][R], exp_reward [S][A], q0 [A][S]   (NumPy C-order)
+ *   out_rows [A][S]: the rows of the last sweep that ran (A action-labelled alpha-vectors); q0 itself for horizon = 0
+ *   out_changes [horizon] (may be NULL): max change of each sweep that ran;  out_iterations (may be NULL).
+ * PBVI_EINVAL (bad sizes, NULL tables, a negative horizon, a reachable state outside [0, S)) and PBVI_EUNSUPPORTED
+ * (S*A*O*R beyond int32) are decided before the device is touched.
+ */
+int pbvi_fib_value_iteration(int device, int32_t S, int32_t A, int32_t O, int32_t R, const int32_t* reach_states,
+                             const double* rto, const double* exp_reward, const double* q0, double gamma,
+                             double max_change_limit, int32_t horizon, double* out_rows, double* out_changes,
+                             int32_t* out_iterations);
+
+/*
  * Belief walk of the FSVI-style expansions (PBVI_Solver.expand_fsvi / expand_fsvi_eg, src/pomdp.py:1895-1935; the
  * trajectory of (action, observation) pairs is simulated by the caller in the underlying MDP and does not depend
  * on the beliefs): n chained Bayes updates (Belief.update, :382-421) entirely on the device, in fp64,

@@ -4897,6 +4897,169 @@ static int mdp_value_iteration(int device, int S, int A, int R, const int32_t* r
     return PBVI_OK;
 }
 
+// --------------------------------------------------------------------------- //
+// Fast Informed Bound (Hauskrecht 2000): the MDP sweep with the observation kept inside the maximisation,
+//   Q'(s,a) = ER[s,a] + gamma * sum_o max_a' sum_r RTO[s,a,o,r] * Q(rs[s,a,r], a')
+// One thread per (s, a), s fastest across lanes; tables re-tiled rs [A][R][S], rto [A][O][R][S], er [A][S] so every
+// table load is coalesced.  The two Q buffers are state-major [S][A]: the action values of one successor are one
+// contiguous segment, gathered R times per (o, tile) (the repeats hit cache).  a' runs in register tiles of TW
+// accumulators with the running maximum carried across tiles; the tail tile is bounded, never padded (0 * -inf).
+// PAIRS: A is even, so every segment starts 16-byte aligned and no tile ends inside a pair: double2 loads.
+// The order of every product and sum is the one pomdp.fib_numpy states, un-fused, so both agree bit for bit on
+// finite inputs.  Early exit and change reduction as in k_vi_sweep.
+// --------------------------------------------------------------------------- //
+template <int TW, bool PAIRS>
+__global__ __launch_bounds__(256) void k_fib_sweep(int S, int A, int O, int R, int s_blocks, const int32_t* __restrict__ rs,
+                                                   const double* __restrict__ rto, const double* __restrict__ er,
+                                                   double gamma, double limit, int it, const double* __restrict__ q_in,
+                                                   double* __restrict__ q_out, double* __restrict__ changes) {
+#pragma clang fp contract(off)   // no FMA fusion: every product and sum rounds like NumPy's separate ufuncs
+    if (it > 0 && changes[it - 1] < limit) return;
+    __shared__ double red[4];
+    const int a = blockIdx.x / s_blocks;
+    const int s = (blockIdx.x - a * s_blocks) * 256 + threadIdx.x;
+    double diff = 0.0;
+    if (s < S) {
+        const int32_t* rs_a = rs + (int64_t)a * R * S + s;
+        double tot = 0.0;
+        for (int o = 0; o < O; ++o) {
+            const double* rto_ao = rto + ((int64_t)a * O + o) * R * S + s;
+            double m = 0.0;                                     // (set by the first accumulator, never compared before)
+            for (int a0 = 0; a0 < A; a0 += TW) {
+                const int n = min(TW, A - a0);
+                double acc[TW];
+                for (int r = 0; r < R; ++r) {
+                    const double p = rto_ao[(int64_t)r * S];
+                    const double* q = q_in + (int64_t)rs_a[(int64_t)r * S] * A + a0;
+                    double v[TW];
+                    if constexpr (PAIRS) {
+#pragma unroll
+                        for (int j = 0; j < TW; j += 2)
+                            if (j < n) {
+                                const double2 t = *reinterpret_cast<const double2*>(q + j);
+                                v[j] = t.x;
+                                v[j + 1] = t.y;
+                            }
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < TW; ++j)
+                            if (j < n) v[j] = q[j];
+                    }
+#pragma unroll
+                    for (int j = 0; j < TW; ++j)
+                        if (j < n) {
+                            const double t = p * v[j];
+                            acc[j] = r == 0 ? t : acc[j] + t;
+                        }
+                }
+#pragma unroll
+                for (int j = 0; j < TW; ++j)
+                    if (j < n) m = (a0 + j == 0 || acc[j] > m) ? acc[j] : m;
+            }
+            tot = o == 0 ? m : tot + m;
+        }
+        const double scaled = gamma * tot;
+        const double q_new = er[(int64_t)a * S + s] + scaled;
+        q_out[(int64_t)s * A + a] = q_new;
+        diff = fabs(q_new - q_in[(int64_t)s * A + a]);
+    }
+    // block max, then one atomic per block (non-negative doubles order like their bit patterns)
+    for (int off = 32; off > 0; off >>= 1) diff = fmax(diff, __shfl_xor(diff, off));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = diff;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double mx = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+        atomicMax(reinterpret_cast<unsigned long long*>(&changes[it]), (unsigned long long)__double_as_longlong(mx));
+    }
+}
+
+static int fib_value_iteration(int device, int S, int A, int O, int R, const int32_t* rs, const double* rto, const double* er,
+                               const double* q0, double gamma, double limit, int horizon, double* out_rows,
+                               double* out_changes, int32_t* out_iterations) {
+    if (S <= 0 || A <= 0 || O <= 0 || R <= 0 || horizon < 0 || !rs || !rto || !er || !q0 || !out_rows)
+        FAIL(PBVI_EINVAL, "fib_value_iteration: bad arguments");
+    if ((int64_t)S * A * O * R > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "fib_value_iteration: S*A*O*R exceeds int32");
+    const size_t n_rs = (size_t)S * A * R, n_rto = n_rs * O, n_q = (size_t)S * A;
+    std::vector<int32_t> h_rs(n_rs);
+    std::vector<double> h_rto(n_rto), h_er(n_q), h_q(n_q);
+    for (int s = 0; s < S; ++s)
+        for (int a = 0; a < A; ++a) {
+            h_er[(size_t)a * S + s] = er[(size_t)s * A + a];
+            h_q[(size_t)s * A + a] = q0[(size_t)a * S + s];
+            for (int r = 0; r < R; ++r) {
+                const size_t src = ((size_t)s * A + a) * R + r;
+                if (rs[src] < 0 || rs[src] >= S) FAIL(PBVI_EINVAL, "fib_value_iteration: reachable state out of range");
+                h_rs[((size_t)a * R + r) * S + s] = rs[src];
+            }
+            for (int o = 0; o < O; ++o)
+                for (int r = 0; r < R; ++r)
+                    h_rto[(((size_t)a * O + o) * R + r) * S + s] = rto[(((size_t)s * A + a) * O + o) * R + r];
+        }
+    if (horizon == 0) {                                      // nothing to sweep: q0 comes back as it is
+        memcpy(out_rows, q0, n_q * sizeof(double));
+        if (out_iterations) *out_iterations = 0;
+        return PBVI_OK;
+    }
+    HIPCHK(hipSetDevice(device));
+    struct Guard {                                           // (in front of the buffers: they are released first)
+        hipStream_t st = nullptr;
+        ~Guard() {
+            if (st) (void)hipStreamDestroy(st);
+        }
+    } guard;
+    DevMem mem;
+    DevBuf d_rs{mem}, d_rto{mem}, d_er{mem}, d_q[2]{{mem}, {mem}}, d_ch{mem};
+    int rc;
+    if ((rc = d_rs.ensure(n_rs * sizeof(int32_t)))) return rc;
+    if ((rc = d_rto.ensure(n_rto * sizeof(double)))) return rc;
+    if ((rc = d_er.ensure(n_q * sizeof(double)))) return rc;
+    if ((rc = d_q[0].ensure(n_q * sizeof(double)))) return rc;
+    if ((rc = d_q[1].ensure(n_q * sizeof(double)))) return rc;
+    if ((rc = d_ch.ensure((size_t)horizon * sizeof(double)))) return rc;
+    HIPCHK(hipStreamCreateWithFlags(&guard.st, hipStreamNonBlocking));
+    hipStream_t st = guard.st;
+    HIPCHK(hipMemcpyAsync(d_rs.p, h_rs.data(), n_rs * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_rto.p, h_rto.data(), n_rto * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_er.p, h_er.data(), n_q * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_q[0].p, h_q.data(), n_q * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_ch.p, 0, (size_t)horizon * sizeof(double), st));
+    auto sweep = A <= 4 ? (A % 2 == 0 ? k_fib_sweep<4, true> : k_fib_sweep<4, false>)
+                        : (A % 2 == 0 ? k_fib_sweep<8, true> : k_fib_sweep<8, false>);
+    const int s_blocks = (S + 255) / 256;                    // (s_blocks * A <= S * A <= int32)
+    std::vector<double> ch((size_t)horizon, 0.0);
+    int done = 0;              // sweeps that ran
+    bool converged = false;
+    const int batch = 64;
+    for (int it0 = 0; it0 < horizon && !converged; it0 += batch) {
+        const int it1 = std::min(horizon, it0 + batch);
+        for (int it = it0; it < it1; ++it) {
+            hipLaunchKernelGGL(sweep, dim3((unsigned)(s_blocks * A)), dim3(256), 0, st, S, A, O, R, s_blocks,
+                               d_rs.as<int32_t>(), d_rto.as<double>(), d_er.as<double>(), gamma, limit, it,
+                               d_q[it & 1].as<double>(), d_q[(it + 1) & 1].as<double>(), d_ch.as<double>());
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(ch.data() + it0, d_ch.as<double>() + it0, (size_t)(it1 - it0) * sizeof(double),
+                              hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int it = it0; it < it1; ++it) {
+            done = it + 1;
+            if (ch[(size_t)it] < limit) {
+                converged = true;
+                break;
+            }
+        }
+    }
+    // sweep done-1 was the last to write: its Q is in buffer done & 1 (the sweeps enqueued after it left at once)
+    HIPCHK(hipMemcpyAsync(h_q.data(), d_q[done & 1].p, n_q * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int s = 0; s < S; ++s)
+        for (int a = 0; a < A; ++a) out_rows[(size_t)a * S + s] = h_q[(size_t)s * A + a];
+    if (out_changes)
+        for (int it = 0; it < done; ++it) out_changes[it] = ch[(size_t)it];
+    if (out_iterations) *out_iterations = done;
+    return PBVI_OK;
+}
+
 }  // namespace pbvi
 
 // --------------------------------------------------------------------------- //
@@ -5400,6 +5563,14 @@ int pbvi_mdp_value_iteration(int device, int32_t S, int32_t A, int32_t R, const 
                              double max_change_limit, int32_t horizon, double* out_rows, double* out_changes,
                              int32_t* out_iterations) {
     return pbvi::mdp_value_iteration(device, S, A, R, reach_states, reach_prob, exp_reward, v0, gamma, max_change_limit,
+                                     horizon, out_rows, out_changes, out_iterations);
+}
+
+int pbvi_fib_value_iteration(int device, int32_t S, int32_t A, int32_t O, int32_t R, const int32_t* reach_states,
+                             const double* rto, const double* exp_reward, const double* q0, double gamma,
+                             double max_change_limit, int32_t horizon, double* out_rows, double* out_changes,
+                             int32_t* out_iterations) {
+    return pbvi::fib_value_iteration(device, S, A, O, R, reach_states, rto, exp_reward, q0, gamma, max_change_limit,
                                      horizon, out_rows, out_changes, out_iterations);
 }
 

@@ -40,6 +40,7 @@ EXPORTS = [
     'pbvi_debug_score_probe', 'pbvi_debug_score_probe_fetch', 'pbvi_debug_refine_counts', 'pbvi_debug_value_max_route',
     'pbvi_upper_reset', 'pbvi_upper_append', 'pbvi_upper_count', 'pbvi_upper_bound', 'pbvi_upper_q',
     'pbvi_state_weights_set', 'pbvi_state_weights_clear', 'pbvi_space_aware', 'pbvi_rollout_space_aware',
+    'pbvi_fib_value_iteration',
 ]
 
 
@@ -152,6 +153,8 @@ def load_library(path: str = LIB_PATH):
         'pbvi_beliefs_fetch': (C.c_int, [vp, vp]),
         'pbvi_beliefs_count': (C.c_int64, [vp]),
         'pbvi_mdp_value_iteration': (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, i32p, f64p, f64p, f64p,
+                                               C.c_double, C.c_double, C.c_int32, f64p, f64p, i32p]),
+        'pbvi_fib_value_iteration': (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i32p, f64p, f64p, f64p,
                                                C.c_double, C.c_double, C.c_int32, f64p, f64p, i32p]),
         'pbvi_set_formulation': (C.c_int, [vp, C.c_int]),
         'pbvi_set_f64_screen': (C.c_int, [vp, C.c_int]),
@@ -317,6 +320,41 @@ def mdp_value_iteration(reach_states: np.ndarray, reach_prob: np.ndarray, exp_re
     its = C.c_int32(0)
     _check(lib.pbvi_mdp_value_iteration(int(device), S, A, R, _p(rs, C.c_int32), _p(p, C.c_double), _p(er, C.c_double),
                                         _p(v, C.c_double), float(gamma), float(max_change_limit), int(horizon),
+                                        _p(rows, C.c_double), _p(changes, C.c_double), C.byref(its)))
+    return rows, changes[:its.value]
+
+
+def fib_value_iteration(reach_states: np.ndarray, rto: np.ndarray, exp_reward: np.ndarray, q0: np.ndarray,
+                        gamma: float, max_change_limit: float, horizon: int, device: int = 0):
+    """Fast Informed Bound sweeps on the device (``pbvi_fib_value_iteration``; ``pomdp.fib_numpy`` is the same definition
+    on the host, bit for bit).  ``reach_states [S,A,R]``, ``rto [S,A,O,R]``, ``exp_reward [S,A]``, ``q0 [A,S]``.
+    Returns ``(rows [A,S] f64, changes [iterations] f64)``.  Shapes, the horizon and the successor range are checked
+    before the device is touched (``ValueError``); ``S*A*O*R`` beyond int32 is ``NotImplementedError``."""
+    lib = load_library()
+    reach_states, rto = np.asarray(reach_states), np.asarray(rto)
+    if reach_states.ndim != 3 or rto.ndim != 4:
+        raise ValueError('fib_value_iteration: reach_states must be [S,A,R] and rto [S,A,O,R]')
+    S, A, R = reach_states.shape
+    O = rto.shape[2]
+    if rto.shape != (S, A, O, R) or np.shape(exp_reward) != (S, A) or np.shape(q0) != (A, S):
+        raise ValueError('fib_value_iteration: table shapes do not agree')
+    if min(S, A, O, R) <= 0:
+        raise ValueError('fib_value_iteration: empty tables')
+    if int(horizon) < 0:
+        raise ValueError('fib_value_iteration: negative horizon')
+    if S * A * O * R > 0x7fffffff:                       # (before any table is copied: the entry refuses it the same way)
+        raise NotImplementedError('fib_value_iteration: S*A*O*R exceeds int32')
+    if int(reach_states.min()) < 0 or int(reach_states.max()) >= S:
+        raise ValueError('reachable state out of range')
+    rs = np.ascontiguousarray(reach_states, dtype=np.int32)
+    t = np.ascontiguousarray(rto, dtype=np.float64)
+    er = np.ascontiguousarray(exp_reward, dtype=np.float64)
+    q = np.ascontiguousarray(q0, dtype=np.float64)
+    rows = np.empty((A, S), dtype=np.float64)
+    changes = np.zeros(max(int(horizon), 1), dtype=np.float64)
+    its = C.c_int32(0)
+    _check(lib.pbvi_fib_value_iteration(int(device), S, A, O, R, _p(rs, C.c_int32), _p(t, C.c_double), _p(er, C.c_double),
+                                        _p(q, C.c_double), float(gamma), float(max_change_limit), int(horizon),
                                         _p(rows, C.c_double), _p(changes, C.c_double), C.byref(its)))
     return rows, changes[:its.value]
 

@@ -1249,23 +1249,145 @@ class HSVI_Solver(PBVI_Solver):
     support of each point (``sawtooth_numpy``), on the engine when the solve runs on the GPU (``expand_hsvi``)."""
 
     def __init__(self, gamma: float = 0.99, eps: float = 0.001, mdp_solution: Union[ValueFunction, None] = None,
-                 sawtooth: str = 'reference'):
+                 sawtooth: str = 'reference', upper_init: str = 'mdp'):
         if sawtooth not in ('reference', 'support'):
             raise ValueError("sawtooth must be 'reference' or 'support'")
+        if upper_init not in ('mdp', 'fib'):
+            raise ValueError("upper_init must be 'mdp' or 'fib'")
         extra = {} if sawtooth == 'reference' else {'sawtooth': sawtooth}
         super().__init__(gamma, eps, 'hsvi', mdp_policy=mdp_solution, **extra)
+        self.upper_init = upper_init
+        self._fib_tightened = False
 
     def solve(self, model, expansions, max_belief_growth: int = 10, initial_belief=None, initial_value_function=None,
               prune_level: int = 1, prune_interval: int = 10, limit_value_function_size: int = -1, use_gpu: bool = False,
               history_tracking_level: int = 1, print_progress: bool = True, engine_dtype: str = 'f64'):
         """``PBVI_Solver.solve`` with ``full_backup=False`` and one update pass.  ``prune_level=2, prune_interval=1`` is
-        cheap: a level-2 prune after the first tests only the pairs that involve the rows the backup added."""
+        cheap: a level-2 prune after the first tests only the pairs that involve the rows the backup added.
+
+        ``upper_init='fib'``: the MDP solution (the given one, or the one ``PBVI_Solver.solve`` would compute) passes
+        through ``FIB_Solver`` once, on the device when ``use_gpu``, before it becomes the corner value function of the
+        upper bound: corner values that are never above the MDP's."""
+        if self.upper_init == 'fib' and not self._fib_tightened:
+            mdp_solution = self.expand_function_params.get('mdp_policy')
+            if mdp_solution is None:
+                log('[Warning] MDP solution not provided, running value iteration on the problem to retrieve it...')
+                mdp_solution, _ = VI_Solver(gamma=self.gamma, eps=self.eps).solve(
+                    model, use_gpu=use_gpu and model.reachable_state_count == 1, print_progress=False)
+            self.expand_function_params['mdp_policy'], _ = FIB_Solver(gamma=self.gamma, eps=self.eps).solve(
+                model, mdp_solution=mdp_solution, use_gpu=use_gpu, print_progress=False)
+            self._fib_tightened = True
         return super().solve(model=model, expansions=expansions, full_backup=False, update_passes=1,
                              max_belief_growth=max_belief_growth, initial_belief=initial_belief,
                              initial_value_function=initial_value_function, prune_level=prune_level,
                              prune_interval=prune_interval, limit_value_function_size=limit_value_function_size,
                              use_gpu=use_gpu, history_tracking_level=history_tracking_level,
                              print_progress=print_progress, engine_dtype=engine_dtype)
+
+
+# --------------------------------------------------------------------------- #
+# Fast Informed Bound (Hauskrecht 2000): the definition ``pbvi_fib_value_iteration`` implements, restated with NumPy
+# --------------------------------------------------------------------------- #
+def _fib_tables(model):
+    """``(reachable_states [S,A,R], rto [S,A,O,R], expected_rewards [S,A])`` of a ``Model``, of any object with ``Model``'s
+    attribute names, or of a ``synth.SynthModel``."""
+    if hasattr(model, 'reachable_transitional_observation_table'):
+        m = model.cpu_model if getattr(model, 'is_on_gpu', False) else model
+        return (np.asarray(m.reachable_states), np.asarray(m.reachable_transitional_observation_table, dtype=np.float64),
+                np.asarray(m.expected_rewards_table, dtype=np.float64))
+    return (np.asarray(model.reachable_states), np.asarray(model.rto, dtype=np.float64),
+            np.asarray(model.expected_rewards, dtype=np.float64))
+
+
+def fib_numpy(model, q0, gamma: float, max_change_limit: float, horizon: int):
+    """Fast Informed Bound sweeps from ``q0 [A,S]``:
+
+        Q'(s,a) = ER[s,a] + gamma * sum_o max_a' sum_r RTO[s,a,o,r] * Q(rs[s,a,r], a')
+
+    until ``max_{s,a} |Q' - Q| < max_change_limit`` or ``horizon`` sweeps; returns ``(rows [A,S], changes)``, the rows of
+    the last sweep that ran (``q0`` for ``horizon = 0``).  The loops over o and r are explicit so that every sum associates
+    as the device kernel's does -- ``acc = t_0``, then ``acc = acc + t_r``; ``tot = m_0``, then ``tot = tot + m_o`` -- and
+    the two agree bit for bit on finite inputs.  Working memory: S * A * A doubles per observation.
+
+    From the same start a sweep is never above the MDP sweep (``sum_o RTO = P``, and ``max_a' sum_r RTO Q(., a')`` is at most
+    ``sum_r RTO max_a' Q(., a')``), it stays an upper bound of the POMDP value, and with one successor per (s, a) the maximum
+    moves inside the sum over o and the sweep IS the MDP sweep."""
+    rs, rto, er = _fib_tables(model)
+    S, A, O, R = rto.shape
+    Q = np.ascontiguousarray(np.asarray(q0, dtype=np.float64).T)           # [S,A]: a successor's action values are one row
+    if Q.shape != (S, A) or rs.shape != (S, A, R) or er.shape != (S, A):
+        raise ValueError('fib_numpy: table shapes do not agree')
+    changes = []
+    for _ in range(int(horizon)):
+        tot = None
+        for o in range(O):
+            acc = None
+            for r in range(R):
+                t = rto[:, :, o, r][:, :, None] * Q[rs[:, :, r]]         # [S,A,A']
+                acc = t if acc is None else acc + t
+            m = np.max(acc, axis=2)
+            tot = m if tot is None else tot + m
+        new = er + gamma * tot
+        change = float(np.max(np.abs(new - Q)))
+        Q = new
+        changes.append(change)
+        if change < max_change_limit:
+            break
+    return np.ascontiguousarray(Q.T), np.array(changes, dtype=np.float64)
+
+
+class FIB_Solver(Solver):
+    """The Fast Informed Bound as a solver: ``solve`` returns A action-labelled rows of length S, the shape of a policy, so
+    the result runs through ``ValueFunction``, ``Agent``, rollouts, ``FSVI_Solver(mdp_policy=...)`` and
+    ``HSVI_Solver(mdp_solution=...)`` like the MDP solution does -- as a tighter upper bound wherever moves are
+    stochastic, and as the same rows where every (s, a) has one successor."""
+
+    def __init__(self, horizon: int = 10000, gamma: float = 0.99, eps: float = 0.001):
+        self.horizon = horizon
+        self.gamma = gamma
+        self.eps = eps
+
+    def solve(self, model: Model, mdp_solution: Union[ValueFunction, None] = None, use_gpu: bool = False,
+              history_tracking_level: int = 1, print_progress: bool = True):
+        """Sweeps from ``q0[a] = max over the rows of mdp_solution`` for every a (``VI_Solver`` runs when none is given):
+        the first sweep then reproduces the MDP rows and every later one can only lower them.  The start reads the
+        maximum over the rows, so it does not depend on how ``ValueFunction`` folded equal rows.  The change limit is
+        ``eps * gamma / (1 - gamma)`` as in ``VI_Solver``.  ``use_gpu=True`` runs ``pbvi_fib_value_iteration`` and raises when
+        the HIP library or the GPU is missing."""
+        from .mdp import SolverHistory as MDP_SolverHistory
+        host = model.cpu_model
+        if mdp_solution is None:
+            # (device VI sweeps are bit-identical to the host's for R = 1 only, PBVI_Solver.solve: keep one start for both)
+            mdp_solution, _ = VI_Solver(horizon=self.horizon, gamma=self.gamma, eps=self.eps).solve(
+                model, use_gpu=use_gpu and host.reachable_state_count == 1, print_progress=False)
+        mdp_rows = (mdp_solution.to_cpu() if mdp_solution.is_on_gpu else mdp_solution).alpha_vector_array
+        rows = np.tile(np.max(np.asarray(mdp_rows, dtype=np.float64), axis=0), (host.action_count, 1))
+        V = ValueFunction(host, rows, host.actions)
+        hist = MDP_SolverHistory(history_tracking_level, host, self.gamma, self.eps, V)
+        limit = self.eps * (self.gamma / (1 - self.gamma))
+        if use_gpu:
+            from .engine import fib_value_iteration          # raises if the HIP library is missing
+            rs, rto, er = _fib_tables(host)
+
+            def run(q, n):
+                return fib_value_iteration(rs, rto, er, q, self.gamma, limit, n)
+        else:
+            def run(q, n):
+                return fib_numpy(host, q, self.gamma, limit, n)
+        # per-sweep value functions (tracking level 2+) need every sweep's rows: one sweep per call then
+        step = 1 if history_tracking_level >= 2 else self.horizon
+        left = self.horizon
+        while left > 0:
+            t0 = datetime.now()
+            rows, changes = run(rows, min(step, left))
+            V = ValueFunction(host, rows, host.actions)
+            dt = (datetime.now() - t0).total_seconds() / max(len(changes), 1)
+            for c in changes:
+                hist.add(dt, float(c), V)
+            left -= len(changes)
+            if len(changes) == 0 or changes[-1] < limit:
+                break
+        return V, hist
 
 
 # --------------------------------------------------------------------------- #

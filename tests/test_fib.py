@@ -1,0 +1,218 @@
+"""The Fast Informed Bound on the host: ``fib_numpy`` against an independent dense restatement, the soundness sandwich
+``V_k(b) <= max_a b . Q^FIB_k(., a) <= max_a b . Q^MDP_k(., a)`` against a brute-force belief-tree value, ``FIB_Solver`` and
+``HSVI_Solver(upper_init='fib')`` on committed example models, and the binding's refusals.  No GPU is needed."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import fib_cases as fc
+import model_cases as mc
+from pomdp_pbvi_exploration_amd import FIB_Solver, HSVI_Solver, VI_Solver, ValueFunction, fib_numpy
+from pomdp_pbvi_exploration_amd import engine as eng
+from pomdp_pbvi_exploration_amd.pomdp import Agent, Belief
+
+STRUCTURE_CASES = [(name, S) for name in mc.STRUCTURES for S in (1, 5, 65)]
+
+
+def check_against_dense(t, gamma, tag):
+    """3 sweeps of ``fib_numpy`` (limit 0: none stops early) against 3 dense sweeps, from both starts, at the project's
+    fp64 bar: the two associate their sums differently, so this is closeness, not equality."""
+    D = fc.dense_rto(t)
+    for start, q0 in fc.starts(t).items():
+        want, want_changes = q0, []
+        for _ in range(3):
+            want, c = fc.dense_sweep(D, t.expected_rewards_table, want, gamma)
+            want_changes.append(c)
+        rows, changes = fib_numpy(t, q0, gamma, 0.0, 3)
+        assert rows.shape == q0.shape and changes.shape == (3,), (tag, start)
+        scale = np.abs(want).max()
+        np.testing.assert_allclose(rows, want, rtol=1e-12, atol=1e-12 * scale, err_msg=f'{tag} {start}')
+        np.testing.assert_allclose(changes, want_changes, rtol=1e-12, atol=1e-12 * scale, err_msg=f'{tag} {start}')
+
+
+@pytest.mark.parametrize('name,S', STRUCTURE_CASES)
+def test_restatement_matches_dense_brute_force_on_structures(name, S):
+    check_against_dense(fc.structure_case(name, S), 0.95, (name, S))
+
+
+@pytest.mark.parametrize('seed', range(8))
+def test_restatement_matches_dense_brute_force_on_random_models(seed):
+    t, gamma = fc.random_tables(seed)
+    check_against_dense(t, gamma, seed)
+
+
+def test_restatement_stops_and_returns_the_last_sweep_that_ran():
+    t = fc.structure_case('ragged', 65)
+    q0 = np.zeros((2, 65))
+    rows, changes = fib_numpy(t, q0, 0.9, 1e-4, 200)
+    assert 1 < len(changes) < 200 and changes[-1] < 1e-4 and (changes[:-1] >= 1e-4).all()
+    again, _ = fib_numpy(t, q0, 0.9, 0.0, len(changes))                      # the same sweeps, none of them the stopping one
+    assert np.array_equal(rows, again)
+    same, none = fib_numpy(t, q0 - 3.0, 0.9, 1e-4, 0)
+    assert np.array_equal(same, q0 - 3.0) and none.shape == (0,)
+
+
+@pytest.mark.parametrize('name', list(mc.STRUCTURES))
+def test_soundness_sandwich(name):
+    """From Q_0 = 0 both inequalities hold exactly, sweep by sweep (induction over k; slack 1e-12 for rounding)."""
+    gamma = 0.9
+    t = fc.structure_case(name, 5)
+    S, A = t.expected_rewards_table.shape
+    beliefs = mc.sparse_beliefs(np.random.default_rng(5), 5, S)
+    strictly_below = False
+    for k in range(1, 5):
+        fib, _ = fib_numpy(t, np.zeros((A, S)), gamma, 0.0, k)
+        mdp = fc.mdp_sweeps(t, gamma, k)
+        assert (fib <= mdp + 1e-12).all(), (name, k)
+        strictly_below |= bool((fib < mdp - 1e-9).any())
+        if name in ('identity', 'duplicate'):                       # one successor state per (s, a): the same rows
+            np.testing.assert_allclose(fib, mdp, rtol=0, atol=1e-12, err_msg=f'{name} {k}')
+        for b in beliefs:
+            exact = fc.exact_value(t, gamma, k, b)
+            upper_fib, upper_mdp = float(np.max(fib @ b)), float(np.max(mdp @ b))
+            assert exact <= upper_fib + 1e-12, (name, k, exact, upper_fib)
+            assert upper_fib <= upper_mdp + 1e-12, (name, k, upper_fib, upper_mdp)
+    assert strictly_below == (name in ('hub', 'ragged')), name
+
+
+# --------------------------------------------------------------------------- #
+# FIB_Solver and HSVI's upper_init on the example models
+# --------------------------------------------------------------------------- #
+_SOLVED = {}
+
+
+def solved(key):
+    """``(model, gamma, VI solution, FIB solution, FIB history)`` of an example model, solved once on the host.
+
+    The MDP solution is iterated to its fixed point (eps = 1e-13: its values are within eps * (gamma / (1 - gamma))^2 =
+    4e-11 of v*).  Value iteration from the rewards rises towards v*, so a solution stopped at the usual eps = 1e-3 lies up
+    to 0.36 BELOW v* at gamma = 0.95 and is no upper bound of anything yet: FIB's first sweep from it is the next MDP
+    sweep, which is above it.  ``rows <= max over the VI rows`` is a statement about the converged solution."""
+    if key not in _SOLVED:
+        model, gamma = fc.file_model(key)
+        mdp, _ = VI_Solver(gamma=gamma, eps=1e-13).solve(model, print_progress=False)
+        vf, hist = FIB_Solver(gamma=gamma, eps=1e-3).solve(model, mdp_solution=mdp, print_progress=False)
+        _SOLVED[key] = (model, gamma, mdp, vf, hist)
+    return _SOLVED[key]
+
+
+@pytest.mark.parametrize('key', list(fc.FILE_MODELS))
+def test_fib_solver_converges_below_the_mdp_solution(key):
+    model, gamma, mdp, vf, hist = solved(key)
+    limit = 1e-3 * gamma / (1 - gamma)
+    changes = hist.value_function_changes
+    assert 0 < len(changes) < 10000 and changes[-1] < limit and all(c >= limit for c in changes[:-1])
+    assert isinstance(vf, ValueFunction) and not vf.is_on_gpu
+    rows = vf.alpha_vector_array
+    assert rows.shape[1] == model.state_count and len(vf.actions) == rows.shape[0] <= model.action_count
+    v_mdp = np.max(mdp.alpha_vector_array, axis=0)
+    assert (rows <= v_mdp[None, :] + 1e-9).all()
+
+
+def test_fib_solver_runs_value_iteration_when_no_mdp_solution_is_given():
+    model, gamma = fc.file_model('tiger-grid')
+    own, _ = VI_Solver(gamma=gamma, eps=1e-3).solve(model, print_progress=False)
+    given, hist_given = FIB_Solver(gamma=gamma, eps=1e-3).solve(model, mdp_solution=own, print_progress=False)
+    alone, hist_alone = FIB_Solver(gamma=gamma, eps=1e-3).solve(model, print_progress=False)
+    assert np.array_equal(alone.alpha_vector_array, given.alpha_vector_array) and np.array_equal(alone.actions, given.actions)
+    assert hist_alone.value_function_changes == hist_given.value_function_changes
+
+
+@pytest.mark.parametrize('key', list(fc.FILE_MODELS))
+def test_agent_follows_the_fib_rows(key):
+    model, gamma, _, vf, _ = solved(key)
+    rng = np.random.default_rng(3)
+    S = model.state_count
+    beliefs = np.concatenate([np.asarray(model.start_probabilities, dtype=np.float64)[None, :], mc.sparse_beliefs(rng, 4, S)])
+    agent = Agent(model, vf)
+    scores = beliefs @ vf.alpha_vector_array.T                                  # [n, rows]
+    acts = agent.get_best_action(beliefs)
+    for i, b in enumerate(beliefs):
+        assert agent.get_best_action(Belief(model, b)) == acts[i]
+        labelled = scores[i][np.asarray(vf.actions) == acts[i]]
+        assert labelled.size and labelled.max() == scores[i].max(), (key, i)
+
+
+@pytest.mark.parametrize('key', list(fc.FILE_MODELS))
+def test_hsvi_upper_init(key):
+    model, gamma, mdp, vf, _ = solved(key)
+    b0 = np.asarray(model.start_probabilities, dtype=np.float64)
+
+    def run(**kw):
+        np.random.seed(0)
+        solver = HSVI_Solver(gamma=gamma, eps=1e-3, mdp_solution=mdp, sawtooth='support', **kw)
+        out, hist = solver.solve(model, expansions=5, max_belief_growth=5, print_progress=False)
+        return solver, out, hist
+
+    s_fib, vf_fib, _ = run(upper_init='fib')
+    s_mdp, vf_mdp, _ = run(upper_init='mdp')
+    s_def, vf_def, _ = run()
+    assert len(vf_fib) >= 1
+    assert np.array_equal(s_fib._upper_bound.corner_values, np.max(vf.alpha_vector_array, axis=0))
+    assert np.array_equal(s_mdp._upper_bound.corner_values, np.max(mdp.alpha_vector_array, axis=0))
+    assert float(b0 @ s_fib._upper_bound.corner_values) <= float(b0 @ s_mdp._upper_bound.corner_values)
+    assert (s_fib._upper_bound.corner_values <= s_mdp._upper_bound.corner_values + 1e-9).all()
+    # 'mdp' is the default and changes nothing
+    assert np.array_equal(vf_mdp.alpha_vector_array, vf_def.alpha_vector_array)
+    assert np.array_equal(vf_mdp.actions, vf_def.actions)
+    assert np.array_equal(s_mdp._upper_bound.value_array, s_def._upper_bound.value_array)
+    with pytest.raises(ValueError):
+        HSVI_Solver(upper_init='qmdp')
+
+
+# --------------------------------------------------------------------------- #
+# The binding refuses bad input before it touches the device
+# --------------------------------------------------------------------------- #
+def small():
+    t = fc.structure_case('hub', 5)
+    return (t.reachable_states, t.reachable_transitional_observation_table, t.expected_rewards_table,
+            np.zeros((2, 5)))
+
+
+def test_binding_refuses_bad_input_without_a_gpu():
+    rs, rto, er, q0 = small()
+    bad = rs.copy()
+    bad[3, 1, 0] = 5
+    with pytest.raises(ValueError):
+        eng.fib_value_iteration(bad, rto, er, q0, 0.9, 0.0, 3)
+    bad[3, 1, 0] = -1
+    with pytest.raises(ValueError):
+        eng.fib_value_iteration(bad, rto, er, q0, 0.9, 0.0, 3)
+    with pytest.raises(ValueError):
+        eng.fib_value_iteration(rs, rto[:, :, :, :1], er, q0, 0.9, 0.0, 3)
+    with pytest.raises(ValueError):
+        eng.fib_value_iteration(rs, rto, er[:4], q0, 0.9, 0.0, 3)
+    with pytest.raises(ValueError):
+        eng.fib_value_iteration(rs, rto, er, q0.T, 0.9, 0.0, 3)
+    with pytest.raises(ValueError):
+        eng.fib_value_iteration(rs, rto, er, q0, 0.9, 0.0, -1)
+    # an oversize product: the tables are views with stride 0, nothing of that size exists
+    O = 2 ** 31
+    one = np.zeros((1, 1, 1), dtype=np.int64)
+    with pytest.raises(NotImplementedError):
+        eng.fib_value_iteration(one, np.broadcast_to(np.ones(1), (1, 1, O, 1)), np.zeros((1, 1)), np.zeros((1, 1)), 0.9, 0.0, 3)
+
+
+def test_entry_point_decides_errors_before_the_device():
+    """The same refusals from the C entry itself (codes of include/pbvi_hip.h), and ``horizon = 0`` returning ``q0``: none
+    of them needs a device."""
+    lib = eng.load_library()
+    rs, rto, er, q0 = small()
+    rs32 = np.ascontiguousarray(rs, dtype=np.int32)
+    q0 = q0 - 2.5
+    out = np.full((2, 5), np.nan)
+    its = C.c_int32(-1)
+
+    def call(S=5, A=2, O=2, R=2, rs_=rs32, horizon=3):
+        p = lambda a, ty: a.ctypes.data_as(C.POINTER(ty))      # noqa: E731
+        return lib.pbvi_fib_value_iteration(0, S, A, O, R, p(rs_, C.c_int32), p(rto, C.c_double), p(er, C.c_double),
+                                            p(q0, C.c_double), 0.9, 0.0, horizon, p(out, C.c_double), None, C.byref(its))
+
+    assert call(horizon=-1) == -1 and b'fib_value_iteration' in lib.pbvi_last_error()
+    assert call(S=0) == -1 and call(O=0) == -1
+    bad = rs32.copy()
+    bad[4, 0, 1] = 5
+    assert call(rs_=bad) == -1 and b'out of range' in lib.pbvi_last_error()
+    assert call(S=2 ** 20, A=2 ** 6, O=2 ** 4, R=2) == -4          # 2^31: decided before any table is read
+    assert call(horizon=0) == 0 and its.value == 0 and np.array_equal(out, q0)

@@ -1,0 +1,108 @@
+"""``pbvi_fib_value_iteration`` against ``pomdp.fib_numpy``: the kernel and the restatement share one definition of a sweep,
+operation for operation, so rows and changes are compared with ``np.array_equal`` -- on the wave and block edges of S, the
+a'-tile edges of A, random models, a mostly negative start, across the seam between two enqueued batches of sweeps, and
+through ``FIB_Solver``.  Every shape is small; every case takes well under a second."""
+import gc
+
+import numpy as np
+import pytest
+
+import fib_cases as fc
+import model_cases as mc
+from pomdp_pbvi_exploration_amd import FIB_Solver, fib_numpy
+from pomdp_pbvi_exploration_amd.engine import debug_live_bytes, fib_value_iteration
+
+pytestmark = pytest.mark.gpu
+
+EDGE_SIZES = (1, 63, 64, 65, 255, 256, 257, 600)                # around one wave (64) and one block (256) of states
+ACTION_CASES = ((1, 1, 1), (2, 2, 2), (7, 5, 4), (8, 1, 2), (9, 2, 4), (17, 5, 1))     # (A, O, R): A around the tiles of 4 and 8
+BATCH = 64                                                      # sweeps the entry enqueues between two synchronisations
+
+
+def device(t, q0, gamma, limit, horizon):
+    return fib_value_iteration(t.reachable_states, t.reachable_transitional_observation_table, t.expected_rewards_table,
+                               q0, gamma, limit, horizon)
+
+
+def assert_same_sweeps(t, gamma, tag):
+    for start, q0 in fc.starts(t).items():
+        want_rows, want_changes = fib_numpy(t, q0, gamma, 0.0, 3)
+        rows, changes = device(t, q0, gamma, 0.0, 3)
+        assert len(changes) == 3, (tag, start)
+        assert np.array_equal(changes, want_changes), (tag, start, changes, want_changes)
+        assert np.array_equal(rows, want_rows), (tag, start, np.abs(rows - want_rows).max())
+
+
+@pytest.mark.parametrize('S', EDGE_SIZES)
+@pytest.mark.parametrize('name', list(mc.STRUCTURES))
+def test_three_sweeps_bit_equal_on_structures(name, S):
+    assert_same_sweeps(fc.structure_case(name, S), 0.95, (name, S))
+
+
+@pytest.mark.parametrize('A,O,R', ACTION_CASES)
+def test_three_sweeps_bit_equal_around_the_action_tiles(A, O, R):
+    assert_same_sweeps(fc.dense_random_case(A, O, R), 0.95, (A, O, R))
+
+
+@pytest.mark.parametrize('seed', range(8))
+def test_three_sweeps_bit_equal_on_random_models(seed):
+    t, gamma = fc.random_tables(seed)
+    assert_same_sweeps(t, gamma, seed)
+
+
+# --------------------------------------------------------------------------- #
+# Stopping
+# --------------------------------------------------------------------------- #
+@pytest.mark.parametrize('name', list(mc.STRUCTURES))
+def test_stopping_across_the_batch_seam(name):
+    """The run converges in the second batch: the sweeps enqueued behind the converged one must leave its rows alone, and
+    the entry must report the sweep that met the limit, not the last one it enqueued."""
+    t = fc.structure_case(name, 257)
+    S, A = t.expected_rewards_table.shape
+    q0 = np.zeros((A, S))
+    want_rows, want_changes = fib_numpy(t, q0, 0.9, 1e-4, 200)
+    assert BATCH < len(want_changes) < 2 * BATCH, len(want_changes)
+    rows, changes = device(t, q0, 0.9, 1e-4, 200)
+    assert len(changes) == len(want_changes)
+    assert np.array_equal(changes, want_changes)
+    assert np.array_equal(rows, want_rows)
+
+
+@pytest.mark.parametrize('horizon', (0, 1, 10, BATCH, BATCH + 6))
+def test_horizon_cuts_the_run(horizon):
+    """No sweep (``q0`` comes back), one, and horizons that end the run before it converges: inside the first batch, at the
+    seam and behind it."""
+    t = fc.structure_case('ragged', 257)
+    S, A = t.expected_rewards_table.shape
+    q0 = fc.starts(t)['negative']
+    want_rows, want_changes = fib_numpy(t, q0, 0.9, 1e-4, horizon)
+    assert len(want_changes) == horizon and (horizon == 0 or want_changes[-1] >= 1e-4)
+    rows, changes = device(t, q0, 0.9, 1e-4, horizon)
+    assert changes.shape == (horizon,) and np.array_equal(changes, want_changes)
+    assert np.array_equal(rows, want_rows)
+    if horizon == 0:
+        assert np.array_equal(rows, q0)
+
+
+# --------------------------------------------------------------------------- #
+# Solver and memory
+# --------------------------------------------------------------------------- #
+@pytest.mark.parametrize('key', list(fc.FILE_MODELS))
+def test_solver_on_the_device_equals_the_host(key):
+    model, gamma = fc.file_model(key)
+    host, hist_host = FIB_Solver(gamma=gamma, eps=1e-3).solve(model, use_gpu=False, print_progress=False)
+    dev, hist_dev = FIB_Solver(gamma=gamma, eps=1e-3).solve(model, use_gpu=True, print_progress=False)
+    assert np.array_equal(dev.alpha_vector_array, host.alpha_vector_array)
+    assert np.array_equal(dev.actions, host.actions)
+    assert hist_dev.value_function_changes == hist_host.value_function_changes
+    assert len(hist_host.value_function_changes) > 0
+
+
+def test_a_call_leaves_no_device_memory_behind():
+    t = fc.structure_case('hub', 600)
+    gc.collect()
+    base = debug_live_bytes()
+    device(t, fc.starts(t)['rewards'], 0.9, 1e-4, 200)
+    assert debug_live_bytes() == base
+    device(t, fc.starts(t)['rewards'], 0.9, 1e-4, 0)
+    assert debug_live_bytes() == base
