@@ -11,6 +11,7 @@ The reference publishes one timing for this step (sim_runtime_test.ipynb:223, BA
     python examples/policy_eval.py --policy expected-distance --device-sim 7   # greedy for the expected distance to the source
     python examples/policy_eval.py --policy fib --reach 5 --device-sim 7   # follow the Fast Informed Bound's rows (no FSVI solve)
     python examples/policy_eval.py --policy qmdp --reach 5 --device-sim 7  # ... or the MDP solution's (QMDP)
+    python examples/policy_eval.py --policy thompson --device-sim 7   # MDP heuristics: mls, voting, thompson (pbvi_state_policy)
     python examples/policy_eval.py --device-sim 1 --environment frames    # observations from recorded frames (pbvi_rollout_env)
     python examples/policy_eval.py --device-sim 1 --environment table --env-flip 0.1   # a sensor that errs 10 % more often
 """
@@ -25,7 +26,7 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 from pomdp_pbvi_exploration_amd import FIB_Solver, FSVI_Solver, Model, set_quiet, synth   # noqa: E402
 from pomdp_pbvi_exploration_amd.pomdp import (Agent, FrameEnvironment, Infotaxis_Agent, SpaceAware_Agent,   # noqa: E402
-                                              TableEnvironment, record_frames)
+                                              StatePolicy_Agent, TableEnvironment, record_frames, state_actions_from)
 from pomdp_pbvi_exploration_amd.mdp import VI_Solver                         # noqa: E402
 
 
@@ -45,12 +46,16 @@ def main():
     ap.add_argument('--device-sim', type=int, default=None, metavar='SEED',
                     help='counter-based simulator draws with this seed: the whole step loop runs in the engine '
                          '(pbvi_rollout) instead of drawing on the host from NumPy\'s stream')
-    ap.add_argument('--policy', default='value', choices=['value', 'infotaxis', 'space-aware', 'expected-distance', 'qmdp', 'fib'],
+    ap.add_argument('--policy', default='value', choices=['value', 'infotaxis', 'space-aware', 'expected-distance', 'qmdp', 'fib',
+                                                         'mls', 'voting', 'thompson'],
                     help='value: solve with FSVI and follow the value function; qmdp / fib: no FSVI solve, follow the A rows of '
                          'MDP value iteration / of the Fast Informed Bound (pbvi_fib_value_iteration); infotaxis: no solve, every step takes the '
                          'action with the smallest expected entropy of the next belief (pbvi_infotaxis); space-aware: no '
                          'solve, greedy for log2(D + 2^(H-1) - 1/2) of the next belief, D its expected Manhattan distance to '
-                         'the source and H its entropy in bits (pbvi_space_aware); expected-distance: greedy for D alone')
+                         'the source and H its entropy in bits (pbvi_space_aware); expected-distance: greedy for D alone; mls / '
+                         'voting / thompson: solve the MDP as qmdp does and act through its policy pi(s) -- in the most likely '
+                         'state, by the votes of all states weighted with the belief, or in a state drawn from the belief '
+                         '(pbvi_state_policy)')
     ap.add_argument('--environment', default=None, choices=['frames', 'table'],
                     help='where the observations come from (needs --device-sim): frames = a recorded movie, max-steps + 100 '
                          'frames drawn from the observation table by record_frames, every simulation starting at its own '
@@ -78,6 +83,12 @@ def main():
         agent = SpaceAware_Agent(model.to_gpu(args.dtype), weights=distance,
                                  objective='space_aware' if args.policy == 'space-aware' else 'expected_weight')
         policy = args.policy
+    elif args.policy in ('mls', 'voting', 'thompson'):
+        t0 = time.perf_counter()
+        vf, h = VI_Solver(gamma=m.gamma, eps=1e-6).solve(model, use_gpu=True, print_progress=False)
+        policy = f'{args.policy} over the MDP policy ({len(h.iteration_times)} sweeps)'
+        print(f'{policy}: solved in {time.perf_counter() - t0:.3f}s', flush=True)
+        agent = StatePolicy_Agent(model.to_gpu(args.dtype), state_actions_from(vf), rule=args.policy)
     elif args.policy in ('qmdp', 'fib'):
         t0 = time.perf_counter()
         vf, h = VI_Solver(gamma=m.gamma, eps=1e-6).solve(model, use_gpu=True, print_progress=False)
@@ -155,6 +166,8 @@ def main():
             host_agent = Infotaxis_Agent(model)
         elif args.policy in ('space-aware', 'expected-distance'):
             host_agent = SpaceAware_Agent(model, weights=agent.weights, objective=agent.objective)
+        elif args.policy in ('mls', 'voting', 'thompson'):
+            host_agent = StatePolicy_Agent(model, agent.state_actions, rule=agent.rule)
         else:
             host_agent = Agent(model, vf.to_cpu(), lookahead=args.lookahead, gamma=m.gamma)   # (value, qmdp, fib)
         np.random.seed(1)

@@ -674,6 +674,69 @@ int pbvi_rollout_space_aware(pbvi_engine_t* e, int objective, int use_env, const
                              int32_t* out_steps /* [B] */, uint8_t* out_lost /* [B] */);
 
 /*
+ * State policies: the three heuristics that act through a policy of the underlying MDP, pi(s), instead of value rows --
+ * most likely state, action voting (Cassandra's MDP heuristics; "most likely state" and "voting" of Loisy & Eloy 2022) and
+ * Thompson / posterior sampling.  One reduction over S per belief, no GEMM.
+ *
+ * State policy table: one per engine, state_actions [S] int32, every entry in [0, A) (checked on the host).
+ *   pbvi_state_policy_set    sets it (PBVI_EINVAL with a pbvi_last_error text: NULL, or an entry outside [0, A)).
+ *   pbvi_state_policy_clear  removes it; the bytes are returned.
+ * The table is device memory of the engine, S int32 exactly, counted against pbvi_debug_alloc_limit (PBVI_ENOMEM as
+ * everywhere) and released by pbvi_engine_after_oom, after which no table is set.  Setting or clearing it touches nothing
+ * else: not the belief block, the alpha set, the stores, the weights, the environment or any result.
+ *
+ * A belief row b is the resident row widened to fp64 (an fp32 engine's values are widened, exactly as pbvi_infotaxis reads
+ * them).  Chunk c is the states [256 c, min(256 c + 256, S)), C = ceil(S / 256).  Every sum below is taken by sequential fp64
+ * adds in the order stated, starting from +0.0 -- fixed, no atomics: a belief's results have the same bits from call to call,
+ * whatever other beliefs share the block and wherever it stands, and equal pomdp.state_policy_numpy's bit for bit.
+ *   rule 0 (most likely state)
+ *     s* = the first s whose b[s] is strictly greater than every earlier entry (a NaN never wins; a row of NaNs gives 0)
+ *     a = state_actions[s*];  out_state = s*
+ *   rule 1 (voting)
+ *     W_c[a] = sum over the states s of chunk c, ascending, of b[s] where state_actions[s] == a (other states add nothing)
+ *     W[a]   = W_0[a] + W_1[a] + ... in chunk order
+ *     a* = the first a whose W[a] is strictly greater than every earlier one, taken from the row of out_votes that is
+ *          returned;  out_state = -1
+ *   rule 2 (Thompson)
+ *     u       the uniform of the belief: uniforms[b] when uniforms is given, else uniform01(splitmix64(seed, i), 2^33 + t) with
+ *             i = first_sim_id + b -- a third counter stream beside the rollouts' t and 2^32 + t (t < 2^31 keeps them apart)
+ *     q_c[j]  the sequential prefix sums of b inside chunk c;  m_c = q_c[last];  P_c = P_{c-1} + m_c;  total = P_{C-1}
+ *     target = u * total (one rounded multiply)
+ *     c* = the first c with target < P_c; if there is none, the last c with m_c > 0
+ *     r  = target - (c* > 0 ? P_{c*-1} : 0) (one rounded subtract)
+ *     s~ = the first state j of chunk c* with r < q_{c*}[j]; if there is none, the last state of that chunk with b > 0
+ *     a = state_actions[s~];  out_state = s~.  The drawn state always has b[s~] > 0.  (A row without any mass, which is no
+ *     belief, gives c* = 0 and s~ = 0.)
+ *
+ * pbvi_state_policy: the above for every belief of the resident block.
+ *   out_action [B] int32 (required); out_state [B] int32, out_votes [B][A] double (written by rule 1 only): may be NULL.
+ *   uniforms [B] double or NULL (rule 2 only); every entry in [0, 1] -- 1.0 itself is accepted: it is the only way to reach
+ *   the two fallbacks on purpose.  Host (or device) memory, caller's belief order.
+ * The resident block, the alpha set, both row stores, the backup's stage buffers and the other greedy policies' results are
+ * untouched.  Works on PBVI_SPARSE and PBVI_DENSE engines and on both number formats.
+ * PBVI_EINVAL: no resident belief block, no table set, a rule other than 0, 1 or 2, out_action == NULL, a uniforms entry
+ * outside [0, 1] (or NaN), uniforms given for a rule other than 2, t < 0 or t >= 2^31.  PBVI_ENOMEM as everywhere
+ * (pbvi_engine_after_oom): the results and rule 2's per-chunk sums, B * C * 2 doubles, are device memory of the engine and
+ * count against pbvi_debug_alloc_limit.
+ *
+ * pbvi_rollout_state_policy: the step loop of the rollouts above with a fifth action source, the action of `rule` for the
+ * simulation's current belief; Thompson's uniform of simulation i at step t is uniform01(splitmix64(seed, i), 2^33 + t).
+ * use_env, the Bayes step's mass in block order, the trajectory layout, the end state of the block and the checks are
+ * pbvi_rollout_space_aware's, with "no state policy set" and the rule in place of the weights and the objective.  No alpha
+ * set is needed.  pbvi_rollout_env itself keeps refusing policy numbers other than 0, 1 and 2.
+ */
+int pbvi_state_policy_set(pbvi_engine_t* e, const int32_t* state_actions /* [S] */);
+int pbvi_state_policy_clear(pbvi_engine_t* e);
+int pbvi_state_policy(pbvi_engine_t* e, int rule, uint64_t seed, uint64_t first_sim_id, int64_t t,
+                      const double* uniforms /* [B] or NULL */, int32_t* out_action /* [B], required */,
+                      int32_t* out_state /* [B], may be NULL */, double* out_votes /* [B][A], may be NULL */);
+int pbvi_rollout_state_policy(pbvi_engine_t* e, int rule, int use_env, const int32_t* start_states /* [B] */,
+                              const uint8_t* end_mask /* [S] */, int end_observation, const int64_t* shifts /* [B] or NULL */,
+                              uint64_t first_sim_id, uint64_t seed, int64_t T, int32_t* out_states /* [T+1][B] */,
+                              int32_t* out_actions /* [T][B] */, int32_t* out_observations /* [T][B] */,
+                              int32_t* out_steps /* [B] */, uint8_t* out_lost /* [B] */);
+
+/*
  * MDP value iteration on the device (VI_Solver.solve, src/mdp.py:1442-1525; seeds FSVI / HSVI):
  *   rows[a][s] = ER[s,a] + gamma * sum_r P[s,a,r] * v[rs[s,a,r]];   v'[s] = max_a rows[a][s]
  * repeated from v0 until max_s |v' - v| < max_change_limit (the reference's eps * gamma / (1 - gamma)) or

@@ -26,6 +26,7 @@
 
 #include "backup_kernels.h"
 #include "split_bf16.h"
+#include "state_policy_kernels.h"
 #include "upper_kernels.h"
 
 namespace pbvi {
@@ -968,6 +969,7 @@ enum RolloutSource {
     ROLLOUT_Q = 1,                    // first argmax_a Q(b, a)                        (pbvi_rollout, lookahead 1)
     ROLLOUT_INFOTAXIS = 2,            // first argmin_a of the expected successor entropy (pbvi_rollout_infotaxis)
     ROLLOUT_SPACE_AWARE = 3,          // first argmin_a of pbvi_space_aware's F, RolloutCall::objective (pbvi_rollout_space_aware)
+    ROLLOUT_STATE_POLICY = 4,         // pbvi_state_policy's action under RolloutCall::rule (pbvi_rollout_state_policy)
 };
 // What the step loop has to know about a source; its stage is EngineT::rollout_stage.  A number that is no source reads as
 // value-max until EngineT::rollout refuses it (`known`), which keeps the refusals before that one in their order.
@@ -975,28 +977,33 @@ struct RolloutSourceInfo {
     bool known;
     bool needs_alpha;                 // a resident alpha set and alpha_actions [V]
     bool needs_weights;               // pbvi_state_weights_set, and RolloutCall::objective 0 or 1
+    bool needs_state_policy;          // pbvi_state_policy_set, and RolloutCall::rule 0, 1 or 2
     // The Bayes step sums the norm in block order, not with atomics: infotaxis (plain or space-aware) meets near-ties between
     // actions on symmetric beliefs, which must not hang on the arrival order of the atomics.  (A rollout against an environment
-    // promises the same bits however a run is cut into blocks, and sums in block order whatever its source.)
+    // promises the same bits however a run is cut into blocks, and sums in block order whatever its source.)  The state
+    // policies too: Thompson sampling reads the belief's bits, which must not depend on that order either.
     bool fixed_order;
     const char* who;                  // the entry point named in the refusals of what only this source needs
 };
 inline RolloutSourceInfo rollout_source_info(int source) {
     switch (source) {
-        case ROLLOUT_VALUE_MAX: return {true, true, false, false, "rollout"};
-        case ROLLOUT_Q: return {true, true, false, false, "rollout"};
-        case ROLLOUT_INFOTAXIS: return {true, false, false, true, "rollout_infotaxis"};
-        case ROLLOUT_SPACE_AWARE: return {true, false, true, true, "rollout_space_aware"};
-        default: return {false, true, false, false, "rollout"};
+        case ROLLOUT_VALUE_MAX: return {true, true, false, false, false, "rollout"};
+        case ROLLOUT_Q: return {true, true, false, false, false, "rollout"};
+        case ROLLOUT_INFOTAXIS: return {true, false, false, false, true, "rollout_infotaxis"};
+        case ROLLOUT_SPACE_AWARE: return {true, false, true, false, true, "rollout_space_aware"};
+        case ROLLOUT_STATE_POLICY: return {true, false, false, true, true, "rollout_state_policy"};
+        default: return {false, true, false, false, false, "rollout"};
     }
 }
 
-// One rollout call, as pbvi_rollout / pbvi_rollout_infotaxis / pbvi_rollout_env / pbvi_rollout_space_aware fill it
+// One rollout call, as pbvi_rollout / pbvi_rollout_infotaxis / pbvi_rollout_env / pbvi_rollout_space_aware /
+// pbvi_rollout_state_policy fill it
 struct RolloutCall {
     int source;                                // RolloutSource (anything else is refused)
     const int32_t* alpha_actions = nullptr;    // [V], read by ROLLOUT_VALUE_MAX
     double gamma = 0.0;                        // read by ROLLOUT_Q
     int objective = 0;                         // read by ROLLOUT_SPACE_AWARE: 0 space-aware, 1 expected weight
+    int rule = 0;                              // read by ROLLOUT_STATE_POLICY: 0 MLS, 1 voting, 2 Thompson
     const int32_t* start_states;               // [B]
     const uint8_t* end_mask;                   // [S]
     uint64_t first_sim_id, seed;
@@ -1181,6 +1188,10 @@ class EngineBase {
     virtual int state_weights_set(const double* w) = 0;
     virtual int state_weights_clear() = 0;
     virtual int space_aware(int objective, double* out_f, int32_t* out_action, double* out_terms) = 0;
+    virtual int state_policy_set(const int32_t* state_actions) = 0;
+    virtual int state_policy_clear() = 0;
+    virtual int state_policy(int rule, uint64_t seed, uint64_t first_sim_id, int64_t t, const double* uniforms,
+                             int32_t* out_action, int32_t* out_state, double* out_votes) = 0;
     // the HSVI upper bound: the device point store, its sawtooth on the resident block, the bound-greedy action values
     virtual int upper_reset(const double* corner) = 0;
     virtual int upper_append(const double* points, const double* values, const double* gaps, int64_t n) = 0;
@@ -1284,6 +1295,11 @@ class EngineT : public EngineBase {
     // pbvi_state_weights_set: w [S] fp64 (a working buffer: after_oom() releases it and no weights are set)
     DevBuf sw_{mem_};
     bool sw_set_ = false;
+    // pbvi_state_policy_set: state_actions [S] int32 (a working buffer: after_oom() releases it and no table is set);
+    // pbvi_state_policy's results in caller order -- action [B], state [B], votes [B][A] --, Thompson's per-chunk sums
+    // (P_c, m_c) [B][ceil(S/256)][2] and the uniforms a caller gave [B]
+    DevBuf sp_table_{mem_}, sp_act_{mem_}, sp_state_{mem_}, sp_votes_{mem_}, sp_sums_{mem_}, sp_u_{mem_};
+    bool sp_set_ = false;
     DevBuf bu_mpart_{mem_};   // bayes_push(fixed_order): the push blocks' partial masses [B][ceil(S/256)]
     // pbvi_upper_*: the point store of the HSVI upper bound -- CSR rows (ub_ptr_ int64 [P+1], ub_idx_ int32 / ub_val_ fp64 [entries]),
     // per point its entries, value and gap (ub_nnz_ int32, ub_v_ / ub_gap_ fp64 [P]), the corner values ub_c_ fp64 [S].  Working
@@ -2019,6 +2035,86 @@ class EngineT : public EngineBase {
         return successor_scores_deliver(objective, out_f, out_action, out_terms, nullptr);
     }
 
+    // ---- state policies (pbvi_state_policy_set / _clear, pbvi_state_policy) ---- //
+    int state_policy_set(const int32_t* state_actions) override {
+        if (!state_actions) FAIL(PBVI_EINVAL, "state_policy_set: NULL state_actions");
+        if (A_ > STATE_POLICY_MAX_A) FAIL(PBVI_EUNSUPPORTED, "state_policy_set: more than 256 actions");
+        for (int s = 0; s < S_; ++s)
+            if (state_actions[s] < 0 || state_actions[s] >= A_)
+                FAIL(PBVI_EINVAL, "state_policy_set: state_actions[" + std::to_string(s) + "] is outside [0, A)");
+        HIPCHK(hipSetDevice(device_));
+        HIPCHK(hipStreamSynchronize(stream_));               // a kernel of an earlier call may still read the old table
+        sp_set_ = false;
+        int rc = sp_table_.ensure((size_t)S_ * sizeof(int32_t));
+        if (rc) return rc;
+        HIPCHK(hipMemcpy(sp_table_.p, state_actions, (size_t)S_ * sizeof(int32_t), hipMemcpyHostToDevice));
+        sp_set_ = true;
+        return PBVI_OK;
+    }
+    int state_policy_clear() override {
+        HIPCHK(hipSetDevice(device_));
+        HIPCHK(hipStreamSynchronize(stream_));
+        sp_table_.release();
+        sp_set_ = false;
+        return PBVI_OK;
+    }
+
+    // The state policy `rule` of the resident block into sp_act_ / sp_state_ (/ sp_votes_), caller order, left on the device.
+    // Thompson's uniform: d_uniforms [B] (device, caller order), or hashed from (seed, first_sim_id + orig[c], t) -- orig
+    // (device, caller row -> simulation row) nullptr: the caller row itself.  Reads the block and the table only.
+    int state_policy_stage(int rule, const double* d_uniforms, uint64_t seed, uint64_t first_sim_id, const int32_t* orig, int64_t t) {
+        int rc;
+        if ((rc = sp_act_.ensure((size_t)blk_.B * sizeof(int32_t)))) return rc;
+        if ((rc = sp_state_.ensure((size_t)blk_.B * sizeof(int32_t)))) return rc;
+        if (rule == STATE_POLICY_VOTING && (rc = sp_votes_.ensure((size_t)blk_.B * A_ * sizeof(double)))) return rc;
+        if (rule == STATE_POLICY_THOMPSON && (rc = sp_sums_.ensure((size_t)blk_.B * state_policy_chunks(S_) * 2 * sizeof(double)))) return rc;
+        StatePolicy<T> sp{};
+        sp.bel = blk_.rows.as<T>();
+        sp.ldb = S_pad_;
+        sp.B = (int)blk_.B;
+        sp.S = S_;
+        sp.A = A_;
+        sp.perm = blk_.sorted ? blk_.perm.as<int32_t>() : nullptr;
+        sp.table = sp_table_.as<int32_t>();
+        sp.rule = rule;
+        sp.uniforms = d_uniforms;
+        sp.seed = seed;
+        sp.first_id = first_sim_id;
+        sp.orig = orig;
+        sp.t = t;
+        sp.chunk_sums = rule == STATE_POLICY_THOMPSON ? sp_sums_.as<double>() : nullptr;
+        sp.action_out = sp_act_.as<int32_t>();
+        sp.state_out = sp_state_.as<int32_t>();
+        sp.votes_out = rule == STATE_POLICY_VOTING ? sp_votes_.as<double>() : nullptr;
+        HIPCHK(launch_state_policy<T>(sp, stream_));
+        return PBVI_OK;
+    }
+
+    int state_policy(int rule, uint64_t seed, uint64_t first_sim_id, int64_t t, const double* uniforms, int32_t* out_action,
+                     int32_t* out_state, double* out_votes) override {
+        if (blk_.B <= 0) FAIL(PBVI_EINVAL, "state_policy: no belief block resident (call pbvi_beliefs_set)");
+        if (!sp_set_) FAIL(PBVI_EINVAL, "state_policy: no state policy set (call pbvi_state_policy_set)");
+        if (rule != STATE_POLICY_MLS && rule != STATE_POLICY_VOTING && rule != STATE_POLICY_THOMPSON)
+            FAIL(PBVI_EINVAL, "state_policy: rule must be 0 (most likely state), 1 (voting) or 2 (Thompson)");
+        if (!out_action) FAIL(PBVI_EINVAL, "state_policy: NULL out_action");
+        if (uniforms && rule != STATE_POLICY_THOMPSON) FAIL(PBVI_EINVAL, "state_policy: uniforms belong to rule 2 (Thompson)");
+        for (int64_t b = 0; uniforms && b < blk_.B; ++b)
+            if (!(uniforms[b] >= 0.0 && uniforms[b] <= 1.0))
+                FAIL(PBVI_EINVAL, "state_policy: uniforms[" + std::to_string(b) + "] is outside [0, 1]");
+        if (t < 0 || t >= (1ll << 31)) FAIL(PBVI_EINVAL, "state_policy: t must be in [0, 2^31)");
+        HIPCHK(hipSetDevice(device_));
+        int rc;
+        if (uniforms) {
+            if ((rc = sp_u_.ensure((size_t)blk_.B * sizeof(double)))) return rc;
+            HIPCHK(hipMemcpyAsync(sp_u_.p, uniforms, (size_t)blk_.B * sizeof(double), hipMemcpyHostToDevice, stream_));
+        }
+        if ((rc = state_policy_stage(rule, uniforms ? sp_u_.as<double>() : nullptr, seed, first_sim_id, nullptr, t))) return rc;
+        const bool votes = rule == STATE_POLICY_VOTING;       // (out_votes is rule 1's: the other rules leave it alone)
+        return out_.deliver({{out_action, sp_act_.p, (size_t)blk_.B * sizeof(int32_t)},
+                             {out_state, sp_state_.p, (size_t)blk_.B * sizeof(int32_t)},
+                             {votes ? out_votes : nullptr, sp_votes_.p, (size_t)blk_.B * A_ * sizeof(double)}});
+    }
+
     // ---- HSVI upper bound (pbvi_upper_reset / _append / _count / _bound / _q) ---- //
     int upper_reset(const double* corner) override {
         if (!corner) FAIL(PBVI_EINVAL, "upper_reset: NULL corner values");
@@ -2251,10 +2347,15 @@ class EngineT : public EngineBase {
 
     // The stage of a rollout call's action source on the resident block; *index = what it leaves on the device for the draw:
     // for ROLLOUT_VALUE_MAX an alpha row per belief in ENGINE row order (the draw maps it through RolloutStep::alpha_actions),
-    // for every other source an action per belief in CALLER row order.
-    int rollout_stage(const RolloutCall& call, const int32_t** index) {
+    // for every other source an action per belief in CALLER row order.  t: the step; orig: the live simulations' rows in the
+    // call (device, caller order) -- what a source that draws (Thompson) forms its simulation ids from.
+    int rollout_stage(const RolloutCall& call, int64_t t, const int32_t* orig, const int32_t** index) {
         int rc;
         switch (call.source) {
+            case ROLLOUT_STATE_POLICY:
+                rc = state_policy_stage(call.rule, nullptr, call.seed, call.first_sim_id, orig, t);
+                *index = sp_act_.as<int32_t>();
+                return rc;
             case ROLLOUT_VALUE_MAX:
                 rc = value_max_device(resident());
                 *index = bv2_.as<int32_t>();
@@ -2292,6 +2393,9 @@ class EngineT : public EngineBase {
         if (info.needs_weights && call.objective != SUCC_SPACE_AWARE && call.objective != SUCC_EXPECTED_WEIGHT)
             FAIL(PBVI_EINVAL, std::string(info.who) + ": objective must be 0 (space-aware) or 1 (expected weight)");
         if (info.needs_weights && !sw_set_) FAIL(PBVI_EINVAL, std::string(info.who) + ": no state weights set (call pbvi_state_weights_set)");
+        if (info.needs_state_policy && call.rule != STATE_POLICY_MLS && call.rule != STATE_POLICY_VOTING && call.rule != STATE_POLICY_THOMPSON)
+            FAIL(PBVI_EINVAL, std::string(info.who) + ": rule must be 0 (most likely state), 1 (voting) or 2 (Thompson)");
+        if (info.needs_state_policy && !sp_set_) FAIL(PBVI_EINVAL, std::string(info.who) + ": no state policy set (call pbvi_state_policy_set)");
         if (n_steps < 1) FAIL(PBVI_EINVAL, "rollout: T must be at least 1");
         if (source == ROLLOUT_Q && mode_ != PBVI_SPARSE)
             FAIL(PBVI_EUNSUPPORTED, "rollout: lookahead = 1 is not available on a PBVI_DENSE engine (create it with PBVI_SPARSE)");
@@ -2388,7 +2492,7 @@ class EngineT : public EngineBase {
         int* d_count = ro_dst_.as<int>() + n0;
         int oc = 0;
         for (int64_t t = 0; t < n_steps; ++t) {
-            if ((rc = rollout_stage(call, &rs.index))) return rc;
+            if ((rc = rollout_stage(call, t, ro_orig_[oc].as<int32_t>(), &rs.index))) return rc;
             rs.n = (int)blk_.B;
             rs.t = (int)t;
             rs.perm = blk_.sorted ? blk_.perm.as<int32_t>() : nullptr;
@@ -2814,6 +2918,7 @@ class EngineT : public EngineBase {
         ub_count_ = ub_entries_ = 0;                         // (so were the point store's)
         ub_corner_ = false;
         sw_set_ = false;                                     // (the weights were a working buffer)
+        sp_set_ = false;                                     // (so was the state policy's table)
         block_emptied();
         store_rows_[0] = store_rows_[1] = 0;
         snz_rows_ = sbt_rows_ = 0;
@@ -5505,7 +5610,8 @@ int pbvi_rollout_env(pbvi_engine_t* e, int policy, const int32_t* alpha_actions,
                      uint8_t* out_lost) {
     using namespace pbvi;
     NEED(e);
-    // (the step loop knows a fourth source, pbvi_rollout_space_aware's: this entry point's numbers are refused here)
+    // (the step loop knows two more sources, pbvi_rollout_space_aware's and pbvi_rollout_state_policy's: this entry point's
+    // numbers are refused here)
     if (policy != pbvi::ROLLOUT_VALUE_MAX && policy != pbvi::ROLLOUT_Q && policy != pbvi::ROLLOUT_INFOTAXIS)
         FAIL(PBVI_EINVAL, "rollout_env: policy must be 0 (value-max), 1 (Q) or 2 (infotaxis)");
     pbvi::RolloutCall c = rollout_call(start_states, end_mask, first_sim_id, seed, T, out_states, out_actions, out_observations, out_steps);
@@ -5542,6 +5648,40 @@ int pbvi_rollout_space_aware(pbvi_engine_t* e, int objective, int use_env, const
     pbvi::RolloutCall c = rollout_call(start_states, end_mask, first_sim_id, seed, T, out_states, out_actions, out_observations, out_steps);
     c.source = pbvi::ROLLOUT_SPACE_AWARE;
     c.objective = objective;
+    c.env = use_env != 0;
+    c.end_observation = end_observation;
+    c.shifts = shifts;
+    c.out_lost = use_env ? out_lost : nullptr;
+    const int64_t n0 = e->impl->beliefs_count();
+    const int rc = e->impl->rollout(c);
+    if (rc == PBVI_OK && !use_env && out_lost && n0 > 0) memset(out_lost, 0, (size_t)n0);   // nothing is lost in the model's world
+    return rc;
+}
+int pbvi_state_policy_set(pbvi_engine_t* e, const int32_t* state_actions) {
+    NEED(e);
+    return e->impl->state_policy_set(state_actions);
+}
+int pbvi_state_policy_clear(pbvi_engine_t* e) {
+    NEED(e);
+    return e->impl->state_policy_clear();
+}
+int pbvi_state_policy(pbvi_engine_t* e, int rule, uint64_t seed, uint64_t first_sim_id, int64_t t, const double* uniforms,
+                      int32_t* out_action, int32_t* out_state, double* out_votes) {
+    NEED(e);
+    return e->impl->state_policy(rule, seed, first_sim_id, t, uniforms, out_action, out_state, out_votes);
+}
+int pbvi_rollout_state_policy(pbvi_engine_t* e, int rule, int use_env, const int32_t* start_states, const uint8_t* end_mask,
+                              int end_observation, const int64_t* shifts, uint64_t first_sim_id, uint64_t seed, int64_t T,
+                              int32_t* out_states, int32_t* out_actions, int32_t* out_observations, int32_t* out_steps,
+                              uint8_t* out_lost) {
+    using namespace pbvi;
+    NEED(e);
+    if (use_env != 0 && use_env != 1) FAIL(PBVI_EINVAL, "rollout_state_policy: use_env must be 0 (the model's world) or 1 (the environment)");
+    if (!use_env && (end_observation != -1 || shifts != nullptr))
+        FAIL(PBVI_EINVAL, "rollout_state_policy: end_observation and shifts belong to an environment (use_env = 0 takes -1 and NULL)");
+    pbvi::RolloutCall c = rollout_call(start_states, end_mask, first_sim_id, seed, T, out_states, out_actions, out_observations, out_steps);
+    c.source = pbvi::ROLLOUT_STATE_POLICY;
+    c.rule = rule;
     c.env = use_env != 0;
     c.end_observation = end_observation;
     c.shifts = shifts;

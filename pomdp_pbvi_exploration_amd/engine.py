@@ -41,6 +41,7 @@ EXPORTS = [
     'pbvi_upper_reset', 'pbvi_upper_append', 'pbvi_upper_count', 'pbvi_upper_bound', 'pbvi_upper_q',
     'pbvi_state_weights_set', 'pbvi_state_weights_clear', 'pbvi_space_aware', 'pbvi_rollout_space_aware',
     'pbvi_fib_value_iteration',
+    'pbvi_state_policy_set', 'pbvi_state_policy_clear', 'pbvi_state_policy', 'pbvi_rollout_state_policy',
 ]
 
 
@@ -150,6 +151,11 @@ def load_library(path: str = LIB_PATH):
         'pbvi_space_aware': (C.c_int, [vp, C.c_int, f64p, i32p, f64p]),
         'pbvi_rollout_space_aware': (C.c_int, [vp, C.c_int, C.c_int, i32p, u8p, C.c_int, C.POINTER(C.c_int64), C.c_uint64,
                                                C.c_uint64, C.c_int64, i32p, i32p, i32p, i32p, u8p]),
+        'pbvi_state_policy_set': (C.c_int, [vp, i32p]),
+        'pbvi_state_policy_clear': (C.c_int, [vp]),
+        'pbvi_state_policy': (C.c_int, [vp, C.c_int, C.c_uint64, C.c_uint64, C.c_int64, f64p, i32p, i32p, f64p]),
+        'pbvi_rollout_state_policy': (C.c_int, [vp, C.c_int, C.c_int, i32p, u8p, C.c_int, C.POINTER(C.c_int64), C.c_uint64,
+                                                C.c_uint64, C.c_int64, i32p, i32p, i32p, i32p, u8p]),
         'pbvi_beliefs_fetch': (C.c_int, [vp, vp]),
         'pbvi_beliefs_count': (C.c_int64, [vp]),
         'pbvi_mdp_value_iteration': (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, i32p, f64p, f64p, f64p,
@@ -1133,6 +1139,55 @@ class Engine:
         out = (f, act.astype(np.int64))
         return out + (terms,) if want_terms else out
 
+    # -- state policies: the per-state action table, MLS / voting / Thompson of the resident block ------------------ #
+    STATE_POLICY_RULES = {'mls': 0, 'voting': 1, 'thompson': 2}
+
+    def set_state_policy(self, state_actions) -> None:
+        """The per-state action table of ``state_policy_resident`` / ``rollout_state_policy``: ``state_actions [S]`` with every
+        entry in ``[0, A)`` (``pbvi_state_policy_set``) -- a policy of the underlying MDP.  Touches nothing else."""
+        sa = np.asarray(state_actions)
+        if sa.shape != (self.S,):
+            raise ValueError('state_actions must be [S]')
+        if sa.size and (sa.min() < -(1 << 31) or sa.max() >= 1 << 31):
+            raise ValueError('state_actions entries must be in [0, A)')
+        sa = np.ascontiguousarray(sa, dtype=np.int32)
+        self._ck(self._lib.pbvi_state_policy_set(self._h, _p(sa, C.c_int32)))
+
+    def clear_state_policy(self) -> None:
+        """No state policy table; its device memory is returned (``pbvi_state_policy_clear``)."""
+        self._ck(self._lib.pbvi_state_policy_clear(self._h))
+
+    def state_policy_resident(self, rule: int, seed: int = 0, first_sim_id: int = 0, t: int = 0, uniforms=None,
+                              want_state: bool = False, want_votes: bool = False):
+        """The state policy ``rule`` for every belief of the resident block (``pbvi_state_policy``): ``0`` the table's action
+        in the most likely state, ``1`` the action with the largest vote ``W[a] = sum_{s: pi(s) = a} b[s]``, ``2`` the
+        table's action in a state drawn from the belief (Thompson).  Rule 2 draws with ``uniforms [B]`` when given (entries in
+        ``[0, 1]``), else with ``uniform01(splitmix64(seed, first_sim_id + b), 2**33 + t)``.  Returns ``actions [B]``;
+        ``want_state`` appends the state acted on (``-1`` for voting), ``want_votes`` (rule 1) appends ``W [B,A]``.  Needs a
+        table (``set_state_policy``), no alpha set, and leaves the block where it is."""
+        if not (0 <= int(seed) < 1 << 64 and 0 <= int(first_sim_id) < 1 << 64):
+            raise ValueError('seed and first_sim_id must fit an unsigned 64-bit integer')
+        if not -(1 << 63) <= int(t) < 1 << 63:
+            raise ValueError('t must be in [0, 2**31)')
+        if want_votes and int(rule) != 1:
+            raise ValueError('votes belong to rule 1 (voting)')
+        u = None
+        if uniforms is not None:
+            u = np.ascontiguousarray(uniforms, dtype=np.float64)
+            if u.shape != (self.B,):
+                raise ValueError('uniforms must be [B]')
+        act = np.empty(self.B, dtype=np.int32)
+        st = np.empty(self.B, dtype=np.int32) if want_state else None
+        votes = np.empty((self.B, self.A), dtype=np.float64) if want_votes else None
+        self._ck(self._lib.pbvi_state_policy(self._h, int(rule), int(seed), int(first_sim_id), int(t), _p(u, C.c_double),
+                                             _p(act, C.c_int32), _p(st, C.c_int32), _p(votes, C.c_double)))
+        out = (act.astype(np.int64),)
+        if want_state:
+            out += (st.astype(np.int64),)
+        if want_votes:
+            out += (votes,)
+        return out if len(out) > 1 else out[0]
+
     # -- HSVI upper bound: device point store, sawtooth, bound-greedy action values -------------------------------- #
     def upper_reset(self, corner) -> None:
         """Empty the point store of the upper bound and set the corner values ``c [S]`` (``pbvi_upper_reset``)."""
@@ -1394,6 +1449,17 @@ class Engine:
         shp = self._shifts_pointer(shifts)
         return self._rollout_call(lambda ss, em, *tail: self._lib.pbvi_rollout_space_aware(
             self._h, int(objective), int(bool(use_env)), ss, em, int(end_observation), shp, *tail),
+            start_states, end_mask, seed, T, first_sim_id, with_lost=True)
+
+    def rollout_state_policy(self, start_states, end_mask, seed: int, T: int, first_sim_id: int = 0, rule: int = 0,
+                             use_env: bool = False, shifts=None, end_observation: int = -1):
+        """``rollout`` with a state policy (``pbvi_rollout_state_policy``): every step takes ``state_policy_resident(rule)``'s
+        action, Thompson with the uniform ``uniform01(splitmix64(seed, id), 2**33 + t)`` of the simulation and step.
+        ``use_env``, ``shifts``, ``end_observation`` and the return value ``(states, actions, observations, steps, lost)`` are
+        ``rollout_space_aware``'s."""
+        shp = self._shifts_pointer(shifts)
+        return self._rollout_call(lambda ss, em, *tail: self._lib.pbvi_rollout_state_policy(
+            self._h, int(rule), int(bool(use_env)), ss, em, int(end_observation), shp, *tail),
             start_states, end_mask, seed, T, first_sim_id, with_lost=True)
 
     def fetch_beliefs(self) -> np.ndarray:

@@ -1642,10 +1642,11 @@ def rollout_numpy(model, alpha, alpha_actions, beliefs, start_states, seed: int,
 
 
 def _rollout_loop(m, block, choose, s, seed: int, first_sim_id: int, T: int, table_dtype, return_beliefs: bool,
-                  observe=None):
+                  observe=None, choose_draws: bool = False):
     """The step loop of the counter-based rollouts (``rollout_numpy``, ``rollout_infotaxis_numpy``, ``rollout_env_numpy``):
     ``choose()`` gives the actions of the beliefs ``block`` holds; the uniform, the done-filter and the Bayes step are the
-    same for every policy.  ``m``: ``_rollout_tables``' tables, ``s``: the validated start states.
+    same for every policy.  ``m``: ``_rollout_tables``' tables, ``s``: the validated start states.  ``choose_draws``: the
+    policy draws itself (Thompson) and is called as ``choose(t, ids)`` with the step and the running simulations' global ids.
 
     ``observe=None``: the ``(observation, successor)`` pair comes from the model's joint row ``RTO[s, a, :, :]`` and a belief
     is always normalised -- ``pbvi_rollout``'s step.  ``observe(t, rows, ids, a, sn, done)``: ``pbvi_rollout_env``'s step --
@@ -1675,7 +1676,7 @@ def _rollout_loop(m, block, choose, s, seed: int, first_sim_id: int, T: int, tab
     for t in range(T):
         if alive.size == 0:
             break
-        a = choose()
+        a = choose(t, ids[alive]) if choose_draws else choose()
         if observe is None:
             k = rollout_draw(rto[s, a], rollout_uniform(seed, ids[alive], t))
             o, sn = k // R, m.reachable_states[s, a, k % R]
@@ -1842,7 +1843,8 @@ def rollout_env_numpy(model, env, policy: int, alpha, alpha_actions, beliefs, st
     return _rollout_env_loop(m, env, block, choose, s, seed, first_sim_id, T, table_dtype, return_beliefs)
 
 
-def _rollout_env_loop(m, env, block, choose, s, seed: int, first_sim_id: int, T: int, table_dtype, return_beliefs: bool):
+def _rollout_env_loop(m, env, block, choose, s, seed: int, first_sim_id: int, T: int, table_dtype, return_beliefs: bool,
+                      choose_draws: bool = False):
     """``_rollout_loop`` against ``env``, for whatever policy ``choose`` is (``rollout_env_numpy``,
     ``rollout_space_aware_numpy``): the environment's checks, then the observation hook -- the frame of the simulation's
     shift, or a draw from the table's row with the second uniform; ``env.end_observation`` on landing in an end state."""
@@ -1856,7 +1858,7 @@ def _rollout_env_loop(m, env, block, choose, s, seed: int, first_sim_id: int, T:
             o = rollout_draw(env.obs_prob[sn, a], rollout_uniform(seed, ids, (1 << 32) + t))
         return np.where(done, end_obs, o) if end_obs >= 0 else o
 
-    return _rollout_loop(m, block, choose, s, seed, first_sim_id, T, table_dtype, return_beliefs, observe)
+    return _rollout_loop(m, block, choose, s, seed, first_sim_id, T, table_dtype, return_beliefs, observe, choose_draws)
 
 
 # --------------------------------------------------------------------------- #
@@ -2076,12 +2078,184 @@ def rollout_space_aware_numpy(model, beliefs, start_states, weights, seed: int, 
     return _rollout_env_loop(m, env, block, choose, s, seed, first_sim_id, T, table_dtype, return_beliefs)
 
 
-class _HostBeliefBlock:
-    """Belief block of the parallel simulator held in NumPy (reference CPU statements, ``:3029``, ``:3306-3311``)."""
+# --------------------------------------------------------------------------- #
+# State policies: most likely state, action voting, Thompson sampling (what ``pbvi_state_policy`` computes).  All three act
+# through a policy of the underlying MDP, ``state_actions [S]``.  The sums are sequential fp64 walks over chunks of 256
+# states, combined in chunk order (``include/pbvi_hip.h``), so host and device agree bit for bit.
+# --------------------------------------------------------------------------- #
+STATE_POLICY_RULES = {'mls': 0, 'voting': 1, 'thompson': 2}
+STATE_POLICY_CHUNK = 256
+THOMPSON_STREAM = 1 << 33                # Thompson's counter is 2^33 + t: beside the draws' t and 2^32 + t
 
-    def __init__(self, model: Model, value_function: ValueFunction, beliefs: np.ndarray):
+
+def _state_policy_rule(rule) -> int:
+    r = STATE_POLICY_RULES.get(rule, rule) if isinstance(rule, str) else rule
+    if isinstance(r, bool) or r not in (0, 1, 2):
+        raise ValueError(f"rule must be 0 / 'mls', 1 / 'voting' or 2 / 'thompson', not {rule!r}")
+    return int(r)
+
+
+def _state_actions(S: int, A: int, state_actions) -> np.ndarray:
+    sa = np.asarray(state_actions)
+    if sa.shape != (S,) or not np.issubdtype(sa.dtype, np.integer) or (S and (sa.min() < 0 or sa.max() >= A)):
+        raise ValueError('state_actions must be [S] integers in [0, A)')
+    return sa.astype(np.int64)
+
+
+def state_actions_from(value_function) -> np.ndarray:
+    """The state policy of an action-labelled solution (``VI_Solver`` or ``FIB_Solver``): ``actions[first argmax_v
+    alpha_v[s]]`` for every state ``s``, ``[S]`` int64."""
+    vf = value_function.to_cpu() if getattr(value_function, 'is_on_gpu', False) else value_function
+    alpha = np.asarray(vf.alpha_vector_array, dtype=np.float64)
+    return np.asarray(vf.actions, dtype=np.int64)[np.argmax(alpha, axis=0)]
+
+
+def _chunked(beliefs: np.ndarray) -> np.ndarray:
+    """``beliefs [n,S]`` as ``[n, C, 256]`` fp64, the last chunk filled with ``+0.0`` (which adds nothing to a sum)."""
+    b = np.asarray(beliefs, dtype=np.float64)
+    n, S = b.shape
+    C = -(-S // STATE_POLICY_CHUNK)
+    out = np.zeros((n, C * STATE_POLICY_CHUNK))
+    out[:, :S] = b
+    return out.reshape(n, C, STATE_POLICY_CHUNK)
+
+
+def _first_greater(x: np.ndarray) -> np.ndarray:
+    """The first index of each row whose entry is strictly greater than every earlier one; a NaN never wins."""
+    return np.argmax(np.where(np.isnan(x), -np.inf, x), axis=1)
+
+
+def thompson_state_numpy(beliefs, u) -> np.ndarray:
+    """The state Thompson sampling draws from each row of ``beliefs [n,S]`` with its uniform ``u [n]`` in ``[0, 1]``: with
+    ``q_c`` the sequential prefix sums of ``b`` inside chunk ``c`` (256 states), ``m_c = q_c[last]``, ``P_c = P_{c-1} + m_c``
+    and ``target = u * P_{C-1}``: the chunk ``c*`` is the first with ``target < P_c`` (else the last with ``m_c > 0``), and the
+    state the first ``j`` of it with ``target - P_{c*-1} < q_{c*}[j]`` (else its last with ``b > 0``).  The drawn state has
+    positive mass."""
+    q = np.cumsum(_chunked(beliefs), axis=2)                    # (np.cumsum adds sequentially)
+    n, C, _ = q.shape
+    u = np.asarray(u, dtype=np.float64)
+    if u.shape != (n,) or not np.all((u >= 0.0) & (u <= 1.0)):
+        raise ValueError('u must be [n] with entries in [0, 1]')
+    rows = np.arange(n)
+    m = q[:, :, -1]
+    P = np.cumsum(m, axis=1)
+    target = u * P[:, -1]
+    hit = target[:, None] < P
+    c = np.argmax(hit, axis=1)
+    none = ~hit.any(axis=1)
+    if none.any():
+        pos = m[none] > 0
+        c[none] = np.where(pos.any(axis=1), C - 1 - np.argmax(pos[:, ::-1], axis=1), 0)
+    r = target - np.where(c > 0, P[rows, np.maximum(c - 1, 0)], 0.0)
+    qc = q[rows, c]
+    hit = r[:, None] < qc
+    j = np.argmax(hit, axis=1)
+    none = ~hit.any(axis=1)
+    if none.any():
+        bc = _chunked(beliefs)[rows[none], c[none]] > 0
+        j[none] = np.where(bc.any(axis=1), STATE_POLICY_CHUNK - 1 - np.argmax(bc[:, ::-1], axis=1), 0)
+    return c * STATE_POLICY_CHUNK + j
+
+
+def state_policy_votes(beliefs, state_actions, A: int) -> np.ndarray:
+    """``W [n,A]``: ``W_c[a]`` = the sequential sum over chunk ``c`` (256 states, ascending) of ``b[s]`` where
+    ``state_actions[s] == a``; ``W[a]`` = the ``W_c[a]`` added in chunk order."""
+    bc = _chunked(beliefs)
+    n, C, L = bc.shape
+    sa = np.full(C * L, -1, dtype=np.int64)
+    sa[:state_actions.shape[0]] = state_actions
+    sa = sa.reshape(C, L)
+    W = np.zeros((n, A))
+    for a in range(A):
+        Wc = np.cumsum(np.where(sa[None] == a, bc, 0.0), axis=2)[:, :, -1]     # (+0.0 leaves the bits of a sum >= +0.0)
+        W[:, a] = np.cumsum(Wc, axis=1)[:, -1]
+    return W
+
+
+def state_policy_numpy(beliefs, state_actions, rule, u=None, table_dtype=np.float64, action_count=None):
+    """The state policy ``rule`` for every row of ``beliefs [n,S]``, on the host: what ``pbvi_state_policy`` computes on the
+    device, bit for bit.  ``beliefs`` are cast to ``table_dtype``, the engine's number format, and widened.  Returns
+    ``(action [n], state [n], votes)``:
+        rule 0 / ``'mls'``:       the table's action in the first maximum of ``b``; ``state`` = that state; ``votes`` ``None``
+        rule 1 / ``'voting'``:    the first maximum of ``votes = state_policy_votes(...)`` ``[n,A]``; ``state`` = -1
+        rule 2 / ``'thompson'``:  the table's action in ``thompson_state_numpy(b, u)``; ``state`` = that state
+    ``action_count``: the model's ``A``, the width of ``votes`` (default ``max(state_actions) + 1``)."""
+    return _state_policy(beliefs, state_actions, action_count, rule, u, table_dtype)
+
+
+def _state_policy(beliefs, state_actions, A, rule, u, table_dtype):
+    rule = _state_policy_rule(rule)
+    b = np.asarray(beliefs, dtype=table_dtype).astype(np.float64)
+    if b.ndim != 2:
+        raise ValueError('beliefs must be [n, S]')
+    sa = np.asarray(state_actions)
+    A = int(A) if A is not None else (int(sa.max()) + 1 if sa.size else 1)
+    sa = _state_actions(b.shape[1], A, sa)
+    if u is not None and rule != 2:
+        raise ValueError('u belongs to rule 2 (Thompson)')
+    if rule == 0:
+        s = _first_greater(b)
+        return sa[s], s, None
+    if rule == 1:
+        W = state_policy_votes(b, sa, A)
+        return _first_greater(W), np.full(b.shape[0], -1, dtype=np.int64), W
+    if u is None:
+        raise ValueError('Thompson sampling needs its uniforms u [n]')
+    s = thompson_state_numpy(b, u)
+    return sa[s], s, None
+
+
+def thompson_uniform(seed: int, sim_ids, t) -> np.ndarray:
+    """Thompson sampling's uniform of simulation ``i`` at step ``t``: ``rollout_uniform(seed, i, 2**33 + t)``, a third
+    stream beside the simulator's ``t`` and ``2**32 + t`` (``t < 2**31``)."""
+    return rollout_uniform(seed, sim_ids, THOMPSON_STREAM + int(t))
+
+
+def rollout_state_policy_numpy(model, beliefs, start_states, state_actions, rule, seed: int, first_sim_id: int, T: int,
+                               table_dtype=np.float64, return_beliefs: bool = False, env=None):
+    """``rollout_numpy`` with a state policy, on the host: what ``pbvi_rollout_state_policy`` computes on the device.  Per
+    step and running simulation the action is ``state_policy_numpy(b, state_actions, rule, u, table_dtype)``'s, Thompson
+    with ``u = thompson_uniform(seed, id, t)``; the beliefs are held in ``table_dtype`` between the steps, as the engine
+    holds them.  ``env=None``: the model's world, with ``rollout_numpy``'s return value; ``env``: the draw, the observation,
+    the lost rule and the return value (``lost [n]`` last) of ``rollout_env_numpy``."""
+    rule = _state_policy_rule(rule)
+    if int(T) >= 1 << 31:
+        raise ValueError('T must be below 2**31')
+    if env is not None and not isinstance(env, (FrameEnvironment, TableEnvironment)):
+        raise ValueError('env must be a FrameEnvironment or a TableEnvironment')
+    m, T, b, s, _, _ = _rollout_inputs(model, beliefs, start_states, T)
+    sa = _state_actions(m.state_count, m.action_count, state_actions)
+    block = _HostBeliefBlock(m, None, b, store_dtype=table_dtype)
+
+    def choose(t, ids):
+        u = thompson_uniform(seed, ids, t) if rule == 2 else None
+        return block.state_policy_actions(sa, rule, u, table_dtype)
+
+    if env is None:
+        return _rollout_loop(m, block, choose, s, seed, first_sim_id, T, table_dtype, return_beliefs, choose_draws=True)
+    return _rollout_env_loop(m, env, block, choose, s, seed, first_sim_id, T, table_dtype, return_beliefs, choose_draws=True)
+
+
+class _HostBeliefBlock:
+    """Belief block of the parallel simulator held in NumPy (reference CPU statements, ``:3029``, ``:3306-3311``).
+    ``store_dtype``: the beliefs are rounded to that format after every step, as an engine of that format stores them."""
+
+    def __init__(self, model: Model, value_function: ValueFunction, beliefs: np.ndarray, store_dtype=None):
         self.m, self.b = model, beliefs
         self.alpha = None if value_function is None else value_function.alpha_vector_array      # (infotaxis has none)
+        self.store_dtype = None if store_dtype is None or np.dtype(store_dtype) == np.float64 else np.dtype(store_dtype)
+        self._stored()
+
+    def _stored(self) -> None:
+        if self.store_dtype is not None:
+            self.b = self.b.astype(self.store_dtype).astype(np.float64)
+
+    def count(self) -> int:
+        return self.b.shape[0]
+
+    def state_policy_actions(self, state_actions, rule: int = 0, u=None, table_dtype=np.float64) -> np.ndarray:
+        """The state policy ``rule`` (``state_policy_numpy``) of every belief of the block; ``u``: Thompson's uniforms."""
+        return _state_policy(self.b, state_actions, self.m.action_count, rule, u, table_dtype)[0]
 
     def best_vectors(self) -> np.ndarray:
         return np.argmax(np.matmul(self.b, self.alpha.T), axis=1)
@@ -2112,6 +2286,7 @@ class _HostBeliefBlock:
         nb = self._push(actions, observations)
         nb /= np.sum(nb, axis=1)[:, None]
         self.b = nb[keep]
+        self._stored()
 
     def advance_or_lose(self, actions: np.ndarray, observations: np.ndarray, keep: np.ndarray) -> np.ndarray:
         """``advance`` with the lost rule of ``rollout_env_numpy``: a kept row whose un-normalised mass ``Z`` is 0 or not
@@ -2122,6 +2297,7 @@ class _HostBeliefBlock:
         lost = keep & ((z == 0) | ~np.isfinite(z))
         go = keep & ~lost
         self.b = nb[go] / z[go][:, None]
+        self._stored()
         return lost
 
 
@@ -2175,6 +2351,24 @@ class _DeviceBeliefBlock:
             self.eng.set_state_weights(weights)
             self._weights = weights
         return self.each(lambda: self.eng.space_aware_resident(objective)[1])
+
+    def count(self) -> int:
+        return self.eng.B if self.chunks is None else sum(c.shape[0] for c in self.chunks)
+
+    def state_policy_actions(self, state_actions, rule: int = 0, u=None) -> np.ndarray:
+        """The state policy ``rule`` (``pbvi_state_policy``) of every belief of the block; ``u``: Thompson's uniforms, one
+        per belief.  The table is uploaded once per block."""
+        if getattr(self, '_state_actions', None) is not state_actions:
+            self.eng.set_state_policy(state_actions)
+            self._state_actions = state_actions
+        if self.chunks is None:
+            return self.eng.state_policy_resident(rule, uniforms=u)
+        out, i0 = [], 0
+        for c in self.chunks:
+            self.eng.set_beliefs(c)
+            out.append(self.eng.state_policy_resident(rule, uniforms=None if u is None else u[i0:i0 + c.shape[0]]))
+            i0 += c.shape[0]
+        return np.concatenate(out) if out else np.zeros(0, dtype=np.int64)
 
     def advance(self, actions: np.ndarray, observations: np.ndarray, keep: np.ndarray) -> None:
         if self.chunks is None:
@@ -2541,6 +2735,45 @@ class SpaceAware_Agent(Agent):
         end_obs = -1 if env is None else env.end_observation
         return lambda s0, first, sh: eng.rollout_space_aware(s0, end_mask, seed, T, first_sim_id=first, objective=self.objective,
                                                              use_env=env is not None, shifts=sh, end_observation=end_obs)
+
+
+class StatePolicy_Agent(Agent):
+    """The heuristics that act through a policy ``pi(s)`` of the underlying MDP: ``rule='mls'`` plays ``pi`` of the most
+    likely state, ``'voting'`` the action with the largest vote ``sum_{s: pi(s) = a} b(s)``, ``'thompson'`` ``pi`` of a state
+    drawn from the belief (``state_policy_numpy``) -- the baselines tabulated beside infotaxis and QMDP.  ``policy``: the
+    table ``[S]`` itself, or an action-labelled ``ValueFunction`` (a ``VI_Solver`` or ``FIB_Solver`` solution), read with
+    ``state_actions_from``.  A model on the GPU (``model.to_gpu()``) has the HIP engine evaluate it (``pbvi_state_policy``,
+    ``pbvi_rollout_state_policy``).  ``simulate``, ``run_n_simulations`` and ``run_n_simulations_parallel(...,
+    device_rng_seed=, environment=)`` are ``Agent``'s with this policy.
+
+    Thompson sampling is reproducible exactly with ``device_rng_seed`` only: simulation ``i`` then draws with
+    ``thompson_uniform(seed, i, t)`` on the host and on the device alike.  In the paths that use NumPy's global stream (no
+    ``device_rng_seed``; ``get_best_action``, ``simulate``) it takes ``np.random.random(n)`` for the ``n`` beliefs of the
+    step, before the simulator's draws of that step."""
+
+    def __init__(self, model: Model, policy, rule='mls') -> None:
+        super().__init__(model, None)
+        self.rule = _state_policy_rule(rule)
+        table = state_actions_from(policy) if isinstance(policy, ValueFunction) else policy
+        self.state_actions = _state_actions(model.state_count, model.action_count, table)
+
+    def _on_gpu(self) -> bool:
+        return bool(self.model.is_on_gpu)
+
+    def _block_actions(self, block) -> np.ndarray:
+        u = np.random.random(block.count()) if self.rule == 2 else None
+        return block.state_policy_actions(self.state_actions, self.rule, u)
+
+    def _upload(self, eng) -> None:
+        eng.set_state_policy(self.state_actions)
+
+    def _host_rollout(self, model: Model, b0: np.ndarray, start_states: np.ndarray, seed: int, T: int, env):
+        return rollout_state_policy_numpy(model, b0, start_states, self.state_actions, self.rule, seed, 0, T, env=env)
+
+    def _device_rollout(self, eng, end_mask: np.ndarray, seed: int, T: int, env):
+        end_obs = -1 if env is None else env.end_observation
+        return lambda s0, first, sh: eng.rollout_state_policy(s0, end_mask, seed, T, first_sim_id=first, rule=self.rule,
+                                                              use_env=env is not None, shifts=sh, end_observation=end_obs)
 
 
 # --------------------------------------------------------------------------- #
