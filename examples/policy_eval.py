@@ -11,6 +11,7 @@ The reference publishes one timing for this step (sim_runtime_test.ipynb:223, BA
     python examples/policy_eval.py --policy expected-distance --device-sim 7   # greedy for the expected distance to the source
     python examples/policy_eval.py --policy fib --reach 5 --device-sim 7   # follow the Fast Informed Bound's rows (no FSVI solve)
     python examples/policy_eval.py --policy qmdp --reach 5 --device-sim 7  # ... or the MDP solution's (QMDP)
+    python examples/policy_eval.py --policy blind --device-sim 7   # follow the blind-policy lower bound's rows (no solve)
     python examples/policy_eval.py --policy thompson --device-sim 7   # MDP heuristics: mls, voting, thompson (pbvi_state_policy)
     python examples/policy_eval.py --device-sim 1 --environment frames    # observations from recorded frames (pbvi_rollout_env)
     python examples/policy_eval.py --device-sim 1 --environment table --env-flip 0.1   # a sensor that errs 10 % more often
@@ -24,7 +25,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
-from pomdp_pbvi_exploration_amd import FIB_Solver, FSVI_Solver, Model, set_quiet, synth   # noqa: E402
+from pomdp_pbvi_exploration_amd import Blind_Solver, FIB_Solver, FSVI_Solver, Model, set_quiet, synth   # noqa: E402
 from pomdp_pbvi_exploration_amd.pomdp import (Agent, FrameEnvironment, Infotaxis_Agent, SpaceAware_Agent,   # noqa: E402
                                               StatePolicy_Agent, TableEnvironment, record_frames, state_actions_from)
 from pomdp_pbvi_exploration_amd.mdp import VI_Solver                         # noqa: E402
@@ -47,9 +48,10 @@ def main():
                     help='counter-based simulator draws with this seed: the whole step loop runs in the engine '
                          '(pbvi_rollout) instead of drawing on the host from NumPy\'s stream')
     ap.add_argument('--policy', default='value', choices=['value', 'infotaxis', 'space-aware', 'expected-distance', 'qmdp', 'fib',
-                                                         'mls', 'voting', 'thompson'],
+                                                         'blind', 'mls', 'voting', 'thompson'],
                     help='value: solve with FSVI and follow the value function; qmdp / fib: no FSVI solve, follow the A rows of '
-                         'MDP value iteration / of the Fast Informed Bound (pbvi_fib_value_iteration); infotaxis: no solve, every step takes the '
+                         'MDP value iteration / of the Fast Informed Bound (pbvi_fib_value_iteration); blind: no solve, follow the A rows of '
+                         'the blind-policy lower bound, "always take action a" (pbvi_controller_value_iteration); infotaxis: no solve, every step takes the '
                          'action with the smallest expected entropy of the next belief (pbvi_infotaxis); space-aware: no '
                          'solve, greedy for log2(D + 2^(H-1) - 1/2) of the next belief, D its expected Manhattan distance to '
                          'the source and H its entropy in bits (pbvi_space_aware); expected-distance: greedy for D alone; mls / '
@@ -89,6 +91,14 @@ def main():
         policy = f'{args.policy} over the MDP policy ({len(h.iteration_times)} sweeps)'
         print(f'{policy}: solved in {time.perf_counter() - t0:.3f}s', flush=True)
         agent = StatePolicy_Agent(model.to_gpu(args.dtype), state_actions_from(vf), rule=args.policy)
+    elif args.policy == 'blind':
+        t0 = time.perf_counter()
+        vf, h = Blind_Solver(gamma=m.gamma, eps=1e-6).solve(model, use_gpu=True, print_progress=False)
+        policy = f'blind ({len(h.iteration_times)} sweeps)'
+        print(f'{policy}: {len(vf)} rows in {time.perf_counter() - t0:.3f}s', flush=True)
+        model.to_gpu(args.dtype)
+        vf = vf.to_gpu()
+        agent = Agent(vf.model, vf, lookahead=args.lookahead, gamma=m.gamma)
     elif args.policy in ('qmdp', 'fib'):
         t0 = time.perf_counter()
         vf, h = VI_Solver(gamma=m.gamma, eps=1e-6).solve(model, use_gpu=True, print_progress=False)
@@ -169,7 +179,7 @@ def main():
         elif args.policy in ('mls', 'voting', 'thompson'):
             host_agent = StatePolicy_Agent(model, agent.state_actions, rule=agent.rule)
         else:
-            host_agent = Agent(model, vf.to_cpu(), lookahead=args.lookahead, gamma=m.gamma)   # (value, qmdp, fib)
+            host_agent = Agent(model, vf.to_cpu(), lookahead=args.lookahead, gamma=m.gamma)   # (value, qmdp, fib, blind)
         np.random.seed(1)
         t0 = time.perf_counter()
         _, hh = host_agent.run_n_simulations_parallel(n=args.n, max_steps=args.cpu_steps, print_progress=False,

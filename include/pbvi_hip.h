@@ -774,6 +774,35 @@ int pbvi_fib_value_iteration(int device, int32_t S, int32_t A, int32_t O, int32_
                              int32_t* out_iterations);
 
 /*
+ * Exact value of a finite-state controller (policy graph) on the device; the blind-policy lower bound (Hauskrecht 1997;
+ * Blind_Solver.solve, the initial lower bound of HSVI with lower_init='blind') is the controller with N = A, a_n = n,
+ * succ[n][o] = n.  Node n takes action a_n = node_action[n] and moves to node succ[n][o] = node_succ[n][o] on observation o:
+ *   V'[n][s] = ER[s,a_n] + gamma * sum_o sum_r RTO[s,a_n,o,r] * V[succ[n][o]][rs[s,a_n,r]]
+ * as Jacobi sweeps (all of V' from the old V), repeated from v0 until max_{n,s} |V' - V| < max_change_limit
+ * (eps * gamma / (1 - gamma)) or `horizon` sweeps.  Every row of the fixed point is the value of a policy that can be run
+ * under partial observability, so the rows are valid alpha-vectors (a lower bound of the POMDP value); from a start below
+ * the fixed point (min ER / (1 - gamma)) the iterates rise towards it and a run stopped anywhere is still below it.  Always
+ * fp64.  Not tied to an engine handle.
+ * One sweep, operation for operation (products and sums un-fused; pomdp.controller_numpy is the same statement in NumPy,
+ * and rows and changes agree with it bit for bit on finite inputs), with a = a_n:
+ *   for o = 0..O-1:  acc_o = RTO[s,a,o,0] * V[succ[n][o]][rs[s,a,0]], then acc_o += RTO[s,a,o,r] * V[succ[n][o]][rs[s,a,r]],
+ *                    r = 1..R-1;   tot = acc_0, then tot += acc_o in order;
+ *   V'[n][s] = ER[s,a] + gamma * tot.
+ *   reach_states [S][A][R] int32, rto [S][A][O][R], exp_reward [S][A], node_action [N] int32, node_succ [N][O] int32,
+ *   v0 [N][S]   (NumPy C-order)
+ *   out_rows [N][S]: the rows of the last sweep that ran, row n the value of starting in node n; v0 itself for horizon = 0
+ *   out_changes [horizon] (may be NULL): max change of each sweep that ran;  out_iterations (may be NULL).
+ * PBVI_EINVAL (bad sizes, NULL tables, a negative horizon, a reachable state outside [0, S), a node action outside [0, A), a
+ * successor outside [0, N)) and PBVI_EUNSUPPORTED (S*A*O*R or N*ceil(S/256) beyond int32; sizes alone decide it, before any
+ * table is read) are decided before the device is touched.  PBVI_ENOMEM when the device has no room; a call leaves no
+ * device memory behind.
+ */
+int pbvi_controller_value_iteration(int device, int32_t S, int32_t A, int32_t O, int32_t R, const int32_t* reach_states,
+                                    const double* rto, const double* exp_reward, int32_t N, const int32_t* node_action,
+                                    const int32_t* node_succ, const double* v0, double gamma, double max_change_limit,
+                                    int32_t horizon, double* out_rows, double* out_changes, int32_t* out_iterations);
+
+/*
  * Belief walk of the FSVI-style expansions (PBVI_Solver.expand_fsvi / expand_fsvi_eg, src/pomdp.py:1895-1935; the
  * trajectory of (action, observation) pairs is simulated by the caller in the underlying MDP and does not depend
  * on the beliefs): n chained Bayes updates (Belief.update, :382-421) entirely on the device, in fp64,

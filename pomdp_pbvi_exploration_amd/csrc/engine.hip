@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "backup_kernels.h"
+#include "controller_kernels.h"
 #include "split_bf16.h"
 #include "state_policy_kernels.h"
 #include "upper_kernels.h"
@@ -5003,6 +5004,35 @@ static int mdp_value_iteration(int device, int S, int A, int R, const int32_t* r
 }
 
 // --------------------------------------------------------------------------- //
+// The model tables of the handle-free sweep entries below (FIB, controller evaluation) as their kernels read them: from
+// the caller's [S][A][..] order to rs [A][R][S], rto [A][O][R][S], er [A][S], so that with s across the lanes every table
+// load is coalesced.  Host work only.  False (and nothing to use) when a reachable state lies outside [0, S).
+// --------------------------------------------------------------------------- //
+struct SweepTables {
+    std::vector<int32_t> rs;
+    std::vector<double> rto, er;
+};
+static bool retile_sweep_tables(int S, int A, int O, int R, const int32_t* rs, const double* rto, const double* er,
+                                SweepTables& t) {
+    t.rs.resize((size_t)S * A * R);
+    t.rto.resize((size_t)S * A * R * O);
+    t.er.resize((size_t)S * A);
+    for (int s = 0; s < S; ++s)
+        for (int a = 0; a < A; ++a) {
+            t.er[(size_t)a * S + s] = er[(size_t)s * A + a];
+            for (int r = 0; r < R; ++r) {
+                const size_t src = ((size_t)s * A + a) * R + r;
+                if (rs[src] < 0 || rs[src] >= S) return false;
+                t.rs[((size_t)a * R + r) * S + s] = rs[src];
+            }
+            for (int o = 0; o < O; ++o)
+                for (int r = 0; r < R; ++r)
+                    t.rto[(((size_t)a * O + o) * R + r) * S + s] = rto[(((size_t)s * A + a) * O + o) * R + r];
+        }
+    return true;
+}
+
+// --------------------------------------------------------------------------- //
 // Fast Informed Bound (Hauskrecht 2000): the MDP sweep with the observation kept inside the maximisation,
 //   Q'(s,a) = ER[s,a] + gamma * sum_o max_a' sum_r RTO[s,a,o,r] * Q(rs[s,a,r], a')
 // One thread per (s, a), s fastest across lanes; tables re-tiled rs [A][R][S], rto [A][O][R][S], er [A][S] so every
@@ -5085,21 +5115,11 @@ static int fib_value_iteration(int device, int S, int A, int O, int R, const int
         FAIL(PBVI_EINVAL, "fib_value_iteration: bad arguments");
     if ((int64_t)S * A * O * R > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "fib_value_iteration: S*A*O*R exceeds int32");
     const size_t n_rs = (size_t)S * A * R, n_rto = n_rs * O, n_q = (size_t)S * A;
-    std::vector<int32_t> h_rs(n_rs);
-    std::vector<double> h_rto(n_rto), h_er(n_q), h_q(n_q);
+    SweepTables h;
+    if (!retile_sweep_tables(S, A, O, R, rs, rto, er, h)) FAIL(PBVI_EINVAL, "fib_value_iteration: reachable state out of range");
+    std::vector<double> h_q(n_q);
     for (int s = 0; s < S; ++s)
-        for (int a = 0; a < A; ++a) {
-            h_er[(size_t)a * S + s] = er[(size_t)s * A + a];
-            h_q[(size_t)s * A + a] = q0[(size_t)a * S + s];
-            for (int r = 0; r < R; ++r) {
-                const size_t src = ((size_t)s * A + a) * R + r;
-                if (rs[src] < 0 || rs[src] >= S) FAIL(PBVI_EINVAL, "fib_value_iteration: reachable state out of range");
-                h_rs[((size_t)a * R + r) * S + s] = rs[src];
-            }
-            for (int o = 0; o < O; ++o)
-                for (int r = 0; r < R; ++r)
-                    h_rto[(((size_t)a * O + o) * R + r) * S + s] = rto[(((size_t)s * A + a) * O + o) * R + r];
-        }
+        for (int a = 0; a < A; ++a) h_q[(size_t)s * A + a] = q0[(size_t)a * S + s];
     if (horizon == 0) {                                      // nothing to sweep: q0 comes back as it is
         memcpy(out_rows, q0, n_q * sizeof(double));
         if (out_iterations) *out_iterations = 0;
@@ -5123,9 +5143,9 @@ static int fib_value_iteration(int device, int S, int A, int O, int R, const int
     if ((rc = d_ch.ensure((size_t)horizon * sizeof(double)))) return rc;
     HIPCHK(hipStreamCreateWithFlags(&guard.st, hipStreamNonBlocking));
     hipStream_t st = guard.st;
-    HIPCHK(hipMemcpyAsync(d_rs.p, h_rs.data(), n_rs * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_rto.p, h_rto.data(), n_rto * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_er.p, h_er.data(), n_q * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_rs.p, h.rs.data(), n_rs * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_rto.p, h.rto.data(), n_rto * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_er.p, h.er.data(), n_q * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_q[0].p, h_q.data(), n_q * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(d_ch.p, 0, (size_t)horizon * sizeof(double), st));
     auto sweep = A <= 4 ? (A % 2 == 0 ? k_fib_sweep<4, true> : k_fib_sweep<4, false>)
@@ -5159,6 +5179,132 @@ static int fib_value_iteration(int device, int S, int A, int O, int R, const int
     HIPCHK(hipStreamSynchronize(st));
     for (int s = 0; s < S; ++s)
         for (int a = 0; a < A; ++a) out_rows[(size_t)a * S + s] = h_q[(size_t)s * A + a];
+    if (out_changes)
+        for (int it = 0; it < done; ++it) out_changes[it] = ch[(size_t)it];
+    if (out_iterations) *out_iterations = done;
+    return PBVI_OK;
+}
+
+// --------------------------------------------------------------------------- //
+// Finite-state controller evaluation (include/pbvi_hip.h; kernel in controller_kernels.hip): Jacobi sweeps of
+//   V'[n][s] = ER[s,a_n] + gamma * sum_o sum_r RTO[s,a_n,o,r] * V[succ[n][o]][rs[s,a_n,r]]
+// The nodes run on the device in the order of their actions (stable; rows and successors are renumbered on the way in
+// and the rows put back on the way out), so that nodes which share an action, and with it every table element, are
+// neighbours a register tile can cover.  A sweep does not depend on the numbering of the nodes: the result is the same,
+// bit for bit.  Batching, early exit and the buffer the result is read from are fib_value_iteration's.
+// --------------------------------------------------------------------------- //
+static int controller_value_iteration(int device, int S, int A, int O, int R, const int32_t* rs, const double* rto,
+                                      const double* er, int N, const int32_t* node_action, const int32_t* node_succ,
+                                      const double* v0, double gamma, double limit, int horizon, double* out_rows,
+                                      double* out_changes, int32_t* out_iterations) {
+    if (S <= 0 || A <= 0 || O <= 0 || R <= 0 || N <= 0 || horizon < 0 || !rs || !rto || !er || !node_action || !node_succ ||
+        !v0 || !out_rows)
+        FAIL(PBVI_EINVAL, "controller_value_iteration: bad arguments");
+    if ((int64_t)S * A * O * R > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "controller_value_iteration: S*A*O*R exceeds int32");
+    const int s_blocks = (S + 255) / 256;
+    if ((int64_t)N * s_blocks > 0x7fffffff)
+        FAIL(PBVI_EUNSUPPORTED, "controller_value_iteration: N*ceil(S/256) exceeds int32");
+    std::vector<int> per_action((size_t)A + 1, 0);           // nodes per action, then the first position of each action
+    for (int n = 0; n < N; ++n) {
+        if (node_action[n] < 0 || node_action[n] >= A) FAIL(PBVI_EINVAL, "controller_value_iteration: node action out of range");
+        ++per_action[(size_t)node_action[n] + 1];
+        for (int o = 0; o < O; ++o)
+            if (node_succ[(size_t)n * O + o] < 0 || node_succ[(size_t)n * O + o] >= N)
+                FAIL(PBVI_EINVAL, "controller_value_iteration: successor node out of range");
+    }
+    SweepTables h;
+    if (!retile_sweep_tables(S, A, O, R, rs, rto, er, h))
+        FAIL(PBVI_EINVAL, "controller_value_iteration: reachable state out of range");
+    const size_t n_rs = (size_t)S * A * R, n_rto = n_rs * O, n_er = (size_t)S * A, n_v = (size_t)N * S;
+    if (horizon == 0) {                                      // nothing to sweep: v0 comes back as it is
+        memcpy(out_rows, v0, n_v * sizeof(double));
+        if (out_iterations) *out_iterations = 0;
+        return PBVI_OK;
+    }
+    // the nodes in the order of their actions; a tile never crosses from one action to the next
+    const int most = *std::max_element(per_action.begin() + 1, per_action.end());
+    const int node_tile = most >= 2 ? CONTROLLER_NODE_TILE : 1;
+    std::vector<int32_t> tile_first;
+    for (int a = 0; a < A; ++a) {
+        if (node_tile > 1)
+            for (int k = 0; k < per_action[(size_t)a + 1]; k += node_tile) tile_first.push_back(per_action[(size_t)a] + k);
+        per_action[(size_t)a + 1] += per_action[(size_t)a];
+    }
+    tile_first.push_back(N);
+    const int tiles = node_tile > 1 ? (int)tile_first.size() - 1 : N;
+    std::vector<int32_t> order((size_t)N), pos((size_t)N), h_action((size_t)N), h_succ((size_t)N * O);
+    for (int n = 0; n < N; ++n) {
+        pos[(size_t)n] = per_action[(size_t)node_action[n]]++;
+        order[(size_t)pos[(size_t)n]] = n;
+    }
+    std::vector<double> h_v(n_v);
+    for (int p = 0; p < N; ++p) {
+        const size_t n = (size_t)order[(size_t)p];
+        h_action[(size_t)p] = node_action[n];
+        for (int o = 0; o < O; ++o) h_succ[(size_t)p * O + o] = pos[(size_t)node_succ[n * O + o]];
+        memcpy(h_v.data() + (size_t)p * S, v0 + n * S, (size_t)S * sizeof(double));
+    }
+    HIPCHK(hipSetDevice(device));
+    struct Guard {                                           // (in front of the buffers: they are released first)
+        hipStream_t st = nullptr;
+        ~Guard() {
+            if (st) (void)hipStreamDestroy(st);
+        }
+    } guard;
+    DevMem mem;
+    DevBuf d_rs{mem}, d_rto{mem}, d_er{mem}, d_action{mem}, d_succ{mem}, d_tiles{mem}, d_v[2]{{mem}, {mem}}, d_ch{mem};
+    int rc;
+    if ((rc = d_rs.ensure(n_rs * sizeof(int32_t)))) return rc;
+    if ((rc = d_rto.ensure(n_rto * sizeof(double)))) return rc;
+    if ((rc = d_er.ensure(n_er * sizeof(double)))) return rc;
+    if ((rc = d_action.ensure((size_t)N * sizeof(int32_t)))) return rc;
+    if ((rc = d_succ.ensure((size_t)N * O * sizeof(int32_t)))) return rc;
+    if ((rc = d_tiles.ensure(tile_first.size() * sizeof(int32_t)))) return rc;
+    if ((rc = d_v[0].ensure(n_v * sizeof(double)))) return rc;
+    if ((rc = d_v[1].ensure(n_v * sizeof(double)))) return rc;
+    if ((rc = d_ch.ensure((size_t)horizon * sizeof(double)))) return rc;
+    HIPCHK(hipStreamCreateWithFlags(&guard.st, hipStreamNonBlocking));
+    hipStream_t st = guard.st;
+    HIPCHK(hipMemcpyAsync(d_rs.p, h.rs.data(), n_rs * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_rto.p, h.rto.data(), n_rto * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_er.p, h.er.data(), n_er * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_action.p, h_action.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_succ.p, h_succ.data(), (size_t)N * O * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_tiles.p, tile_first.data(), tile_first.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_v[0].p, h_v.data(), n_v * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_ch.p, 0, (size_t)horizon * sizeof(double), st));
+    ControllerSweep cs{};
+    cs.S = S, cs.A = A, cs.O = O, cs.R = R, cs.N = N;
+    cs.rs = d_rs.as<int32_t>(), cs.rto = d_rto.as<double>(), cs.er = d_er.as<double>();
+    cs.node_action = d_action.as<int32_t>(), cs.node_succ = d_succ.as<int32_t>();
+    cs.node_tile = node_tile, cs.tiles = tiles, cs.tile_first = d_tiles.as<int32_t>();   // (tiles * s_blocks <= N * s_blocks)
+    cs.gamma = gamma, cs.limit = limit, cs.changes = d_ch.as<double>();
+    std::vector<double> ch((size_t)horizon, 0.0);
+    int done = 0;              // sweeps that ran
+    bool converged = false;
+    const int batch = 64;
+    for (int it0 = 0; it0 < horizon && !converged; it0 += batch) {
+        const int it1 = std::min(horizon, it0 + batch);
+        for (int it = it0; it < it1; ++it) {
+            cs.it = it, cs.v_in = d_v[it & 1].as<double>(), cs.v_out = d_v[(it + 1) & 1].as<double>();
+            HIPCHK(launch_controller_sweep(cs, st));
+        }
+        HIPCHK(hipMemcpyAsync(ch.data() + it0, d_ch.as<double>() + it0, (size_t)(it1 - it0) * sizeof(double),
+                              hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int it = it0; it < it1; ++it) {
+            done = it + 1;
+            if (ch[(size_t)it] < limit) {
+                converged = true;
+                break;
+            }
+        }
+    }
+    // sweep done-1 was the last to write: its V is in buffer done & 1 (the sweeps enqueued after it left at once)
+    HIPCHK(hipMemcpyAsync(h_v.data(), d_v[done & 1].p, n_v * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int p = 0; p < N; ++p)
+        memcpy(out_rows + (size_t)order[(size_t)p] * S, h_v.data() + (size_t)p * S, (size_t)S * sizeof(double));
     if (out_changes)
         for (int it = 0; it < done; ++it) out_changes[it] = ch[(size_t)it];
     if (out_iterations) *out_iterations = done;
@@ -5712,6 +5858,14 @@ int pbvi_fib_value_iteration(int device, int32_t S, int32_t A, int32_t O, int32_
                              int32_t* out_iterations) {
     return pbvi::fib_value_iteration(device, S, A, O, R, reach_states, rto, exp_reward, q0, gamma, max_change_limit,
                                      horizon, out_rows, out_changes, out_iterations);
+}
+
+int pbvi_controller_value_iteration(int device, int32_t S, int32_t A, int32_t O, int32_t R, const int32_t* reach_states,
+                                    const double* rto, const double* exp_reward, int32_t N, const int32_t* node_action,
+                                    const int32_t* node_succ, const double* v0, double gamma, double max_change_limit,
+                                    int32_t horizon, double* out_rows, double* out_changes, int32_t* out_iterations) {
+    return pbvi::controller_value_iteration(device, S, A, O, R, reach_states, rto, exp_reward, N, node_action, node_succ, v0,
+                                            gamma, max_change_limit, horizon, out_rows, out_changes, out_iterations);
 }
 
 int pbvi_belief_update(pbvi_engine_t* e, const int32_t* actions, const int32_t* observations, void* out_beliefs) {

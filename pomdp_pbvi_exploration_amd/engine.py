@@ -40,7 +40,7 @@ EXPORTS = [
     'pbvi_debug_score_probe', 'pbvi_debug_score_probe_fetch', 'pbvi_debug_refine_counts', 'pbvi_debug_value_max_route',
     'pbvi_upper_reset', 'pbvi_upper_append', 'pbvi_upper_count', 'pbvi_upper_bound', 'pbvi_upper_q',
     'pbvi_state_weights_set', 'pbvi_state_weights_clear', 'pbvi_space_aware', 'pbvi_rollout_space_aware',
-    'pbvi_fib_value_iteration',
+    'pbvi_fib_value_iteration', 'pbvi_controller_value_iteration',
     'pbvi_state_policy_set', 'pbvi_state_policy_clear', 'pbvi_state_policy', 'pbvi_rollout_state_policy',
 ]
 
@@ -162,6 +162,9 @@ def load_library(path: str = LIB_PATH):
                                                C.c_double, C.c_double, C.c_int32, f64p, f64p, i32p]),
         'pbvi_fib_value_iteration': (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i32p, f64p, f64p, f64p,
                                                C.c_double, C.c_double, C.c_int32, f64p, f64p, i32p]),
+        'pbvi_controller_value_iteration': (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i32p, f64p, f64p,
+                                                      C.c_int32, i32p, i32p, f64p, C.c_double, C.c_double, C.c_int32, f64p,
+                                                      f64p, i32p]),
         'pbvi_set_formulation': (C.c_int, [vp, C.c_int]),
         'pbvi_set_f64_screen': (C.c_int, [vp, C.c_int]),
         'pbvi_set_fused_projection': (C.c_int, [vp, C.c_int]),
@@ -362,6 +365,58 @@ def fib_value_iteration(reach_states: np.ndarray, rto: np.ndarray, exp_reward: n
     _check(lib.pbvi_fib_value_iteration(int(device), S, A, O, R, _p(rs, C.c_int32), _p(t, C.c_double), _p(er, C.c_double),
                                         _p(q, C.c_double), float(gamma), float(max_change_limit), int(horizon),
                                         _p(rows, C.c_double), _p(changes, C.c_double), C.byref(its)))
+    return rows, changes[:its.value]
+
+
+def controller_value_iteration(reach_states: np.ndarray, rto: np.ndarray, exp_reward: np.ndarray, node_action: np.ndarray,
+                               node_succ: np.ndarray, v0: np.ndarray, gamma: float, max_change_limit: float, horizon: int,
+                               device: int = 0):
+    """Value of a finite-state controller by Jacobi sweeps on the device (``pbvi_controller_value_iteration``;
+    ``pomdp.controller_numpy`` is the same definition on the host, bit for bit).  ``reach_states [S,A,R]``,
+    ``rto [S,A,O,R]``, ``exp_reward [S,A]``, ``node_action [N]``, ``node_succ [N,O]``, ``v0 [N,S]``.  Returns
+    ``(rows [N,S] f64, changes [iterations] f64)``.  Shapes, the horizon and the ranges of successor states, node actions and
+    successor nodes are checked before the device is touched (``ValueError``); ``S*A*O*R`` or ``N*ceil(S/256)`` beyond int32
+    is ``NotImplementedError``."""
+    lib = load_library()
+    reach_states, rto, node_action, node_succ = (np.asarray(x) for x in (reach_states, rto, node_action, node_succ))
+    if reach_states.ndim != 3 or rto.ndim != 4:
+        raise ValueError('controller_value_iteration: reach_states must be [S,A,R] and rto [S,A,O,R]')
+    S, A, R = reach_states.shape
+    O = rto.shape[2]
+    if node_action.ndim != 1 or node_succ.ndim != 2:
+        raise ValueError('controller_value_iteration: node_action must be [N] and node_succ [N,O]')
+    N = node_action.shape[0]
+    if rto.shape != (S, A, O, R) or np.shape(exp_reward) != (S, A) or node_succ.shape != (N, O) or np.shape(v0) != (N, S):
+        raise ValueError('controller_value_iteration: table shapes do not agree')
+    if min(S, A, O, R) <= 0:
+        raise ValueError('controller_value_iteration: empty tables')
+    if N <= 0:
+        raise ValueError('controller_value_iteration: no nodes')
+    if int(horizon) < 0:
+        raise ValueError('controller_value_iteration: negative horizon')
+    if S * A * O * R > 0x7fffffff:                       # (before any table is copied: the entry refuses it the same way)
+        raise NotImplementedError('controller_value_iteration: S*A*O*R exceeds int32')
+    if N * ((S + 255) // 256) > 0x7fffffff:
+        raise NotImplementedError('controller_value_iteration: N*ceil(S/256) exceeds int32')
+    if int(reach_states.min()) < 0 or int(reach_states.max()) >= S:
+        raise ValueError('reachable state out of range')
+    if int(node_action.min()) < 0 or int(node_action.max()) >= A:
+        raise ValueError('node action out of range')
+    if int(node_succ.min()) < 0 or int(node_succ.max()) >= N:
+        raise ValueError('successor node out of range')
+    rs = np.ascontiguousarray(reach_states, dtype=np.int32)
+    t = np.ascontiguousarray(rto, dtype=np.float64)
+    er = np.ascontiguousarray(exp_reward, dtype=np.float64)
+    na = np.ascontiguousarray(node_action, dtype=np.int32)
+    ns = np.ascontiguousarray(node_succ, dtype=np.int32)
+    v = np.ascontiguousarray(v0, dtype=np.float64)
+    rows = np.empty((N, S), dtype=np.float64)
+    changes = np.zeros(max(int(horizon), 1), dtype=np.float64)
+    its = C.c_int32(0)
+    _check(lib.pbvi_controller_value_iteration(int(device), S, A, O, R, _p(rs, C.c_int32), _p(t, C.c_double),
+                                               _p(er, C.c_double), N, _p(na, C.c_int32), _p(ns, C.c_int32), _p(v, C.c_double),
+                                               float(gamma), float(max_change_limit), int(horizon), _p(rows, C.c_double),
+                                               _p(changes, C.c_double), C.byref(its)))
     return rows, changes[:its.value]
 
 

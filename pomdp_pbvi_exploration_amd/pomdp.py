@@ -1249,15 +1249,19 @@ class HSVI_Solver(PBVI_Solver):
     support of each point (``sawtooth_numpy``), on the engine when the solve runs on the GPU (``expand_hsvi``)."""
 
     def __init__(self, gamma: float = 0.99, eps: float = 0.001, mdp_solution: Union[ValueFunction, None] = None,
-                 sawtooth: str = 'reference', upper_init: str = 'mdp'):
+                 sawtooth: str = 'reference', upper_init: str = 'mdp', lower_init: str = 'rewards'):
         if sawtooth not in ('reference', 'support'):
             raise ValueError("sawtooth must be 'reference' or 'support'")
         if upper_init not in ('mdp', 'fib'):
             raise ValueError("upper_init must be 'mdp' or 'fib'")
+        if lower_init not in ('rewards', 'blind'):
+            raise ValueError("lower_init must be 'rewards' or 'blind'")
         extra = {} if sawtooth == 'reference' else {'sawtooth': sawtooth}
         super().__init__(gamma, eps, 'hsvi', mdp_policy=mdp_solution, **extra)
         self.upper_init = upper_init
         self._fib_tightened = False
+        self.lower_init = lower_init
+        self._blind_start = None
 
     def solve(self, model, expansions, max_belief_growth: int = 10, initial_belief=None, initial_value_function=None,
               prune_level: int = 1, prune_interval: int = 10, limit_value_function_size: int = -1, use_gpu: bool = False,
@@ -1267,7 +1271,16 @@ class HSVI_Solver(PBVI_Solver):
 
         ``upper_init='fib'``: the MDP solution (the given one, or the one ``PBVI_Solver.solve`` would compute) passes
         through ``FIB_Solver`` once, on the device when ``use_gpu``, before it becomes the corner value function of the
-        upper bound: corner values that are never above the MDP's."""
+        upper bound: corner values that are never above the MDP's.
+
+        ``lower_init='blind'``: when no ``initial_value_function`` is given the loop starts from ``Blind_Solver``'s rows
+        (computed once per solver object, on the device when ``use_gpu``) instead of the expected-rewards rows, which are a
+        lower bound only where no reward is negative."""
+        if self.lower_init == 'blind' and initial_value_function is None:
+            if self._blind_start is None:
+                self._blind_start, _ = Blind_Solver(gamma=self.gamma, eps=self.eps).solve(
+                    model, use_gpu=use_gpu, print_progress=False)
+            initial_value_function = self._blind_start
         if self.upper_init == 'fib' and not self._fib_tightened:
             mdp_solution = self.expand_function_params.get('mdp_policy')
             if mdp_solution is None:
@@ -1380,6 +1393,126 @@ class FIB_Solver(Solver):
         while left > 0:
             t0 = datetime.now()
             rows, changes = run(rows, min(step, left))
+            V = ValueFunction(host, rows, host.actions)
+            dt = (datetime.now() - t0).total_seconds() / max(len(changes), 1)
+            for c in changes:
+                hist.add(dt, float(c), V)
+            left -= len(changes)
+            if len(changes) == 0 or changes[-1] < limit:
+                break
+        return V, hist
+
+
+# --------------------------------------------------------------------------- #
+# Finite-state controllers (policy graphs) and the blind-policy lower bound (Hauskrecht 1997): the definition
+# ``pbvi_controller_value_iteration`` implements, restated with NumPy
+# --------------------------------------------------------------------------- #
+def controller_numpy(model, node_action, node_succ, v0, gamma: float, max_change_limit: float, horizon: int):
+    """Jacobi sweeps of the value of a finite-state controller from ``v0 [N,S]``.  Node n takes action
+    ``a = node_action[n]`` and moves to node ``node_succ[n][o]`` on observation o:
+
+        V'[n][s] = ER[s,a] + gamma * sum_o sum_r RTO[s,a,o,r] * V[node_succ[n][o]][rs[s,a,r]]
+
+    All of V' is computed from the old V, until ``max_{n,s} |V' - V| < max_change_limit`` or ``horizon`` sweeps; returns
+    ``(rows [N,S], changes)``, the rows of the last sweep that ran (``v0`` for ``horizon = 0``).  The loops over o and r are
+    explicit so that every sum associates as the device kernel's does -- ``acc = t_0``, then ``acc = acc + t_r``;
+    ``tot = acc_0``, then ``tot = tot + acc_o`` -- and the two agree bit for bit on finite inputs.  The tables are read per
+    node through the action-major layout the kernel reads; working memory is a few ``[N,S]`` planes."""
+    rs, rto, er = _fib_tables(model)
+    S, A, O, R = rto.shape
+    na = np.asarray(node_action, dtype=np.int64)
+    ns = np.asarray(node_succ, dtype=np.int64)
+    V = np.array(v0, dtype=np.float64, order='C')
+    if rs.shape != (S, A, R) or er.shape != (S, A):
+        raise ValueError('controller_numpy: table shapes do not agree')
+    N = na.shape[0] if na.ndim == 1 else -1
+    if N <= 0 or ns.shape != (N, O) or V.shape != (N, S):
+        raise ValueError('controller_numpy: node_action must be [N], node_succ [N,O] and v0 [N,S]')
+    if na.min() < 0 or na.max() >= A or ns.min() < 0 or ns.max() >= N:
+        raise ValueError('controller_numpy: node action or successor node out of range')
+    rs_t = np.ascontiguousarray(rs.transpose(1, 2, 0))                     # [A,R,S]
+    rto_t = np.ascontiguousarray(rto.transpose(1, 2, 3, 0))                # [A,O,R,S]
+    er_n = np.ascontiguousarray(er.T)[na]                                  # [N,S]
+    to = [rs_t[na, r] for r in range(R)]                                   # [N,S] each: the landing state of (n, s, r)
+    changes = []
+    for _ in range(int(horizon)):
+        tot = None
+        for o in range(O):
+            succ = ns[:, o][:, None]                                       # [N,1]
+            acc = None
+            for r in range(R):
+                t = rto_t[na, o, r] * V[succ, to[r]]                       # [N,S]
+                acc = t if acc is None else acc + t
+            tot = acc if tot is None else tot + acc
+        new = er_n + gamma * tot
+        change = float(np.max(np.abs(new - V)))
+        V = new
+        changes.append(change)
+        if change < max_change_limit:
+            break
+    return V, np.array(changes, dtype=np.float64)
+
+
+def pessimistic_start(model, gamma: float, n_nodes: int):
+    """The constant ``min(ER) / (1 - gamma)`` as ``[n_nodes, S]``: what the worst reward for ever is worth, below the value
+    of every controller.  From it the sweeps of ``controller_numpy`` rise monotonically (the sweep is monotone and the first
+    one does not go down), so a run stopped anywhere is still below the controller's true value: a valid lower bound at
+    any horizon.  The mirror image of ``FIB_Solver``'s start from the MDP solution, from which the sweeps fall."""
+    _, _, er = _fib_tables(model)
+    return np.full((int(n_nodes), er.shape[0]), float(er.min()) / (1.0 - gamma), dtype=np.float64)
+
+
+def evaluate_controller(model, node_action, node_succ, gamma: float = 0.99, eps: float = 0.001, horizon: int = 10000,
+                        v0=None, use_gpu: bool = False):
+    """The value of a finite-state controller: ``(rows [N,S], changes)``, row n the value of starting the controller in
+    node n, every row a valid alpha-vector.  Sweeps from ``v0`` (``pessimistic_start`` when none is given) until the change
+    is below ``eps * gamma / (1 - gamma)``, as in ``VI_Solver`` and ``FIB_Solver``, or ``horizon`` sweeps; on the device
+    (``pbvi_controller_value_iteration``) when ``use_gpu``, which raises when the HIP library or the GPU is missing, else
+    with ``controller_numpy`` -- the same rows bit for bit.  The rows come back raw, not as a ``ValueFunction``: that would
+    fold byte-equal rows and lose which node a row belongs to."""
+    node_action = np.asarray(node_action)
+    if v0 is None:
+        v0 = pessimistic_start(model, gamma, node_action.shape[0])
+    limit = eps * (gamma / (1 - gamma))
+    if use_gpu:
+        from .engine import controller_value_iteration          # raises if the HIP library is missing
+        rs, rto, er = _fib_tables(model)
+        return controller_value_iteration(rs, rto, er, node_action, node_succ, v0, gamma, limit, horizon)
+    return controller_numpy(model, node_action, node_succ, v0, gamma, limit, horizon)
+
+
+class Blind_Solver(Solver):
+    """The blind-policy lower bound (Hauskrecht 1997) as a solver: row a is the value of taking action a for ever, the
+    controller with one node per action that is its own successor under every observation.  Each row is the value of a
+    policy that can be run, so the A action-labelled rows are a valid lower bound of the POMDP value whatever the sign of
+    the rewards -- the initial value function HSVI and SARSOP start from (``HSVI_Solver(lower_init='blind')``) -- and run
+    through ``ValueFunction``, ``Agent`` and rollouts like any solution."""
+
+    def __init__(self, horizon: int = 10000, gamma: float = 0.99, eps: float = 0.001):
+        self.horizon = horizon
+        self.gamma = gamma
+        self.eps = eps
+
+    def solve(self, model: Model, use_gpu: bool = False, history_tracking_level: int = 1, print_progress: bool = True):
+        """Sweeps from ``pessimistic_start``, so the rows rise and are below the blind policies' values wherever the run
+        stops.  The change limit is ``eps * gamma / (1 - gamma)`` as in ``VI_Solver``.  ``use_gpu=True`` runs
+        ``pbvi_controller_value_iteration`` and raises when the HIP library or the GPU is missing."""
+        from .mdp import SolverHistory as MDP_SolverHistory
+        host = model.cpu_model
+        A = host.action_count
+        node_action = np.arange(A)
+        node_succ = np.tile(np.arange(A)[:, None], (1, len(host.observations)))
+        rows = pessimistic_start(host, self.gamma, A)
+        V = ValueFunction(host, rows, host.actions)
+        hist = MDP_SolverHistory(history_tracking_level, host, self.gamma, self.eps, V)
+        limit = self.eps * (self.gamma / (1 - self.gamma))
+        # per-sweep value functions (tracking level 2+) need every sweep's rows: one sweep per call then
+        step = 1 if history_tracking_level >= 2 else self.horizon
+        left = self.horizon
+        while left > 0:
+            t0 = datetime.now()
+            rows, changes = evaluate_controller(host, node_action, node_succ, gamma=self.gamma, eps=self.eps,
+                                                horizon=min(step, left), v0=rows, use_gpu=use_gpu)
             V = ValueFunction(host, rows, host.actions)
             dt = (datetime.now() - t0).total_seconds() / max(len(changes), 1)
             for c in changes:
