@@ -742,8 +742,11 @@ int pbvi_rollout_state_policy(pbvi_engine_t* e, int rule, int use_env, const int
  * repeated from v0 until max_s |v' - v| < max_change_limit (the reference's eps * gamma / (1 - gamma)) or
  * `horizon` sweeps.  Always fp64.  Not tied to an engine handle (the MDP tables are not the POMDP's).
  *   reach_states [S][A][R] int32, reach_prob [S][A][R], exp_reward [S][A], v0 [S]   (NumPy C-order)
- *   out_rows [A][S]: rows of the last sweep (the solution's alpha-vectors, before the container's dedup)
+ *   out_rows [A][S]: rows of the last sweep (the solution's alpha-vectors, before the container's dedup); all 0.0 for
+ *   horizon = 0 (PBVI_OK, zero iterations)
  *   out_changes [horizon] (may be NULL): max change of each sweep that ran;  out_iterations (may be NULL).
+ * The three handle-free sweep entries (this one, pbvi_fib_value_iteration, pbvi_controller_value_iteration) share one run
+ * driver (csrc/engine.hip, SweepRun) and one kernel file (csrc/sweep_kernels.hip).
  */
 int pbvi_mdp_value_iteration(int device, int32_t S, int32_t A, int32_t R, const int32_t* reach_states,
                              const double* reach_prob, const double* exp_reward, const double* v0, double gamma,

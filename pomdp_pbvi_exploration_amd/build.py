@@ -14,7 +14,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, 'csrc')
 LIB_PATH = os.path.join(PKG_DIR, 'libpbvi_hip.so')
 SOURCES = ['gemm.hip', 'gemm_f64.hip', 'backup_kernels.hip', 'upper_kernels.hip', 'state_policy_kernels.hip',
-           'controller_kernels.hip', 'engine.hip']
+           'sweep_kernels.hip', 'engine.hip']
 
 
 def _stale() -> bool:

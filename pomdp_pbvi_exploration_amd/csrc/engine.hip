@@ -25,9 +25,9 @@
 #include <vector>
 
 #include "backup_kernels.h"
-#include "controller_kernels.h"
 #include "split_bf16.h"
 #include "state_policy_kernels.h"
+#include "sweep_kernels.h"
 #include "upper_kernels.h"
 
 namespace pbvi {
@@ -4886,127 +4886,13 @@ int EngineT<T>::run_backup(double gamma, int flags, pbvi_stats_t* st, Mode mode)
 }
 
 // --------------------------------------------------------------------------- //
-// MDP value iteration (VI_Solver.solve, src/mdp.py:1485-1510).  One thread per state, tables re-tiled [A][R][S] so
-// every load is coalesced; HBM/latency-bound (A*R gathers per state per sweep).  Products and sums are kept
-// un-fused (fp contract off) so R = 1 reproduces NumPy's  ER + gamma * (P * v)  bit for bit.
-// Sweep `it` leaves at once when sweep it-1 already met the change limit, so the host can enqueue sweeps in
-// batches without syncing; the rows / values of the converged sweep stay in place.
-// --------------------------------------------------------------------------- //
-__global__ void k_vi_sweep(int S, int A, int R, const int32_t* __restrict__ rs, const double* __restrict__ prob,
-                           const double* __restrict__ er, double gamma, double limit, int it,
-                           const double* __restrict__ v_in, double* __restrict__ v_out, double* __restrict__ rows,
-                           double* __restrict__ changes) {
-#pragma clang fp contract(off)   // no FMA fusion: every product and sum rounds like NumPy's separate ufuncs
-    if (it > 0 && changes[it - 1] < limit) return;
-    __shared__ double red[4];
-    const int s = blockIdx.x * 256 + threadIdx.x;
-    double diff = 0.0;
-    if (s < S) {
-        double best = 0.0;
-        for (int a = 0; a < A; ++a) {
-            double acc = 0.0;
-            for (int r = 0; r < R; ++r) {
-                const int64_t k = ((int64_t)a * R + r) * S + s;
-                const double t = prob[k] * v_in[rs[k]];
-                acc = r == 0 ? t : acc + t;
-            }
-            const double scaled = gamma * acc;
-            const double row = er[(int64_t)a * S + s] + scaled;
-            rows[(int64_t)a * S + s] = row;
-            best = (a == 0 || row > best) ? row : best;
-        }
-        v_out[s] = best;
-        diff = fabs(best - v_in[s]);
-    }
-    // block max, then one atomic per block (non-negative doubles order like their bit patterns)
-    for (int off = 32; off > 0; off >>= 1) diff = fmax(diff, __shfl_xor(diff, off));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = diff;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const double m = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-        atomicMax(reinterpret_cast<unsigned long long*>(&changes[it]), (unsigned long long)__double_as_longlong(m));
-    }
-}
-
-static int mdp_value_iteration(int device, int S, int A, int R, const int32_t* rs, const double* prob, const double* er,
-                               const double* v0, double gamma, double limit, int horizon, double* out_rows,
-                               double* out_changes, int32_t* out_iterations) {
-    if (S <= 0 || A <= 0 || R <= 0 || horizon < 0 || !rs || !prob || !er || !v0 || !out_rows)
-        FAIL(PBVI_EINVAL, "mdp_value_iteration: bad arguments");
-    if ((int64_t)S * A * R > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "mdp_value_iteration: S*A*R exceeds int32");
-    const size_t n = (size_t)S * A * R;
-    std::vector<int32_t> h_rs(n);
-    std::vector<double> h_p(n), h_er((size_t)S * A);
-    for (int s = 0; s < S; ++s)
-        for (int a = 0; a < A; ++a) {
-            h_er[(size_t)a * S + s] = er[(size_t)s * A + a];
-            for (int r = 0; r < R; ++r) {
-                const size_t src = ((size_t)s * A + a) * R + r, dst = ((size_t)a * R + r) * S + s;
-                if (rs[src] < 0 || rs[src] >= S) FAIL(PBVI_EINVAL, "mdp_value_iteration: reachable state out of range");
-                h_rs[dst] = rs[src];
-                h_p[dst] = prob[src];
-            }
-        }
-    HIPCHK(hipSetDevice(device));
-    struct Guard {                                           // (in front of the buffers: they are released first)
-        hipStream_t st = nullptr;
-        ~Guard() {
-            if (st) (void)hipStreamDestroy(st);
-        }
-    } guard;
-    DevMem mem;
-    DevBuf d_rs{mem}, d_p{mem}, d_er{mem}, d_v[2]{{mem}, {mem}}, d_rows{mem}, d_ch{mem};
-    int rc;
-    if ((rc = d_rs.ensure(n * sizeof(int32_t)))) return rc;
-    if ((rc = d_p.ensure(n * sizeof(double)))) return rc;
-    if ((rc = d_er.ensure((size_t)S * A * sizeof(double)))) return rc;
-    if ((rc = d_v[0].ensure((size_t)S * sizeof(double)))) return rc;
-    if ((rc = d_v[1].ensure((size_t)S * sizeof(double)))) return rc;
-    if ((rc = d_rows.ensure((size_t)S * A * sizeof(double)))) return rc;
-    if ((rc = d_ch.ensure((size_t)std::max(horizon, 1) * sizeof(double)))) return rc;
-    HIPCHK(hipStreamCreateWithFlags(&guard.st, hipStreamNonBlocking));
-    hipStream_t st = guard.st;
-    HIPCHK(hipMemcpyAsync(d_rs.p, h_rs.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_p.p, h_p.data(), n * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_er.p, h_er.data(), (size_t)S * A * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_v[0].p, v0, (size_t)S * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(d_ch.p, 0, (size_t)std::max(horizon, 1) * sizeof(double), st));
-    HIPCHK(hipMemsetAsync(d_rows.p, 0, (size_t)S * A * sizeof(double), st));
-    std::vector<double> ch((size_t)std::max(horizon, 1), 0.0);
-    int done = 0;              // sweeps that ran
-    bool converged = false;
-    const int batch = 64;
-    for (int it0 = 0; it0 < horizon && !converged; it0 += batch) {
-        const int it1 = std::min(horizon, it0 + batch);
-        for (int it = it0; it < it1; ++it) {
-            hipLaunchKernelGGL(k_vi_sweep, dim3((S + 255) / 256), dim3(256), 0, st, S, A, R, d_rs.as<int32_t>(),
-                               d_p.as<double>(), d_er.as<double>(), gamma, limit, it, d_v[it & 1].as<double>(),
-                               d_v[(it + 1) & 1].as<double>(), d_rows.as<double>(), d_ch.as<double>());
-            HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipMemcpyAsync(ch.data() + it0, d_ch.as<double>() + it0, (size_t)(it1 - it0) * sizeof(double),
-                              hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int it = it0; it < it1; ++it) {
-            done = it + 1;
-            if (ch[(size_t)it] < limit) {
-                converged = true;
-                break;
-            }
-        }
-    }
-    HIPCHK(hipMemcpyAsync(out_rows, d_rows.p, (size_t)S * A * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (out_changes)
-        for (int it = 0; it < done; ++it) out_changes[it] = ch[(size_t)it];
-    if (out_iterations) *out_iterations = done;
-    return PBVI_OK;
-}
-
-// --------------------------------------------------------------------------- //
-// The model tables of the handle-free sweep entries below (FIB, controller evaluation) as their kernels read them: from
-// the caller's [S][A][..] order to rs [A][R][S], rto [A][O][R][S], er [A][S], so that with s across the lanes every table
-// load is coalesced.  Host work only.  False (and nothing to use) when a reachable state lies outside [0, S).
+// The handle-free sweep entries (include/pbvi_hip.h; kernels in sweep_kernels.hip): MDP value iteration, the Fast Informed
+// Bound and finite-state controller evaluation.  Each takes the model tables, sweeps on device buffers of its own and
+// leaves nothing behind.
+//
+// The model tables as the sweep kernels read them: from the caller's [S][A][..] order to rs [A][R][S], rto [A][O][R][S],
+// er [A][S], so that with s across the lanes every table load is coalesced (the MDP's transition probabilities are an rto
+// with O = 1).  Host work only.  False (and nothing to use) when a reachable state lies outside [0, S).
 // --------------------------------------------------------------------------- //
 struct SweepTables {
     std::vector<int32_t> rs;
@@ -5033,81 +4919,114 @@ static bool retile_sweep_tables(int S, int A, int O, int R, const int32_t* rs, c
 }
 
 // --------------------------------------------------------------------------- //
-// Fast Informed Bound (Hauskrecht 2000): the MDP sweep with the observation kept inside the maximisation,
-//   Q'(s,a) = ER[s,a] + gamma * sum_o max_a' sum_r RTO[s,a,o,r] * Q(rs[s,a,r], a')
-// One thread per (s, a), s fastest across lanes; tables re-tiled rs [A][R][S], rto [A][O][R][S], er [A][S] so every
-// table load is coalesced.  The two Q buffers are state-major [S][A]: the action values of one successor are one
-// contiguous segment, gathered R times per (o, tile) (the repeats hit cache).  a' runs in register tiles of TW
-// accumulators with the running maximum carried across tiles; the tail tile is bounded, never padded (0 * -inf).
-// PAIRS: A is even, so every segment starts 16-byte aligned and no tile ends inside a pair: double2 loads.
-// The order of every product and sum is the one pomdp.fib_numpy states, un-fused, so both agree bit for bit on
-// finite inputs.  Early exit and change reduction as in k_vi_sweep.
+// One run of sweeps: the stream, the device memory and the per-sweep changes of one call of a sweep entry.  The entry
+// declares its DevBufs on `mem` behind the run (so they are released before the stream is destroyed), then: open, sweep,
+// fetch the result, report.  The host memory an upload reads must outlive the run.
 // --------------------------------------------------------------------------- //
-template <int TW, bool PAIRS>
-__global__ __launch_bounds__(256) void k_fib_sweep(int S, int A, int O, int R, int s_blocks, const int32_t* __restrict__ rs,
-                                                   const double* __restrict__ rto, const double* __restrict__ er,
-                                                   double gamma, double limit, int it, const double* __restrict__ q_in,
-                                                   double* __restrict__ q_out, double* __restrict__ changes) {
-#pragma clang fp contract(off)   // no FMA fusion: every product and sum rounds like NumPy's separate ufuncs
-    if (it > 0 && changes[it - 1] < limit) return;
-    __shared__ double red[4];
-    const int a = blockIdx.x / s_blocks;
-    const int s = (blockIdx.x - a * s_blocks) * 256 + threadIdx.x;
-    double diff = 0.0;
-    if (s < S) {
-        const int32_t* rs_a = rs + (int64_t)a * R * S + s;
-        double tot = 0.0;
-        for (int o = 0; o < O; ++o) {
-            const double* rto_ao = rto + ((int64_t)a * O + o) * R * S + s;
-            double m = 0.0;                                     // (set by the first accumulator, never compared before)
-            for (int a0 = 0; a0 < A; a0 += TW) {
-                const int n = min(TW, A - a0);
-                double acc[TW];
-                for (int r = 0; r < R; ++r) {
-                    const double p = rto_ao[(int64_t)r * S];
-                    const double* q = q_in + (int64_t)rs_a[(int64_t)r * S] * A + a0;
-                    double v[TW];
-                    if constexpr (PAIRS) {
-#pragma unroll
-                        for (int j = 0; j < TW; j += 2)
-                            if (j < n) {
-                                const double2 t = *reinterpret_cast<const double2*>(q + j);
-                                v[j] = t.x;
-                                v[j + 1] = t.y;
-                            }
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < TW; ++j)
-                            if (j < n) v[j] = q[j];
-                    }
-#pragma unroll
-                    for (int j = 0; j < TW; ++j)
-                        if (j < n) {
-                            const double t = p * v[j];
-                            acc[j] = r == 0 ? t : acc[j] + t;
-                        }
-                }
-#pragma unroll
-                for (int j = 0; j < TW; ++j)
-                    if (j < n) m = (a0 + j == 0 || acc[j] > m) ? acc[j] : m;
-            }
-            tot = o == 0 ? m : tot + m;
+struct SweepRun {
+    struct Alloc {                                           // src: host memory to upload, or nullptr (allocated only)
+        DevBuf& buf;
+        size_t bytes;
+        const void* src;
+    };
+    struct Guard {                                           // (in front of the buffers: they are released first)
+        hipStream_t st = nullptr;
+        ~Guard() {
+            if (st) (void)hipStreamDestroy(st);
         }
-        const double scaled = gamma * tot;
-        const double q_new = er[(int64_t)a * S + s] + scaled;
-        q_out[(int64_t)s * A + a] = q_new;
-        diff = fabs(q_new - q_in[(int64_t)s * A + a]);
+    } guard;
+    DevMem mem;
+    DevBuf d_changes{mem};                                   // [max(horizon, 1)]: changes[it] = largest change of sweep it
+    std::vector<double> changes;                             // its host mirror
+    int done = 0;                                            // sweeps that ran
+
+    // Every allocation is made before the first copy is enqueued: an out-of-memory return leaves no copy in flight.
+    int open(int device, int horizon, std::initializer_list<Alloc> bufs) {
+        HIPCHK(hipSetDevice(device));
+        const size_t ch_bytes = (size_t)std::max(horizon, 1) * sizeof(double);
+        int rc;
+        for (const Alloc& a : bufs)
+            if ((rc = a.buf.ensure(a.bytes))) return rc;
+        if ((rc = d_changes.ensure(ch_bytes))) return rc;
+        HIPCHK(hipStreamCreateWithFlags(&guard.st, hipStreamNonBlocking));
+        for (const Alloc& a : bufs)
+            if (a.src) HIPCHK(hipMemcpyAsync(a.buf.p, a.src, a.bytes, hipMemcpyHostToDevice, guard.st));
+        HIPCHK(hipMemsetAsync(d_changes.p, 0, ch_bytes, guard.st));
+        changes.assign((size_t)std::max(horizon, 1), 0.0);
+        return PBVI_OK;
     }
-    // block max, then one atomic per block (non-negative doubles order like their bit patterns)
-    for (int off = 32; off > 0; off >>= 1) diff = fmax(diff, __shfl_xor(diff, off));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = diff;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const double mx = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-        atomicMax(reinterpret_cast<unsigned long long*>(&changes[it]), (unsigned long long)__double_as_longlong(mx));
+    // Up to `horizon` sweeps, `launch(it, stream)` enqueues sweep it.  Sweeps go out in batches of 64 with one read-back of
+    // their changes per batch; the first change below `limit` ends the run (the sweeps enqueued behind it left at once).
+    template <typename Launch>
+    int sweep(int horizon, double limit, Launch&& launch) {
+        bool converged = false;
+        const int batch = 64;
+        for (int it0 = 0; it0 < horizon && !converged; it0 += batch) {
+            const int it1 = std::min(horizon, it0 + batch);
+            for (int it = it0; it < it1; ++it) HIPCHK(launch(it, guard.st));
+            HIPCHK(hipMemcpyAsync(changes.data() + it0, d_changes.as<double>() + it0, (size_t)(it1 - it0) * sizeof(double),
+                                  hipMemcpyDeviceToHost, guard.st));
+            HIPCHK(hipStreamSynchronize(guard.st));
+            for (int it = it0; it < it1; ++it) {
+                done = it + 1;
+                if (changes[(size_t)it] < limit) {
+                    converged = true;
+                    break;
+                }
+            }
+        }
+        return PBVI_OK;
     }
+    int fetch(void* dst, const DevBuf& src, size_t bytes) {
+        HIPCHK(hipMemcpyAsync(dst, src.p, bytes, hipMemcpyDeviceToHost, guard.st));
+        HIPCHK(hipStreamSynchronize(guard.st));
+        return PBVI_OK;
+    }
+    void report(double* out_changes, int32_t* out_iterations) const {
+        if (out_changes)
+            for (int it = 0; it < done; ++it) out_changes[it] = changes[(size_t)it];
+        if (out_iterations) *out_iterations = done;
+    }
+};
+
+// MDP value iteration (VI_Solver.solve, src/mdp.py:1485-1510).  The rows are zeroed before the first sweep: that is
+// what horizon = 0 returns.
+static int mdp_value_iteration(int device, int S, int A, int R, const int32_t* rs, const double* prob, const double* er,
+                               const double* v0, double gamma, double limit, int horizon, double* out_rows,
+                               double* out_changes, int32_t* out_iterations) {
+    if (S <= 0 || A <= 0 || R <= 0 || horizon < 0 || !rs || !prob || !er || !v0 || !out_rows)
+        FAIL(PBVI_EINVAL, "mdp_value_iteration: bad arguments");
+    if ((int64_t)S * A * R > 0x7fffffff) FAIL(PBVI_EUNSUPPORTED, "mdp_value_iteration: S*A*R exceeds int32");
+    const size_t n = (size_t)S * A * R, n_rows = (size_t)S * A;
+    SweepTables h;
+    if (!retile_sweep_tables(S, A, 1, R, rs, prob, er, h)) FAIL(PBVI_EINVAL, "mdp_value_iteration: reachable state out of range");
+    SweepRun run;
+    DevBuf d_rs{run.mem}, d_p{run.mem}, d_er{run.mem}, d_v[2]{{run.mem}, {run.mem}}, d_rows{run.mem};
+    int rc;
+    if ((rc = run.open(device, horizon, {{d_rs, n * sizeof(int32_t), h.rs.data()},
+                                         {d_p, n * sizeof(double), h.rto.data()},
+                                         {d_er, n_rows * sizeof(double), h.er.data()},
+                                         {d_v[0], (size_t)S * sizeof(double), v0},
+                                         {d_v[1], (size_t)S * sizeof(double), nullptr},
+                                         {d_rows, n_rows * sizeof(double), nullptr}})))
+        return rc;
+    HIPCHK(hipMemsetAsync(d_rows.p, 0, n_rows * sizeof(double), run.guard.st));
+    ViSweep vs{};
+    vs.S = S, vs.A = A, vs.O = 1, vs.R = R;
+    vs.rs = d_rs.as<int32_t>(), vs.rto = d_p.as<double>(), vs.er = d_er.as<double>();
+    vs.gamma = gamma, vs.limit = limit, vs.changes = run.d_changes.as<double>(), vs.rows = d_rows.as<double>();
+    if ((rc = run.sweep(horizon, limit, [&](int it, hipStream_t st) {
+            vs.it = it, vs.v_in = d_v[it & 1].as<double>(), vs.v_out = d_v[(it + 1) & 1].as<double>();
+            return launch_vi_sweep(vs, st);
+        })))
+        return rc;
+    if ((rc = run.fetch(out_rows, d_rows, n_rows * sizeof(double)))) return rc;
+    run.report(out_changes, out_iterations);
+    return PBVI_OK;
 }
 
+// Fast Informed Bound (Hauskrecht 2000).  The two Q buffers are state-major [S][A] on the device (k_fib_sweep), action-major
+// [A][S] at the caller.
 static int fib_value_iteration(int device, int S, int A, int O, int R, const int32_t* rs, const double* rto, const double* er,
                                const double* q0, double gamma, double limit, int horizon, double* out_rows,
                                double* out_changes, int32_t* out_iterations) {
@@ -5117,81 +5036,47 @@ static int fib_value_iteration(int device, int S, int A, int O, int R, const int
     const size_t n_rs = (size_t)S * A * R, n_rto = n_rs * O, n_q = (size_t)S * A;
     SweepTables h;
     if (!retile_sweep_tables(S, A, O, R, rs, rto, er, h)) FAIL(PBVI_EINVAL, "fib_value_iteration: reachable state out of range");
-    std::vector<double> h_q(n_q);
-    for (int s = 0; s < S; ++s)
-        for (int a = 0; a < A; ++a) h_q[(size_t)s * A + a] = q0[(size_t)a * S + s];
     if (horizon == 0) {                                      // nothing to sweep: q0 comes back as it is
         memcpy(out_rows, q0, n_q * sizeof(double));
         if (out_iterations) *out_iterations = 0;
         return PBVI_OK;
     }
-    HIPCHK(hipSetDevice(device));
-    struct Guard {                                           // (in front of the buffers: they are released first)
-        hipStream_t st = nullptr;
-        ~Guard() {
-            if (st) (void)hipStreamDestroy(st);
-        }
-    } guard;
-    DevMem mem;
-    DevBuf d_rs{mem}, d_rto{mem}, d_er{mem}, d_q[2]{{mem}, {mem}}, d_ch{mem};
+    std::vector<double> h_q(n_q);
+    for (int s = 0; s < S; ++s)
+        for (int a = 0; a < A; ++a) h_q[(size_t)s * A + a] = q0[(size_t)a * S + s];
+    SweepRun run;
+    DevBuf d_rs{run.mem}, d_rto{run.mem}, d_er{run.mem}, d_q[2]{{run.mem}, {run.mem}};
     int rc;
-    if ((rc = d_rs.ensure(n_rs * sizeof(int32_t)))) return rc;
-    if ((rc = d_rto.ensure(n_rto * sizeof(double)))) return rc;
-    if ((rc = d_er.ensure(n_q * sizeof(double)))) return rc;
-    if ((rc = d_q[0].ensure(n_q * sizeof(double)))) return rc;
-    if ((rc = d_q[1].ensure(n_q * sizeof(double)))) return rc;
-    if ((rc = d_ch.ensure((size_t)horizon * sizeof(double)))) return rc;
-    HIPCHK(hipStreamCreateWithFlags(&guard.st, hipStreamNonBlocking));
-    hipStream_t st = guard.st;
-    HIPCHK(hipMemcpyAsync(d_rs.p, h.rs.data(), n_rs * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_rto.p, h.rto.data(), n_rto * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_er.p, h.er.data(), n_q * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_q[0].p, h_q.data(), n_q * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(d_ch.p, 0, (size_t)horizon * sizeof(double), st));
-    auto sweep = A <= 4 ? (A % 2 == 0 ? k_fib_sweep<4, true> : k_fib_sweep<4, false>)
-                        : (A % 2 == 0 ? k_fib_sweep<8, true> : k_fib_sweep<8, false>);
-    const int s_blocks = (S + 255) / 256;                    // (s_blocks * A <= S * A <= int32)
-    std::vector<double> ch((size_t)horizon, 0.0);
-    int done = 0;              // sweeps that ran
-    bool converged = false;
-    const int batch = 64;
-    for (int it0 = 0; it0 < horizon && !converged; it0 += batch) {
-        const int it1 = std::min(horizon, it0 + batch);
-        for (int it = it0; it < it1; ++it) {
-            hipLaunchKernelGGL(sweep, dim3((unsigned)(s_blocks * A)), dim3(256), 0, st, S, A, O, R, s_blocks,
-                               d_rs.as<int32_t>(), d_rto.as<double>(), d_er.as<double>(), gamma, limit, it,
-                               d_q[it & 1].as<double>(), d_q[(it + 1) & 1].as<double>(), d_ch.as<double>());
-            HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipMemcpyAsync(ch.data() + it0, d_ch.as<double>() + it0, (size_t)(it1 - it0) * sizeof(double),
-                              hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int it = it0; it < it1; ++it) {
-            done = it + 1;
-            if (ch[(size_t)it] < limit) {
-                converged = true;
-                break;
-            }
-        }
-    }
+    if ((rc = run.open(device, horizon, {{d_rs, n_rs * sizeof(int32_t), h.rs.data()},
+                                         {d_rto, n_rto * sizeof(double), h.rto.data()},
+                                         {d_er, n_q * sizeof(double), h.er.data()},
+                                         {d_q[0], n_q * sizeof(double), h_q.data()},
+                                         {d_q[1], n_q * sizeof(double), nullptr}})))
+        return rc;
+    FibSweep fs{};
+    fs.S = S, fs.A = A, fs.O = O, fs.R = R;
+    fs.rs = d_rs.as<int32_t>(), fs.rto = d_rto.as<double>(), fs.er = d_er.as<double>();
+    fs.gamma = gamma, fs.limit = limit, fs.changes = run.d_changes.as<double>();
+    if ((rc = run.sweep(horizon, limit, [&](int it, hipStream_t st) {
+            fs.it = it, fs.q_in = d_q[it & 1].as<double>(), fs.q_out = d_q[(it + 1) & 1].as<double>();
+            return launch_fib_sweep(fs, st);
+        })))
+        return rc;
     // sweep done-1 was the last to write: its Q is in buffer done & 1 (the sweeps enqueued after it left at once)
-    HIPCHK(hipMemcpyAsync(h_q.data(), d_q[done & 1].p, n_q * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if ((rc = run.fetch(h_q.data(), d_q[run.done & 1], n_q * sizeof(double)))) return rc;
     for (int s = 0; s < S; ++s)
         for (int a = 0; a < A; ++a) out_rows[(size_t)a * S + s] = h_q[(size_t)s * A + a];
-    if (out_changes)
-        for (int it = 0; it < done; ++it) out_changes[it] = ch[(size_t)it];
-    if (out_iterations) *out_iterations = done;
+    run.report(out_changes, out_iterations);
     return PBVI_OK;
 }
 
 // --------------------------------------------------------------------------- //
-// Finite-state controller evaluation (include/pbvi_hip.h; kernel in controller_kernels.hip): Jacobi sweeps of
+// Finite-state controller evaluation: Jacobi sweeps of
 //   V'[n][s] = ER[s,a_n] + gamma * sum_o sum_r RTO[s,a_n,o,r] * V[succ[n][o]][rs[s,a_n,r]]
 // The nodes run on the device in the order of their actions (stable; rows and successors are renumbered on the way in
 // and the rows put back on the way out), so that nodes which share an action, and with it every table element, are
 // neighbours a register tile can cover.  A sweep does not depend on the numbering of the nodes: the result is the same,
-// bit for bit.  Batching, early exit and the buffer the result is read from are fib_value_iteration's.
+// bit for bit.
 // --------------------------------------------------------------------------- //
 static int controller_value_iteration(int device, int S, int A, int O, int R, const int32_t* rs, const double* rto,
                                       const double* er, int N, const int32_t* node_action, const int32_t* node_succ,
@@ -5244,70 +5129,35 @@ static int controller_value_iteration(int device, int S, int A, int O, int R, co
         for (int o = 0; o < O; ++o) h_succ[(size_t)p * O + o] = pos[(size_t)node_succ[n * O + o]];
         memcpy(h_v.data() + (size_t)p * S, v0 + n * S, (size_t)S * sizeof(double));
     }
-    HIPCHK(hipSetDevice(device));
-    struct Guard {                                           // (in front of the buffers: they are released first)
-        hipStream_t st = nullptr;
-        ~Guard() {
-            if (st) (void)hipStreamDestroy(st);
-        }
-    } guard;
-    DevMem mem;
-    DevBuf d_rs{mem}, d_rto{mem}, d_er{mem}, d_action{mem}, d_succ{mem}, d_tiles{mem}, d_v[2]{{mem}, {mem}}, d_ch{mem};
+    SweepRun run;
+    DevBuf d_rs{run.mem}, d_rto{run.mem}, d_er{run.mem}, d_action{run.mem}, d_succ{run.mem}, d_tiles{run.mem},
+        d_v[2]{{run.mem}, {run.mem}};
     int rc;
-    if ((rc = d_rs.ensure(n_rs * sizeof(int32_t)))) return rc;
-    if ((rc = d_rto.ensure(n_rto * sizeof(double)))) return rc;
-    if ((rc = d_er.ensure(n_er * sizeof(double)))) return rc;
-    if ((rc = d_action.ensure((size_t)N * sizeof(int32_t)))) return rc;
-    if ((rc = d_succ.ensure((size_t)N * O * sizeof(int32_t)))) return rc;
-    if ((rc = d_tiles.ensure(tile_first.size() * sizeof(int32_t)))) return rc;
-    if ((rc = d_v[0].ensure(n_v * sizeof(double)))) return rc;
-    if ((rc = d_v[1].ensure(n_v * sizeof(double)))) return rc;
-    if ((rc = d_ch.ensure((size_t)horizon * sizeof(double)))) return rc;
-    HIPCHK(hipStreamCreateWithFlags(&guard.st, hipStreamNonBlocking));
-    hipStream_t st = guard.st;
-    HIPCHK(hipMemcpyAsync(d_rs.p, h.rs.data(), n_rs * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_rto.p, h.rto.data(), n_rto * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_er.p, h.er.data(), n_er * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_action.p, h_action.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_succ.p, h_succ.data(), (size_t)N * O * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_tiles.p, tile_first.data(), tile_first.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_v[0].p, h_v.data(), n_v * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(d_ch.p, 0, (size_t)horizon * sizeof(double), st));
+    if ((rc = run.open(device, horizon, {{d_rs, n_rs * sizeof(int32_t), h.rs.data()},
+                                         {d_rto, n_rto * sizeof(double), h.rto.data()},
+                                         {d_er, n_er * sizeof(double), h.er.data()},
+                                         {d_action, (size_t)N * sizeof(int32_t), h_action.data()},
+                                         {d_succ, (size_t)N * O * sizeof(int32_t), h_succ.data()},
+                                         {d_tiles, tile_first.size() * sizeof(int32_t), tile_first.data()},
+                                         {d_v[0], n_v * sizeof(double), h_v.data()},
+                                         {d_v[1], n_v * sizeof(double), nullptr}})))
+        return rc;
     ControllerSweep cs{};
     cs.S = S, cs.A = A, cs.O = O, cs.R = R, cs.N = N;
     cs.rs = d_rs.as<int32_t>(), cs.rto = d_rto.as<double>(), cs.er = d_er.as<double>();
     cs.node_action = d_action.as<int32_t>(), cs.node_succ = d_succ.as<int32_t>();
     cs.node_tile = node_tile, cs.tiles = tiles, cs.tile_first = d_tiles.as<int32_t>();   // (tiles * s_blocks <= N * s_blocks)
-    cs.gamma = gamma, cs.limit = limit, cs.changes = d_ch.as<double>();
-    std::vector<double> ch((size_t)horizon, 0.0);
-    int done = 0;              // sweeps that ran
-    bool converged = false;
-    const int batch = 64;
-    for (int it0 = 0; it0 < horizon && !converged; it0 += batch) {
-        const int it1 = std::min(horizon, it0 + batch);
-        for (int it = it0; it < it1; ++it) {
+    cs.gamma = gamma, cs.limit = limit, cs.changes = run.d_changes.as<double>();
+    if ((rc = run.sweep(horizon, limit, [&](int it, hipStream_t st) {
             cs.it = it, cs.v_in = d_v[it & 1].as<double>(), cs.v_out = d_v[(it + 1) & 1].as<double>();
-            HIPCHK(launch_controller_sweep(cs, st));
-        }
-        HIPCHK(hipMemcpyAsync(ch.data() + it0, d_ch.as<double>() + it0, (size_t)(it1 - it0) * sizeof(double),
-                              hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int it = it0; it < it1; ++it) {
-            done = it + 1;
-            if (ch[(size_t)it] < limit) {
-                converged = true;
-                break;
-            }
-        }
-    }
+            return launch_controller_sweep(cs, st);
+        })))
+        return rc;
     // sweep done-1 was the last to write: its V is in buffer done & 1 (the sweeps enqueued after it left at once)
-    HIPCHK(hipMemcpyAsync(h_v.data(), d_v[done & 1].p, n_v * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if ((rc = run.fetch(h_v.data(), d_v[run.done & 1], n_v * sizeof(double)))) return rc;
     for (int p = 0; p < N; ++p)
         memcpy(out_rows + (size_t)order[(size_t)p] * S, h_v.data() + (size_t)p * S, (size_t)S * sizeof(double));
-    if (out_changes)
-        for (int it = 0; it < done; ++it) out_changes[it] = ch[(size_t)it];
-    if (out_iterations) *out_iterations = done;
+    run.report(out_changes, out_iterations);
     return PBVI_OK;
 }
 

@@ -310,27 +310,63 @@ class PinnedBuffer:
             pass
 
 
-def mdp_value_iteration(reach_states: np.ndarray, reach_prob: np.ndarray, exp_reward: np.ndarray, v0: np.ndarray,
-                        gamma: float, max_change_limit: float, horizon: int, device: int = 0):
-    """MDP value-iteration sweeps on the device (``VI_Solver.solve``, ``src/mdp.py:1485-1510``).
-    Returns ``(rows [A,S] f64, changes [iterations] f64)``."""
-    lib = load_library()
+# The handle-free sweep entries.  Each wrapper checks its input before the device is touched -- shapes and the horizon
+# (``ValueError``), then the products the entry indexes with int32 (``NotImplementedError``, before any table is copied:
+# the entry refuses them the same way), then the index ranges (``ValueError``).
+def _sweep_shapes(name, reach_states, table, exp_reward, horizon, o_axis=True):
+    """The shape checks the sweep wrappers share; ``table`` is ``rto [S,A,O,R]``, or ``reach_prob [S,A,R]`` when not
+    ``o_axis``.  Returns ``(reach_states, table, S, A, O, R)``, the two as arrays, nothing copied."""
+    reach_states, table = np.asarray(reach_states), np.asarray(table)
+    if reach_states.ndim != 3 or table.ndim != (4 if o_axis else 3):
+        raise ValueError(f'{name}: reach_states must be [S,A,R] and ' + ('rto [S,A,O,R]' if o_axis else 'reach_prob [S,A,R]'))
     S, A, R = reach_states.shape
+    O = table.shape[2] if o_axis else 1
+    if table.shape != ((S, A, O, R) if o_axis else (S, A, R)) or np.shape(exp_reward) != (S, A):
+        raise ValueError(f'{name}: table shapes do not agree')
+    if min(S, A, O, R) <= 0:
+        raise ValueError(f'{name}: empty tables')
+    if int(horizon) < 0:
+        raise ValueError(f'{name}: negative horizon')
+    return reach_states, table, S, A, O, R
+
+
+def _sweep_tables(name, reach_states, table, exp_reward, S, sizes):
+    """The int32 limits -- ``sizes``: ``(product, its name)`` pairs -- and the successor range; then the three tables as the
+    entry reads them."""
+    for n, what in sizes:
+        if n > 0x7fffffff:
+            raise NotImplementedError(f'{name}: {what} exceeds int32')
     if int(reach_states.min()) < 0 or int(reach_states.max()) >= S:
         raise ValueError('reachable state out of range')
-    rs = np.ascontiguousarray(reach_states, dtype=np.int32)
-    p = np.ascontiguousarray(reach_prob, dtype=np.float64)
-    er = np.ascontiguousarray(exp_reward, dtype=np.float64)
-    v = np.ascontiguousarray(v0, dtype=np.float64)
-    if p.shape != (S, A, R) or er.shape != (S, A) or v.shape != (S,):
-        raise ValueError('mdp_value_iteration: table shapes do not agree')
-    rows = np.empty((A, S), dtype=np.float64)
+    return (np.ascontiguousarray(reach_states, dtype=np.int32), np.ascontiguousarray(table, dtype=np.float64),
+            np.ascontiguousarray(exp_reward, dtype=np.float64))
+
+
+def _sweep_call(entry, device, args, gamma, max_change_limit, horizon, rows_shape):
+    """``entry(device, *args, gamma, limit, horizon, rows, changes, iterations)``, the int32 and float64 arrays among
+    ``args`` as pointers.  Returns ``(rows, changes[:iterations])``."""
+    lib = load_library()
+    rows = np.empty(rows_shape, dtype=np.float64)
     changes = np.zeros(max(int(horizon), 1), dtype=np.float64)
     its = C.c_int32(0)
-    _check(lib.pbvi_mdp_value_iteration(int(device), S, A, R, _p(rs, C.c_int32), _p(p, C.c_double), _p(er, C.c_double),
-                                        _p(v, C.c_double), float(gamma), float(max_change_limit), int(horizon),
-                                        _p(rows, C.c_double), _p(changes, C.c_double), C.byref(its)))
+    args = [_p(a, C.c_int32 if a.dtype == np.int32 else C.c_double) if isinstance(a, np.ndarray) else a for a in args]
+    _check(getattr(lib, entry)(int(device), *args, float(gamma), float(max_change_limit), int(horizon),
+                               _p(rows, C.c_double), _p(changes, C.c_double), C.byref(its)))
     return rows, changes[:its.value]
+
+
+def mdp_value_iteration(reach_states: np.ndarray, reach_prob: np.ndarray, exp_reward: np.ndarray, v0: np.ndarray,
+                        gamma: float, max_change_limit: float, horizon: int, device: int = 0):
+    """MDP value-iteration sweeps on the device (``VI_Solver.solve``, ``src/mdp.py:1485-1510``).  ``reach_states [S,A,R]``,
+    ``reach_prob [S,A,R]``, ``exp_reward [S,A]``, ``v0 [S]``.  Returns ``(rows [A,S] f64, changes [iterations] f64)``;
+    the rows are zero when ``horizon`` is 0."""
+    name = 'mdp_value_iteration'
+    reach_states, reach_prob, S, A, _, R = _sweep_shapes(name, reach_states, reach_prob, exp_reward, horizon, o_axis=False)
+    if np.shape(v0) != (S,):
+        raise ValueError(f'{name}: table shapes do not agree')
+    rs, p, er = _sweep_tables(name, reach_states, reach_prob, exp_reward, S, [(S * A * R, 'S*A*R')])
+    v = np.ascontiguousarray(v0, dtype=np.float64)
+    return _sweep_call('pbvi_mdp_value_iteration', device, (S, A, R, rs, p, er, v), gamma, max_change_limit, horizon, (A, S))
 
 
 def fib_value_iteration(reach_states: np.ndarray, rto: np.ndarray, exp_reward: np.ndarray, q0: np.ndarray,
@@ -339,33 +375,13 @@ def fib_value_iteration(reach_states: np.ndarray, rto: np.ndarray, exp_reward: n
     on the host, bit for bit).  ``reach_states [S,A,R]``, ``rto [S,A,O,R]``, ``exp_reward [S,A]``, ``q0 [A,S]``.
     Returns ``(rows [A,S] f64, changes [iterations] f64)``.  Shapes, the horizon and the successor range are checked
     before the device is touched (``ValueError``); ``S*A*O*R`` beyond int32 is ``NotImplementedError``."""
-    lib = load_library()
-    reach_states, rto = np.asarray(reach_states), np.asarray(rto)
-    if reach_states.ndim != 3 or rto.ndim != 4:
-        raise ValueError('fib_value_iteration: reach_states must be [S,A,R] and rto [S,A,O,R]')
-    S, A, R = reach_states.shape
-    O = rto.shape[2]
-    if rto.shape != (S, A, O, R) or np.shape(exp_reward) != (S, A) or np.shape(q0) != (A, S):
-        raise ValueError('fib_value_iteration: table shapes do not agree')
-    if min(S, A, O, R) <= 0:
-        raise ValueError('fib_value_iteration: empty tables')
-    if int(horizon) < 0:
-        raise ValueError('fib_value_iteration: negative horizon')
-    if S * A * O * R > 0x7fffffff:                       # (before any table is copied: the entry refuses it the same way)
-        raise NotImplementedError('fib_value_iteration: S*A*O*R exceeds int32')
-    if int(reach_states.min()) < 0 or int(reach_states.max()) >= S:
-        raise ValueError('reachable state out of range')
-    rs = np.ascontiguousarray(reach_states, dtype=np.int32)
-    t = np.ascontiguousarray(rto, dtype=np.float64)
-    er = np.ascontiguousarray(exp_reward, dtype=np.float64)
+    name = 'fib_value_iteration'
+    reach_states, rto, S, A, O, R = _sweep_shapes(name, reach_states, rto, exp_reward, horizon)
+    if np.shape(q0) != (A, S):
+        raise ValueError(f'{name}: table shapes do not agree')
+    rs, t, er = _sweep_tables(name, reach_states, rto, exp_reward, S, [(S * A * O * R, 'S*A*O*R')])
     q = np.ascontiguousarray(q0, dtype=np.float64)
-    rows = np.empty((A, S), dtype=np.float64)
-    changes = np.zeros(max(int(horizon), 1), dtype=np.float64)
-    its = C.c_int32(0)
-    _check(lib.pbvi_fib_value_iteration(int(device), S, A, O, R, _p(rs, C.c_int32), _p(t, C.c_double), _p(er, C.c_double),
-                                        _p(q, C.c_double), float(gamma), float(max_change_limit), int(horizon),
-                                        _p(rows, C.c_double), _p(changes, C.c_double), C.byref(its)))
-    return rows, changes[:its.value]
+    return _sweep_call('pbvi_fib_value_iteration', device, (S, A, O, R, rs, t, er, q), gamma, max_change_limit, horizon, (A, S))
 
 
 def controller_value_iteration(reach_states: np.ndarray, rto: np.ndarray, exp_reward: np.ndarray, node_action: np.ndarray,
@@ -377,47 +393,29 @@ def controller_value_iteration(reach_states: np.ndarray, rto: np.ndarray, exp_re
     ``(rows [N,S] f64, changes [iterations] f64)``.  Shapes, the horizon and the ranges of successor states, node actions and
     successor nodes are checked before the device is touched (``ValueError``); ``S*A*O*R`` or ``N*ceil(S/256)`` beyond int32
     is ``NotImplementedError``."""
-    lib = load_library()
-    reach_states, rto, node_action, node_succ = (np.asarray(x) for x in (reach_states, rto, node_action, node_succ))
-    if reach_states.ndim != 3 or rto.ndim != 4:
-        raise ValueError('controller_value_iteration: reach_states must be [S,A,R] and rto [S,A,O,R]')
-    S, A, R = reach_states.shape
-    O = rto.shape[2]
+    name = 'controller_value_iteration'
+    reach_states, rto, S, A, O, R = _sweep_shapes(name, reach_states, rto, exp_reward, horizon)
+    node_action, node_succ = np.asarray(node_action), np.asarray(node_succ)
     if node_action.ndim != 1 or node_succ.ndim != 2:
-        raise ValueError('controller_value_iteration: node_action must be [N] and node_succ [N,O]')
+        raise ValueError(f'{name}: node_action must be [N] and node_succ [N,O]')
     N = node_action.shape[0]
-    if rto.shape != (S, A, O, R) or np.shape(exp_reward) != (S, A) or node_succ.shape != (N, O) or np.shape(v0) != (N, S):
-        raise ValueError('controller_value_iteration: table shapes do not agree')
-    if min(S, A, O, R) <= 0:
-        raise ValueError('controller_value_iteration: empty tables')
+    if node_succ.shape != (N, O) or np.shape(v0) != (N, S):
+        raise ValueError(f'{name}: table shapes do not agree')
     if N <= 0:
-        raise ValueError('controller_value_iteration: no nodes')
-    if int(horizon) < 0:
-        raise ValueError('controller_value_iteration: negative horizon')
-    if S * A * O * R > 0x7fffffff:                       # (before any table is copied: the entry refuses it the same way)
-        raise NotImplementedError('controller_value_iteration: S*A*O*R exceeds int32')
-    if N * ((S + 255) // 256) > 0x7fffffff:
-        raise NotImplementedError('controller_value_iteration: N*ceil(S/256) exceeds int32')
-    if int(reach_states.min()) < 0 or int(reach_states.max()) >= S:
-        raise ValueError('reachable state out of range')
+        raise ValueError(f'{name}: no nodes')
+    rs, t, er = _sweep_tables(name, reach_states, rto, exp_reward, S,
+                              [(S * A * O * R, 'S*A*O*R'), (N * ((S + 255) // 256), 'N*ceil(S/256)')])
     if int(node_action.min()) < 0 or int(node_action.max()) >= A:
         raise ValueError('node action out of range')
     if int(node_succ.min()) < 0 or int(node_succ.max()) >= N:
         raise ValueError('successor node out of range')
-    rs = np.ascontiguousarray(reach_states, dtype=np.int32)
-    t = np.ascontiguousarray(rto, dtype=np.float64)
-    er = np.ascontiguousarray(exp_reward, dtype=np.float64)
     na = np.ascontiguousarray(node_action, dtype=np.int32)
     ns = np.ascontiguousarray(node_succ, dtype=np.int32)
     v = np.ascontiguousarray(v0, dtype=np.float64)
-    rows = np.empty((N, S), dtype=np.float64)
-    changes = np.zeros(max(int(horizon), 1), dtype=np.float64)
-    its = C.c_int32(0)
-    _check(lib.pbvi_controller_value_iteration(int(device), S, A, O, R, _p(rs, C.c_int32), _p(t, C.c_double),
-                                               _p(er, C.c_double), N, _p(na, C.c_int32), _p(ns, C.c_int32), _p(v, C.c_double),
-                                               float(gamma), float(max_change_limit), int(horizon), _p(rows, C.c_double),
-                                               _p(changes, C.c_double), C.byref(its)))
-    return rows, changes[:its.value]
+    return _sweep_call('pbvi_controller_value_iteration', device, (S, A, O, R, rs, t, er, N, na, ns, v), gamma,
+                       max_change_limit, horizon, (N, S))
+
+
 
 
 def _check(rc: int) -> None:

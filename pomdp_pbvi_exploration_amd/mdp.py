@@ -722,6 +722,27 @@ class Solver:
         raise Exception("Method has to be implemented by subclass...")
 
 
+def _run_sweeps(run, host, V, rows, horizon: int, limit: float, hist):
+    """The loop of the solvers whose sweeps run as one call (``VI_Solver`` on the device, ``FIB_Solver``, ``Blind_Solver``):
+    ``run(rows, n) -> (rows, changes)`` makes up to n sweeps from ``rows`` and stops behind the first whose change is below
+    ``limit``.  Every sweep enters ``hist``, until ``horizon`` of them ran or the limit was met.  Returns the last
+    ``ValueFunction`` (``V`` when nothing ran)."""
+    # per-sweep value functions (tracking level 2+) need every sweep's rows: one sweep per call then
+    step = 1 if hist.tracking_level >= 2 else horizon
+    left = horizon
+    while left > 0:
+        t0 = datetime.now()
+        rows, changes = run(rows, min(step, left))
+        V = ValueFunction(host, rows, host.actions)
+        dt = (datetime.now() - t0).total_seconds() / max(len(changes), 1)
+        for c in changes:
+            hist.add(dt, float(c), V)
+        left -= len(changes)
+        if len(changes) == 0 or changes[-1] < limit:
+            break
+    return V
+
+
 class VI_Solver(Solver):
     """MDP value iteration (``src/mdp.py:1414-1525``); seeds FSVI/HSVI.  ``use_gpu=True`` runs the sweeps on the
     device (``pbvi_mdp_value_iteration``): the whole loop is enqueued in batches and only the per-sweep change
@@ -744,22 +765,11 @@ class VI_Solver(Solver):
         limit = self.eps * (self.gamma / (1 - self.gamma))
         if use_gpu:
             from .engine import mdp_value_iteration          # raises if the HIP library is missing
-            # per-sweep value functions (tracking level 2+) need every sweep's rows: one sweep per call then
-            step = 1 if history_tracking_level >= 2 else self.horizon
-            left = self.horizon
-            while left > 0:
-                t0 = datetime.now()
-                rows, changes = mdp_value_iteration(host.reachable_states, host.reachable_probabilities,
-                                                    host.expected_rewards_table, v_opt, self.gamma, limit, min(step, left))
-                V = ValueFunction(host, rows, host.actions)
-                v_opt = np.max(V.alpha_vector_array, axis=0)
-                dt = (datetime.now() - t0).total_seconds() / max(len(changes), 1)
-                for c in changes:
-                    hist.add(dt, float(c), V)
-                left -= len(changes)
-                if len(changes) == 0 or changes[-1] < limit:
-                    break
-            return V, hist
+
+            def run(rows, n):
+                return mdp_value_iteration(host.reachable_states, host.reachable_probabilities, host.expected_rewards_table,
+                                           np.max(rows, axis=0), self.gamma, limit, n)
+            return _run_sweeps(run, host, V, V.alpha_vector_array, self.horizon, limit, hist), hist
         er_t = host.expected_rewards_table.T
         for _ in range(self.horizon):
             t0 = datetime.now()

@@ -23,7 +23,7 @@ import numpy as np
 from .mdp import AlphaVector, ValueFunction, VI_Solver, log, _log, set_quiet   # noqa: F401
 from .mdp import Model as MDP_Model
 from .mdp import Solver as MDP_Solver
-from .mdp import RewardSet, _RowKey, _draw_index             # noqa: F401
+from .mdp import RewardSet, _RowKey, _draw_index, _run_sweeps            # noqa: F401
 from .mdp import SimulationHistory as MDP_SimulationHistory
 from .mdp import Simulation as MDP_Simulation
 from . import dist as _dist
@@ -1387,20 +1387,7 @@ class FIB_Solver(Solver):
         else:
             def run(q, n):
                 return fib_numpy(host, q, self.gamma, limit, n)
-        # per-sweep value functions (tracking level 2+) need every sweep's rows: one sweep per call then
-        step = 1 if history_tracking_level >= 2 else self.horizon
-        left = self.horizon
-        while left > 0:
-            t0 = datetime.now()
-            rows, changes = run(rows, min(step, left))
-            V = ValueFunction(host, rows, host.actions)
-            dt = (datetime.now() - t0).total_seconds() / max(len(changes), 1)
-            for c in changes:
-                hist.add(dt, float(c), V)
-            left -= len(changes)
-            if len(changes) == 0 or changes[-1] < limit:
-                break
-        return V, hist
+        return _run_sweeps(run, host, V, rows, self.horizon, limit, hist), hist
 
 
 # --------------------------------------------------------------------------- #
@@ -1506,21 +1493,11 @@ class Blind_Solver(Solver):
         V = ValueFunction(host, rows, host.actions)
         hist = MDP_SolverHistory(history_tracking_level, host, self.gamma, self.eps, V)
         limit = self.eps * (self.gamma / (1 - self.gamma))
-        # per-sweep value functions (tracking level 2+) need every sweep's rows: one sweep per call then
-        step = 1 if history_tracking_level >= 2 else self.horizon
-        left = self.horizon
-        while left > 0:
-            t0 = datetime.now()
-            rows, changes = evaluate_controller(host, node_action, node_succ, gamma=self.gamma, eps=self.eps,
-                                                horizon=min(step, left), v0=rows, use_gpu=use_gpu)
-            V = ValueFunction(host, rows, host.actions)
-            dt = (datetime.now() - t0).total_seconds() / max(len(changes), 1)
-            for c in changes:
-                hist.add(dt, float(c), V)
-            left -= len(changes)
-            if len(changes) == 0 or changes[-1] < limit:
-                break
-        return V, hist
+
+        def run(rows, n):
+            return evaluate_controller(host, node_action, node_succ, gamma=self.gamma, eps=self.eps, horizon=n, v0=rows,
+                                       use_gpu=use_gpu)
+        return _run_sweeps(run, host, V, rows, self.horizon, limit, hist), hist
 
 
 # --------------------------------------------------------------------------- #
