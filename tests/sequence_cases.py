@@ -2,21 +2,24 @@
 
 The invariant ``tests/test_engine_sequences.py`` states: what a call of an ``Engine`` returns is a function of the engine's
 LOGICAL state -- tables, working alpha set, belief block, row stores, state weights, the point store of the upper bound,
-switches -- and not of the calls that produced that state.  This module holds everything of that test that is plain Python:
+the state policies' table, switches -- and not of the calls that produced that state.  This module holds everything of that
+test that is plain Python:
 
 * two small models (``model('G')``, ``model('I')``) from the generators of ``test_score_window.py`` / ``model_cases.py``;
 * seeded recipes for alpha sets (exact duplicates, ~100 exact ties per triple, near-duplicates) and belief blocks;
 * ``Shadow``: the logical state as NumPy arrays in the engine's precision;
 * the operations (a name and a dict of arguments) and ``Runner``, which applies a list of them to an engine and to the
   shadow, and after every query compares the engine with (a) the fp64 host statements evaluated on the shadow and (b) a
-  fresh engine brought to the shadow's state by ``set_alpha`` / ``set_beliefs``;
+  fresh engine brought to the shadow's state by ``set_alpha`` / ``set_beliefs`` / ``set_state_policy``;
 * ``HostEngine``: a NumPy stand-in with ``Engine``'s method names built on the oracle and the ``*_numpy`` statements, and
-  ten subclasses with one planted carry-over bug each;
+  seventeen subclasses with one planted carry-over bug each;
 * the scripted sequences (literal lists), the seeded generator and the coverage accounting.
 
 Index comparisons follow the rule of the issue: an entry is compared where fp64 can decide it -- the runner-up is an
 identical row (the lowest index is expected) or lies further than 2^-40 x ``ref_magnitude`` below the maximum -- and the
-share of undecided entries of a query may not exceed 0.5 % (the committed sequences have none).
+share of undecided entries of a query may not exceed 0.5 % (the committed sequences have none).  The state policies (most
+likely state, voting, Thompson) are defined bit for bit, so their actions, states, votes and rollout trajectories are compared
+with ``==`` on every entry.
 """
 import functools
 import hashlib
@@ -24,9 +27,13 @@ from types import SimpleNamespace
 
 import numpy as np
 
+import controller_cases as cc
+import fib_cases as fc
 import hsvi_cases as hc
 import model_cases as mc
+import state_policy_cases as spc
 import test_infotaxis as tit
+import test_mdp_device as tmd
 import test_score_window as sw
 import test_space_aware as tsa
 from oracle import pbvi_oracle as orc
@@ -123,6 +130,78 @@ def belief_rows(mname, B, seed, win=None, onehot=False):
         b[one] = 0.0
         b[one, rng.integers(lo, hi, int(one.sum()))] = 1.0
     return f32r(b)
+
+
+POLICY_KINDS = ('constant', 'striped', 'chunk_edges', 'absent_action', 'random')
+POLICY_CHUNK_EDGES = (256, 512)
+
+
+def policy_table(mname, kind, seed):
+    """[S] int64, a per-state action table.  ``constant``: one action everywhere; ``striped``: ``s % A``; ``chunk_edges``: the
+    action changes exactly at 255|256, 511|512 (where the model has those states) and at the last state; ``absent_action``: one
+    action never appears (its vote is exactly +0.0); ``random``: ``state_policy_cases.action_table``."""
+    m = model(mname)
+    S, A, seed = m.S, m.A, int(seed)
+    if kind == 'constant':
+        return np.full(S, seed % A, dtype=np.int64)
+    if kind == 'striped':
+        return (np.arange(S) % A).astype(np.int64)
+    if kind == 'chunk_edges':
+        sa = np.full(S, seed % A, dtype=np.int64)
+        for edge in POLICY_CHUNK_EDGES + (S - 1,):
+            if 0 < edge < S:
+                sa[edge:] = (sa[edge - 1] + 1) % A
+        return sa
+    if kind == 'absent_action':
+        present = np.array([a for a in range(A) if a != seed % A], dtype=np.int64)
+        return present[np.random.default_rng([seed, 101]).integers(0, len(present), S)]
+    if kind == 'random':
+        return spc.action_table(S, A, seed)
+    raise KeyError(kind)
+
+
+def policy_uniforms(B, seed):
+    """[B] uniforms in [0, 1]: random ones, and spread over the block's rows ``state_policy_cases.UNIFORMS`` (0, 0.5, its
+    lower neighbour, 1 - 2^-53, 1) and the upper neighbour of 0.5 (a block of fewer than six rows gets the first of them)."""
+    u = np.random.default_rng([int(seed), int(B), 103]).random(B)
+    edge = list(spc.UNIFORMS) + [float(np.nextafter(0.5, 1.0))]
+    k = min(len(edge), B)
+    u[(np.arange(k) * B) // k] = edge[:k]
+    return u
+
+
+SWEEP_KINDS = ('fib', 'controller', 'mdp')
+SWEEP_GAMMA = 0.95
+
+
+def sweep_inputs(mname, which):
+    """The arguments of three sweeps of a handle-free entry on the model's own tables (what ``HSVI_Solver(upper_init='fib',
+    lower_init='blind')`` runs beside its engine): a mostly negative start, the blind controller."""
+    m = model(mname)
+    if which == 'fib':
+        return (fc.starts(m.tables)['negative'],)
+    if which == 'controller':
+        na, ns = cc.blind(m.A, m.O)
+        return na, ns, cc.starts(m.tables, SWEEP_GAMMA, len(na))['negative']
+    if which == 'mdp':
+        return (tmd.starts(m.S)['negative'],)
+    raise KeyError(which)
+
+
+@functools.lru_cache(maxsize=None)
+def sweeps_ref(mname, which):
+    """``(rows, changes)`` of the host statements the device tests of the three entries use."""
+    t, args = model(mname).tables, sweep_inputs(mname, which)
+    if which == 'fib':
+        return P.fib_numpy(t, *args, SWEEP_GAMMA, 0.0, 3)
+    if which == 'controller':
+        return P.controller_numpy(t, *args, SWEEP_GAMMA, 0.0, 3)
+    return tmd.vi_numpy(t, *args, SWEEP_GAMMA, 0.0, 3)
+
+
+def host_sweeps(mname, which):
+    """``sweeps_beside`` of a runner without a device: the host statements themselves."""
+    return sweeps_ref(mname, which)
 
 
 def digest(*arrays):
@@ -361,6 +440,7 @@ class Shadow:
         self.sel_ids, self.sel_store = None, 0  # the ids of the last selection of alpha rows, the store's length then
         self.weights = None                     # None, or the state weights [S]
         self.store = None                       # None (no corner set), or the point store: corner, pts, vals, gaps, bounds
+        self.policy = None                      # None, or the per-state action table [S] int64 of the state policies
 
     @property
     def n_points(self):
@@ -425,18 +505,23 @@ RESETS = ('after_oom', 'oom_call')
 # state weights, the point store of the upper bound, the space-aware rollout (a belief mutation); behind the older names, so
 # that those keep their places (the seeded lists of the first vocabulary are drawn from them by position)
 GREEDY_MUTATIONS = ('set_state_weights', 'clear_state_weights', 'upper_reset', 'upper_append', 'rollout_space_aware')
+# the state policies' table and their rollout (a belief mutation): the third vocabulary, again behind the older names
+POLICY_MUTATIONS = ('set_state_policy', 'clear_state_policy', 'rollout_state_policy')
 MUTATIONS_V1 = ALPHA_MUTATIONS + BELIEF_MUTATIONS + RESETS
-MUTATIONS = MUTATIONS_V1 + GREEDY_MUTATIONS
+MUTATIONS_V2 = MUTATIONS_V1 + GREEDY_MUTATIONS
+MUTATIONS = MUTATIONS_V2 + POLICY_MUTATIONS
 QUERIES_V1 = ('run_fetch', 'run_prune_fetch', 'run_fetch_into', 'fetch_compact_into', 'keys_assemble', 'row_hashes', 'q_values',
               'vmax_resident', 'vmax_store', 'infotaxis', 'fetch_beliefs', 'prune_dominated', 'prune_masked', 'belief_update',
               'fetch_refused')
-REFUSALS = ('fetch_refused', 'weights_refused', 'upper_refused')
-QUERIES = QUERIES_V1 + ('space_aware', 'upper_bound', 'upper_q', 'weights_refused', 'upper_refused')
+REFUSALS = ('fetch_refused', 'weights_refused', 'upper_refused', 'policy_refused')
+QUERIES_V2 = QUERIES_V1 + ('space_aware', 'upper_bound', 'upper_q', 'weights_refused', 'upper_refused')
+QUERIES = QUERIES_V2 + ('state_policy', 'policy_refused')
 HARNESS = ('remember', 'same_as', 'layout')
 # calls of the Python layer that answer AND move the working sets (counted, but outside the mutation -> query pairs);
-# 'run_only' is a backup that nobody fetches yet
+# 'run_only' is a backup that nobody fetches yet; 'sweeps_beside' runs a handle-free entry between two calls of the engine
 COMPOUND_V1 = ('vmax_objects', 'clear_environment')
-COMPOUND = COMPOUND_V1 + ('mapping_evaluate', 'run_only')
+COMPOUND_V2 = COMPOUND_V1 + ('mapping_evaluate', 'run_only')
+COMPOUND = COMPOUND_V2 + ('sweeps_beside',)
 VOCABULARY = MUTATIONS + ('switch',) + QUERIES + COMPOUND
 VALUE_QUERIES = tuple(q for q in QUERIES if q not in REFUSALS)
 BACKUPS = ('run_fetch', 'run_prune_fetch', 'run_fetch_into', 'q_values')
@@ -454,6 +539,14 @@ def legal(name, args, sh):
         return sh.weights is not None and 0 < B <= MAX_SIMS
     if name == 'weights_refused':
         return sh.weights is None
+    if name == 'state_policy':                                # (uniforms belong to rule 2, votes to rule 1)
+        rule = args['rule']
+        return sh.policy is not None and B > 0 and (args.get('draw', 'hashed') == 'hashed' or rule == 2) and \
+            (not args.get('want_votes', False) or rule == 1)
+    if name == 'rollout_state_policy':
+        return sh.policy is not None and 0 < B <= MAX_SIMS
+    if name == 'policy_refused':
+        return sh.policy is None
     if name in ('upper_bound', 'upper_q'):
         return sh.store is not None and B > 0
     if name == 'upper_refused':
@@ -504,12 +597,14 @@ class Runner:
     a fresh engine from ``make_engine()`` (b).  ``alloc(shape, dtype)`` gives the arrays ``run_fetch_into`` writes (page-locked
     for a device engine); ``provoke_oom(eng)`` makes one call of ``eng`` fail with ``MemoryError``."""
 
-    def __init__(self, mname, dtype, make_engine, alloc=None, provoke_oom=None):
+    def __init__(self, mname, dtype, make_engine, alloc=None, provoke_oom=None, sweeps=None):
         self.m, self.mname, self.dtype = model(mname), mname, dtype
         self.f32 = dtype == 'f32'
         self.npdt = np.float32 if self.f32 else np.float64
         self.make_engine, self.alloc = make_engine, alloc or (lambda shape, dt: np.empty(shape, dtype=dt))
         self.provoke_oom = provoke_oom
+        self.sweeps = sweeps or host_sweeps     # (mname, which) -> (rows, changes) of three sweeps of a handle-free entry
+        self.policy_blocks = set()              # the sizes of the blocks a state_policy query has seen
         self.sh = Shadow(mname, dtype)
         self.eng = make_engine()
         self.entries = self.skipped = 0
@@ -594,6 +689,8 @@ class Runner:
             e.set_beliefs(sh.bel.astype(self.npdt))
         if sh.weights is not None:
             e.set_state_weights(sh.weights)
+        if sh.policy is not None:
+            e.set_state_policy(sh.policy)
         if sh.store is not None:                               # one append of every point, however they came
             e.upper_reset(sh.store.corner)
             if e.upper_append(sh.store.pts, sh.store.vals, sh.store.gaps) != sh.n_points:
@@ -833,11 +930,18 @@ class Runner:
         self._adopt_block(want[4], tol, tol, f'survivors of {what}')
         self.done(**{f'out{k}': v for k, v in enumerate(got)})
 
-    def _starts(self, seed):
-        """True start states inside each belief's support (an observation the belief rules out has no Bayes step)."""
+    def _starts(self, seed, near_end=False):
+        """True start states inside each belief's support (an observation the belief rules out has no Bayes step).
+        ``near_end``: where the support holds a state one step before an end state, one of those (simulations end early
+        and the survivors are compacted while others run on)."""
         rng = np.random.default_rng([int(seed), 59])
         w = (self.sh.bel > 0) & (self.m.end_mask == 0)[None, :]
         w[~w.any(axis=1), 0] = True
+        if near_end:
+            m = self.m
+            before = ((m.end_mask[m.rs] != 0) & (m.rto.sum(axis=2) > 0)).any(axis=(1, 2))           # [S]
+            near = w & before[None, :]
+            w = np.where(near.any(axis=1)[:, None], near, w)
         return np.array([int(rng.choice(np.flatnonzero(row))) for row in w])
 
     def _policy_values(self, policy, acts):
@@ -1283,6 +1387,101 @@ class Runner:
         if holder is None and np.any(self.last['out4']):
             self.fail('rollout_space_aware: a simulation lost in the model\'s world')
 
+    # -- state policies: the table, the three rules, their rollout ------------------------------------------------------------- #
+    def op_set_state_policy(self, kind, seed):
+        sa = policy_table(self.mname, kind, seed)
+        self.eng.set_state_policy(sa)
+        self.sh.policy = sa
+
+    def op_clear_state_policy(self):
+        self.eng.clear_state_policy()
+        self.sh.policy = None
+
+    def op_policy_refused(self):
+        """Both calls raise; the engine stays usable (whatever follows is compared as ever)."""
+        B, m = self.sh.B, self.m
+        calls = [lambda: self.eng.state_policy_resident(0),
+                 lambda: self.eng.rollout_state_policy(np.zeros(B, dtype=np.int64), m.end_mask, 1, 2)]
+        for call in calls:                                     # (without a block they are refused for that, before anything else)
+            try:
+                call()
+            except ValueError:
+                continue
+            self.fail('a state-policy call answered although no table is set')
+        if self.eng.B != B:
+            self.fail(f'a refused call left {self.eng.B} rows resident, the shadow has {B}')
+        self.done()
+
+    def op_state_policy(self, rule, draw='hashed', seed=0, first=0, t=0, want_state=False, want_votes=False):
+        """Actions, states and votes byte for byte: against ``state_policy_numpy`` on the shadow (the three rules are defined bit
+        for bit, so every entry is decided) and against a fresh engine, which is always asked for the long form."""
+        sh, m = self.sh, self.m
+        B = sh.B
+        self.policy_blocks.add(B)
+        if draw == 'uniforms':
+            u = policy_uniforms(B, seed)
+            kw = {'uniforms': u}
+        else:
+            kw = {'seed': int(seed), 'first_sim_id': int(first), 't': int(t)}
+            u = P.thompson_uniform(seed, np.uint64(first) + np.arange(B, dtype=np.uint64), t) if rule == 2 else None
+        got = self.eng.state_policy_resident(rule, want_state=want_state, want_votes=want_votes, **kw)
+        got = got if isinstance(got, tuple) else (got,)
+        f = self.fresh()
+        try:
+            fresh = f.state_policy_resident(rule, want_state=True, want_votes=rule == 1, **kw)
+        finally:
+            f.close()
+        want = P.state_policy_numpy(sh.bel, sh.policy, rule, u, table_dtype=np.float32 if self.f32 else np.float64, action_count=m.A)
+        names = ('actions',) + (('states',) if want_state else ()) + (('votes',) if want_votes else ())
+        if len(got) != len(names):
+            self.fail(f'state_policy returned {len(got)} arrays, asked for {names}')
+        self.count(np.ones(B, dtype=bool), 'state_policy actions')                # (defined bitwise: every one is decided)
+        for name, g in zip(names, got):
+            k = ('actions', 'states', 'votes').index(name)
+            compare = self.same_bits if name == 'votes' else self.same
+            compare(g, want[k], f'state_policy rule {rule} {name} against the host statement')
+            compare(g, fresh[k], f'state_policy rule {rule} {name} against the fresh engine')
+        self.done(**dict(zip(names, got)))
+
+    def op_rollout_state_policy(self, T, seed, rule=0, env=None, env_seed=0, hold=False, starts='any'):
+        """Trajectories, steps and lost byte for byte against a fresh engine in the state before the call and against
+        ``rollout_state_policy_numpy`` (no step is undecided: the rules are defined bitwise); the survivors at the bar, then
+        their bits into the shadow (as ``op_rollout_space_aware``)."""
+        sh, m = self.sh, self.m
+        s0 = self._starts(seed, near_end=starts == 'near_end')
+        holder = None if env is None else self._env(env, env_seed)
+
+        def call(e):
+            if holder is not None and hold:
+                e.hold_environment(holder)
+            elif env == 'table':
+                e.set_environment_table(holder.obs_prob)
+            elif env == 'frames':
+                e.set_environment_frames(holder.frames, holder.channel_of_action)
+            return e.rollout_state_policy(s0, m.end_mask, seed, T, first_sim_id=1000 * seed, rule=rule, use_env=holder is not None)
+        got, fresh = self.both(call)
+        names = ('states', 'actions', 'observations', 'steps', 'lost')
+        for k, name in enumerate(names):
+            self.same(got[k], fresh[k], f'rollout_state_policy {name} against the fresh engine')
+        want = P.rollout_state_policy_numpy(m.tables, sh.bel, s0, sh.policy, rule, seed, 1000 * seed, T,
+                                            table_dtype=np.float32 if self.f32 else np.float64, return_beliefs=True, env=holder)
+        lost = want[5] if holder is not None else np.zeros(len(s0), dtype=np.uint8)
+        for k, name in enumerate(names):
+            self.same(got[k], (want[:4] + (lost,))[k], f'rollout_state_policy {name} against the host statement')
+        self.count(np.ones(got[1].shape, dtype=bool), 'rollout_state_policy actions')
+        tol = BELIEF_TOL[self.dtype]
+        self._adopt_block(want[4], tol, tol, 'survivors of rollout_state_policy')
+        self.done(**{f'out{k}': v for k, v in enumerate(got)})
+
+    def op_sweeps_beside(self, which):
+        """Three sweeps of a handle-free entry on the model's own tables between two calls of the engine: rows and changes
+        bit-equal to the host statement; the engine's handle is not involved, which the next query shows."""
+        rows, changes = self.sweeps(self.mname, which)
+        want_rows, want_changes = sweeps_ref(self.mname, which)
+        self.same_bits(np.asarray(changes, dtype=np.float64), np.asarray(want_changes, dtype=np.float64), f'{which} sweeps: changes')
+        self.same_bits(np.asarray(rows, dtype=np.float64), np.asarray(want_rows, dtype=np.float64), f'{which} sweeps: rows')
+        self.done(rows=rows, changes=changes)
+
     # -- the point store of the upper bound ------------------------------------------------------------------------------------ #
     def op_upper_reset(self, seed):
         corner = hc.corner_values(np.random.default_rng([int(seed), 79]), self.m.S)
@@ -1423,6 +1622,7 @@ class HostEngine:
         self.weights = self.corner = None
         self.points = []
         self.upper_epoch = getattr(self, 'upper_epoch', 0) + 1
+        self.policy = None
 
     def debug_fail_next_call(self):
         self._fail_next = True
@@ -1639,6 +1839,73 @@ class HostEngine:
         out = P.rollout_space_aware_numpy(self.m.tables, self.bel, start_states, self._query_weights(), seed, first_sim_id, T, objective,
                                           table_dtype=self._td(), return_beliefs=True, env=self.env if use_env else None)
         lost = out[5] if use_env else np.zeros(len(start_states), dtype=np.uint8)
+        return self._survivors(out[:4] + (lost,), out[4])
+
+    # state policies
+    def set_state_policy(self, state_actions):
+        self.policy = P._state_actions(self.m.S, self.m.A, state_actions)
+
+    def clear_state_policy(self):
+        self.policy = None
+
+    def _query_policy(self):
+        """Hook of the defective stand-ins: the table a call reads."""
+        return self.policy
+
+    def _query_step(self, t):
+        """Hook of the defective stand-ins: the step the one-shot call hashes."""
+        return t
+
+    def _query_votes(self, votes):
+        """Hook of the defective stand-ins: the votes rule 1 hands back and decides on."""
+        return votes
+
+    def _caller_order(self, arrays):
+        """Hook of the defective stand-ins: the one-shot call's results as the caller sees them."""
+        return arrays
+
+    def _sim_ids(self, ids, first_sim_id, n):
+        """Hook of the defective stand-ins: the ids Thompson hashes for the running simulations (``n`` started)."""
+        return ids
+
+    def state_policy_resident(self, rule, seed=0, first_sim_id=0, t=0, uniforms=None, want_state=False, want_votes=False):
+        if self.bel is None:
+            raise ValueError('no belief block resident')
+        if self.policy is None:
+            raise ValueError('no state policy set')
+        if want_votes and rule != 1:
+            raise ValueError('votes belong to rule 1 (voting)')
+        u = None if uniforms is None else np.asarray(uniforms, dtype=np.float64)
+        if u is None and rule == 2:
+            u = P.thompson_uniform(seed, np.uint64(first_sim_id) + np.arange(self.B, dtype=np.uint64), self._query_step(t))
+        act, st, votes = P.state_policy_numpy(self.bel, self._query_policy(), rule, u, table_dtype=self._td(), action_count=self.m.A)
+        if rule == 1:
+            votes = self._query_votes(votes)
+            act = P._first_greater(votes)
+        act, st, votes = self._caller_order((act, st, votes))
+        out = (act,) + ((st,) if want_state else ()) + ((votes,) if want_votes else ())
+        return out if len(out) > 1 else out[0]
+
+    def rollout_state_policy(self, start_states, end_mask, seed, T, first_sim_id=0, rule=0, use_env=False, shifts=None,
+                             end_observation=-1):
+        """``rollout_state_policy_numpy``'s loop, with the hooks of the stand-ins around Thompson's uniform."""
+        if self.bel is None:
+            raise ValueError('no belief block resident')
+        if self.policy is None:
+            raise ValueError('no state policy set')
+        td, sa = self._td(), self._query_policy()
+        m, T, b, s, _, _ = P._rollout_inputs(self.m.tables, self.bel, start_states, T)
+        block = P._HostBeliefBlock(m, None, b, store_dtype=td)
+
+        def choose(t, ids):
+            self.last_step = t
+            u = P.thompson_uniform(seed, self._sim_ids(ids, first_sim_id, len(s)), t) if rule == 2 else None
+            return block.state_policy_actions(sa, rule, u, td)
+        if use_env:
+            out = P._rollout_env_loop(m, self.env, block, choose, s, seed, first_sim_id, T, td, True, choose_draws=True)
+        else:
+            out = P._rollout_loop(m, block, choose, s, seed, first_sim_id, T, td, True, choose_draws=True)
+        lost = out[5] if use_env else np.zeros(len(s), dtype=np.uint8)
         return self._survivors(out[:4] + (lost,), out[4])
 
     # the point store of the upper bound
@@ -2024,11 +2291,78 @@ class GivenUpPrimaryAnswers(HostEngine):
         self.prim = self.stale_prim = None
 
 
+class TableSurvivesAReset(HostEngine):
+    """``after_oom`` keeps the state policies' table (``sp_set_`` not cleared): a call that must be refused answers."""
+
+    def after_oom(self):
+        keep = getattr(self, 'policy', None)
+        super().after_oom()
+        self.policy = keep
+
+
+class OldTableRead(HostEngine):
+    """A second ``set_state_policy`` keeps the first table's entries (the upload is skipped while a buffer is held)."""
+
+    def set_state_policy(self, state_actions):
+        held = self.policy
+        super().set_state_policy(state_actions)
+        if held is not None:
+            self.policy = held
+
+
+class VotesOfThePreviousBlock(HostEngine):
+    """Rule 1 on a block no larger than the last one hands back the last call's votes for the rows it shares (``sp_votes_`` is
+    sized by the block of the moment and only grows)."""
+
+    def _query_votes(self, votes):
+        old, self.stale_votes = getattr(self, 'stale_votes', None), votes
+        return votes if old is None or old.shape[0] < votes.shape[0] else old[:votes.shape[0]]
+
+    def after_oom(self):
+        super().after_oom()
+        self.stale_votes = None
+
+
+class SimulationIdsRestart(HostEngine):
+    """After a simulation has ended, Thompson's uniform is taken from the compacted row index instead of the simulation's
+    own id (``orig`` not passed on)."""
+
+    def _sim_ids(self, ids, first_sim_id, n):
+        if len(ids) == n:
+            return ids
+        return np.uint64(first_sim_id) + np.arange(len(ids), dtype=np.uint64)
+
+
+class StepSticks(HostEngine):
+    """The one-shot call hashes the last rollout's final ``t`` instead of its own argument."""
+
+    def _query_step(self, t):
+        return getattr(self, 'last_step', None) if getattr(self, 'last_step', None) is not None else t
+
+    def after_oom(self):
+        super().after_oom()
+        self.last_step = None
+
+
+class PolicyInEngineOrder(HostEngine):
+    """The one-shot state-policy call on a sorted block (more than 256 rows) answers in the engine's row order instead of the
+    caller's (``blk_.perm`` not applied)."""
+
+    def _caller_order(self, arrays):
+        if self.B <= 256:
+            return arrays
+        order = sort_order(self.bel)
+        return tuple(None if a is None else a[order] for a in arrays)
+
+
 DEFECTS = {'dead_map_kept': DeadMapKept, 'magnitude_not_merged': MagnitudeNotMerged, 'previous_caller_order': PreviousCallerOrder,
            'fetch_after_set_alpha': FetchAfterSetAlpha, 'store_zero_maps_kept': StoreZeroMapsKept,
            'weights_survive_a_reset': WeightsSurviveAReset, 'old_weights_read': OldWeightsRead,
            'extra_of_the_other_objective': ExtraOfTheOtherObjective, 'append_offsets_restart': AppendOffsetsRestart,
-           'window_sticks': WindowSticks, 'given_up_primary_answers': GivenUpPrimaryAnswers}
+           'window_sticks': WindowSticks, 'given_up_primary_answers': GivenUpPrimaryAnswers,
+           'table_survives_a_reset': TableSurvivesAReset, 'old_table_read': OldTableRead,
+           'votes_of_the_previous_block': VotesOfThePreviousBlock, 'simulation_ids_restart': SimulationIdsRestart,
+           'step_sticks': StepSticks, 'policy_in_engine_order': PolicyInEngineOrder}
 
 
 # --------------------------------------------------------------------------------------------------------------------- #
@@ -2374,6 +2708,92 @@ SCRIPTED['alpha_placements'] = (MODELS, DTYPES, _ALPHA_PLACEMENTS)
 SCRIPTED['alpha_placements_under_the_screen'] = (MODELS, ('f64',), [sw_('f64_screen', 'always')] + _ALPHA_PLACEMENTS)
 
 
+def sp(rule, **args):
+    return op('state_policy', rule=rule, **args)
+
+
+# sp_table_, sp_set_: set, asked under each rule, replaced by every kind, cleared, set again, dropped by both resets (without a
+# block the calls are refused for that, so each reset is followed by a block and a second refusal)
+SCRIPTED['policy_table_lifecycle'] = (MODELS, DTYPES, [
+    op('set_beliefs', B=40, seed=80), op('policy_refused'), op('set_state_policy', kind='random', seed=1),
+    sp(0, want_state=True), sp(1, want_state=True, want_votes=True), sp(2, seed=3, first=5, t=2, want_state=True),
+    op('remember', tag='first'), sp(2, draw='uniforms', seed=4, want_state=True),
+    op('set_state_policy', kind='chunk_edges', seed=2), sp(1, want_votes=True), sp(2, draw='uniforms', seed=4), sp(0),
+    op('set_state_policy', kind='absent_action', seed=3), sp(1, want_votes=True), sp(2, seed=3, first=5, t=2),
+    op('set_state_policy', kind='striped', seed=4), sp(0, want_state=True), sp(1, want_votes=True),
+    op('set_state_policy', kind='constant', seed=5), sp(1, want_votes=True), sp(2, draw='uniforms', seed=5, want_state=True),
+    op('clear_state_policy'), op('policy_refused'), op('set_state_policy', kind='random', seed=1),
+    sp(2, seed=3, first=5, t=2, want_state=True), op('same_as', tag='first'), op('after_oom'), op('policy_refused'),
+    op('set_beliefs', B=40, seed=80), op('policy_refused'), op('set_state_policy', kind='striped', seed=6), sp(0), op('oom_call'),
+    op('policy_refused'), op('fetch_refused'), op('set_beliefs', B=3, seed=81), op('policy_refused'),
+    op('set_state_policy', kind='random', seed=1), sp(1, want_votes=True), sp(2, seed=1, t=1)])
+
+# sp_act_, sp_state_, sp_votes_, sp_sums_, sp_u_ and blk_.perm: sized by the block of the moment -- sorted, tiny, sorted with
+# another window, unsorted; blocks selected out of the store in between
+SCRIPTED['policy_buffers_follow_the_block'] = (MODELS, DTYPES, [
+    op('set_state_policy', kind='random', seed=1), op('store_beliefs', B=300, seed=82, win=LOW),
+    op('store_beliefs', B=257, seed=83, win=HIGH), op('set_beliefs', B=300, seed=84),
+    sp(1, want_state=True, want_votes=True), sp(2, seed=7, first=1 << 40, t=3, want_state=True), sp(2, draw='uniforms', seed=1),
+    op('set_beliefs', B=3, seed=85), sp(1, want_votes=True), sp(2, seed=7, first=1 << 40, t=3, want_state=True), sp(0, want_state=True),
+    op('select_beliefs', how='last', B=257), sp(1, want_votes=True), sp(2, draw='uniforms', seed=2, want_state=True),
+    sp(2, seed=8, t=4), sp(0, want_state=True), op('set_beliefs', B=128, seed=86, win=(0.25, 0.75)), sp(1, want_votes=True),
+    sp(2, seed=9, t=1, want_state=True), op('select_beliefs', how='random', B=300, seed=5), sp(1), sp(2, seed=9, t=1), sp(0),
+    op('set_state_policy', kind='chunk_edges', seed=2), sp(1, want_votes=True), sp(2, draw='uniforms', seed=3, want_state=True)])
+
+
+def _policy_calls_beside_a_backup(switches):
+    """A backup nobody has fetched yet, the three rules, then the three fetches; the same with each of ``switches`` away from
+    its default (the keep mask on and off in turn): the switches do not reach these calls, and these calls do not reach the
+    result."""
+    calls = [('mls', sp(0, want_state=True)), ('voting', sp(1, want_votes=True)), ('thompson', sp(2, seed=5, first=9, t=1, want_state=True)),
+             ('given', sp(2, draw='uniforms', seed=6))]
+    fetches = [op('fetch_compact_into'), op('keys_assemble'), op('row_hashes')]
+    ops = [op('set_alpha', V=12, seed=1), op('set_state_policy', kind='random', seed=1), op('set_beliefs', B=129, seed=87),
+           op('run_fetch'), op('fetch_compact_into'), op('remember', tag='fetched'), op('run_only')]
+    for tag, call in calls:
+        ops += [call, op('remember', tag=tag)]
+    ops += [fetches[0], op('same_as', tag='fetched')] + fetches[1:]
+    n = 0
+    for switch in switches:
+        for value in [v for v in SWITCH_VALUES[switch] if v != SWITCH_DEFAULTS[switch]]:
+            ops += [sw_(switch, value), op('run_only', prune=bool(n % 2))]
+            for tag, call in calls[:3] + calls[3:] * (n % 2):
+                ops += [call, op('same_as', tag=tag)]
+            ops += fetches
+            n += 1
+        ops.append(sw_(switch, SWITCH_DEFAULTS[switch]))
+    return ops + [op('run_only')] + [calls[0][1], op('same_as', tag='mls'), fetches[0], op('same_as', tag='fetched')]
+
+
+# (two sequences, so that neither takes longer than the slowest sequence before them: profiles/sequence_state_policy.md)
+_SWITCH_HALVES = (('formulation', 'f64_screen', 'fused_projection', 'tie_window'),
+                  ('score_split', 'gamma_tiling', 'value_max_exact', 'score_probe'))
+assert set(_SWITCH_HALVES[0]) | set(_SWITCH_HALVES[1]) == set(SWITCH_VALUES)
+SCRIPTED['policy_calls_leave_a_backup_fetchable'] = (MODELS, DTYPES, _policy_calls_beside_a_backup(_SWITCH_HALVES[0]))
+SCRIPTED['policy_calls_leave_a_backup_fetchable_more_switches'] = (MODELS, DTYPES, _policy_calls_beside_a_backup(_SWITCH_HALVES[1]))
+
+# the fifth rollout source: every rule in the model's world and against a held table and a held frame environment (start states
+# one step before an end state where the belief allows: survivors are compacted while others run on); the survivors as the
+# operand of the next backup; the one-shot call with t = 0 behind a rollout that ended at a later step; the handle-free sweeps
+SCRIPTED['policy_rollouts_leave_their_survivors'] = (MODELS, DTYPES, [
+    op('set_alpha', V=12, seed=1), op('set_state_policy', kind='random', seed=1),
+    op('set_beliefs', B=64, seed=92), op('rollout_state_policy', T=4, seed=1, rule=2, starts='near_end'), op('fetch_beliefs'),
+    op('run_fetch'), sp(2, seed=1, first=1000, t=0, want_state=True),
+    op('set_beliefs', B=40, seed=89), op('rollout_state_policy', T=3, seed=2, rule=0), op('run_fetch'), sp(2, seed=2, t=0),
+    op('set_beliefs', B=40, seed=90), op('rollout_state_policy', T=3, seed=3, rule=1, starts='near_end'), op('fetch_beliefs'),
+    sp(1, want_votes=True),
+    op('set_beliefs', B=64, seed=91), op('rollout_state_policy', T=3, seed=4, rule=0, env='table', hold=True), op('run_fetch'),
+    op('set_beliefs', B=40, seed=92), op('rollout_state_policy', T=3, seed=5, rule=1, env='table', hold=True), op('fetch_beliefs'),
+    op('set_beliefs', B=64, seed=93), op('rollout_state_policy', T=5, seed=6, rule=2, env='table', hold=True, starts='near_end'),
+    op('run_fetch'), sp(2, seed=6, first=6000, t=0, want_state=True),
+    op('set_beliefs', B=40, seed=94), op('rollout_state_policy', T=3, seed=7, rule=0, env='frames', env_seed=1, hold=True),
+    op('fetch_beliefs'), op('sweeps_beside', which='fib'), op('run_fetch'),
+    op('set_beliefs', B=40, seed=95), op('rollout_state_policy', T=3, seed=8, rule=1, env='frames', env_seed=1, hold=True),
+    op('sweeps_beside', which='controller'), op('run_fetch'), sp(1, want_votes=True),
+    op('set_beliefs', B=64, seed=96), op('rollout_state_policy', T=5, seed=9, rule=2, env='frames', env_seed=1, hold=True, starts='near_end'),
+    op('fetch_beliefs'), op('sweeps_beside', which='mdp'), op('run_fetch'), sp(2, seed=9, first=9000, t=0, want_state=True)])
+
+
 def pair_sequence(mutation):
     """Set-up, one mutation, then every query that is legal behind it (a backup in between where a query needs one)."""
     setup = [op('store_alpha', V=12, seed=1), op('select_alpha', how='all'), op('store_beliefs', B=40, seed=1),
@@ -2390,27 +2810,33 @@ def pair_sequence(mutation):
            'after_oom': [op('after_oom')], 'oom_call': [op('oom_call')],
            'set_state_weights': [op('set_state_weights', kind='big', seed=16)], 'clear_state_weights': [op('clear_state_weights')],
            'upper_reset': [op('upper_reset', seed=17)], 'upper_append': [op('upper_append', P=3, seed=18)],
-           'rollout_space_aware': [op('rollout_space_aware', T=2, seed=19, objective=0)]}[mutation]
-    # the greedy calls' state: weights and a store of points, some of them rows of the block
-    greedy = [op('set_state_weights', kind='zero_ends', seed=1), op('upper_reset', seed=1), op('upper_append', P=5, seed=1)]
+           'rollout_space_aware': [op('rollout_space_aware', T=2, seed=19, objective=0)],
+           'set_state_policy': [op('set_state_policy', kind='chunk_edges', seed=20)], 'clear_state_policy': [op('clear_state_policy')],
+           'rollout_state_policy': [op('rollout_state_policy', T=2, seed=21, rule=2)]}[mutation]
+    # the greedy calls' state: weights, a store of points, some of them rows of the block, and a state policy
+    greedy = [op('set_state_weights', kind='zero_ends', seed=1), op('upper_reset', seed=1), op('upper_append', P=5, seed=1),
+              op('set_state_policy', kind='random', seed=1)]
     if mutation in RESETS:
         return setup + greedy + mut + [op(q) for q in REFUSALS]
     keeps_result = ('store_alpha', 'store_beliefs', 'belief_walk', 'reset_alpha_store', 'reset_belief_store_append') + \
-        tuple(m for m in GREEDY_MUTATIONS if m != 'rollout_space_aware')
+        tuple(m for m in GREEDY_MUTATIONS + POLICY_MUTATIONS if not m.startswith('rollout_'))
     first = [] if mutation in keeps_result else [op('fetch_refused')]
     tail = [op('fetch_beliefs'), op('infotaxis'), op('space_aware', objective=0, terms=True), op('upper_bound', window='stale'),
-            op('upper_q', window='all', extras=True), op('vmax_resident'), op('vmax_store'), op('run_fetch'), op('fetch_compact_into'),
-            op('keys_assemble'), op('row_hashes'), op('run_prune_fetch'), op('run_fetch_into'), op('q_values'),
-            op('belief_update', seed=1), op('prune_masked', seed=1), op('prune_dominated')]
+            op('upper_q', window='all', extras=True), sp(2, seed=1, t=1, want_state=True), op('vmax_resident'), op('vmax_store'),
+            op('run_fetch'), op('fetch_compact_into'), op('keys_assemble'), op('row_hashes'), op('run_prune_fetch'),
+            op('run_fetch_into'), op('q_values'), op('belief_update', seed=1), op('prune_masked', seed=1), op('prune_dominated')]
     if mutation == 'clear_state_weights':
         tail = [t for t in tail if t[0] != 'space_aware']
+    if mutation == 'clear_state_policy':
+        tail = [t for t in tail if t[0] != 'state_policy']
     if mutation in keeps_result:
         tail = tail + [op('q_values'), op('fetch_refused')]                       # these leave the result where it is
-    # ... and the same mutation in an engine without weights and without a corner, for the two refusals (where the mutation
-    # itself does not give the engine what they miss)
-    needs = {'rollout_space_aware': greedy[:1], 'upper_append': greedy[1:2]}.get(mutation, [])
+    # ... and the same mutation in an engine without weights, without a corner and without a table, for the three refusals
+    # (where the mutation itself does not give the engine what they miss)
+    needs = {'rollout_space_aware': greedy[:1], 'upper_append': greedy[1:2], 'rollout_state_policy': greedy[3:]}.get(mutation, [])
     refusals = [op(q) for q, givers in (('weights_refused', ('set_state_weights', 'rollout_space_aware')),
-                                        ('upper_refused', ('upper_reset', 'upper_append'))) if mutation not in givers]
+                                        ('upper_refused', ('upper_reset', 'upper_append')),
+                                        ('policy_refused', ('set_state_policy', 'rollout_state_policy'))) if mutation not in givers]
     return setup + greedy + mut + first + tail + [op('after_oom')] + setup + needs + mut + refusals
 
 
@@ -2423,7 +2849,11 @@ DEFECT_SCRIPTS = {'dead_map_kept': 'dead_triples_and_tile_lists', 'magnitude_not
                   'store_zero_maps_kept': 'belief_store_zero_maps', 'weights_survive_a_reset': 'weights_lifecycle',
                   'old_weights_read': 'weights_lifecycle', 'extra_of_the_other_objective': 'successor_score_buffers',
                   'append_offsets_restart': 'point_store_lifecycle', 'window_sticks': 'point_store_lifecycle',
-                  'given_up_primary_answers': 'alpha_placements'}
+                  'given_up_primary_answers': 'alpha_placements',
+                  'table_survives_a_reset': 'policy_table_lifecycle', 'old_table_read': 'policy_table_lifecycle',
+                  'votes_of_the_previous_block': 'policy_buffers_follow_the_block',
+                  'simulation_ids_restart': 'policy_rollouts_leave_their_survivors', 'step_sticks': 'policy_rollouts_leave_their_survivors',
+                  'policy_in_engine_order': 'policy_buffers_follow_the_block'}
 
 
 def scripted_cases():
@@ -2435,9 +2865,14 @@ def scripted_cases():
 # --------------------------------------------------------------------------------------------------------------------- #
 QUERY_WEIGHTS = {'run_fetch': 4, 'run_prune_fetch': 2, 'vmax_resident': 2, 'vmax_store': 2, 'q_values': 2, 'run_fetch_into': 2,
                  'space_aware': 4, 'upper_bound': 4, 'upper_q': 4}        # (the greedy calls: the weight a backup has)
+# the third vocabulary: three rules share one name; the refusal is legal only while no table is set, which is rare, so it is
+# likely then; the plain backup keeps its share among the many names
+QUERY_WEIGHTS_V3 = dict(QUERY_WEIGHTS, state_policy=6, policy_refused=8, run_fetch=6)
 MUTATION_WEIGHTS = {'after_oom': 0.2, 'oom_call': 0.2}            # (a reset empties the engine: rare, and re-populated at once)
+MUTATION_WEIGHTS_V3 = {'after_oom': 0.6, 'oom_call': 0.6}         # (the table is dropped by a reset: less rare)
 ECHOED = ('set_alpha', 'set_beliefs', 'select_beliefs', 'extend_alpha', 'reset_belief_store_append')
 ECHOED_V2 = ECHOED + ('set_state_weights', 'upper_append')
+ECHOED_V3 = ECHOED_V2 + ('set_state_policy',)
 MIN_VALUE_QUERIES, MIN_BACKUPS = 8, 3                           # per seeded sequence (fetch_refused compares no value)
 MAX_UPPER_Q_ROWS = 64                                           # (the host's bounds walk every successor in Python)
 SUPPORT_CHOICES = (hc.SUPPORTS, hc.SUPPORTS[1:], (65, None))
@@ -2448,16 +2883,31 @@ def draw_op(rng, sh, kind, last=None, vocabulary=1):
     ``last``: the most recent mutation.  Carry-overs show when the same kind of state comes again with other content, so
     four times in ten a mutation repeats the last one's kind and sizes with another seed and window; queries lean towards
     the backup, and towards the store scan behind a change of the belief store.  ``vocabulary``: 1 -- the names before the
-    greedy calls came (the first committed lists are drawn from them, draw for draw); 2 -- every name."""
+    greedy calls came (the first committed lists are drawn from them, draw for draw); 2 -- the names before the state
+    policies came (likewise); 3 -- every name."""
     pick = lambda xs: xs[int(rng.integers(0, len(xs)))]
     seed = int(rng.integers(1, 1000))
-    v2 = vocabulary >= 2
-    queries = QUERIES if v2 else QUERIES_V1
+    v2, v3 = vocabulary >= 2, vocabulary >= 3
+    queries = QUERIES if v3 else (QUERIES_V2 if v2 else QUERIES_V1)
     if kind == 'query':
-        w = np.array([QUERY_WEIGHTS.get(q, 1) for q in queries], dtype=np.float64)
+        w = np.array([(QUERY_WEIGHTS_V3 if v3 else QUERY_WEIGHTS).get(q, 1) for q in queries], dtype=np.float64)
         if last is not None and last[0] in ('store_beliefs', 'reset_belief_store_append', 'belief_walk'):
             w[queries.index('vmax_store')] *= 6
+        after_rollout = v3 and last is not None and last[0] == 'rollout_state_policy'
+        if after_rollout:                                         # the one-shot call behind its rollout: the same buffers, its own t
+            w[queries.index('state_policy')] *= 4
         name = queries[int(rng.choice(len(queries), p=w / w.sum()))]
+        if name == 'state_policy':
+            rule = int(pick((0, 1, 2, 2, 2, 2) if after_rollout else (0, 1, 2, 2)))
+            args = dict(rule=rule, want_state=bool(rng.random() < 0.5))
+            if rule == 1:
+                args['want_votes'] = bool(rng.random() < 0.7)
+            if rule == 2:
+                args['draw'] = pick(('hashed', 'hashed', 'uniforms'))
+                args['seed'] = seed
+                if args['draw'] == 'hashed':
+                    args.update(first=int(pick((0, 5, 1 << 40))), t=int(pick((0, 1, 7, (1 << 31) - 1))))
+            return op(name, **args)
         if name == 'space_aware':
             return op(name, objective=int(pick((0, 1))), terms=bool(rng.random() < 0.5))
         if name == 'upper_bound':
@@ -2472,20 +2922,24 @@ def draw_op(rng, sh, kind, last=None, vocabulary=1):
         value = pick([v for v in SWITCH_VALUES[name] if v != sh.switches[name]])
         return sw_(name, value)
     win = pick((None, LOW, HIGH, (0.25, 0.75)))
-    if last is not None and last[0] in (ECHOED_V2 if v2 else ECHOED) and rng.random() < 0.4:
+    if last is not None and last[0] in (ECHOED_V3 if v3 else (ECHOED_V2 if v2 else ECHOED)) and rng.random() < 0.4:
         args = dict(last[1], seed=seed)
         if 'win' in args:
             args['win'] = win
         if 'kind' in args:
-            args['kind'] = pick(tsa.WEIGHT_KINDS)
+            args['kind'] = pick(POLICY_KINDS if last[0] == 'set_state_policy' else tsa.WEIGHT_KINDS)
         return (last[0], args)
-    names = MUTATIONS + COMPOUND if v2 else MUTATIONS_V1 + COMPOUND_V1
-    w = np.array([MUTATION_WEIGHTS.get(n, 1.0) for n in names])
+    names = MUTATIONS + COMPOUND if v3 else (MUTATIONS_V2 + COMPOUND_V2 if v2 else MUTATIONS_V1 + COMPOUND_V1)
+    w = np.array([(MUTATION_WEIGHTS_V3 if v3 else MUTATION_WEIGHTS).get(n, 1.0) for n in names])
     if v2:                                                        # the greedy calls need their state: it comes back soon
         w[names.index('set_state_weights')] = 2.0 if sh.weights is None else 1.0
         w[names.index('upper_reset')] = 2.0 if sh.store is None else 0.4
         w[names.index('upper_append')] = 2.0
         w[names.index('clear_state_weights')] = 0.4
+    if v3:                                                        # ... and so do the state policies
+        w[names.index('set_state_policy')] = 3.0 if sh.policy is None else 1.5
+        w[names.index('clear_state_policy')] = 0.4
+        w[names.index('rollout_state_policy')] = 3.0
     name = names[int(rng.choice(len(names), p=w / w.sum()))]
     small = rng.random() < 0.6                                    # most sets are small; every edge still comes up
     V = int(pick((5, 12, 40) if small else V_EDGES))
@@ -2510,6 +2964,13 @@ def draw_op(rng, sh, kind, last=None, vocabulary=1):
     if name == 'rollout_space_aware':
         return op(name, T=int(pick((1, 3, 5))), seed=seed, objective=int(pick((0, 1))), env=pick((None, 'table', 'frames')),
                   env_seed=int(pick((0, 1, 2))), hold=bool(rng.random() < 0.5))
+    if name == 'set_state_policy':
+        return op(name, kind=pick(POLICY_KINDS), seed=seed)
+    if name == 'rollout_state_policy':
+        return op(name, T=int(pick((3, 5))), seed=seed, rule=int(pick((0, 1, 2, 2))), env=pick((None, 'table', 'frames')),
+                  env_seed=int(pick((0, 1, 2))), hold=bool(rng.random() < 0.5), starts=pick(('any', 'near_end')))
+    if name == 'sweeps_beside':
+        return op(name, which=pick(SWEEP_KINDS))
     if name == 'mapping_evaluate':
         add = int(pick((0, 1, 5)))
         return op(name, which=int(pick((0, 1))), add=add, seed=seed, B=int(pick((3, 40))), update=bool(add == 0 or rng.random() < 0.5))
@@ -2536,7 +2997,7 @@ def draw_op(rng, sh, kind, last=None, vocabulary=1):
 
 
 def seed_parts(seed):
-    """``(vocabulary, number)`` of a committed seed: a plain number (the first vocabulary) or ``'v2-<number>'``."""
+    """``(vocabulary, number)`` of a committed seed: a plain number (the first vocabulary), ``'v2-<number>'`` or ``'v3-<number>'``."""
     if isinstance(seed, str):
         v, n = seed.split('-')
         return int(v[1:]), int(n)
@@ -2558,6 +3019,8 @@ def generate(mname, dtype, seed, n_ops=N_RANDOM_OPS):
     if vocabulary > 1:                                            # ... and with weights and a point store
         ops = [op('set_state_weights', kind=tsa.WEIGHT_KINDS[int(seed) % 5], seed=int(seed) + 1), op('upper_reset', seed=int(seed) + 1),
                op('upper_append', P=int((5, 63, 64, 70)[int(seed) % 4]), seed=int(seed) + 1)] + ops
+    if vocabulary > 2:                                            # ... and with a state policy
+        ops = [op('set_state_policy', kind=POLICY_KINDS[int(seed) % 5], seed=int(seed) + 1)] + ops
     r.run(ops)
     last, prev_kind = ops[-2], 'mutation'
 
@@ -2575,7 +3038,8 @@ def generate(mname, dtype, seed, n_ops=N_RANDOM_OPS):
             add(last)
             prev_kind = 'mutation'
             continue
-        p_query = {'mutation': 0.6, 'switch': 0.5, 'query': 0.15}[prev_kind]
+        # (the third vocabulary spends one more operation on its prologue: its walk asks a little more often)
+        p_query = ({'mutation': 0.65, 'switch': 0.55, 'query': 0.25} if vocabulary > 2 else {'mutation': 0.6, 'switch': 0.5, 'query': 0.15})[prev_kind]
         u = rng.random()
         kind = 'query' if u < p_query else ('switch' if u < p_query + 0.15 else 'mutation')
         for _ in range(100):
@@ -2616,9 +3080,16 @@ SEEDS_V2 = {('G', 'f32'): (1, 4, 5, 7, 10, 21, 25, 28), ('G', 'f64'): (1, 3, 6, 
             ('I', 'f32'): (0, 3, 8, 10, 12, 17, 26, 33), ('I', 'f64'): (2, 3, 8, 9, 10, 17, 29, 37)}
 
 
+# the seeds of the third vocabulary (the state policies' table, rules and rollouts, the sweeps beside the engine): chosen the
+# same way, every stand-in of the state policies failing at least one of them
+SEEDS_V3 = {('G', 'f32'): (0, 1, 4, 5, 12, 13, 24, 31), ('G', 'f64'): (1, 4, 5, 10, 14, 21, 22, 31),
+            ('I', 'f32'): (1, 2, 5, 6, 10, 12, 13, 16), ('I', 'f64'): (1, 3, 6, 8, 9, 10, 11, 27)}
+
+
 def seeded_cases():
     return [(mname, dtype, seed) for mname in MODELS for dtype in DTYPES for seed in SEEDS[mname, dtype]] + \
-        [(mname, dtype, f'v2-{seed}') for mname in MODELS for dtype in DTYPES for seed in SEEDS_V2[mname, dtype]]
+        [(mname, dtype, f'v{v}-{seed}') for v, seeds in ((2, SEEDS_V2), (3, SEEDS_V3)) for mname in MODELS for dtype in DTYPES
+         for seed in seeds[mname, dtype]]
 
 
 def to_json(ops):
@@ -2636,14 +3107,17 @@ NEVER_LEGAL_AFTER_A_RESET = {(m, q) for m in RESETS for q in QUERIES if q not in
 # a refusal is never legal right behind the mutation that gives the engine what the call misses, nor the call behind the
 # mutation that takes it away
 NEVER_LEGAL_BY_CONSTRUCTION = {('set_state_weights', 'weights_refused'), ('rollout_space_aware', 'weights_refused'),
-                               ('clear_state_weights', 'space_aware'), ('upper_reset', 'upper_refused'), ('upper_append', 'upper_refused')}
+                               ('clear_state_weights', 'space_aware'), ('upper_reset', 'upper_refused'), ('upper_append', 'upper_refused'),
+                               ('set_state_policy', 'policy_refused'), ('rollout_state_policy', 'policy_refused'),
+                               ('clear_state_policy', 'state_policy')}
 
 
 def coverage(sequences):
     """Counts over ``[(mname, dtype, ops)]``: operations, (most recent mutation -> query) pairs, switch values, B and V."""
     counts = {n: 0 for n in VOCABULARY}
     pairs, switch_values, Bs, Vs, hows, returned, envs = set(), set(), set(), set(), set(), set(), set()
-    greedy = {k: set() for k in ('kinds', 'windows', 'q_windows', 'appends', 'supports', 'space_aware', 'sa_rollouts', 'hit_blocks', 'mapping')}
+    greedy = {k: set() for k in ('kinds', 'windows', 'q_windows', 'appends', 'supports', 'space_aware', 'sa_rollouts', 'hit_blocks', 'mapping',
+                                 'table_kinds', 'rule_draws', 'want_state', 'want_votes', 'sp_rollouts', 'sweeps')}
     for _, _, ops in sequences:
         last, now, left = None, dict(SWITCH_DEFAULTS), set()
         for name, args in ops:
@@ -2688,5 +3162,16 @@ def coverage(sequences):
                 greedy['hit_blocks'].add(args['B'])
             if name == 'mapping_evaluate':
                 greedy['mapping'].add((args.get('which', 0), bool(args.get('add', 0)), bool(args.get('update', False))))
+            if name == 'set_state_policy':
+                greedy['table_kinds'].add(args['kind'])
+            if name == 'state_policy':
+                greedy['rule_draws'].add((args['rule'], args.get('draw', 'hashed')))
+                greedy['want_state'].add(bool(args.get('want_state', False)))
+                if args['rule'] == 1:
+                    greedy['want_votes'].add(bool(args.get('want_votes', False)))
+            if name == 'rollout_state_policy':
+                greedy['sp_rollouts'].add((args.get('rule', 0), args.get('env')))
+            if name == 'sweeps_beside':
+                greedy['sweeps'].add(args['which'])
     return SimpleNamespace(counts=counts, pairs=pairs, switch_values=switch_values, Bs=Bs, Vs=Vs, hows=hows, returned=returned,
                            envs=envs, **greedy)

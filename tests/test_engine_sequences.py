@@ -5,18 +5,22 @@ the pre-split belief plane, the primary alpha layout and its magnitude row, the 
 fused tile map, the belief store's zero maps, the speculation about the refinement, the fetchable result).  The invariant:
 
     what a call returns is a function of the engine's logical state -- tables, working alpha set, belief block, row stores,
-    switches -- and not of the calls that produced that state.
+    state weights, the point store of the upper bound, the state policies' table, switches -- and not of the calls that
+    produced that state.
 
 ``sequence_cases.py`` holds the sequences (scripted ones aimed at one carry-over each, seeded random ones), the shadow of
 the logical state and the ``Runner`` that, after every query, compares the engine with (a) the fp64 host statements on the
-shadow's arrays and (b) a fresh engine brought to that state by ``set_alpha`` / ``set_beliefs``: indices, actions, masks,
-unique rows, keys, hashes, ``q``, infotaxis, space-aware infotaxis, the sawtooth bound and its action values (over a point
-store the fresh engine receives in ONE append), ``fetch_beliefs`` and rollout trajectories byte for byte, value maxima (also
-through ``max_value_objects``) and, where the score probe is on, ``best_score`` at the bar.  Where the engine's own output becomes state (``advance_beliefs``, ``belief_walk``, rollout survivors, ``store_unique``)
-it is checked against the host statement at the bar and its bits are adopted into the shadow.
+shadow's arrays and (b) a fresh engine brought to that state by ``set_alpha`` / ``set_beliefs`` / ``set_state_policy``:
+indices, actions, masks, unique rows, keys, hashes, ``q``, infotaxis, space-aware infotaxis, the sawtooth bound and its action
+values (over a point store the fresh engine receives in ONE append), ``fetch_beliefs`` and rollout trajectories byte for byte,
+the state policies' actions, states and votes byte for byte against both (the three rules are defined bit for bit), value
+maxima (also through ``max_value_objects``) and, where the score probe is on, ``best_score`` at the bar.  Where the engine's
+own output becomes state (``advance_beliefs``, ``belief_walk``, rollout survivors, ``store_unique``) it is checked against the
+host statement at the bar and its bits are adopted into the shadow.  ``sweeps_beside`` runs three sweeps of a handle-free
+entry (FIB, the blind controller, MDP value iteration) between two calls of the engine, bit-equal to its host statement.
 
 CPU tests: every sequence runs against ``HostEngine`` (the host statements under ``Engine``'s method names) with no entry
-skipped as undecidable; eleven stand-ins with one planted carry-over bug each fail a scripted and a seeded sequence; the
+skipped as undecidable; seventeen stand-ins with one planted carry-over bug each fail a scripted and a seeded sequence; the
 operation lists cover the vocabulary.  GPU tests: the same sequences on the HIP engine, both models, both engine types.
 """
 import functools
@@ -113,11 +117,23 @@ def test_the_sequences_cover_the_vocabulary():
     assert cov.appends >= {0, 1, 63, 64, 65} and cov.supports >= set(sc.hc.SUPPORTS), (cov.appends, cov.supports)
     assert cov.hit_blocks >= {3, 257, 300}, cov.hit_blocks
     assert cov.mapping >= {(w, a, u) for w in (0, 1) for a, u in ((True, True), (True, False), (False, True))}, cov.mapping
-    # the four forms a selection of alpha rows takes, named by the shadow's restatement of the engine's bookkeeping
-    forms = set()
+    # the state policies: every kind of table, every rule with hashed uniforms and rule 2 with given ones (uniforms belong to
+    # rule 2 only), the long and the short forms, every rule's rollout in the model's world and against both environments, all
+    # three handle-free entries beside the engine
+    assert cov.table_kinds >= set(sc.POLICY_KINDS), cov.table_kinds
+    assert cov.rule_draws >= {(0, 'hashed'), (1, 'hashed'), (2, 'hashed'), (2, 'uniforms')}, cov.rule_draws
+    assert cov.want_state == {False, True} and cov.want_votes == {False, True}, (cov.want_state, cov.want_votes)
+    assert cov.sp_rollouts >= {(r, e) for r in (0, 1, 2) for e in (None, 'table', 'frames')}, cov.sp_rollouts
+    assert cov.sweeps >= set(sc.SWEEP_KINDS), cov.sweeps
+    # the four forms a selection of alpha rows takes, named by the shadow's restatement of the engine's bookkeeping, and the
+    # blocks a state_policy query has seen (both sorted sizes among them)
+    forms, policy_blocks = set(), set()
     for mname, dtype, ops in all_sequences()[:len(sc.scripted_cases())]:
-        forms |= set(host_runner(mname, dtype).run(ops).forms)
+        r = host_runner(mname, dtype).run(ops)
+        forms |= set(r.forms)
+        policy_blocks |= r.policy_blocks
     assert forms >= {'extend', 'exhaust', 'small', 'primary', 'fresh'}, forms
+    assert policy_blocks >= {3, 128, 257, 300}, policy_blocks
 
 
 def test_the_backup_reference_is_the_oracles():
@@ -191,7 +207,18 @@ def device_runner(mname, dtype):
         finally:
             em.debug_alloc_limit(prev)
 
-    return sc.Runner(mname, dtype, make, alloc=alloc, provoke_oom=provoke_oom)
+    def sweeps(mname, which):
+        """Three sweeps of a handle-free entry on the model's tables (the arguments of ``sc.sweeps_ref``'s host statements)."""
+        t, args = m.tables, sc.sweep_inputs(mname, which)
+        if which == 'fib':
+            return em.fib_value_iteration(t.reachable_states, t.reachable_transitional_observation_table, t.expected_rewards_table,
+                                          *args, sc.SWEEP_GAMMA, 0.0, 3)
+        if which == 'controller':
+            return em.controller_value_iteration(t.reachable_states, t.reachable_transitional_observation_table,
+                                                 t.expected_rewards_table, *args, sc.SWEEP_GAMMA, 0.0, 3)
+        return em.mdp_value_iteration(*sc.tmd.mdp_tables(t), *args, sc.SWEEP_GAMMA, 0.0, 3)
+
+    return sc.Runner(mname, dtype, make, alloc=alloc, provoke_oom=provoke_oom, sweeps=sweeps)
 
 
 def run_on_device(mname, dtype, ops):
