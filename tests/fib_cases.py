@@ -16,6 +16,13 @@ from pomdp_pbvi_exploration_amd import load_POMDP_file
 
 FILE_MODELS = {'tiger': 'tiger.95.POMDP', 'tiger-grid': 'tiger-grid.POMDP', 'hallway': 'hallway.POMDP'}
 _FILES = {}
+# (A, O, R) around k_fib_sweep<TW, PAIRS>'s a'-tiles: TW = 4 up to A = 4, else 8; double2 loads for even A.  Per instantiation
+# a full tile, a short one and (TW = 8) a full tile followed by a tail, over which the running maximum is carried:
+#   TW 4 scalar: 1, 3            TW 4 pairs: 2, 4
+#   TW 8 scalar: 5, 7 (short), 9 (full + 1), 17 (two full + 1)
+#   TW 8 pairs:  6 (short), 8 (full), 10, 12 (full + pair tail), 16 (two full)
+ACTION_CASES = ((1, 1, 1), (2, 2, 2), (7, 5, 4), (8, 1, 2), (9, 2, 4), (17, 5, 1),
+                (3, 2, 2), (4, 3, 2), (5, 2, 3), (6, 2, 2), (10, 2, 2), (12, 1, 3), (16, 2, 1))
 
 
 def tables(rs, rto, er):

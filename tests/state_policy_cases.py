@@ -1,5 +1,6 @@
 """Shared inputs and plain-Python statements of the state policies (``test_state_policy``, ``test_state_policy_device``):
-belief rows that exercise the chunk edges, per-state action tables, and the definition of include/pbvi_hip.h written as
+belief rows that exercise the chunk edges, the seam between two chunk groups and the MLS lane stride, per-state action tables, a
+model that is sparse at any S, and the definition of include/pbvi_hip.h written as
 loops, one add at a time -- what ``pomdp.state_policy_numpy`` and ``pbvi_state_policy`` are compared with bit for bit."""
 import numpy as np
 
@@ -7,6 +8,13 @@ CHUNK = 256
 SIZES = [2, 11, 255, 256, 257, 513, 600]
 UNIFORMS = [0.0, 0.5, float(np.nextafter(0.5, 0.0)), 1.0 - 2.0 ** -53, 1.0]
 ACTION_COUNTS = [1, 4, 9, 17]
+# The voting and Thompson walks of k_state_policy take the chunks in groups of 128 (one per thread of the row's block); the
+# definition knows no groups, so the statements below are an independent reference for everything that depends on the group.
+GROUP = 128 * CHUNK
+SEAM_SIZES = (32767, 32768, 32769, 33000, 65537)    # 128 chunks, the last ragged | one full group | two groups, the second one
+                                                    # state | the 75 x 440 olfactory grid: a ragged chunk in group 1 | three groups
+MLS_WRAP_SIZES = (1023, 1024, 1025, 1281)           # an fp32 engine's MLS lanes (256, 4 states a load) wrap above 1024 states
+SEAM_UNIFORMS = (0.0, 0.25, float(np.nextafter(0.25, 0.0)), 0.5, float(np.nextafter(0.5, 0.0)), 0.75, 1.0 - 2.0 ** -53, 1.0)
 
 
 def r32(a):
@@ -41,6 +49,93 @@ def belief_rows(S, seed=0):
     b[:S // 2] = 0.0
     rows.append(b / b.sum())
     return r32(np.array(rows))
+
+
+def seam_marks(S):
+    """The states of the exact boundary row: the first and the last state of the last chunk of group 0, the first state of
+    group 1 and the last state (``S > GROUP``); else the first and last state of the last two chunks.  Needs ``S > CHUNK``."""
+    if S > GROUP:
+        return [GROUP - CHUNK, GROUP - 1, GROUP, S - 1]
+    last = (S - 1) // CHUNK * CHUNK
+    return [last - CHUNK, last - 1, last, S - 1]
+
+
+def seam_tie_states(S):
+    """``(lower, upper)``: the states of the vote-tie row.  The first four lie in group 0 only (two chunks, two states each),
+    the last one in group >= 1 only (``S > GROUP``; else: in the chunk before the last, and in the last)."""
+    edge = GROUP if S > GROUP else (S - 1) // CHUNK * CHUNK
+    return [edge - 2 * CHUNK + 7, edge - CHUNK - 1, edge - CHUNK, edge - 1], [edge]
+
+
+def seam_rows(S, seed=0):
+    """``{name: [S] row}``, fp64 rows whose values are fp32 numbers, around the seam between two chunk groups:
+        dense         random mass everywhere: 128 or more chunk partials behind every vote and every Thompson prefix
+        behind, front (``S > GROUP``) all mass in ``[GROUP, S)`` / in ``[0, GROUP)``
+        boundary      0.25 on each of ``seam_marks(S)`` (coinciding states add up): every partial sum is exact, so u = 0.25,
+                      0.5, 0.75 put Thompson's target ON a cumulative sum and ``nextafter(u, 0)`` one ulp below it; the
+                      equal maxima are MLS's tie across the seam
+        one_hot_<s>   at the last state of group 0, the first of group 1 and the last state
+        vote_tie      0.0625 on four states of group 0, 0.25 on one state of group 1 (``seam_tie_states``): under
+                      ``seam_tie_table`` two actions get the same votes, one from either side of the seam"""
+    rng = np.random.default_rng(4000 + S + seed)
+    rows = {}
+    b = rng.random(S)
+    rows['dense'] = b / b.sum()
+    if S > GROUP:
+        b = np.zeros(S)
+        b[GROUP:] = rng.random(S - GROUP) + 0.01
+        rows['behind'] = b / b.sum()
+        b = np.zeros(S)
+        b[:GROUP] = rng.random(GROUP)
+        rows['front'] = b / b.sum()
+    b = np.zeros(S)
+    np.add.at(b, seam_marks(S), 0.25)
+    rows['boundary'] = b
+    for s in sorted(set(seam_marks(S)[1:])):
+        b = np.zeros(S)
+        b[s] = 1.0
+        rows[f'one_hot_{s}'] = b
+    lower, upper = seam_tie_states(S)
+    b = np.zeros(S)
+    b[lower] = 0.0625
+    b[upper] = 0.25
+    rows['vote_tie'] = b
+    return {name: r32(row) for name, row in rows.items()}
+
+
+def seam_tie_table(S, A, seed=0):
+    """``action_table`` with the lower states of ``seam_tie_states`` on action 1 and the upper one on action ``A - 1``: on
+    the ``vote_tie`` row both get exactly 0.25, every other action +0.0, and action 1 must win.  ``A >= 3``."""
+    sa = action_table(S, A, seed)
+    lower, upper = seam_tie_states(S)
+    sa[lower] = 1
+    sa[upper] = A - 1
+    return sa
+
+
+def lane_tie_rows(S):
+    """Rows whose equal maxima lie 512 and (``S > 1024``) 1024 states apart: the stride of one MLS lane on an fp64 / fp32
+    engine, so that one lane compares the two: the lower state must win.  In the last row of either stride the later state
+    holds more, and must win.  Needs ``S > 512``."""
+    rows = []
+    for d in (512, 1024):
+        if S <= d:
+            continue
+        for lo in sorted({0, S - 1 - d}):
+            b = np.zeros(S)
+            b[[lo, lo + d]] = 0.5
+            rows.append(b)
+        b = np.zeros(S)
+        b[0], b[d] = 0.25, 0.75
+        rows.append(b)
+    return np.array(rows)
+
+
+def bare_model(S, A):
+    """``(rs [S,A,1], rto [S,A,1,1])`` of a deterministic model with one observation: ``rs[s, a, 0] = (s + a + 1) % S``.  Nothing
+    of it is dense in S x S, so it can be built at any S."""
+    rs = ((np.arange(S, dtype=np.int64)[:, None] + np.arange(A, dtype=np.int64)[None, :] + 1) % S)[:, :, None]
+    return rs, np.ones((S, A, 1, 1))
 
 
 def action_table(S, A, seed=0):

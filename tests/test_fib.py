@@ -42,6 +42,12 @@ def test_restatement_matches_dense_brute_force_on_random_models(seed):
     check_against_dense(t, gamma, seed)
 
 
+@pytest.mark.parametrize('A,O,R', fc.ACTION_CASES)
+def test_restatement_matches_dense_brute_force_around_the_action_tiles(A, O, R):
+    """The shapes at which ``test_fib_device`` holds the kernel to ``fib_numpy`` bit for bit."""
+    check_against_dense(fc.dense_random_case(A, O, R), 0.95, (A, O, R))
+
+
 def test_restatement_stops_and_returns_the_last_sweep_that_ran():
     t = fc.structure_case('ragged', 65)
     q0 = np.zeros((2, 65))

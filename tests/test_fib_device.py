@@ -15,7 +15,7 @@ from pomdp_pbvi_exploration_amd.engine import debug_live_bytes, fib_value_iterat
 pytestmark = pytest.mark.gpu
 
 EDGE_SIZES = (1, 63, 64, 65, 255, 256, 257, 600)                # around one wave (64) and one block (256) of states
-ACTION_CASES = ((1, 1, 1), (2, 2, 2), (7, 5, 4), (8, 1, 2), (9, 2, 4), (17, 5, 1))     # (A, O, R): A around the tiles of 4 and 8
+ACTION_CASES = fc.ACTION_CASES                                  # (A, O, R): every width of the a'-tiles of 4 and 8
 BATCH = 64                                                      # sweeps the entry enqueues between two synchronisations
 
 

@@ -110,6 +110,172 @@ def test_argument_checks():
     assert got.tobytes() == state_policy_numpy(spc.r32(x), spc.action_table(300, 4), 1, action_count=4)[2].tobytes()
 
 
+# --------------------------------------------------------------------------------------------------------------------- #
+# The seam between two chunk groups (128 chunks = 32768 states) and the MLS lane wrap: the inputs of
+# ``test_state_policy_device``'s seam tests, the host statement on them, and what they can tell apart
+# --------------------------------------------------------------------------------------------------------------------- #
+SEAM_A = 9
+
+
+@pytest.mark.parametrize('S', spc.SEAM_SIZES)
+def test_seam_rows_sit_where_they_say(S):
+    rows = spc.seam_rows(S)
+    for name, row in rows.items():
+        assert row.shape == (S,) and np.array_equal(row, spc.r32(row)) and row.sum() > 0 and np.all(row >= 0), name
+    assert ('behind' in rows) == ('front' in rows) == (S > spc.GROUP)
+    if S > spc.GROUP:
+        assert not np.any(rows['behind'][:spc.GROUP]) and np.all(rows['behind'][spc.GROUP:] > 0)
+        assert not np.any(rows['front'][spc.GROUP:]) and np.count_nonzero(rows['front']) > spc.GROUP - 8
+        assert rows['one_hot_%d' % (spc.GROUP - 1)][spc.GROUP - 1] == 1.0 and rows['one_hot_%d' % spc.GROUP][spc.GROUP] == 1.0
+    assert rows['one_hot_%d' % (S - 1)][S - 1] == 1.0
+    assert np.count_nonzero(rows['dense']) > S - 8
+    # the boundary row: every cumulative sum is one of the stated uniforms times the total, exactly; the chunk in front of
+    # the seam ends ON 0.5, so u = 0.5 is the first state behind the seam and one ulp less the last state in front of it
+    b = rows['boundary']
+    total = float(np.cumsum(b)[-1])
+    assert total == 1.0 and set(np.cumsum(b).tolist()) <= {0.0, 0.25, 0.5, 0.75, 1.0}
+    C = -(-S // spc.CHUNK)
+    chunk_sums = np.cumsum(np.add.reduceat(b, np.arange(C) * spc.CHUNK))
+    assert set(chunk_sums.tolist()) <= {0.0} | {u * total for u in (0.5, 0.75, 1.0)}
+    first, last_front, first_behind, last = spc.seam_marks(S)
+    assert first % spc.CHUNK == 0 and last_front == first + spc.CHUNK - 1 and first_behind == last_front + 1 and last == S - 1
+    assert (first_behind == spc.GROUP) == (S > spc.GROUP)
+    assert chunk_sums[last_front // spc.CHUNK] == 0.5 * total and (first_behind == 0 or chunk_sums[last_front // spc.CHUNK - 1] == 0.0)
+    assert thompson_state_numpy(b[None], np.array([0.5]))[0] == first_behind
+    assert thompson_state_numpy(b[None], np.array([np.nextafter(0.5, 0.0)]))[0] == last_front
+    assert state_policy_numpy(b[None], spc.action_table(S, SEAM_A), 0)[1][0] == (first if last > first_behind else first_behind)
+    # the vote tie: the same bits from either side of the seam, nothing for anybody else, and the lower action wins
+    sa = spc.seam_tie_table(S, SEAM_A)
+    lower, upper = spc.seam_tie_states(S)
+    edge = spc.GROUP if S > spc.GROUP else (S - 1) // spc.CHUNK * spc.CHUNK         # the first state behind the seam
+    assert max(lower) < edge <= min(upper) and np.all(sa[lower] == 1) and np.all(sa[upper] == SEAM_A - 1)
+    assert set(np.flatnonzero(rows['vote_tie']).tolist()) == set(lower) | set(upper)
+    W = pomdp_mod.state_policy_votes(rows['vote_tie'][None], sa, SEAM_A)[0]
+    assert W[1].tobytes() == W[SEAM_A - 1].tobytes() and W[1] == 0.25 and np.count_nonzero(W) == 2
+    assert state_policy_numpy(rows['vote_tie'][None], sa, 1, action_count=SEAM_A)[0][0] == 1
+
+
+@pytest.mark.parametrize('table_dtype', [np.float64, np.float32])
+@pytest.mark.parametrize('S', spc.SEAM_SIZES + spc.MLS_WRAP_SIZES)
+def test_the_statement_equals_the_loops_on_the_seam_rows(S, table_dtype):
+    """Every rule: states, actions and vote bits.  The loops know chunks and nothing of groups or lanes."""
+    rows = spc.seam_rows(S)
+    b = np.concatenate([np.array(list(rows.values())), spc.lane_tie_rows(S)])
+    names = list(rows) + ['lane_tie'] * (b.shape[0] - len(rows))
+    sa = spc.seam_tie_table(S, SEAM_A)
+    act, st, _ = state_policy_numpy(b, sa, 0, table_dtype=table_dtype)
+    act_v, _, W = state_policy_numpy(b, sa, 1, table_dtype=table_dtype, action_count=SEAM_A)
+    for i, name in enumerate(names):
+        s = spc.first_greater_loop(b[i])
+        assert st[i] == s and act[i] == sa[s], (S, name)
+        want = spc.votes_loop(b[i], sa, SEAM_A)
+        assert W[i].tobytes() == want.tobytes() and act_v[i] == spc.first_greater_loop(want), (S, name)
+    for u in spc.SEAM_UNIFORMS:
+        act, st, _ = state_policy_numpy(b, sa, 2, np.full(b.shape[0], u), table_dtype=table_dtype)
+        for i, name in enumerate(names):
+            s = spc.thompson_loop(b[i], u)[0]
+            assert st[i] == s and act[i] == sa[s] and b[i, s] > 0, (S, name, u)
+
+
+def _partials(b, sa, A):
+    """Per chunk: the prefix sums ``q [C,256]``, the mass ``m [C]`` and the votes ``Wc [C,A]`` of one row."""
+    S = b.shape[0]
+    C = -(-S // spc.CHUNK)
+    bc, act = np.zeros(C * spc.CHUNK), np.full(C * spc.CHUNK, -1)
+    bc[:S], act[:S] = b, sa
+    bc, act = bc.reshape(C, spc.CHUNK), act.reshape(C, spc.CHUNK)
+    q = np.cumsum(bc, axis=1)
+    return q, q[:, -1].copy(), np.stack([np.cumsum(np.where(act == a, bc, 0.0), axis=1)[:, -1] for a in range(A)], axis=1)
+
+
+def _grouped(b, sa, A, u, defect=None, lanes=128):
+    """The statement of one row as a kernel organises it -- chunk partials combined group by group (``lanes`` chunks), the
+    Thompson prefix and the votes carried from one group to the next -- with one planted ``defect``:
+        'restart'  the Thompson prefix starts again at 0 in every group
+        'drop'     the chunks behind the first group are never read
+        'short'    the last group combines one partial too few: its last chunk is lost
+        'long'     the last group combines one partial too many: the one left in the next lane by the group before it
+    Returns ``(W [A], Thompson's state)``.  Without a defect it is the definition."""
+    q, m, Wc = _partials(b, sa, A)
+    C = m.shape[0]
+    if defect == 'drop':
+        q[lanes:], m[lanes:], Wc[lanes:] = 0.0, 0.0, 0.0
+    P, W, run = np.zeros(C), np.zeros(A), 0.0
+    for lo in range(0, C, lanes):
+        nvalid = min(C - lo, lanes)
+        last_group = lo + lanes >= C
+        if defect == 'restart':
+            run = 0.0
+        take = list(range(lo, lo + nvalid))
+        if last_group and defect == 'short':
+            take = take[:-1]
+        if last_group and defect == 'long' and lo > 0 and nvalid < lanes:
+            take.append(lo - lanes + nvalid)
+        for c in take:
+            run = run + m[c]
+            W = W + Wc[c]
+            if c >= lo:
+                P[c] = run
+    target = u * run
+    hit = np.flatnonzero(target < P)
+    c = int(hit[0]) if hit.size else int(np.flatnonzero(m > 0)[-1]) if np.any(m > 0) else 0
+    r = target - (P[c - 1] if c > 0 else 0.0)
+    hit = np.flatnonzero(r < q[c])
+    held = np.flatnonzero(b[spc.CHUNK * c:spc.CHUNK * (c + 1)] > 0)
+    j = int(hit[0]) if hit.size else int(held[-1]) if held.size else 0
+    return W, spc.CHUNK * c + j
+
+
+def _mls_keeps_the_later_tie(b, stride=1024, vec=4):
+    """Most likely state with ``>=`` inside a lane (a lane holds the states ``s`` with equal ``s // vec % (stride // vec)``)
+    and the lower state between lanes."""
+    s = np.arange(b.shape[0])
+    lane = s // vec % (stride // vec)
+    best = []
+    for k in np.unique(lane):
+        mine = s[lane == k]
+        best.append(int(mine[len(mine) - 1 - np.argmax(b[mine][::-1])]))
+    best = np.array(best)
+    return int(best[b[best] == b[best].max()].min())
+
+
+@pytest.mark.parametrize('S', [32769, 65537])
+def test_the_seam_rows_catch_a_wrong_grouping(S):
+    """A device with one of ``_grouped``'s defects could not pass the seam tests: each changes a vote bit or a drawn state
+    on at least one seam row."""
+    rows = spc.seam_rows(S)
+    sa = spc.seam_tie_table(S, SEAM_A)
+    caught = {d: [] for d in ('restart', 'drop', 'short', 'long')}
+    for name, b in rows.items():
+        W_true = state_policy_numpy(b[None], sa, 1, action_count=SEAM_A)[2][0]
+        for u in spc.SEAM_UNIFORMS:
+            s_true = state_policy_numpy(b[None], sa, 2, np.array([u]))[1][0]
+            W, s = _grouped(b, sa, SEAM_A, u)
+            assert W.tobytes() == W_true.tobytes() and s == s_true, (S, name, u)        # the model of the kernel is right
+            for d in caught:
+                W, s = _grouped(b, sa, SEAM_A, u, d)
+                if W.tobytes() != W_true.tobytes() or s != s_true:
+                    caught[d].append((name, u))
+    for d, where in caught.items():
+        assert where, (S, d)
+    # the boundary row alone tells a restarted prefix and a dropped group: its u = 0.5 is the first state behind the seam
+    assert ('boundary', 0.5) in caught['restart'] and ('boundary', 0.5) in caught['drop']
+    behind = rows['behind']
+    assert state_policy_numpy(behind[None], sa, 0)[1][0] >= spc.GROUP                      # and MLS has to look there
+
+
+def test_the_lane_tie_rows_catch_a_later_tie():
+    """At 1025 states an fp32 engine's lane 0 holds states 0..3 and 1024: only there does it compare two candidates."""
+    S = 1025
+    b = spc.lane_tie_rows(S)                                      # ties {0, 512}, {512, 1024}, {0, 1024}; a later maximum at 512, 1024
+    want = state_policy_numpy(b, spc.action_table(S, 4), 0)[1]
+    assert want.tolist() == [0, 512, 512, 0, 1024] == [spc.first_greater_loop(row) for row in b]
+    assert [_mls_keeps_the_later_tie(row) for row in b] == [0, 512, 512, 1024, 1024]            # fp32: 1024 states a stride
+    assert [_mls_keeps_the_later_tie(row, stride=512, vec=2) for row in b] == [512, 1024, 512, 1024, 1024]     # fp64: 512
+    for row in spc.seam_rows(S).values():                         # the seam rows hold no such tie: they would let it pass
+        assert _mls_keeps_the_later_tie(row) == spc.first_greater_loop(row)
+
+
 def _sa(c, seed=0):
     return spc.action_table(c.m.state_count, c.m.action_count, seed)
 

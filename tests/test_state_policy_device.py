@@ -4,8 +4,13 @@ the host statements ``state_policy_numpy`` / ``rollout_state_policy_numpy``.
 The definition (include/pbvi_hip.h) fixes the order of every add, so actions, states and the BITS of the votes are compared
 exactly: there is no tolerance in the one-shot call.  A rollout is compared entry for entry with the host's; only the
 beliefs left in the block after it pass through Bayes steps whose sums the device takes in another order, and are held to
-``test_device_rollout``'s belief bars."""
+``test_device_rollout``'s belief bars.
+
+The voting and Thompson walks take the chunks in groups of 128 (32768 states): the tests "past one chunk group" run every
+rule with two and three groups, with a last group of one chunk, on the rows of ``state_policy_cases.seam_rows``, whose host
+side ``test_state_policy`` holds to the loop definitions and shows to catch a wrong grouping."""
 import ctypes as C
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -16,9 +21,10 @@ import test_device_rollout as tdr
 import test_infotaxis as tit
 import test_rollout_env as tre
 from pomdp_pbvi_exploration_amd import pomdp as pomdp_mod
+from pomdp_pbvi_exploration_amd import synth
 from pomdp_pbvi_exploration_amd.pomdp import (FrameEnvironment, SimulationSet, StatePolicy_Agent, TableEnvironment,
                                               rollout_state_policy_numpy, rollout_uniform, state_policy_numpy)
-from test_device_rollout import BELIEF_TOL, CASES, N_SIM, SEED, T_STEPS, _assert_padding, end_mask, get_case
+from test_device_rollout import BELIEF_TOL, CASES, SEED, T_STEPS, _assert_padding, end_mask, get_case
 
 NP_DTYPE = {'f64': np.float64, 'f32': np.float32}
 T_ROLL = 12
@@ -45,8 +51,8 @@ def given_uniforms(n):
     return u
 
 
-def check_one_shot(eng, b, sa, A, dtype, tag):
-    """Every rule, hashed and given uniforms, on the resident block ``b``."""
+def check_one_shot(eng, b, sa, A, dtype, tag, every_row=()):
+    """Every rule, hashed and given uniforms, on the resident block ``b``; each uniform of ``every_row`` given to every row."""
     n = b.shape[0]
     npdt = NP_DTYPE[dtype]
     eng.set_state_policy(sa)
@@ -74,6 +80,10 @@ def check_one_shot(eng, b, sa, A, dtype, tag):
         st = eng.state_policy_resident(2, uniforms=np.full(n, x), want_state=True)[1]
         edge = [np.flatnonzero(row > 0)[0 if x == 0.0 else -1] for row in held]
         assert np.array_equal(st, edge), (tag, x)
+    for x in every_row:
+        act, st = eng.state_policy_resident(2, uniforms=np.full(n, x), want_state=True)
+        want = state_policy_numpy(b, sa, 2, np.full(n, x), table_dtype=npdt)
+        assert np.array_equal(st, want[1]) and np.array_equal(act, want[0]), (tag, x, np.flatnonzero(st != want[1]))
     assert eng.B == n
 
 
@@ -109,6 +119,118 @@ def test_one_shot_on_bare_blocks(S, A, dtype):
         votes = eng.state_policy_resident(1, want_votes=True)[1]
         assert votes.tobytes() == state_policy_numpy(block_rows(S, 3), sa, 1, table_dtype=NP_DTYPE[dtype], action_count=A)[2].tobytes()
         assert not np.any(votes[:, 3:]) and not np.any(np.signbit(votes))
+    finally:
+        eng.close()
+
+
+def seam_block(S, fill=4, seed=0):
+    """``(names, rows)``: ``state_policy_cases.seam_rows`` (the boundary row first) and ``fill`` sparse rows."""
+    rows = spc.seam_rows(S, seed)
+    names = ['boundary'] + [k for k in rows if k != 'boundary']
+    sparse = spc.r32(mc.sparse_beliefs(np.random.default_rng(60 + S + seed), fill, S, density=0.1))
+    return names + ['sparse'] * fill, np.concatenate([np.array([rows[k] for k in names]), sparse])
+
+
+def check_seam_one_shot(m, dtype, tag):
+    """Every rule on the seam rows under the vote-tie table; every seam uniform on every row, the boundary row among them."""
+    S, A = m.state_count, m.action_count
+    names, b = seam_block(S)
+    sa = spc.seam_tie_table(S, A)
+    assert b.shape[0] <= 16
+    eng = tit.make_engine(m, dtype)
+    try:
+        check_one_shot(eng, b, sa, A, dtype, tag, every_row=spc.SEAM_UNIFORMS)
+        act, st, votes = eng.state_policy_resident(1, want_state=True, want_votes=True)
+        tie = names.index('vote_tie')                             # both sides of the seam: the same bits, the lower action
+        assert votes[tie, 1].tobytes() == votes[tie, A - 1].tobytes() == np.float64(0.25).tobytes() and act[tie] == 1
+        assert np.count_nonzero(votes[tie]) == 2
+        first, last_front, first_behind, last = spc.seam_marks(S)
+        st = eng.state_policy_resident(0, want_state=True)[1]     # MLS's tie across the seam: the lowest of the equal maxima
+        assert st[0] == (first if last > first_behind else first_behind)
+        for u, want in ((0.5, first_behind), (float(np.nextafter(0.5, 0.0)), last_front)):
+            assert eng.state_policy_resident(2, uniforms=np.full(b.shape[0], u), want_state=True)[1][0] == want, (tag, u)
+    finally:
+        eng.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('dtype', ['f64', 'f32'])
+@pytest.mark.parametrize('S,A', [(32767, 3), (32768, 9), (32769, 9), (65537, 17)])
+def test_one_shot_past_one_chunk_group(S, A, dtype):
+    """One group with a ragged last chunk, one full group, two groups (the second: one chunk of one state), three groups; 9 and
+    17 actions cross the register tile of 8 and the seam in one launch."""
+    rs, rto = spc.bare_model(S, A)
+    check_seam_one_shot(tit.tables(S, A, 1, 1, rs, rto), dtype, f'{S}-{A}')
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('dtype', ['f64', 'f32'])
+def test_one_shot_on_the_sea_robin_shape(dtype):
+    """S = 61875 = 165 x 375, A = 16: two groups, the second of 114 chunks, the last of them ragged."""
+    S, A, O, rs, rto, _, _, _ = synth.sea_robin_like(V=1, B=1)
+    assert (S, A) == (61875, 16)
+    check_seam_one_shot(tit.tables(S, A, O, 1, rs, rto), dtype, 'sea-robin')
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('dtype', ['f64', 'f32'])
+@pytest.mark.parametrize('S', spc.MLS_WRAP_SIZES)
+def test_mls_lane_wrap_on_the_f32_engine(S, dtype):
+    """Above 1024 states a lane of the fp32 engine (512: of the fp64 engine) holds more than one load, and compares its
+    candidates itself: ties one lane stride apart, where the lower state must win."""
+    A = 9
+    rs, rto = spc.bare_model(S, A)
+    b = np.concatenate([spc.belief_rows(S), spc.lane_tie_rows(S), np.array(list(spc.seam_rows(S).values()))])
+    eng = tit.make_engine(tit.tables(S, A, 1, 1, rs, rto), dtype)
+    try:
+        check_one_shot(eng, b, spc.seam_tie_table(S, A), A, dtype, f'wrap-{S}')
+        ties = spc.lane_tie_rows(S)
+        eng.set_beliefs(ties)
+        st = eng.state_policy_resident(0, want_state=True)[1]
+        assert st.tolist() == [spc.first_greater_loop(row) for row in ties], S
+    finally:
+        eng.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('dtype', ['f64', 'f32'])
+def test_seam_rows_do_not_depend_on_the_block(dtype):
+    """At S = 32769 (two groups) the seam rows alone, reversed and inside a 257-row block, which the engine sorts: the same
+    actions, states and vote bits."""
+    S, A = 32769, 9
+    names, b = seam_block(S, fill=0)
+    n = b.shape[0]
+    u = np.resize(np.array(spc.SEAM_UNIFORMS), n)                 # (the boundary row, row 0, has 0.0 here and every other one below)
+    rng = np.random.default_rng(S)
+    big = np.concatenate([spc.r32(mc.sparse_beliefs(rng, 257 - n, S, density=0.05)), b])
+    where = rng.permutation(257)
+    big_u = np.concatenate([rng.random(257 - n), u])
+    rs, rto = spc.bare_model(S, A)
+    eng = tit.make_engine(tit.tables(S, A, 1, 1, rs, rto), dtype)
+
+    def every_rule(rows, uu):
+        eng.set_beliefs(rows)
+        return (eng.state_policy_resident(0, want_state=True) + eng.state_policy_resident(1, want_state=True, want_votes=True)
+                + eng.state_policy_resident(2, uniforms=uu, want_state=True))
+    try:
+        sa = spc.seam_tie_table(S, A)
+        eng.set_state_policy(sa)
+        alone = every_rule(b, u)
+        want = (state_policy_numpy(b, sa, 0, table_dtype=NP_DTYPE[dtype])[:2] + state_policy_numpy(b, sa, 1, table_dtype=NP_DTYPE[dtype], action_count=A)
+                + state_policy_numpy(b, sa, 2, u, table_dtype=NP_DTYPE[dtype])[:2])
+        for k in range(len(alone)):
+            assert np.array_equal(alone[k], want[k]), k
+        moved = every_rule(b[::-1], u[::-1])
+        for k in range(len(alone)):
+            assert moved[k].tobytes() == np.ascontiguousarray(alone[k][::-1]).tobytes(), k
+        for x in spc.SEAM_UNIFORMS:                               # the boundary row alone, on and one ulp below every cumulative sum
+            one = every_rule(b[:1], np.array([x]))
+            act, st, _ = state_policy_numpy(b[:1], sa, 2, np.array([x]), table_dtype=NP_DTYPE[dtype])
+            assert one[5][0] == act[0] and one[6][0] == st[0], x
+        inside = every_rule(big[where], big_u[where])
+        back = np.argsort(where)[257 - n:]                        # where the seam rows went
+        for k in range(len(alone)):
+            assert np.ascontiguousarray(inside[k][back]).tobytes() == alone[k].tobytes(), (k, names)
     finally:
         eng.close()
 
@@ -155,11 +277,18 @@ def test_a_rows_results_do_not_depend_on_the_block(dtype):
         eng.close()
 
 
-def check_rollout(name, dtype, rule, kind=None):
-    """One device run against the host's, entry for entry; the same run cut into two calls; the block left behind."""
-    c = get_case(name)
+def rollout_case(name):
+    """``test_device_rollout``'s case ``name`` with what ``check_rollout`` reads besides: the case's name, its table ``sa``,
+    the steps ``T`` and the simulation ``cut`` at which the run is cut into two calls."""
+    return SimpleNamespace(**vars(get_case(name)), name=name, sa=case_table(name), T=T_ROLL, cut=100)
+
+
+def check_rollout(case, dtype, rule, kind=None):
+    """One device run against the host's, entry for entry; the same run cut into two calls; the block left behind.
+    ``case``: the name of a case of ``test_device_rollout``, or a case object as ``rollout_case`` returns."""
+    c = rollout_case(case) if isinstance(case, str) else case
+    name, sa, n, T, cut = c.name, c.sa, c.b0.shape[0], c.T, c.cut
     m, _, b0 = tdr.as_engine_holds(c, dtype)
-    sa = case_table(name)
     env = None if kind is None else tre.case_env(name, kind)
     frames = isinstance(env, FrameEnvironment)
     eng = tit.make_engine(c.m, dtype)
@@ -167,7 +296,7 @@ def check_rollout(name, dtype, rule, kind=None):
     def device(lo, hi):
         sub = None if env is None else env.rows(lo, hi)
         eng.set_beliefs(c.b0[lo:hi])
-        out = eng.rollout_state_policy(c.s0[lo:hi], end_mask(c.m), SEED, T_ROLL, first_sim_id=1000 + lo, rule=rule,
+        out = eng.rollout_state_policy(c.s0[lo:hi], end_mask(c.m), SEED, T, first_sim_id=1000 + lo, rule=rule,
                                        use_env=env is not None,
                                        shifts=np.broadcast_to(sub.shifts, (hi - lo,)) if frames else None,
                                        end_observation=-1 if env is None else env.end_observation)
@@ -176,26 +305,26 @@ def check_rollout(name, dtype, rule, kind=None):
         eng.set_state_policy(sa)
         if env is not None:
             tre.install(eng, env)
-        got, block = device(0, N_SIM)
-        want = rollout_state_policy_numpy(m, b0, c.s0, sa, rule, SEED, 1000, T_ROLL, table_dtype=NP_DTYPE[dtype],
+        got, block = device(0, n)
+        want = rollout_state_policy_numpy(m, b0, c.s0, sa, rule, SEED, 1000, T, table_dtype=NP_DTYPE[dtype],
                                           return_beliefs=True, env=env)
         assert all(x.dtype == np.int32 for x in got[:4]) and len(got) == 5 and got[4].dtype == np.uint8
         for k, what in enumerate(('states', 'actions', 'observations', 'steps')):
             differ = int(np.sum(got[k] != want[k]))
             assert differ == 0, (name, dtype, rule, kind, what, differ)
-        assert np.array_equal(got[4], want[5] if env is not None else np.zeros(N_SIM, dtype=np.uint8))
+        assert np.array_equal(got[4], want[5] if env is not None else np.zeros(n, dtype=np.uint8))
         if env is None:
             _assert_padding(got[0], got[1], got[2], got[3], c.m.end_states)
-        for i in range(N_SIM):                                    # -1 behind the last step, in every array
+        for i in range(n):                                        # -1 behind the last step, in every array
             k = int(got[3][i])
-            assert 1 <= k <= T_ROLL and np.all(got[0][:k + 1, i] >= 0) and np.all(got[1][:k, i] >= 0) and np.all(got[2][:k, i] >= 0)
+            assert 1 <= k <= T and np.all(got[0][:k + 1, i] >= 0) and np.all(got[1][:k, i] >= 0) and np.all(got[2][:k, i] >= 0)
             assert np.all(got[0][k + 1:, i] == -1) and np.all(got[1][k:, i] == -1) and np.all(got[2][k:, i] == -1)
-        running = int(np.sum((got[3] == T_ROLL) & (got[4] == 0) & ~np.isin(got[0][-1], c.m.end_states)))
+        running = int(np.sum((got[3] == T) & (got[4] == 0) & ~np.isin(got[0][-1], c.m.end_states)))
         assert running == eng.B == int(eng._lib.pbvi_beliefs_count(eng._h))
         assert block.shape == want[4].shape and eng.B == want[4].shape[0]
         if block.shape[0]:
             np.testing.assert_allclose(block, want[4], rtol=BELIEF_TOL[dtype], atol=BELIEF_TOL[dtype])
-        (first, b_first), (second, b_second) = device(0, 100), device(100, N_SIM)
+        (first, b_first), (second, b_second) = device(0, cut), device(cut, n)
         for k in range(5):
             assert np.array_equal(got[k], np.concatenate([first[k], second[k]], axis=-1)), (name, dtype, rule, kind, k)
         assert b_first.shape[0] + b_second.shape[0] == block.shape[0]
@@ -217,6 +346,37 @@ def test_device_rollout_equals_the_hosts(name, dtype, rule):
 @pytest.mark.parametrize('name,kind', [('olf_R5', 'frames'), ('ragged', 'table')])
 def test_device_rollout_against_an_environment_equals_the_hosts(name, kind, dtype, rule):
     check_rollout(name, dtype, rule, kind)
+
+
+_SEAM_ROLLOUTS = {}
+
+
+def seam_rollout_case(R, rows_down=0):
+    """The 75 x 440 olfactory grid (S = 33000: two chunk groups, one ragged chunk in the second), 40 simulations started in
+    ``synth.belief_points`` beliefs, 6 steps.  The start box of the model ends at grid row 54 and the second group begins in
+    row 74, so those beliefs keep their mass in the first group; ``rows_down`` moves them down the (wrap-around) grid."""
+    if (R, rows_down) not in _SEAM_ROLLOUTS:
+        sm = synth.olfactory_model(H=75, W=440, R=R)
+        b0 = np.roll(synth.belief_points(sm, 40), rows_down * sm.W, axis=1)
+        rng = np.random.default_rng(440 + R)
+        s0 = np.array([rng.choice(sm.S, p=row / row.sum()) for row in b0])
+        _SEAM_ROLLOUTS[R, rows_down] = SimpleNamespace(m=pomdp_mod._rollout_tables(sm), alpha=np.zeros((1, sm.S)), b0=b0, s0=s0,
+                                                       name=f'olf75x440_R{R}+{rows_down}', sa=spc.action_table(sm.S, sm.A), T=6, cut=17)
+    return _SEAM_ROLLOUTS[R, rows_down]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('rule', [0, 1, 2])
+@pytest.mark.parametrize('dtype', ['f64', 'f32'])
+@pytest.mark.parametrize('R,rows_down', [(1, 0), (5, 0), (5, 37)])
+def test_rollout_past_one_chunk_group(R, rows_down, dtype, rule):
+    """``check_rollout`` with two chunk groups under every step's policy call.  Moved 37 rows down, the goal's row is the
+    grid's last one: every start belief then holds 0.9 to 3 % of its mass behind the seam (the second group is 0.7 % of the
+    states), which is part of every vote and every Thompson prefix, and some Thompson draws land there."""
+    c = seam_rollout_case(R, rows_down)
+    assert c.m.state_count == 33000 and c.b0.shape[0] == 40
+    assert rows_down == 0 or np.all(c.b0[:, spc.GROUP:].sum(axis=1) > 0.005)
+    check_rollout(c, dtype, rule)
 
 
 @pytest.mark.gpu
